@@ -9,7 +9,14 @@ buffer.sample(0) -> process_fn (V(obs), V(obs_next), float64 GAE x2, logp_old) -
 weights.  KL early stop is disabled for throughput (target_kl = inf), like BASELINE.md says.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else after the
+timed steps: the roofline leg, the CPU / stock-PyTorch baselines, the other BASELINE configurations and variants, the
+end-to-end training loops (and at N > 1 every rank's loop and the library's own RCCL exchange).
+--dump-outputs DIR writes what the last timed update returned to its caller (DIR/stats.npy: the per-optimiser-step
+statistics; DIR/params.npy: the updated flat parameters), from rank 0, before any --full leg runs.
 
 N > 1: one independent agent (seed = rank) per GPU, no data-path collective ("weak" scaling);
 RCCL is used only for the barrier and the max-over-ranks time.
@@ -67,10 +74,17 @@ def orthogonal_theta(seed, n_params_check=None, hid=None):
         torch.nn.init.orthogonal_(w)
         return [w.reshape(-1), torch.zeros(o)]
 
-    parts.append(torch.full((ACT, ), -0.5))
-    parts += lin(HID, OBS) + lin(HID, HID) + lin(ACT, HID)
-    for _ in range(2):
-        parts += lin(HID, OBS) + lin(HID, HID) + lin(1, HID)
+    # the QR's rounding depends on the intra-op thread count (the agents set 4, the environment may say 16): one thread, so the
+    # weights -- and everything the bench computes from them -- depend on the seed alone
+    n_threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        parts.append(torch.full((ACT, ), -0.5))
+        parts += lin(HID, OBS) + lin(HID, HID) + lin(ACT, HID)
+        for _ in range(2):
+            parts += lin(HID, OBS) + lin(HID, HID) + lin(1, HID)
+    finally:
+        torch.set_num_threads(n_threads)
     theta = torch.cat(parts).numpy()
     assert n_params_check is None or theta.size == n_params_check
     return theta
@@ -684,12 +698,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline, baselines, other configurations, end-to-end loops (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed update's outputs (stats, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip every secondary leg (profiling runs)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: the roofline leg only, no secondary leg (profiling runs)")
     # test hooks (tests/test_gpu_facade.py): run the N > 1 code path on a one-GPU box -- every rank on device 0, gloo
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--share-gpu", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -776,6 +796,12 @@ def main():
     dt = time.perf_counter() - t0
     grad_steps = stats.shape[0]
     assert np.isfinite(stats).all()
+    if args.dump_outputs and rank == 0:
+        # what the last timed update handed its caller: the statistics it returned and the parameters it left on the device
+        # (inputs, weights and update seeds are fixed by the arguments, so two builds can be compared array for array)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "stats.npy"), np.ascontiguousarray(stats, np.float32))
+        np.save(os.path.join(args.dump_outputs, "params.npy"), eng.get_params().astype(np.float32))
     per_rank, dt_local = None, dt
     if dist is not None:
         # the contract's max-over-ranks time, and the SURVEY 8(e) exchange: every rank's figures gathered once
@@ -874,9 +900,10 @@ def main():
                         "exceeds the un-instrumented ms_per_step; only process_fn is used (step_us above)"}
         return r
 
-    legs.run("roofline", roofline_leg, 60.0)
+    if args.full:
+        legs.run("roofline", roofline_leg, 60.0)
 
-    if dist is not None and not args.headline_only:
+    if dist is not None and args.full and not args.headline_only:
         from fsrl_amd import parallel
         # ---- the other half of the headline metric at N > 1: every rank's whole training loop (host collector -> HIP store
         #      -> update) side by side for a few seconds on its own slice of the host cores; job env-steps/s = sum over ranks.
@@ -924,7 +951,7 @@ def main():
                 return res
             legs.run("lib_metrics_allreduce", lib_comm_leg, 30.0)
 
-    if rank == 0 and world == 1 and not args.headline_only:       # rank 0 at N = 1 only
+    if rank == 0 and world == 1 and args.full and not args.headline_only:       # rank 0 at N = 1 only
         if not args.no_cpu_baseline:
             legs.run("cpu_baseline", lambda: cpu_baseline(theta, inputs), 90.0)
             if isinstance(out.get("cpu_baseline"), dict) and "value" in out["cpu_baseline"]:

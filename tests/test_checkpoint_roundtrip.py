@@ -4,16 +4,11 @@ tests/golden/hip_ckpt_{ppo,sac}.pt were TRAINED ON AN MI355X through the engine 
 (tools/make_hip_checkpoint.py); tests/golden/hip_ckpt_ref_forward.npz holds what the UNMODIFIED reference policies return
 after load_state_dict(strict=True) of those files (tests/golden/gen_ckpt_roundtrip.py, build container).
 
-  * always: the host mirror (fsrl_amd.utils.net modules, no engine) loaded from the checkpoint gives the reference's
-    outputs (<= 2e-6) and the outputs the DEVICE actor produced when the checkpoint was written (<= 1e-6);
-  * where /root/reference exists (the build container): the reference-side load + forward is re-run live and must equal
-    the committed fixture bit for bit."""
+The host mirror (fsrl_amd.utils.net modules, no engine) loaded from the checkpoint gives the reference's outputs
+(<= 2e-6) and the outputs the DEVICE actor produced when the checkpoint was written (<= 1e-6)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 import torch
 
 from helpers import GOLDEN, load_npz
@@ -82,16 +77,3 @@ def test_sac_checkpoint_host_mirror_equals_reference_forward():
         flat = np.concatenate([ck["model"][k].numpy().reshape(-1) for k in ck["model"] if k.startswith(pre)])
         assert np.array_equal(flat, ck[key]), key
     assert not np.array_equal(ck["flat_critics"], ck["flat_critics_old"]) and ck["gradient_steps"] > 0
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/fsrl"), reason="the reference tree exists in the build container only")
-def test_unmodified_reference_loads_the_hip_checkpoints_live(tmp_path):
-    out = str(tmp_path / "live.npz")
-    r = subprocess.run([sys.executable, os.path.join(GOLDEN, "gen_ckpt_roundtrip.py"), out], capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert r.stdout.count("strict load ok <All keys matched successfully>") == 2
-    live, ref = dict(np.load(out)), load_npz("hip_ckpt_ref_forward.npz")
-    assert set(live) == set(ref)
-    for k in ref:
-        assert np.array_equal(live[k], ref[k]), k

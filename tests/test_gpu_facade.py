@@ -337,6 +337,57 @@ def test_fused_collect_step_equals_actor_sample_plus_push(tmp_path):
         assert sum(s["n/ep"] for s in st_a) == 19
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_update(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone, and --dump-outputs writes what the LAST timed update
+    returned: its stats and the parameters it left.  The same update count split otherwise between warm-up and timed steps
+    dumps the same bits, and the same sequence of updates run here ends in them too."""
+    import json, os, subprocess, sys
+    import bench
+    from fsrl_amd.engine import Engine, EngineConfig
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(steps, warmup, dump):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+               "--dump-outputs", str(dump)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+    steps, warmup, dump = 3, 1, tmp_path / "out"
+    d = run(steps, warmup, dump)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "updates/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["metric"].startswith("policy-updates/sec")
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "torch_rocm_baseline", "kl_on", "end_to_end", "grouped", "layered"):
+        assert key not in d, key                                                        # secondary legs: --full only
+    stats, params = np.load(dump / "stats.npy"), np.load(dump / "params.npy")
+    assert stats.dtype == np.float32 and params.dtype == np.float32
+    assert stats.shape == (d["grad_steps_per_update"], 11) and np.isfinite(stats).all() and np.isfinite(params).all()
+    run(2, 2, tmp_path / "split")                                                       # the 4th update either way
+    for name, arr in (("stats", stats), ("params", params)):
+        assert np.array_equal(np.load(tmp_path / "split" / f"{name}.npy"), arr), name
+    # the bench's sequence again in a fresh context: every update starts from the restored initial state, update k takes
+    # seed k + 1, and the library's shuffle stream runs on across updates -- so the last one is only reproduced in order
+    eng = Engine(EngineConfig(obs_dim=bench.OBS, act_dim=bench.ACT, hidden=bench.HID, env_num=bench.ENVS, buffer_size=100000,
+                              max_grad_norm=0.5, target_kl=None), device=0)
+    theta = bench.orthogonal_theta(0, eng.n_params)
+    eng.set_params(theta)
+    obs, act, rew, cost, term, trunc = bench.make_inputs(0)
+    ids = np.arange(bench.ENVS)
+    for t in range(bench.NROWS // bench.ENVS):
+        eng.push(ids, obs[t], act[t], rew[t], cost[t], term[t], trunc[t], obs[t + 1])
+    eng.optim_reset(); eng.state_snapshot()
+    for k in range(warmup + steps):
+        eng.state_restore()
+        want, _ = eng.ppo_update(np.array([0.75]), 1.0 / 1.75, bench.BATCH, bench.REPEAT, perms=None, seed=k + 1)
+    want_params = eng.get_params()
+    eng.close()
+    assert params.shape == theta.shape and not np.array_equal(params, theta.astype(np.float32))
+    np.testing.assert_allclose(stats, want, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(params, want_params, rtol=0, atol=1e-6)
+
+
 def test_bench_multi_rank_path_on_one_gpu():
     """bench.py's N > 1 path (one process per rank, barrier + max-over-ranks timing, rank 0 prints the one JSON line
     with the whole-job value) run as two ranks sharing this box's GPU over gloo: the launch line is the driver's."""
@@ -345,7 +396,7 @@ def test_bench_multi_rank_path_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--share-gpu"]
+           "--backend", "gloo", "--share-gpu", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -391,7 +442,8 @@ def test_bench_eight_ranks_dry_run_on_one_gpu(backend):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", FSRL_BENCH_LEG_BUDGET_S="150")
     port = {"gloo": "29551", "nccl": "29553"}[backend]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--share-gpu"]
+           "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--share-gpu",
+           "--full"]
     if backend == "gloo":
         cmd += ["--backend", "gloo"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
@@ -422,7 +474,7 @@ def test_bench_headline_survives_a_failing_leg():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", FSRL_BENCH_FAIL_LEG="end_to_end_rank,grouped")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29543", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--share-gpu"]
+           "--backend", "gloo", "--share-gpu", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
