@@ -9,9 +9,11 @@ the seeds overlap; the Python collector loops take turns.
     python examples/train_multi_seed.py --algo ppol --seeds 3 --epoch 2
     python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag only
 
---grouped: ONE thread; the seeds collect one after the other and their updates run in lock step through the grouped
+--grouped: ONE thread; the seeds collect in lock step (fsrl_amd.data.GroupCollector -> fsrl_group_collect_step: one actor
+request per vector step for all seeds, served by one resident kernel) and their updates run in lock step through the grouped
 launches (fsrl_amd.policy.PolicyGroup -> fsrl_group_ppo_update: every launch of the minibatch step carries all seeds):
-~2x the aggregate updates/s of the thread-per-seed mode at 4 seeds (tools/bench_group.py).
+~2x the aggregate updates/s of the thread-per-seed mode at 4 seeds (tools/bench_group.py); collection: tools/bench_group_collect.py.
+Per seed the run is the one of collecting the seeds one after the other, bit for bit.
 """
 import argparse
 import os
@@ -30,9 +32,9 @@ AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops":
 
 
 def run_grouped(a):
-    """k PPO-Lag seeds, one host thread: collect each seed's episodes, step each PID multiplier, ONE grouped update."""
+    """k PPO-Lag seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier, ONE grouped update."""
     assert a.algo == "ppol", "--grouped: PPO-Lagrangian"
-    from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
     from fsrl_amd.policy import PolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
@@ -45,12 +47,12 @@ def run_grouped(a):
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
     group = PolicyGroup([ag.policy for ag in agents])
+    gcol = GroupCollector(group, cols)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
         while budget > 0:
-            for ag, col in zip(agents, cols):
-                st = col.collect(n_episode=a.envs)
+            for ag, st in zip(agents, gcol.collect(n_episode=a.envs)):
                 ag.policy.pre_update_fn(stats_train=st)
                 ag.logger.store(**{"train/reward": st["rew"], "train/cost": st["cost"]})
                 steps += st["n/st"]

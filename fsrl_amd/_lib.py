@@ -110,6 +110,11 @@ SIGNATURES = {
     "fsrl_group_set_plan": (C.c_int, [_ctx, C.c_int32]),
     "fsrl_group_ppo_update": (C.c_int, [_ctx, _d, _d, C.c_int32, C.c_int32, _P(_i64), C.c_uint64, _P(_f), C.c_int64, _i64,
                                         _i32]),
+    "fsrl_group_collect_step": (C.c_int, [_ctx, _i32, _i32, _f, _f, _d, _d, _u8, _u8, _f, _i64, _d, _i32, _i64, _i32, _f, C.c_int32,
+                                          C.c_int32, _f, _f, _f, _f]),
+    "fsrl_group_actor_set_resident": (C.c_int, [_ctx, C.c_int32, C.c_double]),
+    "fsrl_group_actor_resident_stats": (C.c_int, [_ctx, _i64]),
+    "fsrl_group_actor_release": (C.c_int, [_ctx]),
     "fsrl_gae_return": (C.c_int, [_ctx, _f, _f, _d, _u8, C.c_int64, C.c_double, C.c_double, _d]),
     "fsrl_nstep_return": (C.c_int, [_ctx, _d, _u8, C.c_int64, _f, _i64, C.c_int64, C.c_int64, C.c_double, C.c_int32, _d]),
     "fsrl_launch_floors": (C.c_int, [_ctx, C.c_int32, C.c_int32, _d]),

@@ -233,6 +233,7 @@ static int flush_stage(fsrl_ctx* c);
 // then behind a kernel that is on its way out, and the next actor call launches a new one BEHIND that work -- stream order as with
 // one launch per call.  The actor / collector entry points themselves keep it (plain hipSetDevice).
 static void pactor_release(fsrl_ctx* c);
+static void group_actor_release(fsrl_group* g);     // the group's resident actor (host_group_collect.inc): a member's stream is the group's
 #define ENTER_DEV(c) do { HIPCHK(hipSetDevice((c)->device)); pactor_release(c); } while (0)
 
 static int join_store(fsrl_ctx* c) {
@@ -976,6 +977,7 @@ static bool pactor_ok(const fsrl_ctx* c, int k) {
 }
 
 static void pactor_release(fsrl_ctx* c) {
+    if (c->group) group_actor_release(c->group);      // a grouped member enqueues on the group's stream: its collect kernel ends too
     if (!c->pa_live) return;
     const PaLayout l = pa_layout(c);
     c->pa_seq += 1;
@@ -1186,12 +1188,8 @@ static uint64_t xoshiro_next(uint64_t* s) {
 //   SAC contexts:              a = tanh(mu + sigma(s) * eps)             (sac_lag.py:155-183)
 // deterministic != 0 returns the mean (tanh(mean) for SAC).  Noise is NOT torch's stream: callers that
 // need the reference's random numbers keep the host mirror of the actor (fsrl_amd/policy).
-// second half of fsrl_actor_sample / fsrl_collect_step: wait for the actor, then a = mean (+ std * N(0,1))
-static int actor_sample_finish(fsrl_ctx* c, int32_t deterministic, float* act_out) {
-    const int Da = c->cfg.act_dim, k = c->actor_k;
-    c->act_mu.resize((size_t)k * Da); c->act_sg.resize((size_t)k * Da);
-    int rc = actor_eval_finish(c, c->act_mu.data(), c->act_sg.data());
-    if (rc) return rc;
+// a = mean (+ std * N(0,1)) from c->act_mu / c->act_sg (the actor's answer for c->actor_k rows)
+static void actor_draw(fsrl_ctx* c, int32_t deterministic, float* act_out) {
     const bool squash = ctx_is_replay(c) && sac_squashes(c);
     for (size_t i = 0; i < c->act_mu.size(); ++i) {
         float u = c->act_mu[i];
@@ -1204,7 +1202,29 @@ static int actor_sample_finish(fsrl_ctx* c, int32_t deterministic, float* act_ou
         }
         act_out[i] = squash ? std::tanh(u) : u;     // DDPG-Lag / CVPO: mu is already max_action * tanh
     }
+}
+
+// second half of fsrl_actor_sample / fsrl_collect_step: wait for the actor, then a = mean (+ std * N(0,1))
+static int actor_sample_finish(fsrl_ctx* c, int32_t deterministic, float* act_out) {
+    const int Da = c->cfg.act_dim, k = c->actor_k;
+    c->act_mu.resize((size_t)k * Da); c->act_sg.resize((size_t)k * Da);
+    int rc = actor_eval_finish(c, c->act_mu.data(), c->act_sg.data());
+    if (rc) return rc;
+    actor_draw(c, deterministic, act_out);
     return 0;
+}
+
+// BasePolicy.map_action (base_policy.py:226-256) of k_act policy actions into the env's range
+static void map_env_action(int Da, int k_act, int32_t bound_method, const float* act_low, const float* act_high, const float* act_out,
+                           float* env_act_out) {
+    for (int r = 0; r < k_act; ++r)
+        for (int d = 0; d < Da; ++d) {
+            float a = act_out[(size_t)r * Da + d];
+            if (bound_method == 1) a = std::min(std::max(a, -1.0f), 1.0f);
+            else if (bound_method == 2) a = std::tanh(a);
+            if (act_low) a = act_low[d] + (act_high[d] - act_low[d]) * (a + 1.0f) / 2.0f;
+            env_act_out[(size_t)r * Da + d] = a;
+        }
 }
 
 extern "C" int fsrl_actor_sample(fsrl_ctx* c, const float* obs, int32_t k, int32_t deterministic, uint64_t seed,
@@ -1249,17 +1269,7 @@ extern "C" int fsrl_collect_step(fsrl_ctx* c, const int32_t* env_ids, int32_t k,
     if (k_act == 0) return 0;
     rc = actor_sample_finish(c, deterministic, act_out);
     if (rc) return rc;
-    if (env_act_out) {
-        const int Da = c->cfg.act_dim;
-        for (int r = 0; r < k_act; ++r)
-            for (int d = 0; d < Da; ++d) {
-                float a = act_out[(size_t)r * Da + d];
-                if (bound_method == 1) a = std::min(std::max(a, -1.0f), 1.0f);
-                else if (bound_method == 2) a = std::tanh(a);
-                if (act_low) a = act_low[d] + (act_high[d] - act_low[d]) * (a + 1.0f) / 2.0f;
-                env_act_out[(size_t)r * Da + d] = a;
-            }
-    }
+    if (env_act_out) map_env_action(c->cfg.act_dim, k_act, bound_method, act_low, act_high, act_out, env_act_out);
     return 0;
 }
 
@@ -1357,6 +1367,7 @@ extern "C" int fsrl_nstep_return(fsrl_ctx* c, const double* metric, const uint8_
 #include "host_layered.inc"
 
 #include "host_group.inc"
+#include "host_group_collect.inc"
 
 // abandon an update that began with fsrl_ppo_begin and cannot reach fsrl_ppo_end (an exception between the calls on the
 // caller's side): drain the stream, clear the state machine.  No-op outside an update.

@@ -17,6 +17,16 @@ struct fsrl_group {
     hipEvent_t steps_copied = nullptr; bool steps_in_flight = false;
     bool broken = false;                        // a member was destroyed: no more updates
     int tall_tiles = -1;                        // fsrl_group_set_plan: 32-row tiles per (member, network) of the forward / backward launch
+    // lock-step collection (host_group_collect.inc): ONE resident actor kernel for every member, rung through ONE doorbell
+    bool ga_on = true;                          // fsrl_group_actor_set_resident
+    bool ga_live = false;                       // a kernel of generation ga_gen was launched and not told to end
+    unsigned ga_gen = 0, ga_seq = 0; double ga_idle_us = 2000.0;
+    int ga_blocks = 0;                          // workgroups of every launch: sum of ga_tiles
+    int ga_do = 0, ga_da = 0;                   // observation / action width of the ring (the members' shape)
+    int ga_base[FSRL_MAX_GROUP] = {}, ga_tiles[FSRL_MAX_GROUP] = {};   // member m: workgroups ga_base[m] .. + ga_tiles[m] - 1
+    int ga_k[FSRL_MAX_GROUP] = {};              // rows of each member in the request in flight
+    void* h_ga = nullptr;                       // pinned ring (GaLayout)
+    long long ga_launches = 0, ga_requests = 0; // fsrl_group_actor_resident_stats
 };
 
 extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
@@ -75,6 +85,7 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
 static void group_detach(fsrl_ctx* c) {
     fsrl_group* g = c->group;
     if (!g) return;
+    group_actor_release(g);
     (void)hipStreamSynchronize(g->stream);
     for (size_t i = 0; i < g->m.size(); ++i) {
         fsrl_ctx* m = g->m[i];
@@ -89,6 +100,7 @@ static void group_detach(fsrl_ctx* c) {
 extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (!g) return 0;
     for (fsrl_ctx* c : g->m) if (c) { (void)hipSetDevice(c->device); break; }
+    group_actor_release(g);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (size_t i = 0; i < g->m.size(); ++i)
         if (g->m[i]) { g->m[i]->compute = g->own_stream[i]; g->m[i]->group = nullptr; }
@@ -98,6 +110,7 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (g->d_steps) (void)hipFree(g->d_steps);
     if (g->h_steps) (void)hipHostFree(g->h_steps);
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
+    if (g->h_ga) (void)hipHostFree(g->h_ga);
     delete g;
     return 0;
 }
@@ -133,6 +146,7 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
     CHECK_ARG(g && rescaling, "null argument");
     CHECK_ARG(repeat >= 0, "repeat must be >= 0");
     if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
+    group_actor_release(g);                     // the update goes behind the collect kernel, which ends
     const int k = (int)g->m.size();
     fsrl_ctx* c0 = g->m[0];
     for (fsrl_ctx* m : g->m) m->theta_version += 1;

@@ -578,6 +578,102 @@ __global__ __launch_bounds__(4 * H) void actor_resident_kernel(const float* __re
     if (tid == 0) __hip_atomic_store(a.state + blk, a.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---------------------------------------------------------------- the resident actor of a whole group (lock-step collection)
+// actor_resident_kernel<H, false> serving every member of an fsrl_group from ONE launch and ONE doorbell: a workgroup per
+// (member, 16-row tile), at most PACTOR_BLOCKS tiles per member.  Workgroup b owns rows 16 b .. 16 b + 15 of the pinned observation
+// and output areas (a member's rows start on a tile boundary), its member m = wg_member[b] and tile t = wg_tile[b] come from the
+// kernel arguments (block-uniform), and it runs member m's parameters P[m] over rows 16 t .. of member m's request: k_m[m] rows,
+// written by the host before the doorbell.  A member with no rows in a request is skipped by its workgroups.  Same staging, same
+// tile_forward, same head as the single-context kernels: every member's actions are bit-identical to its own actor's.
+#define GACTOR_MAX_MEMBERS 16
+#define GACTOR_MAX_WG (GACTOR_MAX_MEMBERS * PACTOR_BLOCKS)
+struct GActorArgs {
+    const float* P[GACTOR_MAX_MEMBERS];   // each member's parameter vector (one network shape: one ModelDesc)
+    const float* obs;                     // pinned [GACTOR_MAX_WG * 16 rows][Do]
+    float* mu_out;                        // pinned [GACTOR_MAX_WG * 16 rows][Da]
+    float* sigma_param_out;               // pinned [GACTOR_MAX_MEMBERS][FSRL_MAX_ACT]
+    const unsigned long long* bell;       // pinned: (1 << 32 | seq) for a request, (EXIT << 32 | seq) to end
+    const unsigned* k_m;                  // pinned [GACTOR_MAX_MEMBERS]: rows of each member in the request the doorbell announces
+    unsigned* done;                       // pinned [GACTOR_MAX_WG]: seq of the last request workgroup b served
+    unsigned* state;                      // pinned [GACTOR_MAX_WG]: generation of the last kernel whose workgroup b ended
+    unsigned gen, last_seq;
+    unsigned long long timeout_ticks;
+    float max_action;
+    unsigned char wg_member[GACTOR_MAX_WG], wg_tile[GACTOR_MAX_WG];
+};
+
+template <int H>
+__global__ __launch_bounds__(4 * H) void actor_group_resident_kernel(const ModelDesc md, const GActorArgs a) {
+    __shared__ TileSmem<H> sm;
+    __shared__ unsigned k_s, seq_s;
+    __shared__ unsigned last_s;
+    constexpr int NT = TileGeom<H>::NT;
+    constexpr int NX = TileStage<H>::NX;
+    const int tid = threadIdx.x, blk = blockIdx.x;
+    const int mem = a.wg_member[blk], tile = a.wg_tile[blk];      // block-uniform
+    const float* __restrict__ P = a.P[mem];
+    const NetOff no = md.net[0];
+    const int Do = md.Do;
+    const unsigned magic = div_magic(Do);
+    TileStage<H> stg;
+    stg.issue(P, no, Do, md.Da, P, nullptr, 0, tid);              // the member's small parameters; no rows yet
+    FwdW2Frag<H> wf;
+    wf.load(P + no.W2f, tid >> 6, tid & 63);
+    stg.commit(sm, no, Do, tid);
+    if (tid == 0) last_s = a.last_seq;
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long t0 = wall_clock64();
+            const unsigned last = last_s;
+            unsigned long long v;
+            unsigned polls = 0;
+            for (;;) {
+                v = __hip_atomic_load(a.bell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if ((unsigned)v != last) break;
+                if (wall_clock64() - t0 > a.timeout_ticks || ++polls > (1u << 26)) { v = (unsigned long long)PACTOR_EXIT << 32; break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);             // system scope: k_m and the observations were written before the doorbell
+            const unsigned cmd = (unsigned)(v >> 32);
+            k_s = cmd == PACTOR_EXIT ? PACTOR_EXIT : __hip_atomic_load(a.k_m + mem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            seq_s = (unsigned)v;
+            last_s = (unsigned)v;
+        }
+        __syncthreads();
+        const unsigned k = k_s;
+        if (k == PACTOR_EXIT) break;
+        const int n_valid = min(16, (int)k - tile * 16);
+        if (n_valid <= 0) continue;                              // no rows of this request for this workgroup (block-uniform)
+        const float* xrow = a.obs + blk * 16 * Do;               // block-uniform (scalar registers)
+#pragma unroll
+        for (int u = 0; u < NX; ++u) {
+            const int e = tid + u * NT;
+            if (e < 16 * Do) {
+                const float x = (e < n_valid * Do)
+                    ? __hip_atomic_load(xrow + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0.0f;
+                const int i = div_by_magic((unsigned)e, magic), kk = e - i * Do;
+                sm.xT[kk * 16 + i] = x;
+            }
+        }
+        __syncthreads();
+        tile_forward<H>(sm, P, no, Do, tid, wf);
+        if (tile == 0 && tid < md.Da && no.sigma >= 0) a.sigma_param_out[mem * FSRL_MAX_ACT + tid] = sm.sig[tid];
+        if (tid < n_valid) {
+            const int r = blk * 16 + tid;
+            for (int d = 0; d < md.Da; ++d) {
+                const float x = sm.out[tid * FSRL_MAX_ACT + d];
+                a.mu_out[r * md.Da + d] = md.unbounded ? x : a.max_action * tanhf(x);
+            }
+        }
+        // rows by threads 0 .. 15, sigma_param by threads below Da: only wave 0 stored to pinned memory and fences (r6)
+        if (tid < 64) __atomic_thread_fence(__ATOMIC_RELEASE);
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(a.done + blk, seq_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (tid == 0) __hip_atomic_store(a.state + blk, a.gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---------------------------------------------------------------- fused fwd + loss + bwd
 // One PPO minibatch step, activation side.  1-D grid of 8*slots blocks mapped to
 // (network, 16-row tile) by xcd_assign(); block = 4*H threads.

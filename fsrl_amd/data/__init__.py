@@ -1,8 +1,9 @@
-"""Host-side data plumbing: a minimal Batch, the proxy of the HIP-resident store, the collector."""
+"""Host-side data plumbing: a minimal Batch, the proxy of the HIP-resident store, the collectors."""
 from fsrl_amd._lazy import install
 
 install(__name__, globals(), {
     "Batch": "batch",
     "HipVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
+    "GroupCollector": "group_collector",
 })

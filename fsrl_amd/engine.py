@@ -721,6 +721,7 @@ class EngineGroup:
         k = len(self.engines)
         arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
         self._g = C.c_void_p()
+        self._collect_stage = None      # cached staging arrays + ctypes pointers of collect_step
         _lib.check(self.lib.fsrl_group_create(arr, k, C.byref(self._g)))
 
     def close(self):
@@ -733,6 +734,78 @@ class EngineGroup:
             self.close()
         except Exception:
             pass
+
+    def collect_step(self, prevs, obs_acts, deterministic=False, bound_method=1, low=None, high=None):
+        """Engine.collect_step on every member in ONE call with ONE actor request (fsrl_group_collect_step).  prevs / obs_acts: per
+        member what Engine.collect_step takes (None allowed); low / high: None, one array for every member or a per-member list.
+        -> per member (act, env_act, ep_rew, ep_len), as Engine.collect_step.  Staging arrays / ctypes pointers are cached."""
+        engs = self.engines
+        n = len(engs)
+        Do, Da = engs[0].cfg.obs_dim, engs[0].cfg.act_dim
+        st = self._collect_stage
+        if st is None:
+            cap = sum(e.cfg.env_num for e in engs)
+            arr = dict(ids=np.empty(cap, np.int32), obs=np.empty((cap, Do), np.float32), act=np.empty((cap, Da), np.float32),
+                       rew=np.empty(cap, np.float64), cost=np.empty(cap, np.float64), term=np.empty(cap, np.uint8),
+                       trunc=np.empty(cap, np.uint8), nxt=np.empty((cap, Do), np.float32), ptr=np.empty(cap, np.int64),
+                       er=np.empty(cap, np.float64), el=np.empty(cap, np.int32), ei=np.empty(cap, np.int64),
+                       oa=np.empty((cap, Do), np.float32), ao=np.empty((cap, Da), np.float32), eo=np.empty((cap, Da), np.float32),
+                       lo=np.empty((n, Da), np.float32), hi=np.empty((n, Da), np.float32), k=np.empty(n, np.int32),
+                       ka=np.empty(n, np.int32))
+            types = dict(ids=_i32p, obs=_f32p, act=_f32p, rew=_f64p, cost=_f64p, term=_u8p, trunc=_u8p, nxt=_f32p, ptr=_i64p,
+                         er=_f64p, el=_i32p, ei=_i64p, oa=_f32p, ao=_f32p, eo=_f32p, lo=_f32p, hi=_f32p, k=_i32p, ka=_i32p)
+            st = self._collect_stage = dict(a=arr, p={m: _ptr(arr[m], types[m]) for m in arr})
+        a, p = st["a"], st["p"]
+        ks, kas = a["k"], a["ka"]
+        o = 0
+        for i, prev in enumerate(prevs):
+            k = 0
+            if prev is not None:
+                ids, obs, act, rew, cost, term, trunc, nxt = prev
+                k = len(ids)
+                a["ids"][o:o + k] = ids; a["obs"][o:o + k] = obs; a["act"][o:o + k] = act; a["rew"][o:o + k] = rew
+                a["cost"][o:o + k] = cost; a["term"][o:o + k] = term; a["trunc"][o:o + k] = trunc; a["nxt"][o:o + k] = nxt
+            ks[i] = k
+            o += k
+        o = 0
+        for i, oa in enumerate(obs_acts):
+            ka = 0 if oa is None else len(oa)
+            if ka:
+                a["oa"][o:o + ka] = oa
+            kas[i] = ka
+            o += ka
+        if low is not None:
+            a["lo"][:] = np.asarray(low, np.float32).reshape(-1, Da); a["hi"][:] = np.asarray(high, np.float32).reshape(-1, Da)
+        _lib.check(self.lib.fsrl_group_collect_step(
+            self._g, p["k"], p["ids"], p["obs"], p["act"], p["rew"], p["cost"], p["term"], p["trunc"], p["nxt"], p["ptr"],
+            p["er"], p["el"], p["ei"], p["ka"], p["oa"], int(deterministic), int(bound_method),
+            p["lo"] if low is not None else None, p["hi"] if low is not None else None, p["ao"], p["eo"]))
+        out, o, oa_ = [], 0, 0
+        for i in range(n):
+            k, ka = int(ks[i]), int(kas[i])
+            out.append((a["ao"][oa_:oa_ + ka].copy(), a["eo"][oa_:oa_ + ka].copy(), a["er"][o:o + k], a["el"][o:o + k]))
+            o += k; oa_ += ka
+        return out
+
+    def collect_step_outputs(self):
+        """(ptr, ep_idx) of the rows the last collect_step stored, concatenated over members (views of the staging arrays)."""
+        a = self._collect_stage["a"]
+        k = int(a["k"].sum())
+        return a["ptr"][:k], a["ei"][:k]
+
+    def actor_set_resident(self, on=True, idle_timeout_us=0.0):
+        """The group's resident collect kernel (include/fsrl_hip.h: fsrl_group_actor_set_resident); on by default."""
+        _lib.check(self.lib.fsrl_group_actor_set_resident(self._g, int(bool(on)), float(idle_timeout_us)))
+
+    def actor_release(self):
+        """End the group's resident collect kernel now (a grouped collect is over)."""
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_group_actor_release(self._g)
+
+    def actor_resident_stats(self):
+        out = np.zeros(3, np.int64)
+        _lib.check(self.lib.fsrl_group_actor_resident_stats(self._g, _ptr(out, _i64p)))
+        return dict(launches=int(out[0]), requests=int(out[1]), live=bool(out[2]))
 
     def set_plan(self, tall_tiles=-1):
         """32-row tiles per (member, network) in the forward / backward launch: -1 automatic, 0 none, n > 0 a count (A/B; same bits)."""

@@ -304,6 +304,27 @@ int fsrl_group_set_plan(fsrl_group* group, int32_t tall_tiles);
 int fsrl_group_ppo_update(fsrl_group* group, const double* lagrangians, const double* rescaling, int32_t batch_size,
                           int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
                           int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
+/* Lock-step collection: fsrl_collect_step on every member, member order, in ONE call with ONE actor request for all of them --
+ * same stored rows and slots, same actions, same library-RNG consumption per member, bit for bit.  Row arrays are concatenated
+ * over members: k[m] transitions to store (env_ids / obs / act / rew / cost / terminated / truncated / obs_next and the
+ * ptr / ep_* outputs) and k_act[m] observations to act on (obs_act, act_out, env_act_out) for member m; 0 is allowed.
+ * act_low / act_high: NULL or [k_members][act_dim], member m's action bounds.  The request goes to ONE resident actor kernel for
+ * the group (a workgroup per member and 16-row tile, on the group's stream); it ends before the group's stream gets other work
+ * (fsrl_group_ppo_update, a member's own library calls, fsrl_group_destroy), on fsrl_group_actor_release and after its idle
+ * timeout.  Off the resident path (fsrl_group_actor_set_resident(0), a member asking for more rows than its 16 * min(4,
+ * ceil(env_num / 16)) tiles): one actor launch per member inside the same call, the same bits.                          */
+int fsrl_group_collect_step(fsrl_group* group, const int32_t* k, const int32_t* env_ids, const float* obs, const float* act,
+                            const double* rew, const double* cost, const uint8_t* terminated, const uint8_t* truncated,
+                            const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out,
+                            int64_t* ep_idx_out, const int32_t* k_act, const float* obs_act, int32_t deterministic,
+                            int32_t bound_method, const float* act_low, const float* act_high, float* act_out,
+                            float* env_act_out);
+/* the group's resident collect kernel: on (default) / off, idle timeout (default 2000 us; <= 0 keeps the value) */
+int fsrl_group_actor_set_resident(fsrl_group* group, int32_t on, double idle_timeout_us);
+/* out3 = {group kernels launched, grouped actor requests served through the doorbell, 1 if the group kernel is live}      */
+int fsrl_group_actor_resident_stats(fsrl_group* group, int64_t* out3);
+/* end the group's resident kernel now (a grouped collect is over); a no-op when none is live                               */
+int fsrl_group_actor_release(fsrl_group* group);
 
 /* read back process_fn products of the current batch: which = "values" | "rets" | "advs"
  * ([n][n_critics] float32, like torch.stack(.., -1)) | "logp_old" ([n]).                 */

@@ -1,0 +1,138 @@
+#!/usr/bin/env python
+"""Lock-step collection of a PPO-Lagrangian group (GroupCollector -> fsrl_group_collect_step) against collecting the seeds one after
+the other.  k members of 256 x 256, 20 in-process SyntheticSafetyVectorEnv envs each (obs 8, act 2, episodes of 300 steps, one seed per
+member).  For every k, in one process and alternating `--rounds` times, aggregate env-steps/s of:
+  seq_ungrouped  k ungrouped engines, each FastCollector.collect in turn with its own resident actor (the fair baseline);
+  seq_grouped    the members of a group, each FastCollector.collect in turn (what examples/train_multi_seed.py --grouped did: a grouped
+                 member has no resident actor, one launch per vector step);
+  lockstep       GroupCollector.collect on the same group.
+Also: us per grouped actor call at k x 20 rows against one member's 20-row resident call, resident launches per lock-step collect, and
+a collect + grouped update loop (aggregate env-steps/s and updates/s).  Prints ONE JSON line.
+
+    python tools/bench_group_collect.py [--ks 1,2,4,8] [--rounds 3]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _agents(k, envs, first_seed, device):
+    from fsrl_amd.agent import PPOLagAgent
+    from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+    from fsrl_amd.env import SyntheticSafetyVectorEnv
+    from fsrl_amd.utils import BaseLogger
+    agents, cols, bufs = [], [], []
+    for s in range(first_seed, first_seed + k):
+        env = SyntheticSafetyVectorEnv(env_num=envs, obs_dim=8, act_dim=2, episode_len=300, seed=s)
+        ag = PPOLagAgent(env, BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_bgc{s}_"), name=f"s{s}"), cost_limit=10.0, device=device,
+                         seed=s, hidden_sizes=(256, 256), training_num=envs)
+        ag.policy.train()
+        buf = HipVectorReplayBuffer(ag.policy.engine, None, envs)
+        agents.append(ag); bufs.append(buf); cols.append(FastCollector(ag.policy, env, buf, exploration_noise=True, device_actor=True))
+    return agents, cols, bufs
+
+
+def _seq(cols, n_ep):
+    steps = 0
+    for c in cols:
+        steps += c.collect(n_episode=n_ep)["n/st"]
+        c.reset_buffer(keep_statistics=True)
+    return steps
+
+
+def _lock(gc, cols, n_ep):
+    steps = sum(st["n/st"] for st in gc.collect(n_episode=n_ep))
+    for c in cols:
+        c.reset_buffer(keep_statistics=True)
+    return steps
+
+
+def _call_us(fn, n):
+    for _ in range(20):
+        fn()
+    t = time.perf_counter()
+    for _ in range(n):
+        fn()
+    return (time.perf_counter() - t) / n * 1e6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", default="1,2,4,8")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--envs", type=int, default=20)
+    ap.add_argument("--calls", type=int, default=2000)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    from fsrl_amd.data import GroupCollector
+    from fsrl_amd.policy import PolicyGroup
+    n_ep = a.envs
+    res = {"envs": a.envs, "hidden": 256, "rounds": a.rounds, "k": {}}
+    for k in [int(x) for x in a.ks.split(",")]:
+        solo_agents, solo_cols, _ = _agents(k, a.envs, 0, a.device)
+        grp_agents, grp_cols, grp_bufs = _agents(k, a.envs, 0, a.device)
+        group = PolicyGroup([ag.policy for ag in grp_agents])
+        eg = group.group
+        gc = GroupCollector(group, grp_cols)
+        t = {"seq_ungrouped": [], "seq_grouped": [], "lockstep": []}
+        launches, collects = 0, 0
+        _seq(solo_cols, n_ep); _seq(grp_cols, n_ep); _lock(gc, grp_cols, n_ep)          # warm-up: code loading, first launches
+        for _ in range(a.rounds):
+            for mode in t:
+                l0 = eg.actor_resident_stats()["launches"]
+                t0 = time.perf_counter()
+                if mode == "seq_ungrouped":
+                    st = _seq(solo_cols, n_ep)
+                elif mode == "seq_grouped":
+                    st = _seq(grp_cols, n_ep)
+                else:
+                    st = _lock(gc, grp_cols, n_ep)
+                    launches += eg.actor_resident_stats()["launches"] - l0
+                    collects += 1
+                t[mode].append(st / (time.perf_counter() - t0))
+        out = {m: round(float(np.median(v))) for m, v in t.items()}
+        out["all"] = {m: [round(x) for x in v] for m, v in t.items()}
+        out["lockstep_over_seq_ungrouped"] = round(out["lockstep"] / out["seq_ungrouped"], 3)
+        out["launches_per_collect"] = round(launches / max(collects, 1), 2)
+        out["rows_per_member_per_collect"] = n_ep * 300
+        # one grouped actor call (k x 20 rows) against one member's own resident 20-row call
+        rng = np.random.default_rng(0)
+        obs = rng.standard_normal((a.envs, 8)).astype(np.float32)
+        e0 = solo_agents[0].policy.engine
+        out["us_member_call"] = round(_call_us(lambda: e0.collect_step(None, obs, False, 1), a.calls), 2)
+        e0.actor_release()
+        out["us_group_call"] = round(_call_us(lambda: eg.collect_step([None] * k, [obs] * k, False, 1), a.calls), 2)
+        eg.actor_release()
+        out["group_call_over_member_call"] = round(out["us_group_call"] / out["us_member_call"], 3)
+        # collect + grouped update, the training loop's shape
+        steps, updates = 0, 0
+        t0 = time.perf_counter()
+        for _ in range(2):
+            sts = gc.collect(n_episode=n_ep)
+            for ag, st in zip(grp_agents, sts):
+                ag.policy.pre_update_fn(stats_train=st)
+                steps += st["n/st"]
+            group.update(grp_bufs, batch_size=256, repeat=4)
+            updates += k
+            for c in grp_cols:
+                c.reset_buffer(keep_statistics=True)
+        dt = time.perf_counter() - t0
+        out["loop_env_steps_per_s"] = round(steps / dt)
+        out["loop_updates_per_s"] = round(updates / dt, 1)
+        res["k"][str(k)] = out
+        group.close()
+        for ag in solo_agents + grp_agents:
+            ag.policy.engine.close()
+        print(f"k={k}: {json.dumps(out)}", file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
