@@ -186,6 +186,7 @@ struct fsrl_ctx {
     int probe_phase = 0, probe_wgrad_skip = 0;
     unsigned long long* probe_ts = nullptr;   // probe builds: [1024][16] phase stamps of the last fused-kernel launch
     bool probe_tile16 = false;
+    struct fsrl_sac_group* sac_group = nullptr;      // the grouped SAC-Lagrangian update this context is a member of (host_sac_group.inc)
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
@@ -234,6 +235,7 @@ static int flush_stage(fsrl_ctx* c);
 // one launch per call.  The actor / collector entry points themselves keep it (plain hipSetDevice).
 static void pactor_release(fsrl_ctx* c);
 static void group_actor_release(fsrl_group* g);     // the group's resident actor (host_group_collect.inc): a member's stream is the group's
+static void sac_group_detach(fsrl_ctx* c);        // a member destroyed before its SAC group (host_sac_group.inc)
 #define ENTER_DEV(c) do { HIPCHK(hipSetDevice((c)->device)); pactor_release(c); } while (0)
 
 static int join_store(fsrl_ctx* c) {
@@ -431,6 +433,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     pactor_release(c);
     (void)hipDeviceSynchronize();
     if (c->group) group_detach(c);          // a member destroyed before its group: take its own stream back
+    if (c->sac_group) sac_group_detach(c);
     comm_free(c);
     tr_free(c);
     sac_free(c);
@@ -1467,6 +1470,9 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_sac.inc"
 
 #include "host_cvpo.inc"
+
+#include "kernels_sac_group.hpp"
+#include "host_sac_group.inc"
 
 #include "host_comm.inc"
 

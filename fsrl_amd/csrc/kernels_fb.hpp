@@ -1304,14 +1304,9 @@ __device__ __forceinline__ void wgrad_aux_pass(const FbWgradArgs& wa, const FbWg
 // does not depend on scheduling.  PAIR2: second operand pair (R-op products of the HVP).
 // Rider (kernels_sample.hpp): SgRider appends blocks along x that draw + gather the replay agents' next batch on the CUs this launch
 // leaves idle; NoRider (every other caller) compiles to the kernel as it was.
-template <int H, bool PAIR2, class Rider = NoRider>
-__global__ __launch_bounds__(1024) void fb_wgrad_kernel(const ModelDesc md, const FbWgradArgs wa, const Rider rider = Rider{}) {
-    if constexpr (Rider::on) {
-        if ((int)blockIdx.x >= rider.x0) {
-            sac_sample_gather_block(rider.sa, rider.ga, (int)((blockIdx.z * gridDim.y + blockIdx.y) * rider.nx + blockIdx.x - rider.x0));
-            return;
-        }
-    }
+// the work of logical block (rb, by, bz) of fb_wgrad_kernel's 3-D grid (the grouped replay update, kernels_sac_group.hpp, calls it too)
+template <int H, bool PAIR2>
+__device__ __forceinline__ void fb_wgrad_body(const ModelDesc& md, const FbWgradArgs& wa, const int rb, const int by, const int bz) {
     constexpr int TPD = H / 64;             // dW2 tiles of 64 x 64 outputs
     constexpr int NT2 = TPD * TPD;
     constexpr int NA = H / FB_AUX_COLS;
@@ -1319,16 +1314,6 @@ __global__ __launch_bounds__(1024) void fb_wgrad_kernel(const ModelDesc md, cons
     constexpr int SLOT = 64 * 65;           // one 64 x 64 partial tile (+1 column of padding)
     __shared__ float red[(4 * SLOT > 8 * FB_AUX_SLOT) ? 4 * SLOT : 8 * FB_AUX_SLOT];     // tile role: 4 partial tiles; aux role: 8 partial slots
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int rb = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (wa.remap_total) {
-        const int L = blockIdx.x, per = gridDim.x >> 3;
-        const int Lp = (L & 7) * per + (L >> 3);
-        if (Lp >= wa.remap_total) return;
-        const int NB = NT2 + NA * wa.aux_passes + 1;
-        rb = Lp % NB;
-        const int g = Lp / NB;
-        by = g % wa.remap_ny; bz = g / wa.remap_ny;
-    }
     const FbWgradNet wn = wa.nets[by];
     const NetOff no = md.net[wn.net];
     const int KS0 = bz * wa.ks_per_split;
@@ -1448,6 +1433,30 @@ __global__ __launch_bounds__(1024) void fb_wgrad_kernel(const ModelDesc md, cons
             if (no.sigma >= 0 && tid >= 16 && tid < 16 + md.Da) gout[no.sigma + tid - 16] = tot;
         }
     }
+}
+
+template <int H, bool PAIR2, class Rider = NoRider>
+__global__ __launch_bounds__(1024) void fb_wgrad_kernel(const ModelDesc md, const FbWgradArgs wa, const Rider rider = Rider{}) {
+    if constexpr (Rider::on) {
+        if ((int)blockIdx.x >= rider.x0) {
+            sac_sample_gather_block(rider.sa, rider.ga, (int)((blockIdx.z * gridDim.y + blockIdx.y) * rider.nx + blockIdx.x - rider.x0));
+            return;
+        }
+    }
+    constexpr int TPD = H / 64;             // dW2 tiles of 64 x 64 outputs
+    constexpr int NT2 = TPD * TPD;
+    constexpr int NA = H / FB_AUX_COLS;
+    int rb = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    if (wa.remap_total) {
+        const int L = blockIdx.x, per = gridDim.x >> 3;
+        const int Lp = (L & 7) * per + (L >> 3);
+        if (Lp >= wa.remap_total) return;
+        const int NB = NT2 + NA * wa.aux_passes + 1;
+        rb = Lp % NB;
+        const int g = Lp / NB;
+        by = g % wa.remap_ny; bz = g / wa.remap_ny;
+    }
+    fb_wgrad_body<H, PAIR2>(md, wa, rb, by, bz);
 }
 
 // sum of the split partials of one element (or four adjacent ones) in float64, z ascending: the loads of EIGHT partials are

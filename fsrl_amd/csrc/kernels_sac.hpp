@@ -118,20 +118,22 @@ struct SacActorArgs {
     int probe;           // -DFSRL_PROBES builds: FWD launches return early -- 1 at entry, 2 behind the prologue, 3 behind the forward pass
 };
 
+// bx: this workgroup's tile of the launch (blockIdx.x of the single-context launch; the grouped launch passes it on); sa: the
+// sample's arguments when a.sg_on (a.sa of the single-context launch; the grouped launch's per-update step table)
 template <int H, int R>
-__global__ __launch_bounds__(4 * H) void sac_actor_tile_kernel(const float* __restrict__ P_,
-                                                              const ModelDesc md, const SacActorArgs a) {
-    __shared__ TileSmem<H> sm;
+__device__ __forceinline__ void sac_actor_tile_body(TileSmem<H>& sm, const float* __restrict__ P_, const ModelDesc& md,
+                                                    const SacActorArgs& a, const int bx,
+                                                    const SacSampleArgs& sa) {
     constexpr int NT = TileGeom<H>::NT;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, li = lane & 15, q = lane >> 4;
-    const bool second = a.tiles_half > 0 && (int)blockIdx.x >= a.tiles_half;
+    const bool second = a.tiles_half > 0 && bx >= a.tiles_half;
     const float* __restrict__ Pn = second ? a.P2 : P_;
     const float* __restrict__ obs_ = second ? a.obs2 : a.obs;
     const float* __restrict__ eps_ = second ? a.eps2 : a.eps;
     float* __restrict__ X_ = second ? a.X2 : a.X;
     float* __restrict__ lp_ = second ? a.lp2 : a.lp_out;
-    const int row0 = (second ? (int)blockIdx.x - a.tiles_half : (int)blockIdx.x) * R;
+    const int row0 = (second ? bx - a.tiles_half : bx) * R;
     const NetOff no = md.net[0];
     const int Do = md.Do, Da = md.Da;
     const int n_valid = max(0, min(R, a.B - row0));
@@ -145,12 +147,12 @@ __global__ __launch_bounds__(4 * H) void sac_actor_tile_kernel(const float* __re
         constexpr int BOOK_LDS = 512;
         __shared__ SacBook book_s[BOOK_LDS];
         __shared__ int idx_s[16], term_s[16];
-        const bool in_lds = a.sa.env_num <= BOOK_LDS;
+        const bool in_lds = sa.env_num <= BOOK_LDS;
         if (in_lds) {
-            for (int e = tid; e < a.sa.env_num; e += NT) book_s[e] = a.sa.book[e];
+            for (int e = tid; e < sa.env_num; e += NT) book_s[e] = sa.book[e];
             __syncthreads();
         }
-        const SacBook* __restrict__ book = in_lds ? book_s : a.sa.book;
+        const SacBook* __restrict__ book = in_lds ? book_s : sa.book;
         if (tid < 16) { idx_s[tid] = 0; term_s[tid] = 0; }
         // both halves draw their rows: the same counters, the same values, written twice.  Index + chain: one thread per row in wave 0;
         // the noise: one thread per (row, pair of action dimensions) from wave 1 on
@@ -160,14 +162,14 @@ __global__ __launch_bounds__(4 * H) void sac_actor_tile_kernel(const float* __re
         bool head_last = false;
         if (sampler) {
             int idx, term;
-            sac_sample_index(a.sa, book, row0 + tid, (uint32_t)a.sa.key, (uint32_t)(a.sa.key >> 32), idx, term, f_last, head_last);
+            sac_sample_index(sa, book, row0 + tid, (uint32_t)sa.key, (uint32_t)(sa.key >> 32), idx, term, f_last, head_last);
             idx_s[tid] = idx; term_s[tid] = term;
         } else if (tid >= 64 && tid < 64 + R * npair) {
             const int t = tid - 64, rl = t / npair, pp = t - rl * npair;
-            if (row0 + rl < a.B) sac_sample_noise(a.sa, row0 + rl, 2 * pp, (uint32_t)a.sa.key, (uint32_t)(a.sa.key >> 32));
+            if (row0 + rl < a.B) sac_sample_noise(sa, row0 + rl, 2 * pp, (uint32_t)sa.key, (uint32_t)(sa.key >> 32));
         }
         __syncthreads();
-        if (sampler) sac_sample_end_last(a.sa, row0 + tid, f_last, head_last);     // its flag byte may still be in flight at the barrier
+        if (sampler) sac_sample_end_last(sa, row0 + tid, f_last, head_last);     // its flag byte may still be in flight at the barrier
         // r6: the gathered rows go STRAIGHT into the stage registers (element e = row * Do + k: the stage's own mapping) and to the
         // batch arrays the later launches read; until r5 they were stored, waited for and read back (two more round trips)
         const SacGatherArgs& g = a.ga;
@@ -293,11 +295,18 @@ __global__ __launch_bounds__(4 * H) void sac_actor_tile_kernel(const float* __re
         float t = 0.0f;
         if (tid == 0 || a.mode == SAC_A_BWD)
             for (int i = 0; i < R; ++i) t += sm.w1[i * FB_NSTAT + tid];
-        a.statp[(size_t)blockIdx.x * FB_NSTAT + tid] = t;
+        a.statp[(size_t)bx * FB_NSTAT + tid] = t;
     }
     if (a.mode != SAC_A_BWD) return;
     tile_backward<H, R>(sm, no, wb, a.A1 + (size_t)row0 * H, a.A2 + (size_t)row0 * H, a.D1 + (size_t)row0 * H,
                      a.D2 + (size_t)row0 * H, a.DO + (size_t)row0 * FSRL_DOW, tid, false);
+}
+
+template <int H, int R>
+__global__ __launch_bounds__(4 * H) void sac_actor_tile_kernel(const float* __restrict__ P_,
+                                                              const ModelDesc md, const SacActorArgs a) {
+    __shared__ TileSmem<H> sm;
+    sac_actor_tile_body<H, R>(sm, P_, md, a, (int)blockIdx.x, a.sa);
 }
 
 // ---- n-step target (float64), base_policy.py:453-512 + nstep_return :543-567: the stand-alone launch (CVPO; SAC / DDPG-Lag fold

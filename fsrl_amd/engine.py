@@ -836,3 +836,41 @@ class EngineGroup:
         for e, n in zip(self.engines, sizes):
             e._n = n
         return [s[:int(n)] for s, n in zip(stats, nst)], [int(x) for x in stop]
+
+
+class EngineSacGroup:
+    """k SAC-Lagrangian engines (sac_init, stochastic actor) of one shape on one GPU, updated in lock step
+    (fsrl_sac_group_*): every launch of an update carries all members that still have updates to run.  Members keep their
+    own streams, stores, parameters, Philox keys and statistics rings, and stay ordinary engines between updates (push,
+    collect_step with the resident actor, sac_get_params, sac_drain ...)."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        assert self.engines, "a group needs at least one engine"
+        self.lib = self.engines[0].lib
+        k = len(self.engines)
+        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
+        self._g = C.c_void_p()
+        _lib.check(self.lib.fsrl_sac_group_create(arr, k, C.byref(self._g)))
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_sac_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, batch_size, n_updates, lagrangians=None, rescalings=None):
+        """n_updates[i] x Engine.sac_update(batch_size, ..., sync=False) on member i (library RNG), all in lock step.
+        lagrangians: None (use_lagrangian off) or [k][n_critics - 1]; rescalings: [k] (default 1).  Enqueues only: the
+        statistics rows wait in each member's ring for its sac_drain()."""
+        k = len(self.engines)
+        n = np.ascontiguousarray(n_updates, np.int32).reshape(k)
+        resc = np.ascontiguousarray(np.ones(k) if rescalings is None else rescalings, np.float64).reshape(k)
+        lag = None if lagrangians is None else np.ascontiguousarray(lagrangians, np.float64).reshape(k, -1)
+        _lib.check(self.lib.fsrl_sac_group_update(self._g, int(batch_size), _ptr(n, _i32p),
+                                                  _ptr(lag, _f64p) if lag is not None and lag.size else None, _ptr(resc, _f64p)))

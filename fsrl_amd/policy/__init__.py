@@ -12,4 +12,5 @@ install(__name__, globals(), {
     "DDPGLagrangian": "ddpg_lag",
     "CVPO": "cvpo",
     "PolicyGroup": "grouped",
+    "SACPolicyGroup": "grouped_sac",
 })

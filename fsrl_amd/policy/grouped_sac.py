@@ -1,0 +1,82 @@
+"""Grouped SAC-Lagrangian updates: k independent SACLagrangian policies of one network shape (multi-seed runs) stepped in lock
+step on one MI355X -- `fsrl_sac_group_update`, every launch of an update carrying all members.  Per member,
+`SACPolicyGroup.update(buffers, batch_size, n_updates)` is what OffpolicyTrainer.policy_update_fn does between pre_update_fn and
+post_update_fn: n_i calls of `policy.update(batch_size, buffer)` -- same lambda and rescaling, same Philox stream, same statistics
+rows, same lr_scheduler steps.
+
+    group = SACPolicyGroup([agent.policy for agent in agents])
+    ... every agent collects into ITS buffer (its own resident device actor), steps ITS PID multiplier (pre_update_fn) ...
+    group.update(buffers, batch_size=256, n_updates=[n_0, n_1, ...])
+    ... post_update_fn per agent (drains the rows into its logger) ..."""
+from typing import Sequence, Union
+
+from fsrl_amd.engine import EngineSacGroup
+from fsrl_amd.policy.sac_lag import SACLagrangian
+
+_RING_DRAIN = 2048          # SACLagrangian.learn drains its statistics ring after this many pending updates
+
+
+class SACPolicyGroup:
+    def __init__(self, policies: Sequence[SACLagrangian], engine_group=None):
+        self.policies = list(policies)
+        assert self.policies, "a group needs at least one policy"
+        assert all(isinstance(p, SACLagrangian) for p in self.policies), "grouped SAC updates: SACLagrangian policies"
+        # reference_rng=True draws the sample and the noise from the host's numpy / torch streams, one update at a time: a grouped
+        # update has the device's Philox streams only
+        assert not any(getattr(p, "_reference_rng", False) for p in self.policies), "reference_rng policies cannot be grouped"
+        self.group = engine_group if engine_group is not None else EngineSacGroup([p.engine for p in self.policies])
+
+    def close(self):
+        self.group.close()
+
+    def update(self, buffers, batch_size: int = 256, n_updates: Union[int, Sequence[int]] = 1):
+        pols = self.policies
+        k = len(pols)
+        n = [int(n_updates)] * k if isinstance(n_updates, (int,)) else [int(x) for x in n_updates]
+        assert len(n) == k and all(x >= 0 for x in n), "n_updates: one count >= 0 per policy"
+        assert len(buffers) == k, "one buffer per policy"
+        for p, b in zip(pols, buffers):
+            assert getattr(b, "engine", None) is p.engine, "buffer i must be the HipVectorReplayBuffer of policy i"
+        B = int(batch_size)
+        for p in pols:
+            p.updating = True
+        try:
+            # a fresh policy's first update keys its Philox stream (SACLagrangian.learn: seed + 1): that one runs on its own
+            for i, (p, b) in enumerate(zip(pols, buffers)):
+                if n[i] > 0 and p.gradient_steps == 0:
+                    p.update(B, b)
+                    p.updating = True
+                    n[i] -= 1
+            use_lag = pols[0].use_lagrangian
+            lags, resc = [], []
+            for p in pols:
+                lg, rs = p.lagrangians_and_rescaling() if p.use_lagrangian else ([], 1.0)
+                lags.append([float(x) for x in lg] or [0.0])
+                resc.append(float(rs))
+            # an lr scheduler moves the rates between two updates: one update per grouped call then
+            per_call = 1 if any(p.lr_scheduler is not None for p in pols) else _RING_DRAIN
+            left = list(n)
+            while any(left):
+                step = [min(x, per_call, _RING_DRAIN - p._pending) for x, p in zip(left, pols)]
+                self.group.update(B, step, lags if use_lag else None, resc)
+                for i, p in enumerate(pols):
+                    if not step[i]:
+                        continue
+                    left[i] -= step[i]
+                    p.gradient_steps += step[i]
+                    p._pending += step[i]
+                    p._dirty = p._rest_dirty = True
+                    for _ in range(step[i]):
+                        p._step_lr_scheduler()
+                    if p._pending >= _RING_DRAIN:
+                        p._drain()
+        except BaseException:
+            # a failed group update may have stepped some parameters already: the host mirrors are stale, nobody is updating
+            for p in pols:
+                p.updating = False
+                p._dirty = p._rest_dirty = True
+                p._mark_stale()
+            raise
+        for p in pols:
+            p.updating = False
+        return [{} for _ in pols]

@@ -538,6 +538,23 @@ int fsrl_sac_last_sample(fsrl_ctx* ctx, int64_t* indices, float* eps_target, flo
 /* the actor for the collector: mu and sigma = exp(clamp(log sigma)) of the tanh-Gaussian policy   */
 int fsrl_sac_actor_forward(fsrl_ctx* ctx, const float* obs, int32_t k, float* mu_out, float* sigma_out);
 
+/* ---- Grouped SAC-Lagrangian updates: k SAC-Lag contexts (fsrl_sac_init, stochastic actor) of one shape on one device, each
+ *      stepped n_updates[i] times per call in lock step; every launch of an update (nine, whatever k is) carries all members that
+ *      still have updates to run.  Members keep their own streams, stores, parameters, targets, Adam state, alpha, Philox key and
+ *      statistics ring, and stay ordinary contexts between calls (a call ends a member's resident actor; its next collect
+ *      relaunches it).  Shapes (obs / act / hidden), n_step, auto_alpha and use_lagrangian must agree; learning rates, tau, seeds
+ *      and store contents may differ.  Rejected with FSRL_EINVAL: DDPG-Lag, CVPO and layered contexts, a member listed twice or
+ *      already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works. */
+typedef struct fsrl_sac_group fsrl_sac_group;
+int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group** out);   /* 1 <= k <= 16, members not owned */
+int fsrl_sac_group_destroy(fsrl_sac_group* g);
+/* n_updates[k] back-to-back fsrl_sac_update calls per member (library RNG), all members in lock step; a member with fewer updates
+ * sits out the later ones (0: left untouched).  lagrangians [k][n_critics-1] (NULL when use_lagrangian is off), rescaling [k].
+ * Statistics rows go to each member's own ring (fsrl_sac_stats_drain works unchanged).  Enqueues only: each member's stream
+ * waits for the call before its next work.                                                                                   */
+int fsrl_sac_group_update(fsrl_sac_group* g, int32_t batch_size, const int32_t* n_updates,
+                          const double* lagrangians, const double* rescaling);
+
 /* ---- CVPO (fsrl/policy/cvpo.py:71-430), on the replay context of SAC-Lagrangian: create the
  *      context with algo = FSRL_ALGO_SAC_LAG, then fsrl_cvpo_init INSTEAD of fsrl_sac_init.
  *      Networks (cvpo_agent.py:143-186): Gaussian actor, mu = max_action * tanh(head), sigma = exp(clamp(head,
