@@ -950,6 +950,7 @@ struct SacState;
 static bool ctx_is_replay(const fsrl_ctx* c) { return c->cfg.algo == FSRL_ALGO_SAC_LAG; }
 static int sac_actor_launch(fsrl_ctx* c, const float* h_obs, float* h_raw, int k);                 // defined with the SAC code
 static void sac_actor_finish(fsrl_ctx* c, const float* h_raw, int k, float* mu_out, float* sigma_out);
+static int sac_raw_cols(const fsrl_ctx* c);                                                         // head outputs per row
 static bool sac_squashes(fsrl_ctx* c);
 static bool sac_actor_resident_args(fsrl_ctx* c, const float** P, const ModelDesc** md);   // false: no fused actor (layered / not initialised)
 
@@ -1019,7 +1020,7 @@ static int pactor_launch(fsrl_ctx* c, unsigned last_seq) {
     const float* P = c->P; const ModelDesc* md = &c->md;
     if (c->cfg.algo == FSRL_ALGO_SAC_LAG) {                                    // the replay agents' actor: raw head outputs, as sac_actor_launch
         if (!sac_actor_resident_args(c, &P, &md)) return fail(FSRL_ESTATE, "no fused actor network");
-        a.raw_cols = 2 * c->cfg.act_dim; a.max_action = 1.0f;
+        a.raw_cols = sac_raw_cols(c); a.max_action = 1.0f;
     }
     const ModelDesc mdv = *md;
     const int rc = dispatch_H(c->cfg.hidden, [&](auto hc) {

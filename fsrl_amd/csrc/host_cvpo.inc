@@ -312,7 +312,11 @@ extern "C" int fsrl_sac_last_sample(fsrl_ctx* c, int64_t* indices, float* eps_ta
 }
 
 // replay-context halves of actor_eval_launch / actor_eval_finish: mlp_infer_kernel writes the raw head outputs
-// [mu | log sigma] (2*Da per row; DDPG-Lag: the mean head in the first Da) straight into pinned host memory
+// [mu | log sigma] (2*Da per row; DDPG-Lag: the mean head only, Da per row) straight into pinned host memory
+static int sac_raw_cols(const fsrl_ctx* c) {
+    const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
+    return (s && s->ddpg ? 1 : 2) * c->cfg.act_dim;       // never more than a head row (FSRL_MAX_ACT): DDPG allows act_dim 16
+}
 static int sac_actor_launch(fsrl_ctx* c, const float* h_obs, float* h_raw, int k) {
     SacState* s = sac_of(c);
     if (!s) return fail(FSRL_ESTATE, "fsrl_sac_init / fsrl_cvpo_init first");
@@ -321,14 +325,14 @@ static int sac_actor_launch(fsrl_ctx* c, const float* h_obs, float* h_raw, int k
         if (rc) return rc;
         rc = lay_fwd_k(c, s->ka, s->PA, h_obs, k);
         if (rc) return rc;
-        hipLaunchKernelGGL(lay_raw_out_kernel, dim3((k + 15) / 16), dim3(64), 0, c->compute, s->ka.out, h_raw, 2 * c->cfg.act_dim, k,
+        hipLaunchKernelGGL(lay_raw_out_kernel, dim3((k + 15) / 16), dim3(64), 0, c->compute, s->ka.out, h_raw, sac_raw_cols(c), k,
                            c->h_done, c->actor_seq);
         HIPCHK(hipGetLastError());
         return 0;
     }
     InferArgs ia{};
     ia.obs = h_obs; ia.obs_next = h_obs; ia.N = k; ia.C = 0; ia.max_action = 1.0f; ia.raw_out = h_raw;
-    ia.raw_cols = 2 * c->cfg.act_dim; ia.done = c->h_done; ia.seq = c->actor_seq;
+    ia.raw_cols = sac_raw_cols(c); ia.done = c->h_done; ia.seq = c->actor_seq;
     return dispatch_H(c->cfg.hidden, [&](auto hc) {
         constexpr int H = decltype(hc)::value;
         hipLaunchKernelGGL(mlp_infer_kernel<H>, dim3((k + 15) / 16, 1), dim3(4 * H), 0, c->compute, s->PA, s->mda, ia);
@@ -344,18 +348,18 @@ static bool sac_actor_resident_args(fsrl_ctx* c, const float** P, const ModelDes
 }
 static void sac_actor_finish(fsrl_ctx* c, const float* raw, int k, float* mu_out, float* sigma_out) {
     SacState* s = sac_of(c);
-    const int Da = c->cfg.act_dim;
+    const int Da = c->cfg.act_dim, rc = sac_raw_cols(c);
     for (int r = 0; r < k; ++r)
         for (int d = 0; d < Da; ++d) {
             if (s->ddpg) {     // deterministic actor: the action itself, and the exploration-noise std
-                mu_out[(size_t)r * Da + d] = c->cfg.max_action * std::tanh(raw[(size_t)r * 2 * Da + d]);
+                mu_out[(size_t)r * Da + d] = c->cfg.max_action * std::tanh(raw[(size_t)r * rc + d]);
                 if (sigma_out) sigma_out[(size_t)r * Da + d] = s->cfg.exploration_sigma;
                 continue;
             }
-            mu_out[(size_t)r * Da + d] = s->cvpo ? c->cfg.max_action * std::tanh(raw[(size_t)r * 2 * Da + d])
-                                                 : raw[(size_t)r * 2 * Da + d];
+            mu_out[(size_t)r * Da + d] = s->cvpo ? c->cfg.max_action * std::tanh(raw[(size_t)r * rc + d])
+                                                 : raw[(size_t)r * rc + d];
             if (sigma_out) {
-                const float l = std::min(std::max(raw[(size_t)r * 2 * Da + Da + d], -20.0f), 2.0f);
+                const float l = std::min(std::max(raw[(size_t)r * rc + Da + d], -20.0f), 2.0f);
                 sigma_out[(size_t)r * Da + d] = std::exp(l);
             }
         }

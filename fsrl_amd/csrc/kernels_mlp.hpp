@@ -468,9 +468,9 @@ __global__ __launch_bounds__(4 * H) void mlp_infer_kernel(const float* __restric
         tile = ntile; row0 = nrow0; n_valid = nn_valid;
     }
     if (a.done) {                 // the collector's call (C = 0: actor rows only).  Only the waves that stored to pinned memory wait for their
-        // stores -- rows by threads 0 .. 15, raw outputs by elements 0 .. 255: a system-scope fence is an L2 write-back per wave, and
-        // sixteen of them serialise (r6: 3.7 us of a 15.7 us resident call)
-        if (tid < 256) __atomic_thread_fence(__ATOMIC_RELEASE);
+        // stores -- rows by threads 0 .. 15, raw outputs by elements 0 .. 16 * raw_cols - 1 (whole waves, at least the first 256 threads
+        // as in r6): a system-scope fence is an L2 write-back per wave, and sixteen of them serialise (r6: 3.7 us of a 15.7 us resident call)
+        if (tid < min(NT, max(256, (16 * a.raw_cols + 63) & ~63))) __atomic_thread_fence(__ATOMIC_RELEASE);
         __syncthreads();
         if (tid == 0) __hip_atomic_store(a.done + blockIdx.x, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -491,6 +491,7 @@ __global__ __launch_bounds__(4 * H) void mlp_infer_kernel(const float* __restric
 struct PActorArgs {
     const float* obs;                 // pinned [16 * blocks rows][Do]
     float* mu_out;                    // pinned [16 * blocks rows][Da]; raw_cols > 0 (replay contexts' actors): [rows][raw_cols] raw head outputs
+                                      //   (raw_cols <= FSRL_MAX_ACT: a row's outputs only)
     float* sigma_param_out;           // pinned [Da]
     const unsigned long long* bell;   // pinned: (k << 32) | seq
     unsigned* done;                   // pinned [blocks]: seq of the last request workgroup b served
@@ -569,9 +570,10 @@ __global__ __launch_bounds__(4 * H) void actor_resident_kernel(const float* __re
                 }
             }
         }
-        // only the waves that stored to pinned memory wait for their stores (RAW: elements 0 .. 16 * raw_cols - 1 <= 255, else rows by
-        // threads 0 .. 15): a system-scope fence is an L2 write-back per wave, sixteen of them serialise
-        if (tid < (RAW ? 256 : 64)) __atomic_thread_fence(__ATOMIC_RELEASE);
+        // only the waves that stored to pinned memory wait for their stores (RAW: elements 0 .. 16 * raw_cols - 1, whole waves, at least
+        // the first 256 threads as in r6; else rows by threads 0 .. 15): a system-scope fence is an L2 write-back per wave, sixteen of
+        // them serialise
+        if (tid < (RAW ? min(NT, max(256, (16 * a.raw_cols + 63) & ~63)) : 64)) __atomic_thread_fence(__ATOMIC_RELEASE);
         __syncthreads();
         if (tid == 0) __hip_atomic_store(a.done + blk, seq_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }

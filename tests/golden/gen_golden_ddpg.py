@@ -3,7 +3,7 @@
 build container only.  Records the replay store, parameters and the sampled indices (the update itself
 draws no other random numbers) and the per-update stats / parameters after K updates.
 
-    python tests/golden/gen_golden_ddpg.py
+    python tests/golden/gen_golden_ddpg.py            (small, scaled, nolag; `depths`: deep3; `wide16`: wide16)
 """
 import json
 import os
@@ -30,7 +30,10 @@ def flat(mods):
 
 
 def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates, seed, n_step=3, max_action=1.0,
-        cost_stat=25.0, cost_limit=10.0, tau=0.05, actor_lr=1e-4, critic_lr=1e-3, gamma=0.99, use_lagrangian=True):
+        cost_stat=25.0, cost_limit=10.0, tau=0.05, actor_lr=1e-4, critic_lr=1e-3, gamma=0.99, use_lagrangian=True,
+        compact=False):
+    """compact: for shapes whose four parameter snapshots alone would exceed the size limit of a committed file -- initial
+    parameters rounded to float16 values (stored as float16, exact in float32) and no target-network snapshots"""
     seed_all(seed)
     actor = Actor(Net((obs_dim, ), hidden_sizes=hidden), (act_dim, ), max_action=max_action)
     actor_optim = torch.optim.Adam(actor.parameters(), lr=actor_lr)
@@ -46,6 +49,8 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
         for p in ac.parameters():
             if p.ndim == 1:
                 p.add_(0.05 * torch.randn(p.shape, generator=g))
+            if compact:
+                p.copy_(p.half().float())
     logger = CaptureLogger()
     policy = DDPGLagrangian(actor=actor, critics=critics, actor_optim=actor_optim, critic_optim=critic_optim,
                             logger=logger, tau=tau, gamma=gamma, n_step=n_step, exploration_noise=None,
@@ -57,6 +62,8 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
     buf = fill_buffer(rng, env_num, ep_lens, obs_dim, act_dim, buffer_size=100000)
     buf._meta["act"][:] = max_action * np.tanh(buf._meta["act"])
     out = {"theta_actor0": flat([actor]), "theta_critics0": flat(critics)}
+    if compact:
+        out = {k: v.astype(np.float16) for k, v in out.items()}
     meta = buf._meta
     used = np.concatenate([np.arange(o, o + len(b)) for o, b in zip(buf._offset, buf.buffers)])
     out["slots"] = used
@@ -87,9 +94,10 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
     out["stats_actor"] = np.array([[rows[2 * i][k] for k in ka] for i in range(n_updates)], np.float64)
     out["stats_critic"] = np.array([[rows[2 * i + 1][k] for k in kc] for i in range(n_updates)], np.float64)
     out["theta_actor_final"] = flat([actor])
-    out["theta_actor_old_final"] = flat([policy.actor_old])
     out["theta_critics_final"] = flat(critics)
-    out["theta_critics_old_final"] = flat(list(policy.critics_old))
+    if not compact:
+        out["theta_actor_old_final"] = flat([policy.actor_old])
+        out["theta_critics_old_final"] = flat(list(policy.critics_old))
     cfg = dict(obs_dim=obs_dim, act_dim=act_dim, hidden=list(hidden), env_num=env_num, batch_size=batch_size,
                n_updates=n_updates, seed=seed, n_step=n_step, cost_stat=cost_stat, cost_limit=cost_limit, tau=tau,
                actor_lr=actor_lr, critic_lr=critic_lr, gamma=gamma, max_action=max_action,
@@ -103,6 +111,11 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
 if __name__ == "__main__":
     torch.set_num_threads(4)
     eps = [[60, 50, -17], [70, 55], [40, 40, 40, -9]]
+    if sys.argv[1:] == ["wide16"]:
+        # the widest allowed shape: a 16-wide deterministic head and a critic input of obs_dim + act_dim = 128 (FSRL_MAX_OBS)
+        gen("wide16", 112, 16, (128, 128), 3, [[20, -6], [18, 12], [25, -5]], batch_size=100, n_updates=5, seed=44,
+            n_step=2, max_action=2.0, compact=True)
+        sys.exit(0)
     if sys.argv[1:] == ["depths"]:
         # hidden_sizes the fused kernels do not hold (ddpg_lag_agent.py: any tuple): layered contexts on the HIP side
         gen("deep3", 6, 3, (40, 56, 32), 3, eps, batch_size=64, n_updates=5, seed=43, n_step=2)

@@ -337,14 +337,14 @@ def test_resident_actor_survives_updates_between_collects():
     assert 3 <= outs[0][2]["launches"] <= 12 and outs[0][2]["requests"] == 120, outs[0][2]
 
 
-@pytest.mark.parametrize("kind", ["sac", "ddpg", "cvpo"])
-def test_resident_actor_of_the_replay_agents_is_the_launched_one_bit_for_bit(kind):
+@pytest.mark.parametrize("kind,Da", [("sac", 3), ("ddpg", 3), ("cvpo", 3), ("ddpg", 16)], ids=["sac", "ddpg", "cvpo", "ddpg16"])
+def test_resident_actor_of_the_replay_agents_is_the_launched_one_bit_for_bit(kind, Da):
     """The replay agents' collector actor (raw head outputs [mu | log sigma], sac_lag.py:155-183) through the resident kernel against
     one launch per call: identical (mu, sigma) and identical sampled actions for every row count, before and after updates (the
     update's launches end the resident kernel; the next call runs the updated actor)."""
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
-    E, sub, Do, Da, B = 24, 64, 11, 3, 64
+    E, sub, Do, B = 24, 64, 11, 64
     outs = []
     for resident in (True, False):
         eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden_sizes=(128, 128), n_critics=2, env_num=E,
@@ -380,6 +380,76 @@ def test_resident_actor_of_the_replay_agents_is_the_launched_one_bit_for_bit(kin
     assert np.array_equal(outs[0][1], outs[1][1])
     assert outs[0][2]["requests"] == 120 and 2 <= outs[0][2]["launches"] <= 12, outs[0][2]
     assert outs[1][2] == dict(launches=0, requests=0, live=False)
+
+
+def _ddpg_actor_engine(hidden, Do, Da, resident, max_action=2.0, sigma=0.3):
+    """A DDPG-Lag context with fan-in scaled actor parameters (the head stays off tanh's tails), and its float64 actor."""
+    from fsrl_amd import _lib
+    from fsrl_amd.engine import Engine, EngineConfig
+    from oracle.ddpg_lag import mlp_spec
+    hs = (hidden, hidden) if isinstance(hidden, int) else tuple(hidden)
+    eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden_sizes=hs, n_critics=2, env_num=64,
+                              buffer_size=64 * 4, max_action=max_action, target_kl=None))
+    eng.sac_init(n_step=1, deterministic=True, exploration_sigma=sigma)
+    eng.actor_set_resident(resident, idle_timeout_us=2.0e5)
+    rng = np.random.default_rng(Da + len(hs))
+    spec = mlp_spec(Do, Da, hs)
+    last = list(spec)[-2]                          # the head: half the fan-in scale, |pre-activation| ~ 0.5
+    tha = np.concatenate([((0.5 if name == last else 1.0) * rng.standard_normal(shp) / np.sqrt(shp[1]) if len(shp) == 2
+                           else 0.1 * rng.standard_normal(shp)).ravel() for name, shp in spec.items()]).astype(np.float32)
+    eng.sac_set_params(tha, (0.1 * rng.standard_normal(eng.n_sac_critics)).astype(np.float32), 0.0)
+    th, off, p = eng.sac_get_params(0)[0].astype(np.float64), 0, {}
+    for name, shp in spec.items():
+        n = int(np.prod(shp))
+        p[name] = th[off:off + n].reshape(shp); off += n
+    assert off == th.size
+
+    def ref(obs):                                  # max_action * tanh(MLP(obs)), float64 (oracle/ddpg_lag.py: Actor)
+        h = obs.astype(np.float64)
+        n_lin = len(spec) // 2
+        for l in range(1, n_lin):
+            h = np.maximum(h @ p[f"W{l}"].T + p[f"b{l}"], 0.0)
+        return max_action * np.tanh(h @ p[f"W{n_lin}"].T + p[f"b{n_lin}"])
+    return eng, ref
+
+
+@pytest.mark.parametrize("resident", [True, False])
+@pytest.mark.parametrize("Da", [9, 16])
+@pytest.mark.parametrize("hidden", [64, 128, 256, (40, 72, 24)])
+def test_ddpg_collector_actor_vs_float64_reference(hidden, Da, resident):
+    """The DDPG-Lag collector actor with more than 8 actions (its head only: act_dim up to 16) against a float64 forward of the
+    same parameters: one row, both sides of row 8 of a tile, ragged tiles, the resident kernel's cap of 64 rows and beyond it."""
+    Do, amax, sigma = 21, 2.0, 0.3
+    eng, ref = _ddpg_actor_engine(hidden, Do, Da, resident, amax, sigma)
+    rng = np.random.default_rng(7)
+    for k in (1, 8, 9, 15, 16, 17, 31, 33, 64, 65, 130):
+        obs = rng.standard_normal((k, Do)).astype(np.float32)
+        want = ref(obs)
+        assert 0.05 < np.abs(want).mean() < 0.8 * amax        # neither zero nor saturated
+        mu, sg = eng.sac_actor_forward(obs)
+        np.testing.assert_allclose(mu, want, rtol=0, atol=2e-6, err_msg=f"k={k}")
+        assert np.array_equal(sg, np.full((k, Da), np.float32(sigma))), k
+        assert np.array_equal(eng.actor_sample(obs, deterministic=True), mu), k
+    eng.close()
+
+
+def test_ddpg_resident_actor_answers_every_call_with_its_own_rows():
+    """2 000 resident calls at H = 256 (1 024 threads, 16 waves) and act_dim 16, 16 and 64 rows in turn, fresh observations on every
+    call: every row equals the float64 actor's answer for THIS call, so a row the host read before its store landed (the answer of
+    the previous call) fails.  Checks values only; a few seconds."""
+    Do, Da = 24, 16
+    eng, ref = _ddpg_actor_engine(256, Do, Da, True)
+    rng = np.random.default_rng(12)
+    n = 2000
+    for i in range(n):
+        k = 16 if i % 2 == 0 else 64
+        obs = rng.standard_normal((k, Do)).astype(np.float32)
+        mu, _ = eng.sac_actor_forward(obs)
+        err = np.abs(mu - ref(obs)).max(axis=1)          # 1e-5: above the rounding tail of 2e6 values, far below a stale row's O(1)
+        assert (err <= 1e-5).all(), (i, k, np.flatnonzero(err > 1e-5), err.max())
+    st = eng.actor_resident_stats()
+    assert st["requests"] == n and 1 <= st["launches"] <= 12, st
+    eng.close()
 
 
 def test_resident_actor_calls_spaced_around_its_idle_timeout():

@@ -178,6 +178,7 @@ CVPO_VARIANTS = [  # Do, Da, H, rows per env, batch, K, n_step, double_critic, e
     (41, 1, 64, [90, 45], 333, 5, 2, False, 1, 1, 0.5),       # batch larger than the store, K not a power of two
     (7, 3, (40, 24, 56), [40, 17], 100, 16, 2, False, 1, 1, 1.0),    # layered context: three ragged hidden layers
     (12, 4, (300, ), [64, 64], 50, 8, 3, True, 2, 2, 2.0),            # layered context: one wide layer, DoubleCritic, scaled actions
+    (120, 8, 128, [70, 50], 100, 16, 2, True, 1, 1, 1.0),     # widest critic input: obs_dim + act_dim = 128 (FSRL_MAX_OBS)
 ]
 
 

@@ -30,7 +30,8 @@ def _engine(cfg, g):
     return eng
 
 
-@pytest.mark.parametrize("name", ["small", "scaled", "nolag", "deep3"])
+# wide16: act_dim 16 and obs_dim + act_dim = 128, a compact fixture without target-network snapshots (1 MiB limit)
+@pytest.mark.parametrize("name", ["small", "scaled", "nolag", "deep3", "wide16"])
 def test_ddpg_updates_vs_golden(name):
     g, cfg, ocfg, store, index = ddpg_setup(name)
     eng = _engine(cfg, g)
@@ -49,6 +50,8 @@ def test_ddpg_updates_vs_golden(name):
                 assert abs(st[j] - want[k]) <= 5e-5 * abs(want[k]) + 5e-6, (u, k, st[j], want[k])
     for which, key in ((0, "theta_actor_final"), (3, "theta_actor_old_final"), (1, "theta_critics_final"),
                        (2, "theta_critics_old_final")):
+        if name == "wide16" and "old" in key:
+            continue                  # not in the compact fixture: test_ddpg_variants_vs_oracle checks the targets at this shape
         d = np.abs(eng.sac_get_params(which)[0] - g[key])
         assert np.quantile(d, 0.99) <= 5e-6 and d.max() <= 2e-3, (key, np.quantile(d, 0.99), d.max())
     # collector-time action: deterministic = max_action * tanh(actor(s)); exploration adds N(0, 0.1^2)
@@ -58,6 +61,147 @@ def test_ddpg_updates_vs_golden(name):
     a = np.stack([eng.actor_sample(obs, seed=3 if i == 0 else 0) for i in range(400)])
     assert abs((a - a_det).std() - 0.1) < 0.01
     eng.close()
+
+
+def _synthetic_engine(Do, Da, hidden, rows, n_step, use_lag, max_action, seed, sub=128):
+    """A DDPG-Lag context and the oracle on the same random replay store (fan-in scaled parameters: the heads stay off tanh's tails)."""
+    from fsrl_amd import _lib
+    from fsrl_amd.engine import Engine, EngineConfig
+    from oracle.ddpg_lag import DDPGConfig, DDPGLagOracle
+    from oracle.sac_lag import ReplayIndex
+    rng = np.random.default_rng(seed)
+    E = len(rows)
+    hs = (hidden, hidden) if isinstance(hidden, int) else tuple(hidden)
+    ocfg = DDPGConfig(obs_dim=Do, act_dim=Da, hidden=hs, max_action=max_action, gamma=0.98, n_step=n_step, tau=0.1,
+                      actor_lr=1e-3, critic_lr=1e-3, use_lagrangian=use_lag)
+    eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden_sizes=hs, n_critics=2, env_num=E,
+                              buffer_size=E * sub, gamma=0.98, max_action=max_action, target_kl=None))
+    eng.sac_init(actor_lr=1e-3, critic_lr=1e-3, tau=0.1, n_step=n_step, use_lagrangian=use_lag, deterministic=True)
+    o = DDPGLagOracle(ocfg)
+
+    def init(spec):
+        return np.concatenate([(rng.standard_normal(shp) / np.sqrt(shp[1]) if len(shp) == 2 else 0.1 * rng.standard_normal(shp)).ravel()
+                               for shp in spec.values()]).astype(np.float32)
+    tha, thc = init(o.aspec), np.concatenate([init(o.cspec), init(o.cspec)])
+    o.set_params(tha, thc); eng.sac_set_params(tha, thc, 0.0)
+    store = {k: np.zeros((E * sub, ) + s, d) for k, s, d in (("obs", (Do, ), np.float32), ("obs_next", (Do, ), np.float32),
+             ("act", (Da, ), np.float32), ("rew", (), np.float64), ("cost", (), np.float64),
+             ("terminated", (), bool), ("truncated", (), bool))}
+    for t in range(max(rows)):
+        ids = [e for e in range(E) if t < rows[e]]
+        k = len(ids)
+        row = dict(obs=rng.standard_normal((k, Do)).astype(np.float32),
+                   act=(max_action * np.tanh(rng.standard_normal((k, Da)))).astype(np.float32), rew=rng.normal(0, 1, k),
+                   cost=(rng.random(k) < 0.3).astype(np.float64), terminated=rng.random(k) < 0.1,
+                   truncated=np.full(k, t % 11 == 10), obs_next=rng.standard_normal((k, Do)).astype(np.float32))
+        eng.push(ids, row["obs"], row["act"], row["rew"], row["cost"], row["terminated"], row["truncated"], row["obs_next"])
+        for e, j in zip(ids, range(k)):
+            for key in store:
+                store[key][e * sub + t] = row[key][j]
+    index = ReplayIndex(rows, sub, store["terminated"] | store["truncated"])
+    valid = np.concatenate([e * sub + np.arange(r) for e, r in enumerate(rows)])
+    return eng, o, store, index, valid, rng
+
+
+DDPG_VARIANTS = [  # Do, Da, hidden, rows per env, batch, n_step, use_lagrangian, max_action, plan
+    (112, 16, 128, [70, 50], 100, 2, True, 2.0, 0),         # Din = 128 with the widest head, batch not a multiple of 16
+    (30, 16, 256, [33], 1, 1, False, 1.0, 0),               # a batch of one row at the widest hidden width, no Lagrangian term
+    (9, 13, 64, [60, 45], 333, 3, True, 1.0, 0),            # odd action width, batch larger than the store
+    (9, 13, 64, [60, 45], 333, 3, True, 1.0, 1),            # the same with split-K weight gradients below 512 rows (plan bit 0)
+    (20, 16, 256, [100, 80, 120], 700, 2, True, 1.0, 0),    # above 512 rows: the split-K weight-gradient path
+    (120, 8, 64, [64, 64], 64, 2, True, 1.0, 0),            # Din = 128 at H = 64
+    (7, 11, (40, 72, 24), [40, 17], 64, 2, True, 1.0, 0),   # a layered context with a wide head
+]
+
+
+@pytest.mark.parametrize("Do,Da,hidden,rows,B,n_step,use_lag,amax,plan", DDPG_VARIANTS)
+def test_ddpg_variants_vs_oracle(Do, Da, hidden, rows, B, n_step, use_lag, amax, plan):
+    """Shapes outside the golden set (action heads up to 16 wide, critic inputs up to FSRL_MAX_OBS) against the oracle on the same
+    random problem; bounds as test_sac_variants_vs_oracle."""
+    eng, o, store, index, valid, rng = _synthetic_engine(Do, Da, hidden, rows, n_step, use_lag, amax, seed=Do + 10 * Da)
+    eng.sac_set_plan(plan)
+    lag = np.array([0.3]) if use_lag else np.zeros(0)
+    zero = np.zeros((B, Da), np.float32)
+    for u in range(3):
+        idx = rng.choice(valid, B)
+        sa, sc, _ = o.update(store, index, idx, lag, 1 / 1.3)
+        st = eng.sac_update(B, lag, 1 / 1.3, indices=idx, eps_target=zero, eps_pi=zero)
+        want = {**sa, **sc}
+        for j, kname in enumerate(KEYS):
+            if kname in want:
+                w = float(want[kname])
+                assert abs(st[j] - w) <= 1e-4 * abs(w) + 1e-5, (u, kname, st[j], w)
+    for which, ref in ((0, o.actor_flat()), (3, o.actor_flat(old=True)), (1, o.critics_flat()), (2, o.critics_flat(old=True))):
+        d = np.abs(eng.sac_get_params(which)[0] - ref)      # Adam: an entry whose gradient is rounding noise moves by +-lr per step
+        assert np.quantile(d, 0.99) <= 5e-6 and d.max() <= 3 * 1e-3, (which, np.quantile(d, 0.99), d.max())
+    eng.close()
+
+
+def test_ddpg_on_a_wrapped_store_device_and_host_chains_agree():
+    """act_dim 16, sub-buffers overwritten 2.5 times: the device sampler's n-step chains and the caller-RNG mode's (host) give
+    bit-identical DDPG-Lag updates from the same indices."""
+    from fsrl_amd import _lib
+    from fsrl_amd.engine import Engine, EngineConfig
+    rng = np.random.default_rng(3)
+    Do, Da, E, sub = 20, 16, 3, 40
+
+    def make():
+        eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden_sizes=(128, 128), n_critics=2, env_num=E,
+                                  buffer_size=E * sub, gamma=0.97, target_kl=None))
+        eng.sac_init(n_step=3, deterministic=True)
+        r = np.random.default_rng(0)
+        eng.sac_set_params((0.1 * r.standard_normal(eng.n_sac_actor)).astype(np.float32),
+                           (0.1 * r.standard_normal(eng.n_sac_critics)).astype(np.float32), 0.0)
+        return eng
+    dev, twin = make(), make()
+    T = 100                                                  # 2.5 x the sub-buffer
+    obs = rng.standard_normal((T + 1, E, Do)).astype(np.float32)
+    act = np.tanh(rng.standard_normal((T, E, Da))).astype(np.float32)
+    rew = rng.normal(0, 1, (T, E)); cost = (rng.random((T, E)) < 0.3).astype(np.float64)
+    term = rng.random((T, E)) < 0.05; trunc = np.zeros((T, E), bool); trunc[12::13] = True
+    for t in range(T):
+        ids = [0, 1, 2] if t % 7 else [0, 2]                 # env 1 lags: different write cursors
+        for e_ in (dev, twin):
+            e_.push(ids, obs[t, ids], act[t, ids], rew[t, ids], cost[t, ids], term[t, ids], trunc[t, ids], obs[t + 1, ids])
+    assert len(dev) == E * sub
+    for u in range(6):
+        dev.sac_update(64, [0.2], 1 / 1.2, seed=5 if u == 0 else 0, sync=False)
+        idx, et, ep = dev.sac_last_sample(64)
+        assert (idx >= 0).all() and (idx < E * sub).all()
+        st = twin.sac_update(64, [0.2], 1 / 1.2, indices=idx, eps_target=et, eps_pi=ep)
+    rows = dev.sac_drain()
+    assert np.isfinite(rows).all() and np.array_equal(rows[-1], st)
+    for which in (0, 1, 2, 3):
+        assert np.array_equal(dev.sac_get_params(which)[0], twin.sac_get_params(which)[0])
+    dev.close(); twin.close()
+
+
+@pytest.mark.parametrize("batch", [256, 1024])
+def test_ddpg_launch_plans_are_bit_identical(batch):
+    """test_fused_launch_plan_is_bit_identical_to_the_separate_launches (test_gpu_sac.py) on a DDPG-Lag context at act_dim 16: every
+    plan there (none sets bit 0, which changes sums) gives bit-identical statistics, parameters and samples over library-RNG updates,
+    rows pushed in between, and a caller-index update."""
+    Do, Da, rows = 20, 16, [200, 150, 180, 170]
+    outs = []
+    for plan in (0, 32, 64, 16, 6, 2, 8, 40, 14, 22):
+        eng, o, store, index, valid, rng = _synthetic_engine(Do, Da, 128, rows, 2, True, 1.0, seed=11, sub=256)
+        eng.sac_set_plan(plan)
+        got = [eng.sac_update(batch, [0.5], 1 / 1.5, seed=7 if u == 0 else 0).copy() for u in range(12)]
+        k = len(rows)                                       # new rows: the store changed, a prefetched sample must be dropped
+        eng.push(np.arange(k), store["obs"][:k], store["act"][:k], np.ones(k), np.zeros(k), np.zeros(k, bool), np.zeros(k, bool),
+                 store["obs"][:k])
+        got += [eng.sac_update(batch, [0.5], 1 / 1.5, sync=(u % 2 == 0)) for u in range(6)]
+        got = [r.copy() for r in got if r is not None]
+        idx = np.random.default_rng(1).choice(valid, batch)
+        zero = np.zeros((batch, Da), np.float32)
+        got.append(eng.sac_update(batch, [0.5], 1 / 1.5, indices=idx, eps_target=zero, eps_pi=zero).copy())
+        outs.append((np.stack(got), eng.sac_get_params(0)[0], eng.sac_get_params(1)[0], eng.sac_get_params(2)[0],
+                     eng.sac_get_params(3)[0], eng.sac_last_sample(batch)[0].copy()))
+        eng.close()
+    for other in outs[1:]:
+        for a, b in zip(outs[0], other):
+            assert np.array_equal(a, b)
+    assert np.isfinite(outs[0][0]).all()
 
 
 def test_ddpg_facade_matches_reference_and_agent_learns(tmp_path):

@@ -147,6 +147,7 @@ SAC_VARIANTS = [  # Do, Da, H, rows per env, batch, n_step, auto_alpha, use_lagr
     (20, 8, 128, [64, 64, 64], 16, 3, False, True),      # fixed temperature, maximum action width
     (9, 2, 256, [33], 1, 2, True, False),                # batch of one row, no Lagrangian term
     (41, 1, 64, [90, 45], 333, 2, True, True),           # batch larger than the store (sampling with replacement)
+    (120, 8, 64, [70, 50], 100, 2, True, True),          # widest critic input: obs_dim + act_dim = 128 (FSRL_MAX_OBS)
 ]
 
 
