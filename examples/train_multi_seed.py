@@ -7,14 +7,16 @@ kernels fill (3 agents: ~190 updates/s together).  ctypes releases the GIL insid
 the seeds overlap; the Python collector loops take turns.
 
     python examples/train_multi_seed.py --algo ppol --seeds 3 --epoch 2
-    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag and SAC-Lag
+    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag, FOCOPS and SAC-Lag
+    python examples/train_multi_seed.py --algo focops --seeds 4 --epoch 2 --grouped
     python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped
 
 --grouped: ONE thread; the seeds collect in lock step (fsrl_amd.data.GroupCollector -> fsrl_group_collect_step: one actor
 request per vector step for all seeds, served by one resident kernel) and their updates run in lock step through the grouped
 launches (fsrl_amd.policy.PolicyGroup -> fsrl_group_ppo_update: every launch of the minibatch step carries all seeds):
 ~2x the aggregate updates/s of the thread-per-seed mode at 4 seeds (tools/bench_group.py); collection: tools/bench_group_collect.py.
-Per seed the run is the one of collecting the seeds one after the other, bit for bit.
+Per seed the run is the one of collecting the seeds one after the other, bit for bit.  --grouped --algo focops: the same loop
+with FOCOPS seeds (each seed's nu step, then one grouped FOCOPS update; tools/bench_group_focops.py).
 --grouped --algo sacl: ONE thread; each seed collects with its own FastCollector (its resident device actor) and steps its PID
 multiplier, then ONE grouped update (fsrl_amd.policy.SACPolicyGroup -> fsrl_sac_group_update) runs round(update_per_step * n/st)
 updates per seed, every launch carrying all seeds (tools/bench_group_sac.py).
@@ -81,8 +83,9 @@ def run_grouped_sac(a):
 
 
 def run_grouped(a):
-    """k PPO-Lag seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier, ONE grouped update."""
-    assert a.algo in ("ppol", "sacl"), "--grouped: PPO-Lagrangian or SAC-Lagrangian"
+    """k PPO-Lag (FOCOPS) seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier (each
+    seed's cost goes to its nu step), ONE grouped update."""
+    assert a.algo in ("ppol", "focops", "sacl"), "--grouped: PPO-Lagrangian, FOCOPS or SAC-Lagrangian"
     if a.algo == "sacl":
         return run_grouped_sac(a)
     from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
@@ -90,14 +93,15 @@ def run_grouped(a):
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
-        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"ppol-s{seed}")
-        agent = PPOLagAgent(env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
-                            training_num=a.envs)
+        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
+        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
+                               training_num=a.envs)
         agent.policy.train()
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
     group = PolicyGroup([ag.policy for ag in agents])
+    mult = (lambda p: f"nu {float(p._nu):.3f}") if a.algo == "focops" else (lambda p: f"lambda {p.lag_optims[0].get_lag():.3f}")
     gcol = GroupCollector(group, cols)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
@@ -114,7 +118,7 @@ def run_grouped(a):
                 col.reset_buffer(keep_statistics=True)
         for seed, ag in enumerate(agents):
             print(f"epoch {ep + 1} seed {seed}: reward {ag.logger.get_mean('train/reward'):.2f} "
-                  f"cost {ag.logger.get_mean('train/cost'):.2f} lambda {ag.policy.lag_optims[0].get_lag():.3f}")
+                  f"cost {ag.logger.get_mean('train/cost'):.2f} {mult(ag.policy)}")
             ag.logger.write(steps, display=False)
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
@@ -131,7 +135,7 @@ def main():
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / SAC-Lag: lock-step grouped updates from one thread")
+    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag: lock-step grouped updates from one thread")
     a = ap.parse_args()
     out, errs = {}, []
     if a.grouped:

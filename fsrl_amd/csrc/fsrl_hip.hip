@@ -24,6 +24,7 @@
 #include "kernels_wgrad2.hpp"
 #include "kernels_wgrad3.hpp"
 #include "kernels_layered.hpp"
+#include "kernels_focops_group.hpp"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -236,6 +237,10 @@ static int flush_stage(fsrl_ctx* c);
 static void pactor_release(fsrl_ctx* c);
 static void group_actor_release(fsrl_group* g);     // the group's resident actor (host_group_collect.inc): a member's stream is the group's
 static void sac_group_detach(fsrl_ctx* c);        // a member destroyed before its SAC group (host_sac_group.inc)
+// grouped FOCOPS (host_focops_group.inc): the member checks of fsrl_group_create / _ppo_update, and the update itself
+static int focops_group_check(fsrl_ctx* const* ctxs, int k);
+static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
+                               float* const* stats_out, int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
 #define ENTER_DEV(c) do { HIPCHK(hipSetDevice((c)->device)); pactor_release(c); } while (0)
 
 static int join_store(fsrl_ctx* c) {
@@ -1467,6 +1472,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_trust.inc"
 
 #include "host_focops.inc"
+#include "host_focops_group.inc"
 
 #include "host_sac.inc"
 

@@ -47,6 +47,103 @@ extern "C" int fsrl_focops_set_nu(fsrl_ctx* c, double nu, double nu_loss) {
     return 0;
 }
 
+// parameter blocks of 256 of the three networks (focops_prep_kernel / focops_step_kernel lay them out actor | critic 0 | critic 1)
+static void focops_blocks(const fsrl_ctx* c, int* nb_a, int* nb_c0, int* nb_c1) {
+    *nb_a = (c->md.net[0].end - c->md.net[0].begin + 255) / 256;
+    *nb_c0 = (c->md.net[1].end - c->md.net[1].begin + 255) / 256;
+    *nb_c1 = (c->md.net[2].end - c->md.net[2].begin + 255) / 256;
+}
+// the FOCOPS working set for the current minibatch plan (c->mbp_max): allocated on first use, regrown with the minibatch
+// (focops_pass and, per member, the grouped update)
+static int focops_alloc(fsrl_ctx* c) {
+    FocState* f = c->foc;
+    const int max_tiles = c->mbp_max / 16;
+    int nb_a, nb_c0, nb_c1;
+    focops_blocks(c, &nb_a, &nb_c0, &nb_c1);
+    if (f->cap_tiles < max_tiles || f->cap_psq < nb_c0 + nb_c1) {
+        HIPCHK(hipStreamSynchronize(c->compute));
+        for (float** p : {&f->statp_pi, &f->psq, &f->gsq}) { if (*p) HIPCHK(hipFree(*p)); *p = nullptr; }
+        HIPCHK(hipMalloc(&f->statp_pi, (size_t)(4 * max_tiles + 4) * 3 * FB_NSTAT * 4));      // three networks per tile
+        if (!f->sig_stash) HIPCHK(hipMalloc(&f->sig_stash, 2 * FSRL_MAX_ACT * 4));
+        if (!f->gsq_net) HIPCHK(hipMalloc(&f->gsq_net, FSRL_MAX_NETS * 4));
+        HIPCHK(hipMalloc(&f->psq, (size_t)2 * (nb_c0 + nb_c1) * 4));
+        HIPCHK(hipMalloc(&f->gsq, (size_t)nb_a * 4));
+        f->cap_tiles = max_tiles; f->cap_psq = nb_c0 + nb_c1;
+    }
+    return 0;
+}
+// the step / prep launch's arguments that do not depend on the minibatch; pp: the psq / sig_stash parity of the step
+static FocopsStepArgs focops_step_args(const fsrl_ctx* c, int pp) {
+    const FocState* f = c->foc;
+    int nb_a, nb_c0, nb_c1;
+    focops_blocks(c, &nb_a, &nb_c0, &nb_c1);
+    const int npsq = nb_c0 + nb_c1;
+    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+    FocopsStepArgs sa{};
+    sa.P = c->P; sa.M = c->M; sa.V = c->V; sa.stride = c->n_dev;
+    sa.G = c->G; sa.gsq = f->gsq; sa.psq = f->psq + (size_t)pp * npsq; sa.sig_stash = f->sig_stash + pp * FSRL_MAX_ACT;
+    sa.psq_next = f->psq + (size_t)(pp ^ 1) * npsq; sa.sig_next = f->sig_stash + (pp ^ 1) * FSRL_MAX_ACT;
+    sa.nb_a = nb_a; sa.nb_c0 = nb_c0; sa.nb_c1 = nb_c1; sa.max_norm = f->cfg.max_grad_norm; sa.l2 = f->cfg.l2_reg;
+    sa.one_minus_b1 = (float)(1.0 - b1); sa.beta2 = c->cfg.beta2; sa.one_minus_b2 = (float)(1.0 - b2);
+    sa.adam_eps = c->cfg.adam_eps;
+    return sa;
+}
+// the tile launch's arguments for the minibatch of `size` rows at `start` (the rows prepared by ppo_pass_prepare)
+static FbArgs focops_tile_args(const fsrl_ctx* c, int start, int size) {
+    const FocState* f = c->foc;
+    FbArgs a{};
+    a.obs = c->obs_p + (size_t)start * c->cfg.obs_dim; a.rd = c->rd_p + (size_t)start * FSRL_RD;
+    a.A1 = c->A1; a.A2 = c->A2; a.D1 = c->D1; a.D2 = c->D2; a.DO = c->DO;
+    a.N = size; a.rows_pad = (size + 15) / 16 * 16; a.max_action = c->cfg.max_action;
+    a.cr = 1.0f / f->cfg.tem_lambda; a.cc = (float)f->nu; a.eta = f->cfg.eta;
+    a.mode = FB_MODE_FOCOPS; a.net0 = 0; a.statp = f->statp_pi;      // [tiles][3][FB_NSTAT]
+    return a;
+}
+// the minibatch's weight gradients of all three networks in ppo_wgrad_kernel's layout (three-launch step)
+static WgradPtrs focops_wgrad_ptrs(const fsrl_ctx* c, const float* obs, int rows_pad) {
+    WgradPtrs wp{};
+    wp.A1 = c->A1; wp.A2 = c->A2; wp.D1 = c->D1; wp.D2 = c->D2; wp.DO = c->DO; wp.X = obs; wp.grad = c->G;
+    wp.gsq_part = c->gsq_part; wp.ctrl = c->ctrl; wp.mbp_max = rows_pad;     // the tile kernel laid network y out at y * rows_pad
+    wp.P = c->P; wp.statp = nullptr; wp.stats = nullptr;                      // no PPO row: focops_step_kernel's extra block logs
+    wp.gsq_net = c->foc->gsq_net;
+    return wp;
+}
+// ... and in fb_wgrad_kernel's (four-launch step; wgrad_launch fills in the split-K plan)
+static FbWgradArgs focops_split_args(const fsrl_ctx* c, const float* obs, int size, int rows_pad) {
+    const int H = c->cfg.hidden;
+    FbWgradArgs wa{};
+    for (int y = 0; y < 3; ++y) {
+        const size_t nb = (size_t)y * rows_pad;
+        FbWgradNet& wn = wa.nets[y];
+        wn.w2_ya = c->D2 + nb * H; wn.w2_xa = c->A1 + nb * H; wn.w1_y = c->D1 + nb * H;
+        wn.w3_xa = c->A2 + nb * H; wn.w3_ya = c->DO + nb * FSRL_DOW;
+        wn.b1_src = c->D1 + nb * H; wn.b2_src = c->D2 + nb * H; wn.do_src = c->DO + nb * FSRL_DOW;
+        wn.net = y;
+    }
+    wa.obs = obs; wa.rows = rows_pad; wa.N = size;
+    return wa;
+}
+// one minibatch step's optimiser side: both Adam step counters advance, the logged row goes to statistics row `row`
+static void focops_step_fill(fsrl_ctx* c, FocopsStepArgs& sa, int64_t row, int mb, int nmb, int size, int n_tiles) {
+    FocState* f = c->foc;
+    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+    f->t_critic += 1; f->t_actor += 1;
+    sa.step_a = (float)((double)f->cfg.actor_lr / (1.0 - std::pow(b1, (double)f->t_actor)));
+    sa.bc2s_a = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_actor));
+    sa.step_c = (float)((double)f->cfg.critic_lr / (1.0 - std::pow(b1, (double)f->t_critic)));
+    sa.bc2s_c = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_critic));
+    // ---- logged row, pass KL sum, pass-level early stop flag (the extra block of the step launch)
+    FocopsFinalArgs& fa = sa.fin;
+    fa.statp_vf = f->statp_pi + FB_NSTAT; fa.statp_pi = f->statp_pi; fa.vf_stride = 3; fa.pi_stride = 3;
+    fa.psq0 = sa.psq; fa.psq1 = sa.psq + sa.nb_c0; fa.n_psq0 = sa.nb_c0; fa.n_psq1 = sa.nb_c1;
+    fa.P = sa.sig_stash; fa.sigma_off = 0; fa.Da = c->cfg.act_dim;          // entropy of the PRE-update policy
+    fa.stats = c->d_stats + (size_t)row * FSRL_PPO_NSTATS; fa.ctrl = c->ctrl;
+    fa.n_tiles = n_tiles; fa.n_tiles_pi = fa.n_tiles; fa.mb = size;
+    fa.first_in_pass = mb == 0; fa.last_in_pass = mb == nmb - 1;
+    fa.iters_in_pass = nmb; fa.pass = (int)c->pass_index; fa.l2 = f->cfg.l2_reg; fa.nu_loss = (float)f->nu_loss;
+    fa.nu_value = (float)f->nu; fa.delta = f->cfg.delta;
+}
+
 // one pass of FOCOPS minibatch steps over the batch prepared by fsrl_ppo_pass (permuted rows, per-minibatch
 // normalised advantages, old means / stds in the row data).  Per minibatch (focops.py:226-241):
 //   critics:  fb_tile(VF, 2 nets) -> fb_wgrad -> Adam per critic (+ l2, records sum(theta^2))
@@ -56,33 +153,14 @@ static int focops_pass(fsrl_ctx* c, int32_t* stopped_out) {
     FocState* f = c->foc;
     if (!f) return fail(FSRL_ESTATE, "fsrl_focops_init first");
     hipStream_t s = c->compute;
-    const int H = c->cfg.hidden, Do = c->cfg.obs_dim;
+    const int H = c->cfg.hidden;
     const int nmb = (int)c->mb_start.size();
-    const int max_tiles = c->mbp_max / 16;
-    const int nb_c0 = (c->md.net[1].end - c->md.net[1].begin + 255) / 256, nb_c1 = (c->md.net[2].end - c->md.net[2].begin + 255) / 256;
-    const int nb_a = (c->md.net[0].end - c->md.net[0].begin + 255) / 256;
-    if (f->cap_tiles < max_tiles || f->cap_psq < nb_c0 + nb_c1) {
-        HIPCHK(hipStreamSynchronize(s));
-        for (float** p : {&f->statp_pi, &f->psq, &f->gsq}) { if (*p) HIPCHK(hipFree(*p)); *p = nullptr; }
-        HIPCHK(hipMalloc(&f->statp_pi, (size_t)(4 * max_tiles + 4) * 3 * FB_NSTAT * 4));      // three networks per tile
-        if (!f->sig_stash) HIPCHK(hipMalloc(&f->sig_stash, 2 * FSRL_MAX_ACT * 4));
-        if (!f->gsq_net) HIPCHK(hipMalloc(&f->gsq_net, FSRL_MAX_NETS * 4));
-        HIPCHK(hipMalloc(&f->psq, (size_t)2 * (nb_c0 + nb_c1) * 4));
-        HIPCHK(hipMalloc(&f->gsq, (size_t)nb_a * 4));
-        f->cap_tiles = max_tiles; f->cap_psq = nb_c0 + nb_c1;
-    }
-    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-    const int npsq = nb_c0 + nb_c1, nb_all = nb_a + nb_c0 + nb_c1;
-    auto step_args = [&]() {
-        FocopsStepArgs sa{};
-        sa.P = c->P; sa.M = c->M; sa.V = c->V; sa.stride = c->n_dev;
-        sa.G = c->G; sa.gsq = f->gsq; sa.psq = f->psq + (size_t)f->pp * npsq; sa.sig_stash = f->sig_stash + f->pp * FSRL_MAX_ACT;
-        sa.psq_next = f->psq + (size_t)(f->pp ^ 1) * npsq; sa.sig_next = f->sig_stash + (f->pp ^ 1) * FSRL_MAX_ACT;
-        sa.nb_a = nb_a; sa.nb_c0 = nb_c0; sa.nb_c1 = nb_c1; sa.max_norm = f->cfg.max_grad_norm; sa.l2 = f->cfg.l2_reg;
-        sa.one_minus_b1 = (float)(1.0 - b1); sa.beta2 = c->cfg.beta2; sa.one_minus_b2 = (float)(1.0 - b2);
-        sa.adam_eps = c->cfg.adam_eps;
-        return sa;
-    };
+    int rc0 = focops_alloc(c);
+    if (rc0) return rc0;
+    int nb_a, nb_c0, nb_c1;
+    focops_blocks(c, &nb_a, &nb_c0, &nb_c1);
+    const int nb_all = nb_a + nb_c0 + nb_c1;
+    auto step_args = [&]() { return focops_step_args(c, f->pp); };
     // A minibatch step is THREE launches when its rows fit ppo_wgrad_kernel's one-workgroup-per-output-tile layout (<= 512 rows:
     // every batch size up to 256 incl. its merged last minibatch): the activation side of all three networks (actor: FOCOPS
     // loss head, critics: regression head), ppo_wgrad_kernel (final gradients + per-block squared norms, no split-K partials
@@ -104,12 +182,7 @@ static int focops_pass(fsrl_ctx* c, int32_t* stopped_out) {
     for (int mb = 0; mb < nmb; ++mb) {
         const int start = c->mb_start[(size_t)mb], size = c->mb_size[(size_t)mb];
         const int tiles = (size + 15) / 16, rows_pad = tiles * 16;
-        FbArgs a{};
-        a.obs = c->obs_p + (size_t)start * Do; a.rd = c->rd_p + (size_t)start * FSRL_RD;
-        a.A1 = c->A1; a.A2 = c->A2; a.D1 = c->D1; a.D2 = c->D2; a.DO = c->DO;
-        a.N = size; a.rows_pad = rows_pad; a.max_action = c->cfg.max_action;
-        a.cr = 1.0f / f->cfg.tem_lambda; a.cc = (float)f->nu; a.eta = f->cfg.eta;
-        a.mode = FB_MODE_FOCOPS; a.net0 = 0; a.statp = f->statp_pi;      // [tiles][3][FB_NSTAT]
+        FbArgs a = focops_tile_args(c, start, size);
         const bool rows4 = !layered && 4 * tiles * 3 <= c->n_cus;
         int rc = 0;
         if (layered) {
@@ -135,11 +208,7 @@ static int focops_pass(fsrl_ctx* c, int32_t* stopped_out) {
         FocopsStepArgs sa = step_args();
         const int pb = wg_blocks_per_net(H);                  // ppo_wgrad_kernel: tile + aux blocks per network
         if (fast_pass) {
-            WgradPtrs wp{};
-            wp.A1 = c->A1; wp.A2 = c->A2; wp.D1 = c->D1; wp.D2 = c->D2; wp.DO = c->DO; wp.X = a.obs; wp.grad = c->G;
-            wp.gsq_part = c->gsq_part; wp.ctrl = c->ctrl; wp.mbp_max = rows_pad;     // the tile kernel laid network y out at y * rows_pad
-            wp.P = c->P; wp.statp = nullptr; wp.stats = nullptr;                      // no PPO row: focops_step_kernel's extra block logs
-            wp.gsq_net = f->gsq_net;
+            const WgradPtrs wp = focops_wgrad_ptrs(c, a.obs, rows_pad);
             const PpoStepArgs none{};
             rc = dispatch_H(H, [&](auto hc) {
                 constexpr int HH = decltype(hc)::value;
@@ -153,36 +222,13 @@ static int focops_pass(fsrl_ctx* c, int32_t* stopped_out) {
         } else if (layered) {
             sa.parts = c->G; sa.nparts = 1;          // lay_bwd left the whole gradient in G
         } else {
-            FbWgradArgs wa{};
-            for (int y = 0; y < 3; ++y) {
-                const size_t nb = (size_t)y * rows_pad;
-                FbWgradNet& wn = wa.nets[y];
-                wn.w2_ya = c->D2 + nb * H; wn.w2_xa = c->A1 + nb * H; wn.w1_y = c->D1 + nb * H;
-                wn.w3_xa = c->A2 + nb * H; wn.w3_ya = c->DO + nb * FSRL_DOW;
-                wn.b1_src = c->D1 + nb * H; wn.b2_src = c->D2 + nb * H; wn.do_src = c->DO + nb * FSRL_DOW;
-                wn.net = y;
-            }
-            wa.obs = a.obs; wa.rows = rows_pad; wa.N = size;
+            FbWgradArgs wa = focops_split_args(c, a.obs, size, rows_pad);
             int nsplit = 1;
             rc = wgrad_launch<false>(c, c->md, wa, 3, c->n_dev, &nsplit);
             if (rc) return rc;
             sa.parts = c->wg_parts; sa.nparts = nsplit;
         }
-        f->t_critic += 1; f->t_actor += 1;
-        sa.step_a = (float)((double)f->cfg.actor_lr / (1.0 - std::pow(b1, (double)f->t_actor)));
-        sa.bc2s_a = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_actor));
-        sa.step_c = (float)((double)f->cfg.critic_lr / (1.0 - std::pow(b1, (double)f->t_critic)));
-        sa.bc2s_c = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_critic));
-        // ---- logged row, pass KL sum, pass-level early stop flag (the extra block of the step launch)
-        FocopsFinalArgs& fa = sa.fin;
-        fa.statp_vf = f->statp_pi + FB_NSTAT; fa.statp_pi = f->statp_pi; fa.vf_stride = 3; fa.pi_stride = 3;
-        fa.psq0 = sa.psq; fa.psq1 = sa.psq + nb_c0; fa.n_psq0 = nb_c0; fa.n_psq1 = nb_c1;
-        fa.P = sa.sig_stash; fa.sigma_off = 0; fa.Da = c->cfg.act_dim;          // entropy of the PRE-update policy
-        fa.stats = c->d_stats + (size_t)(c->n_steps + mb) * FSRL_PPO_NSTATS; fa.ctrl = c->ctrl;
-        fa.n_tiles = rows4 ? 4 * tiles : tiles; fa.n_tiles_pi = fa.n_tiles; fa.mb = size;
-        fa.first_in_pass = mb == 0; fa.last_in_pass = mb == nmb - 1;
-        fa.iters_in_pass = nmb; fa.pass = (int)c->pass_index; fa.l2 = f->cfg.l2_reg; fa.nu_loss = (float)f->nu_loss;
-        fa.nu_value = (float)f->nu; fa.delta = f->cfg.delta;
+        focops_step_fill(c, sa, c->n_steps + mb, mb, nmb, size, rows4 ? 4 * tiles : tiles);
         if (!fast_pass) hipLaunchKernelGGL(focops_prep_kernel, dim3(nb_all), dim3(256), 0, s, c->md, sa);
         hipLaunchKernelGGL(focops_step_kernel, dim3(nb_all + 1), dim3(256), 0, s, c->md, sa);
         HIPCHK(hipGetLastError());

@@ -1,0 +1,216 @@
+// host_focops_group.inc -- grouped FOCOPS updates: fsrl_group_create / fsrl_group_ppo_update for a group of FOCOPS contexts
+// (part of fsrl_hip.hip, kernels: kernels_focops_group.hpp).  k x Engine.focops_update in lock step: begin -> per pass
+// ppo_pass_prepare of every member -> the minibatch steps, every launch carrying all members still active -> end.  Each
+// member keeps its own nu / nu_loss (fsrl_focops_set_nu), Adam counters, psq / sig_stash parity, store, statistics rows
+// and KL early stop (the `delta` check, always watched: a member that stops sits the later passes out).
+// Bit-identity with focops_pass: the step table holds exactly the arguments focops_pass builds for the member's minibatch
+// (the same host helpers, host_focops.inc), each member keeps its own three- or four-launch plan, and the kernels run the
+// single-context bodies.  The tile height of a launch is the PPO group's rule (4-row tiles only while every active member
+// fits one round of workgroups), so a group of one is bit-identical to its solo run, and larger groups are wherever the tile
+// height does not change (tests/test_gpu_group_focops.py).
+// ====================================================================================== grouped FOCOPS
+
+// what grouped FOCOPS needs of its members beyond fsrl_group_create's shape / PPO checks; run at create and at every
+// update, since fsrl_focops_init / _set_plan can be called again in between
+static int focops_group_check(fsrl_ctx* const* ctxs, int k) {
+    const fsrl_ctx* c0 = ctxs[0];
+    for (int i = 0; i < k; ++i) {
+        const fsrl_ctx* c = ctxs[i];
+        CHECK_ARG(c->foc, "member %d: fsrl_focops_init first (a grouped FOCOPS member needs its FOCOPS configuration)", i);
+        CHECK_ARG(!c->lay, "member %d is a layered context: grouped FOCOPS runs the fused kernels (two hidden layers)", i);
+        CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256),
+                  "member %d: fsrl_tr_set_plan's streaming weight-gradient plan is not grouped", i);
+        const fsrl_focops_config &a = c->foc->cfg, &b = c0->foc->cfg;
+        CHECK_ARG(a.l2_reg == b.l2_reg && a.delta == b.delta && a.eta == b.eta && a.tem_lambda == b.tem_lambda &&
+                  a.max_grad_norm == b.max_grad_norm,
+                  "member %d: members must share l2_reg, delta, eta, tem_lambda and max_grad_norm (learning rates may differ)", i);
+        CHECK_ARG(c->foc->no_fast == c0->foc->no_fast, "member %d: members must agree on fsrl_focops_set_plan", i);
+    }
+    return 0;
+}
+
+static int focops_group_ensure_steps(fsrl_group* g, size_t nmb) {
+    const size_t k = g->m.size();
+    if (!g->d_ftab) {
+        HIPCHK(hipMalloc(&g->d_ftab, k * sizeof(FocGroupMember)));
+        HIPCHK(hipHostMalloc(&g->h_ftab, k * sizeof(FocGroupMember)));
+    }
+    if (nmb <= g->cap_fmb) return 0;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (g->d_fsteps) HIPCHK(hipFree(g->d_fsteps));
+    if (g->h_fsteps) HIPCHK(hipHostFree(g->h_fsteps));
+    g->d_fsteps = nullptr; g->h_fsteps = nullptr;
+    const size_t cap = nmb * 2, bytes = cap * k * sizeof(FocGroupStep);
+    HIPCHK(hipMalloc(&g->d_fsteps, bytes));
+    HIPCHK(hipHostMalloc(&g->h_fsteps, bytes));
+    g->cap_fmb = cap;
+    return 0;
+}
+
+static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
+                               float* const* stats_out, int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
+    const int k = (int)g->m.size();
+    int rc = focops_group_check(g->m.data(), k);
+    if (rc) return rc;
+    group_actor_release(g);                     // the update goes behind the collect kernel, which ends
+    fsrl_ctx* c0 = g->m[0];
+    for (fsrl_ctx* m : g->m) m->theta_version += 1;
+    HIPCHK(hipSetDevice(c0->device));
+    hipStream_t s = g->stream;
+    const int H = c0->cfg.hidden, nn = 3;
+    auto abort_all = [&](int rc_) { for (fsrl_ctx* c : g->m) c->in_update = false; return rc_; };
+    // ---- begin: sample(0) + process_fn of every member (FOCOPS: no multipliers, rescaling 1, as Engine.focops_update)
+    const double zero_lag[FSRL_MAX_CRITICS] = {};
+    std::vector<int64_t> n((size_t)k, 0);
+    for (int i = 0; i < k; ++i) {
+        rc = fsrl_ppo_begin(g->m[i], zero_lag, 1.0, batch_size, &n[i]);
+        if (rc) return abort_all(rc);
+        if (stopped_pass_out) stopped_pass_out[i] = -1;
+    }
+    std::vector<char> active((size_t)k, 1), fast((size_t)k, 0);
+    for (int i = 0; i < k; ++i) {
+        fsrl_ctx* c = g->m[i];
+        if (n[i] == 0) { active[(size_t)i] = 0; continue; }
+        rc = focops_alloc(c);                   // the members' working sets before the first grouped pass
+        if (rc) return abort_all(rc);
+        fast[(size_t)i] = !c->foc->no_fast && c->mbp_max <= 512;
+    }
+    size_t cap_nmb = 0;
+    for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
+    rc = focops_group_ensure_steps(g, std::max<size_t>(cap_nmb, 1));
+    if (rc) return abort_all(rc);
+    int nb_a, nb_c0, nb_c1;
+    focops_blocks(c0, &nb_a, &nb_c0, &nb_c1);
+    const int nb_all = nb_a + nb_c0 + nb_c1;
+    // fb_wgrad_kernel's plan in wgrad_launch (PAIR2 = false): blocks of one split and network
+    const int passes = 1 + std::max(0, (c0->md.Do - 16 * 2 + 63) / 64);
+    const int NB = (H / 64) * (H / 64) + (H / FB_AUX_COLS) * passes + 1;
+    std::vector<char> rows4;
+    for (int pass = 0; pass < repeat; ++pass) {
+        int n_act = 0;
+        for (int i = 0; i < k; ++i) n_act += active[(size_t)i] ? 1 : 0;
+        if (n_act == 0) break;
+        size_t max_nmb = 0;
+        for (int i = 0; i < k; ++i) if (active[(size_t)i]) max_nmb = std::max(max_nmb, g->m[i]->mb_start.size());
+        // the pinned tables of the previous pass must have left host memory before they are rewritten
+        if (g->steps_in_flight) { HIPCHK(hipEventSynchronize(g->steps_copied)); g->steps_in_flight = false; }
+        // ---- per member: permutation + batch preparation of this pass; split-K buffers for its largest minibatch
+        for (int i = 0; i < k; ++i) {
+            if (!active[(size_t)i]) continue;
+            fsrl_ctx* c = g->m[i];
+            rc = ppo_pass_prepare(c, perms ? perms[i] + (size_t)pass * (size_t)n[i] : nullptr, seed ? seed + 1000003ull * i + pass : 0);
+            if (rc) return abort_all(rc);
+            if (!fast[(size_t)i]) {
+                int ns = 1;
+                for (int sz : c->mb_size) ns = std::max(ns, wgrad_plan((sz + 15) / 16 * 16, NB * nn, c->n_cus).nsplit);
+                rc = ensure_parts(c, c->n_dev, ns);
+                if (rc) return abort_all(rc);
+            }
+        }
+        // ---- tile height per minibatch step: the PPO group's rule over the members active in the pass
+        rows4.assign(max_nmb, 0);
+        for (size_t mb = 0; mb < max_nmb; ++mb) {
+            int tiles = 0;
+            for (int i = 0; i < k; ++i)
+                if (active[(size_t)i] && mb < g->m[i]->mb_size.size()) tiles = std::max(tiles, (g->m[i]->mb_size[mb] + 15) / 16);
+            rows4[mb] = (size_t)tiles * 4 * nn * n_act <= (size_t)c0->n_cus;
+        }
+        // ---- member table and step table of the pass: focops_pass's arguments, member by member
+        memset(g->h_fsteps, 0, max_nmb * k * sizeof(FocGroupStep));
+        for (int i = 0; i < k; ++i) {
+            fsrl_ctx* c = g->m[i];
+            FocGroupMember& t = g->h_ftab[i];
+            memset(&t, 0, sizeof(t));
+            t.P = c->P;
+            if (!active[(size_t)i]) continue;
+            FocState* f = c->foc;
+            t.fast = fast[(size_t)i];
+            t.pass_prep = focops_step_args(c, f->pp);
+            t.pass_prep.nparts = 0;
+            const int nmb = (int)c->mb_start.size();
+            for (size_t mb = 0; mb < max_nmb; ++mb) {
+                if ((int)mb >= nmb) break;
+                FocGroupStep& st = g->h_fsteps[mb * k + i];
+                const int start = c->mb_start[mb], size = c->mb_size[mb];
+                const int tiles = (size + 15) / 16, rows_pad = tiles * 16;
+                st.active = 1;
+                st.n_tiles = rows4[mb] ? 4 * tiles : tiles;
+                st.rows_pad = rows_pad;
+                st.fb = focops_tile_args(c, start, size);
+                st.sa = focops_step_args(c, f->pp);
+                if (t.fast) {
+                    st.wp = focops_wgrad_ptrs(c, st.fb.obs, rows_pad);
+                    st.sa.nparts = 0; st.sa.parts = nullptr;
+                    st.sa.gsq_part = c->gsq_part; st.sa.n_gsq_part = wg_blocks_per_net(H); st.sa.gsq_net = f->gsq_net;
+                } else {
+                    FbWgradArgs& wa = st.wa;
+                    wa = focops_split_args(c, st.fb.obs, size, rows_pad);
+                    const WgradPlan pl = wgrad_plan(rows_pad, NB * nn, c->n_cus);
+                    wa.out = c->wg_parts; wa.ks_per_split = pl.ks_per_split; wa.split_stride = c->n_dev;
+                    wa.dbg_skip = c->probe_wgrad_skip; wa.aux_passes = passes;
+                    wa.remap_total = NB * nn * pl.nsplit; wa.remap_ny = nn;
+                    st.sa.parts = c->wg_parts; st.sa.nparts = pl.nsplit;
+                }
+                focops_step_fill(c, st.sa, c->n_steps + (int64_t)mb, (int)mb, nmb, size, st.n_tiles);
+                f->pp ^= 1;
+            }
+        }
+        HIPCHK(hipMemcpyAsync(g->d_ftab, g->h_ftab, (size_t)k * sizeof(FocGroupMember), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->d_fsteps, g->h_fsteps, max_nmb * k * sizeof(FocGroupStep), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(g->steps_copied, s));
+        g->steps_in_flight = true;
+        // ---- the pass: one pass-start prep for the three-launch members, then per minibatch step 3 or 4 launches for all
+        bool any_fast = false;
+        for (int i = 0; i < k; ++i) any_fast = any_fast || (active[(size_t)i] && fast[(size_t)i]);
+        if (any_fast)
+            hipLaunchKernelGGL((focops_prep_group_kernel<1>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->d_ftab, g->d_fsteps);
+        for (size_t mb = 0; mb < max_nmb; ++mb) {
+            const FocGroupStep* hst = g->h_fsteps + mb * k;
+            const FocGroupStep* st = g->d_fsteps + mb * k;
+            int tiles = 0, remap = 0;
+            bool f3 = false, f4 = false;
+            for (int i = 0; i < k; ++i) {
+                if (!hst[i].active) continue;
+                tiles = std::max(tiles, hst[i].n_tiles);
+                if (fast[(size_t)i]) f3 = true;
+                else { f4 = true; remap = std::max(remap, hst[i].wa.remap_total); }
+            }
+            if (tiles == 0) continue;                            // no active member has a minibatch at this index
+            rc = dispatch_H(H, [&](auto hc) {
+                constexpr int HH = decltype(hc)::value;
+                if (rows4[mb]) hipLaunchKernelGGL((focops_tile_group_kernel<HH, 4>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->d_ftab, st);
+                else hipLaunchKernelGGL((focops_tile_group_kernel<HH, 16>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->d_ftab, st);
+                if (f3) hipLaunchKernelGGL((focops_wgrad_group_kernel<HH>), dim3(wg_grid(HH, nn), k), dim3(1024), 0, s, c0->md, g->d_ftab, st);
+                if (f4) hipLaunchKernelGGL((focops_wgrad_split_group_kernel<HH>), dim3(round_up(remap, 8), k), dim3(1024), 0, s, c0->md,
+                                           g->d_ftab, st);
+                return 0;
+            });
+            if (rc) return abort_all(rc);
+            if (f4) hipLaunchKernelGGL((focops_prep_group_kernel<0>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->d_ftab, st);
+            hipLaunchKernelGGL(focops_step_group_kernel, dim3(nb_all + 1, k), dim3(256), 0, s, c0->md, st);
+            HIPCHK(hipGetLastError());
+        }
+        for (int i = 0; i < k; ++i) {
+            if (!active[(size_t)i]) continue;
+            fsrl_ctx* c = g->m[i];
+            c->n_steps += (int64_t)c->mb_start.size();
+            c->pass_index += 1;
+        }
+        // ---- pass-level KL early stop per member (focops_pass's verdict, always watched): one readback per pass for the group
+        for (int i = 0; i < k; ++i)
+            if (active[(size_t)i]) HIPCHK(hipMemcpyAsync(g->m[i]->h_ctrl, g->m[i]->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int i = 0; i < k; ++i) {
+            if (active[(size_t)i] && g->m[i]->h_ctrl->stopped_after != INT_MAX) {
+                active[(size_t)i] = 0;
+                if (stopped_pass_out) stopped_pass_out[i] = pass;
+            }
+        }
+    }
+    // ---- end: statistics of every member
+    for (int i = 0; i < k; ++i) {
+        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, cap_steps, n_steps_out ? n_steps_out + i : nullptr);
+        if (rc) return abort_all(rc);
+    }
+    return 0;
+}

@@ -4,6 +4,7 @@
 // only when the launch shapes agree (a group of ONE with at most 512 rows per minibatch): the group picks its tile height
 // from the number of active members and the largest member, and above 512 rows it keeps the in-kernel reduction where the
 // single path goes through the split-K kernels.  Otherwise: the golden tests' tolerances (tests/test_gpu_group.py).
+// A group of FOCOPS contexts runs the same entry points through host_focops_group.inc (one algorithm per group).
 // ====================================================================================== groups
 #define FSRL_MAX_GROUP 16
 
@@ -17,6 +18,10 @@ struct fsrl_group {
     hipEvent_t steps_copied = nullptr; bool steps_in_flight = false;
     bool broken = false;                        // a member was destroyed: no more updates
     int tall_tiles = -1;                        // fsrl_group_set_plan: 32-row tiles per (member, network) of the forward / backward launch
+    // FOCOPS groups (host_focops_group.inc): member table and [cap_fmb][k] step table
+    FocGroupMember* d_ftab = nullptr; FocGroupMember* h_ftab = nullptr;
+    FocGroupStep* d_fsteps = nullptr; FocGroupStep* h_fsteps = nullptr;
+    size_t cap_fmb = 0;
     // lock-step collection (host_group_collect.inc): ONE resident actor kernel for every member, rung through ONE doorbell
     bool ga_on = true;                          // fsrl_group_actor_set_resident
     bool ga_live = false;                       // a kernel of generation ga_gen was launched and not told to end
@@ -37,8 +42,10 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
     for (int i = 0; i < k; ++i) {
         const fsrl_ctx* c = ctxs[i];
         CHECK_ARG(c, "null member");
-        CHECK_ARG(c->cfg.algo == FSRL_ALGO_PPO_LAG, "grouped updates are PPO-Lagrangian contexts");
-        CHECK_ARG(!c->lay, "grouped updates run the fused kernels: two hidden layers of at most 256 units");
+        CHECK_ARG(c->cfg.algo == FSRL_ALGO_PPO_LAG || c->cfg.algo == FSRL_ALGO_FOCOPS,
+                  "member %d: grouped updates are PPO-Lagrangian or FOCOPS contexts", i);
+        CHECK_ARG(c->cfg.algo == c0->cfg.algo, "member %d: a group has one algorithm (all PPO-Lagrangian or all FOCOPS members)", i);
+        CHECK_ARG(!c->lay, "member %d is a layered context: grouped updates run the fused kernels (two hidden layers of at most 256 units)", i);
         CHECK_ARG(c->device == c0->device, "members live on one device");
         CHECK_ARG(!c->in_update && !c->group, "member %d is inside an update or already grouped", i);
         const fsrl_config &a = c->cfg, &b = c0->cfg;
@@ -51,6 +58,10 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
                   a.rew_norm == b.rew_norm && a.value_clip == b.value_clip,
                   "members must share the PPO hyper-parameters (learning rates, seeds and data may differ)");
         for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member listed twice");
+    }
+    if (c0->cfg.algo == FSRL_ALGO_FOCOPS) {
+        int rc = focops_group_check(ctxs, k);
+        if (rc) return rc;
     }
     HIPCHK(hipSetDevice(c0->device));
     for (int i = 0; i < k; ++i) pactor_release(ctxs[i]);      // members share the group's stream from here on: no resident actors (pactor_ok)
@@ -111,6 +122,10 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (g->h_steps) (void)hipHostFree(g->h_steps);
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
     if (g->h_ga) (void)hipHostFree(g->h_ga);
+    if (g->d_ftab) (void)hipFree(g->d_ftab);
+    if (g->h_ftab) (void)hipHostFree(g->h_ftab);
+    if (g->d_fsteps) (void)hipFree(g->d_fsteps);
+    if (g->h_fsteps) (void)hipHostFree(g->h_fsteps);
     delete g;
     return 0;
 }
@@ -140,12 +155,16 @@ static int group_ensure_steps(fsrl_group* g, size_t nmb) {
 
 // k x BasePolicy.update (base_policy.py:332-355) in lock step.  lagrangians: [k][n_critics - 1]; rescaling: [k];
 // perms: NULL (library shuffles) or k pointers, member i's = [repeat][n_i]; stats_out: k pointers or NULL.
+// A FOCOPS group: k x Engine.focops_update (lagrangians / rescaling ignored, host_focops_group.inc).
 extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, const double* rescaling, int32_t batch_size,
                                      int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
                                      int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
-    CHECK_ARG(g && rescaling, "null argument");
+    CHECK_ARG(g, "null argument");
     CHECK_ARG(repeat >= 0, "repeat must be >= 0");
     if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
+    if (g->m[0]->cfg.algo == FSRL_ALGO_FOCOPS)
+        return focops_group_update(g, batch_size, repeat, perms, seed, stats_out, cap_steps, n_steps_out, stopped_pass_out);
+    CHECK_ARG(rescaling, "null argument");
     group_actor_release(g);                     // the update goes behind the collect kernel, which ends
     const int k = (int)g->m.size();
     fsrl_ctx* c0 = g->m[0];

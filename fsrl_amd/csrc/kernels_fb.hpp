@@ -1880,18 +1880,19 @@ struct FocopsStepArgs {
     float step_a, bc2s_a, step_c, bc2s_c;    // lr / (1 - beta1^t), sqrt(1 - beta2^t) of the two optimisers
     FocopsFinalArgs fin;                     // the logged row / pass KL bookkeeping (done by the extra block of the step)
 };
-__device__ __forceinline__ void focops_block(const ModelDesc& md, const FocopsStepArgs& a, int& net, int& i) {
-    int b = blockIdx.x;
+__device__ __forceinline__ void focops_block(const ModelDesc& md, const FocopsStepArgs& a, const int bx, int& net, int& i) {
+    int b = bx;
     net = 0;
     if (b >= a.nb_a) { b -= a.nb_a; net = 1; if (b >= a.nb_c0) { b -= a.nb_c0; net = 2; } }
     i = md.net[net].begin + b * 256 + threadIdx.x;
 }
 // prep: actor blocks add the split-K partials in z order (-> G) and leave per-block sums of squares (clip_grad_norm_ over
-// the actor); critic blocks leave per-block sums of squares of their parameters (the L2 term of the logged loss).
-__global__ __launch_bounds__(256) void focops_prep_kernel(const ModelDesc md, const FocopsStepArgs a) {
+// the actor); critic blocks leave per-block sums of squares of their parameters (the L2 term of the logged loss).  bx: the block
+// index (the grouped update, kernels_focops_group.hpp, runs the body per member).
+__device__ __forceinline__ void focops_prep_body(const ModelDesc& md, const FocopsStepArgs& a, const int bx) {
     __shared__ float sh[4];
     int net, i;
-    focops_block(md, a, net, i);
+    focops_block(md, a, bx, net, i);
     float q = 0.0f;
     if (i < md.net[net].end) {
         if (net == 0) {
@@ -1906,27 +1907,30 @@ __global__ __launch_bounds__(256) void focops_prep_kernel(const ModelDesc md, co
             q = p * p;
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x < md.Da) a.sig_stash[threadIdx.x] = a.P[md.net[0].sigma + threadIdx.x];
+    if (bx == 0 && threadIdx.x < md.Da) a.sig_stash[threadIdx.x] = a.P[md.net[0].sigma + threadIdx.x];
     q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = q;
     __syncthreads();
     if (threadIdx.x == 0) {
         const float t = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-        if (net == 0) a.gsq[blockIdx.x] = t; else a.psq[blockIdx.x - a.nb_a] = t;
+        if (net == 0) a.gsq[bx] = t; else a.psq[bx - a.nb_a] = t;
     }
 }
+__global__ __launch_bounds__(256) void focops_prep_kernel(const ModelDesc md, const FocopsStepArgs a) {
+    focops_prep_body(md, a, (int)blockIdx.x);
+}
 // step: Adam of the actor (clipped to max_norm) and of both critics (L2 inside the gradient) in one launch; one extra
-// block writes the logged row from the per-tile statistics, the parameter sums and the stashed sigma_param.
-__global__ __launch_bounds__(256) void focops_step_kernel(const ModelDesc md, const FocopsStepArgs a) {
+// block writes the logged row from the per-tile statistics, the parameter sums and the stashed sigma_param.  bx: the block index.
+__device__ __forceinline__ void focops_step_body(const ModelDesc& md, const FocopsStepArgs& a, const int bx) {
     __shared__ double shd[4];
     __shared__ float coef_s;
     __shared__ float shq[4];
-    if ((int)blockIdx.x == a.nb_a + a.nb_c0 + a.nb_c1) {
+    if (bx == a.nb_a + a.nb_c0 + a.nb_c1) {
         if (threadIdx.x < 64) focops_finalize_row(a.fin, threadIdx.x);
         return;
     }
     int net, i;
-    focops_block(md, a, net, i);
+    focops_block(md, a, bx, net, i);
     float coef = 1.0f;
     if (net == 0 && a.max_norm > 0.0f) {     // same reduction order as adam_range_kernel's clip
         double sq = 0.0;
@@ -1962,8 +1966,11 @@ __global__ __launch_bounds__(256) void focops_step_kernel(const ModelDesc md, co
         float q = wave_sum(pn * pn);
         if ((threadIdx.x & 63) == 0) shq[threadIdx.x >> 6] = q;
         __syncthreads();
-        if (threadIdx.x == 0) a.psq_next[blockIdx.x - a.nb_a] = (shq[0] + shq[1]) + (shq[2] + shq[3]);
+        if (threadIdx.x == 0) a.psq_next[bx - a.nb_a] = (shq[0] + shq[1]) + (shq[2] + shq[3]);
     }
+}
+__global__ __launch_bounds__(256) void focops_step_kernel(const ModelDesc md, const FocopsStepArgs a) {
+    focops_step_body(md, a, (int)blockIdx.x);
 }
 
 // full-batch advantage normalisation (CPO cpo.py:127-131, TRPO trpo_lag.py:129-133): per critic

@@ -1,4 +1,4 @@
-"""Lock-step collection for the members of a grouped PPO-Lagrangian run (multi-seed on one GPU).
+"""Lock-step collection for the members of a grouped PPO-Lagrangian or FOCOPS run (multi-seed on one GPU).
 
 `GroupCollector(policy_group, collectors).collect(n_episode)` is `collector.collect(n_episode)` of every member, with the members'
 vector envs stepped in lock step and ONE library call per vector step for all of them (`EngineGroup.collect_step` ->

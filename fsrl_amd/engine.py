@@ -710,9 +710,9 @@ class Engine:
 
 
 class EngineGroup:
-    """k PPO-Lagrangian engines of one network shape on one GPU, updated in lock step (fsrl_group_*): every launch of
-    the minibatch step carries all members.  Members keep their own store, parameters and random streams; use the
-    engines as usual for everything else (push, collect_step, get_params ...)."""
+    """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
+    (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
+    random streams; use the engines as usual for everything else (push, collect_step, get_params ...)."""
 
     def __init__(self, engines):
         self.engines = list(engines)
@@ -836,6 +836,16 @@ class EngineGroup:
         for e, n in zip(self.engines, sizes):
             e._n = n
         return [s[:int(n)] for s, n in zip(stats, nst)], [int(x) for x in stop]
+
+    def focops_update(self, nus, nu_losses, batch_size, repeat, perms=None, seed=0):
+        """k x Engine.focops_update (a group of FOCOPS engines): member i's nu / nu_loss set, then ONE grouped update.
+        -> (list of stats arrays [steps_i, 8] as Engine.focops_update, list of stopped passes (-1 = none))."""
+        k = len(self.engines)
+        assert len(nus) == k and len(nu_losses) == k, "one nu and one nu_loss per member"
+        for e, nu, nl in zip(self.engines, nus, nu_losses):
+            _lib.check(self.lib.fsrl_focops_set_nu(e._ctx, float(nu), float(nl)))
+        stats, stopped = self.ppo_update(np.zeros((k, 1)), np.ones(k), batch_size, repeat, perms=perms, seed=seed)
+        return [s[:, :_lib.FOCOPS_NSTATS] for s in stats], stopped
 
 
 class EngineSacGroup:

@@ -47,16 +47,22 @@ class FOCOPS(BasePolicy):
     def update_cost_limit(self, cost_limit: float) -> None:
         self.cost_limit = cost_limit
 
+    def nu_step(self) -> Tuple[float, float]:
+        """focops.py:155-158, float32 tensor arithmetic: one step of nu -> (nu, nu_loss) for `fsrl_focops_set_nu`.
+        process_fn and the grouped update (PolicyGroup) both take it from here."""
+        loss_nu = self.cost_limit - self._ave_cost_return
+        self._nu = self._nu + (-self._nu_lr * loss_nu)
+        self._nu = torch.clamp(self._nu, 0, self._nu_max)
+        return float(self._nu), float(loss_nu)
+
     def process_fn(self, batch=None, buffer=None, indices=None, batch_size: int = 256):
         """focops.py:126-153 on the device: the nu step (:155-158, host float32) + `fsrl_ppo_begin` (sample(0), V / GAE per critic,
         logp_old, mean_old / std_old).  -> DeviceBatch; `batch` / `indices` ignored (the on-policy batch is the whole store)."""
         assert getattr(buffer, "engine", None) is self.engine
         self.updating = True
-        loss_nu = self.cost_limit - self._ave_cost_return            # focops.py:155-158, float32 tensor arithmetic
-        self._nu = self._nu + (-self._nu_lr * loss_nu)
-        self._nu = torch.clamp(self._nu, 0, self._nu_max)
+        nu, loss_nu = self.nu_step()
         eng = self.engine
-        _lib.check(eng.lib.fsrl_focops_set_nu(eng._ctx, float(self._nu), float(loss_nu)))
+        _lib.check(eng.lib.fsrl_focops_set_nu(eng._ctx, nu, loss_nu))
         n = eng.ppo_begin([0.0], 1.0, batch_size)
         try:
             if self._reference_rng and (self.training or not self._deterministic_eval):
@@ -103,6 +109,11 @@ class FOCOPS(BasePolicy):
             eng.ppo_abort()
             self.updating = False
             raise
+        return self.log_learn(stats, stopped_at)
+
+    def log_learn(self, stats, stopped_at: int) -> Dict[str, int]:
+        """learn()'s bookkeeping after the device update (the grouped update, PolicyGroup, does the same per member): the
+        FOCOPS_KEYS rows, gradient_steps, stale host mirrors.  stats: [steps, FOCOPS_NSTATS]."""
         table = getattr(self.logger, "store_rows", None)         # fsrl_amd loggers take the per-step table at once
         if table is not None:
             table(FOCOPS_KEYS, stats)

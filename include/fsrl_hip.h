@@ -281,7 +281,7 @@ int fsrl_ppo_update(fsrl_ctx* ctx, const double* lagrangians, double rescaling,
  * ~1 360 rows with three networks), 0 none, n > 0 min(n, tiles / 2).  Needs hidden >= 128 and obs_dim <= 64.                        */
 int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
 
-/* ---- grouped updates: k independent PPO-Lagrangian agents of ONE network shape on one GPU, stepped in lock step
+/* ---- grouped updates: k independent PPO-Lagrangian agents, or k FOCOPS agents, of ONE network shape on one GPU, stepped in lock step
  *      (multi-seed runs; SURVEY 8e "within-GPU batching of k seeds").  The reference runs seeds as separate jobs; one
  *      agent's update is a chain of small dependent launches that leaves most of an MI355X idle, so k agents share every
  *      launch of the minibatch step (grid.y = member).  Per member the result is fsrl_ppo_update's on that member
@@ -289,7 +289,10 @@ int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
  *      minibatches of at most 512 rows): the group picks its tile height from the number of active members and keeps the
  *      in-kernel weight-gradient reduction above 512 rows.  Members keep their own store, parameters,
  *      Adam state and random streams; shape and PPO hyper-parameters must agree, batch sizes N_i may differ.
- *      While grouped, a member's own update calls still work (they run on the group's stream).                         */
+ *      While grouped, a member's own update calls still work (they run on the group's stream).
+ *      A group has one algorithm.  FOCOPS members (not layered) must have run fsrl_focops_init and share l2_reg, delta,
+ *      eta, tem_lambda, max_grad_norm and fsrl_focops_set_plan (learning rates may differ); checked again at every update.
+ *      Per FOCOPS member the result is bit-identical to its own update wherever the group keeps the member's tile height.  */
 typedef struct fsrl_group fsrl_group;
 int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out);       /* 1 <= k <= 16; members are not owned   */
 int fsrl_group_destroy(fsrl_group* group);
@@ -300,7 +303,9 @@ int fsrl_group_destroy(fsrl_group* group);
 int fsrl_group_set_plan(fsrl_group* group, int32_t tall_tiles);
 /* k x BasePolicy.update (base_policy.py:332-355).  lagrangians [k][n_critics - 1], rescaling [k]; perms: NULL (library
  * shuffle, member i seeded by seed + 1000003 i + pass) or k pointers to [repeat][N_i]; stats_out: NULL or k pointers to
- * [cap_steps][FSRL_PPO_NSTATS]; n_steps_out [k]; stopped_pass_out [k] (-1 = ran every pass).                          */
+ * [cap_steps][FSRL_PPO_NSTATS]; n_steps_out [k]; stopped_pass_out [k] (-1 = ran every pass).
+ * A FOCOPS group: k x FOCOPS learn with each member's fsrl_focops_set_nu values; lagrangians and rescaling are ignored (may
+ * be NULL); the delta KL stop is always watched, and a member that stops sits out the later passes.                    */
 int fsrl_group_ppo_update(fsrl_group* group, const double* lagrangians, const double* rescaling, int32_t batch_size,
                           int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
                           int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
