@@ -71,11 +71,11 @@ class FOCOPSOracle(PPOLagOracle):
         self.nu = float(torch.clamp(nu, 0, self.fcfg.nu_max))
         return {"loss/nu_loss": loss_nu, "loss/nu_value": self.nu}
 
-    def step(self, pb, chunk):
+    def critics_loss(self, pb, chunk):
+        """-> (sum of both critics' losses incl. their l2 terms, logged critic stats) on the rows `chunk` (focops.py:161-177)"""
         c = self.fcfg
         idx = torch.as_tensor(np.asarray(chunk))
-        obs, act = pb["obs"][idx], pb["act"][idx]
-        # ---- critics
+        obs = pb["obs"][idx]
         total, sc = torch.zeros(1), {}
         for i in range(2):
             vf = (pb["rets"][idx][..., i] - self.value(i, obs)).pow(2).mean()
@@ -83,11 +83,13 @@ class FOCOPSOracle(PPOLagOracle):
                 vf = vf + p.pow(2).sum() * c.l2_reg
             total = total + vf
             sc["loss/vf" + str(i)] = vf.item()
-        self.critic_optim.zero_grad()
-        total.backward()
-        self.critic_optim.step()
-        sc["loss/vf_total"] = total.item()
-        # ---- actor
+        return total, sc
+
+    def policy_loss(self, pb, chunk):
+        """-> (masked FOCOPS loss, per-row KL(new || old), entropy) on the rows `chunk` (focops.py:179-203)"""
+        c = self.fcfg
+        idx = torch.as_tensor(np.asarray(chunk))
+        obs, act = pb["obs"][idx], pb["act"][idx]
         dist = self.actor_dist(obs)
         ent = dist.entropy().mean()
         ratio = (dist.log_prob(act) - pb["logp_old"][idx]).exp()
@@ -98,6 +100,18 @@ class FOCOPSOracle(PPOLagOracle):
                 a = advs[..., i]
                 advs[..., i] = (a - a.mean()) / a.std()
         loss = ((kl - 1 / c.tem_lambda * ratio * (advs[..., 0] - self.nu * advs[..., 1])) * (kl.detach() <= c.eta)).mean()
+        return loss, kl, ent
+
+    def step(self, pb, chunk):
+        c = self.fcfg
+        # ---- critics
+        total, sc = self.critics_loss(pb, chunk)
+        self.critic_optim.zero_grad()
+        total.backward()
+        self.critic_optim.step()
+        sc["loss/vf_total"] = total.item()
+        # ---- actor
+        loss, kl, ent = self.policy_loss(pb, chunk)
         self.actor_optim.zero_grad()
         loss.backward()
         if c.max_grad_norm:

@@ -188,3 +188,25 @@ def sac_full_case(name):
         g[f"theta_{key}0"] = synth_theta(int(g[f"theta_{key}_seed"]), shapes)
         assert np.array_equal(theta_checksum(g[f"theta_{key}0"]), g[f"theta_{key}0_checksum"])
     return g
+
+
+def focops_case(name):
+    """tests/golden/focops_<name>.npz -> (cfg, arrays).  The compact case (`wide`) stores neither its rollout nor theta0: they are
+    regenerated from the stored seeds (checksums stored), and its theta_final holds the actor in full and every
+    theta_final_stride-th entry of the critics.  theta_final_idx: the entries of the parameter vector theta_final holds."""
+    g = load_npz(f"focops_{name}.npz")
+    cfg = json.loads(str(g["cfg_json"]))
+    if "rollout_seed" in g:
+        arr, _ = full_rollout_arrays(g, cfg["obs_dim"], cfg["act_dim"])
+        g.update(arr)
+        shapes = [tuple(s) for s in json.loads(str(g["theta_shapes_json"]))]
+        g["theta0"] = synth_theta(int(g["theta_seed"]), shapes)
+        assert np.array_equal(theta_checksum(g["theta0"]), g["theta0_checksum"])
+    n = g["theta0"].size
+    if "theta_final_stride" in g:
+        nf = int(g["theta_final_n_full"])
+        g["theta_final_idx"] = np.concatenate([np.arange(nf), np.arange(nf, n, int(g["theta_final_stride"]))])
+    else:
+        g["theta_final_idx"] = np.arange(n)
+    assert g["theta_final"].size == g["theta_final_idx"].size
+    return cfg, g

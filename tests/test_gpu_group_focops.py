@@ -226,6 +226,59 @@ def test_ragged_members_an_empty_member_and_a_kl_stop(four_launch):
         e.close()
 
 
+GROUP_SHAPES = [  # Do, Da, hidden, rows per env of each member, batch, repeat
+    # 256 wide: 256-row minibatches take 4-row tiles solo and 16-row tiles in the group of three; 324 / 390 / 510-row merged ones
+    (33, 6, 256, ([300, 280], [200, 190], [260, 250]), 256, 2),
+    # minibatches over 512 rows: every member on the four-launch step, focops_wgrad_split_group_kernel; act_dim > 4
+    (20, 9, 128, ([700, 650], [560, 600], [900, 800]), 600, 2),
+]
+
+
+@pytest.mark.parametrize("Do,Da,h,member_rows,B,R", GROUP_SHAPES)
+def test_grouped_members_vs_their_own_fp32_oracle(Do, Da, h, member_rows, B, R):
+    """k = 3 members with ragged N, their own theta0, nu and permutations: each member's rows, stopped pass and parameters
+    against its own fp32 oracle run at test_gpu_focops_shapes.py's bars (not only against its solo run, which shares the HIP
+    kernels' arithmetic)"""
+    import torch
+    from fsrl_amd.engine import EngineGroup
+    from test_gpu_focops_shapes import _engine as engine_on, _oracle, _plan, _rollout, _theta0, check_update
+    torch.set_num_threads(4)
+    foc = dict(actor_lr=5e-4, critic_lr=1e-3, l2_reg=1e-3, delta=0.02, eta=0.02, tem_lambda=0.95, max_grad_norm=0.5)
+    k = len(member_rows)
+    engs, refs, nus, perms = [], [], [], []
+    for i, rows in enumerate(member_rows):
+        seed = 300 + 17 * i + Do
+        cols, data = _rollout(seed, rows, Do, Da, 45)
+        o = _oracle(Do, Da, h, **foc)
+        theta0 = _theta0(o, seed + 1)
+        o.set_params(theta0, nu=0.1 + 0.2 * i)
+        rng = np.random.default_rng(seed + 2)
+        perms.append([rng.permutation(len(data)) for _ in range(R)])
+        pb, orows, ostopped = o.update(data, 20.0 + 5 * i, B, R, perms[i])
+        want = np.array([[sn["loss/nu_loss"], sn["loss/nu_value"], sa["loss/actor_loss"], sa["loss/kl"], sa["loss/entropy"],
+                          sc["loss/vf0"], sc["loss/vf1"], sc["loss/vf_total"]] for sn, sa, sc in orows])
+        refs.append((pb, want, ostopped, o))
+        nus.append((want[0, 1], want[0, 0]))
+        e = engine_on(Do, Da, h, rows, cols, **foc)
+        e.set_params(theta0)
+        engs.append(e)
+    sizes = [sum(r) for r in member_rows]
+    assert len(set(sizes)) == k
+    exact = _exact([_chunks(n, B) for n in sizes], k)
+    if B <= 256:
+        assert not all(exact), exact                        # the group changes some member's tile height
+    else:
+        assert not any(_plan(h, n, B, 0)[0] for n in sizes)   # four-launch members
+    grp = EngineGroup(engs)
+    st, sp = grp.focops_update([x[0] for x in nus], [x[1] for x in nus], B, R, perms=perms)
+    for i in range(k):
+        pb, want, ostopped, o = refs[i]
+        check_update(st[i], sp[i], engs[i], None, want, ostopped, o)
+    grp.close()
+    for e in engs:
+        e.close()
+
+
 def test_refusals_name_their_reason():
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig, EngineGroup
