@@ -10,6 +10,7 @@ the seeds overlap; the Python collector loops take turns.
     python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag, FOCOPS and SAC-Lag
     python examples/train_multi_seed.py --algo focops --seeds 4 --epoch 2 --grouped
     python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped
+    python examples/train_multi_seed.py --algo cvpo --seeds 4 --epoch 2 --grouped
 
 --grouped: ONE thread; the seeds collect in lock step (fsrl_amd.data.GroupCollector -> fsrl_group_collect_step: one actor
 request per vector step for all seeds, served by one resident kernel) and their updates run in lock step through the grouped
@@ -20,6 +21,9 @@ with FOCOPS seeds (each seed's nu step, then one grouped FOCOPS update; tools/be
 --grouped --algo sacl: ONE thread; each seed collects with its own FastCollector (its resident device actor) and steps its PID
 multiplier, then ONE grouped update (fsrl_amd.policy.SACPolicyGroup -> fsrl_sac_group_update) runs round(update_per_step * n/st)
 updates per seed, every launch carrying all seeds (tools/bench_group_sac.py).
+--grouped --algo cvpo: the same loop with CVPO seeds (each seed's pre_update_fn resets its M-step multipliers, ONE grouped update
+through fsrl_amd.policy.CVPOPolicyGroup -> fsrl_cvpo_group_update, each seed's post_update_fn copies actor -> actor_old;
+tools/bench_group_cvpo.py).
 """
 import argparse
 import os
@@ -35,24 +39,26 @@ from fsrl_amd.utils import BaseLogger  # noqa: E402
 
 AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops": FOCOPSAgent, "sacl": SACLagAgent,
           "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}
+GROUPED_ALGOS = ("ppol", "focops", "sacl", "cvpo")      # what --grouped takes
 
 
-def run_grouped_sac(a):
-    """k SAC-Lag seeds, one host thread: every seed collects with its own collector and steps its PID multiplier, then ONE grouped
-    update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed)."""
+def run_grouped_replay(a):
+    """k SAC-Lag (CVPO) seeds, one host thread: every seed collects with its own collector and runs its pre_update_fn (SAC-Lag: the
+    PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped update runs each seed's
+    round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed), then each seed's post_update_fn."""
     from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
-    from fsrl_amd.policy import SACPolicyGroup
+    from fsrl_amd.policy import CVPOPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
-        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"sacl-s{seed}")
-        agent = SACLagAgent(env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
-                            training_num=a.envs)
+        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
+        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
+                               training_num=a.envs)
         agent.policy.train()
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
-    group = SACPolicyGroup([ag.policy for ag in agents])
+    group = (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in agents])
     update_per_step, t0, steps, updates = 0.2, time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -85,9 +91,9 @@ def run_grouped_sac(a):
 def run_grouped(a):
     """k PPO-Lag (FOCOPS) seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier (each
     seed's cost goes to its nu step), ONE grouped update."""
-    assert a.algo in ("ppol", "focops", "sacl"), "--grouped: PPO-Lagrangian, FOCOPS or SAC-Lagrangian"
-    if a.algo == "sacl":
-        return run_grouped_sac(a)
+    assert a.algo in GROUPED_ALGOS, "--grouped: PPO-Lagrangian, FOCOPS, SAC-Lagrangian or CVPO"
+    if a.algo in ("sacl", "cvpo"):
+        return run_grouped_replay(a)
     from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
     from fsrl_amd.policy import PolicyGroup
     agents, cols, bufs = [], [], []
@@ -135,7 +141,7 @@ def main():
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag: lock-step grouped updates from one thread")
+    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / CVPO: lock-step grouped updates from one thread")
     a = ap.parse_args()
     out, errs = {}, []
     if a.grouped:

@@ -118,6 +118,9 @@ SIGNATURES = {
     "fsrl_sac_group_create": (C.c_int, [_P(_ctx), C.c_int32, _P(_ctx)]),
     "fsrl_sac_group_destroy": (C.c_int, [_ctx]),
     "fsrl_sac_group_update": (C.c_int, [_ctx, C.c_int32, _i32, _d, _d]),
+    "fsrl_cvpo_group_create": (C.c_int, [_P(_ctx), C.c_int32, _P(_ctx)]),
+    "fsrl_cvpo_group_destroy": (C.c_int, [_ctx]),
+    "fsrl_cvpo_group_update": (C.c_int, [_ctx, C.c_int32, _i32]),
     "fsrl_gae_return": (C.c_int, [_ctx, _f, _f, _d, _u8, C.c_int64, C.c_double, C.c_double, _d]),
     "fsrl_nstep_return": (C.c_int, [_ctx, _d, _u8, C.c_int64, _f, _i64, C.c_int64, C.c_int64, C.c_double, C.c_int32, _d]),
     "fsrl_launch_floors": (C.c_int, [_ctx, C.c_int32, C.c_int32, _d]),

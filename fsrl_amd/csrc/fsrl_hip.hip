@@ -188,6 +188,7 @@ struct fsrl_ctx {
     unsigned long long* probe_ts = nullptr;   // probe builds: [1024][16] phase stamps of the last fused-kernel launch
     bool probe_tile16 = false;
     struct fsrl_sac_group* sac_group = nullptr;      // the grouped SAC-Lagrangian update this context is a member of (host_sac_group.inc)
+    struct fsrl_cvpo_group* cvpo_group = nullptr;    // the grouped CVPO update this context is a member of (host_cvpo_group.inc)
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
@@ -237,6 +238,7 @@ static int flush_stage(fsrl_ctx* c);
 static void pactor_release(fsrl_ctx* c);
 static void group_actor_release(fsrl_group* g);     // the group's resident actor (host_group_collect.inc): a member's stream is the group's
 static void sac_group_detach(fsrl_ctx* c);        // a member destroyed before its SAC group (host_sac_group.inc)
+static void cvpo_group_detach(fsrl_ctx* c);       // ... before its CVPO group (host_cvpo_group.inc)
 // grouped FOCOPS (host_focops_group.inc): the member checks of fsrl_group_create / _ppo_update, and the update itself
 static int focops_group_check(fsrl_ctx* const* ctxs, int k);
 static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
@@ -439,6 +441,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     (void)hipDeviceSynchronize();
     if (c->group) group_detach(c);          // a member destroyed before its group: take its own stream back
     if (c->sac_group) sac_group_detach(c);
+    if (c->cvpo_group) cvpo_group_detach(c);
     comm_free(c);
     tr_free(c);
     sac_free(c);
@@ -532,10 +535,13 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->h1 = h1_; c->h2 = h2_;
     c->device = device_id;
     c->n_cus = n_cus_probe > 0 ? n_cus_probe : 256;
+    // the one switch the shipped library reads: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
+    // run sixteen-row tiles from a few members on; a single context created under FSRL_TILE16 is their exact twin
+    // (tests/test_gpu_cvpo_group.py).  Results stay valid, a small batch only gets slower.
+    c->probe_tile16 = getenv("FSRL_TILE16") != nullptr;
 #ifdef FSRL_PROBES
     { const char* e = getenv("FSRL_DBG_PHASE"); c->probe_phase = e ? atoi(e) : 0; }
     { const char* e = getenv("FSRL_WGRAD_SKIP"); c->probe_wgrad_skip = e ? atoi(e) : 0; }
-    c->probe_tile16 = getenv("FSRL_TILE16") != nullptr;
     c->no_spin = getenv("FSRL_NO_SPIN") != nullptr;
     c->no_xcd_pair = getenv("FSRL_NO_XCD_PAIR") != nullptr;
     c->no_fuse_adam = getenv("FSRL_NO_FUSE_ADAM") != nullptr;
@@ -1480,6 +1486,8 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 
 #include "kernels_sac_group.hpp"
 #include "host_sac_group.inc"
+#include "kernels_cvpo_group.hpp"
+#include "host_cvpo_group.inc"
 
 #include "host_comm.inc"
 

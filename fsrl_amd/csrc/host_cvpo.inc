@@ -92,6 +92,68 @@ extern "C" int fsrl_cvpo_last_particles(fsrl_ctx* c, float* eps_particles, int64
     return 0;
 }
 
+// ---- the arguments of one update's launches.  fsrl_cvpo_update and the grouped update (host_cvpo_group.inc) both form them
+//      here, so a member of a group cannot be handed anything its own update would not be.
+static SacGatherArgs cvpo_gather_args(const fsrl_ctx* c, const SacState* s, int B) {
+    const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, ns = s->ccfg.n_step;
+    SacGatherArgs ga{};
+    ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(ns - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
+    ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = Do; ga.Da = Da;
+    return ga;
+}
+// library RNG: the sample of the update that s->n_updates counts (the grouped update sets the counter per step)
+static SacSampleArgs cvpo_sample_args(const fsrl_ctx* c, const SacState* s, int B, int64_t stored) {
+    SacSampleArgs sa{};
+    sa.book = s->d_book; sa.flags = c->st.flags; sa.idx = s->d_idx; sa.chain = s->d_chain; sa.endbits = s->d_end;
+    sa.eps_t = s->eps_t; sa.eps_p = s->eps_p; sa.env_num = c->cfg.env_num; sa.sub_size = (int)c->sub_size; sa.B = B;
+    sa.n_step = s->ccfg.n_step; sa.Da = c->cfg.act_dim; sa.stored = (unsigned long long)stored; sa.key = s->key;
+    sa.counter = (unsigned long long)s->n_updates;
+    sa.eps_k = s->eps_k; sa.K = s->ccfg.sample_act_num;
+    return sa;
+}
+// with_particles: the launch's second batch is CVPO_A_PARTICLES (actor_old on OBS / eps_k -> MU_OLD, STD_OLD, XK); tiles: the
+// workgroups of one batch
+static CvpoActorArgs cvpo_actor_args(const fsrl_ctx* c, const SacState* s, int B, int mode, const float* obs, const float* eps,
+                                     float* X, bool with_particles, int tiles) {
+    CvpoActorArgs aa{};
+    if (with_particles) {
+        aa.P2 = s->PAT; aa.obs2 = s->OBS; aa.eps2 = s->eps_k; aa.X2 = s->XK; aa.mode2 = CVPO_A_PARTICLES; aa.tiles_half = tiles;
+    }
+    aa.obs = obs; aa.eps = eps; aa.X = X; aa.mu_old = s->MU_OLD; aa.std_old = s->STD_OLD; aa.W = s->Wk; aa.XK = s->XK;
+    aa.sc = s->csc; aa.A1 = s->A1; aa.A2 = s->A2; aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi;
+    aa.B = B; aa.K = s->ccfg.sample_act_num; aa.mode = mode; aa.max_action = c->cfg.max_action;
+    return aa;
+}
+static SacNstepArgs cvpo_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
+    SacNstepArgs na{};
+    na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
+    na.flags = c->st.flags; na.sc = s->sc; na.Y = s->Y; na.B = B; na.n_step = s->ccfg.n_step; na.gamma = c->cfg.gamma;
+    na.auto_alpha = 0; na.alpha_fixed = 0.0f; na.single = s->n_q == 2 ? 1 : 0;    // LPN stays zero: no entropy term
+    return na;
+}
+static CvpoEstepArgs cvpo_estep_args(const fsrl_ctx* c, const SacState* s, int B) {
+    const fsrl_cvpo_config& cc = s->ccfg;
+    CvpoEstepArgs ea{};
+    ea.QK = s->QK; ea.q0 = s->q0; ea.q1 = s->q1; ea.W = s->Wk; ea.sc = s->csc; ea.B = B; ea.K = cc.sample_act_num; ea.n_q = s->n_q;
+    ea.iters = cc.estep_iter_num; ea.kl = cc.estep_kl; ea.thres = (float)cc.qc_thres; ea.lr = cc.estep_dual_lr;
+    ea.dual_max = cc.estep_dual_max; ea.beta1 = c->cfg.beta1; ea.beta2 = c->cfg.beta2; ea.adam_eps = c->cfg.adam_eps;
+    return ea;
+}
+static CvpoMdualArgs cvpo_mdual_args(const fsrl_ctx* c, const SacState* s, int B, int n_tiles_pi, int log_it) {
+    const fsrl_cvpo_config& cc = s->ccfg;
+    CvpoMdualArgs ma{};
+    ma.statp = s->stpi; ma.n_tiles = n_tiles_pi; ma.B = B; ma.K = cc.sample_act_num; ma.sc = s->csc; ma.kl_mu_eps = cc.mstep_kl_mu;
+    ma.kl_std_eps = cc.mstep_kl_std; ma.dual_max = cc.mstep_dual_max; ma.lr = cc.mstep_dual_lr; ma.beta1 = c->cfg.beta1;
+    ma.beta2 = c->cfg.beta2; ma.adam_eps = c->cfg.adam_eps; ma.log_it = log_it;
+    return ma;
+}
+static CvpoFinalArgs cvpo_final_args(const fsrl_ctx* c, const SacState* s, int B, int n_tiles_q, float* stats_row) {
+    CvpoFinalArgs fa{};
+    fa.statp_q = s->stq; fa.Y = s->Y; fa.sc = s->csc; fa.stats = stats_row;
+    fa.n_tiles_q = n_tiles_q; fa.n_q = s->n_q; fa.B = B; fa.thres = (float)s->ccfg.qc_thres;
+    return fa;
+}
+
 extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, const float* eps_target,
                                 const float* eps_particles, uint64_t seed, float* stats_out) {
     CHECK_ARG(c, "null ctx");
@@ -113,9 +175,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     const size_t nk = (size_t)K * B * Da;
     if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
     bool fused_sg = false;
-    SacGatherArgs ga{};
-    ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(ns - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
-    ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = Do; ga.Da = Da;
+    const SacGatherArgs ga = cvpo_gather_args(c, s, B);
     if (indices) {
         HIPCHK(hipStreamSynchronize(st));      // pinned staging of the previous update has landed
         for (int b = 0; b < B; ++b) {
@@ -146,12 +206,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
             HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, st));
             s->book_version = c->store_version;
         }
-        SacSampleArgs sa{};
-        sa.book = s->d_book; sa.flags = c->st.flags; sa.idx = s->d_idx; sa.chain = s->d_chain; sa.endbits = s->d_end;
-        sa.eps_t = s->eps_t; sa.eps_p = s->eps_p; sa.env_num = c->cfg.env_num; sa.sub_size = (int)c->sub_size; sa.B = B;
-        sa.n_step = ns; sa.Da = Da; sa.stored = (unsigned long long)stored; sa.key = s->key;
-        sa.counter = (unsigned long long)s->n_updates;
-        sa.eps_k = s->eps_k; sa.K = K;
+        const SacSampleArgs sa = cvpo_sample_args(c, s, B, stored);
         fused_sg = !s->plan_separate;
         if (fused_sg) {          // r6: sample + gather + the particles' noise in one launch (fsrl_sac_set_plan bit 1 keeps the two)
             hipLaunchKernelGGL(cvpo_sample_gather_kernel, dim3((B + SG_ROWS - 1) / SG_ROWS + (B * K + 255) / 256), dim3(256), 0, st, sa, ga);
@@ -184,16 +239,10 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
             if (with_particles) { rc2 = one(CVPO_A_PARTICLES, s->PAT, s->OBS, s->eps_k, s->XK); if (rc2) return rc2; }
             return mode == CVPO_A_MBWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
         }
-        CvpoActorArgs aa{};
         const bool r4 = s->a_rows4 && (!with_particles || 8 * s->n_tiles <= c->n_cus);
         const int tiles = r4 ? 4 * s->n_tiles : s->n_tiles;
-        if (with_particles) {
-            aa.P2 = s->PAT; aa.obs2 = s->OBS; aa.eps2 = s->eps_k; aa.X2 = s->XK; aa.mode2 = CVPO_A_PARTICLES; aa.tiles_half = tiles;
-        }
         const int grid = with_particles ? 2 * tiles : tiles;
-        aa.obs = obs; aa.eps = eps; aa.X = X; aa.mu_old = s->MU_OLD; aa.std_old = s->STD_OLD; aa.W = s->Wk; aa.XK = s->XK;
-        aa.sc = s->csc; aa.A1 = s->A1; aa.A2 = s->A2; aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi;
-        aa.B = B; aa.K = K; aa.mode = mode; aa.max_action = c->cfg.max_action;
+        const CvpoActorArgs aa = cvpo_actor_args(c, s, B, mode, obs, eps, X, with_particles, tiles);
         return dispatch_H(c->cfg.hidden, [&](auto hc) {
             constexpr int H = decltype(hc)::value;
             if (r4) hipLaunchKernelGGL((cvpo_actor_tile_kernel<H, 4>), dim3(grid), dim3(4 * H), 0, st, PAx, s->mda, aa);
@@ -208,10 +257,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     if (rc) return rc;
     rc = sac_q_launch(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B);
     if (rc) return rc;
-    SacNstepArgs na{};
-    na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
-    na.flags = c->st.flags; na.sc = s->sc; na.Y = s->Y; na.B = B; na.n_step = ns; na.gamma = c->cfg.gamma;
-    na.auto_alpha = 0; na.alpha_fixed = 0.0f; na.single = s->n_q == 2 ? 1 : 0;    // LPN stays zero: no entropy term
+    const SacNstepArgs na = cvpo_nstep_args(c, s, B);
     // r6: the critics' tile launch computes its float64 targets itself (as SAC's does since r4) and leaves them in Y for the logged
     // row; layered contexts and fsrl_sac_set_plan bit 2 keep the stand-alone launch
     const bool ns_fold = !s->layered && !s->plan_nstep_sep;
@@ -231,10 +277,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     // ---- E-step: K particles of actor_old through the UPDATED critics                (cvpo.py:319-371)
     rc = sac_q_launch(c, s, s->PQ, s->XK, FB_MODE_Q_FWD, 0.f, 0.f, s->stqk, K * B, s->QK, s->n_tiles_k, s->k_rows4 ? 1 : 0);
     if (rc) return rc;
-    CvpoEstepArgs ea{};
-    ea.QK = s->QK; ea.q0 = s->q0; ea.q1 = s->q1; ea.W = s->Wk; ea.sc = s->csc; ea.B = B; ea.K = K; ea.n_q = s->n_q;
-    ea.iters = cc.estep_iter_num; ea.kl = cc.estep_kl; ea.thres = (float)cc.qc_thres; ea.lr = cc.estep_dual_lr;
-    ea.dual_max = cc.estep_dual_max; ea.beta1 = c->cfg.beta1; ea.beta2 = c->cfg.beta2; ea.adam_eps = c->cfg.adam_eps;
+    const CvpoEstepArgs ea = cvpo_estep_args(c, s, B);
     hipLaunchKernelGGL(cvpo_estep_kernel, dim3(1), dim3(1024), 0, st, ea);
     HIPCHK(hipGetLastError());
     // ---- M-step                                                                     (cvpo.py:378-417)
@@ -242,10 +285,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     for (int it = 0; it < cc.mstep_iter_num; ++it) {
         rc = actor_launch(CVPO_A_MFWD, s->PA, s->OBS, nullptr, nullptr);
         if (rc) return rc;
-        CvpoMdualArgs ma{};
-        ma.statp = s->stpi; ma.n_tiles = n_tiles_pi; ma.B = B; ma.K = K; ma.sc = s->csc; ma.kl_mu_eps = cc.mstep_kl_mu;
-        ma.kl_std_eps = cc.mstep_kl_std; ma.dual_max = cc.mstep_dual_max; ma.lr = cc.mstep_dual_lr; ma.beta1 = c->cfg.beta1;
-        ma.beta2 = c->cfg.beta2; ma.adam_eps = c->cfg.adam_eps; ma.log_it = it == 0;
+        const CvpoMdualArgs ma = cvpo_mdual_args(c, s, B, n_tiles_pi, it == 0);
         hipLaunchKernelGGL(cvpo_mdual_kernel, dim3(1), dim3(64), 0, st, ma);
         HIPCHK(hipGetLastError());
         rc = actor_launch(CVPO_A_MBWD, s->PA, s->OBS, nullptr, nullptr);
@@ -257,10 +297,8 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
             adam_launch(c, s->mda, s->PA, s->MA, s->VA, c->wg_parts, s->na_dev, cc.actor_lr, s->t_actor, nsplit, s->na_dev);
     }
     // ---- the last actor Adam carries the logged-row block                             (cvpo.py:422-430)
-    CvpoFinalArgs fa{};
     float* stats_row = s->d_stats + (size_t)(s->n_updates % SAC_RING) * s->nstats;
-    fa.statp_q = s->stq; fa.Y = s->Y; fa.sc = s->csc; fa.stats = stats_row;
-    fa.n_tiles_q = s->q_rows4 ? 4 * s->n_tiles : s->n_tiles; fa.n_q = s->n_q; fa.B = B; fa.thres = (float)cc.qc_thres;
+    const CvpoFinalArgs fa = cvpo_final_args(c, s, B, s->q_rows4 ? 4 * s->n_tiles : s->n_tiles, stats_row);
     adam_final_launch<CvpoFinalArgs, cvpo_finalize_row>(c, s->mda, s->PA, s->MA, s->VA, c->wg_parts, s->na_dev, cc.actor_lr,
                                                         s->t_actor, nsplit, s->na_dev, nullptr, 0.0f, fa);
     HIPCHK(hipGetLastError());

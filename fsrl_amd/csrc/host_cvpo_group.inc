@@ -1,0 +1,333 @@
+// host_cvpo_group.inc -- grouped CVPO updates: fsrl_cvpo_group_* (part of fsrl_hip.hip, kernels: kernels_cvpo_group.hpp and the
+// shared ones of kernels_sac_group.hpp).
+// k CVPO contexts of one launch structure, each stepped n_i times per call in lock step: every launch of an update carries all
+// members that still have updates to run (9 + 4 * mstep_iter_num launches per update, whatever k is).  The structure is
+// host_sac_group.inc's: members keep their own streams, stores, parameters, targets, actor_old, Adam state, duals, Philox key and
+// statistics ring; the group's stream waits on each active member's stream before the call and each member's streams wait on the
+// group's completion event after it, so fsrl_cvpo_pre_update / _post_update / _set_thres and the member's own updates order against
+// grouped calls like any other work on the member's stream.
+// A member's arguments are formed by the helpers fsrl_cvpo_update uses (host_cvpo.inc), its arithmetic is the single path's bodies
+// with the single path's split-K plan, and the tile height of a launch is the single-context rule applied to the whole group's
+// launch: a group of one is bit-identical to its solo run, a group that runs sixteen-row tiles in every launch is bit-identical to
+// solo runs created under FSRL_TILE16 (tests/test_gpu_cvpo_group.py).
+// ====================================================================================== grouped CVPO
+struct fsrl_cvpo_group {
+    std::vector<fsrl_ctx*> m;                  // members (not owned; nullptr once destroyed)
+    int device = 0;
+    hipStream_t stream = nullptr;              // the group's own stream
+    hipEvent_t done = nullptr;                 // end of the last grouped call on `stream`
+    std::vector<hipEvent_t> ready;             // per member: its stream's work before the call
+    SacGroupMember *d_tab = nullptr, *h_tab = nullptr;       // device / pinned, [k]: what the SAC group's kernels read
+    CvpoGroupMember *d_ctab = nullptr, *h_ctab = nullptr;    // device / pinned, [k]: CVPO's own launches
+    SacGroupStep *d_steps = nullptr, *h_steps = nullptr;     // device / pinned, [updates][k]
+    CvpoGroupIter *d_iters = nullptr, *h_iters = nullptr;    // device / pinned, [updates][mstep_iter_num][k]
+    size_t cap_steps = 0, cap_iters = 0;
+    bool broken = false;                       // a member was destroyed first: no more updates
+};
+
+// a member destroyed before its group (fsrl_ctx_destroy): the group stops updating, its destroy still works
+static void cvpo_group_detach(fsrl_ctx* c) {
+    fsrl_cvpo_group* g = c->cvpo_group;
+    if (!g) return;
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (auto& x : g->m) if (x == c) x = nullptr;
+    c->cvpo_group = nullptr;
+    g->broken = true;
+}
+
+extern "C" int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g) {
+    if (!g) return 0;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (fsrl_ctx* c : g->m) if (c) c->cvpo_group = nullptr;
+    for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
+    if (g->done) (void)hipEventDestroy(g->done);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    if (g->d_tab) (void)hipFree(g->d_tab);
+    if (g->h_tab) (void)hipHostFree(g->h_tab);
+    if (g->d_ctab) (void)hipFree(g->d_ctab);
+    if (g->h_ctab) (void)hipHostFree(g->h_ctab);
+    if (g->d_steps) (void)hipFree(g->d_steps);
+    if (g->h_steps) (void)hipHostFree(g->h_steps);
+    if (g->d_iters) (void)hipFree(g->d_iters);
+    if (g->h_iters) (void)hipHostFree(g->h_iters);
+    delete g;
+    return 0;
+}
+
+// what decides the launch structure must agree (checked at create and again at every update); `own`: the group the members may
+// already belong to (nullptr at create)
+static int cvpo_group_check(fsrl_ctx* const* ctxs, int k, const fsrl_cvpo_group* own) {
+    const fsrl_ctx* c0 = ctxs[0];
+    CHECK_ARG(c0, "null member");
+    for (int i = 0; i < k; ++i) {
+        const fsrl_ctx* c = ctxs[i];
+        CHECK_ARG(c, "null member");
+        for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member %d is listed twice", i);
+        const SacState* s = reinterpret_cast<const SacState*>(c->sac);
+        CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
+        CHECK_ARG(!s->ddpg, "member %d is a DDPG-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
+        CHECK_ARG(s->cvpo, "member %d is a SAC-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
+        CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: grouped CVPO updates run the fused kernels (two hidden layers)", i);
+        CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
+        CHECK_ARG(!c->sac_group, "member %d is already in a SAC group", i);
+        CHECK_ARG(c->cvpo_group == own, "member %d is already in a CVPO group", i);
+        const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
+        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden &&
+                  c->h1 == c0->h1 && c->h2 == c0->h2,
+                  "member %d: members must have one network shape (obs_dim, act_dim, hidden layer widths)", i);
+        CHECK_ARG(s->ccfg.n_step == s0->ccfg.n_step, "member %d: members must share n_step", i);
+        CHECK_ARG((s->ccfg.double_critic != 0) == (s0->ccfg.double_critic != 0), "member %d: members must share double_critic", i);
+        CHECK_ARG(s->ccfg.sample_act_num == s0->ccfg.sample_act_num, "member %d: members must share sample_act_num", i);
+        CHECK_ARG(s->ccfg.estep_iter_num == s0->ccfg.estep_iter_num, "member %d: members must share estep_iter_num", i);
+        CHECK_ARG(s->ccfg.mstep_iter_num == s0->ccfg.mstep_iter_num, "member %d: members must share mstep_iter_num", i);
+        CHECK_ARG(s->wgrad_splitk == s0->wgrad_splitk, "member %d: members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)", i);
+    }
+    return 0;
+}
+
+extern "C" int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_group** out) {
+    CHECK_ARG(ctxs && out, "null argument");
+    CHECK_ARG(k >= 1 && k <= FSRL_MAX_GROUP, "a CVPO group has 1..%d members", FSRL_MAX_GROUP);
+    int rc = cvpo_group_check(ctxs, k, nullptr);
+    if (rc) return rc;
+    const fsrl_ctx* c0 = ctxs[0];
+    HIPCHK(hipSetDevice(c0->device));
+    fsrl_cvpo_group* g = new fsrl_cvpo_group();
+    g->device = c0->device;
+    g->ready.assign((size_t)k, nullptr);
+    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->done, hipEventDisableTiming);
+    for (int i = 0; i < k && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&g->ready[(size_t)i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc(&g->d_tab, (size_t)k * sizeof(SacGroupMember));
+    if (e == hipSuccess) e = hipHostMalloc(&g->h_tab, (size_t)k * sizeof(SacGroupMember));
+    if (e == hipSuccess) e = hipMalloc(&g->d_ctab, (size_t)k * sizeof(CvpoGroupMember));
+    if (e == hipSuccess) e = hipHostMalloc(&g->h_ctab, (size_t)k * sizeof(CvpoGroupMember));
+    if (e != hipSuccess) {
+        fail(FSRL_EHIP, "CVPO group allocation failed: %s", hipGetErrorString(e));
+        (void)fsrl_cvpo_group_destroy(g);
+        return FSRL_EHIP;
+    }
+    for (int i = 0; i < k; ++i) { g->m.push_back(ctxs[i]); ctxs[i]->cvpo_group = g; }
+    *out = g;
+    return 0;
+}
+
+// the member's entries in both tables: every argument of the update's launches as fsrl_cvpo_update forms it (library RNG, fused
+// sample + gather, n-step targets folded into the critics' launch); *sa: its sample arguments (the counter is set per step)
+struct CvpoGroupTiles { bool q_r4, a_r4, f_r4, k_r4; };
+static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGroupMember& v, SacSampleArgs* sa, int B, int64_t stored,
+                             const CvpoGroupTiles& th, bool small_wgrad, int* nsplit_q, int* nsplit_a) {
+    const int nt = s->n_tiles, rp = nt * 16, K = s->ccfg.sample_act_num;
+    t = SacGroupMember{};
+    v = CvpoGroupMember{};
+    t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
+    v.PA = s->PA; v.MA = s->MA; v.VA = s->VA;
+    *sa = cvpo_sample_args(c, s, B, stored);
+    v.ga = cvpo_gather_args(c, s, B);
+    v.at = cvpo_actor_args(c, s, B, CVPO_A_TARGET, s->OBSN, s->eps_t, s->XN, true, th.f_r4 ? 4 * nt : nt);
+    v.am = cvpo_actor_args(c, s, B, CVPO_A_MFWD, s->OBS, nullptr, nullptr, false, 0);
+    v.ab = cvpo_actor_args(c, s, B, CVPO_A_MBWD, s->OBS, nullptr, nullptr, false, 0);
+    const SacNstepArgs na = cvpo_nstep_args(c, s, B);
+    t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, nt, nullptr);
+    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, nt, &na);
+    t.qd = sac_q_args(c, s, s->PQ, s->XK, FB_MODE_Q_FWD, 0.f, 0.f, s->stqk, K * B, s->QK, s->n_tiles_k, nullptr);   // the K * B particles
+    v.es = cvpo_estep_args(c, s, B);
+    v.md = cvpo_mdual_args(c, s, B, th.a_r4 ? 4 * nt : nt, 0);
+    v.fin = cvpo_final_args(c, s, B, th.q_r4 ? 4 * nt : nt, nullptr);
+    v.stats = s->d_stats; v.nstats = s->nstats;
+    // ---- weight gradients: sac_wgrad's plan for this member alone
+    if (small_wgrad) {
+        int rc = ensure_parts(c, s->nq_dev, 1);
+        if (rc) return rc;
+        t.GQ = c->wg_parts;
+        rc = ensure_parts(c, s->na_dev, 1);
+        if (rc) return rc;
+        t.GA = c->wg_parts;
+        if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
+        t.wq = group_wgrad_small(s, rp, s->XQ, const_cast<float*>(t.GQ));
+        t.wa = group_wgrad_small(s, rp, s->OBS, const_cast<float*>(t.GA));
+        *nsplit_q = *nsplit_a = 1;
+    } else {
+        int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
+        if (rc) return rc;
+        rc = group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
+        if (rc) return rc;
+    }
+    v.GA = t.GA;
+    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+    t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
+    t.tau = s->ccfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->ccfg.tau);
+    v.one_minus_b1 = t.one_minus_b1; v.beta2 = t.beta2; v.one_minus_b2 = t.one_minus_b2; v.adam_eps = t.adam_eps;
+    return 0;
+}
+
+template <class T>
+static int cvpo_group_table(T** d, T** h, size_t* cap, size_t need) {
+    if (need <= *cap) return 0;
+    if (*d) HIPCHK(hipFree(*d));
+    if (*h) HIPCHK(hipHostFree(*h));
+    *d = nullptr; *h = nullptr; *cap = 0;
+    const size_t n = std::max<size_t>(need, 64);
+    HIPCHK(hipMalloc(d, n * sizeof(T)));
+    HIPCHK(hipHostMalloc(h, n * sizeof(T)));
+    *cap = n;
+    return 0;
+}
+
+extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32_t* n_updates) {
+    CHECK_ARG(g && n_updates, "null argument");
+    if (g->broken) return fail(FSRL_ESTATE, "a member of this CVPO group was destroyed: destroy the group");
+    CHECK_ARG(B >= 1, "batch_size must be >= 1");
+    const int k = (int)g->m.size();
+    int rc = cvpo_group_check(g->m.data(), k, g);
+    if (rc) return rc;
+    fsrl_ctx* c0 = g->m[0];
+    SacState* s0 = sac_of(c0);
+    int n_max = 0;
+    for (int i = 0; i < k; ++i) {
+        fsrl_ctx* c = g->m[i];
+        CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
+        // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
+        CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
+                  "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
+        if (n_updates[i] > 0) CHECK_ARG(fsrl_store_len(c) > 0, "member %d: empty replay store", i);
+        n_max = std::max(n_max, (int)n_updates[i]);
+    }
+    if (n_max == 0) return 0;
+    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipStreamSynchronize(g->stream));           // the pinned tables of the previous call have been read
+    const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = s0->n_q;
+    const int K = s0->ccfg.sample_act_num, M = s0->ccfg.mstep_iter_num, ntk = (B * K + 15) / 16;
+    // tile heights: the single-context rule applied to the group's whole launch (4-row tiles while it fits one round)
+    const bool t16 = c0->probe_tile16;
+    CvpoGroupTiles th;
+    th.q_r4 = (size_t)4 * nt * n_q * k <= (size_t)c0->n_cus && !t16;
+    th.a_r4 = (size_t)4 * nt * k <= (size_t)c0->n_cus && !t16;
+    th.f_r4 = th.a_r4 && (size_t)8 * nt * k <= (size_t)c0->n_cus;
+    th.k_r4 = (size_t)4 * ntk * n_q * k <= (size_t)c0->n_cus && !t16;
+    const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
+    rc = cvpo_group_table(&g->d_steps, &g->h_steps, &g->cap_steps, (size_t)n_max * k);
+    if (rc) return rc;
+    rc = cvpo_group_table(&g->d_iters, &g->h_iters, &g->cap_iters, (size_t)n_max * M * k);
+    if (rc) return rc;
+    // ---- every member with work: its resident actor ends, its pushes land, its batch buffers and sub-buffer books are current
+    int nsq = 1, nsa = 1, rq_total = 0, ra_total = 0;
+    std::vector<SacSampleArgs> sas((size_t)k);
+    for (int i = 0; i < k; ++i) {
+        fsrl_ctx* c = g->m[i];
+        SacState* s = sac_of(c);
+        if (n_updates[i] == 0) continue;
+        ENTER_DEV(c);
+        rc = join_store(c);
+        if (rc) return rc;
+        rc = sac_alloc_batch(c, s, B);
+        if (rc) return rc;
+        if (s->book_version != c->store_version) {
+            HIPCHK(hipStreamSynchronize(c->compute));
+            for (int e = 0; e < c->cfg.env_num; ++e) {
+                const EnvBook& eb = c->env[(size_t)e];
+                s->h_book[e] = SacBook{(int)eb.size, (int)eb.index, (int)eb.last_index, 0};
+            }
+            HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, c->compute));
+            s->book_version = c->store_version;
+        }
+        int q_split = 1, a_split = 1;
+        rc = cvpo_group_member(c, s, g->h_tab[i], g->h_ctab[i], &sas[(size_t)i], B, fsrl_store_len(c), th, small_wgrad, &q_split, &a_split);
+        if (rc) return rc;
+        nsq = q_split; nsa = a_split;                  // one shape, one plan: the same for every member
+        rq_total = g->h_tab[i].fq.remap_total; ra_total = g->h_tab[i].fa.remap_total;
+        HIPCHK(hipEventRecord(g->ready[(size_t)i], c->compute));
+        HIPCHK(hipStreamWaitEvent(g->stream, g->ready[(size_t)i], 0));
+    }
+    // ---- the step tables: what each member's own fsrl_cvpo_update calls would use
+    for (int u = 0; u < n_max; ++u)
+        for (int i = 0; i < k; ++i) {
+            SacGroupStep& st = g->h_steps[(size_t)u * k + i];
+            st = SacGroupStep{};
+            for (int it = 0; it < M; ++it) g->h_iters[((size_t)u * M + it) * k + i] = CvpoGroupIter{};
+            if (u >= n_updates[i]) continue;
+            const fsrl_ctx* c = g->m[i];
+            const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
+            const int64_t n = s->n_updates + u, tc = s->t_critic + u + 1;
+            const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+            st.sa = sas[(size_t)i]; st.sa.counter = (unsigned long long)n; st.row = (int)(n % SAC_RING); st.active = 1;
+            st.c_step = (float)((double)s->ccfg.critic_lr / (1.0 - std::pow(b1, (double)tc)));
+            st.c_bc2 = (float)std::sqrt(1.0 - std::pow(b2, (double)tc));
+            for (int it = 0; it < M; ++it) {           // t_actor advances once per M iteration
+                const int64_t ta = s->t_actor + (int64_t)u * M + it + 1;
+                CvpoGroupIter& gi = g->h_iters[((size_t)u * M + it) * k + i];
+                gi.a_step = (float)((double)s->ccfg.actor_lr / (1.0 - std::pow(b1, (double)ta)));
+                gi.a_bc2 = (float)std::sqrt(1.0 - std::pow(b2, (double)ta));
+            }
+        }
+    hipStream_t gs = g->stream;
+    HIPCHK(hipMemcpyAsync(g->d_tab, g->h_tab, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->d_ctab, g->h_ctab, (size_t)k * sizeof(CvpoGroupMember), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->d_steps, g->h_steps, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->d_iters, g->h_iters, (size_t)n_max * M * k * sizeof(CvpoGroupIter), hipMemcpyHostToDevice, gs));
+    const ModelDesc mda = s0->mda;
+    ModelDesc mdq = s0->mdq, mdq_w = s0->mdq, mda_w = s0->mda;
+    mdq_w.n_nets = n_q; mda_w.n_nets = 1;              // sac_wgrad: the launch covers the first ny networks
+    const int na_dev = s0->na_dev, nq_dev = s0->nq_dev;
+    const SacGroupMember* tab = g->d_tab;
+    const CvpoGroupMember* ctab = g->d_ctab;
+    const int sg_blocks = (B + SG_ROWS - 1) / SG_ROWS + (B * K + 255) / 256;
+    rc = dispatch_H(H, [&](auto hc) {
+        constexpr int HH = decltype(hc)::value;
+        const int ft = th.f_r4 ? 4 * nt : nt, qt = th.q_r4 ? 4 * nt : nt, at = th.a_r4 ? 4 * nt : nt, kt = th.k_r4 ? 4 * ntk : ntk;
+        const int gq = round_up(rq_total, 8), ga = round_up(ra_total, 8);
+        for (int u = 0; u < n_max; ++u) {
+            const SacGroupStep* st = g->d_steps + (size_t)u * k;
+            // 1. sample + gather + the particles' noise; 2. a' ~ actor(s_{t+n}) and the K particles of actor_old at s_t
+            hipLaunchKernelGGL(cvpo_sample_gather_group_kernel, dim3(sg_blocks, k), dim3(256), 0, gs, ctab, st);
+            if (th.f_r4) hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 4, 0>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+            else hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 16, 0>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+            // 3. target Q-networks on (s_{t+n}, a'); 4. the critics' forward + backward with their n-step targets
+            if (th.q_r4) {
+                hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+                hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+            } else {
+                hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+                hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+            }
+            // 5. the critics' weight gradients; 6. their Adam with the Polyak targets
+            if (small_wgrad) hipLaunchKernelGGL((sac_wgrad_group_kernel<HH, 0>), dim3(wg_grid(HH, n_q), k), dim3(1024), 0, gs, mdq_w, tab, st, rp);
+            else hipLaunchKernelGGL((sac_wgrad_split_group_kernel<HH, 0>), dim3(gq, k), dim3(1024), 0, gs, mdq, tab, st);
+            hipLaunchKernelGGL(sac_adam_group_kernel, dim3((nq_dev + 255) / 256, k), dim3(256), 0, gs, mdq, tab, st, nq_dev, nsq, nq_dev);
+            // 7. the K * B particles through the updated critics; 8. the E-step, one workgroup per member
+            if (th.k_r4) hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 2>), dim3(kt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+            else hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 2>), dim3(kt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+            hipLaunchKernelGGL(cvpo_estep_group_kernel, dim3(k), dim3(1024), 0, gs, ctab, st);
+            // ---- M-step: statistics, dual step (one wave per member), backward, weight gradients, Adam
+            for (int it = 0; it < M; ++it) {
+                const CvpoGroupIter* gi = g->d_iters + ((size_t)u * M + it) * k;
+                if (th.a_r4) hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 4, 1>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+                else hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 16, 1>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+                hipLaunchKernelGGL(cvpo_mdual_group_kernel, dim3(k), dim3(64), 0, gs, ctab, st, it == 0 ? 1 : 0);
+                if (th.a_r4) hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 4, 2>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+                else hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 16, 2>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
+                if (small_wgrad) hipLaunchKernelGGL((sac_wgrad_group_kernel<HH, 1>), dim3(wg_grid(HH, 1), k), dim3(1024), 0, gs, mda_w, tab, st, rp);
+                else hipLaunchKernelGGL((sac_wgrad_split_group_kernel<HH, 1>), dim3(ga, k), dim3(1024), 0, gs, mda, tab, st);
+                // the last actor Adam carries the logged-row block
+                if (it < M - 1) hipLaunchKernelGGL(cvpo_adam_group_kernel<0>, dim3((na_dev + 255) / 256, k), dim3(256), 0, gs, mda, ctab, st, gi, na_dev, nsa, na_dev);
+                else hipLaunchKernelGGL(cvpo_adam_group_kernel<1>, dim3((na_dev + 255) / 256 + 1, k), dim3(256), 0, gs, mda, ctab, st, gi, na_dev, nsa, na_dev);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(g->done, gs));
+    // ---- each member's streams wait for the call; its bookkeeping is that of n_i own updates
+    for (int i = 0; i < k; ++i) {
+        if (n_updates[i] == 0) continue;
+        fsrl_ctx* c = g->m[i];
+        SacState* s = sac_of(c);
+        HIPCHK(hipStreamWaitEvent(c->compute, g->done, 0));
+        HIPCHK(hipStreamWaitEvent(c->side, g->done, 0));     // a push must not overwrite rows the call still samples
+        s->n_updates += n_updates[i]; s->t_critic += n_updates[i]; s->t_actor += (int64_t)n_updates[i] * M;
+        s->last_B = B;
+    }
+    return 0;
+}

@@ -414,6 +414,19 @@ static inline bool store_end_flag(const fsrl_ctx* c, int64_t idx) {
     return eb.size > 0 && local == (eb.index - 1 + eb.size) % eb.size;   // unfinished tail
 }
 
+// the arguments of a Q-network tile launch of n_tiles 16-row groups (sac_q_launch; the grouped CVPO update, host_cvpo_group.inc)
+static FbArgs sac_q_args(const fsrl_ctx* c, const SacState* s, const float* params, const float* X, int mode, float cr, float cc,
+                         float* statp, int B, float* qout_override, int n_tiles, const SacNstepArgs* ns) {
+    FbArgs a{};
+    a.obs = X; a.rd = nullptr; a.A1 = s->A1; a.A2 = s->A2; a.D1 = s->D1; a.D2 = s->D2; a.DO = s->DO; a.statp = statp;
+    a.N = B; a.rows_pad = n_tiles * 16; a.mode = mode; a.net0 = 0; a.cr = cr; a.cc = cc; a.max_action = 1.0f;
+    a.tgt = s->Y; a.qout = (mode == FB_MODE_Q_FWD && params == s->PQT) ? s->QT : s->QP; a.qin = s->QP; a.da_out = s->DA;
+    if (qout_override) a.qout = qout_override;
+    a.act_cols = c->cfg.act_dim; a.pair_shift = s->n_q == 2 ? 0 : 1;
+    if (ns) { a.ns_on = 1; a.ns = *ns; }          // Q_TRAIN: the tile launch computes its n-step targets itself
+    return a;
+}
+
 // qout_override / n_tiles / rows4: the K*B particle launch of CVPO's E-step (forward only) reuses the Q-net kernel
 static int sac_q_launch(fsrl_ctx* c, SacState* s, const float* params, const float* X, int mode, float cr, float cc,
                         float* statp, int B, float* qout_override = nullptr, int n_tiles = -1, int rows4 = -1,
@@ -435,15 +448,9 @@ static int sac_q_launch(fsrl_ctx* c, SacState* s, const float* params, const flo
         for (int n = 0; n < s->n_q; ++n) dx[n] = s->DXQ + (size_t)n * s->kq.mbp * (c->cfg.obs_dim + c->cfg.act_dim);
         return lay_bwd_dz_k(c, s->kq, params, B, 0, -1, dx);
     }
-    FbArgs a{};
     if (n_tiles < 0) n_tiles = s->n_tiles;
     const bool r4 = rows4 < 0 ? s->q_rows4 : rows4 != 0;
-    a.obs = X; a.rd = nullptr; a.A1 = s->A1; a.A2 = s->A2; a.D1 = s->D1; a.D2 = s->D2; a.DO = s->DO; a.statp = statp;
-    a.N = B; a.rows_pad = n_tiles * 16; a.mode = mode; a.net0 = 0; a.cr = cr; a.cc = cc; a.max_action = 1.0f;
-    a.tgt = s->Y; a.qout = (mode == FB_MODE_Q_FWD && params == s->PQT) ? s->QT : s->QP; a.qin = s->QP; a.da_out = s->DA;
-    if (qout_override) a.qout = qout_override;
-    a.act_cols = c->cfg.act_dim; a.pair_shift = s->n_q == 2 ? 0 : 1;
-    if (ns) { a.ns_on = 1; a.ns = *ns; }          // Q_TRAIN: the tile launch computes its n-step targets itself
+    FbArgs a = sac_q_args(c, s, params, X, mode, cr, cc, statp, B, qout_override, n_tiles, ns);
 #ifdef FSRL_PROBES
     { static const char* e = getenv("FSRL_QTILE_PROBE"); if (e) a.eta = (float)atoi(e); }      // kernels_fb.hpp FBT_PROBE (results invalid)
 #endif

@@ -90,6 +90,40 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
     return 0;
 }
 
+// a member's weight-gradient arguments (the grouped CVPO update, host_cvpo_group.inc, forms its members' here too).
+// Batches of up to 512 padded rows: ppo_wgrad_body writes the final gradient into G.
+static WgradPtrs group_wgrad_small(const SacState* s, int rp, const float* X, float* G) {
+    WgradPtrs w{};
+    w.A1 = s->A1; w.A2 = s->A2; w.D1 = s->D1; w.D2 = s->D2; w.DO = s->DO; w.X = X; w.grad = G;
+    w.gsq_part = s->gsq_scratch; w.mbp_max = rp;
+    return w;
+}
+// larger batches: sac_wgrad's split-K plan of `ny` networks for this member alone, its partials in the member's own buffer *G
+static int group_wgrad_split(fsrl_ctx* c, const SacState* s, FbWgradArgs& wa, const ModelDesc& md, int ny, const float* X, int stride,
+                             int B, const float** G, int* nsplit) {
+    const int H = c->cfg.hidden, rp = s->n_tiles * 16;
+    wa = FbWgradArgs{};
+    for (int y = 0; y < ny; ++y) {
+        FbWgradNet& wn = wa.nets[y];
+        const size_t nb = (size_t)y * rp;
+        wn.w2_ya = s->D2 + nb * H; wn.w2_xa = s->A1 + nb * H; wn.w2_yb = nullptr; wn.w2_xb = nullptr;
+        wn.w1_y = s->D1 + nb * H; wn.w3_xa = s->A2 + nb * H; wn.w3_ya = s->DO + nb * FSRL_DOW;
+        wn.w3_xb = nullptr; wn.w3_yb = nullptr; wn.b1_src = s->D1 + nb * H; wn.b2_src = s->D2 + nb * H;
+        wn.do_src = s->DO + nb * FSRL_DOW; wn.net = y;
+    }
+    wa.obs = X; wa.rows = rp; wa.N = B;
+    // wgrad_launch's fb_wgrad_kernel plan
+    const int passes = 1 + std::max(0, (md.Do - 16 * 2 + 63) / 64);
+    const int NB = (H / 64) * (H / 64) + (H / FB_AUX_COLS) * passes + 1;
+    const WgradPlan pl = wgrad_plan(rp, NB * ny, c->n_cus);
+    int rc = ensure_parts(c, stride, pl.nsplit);
+    if (rc) return rc;
+    wa.out = c->wg_parts; wa.ks_per_split = pl.ks_per_split; wa.split_stride = stride; wa.dbg_skip = 0;
+    wa.aux_passes = passes; wa.remap_total = NB * ny * pl.nsplit; wa.remap_ny = ny;
+    *G = c->wg_parts; *nsplit = pl.nsplit;
+    return 0;
+}
+
 // the member's table entry: every argument of the nine launches as fsrl_sac_update forms it (library RNG, fold path)
 static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, int64_t stored, const double* lags, double rescaling,
                             bool q_r4, bool a_r4, bool f_r4, bool small_wgrad, int* nsplit_q, int* nsplit_a) {
@@ -145,40 +179,13 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
         if (rc) return rc;
         t.GA = c->wg_parts;
         if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
-        auto wp = [&](WgradPtrs& w, const float* X, float* G) {
-            w = WgradPtrs{};
-            w.A1 = s->A1; w.A2 = s->A2; w.D1 = s->D1; w.D2 = s->D2; w.DO = s->DO; w.X = X; w.grad = G;
-            w.gsq_part = s->gsq_scratch; w.mbp_max = rp;
-        };
-        wp(t.wq, s->XQ, const_cast<float*>(t.GQ));
-        wp(t.wa, s->OBS, const_cast<float*>(t.GA));
+        t.wq = group_wgrad_small(s, rp, s->XQ, const_cast<float*>(t.GQ));
+        t.wa = group_wgrad_small(s, rp, s->OBS, const_cast<float*>(t.GA));
         *nsplit_q = *nsplit_a = 1;
     } else {
-        auto fw = [&](FbWgradArgs& wa, const ModelDesc& md, int ny, const float* X, int stride, const float** G, int* nsplit) -> int {
-            wa = FbWgradArgs{};
-            for (int y = 0; y < ny; ++y) {
-                FbWgradNet& wn = wa.nets[y];
-                const size_t nb = (size_t)y * rp;
-                wn.w2_ya = s->D2 + nb * H; wn.w2_xa = s->A1 + nb * H; wn.w2_yb = nullptr; wn.w2_xb = nullptr;
-                wn.w1_y = s->D1 + nb * H; wn.w3_xa = s->A2 + nb * H; wn.w3_ya = s->DO + nb * FSRL_DOW;
-                wn.w3_xb = nullptr; wn.w3_yb = nullptr; wn.b1_src = s->D1 + nb * H; wn.b2_src = s->D2 + nb * H;
-                wn.do_src = s->DO + nb * FSRL_DOW; wn.net = y;
-            }
-            wa.obs = X; wa.rows = rp; wa.N = B;
-            // wgrad_launch's fb_wgrad_kernel plan
-            const int passes = 1 + std::max(0, (md.Do - 16 * 2 + 63) / 64);
-            const int NB = (H / 64) * (H / 64) + (H / FB_AUX_COLS) * passes + 1;
-            const WgradPlan pl = wgrad_plan(rp, NB * ny, c->n_cus);
-            int rc = ensure_parts(c, stride, pl.nsplit);
-            if (rc) return rc;
-            wa.out = c->wg_parts; wa.ks_per_split = pl.ks_per_split; wa.split_stride = stride; wa.dbg_skip = 0;
-            wa.aux_passes = passes; wa.remap_total = NB * ny * pl.nsplit; wa.remap_ny = ny;
-            *G = c->wg_parts; *nsplit = pl.nsplit;
-            return 0;
-        };
-        int rc = fw(t.fq, s->mdq, 4, s->XQ, s->nq_dev, &t.GQ, nsplit_q);
+        int rc = group_wgrad_split(c, s, t.fq, s->mdq, 4, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
         if (rc) return rc;
-        rc = fw(t.fa, s->mda, 1, s->OBS, s->na_dev, &t.GA, nsplit_a);
+        rc = group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
         if (rc) return rc;
     }
     // ---- the logged row (fin.stats per step) and Adam's constants

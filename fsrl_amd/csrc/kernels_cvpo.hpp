@@ -44,20 +44,21 @@ struct CvpoActorArgs {
     const float* P2; const float* obs2; const float* eps2; float* X2; int mode2, tiles_half;
 };
 
+// bx: this workgroup's tile of the launch (blockIdx.x of the single-context launch; the grouped launch, kernels_cvpo_group.hpp,
+// passes it on)
 template <int H, int R>
-__global__ __launch_bounds__(4 * H) void cvpo_actor_tile_kernel(const float* __restrict__ P_,
-                                                               const ModelDesc md, const CvpoActorArgs a) {
-    __shared__ TileSmem<H> sm;
+__device__ __forceinline__ void cvpo_actor_tile_body(TileSmem<H>& sm, const float* __restrict__ P_, const ModelDesc& md,
+                                                     const CvpoActorArgs& a, const int bx) {
     constexpr int NT = TileGeom<H>::NT;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, li = lane & 15, q = lane >> 4;
-    const bool second = a.tiles_half > 0 && (int)blockIdx.x >= a.tiles_half;
+    const bool second = a.tiles_half > 0 && bx >= a.tiles_half;
     const float* __restrict__ P = second ? a.P2 : P_;
     const float* __restrict__ obs_ = second ? a.obs2 : a.obs;
     const float* __restrict__ eps_ = second ? a.eps2 : a.eps;
     float* __restrict__ X_ = second ? a.X2 : a.X;
     const int mode = second ? a.mode2 : a.mode;
-    const int row0 = (second ? (int)blockIdx.x - a.tiles_half : (int)blockIdx.x) * R;
+    const int row0 = (second ? bx - a.tiles_half : bx) * R;
     const NetOff no = md.net[0];
     const int Do = md.Do, Da = md.Da, Din = Do + Da;
     const int n_valid = max(0, min(R, a.B - row0));
@@ -165,12 +166,19 @@ __global__ __launch_bounds__(4 * H) void cvpo_actor_tile_kernel(const float* __r
         if (tid < 4) {
             float t = 0.0f;
             for (int i = 0; i < R; ++i) t += sm.w1[i * FB_NSTAT + tid];
-            a.statp[(size_t)blockIdx.x * FB_NSTAT + tid] = t;
+            a.statp[(size_t)bx * FB_NSTAT + tid] = t;
         }
         return;
     }
     tile_backward<H, R>(sm, no, wb, a.A1 + (size_t)row0 * H, a.A2 + (size_t)row0 * H, a.D1 + (size_t)row0 * H,
                         a.D2 + (size_t)row0 * H, a.DO + (size_t)row0 * FSRL_DOW, tid, false);
+}
+
+template <int H, int R>
+__global__ __launch_bounds__(4 * H) void cvpo_actor_tile_kernel(const float* __restrict__ P_,
+                                                               const ModelDesc md, const CvpoActorArgs a) {
+    __shared__ TileSmem<H> sm;
+    cvpo_actor_tile_body<H, R>(sm, P_, md, a, (int)blockIdx.x);
 }
 
 // ---- E-step (cvpo.py:278-288, 341-371): one workgroup.  Q values arrive as [n_q][K*B] (row k*B + b);
@@ -220,9 +228,8 @@ __device__ __forceinline__ float row_max(float v, const int KP) {
     return v;
 }
 
-__global__ __launch_bounds__(1024) void cvpo_estep_kernel(const CvpoEstepArgs a) {
-    __shared__ double red[3][1024];
-    __shared__ float duals[2];
+// one workgroup of 1024 threads; red / duals: its LDS
+__device__ __forceinline__ void cvpo_estep_body(const CvpoEstepArgs& a, double (*red)[1024], float* duals) {
     const int tid = threadIdx.x;
     const size_t KB = (size_t)a.K * a.B;
     const float logK = logf((float)a.K);
@@ -328,6 +335,12 @@ __global__ __launch_bounds__(1024) void cvpo_estep_kernel(const CvpoEstepArgs a)
     }
 }
 
+__global__ __launch_bounds__(1024) void cvpo_estep_kernel(const CvpoEstepArgs a) {
+    __shared__ double red[3][1024];
+    __shared__ float duals[2];
+    cvpo_estep_body(a, red, duals);
+}
+
 // ---- M-step dual step (cvpo.py:392-405): KL means over the tiles, Adam on (mstep_dual_mu, mstep_dual_std),
 //      the clipped multipliers for the backward, and the logged values of the first iteration.
 struct CvpoMdualArgs {
@@ -336,7 +349,8 @@ struct CvpoMdualArgs {
     float kl_mu_eps, kl_std_eps, dual_max, lr, beta1, beta2, adam_eps;
     int log_it;
 };
-__global__ __launch_bounds__(64) void cvpo_mdual_kernel(const CvpoMdualArgs a) {
+// one wave
+__device__ __forceinline__ void cvpo_mdual_body(const CvpoMdualArgs& a) {
     const int lane = threadIdx.x;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int t = lane; t < a.n_tiles; t += 64) {
@@ -370,6 +384,7 @@ __global__ __launch_bounds__(64) void cvpo_mdual_kernel(const CvpoMdualArgs a) {
     }
     *a.sc = sc;
 }
+__global__ __launch_bounds__(64) void cvpo_mdual_kernel(const CvpoMdualArgs a) { cvpo_mdual_body(a); }
 
 // ---- one row of logged statistics, in the order the reference's logger receives them (cvpo.py:248-276, 341-417)
 struct CvpoFinalArgs {

@@ -62,10 +62,11 @@ __global__ __launch_bounds__(256) void sac_sample_kernel(const SacSampleArgs a) 
 // ---- CVPO, library RNG: sample + gather + the K particles' noise in ONE launch (r6; sac_sample_kernel + sac_gather_kernel before).
 //      Blocks [0, ceil(B / SG_ROWS)): sac_sample_gather_block; the blocks behind them: thread (b, kp) draws particle kp's noise for
 //      row b -- the Philox counters of sac_sample_kernel's CVPO branch, so the same values.
-__global__ __launch_bounds__(256) void cvpo_sample_gather_kernel(const SacSampleArgs a, const SacGatherArgs g) {
+//      bx: this workgroup's block of the launch (the grouped launch, kernels_cvpo_group.hpp, passes it on)
+__device__ __forceinline__ void cvpo_sample_gather_body(const SacSampleArgs& a, const SacGatherArgs& g, const int bx) {
     const int nb = (a.B + SG_ROWS - 1) / SG_ROWS;
-    if ((int)blockIdx.x < nb) { sac_sample_gather_block(a, g, blockIdx.x); return; }
-    const int t = ((int)blockIdx.x - nb) * 256 + threadIdx.x;
+    if (bx < nb) { sac_sample_gather_block(a, g, bx); return; }
+    const int t = (bx - nb) * 256 + threadIdx.x;
     const int b = t % a.B, kp = t / a.B;
     if (kp >= a.K) return;
     const uint32_t k0 = (uint32_t)a.key, k1 = (uint32_t)(a.key >> 32);
@@ -78,6 +79,9 @@ __global__ __launch_bounds__(256) void cvpo_sample_gather_kernel(const SacSample
         float* o = a.eps_k + ((size_t)kp * a.B + b) * a.Da + d0;
         for (int j = 0; j < 4 && d0 + j < a.Da; ++j) o[j] = v[j];
     }
+}
+__global__ __launch_bounds__(256) void cvpo_sample_gather_kernel(const SacSampleArgs a, const SacGatherArgs g) {
+    cvpo_sample_gather_body(a, g, (int)blockIdx.x);
 }
 
 // ---- sample + gather in ONE launch (SAC / DDPG-Lag, library RNG): sac_sample_gather_block (kernels_sample.hpp) per workgroup.

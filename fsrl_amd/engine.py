@@ -884,3 +884,37 @@ class EngineSacGroup:
         lag = None if lagrangians is None else np.ascontiguousarray(lagrangians, np.float64).reshape(k, -1)
         _lib.check(self.lib.fsrl_sac_group_update(self._g, int(batch_size), _ptr(n, _i32p),
                                                   _ptr(lag, _f64p) if lag is not None and lag.size else None, _ptr(resc, _f64p)))
+
+
+class EngineCvpoGroup:
+    """k CVPO engines (cvpo_init) of one launch structure on one GPU, updated in lock step (fsrl_cvpo_group_*): every launch of
+    an update carries all members that still have updates to run.  Members keep their own streams, stores, parameters, duals,
+    Philox keys and statistics rings, and stay ordinary engines between updates (push, collect_step with the resident actor,
+    cvpo_pre_update / cvpo_post_update / cvpo_set_thres, own cvpo_update calls, sac_drain ...)."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        assert self.engines, "a group needs at least one engine"
+        self.lib = self.engines[0].lib
+        k = len(self.engines)
+        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
+        self._g = C.c_void_p()
+        _lib.check(self.lib.fsrl_cvpo_group_create(arr, k, C.byref(self._g)))
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_cvpo_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, batch_size, n_updates):
+        """n_updates[i] x Engine.cvpo_update(batch_size, sync=False) on member i (library RNG), all in lock step.  Enqueues only:
+        the statistics rows wait in each member's ring for its sac_drain()."""
+        k = len(self.engines)
+        n = np.ascontiguousarray(n_updates, np.int32).reshape(k)
+        _lib.check(self.lib.fsrl_cvpo_group_update(self._g, int(batch_size), _ptr(n, _i32p)))

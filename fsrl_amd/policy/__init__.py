@@ -13,4 +13,5 @@ install(__name__, globals(), {
     "CVPO": "cvpo",
     "PolicyGroup": "grouped",
     "SACPolicyGroup": "grouped_sac",
+    "CVPOPolicyGroup": "grouped_cvpo",
 })

@@ -601,6 +601,26 @@ int fsrl_cvpo_duals_get(fsrl_ctx* ctx, float* out4);
 /* The K particles' N(0,1) block of the last update ([K][B][Da]); indices / eps_target: fsrl_sac_last_sample. */
 int fsrl_cvpo_last_particles(fsrl_ctx* ctx, float* eps_particles, int64_t n);
 
+/* ---- Grouped CVPO updates: k CVPO contexts (fsrl_cvpo_init) on one device, each stepped n_updates[i] times per call in lock
+ *      step; every launch of an update (9 + 4 * mstep_iter_num, whatever k is) carries all members that still have updates to
+ *      run.  Members keep their own streams, stores, parameters, targets, actor_old, Adam state, duals, Philox key and
+ *      statistics ring, and stay ordinary contexts between calls: fsrl_cvpo_pre_update / _post_update / _set_thres and own
+ *      fsrl_cvpo_update calls order against grouped calls on the member's stream (a call ends a member's resident actor; its
+ *      next collect relaunches it).  Members must share what decides the launch structure: obs_dim, act_dim, the hidden layer
+ *      widths, n_step, double_critic, sample_act_num, estep_iter_num, mstep_iter_num and fsrl_sac_set_plan bit 0; learning
+ *      rates, tau, the KL bounds, dual learning rates and caps, qc_thres, seeds and store contents may differ.  Rejected with
+ *      FSRL_EINVAL and the reason in fsrl_last_error: SAC-Lag, DDPG-Lag and layered contexts, another device, a mismatch of the
+ *      list above, a member listed twice or already in a SAC or CVPO group.  A member destroyed before its group makes the
+ *      next update fail (FSRL_ESTATE); fsrl_cvpo_group_destroy still works.                                                 */
+typedef struct fsrl_cvpo_group fsrl_cvpo_group;
+int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_group** out);   /* 1 <= k <= 16, members not owned */
+int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g);
+/* n_updates[k] back-to-back fsrl_cvpo_update calls per member (library RNG: the member's Philox key, its update count as the
+ * counter), all members in lock step; a member with fewer updates sits out the later ones (0: left untouched).  Statistics
+ * rows go to each member's own ring (fsrl_sac_stats_drain).  Enqueues only: each member's stream waits for the call before its
+ * next work.                                                                                                                */
+int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t* n_updates);
+
 /* ---- timing of the last update, measured with hipEvents on the compute stream --------- */
 /* out[0] = process_fn ms, out[1] = learn ms (all passes), out[2] = fused fwd/bwd kernel
  * total ms over the update (sum of per-launch event pairs when profiling is enabled),
