@@ -18,12 +18,16 @@ launches (fsrl_amd.policy.PolicyGroup -> fsrl_group_ppo_update: every launch of 
 ~2x the aggregate updates/s of the thread-per-seed mode at 4 seeds (tools/bench_group.py); collection: tools/bench_group_collect.py.
 Per seed the run is the one of collecting the seeds one after the other, bit for bit.  --grouped --algo focops: the same loop
 with FOCOPS seeds (each seed's nu step, then one grouped FOCOPS update; tools/bench_group_focops.py).
---grouped --algo sacl: ONE thread; each seed collects with its own FastCollector (its resident device actor) and steps its PID
-multiplier, then ONE grouped update (fsrl_amd.policy.SACPolicyGroup -> fsrl_sac_group_update) runs round(update_per_step * n/st)
+--grouped --algo sacl: ONE thread; the seeds collect in lock step (GroupCollector over an fsrl_amd.engine.EngineCollectGroup ->
+fsrl_collect_group_step: one request per vector step to one resident kernel running every seed's actor network), each seed steps
+its PID multiplier, then ONE grouped update (fsrl_amd.policy.SACPolicyGroup -> fsrl_sac_group_update) runs round(update_per_step * n/st)
 updates per seed, every launch carrying all seeds (tools/bench_group_sac.py).
 --grouped --algo cvpo: the same loop with CVPO seeds (each seed's pre_update_fn resets its M-step multipliers, ONE grouped update
 through fsrl_amd.policy.CVPOPolicyGroup -> fsrl_cvpo_group_update, each seed's post_update_fn copies actor -> actor_old;
 tools/bench_group_cvpo.py).
+--grouped --algo ddpgl: lock-step collection as for sacl, then each seed's OWN updates one after the other (grouped DDPG-Lag
+updates do not exist).
+    python examples/train_multi_seed.py --algo ddpgl --seeds 4 --epoch 2 --grouped
 """
 import argparse
 import os
@@ -39,14 +43,16 @@ from fsrl_amd.utils import BaseLogger  # noqa: E402
 
 AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops": FOCOPSAgent, "sacl": SACLagAgent,
           "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}
-GROUPED_ALGOS = ("ppol", "focops", "sacl", "cvpo")      # what --grouped takes
+GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo")      # what --grouped takes
 
 
 def run_grouped_replay(a):
-    """k SAC-Lag (CVPO) seeds, one host thread: every seed collects with its own collector and runs its pre_update_fn (SAC-Lag: the
-    PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped update runs each seed's
-    round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed), then each seed's post_update_fn."""
-    from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+    """k SAC-Lag (CVPO, DDPG-Lag) seeds, one host thread: the seeds collect in lock step (one collect-group call per vector step) and
+    run their pre_update_fn (SAC-Lag / DDPG-Lag: the PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped
+    update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed; DDPG-Lag:
+    each seed's own updates, one seed after the other), then each seed's post_update_fn."""
+    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
+    from fsrl_amd.engine import EngineCollectGroup
     from fsrl_amd.policy import CVPOPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
@@ -58,21 +64,27 @@ def run_grouped_replay(a):
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
-    group = (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in agents])
+    group = None if a.algo == "ddpgl" else (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in agents])
+    cgroup = EngineCollectGroup([ag.policy.engine for ag in agents])
+    gcol = GroupCollector(cgroup, cols)
     update_per_step, t0, steps, updates = 0.2, time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
         while budget > 0:
             n, sts = [], []
-            for ag, col in zip(agents, cols):
-                st = col.collect(n_episode=a.envs)
+            for ag, st in zip(agents, gcol.collect(n_episode=a.envs)):
                 sts.append(st)
                 ag.policy.pre_update_fn(stats_train=st)
                 ag.logger.store(**{"train/reward": st["rew"], "train/cost": st["cost"]})
                 steps += st["n/st"]
                 n.append(round(update_per_step * st["n/st"]))
             budget -= st["n/st"]
-            group.update(bufs, batch_size=256, n_updates=n)
+            if group is not None:
+                group.update(bufs, batch_size=256, n_updates=n)
+            else:
+                for ag, buf, n_i in zip(agents, bufs, n):
+                    for _ in range(n_i):
+                        ag.policy.update(256, buf)
             for ag, st in zip(agents, sts):
                 ag.policy.post_update_fn(stats_train=st)
             updates += sum(n)
@@ -83,7 +95,9 @@ def run_grouped_replay(a):
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
-    group.close()
+    cgroup.close()
+    if group is not None:
+        group.close()
     for ag in agents:
         ag.policy.engine.close()
 
@@ -91,8 +105,8 @@ def run_grouped_replay(a):
 def run_grouped(a):
     """k PPO-Lag (FOCOPS) seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier (each
     seed's cost goes to its nu step), ONE grouped update."""
-    assert a.algo in GROUPED_ALGOS, "--grouped: PPO-Lagrangian, FOCOPS, SAC-Lagrangian or CVPO"
-    if a.algo in ("sacl", "cvpo"):
+    assert a.algo in GROUPED_ALGOS, "--grouped: PPO-Lagrangian, FOCOPS, SAC-Lagrangian, DDPG-Lagrangian or CVPO"
+    if a.algo in ("sacl", "ddpgl", "cvpo"):
         return run_grouped_replay(a)
     from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
     from fsrl_amd.policy import PolicyGroup
@@ -141,7 +155,8 @@ def main():
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / CVPO: lock-step grouped updates from one thread")
+    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / CVPO: lock-step collection and grouped updates from one thread; "
+                    "DDPG-Lag: lock-step collection, then each seed's own updates (there are no grouped DDPG-Lag updates)")
     a = ap.parse_args()
     out, errs = {}, []
     if a.grouped:

@@ -121,6 +121,13 @@ SIGNATURES = {
     "fsrl_cvpo_group_create": (C.c_int, [_P(_ctx), C.c_int32, _P(_ctx)]),
     "fsrl_cvpo_group_destroy": (C.c_int, [_ctx]),
     "fsrl_cvpo_group_update": (C.c_int, [_ctx, C.c_int32, _i32]),
+    "fsrl_collect_group_create": (C.c_int, [_P(_ctx), C.c_int32, _P(_ctx)]),
+    "fsrl_collect_group_destroy": (C.c_int, [_ctx]),
+    "fsrl_collect_group_step": (C.c_int, [_ctx, _i32, _i32, _f, _f, _d, _d, _u8, _u8, _f, _i64, _d, _i32, _i64, _i32, _f, C.c_int32,
+                                          C.c_int32, _f, _f, _f, _f]),
+    "fsrl_collect_group_actor_set_resident": (C.c_int, [_ctx, C.c_int32, C.c_double]),
+    "fsrl_collect_group_actor_resident_stats": (C.c_int, [_ctx, _i64]),
+    "fsrl_collect_group_actor_release": (C.c_int, [_ctx]),
     "fsrl_gae_return": (C.c_int, [_ctx, _f, _f, _d, _u8, C.c_int64, C.c_double, C.c_double, _d]),
     "fsrl_nstep_return": (C.c_int, [_ctx, _d, _u8, C.c_int64, _f, _i64, C.c_int64, C.c_int64, C.c_double, C.c_int32, _d]),
     "fsrl_launch_floors": (C.c_int, [_ctx, C.c_int32, C.c_int32, _d]),

@@ -189,6 +189,7 @@ struct fsrl_ctx {
     bool probe_tile16 = false;
     struct fsrl_sac_group* sac_group = nullptr;      // the grouped SAC-Lagrangian update this context is a member of (host_sac_group.inc)
     struct fsrl_cvpo_group* cvpo_group = nullptr;    // the grouped CVPO update this context is a member of (host_cvpo_group.inc)
+    struct fsrl_collect_group* cgroup = nullptr;     // the replay agents' collect group this context is a member of (host_collect_group.inc)
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
@@ -239,6 +240,8 @@ static void pactor_release(fsrl_ctx* c);
 static void group_actor_release(fsrl_group* g);     // the group's resident actor (host_group_collect.inc): a member's stream is the group's
 static void sac_group_detach(fsrl_ctx* c);        // a member destroyed before its SAC group (host_sac_group.inc)
 static void cvpo_group_detach(fsrl_ctx* c);       // ... before its CVPO group (host_cvpo_group.inc)
+static void collect_group_detach(fsrl_ctx* c);    // ... before its collect group (host_collect_group.inc)
+static void collect_group_actor_release(struct fsrl_collect_group* g);   // that group's resident actor: it holds this member's actor weights
 // grouped FOCOPS (host_focops_group.inc): the member checks of fsrl_group_create / _ppo_update, and the update itself
 static int focops_group_check(fsrl_ctx* const* ctxs, int k);
 static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
@@ -442,6 +445,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (c->group) group_detach(c);          // a member destroyed before its group: take its own stream back
     if (c->sac_group) sac_group_detach(c);
     if (c->cvpo_group) cvpo_group_detach(c);
+    if (c->cgroup) collect_group_detach(c);
     comm_free(c);
     tr_free(c);
     sac_free(c);
@@ -991,13 +995,19 @@ static bool pactor_ok(const fsrl_ctx* c, int k) {
     return sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md);      // replay contexts: their fused actor network
 }
 
-static void pactor_release(fsrl_ctx* c) {
-    if (c->group) group_actor_release(c->group);      // a grouped member enqueues on the group's stream: its collect kernel ends too
+// the context's own resident kernel only
+static void pactor_release_own(fsrl_ctx* c) {
     if (!c->pa_live) return;
     const PaLayout l = pa_layout(c);
     c->pa_seq += 1;
     __atomic_store_n(l.bell, ((unsigned long long)PACTOR_EXIT << 32) | c->pa_seq, __ATOMIC_RELEASE);
     c->pa_live = false;
+}
+
+static void pactor_release(fsrl_ctx* c) {
+    if (c->group) group_actor_release(c->group);      // a grouped member enqueues on the group's stream: its collect kernel ends too
+    if (c->cgroup) collect_group_actor_release(c->cgroup);   // a collect group's kernel holds this member's actor weights in registers
+    pactor_release_own(c);
 }
 
 // how many workgroups of generation pa_gen have ended
@@ -1099,6 +1109,7 @@ static int pactor_wait(fsrl_ctx* c) {
 static int actor_eval_launch(fsrl_ctx* c, const float* obs, int32_t k, bool want_sigma) {
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim;
     c->pa_req = false;
+    if (c->cgroup) collect_group_actor_release(c->cgroup);     // a member's own actor call ends its collect group's kernel
     if (want_sigma && pactor_ok(c, k)) return pactor_post(c, obs, k);
     pactor_release(c);                       // a launch behind a live resident kernel would wait for its idle timeout
     // pinned staging [obs | head outputs (2*Da per row) | sigma_param]
@@ -1381,6 +1392,7 @@ extern "C" int fsrl_nstep_return(fsrl_ctx* c, const double* metric, const uint8_
 
 #include "host_layered.inc"
 
+#include "host_actor_ring.inc"
 #include "host_group.inc"
 #include "host_group_collect.inc"
 
@@ -1488,6 +1500,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_sac_group.inc"
 #include "kernels_cvpo_group.hpp"
 #include "host_cvpo_group.inc"
+#include "host_collect_group.inc"
 
 #include "host_comm.inc"
 

@@ -1,0 +1,191 @@
+// host_actor_ring.inc -- the pinned ring and the host half of the protocol of a resident actor kernel that serves SEVERAL contexts
+// from one launch and one doorbell (part of fsrl_hip.hip, before host_group.inc).  Two owners embed a GaRing: fsrl_group
+// (host_group_collect.inc: on-policy members, actor_group_resident_kernel<H, false>) and fsrl_collect_group (host_collect_group.inc:
+// replay members, actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on and the launch itself;
+// everything else -- post / ring / wait / release, generation and sequence numbers, the bounded wait -- is here.
+// Protocol as pactor_* (fsrl_hip.hip), with one doorbell for all members and a per-member row count k_m next to it.
+
+// pinned ring: [bell 8 B | pad | k_m[16] at 64 | done[64] at 128 | state[64] at 384 | pad | obs [64 * 16][Do] at 1024 |
+//               out [64 * 16][cols] | sigma_param [16][FSRL_MAX_ACT]]
+// cols = floats per output row: act_dim for the on-policy head, raw_cols for the replay actors.  Workgroup b owns rows 16 b .. 16 b + 15
+// of obs and out, so a member's rows start on a tile boundary.
+struct GaLayout { unsigned long long* bell; unsigned* k_m; unsigned* done; unsigned* state; float* obs; float* mu; float* sp; };
+static constexpr int GA_ROWS = GACTOR_MAX_WG * 16;
+
+struct GaRing {
+    bool on = true;                             // *_actor_set_resident
+    bool live = false;                          // a kernel of generation gen was launched and not told to end
+    unsigned gen = 0, seq = 0; double idle_us = 2000.0;
+    int n = 0;                                  // members
+    int blocks = 0;                             // workgroups of every launch: sum of tiles
+    int Do = 0, cols = 0;                       // observation width / floats per output row of the ring
+    int base[GACTOR_MAX_MEMBERS] = {}, tiles[GACTOR_MAX_MEMBERS] = {};   // member m: workgroups base[m] .. + tiles[m] - 1
+    int k[GACTOR_MAX_MEMBERS] = {};             // rows of each member in the request in flight
+    void* h = nullptr;                          // pinned ring (GaLayout)
+    long long launches = 0, requests = 0;       // *_actor_resident_stats
+    hipStream_t stream = nullptr;               // the stream the kernel is launched on (the owner's)
+    int (*launch)(void* owner, GaRing& r, unsigned last_seq) = nullptr;   // launches generation r.gen on r.stream
+    void* owner = nullptr;
+};
+
+static GaLayout ga_layout(const GaRing& r) {
+    char* b = (char*)r.h;
+    GaLayout l;
+    l.bell = (unsigned long long*)b; l.k_m = (unsigned*)(b + 64); l.done = (unsigned*)(b + 128); l.state = (unsigned*)(b + 384);
+    l.obs = (float*)(b + 1024);
+    l.mu = l.obs + (size_t)GA_ROWS * r.Do;
+    l.sp = l.mu + (size_t)GA_ROWS * r.cols;
+    return l;
+}
+static size_t ga_bytes(int Do, int cols) {
+    return 1024 + ((size_t)GA_ROWS * (Do + cols) + (size_t)GACTOR_MAX_MEMBERS * FSRL_MAX_ACT) * 4;
+}
+
+static void ga_release(GaRing& r) {
+    if (!r.live) return;
+    r.seq += 1;
+    __atomic_store_n(ga_layout(r).bell, ((unsigned long long)PACTOR_EXIT << 32) | r.seq, __ATOMIC_RELEASE);
+    r.live = false;
+}
+
+// how many workgroups of generation gen have ended
+static int gactor_ended_count(const GaRing& r) {
+    const GaLayout l = ga_layout(r);
+    int n = 0;
+    for (int b = 0; b < r.blocks; ++b) n += __atomic_load_n(l.state + b, __ATOMIC_ACQUIRE) == r.gen;
+    return n;
+}
+
+static double ga_now_us() {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3;
+}
+
+// Bounded wait: `ready()` polled; every 2 ms without it the ring's stream is asked.  A HIP error there -> FSRL_EHIP; an idle stream
+// (every workgroup has ended, nothing else queued) -> 1; 20 s -> FSRL_EHIP.  0 once `ready()` holds.
+template <typename F>
+static int ga_poll(GaRing& r, F&& ready, const char* what) {
+    const double t0 = ga_now_us();
+    double next_query = t0 + 2000.0;
+    for (long spins = 0;; ++spins) {
+        if (ready()) return 0;
+        if ((spins & 255) == 255) {
+            const double t = ga_now_us();
+            if (t >= next_query) {
+                next_query = t + 2000.0;
+                const hipError_t e = hipStreamQuery(r.stream);
+                if (e == hipSuccess) return ready() ? 0 : 1;
+                if (e != hipErrorNotReady) return fail(FSRL_EHIP, "%s: %s", what, hipGetErrorString(e));
+            }
+            if (t - t0 > 20.0e6) return fail(FSRL_EHIP, "%s: no answer for 20 s", what);
+        }
+        __builtin_ia32_pause();
+    }
+}
+
+// generation gen has ended (at once if none was launched); it was told to end, so this waits for a kernel on its way out
+static int gactor_wait_ended(GaRing& r) {
+    if (r.gen == 0) return 0;
+    const int rc = ga_poll(r, [&]() { return gactor_ended_count(r) == r.blocks; }, "the group's resident actor did not end");
+    return rc == 1 ? 0 : rc;                    // an idle stream: the kernel is gone
+}
+
+// the next generation through the owner's launch: its number first, the bookkeeping after a launch that went out
+static int gactor_launch(GaRing& r, unsigned last_seq) {
+    r.gen += 1;
+    if (r.gen == 0) r.gen = 1;
+    const int rc = r.launch(r.owner, r, last_seq);
+    if (rc) return rc;
+    r.live = true; r.launches += 1;
+    return 0;
+}
+
+// ring the doorbell for the request already in place (launching a kernel first if none can hear it)
+static int gactor_ring(GaRing& r) {
+    const GaLayout l = ga_layout(r);
+    if (r.live && gactor_ended_count(r) > 0) ga_release(r);      // (some of) it ended by its idle timeout: the rest follows
+    r.seq += 1;
+    if (!r.live) {
+        int rc = gactor_wait_ended(r);
+        if (rc) return rc;
+        rc = gactor_launch(r, r.seq - 1);
+        if (rc) return rc;
+    }
+    __atomic_store_n(l.bell, ((unsigned long long)1 << 32) | r.seq, __ATOMIC_RELEASE);
+    return 0;
+}
+
+// the ring and the workgroup layout: member m gets min(PACTOR_BLOCKS, ceil(env_num / 16)) tiles, as its own resident actor would
+static int gactor_ensure(GaRing& r, fsrl_ctx* const* m, int n, int cols) {
+    if (r.h) return 0;
+    const size_t bytes = ga_bytes(m[0]->cfg.obs_dim, cols);
+    HIPCHK(hipHostMalloc(&r.h, bytes));
+    memset(r.h, 0, bytes);
+    r.n = n; r.Do = m[0]->cfg.obs_dim; r.cols = cols;
+    int base = 0;
+    for (int i = 0; i < n; ++i) {
+        r.base[i] = base;
+        r.tiles[i] = std::min(PACTOR_BLOCKS, std::max(1, (m[i]->cfg.env_num + 15) / 16));
+        base += r.tiles[i];
+    }
+    r.blocks = base;
+    return 0;
+}
+
+// the common part of a launch's arguments: the ring's areas, the workgroup -> (member, tile) table, generation and timeout
+static void gactor_fill_args(const GaRing& r, GActorArgs& a, unsigned last_seq) {
+    const GaLayout l = ga_layout(r);
+    for (int i = 0; i < r.n; ++i)
+        for (int t = 0; t < r.tiles[i]; ++t) {
+            a.wg_member[r.base[i] + t] = (unsigned char)i;
+            a.wg_tile[r.base[i] + t] = (unsigned char)t;
+        }
+    a.obs = l.obs; a.mu_out = l.mu; a.sigma_param_out = l.sp; a.bell = l.bell; a.k_m = l.k_m; a.done = l.done; a.state = l.state;
+    a.gen = r.gen; a.last_seq = last_seq;
+    a.timeout_ticks = (unsigned long long)(r.idle_us * 100.0);               // wall_clock64: 100 MHz
+}
+
+// one request for every member: k_act[m] rows of obs_act (concatenated over members)
+static int gactor_post(GaRing& r, const int32_t* k_act, const float* obs_act) {
+    const int Do = r.Do;
+    const GaLayout l = ga_layout(r);
+    size_t off = 0;
+    for (int i = 0; i < r.n; ++i) {
+        const int k = k_act[i];
+        if (k > 0) memcpy(l.obs + (size_t)r.base[i] * 16 * Do, obs_act + off * Do, (size_t)k * Do * 4);
+        l.k_m[i] = (unsigned)k;
+        r.k[i] = k;
+        off += (size_t)k;
+    }
+    const int rc = gactor_ring(r);
+    if (rc) return rc;
+    r.requests += 1;
+    return 0;
+}
+
+static int gactor_wait(GaRing& r) {
+    const GaLayout l = ga_layout(r);
+    auto served = [&]() {
+        for (int i = 0; i < r.n; ++i) {
+            const int tiles = (r.k[i] + 15) / 16;
+            for (int t = 0; t < tiles; ++t)
+                if (__atomic_load_n(l.done + r.base[i] + t, __ATOMIC_ACQUIRE) != r.seq) return false;
+        }
+        return true;
+    };
+    for (;;) {
+        // a workgroup gone before it served the request (idle timeout just before the doorbell): end the rest, relaunch, ring again
+        const int rc = ga_poll(r, [&]() { return served() || gactor_ended_count(r) > 0; }, "the group's resident actor");
+        if (rc < 0 || rc > 1) return rc;
+        if (served()) return 0;
+        if (rc == 1) r.live = false;            // the stream is idle: every workgroup has ended
+        const int rr = gactor_ring(r);
+        if (rr) return rr;
+    }
+}
+
+// a member's row cap on the resident path: what its own resident actor serves
+static inline int gactor_member_rows(const fsrl_ctx* c) {
+    return 16 * std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
+}

@@ -1,0 +1,256 @@
+// host_collect_group.inc -- lock-step collection for replay-agent seeds: fsrl_collect_group_* (part of fsrl_hip.hip, after the SAC /
+// CVPO code).  k SAC-Lag, DDPG-Lag or CVPO contexts of one network shape collect with ONE library call and ONE request per vector
+// step to actor_group_resident_kernel<H, true> (kernels_mlp.hpp): a workgroup per (member, 16-row tile) running the member's ACTOR
+// network (SacState::PA, mda) and writing the raw head rows [rows][raw_cols] to the pinned ring; the host then finishes each member
+// as its own fsrl_collect_step would (sac_actor_finish, actor_draw from ITS xoshiro stream, map_env_action with its bounds).  The
+// ring and the protocol are host_actor_ring.inc's (GaRing), shared with the on-policy group (host_group_collect.inc).
+// The object is independent of the update groups: a member may at the same time be in an fsrl_sac_group / fsrl_cvpo_group, keeps its
+// own streams, store and resident actor, and is not owned.
+//
+// Ordering.  The kernel runs on a stream of the collect group's own and holds every member's actor weights in registers / LDS from
+// its prologue on, so:
+//   * launch: a request must be answered with the parameters the member's own actor call would have used at that point of the host
+//     program.  Before a generation is launched, an event is recorded on EACH member's compute stream and the group's stream waits
+//     on it: the kernel's prologue reads the parameters behind everything the members have enqueued (grouped updates make the
+//     members' streams wait on the update group's `done` event, so they are covered).  The members' own resident actors are told to
+//     end first -- an event behind a live one would only complete at its idle timeout.
+//   * release: the kernel is told to end (EXIT) before anything can change a member's actor.  pactor_release carries the hook
+//     (c->cgroup), so every ENTER_DEV entry point does it -- a member's own updates, fsrl_sac_put_params, fsrl_sac_group_update and
+//     fsrl_cvpo_group_update (ENTER_DEV for every active member) -- and so does a member's own actor call (actor_eval_launch).
+//     fsrl_store_push keeps it alive (plain hipSetDevice), as it keeps the solo resident actor.
+//   * after EXIT nothing is waited for.  Requests are synchronous, so none is in flight at release: every workgroup that had rows in
+//     a request is past its prologue.  A workgroup that never had rows may still be in its prologue when a member's stream overwrites
+//     the parameters; what it reads then it never uses -- the next doorbell it sees is EXIT.  The NEXT generation is only launched
+//     once every workgroup of this one has stored its `state` word (gactor_wait_ended), behind the events above.
+//   * fsrl_ctx_destroy of a member breaks the group (collect_group_detach: later steps fail with FSRL_ESTATE, destroy still works).
+//   * the wait is ga_poll's: hipStreamQuery every 2 ms, a HIP error fails the call, an idle stream relaunches, 20 s fails.
+// The step path allocates nothing: ring, stream and events are made at create.
+// ====================================================================================== replay agents' collect group
+struct fsrl_collect_group {
+    std::vector<fsrl_ctx*> m;                  // members (not owned; all nullptr once one was destroyed)
+    int device = 0;
+    hipStream_t stream = nullptr;              // the kernel's stream
+    std::vector<hipEvent_t> ready;             // per member: its compute stream's work before a launch
+    bool broken = false;
+    int raw_cols = 0;
+    GaRing ga;
+};
+
+static void collect_group_actor_release(fsrl_collect_group* g) { ga_release(g->ga); }
+
+static void collect_group_detach(fsrl_ctx* c) {
+    fsrl_collect_group* g = c->cgroup;
+    if (!g) return;
+    ga_release(g->ga);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (auto& x : g->m) if (x) { x->cgroup = nullptr; x = nullptr; }
+    g->broken = true;
+}
+
+// GaRing::launch: order the group's stream behind every member's compute stream, then the RAW kernel over the members' actor networks
+static int collect_group_launch(void* owner, GaRing& r, unsigned last_seq) {
+    fsrl_collect_group* g = (fsrl_collect_group*)owner;
+    GActorArgs a{};
+    const ModelDesc* md0 = nullptr;
+    for (size_t i = 0; i < g->m.size(); ++i) {
+        fsrl_ctx* c = g->m[i];
+        const float* P; const ModelDesc* md;
+        if (!sac_actor_resident_args(c, &P, &md)) return fail(FSRL_ESTATE, "member %d has no fused actor network", (int)i);
+        a.P[i] = P;
+        if (i == 0) md0 = md;
+        pactor_release_own(c);                  // its own resident actor: the event below would wait for its idle timeout
+        HIPCHK(hipEventRecord(g->ready[i], c->compute));
+        HIPCHK(hipStreamWaitEvent(g->stream, g->ready[i], 0));
+    }
+    gactor_fill_args(r, a, last_seq);
+    a.max_action = 1.0f; a.raw_cols = g->raw_cols;
+    const ModelDesc mdv = *md0;
+    return dispatch_H(g->m[0]->cfg.hidden, [&](auto hc) {
+        constexpr int H = decltype(hc)::value;
+        hipLaunchKernelGGL((actor_group_resident_kernel<H, true>), dim3(r.blocks), dim3(4 * H), 0, r.stream, mdv, a);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int fsrl_collect_group_destroy(fsrl_collect_group* g) {
+    if (!g) return 0;
+    (void)hipSetDevice(g->device);
+    ga_release(g->ga);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (fsrl_ctx* c : g->m) if (c) c->cgroup = nullptr;
+    for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
+    if (g->stream) (void)hipStreamDestroy(g->stream);
+    if (g->ga.h) (void)hipHostFree(g->ga.h);
+    delete g;
+    return 0;
+}
+
+static int collect_group_kind(const SacState* s) { return s->ddpg ? 1 : s->cvpo ? 2 : 0; }
+
+extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collect_group** out) {
+    CHECK_ARG(ctxs && out, "null argument");
+    CHECK_ARG(k >= 1 && k <= GACTOR_MAX_MEMBERS, "a collect group has 1..%d members", GACTOR_MAX_MEMBERS);
+    static const char* const kinds[] = {"SAC-Lagrangian", "DDPG-Lagrangian", "CVPO"};
+    fsrl_ctx* c0 = ctxs[0];
+    for (int i = 0; i < k; ++i) {
+        fsrl_ctx* c = ctxs[i];
+        CHECK_ARG(c, "null member");
+        CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG,
+                  "member %d is an on-policy context: collect groups take replay contexts (SAC-Lag, DDPG-Lag, CVPO); on-policy seeds "
+                  "collect through fsrl_group_create / fsrl_group_collect_step", i);
+        const SacState* s = sac_of(c);
+        CHECK_ARG(s, "member %d is not initialised: fsrl_sac_init / fsrl_cvpo_init first", i);
+        CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: it has no fused actor network for the resident kernel", i);
+        const SacState* s0 = sac_of(c0);
+        CHECK_ARG(!s0 || collect_group_kind(s) == collect_group_kind(s0),
+                  "member %d is a %s context, member 0 a %s one: a collect group has one kind of member", i, kinds[collect_group_kind(s)],
+                  kinds[collect_group_kind(s0)]);
+        CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
+        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden,
+                  "member %d: members must have one network shape (obs_dim, act_dim, hidden)", i);
+        for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member %d is listed twice", i);
+        CHECK_ARG(!c->cgroup, "member %d is already in a collect group", i);
+    }
+    HIPCHK(hipSetDevice(c0->device));
+    for (int i = 0; i < k; ++i) pactor_release(ctxs[i]);       // the allocations below would wait for a live resident actor's idle timeout
+    fsrl_collect_group* g = new fsrl_collect_group();
+    g->device = c0->device;
+    g->raw_cols = sac_raw_cols(c0);
+    g->ready.assign((size_t)k, nullptr);
+    for (int i = 0; i < k; ++i) g->m.push_back(ctxs[i]);
+    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+    for (int i = 0; i < k && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&g->ready[(size_t)i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        fail(FSRL_EHIP, "collect group allocation failed: %s", hipGetErrorString(e));
+        g->m.clear();
+        (void)fsrl_collect_group_destroy(g);
+        return FSRL_EHIP;
+    }
+    g->ga.stream = g->stream; g->ga.launch = collect_group_launch; g->ga.owner = g;
+    const int rc = gactor_ensure(g->ga, g->m.data(), k, g->raw_cols);
+    if (rc) { g->m.clear(); (void)fsrl_collect_group_destroy(g); return rc; }
+    for (int i = 0; i < k; ++i) ctxs[i]->cgroup = g;
+    *out = g;
+    return 0;
+}
+
+// fsrl_collect_step on every member, in member order, with one request to the group's kernel.  Row arrays are concatenated over
+// members; k[m] / k_act[m] may be 0; act_low / act_high: NULL or [members][act_dim].
+extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, const int32_t* env_ids, const float* obs, const float* act,
+                                       const double* rew, const double* cost, const uint8_t* terminated, const uint8_t* truncated,
+                                       const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out,
+                                       int64_t* ep_idx_out, const int32_t* k_act, const float* obs_act, int32_t deterministic,
+                                       int32_t bound_method, const float* act_low, const float* act_high, float* act_out,
+                                       float* env_act_out) {
+    CHECK_ARG(g && k && k_act, "null argument");
+    if (g->broken) return fail(FSRL_ESTATE, "a member of this collect group has been destroyed");
+    const int n = (int)g->m.size();
+    fsrl_ctx* c0 = g->m[0];
+    const int Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim, rcols = g->raw_cols;
+    int64_t rows = 0, rows_act = 0;
+    bool resident = g->ga.on;
+    for (int i = 0; i < n; ++i) {
+        CHECK_ARG(k[i] >= 0 && k_act[i] >= 0, "negative row count (member %d)", i);
+        rows += k[i]; rows_act += k_act[i];
+        const fsrl_ctx* c = g->m[i];
+        resident = resident && !c->no_spin && k_act[i] <= gactor_member_rows(c);
+    }
+    CHECK_ARG(rows_act == 0 || (obs_act && act_out), "obs_act / act_out missing");
+    CHECK_ARG(rows == 0 || env_ids, "env_ids missing");
+    CHECK_ARG(bound_method >= 0 && bound_method <= 2, "bound_method: 0 none, 1 clip, 2 tanh");
+    CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
+    HIPCHK(hipSetDevice(g->device));            // keeps the group's resident actor alive
+    // 1. one request for every member (or, off the resident path, every member's own actor call)
+    int rc = 0;
+    if (rows_act > 0) {
+        if (resident) {
+            rc = gactor_post(g->ga, k_act, obs_act);
+            if (rc) return rc;
+        } else {
+            ga_release(g->ga);
+            size_t off = 0;
+            for (int i = 0; i < n; ++i) {
+                if (k_act[i] > 0) {
+                    rc = actor_eval_launch(g->m[i], obs_act + off * Do, k_act[i], true);
+                    if (rc) return rc;
+                }
+                off += (size_t)k_act[i];
+            }
+        }
+    }
+    // 2. every member's finished transitions into its own store (flushes on the member's side stream)
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (k[i] > 0) {
+            const size_t o = off;
+            rc = fsrl_store_push(g->m[i], env_ids + o, k[i], obs + o * Do, act + o * Da, rew + o, cost ? cost + o : nullptr,
+                                 terminated + o, truncated + o, obs_next + o * Do, ptr_out ? ptr_out + o : nullptr,
+                                 ep_rew_out ? ep_rew_out + o : nullptr, ep_len_out ? ep_len_out + o : nullptr,
+                                 ep_idx_out ? ep_idx_out + o : nullptr);
+            if (rc) {                           // leave no evaluation in flight behind the error
+                if (rows_act > 0 && resident) (void)gactor_wait(g->ga);
+                else if (rows_act > 0)
+                    for (int j = 0; j < n; ++j) {
+                        fsrl_ctx* c = g->m[j];
+                        if (k_act[j] <= 0) continue;
+                        c->act_mu.resize((size_t)k_act[j] * Da); c->act_sg.resize((size_t)k_act[j] * Da);
+                        (void)actor_eval_finish(c, c->act_mu.data(), c->act_sg.data());
+                    }
+                return rc;
+            }
+        }
+        off += (size_t)k[i];
+    }
+    if (rows_act == 0) return 0;
+    // 3. wait; 4. per member in order: mean / std from its raw rows, its noise from its own stream, then map_action
+    if (resident) {
+        rc = gactor_wait(g->ga);
+        if (rc) return rc;
+    }
+    const GaLayout l = resident ? ga_layout(g->ga) : GaLayout{};
+    off = 0;
+    for (int i = 0; i < n; ++i) {
+        const int ka = k_act[i];
+        fsrl_ctx* c = g->m[i];
+        if (ka > 0) {
+            float* ao = act_out + off * Da;
+            if (resident) {
+                c->actor_k = ka;
+                c->act_mu.resize((size_t)ka * Da); c->act_sg.resize((size_t)ka * Da);
+                sac_actor_finish(c, l.mu + (size_t)g->ga.base[i] * 16 * rcols, ka, c->act_mu.data(), c->act_sg.data());
+                actor_draw(c, deterministic, ao);
+            } else {
+                rc = actor_sample_finish(c, deterministic, ao);
+                if (rc) return rc;
+            }
+            if (env_act_out)
+                map_env_action(Da, ka, bound_method, act_low ? act_low + (size_t)i * Da : nullptr,
+                               act_high ? act_high + (size_t)i * Da : nullptr, ao, env_act_out + off * Da);
+        }
+        off += (size_t)ka;
+    }
+    return 0;
+}
+
+extern "C" int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us) {
+    CHECK_ARG(g, "null group");
+    CHECK_ARG(idle_timeout_us <= 1.0e6, "idle_timeout_us above one second");
+    ga_release(g->ga);
+    g->ga.on = on != 0;
+    if (idle_timeout_us > 0.0) g->ga.idle_us = idle_timeout_us;
+    return 0;
+}
+
+// out3 = {kernel launches, requests served through the doorbell, 1 if the group's resident kernel is live now}
+extern "C" int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3) {
+    CHECK_ARG(g && out3, "null argument");
+    out3[0] = g->ga.launches; out3[1] = g->ga.requests; out3[2] = g->ga.live ? 1 : 0;
+    return 0;
+}
+
+extern "C" int fsrl_collect_group_actor_release(fsrl_collect_group* g) {
+    CHECK_ARG(g, "null group");
+    ga_release(g->ga);
+    return 0;
+}

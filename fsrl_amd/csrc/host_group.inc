@@ -23,15 +23,7 @@ struct fsrl_group {
     FocGroupStep* d_fsteps = nullptr; FocGroupStep* h_fsteps = nullptr;
     size_t cap_fmb = 0;
     // lock-step collection (host_group_collect.inc): ONE resident actor kernel for every member, rung through ONE doorbell
-    bool ga_on = true;                          // fsrl_group_actor_set_resident
-    bool ga_live = false;                       // a kernel of generation ga_gen was launched and not told to end
-    unsigned ga_gen = 0, ga_seq = 0; double ga_idle_us = 2000.0;
-    int ga_blocks = 0;                          // workgroups of every launch: sum of ga_tiles
-    int ga_do = 0, ga_da = 0;                   // observation / action width of the ring (the members' shape)
-    int ga_base[FSRL_MAX_GROUP] = {}, ga_tiles[FSRL_MAX_GROUP] = {};   // member m: workgroups ga_base[m] .. + ga_tiles[m] - 1
-    int ga_k[FSRL_MAX_GROUP] = {};              // rows of each member in the request in flight
-    void* h_ga = nullptr;                       // pinned ring (GaLayout)
-    long long ga_launches = 0, ga_requests = 0; // fsrl_group_actor_resident_stats
+    GaRing ga;                                  // ring, protocol state and counters (host_actor_ring.inc); its stream is `stream`
 };
 
 extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
@@ -121,7 +113,7 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (g->d_steps) (void)hipFree(g->d_steps);
     if (g->h_steps) (void)hipHostFree(g->h_steps);
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
-    if (g->h_ga) (void)hipHostFree(g->h_ga);
+    if (g->ga.h) (void)hipHostFree(g->ga.h);
     if (g->d_ftab) (void)hipFree(g->d_ftab);
     if (g->h_ftab) (void)hipHostFree(g->h_ftab);
     if (g->d_fsteps) (void)hipFree(g->d_fsteps);

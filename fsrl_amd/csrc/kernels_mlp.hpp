@@ -587,13 +587,16 @@ __global__ __launch_bounds__(4 * H) void actor_resident_kernel(const float* __re
 // kernel arguments (block-uniform), and it runs member m's parameters P[m] over rows 16 t .. of member m's request: k_m[m] rows,
 // written by the host before the doorbell.  A member with no rows in a request is skipped by its workgroups.  Same staging, same
 // tile_forward, same head as the single-context kernels: every member's actions are bit-identical to its own actor's.
+// RAW (the replay agents' collect group, host_collect_group.inc): what actor_resident_kernel<H, true> is to <H, false>.  P[m] is member
+// m's ACTOR network, md its one-network ModelDesc, and the output is the head as tile_forward left it, [rows][raw_cols] per member
+// (raw_cols <= FSRL_MAX_ACT: [mu | log sigma], or the mean head alone for DDPG-Lag), element-strided over the block.  No sigma_param.
 #define GACTOR_MAX_MEMBERS 16
 #define GACTOR_MAX_WG (GACTOR_MAX_MEMBERS * PACTOR_BLOCKS)
 struct GActorArgs {
     const float* P[GACTOR_MAX_MEMBERS];   // each member's parameter vector (one network shape: one ModelDesc)
     const float* obs;                     // pinned [GACTOR_MAX_WG * 16 rows][Do]
-    float* mu_out;                        // pinned [GACTOR_MAX_WG * 16 rows][Da]
-    float* sigma_param_out;               // pinned [GACTOR_MAX_MEMBERS][FSRL_MAX_ACT]
+    float* mu_out;                        // pinned [GACTOR_MAX_WG * 16 rows][Da]; RAW: [GACTOR_MAX_WG * 16 rows][raw_cols]
+    float* sigma_param_out;               // pinned [GACTOR_MAX_MEMBERS][FSRL_MAX_ACT] (not RAW)
     const unsigned long long* bell;       // pinned: (1 << 32 | seq) for a request, (EXIT << 32 | seq) to end
     const unsigned* k_m;                  // pinned [GACTOR_MAX_MEMBERS]: rows of each member in the request the doorbell announces
     unsigned* done;                       // pinned [GACTOR_MAX_WG]: seq of the last request workgroup b served
@@ -602,9 +605,10 @@ struct GActorArgs {
     unsigned long long timeout_ticks;
     float max_action;
     unsigned char wg_member[GACTOR_MAX_WG], wg_tile[GACTOR_MAX_WG];
+    int raw_cols;                         // RAW: head outputs per row
 };
 
-template <int H>
+template <int H, bool RAW = false>
 __global__ __launch_bounds__(4 * H) void actor_group_resident_kernel(const ModelDesc md, const GActorArgs a) {
     __shared__ TileSmem<H> sm;
     __shared__ unsigned k_s, seq_s;
@@ -660,16 +664,27 @@ __global__ __launch_bounds__(4 * H) void actor_group_resident_kernel(const Model
         }
         __syncthreads();
         tile_forward<H>(sm, P, no, Do, tid, wf);
-        if (tile == 0 && tid < md.Da && no.sigma >= 0) a.sigma_param_out[mem * FSRL_MAX_ACT + tid] = sm.sig[tid];
-        if (tid < n_valid) {
-            const int r = blk * 16 + tid;
-            for (int d = 0; d < md.Da; ++d) {
-                const float x = sm.out[tid * FSRL_MAX_ACT + d];
-                a.mu_out[r * md.Da + d] = md.unbounded ? x : a.max_action * tanhf(x);
+        if constexpr (RAW) {
+            // elements 0 .. n_valid * raw_cols - 1 by threads of the same number (16 * raw_cols <= 256 <= NT: one round): every wave that
+            // stored fences below, and no other (raw_cols 16: four waves; a fence is an L2 write-back per wave and they serialise)
+            const int n_out = n_valid * a.raw_cols;
+            if (tid < n_out) {
+                const int i = tid / a.raw_cols, o = tid - i * a.raw_cols;
+                a.mu_out[(blk * 16 + i) * a.raw_cols + o] = sm.out[i * FSRL_MAX_ACT + o];
             }
+            if (tid < ((n_out + 63) & ~63)) __atomic_thread_fence(__ATOMIC_RELEASE);
+        } else {
+            if (tile == 0 && tid < md.Da && no.sigma >= 0) a.sigma_param_out[mem * FSRL_MAX_ACT + tid] = sm.sig[tid];
+            if (tid < n_valid) {
+                const int r = blk * 16 + tid;
+                for (int d = 0; d < md.Da; ++d) {
+                    const float x = sm.out[tid * FSRL_MAX_ACT + d];
+                    a.mu_out[r * md.Da + d] = md.unbounded ? x : a.max_action * tanhf(x);
+                }
+            }
+            // rows by threads 0 .. 15, sigma_param by threads below Da: only wave 0 stored to pinned memory and fences (r6)
+            if (tid < 64) __atomic_thread_fence(__ATOMIC_RELEASE);
         }
-        // rows by threads 0 .. 15, sigma_param by threads below Da: only wave 0 stored to pinned memory and fences (r6)
-        if (tid < 64) __atomic_thread_fence(__ATOMIC_RELEASE);
         __syncthreads();
         if (tid == 0) __hip_atomic_store(a.done + blk, seq_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }

@@ -1,4 +1,6 @@
-"""Lock-step collection for the members of a grouped PPO-Lagrangian or FOCOPS run (multi-seed on one GPU).
+"""Lock-step collection for the members of a grouped run (multi-seed on one GPU): PPO-Lagrangian or FOCOPS seeds through their
+PolicyGroup / EngineGroup, SAC-Lag, DDPG-Lag or CVPO seeds through an EngineCollectGroup (fsrl_collect_group_step: the replay
+agents' collect group, independent of their update groups).
 
 `GroupCollector(policy_group, collectors).collect(n_episode)` is `collector.collect(n_episode)` of every member, with the members'
 vector envs stepped in lock step and ONE library call per vector step for all of them (`EngineGroup.collect_step` ->
@@ -15,7 +17,8 @@ import numpy as np
 
 class GroupCollector:
     def __init__(self, policy_group, collectors: Sequence):
-        # policy_group: a PolicyGroup (its EngineGroup is used) or anything with EngineGroup's collect_step / actor_release
+        # policy_group: a PolicyGroup (its EngineGroup is used), an EngineCollectGroup (replay agents) or anything with
+        # EngineGroup's collect_step / actor_release
         self.group = getattr(policy_group, "group", policy_group)
         self.collectors = list(collectors)
         engines = getattr(self.group, "engines", None)

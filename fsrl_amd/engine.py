@@ -709,35 +709,15 @@ class Engine:
                     fwdbwd_raw_ms=out[4])
 
 
-class EngineGroup:
-    """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
-    (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
-    random streams; use the engines as usual for everything else (push, collect_step, get_params ...)."""
-
-    def __init__(self, engines):
-        self.engines = list(engines)
-        assert self.engines, "a group needs at least one engine"
-        self.lib = self.engines[0].lib
-        k = len(self.engines)
-        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
-        self._g = C.c_void_p()
-        self._collect_stage = None      # cached staging arrays + ctypes pointers of collect_step
-        _lib.check(self.lib.fsrl_group_create(arr, k, C.byref(self._g)))
-
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _LockStepCollect:
+    """collect_step of an object that owns `engines`, a native group handle `_g` and a `_collect_step_symbol` with
+    fsrl_group_collect_step's signature: the staging arrays and the call, shared by EngineGroup and EngineCollectGroup."""
+    _collect_stage = None               # cached staging arrays + ctypes pointers of collect_step
 
     def collect_step(self, prevs, obs_acts, deterministic=False, bound_method=1, low=None, high=None):
-        """Engine.collect_step on every member in ONE call with ONE actor request (fsrl_group_collect_step).  prevs / obs_acts: per
-        member what Engine.collect_step takes (None allowed); low / high: None, one array for every member or a per-member list.
+        """Engine.collect_step on every member in ONE call with ONE actor request (fsrl_group_collect_step for an EngineGroup,
+        fsrl_collect_group_step for an EngineCollectGroup).  prevs / obs_acts: per member what Engine.collect_step takes (None
+        allowed); low / high: None, one array for every member or a per-member list.
         -> per member (act, env_act, ep_rew, ep_len), as Engine.collect_step.  Staging arrays / ctypes pointers are cached."""
         engs = self.engines
         n = len(engs)
@@ -776,7 +756,7 @@ class EngineGroup:
             o += ka
         if low is not None:
             a["lo"][:] = np.asarray(low, np.float32).reshape(-1, Da); a["hi"][:] = np.asarray(high, np.float32).reshape(-1, Da)
-        _lib.check(self.lib.fsrl_group_collect_step(
+        _lib.check(getattr(self.lib, self._collect_step_symbol)(
             self._g, p["k"], p["ids"], p["obs"], p["act"], p["rew"], p["cost"], p["term"], p["trunc"], p["nxt"], p["ptr"],
             p["er"], p["el"], p["ei"], p["ka"], p["oa"], int(deterministic), int(bound_method),
             p["lo"] if low is not None else None, p["hi"] if low is not None else None, p["ao"], p["eo"]))
@@ -792,6 +772,34 @@ class EngineGroup:
         a = self._collect_stage["a"]
         k = int(a["k"].sum())
         return a["ptr"][:k], a["ei"][:k]
+
+
+class EngineGroup(_LockStepCollect):
+    """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
+    (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
+    random streams; use the engines as usual for everything else (push, collect_step, get_params ...)."""
+
+    _collect_step_symbol = "fsrl_group_collect_step"
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        assert self.engines, "a group needs at least one engine"
+        self.lib = self.engines[0].lib
+        k = len(self.engines)
+        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
+        self._g = C.c_void_p()
+        _lib.check(self.lib.fsrl_group_create(arr, k, C.byref(self._g)))
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def actor_set_resident(self, on=True, idle_timeout_us=0.0):
         """The group's resident collect kernel (include/fsrl_hip.h: fsrl_group_actor_set_resident); on by default."""
@@ -918,3 +926,46 @@ class EngineCvpoGroup:
         k = len(self.engines)
         n = np.ascontiguousarray(n_updates, np.int32).reshape(k)
         _lib.check(self.lib.fsrl_cvpo_group_update(self._g, int(batch_size), _ptr(n, _i32p)))
+
+
+class EngineCollectGroup(_LockStepCollect):
+    """k replay-agent engines (all SAC-Lag, all DDPG-Lag or all CVPO: sac_init / cvpo_init) of one network shape on one GPU that
+    COLLECT in lock step (fsrl_collect_group_*): one library call and one request to one resident actor kernel per vector step
+    for all members, per member bit-identical to its own collect_step.  Independent of the update groups: the members may also
+    be in an EngineSacGroup / EngineCvpoGroup, and stay ordinary engines.  EngineGroup's collect interface, so
+    GroupCollector(engine_collect_group, collectors) drives it."""
+    _collect_step_symbol = "fsrl_collect_group_step"
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        assert self.engines, "a group needs at least one engine"
+        self.lib = self.engines[0].lib
+        k = len(self.engines)
+        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
+        self._g = C.c_void_p()
+        _lib.check(self.lib.fsrl_collect_group_create(arr, k, C.byref(self._g)))
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_collect_group_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def actor_set_resident(self, on=True, idle_timeout_us=0.0):
+        """The group's resident collect kernel (include/fsrl_hip.h: fsrl_collect_group_actor_set_resident); on by default."""
+        _lib.check(self.lib.fsrl_collect_group_actor_set_resident(self._g, int(bool(on)), float(idle_timeout_us)))
+
+    def actor_release(self):
+        """End the group's resident collect kernel now (a grouped collect is over)."""
+        if getattr(self, "_g", None) is not None and self._g:
+            self.lib.fsrl_collect_group_actor_release(self._g)
+
+    def actor_resident_stats(self):
+        out = np.zeros(3, np.int64)
+        _lib.check(self.lib.fsrl_collect_group_actor_resident_stats(self._g, _ptr(out, _i64p)))
+        return dict(launches=int(out[0]), requests=int(out[1]), live=bool(out[2]))

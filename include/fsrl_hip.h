@@ -621,6 +621,41 @@ int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g);
  * next work.                                                                                                                */
 int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t* n_updates);
 
+/* ---- Lock-step collection for replay-agent seeds: k SAC-Lag, k DDPG-Lag or k CVPO contexts (FSRL_ALGO_SAC_LAG after
+ *      fsrl_sac_init / fsrl_cvpo_init) on one device collect with ONE call and ONE request per vector step to one resident actor
+ *      kernel (a workgroup per member and 16-row tile, running the member's actor network; raw head rows come back through a
+ *      pinned ring).  Per member every result is bit-identical to fsrl_collect_step on that member: its own store and side
+ *      stream, its own noise stream, its own bounds.  The object is independent of the update groups: a member may also be in an
+ *      fsrl_sac_group or fsrl_cvpo_group, keeps its own streams and its own resident actor, and is not owned.
+ *      The kernel runs on a stream of the group's own.  Before it is launched that stream waits for everything the members have
+ *      enqueued on their compute streams; it holds the actors' weights in registers, so it is told to end by everything that
+ *      can change a member's actor or runs the member's actor itself (every member entry point but fsrl_store_push and the
+ *      read-only queries: own updates, fsrl_sac_put_params, fsrl_sac_group_update / fsrl_cvpo_group_update, own
+ *      fsrl_collect_step / fsrl_actor_sample), by fsrl_collect_group_actor_release, and by its idle timeout; the next step
+ *      launches it again.
+ *      create rejects with FSRL_EINVAL and the reason in fsrl_last_error: on-policy contexts (fsrl_group_create is theirs),
+ *      layered contexts (no fused actor network), contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds, another device or
+ *      network shape (obs_dim, act_dim, hidden), a member listed twice or already in a collect group, k outside 1..16.
+ *      A member destroyed before its group breaks it: later steps fail with FSRL_ESTATE, fsrl_collect_group_destroy still works. */
+typedef struct fsrl_collect_group fsrl_collect_group;
+int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collect_group** out);
+int fsrl_collect_group_destroy(fsrl_collect_group* g);
+/* fsrl_collect_step on every member in member order; arguments as fsrl_group_collect_step: row arrays concatenated over members,
+ * k[m] / k_act[m] >= 0 rows of member m, act_low / act_high NULL or [members][act_dim].  Off the resident path
+ * (fsrl_collect_group_actor_set_resident(0), a member that waits with stream synchronisations, a member asking for more than its
+ * 16 * min(4, ceil(env_num / 16)) rows) every member's own actor call runs inside the same call: the same bits.             */
+int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, const int32_t* env_ids, const float* obs, const float* act,
+                            const double* rew, const double* cost, const uint8_t* terminated, const uint8_t* truncated,
+                            const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out, int64_t* ep_idx_out,
+                            const int32_t* k_act, const float* obs_act, int32_t deterministic, int32_t bound_method,
+                            const float* act_low, const float* act_high, float* act_out, float* env_act_out);
+/* on = 0: no resident kernel; idle_timeout_us > 0 sets the idle timeout (default 2000, at most 1e6).  Ends a live kernel.     */
+int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us);
+/* out3 = {kernel launches, requests served through the doorbell, 1 if the kernel is live now}                                 */
+int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3);
+/* the collect is over: end the kernel now instead of at its idle timeout                                                      */
+int fsrl_collect_group_actor_release(fsrl_collect_group* g);
+
 /* ---- timing of the last update, measured with hipEvents on the compute stream --------- */
 /* out[0] = process_fn ms, out[1] = learn ms (all passes), out[2] = fused fwd/bwd kernel
  * total ms over the update (sum of per-launch event pairs when profiling is enabled),

@@ -9,7 +9,12 @@ member).  For every k, in one process and alternating `--rounds` times, aggregat
 Also: us per grouped actor call at k x 20 rows against one member's 20-row resident call, resident launches per lock-step collect, and
 a collect + grouped update loop (aggregate env-steps/s and updates/s).  Prints ONE JSON line.
 
-    python tools/bench_group_collect.py [--ks 1,2,4,8] [--rounds 3]
+--algo sacl | ddpgl | cvpo: the replay agents' collect group (GroupCollector over an EngineCollectGroup -> fsrl_collect_group_step).
+Modes: seq_ungrouped (each member's own FastCollector with its own resident actor) and lockstep; the same per-call figures and
+launches per collect; the loop is lock-step collection + round(0.2 * n/st) updates per seed through SACPolicyGroup / CVPOPolicyGroup
+(DDPG-Lag: each seed's own updates, one seed after the other).
+
+    python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3]
 """
 import argparse
 import json
@@ -23,16 +28,17 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _agents(k, envs, first_seed, device):
-    from fsrl_amd.agent import PPOLagAgent
+def _agents(k, envs, first_seed, device, algo="ppol"):
+    from fsrl_amd.agent import CVPOAgent, DDPGLagAgent, PPOLagAgent, SACLagAgent
+    Agent = {"ppol": PPOLagAgent, "sacl": SACLagAgent, "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}[algo]
     from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
     from fsrl_amd.env import SyntheticSafetyVectorEnv
     from fsrl_amd.utils import BaseLogger
     agents, cols, bufs = [], [], []
     for s in range(first_seed, first_seed + k):
         env = SyntheticSafetyVectorEnv(env_num=envs, obs_dim=8, act_dim=2, episode_len=300, seed=s)
-        ag = PPOLagAgent(env, BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_bgc{s}_"), name=f"s{s}"), cost_limit=10.0, device=device,
-                         seed=s, hidden_sizes=(256, 256), training_num=envs)
+        ag = Agent(env, BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_bgc{s}_"), name=f"s{s}"), cost_limit=10.0, device=device,
+                   seed=s, hidden_sizes=(256, 256), training_num=envs)
         ag.policy.train()
         buf = HipVectorReplayBuffer(ag.policy.engine, None, envs)
         agents.append(ag); bufs.append(buf); cols.append(FastCollector(ag.policy, env, buf, exploration_noise=True, device_actor=True))
@@ -63,14 +69,90 @@ def _call_us(fn, n):
     return (time.perf_counter() - t) / n * 1e6
 
 
+def _replay(a):
+    """--algo sacl / ddpgl / cvpo: the collect group of the replay agents"""
+    from fsrl_amd.data import GroupCollector
+    from fsrl_amd.engine import EngineCollectGroup
+    from fsrl_amd.policy import CVPOPolicyGroup, SACPolicyGroup
+    n_ep = a.envs
+    res = {"algo": a.algo, "envs": a.envs, "hidden": 256, "rounds": a.rounds, "k": {}}
+    for k in [int(x) for x in a.ks.split(",")]:
+        solo_agents, solo_cols, _ = _agents(k, a.envs, 0, a.device, a.algo)
+        grp_agents, grp_cols, grp_bufs = _agents(k, a.envs, 0, a.device, a.algo)
+        cg = EngineCollectGroup([ag.policy.engine for ag in grp_agents])
+        gc = GroupCollector(cg, grp_cols)
+        t = {"seq_ungrouped": [], "lockstep": []}
+        launches, collects = 0, 0
+        _seq(solo_cols, n_ep); _lock(gc, grp_cols, n_ep)          # warm-up: code loading, first launches
+        for _ in range(a.rounds):
+            for mode in t:
+                l0 = cg.actor_resident_stats()["launches"]
+                t0 = time.perf_counter()
+                if mode == "seq_ungrouped":
+                    st = _seq(solo_cols, n_ep)
+                else:
+                    st = _lock(gc, grp_cols, n_ep)
+                    launches += cg.actor_resident_stats()["launches"] - l0
+                    collects += 1
+                t[mode].append(st / (time.perf_counter() - t0))
+        out = {m: round(float(np.median(v))) for m, v in t.items()}
+        out["all"] = {m: [round(x) for x in v] for m, v in t.items()}
+        out["spread"] = {m: round(max(v) - min(v)) for m, v in t.items()}
+        out["lockstep_over_seq_ungrouped"] = round(out["lockstep"] / out["seq_ungrouped"], 3)
+        out["launches_per_collect"] = round(launches / max(collects, 1), 2)
+        out["rows_per_member_per_collect"] = n_ep * 300
+        rng = np.random.default_rng(0)
+        obs = rng.standard_normal((a.envs, 8)).astype(np.float32)
+        e0 = solo_agents[0].policy.engine
+        out["us_member_call"] = round(_call_us(lambda: e0.collect_step(None, obs, False, 1), a.calls), 2)
+        e0.actor_release()
+        out["us_group_call"] = round(_call_us(lambda: cg.collect_step([None] * k, [obs] * k, False, 1), a.calls), 2)
+        cg.actor_release()
+        out["group_call_over_member_call"] = round(out["us_group_call"] / out["us_member_call"], 3)
+        # collect + update, the training loop's shape (examples/train_multi_seed.py --grouped): update_per_step 0.2
+        group = None if a.algo == "ddpgl" else (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in grp_agents])
+        steps, updates = 0, 0
+        t0 = time.perf_counter()
+        for _ in range(2):
+            sts = gc.collect(n_episode=n_ep)
+            n = []
+            for ag, st in zip(grp_agents, sts):
+                ag.policy.pre_update_fn(stats_train=st)
+                steps += st["n/st"]
+                n.append(round(0.2 * st["n/st"]))
+            if group is not None:
+                group.update(grp_bufs, batch_size=256, n_updates=n)
+            else:
+                for ag, buf, n_i in zip(grp_agents, grp_bufs, n):
+                    for _ in range(n_i):
+                        ag.policy.update(256, buf)
+            for ag, st in zip(grp_agents, sts):
+                ag.policy.post_update_fn(stats_train=st)
+            updates += sum(n)
+        dt = time.perf_counter() - t0
+        out["loop_env_steps_per_s"] = round(steps / dt)
+        out["loop_updates_per_s"] = round(updates / dt, 1)
+        res["k"][str(k)] = out
+        cg.close()
+        if group is not None:
+            group.close()
+        for ag in solo_agents + grp_agents:
+            ag.policy.engine.close()
+        print(f"k={k}: {json.dumps(out)}", file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=("ppol", "sacl", "ddpgl", "cvpo"), default="ppol")
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
+    if a.algo != "ppol":
+        return _replay(a)
     from fsrl_amd.data import GroupCollector
     from fsrl_amd.policy import PolicyGroup
     n_ep = a.envs
