@@ -88,21 +88,38 @@ def _leaves(flat, spec, off):
 
 
 class ReplayIndex:
-    """Index semantics of tianshou-0.5 VectorReplayBuffer for rows stored without wrap-around:
-    env e owns slots [e*sub, e*sub + rows[e])."""
+    """Index semantics of tianshou-0.5 VectorReplayBuffer.  Without `heads`: rows stored without wrap-around,
+    env e owns slots [e*sub, e*sub + rows[e]).  With heads = [(size, index, last_index)] per env (rows held, write head,
+    slot written last, all local to the sub-buffer; env_rows is then ignored): a store whose sub-buffers may have
+    been overwritten -- next() steps modulo the sub-buffer's size and stops at the slot written last, the unfinished
+    tail is the slot before the write head."""
 
-    def __init__(self, env_rows, sub_size, done):
-        self.rows, self.sub = np.asarray(env_rows), int(sub_size)
+    def __init__(self, env_rows, sub_size, done, heads=None):
+        self.sub = int(sub_size)
         self.done = np.asarray(done, bool)            # indexed by SLOT (size = n_env*sub)
-        self.last = np.array([e * self.sub + r - 1 for e, r in enumerate(self.rows)])
+        self.heads = None if heads is None else np.asarray(heads, np.int64).reshape(-1, 3)
+        if self.heads is None:
+            self.rows = np.asarray(env_rows)
+            self.last = np.array([e * self.sub + r - 1 for e, r in enumerate(self.rows)])
+        else:
+            self.rows = self.heads[:, 0]
+            self.last = np.arange(len(self.heads)) * self.sub + self.heads[:, 2]
 
     def next(self, idx):
         idx = np.asarray(idx)
-        stop = self.done[idx] | np.isin(idx, self.last)
-        return idx + (~stop).astype(idx.dtype)
+        if self.heads is None:
+            stop = self.done[idx] | np.isin(idx, self.last)
+            return idx + (~stop).astype(idx.dtype)
+        env = idx // self.sub
+        local = idx - env * self.sub
+        stop = self.done[idx] | (local == self.heads[env, 2])
+        return ((local + 1 - stop) % np.maximum(self.heads[env, 0], 1) + env * self.sub).astype(idx.dtype)
 
     def unfinished_index(self):
-        return np.array([l for l, r in zip(self.last, self.rows) if r > 0 and not self.done[l]], int)
+        if self.heads is None:
+            return np.array([l for l, r in zip(self.last, self.rows) if r > 0 and not self.done[l]], int)
+        tails = [e * self.sub + (h - 1) % n for e, (n, h, _) in enumerate(self.heads) if n > 0]
+        return np.array([t for t in tails if not self.done[t]], int)
 
 
 class SACLagOracle:

@@ -32,8 +32,11 @@ def flat(mods):
 
 def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates, seed, n_step=2,
         cost_stat=25.0, cost_limit=10.0, auto_alpha=True, alpha=0.005, tau=0.05, actor_lr=5e-4,
-        critic_lr=1e-3, alpha_lr=3e-4, gamma=0.99, buffer_size=None, full=False):
-    """full: a BASELINE-size case -- the rollout (tests/helpers.synth_rollout) and the initial parameters (synth_theta) are
+        critic_lr=1e-3, alpha_lr=3e-4, gamma=0.99, buffer_size=None, full=False, wrapped=False):
+    """wrapped: ep_lens holds one episode plan PER ENV and buffer_size is smaller than the rollout, so the sub-buffers are
+    overwritten with different write heads; the rollout is stored as seed + checksum (tests/helpers.sac_wrapped_case replays it,
+    last write wins), the parameters in full.
+    full: a BASELINE-size case -- the rollout (tests/helpers.synth_rollout) and the initial parameters (synth_theta) are
     regenerated from seeds by the tests, the fixture keeps their checksums, the sampled indices, both noise blocks of every
     update, the logged rows and the parameters after the updates (the target critics as every 8th element)."""
     seed_all(seed)
@@ -86,22 +89,33 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
                            action_space=_Box(-1, 1, (act_dim, )))
     policy.train()
     rng = np.random.default_rng(seed + 1000)
-    if full:
+    if full or wrapped:
         from ref_shim import VectorReplayBuffer
-        steps = synth_rollout(seed + 1000, env_num, [list(ep_lens)] * env_num, obs_dim, act_dim)
+        if wrapped:
+            sys.path.insert(0, os.path.dirname(HERE))
+            from helpers import rollout_checksum, synth_rollout
+        plans = [list(p) for p in ep_lens] if wrapped else [list(ep_lens)] * env_num
+        steps = synth_rollout(seed + 1000, env_num, plans, obs_dim, act_dim)
         buf = VectorReplayBuffer(buffer_size or 100000, env_num)
         for ids, obs, act, rew, cost, term, trunc, nxt in steps:
             buf.add({"obs": obs, "act": act, "rew": rew, "terminated": term, "truncated": trunc, "done": term | trunc,
                      "obs_next": nxt, "info.cost": cost}, ids)
-        out.update(rollout_seed=np.array(seed + 1000), rollout_checksum=rollout_checksum(steps), ep_lens=np.array(ep_lens),
-                   env_num=np.array(env_num))
+        out.update(rollout_seed=np.array(seed + 1000), rollout_checksum=rollout_checksum(steps), env_num=np.array(env_num))
+        if wrapped:
+            out["ep_lens_json"] = np.array(json.dumps(plans))
+            assert all(len(b) == b.maxsize for b in buf.buffers) and len({b._index for b in buf.buffers}) == env_num
+            out["heads"] = np.array([[len(b), b._index, int(b.last_index[0])] for b in buf.buffers])
+        else:
+            out["ep_lens"] = np.array(ep_lens)
     else:
         buf = fill_buffer(rng, env_num, ep_lens, obs_dim, act_dim, buffer_size=buffer_size or 100000)
     # stored actions of a tanh policy live in (-1, 1)
     buf._meta["act"][:] = np.tanh(buf._meta["act"])
     meta = buf._meta
     used = np.concatenate([np.arange(o, o + len(b)) for o, b in zip(buf._offset, buf.buffers)])
-    if not full:
+    if wrapped:
+        out.update(theta_actor0=flat([actor]), theta_critics0=flat(critics))
+    elif not full:
         out.update(theta_actor0=flat([actor]), theta_critics0=flat(critics))
         out["slots"] = used
         for k in ("obs", "act", "rew", "terminated", "truncated", "obs_next"):
@@ -169,6 +183,12 @@ if __name__ == "__main__":
         # BASELINE configs[3]'s shape (SafetyAntRun: obs 33, act 8; 256x256; batch 1024; n_step 2, sacl_cfg.py:21) over a
         # 97 000-row store (10 envs x nine 1000-step episodes + an unfinished tail of 700)
         gen("c4full", 33, 8, (256, 256), 10, [1000] * 9 + [-700], batch_size=1024, n_updates=3, seed=62, n_step=2, full=True)
+        sys.exit(0)
+    if sys.argv[1:] == ["wrapped"]:
+        # a store spent past its first fill: 3 envs of 100 / 93 / 86 steps into sub-buffers of 40 rows (overwritten 2.5 / 2.3 /
+        # 2.15 times, three different write heads; env 1 ends on a finished episode, envs 0 and 2 on unfinished tails), n_step 3
+        gen("wrapped", 6, 3, (64, 64), 3, [[40, 35, -25], [50, 43], [30, 30, 20, -6]], batch_size=64, n_updates=5, seed=38,
+            n_step=3, buffer_size=120, wrapped=True)
         sys.exit(0)
     if sys.argv[1:] == ["widths"]:
         # two hidden layers of different widths that are not 64 / 128 / 256 (zero-padded on the device)

@@ -210,3 +210,36 @@ def focops_case(name):
         g["theta_final_idx"] = np.arange(n)
     assert g["theta_final"].size == g["theta_final_idx"].size
     return cfg, g
+
+
+def replay_last_write_wins(steps, env_num, sub, obs_dim, act_dim):
+    """Lock-step vector steps (synth_rollout's format) replayed into SLOT-indexed arrays the way a ring of `sub` rows per env
+    keeps them: row n of env e lands in slot e * sub + n % sub, the last write wins.
+    -> (store dict for the oracles, heads [(size, index, last_index)] per env, the slot of every pushed row per step)"""
+    store = {k: np.zeros((env_num * sub, ) + s, d) for k, s, d in (
+        ("obs", (obs_dim, ), np.float32), ("obs_next", (obs_dim, ), np.float32), ("act", (act_dim, ), np.float32),
+        ("rew", (), np.float64), ("cost", (), np.float64), ("terminated", (), bool), ("truncated", (), bool))}
+    count = np.zeros(env_num, np.int64)
+    slots = []
+    for ids, obs, act, rew, cost, term, trunc, nxt in steps:
+        at = np.array([e * sub + count[e] % sub for e in ids], np.int64)
+        for k, v in (("obs", obs), ("act", act), ("rew", rew), ("cost", cost), ("terminated", term), ("truncated", trunc),
+                     ("obs_next", nxt)):
+            store[k][at] = v
+        count[list(ids)] += 1
+        slots.append(at)
+    heads = np.array([[min(n, sub), n % sub, (n - 1) % sub if n else 0] for n in count], np.int64)
+    return store, heads, slots
+
+
+def sac_wrapped_case(name):
+    """tests/golden/sac_wrapped.npz: SACLagrangian.update of the unmodified reference over a VectorReplayBuffer whose sub-buffers
+    were overwritten about 2.5 times with three different write heads (n_step 3).  The rollout is regenerated from its seed
+    (checksum in the fixture); the stored actions are the tanh of the rollout's.  g["steps"]: the vector steps to push in order."""
+    g = load_npz(f"sac_{name}.npz")
+    cfg = json.loads(str(g["cfg_json"]))
+    env_num = int(g["env_num"])
+    steps = synth_rollout(int(g["rollout_seed"]), env_num, json.loads(str(g["ep_lens_json"])), cfg["obs_dim"], cfg["act_dim"])
+    assert np.array_equal(rollout_checksum(steps), g["rollout_checksum"]), "numpy's generators no longer reproduce the fixture's rollout"
+    g["steps"] = [(ids, obs, np.tanh(act), rew, cost, term, trunc, nxt) for ids, obs, act, rew, cost, term, trunc, nxt in steps]
+    return g

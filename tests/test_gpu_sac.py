@@ -21,6 +21,11 @@ def _engine(cfg, g):
     eng.sac_init(actor_lr=cfg["actor_lr"], critic_lr=cfg["critic_lr"], alpha_lr=cfg["alpha_lr"], tau=cfg["tau"],
                  alpha=cfg["alpha"], n_step=cfg["n_step"], auto_alpha=cfg["auto_alpha"])
     eng.sac_set_params(g["theta_actor0"], g["theta_critics0"], 0.0)
+    if "steps" in g:                      # a wrapped store: the vector steps pushed in order, every row where the reference's buffer put it
+        for step, slots in zip(g["steps"], g["step_slots"]):
+            ptr, *_ = eng.push(*step)
+            assert np.array_equal(ptr, slots)
+        return eng
     rows = g["env_rows"]
     off = np.concatenate([[0], np.cumsum(rows)])
     for t in range(rows.max()):
@@ -34,7 +39,8 @@ def _engine(cfg, g):
 
 @pytest.mark.parametrize("splitk", [0, 1])      # weight gradients: 0 = one workgroup per output tile (batches <= 512 rows), 1 = split-K
 # deep3, wide1: layered contexts; c4full: BASELINE configs[3]'s shape at batch 1024 from the unmodified reference (r5)
-@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full"])
+# wrapped: sub-buffers overwritten ~2.5 times with three different write heads, n_step 3, recorded from the unmodified reference
+@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped"])
 def test_sac_updates_vs_golden(name, splitk):
     g, cfg, ocfg, store, index = sac_setup(name)
     eng = _engine(cfg, g)

@@ -5,13 +5,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_npz, sac_full_case
+from helpers import load_npz, replay_last_write_wins, sac_full_case, sac_wrapped_case
 from oracle.sac_lag import ReplayIndex, SACConfig, SACLagOracle
 
 
 def sac_setup(name):
     # c4full: BASELINE configs[3]'s shape at batch 1024 over a 97 000-row store (rollout + parameters regenerated from seeds)
-    g = sac_full_case(name) if name.endswith("full") else load_npz(f"sac_{name}.npz")
+    # wrapped: sub-buffers overwritten ~2.5 times with three different write heads, n_step 3 (rollout regenerated from its seed)
+    g = sac_full_case(name) if name.endswith("full") else sac_wrapped_case(name) if name == "wrapped" else load_npz(f"sac_{name}.npz")
     cfg = json.loads(str(g["cfg_json"]))
     ocfg = SACConfig(obs_dim=cfg["obs_dim"], act_dim=cfg["act_dim"], hidden=tuple(cfg["hidden"]),
                      gamma=cfg["gamma"], n_step=cfg["n_step"], tau=cfg["tau"], alpha=cfg["alpha"],
@@ -19,6 +20,10 @@ def sac_setup(name):
                      alpha_lr=cfg["alpha_lr"])
     sub = int(g["sub_size"])
     nslots = sub * cfg["env_num"]
+    if "steps" in g:                     # the steps replayed into the oracle's store, last write wins
+        store, heads, g["step_slots"] = replay_last_write_wins(g["steps"], cfg["env_num"], sub, cfg["obs_dim"], cfg["act_dim"])
+        assert np.array_equal(heads, g["heads"])
+        return g, cfg, ocfg, store, ReplayIndex(None, sub, store["terminated"] | store["truncated"], heads=heads)
     store = {}
     for k in ("obs", "act", "rew", "cost", "terminated", "truncated", "obs_next"):
         src = g["st_" + k]
@@ -34,7 +39,7 @@ def old_final(g, flat_old):
     return flat_old[::8] if flat_old.size != g["theta_critics_old_final"].size else flat_old
 
 
-@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full"])
+@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped"])
 def test_sac_updates(name):
     torch.set_num_threads(4)
     g, cfg, ocfg, store, index = sac_setup(name)
