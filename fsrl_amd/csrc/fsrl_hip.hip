@@ -267,6 +267,38 @@ static int ensure_scratch(fsrl_ctx* c, size_t bytes) {
     return 0;
 }
 
+// ---- a device table with its pinned twin (the grouped updates' member and step tables).  table_ensure regrows both to `grow_to`
+//      entries once a call needs more than they hold (the contents are dropped); the growth policy is the caller's.  sync: a stream
+//      that may still be reading the old tables.
+template <class T>
+struct DevTable { T *d = nullptr, *h = nullptr; size_t cap = 0; };
+template <class T>
+static int table_ensure(DevTable<T>& t, size_t need, size_t grow_to, hipStream_t sync = nullptr) {
+    if (need <= t.cap) return 0;
+    if (sync) HIPCHK(hipStreamSynchronize(sync));
+    if (t.d) HIPCHK(hipFree(t.d));
+    if (t.h) HIPCHK(hipHostFree(t.h));
+    t.d = nullptr; t.h = nullptr; t.cap = 0;
+    HIPCHK(hipMalloc(&t.d, grow_to * sizeof(T)));
+    HIPCHK(hipHostMalloc(&t.h, grow_to * sizeof(T)));
+    t.cap = grow_to;
+    return 0;
+}
+template <class T>
+static void table_free(DevTable<T>& t) {
+    if (t.d) (void)hipFree(t.d);
+    if (t.h) (void)hipHostFree(t.h);
+    t = DevTable<T>{};
+}
+
+// ---- Adam's bias-corrected step size and sqrt(1 - beta2^t) at step t, as every Adam kernel takes them
+struct AdamStep { float step_size, bc2_sqrt; };
+static AdamStep adam_step(float lr, float beta1, float beta2, int64_t t) {
+    const double b1 = beta1, b2 = beta2;
+    const double bc1 = 1.0 - std::pow(b1, (double)t), bc2 = 1.0 - std::pow(b2, (double)t);
+    return AdamStep{(float)((double)lr / bc1), (float)std::sqrt(bc2)};
+}
+
 // ---- split-K launch of fb_wgrad_kernel.  Rows are cut into <= 24 splits of >= 256 rows; every split
 //      writes a partial gradient at parts + z * stride, summed later in z order.
 struct WgradPlan { int nsplit, ks_per_split; };
@@ -280,6 +312,14 @@ static WgradPlan wgrad_plan(int rows, int blocks_per_split, int n_cus) {
     const int per = round_up((KS + n - 1) / n, 16);
     n = (KS + per - 1) / per;
     return WgradPlan{std::max(n, 1), per};
+}
+// fb_wgrad_kernel's blocks of one split and network: 64x64 dW2 tiles + one block per (64-column group, pass over the rows) + the
+// db3 block.  Passes: the first carries NCH0 16-column chunks of dW1 (+ dW3, db1, db2), every further one four chunks.
+struct WgradBlocks { int passes, NB; };
+static WgradBlocks wgrad_blocks(int Do, int H, bool pair2) {
+    const int nch0 = pair2 ? 1 : 2;
+    const int passes = 1 + std::max(0, (Do - 16 * nch0 + 63) / 64);
+    return WgradBlocks{passes, (H / 64) * (H / 64) + (H / FB_AUX_COLS) * passes + 1};
 }
 static int ensure_parts(fsrl_ctx* c, int stride, int nsplit) {
     fsrl_ctx::Parts* slot = nullptr;
@@ -297,6 +337,19 @@ static int ensure_parts(fsrl_ctx* c, int stride, int nsplit) {
     }
     c->wg_parts = slot->p;
     return 0;
+}
+// the plain operands of `ny` networks (one product per gradient, the bias sums off the same operands) behind a tile launch that
+// laid network y out `stride` rows apart in A1 .. DO; network y writes the slice of network net0 + y.  wa is zero-initialised.
+static void wgrad_fill_nets(FbWgradArgs& wa, int ny, int net0, size_t H, size_t stride, const float* A1, const float* A2,
+                            const float* D1, const float* D2, const float* DO) {
+    for (int y = 0; y < ny; ++y) {
+        FbWgradNet& wn = wa.nets[y];
+        const size_t nb = (size_t)y * stride;
+        wn.w2_ya = D2 + nb * H; wn.w2_xa = A1 + nb * H; wn.w1_y = D1 + nb * H;
+        wn.w3_xa = A2 + nb * H; wn.w3_ya = DO + nb * FSRL_DOW;
+        wn.b1_src = D1 + nb * H; wn.b2_src = D2 + nb * H; wn.do_src = DO + nb * FSRL_DOW;
+        wn.net = net0 + y;
+    }
 }
 // rider (replay agents, the actor's launch): blocks appended along x draw + gather the next update's batch (kernels_sample.hpp);
 // *rider_done tells the caller whether this launch carried them (only the 3-D grid of round 5's split-K kernel does)
@@ -354,11 +407,8 @@ static int wgrad_launch(fsrl_ctx* c, const ModelDesc& md, FbWgradArgs& wa, int n
         HIPCHK(hipGetLastError());
         return 0;
     }
-    // blocks of one split and network: 64x64 dW2 tiles + one block per (64-column group, pass over the rows) + the db3 block.
-    // Passes: the first carries NCH0 16-column chunks of dW1 (+ dW3, db1, db2), every further one four chunks.
-    const int nch0 = PAIR2 ? 1 : 2;
-    const int passes = 1 + std::max(0, (md.Do - 16 * nch0 + 63) / 64);
-    const int NB = (H_ / 64) * (H_ / 64) + (H_ / FB_AUX_COLS) * passes + 1;
+    const WgradBlocks wb = wgrad_blocks(md.Do, H_, PAIR2);
+    const int passes = wb.passes, NB = wb.NB;
     const WgradPlan pl = wgrad_plan(wa.rows, NB * ny, c->n_cus);
     int rc = ensure_parts(c, stride, pl.nsplit);
     if (rc) return rc;

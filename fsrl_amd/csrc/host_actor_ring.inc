@@ -1,8 +1,9 @@
 // host_actor_ring.inc -- the pinned ring and the host half of the protocol of a resident actor kernel that serves SEVERAL contexts
 // from one launch and one doorbell (part of fsrl_hip.hip, before host_group.inc).  Two owners embed a GaRing: fsrl_group
-// (host_group_collect.inc: on-policy members, actor_group_resident_kernel<H, false>) and fsrl_collect_group (host_collect_group.inc:
-// replay members, actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on and the launch itself;
-// everything else -- post / ring / wait / release, generation and sequence numbers, the bounded wait -- is here.
+// (host_group_collect.inc: on-policy members, actor_group_resident_kernel<H, false>) and fsrl_collect_group
+// (host_collect_group.inc: replay members, actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on
+// and the launch itself; everything else -- post / ring / wait / release, generation and sequence numbers, the bounded wait, and the
+// lock-step collect step both owners' entry points run (ga_collect_step) -- is here.
 // Protocol as pactor_* (fsrl_hip.hip), with one doorbell for all members and a per-member row count k_m next to it.
 
 // pinned ring: [bell 8 B | pad | k_m[16] at 64 | done[64] at 128 | state[64] at 384 | pad | obs [64 * 16][Do] at 1024 |
@@ -188,4 +189,109 @@ static int gactor_wait(GaRing& r) {
 // a member's row cap on the resident path: what its own resident actor serves
 static inline int gactor_member_rows(const fsrl_ctx* c) {
     return 16 * std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
+}
+
+// *_actor_set_resident / *_actor_resident_stats of both owners
+static int ga_set_resident(GaRing& r, int32_t on, double idle_timeout_us) {
+    CHECK_ARG(idle_timeout_us <= 1.0e6, "idle_timeout_us above one second");
+    ga_release(r);
+    r.on = on != 0;
+    if (idle_timeout_us > 0.0) r.idle_us = idle_timeout_us;
+    return 0;
+}
+// out3 = {kernel launches, requests served through the doorbell, 1 if the resident kernel is live now}
+static void ga_stats(const GaRing& r, int64_t* out3) { out3[0] = r.launches; out3[1] = r.requests; out3[2] = r.live ? 1 : 0; }
+
+// ---- one lock-step collect step: fsrl_collect_step on every member, in member order, with one request to the ring's kernel.  Row
+//      arrays are concatenated over members; k[m] / k_act[m] may be 0; act_low / act_high: NULL or [members][act_dim].
+struct GaStepArgs {
+    const int32_t* k; const int32_t* env_ids; const float* obs; const float* act; const double* rew; const double* cost;
+    const uint8_t* terminated; const uint8_t* truncated; const float* obs_next; int64_t* ptr_out; double* ep_rew_out;
+    int32_t* ep_len_out; int64_t* ep_idx_out; const int32_t* k_act; const float* obs_act; int32_t deterministic; int32_t bound_method;
+    const float* act_low; const float* act_high; float* act_out; float* env_act_out;
+};
+// The owners differ in three callables: ensure() makes the ring before a request (0 or an error); finish(i, c, ka, l) turns member
+// i's ka ring rows into c->act_mu / c->act_sg (sized [ka][act_dim] already); drain() leaves no evaluation in flight when a push
+// fails off the resident path.
+template <class Ensure, class Finish, class Drain>
+static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, const GaStepArgs& a, Ensure&& ensure, Finish&& finish,
+                           Drain&& drain) {
+    const int32_t *k = a.k, *k_act = a.k_act;
+    const int Do = m[0]->cfg.obs_dim, Da = m[0]->cfg.act_dim;
+    int64_t rows = 0, rows_act = 0;
+    bool resident = ga.on;
+    for (int i = 0; i < n; ++i) {
+        CHECK_ARG(k[i] >= 0 && k_act[i] >= 0, "negative row count (member %d)", i);
+        rows += k[i]; rows_act += k_act[i];
+        resident = resident && !m[i]->no_spin && k_act[i] <= gactor_member_rows(m[i]);
+    }
+    CHECK_ARG(rows_act == 0 || (a.obs_act && a.act_out), "obs_act / act_out missing");
+    CHECK_ARG(rows == 0 || a.env_ids, "env_ids missing");
+    CHECK_ARG(a.bound_method >= 0 && a.bound_method <= 2, "bound_method: 0 none, 1 clip, 2 tanh");
+    CHECK_ARG((a.act_low == nullptr) == (a.act_high == nullptr), "act_low and act_high are given together");
+    HIPCHK(hipSetDevice(device));               // keeps the group's resident actor alive
+    // 1. one request for every member (or, off the resident path, every member's own actor call)
+    int rc = 0;
+    if (rows_act > 0) {
+        if (resident) {
+            rc = ensure();
+            if (!rc) rc = gactor_post(ga, k_act, a.obs_act);
+            if (rc) return rc;
+        } else {
+            ga_release(ga);
+            size_t off = 0;
+            for (int i = 0; i < n; ++i) {
+                if (k_act[i] > 0) {
+                    rc = actor_eval_launch(m[i], a.obs_act + off * Do, k_act[i], true);
+                    if (rc) return rc;
+                }
+                off += (size_t)k_act[i];
+            }
+        }
+    }
+    // 2. every member's finished transitions into its own store (flushes on the member's side stream)
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        if (k[i] > 0) {
+            const size_t o = off;
+            rc = fsrl_store_push(m[i], a.env_ids + o, k[i], a.obs + o * Do, a.act + o * Da, a.rew + o, a.cost ? a.cost + o : nullptr,
+                                 a.terminated + o, a.truncated + o, a.obs_next + o * Do, a.ptr_out ? a.ptr_out + o : nullptr,
+                                 a.ep_rew_out ? a.ep_rew_out + o : nullptr, a.ep_len_out ? a.ep_len_out + o : nullptr,
+                                 a.ep_idx_out ? a.ep_idx_out + o : nullptr);
+            if (rc) {                           // leave no evaluation in flight behind the error
+                if (rows_act > 0) { if (resident) (void)gactor_wait(ga); else drain(); }
+                return rc;
+            }
+        }
+        off += (size_t)k[i];
+    }
+    if (rows_act == 0) return 0;
+    // 3. wait; 4. per member in order: mean / std from its ring rows, its noise from its own stream, then map_action
+    if (resident) {
+        rc = gactor_wait(ga);
+        if (rc) return rc;
+    }
+    const GaLayout l = resident ? ga_layout(ga) : GaLayout{};
+    off = 0;
+    for (int i = 0; i < n; ++i) {
+        const int ka = k_act[i];
+        fsrl_ctx* c = m[i];
+        if (ka > 0) {
+            float* ao = a.act_out + off * Da;
+            if (resident) {
+                c->actor_k = ka;
+                c->act_mu.resize((size_t)ka * Da); c->act_sg.resize((size_t)ka * Da);
+                finish(i, c, ka, l);
+                actor_draw(c, a.deterministic, ao);
+            } else {
+                rc = actor_sample_finish(c, a.deterministic, ao);
+                if (rc) return rc;
+            }
+            if (a.env_act_out)
+                map_env_action(Da, ka, a.bound_method, a.act_low ? a.act_low + (size_t)i * Da : nullptr,
+                               a.act_high ? a.act_high + (size_t)i * Da : nullptr, ao, a.env_act_out + off * Da);
+        }
+        off += (size_t)ka;
+    }
+    return 0;
 }

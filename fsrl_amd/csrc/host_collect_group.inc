@@ -135,8 +135,8 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
     return 0;
 }
 
-// fsrl_collect_step on every member, in member order, with one request to the group's kernel.  Row arrays are concatenated over
-// members; k[m] / k_act[m] may be 0; act_low / act_high: NULL or [members][act_dim].
+// ga_collect_step (host_actor_ring.inc) with the replay members' three differences: the ring exists since create, a member's mean /
+// std come from its raw head rows (sac_actor_finish), and off the resident path every member's own evaluation is drained
 extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, const int32_t* env_ids, const float* obs, const float* act,
                                        const double* rew, const double* cost, const uint8_t* terminated, const uint8_t* truncated,
                                        const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out,
@@ -145,107 +145,32 @@ extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, 
                                        float* env_act_out) {
     CHECK_ARG(g && k && k_act, "null argument");
     if (g->broken) return fail(FSRL_ESTATE, "a member of this collect group has been destroyed");
-    const int n = (int)g->m.size();
-    fsrl_ctx* c0 = g->m[0];
-    const int Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim, rcols = g->raw_cols;
-    int64_t rows = 0, rows_act = 0;
-    bool resident = g->ga.on;
-    for (int i = 0; i < n; ++i) {
-        CHECK_ARG(k[i] >= 0 && k_act[i] >= 0, "negative row count (member %d)", i);
-        rows += k[i]; rows_act += k_act[i];
-        const fsrl_ctx* c = g->m[i];
-        resident = resident && !c->no_spin && k_act[i] <= gactor_member_rows(c);
-    }
-    CHECK_ARG(rows_act == 0 || (obs_act && act_out), "obs_act / act_out missing");
-    CHECK_ARG(rows == 0 || env_ids, "env_ids missing");
-    CHECK_ARG(bound_method >= 0 && bound_method <= 2, "bound_method: 0 none, 1 clip, 2 tanh");
-    CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
-    HIPCHK(hipSetDevice(g->device));            // keeps the group's resident actor alive
-    // 1. one request for every member (or, off the resident path, every member's own actor call)
-    int rc = 0;
-    if (rows_act > 0) {
-        if (resident) {
-            rc = gactor_post(g->ga, k_act, obs_act);
-            if (rc) return rc;
-        } else {
-            ga_release(g->ga);
-            size_t off = 0;
-            for (int i = 0; i < n; ++i) {
-                if (k_act[i] > 0) {
-                    rc = actor_eval_launch(g->m[i], obs_act + off * Do, k_act[i], true);
-                    if (rc) return rc;
-                }
-                off += (size_t)k_act[i];
+    const GaStepArgs a{k, env_ids, obs, act, rew, cost, terminated, truncated, obs_next, ptr_out, ep_rew_out, ep_len_out, ep_idx_out,
+                       k_act, obs_act, deterministic, bound_method, act_low, act_high, act_out, env_act_out};
+    const int n = (int)g->m.size(), Da = g->m[0]->cfg.act_dim, rcols = g->raw_cols;
+    return ga_collect_step(
+        g->ga, g->m.data(), n, g->device, a, []() { return 0; },
+        [&](int i, fsrl_ctx* c, int ka, const GaLayout& l) {
+            sac_actor_finish(c, l.mu + (size_t)g->ga.base[i] * 16 * rcols, ka, c->act_mu.data(), c->act_sg.data());
+        },
+        [&]() {
+            for (int j = 0; j < n; ++j) {
+                fsrl_ctx* c = g->m[j];
+                if (k_act[j] <= 0) continue;
+                c->act_mu.resize((size_t)k_act[j] * Da); c->act_sg.resize((size_t)k_act[j] * Da);
+                (void)actor_eval_finish(c, c->act_mu.data(), c->act_sg.data());
             }
-        }
-    }
-    // 2. every member's finished transitions into its own store (flushes on the member's side stream)
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        if (k[i] > 0) {
-            const size_t o = off;
-            rc = fsrl_store_push(g->m[i], env_ids + o, k[i], obs + o * Do, act + o * Da, rew + o, cost ? cost + o : nullptr,
-                                 terminated + o, truncated + o, obs_next + o * Do, ptr_out ? ptr_out + o : nullptr,
-                                 ep_rew_out ? ep_rew_out + o : nullptr, ep_len_out ? ep_len_out + o : nullptr,
-                                 ep_idx_out ? ep_idx_out + o : nullptr);
-            if (rc) {                           // leave no evaluation in flight behind the error
-                if (rows_act > 0 && resident) (void)gactor_wait(g->ga);
-                else if (rows_act > 0)
-                    for (int j = 0; j < n; ++j) {
-                        fsrl_ctx* c = g->m[j];
-                        if (k_act[j] <= 0) continue;
-                        c->act_mu.resize((size_t)k_act[j] * Da); c->act_sg.resize((size_t)k_act[j] * Da);
-                        (void)actor_eval_finish(c, c->act_mu.data(), c->act_sg.data());
-                    }
-                return rc;
-            }
-        }
-        off += (size_t)k[i];
-    }
-    if (rows_act == 0) return 0;
-    // 3. wait; 4. per member in order: mean / std from its raw rows, its noise from its own stream, then map_action
-    if (resident) {
-        rc = gactor_wait(g->ga);
-        if (rc) return rc;
-    }
-    const GaLayout l = resident ? ga_layout(g->ga) : GaLayout{};
-    off = 0;
-    for (int i = 0; i < n; ++i) {
-        const int ka = k_act[i];
-        fsrl_ctx* c = g->m[i];
-        if (ka > 0) {
-            float* ao = act_out + off * Da;
-            if (resident) {
-                c->actor_k = ka;
-                c->act_mu.resize((size_t)ka * Da); c->act_sg.resize((size_t)ka * Da);
-                sac_actor_finish(c, l.mu + (size_t)g->ga.base[i] * 16 * rcols, ka, c->act_mu.data(), c->act_sg.data());
-                actor_draw(c, deterministic, ao);
-            } else {
-                rc = actor_sample_finish(c, deterministic, ao);
-                if (rc) return rc;
-            }
-            if (env_act_out)
-                map_env_action(Da, ka, bound_method, act_low ? act_low + (size_t)i * Da : nullptr,
-                               act_high ? act_high + (size_t)i * Da : nullptr, ao, env_act_out + off * Da);
-        }
-        off += (size_t)ka;
-    }
-    return 0;
+        });
 }
 
 extern "C" int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us) {
     CHECK_ARG(g, "null group");
-    CHECK_ARG(idle_timeout_us <= 1.0e6, "idle_timeout_us above one second");
-    ga_release(g->ga);
-    g->ga.on = on != 0;
-    if (idle_timeout_us > 0.0) g->ga.idle_us = idle_timeout_us;
-    return 0;
+    return ga_set_resident(g->ga, on, idle_timeout_us);
 }
 
-// out3 = {kernel launches, requests served through the doorbell, 1 if the group's resident kernel is live now}
 extern "C" int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3) {
     CHECK_ARG(g && out3, "null argument");
-    out3[0] = g->ga.launches; out3[1] = g->ga.requests; out3[2] = g->ga.live ? 1 : 0;
+    ga_stats(g->ga, out3);
     return 0;
 }
 

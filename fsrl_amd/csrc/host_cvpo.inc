@@ -93,21 +93,12 @@ extern "C" int fsrl_cvpo_last_particles(fsrl_ctx* c, float* eps_particles, int64
 }
 
 // ---- the arguments of one update's launches.  fsrl_cvpo_update and the grouped update (host_cvpo_group.inc) both form them
-//      here, so a member of a group cannot be handed anything its own update would not be.
-static SacGatherArgs cvpo_gather_args(const fsrl_ctx* c, const SacState* s, int B) {
-    const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, ns = s->ccfg.n_step;
-    SacGatherArgs ga{};
-    ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(ns - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
-    ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = Do; ga.Da = Da;
-    return ga;
-}
-// library RNG: the sample of the update that s->n_updates counts (the grouped update sets the counter per step)
+//      here (sample, gather and n-step: on the SAC builders of host_sac.inc), so a member of a group cannot be handed anything its
+//      own update would not be.
+// library RNG: the sample of the update that s->n_updates counts (the grouped update sets the counter per step), with the
+// particles' noise
 static SacSampleArgs cvpo_sample_args(const fsrl_ctx* c, const SacState* s, int B, int64_t stored) {
-    SacSampleArgs sa{};
-    sa.book = s->d_book; sa.flags = c->st.flags; sa.idx = s->d_idx; sa.chain = s->d_chain; sa.endbits = s->d_end;
-    sa.eps_t = s->eps_t; sa.eps_p = s->eps_p; sa.env_num = c->cfg.env_num; sa.sub_size = (int)c->sub_size; sa.B = B;
-    sa.n_step = s->ccfg.n_step; sa.Da = c->cfg.act_dim; sa.stored = (unsigned long long)stored; sa.key = s->key;
-    sa.counter = (unsigned long long)s->n_updates;
+    SacSampleArgs sa = sac_sample_args(c, s, B, s->ccfg.n_step, stored, s->n_updates);
     sa.eps_k = s->eps_k; sa.K = s->ccfg.sample_act_num;
     return sa;
 }
@@ -125,9 +116,7 @@ static CvpoActorArgs cvpo_actor_args(const fsrl_ctx* c, const SacState* s, int B
     return aa;
 }
 static SacNstepArgs cvpo_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
-    SacNstepArgs na{};
-    na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
-    na.flags = c->st.flags; na.sc = s->sc; na.Y = s->Y; na.B = B; na.n_step = s->ccfg.n_step; na.gamma = c->cfg.gamma;
+    SacNstepArgs na = sac_nstep_args(c, s, B);       // n_step: fsrl_cvpo_init copies it into s->cfg
     na.auto_alpha = 0; na.alpha_fixed = 0.0f; na.single = s->n_q == 2 ? 1 : 0;    // LPN stays zero: no entropy term
     return na;
 }
@@ -171,41 +160,19 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     if (rc) return rc;
     hipStream_t st = c->compute;
     const fsrl_cvpo_config& cc = s->ccfg;
-    const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, ns = cc.n_step, K = cc.sample_act_num;
+    const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, K = cc.sample_act_num;
     const size_t nk = (size_t)K * B * Da;
     if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
     bool fused_sg = false;
-    const SacGatherArgs ga = cvpo_gather_args(c, s, B);
+    const SacGatherArgs ga = sac_gather_args(c, s, B, cc.n_step);
     if (indices) {
-        HIPCHK(hipStreamSynchronize(st));      // pinned staging of the previous update has landed
-        for (int b = 0; b < B; ++b) {
-            const int64_t idx = indices[b];
-            CHECK_ARG(idx >= 0 && idx < c->maxsize, "index %lld out of range", (long long)idx);
-            s->h_idx[b] = (int)idx;
-            int64_t cur = idx;
-            for (int n = 0; n < ns; ++n) {
-                if (n > 0) cur = store_next(c, cur);
-                s->h_chain[(size_t)n * B + b] = (int)cur;
-                s->h_end[(size_t)n * B + b] = store_end_flag(c, cur) ? 1 : 0;
-            }
-        }
-        memcpy(s->h_eps, eps_target, (size_t)B * Da * 4);
+        rc = sac_stage_indices(c, s, B, indices, eps_target);
+        if (rc) return rc;
         memcpy(s->h_epsk, eps_particles, nk * 4);
-        HIPCHK(hipMemcpyAsync(s->d_idx, s->h_idx, (size_t)B * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain, (size_t)B * ns * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->d_end, s->h_end, (size_t)B * ns, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->eps_t, s->h_eps, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(s->eps_k, s->h_epsk, nk * 4, hipMemcpyHostToDevice, st));
     } else {
-        if (s->book_version != c->store_version) {
-            HIPCHK(hipStreamSynchronize(st));
-            for (int e = 0; e < c->cfg.env_num; ++e) {
-                const EnvBook& eb = c->env[(size_t)e];
-                s->h_book[e] = SacBook{(int)eb.size, (int)eb.index, (int)eb.last_index, 0};
-            }
-            HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, st));
-            s->book_version = c->store_version;
-        }
+        rc = sac_upload_book(c, s);
+        if (rc) return rc;
         const SacSampleArgs sa = cvpo_sample_args(c, s, B, stored);
         fused_sg = !s->plan_separate;
         if (fused_sg) {          // r6: sample + gather + the particles' noise in one launch (fsrl_sac_set_plan bit 1 keeps the two)

@@ -12,45 +12,24 @@
 // solo runs created under FSRL_TILE16 (tests/test_gpu_cvpo_group.py).
 // ====================================================================================== grouped CVPO
 struct fsrl_cvpo_group {
-    std::vector<fsrl_ctx*> m;                  // members (not owned; nullptr once destroyed)
-    int device = 0;
-    hipStream_t stream = nullptr;              // the group's own stream
-    hipEvent_t done = nullptr;                 // end of the last grouped call on `stream`
-    std::vector<hipEvent_t> ready;             // per member: its stream's work before the call
-    SacGroupMember *d_tab = nullptr, *h_tab = nullptr;       // device / pinned, [k]: what the SAC group's kernels read
-    CvpoGroupMember *d_ctab = nullptr, *h_ctab = nullptr;    // device / pinned, [k]: CVPO's own launches
-    SacGroupStep *d_steps = nullptr, *h_steps = nullptr;     // device / pinned, [updates][k]
-    CvpoGroupIter *d_iters = nullptr, *h_iters = nullptr;    // device / pinned, [updates][mstep_iter_num][k]
-    size_t cap_steps = 0, cap_iters = 0;
-    bool broken = false;                       // a member was destroyed first: no more updates
+    ReplayGroupCore core;                      // members, stream, events (host_sac_group.inc)
+    DevTable<SacGroupMember> tab;              // [k]: what the SAC group's kernels read
+    DevTable<CvpoGroupMember> ctab;            // [k]: CVPO's own launches
+    DevTable<SacGroupStep> steps;              // [updates][k]
+    DevTable<CvpoGroupIter> iters;             // [updates][mstep_iter_num][k]
 };
 
-// a member destroyed before its group (fsrl_ctx_destroy): the group stops updating, its destroy still works
 static void cvpo_group_detach(fsrl_ctx* c) {
-    fsrl_cvpo_group* g = c->cvpo_group;
-    if (!g) return;
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (auto& x : g->m) if (x == c) x = nullptr;
+    if (!c->cvpo_group) return;
+    rgroup_detach(c->cvpo_group->core, c);
     c->cvpo_group = nullptr;
-    g->broken = true;
 }
 
 extern "C" int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g) {
     if (!g) return 0;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (fsrl_ctx* c : g->m) if (c) c->cvpo_group = nullptr;
-    for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
-    if (g->done) (void)hipEventDestroy(g->done);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->d_tab) (void)hipFree(g->d_tab);
-    if (g->h_tab) (void)hipHostFree(g->h_tab);
-    if (g->d_ctab) (void)hipFree(g->d_ctab);
-    if (g->h_ctab) (void)hipHostFree(g->h_ctab);
-    if (g->d_steps) (void)hipFree(g->d_steps);
-    if (g->h_steps) (void)hipHostFree(g->h_steps);
-    if (g->d_iters) (void)hipFree(g->d_iters);
-    if (g->h_iters) (void)hipHostFree(g->h_iters);
+    for (fsrl_ctx* c : g->core.m) if (c) c->cvpo_group = nullptr;
+    rgroup_destroy(g->core);
+    table_free(g->tab); table_free(g->ctab); table_free(g->steps); table_free(g->iters);
     delete g;
     return 0;
 }
@@ -94,21 +73,17 @@ extern "C" int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_grou
     const fsrl_ctx* c0 = ctxs[0];
     HIPCHK(hipSetDevice(c0->device));
     fsrl_cvpo_group* g = new fsrl_cvpo_group();
-    g->device = c0->device;
-    g->ready.assign((size_t)k, nullptr);
-    hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->done, hipEventDisableTiming);
-    for (int i = 0; i < k && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&g->ready[(size_t)i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc(&g->d_tab, (size_t)k * sizeof(SacGroupMember));
-    if (e == hipSuccess) e = hipHostMalloc(&g->h_tab, (size_t)k * sizeof(SacGroupMember));
-    if (e == hipSuccess) e = hipMalloc(&g->d_ctab, (size_t)k * sizeof(CvpoGroupMember));
-    if (e == hipSuccess) e = hipHostMalloc(&g->h_ctab, (size_t)k * sizeof(CvpoGroupMember));
+    hipError_t e = rgroup_create(g->core, c0->device, k);
+    if (e == hipSuccess) e = hipMalloc(&g->tab.d, (size_t)k * sizeof(SacGroupMember));
+    if (e == hipSuccess) e = hipHostMalloc(&g->tab.h, (size_t)k * sizeof(SacGroupMember));
+    if (e == hipSuccess) e = hipMalloc(&g->ctab.d, (size_t)k * sizeof(CvpoGroupMember));
+    if (e == hipSuccess) e = hipHostMalloc(&g->ctab.h, (size_t)k * sizeof(CvpoGroupMember));
     if (e != hipSuccess) {
         fail(FSRL_EHIP, "CVPO group allocation failed: %s", hipGetErrorString(e));
         (void)fsrl_cvpo_group_destroy(g);
         return FSRL_EHIP;
     }
-    for (int i = 0; i < k; ++i) { g->m.push_back(ctxs[i]); ctxs[i]->cvpo_group = g; }
+    for (int i = 0; i < k; ++i) { g->core.m.push_back(ctxs[i]); ctxs[i]->cvpo_group = g; }
     *out = g;
     return 0;
 }
@@ -124,7 +99,7 @@ static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGr
     t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
     v.PA = s->PA; v.MA = s->MA; v.VA = s->VA;
     *sa = cvpo_sample_args(c, s, B, stored);
-    v.ga = cvpo_gather_args(c, s, B);
+    v.ga = sac_gather_args(c, s, B, s->ccfg.n_step);
     v.at = cvpo_actor_args(c, s, B, CVPO_A_TARGET, s->OBSN, s->eps_t, s->XN, true, th.f_r4 ? 4 * nt : nt);
     v.am = cvpo_actor_args(c, s, B, CVPO_A_MFWD, s->OBS, nullptr, nullptr, false, 0);
     v.ab = cvpo_actor_args(c, s, B, CVPO_A_MBWD, s->OBS, nullptr, nullptr, false, 0);
@@ -162,31 +137,19 @@ static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGr
     return 0;
 }
 
-template <class T>
-static int cvpo_group_table(T** d, T** h, size_t* cap, size_t need) {
-    if (need <= *cap) return 0;
-    if (*d) HIPCHK(hipFree(*d));
-    if (*h) HIPCHK(hipHostFree(*h));
-    *d = nullptr; *h = nullptr; *cap = 0;
-    const size_t n = std::max<size_t>(need, 64);
-    HIPCHK(hipMalloc(d, n * sizeof(T)));
-    HIPCHK(hipHostMalloc(h, n * sizeof(T)));
-    *cap = n;
-    return 0;
-}
-
 extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32_t* n_updates) {
     CHECK_ARG(g && n_updates, "null argument");
-    if (g->broken) return fail(FSRL_ESTATE, "a member of this CVPO group was destroyed: destroy the group");
+    ReplayGroupCore& gc = g->core;
+    if (gc.broken) return fail(FSRL_ESTATE, "a member of this CVPO group was destroyed: destroy the group");
     CHECK_ARG(B >= 1, "batch_size must be >= 1");
-    const int k = (int)g->m.size();
-    int rc = cvpo_group_check(g->m.data(), k, g);
+    const int k = (int)gc.m.size();
+    int rc = cvpo_group_check(gc.m.data(), k, g);
     if (rc) return rc;
-    fsrl_ctx* c0 = g->m[0];
+    fsrl_ctx* c0 = gc.m[0];
     SacState* s0 = sac_of(c0);
     int n_max = 0;
     for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = g->m[i];
+        fsrl_ctx* c = gc.m[i];
         CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
         // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
         CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
@@ -195,8 +158,8 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
         n_max = std::max(n_max, (int)n_updates[i]);
     }
     if (n_max == 0) return 0;
-    HIPCHK(hipSetDevice(g->device));
-    HIPCHK(hipStreamSynchronize(g->stream));           // the pinned tables of the previous call have been read
+    HIPCHK(hipSetDevice(gc.device));
+    HIPCHK(hipStreamSynchronize(gc.stream));           // the pinned tables of the previous call have been read
     const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = s0->n_q;
     const int K = s0->ccfg.sample_act_num, M = s0->ccfg.mstep_iter_num, ntk = (B * K + 15) / 16;
     // tile heights: the single-context rule applied to the group's whole launch (4-row tiles while it fits one round)
@@ -207,101 +170,77 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     th.f_r4 = th.a_r4 && (size_t)8 * nt * k <= (size_t)c0->n_cus;
     th.k_r4 = (size_t)4 * ntk * n_q * k <= (size_t)c0->n_cus && !t16;
     const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
-    rc = cvpo_group_table(&g->d_steps, &g->h_steps, &g->cap_steps, (size_t)n_max * k);
+    const size_t n_steps = (size_t)n_max * k, n_iters = n_steps * M;
+    rc = table_ensure(g->steps, n_steps, std::max<size_t>(n_steps, 64));
     if (rc) return rc;
-    rc = cvpo_group_table(&g->d_iters, &g->h_iters, &g->cap_iters, (size_t)n_max * M * k);
+    rc = table_ensure(g->iters, n_iters, std::max<size_t>(n_iters, 64));
     if (rc) return rc;
-    // ---- every member with work: its resident actor ends, its pushes land, its batch buffers and sub-buffer books are current
+    // ---- every member with work joins; its table entries; then the group's stream goes behind the member's
     int nsq = 1, nsa = 1, rq_total = 0, ra_total = 0;
     std::vector<SacSampleArgs> sas((size_t)k);
     for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = g->m[i];
-        SacState* s = sac_of(c);
+        fsrl_ctx* c = gc.m[i];
         if (n_updates[i] == 0) continue;
-        ENTER_DEV(c);
-        rc = join_store(c);
+        rc = rgroup_join(c, B);
         if (rc) return rc;
-        rc = sac_alloc_batch(c, s, B);
+        SacGroupMember& t = g->tab.h[i];
+        rc = cvpo_group_member(c, sac_of(c), t, g->ctab.h[i], &sas[(size_t)i], B, fsrl_store_len(c), th, small_wgrad, &nsq, &nsa);
+        if (rc) return rc;                             // nsq, nsa, remap totals: one shape, one plan -- the same for every member
+        rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
+        rc = rgroup_ready(gc, i);
         if (rc) return rc;
-        if (s->book_version != c->store_version) {
-            HIPCHK(hipStreamSynchronize(c->compute));
-            for (int e = 0; e < c->cfg.env_num; ++e) {
-                const EnvBook& eb = c->env[(size_t)e];
-                s->h_book[e] = SacBook{(int)eb.size, (int)eb.index, (int)eb.last_index, 0};
-            }
-            HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, c->compute));
-            s->book_version = c->store_version;
-        }
-        int q_split = 1, a_split = 1;
-        rc = cvpo_group_member(c, s, g->h_tab[i], g->h_ctab[i], &sas[(size_t)i], B, fsrl_store_len(c), th, small_wgrad, &q_split, &a_split);
-        if (rc) return rc;
-        nsq = q_split; nsa = a_split;                  // one shape, one plan: the same for every member
-        rq_total = g->h_tab[i].fq.remap_total; ra_total = g->h_tab[i].fa.remap_total;
-        HIPCHK(hipEventRecord(g->ready[(size_t)i], c->compute));
-        HIPCHK(hipStreamWaitEvent(g->stream, g->ready[(size_t)i], 0));
     }
     // ---- the step tables: what each member's own fsrl_cvpo_update calls would use
     for (int u = 0; u < n_max; ++u)
         for (int i = 0; i < k; ++i) {
-            SacGroupStep& st = g->h_steps[(size_t)u * k + i];
+            SacGroupStep& st = g->steps.h[(size_t)u * k + i];
             st = SacGroupStep{};
-            for (int it = 0; it < M; ++it) g->h_iters[((size_t)u * M + it) * k + i] = CvpoGroupIter{};
+            for (int it = 0; it < M; ++it) g->iters.h[((size_t)u * M + it) * k + i] = CvpoGroupIter{};
             if (u >= n_updates[i]) continue;
-            const fsrl_ctx* c = g->m[i];
+            const fsrl_ctx* c = gc.m[i];
             const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
-            const int64_t n = s->n_updates + u, tc = s->t_critic + u + 1;
-            const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+            const int64_t n = s->n_updates + u;
             st.sa = sas[(size_t)i]; st.sa.counter = (unsigned long long)n; st.row = (int)(n % SAC_RING); st.active = 1;
-            st.c_step = (float)((double)s->ccfg.critic_lr / (1.0 - std::pow(b1, (double)tc)));
-            st.c_bc2 = (float)std::sqrt(1.0 - std::pow(b2, (double)tc));
+            const AdamStep cs = adam_step(s->ccfg.critic_lr, c->cfg.beta1, c->cfg.beta2, s->t_critic + u + 1);
+            st.c_step = cs.step_size; st.c_bc2 = cs.bc2_sqrt;
             for (int it = 0; it < M; ++it) {           // t_actor advances once per M iteration
-                const int64_t ta = s->t_actor + (int64_t)u * M + it + 1;
-                CvpoGroupIter& gi = g->h_iters[((size_t)u * M + it) * k + i];
-                gi.a_step = (float)((double)s->ccfg.actor_lr / (1.0 - std::pow(b1, (double)ta)));
-                gi.a_bc2 = (float)std::sqrt(1.0 - std::pow(b2, (double)ta));
+                const AdamStep as = adam_step(s->ccfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + (int64_t)u * M + it + 1);
+                CvpoGroupIter& gi = g->iters.h[((size_t)u * M + it) * k + i];
+                gi.a_step = as.step_size; gi.a_bc2 = as.bc2_sqrt;
             }
         }
-    hipStream_t gs = g->stream;
-    HIPCHK(hipMemcpyAsync(g->d_tab, g->h_tab, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));
-    HIPCHK(hipMemcpyAsync(g->d_ctab, g->h_ctab, (size_t)k * sizeof(CvpoGroupMember), hipMemcpyHostToDevice, gs));
-    HIPCHK(hipMemcpyAsync(g->d_steps, g->h_steps, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
-    HIPCHK(hipMemcpyAsync(g->d_iters, g->h_iters, (size_t)n_max * M * k * sizeof(CvpoGroupIter), hipMemcpyHostToDevice, gs));
+    hipStream_t gs = gc.stream;
+    HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->ctab.d, g->ctab.h, (size_t)k * sizeof(CvpoGroupMember), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, n_steps * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
+    HIPCHK(hipMemcpyAsync(g->iters.d, g->iters.h, n_iters * sizeof(CvpoGroupIter), hipMemcpyHostToDevice, gs));
     const ModelDesc mda = s0->mda;
     ModelDesc mdq = s0->mdq, mdq_w = s0->mdq, mda_w = s0->mda;
     mdq_w.n_nets = n_q; mda_w.n_nets = 1;              // sac_wgrad: the launch covers the first ny networks
-    const int na_dev = s0->na_dev, nq_dev = s0->nq_dev;
-    const SacGroupMember* tab = g->d_tab;
-    const CvpoGroupMember* ctab = g->d_ctab;
+    const int na_dev = s0->na_dev;
+    const SacGroupMember* tab = g->tab.d;
+    const CvpoGroupMember* ctab = g->ctab.d;
     const int sg_blocks = (B + SG_ROWS - 1) / SG_ROWS + (B * K + 255) / 256;
     rc = dispatch_H(H, [&](auto hc) {
         constexpr int HH = decltype(hc)::value;
         const int ft = th.f_r4 ? 4 * nt : nt, qt = th.q_r4 ? 4 * nt : nt, at = th.a_r4 ? 4 * nt : nt, kt = th.k_r4 ? 4 * ntk : ntk;
-        const int gq = round_up(rq_total, 8), ga = round_up(ra_total, 8);
+        const int ga = round_up(ra_total, 8);
+        const ReplayGroupCritic cr{k, n_q, qt, rp, round_up(rq_total, 8), s0->nq_dev, nsq, th.q_r4, small_wgrad};
         for (int u = 0; u < n_max; ++u) {
-            const SacGroupStep* st = g->d_steps + (size_t)u * k;
+            const SacGroupStep* st = g->steps.d + (size_t)u * k;
             // 1. sample + gather + the particles' noise; 2. a' ~ actor(s_{t+n}) and the K particles of actor_old at s_t
             hipLaunchKernelGGL(cvpo_sample_gather_group_kernel, dim3(sg_blocks, k), dim3(256), 0, gs, ctab, st);
             if (th.f_r4) hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 4, 0>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, ctab, st);
             else hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 16, 0>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, ctab, st);
-            // 3. target Q-networks on (s_{t+n}, a'); 4. the critics' forward + backward with their n-step targets
-            if (th.q_r4) {
-                hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-                hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-            } else {
-                hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-                hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-            }
-            // 5. the critics' weight gradients; 6. their Adam with the Polyak targets
-            if (small_wgrad) hipLaunchKernelGGL((sac_wgrad_group_kernel<HH, 0>), dim3(wg_grid(HH, n_q), k), dim3(1024), 0, gs, mdq_w, tab, st, rp);
-            else hipLaunchKernelGGL((sac_wgrad_split_group_kernel<HH, 0>), dim3(gq, k), dim3(1024), 0, gs, mdq, tab, st);
-            hipLaunchKernelGGL(sac_adam_group_kernel, dim3((nq_dev + 255) / 256, k), dim3(256), 0, gs, mdq, tab, st, nq_dev, nsq, nq_dev);
+            // 3. - 6. the critic half
+            rgroup_critic_half<HH>(gs, cr, mdq, mdq_w, tab, st);
             // 7. the K * B particles through the updated critics; 8. the E-step, one workgroup per member
             if (th.k_r4) hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 2>), dim3(kt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
             else hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 2>), dim3(kt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
             hipLaunchKernelGGL(cvpo_estep_group_kernel, dim3(k), dim3(1024), 0, gs, ctab, st);
             // ---- M-step: statistics, dual step (one wave per member), backward, weight gradients, Adam
             for (int it = 0; it < M; ++it) {
-                const CvpoGroupIter* gi = g->d_iters + ((size_t)u * M + it) * k;
+                const CvpoGroupIter* gi = g->iters.d + ((size_t)u * M + it) * k;
                 if (th.a_r4) hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 4, 1>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
                 else hipLaunchKernelGGL((cvpo_actor_group_kernel<HH, 16, 1>), dim3(at, k), dim3(4 * HH), 0, gs, mda, ctab, st);
                 hipLaunchKernelGGL(cvpo_mdual_group_kernel, dim3(k), dim3(64), 0, gs, ctab, st, it == 0 ? 1 : 0);
@@ -318,14 +257,13 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
         return 0;
     });
     if (rc) return rc;
-    HIPCHK(hipEventRecord(g->done, gs));
+    HIPCHK(hipEventRecord(gc.done, gs));
     // ---- each member's streams wait for the call; its bookkeeping is that of n_i own updates
     for (int i = 0; i < k; ++i) {
         if (n_updates[i] == 0) continue;
-        fsrl_ctx* c = g->m[i];
-        SacState* s = sac_of(c);
-        HIPCHK(hipStreamWaitEvent(c->compute, g->done, 0));
-        HIPCHK(hipStreamWaitEvent(c->side, g->done, 0));     // a push must not overwrite rows the call still samples
+        rc = rgroup_fanout(gc, i);
+        if (rc) return rc;
+        SacState* s = sac_of(gc.m[i]);
         s->n_updates += n_updates[i]; s->t_critic += n_updates[i]; s->t_actor += (int64_t)n_updates[i] * M;
         s->last_B = B;
     }

@@ -110,28 +110,18 @@ static WgradPtrs focops_wgrad_ptrs(const fsrl_ctx* c, const float* obs, int rows
 }
 // ... and in fb_wgrad_kernel's (four-launch step; wgrad_launch fills in the split-K plan)
 static FbWgradArgs focops_split_args(const fsrl_ctx* c, const float* obs, int size, int rows_pad) {
-    const int H = c->cfg.hidden;
     FbWgradArgs wa{};
-    for (int y = 0; y < 3; ++y) {
-        const size_t nb = (size_t)y * rows_pad;
-        FbWgradNet& wn = wa.nets[y];
-        wn.w2_ya = c->D2 + nb * H; wn.w2_xa = c->A1 + nb * H; wn.w1_y = c->D1 + nb * H;
-        wn.w3_xa = c->A2 + nb * H; wn.w3_ya = c->DO + nb * FSRL_DOW;
-        wn.b1_src = c->D1 + nb * H; wn.b2_src = c->D2 + nb * H; wn.do_src = c->DO + nb * FSRL_DOW;
-        wn.net = y;
-    }
+    wgrad_fill_nets(wa, 3, 0, (size_t)c->cfg.hidden, (size_t)rows_pad, c->A1, c->A2, c->D1, c->D2, c->DO);
     wa.obs = obs; wa.rows = rows_pad; wa.N = size;
     return wa;
 }
 // one minibatch step's optimiser side: both Adam step counters advance, the logged row goes to statistics row `row`
 static void focops_step_fill(fsrl_ctx* c, FocopsStepArgs& sa, int64_t row, int mb, int nmb, int size, int n_tiles) {
     FocState* f = c->foc;
-    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
     f->t_critic += 1; f->t_actor += 1;
-    sa.step_a = (float)((double)f->cfg.actor_lr / (1.0 - std::pow(b1, (double)f->t_actor)));
-    sa.bc2s_a = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_actor));
-    sa.step_c = (float)((double)f->cfg.critic_lr / (1.0 - std::pow(b1, (double)f->t_critic)));
-    sa.bc2s_c = (float)std::sqrt(1.0 - std::pow(b2, (double)f->t_critic));
+    const AdamStep aa = adam_step(f->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, f->t_actor);
+    const AdamStep ac = adam_step(f->cfg.critic_lr, c->cfg.beta1, c->cfg.beta2, f->t_critic);
+    sa.step_a = aa.step_size; sa.bc2s_a = aa.bc2_sqrt; sa.step_c = ac.step_size; sa.bc2s_c = ac.bc2_sqrt;
     // ---- logged row, pass KL sum, pass-level early stop flag (the extra block of the step launch)
     FocopsFinalArgs& fa = sa.fin;
     fa.statp_vf = f->statp_pi + FB_NSTAT; fa.statp_pi = f->statp_pi; fa.vf_stride = 3; fa.pi_stride = 3;

@@ -29,24 +29,6 @@ static int focops_group_check(fsrl_ctx* const* ctxs, int k) {
     return 0;
 }
 
-static int focops_group_ensure_steps(fsrl_group* g, size_t nmb) {
-    const size_t k = g->m.size();
-    if (!g->d_ftab) {
-        HIPCHK(hipMalloc(&g->d_ftab, k * sizeof(FocGroupMember)));
-        HIPCHK(hipHostMalloc(&g->h_ftab, k * sizeof(FocGroupMember)));
-    }
-    if (nmb <= g->cap_fmb) return 0;
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (g->d_fsteps) HIPCHK(hipFree(g->d_fsteps));
-    if (g->h_fsteps) HIPCHK(hipHostFree(g->h_fsteps));
-    g->d_fsteps = nullptr; g->h_fsteps = nullptr;
-    const size_t cap = nmb * 2, bytes = cap * k * sizeof(FocGroupStep);
-    HIPCHK(hipMalloc(&g->d_fsteps, bytes));
-    HIPCHK(hipHostMalloc(&g->h_fsteps, bytes));
-    g->cap_fmb = cap;
-    return 0;
-}
-
 static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
                                float* const* stats_out, int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
     const int k = (int)g->m.size();
@@ -77,14 +59,17 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
     }
     size_t cap_nmb = 0;
     for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
-    rc = focops_group_ensure_steps(g, std::max<size_t>(cap_nmb, 1));
+    rc = table_ensure(g->ftab, (size_t)k, (size_t)k);
+    if (rc) return abort_all(rc);
+    const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;          // grown as the PPO group's step table
+    rc = table_ensure(g->fsteps, n_steps, 2 * n_steps, g->stream);
     if (rc) return abort_all(rc);
     int nb_a, nb_c0, nb_c1;
     focops_blocks(c0, &nb_a, &nb_c0, &nb_c1);
     const int nb_all = nb_a + nb_c0 + nb_c1;
     // fb_wgrad_kernel's plan in wgrad_launch (PAIR2 = false): blocks of one split and network
-    const int passes = 1 + std::max(0, (c0->md.Do - 16 * 2 + 63) / 64);
-    const int NB = (H / 64) * (H / 64) + (H / FB_AUX_COLS) * passes + 1;
+    const WgradBlocks wb = wgrad_blocks(c0->md.Do, H, false);
+    const int passes = wb.passes, NB = wb.NB;
     std::vector<char> rows4;
     for (int pass = 0; pass < repeat; ++pass) {
         int n_act = 0;
@@ -116,10 +101,10 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             rows4[mb] = (size_t)tiles * 4 * nn * n_act <= (size_t)c0->n_cus;
         }
         // ---- member table and step table of the pass: focops_pass's arguments, member by member
-        memset(g->h_fsteps, 0, max_nmb * k * sizeof(FocGroupStep));
+        memset(g->fsteps.h, 0, max_nmb * k * sizeof(FocGroupStep));
         for (int i = 0; i < k; ++i) {
             fsrl_ctx* c = g->m[i];
-            FocGroupMember& t = g->h_ftab[i];
+            FocGroupMember& t = g->ftab.h[i];
             memset(&t, 0, sizeof(t));
             t.P = c->P;
             if (!active[(size_t)i]) continue;
@@ -130,7 +115,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             const int nmb = (int)c->mb_start.size();
             for (size_t mb = 0; mb < max_nmb; ++mb) {
                 if ((int)mb >= nmb) break;
-                FocGroupStep& st = g->h_fsteps[mb * k + i];
+                FocGroupStep& st = g->fsteps.h[mb * k + i];
                 const int start = c->mb_start[mb], size = c->mb_size[mb];
                 const int tiles = (size + 15) / 16, rows_pad = tiles * 16;
                 st.active = 1;
@@ -155,18 +140,18 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
                 f->pp ^= 1;
             }
         }
-        HIPCHK(hipMemcpyAsync(g->d_ftab, g->h_ftab, (size_t)k * sizeof(FocGroupMember), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->d_fsteps, g->h_fsteps, max_nmb * k * sizeof(FocGroupStep), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->ftab.d, g->ftab.h, (size_t)k * sizeof(FocGroupMember), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->fsteps.d, g->fsteps.h, max_nmb * k * sizeof(FocGroupStep), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(g->steps_copied, s));
         g->steps_in_flight = true;
         // ---- the pass: one pass-start prep for the three-launch members, then per minibatch step 3 or 4 launches for all
         bool any_fast = false;
         for (int i = 0; i < k; ++i) any_fast = any_fast || (active[(size_t)i] && fast[(size_t)i]);
         if (any_fast)
-            hipLaunchKernelGGL((focops_prep_group_kernel<1>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->d_ftab, g->d_fsteps);
+            hipLaunchKernelGGL((focops_prep_group_kernel<1>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->ftab.d, g->fsteps.d);
         for (size_t mb = 0; mb < max_nmb; ++mb) {
-            const FocGroupStep* hst = g->h_fsteps + mb * k;
-            const FocGroupStep* st = g->d_fsteps + mb * k;
+            const FocGroupStep* hst = g->fsteps.h + mb * k;
+            const FocGroupStep* st = g->fsteps.d + mb * k;
             int tiles = 0, remap = 0;
             bool f3 = false, f4 = false;
             for (int i = 0; i < k; ++i) {
@@ -178,15 +163,15 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             if (tiles == 0) continue;                            // no active member has a minibatch at this index
             rc = dispatch_H(H, [&](auto hc) {
                 constexpr int HH = decltype(hc)::value;
-                if (rows4[mb]) hipLaunchKernelGGL((focops_tile_group_kernel<HH, 4>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->d_ftab, st);
-                else hipLaunchKernelGGL((focops_tile_group_kernel<HH, 16>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->d_ftab, st);
-                if (f3) hipLaunchKernelGGL((focops_wgrad_group_kernel<HH>), dim3(wg_grid(HH, nn), k), dim3(1024), 0, s, c0->md, g->d_ftab, st);
+                if (rows4[mb]) hipLaunchKernelGGL((focops_tile_group_kernel<HH, 4>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->ftab.d, st);
+                else hipLaunchKernelGGL((focops_tile_group_kernel<HH, 16>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->ftab.d, st);
+                if (f3) hipLaunchKernelGGL((focops_wgrad_group_kernel<HH>), dim3(wg_grid(HH, nn), k), dim3(1024), 0, s, c0->md, g->ftab.d, st);
                 if (f4) hipLaunchKernelGGL((focops_wgrad_split_group_kernel<HH>), dim3(round_up(remap, 8), k), dim3(1024), 0, s, c0->md,
-                                           g->d_ftab, st);
+                                           g->ftab.d, st);
                 return 0;
             });
             if (rc) return abort_all(rc);
-            if (f4) hipLaunchKernelGGL((focops_prep_group_kernel<0>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->d_ftab, st);
+            if (f4) hipLaunchKernelGGL((focops_prep_group_kernel<0>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->ftab.d, st);
             hipLaunchKernelGGL(focops_step_group_kernel, dim3(nb_all + 1, k), dim3(256), 0, s, c0->md, st);
             HIPCHK(hipGetLastError());
         }

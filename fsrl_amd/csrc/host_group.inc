@@ -12,16 +12,14 @@ struct fsrl_group {
     std::vector<fsrl_ctx*> m;                   // members (not owned)
     std::vector<hipStream_t> own_stream;        // each member's own compute stream, restored at destroy
     hipStream_t stream = nullptr;               // the shared stream: the group's own (a member's death must not take it along)
-    GroupAgent* d_tab = nullptr; GroupAgent* h_tab = nullptr;      // device / pinned
-    GroupStep* d_steps = nullptr; GroupStep* h_steps = nullptr;    // [cap_mb][k]
-    size_t cap_mb = 0;
+    DevTable<GroupAgent> tab;                   // [k]
+    DevTable<GroupStep> steps;                  // [minibatch steps of a pass][k]
     hipEvent_t steps_copied = nullptr; bool steps_in_flight = false;
     bool broken = false;                        // a member was destroyed: no more updates
     int tall_tiles = -1;                        // fsrl_group_set_plan: 32-row tiles per (member, network) of the forward / backward launch
-    // FOCOPS groups (host_focops_group.inc): member table and [cap_fmb][k] step table
-    FocGroupMember* d_ftab = nullptr; FocGroupMember* h_ftab = nullptr;
-    FocGroupStep* d_fsteps = nullptr; FocGroupStep* h_fsteps = nullptr;
-    size_t cap_fmb = 0;
+    // FOCOPS groups (host_focops_group.inc): member table and [minibatch steps of a pass][k] step table
+    DevTable<FocGroupMember> ftab;
+    DevTable<FocGroupStep> fsteps;
     // lock-step collection (host_group_collect.inc): ONE resident actor kernel for every member, rung through ONE doorbell
     GaRing ga;                                  // ring, protocol state and counters (host_actor_ring.inc); its stream is `stream`
 };
@@ -70,8 +68,8 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
         c->compute = g->stream;                 // everything a member enqueues from now on goes to the shared stream
         c->group = g;
     }
-    hipError_t e = hipMalloc(&g->d_tab, (size_t)k * sizeof(GroupAgent));
-    if (e == hipSuccess) e = hipHostMalloc(&g->h_tab, (size_t)k * sizeof(GroupAgent));
+    hipError_t e = hipMalloc(&g->tab.d, (size_t)k * sizeof(GroupAgent));
+    if (e == hipSuccess) e = hipHostMalloc(&g->tab.h, (size_t)k * sizeof(GroupAgent));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->steps_copied, hipEventDisableTiming);
     if (e != hipSuccess) {
         fail(FSRL_EHIP, "group allocation failed: %s", hipGetErrorString(e));
@@ -108,16 +106,10 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     for (size_t i = 0; i < g->m.size(); ++i)
         if (g->m[i]) { g->m[i]->compute = g->own_stream[i]; g->m[i]->group = nullptr; }
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->d_tab) (void)hipFree(g->d_tab);
-    if (g->h_tab) (void)hipHostFree(g->h_tab);
-    if (g->d_steps) (void)hipFree(g->d_steps);
-    if (g->h_steps) (void)hipHostFree(g->h_steps);
+    table_free(g->tab); table_free(g->steps);
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
     if (g->ga.h) (void)hipHostFree(g->ga.h);
-    if (g->d_ftab) (void)hipFree(g->d_ftab);
-    if (g->h_ftab) (void)hipHostFree(g->h_ftab);
-    if (g->d_fsteps) (void)hipFree(g->d_fsteps);
-    if (g->h_fsteps) (void)hipHostFree(g->h_fsteps);
+    table_free(g->ftab); table_free(g->fsteps);
     delete g;
     return 0;
 }
@@ -129,19 +121,6 @@ extern "C" int fsrl_group_set_plan(fsrl_group* g, int32_t tall_tiles) {
     CHECK_ARG(g, "null group");
     CHECK_ARG(tall_tiles >= -1 && tall_tiles <= 1024, "tall_tiles: -1 (automatic), 0 (none) or a count");
     g->tall_tiles = tall_tiles;
-    return 0;
-}
-
-static int group_ensure_steps(fsrl_group* g, size_t nmb) {
-    if (nmb <= g->cap_mb) return 0;
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (g->d_steps) HIPCHK(hipFree(g->d_steps));
-    if (g->h_steps) HIPCHK(hipHostFree(g->h_steps));
-    g->d_steps = nullptr; g->h_steps = nullptr;
-    const size_t cap = nmb * 2, bytes = cap * g->m.size() * sizeof(GroupStep);
-    HIPCHK(hipMalloc(&g->d_steps, bytes));
-    HIPCHK(hipHostMalloc(&g->h_steps, bytes));
-    g->cap_mb = cap;
     return 0;
 }
 
@@ -176,7 +155,7 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
     const int nparts = wg_grid(H, nn);
     for (int i = 0; i < k; ++i) {
         fsrl_ctx* c = g->m[i];
-        GroupAgent& a = g->h_tab[i];
+        GroupAgent& a = g->tab.h[i];
         memset(&a, 0, sizeof(a));
         a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G;
         a.bp.obs_p = c->obs_p; a.bp.rd_p = c->rd_p; a.bp.A1 = c->A1; a.bp.A2 = c->A2; a.bp.D1 = c->D1; a.bp.D2 = c->D2;
@@ -197,7 +176,9 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
     // from an earlier update; a member that stopped on KL no longer counts): recomputed per pass
     size_t cap_nmb = 0;
     for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
-    int rc = group_ensure_steps(g, std::max<size_t>(cap_nmb, 1));
+    // grown to twice what this call needs, behind the stream's reads of the old tables
+    const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;
+    int rc = table_ensure(g->steps, n_steps, 2 * n_steps, g->stream);
     if (rc) return abort_all(rc);
     for (int pass = 0; pass < repeat; ++pass) {
         bool any = false;
@@ -214,15 +195,15 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
             fsrl_ctx* c = g->m[i];
             rc = ppo_pass_prepare(c, perms ? perms[i] + (size_t)pass * (size_t)n[i] : nullptr, seed ? seed + 1000003ull * i + pass : 0);
             if (rc) return abort_all(rc);
-            g->h_tab[i].wp.stats = c->d_stats;
+            g->tab.h[i].wp.stats = c->d_stats;
             for (int sz : c->mb_size) max_mbsize = std::max(max_mbsize, sz);
         }
-        HIPCHK(hipMemcpyAsync(g->d_tab, g->h_tab, (size_t)k * sizeof(GroupAgent), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(GroupAgent), hipMemcpyHostToDevice, s));
         // ---- step table of the pass
         for (size_t mb = 0; mb < max_nmb; ++mb) {
             for (int i = 0; i < k; ++i) {
                 fsrl_ctx* c = g->m[i];
-                GroupStep& st = g->h_steps[mb * k + i];
+                GroupStep& st = g->steps.h[mb * k + i];
                 memset(&st, 0, sizeof(st));
                 const size_t nmb = c->mb_start.size();
                 if (!active[(size_t)i] || mb >= nmb) continue;
@@ -231,12 +212,11 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
                 st.step = (int)c->n_steps + (int)mb;
                 st.first_in_pass = (mb == 0); st.last_in_pass = (mb == nmb - 1); st.iters_in_pass = (int)nmb;
                 st.pass = c->pass_index;
-                const double t = (double)(c->adam_t + (int64_t)mb + 1);
-                st.step_size = (float)((double)c->cfg.lr / (1.0 - std::pow((double)c->cfg.beta1, t)));
-                st.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)c->cfg.beta2, t));
+                const AdamStep as = adam_step(c->cfg.lr, c->cfg.beta1, c->cfg.beta2, c->adam_t + (int64_t)mb + 1);
+                st.step_size = as.step_size; st.bc2_sqrt = as.bc2_sqrt;
             }
         }
-        HIPCHK(hipMemcpyAsync(g->d_steps, g->h_steps, max_nmb * k * sizeof(GroupStep), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, max_nmb * k * sizeof(GroupStep), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(g->steps_copied, s));
         g->steps_in_flight = true;
         // ---- the minibatch steps: 3 (2 without a clip) launches for all members
@@ -244,9 +224,9 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
         for (int i = 0; i < k; ++i) n_act += active[(size_t)i] ? 1 : 0;
         (void)max_mbsize;
         for (size_t mb = 0; mb < max_nmb; ++mb) {
-            const GroupStep* st = g->d_steps + mb * k;
+            const GroupStep* st = g->steps.d + mb * k;
             int mbs = 0;                                         // the largest minibatch any member has at this step
-            for (int i = 0; i < k; ++i) mbs = std::max(mbs, g->h_steps[mb * k + i].active ? g->h_steps[mb * k + i].mb_size : 0);
+            for (int i = 0; i < k; ++i) mbs = std::max(mbs, g->steps.h[mb * k + i].active ? g->steps.h[mb * k + i].mb_size : 0);
             if (mbs == 0) continue;                              // no active member has a minibatch at this index: nothing to launch
             const int tiles = (mbs + 15) / 16;
             // 4-row tiles only while the whole group still fits the chip in one round (a lone member: the single-agent rule)
@@ -268,18 +248,18 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
             const bool big = tiles * 16 > 256;                  // up to 256 rows: bursts of 4 k-steps, two workgroups per CU; above: the chunked 512-row form
             rc = dispatch_H(H, [&](auto hc) {
                 constexpr int HH = decltype(hc)::value;
-                if (rows4) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 4>), dim3(tiles * 4 * nn, k), dim3(4 * HH), 0, s, c0->md, g->d_tab, st, base);
-                else if (rows8) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 8>), dim3(tiles * 2 * nn, k), dim3(4 * HH), 0, s, c0->md, g->d_tab, st, base);
+                if (rows4) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 4>), dim3(tiles * 4 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
+                else if (rows8) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 8>), dim3(tiles * 2 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
                 else if (n32 > 0) {
                     if constexpr (HH >= 128)
-                        hipLaunchKernelGGL((ppo_fwd_bwd_group_mix_kernel<HH>), dim3(per_net * nn, k), dim3(4 * HH), 0, s, c0->md, g->d_tab, st, base,
+                        hipLaunchKernelGGL((ppo_fwd_bwd_group_mix_kernel<HH>), dim3(per_net * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base,
                                            n32, per_net);
-                } else hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 16>), dim3(tiles * nn, k), dim3(4 * HH), 0, s, c0->md, g->d_tab, st, base);
+                } else hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 16>), dim3(tiles * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
 #define FSRL_WG(BIGV, FUSEV)                                                                                                      \
     do {                                                                                                                          \
-        if (rows4) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 4>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->d_tab, st, base); \
-        else if (rows8) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 8>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->d_tab, st, base); \
-        else hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 16>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->d_tab, st, base);      \
+        if (rows4) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 4>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
+        else if (rows8) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 8>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
+        else hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 16>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base);      \
     } while (0)
                 if (base.fuse_adam) { if (big) FSRL_WG(true, true); else FSRL_WG(false, true); }
                 else { if (big) FSRL_WG(true, false); else FSRL_WG(false, false); }
@@ -289,7 +269,7 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
             if (rc) return abort_all(rc);
             if (!base.fuse_adam)
                 hipLaunchKernelGGL(adam_clip_group_kernel, dim3((c0->n_dev + 4 * ADAM_NT - 1) / (4 * ADAM_NT), k), dim3(ADAM_NT), 0, s,
-                                   c0->md, g->d_tab, st, base);
+                                   c0->md, g->tab.d, st, base);
             HIPCHK(hipGetLastError());
         }
         for (int i = 0; i < k; ++i) {

@@ -452,10 +452,8 @@ static int lay_ppo_steps(fsrl_ctx* c) {
         sa.step = (int)c->n_steps + mb;
         sa.first_in_pass = (mb == 0); sa.last_in_pass = (mb == nmb - 1);
         c->adam_t += 1;
-        const double bc1 = 1.0 - std::pow((double)c->cfg.beta1, (double)c->adam_t);
-        const double bc2 = 1.0 - std::pow((double)c->cfg.beta2, (double)c->adam_t);
-        sa.step_size = (float)((double)c->cfg.lr / bc1);
-        sa.bc2_sqrt = (float)std::sqrt(bc2);
+        const AdamStep as = adam_step(c->cfg.lr, c->cfg.beta1, c->cfg.beta2, c->adam_t);
+        sa.step_size = as.step_size; sa.bc2_sqrt = as.bc2_sqrt;
         const int rows = sa.mb_size, tiles = (rows + 15) / 16;
         const float* X = c->obs_p + (size_t)sa.mb_start * Do;
         int rc = lay_fwd(c, X, rows);

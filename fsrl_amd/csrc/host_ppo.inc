@@ -314,10 +314,8 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
         sa.step = (int)c->n_steps + mb;
         sa.first_in_pass = (mb == 0); sa.last_in_pass = (mb == nmb - 1);
         c->adam_t += 1;
-        const double bc1 = 1.0 - std::pow((double)c->cfg.beta1, (double)c->adam_t);
-        const double bc2 = 1.0 - std::pow((double)c->cfg.beta2, (double)c->adam_t);
-        sa.step_size = (float)((double)c->cfg.lr / bc1);
-        sa.bc2_sqrt = (float)std::sqrt(bc2);
+        const AdamStep as = adam_step(c->cfg.lr, c->cfg.beta1, c->cfg.beta2, c->adam_t);
+        sa.step_size = as.step_size; sa.bc2_sqrt = as.bc2_sqrt;
         const int tiles = (sa.mb_size + 15) / 16;
         wp.X = c->obs_p + (size_t)sa.mb_start * c->cfg.obs_dim;
         const bool prof = c->profiling;
@@ -371,14 +369,7 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
             // weight-gradient kernel splits the rows over workgroups instead (17 us), followed by the sum of its partials
             // (+ the per-block squared norms), the logged row and the Adam kernel: 5 launches for a step of this size.
             FbWgradArgs wa{};
-            for (int y = 0; y < nn; ++y) {
-                const size_t nb = (size_t)y * c->mbp_max;
-                FbWgradNet& wn = wa.nets[y];
-                wn.w2_ya = c->D2 + nb * H; wn.w2_xa = c->A1 + nb * H; wn.w1_y = c->D1 + nb * H;
-                wn.w3_xa = c->A2 + nb * H; wn.w3_ya = c->DO + nb * FSRL_DOW;
-                wn.b1_src = c->D1 + nb * H; wn.b2_src = c->D2 + nb * H; wn.do_src = c->DO + nb * FSRL_DOW;
-                wn.net = y;
-            }
+            wgrad_fill_nets(wa, nn, 0, (size_t)H, (size_t)c->mbp_max, c->A1, c->A2, c->D1, c->D2, c->DO);
             wa.obs = wp.X; wa.rows = tiles * 16; wa.N = sa.mb_size;
             int nsplit = 1;
             rc = wgrad_launch<false>(c, c->md, wa, nn, c->n_dev, &nsplit);

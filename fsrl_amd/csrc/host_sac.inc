@@ -414,7 +414,101 @@ static inline bool store_end_flag(const fsrl_ctx* c, int64_t idx) {
     return eb.size > 0 && local == (eb.index - 1 + eb.size) % eb.size;   // unfinished tail
 }
 
-// the arguments of a Q-network tile launch of n_tiles 16-row groups (sac_q_launch; the grouped CVPO update, host_cvpo_group.inc)
+// ---- the arguments of one update's launches.  fsrl_sac_update, fsrl_cvpo_update and the grouped updates (host_sac_group.inc,
+//      host_cvpo_group.inc) all form them here, so a member of a group cannot be handed anything its own update would not be.
+// library RNG: the sample of update `counter`
+static SacSampleArgs sac_sample_args(const fsrl_ctx* c, const SacState* s, int B, int n_step, int64_t stored, int64_t counter) {
+    SacSampleArgs sa{};
+    sa.book = s->d_book; sa.flags = c->st.flags; sa.idx = s->d_idx; sa.chain = s->d_chain; sa.endbits = s->d_end;
+    sa.eps_t = s->eps_t; sa.eps_p = s->eps_p; sa.env_num = c->cfg.env_num; sa.sub_size = (int)c->sub_size; sa.B = B;
+    sa.n_step = n_step; sa.Da = c->cfg.act_dim; sa.stored = (unsigned long long)stored; sa.key = s->key;
+    sa.counter = (unsigned long long)counter;
+    return sa;
+}
+static SacGatherArgs sac_gather_args(const fsrl_ctx* c, const SacState* s, int B, int n_step) {
+    SacGatherArgs ga{};
+    ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(n_step - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
+    ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = c->cfg.obs_dim; ga.Da = c->cfg.act_dim;
+    return ga;
+}
+// what the actor's forward and backward launches share; the caller adds the second batch, tiles_half and the folded sample
+static SacActorArgs sac_actor_args(const fsrl_ctx* c, const SacState* s, int B, int mode, const float* obs, const float* eps, float* X,
+                                   float* lp, float resc, float lam, int deterministic, int probe) {
+    SacActorArgs aa{};
+    aa.deterministic = deterministic; aa.max_action = c->cfg.max_action;
+    aa.obs = obs; aa.eps = eps; aa.X = X; aa.lp_out = lp; aa.DA = s->DA; aa.QP = s->QP; aa.sc = s->sc; aa.A1 = s->A1; aa.A2 = s->A2;
+    aa.cr = -resc; aa.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f;
+    aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi; aa.B = B; aa.mode = mode; aa.rescale = resc;
+    aa.auto_alpha = s->cfg.auto_alpha; aa.alpha_fixed = s->cfg.alpha;
+    aa.probe = probe;
+    return aa;
+}
+static SacNstepArgs sac_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
+    SacNstepArgs na{};
+    na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
+    na.flags = c->st.flags; na.sc = s->sc; na.Y = s->Y; na.B = B; na.n_step = s->cfg.n_step; na.gamma = c->cfg.gamma;
+    na.auto_alpha = s->cfg.auto_alpha; na.alpha_fixed = s->cfg.alpha; na.single = s->ddpg ? 1 : 0;
+    return na;
+}
+// the logged-row block of the actor's Adam pass; n_tiles_q / n_tiles_pi: the tiles whose partial statistics it adds up
+static SacFinalArgs sac_final_args(const fsrl_ctx* c, const SacState* s, int B, float resc, float lam, int n_tiles_q, int n_tiles_pi,
+                                   float* stats_row) {
+    SacFinalArgs fa{};
+    fa.statp_q = s->stq; fa.statp_pi = s->stpi; fa.sc = s->sc; fa.stats = stats_row;
+    fa.n_tiles_q = n_tiles_q; fa.n_tiles_pi = n_tiles_pi; fa.B = B; fa.rescale = resc; fa.lam = lam;
+    fa.target_entropy = s->cfg.target_entropy;
+    fa.alpha_lr = s->cfg.alpha_lr; fa.beta1 = c->cfg.beta1; fa.beta2 = c->cfg.beta2; fa.adam_eps = c->cfg.adam_eps;
+    fa.alpha_fixed = s->cfg.alpha; fa.auto_alpha = s->cfg.auto_alpha; fa.use_lagrangian = s->cfg.use_lagrangian;
+    fa.n_q = s->n_q;
+    return fa;
+}
+
+// the sampler's sub-buffer books (size, index, last_index per environment): uploaded again once the store has changed.  The
+// pre_valid / book_done steps belong to the SAC contexts' prefetched samples.  On a CVPO context pre_valid is never set (only
+// fsrl_sac_update sets it, and it refuses CVPO contexts), so the wait and the reset do nothing there, and book_done, which only
+// the side-stream prefetch waits on, is not recorded.
+static int sac_upload_book(fsrl_ctx* c, SacState* s) {
+    if (s->book_version == c->store_version) return 0;
+    hipStream_t st = c->compute;
+    HIPCHK(hipStreamSynchronize(st));           // h_book may still be in flight
+    if (s->pre_valid && s->pre_side) HIPCHK(hipEventSynchronize(s->pre_done));   // a prefetched sample still reads d_book
+    s->pre_valid = false;                       // (rider blocks ran on `st`: done)
+    for (int e = 0; e < c->cfg.env_num; ++e) {
+        const EnvBook& eb = c->env[(size_t)e];
+        s->h_book[e] = SacBook{(int)eb.size, (int)eb.index, (int)eb.last_index, 0};
+    }
+    HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, st));
+    if (s->book_done && s->plan_prefetch && !s->cvpo) HIPCHK(hipEventRecord(s->book_done, st));
+    s->book_version = c->store_version;
+    return 0;
+}
+
+// caller-provided sample (parity mode): the index chains on the host, staged through pinned memory with the target noise; the
+// caller stages its second noise block behind this
+static int sac_stage_indices(fsrl_ctx* c, SacState* s, int B, const int64_t* indices, const float* eps_target) {
+    hipStream_t st = c->compute;
+    const int Da = c->cfg.act_dim, ns = s->cfg.n_step;
+    HIPCHK(hipStreamSynchronize(st));      // pinned staging of the previous update has landed
+    for (int b = 0; b < B; ++b) {
+        const int64_t idx = indices[b];
+        CHECK_ARG(idx >= 0 && idx < c->maxsize, "index %lld out of range", (long long)idx);
+        s->h_idx[b] = (int)idx;
+        int64_t cur = idx;
+        for (int n = 0; n < ns; ++n) {      // indices[n] = buffer.next(indices[n-1])
+            if (n > 0) cur = store_next(c, cur);
+            s->h_chain[(size_t)n * B + b] = (int)cur;
+            s->h_end[(size_t)n * B + b] = store_end_flag(c, cur) ? 1 : 0;
+        }
+    }
+    memcpy(s->h_eps, eps_target, (size_t)B * Da * 4);
+    HIPCHK(hipMemcpyAsync(s->d_idx, s->h_idx, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain, (size_t)B * ns * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_end, s->h_end, (size_t)B * ns, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->eps_t, s->h_eps, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// the arguments of a Q-network tile launch of n_tiles 16-row groups (sac_q_launch; the grouped updates)
 static FbArgs sac_q_args(const fsrl_ctx* c, const SacState* s, const float* params, const float* X, int mode, float cr, float cc,
                          float* statp, int B, float* qout_override, int n_tiles, const SacNstepArgs* ns) {
     FbArgs a{};
@@ -464,6 +558,15 @@ static int sac_q_launch(fsrl_ctx* c, SacState* s, const float* params, const flo
     });
 }
 
+// the split-K weight-gradient operands of the first `ny` networks behind a tile launch over X (sac_wgrad; the grouped updates)
+static FbWgradArgs sac_wgrad_args(const fsrl_ctx* c, const SacState* s, int ny, const float* X, int B) {
+    FbWgradArgs wa{};
+    const size_t rp = (size_t)s->n_tiles * 16;
+    wgrad_fill_nets(wa, ny, 0, (size_t)c->cfg.hidden, rp, s->A1, s->A2, s->D1, s->D2, s->DO);
+    wa.obs = X; wa.rows = (int)rp; wa.N = B;
+    return wa;
+}
+
 // weight gradients of `ny` networks of `md` as split-K partials in c->wg_parts (stride = n_dev)
 static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, const float* X, int n_dev, int B, int* nsplit,
                      SgRider* rider = nullptr, bool* rode = nullptr) {
@@ -478,17 +581,7 @@ static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, cons
         *nsplit = 1;
         return 0;
     }
-    FbWgradArgs wa{};
-    const size_t H = c->cfg.hidden, rp = (size_t)s->n_tiles * 16;
-    for (int y = 0; y < ny; ++y) {
-        FbWgradNet& wn = wa.nets[y];
-        const size_t nb = (size_t)y * rp;
-        wn.w2_ya = s->D2 + nb * H; wn.w2_xa = s->A1 + nb * H; wn.w2_yb = nullptr; wn.w2_xb = nullptr;
-        wn.w1_y = s->D1 + nb * H; wn.w3_xa = s->A2 + nb * H; wn.w3_ya = s->DO + nb * FSRL_DOW;
-        wn.w3_xb = nullptr; wn.w3_yb = nullptr; wn.b1_src = s->D1 + nb * H; wn.b2_src = s->D2 + nb * H;
-        wn.do_src = s->DO + nb * FSRL_DOW; wn.net = y;
-    }
-    wa.obs = X; wa.rows = (int)rp; wa.N = B;
+    const size_t rp = (size_t)s->n_tiles * 16;
     if (rp <= 512 && !s->wgrad_splitk) {
         // Batches of up to 512 rows (the replay agents' default 256): the PPO step's weight-gradient kernel -- one workgroup per
         // 32 x 32 output tile, all rows, 16-way split-K over its waves -- writes the FINAL gradient where the Adam kernels expect
@@ -511,6 +604,7 @@ static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, cons
             return 0;
         });
     }
+    FbWgradArgs wa = sac_wgrad_args(c, s, ny, X, B);
     // the critics' launch (four networks x 25 blocks x 2 splits) in XCD-aware block order: the blocks of one (network, split) -- which
     // stream the same rows -- behind one L2.  Same sums, same time (127.6 / 127.9 us per update), 46 -> 20 MB of memory-side traffic per launch;
     // the actor's launch keeps the 3-D grid its rider blocks extend
@@ -538,10 +632,10 @@ extern "C" int fsrl_sac_set_plan(fsrl_ctx* c, int32_t plan) {
 static void adam_launch(fsrl_ctx* c, const ModelDesc& md, float* P, float* M, float* V, const float* G, int n, float lr,
                         int64_t t, int nparts, int stride, float* tgt = nullptr, float tau = 0.0f) {
     const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-    const double bc1 = 1.0 - std::pow(b1, (double)t), bc2 = 1.0 - std::pow(b2, (double)t);
+    const AdamStep as = adam_step(lr, c->cfg.beta1, c->cfg.beta2, t);
     hipLaunchKernelGGL(adam_range_kernel, dim3((n + 255) / 256), dim3(256), 0, c->compute, P, M, V, G, 0, n, 0.0f,
-                       (float)(1.0 - b1), c->cfg.beta2, (float)(1.0 - b2), (float)((double)lr / bc1),
-                       (float)std::sqrt(bc2), c->cfg.adam_eps, nparts, stride, md, (const float*)nullptr, 0, 0.0f,
+                       (float)(1.0 - b1), c->cfg.beta2, (float)(1.0 - b2), as.step_size,
+                       as.bc2_sqrt, c->cfg.adam_eps, nparts, stride, md, (const float*)nullptr, 0, 0.0f,
                        (float*)nullptr, tgt, tau, (float)(1.0 - (double)tau));
 }
 
@@ -550,9 +644,9 @@ template <class FinalArgs, void (*FINAL)(const FinalArgs&, int)>
 static void adam_final_launch(fsrl_ctx* c, const ModelDesc& md, float* P, float* M, float* V, const float* G, int n, float lr,
                               int64_t t, int nparts, int stride, float* tgt, float tau, const FinalArgs& fa) {
     const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-    const double bc1 = 1.0 - std::pow(b1, (double)t), bc2 = 1.0 - std::pow(b2, (double)t);
+    const AdamStep as = adam_step(lr, c->cfg.beta1, c->cfg.beta2, t);
     hipLaunchKernelGGL((adam_final_kernel<FinalArgs, FINAL>), dim3((n + 255) / 256 + 1), dim3(256), 0, c->compute, P, M, V, G, n,
-                       (float)(1.0 - b1), c->cfg.beta2, (float)(1.0 - b2), (float)((double)lr / bc1), (float)std::sqrt(bc2),
+                       (float)(1.0 - b1), c->cfg.beta2, (float)(1.0 - b2), as.step_size, as.bc2_sqrt,
                        c->cfg.adam_eps, nparts, stride, md, tgt, tau, (float)(1.0 - (double)tau), fa);
 }
 
@@ -578,13 +672,9 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
     bool fused_gather = false;
     bool want_rider = false;                           // r6: the NEXT update's sample + gather inside this update's actor weight-gradient launch
-    auto sample_args = [&](SacSampleArgs& sa, SacGatherArgs& ga, int64_t counter) {
-        sa.book = s->d_book; sa.flags = c->st.flags; sa.idx = s->d_idx; sa.chain = s->d_chain; sa.endbits = s->d_end;
-        sa.eps_t = s->eps_t; sa.eps_p = s->eps_p; sa.env_num = c->cfg.env_num; sa.sub_size = (int)c->sub_size; sa.B = B;
-        sa.n_step = ns; sa.Da = Da; sa.stored = (unsigned long long)stored; sa.key = s->key;
-        sa.counter = (unsigned long long)counter;
-        ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(ns - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
-        ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = Do; ga.Da = Da;
+    auto sample_args = [&](SacSampleArgs& sa, SacGatherArgs& ga, int64_t counter) {      // of the batch set `s` addresses when called (swap_sets)
+        sa = sac_sample_args(c, s, B, ns, stored, counter);
+        ga = sac_gather_args(c, s, B, ns);
     };
     auto swap_sets = [&]() {
         std::swap(s->d_idx, s->alt.d_idx); std::swap(s->d_chain, s->alt.d_chain); std::swap(s->d_end, s->alt.d_end);
@@ -594,41 +684,16 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     bool fold = false;                                 // r5: sample + gather inside the actors' forward launch
     SacSampleArgs fold_sa{}; SacGatherArgs fold_ga{};
     if (indices) {
-        // ---- caller-provided sample (parity mode): index chains on the host, staged through pinned memory
-        HIPCHK(hipStreamSynchronize(st));      // pinned staging of the previous update has landed
-        for (int b = 0; b < B; ++b) {
-            const int64_t idx = indices[b];
-            CHECK_ARG(idx >= 0 && idx < c->maxsize, "index %lld out of range", (long long)idx);
-            s->h_idx[b] = (int)idx;
-            int64_t cur = idx;
-            for (int n = 0; n < ns; ++n) {      // indices[n] = buffer.next(indices[n-1])
-                if (n > 0) cur = store_next(c, cur);
-                s->h_chain[(size_t)n * B + b] = (int)cur;
-                s->h_end[(size_t)n * B + b] = store_end_flag(c, cur) ? 1 : 0;
-            }
-        }
-        float* he_t = s->h_eps; float* he_p = s->h_eps + (size_t)B * Da;
-        memcpy(he_t, eps_target, (size_t)B * Da * 4);
+        // ---- caller-provided sample (parity mode): the policy's noise goes behind the target's in the pinned block
+        rc = sac_stage_indices(c, s, B, indices, eps_target);
+        if (rc) return rc;
+        float* he_p = s->h_eps + (size_t)B * Da;
         memcpy(he_p, eps_pi, (size_t)B * Da * 4);
-        HIPCHK(hipMemcpyAsync(s->d_idx, s->h_idx, (size_t)B * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain, (size_t)B * ns * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->d_end, s->h_end, (size_t)B * ns, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s->eps_t, he_t, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(s->eps_p, he_p, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
     } else {
         // ---- library RNG: everything on the device, nothing to wait for
-        if (s->book_version != c->store_version) {     // the store changed since the last upload
-            HIPCHK(hipStreamSynchronize(st));           // h_book may still be in flight
-            if (s->pre_valid && s->pre_side) HIPCHK(hipEventSynchronize(s->pre_done));   // a prefetched sample still reads d_book
-            s->pre_valid = false;                       // (rider blocks ran on `st`: done)
-            for (int e = 0; e < c->cfg.env_num; ++e) {
-                const EnvBook& eb = c->env[(size_t)e];
-                s->h_book[e] = SacBook{(int)eb.size, (int)eb.index, (int)eb.last_index, 0};
-            }
-            HIPCHK(hipMemcpyAsync(s->d_book, s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook), hipMemcpyHostToDevice, st));
-            if (s->book_done && s->plan_prefetch) HIPCHK(hipEventRecord(s->book_done, st));
-            s->book_version = c->store_version;
-        }
+        rc = sac_upload_book(c, s);
+        if (rc) return rc;
         // sample + gather as ONE launch (plan 0); fsrl_sac_set_plan bit 1 keeps the two launches for A/B
         fused_gather = !s->plan_separate;
         const bool can_prefetch = fused_gather && s->plan_prefetch && !s->cvpo;
@@ -670,9 +735,7 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     const float resc = (float)rescaling;
     // ---- gather (the caller's indices, or the two-launch plan)
     if (!fused_gather) {
-        SacGatherArgs ga{};
-        ga.st = c->st; ga.idx = s->d_idx; ga.term = s->d_chain + (size_t)(ns - 1) * B; ga.XQ = s->XQ; ga.OBS = s->OBS;
-        ga.OBSN = s->OBSN; ga.XN = s->XN; ga.XP = s->XP; ga.B = B; ga.Do = Do; ga.Da = Da;
+        const SacGatherArgs ga = sac_gather_args(c, s, B, ns);
         hipLaunchKernelGGL(sac_gather_kernel, dim3(std::min(1024, (B * (Do + Da) + 255) / 256)), dim3(256), 0, st, ga);
         HIPCHK(hipGetLastError());
     }
@@ -697,19 +760,14 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
             if (both) { rc2 = one(s->PA, s->OBS, s->eps_p, s->XP, s->LP); if (rc2) return rc2; }
             return mode == SAC_A_BWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
         }
-        SacActorArgs aa{};
+        // probe: c->probe_phase is 0 outside probe builds
+        SacActorArgs aa = sac_actor_args(c, s, B, mode, obs, eps, X, lp, resc, lam, s->ddpg ? 1 : 0, c->probe_phase);
         // 4-row tiles while the launch fits the chip in one round; the two-batch forward is twice as many workgroups
         const bool r4 = s->a_rows4 && (!both || 8 * s->n_tiles <= c->n_cus);
         const int tiles = r4 ? 4 * s->n_tiles : s->n_tiles;
         if (both) { aa.P2 = s->PA; aa.obs2 = s->OBS; aa.eps2 = s->eps_p; aa.X2 = s->XP; aa.lp2 = s->LP; aa.tiles_half = tiles; }
         if (both && fold) { aa.sg_on = 1; aa.sa = fold_sa; aa.ga = fold_ga; }
         const int grid = both ? 2 * tiles : tiles;
-        aa.deterministic = s->ddpg ? 1 : 0; aa.max_action = c->cfg.max_action;
-        aa.obs = obs; aa.eps = eps; aa.X = X; aa.lp_out = lp; aa.DA = s->DA; aa.QP = s->QP; aa.sc = s->sc; aa.A1 = s->A1; aa.A2 = s->A2;
-        aa.cr = -resc; aa.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f;
-        aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi; aa.B = B; aa.mode = mode; aa.rescale = resc;
-        aa.auto_alpha = s->cfg.auto_alpha; aa.alpha_fixed = s->cfg.alpha;
-        aa.probe = c->probe_phase;                 // 0 outside probe builds
         return dispatch_H(c->cfg.hidden, [&](auto hc) {
             constexpr int H = decltype(hc)::value;
             if (r4) hipLaunchKernelGGL((sac_actor_tile_kernel<H, 4>), dim3(grid), dim3(4 * H), 0, st, PAx, s->mda, aa);
@@ -724,10 +782,7 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     if (rc) return rc;
     rc = sac_q_launch(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B);
     if (rc) return rc;
-    SacNstepArgs na{};
-    na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
-    na.flags = c->st.flags; na.sc = s->sc; na.Y = s->Y; na.B = B; na.n_step = ns; na.gamma = c->cfg.gamma;
-    na.auto_alpha = s->cfg.auto_alpha; na.alpha_fixed = s->cfg.alpha; na.single = s->ddpg ? 1 : 0;
+    const SacNstepArgs na = sac_nstep_args(c, s, B);
     if (s->plan_nstep_sep) {     // the stand-alone float64 n-step launch; by default the critics' tile launch computes its targets itself
         hipLaunchKernelGGL(sac_nstep_kernel, dim3((B + 255) / 256), dim3(256), 0, st, na);
         HIPCHK(hipGetLastError());
@@ -764,13 +819,9 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     }
     s->t_actor += 1;
     // ---- actor Adam; its extra block does the alpha step + logged stats (reads only what earlier launches wrote)
-    SacFinalArgs fa{};
     float* stats_row = s->d_stats + (size_t)(s->n_updates % SAC_RING) * s->nstats;
-    fa.statp_q = s->stq; fa.statp_pi = s->stpi; fa.sc = s->sc; fa.stats = stats_row;
-    fa.n_tiles_q = s->q_rows4 ? 4 * s->n_tiles : s->n_tiles; fa.n_tiles_pi = s->a_rows4 ? 4 * s->n_tiles : s->n_tiles; fa.B = B; fa.rescale = resc; fa.lam = lam; fa.target_entropy = s->cfg.target_entropy;
-    fa.alpha_lr = s->cfg.alpha_lr; fa.beta1 = c->cfg.beta1; fa.beta2 = c->cfg.beta2; fa.adam_eps = c->cfg.adam_eps;
-    fa.alpha_fixed = s->cfg.alpha; fa.auto_alpha = s->cfg.auto_alpha; fa.use_lagrangian = s->cfg.use_lagrangian;
-    fa.n_q = s->n_q;
+    const SacFinalArgs fa = sac_final_args(c, s, B, resc, lam, s->q_rows4 ? 4 * s->n_tiles : s->n_tiles,
+                                           s->a_rows4 ? 4 * s->n_tiles : s->n_tiles, stats_row);
     // DDPG-Lag: actor_old <- tau * actor + (1 - tau) * actor_old in the same pass (ddpg_lag.py:120-123)
     adam_final_launch<SacFinalArgs, sac_finalize_row>(c, s->mda, s->PA, s->MA, s->VA, c->wg_parts, s->na_dev, s->cfg.actor_lr,
                                                       s->t_actor, nsplit, s->na_dev, s->ddpg ? s->PAT : nullptr, s->cfg.tau, fa);

@@ -445,16 +445,7 @@ static int tr_wgrad_plain(fsrl_ctx* c, TrState* t, int net0, int ny, float* out,
         return 0;
     }
     FbWgradArgs wa{};
-    const size_t H = c->cfg.hidden;
-    for (int y = 0; y < ny; ++y) {
-        const size_t nb = (size_t)y * t->rows_pad;
-        FbWgradNet& wn = wa.nets[y];
-        wn.w2_ya = t->D2 + nb * H; wn.w2_xa = t->A1 + nb * H; wn.w2_yb = nullptr; wn.w2_xb = nullptr;
-        wn.w1_y = t->D1 + nb * H;
-        wn.w3_xa = t->A2 + nb * H; wn.w3_ya = t->DO + nb * FSRL_DOW; wn.w3_xb = nullptr; wn.w3_yb = nullptr;
-        wn.b1_src = t->D1 + nb * H; wn.b2_src = t->D2 + nb * H; wn.do_src = t->DO + nb * FSRL_DOW;
-        wn.net = net0 + y;
-    }
+    wgrad_fill_nets(wa, ny, net0, (size_t)c->cfg.hidden, (size_t)t->rows_pad, t->A1, t->A2, t->D1, t->D2, t->DO);
     wa.obs = t->vobs; wa.rows = t->rows16; wa.N = (int)t->vN;
     int nsplit = 1;
     int rc = tr_ensure_pad(c, t);
@@ -835,10 +826,10 @@ static int tr_critic_enqueue(fsrl_ctx* c, TrState* t, int iters, float l2) {
         }
         t->critic_t += 1;
         const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-        const double bc1 = 1.0 - std::pow(b1, (double)t->critic_t), bc2 = 1.0 - std::pow(b2, (double)t->critic_t);
+        const AdamStep as = adam_step(t->cfg.critic_lr, c->cfg.beta1, c->cfg.beta2, t->critic_t);
         hipLaunchKernelGGL(adam_range_kernel, dim3((end - begin + 255) / 256), dim3(256), 0, c->compute, c->P, c->M,
                            c->V, (const float*)c->wg_parts, begin, end, l2, (float)(1.0 - b1), c->cfg.beta2, (float)(1.0 - b2),
-                           (float)((double)t->cfg.critic_lr / bc1), (float)std::sqrt(bc2), c->cfg.adam_eps, nparts, c->n_dev, c->md,
+                           as.step_size, as.bc2_sqrt, c->cfg.adam_eps, nparts, c->n_dev, c->md,
                            (const float*)nullptr, 0, 0.0f, (float*)nullptr, (float*)nullptr, 0.0f, 0.0f, 1);   // 1: float64 sum of the partials
         HIPCHK(hipGetLastError());
     }
