@@ -7,7 +7,7 @@ kernels fill (3 agents: ~190 updates/s together).  ctypes releases the GIL insid
 the seeds overlap; the Python collector loops take turns.
 
     python examples/train_multi_seed.py --algo ppol --seeds 3 --epoch 2
-    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag, FOCOPS and SAC-Lag
+    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped     # PPO-Lag, FOCOPS, SAC-Lag, DDPG-Lag and CVPO
     python examples/train_multi_seed.py --algo focops --seeds 4 --epoch 2 --grouped
     python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped
     python examples/train_multi_seed.py --algo cvpo --seeds 4 --epoch 2 --grouped
@@ -25,8 +25,8 @@ updates per seed, every launch carrying all seeds (tools/bench_group_sac.py).
 --grouped --algo cvpo: the same loop with CVPO seeds (each seed's pre_update_fn resets its M-step multipliers, ONE grouped update
 through fsrl_amd.policy.CVPOPolicyGroup -> fsrl_cvpo_group_update, each seed's post_update_fn copies actor -> actor_old;
 tools/bench_group_cvpo.py).
---grouped --algo ddpgl: lock-step collection as for sacl, then each seed's OWN updates one after the other (grouped DDPG-Lag
-updates do not exist).
+--grouped --algo ddpgl: the same loop with DDPG-Lag seeds (ONE grouped update through fsrl_amd.policy.DDPGPolicyGroup ->
+fsrl_sac_group_update over deterministic-actor contexts; tools/bench_group_sac.py --algo ddpgl).
     python examples/train_multi_seed.py --algo ddpgl --seeds 4 --epoch 2 --grouped
 """
 import argparse
@@ -49,11 +49,11 @@ GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo")      # what --groupe
 def run_grouped_replay(a):
     """k SAC-Lag (CVPO, DDPG-Lag) seeds, one host thread: the seeds collect in lock step (one collect-group call per vector step) and
     run their pre_update_fn (SAC-Lag / DDPG-Lag: the PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped
-    update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed; DDPG-Lag:
-    each seed's own updates, one seed after the other), then each seed's post_update_fn."""
+    update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed), then each
+    seed's post_update_fn."""
     from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
     from fsrl_amd.engine import EngineCollectGroup
-    from fsrl_amd.policy import CVPOPolicyGroup, SACPolicyGroup
+    from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
@@ -64,7 +64,7 @@ def run_grouped_replay(a):
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
-    group = None if a.algo == "ddpgl" else (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in agents])
+    group = {"sacl": SACPolicyGroup, "ddpgl": DDPGPolicyGroup, "cvpo": CVPOPolicyGroup}[a.algo]([ag.policy for ag in agents])
     cgroup = EngineCollectGroup([ag.policy.engine for ag in agents])
     gcol = GroupCollector(cgroup, cols)
     update_per_step, t0, steps, updates = 0.2, time.time(), 0, 0
@@ -79,12 +79,7 @@ def run_grouped_replay(a):
                 steps += st["n/st"]
                 n.append(round(update_per_step * st["n/st"]))
             budget -= st["n/st"]
-            if group is not None:
-                group.update(bufs, batch_size=256, n_updates=n)
-            else:
-                for ag, buf, n_i in zip(agents, bufs, n):
-                    for _ in range(n_i):
-                        ag.policy.update(256, buf)
+            group.update(bufs, batch_size=256, n_updates=n)
             for ag, st in zip(agents, sts):
                 ag.policy.post_update_fn(stats_train=st)
             updates += sum(n)
@@ -96,8 +91,7 @@ def run_grouped_replay(a):
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
     cgroup.close()
-    if group is not None:
-        group.close()
+    group.close()
     for ag in agents:
         ag.policy.engine.close()
 
@@ -155,8 +149,7 @@ def main():
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / CVPO: lock-step collection and grouped updates from one thread; "
-                    "DDPG-Lag: lock-step collection, then each seed's own updates (there are no grouped DDPG-Lag updates)")
+    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread")
     a = ap.parse_args()
     out, errs = {}, []
     if a.grouped:

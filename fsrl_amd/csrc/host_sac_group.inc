@@ -1,5 +1,7 @@
-// host_sac_group.inc -- grouped SAC-Lagrangian updates: fsrl_sac_group_* (part of fsrl_hip.hip, kernels: kernels_sac_group.hpp).
-// k SAC-Lag contexts of one network shape, each stepped n_i times per call in lock step: every launch of an update carries all
+// host_sac_group.inc -- grouped SAC-Lagrangian and DDPG-Lagrangian updates: fsrl_sac_group_* (part of fsrl_hip.hip, kernels:
+// kernels_sac_group.hpp).
+// k SAC-Lag contexts -- or k DDPG-Lag contexts (fsrl_sac_init with deterministic = 1); the group's kind is member 0's and the two
+// do not mix -- of one network shape, each stepped n_i times per call in lock step: every launch of an update carries all
 // members that still have updates to run (nine launches per update, whatever k is).  Members keep their own streams, stores,
 // parameters, targets, Adam state, alpha, Philox key and statistics ring; the group has a stream of its own that waits on each
 // member's stream before the call and that each member's streams wait on after it.  Between grouped calls a member is an ordinary
@@ -7,7 +9,10 @@
 // Bit-identity with fsrl_sac_update: the member's arithmetic is the single path's body with the single path's split-K plan; the
 // tile height of a launch is the single-context rule applied to the whole group's launch (4-row tiles while the group still fits
 // one round of workgroups), so a group of one is bit-identical to its solo run, and larger groups are wherever the tile height
-// does not change a row's result (tests/test_gpu_sac_group.py).
+// does not change a row's result (tests/test_gpu_sac_group.py, tests/test_gpu_ddpg_group.py).
+// A DDPG-Lag group is the same nine launches with the DDPG context's arguments: n_q = 2 single critics (the Q grids, the small
+// weight-gradient grid, the split-K plan and the tile-height rule all take the group's n_q), the deterministic actor, the target
+// actor in the first half of the forward launch, and its Polyak update in the actor's Adam pass, where SAC-Lag steps alpha.
 // ====================================================================================== grouped SAC-Lagrangian
 // ---- what the grouped SAC and CVPO updates share: the members, the group's stream and the events that order it against the
 //      members' streams.  Each group type embeds one as `core`.
@@ -97,11 +102,12 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
         const SacState* s = reinterpret_cast<const SacState*>(c->sac);
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped SAC updates take SAC-Lagrangian contexts (fsrl_sac_init)", i);
         CHECK_ARG(!s->cvpo, "member %d runs CVPO: grouped SAC updates take SAC-Lagrangian contexts only", i);
-        CHECK_ARG(!s->ddpg, "member %d is a DDPG-Lagrangian context (deterministic actor): grouped SAC updates need the stochastic actor", i);
         CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: grouped SAC updates run the fused kernels (two hidden layers)", i);
         CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
         CHECK_ARG(!c->sac_group, "member %d is already in a SAC group", i);
         const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
+        CHECK_ARG(s->ddpg == s0->ddpg, "member %d: a group is all SAC-Lagrangian or all DDPG-Lagrangian (deterministic actor) contexts, "
+                  "and member 0 is %s", i, s0->ddpg ? "DDPG-Lagrangian" : "SAC-Lagrangian");
         CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden,
                   "member %d: members must have one network shape (obs_dim, act_dim, hidden)", i);
         CHECK_ARG(s->cfg.n_step == s0->cfg.n_step && (s->cfg.auto_alpha != 0) == (s0->cfg.auto_alpha != 0) &&
@@ -157,12 +163,14 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
     const float resc = (float)rescaling;
     t = SacGroupMember{};
     t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
-    // ---- actors (deterministic = 0, probe = 0: members are never DDPG contexts, and a probe build's phases are the solo path's);
-    //      the forward launch carries the current actor's batch and the sample + gather (sa.counter per step)
-    t.af = sac_actor_args(c, s, B, SAC_A_FWD, s->OBSN, s->eps_t, s->XN, s->LPN, resc, lam, 0, 0);
+    t.PAT = s->ddpg ? s->PAT : nullptr;        // DDPG-Lag: the forward launch's first half runs it, the actor's Adam pass moves it
+    // ---- actors (probe = 0: a probe build's phases are the solo path's); the forward launch carries the current actor's batch
+    //      and the sample + gather (sa.counter per step)
+    const int det = s->ddpg ? 1 : 0;
+    t.af = sac_actor_args(c, s, B, SAC_A_FWD, s->OBSN, s->eps_t, s->XN, s->LPN, resc, lam, det, 0);
     t.af.P2 = s->PA; t.af.obs2 = s->OBS; t.af.eps2 = s->eps_p; t.af.X2 = s->XP; t.af.lp2 = s->LP; t.af.tiles_half = f_r4 ? 4 * nt : nt;
     t.af.sg_on = 1; t.af.sa = sac_sample_args(c, s, B, ns, stored, 0); t.af.ga = sac_gather_args(c, s, B, ns);
-    t.ab = sac_actor_args(c, s, B, SAC_A_BWD, s->OBS, s->eps_p, s->XP, s->LP, resc, lam, 0, 0);
+    t.ab = sac_actor_args(c, s, B, SAC_A_BWD, s->OBS, s->eps_p, s->XP, s->LP, resc, lam, det, 0);
     // ---- Q-network tile launches
     const SacNstepArgs na = sac_nstep_args(c, s, B);
     t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, nt, nullptr);
@@ -181,7 +189,7 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
         t.wa = group_wgrad_small(s, rp, s->OBS, const_cast<float*>(t.GA));
         *nsplit_q = *nsplit_a = 1;
     } else {
-        int rc = group_wgrad_split(c, s, t.fq, s->mdq, 4, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
+        int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
         if (rc) return rc;
         rc = group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
         if (rc) return rc;
@@ -229,7 +237,7 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
         fsrl_ctx* c = gc.m[i];
         const SacState* s = sac_of(c);
         CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
-        CHECK_ARG(s && !s->cvpo && !s->ddpg && !s->layered && s->cfg.n_step == s0->cfg.n_step, "member %d is no longer a SAC-Lagrangian context of the group's shape", i);
+        CHECK_ARG(s && !s->cvpo && s->ddpg == s0->ddpg && !s->layered && s->cfg.n_step == s0->cfg.n_step, "member %d is no longer a context of the group's kind and shape", i);
         CHECK_ARG(s->wgrad_splitk == s0->wgrad_splitk, "members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)");
         // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
         // (fb_wgrad2_kernel); the tiled kernel fb_wgrad3_kernel needs re-laid observations the replay agents never hand over
@@ -242,7 +250,7 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     if (n_max == 0) return 0;
     HIPCHK(hipSetDevice(gc.device));
     HIPCHK(hipStreamSynchronize(gc.stream));           // the pinned tables of the previous call have been read
-    const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = 4;
+    const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = s0->n_q;     // 4 (SAC-Lag) or 2 (DDPG-Lag)
     // tile heights: the single-context rule applied to the group's whole launch (4-row tiles while it fits one round)
     const bool t16 = c0->probe_tile16;
     const bool q_r4 = (size_t)4 * nt * n_q * k <= (size_t)c0->n_cus && !t16;
@@ -305,7 +313,7 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
             else hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 2>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
             if (a_r4) hipLaunchKernelGGL((sac_actor_group_kernel<HH, 4, SAC_A_BWD>), dim3(at, k), dim3(4 * HH), 0, gs, mda, tab, st);
             else hipLaunchKernelGGL((sac_actor_group_kernel<HH, 16, SAC_A_BWD>), dim3(at, k), dim3(4 * HH), 0, gs, mda, tab, st);
-            // 8. the actor's weight gradients; 9. its Adam, alpha step and logged row
+            // 8. the actor's weight gradients; 9. its Adam, alpha step (DDPG-Lag: the target actor's Polyak update) and logged row
             if (small_wgrad) hipLaunchKernelGGL((sac_wgrad_group_kernel<HH, 1>), dim3(wg_grid(HH, 1), k), dim3(1024), 0, gs, mda, tab, st, rp);
             else hipLaunchKernelGGL((sac_wgrad_split_group_kernel<HH, 1>), dim3(ga, k), dim3(1024), 0, gs, mda, tab, st);
             hipLaunchKernelGGL(sac_adam_final_group_kernel, dim3((na_dev + 255) / 256 + 1, k), dim3(256), 0, gs, mda, tab, st, na_dev, nsa, na_dev);

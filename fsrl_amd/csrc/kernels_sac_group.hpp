@@ -1,5 +1,5 @@
-// kernels_sac_group.hpp -- grouped SAC-Lagrangian updates (part of fsrl_hip.hip, host side: host_sac_group.inc).
-// k SAC-Lag contexts of one network shape step in lock step: every launch of the update carries all active members, the
+// kernels_sac_group.hpp -- grouped SAC-Lagrangian and DDPG-Lagrangian updates (part of fsrl_hip.hip, host side: host_sac_group.inc).
+// k SAC-Lag contexts (or k DDPG-Lag contexts) of one network shape step in lock step: every launch of the update carries all active members, the
 // member being one more grid coordinate.  Each kernel reads its member's arguments from a device table (SacGroupMember,
 // rewritten once per grouped call) and the per-(update, member) values from a step table (SacGroupStep: the sample's arguments,
 // Adam step sizes from t_critic / t_actor, stats-ring row, active flag), and then runs the single-context body inlined:
@@ -7,8 +7,12 @@
 //   actors' forward (sample + gather folded in)  -> target Q -> critics' Q_TRAIN (n-step targets in-kernel)
 //   -> critics' weight gradients -> critics' Adam + Polyak -> Q_DIN -> actor backward -> actor weight gradients
 //   -> actor Adam + alpha step + logged row.
+// A DDPG-Lag member differs where fsrl_sac_update does: two critics (the y extent of the Q grids), the deterministic actor
+// (SacActorArgs::deterministic), the target actor PAT in the first half of the forward launch, and PAT's Polyak update in the
+// actor's Adam pass instead of an alpha step.
 struct SacGroupMember {
     float *PA, *MA, *VA, *PQ, *PQT, *MQ, *VQ;
+    float* PAT;                    // DDPG-Lag: the target actor (actor_old); null for SAC-Lag members
     const float *GA, *GQ;          // split-K partial gradients of the actor / the critics (the member's own buffers)
     FbArgs qf, qt, qd;             // target-Q forward (P = PQT), critics' training launch, Q input gradients (P = PQ)
     SacActorArgs af, ab;           // both actors' forward (its sample: SacGroupStep::sa), actor backward
@@ -25,7 +29,8 @@ struct SacGroupStep {              // per (update index, member)
     float c_step, c_bc2, a_step, a_bc2;    // Adam lr / bias_correction1 and sqrt(bias_correction2) at t_critic / t_actor
 };
 
-// FWD: both actors' forward, the member's sample drawn and gathered in the same launch; BWD: the actor's backward.
+// FWD: both actors' forward, the member's sample drawn and gathered in the same launch (first half: a' at s_{t+n}, from the
+// target actor for a DDPG-Lag member; second half: af.P2 = PA at s_t); BWD: the actor's backward.
 // grid = (tiles of the launch, k)
 template <int H, int R, int MODE>
 __global__ __launch_bounds__(4 * H) void sac_actor_group_kernel(const ModelDesc md, const SacGroupMember* __restrict__ tab,
@@ -34,7 +39,8 @@ __global__ __launch_bounds__(4 * H) void sac_actor_group_kernel(const ModelDesc 
     const SacGroupStep& st = steps[blockIdx.y];
     if (!st.active) return;
     const SacGroupMember& g = tab[blockIdx.y];
-    sac_actor_tile_body<H, R>(sm, g.PA, md, MODE == SAC_A_FWD ? g.af : g.ab, (int)blockIdx.x, st.sa);
+    const float* P = (MODE == SAC_A_FWD && g.PAT) ? g.PAT : g.PA;
+    sac_actor_tile_body<H, R>(sm, P, md, MODE == SAC_A_FWD ? g.af : g.ab, (int)blockIdx.x, st.sa);
 }
 
 // the Q-network tile launches: WHICH 0 = target Q forward, 1 = critics' Q_TRAIN, 2 = Q_DIN.  grid = (tiles, n_q, k)
@@ -94,6 +100,7 @@ __global__ __launch_bounds__(256) void sac_adam_group_kernel(const ModelDesc md,
 }
 
 // the actor's Adam; the last block of every member writes its logged row and steps alpha (adam_final_kernel + sac_finalize_row).
+// DDPG-Lag: actor_old <- tau * actor + (1 - tau) * actor_old rides in the same pass, as in fsrl_sac_update.
 // grid = (n / 256 + 1, k)
 __global__ __launch_bounds__(256) void sac_adam_final_group_kernel(const ModelDesc md, const SacGroupMember* __restrict__ tab,
                                                                   const SacGroupStep* __restrict__ steps, const int n,
@@ -115,5 +122,5 @@ __global__ __launch_bounds__(256) void sac_adam_final_group_kernel(const ModelDe
     float gs = g.GA[i];
     for (int z = 1; z < nparts; ++z) gs += g.GA[(size_t)z * stride + i];
     adam_element(g.PA, g.MA, g.VA, i, p, gs, 1.0f, 0.0f, g.one_minus_b1, g.beta2, g.one_minus_b2, st.a_step, st.a_bc2, g.adam_eps,
-                 md, nullptr, g.tau, g.one_minus_tau);
+                 md, g.PAT, g.tau, g.one_minus_tau);
 }

@@ -857,8 +857,9 @@ class EngineGroup(_LockStepCollect):
 
 
 class EngineSacGroup:
-    """k SAC-Lagrangian engines (sac_init, stochastic actor) of one shape on one GPU, updated in lock step
-    (fsrl_sac_group_*): every launch of an update carries all members that still have updates to run.  Members keep their
+    """k SAC-Lagrangian engines (sac_init, stochastic actor), or k DDPG-Lagrangian engines (sac_init(deterministic=True)),
+    of one shape on one GPU, updated in lock step (fsrl_sac_group_*): every launch of an update carries all members that
+    still have updates to run.  The group's kind is its first member's; the two kinds do not mix.  Members keep their
     own streams, stores, parameters, Philox keys and statistics rings, and stay ordinary engines between updates (push,
     collect_step with the resident actor, sac_get_params, sac_drain ...)."""
 

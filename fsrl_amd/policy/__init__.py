@@ -13,5 +13,6 @@ install(__name__, globals(), {
     "CVPO": "cvpo",
     "PolicyGroup": "grouped",
     "SACPolicyGroup": "grouped_sac",
+    "DDPGPolicyGroup": "grouped_ddpg",
     "CVPOPolicyGroup": "grouped_cvpo",
 })

@@ -7,20 +7,27 @@ rows, same lr_scheduler steps.
     group = SACPolicyGroup([agent.policy for agent in agents])
     ... every agent collects into ITS buffer (its own resident device actor), steps ITS PID multiplier (pre_update_fn) ...
     group.update(buffers, batch_size=256, n_updates=[n_0, n_1, ...])
-    ... post_update_fn per agent (drains the rows into its logger) ..."""
+    ... post_update_fn per agent (drains the rows into its logger) ...
+
+`ReplayPolicyGroup` holds the loop; `SACPolicyGroup` here and `DDPGPolicyGroup` (grouped_ddpg.py) name their policy class."""
 from typing import Sequence, Union
 
 from fsrl_amd.engine import EngineSacGroup
 from fsrl_amd.policy.sac_lag import SACLagrangian
 
-_RING_DRAIN = 2048          # SACLagrangian.learn drains its statistics ring after this many pending updates
+_RING_DRAIN = 2048          # SACLagrangian.learn / DDPGLagrangian.learn drain their statistics ring after this many pending updates
 
 
-class SACPolicyGroup:
-    def __init__(self, policies: Sequence[SACLagrangian], engine_group=None):
+class ReplayPolicyGroup:
+    """k policies of `policy_cls` over an EngineSacGroup (fsrl_sac_group_*); subclasses set `policy_cls` and `algo_name`"""
+    policy_cls: type = None
+    algo_name: str = ""
+
+    def __init__(self, policies: Sequence, engine_group=None):
         self.policies = list(policies)
         assert self.policies, "a group needs at least one policy"
-        assert all(isinstance(p, SACLagrangian) for p in self.policies), "grouped SAC updates: SACLagrangian policies"
+        assert all(isinstance(p, self.policy_cls) for p in self.policies), \
+            "grouped %s updates: %s policies" % (self.algo_name, self.policy_cls.__name__)
         # reference_rng=True draws the sample and the noise from the host's numpy / torch streams, one update at a time: a grouped
         # update has the device's Philox streams only
         assert not any(getattr(p, "_reference_rng", False) for p in self.policies), "reference_rng policies cannot be grouped"
@@ -41,7 +48,7 @@ class SACPolicyGroup:
         for p in pols:
             p.updating = True
         try:
-            # a fresh policy's first update keys its Philox stream (SACLagrangian.learn: seed + 1): that one runs on its own
+            # a fresh policy's first update keys its Philox stream (learn: seed + 1): that one runs on its own
             for i, (p, b) in enumerate(zip(pols, buffers)):
                 if n[i] > 0 and p.gradient_steps == 0:
                     p.update(B, b)
@@ -80,3 +87,8 @@ class SACPolicyGroup:
         for p in pols:
             p.updating = False
         return [{} for _ in pols]
+
+
+class SACPolicyGroup(ReplayPolicyGroup):
+    policy_cls = SACLagrangian
+    algo_name = "SAC"

@@ -543,13 +543,15 @@ int fsrl_sac_last_sample(fsrl_ctx* ctx, int64_t* indices, float* eps_target, flo
 /* the actor for the collector: mu and sigma = exp(clamp(log sigma)) of the tanh-Gaussian policy   */
 int fsrl_sac_actor_forward(fsrl_ctx* ctx, const float* obs, int32_t k, float* mu_out, float* sigma_out);
 
-/* ---- Grouped SAC-Lagrangian updates: k SAC-Lag contexts (fsrl_sac_init, stochastic actor) of one shape on one device, each
- *      stepped n_updates[i] times per call in lock step; every launch of an update (nine, whatever k is) carries all members that
- *      still have updates to run.  Members keep their own streams, stores, parameters, targets, Adam state, alpha, Philox key and
- *      statistics ring, and stay ordinary contexts between calls (a call ends a member's resident actor; its next collect
+/* ---- Grouped SAC-Lagrangian and DDPG-Lagrangian updates: k SAC-Lag contexts (fsrl_sac_init, stochastic actor), or k DDPG-Lag
+ *      contexts (fsrl_sac_init with deterministic = 1; act_dim up to 16), of one shape on one device, each stepped n_updates[i]
+ *      times per call in lock step; every launch of an update (nine, whatever k is) carries all members that still have updates
+ *      to run.  The group's kind is member 0's; the two kinds do not mix.  Members keep their own streams, stores, parameters,
+ *      targets (DDPG-Lag: the target actor too, moved by the member's own tau in the actor's Adam pass), Adam state, alpha, Philox
+ *      key and statistics ring, and stay ordinary contexts between calls (a call ends a member's resident actor; its next collect
  *      relaunches it).  Shapes (obs / act / hidden), n_step, auto_alpha and use_lagrangian must agree; learning rates, tau, seeds
- *      and store contents may differ.  Rejected with FSRL_EINVAL: DDPG-Lag, CVPO and layered contexts, a member listed twice or
- *      already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works. */
+ *      and store contents may differ.  Rejected with FSRL_EINVAL: a mixture of SAC-Lag and DDPG-Lag members (either order), CVPO
+ *      and layered contexts, a member listed twice or already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works. */
 typedef struct fsrl_sac_group fsrl_sac_group;
 int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group** out);   /* 1 <= k <= 16, members not owned */
 int fsrl_sac_group_destroy(fsrl_sac_group* g);

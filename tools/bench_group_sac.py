@@ -1,11 +1,12 @@
-"""Aggregate SAC-Lagrangian updates/s of k seeds on one GPU, three ways: grouped (fsrl_sac_group_update: every launch carries all
+"""Aggregate SAC-Lagrangian (or, with --algo ddpgl, DDPG-Lagrangian) updates/s of k seeds on one GPU, three ways: grouped (fsrl_sac_group_update: every launch carries all
 members), one context alone, and k contexts with one host thread each (train_multi_seed.py's threaded mode).  One JSON line per
 (shape, k, mode).
 
-    python tools/bench_group_sac.py [--shapes default,configs3] [--ks 1,2,4,8] [--updates 200] [--modes grouped,solo,threaded]
+    python tools/bench_group_sac.py [--algo sacl|ddpgl] [--shapes default,configs3] [--ks 1,2,4,8] [--updates 200] [--modes grouped,solo,threaded]
 
 Shapes: default = the reference's sacl_cfg.py (obs 8, act 2, 128 x 128, batch 256, n_step 2); configs3 = BASELINE configs[3]
-(obs 33, act 8, 256 x 256, batch 1024, 1 M-row stores)."""
+(obs 33, act 8, 256 x 256, batch 1024, 1 M-row stores).  --algo ddpgl: the same two shapes with sac_init(deterministic=True)
+engines (the default shape is also the reference's ddpgl_cfg.py)."""
 import argparse
 import json
 import os
@@ -23,14 +24,17 @@ SHAPES = {
 }
 
 
-def _engine(sh, seed):
+def _engine(sh, seed, algo="sacl"):
     import torch
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
     E = sh["env_num"]
     eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=sh["obs"], act_dim=sh["act"], hidden_sizes=(sh["H"], sh["H"]),
                               n_critics=2, env_num=E, buffer_size=sh["rows"], gamma=0.99, target_kl=None))
-    eng.sac_init(n_step=sh["n_step"])
+    if algo == "ddpgl":
+        eng.sac_init(deterministic=True, n_step=sh["n_step"])
+    else:
+        eng.sac_init(n_step=sh["n_step"])
     g = torch.Generator().manual_seed(seed)
     eng.sac_set_params((0.1 * torch.randn(eng.n_sac_actor, generator=g)).numpy(),
                        (0.1 * torch.randn(eng.n_sac_critics, generator=g)).numpy(), 0.0)
@@ -53,11 +57,11 @@ def _sync(engs):
         e.sac_get_params(0)
 
 
-def run(shape, k, mode, updates):
+def run(shape, k, mode, updates, algo="sacl"):
     from fsrl_amd.engine import EngineSacGroup
     sh = SHAPES[shape]
     B = sh["B"]
-    engs = [_engine(sh, 10 + i) for i in range(1 if mode == "solo" else k)]
+    engs = [_engine(sh, 10 + i, algo) for i in range(1 if mode == "solo" else k)]
     per_call = 50
     if mode == "grouped":
         g = EngineSacGroup(engs)
@@ -98,12 +102,13 @@ def run(shape, k, mode, updates):
         total = updates * len(engs)
     for e in engs:
         e.close()
-    return dict(shape=shape, k=k, mode=mode, batch=B, hidden=sh["H"], updates=total, seconds=round(dt, 4),
+    return dict(algo=algo, shape=shape, k=k, mode=mode, batch=B, hidden=sh["H"], updates=total, seconds=round(dt, 4),
                 updates_per_s=round(total / dt, 1), us_per_member_update=round(dt / total * 1e6, 2))
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=("sacl", "ddpgl"), default="sacl")
     ap.add_argument("--shapes", default="default,configs3")
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--modes", default="grouped,solo,threaded")
@@ -117,7 +122,7 @@ def main():
                 for mode in a.modes.split(","):
                     if mode == "solo" and k != ks[0]:
                         continue                            # one context alone: measured once per shape
-                    print(json.dumps(run(shape, k, mode, a.updates)), flush=True)
+                    print(json.dumps(run(shape, k, mode, a.updates, a.algo)), flush=True)
 
 
 if __name__ == "__main__":
