@@ -28,6 +28,10 @@ tools/bench_group_cvpo.py).
 --grouped --algo ddpgl: the same loop with DDPG-Lag seeds (ONE grouped update through fsrl_amd.policy.DDPGPolicyGroup ->
 fsrl_sac_group_update over deterministic-actor contexts; tools/bench_group_sac.py --algo ddpgl).
     python examples/train_multi_seed.py --algo ddpgl --seeds 4 --epoch 2 --grouped
+--hidden-sizes 64x48x32 (every mode): the networks' hidden layers.  Anything but two layers of at most 256 units makes layered
+contexts; --grouped --algo ppol takes them as well: a layered minibatch step is 2 L + 5 launches whatever the number of seeds
+and the actor request of a vector step L + 2 (tools/bench_group_layered.py).
+    python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --hidden-sizes 256x256x256
 """
 import argparse
 import os
@@ -58,7 +62,7 @@ def run_grouped_replay(a):
     for seed in range(a.seeds):
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
+        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
         agent.policy.train()
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
@@ -108,7 +112,7 @@ def run_grouped(a):
     for seed in range(a.seeds):
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
+        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
         agent.policy.train()
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
@@ -150,7 +154,12 @@ def main():
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread")
+    ap.add_argument("--hidden-sizes", default="128x128", type=lambda t: tuple(int(w) for w in t.lower().split("x")),
+                    help="hidden layers of every network, e.g. 64x48x32 (anything but two layers of at most 256 units runs the "
+                         "layered kernels; --grouped takes such PPO-Lag seeds too)")
     a = ap.parse_args()
+    if isinstance(a.hidden_sizes, str):
+        a.hidden_sizes = tuple(int(w) for w in a.hidden_sizes.lower().split("x"))
     out, errs = {}, []
     if a.grouped:
         return run_grouped(a)
@@ -159,7 +168,7 @@ def main():
         try:
             env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
             logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-            agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=(128, 128),
+            agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                    training_num=a.envs)
             kw = dict(epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, device_actor=True, verbose=False,
                       save_ckpt=False, show_progress=False)

@@ -1443,6 +1443,8 @@ extern "C" int fsrl_nstep_return(fsrl_ctx* c, const double* metric, const uint8_
 #include "host_layered.inc"
 
 #include "host_actor_ring.inc"
+#include "kernels_layered_group.hpp"
+#include "host_layered_group.inc"
 #include "host_group.inc"
 #include "host_group_collect.inc"
 

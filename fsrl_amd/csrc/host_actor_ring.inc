@@ -213,9 +213,13 @@ struct GaStepArgs {
 // The owners differ in three callables: ensure() makes the ring before a request (0 or an error); finish(i, c, ka, l) turns member
 // i's ka ring rows into c->act_mu / c->act_sg (sized [ka][act_dim] already); drain() leaves no evaluation in flight when a push
 // fails off the resident path.
-template <class Ensure, class Finish, class Drain>
-static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, const GaStepArgs& a, Ensure&& ensure, Finish&& finish,
-                           Drain&& drain) {
+// ga_collect_step_via is the step itself with the shared request as three more callables, so that an owner without a resident
+// kernel (a group of layered contexts, host_layered_group.inc: one launch sequence per step for all members) runs the same
+// step: fits(i) -- member i's rows can go through the shared request; post() -- place and start it (0 or an error); wait() --
+// its answer is in host memory (0 or an error); abandon() -- a push failed behind a posted request: leave nothing in flight.
+template <class Fits, class Post, class Wait, class Abandon, class Finish, class Drain>
+static int ga_collect_step_via(GaRing& ga, fsrl_ctx* const* m, int n, int device, const GaStepArgs& a, Fits&& fits, Post&& post,
+                               Wait&& wait, Abandon&& abandon, Finish&& finish, Drain&& drain) {
     const int32_t *k = a.k, *k_act = a.k_act;
     const int Do = m[0]->cfg.obs_dim, Da = m[0]->cfg.act_dim;
     int64_t rows = 0, rows_act = 0;
@@ -223,7 +227,7 @@ static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, co
     for (int i = 0; i < n; ++i) {
         CHECK_ARG(k[i] >= 0 && k_act[i] >= 0, "negative row count (member %d)", i);
         rows += k[i]; rows_act += k_act[i];
-        resident = resident && !m[i]->no_spin && k_act[i] <= gactor_member_rows(m[i]);
+        resident = resident && !m[i]->no_spin && fits(i);
     }
     CHECK_ARG(rows_act == 0 || (a.obs_act && a.act_out), "obs_act / act_out missing");
     CHECK_ARG(rows == 0 || a.env_ids, "env_ids missing");
@@ -234,8 +238,7 @@ static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, co
     int rc = 0;
     if (rows_act > 0) {
         if (resident) {
-            rc = ensure();
-            if (!rc) rc = gactor_post(ga, k_act, a.obs_act);
+            rc = post();
             if (rc) return rc;
         } else {
             ga_release(ga);
@@ -259,7 +262,7 @@ static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, co
                                  a.ep_rew_out ? a.ep_rew_out + o : nullptr, a.ep_len_out ? a.ep_len_out + o : nullptr,
                                  a.ep_idx_out ? a.ep_idx_out + o : nullptr);
             if (rc) {                           // leave no evaluation in flight behind the error
-                if (rows_act > 0) { if (resident) (void)gactor_wait(ga); else drain(); }
+                if (rows_act > 0) { if (resident) abandon(); else drain(); }
                 return rc;
             }
         }
@@ -268,10 +271,10 @@ static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, co
     if (rows_act == 0) return 0;
     // 3. wait; 4. per member in order: mean / std from its ring rows, its noise from its own stream, then map_action
     if (resident) {
-        rc = gactor_wait(ga);
+        rc = wait();
         if (rc) return rc;
     }
-    const GaLayout l = resident ? ga_layout(ga) : GaLayout{};
+    const GaLayout l = (resident && ga.h) ? ga_layout(ga) : GaLayout{};
     off = 0;
     for (int i = 0; i < n; ++i) {
         const int ka = k_act[i];
@@ -294,4 +297,12 @@ static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, co
         off += (size_t)ka;
     }
     return 0;
+}
+template <class Ensure, class Finish, class Drain>
+static int ga_collect_step(GaRing& ga, fsrl_ctx* const* m, int n, int device, const GaStepArgs& a, Ensure&& ensure, Finish&& finish,
+                           Drain&& drain) {
+    return ga_collect_step_via(
+        ga, m, n, device, a, [&](int i) { return a.k_act[i] <= gactor_member_rows(m[i]); },
+        [&]() { const int rc = ensure(); return rc ? rc : gactor_post(ga, a.k_act, a.obs_act); }, [&]() { return gactor_wait(ga); },
+        [&]() { (void)gactor_wait(ga); }, finish, drain);
 }

@@ -5,6 +5,9 @@
 // from the number of active members and the largest member, and above 512 rows it keeps the in-kernel reduction where the
 // single path goes through the split-K kernels.  Otherwise: the golden tests' tolerances (tests/test_gpu_group.py).
 // A group of FOCOPS contexts runs the same entry points through host_focops_group.inc (one algorithm per group).
+// A group of LAYERED PPO-Lagrangian contexts (any other `hidden_sizes`, all members of one shape) runs the layered minibatch
+// step with every member in each of its 2 L + 5 launches (host_layered_group.inc); there a member's update IS its own
+// fsrl_ppo_update bit for bit, whatever the group.
 // ====================================================================================== groups
 #define FSRL_MAX_GROUP 16
 
@@ -22,6 +25,7 @@ struct fsrl_group {
     DevTable<FocGroupStep> fsteps;
     // lock-step collection (host_group_collect.inc): ONE resident actor kernel for every member, rung through ONE doorbell
     GaRing ga;                                  // ring, protocol state and counters (host_actor_ring.inc); its stream is `stream`
+    LayGroup lay;                               // a group of layered contexts (host_layered_group.inc): job tables, the shared actor request
 };
 
 extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
@@ -35,11 +39,14 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_PPO_LAG || c->cfg.algo == FSRL_ALGO_FOCOPS,
                   "member %d: grouped updates are PPO-Lagrangian or FOCOPS contexts", i);
         CHECK_ARG(c->cfg.algo == c0->cfg.algo, "member %d: a group has one algorithm (all PPO-Lagrangian or all FOCOPS members)", i);
-        CHECK_ARG(!c->lay, "member %d is a layered context: grouped updates run the fused kernels (two hidden layers of at most 256 units)", i);
+        // layered members: PPO-Lagrangian groups only, all members layered and of one shape (checked below)
+        CHECK_ARG(!c->lay || c->cfg.algo == FSRL_ALGO_PPO_LAG,
+                  "member %d is a layered context: grouped FOCOPS runs the fused kernels (two hidden layers of at most 256 units)", i);
         CHECK_ARG(c->device == c0->device, "members live on one device");
         CHECK_ARG(!c->in_update && !c->group, "member %d is inside an update or already grouped", i);
         const fsrl_config &a = c->cfg, &b = c0->cfg;
-        CHECK_ARG(a.obs_dim == b.obs_dim && a.act_dim == b.act_dim && a.hidden == b.hidden && a.n_critics == b.n_critics,
+        CHECK_ARG(a.obs_dim == b.obs_dim && a.act_dim == b.act_dim && a.n_critics == b.n_critics && (c->lay != nullptr) == (c0->lay != nullptr) &&
+                  (c->lay ? lay_same_shape(a, b) : a.hidden == b.hidden),
                   "members must have one network shape");
         CHECK_ARG(a.eps_clip == b.eps_clip && a.dual_clip == b.dual_clip && a.vf_coef == b.vf_coef &&
                   a.max_grad_norm == b.max_grad_norm && a.target_kl == b.target_kl && a.norm_adv == b.norm_adv &&
@@ -88,6 +95,7 @@ static void group_detach(fsrl_ctx* c) {
     if (!g) return;
     group_actor_release(g);
     (void)hipStreamSynchronize(g->stream);
+    lay_group_free(g->lay);                     // job tables and collect buffers of a layered group: they name this member's memory
     for (size_t i = 0; i < g->m.size(); ++i) {
         fsrl_ctx* m = g->m[i];
         if (!m) continue;
@@ -110,10 +118,12 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
     if (g->ga.h) (void)hipHostFree(g->ga.h);
     table_free(g->ftab); table_free(g->fsteps);
+    lay_group_free(g->lay);
     delete g;
     return 0;
 }
 
+// (a group of layered contexts accepts the call and ignores it: the layered step has no tile plan)
 // A/B and test switch: how many of a (member, network)'s leading tiles are 32 rows tall in the forward / backward launch of the minibatch
 // step.  -1: automatic (just enough for one round of workgroups once the 16-row tiles exceed the CU count), 0: none (the plan up to r6
 // early), n > 0: min(n, tiles / 2).  Every plan gives the same bits.
@@ -143,6 +153,7 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
     HIPCHK(hipSetDevice(c0->device));
     hipStream_t s = g->stream;
     const int C = c0->cfg.n_critics, H = c0->cfg.hidden, nn = c0->md.n_nets, Do = c0->cfg.obs_dim;
+    const bool layered = c0->lay != nullptr;
     auto abort_all = [&](int rc) { for (fsrl_ctx* c : g->m) c->in_update = false; return rc; };
     // ---- begin: sample(0) + process_fn of every member, back to back on the shared stream
     std::vector<int64_t> n((size_t)k, 0);
@@ -152,10 +163,11 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
         if (stopped_pass_out) stopped_pass_out[i] = -1;
     }
     // ---- member table
-    const int nparts = wg_grid(H, nn);
+    const int nparts = layered ? 0 : wg_grid(H, nn);
     for (int i = 0; i < k; ++i) {
         fsrl_ctx* c = g->m[i];
         GroupAgent& a = g->tab.h[i];
+        if (layered) { lay_group_agent(c, a); continue; }
         memset(&a, 0, sizeof(a));
         a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G;
         a.bp.obs_p = c->obs_p; a.bp.rd_p = c->rd_p; a.bp.A1 = c->A1; a.bp.A2 = c->A2; a.bp.D1 = c->D1; a.bp.D2 = c->D2;
@@ -180,6 +192,11 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
     const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;
     int rc = table_ensure(g->steps, n_steps, 2 * n_steps, g->stream);
     if (rc) return abort_all(rc);
+    if (layered) {                              // job tables of this update: the members' working sets are in place now
+        rc = lay_group_tables(g->lay, g->m.data(), k, active.data(), s);
+        if (rc) return abort_all(rc);
+        base.fuse_adam = 0;                     // the layered step keeps the separate Adam launch (lay_ppo_steps)
+    }
     for (int pass = 0; pass < repeat; ++pass) {
         bool any = false;
         for (int i = 0; i < k; ++i) any = any || active[(size_t)i];
@@ -228,6 +245,11 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
             int mbs = 0;                                         // the largest minibatch any member has at this step
             for (int i = 0; i < k; ++i) mbs = std::max(mbs, g->steps.h[mb * k + i].active ? g->steps.h[mb * k + i].mb_size : 0);
             if (mbs == 0) continue;                              // no active member has a minibatch at this index: nothing to launch
+            if (layered) {                                       // 2 L + 5 launches for all members (host_layered_group.inc)
+                rc = lay_group_step(g->lay, g->m.data(), k, s, g->tab.d, st, g->steps.h + mb * k, base);
+                if (rc) return abort_all(rc);
+                continue;
+            }
             const int tiles = (mbs + 15) / 16;
             // 4-row tiles only while the whole group still fits the chip in one round (a lone member: the single-agent rule)
             const bool rows4 = (size_t)tiles * 4 * nn * n_act <= (size_t)c0->n_cus && !c0->probe_tile16;

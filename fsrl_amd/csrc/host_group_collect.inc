@@ -2,6 +2,9 @@
 // all of them (part of fsrl_hip.hip, after host_group.inc).  The request goes to actor_group_resident_kernel (kernels_mlp.hpp): the
 // resident actor of DESIGN 3.4 with a workgroup per (member, 16-row tile), on the group's stream.  Protocol as pactor_* (post / ring /
 // wait / release, generation and sequence numbers), with one doorbell for the group and a per-member row count k_m next to it.
+// A group of LAYERED contexts has no resident kernel: its request is one launch sequence for all members (host_layered_group.inc);
+// fsrl_group_actor_resident_stats then reports {shared launch sequences, requests served by them, 0}, fsrl_group_actor_release
+// has nothing to end.
 // The kernel is told to end (EXIT) before anything else is enqueued on the group's stream: fsrl_group_ppo_update, fsrl_group_destroy,
 // group_detach and every member entry point that goes through pactor_release (ENTER_DEV, a member's own actor calls).
 
@@ -42,6 +45,25 @@ extern "C" int fsrl_group_collect_step(fsrl_group* g, const int32_t* k, const in
     const GaStepArgs a{k, env_ids, obs, act, rew, cost, terminated, truncated, obs_next, ptr_out, ep_rew_out, ep_len_out, ep_idx_out,
                        k_act, obs_act, deterministic, bound_method, act_low, act_high, act_out, env_act_out};
     const int Da = g->m[0]->cfg.act_dim;
+    if (g->m[0]->lay) {
+        // a group of layered contexts: no resident kernel, ONE launch sequence per step for all members (host_layered_group.inc);
+        // any row count per member goes through it.  fsrl_group_actor_set_resident(g, 0, ...) selects the member-by-member calls.
+        const int n = (int)g->m.size(), Do = g->m[0]->cfg.obs_dim;
+        g->ga.stream = g->stream;
+        return ga_collect_step_via(
+            g->ga, g->m.data(), n, g->m[0]->device, a, [](int) { return true; },
+            [&]() { return lay_group_collect_post(g->lay, g->ga, g->m.data(), n, k_act, obs_act); },
+            [&]() { return lay_group_collect_wait(g->lay, g->ga, n, Do, Da); },
+            [&]() { (void)hipStreamSynchronize(g->stream); },       // a push failed behind the request: drain the stream
+            [&](int i, fsrl_ctx* c, int ka, const GaLayout&) {
+                const LayGroupPinned pin = lay_group_pinned(g->lay, Do, Da);
+                memcpy(c->act_mu.data(), pin.mu + (size_t)i * g->lay.ccap * Da, (size_t)ka * Da * 4);
+                const float* sp = pin.sp + (size_t)i * FSRL_MAX_ACT;
+                for (int r = 0; r < ka; ++r)
+                    for (int d = 0; d < Da; ++d) c->act_sg[(size_t)r * Da + d] = expf(sp[d]);
+            },
+            [&]() { (void)hipStreamSynchronize(g->stream); });
+    }
     return ga_collect_step(
         g->ga, g->m.data(), (int)g->m.size(), g->m[0]->device, a, [&]() { return group_actor_ensure(g); },
         // the ring holds the means and each member's log-sigma parameter row

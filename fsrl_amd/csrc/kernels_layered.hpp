@@ -127,29 +127,19 @@ __device__ __forceinline__ f32x4 lin_frag(const float* __restrict__ s, const int
 // the 4 / NW column tiles from 16 (4 / NW) wn.  A minibatch-sized product has only a few hundred workgroups: with NW = 1 that is
 // less than one wave per SIMD and every load, LDS read and barrier is exposed; NW = 4 puts up to four waves on each SIMD of the
 // workgroup's CU (the host picks NW from the number of workgroups of the launch).
+// The workgroup's work on ONE job, shared by lin_kernel (job table in the kernel arguments) and lin_group_kernel
+// (kernels_layered_group.hpp: job table in device memory, one member of a group per job): `jb` is the job as this workgroup
+// sees it (split-K range and per-step quantities already applied), `by` its row tile, `blk` the slot of its squared-norm share.
 template <int FORM, bool VEC, int NW>
-__global__ __launch_bounds__(256 * NW) void lin_kernel(const LinJobs jobs, float* __restrict__ gsq_part) {
+__device__ __forceinline__ void lin_body(const LinJob& jb, const int by, float* __restrict__ gsq_part, const int blk) {
     constexpr bool AKJ = (FORM == LIN_W), BKJ = (FORM != LIN_F);
     constexpr int T = 4 / NW, SLOTS = 4 / NW;
     __shared__ __attribute__((aligned(16))) float sA[64 * LIN_LD];
     __shared__ __attribute__((aligned(16))) float sB[64 * LIN_LD];
     __shared__ float red[4 * NW];
     const int tid = threadIdx.x, wv = tid >> 6, wave = wv & 3, wn = wv >> 2, lane = tid & 63, li = lane & 15, q = lane >> 4;
-    LinJob jb = jobs.j[blockIdx.z];              // by value: the fields live in SGPRs, not re-read from the kernel arguments per chunk
-    int by = blockIdx.y;
-    if (FORM == LIN_W && jobs.ksplit > 1) {      // this workgroup's range of batch rows and its partial
-        const int row_tiles = gridDim.y / jobs.ksplit, sp = by / row_tiles;
-        by -= sp * row_tiles;
-        const int kb = min(sp * jobs.kchunk, jb.K);
-        jb.K = min(jb.K - kb, jobs.kchunk);
-        jb.A += (size_t)kb * jb.lda; jb.B += (size_t)kb * jb.ldb;
-        if (jb.A2) { jb.A2 += (size_t)kb * jb.lda; jb.B2 += (size_t)kb * jb.ldb; }
-        jb.C += (size_t)sp * jobs.part_stride;
-        if (jb.bias_out) jb.bias_out += (size_t)sp * jobs.part_stride;
-    }
     const int M = jb.M, N = jb.N, K = jb.K;
     const int m0 = by * 64, n0 = blockIdx.x * 64;
-    const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const bool bias_role = (FORM == LIN_W) && blockIdx.x == 0 && jb.bias_out != nullptr;
     if (m0 >= M || (n0 >= N && !bias_role)) {
         if (FORM == LIN_W && gsq_part && tid == 0) gsq_part[blk] = 0.0f;
@@ -258,6 +248,22 @@ __global__ __launch_bounds__(256 * NW) void lin_kernel(const LinJobs jobs, float
         }
     }
 }
+template <int FORM, bool VEC, int NW>
+__global__ __launch_bounds__(256 * NW) void lin_kernel(const LinJobs jobs, float* __restrict__ gsq_part) {
+    LinJob jb = jobs.j[blockIdx.z];              // by value: the fields live in SGPRs, not re-read from the kernel arguments per chunk
+    int by = blockIdx.y;
+    if (FORM == LIN_W && jobs.ksplit > 1) {      // this workgroup's range of batch rows and its partial
+        const int row_tiles = gridDim.y / jobs.ksplit, sp = by / row_tiles;
+        by -= sp * row_tiles;
+        const int kb = min(sp * jobs.kchunk, jb.K);
+        jb.K = min(jb.K - kb, jobs.kchunk);
+        jb.A += (size_t)kb * jb.lda; jb.B += (size_t)kb * jb.ldb;
+        if (jb.A2) { jb.A2 += (size_t)kb * jb.lda; jb.B2 += (size_t)kb * jb.ldb; }
+        jb.C += (size_t)sp * jobs.part_stride;
+        if (jb.bias_out) jb.bias_out += (size_t)sp * jobs.part_stride;
+    }
+    lin_body<FORM, VEC, NW>(jb, by, gsq_part, (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+}
 
 // ---------------------------------------------------------------- loss heads of one minibatch step
 // grid = (ceil(mb_size / 16), n_nets), 256 threads = (row i = tid >> 4, action dim d = tid & 15): the head arithmetic of
@@ -269,10 +275,11 @@ struct LayHeadArgs {
     const float* P; int sigma;      // the actor's sigma_param inside P
     int mbp, n_nets, Da, unbounded;
 };
-__global__ __launch_bounds__(256) void lay_ppo_head_kernel(const LayHeadArgs h, const PpoStepArgs sa) {
+// (the body is shared with lay_ppo_head_group_kernel, kernels_layered_group.hpp: one member of a group per grid.z)
+__device__ __forceinline__ void lay_ppo_head_body(const LayHeadArgs& h, const PpoStepArgs& sa, const int tile, const int net) {
     __shared__ float st[16 * 4];
     const int tid = threadIdx.x, i = tid >> 4, d = tid & 15, lane = tid & 63;
-    const int net = blockIdx.y, tile = blockIdx.x, C = h.n_nets - 1, Da = h.Da;
+    const int C = h.n_nets - 1, Da = h.Da;
     const int row = tile * 16 + i;
     const bool valid = row < sa.mb_size;
     const float* rd = h.rd + (size_t)(sa.mb_start + (valid ? row : 0)) * FSRL_RD;
@@ -359,6 +366,9 @@ __global__ __launch_bounds__(256) void lay_ppo_head_kernel(const LayHeadArgs h, 
             for (int r = 0; r < 16; ++r) t += st[r * 4 + tid];
         h.statp[((size_t)tile * h.n_nets + net) * 4 + tid] = t;
     }
+}
+__global__ __launch_bounds__(256) void lay_ppo_head_kernel(const LayHeadArgs h, const PpoStepArgs sa) {
+    lay_ppo_head_body(h, sa, blockIdx.x, blockIdx.y);
 }
 
 // ---------------------------------------------------------------- heads of the full-batch family (FOCOPS step, CPO / TRPO-Lag)

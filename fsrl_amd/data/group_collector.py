@@ -4,7 +4,8 @@ agents' collect group, independent of their update groups).
 
 `GroupCollector(policy_group, collectors).collect(n_episode)` is `collector.collect(n_episode)` of every member, with the members'
 vector envs stepped in lock step and ONE library call per vector step for all of them (`EngineGroup.collect_step` ->
-fsrl_group_collect_step: one actor request, served by one resident kernel for the whole group).  Per member the bookkeeping is
+fsrl_group_collect_step: one actor request, served by one resident kernel for the whole group -- or, for a group of layered
+PPO-Lagrangian seeds, by one sequence of L + 2 launches carrying every member's rows).  Per member the bookkeeping is
 FastCollector._collect_fused's interpreted loop -- episode counts, resets of finished envs, surplus envs dropped, fill levels, the
 collector's counters, `reset_env` at the end -- and the library calls a member sees are the ones its own collect would make, so the
 stored rows, the actions and the member's noise stream are the same bit for bit.  A member that has its episodes stops contributing

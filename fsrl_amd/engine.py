@@ -777,7 +777,11 @@ class _LockStepCollect:
 class EngineGroup(_LockStepCollect):
     """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
     (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
-    random streams; use the engines as usual for everything else (push, collect_step, get_params ...)."""
+    random streams; use the engines as usual for everything else (push, collect_step, get_params ...).
+    PPO-Lagrangian members may all be layered contexts of one `hidden_sizes` (not FOCOPS members): the group then runs the layered
+    step, 2 L + 5 launches for all members, bit-identical per member to Engine.ppo_update; collect_step is one sequence of L + 2
+    launches for all members instead of a resident kernel (actor_resident_stats counts those sequences, `live` stays False;
+    actor_set_resident(False) selects the member-by-member calls; set_plan is accepted and has no effect)."""
 
     _collect_step_symbol = "fsrl_group_collect_step"
 

@@ -292,14 +292,20 @@ int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
  *      While grouped, a member's own update calls still work (they run on the group's stream).
  *      A group has one algorithm.  FOCOPS members (not layered) must have run fsrl_focops_init and share l2_reg, delta,
  *      eta, tem_lambda, max_grad_norm and fsrl_focops_set_plan (learning rates may differ); checked again at every update.
- *      Per FOCOPS member the result is bit-identical to its own update wherever the group keeps the member's tile height.  */
+ *      Per FOCOPS member the result is bit-identical to its own update wherever the group keeps the member's tile height.
+ *      LAYERED PPO-Lagrangian members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are layered
+ *      and n_hidden, hidden_sizes[] and force_layered agree (a mix of fused and layered members, or of widths: "one network
+ *      shape"; layered FOCOPS members are refused).  The group then runs the layered minibatch step with every member in each
+ *      of its 2 L + 5 launches (L hidden layers), whatever k; per member the update is bit-identical to its own
+ *      fsrl_ppo_update, for every k, batch length and minibatch size.                                                        */
 typedef struct fsrl_group fsrl_group;
 int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out);       /* 1 <= k <= 16; members are not owned   */
 int fsrl_group_destroy(fsrl_group* group);
 /* Launch plan of the group's forward / backward launch (A/B and tests; every plan gives the same bits): how many leading tiles of a
  * (member, network) are 32 rows tall.  -1 automatic (default: all of them once the 16-row tiles of the group exceed the CU count, e.g.
  * 8 members x 3 networks x 256 rows: 192 workgroups of 32 rows instead of 384 of 16), 0 none, n > 0 min(n, tiles / 2).
- * Needs hidden >= 128 and obs_dim <= 64 (else 16-row tiles whatever the plan).                                                      */
+ * Needs hidden >= 128 and obs_dim <= 64 (else 16-row tiles whatever the plan).  A group of layered contexts accepts the call and
+ * ignores it (the layered step has no tile plan).                                                                                    */
 int fsrl_group_set_plan(fsrl_group* group, int32_t tall_tiles);
 /* k x BasePolicy.update (base_policy.py:332-355).  lagrangians [k][n_critics - 1], rescaling [k]; perms: NULL (library
  * shuffle, member i seeded by seed + 1000003 i + pass) or k pointers to [repeat][N_i]; stats_out: NULL or k pointers to
@@ -317,7 +323,12 @@ int fsrl_group_ppo_update(fsrl_group* group, const double* lagrangians, const do
  * the group (a workgroup per member and 16-row tile, on the group's stream); it ends before the group's stream gets other work
  * (fsrl_group_ppo_update, a member's own library calls, fsrl_group_destroy), on fsrl_group_actor_release and after its idle
  * timeout.  Off the resident path (fsrl_group_actor_set_resident(0), a member asking for more rows than its 16 * min(4,
- * ceil(env_num / 16)) tiles): one actor launch per member inside the same call, the same bits.                          */
+ * ceil(env_num / 16)) tiles): one actor launch per member inside the same call, the same bits.
+ * A group of LAYERED contexts has no resident kernel: the members' rows are staged side by side in pinned memory and ONE sequence of
+ * L + 2 launches on the group's stream (one job per member that has rows) serves the request, for any row count per member; the
+ * host waits on completion words with a bounded poll.  fsrl_group_actor_set_resident(g, 0, ..) selects the member-by-member calls
+ * (k (L + 2) launches), fsrl_group_actor_resident_stats reports {shared launch sequences, requests served by them, 0}, and
+ * fsrl_group_actor_release has nothing to end.  The same bits either way.                                                */
 int fsrl_group_collect_step(fsrl_group* group, const int32_t* k, const int32_t* env_ids, const float* obs, const float* act,
                             const double* rew, const double* cost, const uint8_t* terminated, const uint8_t* truncated,
                             const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out,
