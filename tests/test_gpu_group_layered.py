@@ -88,6 +88,25 @@ def test_golden_fixtures_through_a_group(name, k):
     _close(engs, solo)
 
 
+def test_minibatches_of_1300_rows_through_a_group_of_two():
+    """tests/test_gpu_layered.py's large-minibatch case (hidden (64, 48, 32), 2 600 rows, batch 1 300, no gradient clip) with member 0
+    on the oracle's inputs and member 1 on perturbed parameters, its own multiplier and permutations: lin_group_kernel past 512 rows.
+    Member 0 meets the oracle's bars after the first update, every member equals its solo twin after both."""
+    from test_gpu_layered import large_minibatch_bars, large_minibatch_case, large_minibatch_engine
+    case = large_minibatch_case()
+    n, R = sum(case["rows"]), case["repeat"]
+    rng = np.random.default_rng(6)
+    thetas = [case["theta"], case["theta"] + (0.01 * rng.standard_normal(case["theta"].size)).astype(np.float32)]
+    perms = [list(case["perms"]), [rng.permutation(n) for _ in range(R)]]
+    lags = [case["lag"], case["lag"] * 1.5]
+    resc = [case["resc"], _rescale(lags[1])]
+    engs = [large_minibatch_engine(case, th) for th in thetas]
+    solo = [large_minibatch_engine(case, th) for th in thetas]
+    _twice(engs, solo, lags, resc, case["B"], R, perms,
+           after_first=lambda st, stop: large_minibatch_bars(case, st[0], stop[0], engs[0].get_params()))
+    _close(engs, solo)
+
+
 def test_ragged_shapes_row_counts_and_an_empty_member():
     """obs 17 (rows that are no multiple of 4 floats: the dword-load instantiation), act 3, hidden (33, 100, 7), gradient clip; members
     with 300 / 257 / 143 / 0 rows at batch 64: different step counts, merged last minibatches, a member that never held a row."""

@@ -78,6 +78,65 @@ def test_batch_of_baseline_size_vs_oracle(hidden):
     eng.close()
 
 
+_LARGE = {}
+
+
+def large_minibatch_case():
+    """obs 8, act 2, hidden (64, 48, 32), 2 x 1 300 rows, batch 1 300, two passes, NO gradient clip: inputs and the oracle's logged
+    rows and parameters (computed once; tests/test_gpu_group_layered.py runs the same case through a group)"""
+    if not _LARGE:
+        from oracle.ppo_lag import OnPolicyData, PPOLagConfig, PPOLagOracle
+        from test_gpu_shapes import _synthetic
+        Do, Da, hidden, rows, ep, B, repeat = 8, 2, (64, 48, 32), [1300, 1300], 80, 1300, 2
+        rng = np.random.default_rng(78)
+        cols = _synthetic(rng, rows, Do, Da, ep)
+        o = PPOLagOracle(PPOLagConfig(obs_dim=Do, act_dim=Da, hidden=hidden, max_grad_norm=None, target_kl=1e9))
+        torch.manual_seed(5)
+        theta = (0.15 * torch.randn(o.n_params)).numpy()
+        o.set_params(theta)
+        cat = {k: np.concatenate(v) for k, v in cols.items()}
+        end = (cat["term"] | cat["trunc"]).copy(); end[np.cumsum(rows) - 1] = True
+        data = OnPolicyData(obs=cat["obs"], act=cat["act"], rew=cat["rew"], cost=cat["cost"], terminated=cat["term"],
+                            truncated=cat["trunc"], obs_next=cat["obs_next"], end_flag=end)
+        perms = [rng.permutation(len(data)) for _ in range(repeat)]
+        lag = np.array([0.4])
+        _, ostats, _ = o.update(data, lag, 1 / 1.4, B, repeat, perms=perms)
+        _LARGE.update(Do=Do, Da=Da, hidden=hidden, rows=rows, B=B, repeat=repeat, cols=cols, theta=theta, perms=perms, lag=lag,
+                      resc=1 / 1.4, ostats=np.asarray(ostats), otheta=o.get_params())
+    return _LARGE
+
+
+def large_minibatch_engine(case, theta):
+    from fsrl_amd.engine import Engine, EngineConfig
+    rows, cols = case["rows"], case["cols"]
+    eng = Engine(EngineConfig(obs_dim=case["Do"], act_dim=case["Da"], hidden_sizes=case["hidden"], env_num=len(rows), buffer_size=4096,
+                              max_grad_norm=None, target_kl=None))
+    eng.set_params(theta)
+    for t in range(max(rows)):
+        ids = [e for e in range(len(rows)) if t < rows[e]]
+        eng.push(ids, *[np.stack([cols[k][e][t] for e in ids]) for k in ("obs", "act", "rew", "cost", "term", "trunc", "obs_next")])
+    return eng
+
+
+def large_minibatch_bars(case, stats, stopped, theta):
+    """the assertions of tests/test_gpu_shapes.py::test_large_minibatch_without_grad_clip_vs_oracle"""
+    assert stopped == -1 and stats.shape == case["ostats"].shape == (4, 11)
+    np.testing.assert_allclose(stats, case["ostats"], rtol=3e-5, atol=3e-5)
+    d = np.abs(theta - case["otheta"])
+    assert np.quantile(d, 0.999) <= 5e-6 and d.max() <= 1e-4, (np.quantile(d, 0.999), d.max())
+
+
+def test_large_layered_minibatch_without_grad_clip_vs_oracle():
+    """The layered twin of test_gpu_shapes.test_large_minibatch_without_grad_clip_vs_oracle: minibatches of 1 300 rows on hidden
+    (64, 48, 32) -- the longest UNSPLIT fp32 chain of the weight side any test runs (the minibatch step never splits), Adam
+    without a clip coefficient."""
+    case = large_minibatch_case()
+    eng = large_minibatch_engine(case, case["theta"])
+    stats, stopped = eng.ppo_update(case["lag"], case["resc"], case["B"], case["repeat"], perms=case["perms"])
+    large_minibatch_bars(case, stats, stopped, eng.get_params())
+    eng.close()
+
+
 def test_layered_update_is_deterministic():
     cfg, g = ppo_case("deep3")
     outs = []

@@ -61,3 +61,27 @@ def test_replay_oracles_take_any_depth(hidden):
     assert n(single_critic_spec(Do, Da, hidden)) == cnt(SingleCritic(Net((Do, ), (Da, ), hidden_sizes=hidden, concat=True)))
     assert [k for k in double_critic_spec(Do, Da, hidden)][-1] == f"b{len(hidden) + 1}_2"
     torch.manual_seed(0)
+
+
+def test_split_ranges_of_the_full_batch_weight_side_cover_every_row_once():
+    """The split-K rule of lay_wgrad_k / lin_kernel (restated in tests/test_gpu_layered_fullbatch.py) for 1 .. 40 000 batch rows:
+    at most 24 ranges, each starting on a multiple of 64 rows where the last one ended, every row in exactly one of them, empty
+    ranges only at the tail."""
+    from test_gpu_layered_fullbatch import split_ranges
+    one_row, empty = [], []
+    for rows in range(1, 40001):
+        r = split_ranges(rows)
+        assert 1 <= len(r) <= 24 and (len(r) == 1) == (rows <= 1024), rows
+        end = 0
+        for start, n in r:
+            assert n >= 0 and start == end and (n == 0 or start % 64 == 0), (rows, r)      # contiguous: no row twice, none left out
+            end += n
+        assert end == rows, (rows, r)
+        sizes = [n for _, n in r]
+        first_empty = sizes.index(0) if 0 in sizes else len(sizes)
+        assert not any(sizes[first_empty:]) and sizes[0] > 0, (rows, r)
+        if sizes[-1] == 1:
+            one_row.append(rows)
+        if sizes[-1] == 0:
+            empty.append(rows)
+    assert 16385 in one_row and 19457 in one_row and 24600 in empty          # the sizes the GPU cases use do occur
