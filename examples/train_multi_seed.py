@@ -32,6 +32,12 @@ fsrl_sac_group_update over deterministic-actor contexts; tools/bench_group_sac.p
 contexts; --grouped --algo ppol takes them as well: a layered minibatch step is 2 L + 5 launches whatever the number of seeds
 and the actor request of a vector step L + 2 (tools/bench_group_layered.py).
     python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --hidden-sizes 256x256x256
+--grouped --algo sacl / ddpgl take layered seeds too: a layered replay update is 9 L + 19 launches whatever the number of seeds,
+per seed bit-identical to its own update, and the actor request of a vector step L + 2 (tools/bench_group_sac.py --hidden ...,
+tools/bench_group_collect.py --hidden ...): at 8 seeds of (256, 256, 256) 1.9x the updates/s of 8 threads and 2.3x the env-steps/s of
+collecting seed by seed; grouped updates lose to threads at 2 seeds or fewer, shared collection loses at one seed.
+Layered CVPO seeds do not group yet: --grouped --algo cvpo refuses them.
+    python examples/train_multi_seed.py --algo sacl --seeds 8 --epoch 2 --grouped --hidden-sizes 64x48x32
 """
 import argparse
 import os
@@ -146,7 +152,12 @@ def run_grouped(a):
         ag.policy.engine.close()
 
 
-def main():
+def is_layered(hidden_sizes):
+    """the engine's rule: anything but two hidden layers of at most 256 units makes a layered context"""
+    return len(hidden_sizes) != 2 or max(hidden_sizes) > 256
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", choices=sorted(AGENTS), default="ppol")
     ap.add_argument("--seeds", type=int, default=3)
@@ -156,10 +167,17 @@ def main():
     ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread")
     ap.add_argument("--hidden-sizes", default="128x128", type=lambda t: tuple(int(w) for w in t.lower().split("x")),
                     help="hidden layers of every network, e.g. 64x48x32 (anything but two layers of at most 256 units runs the "
-                         "layered kernels; --grouped takes such PPO-Lag seeds too)")
-    a = ap.parse_args()
+                         "layered kernels; --grouped takes such PPO-Lag, SAC-Lag and DDPG-Lag seeds too, not FOCOPS or CVPO seeds)")
+    a = ap.parse_args(argv)
     if isinstance(a.hidden_sizes, str):
         a.hidden_sizes = tuple(int(w) for w in a.hidden_sizes.lower().split("x"))
+    if a.grouped and a.algo in ("focops", "cvpo") and is_layered(a.hidden_sizes):
+        ap.error(f"--grouped --algo {a.algo}: layered seeds (--hidden-sizes other than two layers of at most 256 units) do not group yet")
+    return a
+
+
+def main():
+    a = parse_args()
     out, errs = {}, []
     if a.grouped:
         return run_grouped(a)

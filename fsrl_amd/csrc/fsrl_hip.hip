@@ -1550,9 +1550,11 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 
 #include "kernels_sac_group.hpp"
 #include "host_sac_group.inc"
+#include "kernels_layered_sac_group.hpp"
 #include "kernels_cvpo_group.hpp"
 #include "host_cvpo_group.inc"
 #include "host_collect_group.inc"
+#include "host_sac_group_layered.inc"
 
 #include "host_comm.inc"
 

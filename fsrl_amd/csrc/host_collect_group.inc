@@ -34,9 +34,18 @@ struct fsrl_collect_group {
     bool broken = false;
     int raw_cols = 0;
     GaRing ga;
+    // a group of layered members (host_sac_group_layered.inc): no resident kernel, one launch sequence per request
+    bool layered = false;
+    bool reorder = true;                       // a release since the last request: the next one goes behind the members' streams first
+    LayGroup lay;
 };
+static int lay_collect_group_step(fsrl_collect_group* g, const GaStepArgs& a);
 
-static void collect_group_actor_release(fsrl_collect_group* g) { ga_release(g->ga); }
+// The hook of pactor_release / actor_eval_launch: something may change a member's actor, or runs it.  A fused group's kernel ends;
+// a layered group has no kernel to end, so the hook marks it and its next request orders the group's stream behind the members'
+// streams (a fused group never reads the mark).  Only this hook re-orders: the public fsrl_collect_group_actor_release changes
+// nothing of a member and leaves the mark alone.
+static void collect_group_actor_release(fsrl_collect_group* g) { ga_release(g->ga); g->reorder = true; }
 
 static void collect_group_detach(fsrl_ctx* c) {
     fsrl_collect_group* g = c->cgroup;
@@ -80,6 +89,7 @@ extern "C" int fsrl_collect_group_destroy(fsrl_collect_group* g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (fsrl_ctx* c : g->m) if (c) c->cgroup = nullptr;
     for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
+    lay_group_free(g->lay);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     if (g->ga.h) (void)hipHostFree(g->ga.h);
     delete g;
@@ -101,14 +111,18 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
                   "collect through fsrl_group_create / fsrl_group_collect_step", i);
         const SacState* s = sac_of(c);
         CHECK_ARG(s, "member %d is not initialised: fsrl_sac_init / fsrl_cvpo_init first", i);
-        CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: it has no fused actor network for the resident kernel", i);
+        CHECK_ARG(!(s->layered && s->cvpo), "member %d is a layered CVPO context: it has no fused actor network for the resident kernel, "
+                  "and layered CVPO members do not group yet", i);
         const SacState* s0 = sac_of(c0);
+        CHECK_ARG(!s0 || s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a collect group is all fused (the "
+                  "resident kernel) or all layered contexts", i, s->layered ? "layered" : "fused", s0->layered ? "layered" : "fused");
         CHECK_ARG(!s0 || collect_group_kind(s) == collect_group_kind(s0),
                   "member %d is a %s context, member 0 a %s one: a collect group has one kind of member", i, kinds[collect_group_kind(s)],
                   kinds[collect_group_kind(s0)]);
         CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
-        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden,
-                  "member %d: members must have one network shape (obs_dim, act_dim, hidden)", i);
+        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden &&
+                  (!s->layered || lay_same_shape(c->cfg, c0->cfg)),
+                  "member %d: members must have one network shape (obs_dim, act_dim, hidden; layered: every hidden_sizes[l] and force_layered)", i);
         for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member %d is listed twice", i);
         CHECK_ARG(!c->cgroup, "member %d is already in a collect group", i);
     }
@@ -117,6 +131,7 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
     fsrl_collect_group* g = new fsrl_collect_group();
     g->device = c0->device;
     g->raw_cols = sac_raw_cols(c0);
+    g->layered = sac_of(c0)->layered;
     g->ready.assign((size_t)k, nullptr);
     for (int i = 0; i < k; ++i) g->m.push_back(ctxs[i]);
     hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
@@ -128,7 +143,7 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
         return FSRL_EHIP;
     }
     g->ga.stream = g->stream; g->ga.launch = collect_group_launch; g->ga.owner = g;
-    const int rc = gactor_ensure(g->ga, g->m.data(), k, g->raw_cols);
+    const int rc = g->layered ? 0 : gactor_ensure(g->ga, g->m.data(), k, g->raw_cols);      // a layered group has no ring
     if (rc) { g->m.clear(); (void)fsrl_collect_group_destroy(g); return rc; }
     for (int i = 0; i < k; ++i) ctxs[i]->cgroup = g;
     *out = g;
@@ -147,6 +162,7 @@ extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, 
     if (g->broken) return fail(FSRL_ESTATE, "a member of this collect group has been destroyed");
     const GaStepArgs a{k, env_ids, obs, act, rew, cost, terminated, truncated, obs_next, ptr_out, ep_rew_out, ep_len_out, ep_idx_out,
                        k_act, obs_act, deterministic, bound_method, act_low, act_high, act_out, env_act_out};
+    if (g->layered) return lay_collect_group_step(g, a);
     const int n = (int)g->m.size(), Da = g->m[0]->cfg.act_dim, rcols = g->raw_cols;
     return ga_collect_step(
         g->ga, g->m.data(), n, g->device, a, []() { return 0; },
@@ -165,6 +181,7 @@ extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, 
 
 extern "C" int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us) {
     CHECK_ARG(g, "null group");
+    if (g->layered) return 0;                  // no resident kernel to switch: accepted, no effect
     return ga_set_resident(g->ga, on, idle_timeout_us);
 }
 
@@ -176,6 +193,6 @@ extern "C" int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, in
 
 extern "C" int fsrl_collect_group_actor_release(fsrl_collect_group* g) {
     CHECK_ARG(g, "null group");
-    ga_release(g->ga);
+    ga_release(g->ga);                         // (a layered group: nothing is live)
     return 0;
 }

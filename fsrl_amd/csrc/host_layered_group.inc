@@ -15,20 +15,21 @@ struct LayGroup {
     int nw_w = 4;                               // NW of the weight-side launch: the one a member's own launch has
     hipEvent_t copied = nullptr; bool in_flight = false;     // the pinned tables have left host memory
     // lock-step collection
-    void* ch = nullptr;                         // pinned: [done k x cap / 16 | pad | obs k x cap x Do | mu k x cap x Da | sigma_param k x 16]
+    void* ch = nullptr;                         // pinned: [done k x cap / 16 | pad | obs k x cap x Do | mu k x cap x cols | sigma_param k x 16]
+                                                // (cols: Da for the on-policy group, the raw head columns for the replay agents)
     float* cd = nullptr;                        // device: two activation buffers k x cap x hm, head outputs k x cap x 16
     int ccap = 0, ck = 0;                       // rows reserved per member; members the buffers were made for
     unsigned cseq = 0;
     int crow[GACTOR_MAX_MEMBERS] = {};          // rows of each member in the request in flight
 };
 struct LayGroupPinned { unsigned* done; float* obs; float* mu; float* sp; };
-static LayGroupPinned lay_group_pinned(const LayGroup& lg, int Do, int Da) {
+static LayGroupPinned lay_group_pinned(const LayGroup& lg, int Do, int cols) {
     char* b = (char*)lg.ch;
     LayGroupPinned p;
     p.done = (unsigned*)b;
     p.obs = (float*)(b + round_up(lg.ck * (lg.ccap / 16) * 4, 256));
     p.mu = p.obs + (size_t)lg.ck * lg.ccap * Do;
-    p.sp = p.mu + (size_t)lg.ck * lg.ccap * Da;
+    p.sp = p.mu + (size_t)lg.ck * lg.ccap * cols;
     return p;
 }
 
@@ -217,13 +218,15 @@ static int lay_group_step(LayGroup& lg, fsrl_ctx* const* m, int k, hipStream_t s
 }
 
 // ---------------------------------------------------------------- lock-step collection
-// the shared request: k_act[i] rows of obs_act (concatenated over members) -> L + 2 launches on the group's stream
-static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, int k, const int32_t* k_act, const float* obs_act) {
-    fsrl_ctx* c0 = m[0];
-    const LayState* l0 = c0->lay;
-    const LayModel& lm = l0->lm;
-    const int Do = lm.Do, Da = lm.Da, L = l0->L;
-    const size_t hm = (size_t)round_up(l0->hmax, 4);
+// the shared request: k_act[i] rows of obs_act (concatenated over members) -> L + 2 launches on the group's stream.  The staging is
+// shared by the on-policy group below and the replay agents' collect group (host_sac_group_layered.inc): `net` is the actor
+// network's layers, P(i) member i's parameter vector of it, `cols` the floats per answered row in pinned memory, and
+// tail(outb, pin, maxk) the last launch, which leaves the answer and the completion words there.
+template <class ParamOf, class Tail>
+static int lay_group_collect_stage(LayGroup& lg, GaRing& ga, fsrl_ctx* c0, const LayNet& net, int Do, int hmax, int k, int cols,
+                                   const int32_t* k_act, const float* obs_act, ParamOf&& P, Tail&& tail) {
+    const int L = net.nl - 1;
+    const size_t hm = (size_t)round_up(hmax, 4);
     hipStream_t s = ga.stream;
     int maxk = 0;
     for (int i = 0; i < k; ++i) maxk = std::max(maxk, (int)k_act[i]);
@@ -233,13 +236,13 @@ static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, 
         if (lg.cd) { HIPCHK(hipFree(lg.cd)); lg.cd = nullptr; }
         lg.ccap = 0;
         const int cap = round_up(std::max(2 * maxk, 64), 16);
-        const size_t hbytes = (size_t)round_up(k * (cap / 16) * 4, 256) + ((size_t)k * cap * (Do + Da) + (size_t)k * FSRL_MAX_ACT) * 4;
+        const size_t hbytes = (size_t)round_up(k * (cap / 16) * 4, 256) + ((size_t)k * cap * (Do + cols) + (size_t)k * FSRL_MAX_ACT) * 4;
         HIPCHK(hipHostMalloc(&lg.ch, hbytes));
         memset(lg.ch, 0, hbytes);
         HIPCHK(hipMalloc(&lg.cd, (size_t)k * cap * (2 * hm + FSRL_MAX_ACT) * 4));
         lg.ccap = cap; lg.ck = k;
     }
-    const LayGroupPinned pin = lay_group_pinned(lg, Do, Da);
+    const LayGroupPinned pin = lay_group_pinned(lg, Do, cols);
     const int cap = lg.ccap;
     lg.cseq += 1;
     if (lg.cseq == 0) lg.cseq = 1;
@@ -252,15 +255,15 @@ static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, 
     float* bufs[2] = {lg.cd, lg.cd + (size_t)k * cap * hm};
     float* outb = lg.cd + 2 * (size_t)k * cap * hm;
     for (int l = 0; l <= L; ++l) {
-        const LayLayer& ll = lm.net[0].l[l];
+        const LayLayer& ll = net.l[l];
         LinJobs jobs{};
         for (int i = 0; i < k; ++i) {
             if (k_act[i] <= 0) continue;
             LinJob& jb = jobs.j[jobs.n++];
             jb.A = (l == 0) ? pin.obs + (size_t)i * cap * Do : bufs[(l - 1) & 1] + (size_t)i * cap * hm;
             jb.lda = ll.in;
-            jb.B = m[i]->P + ll.W; jb.ldb = ll.in;
-            jb.aux = m[i]->P + ll.b;
+            jb.B = P(i) + ll.W; jb.ldb = ll.in;
+            jb.aux = P(i) + ll.b;
             jb.M = k_act[i]; jb.N = ll.out; jb.K = ll.in;
             if (l < L) { jb.C = bufs[l & 1] + (size_t)i * cap * hm; jb.ldc = ll.out; jb.relu = 1; }
             else { jb.C = outb + (size_t)i * cap * FSRL_MAX_ACT; jb.ldc = FSRL_MAX_ACT; jb.relu = 0; }
@@ -268,20 +271,31 @@ static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, 
         const int rc = lay_launch<LIN_F>(c0, jobs, nullptr, s);
         if (rc) return rc;
     }
-    LayInferGroupArgs a{};
-    for (int i = 0; i < k; ++i) { a.P[i] = m[i]->P; a.rows[i] = k_act[i]; }
-    a.out = outb; a.mu = pin.mu; a.sp = pin.sp; a.done = pin.done;
-    a.cap = cap; a.tiles_cap = cap / 16;
-    a.sigma = lm.net[0].sigma; a.Da = Da; a.unbounded = lm.unbounded; a.max_action = c0->cfg.max_action; a.seq = lg.cseq;
-    hipLaunchKernelGGL(lay_infer_out_group_kernel, dim3((maxk + 15) / 16, k), dim3(64), 0, s, a);
+    tail(outb, pin, maxk);
     HIPCHK(hipGetLastError());
     ga.launches += 1; ga.requests += 1;
     return 0;
 }
+static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, int k, const int32_t* k_act, const float* obs_act) {
+    fsrl_ctx* c0 = m[0];
+    const LayState* l0 = c0->lay;
+    const LayModel& lm = l0->lm;
+    const int Da = lm.Da;
+    return lay_group_collect_stage(
+        lg, ga, c0, lm.net[0], lm.Do, l0->hmax, k, Da, k_act, obs_act, [&](int i) { return m[i]->P; },
+        [&](float* outb, const LayGroupPinned& pin, int maxk) {
+            LayInferGroupArgs a{};
+            for (int i = 0; i < k; ++i) { a.P[i] = m[i]->P; a.rows[i] = k_act[i]; }
+            a.out = outb; a.mu = pin.mu; a.sp = pin.sp; a.done = pin.done;
+            a.cap = lg.ccap; a.tiles_cap = lg.ccap / 16;
+            a.sigma = lm.net[0].sigma; a.Da = Da; a.unbounded = lm.unbounded; a.max_action = c0->cfg.max_action; a.seq = lg.cseq;
+            hipLaunchKernelGGL(lay_infer_out_group_kernel, dim3((maxk + 15) / 16, k), dim3(64), 0, ga.stream, a);
+        });
+}
 
 // the answer of the request in flight is in pinned memory: ga_poll's bounded wait on the completion words
-static int lay_group_collect_wait(LayGroup& lg, GaRing& ga, int k, int Do, int Da) {
-    const LayGroupPinned pin = lay_group_pinned(lg, Do, Da);
+static int lay_group_collect_wait(LayGroup& lg, GaRing& ga, int k, int Do, int cols) {
+    const LayGroupPinned pin = lay_group_pinned(lg, Do, cols);
     const int tc = lg.ccap / 16;
     auto served = [&]() {
         for (int i = 0; i < k; ++i)

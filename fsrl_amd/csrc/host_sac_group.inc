@@ -70,10 +70,16 @@ static int rgroup_fanout(ReplayGroupCore& g, int i) {
     return 0;
 }
 
+// a group of layered members (all fused or all layered): host_sac_group_layered.inc
+struct LaySacGroup;
+static void lay_sac_group_free(LaySacGroup* lg);
+static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_updates, const double* lagrangians, const double* rescaling);
+
 struct fsrl_sac_group {
     ReplayGroupCore core;
     DevTable<SacGroupMember> tab;              // [k]
     DevTable<SacGroupStep> steps;              // [updates][k]
+    LaySacGroup* lay = nullptr;                // job and head tables of a layered group, made by its first update
 };
 
 static void sac_group_detach(fsrl_ctx* c) {
@@ -87,6 +93,7 @@ extern "C" int fsrl_sac_group_destroy(fsrl_sac_group* g) {
     for (fsrl_ctx* c : g->core.m) if (c) c->sac_group = nullptr;
     rgroup_destroy(g->core);
     table_free(g->tab); table_free(g->steps);
+    lay_sac_group_free(g->lay);
     delete g;
     return 0;
 }
@@ -102,14 +109,16 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
         const SacState* s = reinterpret_cast<const SacState*>(c->sac);
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped SAC updates take SAC-Lagrangian contexts (fsrl_sac_init)", i);
         CHECK_ARG(!s->cvpo, "member %d runs CVPO: grouped SAC updates take SAC-Lagrangian contexts only", i);
-        CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: grouped SAC updates run the fused kernels (two hidden layers)", i);
+        const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
+        CHECK_ARG(s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a group is all fused (two hidden layers of at "
+                  "most 256 units) or all layered contexts", i, s->layered ? "layered" : "fused", s0->layered ? "layered" : "fused");
         CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
         CHECK_ARG(!c->sac_group, "member %d is already in a SAC group", i);
-        const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
         CHECK_ARG(s->ddpg == s0->ddpg, "member %d: a group is all SAC-Lagrangian or all DDPG-Lagrangian (deterministic actor) contexts, "
                   "and member 0 is %s", i, s0->ddpg ? "DDPG-Lagrangian" : "SAC-Lagrangian");
-        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden,
-                  "member %d: members must have one network shape (obs_dim, act_dim, hidden)", i);
+        CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden &&
+                  (!s->layered || lay_same_shape(c->cfg, c0->cfg)),
+                  "member %d: members must have one network shape (obs_dim, act_dim, hidden; layered: every hidden_sizes[l] and force_layered)", i);
         CHECK_ARG(s->cfg.n_step == s0->cfg.n_step && (s->cfg.auto_alpha != 0) == (s0->cfg.auto_alpha != 0) &&
                   (s->cfg.use_lagrangian != 0) == (s0->cfg.use_lagrangian != 0),
                   "member %d: members must share n_step, auto_alpha and use_lagrangian (learning rates, tau, seeds and data may differ)", i);
@@ -232,6 +241,7 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     const int k = (int)gc.m.size();
     fsrl_ctx* c0 = gc.m[0];
     SacState* s0 = sac_of(c0);
+    if (s0 && s0->layered) return lay_sac_group_update(g, B, n_updates, lagrangians, rescaling);
     int n_max = 0;
     for (int i = 0; i < k; ++i) {
         fsrl_ctx* c = gc.m[i];

@@ -19,10 +19,11 @@ struct LaySacActorArgs {
     int B, Bq, Do, Da, mode, deterministic, auto_alpha;
     float max_action, cr, cc, rescale, alpha_fixed;
 };
-__global__ __launch_bounds__(256) void lay_sac_actor_head_kernel(const LaySacActorArgs a) {
+// the workgroup's work on 16-row tile `tile`: shared by the kernel below and the grouped launch (kernels_layered_sac_group.hpp)
+__device__ __forceinline__ void lay_sac_actor_head_body(const LaySacActorArgs& a, const int tile) {
     __shared__ float stl[16 * 4];
     const int tid = threadIdx.x, i = tid >> 4, d = tid & 15, lane = tid & 63;
-    const int r = blockIdx.x * 16 + i, Da = a.Da, Din = a.Do + Da;
+    const int r = tile * 16 + i, Da = a.Da, Din = a.Do + Da;
     const bool valid = r < a.B;
     const float invB = 1.0f / (float)a.B;
     const float* o = a.out + (size_t)(valid ? r : 0) * FSRL_MAX_ACT;
@@ -94,9 +95,10 @@ __global__ __launch_bounds__(256) void lay_sac_actor_head_kernel(const LaySacAct
     if (tid < 3) {
         float t = 0.0f;
         for (int rr = 0; rr < 16; ++rr) t += stl[rr * 4 + tid];
-        a.statp[(size_t)blockIdx.x * FB_NSTAT + tid] = t;
+        a.statp[(size_t)tile * FB_NSTAT + tid] = t;
     }
 }
+__global__ __launch_bounds__(256) void lay_sac_actor_head_kernel(const LaySacActorArgs a) { lay_sac_actor_head_body(a, (int)blockIdx.x); }
 
 // ---- Q heads: FB_MODE_Q_FWD (write Q), _Q_TRAIN (td = Q - y, dout = 2 td / B, sum td^2), _Q_DIN (write Q, unit seed).
 //      grid = (ceil(B / 16), n_q), 64 threads: lane r < 16 = row.
@@ -105,8 +107,8 @@ struct LaySacQArgs {
     const float* tgt; float* qout; float* statp;
     int B, mbp, n_q, mode, pair_shift;
 };
-__global__ __launch_bounds__(64) void lay_sac_q_head_kernel(const LaySacQArgs a) {
-    const int net = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+__device__ __forceinline__ void lay_sac_q_head_body(const LaySacQArgs& a, const int tile, const int net) {
+    const int tid = threadIdx.x;
     const int r = tile * 16 + tid;
     float st0 = 0.0f;
     if (tid < 16 && r < a.B) {
@@ -131,6 +133,7 @@ __global__ __launch_bounds__(64) void lay_sac_q_head_kernel(const LaySacQArgs a)
     for (int rr = 0; rr < 16; ++rr) t += __shfl(st0, rr, 64);
     if (tid < FB_NSTAT) a.statp[((size_t)tile * a.n_q + net) * FB_NSTAT + tid] = (tid == 0) ? t : 0.0f;
 }
+__global__ __launch_bounds__(64) void lay_sac_q_head_kernel(const LaySacQArgs a) { lay_sac_q_head_body(a, (int)blockIdx.x, (int)blockIdx.y); }
 
 // ---- the collector's actor on a layered replay context: raw head outputs to pinned host memory + completion words
 __global__ __launch_bounds__(64) void lay_raw_out_kernel(const float* __restrict__ out, float* __restrict__ raw_out, const int cols,

@@ -865,7 +865,10 @@ class EngineSacGroup:
     of one shape on one GPU, updated in lock step (fsrl_sac_group_*): every launch of an update carries all members that
     still have updates to run.  The group's kind is its first member's; the two kinds do not mix.  Members keep their
     own streams, stores, parameters, Philox keys and statistics rings, and stay ordinary engines between updates (push,
-    collect_step with the resident actor, sac_get_params, sac_drain ...)."""
+    collect_step with the resident actor, sac_get_params, sac_drain ...).
+    The members are all fused (two hidden layers of at most 256 units) or all layered contexts of one `hidden_sizes` and
+    `force_layered`: a layered group runs the layered update's launch sequence with every member in each launch, and a member's
+    grouped update is then bit-identical to its own sac_update at every group size."""
 
     def __init__(self, engines):
         self.engines = list(engines)
@@ -938,7 +941,10 @@ class EngineCollectGroup(_LockStepCollect):
     COLLECT in lock step (fsrl_collect_group_*): one library call and one request to one resident actor kernel per vector step
     for all members, per member bit-identical to its own collect_step.  Independent of the update groups: the members may also
     be in an EngineSacGroup / EngineCvpoGroup, and stay ordinary engines.  EngineGroup's collect interface, so
-    GroupCollector(engine_collect_group, collectors) drives it."""
+    GroupCollector(engine_collect_group, collectors) drives it.
+    SAC-Lag / DDPG-Lag members may all be layered contexts of one `hidden_sizes` (not CVPO members yet): the group then has no
+    resident kernel -- a request is one launch sequence (L + 2 launches) for all members, actor_set_resident is accepted and has no
+    effect, actor_release does nothing and actor_resident_stats counts the requests."""
     _collect_step_symbol = "fsrl_collect_group_step"
 
     def __init__(self, engines):

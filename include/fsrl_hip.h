@@ -562,7 +562,12 @@ int fsrl_sac_actor_forward(fsrl_ctx* ctx, const float* obs, int32_t k, float* mu
  *      key and statistics ring, and stay ordinary contexts between calls (a call ends a member's resident actor; its next collect
  *      relaunches it).  Shapes (obs / act / hidden), n_step, auto_alpha and use_lagrangian must agree; learning rates, tau, seeds
  *      and store contents may differ.  Rejected with FSRL_EINVAL: a mixture of SAC-Lag and DDPG-Lag members (either order), CVPO
- *      and layered contexts, a member listed twice or already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works. */
+ *      contexts, a member listed twice or already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works.
+ *      LAYERED members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are layered and n_hidden,
+ *      hidden_sizes[] and force_layered agree (a mix of fused and layered members, either order: "layered"; of widths or depths:
+ *      "one network shape"; layered CVPO contexts are refused as CVPO contexts).  Each update is then the launch sequence of the
+ *      member's own layered fsrl_sac_update (9 L + 19 launches for L hidden layers, whatever k is) with every launch carrying all
+ *      members that still have updates to run, and a member's grouped update is bit-identical to its own at every k and batch size. */
 typedef struct fsrl_sac_group fsrl_sac_group;
 int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group** out);   /* 1 <= k <= 16, members not owned */
 int fsrl_sac_group_destroy(fsrl_sac_group* g);
@@ -646,9 +651,16 @@ int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t
  *      read-only queries: own updates, fsrl_sac_put_params, fsrl_sac_group_update / fsrl_cvpo_group_update, own
  *      fsrl_collect_step / fsrl_actor_sample), by fsrl_collect_group_actor_release, and by its idle timeout; the next step
  *      launches it again.
+ *      LAYERED SAC-Lag / DDPG-Lag members (all members layered, one n_hidden / hidden_sizes[] / force_layered) have no resident
+ *      kernel: a request is one launch sequence on the group's stream for all members -- the observation rows side by side in
+ *      pinned memory, L + 1 linear launches with one job per member that has rows, one launch that leaves the raw head rows and
+ *      completion words in pinned memory -- L + 2 launches per vector step instead of k (L + 2), any row count per member.  The
+ *      releases listed above mark such a group instead of ending a kernel: its next request first waits for everything the
+ *      members have enqueued on their compute streams; requests between two releases are ordered by the group's stream alone.
  *      create rejects with FSRL_EINVAL and the reason in fsrl_last_error: on-policy contexts (fsrl_group_create is theirs),
- *      layered contexts (no fused actor network), contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds, another device or
- *      network shape (obs_dim, act_dim, hidden), a member listed twice or already in a collect group, k outside 1..16.
+ *      layered CVPO contexts, a mix of fused and layered contexts, contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds,
+ *      another device or network shape (obs_dim, act_dim, hidden; layered: hidden_sizes[], force_layered), a member listed twice or
+ *      already in a collect group, k outside 1..16.
  *      A member destroyed before its group breaks it: later steps fail with FSRL_ESTATE, fsrl_collect_group_destroy still works. */
 typedef struct fsrl_collect_group fsrl_collect_group;
 int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collect_group** out);
@@ -662,11 +674,13 @@ int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, const int32
                             const float* obs_next, int64_t* ptr_out, double* ep_rew_out, int32_t* ep_len_out, int64_t* ep_idx_out,
                             const int32_t* k_act, const float* obs_act, int32_t deterministic, int32_t bound_method,
                             const float* act_low, const float* act_high, float* act_out, float* env_act_out);
-/* on = 0: no resident kernel; idle_timeout_us > 0 sets the idle timeout (default 2000, at most 1e6).  Ends a live kernel.     */
+/* on = 0: no resident kernel; idle_timeout_us > 0 sets the idle timeout (default 2000, at most 1e6).  Ends a live kernel.
+ * A group of layered members accepts the call and ignores it.                                                                  */
 int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us);
-/* out3 = {kernel launches, requests served through the doorbell, 1 if the kernel is live now}                                 */
+/* out3 = {kernel launches, requests served through the doorbell, 1 if the kernel is live now}; a group of layered members:
+ * {requests, requests, 0}                                                                                                      */
 int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3);
-/* the collect is over: end the kernel now instead of at its idle timeout                                                      */
+/* the collect is over: end the kernel now instead of at its idle timeout (a group of layered members: nothing to end)         */
 int fsrl_collect_group_actor_release(fsrl_collect_group* g);
 
 /* ---- timing of the last update, measured with hipEvents on the compute stream --------- */

@@ -14,7 +14,11 @@ Modes: seq_ungrouped (each member's own FastCollector with its own resident acto
 launches per collect; the loop is lock-step collection + round(0.2 * n/st) updates per seed through SACPolicyGroup / CVPOPolicyGroup
 (DDPG-Lag: each seed's own updates, one seed after the other).
 
-    python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3]
+--hidden 256x256x256 (--algo sacl | ddpgl): layered members.  Their collect group has no resident kernel: a lock-step vector step is
+one launch sequence (L + 2 launches) for all members against k (L + 2) member by member, and launches_per_collect counts requests.
+With --hidden the DDPG-Lag loop updates through DDPGPolicyGroup as the SAC-Lag loop does through SACPolicyGroup.
+
+    python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3] [--hidden 256x256x256]
 """
 import argparse
 import json
@@ -28,7 +32,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _agents(k, envs, first_seed, device, algo="ppol"):
+def _agents(k, envs, first_seed, device, algo="ppol", hidden=None):
     from fsrl_amd.agent import CVPOAgent, DDPGLagAgent, PPOLagAgent, SACLagAgent
     Agent = {"ppol": PPOLagAgent, "sacl": SACLagAgent, "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}[algo]
     from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
@@ -38,7 +42,7 @@ def _agents(k, envs, first_seed, device, algo="ppol"):
     for s in range(first_seed, first_seed + k):
         env = SyntheticSafetyVectorEnv(env_num=envs, obs_dim=8, act_dim=2, episode_len=300, seed=s)
         ag = Agent(env, BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_bgc{s}_"), name=f"s{s}"), cost_limit=10.0, device=device,
-                   seed=s, hidden_sizes=(256, 256), training_num=envs)
+                   seed=s, hidden_sizes=hidden or (256, 256), training_num=envs)
         ag.policy.train()
         buf = HipVectorReplayBuffer(ag.policy.engine, None, envs)
         agents.append(ag); bufs.append(buf); cols.append(FastCollector(ag.policy, env, buf, exploration_noise=True, device_actor=True))
@@ -73,12 +77,12 @@ def _replay(a):
     """--algo sacl / ddpgl / cvpo: the collect group of the replay agents"""
     from fsrl_amd.data import GroupCollector
     from fsrl_amd.engine import EngineCollectGroup
-    from fsrl_amd.policy import CVPOPolicyGroup, SACPolicyGroup
+    from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
     n_ep = a.envs
-    res = {"algo": a.algo, "envs": a.envs, "hidden": 256, "rounds": a.rounds, "k": {}}
+    res = {"algo": a.algo, "envs": a.envs, "hidden": "x".join(str(w) for w in a.hidden) if a.hidden else 256, "rounds": a.rounds, "k": {}}
     for k in [int(x) for x in a.ks.split(",")]:
-        solo_agents, solo_cols, _ = _agents(k, a.envs, 0, a.device, a.algo)
-        grp_agents, grp_cols, grp_bufs = _agents(k, a.envs, 0, a.device, a.algo)
+        solo_agents, solo_cols, _ = _agents(k, a.envs, 0, a.device, a.algo, a.hidden)
+        grp_agents, grp_cols, grp_bufs = _agents(k, a.envs, 0, a.device, a.algo, a.hidden)
         cg = EngineCollectGroup([ag.policy.engine for ag in grp_agents])
         gc = GroupCollector(cg, grp_cols)
         t = {"seq_ungrouped": [], "lockstep": []}
@@ -110,7 +114,8 @@ def _replay(a):
         cg.actor_release()
         out["group_call_over_member_call"] = round(out["us_group_call"] / out["us_member_call"], 3)
         # collect + update, the training loop's shape (examples/train_multi_seed.py --grouped): update_per_step 0.2
-        group = None if a.algo == "ddpgl" else (CVPOPolicyGroup if a.algo == "cvpo" else SACPolicyGroup)([ag.policy for ag in grp_agents])
+        group_cls = {"sacl": SACPolicyGroup, "cvpo": CVPOPolicyGroup, "ddpgl": DDPGPolicyGroup if a.hidden else None}[a.algo]
+        group = group_cls([ag.policy for ag in grp_agents]) if group_cls else None
         steps, updates = 0, 0
         t0 = time.perf_counter()
         for _ in range(2):
@@ -150,7 +155,10 @@ def main():
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
+                    help="--algo sacl | ddpgl: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
     a = ap.parse_args()
+    assert a.hidden is None or a.algo in ("sacl", "ddpgl"), "--hidden: the replay agents' layered collect groups (--algo sacl | ddpgl)"
     if a.algo != "ppol":
         return _replay(a)
     from fsrl_amd.data import GroupCollector

@@ -6,7 +6,12 @@ members), one context alone, and k contexts with one host thread each (train_mul
 
 Shapes: default = the reference's sacl_cfg.py (obs 8, act 2, 128 x 128, batch 256, n_step 2); configs3 = BASELINE configs[3]
 (obs 33, act 8, 256 x 256, batch 1024, 1 M-row stores).  --algo ddpgl: the same two shapes with sac_init(deterministic=True)
-engines (the default shape is also the reference's ddpgl_cfg.py)."""
+engines (the default shape is also the reference's ddpgl_cfg.py).
+--hidden 256x256x256: the shapes' hidden layers replaced by these (anything but two layers of at most 256 units: LAYERED members,
+whose grouped update is the layered launch sequence with every member in each launch, bit-identical per member to its own update).
+
+    python tools/bench_group_sac.py --hidden 256x256x256 --shapes default --repeats 3
+    python tools/bench_group_sac.py --algo ddpgl --hidden 64x48x32 --shapes default --repeats 3"""
 import argparse
 import json
 import os
@@ -24,12 +29,12 @@ SHAPES = {
 }
 
 
-def _engine(sh, seed, algo="sacl"):
+def _engine(sh, seed, algo="sacl", hidden=None):
     import torch
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
     E = sh["env_num"]
-    eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=sh["obs"], act_dim=sh["act"], hidden_sizes=(sh["H"], sh["H"]),
+    eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=sh["obs"], act_dim=sh["act"], hidden_sizes=hidden or (sh["H"], sh["H"]),
                               n_critics=2, env_num=E, buffer_size=sh["rows"], gamma=0.99, target_kl=None))
     if algo == "ddpgl":
         eng.sac_init(deterministic=True, n_step=sh["n_step"])
@@ -57,11 +62,11 @@ def _sync(engs):
         e.sac_get_params(0)
 
 
-def run(shape, k, mode, updates, algo="sacl"):
+def run(shape, k, mode, updates, algo="sacl", hidden=None):
     from fsrl_amd.engine import EngineSacGroup
     sh = SHAPES[shape]
     B = sh["B"]
-    engs = [_engine(sh, 10 + i, algo) for i in range(1 if mode == "solo" else k)]
+    engs = [_engine(sh, 10 + i, algo, hidden) for i in range(1 if mode == "solo" else k)]
     per_call = 50
     if mode == "grouped":
         g = EngineSacGroup(engs)
@@ -102,7 +107,7 @@ def run(shape, k, mode, updates, algo="sacl"):
         total = updates * len(engs)
     for e in engs:
         e.close()
-    return dict(algo=algo, shape=shape, k=k, mode=mode, batch=B, hidden=sh["H"], updates=total, seconds=round(dt, 4),
+    return dict(algo=algo, shape=shape, k=k, mode=mode, batch=B, hidden="x".join(str(w) for w in hidden) if hidden else sh["H"], updates=total, seconds=round(dt, 4),
                 updates_per_s=round(total / dt, 1), us_per_member_update=round(dt / total * 1e6, 2))
 
 
@@ -114,6 +119,8 @@ def main():
     ap.add_argument("--modes", default="grouped,solo,threaded")
     ap.add_argument("--updates", type=int, default=200, help="updates per member (grouped / threaded) or for the single context")
     ap.add_argument("--repeats", type=int, default=1, help="alternate the modes this many times on the same box")
+    ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
+                    help="hidden layers instead of the shape's, e.g. 256x256x256 or 64x48x32 (layered members)")
     a = ap.parse_args()
     ks = [int(x) for x in a.ks.split(",")]
     for shape in a.shapes.split(","):
@@ -122,7 +129,7 @@ def main():
                 for mode in a.modes.split(","):
                     if mode == "solo" and k != ks[0]:
                         continue                            # one context alone: measured once per shape
-                    print(json.dumps(run(shape, k, mode, a.updates, a.algo)), flush=True)
+                    print(json.dumps(run(shape, k, mode, a.updates, a.algo, a.hidden)), flush=True)
 
 
 if __name__ == "__main__":
