@@ -566,6 +566,12 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     const int Hpad_ = layered ? 0 : std::max(h1_, h2_) <= 64 ? 64 : std::max(h1_, h2_) <= 128 ? 128 : 256;
     CHECK_ARG(layered || n_hid1 == 0 || cfg->hidden == 0 || cfg->hidden == Hpad_ ,
               "hidden = %d does not fit hidden1 / hidden2 = %d / %d (leave hidden 0 or give %d)", cfg->hidden, h1_, h2_, Hpad_);
+    // a layered on-policy step writes every weight gradient in ONE launch with per-workgroup squared-norm slots (lay_wgrad,
+    // host_layered.inc): its job table -- every Linear of the actor and the critics, + sigma_param -- has to fit LAY_MAX_JOBS
+    CHECK_ARG(!layered || cfg->n_critics < 1 || cfg->n_critics > FSRL_MAX_CRITICS ||
+                  (1 + cfg->n_critics) * (cfg->n_hidden + 1) + 1 <= LAY_MAX_JOBS,
+              "layered context: (1 + n_critics) * (n_hidden + 1) + 1 = %d weight-gradient jobs exceed the job table of %d "
+              "(n_critics = %d, n_hidden = %d)", (1 + cfg->n_critics) * (cfg->n_hidden + 1) + 1, LAY_MAX_JOBS, cfg->n_critics, cfg->n_hidden);
     CHECK_ARG(cfg->n_critics >= 1 && cfg->n_critics <= 2,
               "n_critics must be 1 or 2 (reward [+ one cost], get_metrics base_policy.py:377-382)");
     CHECK_ARG(cfg->env_num >= 1 && cfg->buffer_size >= cfg->env_num, "bad env_num/buffer_size");

@@ -303,15 +303,41 @@ static int lay_bwd_dz(fsrl_ctx* c, int rows, int net0 = 0, int ny = -1) { return
 // output tile too few
 // k-version: any LayWork; Xn: one input matrix per network (the replay agents' Q-networks all read [obs | act], the API allows
 // different ones); rop_state: the R-operator buffers (on-policy actor only); split_stride > 0: split-K partials that far apart.
+// The job table holds LAY_MAX_JOBS entries and a network is L + 1 jobs (+ sigma_param): four Q-networks of eight hidden layers
+// (SAC-Lag, CVPO with double_critic) are 36.  So the jobs go out in launches of WHOLE networks, as many as fit the table.  Every
+// job writes its own slice of `out` from its own operands, one accumulator per element over ascending batch rows whichever
+// launch carries it: the split moves no result.  A launch with squared-norm slots or a fixed grid (the on-policy step: slots
+// numbered by workgroup of ONE launch) is never split -- fsrl_ctx_create refuses an on-policy context whose table would not fit.
+static_assert(FSRL_MAX_HIDDEN + 2 <= LAY_MAX_JOBS, "one network's weight-side jobs (every Linear + sigma_param) fit one launch");
+static_assert(FSRL_MAX_NETS <= LAY_MAX_JOBS, "lay_fwd_k / lay_bwd_dz_k: one job per network in a launch");
 static int lay_wgrad_k(fsrl_ctx* c, LayWork& k, const float* X, const float* const* Xn, int rows, int net0, int ny, float* out,
                        float* gsq, LayState* rs, int split_stride, int* gparts_out, const dim3* grid_fixed) {
     const LayModel& lm = k.lm;
     const int L = k.L;
+    CHECK_ARG(net0 >= 0 && ny >= 1 && net0 + ny <= lm.n_nets && ny <= FSRL_MAX_NETS, "weight-side launch: networks %d .. %d of %d",
+              net0, net0 + ny - 1, lm.n_nets);
     LinJobs jobs{};
+    int gp = 1;
+    if (split_stride > 0) {
+        const int ks = std::max(1, std::min(LAY_KSPLIT_MAX, (rows + 1023) / 1024));
+        jobs.ksplit = ks; jobs.kchunk = round_up((rows + ks - 1) / ks, 64); jobs.part_stride = split_stride;
+        gp = ks;
+    }
+    if (gparts_out) *gparts_out = gp;
     int nj = 0;
     for (int y = 0; y < ny; ++y) {
         const int net = net0 + y;
         const float* X0 = Xn ? Xn[y] : X;
+        const int need = L + 1 + (lm.net[net].sigma >= 0 ? 1 : 0);
+        CHECK_ARG(need <= LAY_MAX_JOBS, "too many weight-side jobs: %d for one network (limit %d)", need, LAY_MAX_JOBS);
+        if (nj + need > LAY_MAX_JOBS) {     // the table is full: launch the networks gathered so far
+            CHECK_ARG(!gsq && !grid_fixed, "too many weight-side jobs for one launch with squared-norm slots (limit %d)", LAY_MAX_JOBS);
+            jobs.n = nj;
+            int rc = lay_launch<LIN_W>(c, jobs, nullptr, c->compute, nullptr);
+            if (rc) return rc;
+            for (int j = 0; j < nj; ++j) jobs.j[j] = LinJob{};
+            nj = 0;
+        }
         for (int l = 0; l <= L; ++l) {
             const LayLayer& ll = lm.net[net].l[l];
             LinJob& jb = jobs.j[nj++];
@@ -335,13 +361,6 @@ static int lay_wgrad_k(fsrl_ctx* c, LayWork& k, const float* X, const float* con
         }
     }
     jobs.n = nj;
-    int gp = 1;
-    if (split_stride > 0) {
-        const int ks = std::max(1, std::min(LAY_KSPLIT_MAX, (rows + 1023) / 1024));
-        jobs.ksplit = ks; jobs.kchunk = round_up((rows + ks - 1) / ks, 64); jobs.part_stride = split_stride;
-        gp = ks;
-    }
-    if (gparts_out) *gparts_out = gp;
     return lay_launch<LIN_W>(c, jobs, gsq, c->compute, grid_fixed);
 }
 // the on-policy context's own networks.  rop: the R-operator form of the actor's products, R{dW_l} = R{dz_l}^T a_{l-1} +

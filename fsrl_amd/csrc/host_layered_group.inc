@@ -222,9 +222,11 @@ static int lay_group_step(LayGroup& lg, fsrl_ctx* const* m, int k, hipStream_t s
 // shared by the on-policy group below and the replay agents' collect group (host_sac_group_layered.inc): `net` is the actor
 // network's layers, P(i) member i's parameter vector of it, `cols` the floats per answered row in pinned memory, and
 // tail(outb, pin, maxk) the last launch, which leaves the answer and the completion words there.
+static_assert(GACTOR_MAX_MEMBERS <= LAY_MAX_JOBS, "lay_group_collect_stage: one inference job per member in a launch's table");
 template <class ParamOf, class Tail>
 static int lay_group_collect_stage(LayGroup& lg, GaRing& ga, fsrl_ctx* c0, const LayNet& net, int Do, int hmax, int k, int cols,
                                    const int32_t* k_act, const float* obs_act, ParamOf&& P, Tail&& tail) {
+    CHECK_ARG(k >= 1 && k <= LAY_MAX_JOBS, "too many members for one inference launch (limit %d)", LAY_MAX_JOBS);
     const int L = net.nl - 1;
     const size_t hm = (size_t)round_up(hmax, 4);
     hipStream_t s = ga.stream;

@@ -91,8 +91,15 @@ typedef struct fsrl_config {
                                 LAYERED context (every algorithm): the same entry points (store, collector actor,
                                 fsrl_ppo_* / fsrl_tr_* / fsrl_sac_* / fsrl_cvpo_*, parameters, snapshot, lr), the same float64 scans and logged rows, but the network
                                 math runs one MFMA GEMM launch per Linear (2 L + 5 launches per minibatch step instead of 3)
-                                on activations kept in HBM.  Grouped updates and fsrl_launch_floors refuse such a
-                                context with FSRL_EINVAL.                                                   */
+                                on activations kept in HBM.  Grouped PPO-Lag, SAC-Lag and DDPG-Lag updates and their lock-step
+                                collection take layered members (all members of one `hidden_sizes`); grouped FOCOPS and CVPO
+                                updates and fsrl_launch_floors refuse a layered context with FSRL_EINVAL.
+                                Limits, as enforced: the replay agents (fsrl_sac_* / fsrl_cvpo_*) run every depth 1 ..
+                                FSRL_MAX_HIDDEN with two or four Q-networks -- a weight-side job table larger than one launch
+                                holds (32 jobs; four Q-networks of eight layers are 36) goes out in launches of whole
+                                networks, bit-identical to one launch.  An on-policy step needs its table in ONE launch:
+                                fsrl_ctx_create refuses (1 + n_critics) * (n_hidden + 1) + 1 > 32 with FSRL_EINVAL; with
+                                n_critics <= 2, the present limit, every depth up to FSRL_MAX_HIDDEN fits (28 jobs).  */
     int32_t hidden_sizes[FSRL_MAX_HIDDEN];
     int32_t force_layered;   /* tests: run a two-layer network of at most 256 units through the layered kernels as well   */
 } fsrl_config;

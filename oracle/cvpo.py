@@ -82,16 +82,18 @@ def single_critic_spec(Do, Da, hidden):
 
 
 class CVPOOracle:
-    def __init__(self, cfg: CVPOConfig):
+    def __init__(self, cfg: CVPOConfig, dtype=torch.float32):
+        """dtype: the precision of every tensor of the update (torch.float64: the yardstick the fp32 run is measured against)"""
         self.cfg = cfg
+        self.dtype = dtype
         self.aspec = actor_spec(cfg.obs_dim, cfg.act_dim, cfg.hidden)
         self.cspec = (double_critic_spec if cfg.double_critic else single_critic_spec)(cfg.obs_dim, cfg.act_dim,
                                                                                        cfg.hidden)
         self.n_q = 2 if cfg.double_critic else 1
 
     def set_params(self, actor_flat, critics_flat):
-        a = torch.as_tensor(np.asarray(actor_flat, np.float32))
-        c = torch.as_tensor(np.asarray(critics_flat, np.float32))
+        a = torch.as_tensor(np.asarray(actor_flat, np.float32)).to(self.dtype)
+        c = torch.as_tensor(np.asarray(critics_flat, np.float32)).to(self.dtype)
         self.actor, _ = _leaves(a, self.aspec, 0)
         self.actor_old = OrderedDict((k, v.detach().clone()) for k, v in self.actor.items())
         self.critics, self.critics_old, off = [], [], 0
@@ -101,14 +103,14 @@ class CVPOOracle:
             self.critics_old.append(OrderedDict((k, v.detach().clone()) for k, v in leaves.items()))
         self.actor_optim = torch.optim.Adam(list(self.actor.values()), lr=self.cfg.actor_lr)
         self.critic_optim = torch.optim.Adam([p for cr in self.critics for p in cr.values()], lr=self.cfg.critic_lr)
-        self.estep_dual = torch.tensor([1.0, 0.0], requires_grad=True)            # cvpo.py:150-155
+        self.estep_dual = torch.tensor([1.0, 0.0], dtype=self.dtype, requires_grad=True)            # cvpo.py:150-155
         self.estep_optim = torch.optim.Adam([self.estep_dual], lr=self.cfg.estep_dual_lr)
         self.pre_update()
 
     def pre_update(self):
         """cvpo.py:178-188: fresh M-step duals and optimiser at every collect cycle."""
-        self.mstep_dual_mu = torch.zeros(1, requires_grad=True)
-        self.mstep_dual_std = torch.zeros(1, requires_grad=True)
+        self.mstep_dual_mu = torch.zeros(1, dtype=self.dtype, requires_grad=True)
+        self.mstep_dual_std = torch.zeros(1, dtype=self.dtype, requires_grad=True)
         self.mstep_optim = torch.optim.Adam([self.mstep_dual_mu, self.mstep_dual_std], lr=self.cfg.mstep_dual_lr)
 
     def post_update(self):
@@ -157,7 +159,7 @@ class CVPOOracle:
         """One CVPO.update: process_fn + learn.  store: dict of SLOT-indexed arrays."""
         cfg = self.cfg
         B, K = len(indices), cfg.sample_act_num
-        t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
+        t = lambda a: torch.as_tensor(np.asarray(a), dtype=self.dtype)  # noqa: E731
         # ---- n-step returns (float64)
         chain = [np.asarray(indices)]
         for _ in range(cfg.n_step - 1):
@@ -177,7 +179,7 @@ class CVPOOracle:
         for i in range(2):
             tq = targets[i].reshape(B, -1).numpy() * value_mask
             rets.append(torch.from_numpy(nstep_return_np(metrics[i], end_flag, tq, chain, cfg.gamma,
-                                                         cfg.n_step)).to(torch.float32))
+                                                         cfg.n_step)).to(self.dtype))
         rets = torch.stack(rets, -1)
         obs, act = t(store["obs"][indices]), t(store["act"][indices])
         stats = {}

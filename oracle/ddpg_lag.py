@@ -59,16 +59,18 @@ def mlp(p, x):
 
 
 class DDPGLagOracle:
-    def __init__(self, cfg: DDPGConfig):
+    def __init__(self, cfg: DDPGConfig, dtype=torch.float32):
+        """dtype: the precision of every tensor of the update (torch.float64: the yardstick the fp32 run is measured against)"""
         self.cfg = cfg
+        self.dtype = dtype
         self.aspec = mlp_spec(cfg.obs_dim, cfg.act_dim, cfg.hidden)
         self.cspec = mlp_spec(cfg.obs_dim + cfg.act_dim, 1, cfg.hidden)
         self.n_actor = sum(int(np.prod(s)) for s in self.aspec.values())
         self.n_critic = sum(int(np.prod(s)) for s in self.cspec.values())
 
     def set_params(self, actor_flat, critics_flat):
-        a = torch.as_tensor(np.asarray(actor_flat, np.float32))
-        c = torch.as_tensor(np.asarray(critics_flat, np.float32))
+        a = torch.as_tensor(np.asarray(actor_flat, np.float32)).to(self.dtype)
+        c = torch.as_tensor(np.asarray(critics_flat, np.float32)).to(self.dtype)
         self.actor, _ = _leaves(a, self.aspec, 0)
         self.actor_old = OrderedDict((k, v.detach().clone()) for k, v in self.actor.items())
         self.critics, self.critics_old, off = [], [], 0
@@ -95,7 +97,7 @@ class DDPGLagOracle:
     def update(self, store, index, indices, lagrangians, rescaling):
         cfg = self.cfg
         B = len(indices)
-        t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
+        t = lambda a: torch.as_tensor(np.asarray(a), dtype=self.dtype)  # noqa: E731
         chain = [np.asarray(indices)]
         for _ in range(cfg.n_step - 1):
             chain.append(index.next(chain[-1]))
@@ -113,7 +115,7 @@ class DDPGLagOracle:
         for i in range(2):
             tq = targets[i].reshape(B, -1).numpy() * value_mask
             rets.append(torch.from_numpy(nstep_return_np(metrics[i], end_flag, tq, chain, cfg.gamma, cfg.n_step)).to(
-                torch.float32))
+                self.dtype))
         obs, act = t(store["obs"][indices]), t(store["act"][indices])
         x = torch.cat([obs, act], 1)
         stats_c, loss_c = {}, 0

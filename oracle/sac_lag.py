@@ -123,8 +123,10 @@ class ReplayIndex:
 
 
 class SACLagOracle:
-    def __init__(self, cfg: SACConfig):
+    def __init__(self, cfg: SACConfig, dtype=torch.float32):
+        """dtype: the precision of every tensor of the update (torch.float64: the yardstick the fp32 run is measured against)"""
         self.cfg = cfg
+        self.dtype = dtype
         self.aspec = actor_spec(cfg.obs_dim, cfg.act_dim, cfg.hidden)
         self.cspec = double_critic_spec(cfg.obs_dim, cfg.act_dim, cfg.hidden)
         self.n_actor = sum(int(np.prod(s)) for s in self.aspec.values())
@@ -132,8 +134,8 @@ class SACLagOracle:
         self.target_entropy = cfg.target_entropy if cfg.target_entropy is not None else -float(cfg.act_dim)
 
     def set_params(self, actor_flat, critics_flat, log_alpha=0.0):
-        a = torch.as_tensor(np.asarray(actor_flat, np.float32))
-        c = torch.as_tensor(np.asarray(critics_flat, np.float32))
+        a = torch.as_tensor(np.asarray(actor_flat, np.float32)).to(self.dtype)
+        c = torch.as_tensor(np.asarray(critics_flat, np.float32)).to(self.dtype)
         self.actor, _ = _leaves(a, self.aspec, 0)
         self.critics, self.critics_old, off = [], [], 0
         for _ in range(2):
@@ -144,7 +146,7 @@ class SACLagOracle:
         self.actor_optim = torch.optim.Adam(list(self.actor.values()), lr=self.cfg.actor_lr)
         self.critic_optim = torch.optim.Adam([p for cr in self.critics for p in cr.values()],
                                              lr=self.cfg.critic_lr)
-        self.log_alpha = torch.full((1, ), float(log_alpha), requires_grad=True)
+        self.log_alpha = torch.full((1, ), float(log_alpha), dtype=self.dtype, requires_grad=True)
         self.alpha_optim = torch.optim.Adam([self.log_alpha], lr=self.cfg.alpha_lr)
         self.alpha = self.log_alpha.detach().exp() if self.cfg.auto_alpha else self.cfg.alpha
 
@@ -183,7 +185,7 @@ class SACLagOracle:
         """store: dict of SLOT-indexed arrays obs, act, rew, cost, terminated, obs_next."""
         cfg = self.cfg
         B = len(indices)
-        t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
+        t = lambda a: torch.as_tensor(np.asarray(a), dtype=self.dtype)  # noqa: E731
         # ---- n-step index chain and returns (float64)
         chain = [np.asarray(indices)]
         for _ in range(cfg.n_step - 1):
@@ -205,7 +207,7 @@ class SACLagOracle:
         for i in range(2):
             tq = targets[i].reshape(B, -1).numpy() * value_mask
             rets.append(torch.from_numpy(nstep_return_np(metrics[i], end_flag, tq, chain, cfg.gamma,
-                                                         cfg.n_step)).to(torch.float32))
+                                                         cfg.n_step)).to(self.dtype))
         rets = torch.stack(rets, -1)                                   # [B, 1, 2]
         obs, act = t(store["obs"][indices]), t(store["act"][indices])
         # ---- critics

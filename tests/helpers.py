@@ -243,3 +243,37 @@ def sac_wrapped_case(name):
     assert np.array_equal(rollout_checksum(steps), g["rollout_checksum"]), "numpy's generators no longer reproduce the fixture's rollout"
     g["steps"] = [(ids, obs, np.tanh(act), rew, cost, term, trunc, nxt) for ids, obs, act, rew, cost, term, trunc, nxt in steps]
     return g
+
+
+def replay_problem(rng, engines, rows, obs_dim, act_dim, act_of, sub=128):
+    """A random replay store for the SAC-Lag / DDPG-Lag / CVPO variant tests, pushed in lock step (env e gets rows[e] rows, the
+    envs drop out as they run dry) into every engine of `engines` and mirrored into SLOT-indexed arrays for the oracles.
+    act_of: standard normal draws [k, act_dim] -> the stored actions (tanh, scaled tanh, clip).  The draws of a step come in the
+    order obs, act, rew, cost, terminated, obs_next.  -> (store dict, oracle.sac_lag.ReplayIndex, the valid slots)"""
+    from oracle.sac_lag import ReplayIndex
+    E = len(rows)
+    store = {k: np.zeros((E * sub, ) + s, d) for k, s, d in (("obs", (obs_dim, ), np.float32), ("obs_next", (obs_dim, ), np.float32),
+             ("act", (act_dim, ), np.float32), ("rew", (), np.float64), ("cost", (), np.float64),
+             ("terminated", (), bool), ("truncated", (), bool))}
+    for t in range(max(rows)):
+        ids = [e for e in range(E) if t < rows[e]]
+        k = len(ids)
+        row = dict(obs=rng.standard_normal((k, obs_dim)).astype(np.float32),
+                   act=act_of(rng.standard_normal((k, act_dim))).astype(np.float32), rew=rng.normal(0, 1, k),
+                   cost=(rng.random(k) < 0.3).astype(np.float64), terminated=rng.random(k) < 0.1,
+                   truncated=np.full(k, t % 11 == 10), obs_next=rng.standard_normal((k, obs_dim)).astype(np.float32))
+        for eng in engines:
+            eng.push(ids, row["obs"], row["act"], row["rew"], row["cost"], row["terminated"], row["truncated"], row["obs_next"])
+        for e, j in zip(ids, range(k)):
+            for key in store:
+                store[key][e * sub + t] = row[key][j]
+    index = ReplayIndex(rows, sub, store["terminated"] | store["truncated"])
+    valid = np.concatenate([e * sub + np.arange(r) for e, r in enumerate(rows)])
+    return store, index, valid
+
+
+def fan_in_params(rng, spec):
+    """A flat parameter vector over `spec` (name -> shape, torch parameters() order): W ~ N(0, 1 / fan_in), b ~ 0.1 N(0, 1) -- the
+    heads stay off the tails of tanh at any depth and width"""
+    return np.concatenate([(rng.standard_normal(shp) / np.sqrt(shp[1]) if len(shp) == 2 else 0.1 * rng.standard_normal(shp)).ravel()
+                           for shp in spec.values()]).astype(np.float32)

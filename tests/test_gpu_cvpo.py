@@ -187,8 +187,8 @@ def test_cvpo_variants_vs_oracle(Do, Da, H, rows, B, K, n_step, double, eit, mit
     """Shapes and options outside the golden set, checked against the (pinned) oracle on the same random problem."""
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
+    from helpers import replay_problem
     from oracle.cvpo import CVPOConfig, CVPOOracle
-    from oracle.sac_lag import ReplayIndex
     rng = np.random.default_rng(Do + 10 * Da)
     E, sub = len(rows), 128
     hs = (H, H) if isinstance(H, int) else tuple(H)
@@ -204,22 +204,7 @@ def test_cvpo_variants_vs_oracle(Do, Da, H, rows, B, K, n_step, double, eit, mit
     tha = (0.2 * rng.standard_normal(n_a)).astype(np.float32)
     thc = (0.2 * rng.standard_normal(2 * n_c)).astype(np.float32)
     o.set_params(tha, thc); eng.sac_set_params(tha, thc, 0.0)
-    store = {k: np.zeros((E * sub, ) + s, d) for k, s, d in (("obs", (Do, ), np.float32), ("obs_next", (Do, ), np.float32),
-             ("act", (Da, ), np.float32), ("rew", (), np.float64), ("cost", (), np.float64),
-             ("terminated", (), bool), ("truncated", (), bool))}
-    for t in range(max(rows)):
-        ids = [e for e in range(E) if t < rows[e]]
-        k = len(ids)
-        row = dict(obs=rng.standard_normal((k, Do)).astype(np.float32),
-                   act=np.clip(rng.standard_normal((k, Da)), -amax, amax).astype(np.float32), rew=rng.normal(0, 1, k),
-                   cost=(rng.random(k) < 0.3).astype(np.float64), terminated=rng.random(k) < 0.1,
-                   truncated=np.full(k, t % 11 == 10), obs_next=rng.standard_normal((k, Do)).astype(np.float32))
-        eng.push(ids, row["obs"], row["act"], row["rew"], row["cost"], row["terminated"], row["truncated"], row["obs_next"])
-        for e, j in zip(ids, range(k)):
-            for key in store:
-                store[key][e * sub + t] = row[key][j]
-    index = ReplayIndex(rows, sub, store["terminated"] | store["truncated"])
-    valid = np.concatenate([e * sub + np.arange(r) for e, r in enumerate(rows)])
+    store, index, valid = replay_problem(rng, [eng], rows, Do, Da, lambda z: np.clip(z, -amax, amax), sub)
     keys = ["loss/estep_loss", "estep/dual0", "estep/dual1", "mstep/mstep_kl_mu", "mstep/mstep_kl_std", "mstep/mstep_loss_kl",
             "mstep/mstep_loss_mle", "mstep/mstep_loss_total", "mstep/mstep_dual_mu", "mstep/mstep_dual_std", "mstep/entropy",
             "loss/loss_q0", "estep/val_q0", "loss/loss_q1", "estep/val_q1", "estep/thres_q1", "loss/q_total"]

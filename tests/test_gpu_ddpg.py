@@ -67,8 +67,8 @@ def _synthetic_engine(Do, Da, hidden, rows, n_step, use_lag, max_action, seed, s
     """A DDPG-Lag context and the oracle on the same random replay store (fan-in scaled parameters: the heads stay off tanh's tails)."""
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
+    from helpers import fan_in_params as init, replay_problem
     from oracle.ddpg_lag import DDPGConfig, DDPGLagOracle
-    from oracle.sac_lag import ReplayIndex
     rng = np.random.default_rng(seed)
     E = len(rows)
     hs = (hidden, hidden) if isinstance(hidden, int) else tuple(hidden)
@@ -78,28 +78,9 @@ def _synthetic_engine(Do, Da, hidden, rows, n_step, use_lag, max_action, seed, s
                               buffer_size=E * sub, gamma=0.98, max_action=max_action, target_kl=None))
     eng.sac_init(actor_lr=1e-3, critic_lr=1e-3, tau=0.1, n_step=n_step, use_lagrangian=use_lag, deterministic=True)
     o = DDPGLagOracle(ocfg)
-
-    def init(spec):
-        return np.concatenate([(rng.standard_normal(shp) / np.sqrt(shp[1]) if len(shp) == 2 else 0.1 * rng.standard_normal(shp)).ravel()
-                               for shp in spec.values()]).astype(np.float32)
-    tha, thc = init(o.aspec), np.concatenate([init(o.cspec), init(o.cspec)])
+    tha, thc = init(rng, o.aspec), np.concatenate([init(rng, o.cspec), init(rng, o.cspec)])
     o.set_params(tha, thc); eng.sac_set_params(tha, thc, 0.0)
-    store = {k: np.zeros((E * sub, ) + s, d) for k, s, d in (("obs", (Do, ), np.float32), ("obs_next", (Do, ), np.float32),
-             ("act", (Da, ), np.float32), ("rew", (), np.float64), ("cost", (), np.float64),
-             ("terminated", (), bool), ("truncated", (), bool))}
-    for t in range(max(rows)):
-        ids = [e for e in range(E) if t < rows[e]]
-        k = len(ids)
-        row = dict(obs=rng.standard_normal((k, Do)).astype(np.float32),
-                   act=(max_action * np.tanh(rng.standard_normal((k, Da)))).astype(np.float32), rew=rng.normal(0, 1, k),
-                   cost=(rng.random(k) < 0.3).astype(np.float64), terminated=rng.random(k) < 0.1,
-                   truncated=np.full(k, t % 11 == 10), obs_next=rng.standard_normal((k, Do)).astype(np.float32))
-        eng.push(ids, row["obs"], row["act"], row["rew"], row["cost"], row["terminated"], row["truncated"], row["obs_next"])
-        for e, j in zip(ids, range(k)):
-            for key in store:
-                store[key][e * sub + t] = row[key][j]
-    index = ReplayIndex(rows, sub, store["terminated"] | store["truncated"])
-    valid = np.concatenate([e * sub + np.arange(r) for e, r in enumerate(rows)])
+    store, index, valid = replay_problem(rng, [eng], rows, Do, Da, lambda z: max_action * np.tanh(z), sub)
     return eng, o, store, index, valid, rng
 
 

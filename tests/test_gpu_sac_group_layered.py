@@ -93,6 +93,9 @@ CASES = {
     "sacl-wide1": dict(hs=(320, ), Do=8, Da=2, B=272, k=2, n=[4, 4], use_lag=False),
     # a two-layer network through the layered kernels
     "sacl-forced": dict(hs=(64, 64), Do=8, Da=2, B=64, k=2, n=[3, 3], force=True),
+    # eight hidden layers: the solo twin's 36 weight-side jobs of the four Q-networks exceed the 32-entry job table of a launch and go
+    # out as two launches of whole networks (lay_wgrad_k); the group's table is in device memory, one launch
+    "sacl-eight-k2": dict(hs=(24, 17, 32, 9, 40, 4, 28, 12), Do=20, Da=8, B=64, k=2, n=[3, 2]),
     # 16-wide deterministic head, the target actor's Polyak update
     "ddpgl-deep3": dict(hs=(64, 48, 32), Do=20, Da=16, B=64, k=3, n=[4, 0, 2], kind="ddpgl", n_step=1),
     "ddpgl-ragged-k8": dict(hs=(50, 30), Do=8, Da=2, B=20, k=8, n=N8, kind="ddpgl", use_lag=False),

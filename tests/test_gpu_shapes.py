@@ -155,7 +155,8 @@ SAC_VARIANTS = [  # Do, Da, H, rows per env, batch, n_step, auto_alpha, use_lagr
 def test_sac_variants_vs_oracle(Do, Da, H, rows, B, n_step, auto_alpha, use_lag):
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
-    from oracle.sac_lag import ReplayIndex, SACConfig, SACLagOracle
+    from helpers import replay_problem
+    from oracle.sac_lag import SACConfig, SACLagOracle
     rng = np.random.default_rng(Do + 10 * Da)
     E, sub = len(rows), 128
     eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden=H, n_critics=2, env_num=E,
@@ -166,21 +167,7 @@ def test_sac_variants_vs_oracle(Do, Da, H, rows, B, n_step, auto_alpha, use_lag)
     tha = (0.2 * rng.standard_normal(o.n_actor)).astype(np.float32)
     thc = (0.2 * rng.standard_normal(2 * o.n_critic)).astype(np.float32)
     o.set_params(tha, thc, -0.5); eng.sac_set_params(tha, thc, -0.5)
-    store = {k: np.zeros((E * sub, ) + s, d) for k, s, d in (("obs", (Do, ), np.float32), ("obs_next", (Do, ), np.float32),
-             ("act", (Da, ), np.float32), ("rew", (), np.float64), ("cost", (), np.float64),
-             ("terminated", (), bool), ("truncated", (), bool))}
-    for t in range(max(rows)):
-        ids = [e for e in range(E) if t < rows[e]]
-        k = len(ids)
-        row = dict(obs=rng.standard_normal((k, Do)).astype(np.float32), act=np.tanh(rng.standard_normal((k, Da))).astype(np.float32),
-                   rew=rng.normal(0, 1, k), cost=(rng.random(k) < 0.3).astype(np.float64), terminated=rng.random(k) < 0.1,
-                   truncated=np.full(k, t % 11 == 10), obs_next=rng.standard_normal((k, Do)).astype(np.float32))
-        eng.push(ids, row["obs"], row["act"], row["rew"], row["cost"], row["terminated"], row["truncated"], row["obs_next"])
-        for e, j in zip(ids, range(k)):
-            for key in store:
-                store[key][e * sub + t] = row[key][j]
-    index = ReplayIndex(rows, sub, store["terminated"] | store["truncated"])
-    valid = np.concatenate([e * sub + np.arange(r) for e, r in enumerate(rows)])
+    store, index, valid = replay_problem(rng, [eng], rows, Do, Da, np.tanh, sub)
     lag = [0.3] if use_lag else []
     for u in range(3):
         idx = rng.choice(valid, B)

@@ -85,3 +85,17 @@ def test_split_ranges_of_the_full_batch_weight_side_cover_every_row_once():
         if sizes[-1] == 0:
             empty.append(rows)
     assert 16385 in one_row and 19457 in one_row and 24600 in empty          # the sizes the GPU cases use do occur
+
+
+def test_an_on_policy_job_table_that_does_not_fit_one_launch_is_refused_at_create():
+    """The layered on-policy step writes every weight gradient in one launch of at most 32 jobs, (1 + n_critics) * (n_hidden + 1)
+    + 1 of them (include/fsrl_hip.h, fsrl_config.n_hidden): fsrl_ctx_create refuses a larger table with FSRL_EINVAL and names the
+    limit -- before it looks for a device, so this runs anywhere.  n_critics = 4 with eight layers is 46 jobs, n_critics = 3 with
+    seven is 33; where the table fits, the older limit on n_critics answers."""
+    from fsrl_amd.engine import Engine, EngineConfig
+    for n_critics, depth, jobs in ((4, 8, 46), (3, 7, 33), (4, 6, 36)):
+        with pytest.raises(AssertionError, match=f"= {jobs} weight-gradient jobs exceed the job table of 32"):
+            Engine(EngineConfig(obs_dim=6, act_dim=2, hidden_sizes=(8, ) * depth, n_critics=n_critics, env_num=2))
+    for n_critics, depth in ((3, 6), (4, 5)):            # 29 and 31 jobs
+        with pytest.raises(AssertionError, match="n_critics must be 1 or 2"):
+            Engine(EngineConfig(obs_dim=6, act_dim=2, hidden_sizes=(8, ) * depth, n_critics=n_critics, env_num=2))
