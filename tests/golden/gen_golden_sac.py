@@ -32,8 +32,12 @@ def flat(mods):
 
 def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates, seed, n_step=2,
         cost_stat=25.0, cost_limit=10.0, auto_alpha=True, alpha=0.005, tau=0.05, actor_lr=5e-4,
-        critic_lr=1e-3, alpha_lr=3e-4, gamma=0.99, buffer_size=None, full=False, wrapped=False):
-    """wrapped: ep_lens holds one episode plan PER ENV and buffer_size is smaller than the rollout, so the sub-buffers are
+        critic_lr=1e-3, alpha_lr=3e-4, gamma=0.99, buffer_size=None, full=False, wrapped=False, clamp_cols=None):
+    """clamp_cols = (up, lo): after initialisation the sigma head's bias of action column `up` is set so that the upper clamp (2) lies
+    in the widest gap around the median of the stored rows' raw log sigma (no row within 1e-3 relative of it: asserted), and that of column `lo` to -25 (every row below the lower clamp); the noise rsample draws
+    for column `up` is scaled by 0.05 (the recorded draws are the scaled ones), the mean head's row and bias of column `lo` are 0
+    and its noise is 0.
+    wrapped: ep_lens holds one episode plan PER ENV and buffer_size is smaller than the rollout, so the sub-buffers are
     overwritten with different write heads; the rollout is stored as seed + checksum (tests/helpers.sac_wrapped_case replays it,
     last write wins), the parameters in full.
     full: a BASELINE-size case -- the rollout (tests/helpers.synth_rollout) and the initial parameters (synth_theta) are
@@ -113,6 +117,26 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
     buf._meta["act"][:] = np.tanh(buf._meta["act"])
     meta = buf._meta
     used = np.concatenate([np.arange(o, o + len(b)) for o, b in zip(buf._offset, buf.buffers)])
+    if clamp_cols is not None:
+        up, lo = clamp_cols
+        with torch.no_grad():
+            bias = list(actor.sigma.parameters())[-1]
+            logits, _ = actor.preprocess(torch.as_tensor(meta["obs"][used]))
+            nxt = actor.preprocess(torch.as_tensor(meta["obs_next"][used]))[0]
+            raw = torch.cat([actor.sigma(logits), actor.sigma(nxt)])[:, up].sort().values      # every row an update can meet: s_t and s_t+n
+            lo_q, hi_q = int(0.4 * len(raw)), int(0.6 * len(raw))
+            j = lo_q + int((raw[lo_q + 1:hi_q + 1] - raw[lo_q:hi_q]).argmax())                   # the widest gap between the 40 % and 60 % quantiles:
+            bias[up] += 2.0 - 0.5 * (raw[j] + raw[j + 1])                                       # the clamp goes into its middle
+            bias[lo] = -25.0
+            for q in actor.mu.parameters():     # sigma = e^-20 under a non-zero mean: (u - mu) cancels to 0 or an ulp of mu in float32,
+                q[lo] = 0.0                     # an error of many sigma in any implementation -- that column's mean is exactly 0
+            raw = torch.cat([actor.sigma(logits), actor.sigma(nxt)])
+        share = float((raw[:, up] > 2).float().mean())
+        margin = float((raw[:, up] / 2.0 - 1.0).abs().min())       # no stored row within 1e-3 (relative) of the clamp: a row inside float32
+        assert 0.3 < share < 0.7 and margin >= 1e-3, (share, margin)   # rounding of it could take either side of the mask in two implementations
+        assert bool((raw[:, lo] < -20 * (1 + 1e-3)).all()), float(raw[:, lo].max())
+        print(f"clamped: column {up} above the clamp on {share:.0%} of the stored rows, nearest row {margin:.1e} (relative) from it")
+        out["clamp_cols"] = np.array(clamp_cols)
     if wrapped:
         out.update(theta_actor0=flat([actor]), theta_critics0=flat(critics))
     elif not full:
@@ -138,6 +162,10 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, n_updates,
 
     def rec_sn(shape, dtype, device):
         e = orig_sn(shape, dtype, device)
+        if clamp_cols is not None:        # sigma = e^2 on standard normal noise throws u = mu + sigma e into the transition band of tanh,
+            e[..., clamp_cols[0]] *= 0.05  # where 1 - tanh(u)^2 is ill-conditioned in any float32 implementation: that column's noise is scaled
+            e[..., clamp_cols[1]] = 0.0    # sigma = e^-20: autograd sends -+(u - mu) / sigma^2 = 5e8 eps through u and mu, which absorbs the Q
+            #                                gradient on the way (float32 sum) before it cancels: the reference's gradient of that mean is 0 or noise
         eps_log.append(e.numpy().copy())
         return e
 
@@ -189,6 +217,11 @@ if __name__ == "__main__":
         # 2.15 times, three different write heads; env 1 ends on a finished episode, envs 0 and 2 on unfinished tails), n_step 3
         gen("wrapped", 6, 3, (64, 64), 3, [[40, 35, -25], [50, 43], [30, 30, 20, -6]], batch_size=64, n_updates=5, seed=38,
             n_step=3, buffer_size=120, wrapped=True)
+        sys.exit(0)
+    if sys.argv[1:] == ["clamped"]:
+        # the sigma head on its clamps: column 0 straddles log sigma = 2 over the stored rows, column 2 sits below -20; one update
+        gen("clamped", 6, 3, (64, 64), 3, [[40, 30], [45, -20], [35, 25]], batch_size=64, n_updates=1, seed=39, n_step=2,
+            clamp_cols=(0, 2))
         sys.exit(0)
     if sys.argv[1:] == ["widths"]:
         # two hidden layers of different widths that are not 64 / 128 / 256 (zero-padded on the device)

@@ -277,3 +277,59 @@ def fan_in_params(rng, spec):
     heads stay off the tails of tanh at any depth and width"""
     return np.concatenate([(rng.standard_normal(shp) / np.sqrt(shp[1]) if len(shp) == 2 else 0.1 * rng.standard_normal(shp)).ravel()
                            for shp in spec.values()]).astype(np.float32)
+
+
+# ---- the replay agents' oracle runs (tests/test_gpu_layered_replay.py, tests/branch_problems.py): a case is a dict with Do, Da, hidden,
+# and the options n_step, auto_alpha, use_lag (SAC-Lag), K, double (CVPO)
+SAC_KEYS = ["loss/rescaling", "loss/lagrangian", "loss/actor_safety", "loss/alpha_loss", "loss/alpha_value",
+            "loss/actor_rew", "loss/actor_total", "loss/q0", "loss/q1", "loss/q_total"]
+CVPO_KEYS = ["loss/estep_loss", "estep/dual0", "estep/dual1", "mstep/mstep_kl_mu", "mstep/mstep_kl_std", "mstep/mstep_loss_kl",
+             "mstep/mstep_loss_mle", "mstep/mstep_loss_total", "mstep/mstep_dual_mu", "mstep/mstep_dual_std", "mstep/entropy",
+             "loss/loss_q0", "estep/val_q0", "loss/loss_q1", "estep/val_q1", "estep/thres_q1", "loss/q_total"]
+ROW_BAR = {"sac": (1e-4, 1e-5), "ddpg": (1e-4, 1e-5), "cvpo": (2e-4, 2e-5)}          # rel, abs
+VEC_BAR = {"sac": (5e-6, 3e-3), "ddpg": (5e-6, 3e-3), "cvpo": (1e-5, 5e-3)}          # q99, max
+
+
+def replay_cvpo_cfg(c):
+    from oracle.cvpo import CVPOConfig
+    return CVPOConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), max_action=1.0, gamma=0.97, n_step=2, tau=0.1,
+                      double_critic=c.get("double", False), sample_act_num=c["K"], estep_iter_num=1, mstep_iter_num=1, cost_limit=0.5,
+                      max_episode_steps=50, mstep_kl_mu=1e-4, mstep_kl_std=1e-5, actor_lr=1e-3)
+
+
+def replay_oracles(kind, c):
+    """the fp32 oracle and its float64 twin"""
+    import torch
+    if kind == "sac":
+        from oracle.sac_lag import SACConfig, SACLagOracle
+        cfg = SACConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), gamma=0.98, n_step=c.get("n_step", 2), tau=0.1,
+                        alpha=0.05, auto_alpha=c.get("auto_alpha", True), use_lagrangian=c.get("use_lag", True))
+        return SACLagOracle(cfg), SACLagOracle(cfg, dtype=torch.float64)
+    if kind == "ddpg":
+        from oracle.ddpg_lag import DDPGConfig, DDPGLagOracle
+        cfg = DDPGConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), max_action=1.0, gamma=0.98, n_step=2, tau=0.1,
+                         actor_lr=1e-3, critic_lr=1e-3, use_lagrangian=True)
+        return DDPGLagOracle(cfg), DDPGLagOracle(cfg, dtype=torch.float64)
+    from oracle.cvpo import CVPOOracle
+    return CVPOOracle(replay_cvpo_cfg(c)), CVPOOracle(replay_cvpo_cfg(c), dtype=torch.float64)
+
+
+def replay_vectors(kind, o):
+    v = {"actor": o.actor_flat(), "critics": o.critics_flat(), "critics_old": o.critics_flat(old=True)}
+    if kind != "sac":
+        v["actor_old"] = o.actor_flat(old=True)
+    return v
+
+
+def replay_row_items(kind, row):
+    """(key, value) of a logged row -- an oracle's dict or a device row (CVPO: with the duals)"""
+    keys = CVPO_KEYS if kind == "cvpo" else SAC_KEYS
+    if isinstance(row, dict):
+        items = [(k, float(row[k])) for k in keys if k in row]
+        duals = row.get("duals")
+    else:
+        st, duals = row if kind == "cvpo" else (row, None)
+        items = [(k, float(st[j])) for j, k in enumerate(keys)]
+    if duals is not None:
+        items += [(f"duals[{j}]", float(d)) for j, d in enumerate(duals)]
+    return dict(items)

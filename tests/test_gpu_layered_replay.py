@@ -61,18 +61,15 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import fan_in_params, replay_problem
+from helpers import (CVPO_KEYS, ROW_BAR, SAC_KEYS, VEC_BAR, fan_in_params, replay_problem)  # noqa: F401
+from helpers import replay_cvpo_cfg as _cvpo_cfg
+from helpers import replay_oracles as _oracles
+from helpers import replay_row_items as _row_items
+from helpers import replay_vectors as _vectors
 
 pytestmark = pytest.mark.gpu
 
 EIGHT = (24, 17, 32, 9, 40, 4, 28, 12)       # FSRL_MAX_HIDDEN ragged layers: one below a float4, one of 4, none a multiple of 16 twice
-SAC_KEYS = ["loss/rescaling", "loss/lagrangian", "loss/actor_safety", "loss/alpha_loss", "loss/alpha_value",
-            "loss/actor_rew", "loss/actor_total", "loss/q0", "loss/q1", "loss/q_total"]
-CVPO_KEYS = ["loss/estep_loss", "estep/dual0", "estep/dual1", "mstep/mstep_kl_mu", "mstep/mstep_kl_std", "mstep/mstep_loss_kl",
-             "mstep/mstep_loss_mle", "mstep/mstep_loss_total", "mstep/mstep_dual_mu", "mstep/mstep_dual_std", "mstep/entropy",
-             "loss/loss_q0", "estep/val_q0", "loss/loss_q1", "estep/val_q1", "estep/thres_q1", "loss/q_total"]
-ROW_BAR = {"sac": (1e-4, 1e-5), "ddpg": (1e-4, 1e-5), "cvpo": (2e-4, 2e-5)}          # rel, abs
-VEC_BAR = {"sac": (5e-6, 3e-3), "ddpg": (5e-6, 3e-3), "cvpo": (1e-5, 5e-3)}          # q99, max
 SUB = 256                                     # rows of a sub-buffer
 
 # B: one batch size, or the three of the `regrow` cases.  Defaults: n_step 2, learned alpha, Lagrangian term, data seed 0.
@@ -136,36 +133,6 @@ def _engine(kind, c, force=None):
         eng.cvpo_init(_cvpo_cfg(c).qc_thres, actor_lr=1e-3, tau=0.1, n_step=2, double_critic=c.get("double", False),
                       sample_act_num=c["K"], estep_iter_num=1, mstep_iter_num=1, mstep_kl_mu=1e-4, mstep_kl_std=1e-5)
     return eng
-
-
-def _cvpo_cfg(c):
-    from oracle.cvpo import CVPOConfig
-    return CVPOConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), max_action=1.0, gamma=0.97, n_step=2, tau=0.1,
-                      double_critic=c.get("double", False), sample_act_num=c["K"], estep_iter_num=1, mstep_iter_num=1, cost_limit=0.5,
-                      max_episode_steps=50, mstep_kl_mu=1e-4, mstep_kl_std=1e-5, actor_lr=1e-3)
-
-
-def _oracles(kind, c):
-    """the fp32 oracle and its float64 twin"""
-    if kind == "sac":
-        from oracle.sac_lag import SACConfig, SACLagOracle
-        cfg = SACConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), gamma=0.98, n_step=c.get("n_step", 2), tau=0.1,
-                        alpha=0.05, auto_alpha=c.get("auto_alpha", True), use_lagrangian=c.get("use_lag", True))
-        return SACLagOracle(cfg), SACLagOracle(cfg, dtype=torch.float64)
-    if kind == "ddpg":
-        from oracle.ddpg_lag import DDPGConfig, DDPGLagOracle
-        cfg = DDPGConfig(obs_dim=c["Do"], act_dim=c["Da"], hidden=tuple(c["hidden"]), max_action=1.0, gamma=0.98, n_step=2, tau=0.1,
-                         actor_lr=1e-3, critic_lr=1e-3, use_lagrangian=True)
-        return DDPGLagOracle(cfg), DDPGLagOracle(cfg, dtype=torch.float64)
-    from oracle.cvpo import CVPOOracle
-    return CVPOOracle(_cvpo_cfg(c)), CVPOOracle(_cvpo_cfg(c), dtype=torch.float64)
-
-
-def _vectors(kind, o):
-    v = {"actor": o.actor_flat(), "critics": o.critics_flat(), "critics_old": o.critics_flat(old=True)}
-    if kind != "sac":
-        v["actor_old"] = o.actor_flat(old=True)
-    return v
 
 
 WHICH = {"actor": 0, "critics": 1, "critics_old": 2, "actor_old": 3}
@@ -237,20 +204,6 @@ def run_case(kind, name, engines=()):
             v["alpha"] = e.sac_get_params(0)[1]
         final.append(v)
     return c, rows, final
-
-
-def _row_items(kind, row):
-    """(key, value) of a logged row -- an oracle's dict or a device row (CVPO: with the duals)"""
-    keys = CVPO_KEYS if kind == "cvpo" else SAC_KEYS
-    if isinstance(row, dict):
-        items = [(k, float(row[k])) for k in keys if k in row]
-        duals = row.get("duals")
-    else:
-        st, duals = row if kind == "cvpo" else (row, None)
-        items = [(k, float(st[j])) for j, k in enumerate(keys)]
-    if duals is not None:
-        items += [(f"duals[{j}]", float(d)) for j, d in enumerate(duals)]
-    return dict(items)
 
 
 def row_figures(kind, a, b, y):

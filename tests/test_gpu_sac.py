@@ -40,7 +40,8 @@ def _engine(cfg, g):
 @pytest.mark.parametrize("splitk", [0, 1])      # weight gradients: 0 = one workgroup per output tile (batches <= 512 rows), 1 = split-K
 # deep3, wide1: layered contexts; c4full: BASELINE configs[3]'s shape at batch 1024 from the unmodified reference (r5)
 # wrapped: sub-buffers overwritten ~2.5 times with three different write heads, n_step 3, recorded from the unmodified reference
-@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped"])
+# clamped: the sigma head on its clamps (one column straddles log sigma = 2, one sits below -20), one update of the unmodified reference
+@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped", "clamped"])
 def test_sac_updates_vs_golden(name, splitk):
     g, cfg, ocfg, store, index = sac_setup(name)
     eng = _engine(cfg, g)

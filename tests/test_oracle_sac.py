@@ -39,7 +39,8 @@ def old_final(g, flat_old):
     return flat_old[::8] if flat_old.size != g["theta_critics_old_final"].size else flat_old
 
 
-@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped"])
+# clamped: the sigma head on its clamps (one column straddles log sigma = 2 over the stored rows, one sits below -20), one update
+@pytest.mark.parametrize("name", ["small", "nstep3", "c4", "widths", "deep3", "wide1", "c4full", "wrapped", "clamped"])
 def test_sac_updates(name):
     torch.set_num_threads(4)
     g, cfg, ocfg, store, index = sac_setup(name)
