@@ -25,6 +25,7 @@
 #include "kernels_wgrad3.hpp"
 #include "kernels_layered.hpp"
 #include "kernels_focops_group.hpp"
+#include "resident_ring.hpp"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -176,12 +177,10 @@ struct fsrl_ctx {
     unsigned* h_done = nullptr; int done_cap = 0;        // pinned per-block completion words of that evaluation
     unsigned actor_seq = 0; int actor_blocks = 0;
     // r6: the collector's actor as a RESIDENT workgroup (actor_resident_kernel: one launch per collect instead of one per vector step)
-    bool pa_on = true;              // fsrl_actor_set_resident
-    bool pa_live = false;           // a kernel of generation pa_gen was launched and not told to end
+    ResidentRing pa;                // protocol state and counters (resident_ring.hpp): one member, base 0; its stream is `compute`
     bool pa_req = false;            // the evaluation in flight went to the resident kernel (actor_eval_finish)
-    unsigned pa_gen = 0, pa_seq = 0; int pa_cap = 0, pa_blocks = 1; double pa_idle_us = 2000.0;
+    int pa_cap = 0;
     void* h_pa = nullptr;           // pinned: [bell 8 B | pad | done[4] at 16 | state[4] at 32 | pad to 64 B | obs cap x Do | mu cap x Da | sigma_param]
-    long long pa_launches = 0, pa_requests = 0;          // fsrl_actor_resident_stats
     // timing-probe switches: always 0 / false in the shipped library; a -DFSRL_PROBES build reads them ONCE, at
     // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_TILE16 / FSRL_WGRAD_SKIP / FSRL_NO_SPIN (tools/phase_probe.sh)
     int probe_phase = 0, probe_wgrad_skip = 0;
@@ -1025,13 +1024,8 @@ static int sac_raw_cols(const fsrl_ctx* c);                                     
 static bool sac_squashes(fsrl_ctx* c);
 static bool sac_actor_resident_args(fsrl_ctx* c, const float** P, const ModelDesc** md);   // false: no fused actor (layered / not initialised)
 
-// ---- the resident actor (actor_resident_kernel, kernels_mlp.hpp).  Protocol, host side:
-//   post:    [wait until every workgroup of every earlier generation has reported its end] -> launch generation g if none is live ->
-//            write the k observations -> ring the doorbell (k << 32 | seq, one release store);
-//   finish:  spin on `done[b] == seq` of the request's tiles; if a `state[b] == g` shows up instead (a workgroup ended by its idle
-//            timeout just before the doorbell), tell the rest to end, wait for them, launch generation g + 1 and ring again;
-//   release: doorbell = EXIT; nothing is waited for (the stream orders what follows behind the kernel).
-// A doorbell is only ever rung when generation pa_gen is the one kernel that can hear it.
+// ---- the resident actor (actor_resident_kernel, kernels_mlp.hpp).  The protocol is resident_ring.hpp's; here: the pinned layout,
+//      the launch and the stream of a context's own kernel.
 struct PaLayout { unsigned long long* bell; unsigned* done; unsigned* state; float* obs; float* mu; float* sp; };
 static PaLayout pa_layout(const fsrl_ctx* c) {
     char* b = (char*)c->h_pa;
@@ -1045,121 +1039,81 @@ static PaLayout pa_layout(const fsrl_ctx* c) {
 
 static bool pactor_ok(const fsrl_ctx* c, int k) {
     const int blocks = std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
-    if (!(c->pa_on && !c->no_spin && !c->lay && !c->group && k >= 1 && k <= 16 * blocks)) return false;
+    if (!(c->pa.on && !c->no_spin && !c->lay && !c->group && k >= 1 && k <= 16 * blocks)) return false;
     if (c->cfg.algo != FSRL_ALGO_SAC_LAG) return true;
     const float* P; const ModelDesc* md;
     return sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md);      // replay contexts: their fused actor network
 }
 
-// the context's own resident kernel only
-static void pactor_release_own(fsrl_ctx* c) {
-    if (!c->pa_live) return;
-    const PaLayout l = pa_layout(c);
-    c->pa_seq += 1;
-    __atomic_store_n(l.bell, ((unsigned long long)PACTOR_EXIT << 32) | c->pa_seq, __ATOMIC_RELEASE);
-    c->pa_live = false;
-}
-
 static void pactor_release(fsrl_ctx* c) {
     if (c->group) group_actor_release(c->group);      // a grouped member enqueues on the group's stream: its collect kernel ends too
     if (c->cgroup) collect_group_actor_release(c->cgroup);   // a collect group's kernel holds this member's actor weights in registers
-    pactor_release_own(c);
+    rr_release(c->pa);
 }
 
-// how many workgroups of generation pa_gen have ended
-static int pactor_ended_count(const fsrl_ctx* c) {
-    const PaLayout l = pa_layout(c);
-    int n = 0;
-    for (int b = 0; b < c->pa_blocks; ++b) n += __atomic_load_n(l.state + b, __ATOMIC_ACQUIRE) == c->pa_gen;
-    return n;
+// ResidentRing::query of every HIP owner: hipStreamQuery on the kernel's stream, the error text through fail()
+static int stream_state(hipStream_t s) {
+    const hipError_t e = hipStreamQuery(s);
+    if (e == hipSuccess || e == hipErrorNotReady) return e == hipSuccess ? RR_STREAM_IDLE : RR_STREAM_BUSY;
+    fail(FSRL_EHIP, "the resident actor's stream: %s", hipGetErrorString(e));
+    return RR_STREAM_ERROR;
+}
+// a ring function's code as the library's (a launch hook's error and its text pass through)
+static int rr_code(int rc, const char* what) {
+    if (rc <= 0) return rc;
+    if (rc == RR_ERROR) return FSRL_EHIP;       // stream_state has recorded the text
+    if (rc == RR_BAD_TIMEOUT) return fail(FSRL_EINVAL, "idle_timeout_us above one second");
+    return fail(FSRL_EHIP, "%s does not answer", what);
 }
 
-// generation pa_gen has ended (true at once if none was ever launched); waits for a kernel that was told to end, never for a live one
-static bool pactor_ended(fsrl_ctx* c, bool wait) {
-    if (c->pa_gen == 0) return true;
-    for (long spins = 0;; ++spins) {
-        if (pactor_ended_count(c) == c->pa_blocks) return true;
-        if (!wait) return false;
-        if (spins > 4000000) { (void)hipStreamSynchronize(c->compute); return pactor_ended_count(c) == c->pa_blocks; }
-        __builtin_ia32_pause();
-    }
-}
-
-static int pactor_launch(fsrl_ctx* c, unsigned last_seq) {
+// ResidentRing::launch of a context's own kernel.  Its stream is c->compute at the time of the request (joining an fsrl_group swaps
+// that stream; pactor_ok keeps grouped and layered members off this path).
+static int pactor_launch(void* owner, ResidentRing& r, unsigned last_seq) {
+    fsrl_ctx* c = (fsrl_ctx*)owner;
     const PaLayout l = pa_layout(c);
     PActorArgs a{};
     a.obs = l.obs; a.mu_out = l.mu; a.sigma_param_out = l.sp; a.bell = l.bell; a.done = l.done; a.state = l.state;
-    c->pa_gen += 1;
-    if (c->pa_gen == 0) c->pa_gen = 1;
-    a.gen = c->pa_gen; a.last_seq = last_seq; a.max_action = c->cfg.max_action;
-    a.timeout_ticks = (unsigned long long)(c->pa_idle_us * 100.0);            // wall_clock64: 100 MHz
-    c->pa_blocks = std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
+    a.gen = r.gen; a.last_seq = last_seq; a.max_action = c->cfg.max_action;
+    a.timeout_ticks = (unsigned long long)(r.idle_us * 100.0);                // wall_clock64: 100 MHz
+    r.blocks = r.tiles[0] = std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
     const float* P = c->P; const ModelDesc* md = &c->md;
     if (c->cfg.algo == FSRL_ALGO_SAC_LAG) {                                    // the replay agents' actor: raw head outputs, as sac_actor_launch
         if (!sac_actor_resident_args(c, &P, &md)) return fail(FSRL_ESTATE, "no fused actor network");
         a.raw_cols = sac_raw_cols(c); a.max_action = 1.0f;
     }
     const ModelDesc mdv = *md;
-    const int rc = dispatch_H(c->cfg.hidden, [&](auto hc) {
+    return dispatch_H(c->cfg.hidden, [&](auto hc) {
         constexpr int H = decltype(hc)::value;
-        if (a.raw_cols > 0) hipLaunchKernelGGL((actor_resident_kernel<H, true>), dim3(c->pa_blocks), dim3(4 * H), 0, c->compute, P, mdv, a);
-        else hipLaunchKernelGGL((actor_resident_kernel<H, false>), dim3(c->pa_blocks), dim3(4 * H), 0, c->compute, P, mdv, a);
+        if (a.raw_cols > 0) hipLaunchKernelGGL((actor_resident_kernel<H, true>), dim3(r.blocks), dim3(4 * H), 0, c->compute, P, mdv, a);
+        else hipLaunchKernelGGL((actor_resident_kernel<H, false>), dim3(r.blocks), dim3(4 * H), 0, c->compute, P, mdv, a);
         HIPCHK(hipGetLastError());
         return 0;
     });
-    if (rc) return rc;
-    c->pa_live = true; c->pa_launches += 1;
-    return 0;
 }
 
-// ring the doorbell for the k rows already in place (launching a kernel first if none can hear it)
-static int pactor_ring(fsrl_ctx* c, int k) {
-    const PaLayout l = pa_layout(c);
-    if (c->pa_live && pactor_ended_count(c) > 0) pactor_release(c);          // (some of) it ended by its idle timeout: the rest follows
-    c->pa_seq += 1;
-    if (!c->pa_live) {
-        if (!pactor_ended(c, true)) return fail(FSRL_EHIP, "the resident actor did not end");
-        const int rc = pactor_launch(c, c->pa_seq - 1);
-        if (rc) return rc;
-    }
-    __atomic_store_n(l.bell, ((unsigned long long)(unsigned)k << 32) | c->pa_seq, __ATOMIC_RELEASE);
-    return 0;
-}
-
+// On a partial end (a workgroup ended by its idle timeout) the ring releases ITSELF only, where this path once went through the whole
+// pactor_release: no group kernel can be live then -- pactor_ok refuses grouped members, and actor_eval_launch has released a
+// collect group's kernel before it gets here -- so that is the same.
 static int pactor_post(fsrl_ctx* c, const float* obs, int k) {
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim;
+    ResidentRing& r = c->pa;
     if (!c->h_pa) {
         c->pa_cap = 16 * PACTOR_BLOCKS;
         const size_t bytes = 64 + ((size_t)c->pa_cap * (Do + 2 * Da) + FSRL_MAX_ACT) * 4;
         HIPCHK(hipHostMalloc(&c->h_pa, bytes));
         memset(c->h_pa, 0, bytes);
+        const PaLayout l = pa_layout(c);
+        r.bell = l.bell; r.done = l.done; r.state = l.state;
+        r.n = 1;
+        r.launch = pactor_launch; r.owner = c;
+        r.query = [](void* ctx) { return stream_state(((fsrl_ctx*)ctx)->compute); };
     }
     memcpy(pa_layout(c).obs, obs, (size_t)k * Do * 4);
-    const int rc = pactor_ring(c, k);
-    if (rc) return rc;
-    c->actor_k = k; c->pa_req = true; c->pa_requests += 1;
+    r.k[0] = k;
+    const int rc = rr_request(r, (unsigned)k);           // the kernel reads the row count in the command word
+    if (rc) return rr_code(rc, "the resident actor");
+    c->actor_k = k; c->pa_req = true;
     return 0;
-}
-
-static int pactor_wait(fsrl_ctx* c) {
-    const PaLayout l = pa_layout(c);
-    const int tiles = (c->actor_k + 15) / 16;
-    auto served = [&]() {
-        for (int b = 0; b < tiles; ++b)
-            if (__atomic_load_n(l.done + b, __ATOMIC_ACQUIRE) != c->pa_seq) return false;
-        return true;
-    };
-    for (long spins = 0;; ++spins) {
-        if (served()) return 0;
-        if ((spins & 255) == 255 && pactor_ended_count(c) > 0) {
-            // a workgroup is gone (idle timeout just before the doorbell) -- unless it served the request first
-            if (served()) return 0;
-            const int rc = pactor_ring(c, c->actor_k);
-            if (rc) return rc;
-        }
-        if (spins > 500000000L) return fail(FSRL_EHIP, "the resident actor does not answer");
-        __builtin_ia32_pause();
-    }
 }
 
 static int actor_eval_launch(fsrl_ctx* c, const float* obs, int32_t k, bool want_sigma) {
@@ -1213,8 +1167,8 @@ static int actor_eval_finish(fsrl_ctx* c, float* mu_out, float* sigma_out) {
     const int Da = c->cfg.act_dim, k = c->actor_k;
     if (c->pa_req) {                                    // served by the resident kernel
         c->pa_req = false;
-        const int rc = pactor_wait(c);
-        if (rc) return rc;
+        const int rc = rr_wait(c->pa);
+        if (rc) return rr_code(rc, "the resident actor");
         const PaLayout l = pa_layout(c);
         if (ctx_is_replay(c)) { sac_actor_finish(c, l.mu, k, mu_out, sigma_out); return 0; }
         memcpy(mu_out, l.mu, (size_t)k * Da * 4);

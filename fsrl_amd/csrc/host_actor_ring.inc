@@ -1,10 +1,11 @@
-// host_actor_ring.inc -- the pinned ring and the host half of the protocol of a resident actor kernel that serves SEVERAL contexts
-// from one launch and one doorbell (part of fsrl_hip.hip, before host_group.inc).  Two owners embed a GaRing: fsrl_group
-// (host_group_collect.inc: on-policy members, actor_group_resident_kernel<H, false>) and fsrl_collect_group
-// (host_collect_group.inc: replay members, actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on
-// and the launch itself; everything else -- post / ring / wait / release, generation and sequence numbers, the bounded wait, and the
-// lock-step collect step both owners' entry points run (ga_collect_step) -- is here.
-// Protocol as pactor_* (fsrl_hip.hip), with one doorbell for all members and a per-member row count k_m next to it.
+// host_actor_ring.inc -- the pinned ring of a resident actor kernel that serves SEVERAL contexts from one launch and one doorbell
+// (part of fsrl_hip.hip, before host_group.inc).  Two owners embed a GaRing: fsrl_group (host_group_collect.inc: on-policy members,
+// actor_group_resident_kernel<H, false>) and fsrl_collect_group (host_collect_group.inc: replay members,
+// actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on and the launch itself; the protocol --
+// request / wait / release, generation and sequence numbers, the bounded wait -- is resident_ring.hpp's, the one a context's own
+// kernel runs, with 1 in the command word and a per-member row count k_m next to the doorbell.  Here: the layout, the request's rows
+// and the lock-step collect step both owners' entry points run (ga_collect_step).
+static_assert(RR_MAX_MEMBERS == GACTOR_MAX_MEMBERS && RR_EXIT == PACTOR_EXIT, "resident_ring.hpp and kernels_mlp.hpp disagree");
 
 // pinned ring: [bell 8 B | pad | k_m[16] at 64 | done[64] at 128 | state[64] at 384 | pad | obs [64 * 16][Do] at 1024 |
 //               out [64 * 16][cols] | sigma_param [16][FSRL_MAX_ACT]]
@@ -13,20 +14,11 @@
 struct GaLayout { unsigned long long* bell; unsigned* k_m; unsigned* done; unsigned* state; float* obs; float* mu; float* sp; };
 static constexpr int GA_ROWS = GACTOR_MAX_WG * 16;
 
-struct GaRing {
-    bool on = true;                             // *_actor_set_resident
-    bool live = false;                          // a kernel of generation gen was launched and not told to end
-    unsigned gen = 0, seq = 0; double idle_us = 2000.0;
-    int n = 0;                                  // members
-    int blocks = 0;                             // workgroups of every launch: sum of tiles
+struct GaRing : ResidentRing {                  // ResidentRing::owner is the GaRing itself (ga_bind)
     int Do = 0, cols = 0;                       // observation width / floats per output row of the ring
-    int base[GACTOR_MAX_MEMBERS] = {}, tiles[GACTOR_MAX_MEMBERS] = {};   // member m: workgroups base[m] .. + tiles[m] - 1
-    int k[GACTOR_MAX_MEMBERS] = {};             // rows of each member in the request in flight
     void* h = nullptr;                          // pinned ring (GaLayout)
-    long long launches = 0, requests = 0;       // *_actor_resident_stats
-    hipStream_t stream = nullptr;               // the stream the kernel is launched on (the owner's)
-    int (*launch)(void* owner, GaRing& r, unsigned last_seq) = nullptr;   // launches generation r.gen on r.stream
-    void* owner = nullptr;
+    hipStream_t stream = nullptr;               // the stream the kernel is launched on (the group's)
+    void* group = nullptr;                      // the fsrl_group / fsrl_collect_group, for its launch hook
 };
 
 static GaLayout ga_layout(const GaRing& r) {
@@ -42,79 +34,10 @@ static size_t ga_bytes(int Do, int cols) {
     return 1024 + ((size_t)GA_ROWS * (Do + cols) + (size_t)GACTOR_MAX_MEMBERS * FSRL_MAX_ACT) * 4;
 }
 
-static void ga_release(GaRing& r) {
-    if (!r.live) return;
-    r.seq += 1;
-    __atomic_store_n(ga_layout(r).bell, ((unsigned long long)PACTOR_EXIT << 32) | r.seq, __ATOMIC_RELEASE);
-    r.live = false;
-}
-
-// how many workgroups of generation gen have ended
-static int gactor_ended_count(const GaRing& r) {
-    const GaLayout l = ga_layout(r);
-    int n = 0;
-    for (int b = 0; b < r.blocks; ++b) n += __atomic_load_n(l.state + b, __ATOMIC_ACQUIRE) == r.gen;
-    return n;
-}
-
-static double ga_now_us() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3;
-}
-
-// Bounded wait: `ready()` polled; every 2 ms without it the ring's stream is asked.  A HIP error there -> FSRL_EHIP; an idle stream
-// (every workgroup has ended, nothing else queued) -> 1; 20 s -> FSRL_EHIP.  0 once `ready()` holds.
-template <typename F>
-static int ga_poll(GaRing& r, F&& ready, const char* what) {
-    const double t0 = ga_now_us();
-    double next_query = t0 + 2000.0;
-    for (long spins = 0;; ++spins) {
-        if (ready()) return 0;
-        if ((spins & 255) == 255) {
-            const double t = ga_now_us();
-            if (t >= next_query) {
-                next_query = t + 2000.0;
-                const hipError_t e = hipStreamQuery(r.stream);
-                if (e == hipSuccess) return ready() ? 0 : 1;
-                if (e != hipErrorNotReady) return fail(FSRL_EHIP, "%s: %s", what, hipGetErrorString(e));
-            }
-            if (t - t0 > 20.0e6) return fail(FSRL_EHIP, "%s: no answer for 20 s", what);
-        }
-        __builtin_ia32_pause();
-    }
-}
-
-// generation gen has ended (at once if none was launched); it was told to end, so this waits for a kernel on its way out
-static int gactor_wait_ended(GaRing& r) {
-    if (r.gen == 0) return 0;
-    const int rc = ga_poll(r, [&]() { return gactor_ended_count(r) == r.blocks; }, "the group's resident actor did not end");
-    return rc == 1 ? 0 : rc;                    // an idle stream: the kernel is gone
-}
-
-// the next generation through the owner's launch: its number first, the bookkeeping after a launch that went out
-static int gactor_launch(GaRing& r, unsigned last_seq) {
-    r.gen += 1;
-    if (r.gen == 0) r.gen = 1;
-    const int rc = r.launch(r.owner, r, last_seq);
-    if (rc) return rc;
-    r.live = true; r.launches += 1;
-    return 0;
-}
-
-// ring the doorbell for the request already in place (launching a kernel first if none can hear it)
-static int gactor_ring(GaRing& r) {
-    const GaLayout l = ga_layout(r);
-    if (r.live && gactor_ended_count(r) > 0) ga_release(r);      // (some of) it ended by its idle timeout: the rest follows
-    r.seq += 1;
-    if (!r.live) {
-        int rc = gactor_wait_ended(r);
-        if (rc) return rc;
-        rc = gactor_launch(r, r.seq - 1);
-        if (rc) return rc;
-    }
-    __atomic_store_n(l.bell, ((unsigned long long)1 << 32) | r.seq, __ATOMIC_RELEASE);
-    return 0;
+// the group's stream, its launch hook (none: a group of layered contexts, which only waits through the ring) and the stream query
+static void ga_bind(GaRing& r, hipStream_t stream, int (*launch)(void*, ResidentRing&, unsigned), void* group) {
+    r.stream = stream; r.launch = launch; r.group = group; r.owner = &r;
+    r.query = [](void* ring) { return stream_state(((GaRing*)ring)->stream); };
 }
 
 // the ring and the workgroup layout: member m gets min(PACTOR_BLOCKS, ceil(env_num / 16)) tiles, as its own resident actor would
@@ -131,6 +54,8 @@ static int gactor_ensure(GaRing& r, fsrl_ctx* const* m, int n, int cols) {
         base += r.tiles[i];
     }
     r.blocks = base;
+    const GaLayout l = ga_layout(r);
+    r.bell = l.bell; r.done = l.done; r.state = l.state;
     return 0;
 }
 
@@ -159,48 +84,14 @@ static int gactor_post(GaRing& r, const int32_t* k_act, const float* obs_act) {
         r.k[i] = k;
         off += (size_t)k;
     }
-    const int rc = gactor_ring(r);
-    if (rc) return rc;
-    r.requests += 1;
-    return 0;
+    return rr_code(rr_request(r, 1u), "the group's resident actor");
 }
-
-static int gactor_wait(GaRing& r) {
-    const GaLayout l = ga_layout(r);
-    auto served = [&]() {
-        for (int i = 0; i < r.n; ++i) {
-            const int tiles = (r.k[i] + 15) / 16;
-            for (int t = 0; t < tiles; ++t)
-                if (__atomic_load_n(l.done + r.base[i] + t, __ATOMIC_ACQUIRE) != r.seq) return false;
-        }
-        return true;
-    };
-    for (;;) {
-        // a workgroup gone before it served the request (idle timeout just before the doorbell): end the rest, relaunch, ring again
-        const int rc = ga_poll(r, [&]() { return served() || gactor_ended_count(r) > 0; }, "the group's resident actor");
-        if (rc < 0 || rc > 1) return rc;
-        if (served()) return 0;
-        if (rc == 1) r.live = false;            // the stream is idle: every workgroup has ended
-        const int rr = gactor_ring(r);
-        if (rr) return rr;
-    }
-}
+static int gactor_wait(GaRing& r) { return rr_code(rr_wait(r), "the group's resident actor"); }
 
 // a member's row cap on the resident path: what its own resident actor serves
 static inline int gactor_member_rows(const fsrl_ctx* c) {
     return 16 * std::min(PACTOR_BLOCKS, std::max(1, (c->cfg.env_num + 15) / 16));
 }
-
-// *_actor_set_resident / *_actor_resident_stats of both owners
-static int ga_set_resident(GaRing& r, int32_t on, double idle_timeout_us) {
-    CHECK_ARG(idle_timeout_us <= 1.0e6, "idle_timeout_us above one second");
-    ga_release(r);
-    r.on = on != 0;
-    if (idle_timeout_us > 0.0) r.idle_us = idle_timeout_us;
-    return 0;
-}
-// out3 = {kernel launches, requests served through the doorbell, 1 if the resident kernel is live now}
-static void ga_stats(const GaRing& r, int64_t* out3) { out3[0] = r.launches; out3[1] = r.requests; out3[2] = r.live ? 1 : 0; }
 
 // ---- one lock-step collect step: fsrl_collect_step on every member, in member order, with one request to the ring's kernel.  Row
 //      arrays are concatenated over members; k[m] / k_act[m] may be 0; act_low / act_high: NULL or [members][act_dim].
@@ -241,7 +132,7 @@ static int ga_collect_step_via(GaRing& ga, fsrl_ctx* const* m, int n, int device
             rc = post();
             if (rc) return rc;
         } else {
-            ga_release(ga);
+            rr_release(ga);
             size_t off = 0;
             for (int i = 0; i < n; ++i) {
                 if (k_act[i] > 0) {

@@ -298,8 +298,10 @@ extern "C" int fsrl_collect_episodes_split(fsrl_ctx* c, fsrl_shm_env* env, const
     // counter the workers are still decrementing (the Python side marks the env broken as well)
     auto bail = [&](int code) {
         const std::string keep = g_err;
+        pactor_release(c);                                        // the resident actor ends here, not at its idle timeout
         for (int l = 0; l < 2; ++l)
             if (g[l].busy) { fsrl_env_wait_done(env->hs + (l * 3 + 1) * 16, 0u, 2000); g[l].busy = false; }
+        (void)hipStreamSynchronize(c->compute); (void)hipStreamSynchronize(c->side);       // as fsrl_collect_episodes' bail
         g_err = keep;
         return code;
     };
@@ -423,17 +425,14 @@ extern "C" int fsrl_collect_timing(fsrl_ctx* c, double* out2) {
 // Takes effect with the next actor call.  Identical actions either way.
 extern "C" int fsrl_actor_set_resident(fsrl_ctx* c, int32_t on, double idle_timeout_us) {
     CHECK_ARG(c, "null ctx");
-    CHECK_ARG(idle_timeout_us <= 1.0e6, "idle_timeout_us above one second");
-    ENTER_DEV(c);
-    c->pa_on = on != 0;
-    if (idle_timeout_us > 0.0) c->pa_idle_us = idle_timeout_us;
-    return 0;
+    ENTER_DEV(c);                             // has ended the kernel (pactor_release): rr_set_resident's own release finds nothing live
+    return rr_code(rr_set_resident(c->pa, on, idle_timeout_us), "");
 }
 
 // out3 = {kernel launches, requests served through the doorbell, 1 if a resident kernel is live now}
 extern "C" int fsrl_actor_resident_stats(fsrl_ctx* c, int64_t* out3) {
     CHECK_ARG(c && out3, "null argument");
-    out3[0] = c->pa_launches; out3[1] = c->pa_requests; out3[2] = c->pa_live ? 1 : 0;
+    rr_stats(c->pa, out3);
     return 0;
 }
 

@@ -3,7 +3,7 @@
 // step to actor_group_resident_kernel<H, true> (kernels_mlp.hpp): a workgroup per (member, 16-row tile) running the member's ACTOR
 // network (SacState::PA, mda) and writing the raw head rows [rows][raw_cols] to the pinned ring; the host then finishes each member
 // as its own fsrl_collect_step would (sac_actor_finish, actor_draw from ITS xoshiro stream, map_env_action with its bounds).  The
-// ring and the protocol are host_actor_ring.inc's (GaRing), shared with the on-policy group (host_group_collect.inc).
+// ring is host_actor_ring.inc's (GaRing), the protocol resident_ring.hpp's, shared with the on-policy group (host_group_collect.inc).
 // The object is independent of the update groups: a member may at the same time be in an fsrl_sac_group / fsrl_cvpo_group, keeps its
 // own streams, store and resident actor, and is not owned.
 //
@@ -21,9 +21,9 @@
 //   * after EXIT nothing is waited for.  Requests are synchronous, so none is in flight at release: every workgroup that had rows in
 //     a request is past its prologue.  A workgroup that never had rows may still be in its prologue when a member's stream overwrites
 //     the parameters; what it reads then it never uses -- the next doorbell it sees is EXIT.  The NEXT generation is only launched
-//     once every workgroup of this one has stored its `state` word (gactor_wait_ended), behind the events above.
+//     once every workgroup of this one has stored its `state` word (rr_ring), behind the events above.
 //   * fsrl_ctx_destroy of a member breaks the group (collect_group_detach: later steps fail with FSRL_ESTATE, destroy still works).
-//   * the wait is ga_poll's: hipStreamQuery every 2 ms, a HIP error fails the call, an idle stream relaunches, 20 s fails.
+//   * the wait is resident_ring.hpp's (rr_poll): hipStreamQuery every 2 ms, a HIP error fails the call, an idle stream relaunches, 20 s fails.
 // The step path allocates nothing: ring, stream and events are made at create.
 // ====================================================================================== replay agents' collect group
 struct fsrl_collect_group {
@@ -45,20 +45,21 @@ static int lay_collect_group_step(fsrl_collect_group* g, const GaStepArgs& a);
 // a layered group has no kernel to end, so the hook marks it and its next request orders the group's stream behind the members'
 // streams (a fused group never reads the mark).  Only this hook re-orders: the public fsrl_collect_group_actor_release changes
 // nothing of a member and leaves the mark alone.
-static void collect_group_actor_release(fsrl_collect_group* g) { ga_release(g->ga); g->reorder = true; }
+static void collect_group_actor_release(fsrl_collect_group* g) { rr_release(g->ga); g->reorder = true; }
 
 static void collect_group_detach(fsrl_ctx* c) {
     fsrl_collect_group* g = c->cgroup;
     if (!g) return;
-    ga_release(g->ga);
+    rr_release(g->ga);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (auto& x : g->m) if (x) { x->cgroup = nullptr; x = nullptr; }
     g->broken = true;
 }
 
 // GaRing::launch: order the group's stream behind every member's compute stream, then the RAW kernel over the members' actor networks
-static int collect_group_launch(void* owner, GaRing& r, unsigned last_seq) {
-    fsrl_collect_group* g = (fsrl_collect_group*)owner;
+static int collect_group_launch(void* ring, ResidentRing&, unsigned last_seq) {
+    GaRing& r = *(GaRing*)ring;
+    fsrl_collect_group* g = (fsrl_collect_group*)r.group;
     GActorArgs a{};
     const ModelDesc* md0 = nullptr;
     for (size_t i = 0; i < g->m.size(); ++i) {
@@ -67,7 +68,7 @@ static int collect_group_launch(void* owner, GaRing& r, unsigned last_seq) {
         if (!sac_actor_resident_args(c, &P, &md)) return fail(FSRL_ESTATE, "member %d has no fused actor network", (int)i);
         a.P[i] = P;
         if (i == 0) md0 = md;
-        pactor_release_own(c);                  // its own resident actor: the event below would wait for its idle timeout
+        rr_release(c->pa);                      // its own resident actor: the event below would wait for its idle timeout
         HIPCHK(hipEventRecord(g->ready[i], c->compute));
         HIPCHK(hipStreamWaitEvent(g->stream, g->ready[i], 0));
     }
@@ -85,7 +86,7 @@ static int collect_group_launch(void* owner, GaRing& r, unsigned last_seq) {
 extern "C" int fsrl_collect_group_destroy(fsrl_collect_group* g) {
     if (!g) return 0;
     (void)hipSetDevice(g->device);
-    ga_release(g->ga);
+    rr_release(g->ga);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (fsrl_ctx* c : g->m) if (c) c->cgroup = nullptr;
     for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
@@ -142,7 +143,7 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
         (void)fsrl_collect_group_destroy(g);
         return FSRL_EHIP;
     }
-    g->ga.stream = g->stream; g->ga.launch = collect_group_launch; g->ga.owner = g;
+    ga_bind(g->ga, g->stream, collect_group_launch, g);
     const int rc = g->layered ? 0 : gactor_ensure(g->ga, g->m.data(), k, g->raw_cols);      // a layered group has no ring
     if (rc) { g->m.clear(); (void)fsrl_collect_group_destroy(g); return rc; }
     for (int i = 0; i < k; ++i) ctxs[i]->cgroup = g;
@@ -182,17 +183,17 @@ extern "C" int fsrl_collect_group_step(fsrl_collect_group* g, const int32_t* k, 
 extern "C" int fsrl_collect_group_actor_set_resident(fsrl_collect_group* g, int32_t on, double idle_timeout_us) {
     CHECK_ARG(g, "null group");
     if (g->layered) return 0;                  // no resident kernel to switch: accepted, no effect
-    return ga_set_resident(g->ga, on, idle_timeout_us);
+    return rr_code(rr_set_resident(g->ga, on, idle_timeout_us), "");
 }
 
 extern "C" int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3) {
     CHECK_ARG(g && out3, "null argument");
-    ga_stats(g->ga, out3);
+    rr_stats(g->ga, out3);
     return 0;
 }
 
 extern "C" int fsrl_collect_group_actor_release(fsrl_collect_group* g) {
     CHECK_ARG(g, "null group");
-    ga_release(g->ga);                         // (a layered group: nothing is live)
+    rr_release(g->ga);                         // (a layered group: nothing is live)
     return 0;
 }

@@ -1,20 +1,21 @@
 // host_group_collect.inc -- lock-step collection of a group: fsrl_collect_step on every member in ONE call with ONE actor request for
 // all of them (part of fsrl_hip.hip, after host_group.inc).  The request goes to actor_group_resident_kernel (kernels_mlp.hpp): the
-// resident actor of DESIGN 3.4 with a workgroup per (member, 16-row tile), on the group's stream.  Protocol as pactor_* (post / ring /
-// wait / release, generation and sequence numbers), with one doorbell for the group and a per-member row count k_m next to it.
+// resident actor of DESIGN 3.4 with a workgroup per (member, 16-row tile), on the group's stream.  Protocol: resident_ring.hpp
+// (request / wait / release, generation and sequence numbers), with one doorbell for the group and a per-member row count k_m next to it.
 // A group of LAYERED contexts has no resident kernel: its request is one launch sequence for all members (host_layered_group.inc);
 // fsrl_group_actor_resident_stats then reports {shared launch sequences, requests served by them, 0}, fsrl_group_actor_release
 // has nothing to end.
 // The kernel is told to end (EXIT) before anything else is enqueued on the group's stream: fsrl_group_ppo_update, fsrl_group_destroy,
 // group_detach and every member entry point that goes through pactor_release (ENTER_DEV, a member's own actor calls).
 
-// The ring and the protocol live in host_actor_ring.inc (GaRing), shared with the replay agents' collect group.
+// The ring lives in host_actor_ring.inc (GaRing), shared with the replay agents' collect group.
 
-static void group_actor_release(fsrl_group* g) { ga_release(g->ga); }
+static void group_actor_release(fsrl_group* g) { rr_release(g->ga); }
 
 // GaRing::launch of an on-policy group: the members' parameter vectors, the on-policy head
-static int group_actor_launch(void* owner, GaRing& r, unsigned last_seq) {
-    fsrl_group* g = (fsrl_group*)owner;
+static int group_actor_launch(void* ring, ResidentRing&, unsigned last_seq) {
+    GaRing& r = *(GaRing*)ring;
+    fsrl_group* g = (fsrl_group*)r.group;
     const fsrl_ctx* c0 = g->m[0];
     GActorArgs a{};
     for (size_t i = 0; i < g->m.size(); ++i) a.P[i] = g->m[i]->P;
@@ -30,7 +31,7 @@ static int group_actor_launch(void* owner, GaRing& r, unsigned last_seq) {
 }
 
 static int group_actor_ensure(fsrl_group* g) {
-    g->ga.stream = g->stream; g->ga.launch = group_actor_launch; g->ga.owner = g;
+    ga_bind(g->ga, g->stream, group_actor_launch, g);
     return gactor_ensure(g->ga, g->m.data(), (int)g->m.size(), g->m[0]->cfg.act_dim);
 }
 
@@ -49,7 +50,7 @@ extern "C" int fsrl_group_collect_step(fsrl_group* g, const int32_t* k, const in
         // a group of layered contexts: no resident kernel, ONE launch sequence per step for all members (host_layered_group.inc);
         // any row count per member goes through it.  fsrl_group_actor_set_resident(g, 0, ...) selects the member-by-member calls.
         const int n = (int)g->m.size(), Do = g->m[0]->cfg.obs_dim;
-        g->ga.stream = g->stream;
+        ga_bind(g->ga, g->stream, nullptr, g);
         return ga_collect_step_via(
             g->ga, g->m.data(), n, g->m[0]->device, a, [](int) { return true; },
             [&]() { return lay_group_collect_post(g->lay, g->ga, g->m.data(), n, k_act, obs_act); },
@@ -78,12 +79,12 @@ extern "C" int fsrl_group_collect_step(fsrl_group* g, const int32_t* k, const in
 
 extern "C" int fsrl_group_actor_set_resident(fsrl_group* g, int32_t on, double idle_timeout_us) {
     CHECK_ARG(g, "null group");
-    return ga_set_resident(g->ga, on, idle_timeout_us);
+    return rr_code(rr_set_resident(g->ga, on, idle_timeout_us), "");
 }
 
 extern "C" int fsrl_group_actor_resident_stats(fsrl_group* g, int64_t* out3) {
     CHECK_ARG(g && out3, "null argument");
-    ga_stats(g->ga, out3);
+    rr_stats(g->ga, out3);
     return 0;
 }
 

@@ -295,7 +295,7 @@ static int lay_group_collect_post(LayGroup& lg, GaRing& ga, fsrl_ctx* const* m, 
         });
 }
 
-// the answer of the request in flight is in pinned memory: ga_poll's bounded wait on the completion words
+// the answer of the request in flight is in pinned memory: the ring's bounded wait (rr_poll) on the completion words
 static int lay_group_collect_wait(LayGroup& lg, GaRing& ga, int k, int Do, int cols) {
     const LayGroupPinned pin = lay_group_pinned(lg, Do, cols);
     const int tc = lg.ccap / 16;
@@ -305,7 +305,7 @@ static int lay_group_collect_wait(LayGroup& lg, GaRing& ga, int k, int Do, int c
                 if (__atomic_load_n(pin.done + (size_t)i * tc + t, __ATOMIC_ACQUIRE) != lg.cseq) return false;
         return true;
     };
-    const int rc = ga_poll(ga, served, "the group's actor launches");
-    if (rc == 1) return fail(FSRL_EHIP, "the group's actor launches ended without an answer");
-    return rc;
+    const int rc = rr_poll(ga, served);
+    if (rc == RR_IDLE) return fail(FSRL_EHIP, "the group's actor launches ended without an answer");
+    return rr_code(rc, "the group's actor launches");
 }

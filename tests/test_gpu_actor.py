@@ -263,6 +263,38 @@ def test_native_collect_fails_fast_on_a_dead_worker_and_leaves_the_env_object_co
         env.close()
 
 
+def test_native_split_collect_ends_the_resident_actor_when_a_worker_dies():
+    """fsrl_collect_episodes_split leaves as fsrl_collect_episodes does when it fails: the resident actor is told to end by the
+    library itself (no kernel left to its idle timeout, none still writing the pinned head outputs), within seconds.  The call
+    goes to the engine directly: FastCollector.collect releases the actor in a `finally`, which would hide the difference."""
+    import time
+    from fsrl_amd.agent import PPOLagAgent
+    from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+    from fsrl_amd.env import ShmemVectorEnv
+    env = ShmemVectorEnv(env_num=4, workers=2, obs_dim=8, act_dim=2, episode_len=50, seed=1)
+    try:
+        assert env.n_lanes == 2
+        agent = PPOLagAgent(env, None, cost_limit=10, device="cuda:0", seed=2, hidden_sizes=(64, 64), training_num=4)
+        eng = agent.policy.engine
+        buf = HipVectorReplayBuffer(eng, 4 * 300, 4)
+        col = FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True, split_phase=True)
+        assert col.split_phase
+        col.collect(n_episode=4)
+        env._procs[1].terminate(); env._procs[1].join(5)
+        t0 = time.time()
+        try:
+            with pytest.raises(Exception, match="worker"):
+                eng.collect_episodes(env.native_desc(), np.arange(4), np.asarray(col._obs[:4], np.float32), 4, bound_method=0, split=True)
+        finally:
+            env.sync_native()
+            env.mark_broken("a native collect failed while env commands were in flight")
+        assert time.time() - t0 < 10.0
+        assert eng.actor_resident_stats()["live"] is False
+        eng.close()
+    finally:
+        env.close()
+
+
 def _mk_engine(resident, hidden=256, obs_dim=8, act_dim=2, unbounded=False):
     from fsrl_amd.engine import Engine, EngineConfig
     eng = Engine(EngineConfig(obs_dim=obs_dim, act_dim=act_dim, hidden=hidden, env_num=64, max_grad_norm=0.5, target_kl=None,
