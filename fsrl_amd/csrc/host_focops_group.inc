@@ -8,6 +8,11 @@
 // single-context bodies.  The tile height of a launch is the PPO group's rule (4-row tiles only while every active member
 // fits one round of workgroups), so a group of one is bit-identical to its solo run, and larger groups are wherever the tile
 // height does not change (tests/test_gpu_group_focops.py).
+// A group of LAYERED members (all of one shape) runs focops_pass's layered step instead: 2 L + 5 launches per minibatch step for
+// all members -- the PPO group's forward / backward / weight-side launches over its job tables (host_layered_group.inc), the
+// loss heads (lay_fb_head_group_kernel), prep with the finished gradient in G as the one partial, step.  No tile plan, no
+// split-K: a member's update is its own Engine.focops_update bit for bit at every group size
+// (tests/test_gpu_group_focops_layered.py).
 // ====================================================================================== grouped FOCOPS
 
 // what grouped FOCOPS needs of its members beyond fsrl_group_create's shape / PPO checks; run at create and at every
@@ -17,7 +22,8 @@ static int focops_group_check(fsrl_ctx* const* ctxs, int k) {
     for (int i = 0; i < k; ++i) {
         const fsrl_ctx* c = ctxs[i];
         CHECK_ARG(c->foc, "member %d: fsrl_focops_init first (a grouped FOCOPS member needs its FOCOPS configuration)", i);
-        CHECK_ARG(!c->lay, "member %d is a layered context: grouped FOCOPS runs the fused kernels (two hidden layers)", i);
+        CHECK_ARG((c->lay != nullptr) == (c0->lay != nullptr), "member %d: members must have one network shape (a FOCOPS group is all fused or all layered contexts)", i);
+        CHECK_ARG(!c->lay || lay_same_shape(c->cfg, c0->cfg), "member %d: members must have one network shape", i);
         CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256),
                   "member %d: fsrl_tr_set_plan's streaming weight-gradient plan is not grouped", i);
         const fsrl_focops_config &a = c->foc->cfg, &b = c0->foc->cfg;
@@ -40,6 +46,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
     HIPCHK(hipSetDevice(c0->device));
     hipStream_t s = g->stream;
     const int H = c0->cfg.hidden, nn = 3;
+    const bool layered = c0->lay != nullptr;
     auto abort_all = [&](int rc_) { for (fsrl_ctx* c : g->m) c->in_update = false; return rc_; };
     // ---- begin: sample(0) + process_fn of every member (FOCOPS: no multipliers, rescaling 1, as Engine.focops_update)
     const double zero_lag[FSRL_MAX_CRITICS] = {};
@@ -55,7 +62,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
         if (n[i] == 0) { active[(size_t)i] = 0; continue; }
         rc = focops_alloc(c);                   // the members' working sets before the first grouped pass
         if (rc) return abort_all(rc);
-        fast[(size_t)i] = !c->foc->no_fast && c->mbp_max <= 512;
+        fast[(size_t)i] = !layered && !c->foc->no_fast && c->mbp_max <= 512;
     }
     size_t cap_nmb = 0;
     for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
@@ -64,11 +71,20 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
     const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;          // grown as the PPO group's step table
     rc = table_ensure(g->fsteps, n_steps, 2 * n_steps, g->stream);
     if (rc) return abort_all(rc);
+    if (layered) {
+        // the layered step's launches read the PPO group's tables: job tables of this update (the members' working sets are in
+        // place now), the member table for the observation operands, and per pass the step rows' active / mb_size / mb_start
+        rc = table_ensure(g->steps, n_steps, 2 * n_steps, g->stream);
+        if (!rc) rc = lay_group_tables(g->lay, g->m.data(), k, active.data(), s);
+        if (rc) return abort_all(rc);
+        for (int i = 0; i < k; ++i) lay_group_agent(g->m[i], g->tab.h[i]);
+        HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(GroupAgent), hipMemcpyHostToDevice, s));
+    }
     int nb_a, nb_c0, nb_c1;
     focops_blocks(c0, &nb_a, &nb_c0, &nb_c1);
     const int nb_all = nb_a + nb_c0 + nb_c1;
-    // fb_wgrad_kernel's plan in wgrad_launch (PAIR2 = false): blocks of one split and network
-    const WgradBlocks wb = wgrad_blocks(c0->md.Do, H, false);
+    // fb_wgrad_kernel's plan in wgrad_launch (PAIR2 = false): blocks of one split and network (fused members)
+    const WgradBlocks wb = layered ? WgradBlocks{} : wgrad_blocks(c0->md.Do, H, false);
     const int passes = wb.passes, NB = wb.NB;
     std::vector<char> rows4;
     for (int pass = 0; pass < repeat; ++pass) {
@@ -85,16 +101,17 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             fsrl_ctx* c = g->m[i];
             rc = ppo_pass_prepare(c, perms ? perms[i] + (size_t)pass * (size_t)n[i] : nullptr, seed ? seed + 1000003ull * i + pass : 0);
             if (rc) return abort_all(rc);
-            if (!fast[(size_t)i]) {
+            if (!fast[(size_t)i] && !layered) {
                 int ns = 1;
                 for (int sz : c->mb_size) ns = std::max(ns, wgrad_plan((sz + 15) / 16 * 16, NB * nn, c->n_cus).nsplit);
                 rc = ensure_parts(c, c->n_dev, ns);
                 if (rc) return abort_all(rc);
             }
         }
-        // ---- tile height per minibatch step: the PPO group's rule over the members active in the pass
+        // ---- tile height per minibatch step: the PPO group's rule over the members active in the pass (the layered step has
+        // no tile plan: 16-row tiles of the loss head, as the member's own pass)
         rows4.assign(max_nmb, 0);
-        for (size_t mb = 0; mb < max_nmb; ++mb) {
+        for (size_t mb = 0; mb < max_nmb && !layered; ++mb) {
             int tiles = 0;
             for (int i = 0; i < k; ++i)
                 if (active[(size_t)i] && mb < g->m[i]->mb_size.size()) tiles = std::max(tiles, (g->m[i]->mb_size[mb] + 15) / 16);
@@ -102,6 +119,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
         }
         // ---- member table and step table of the pass: focops_pass's arguments, member by member
         memset(g->fsteps.h, 0, max_nmb * k * sizeof(FocGroupStep));
+        if (layered) memset(g->steps.h, 0, max_nmb * k * sizeof(GroupStep));
         for (int i = 0; i < k; ++i) {
             fsrl_ctx* c = g->m[i];
             FocGroupMember& t = g->ftab.h[i];
@@ -123,7 +141,11 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
                 st.rows_pad = rows_pad;
                 st.fb = focops_tile_args(c, start, size);
                 st.sa = focops_step_args(c, f->pp);
-                if (t.fast) {
+                if (layered) {
+                    st.sa.parts = c->G; st.sa.nparts = 1;            // the weight-side launch leaves the whole gradient in G
+                    GroupStep& gs = g->steps.h[mb * k + i];
+                    gs.active = 1; gs.mb_start = start; gs.mb_size = size; gs.mb_index = (int)mb;
+                } else if (t.fast) {
                     st.wp = focops_wgrad_ptrs(c, st.fb.obs, rows_pad);
                     st.sa.nparts = 0; st.sa.parts = nullptr;
                     st.sa.gsq_part = c->gsq_part; st.sa.n_gsq_part = wg_blocks_per_net(H); st.sa.gsq_net = f->gsq_net;
@@ -142,6 +164,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
         }
         HIPCHK(hipMemcpyAsync(g->ftab.d, g->ftab.h, (size_t)k * sizeof(FocGroupMember), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(g->fsteps.d, g->fsteps.h, max_nmb * k * sizeof(FocGroupStep), hipMemcpyHostToDevice, s));
+        if (layered) HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, max_nmb * k * sizeof(GroupStep), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(g->steps_copied, s));
         g->steps_in_flight = true;
         // ---- the pass: one pass-start prep for the three-launch members, then per minibatch step 3 or 4 launches for all
@@ -161,6 +184,18 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
                 else { f4 = true; remap = std::max(remap, hst[i].wa.remap_total); }
             }
             if (tiles == 0) continue;                            // no active member has a minibatch at this index
+            if (layered) {
+                // 2 L + 5 launches for all members: focops_pass's layered step (lay_fwd, the loss heads, lay_bwd, prep with G as
+                // the one partial, step)
+                const LayGroupLaunch ll(g->lay, g->m.data(), k, s, g->tab.d, g->steps.d + mb * k, g->steps.h + mb * k);
+                ll.forward();
+                hipLaunchKernelGGL(lay_fb_head_group_kernel, dim3(ll.tiles, nn, k), dim3(256), 0, s, g->lay.heads.d, st);
+                ll.backward();
+                hipLaunchKernelGGL((focops_prep_group_kernel<0>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->ftab.d, st);
+                hipLaunchKernelGGL(focops_step_group_kernel, dim3(nb_all + 1, k), dim3(256), 0, s, c0->md, st);
+                HIPCHK(hipGetLastError());
+                continue;
+            }
             rc = dispatch_H(H, [&](auto hc) {
                 constexpr int HH = decltype(hc)::value;
                 if (rows4[mb]) hipLaunchKernelGGL((focops_tile_group_kernel<HH, 4>), dim3(tiles, nn, k), dim3(4 * HH), 0, s, c0->md, g->ftab.d, st);

@@ -5,9 +5,9 @@
 // from the number of active members and the largest member, and above 512 rows it keeps the in-kernel reduction where the
 // single path goes through the split-K kernels.  Otherwise: the golden tests' tolerances (tests/test_gpu_group.py).
 // A group of FOCOPS contexts runs the same entry points through host_focops_group.inc (one algorithm per group).
-// A group of LAYERED PPO-Lagrangian contexts (any other `hidden_sizes`, all members of one shape) runs the layered minibatch
-// step with every member in each of its 2 L + 5 launches (host_layered_group.inc); there a member's update IS its own
-// fsrl_ppo_update bit for bit, whatever the group.
+// A group of LAYERED PPO-Lagrangian or FOCOPS contexts (any other `hidden_sizes`, all members of one shape) runs the layered
+// minibatch step with every member in each of its 2 L + 5 launches (host_layered_group.inc); there a member's update IS its own
+// fsrl_ppo_update / Engine.focops_update bit for bit, whatever the group.
 // ====================================================================================== groups
 #define FSRL_MAX_GROUP 16
 
@@ -39,9 +39,9 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_PPO_LAG || c->cfg.algo == FSRL_ALGO_FOCOPS,
                   "member %d: grouped updates are PPO-Lagrangian or FOCOPS contexts", i);
         CHECK_ARG(c->cfg.algo == c0->cfg.algo, "member %d: a group has one algorithm (all PPO-Lagrangian or all FOCOPS members)", i);
-        // layered members: PPO-Lagrangian groups only, all members layered and of one shape (checked below)
-        CHECK_ARG(!c->lay || c->cfg.algo == FSRL_ALGO_PPO_LAG,
-                  "member %d is a layered context: grouped FOCOPS runs the fused kernels (two hidden layers of at most 256 units)", i);
+        // layered members: all members layered and of one shape (checked below); a FOCOPS group names the mix of kinds
+        CHECK_ARG(c->cfg.algo != FSRL_ALGO_FOCOPS || (c->lay != nullptr) == (c0->lay != nullptr),
+                  "member %d: members must have one network shape (a FOCOPS group is all fused or all layered contexts)", i);
         CHECK_ARG(c->device == c0->device, "members live on one device");
         CHECK_ARG(!c->in_update && !c->group, "member %d is inside an update or already grouped", i);
         const fsrl_config &a = c->cfg, &b = c0->cfg;

@@ -1,6 +1,7 @@
-// host_layered_group.inc -- a group of LAYERED PPO-Lagrangian contexts of one shape (part of fsrl_hip.hip, before host_group.inc;
-// kernels_layered_group.hpp has the kernels): the minibatch step of fsrl_group_ppo_update and the shared actor request of
-// fsrl_group_collect_step.
+// host_layered_group.inc -- a group of LAYERED PPO-Lagrangian or FOCOPS contexts of one shape (part of fsrl_hip.hip, before
+// host_group.inc; kernels_layered_group.hpp has the kernels): the minibatch step of fsrl_group_ppo_update and the shared actor
+// request of fsrl_group_collect_step.  A FOCOPS group shares the job tables, the forward / backward / weight-side launches and the
+// collection below; its loss head, prep and step launches are host_focops_group.inc's.
 //   update:  lay_ppo_steps' 2 L + 5 launches, each carrying every member (job tables in device memory, built once per grouped
 //            update; rows and the minibatch's offset come from the member's GroupStep row).  Bit-identical to the member's own
 //            fsrl_ppo_update: see kernels_layered_group.hpp.
@@ -176,40 +177,66 @@ static void lay_group_launch(bool vec, int nw, dim3 grid, hipStream_t s, const L
 #undef LAYG_GO
 }
 
-// one minibatch step of every member that has one at this index: 2 L + 5 launches.  st_h: the pinned twin of the step rows st_d.
+// The launches of a minibatch step that do not depend on the algorithm, for every member that has a minibatch at this index
+// (st_h: the pinned twin of the step rows st_d): forward() the L + 1 LIN_F launches, backward() the L LIN_X launches and the
+// LIN_W launch.  The loss heads go in between and the optimiser behind: lay_group_step (PPO-Lagrangian) below,
+// focops_group_update's layered branch (host_focops_group.inc).
+struct LayGroupLaunch {
+    const LayGroup& lg;
+    const fsrl_ctx* c0;
+    int k;
+    hipStream_t s;
+    const GroupAgent* tab;
+    const GroupStep* st_d;
+    int mbs = 0, gy = 0, tiles = 0;             // the largest minibatch of the step: rows, 64-row tiles, 16-row tiles
+    long row_tiles = 0;                         // 64-row tiles of the members that step
+    LayGroupLaunch(const LayGroup& lg_, fsrl_ctx* const* m, int k_, hipStream_t s_, const GroupAgent* tab_, const GroupStep* st_d_,
+                   const GroupStep* st_h)
+        : lg(lg_), c0(m[0]), k(k_), s(s_), tab(tab_), st_d(st_d_) {
+        for (int i = 0; i < k; ++i)
+            if (st_h[i].active) { mbs = std::max(mbs, st_h[i].mb_size); row_tiles += (st_h[i].mb_size + 63) / 64; }
+        gy = (mbs + 63) / 64; tiles = (mbs + 15) / 16;
+    }
+    // NW of a forward / backward launch from the workgroups of the WHOLE launch (any NW gives the same bits there)
+    int nw_of(long col_tiles) const {
+        const long wgs = col_tiles * row_tiles;
+        return wgs <= 2 * c0->n_cus ? 4 : (wgs <= 4 * c0->n_cus ? 2 : 1);
+    }
+    void forward() const {
+        const LayModel& lm = c0->lay->lm;
+        const int nn = lg.nn, L = lg.L;
+        const LinGroupJob* fw = lg.jobs.d;
+        for (int l = 0; l <= L; ++l) {
+            int gx = 1; long ct = 0;
+            for (int net = 0; net < nn; ++net) { const int t = (lm.net[net].l[l].out + 63) / 64; gx = std::max(gx, t); ct += t; }
+            lay_group_launch<LIN_F>(lg.vec_f[l], nw_of(ct), dim3(gx, gy, k * nn), s, fw + (size_t)l * k * nn, tab, st_d);
+        }
+    }
+    void backward() const {
+        const LayState* l0 = c0->lay;
+        const LayModel& lm = l0->lm;
+        const int nn = lg.nn, L = lg.L;
+        const LinGroupJob* bw = lg.jobs.d + (size_t)(L + 1) * k * nn;
+        const LinGroupJob* wg = bw + (size_t)L * k * nn;
+        for (int t = 0; t < L; ++t) {
+            const int l = L - 1 - t;
+            int gx = 1; long ct = 0;
+            for (int net = 0; net < nn; ++net) { const int u = (lm.net[net].l[l + 1].in + 63) / 64; gx = std::max(gx, u); ct += u; }
+            lay_group_launch<LIN_X>(lg.vec_x[t], nw_of(ct), dim3(gx, gy, k * nn), s, bw + (size_t)t * k * nn, tab, st_d);
+        }
+        lay_group_launch<LIN_W>(lg.vec_w, lg.nw_w, dim3(l0->wgrid.x, l0->wgrid.y, k * lg.J), s, wg, tab, st_d);
+    }
+};
+
+// one PPO-Lagrangian minibatch step of every member that has one at this index: 2 L + 5 launches
 static int lay_group_step(LayGroup& lg, fsrl_ctx* const* m, int k, hipStream_t s, const GroupAgent* tab, const GroupStep* st_d,
                           const GroupStep* st_h, const PpoStepArgs& base) {
     const fsrl_ctx* c0 = m[0];
-    const LayState* l0 = c0->lay;
-    const LayModel& lm = l0->lm;
-    const int nn = lg.nn, L = lg.L;
-    int mbs = 0;
-    long row_tiles = 0;                          // 64-row tiles of the members that step
-    for (int i = 0; i < k; ++i)
-        if (st_h[i].active) { mbs = std::max(mbs, st_h[i].mb_size); row_tiles += (st_h[i].mb_size + 63) / 64; }
-    if (mbs == 0) return 0;
-    const int gy = (mbs + 63) / 64, tiles = (mbs + 15) / 16;
-    // NW of a forward / backward launch from the workgroups of the WHOLE launch (any NW gives the same bits there)
-    auto nw_of = [&](long col_tiles) {
-        const long wgs = col_tiles * row_tiles;
-        return wgs <= 2 * c0->n_cus ? 4 : (wgs <= 4 * c0->n_cus ? 2 : 1);
-    };
-    const LinGroupJob* fw = lg.jobs.d;
-    const LinGroupJob* bw = fw + (size_t)(L + 1) * k * nn;
-    const LinGroupJob* wg = bw + (size_t)L * k * nn;
-    for (int l = 0; l <= L; ++l) {
-        int gx = 1; long ct = 0;
-        for (int net = 0; net < nn; ++net) { const int t = (lm.net[net].l[l].out + 63) / 64; gx = std::max(gx, t); ct += t; }
-        lay_group_launch<LIN_F>(lg.vec_f[l], nw_of(ct), dim3(gx, gy, k * nn), s, fw + (size_t)l * k * nn, tab, st_d);
-    }
-    hipLaunchKernelGGL(lay_ppo_head_group_kernel, dim3(tiles, nn, k), dim3(256), 0, s, lg.heads.d, tab, st_d, base);
-    for (int t = 0; t < L; ++t) {
-        const int l = L - 1 - t;
-        int gx = 1; long ct = 0;
-        for (int net = 0; net < nn; ++net) { const int u = (lm.net[net].l[l + 1].in + 63) / 64; gx = std::max(gx, u); ct += u; }
-        lay_group_launch<LIN_X>(lg.vec_x[t], nw_of(ct), dim3(gx, gy, k * nn), s, bw + (size_t)t * k * nn, tab, st_d);
-    }
-    lay_group_launch<LIN_W>(lg.vec_w, lg.nw_w, dim3(l0->wgrid.x, l0->wgrid.y, k * lg.J), s, wg, tab, st_d);
+    const LayGroupLaunch ll(lg, m, k, s, tab, st_d, st_h);
+    if (ll.mbs == 0) return 0;
+    ll.forward();
+    hipLaunchKernelGGL(lay_ppo_head_group_kernel, dim3(ll.tiles, lg.nn, k), dim3(256), 0, s, lg.heads.d, tab, st_d, base);
+    ll.backward();
     hipLaunchKernelGGL(ppo_stats_group_kernel, dim3(k), dim3(64), 0, s, c0->md, tab, st_d, base);
     hipLaunchKernelGGL(adam_clip_group_kernel, dim3((c0->n_dev + 4 * ADAM_NT - 1) / (4 * ADAM_NT), k), dim3(ADAM_NT), 0, s, c0->md,
                        tab, st_d, base);

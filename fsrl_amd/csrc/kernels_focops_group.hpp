@@ -9,6 +9,9 @@
 //   four-launch members (larger, or set_plan(1)):    tile -> split-K fb_wgrad_body -> prep      -> step
 // plus one pass-start prep (nparts = 0) for the three-launch members.  A launch one kind of member does not need returns
 // at once for the others, and the host skips launches no active member needs.
+// A group of LAYERED members (host_layered_group.inc) runs the layered step instead, 2 L + 5 launches for all members:
+//   lin_group_kernel<LIN_F> x (L + 1) -> lay_fb_head_group_kernel -> lin_group_kernel<LIN_X> x L -> <LIN_W> -> prep -> step
+// with the finished gradient in G as the prep launch's one "partial", as focops_pass does for a layered context.
 struct FocGroupMember {
     const float* P;                // the member's parameters (the tile launch's weights)
     FocopsStepArgs pass_prep;      // three-launch pass start: psq / sig_stash of the pass's first parity (nparts = 0)
@@ -59,6 +62,26 @@ __global__ __launch_bounds__(1024) void focops_wgrad_split_group_kernel(const Mo
     const int NB = NT2 + NA * wa.aux_passes + 1;
     const int gi = Lp / NB;
     fb_wgrad_body<H, false>(md, wa, Lp % NB, gi % wa.remap_ny, gi / wa.remap_ny);
+}
+
+// the loss heads of a LAYERED group's step (kernels_layered.hpp: lay_fb_head_kernel's body on head outputs the grouped forward
+// launches left in the member's `out`).  grid = (tiles of the step's largest minibatch, 3, k); heads[member]: the member's buffers
+// (out / dout / P / sigma / mbp / Da / unbounded), the step row's fb: the minibatch's row data, size, 1 / tem_lambda, the member's
+// nu, eta and the statistics slots -- focops_tile_args' values, mode FB_MODE_FOCOPS from network 0 among them.  Copied into a
+// local argument block first, for focops_step_group_kernel's reason below.
+__global__ __launch_bounds__(256) void lay_fb_head_group_kernel(const LayHeadArgs* __restrict__ heads,
+                                                               const FocGroupStep* __restrict__ steps) {
+    const int m = blockIdx.z;
+    const int active = steps[m].active;
+    const FbArgs fb = steps[m].fb;
+    if (!active || (int)blockIdx.x * 16 >= fb.N) return;                // the member's own tile count
+    const LayHeadArgs hm = heads[m];
+    LayFbHeadArgs h;
+    h.out = hm.out; h.dout = hm.dout; h.rd = fb.rd; h.statp = fb.statp;
+    h.P = hm.P; h.sigma = hm.sigma;
+    h.mbp = hm.mbp; h.net0 = fb.net0; h.ny = 3; h.Da = hm.Da; h.unbounded = hm.unbounded; h.N = fb.N; h.mode = fb.mode;
+    h.max_action = fb.max_action; h.cr = fb.cr; h.cc = fb.cc; h.eta = fb.eta;
+    lay_fb_head_body(h, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // prep of a four-launch step (PASS_START 0: the split-K partials summed into G, the actor's per-block squares, the critics'

@@ -381,10 +381,11 @@ struct LayFbHeadArgs {
     int mbp, net0, ny, Da, unbounded, N, mode;
     float max_action, cr, cc, eta;
 };
-__global__ __launch_bounds__(256) void lay_fb_head_kernel(const LayFbHeadArgs h) {
+// (the body is shared with lay_fb_head_group_kernel, kernels_focops_group.hpp: one member of a group per grid.z)
+__device__ __forceinline__ void lay_fb_head_body(const LayFbHeadArgs& h, const int tile, const int y) {
     __shared__ float stl[16 * FB_NSTAT];
     const int tid = threadIdx.x, i = tid >> 4, d = tid & 15, lane = tid & 63;
-    const int y = blockIdx.y, net = h.net0 + y, tile = blockIdx.x, Da = h.Da;
+    const int net = h.net0 + y, Da = h.Da;
     const int row = tile * 16 + i;
     const bool valid = row < h.N;
     const bool backward = h.mode != FB_MODE_EVAL;
@@ -471,6 +472,9 @@ __global__ __launch_bounds__(256) void lay_fb_head_kernel(const LayFbHeadArgs h)
         for (int r = 0; r < 16; ++r) t += stl[r * FB_NSTAT + tid];
         h.statp[((size_t)tile * h.ny + y) * FB_NSTAT + tid] = t;
     }
+}
+__global__ __launch_bounds__(256) void lay_fb_head_kernel(const LayFbHeadArgs h) {
+    lay_fb_head_body(h, blockIdx.x, blockIdx.y);
 }
 
 // KL head of a Hessian-vector product (the head of fb_hvp_body, kernels_fb.hpp; cpo.py:169-182): from the head outputs x and their

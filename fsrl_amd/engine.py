@@ -778,8 +778,9 @@ class EngineGroup(_LockStepCollect):
     """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
     (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
     random streams; use the engines as usual for everything else (push, collect_step, get_params ...).
-    PPO-Lagrangian members may all be layered contexts of one `hidden_sizes` (not FOCOPS members): the group then runs the layered
-    step, 2 L + 5 launches for all members, bit-identical per member to Engine.ppo_update; collect_step is one sequence of L + 2
+    The members may all be layered contexts of one `hidden_sizes` and `force_layered`: the group then runs the layered step,
+    2 L + 5 launches for all members, bit-identical per member to Engine.ppo_update / Engine.focops_update at every group size
+    (a layered FOCOPS group has no tile-height plan to differ in); collect_step is one sequence of L + 2
     launches for all members instead of a resident kernel (actor_resident_stats counts those sequences, `live` stays False;
     actor_set_resident(False) selects the member-by-member calls; set_plan is accepted and has no effect)."""
 
@@ -855,7 +856,8 @@ class EngineGroup(_LockStepCollect):
         k = len(self.engines)
         assert len(nus) == k and len(nu_losses) == k, "one nu and one nu_loss per member"
         for e, nu, nl in zip(self.engines, nus, nu_losses):
-            _lib.check(self.lib.fsrl_focops_set_nu(e._ctx, float(nu), float(nl)))
+            if e._ctx:                                   # a closed member: the grouped call below reports the destroyed member
+                _lib.check(self.lib.fsrl_focops_set_nu(e._ctx, float(nu), float(nl)))
         stats, stopped = self.ppo_update(np.zeros((k, 1)), np.ones(k), batch_size, repeat, perms=perms, seed=seed)
         return [s[:, :_lib.FOCOPS_NSTATS] for s in stats], stopped
 

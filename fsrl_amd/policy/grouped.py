@@ -5,9 +5,9 @@ batching of k seeds").  The reference runs seeds as separate jobs; per member th
 - FOCOPS.update (fsrl/policy/focops.py:126-251): each member's nu step (FOCOPS.nu_step, the host float32 arithmetic of
   process_fn), then the grouped update,
 with the same arguments, the same logger keys and the same lr_scheduler step.  A group is all PPOLagrangian or all FOCOPS.
-PPOLagrangian members may be layered (`hidden_sizes` other than two layers of at most 256 units) when all of them have the same
-`hidden_sizes`: the layered minibatch step then carries every member in each of its 2 L + 5 launches, and a member's grouped
-update is its own update bit for bit.
+The members (PPOLagrangian or FOCOPS) may be layered (`hidden_sizes` other than two layers of at most 256 units) when all of them
+have the same `hidden_sizes`: the layered minibatch step then carries every member in each of its 2 L + 5 launches, and a
+member's grouped update is its own update bit for bit.
 
     group = PolicyGroup([agent.policy for agent in agents])
     ... every agent collects into ITS buffer, steps ITS PID multiplier / sees ITS cost (trainer.policy_update_fn does

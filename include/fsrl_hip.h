@@ -91,8 +91,8 @@ typedef struct fsrl_config {
                                 LAYERED context (every algorithm): the same entry points (store, collector actor,
                                 fsrl_ppo_* / fsrl_tr_* / fsrl_sac_* / fsrl_cvpo_*, parameters, snapshot, lr), the same float64 scans and logged rows, but the network
                                 math runs one MFMA GEMM launch per Linear (2 L + 5 launches per minibatch step instead of 3)
-                                on activations kept in HBM.  Grouped PPO-Lag, SAC-Lag and DDPG-Lag updates and their lock-step
-                                collection take layered members (all members of one `hidden_sizes`); grouped FOCOPS and CVPO
+                                on activations kept in HBM.  Grouped PPO-Lag, FOCOPS, SAC-Lag and DDPG-Lag updates and their
+                                lock-step collection take layered members (all members of one `hidden_sizes`); grouped CVPO
                                 updates and fsrl_launch_floors refuse a layered context with FSRL_EINVAL.
                                 Limits, as enforced: the replay agents (fsrl_sac_* / fsrl_cvpo_*) run every depth 1 ..
                                 FSRL_MAX_HIDDEN with two or four Q-networks -- a weight-side job table larger than one launch
@@ -297,14 +297,14 @@ int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
  *      in-kernel weight-gradient reduction above 512 rows.  Members keep their own store, parameters,
  *      Adam state and random streams; shape and PPO hyper-parameters must agree, batch sizes N_i may differ.
  *      While grouped, a member's own update calls still work (they run on the group's stream).
- *      A group has one algorithm.  FOCOPS members (not layered) must have run fsrl_focops_init and share l2_reg, delta,
+ *      A group has one algorithm.  FOCOPS members must have run fsrl_focops_init and share l2_reg, delta,
  *      eta, tem_lambda, max_grad_norm and fsrl_focops_set_plan (learning rates may differ); checked again at every update.
- *      Per FOCOPS member the result is bit-identical to its own update wherever the group keeps the member's tile height.
- *      LAYERED PPO-Lagrangian members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are layered
- *      and n_hidden, hidden_sizes[] and force_layered agree (a mix of fused and layered members, or of widths: "one network
- *      shape"; layered FOCOPS members are refused).  The group then runs the layered minibatch step with every member in each
- *      of its 2 L + 5 launches (L hidden layers), whatever k; per member the update is bit-identical to its own
- *      fsrl_ppo_update, for every k, batch length and minibatch size.                                                        */
+ *      Per fused FOCOPS member the result is bit-identical to its own update wherever the group keeps the member's tile height.
+ *      LAYERED PPO-Lagrangian or FOCOPS members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are
+ *      layered and n_hidden, hidden_sizes[] and force_layered agree (a mix of fused and layered members, or of widths: "one
+ *      network shape"; a FOCOPS group's message for the mix also says "layered").  The group then runs the layered minibatch step
+ *      with every member in each of its 2 L + 5 launches (L hidden layers), whatever k; per member the update is bit-identical
+ *      to its own fsrl_ppo_update (FOCOPS: its own pass-by-pass FOCOPS update), for every k, batch length and minibatch size.  */
 typedef struct fsrl_group fsrl_group;
 int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out);       /* 1 <= k <= 16; members are not owned   */
 int fsrl_group_destroy(fsrl_group* group);

@@ -6,6 +6,10 @@ stop cuts an update short); --hidden 256 is the FOCOPS leg of tools/bench_trust.
 One JSON line per k.
 
     python tools/bench_group_focops.py [--hidden 256] [--ks 1 2 4 8] [--updates 6]
+    python tools/bench_group_focops.py --hidden 256x256x256 [--ks 1 2 4 8] [--legs update,collect]
+
+--hidden AxBxC (any tuple) makes LAYERED members: tools/bench_group_layered.py's legs with --algo focops (grouped / k threads / one
+context alternated in one process, and the collect leg), one JSON line per (leg, k).
 
 Every timed update starts from the same state (initial weights, fresh Adam moments), restored from the HBM snapshot."""
 import argparse
@@ -91,9 +95,16 @@ def run(k, hidden, updates):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--hidden", default="256", help="a width (fused members) or a tuple such as 256x256x256 (layered members)")
     ap.add_argument("--ks", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--updates", type=int, default=6)
+    ap.add_argument("--legs", default="update,collect", help="layered members: bench_group_layered.py's legs")
     a = ap.parse_args()
-    for k in a.ks:
-        print(json.dumps(run(k, a.hidden, a.updates)), flush=True)
+    if "x" in a.hidden.lower():
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import bench_group_layered
+        bench_group_layered.main(["--algo", "focops", "--hidden", a.hidden, "--ks", ",".join(map(str, a.ks)), "--legs", a.legs,
+                                  "--rounds", str(max(a.updates, 5))])
+    else:
+        for k in a.ks:
+            print(json.dumps(run(k, int(a.hidden), a.updates)), flush=True)
