@@ -2,10 +2,11 @@
 // shared ones of kernels_sac_group.hpp).
 // k CVPO contexts of one launch structure, each stepped n_i times per call in lock step: every launch of an update carries all
 // members that still have updates to run (9 + 4 * mstep_iter_num launches per update, whatever k is).  The structure is
-// host_sac_group.inc's: members keep their own streams, stores, parameters, targets, actor_old, Adam state, duals, Philox key and
-// statistics ring; the group's stream waits on each active member's stream before the call and each member's streams wait on the
-// group's completion event after it, so fsrl_cvpo_pre_update / _post_update / _set_thres and the member's own updates order against
-// grouped calls like any other work on the member's stream.
+// host_sac_group.inc's, and so is the frame of a call (rgroup_begin / rgroup_enter / rgroup_end): members keep their own streams,
+// stores, parameters, targets, actor_old, Adam state, duals, Philox key and statistics ring; the group's stream waits on each
+// active member's stream before the call and each member's streams wait on the group's completion event after it, so
+// fsrl_cvpo_pre_update / _post_update / _set_thres and the member's own updates order against grouped calls like any other work on
+// the member's stream.
 // A member's arguments are formed by the helpers fsrl_cvpo_update uses (host_cvpo.inc), its arithmetic is the single path's bodies
 // with the single path's split-K plan, and the tile height of a launch is the single-context rule applied to the whole group's
 // launch: a group of one is bit-identical to its solo run, a group that runs sixteen-row tiles in every launch is bit-identical to
@@ -89,16 +90,15 @@ extern "C" int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_grou
 }
 
 // the member's entries in both tables: every argument of the update's launches as fsrl_cvpo_update forms it (library RNG, fused
-// sample + gather, n-step targets folded into the critics' launch); *sa: its sample arguments (the counter is set per step)
+// sample + gather, n-step targets folded into the critics' launch)
 struct CvpoGroupTiles { bool q_r4, a_r4, f_r4, k_r4; };
-static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGroupMember& v, SacSampleArgs* sa, int B, int64_t stored,
-                             const CvpoGroupTiles& th, bool small_wgrad, int* nsplit_q, int* nsplit_a) {
+static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGroupMember& v, int B, const CvpoGroupTiles& th,
+                             bool small_wgrad, int* nsplit_q, int* nsplit_a) {
     const int nt = s->n_tiles, rp = nt * 16, K = s->ccfg.sample_act_num;
     t = SacGroupMember{};
     v = CvpoGroupMember{};
     t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
     v.PA = s->PA; v.MA = s->MA; v.VA = s->VA;
-    *sa = cvpo_sample_args(c, s, B, stored);
     v.ga = sac_gather_args(c, s, B, s->ccfg.n_step);
     v.at = cvpo_actor_args(c, s, B, CVPO_A_TARGET, s->OBSN, s->eps_t, s->XN, true, th.f_r4 ? 4 * nt : nt);
     v.am = cvpo_actor_args(c, s, B, CVPO_A_MFWD, s->OBS, nullptr, nullptr, false, 0);
@@ -147,19 +147,16 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     if (rc) return rc;
     fsrl_ctx* c0 = gc.m[0];
     SacState* s0 = sac_of(c0);
-    int n_max = 0;
-    for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = gc.m[i];
-        CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
+    ReplayGroupCall call;
+    rc = rgroup_begin(gc, true, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState*) {
         // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
         CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
                   "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
-        if (n_updates[i] > 0) CHECK_ARG(fsrl_store_len(c) > 0, "member %d: empty replay store", i);
-        n_max = std::max(n_max, (int)n_updates[i]);
-    }
+        return 0;
+    });
+    if (rc) return rc;
+    const int n_max = call.n_max;
     if (n_max == 0) return 0;
-    HIPCHK(hipSetDevice(gc.device));
-    HIPCHK(hipStreamSynchronize(gc.stream));           // the pinned tables of the previous call have been read
     const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = s0->n_q;
     const int K = s0->ccfg.sample_act_num, M = s0->ccfg.mstep_iter_num, ntk = (B * K + 15) / 16;
     // tile heights: the single-context rule applied to the group's whole launch (4-row tiles while it fits one round)
@@ -171,44 +168,31 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     th.k_r4 = (size_t)4 * ntk * n_q * k <= (size_t)c0->n_cus && !t16;
     const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
     const size_t n_steps = (size_t)n_max * k, n_iters = n_steps * M;
-    rc = table_ensure(g->steps, n_steps, std::max<size_t>(n_steps, 64));
+    HIPCHK(hipSetDevice(gc.device));
+    rc = table_ensure(g->iters, n_iters, std::max<size_t>(n_iters, 64), gc.stream);    // before any member is touched
     if (rc) return rc;
-    rc = table_ensure(g->iters, n_iters, std::max<size_t>(n_iters, 64));
-    if (rc) return rc;
-    // ---- every member with work joins; its table entries; then the group's stream goes behind the member's
     int nsq = 1, nsa = 1, rq_total = 0, ra_total = 0;
-    std::vector<SacSampleArgs> sas((size_t)k);
-    for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = gc.m[i];
-        if (n_updates[i] == 0) continue;
-        rc = rgroup_join(c, B);
-        if (rc) return rc;
-        SacGroupMember& t = g->tab.h[i];
-        rc = cvpo_group_member(c, sac_of(c), t, g->ctab.h[i], &sas[(size_t)i], B, fsrl_store_len(c), th, small_wgrad, &nsq, &nsa);
-        if (rc) return rc;                             // nsq, nsa, remap totals: one shape, one plan -- the same for every member
-        rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
-        rc = rgroup_ready(gc, i);
-        if (rc) return rc;
-    }
-    // ---- the step tables: what each member's own fsrl_cvpo_update calls would use
-    for (int u = 0; u < n_max; ++u)
+    rc = rgroup_enter(gc, g->steps, call, B, [&]() {
         for (int i = 0; i < k; ++i) {
-            SacGroupStep& st = g->steps.h[(size_t)u * k + i];
-            st = SacGroupStep{};
-            for (int it = 0; it < M; ++it) g->iters.h[((size_t)u * M + it) * k + i] = CvpoGroupIter{};
-            if (u >= n_updates[i]) continue;
-            const fsrl_ctx* c = gc.m[i];
-            const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
-            const int64_t n = s->n_updates + u;
-            st.sa = sas[(size_t)i]; st.sa.counter = (unsigned long long)n; st.row = (int)(n % SAC_RING); st.active = 1;
-            const AdamStep cs = adam_step(s->ccfg.critic_lr, c->cfg.beta1, c->cfg.beta2, s->t_critic + u + 1);
-            st.c_step = cs.step_size; st.c_bc2 = cs.bc2_sqrt;
-            for (int it = 0; it < M; ++it) {           // t_actor advances once per M iteration
-                const AdamStep as = adam_step(s->ccfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + (int64_t)u * M + it + 1);
-                CvpoGroupIter& gi = g->iters.h[((size_t)u * M + it) * k + i];
-                gi.a_step = as.step_size; gi.a_bc2 = as.bc2_sqrt;
-            }
+            if (!call.work[i]) continue;
+            fsrl_ctx* c = gc.m[i];
+            SacGroupMember& t = g->tab.h[i];
+            const int rc = cvpo_group_member(c, sac_of(c), t, g->ctab.h[i], B, th, small_wgrad, &nsq, &nsa);
+            if (rc) return rc;                         // nsq, nsa, remap totals: one shape, one plan -- the same for every member
+            rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
         }
+        return 0;
+    }, [&](int u, int i, SacGroupStep&, const fsrl_ctx* c, const SacState* s) {
+        // the actor's M Adam steps of the update (t_actor advances once per M iteration); zero where the member sits it out
+        for (int it = 0; it < M; ++it) {
+            CvpoGroupIter& gi = g->iters.h[((size_t)u * M + it) * k + i];
+            gi = CvpoGroupIter{};
+            if (!s) continue;
+            const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + (int64_t)u * M + it + 1);
+            gi.a_step = as.step_size; gi.a_bc2 = as.bc2_sqrt;
+        }
+    });
+    if (rc) return rc;
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(g->ctab.d, g->ctab.h, (size_t)k * sizeof(CvpoGroupMember), hipMemcpyHostToDevice, gs));
@@ -257,15 +241,5 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
         return 0;
     });
     if (rc) return rc;
-    HIPCHK(hipEventRecord(gc.done, gs));
-    // ---- each member's streams wait for the call; its bookkeeping is that of n_i own updates
-    for (int i = 0; i < k; ++i) {
-        if (n_updates[i] == 0) continue;
-        rc = rgroup_fanout(gc, i);
-        if (rc) return rc;
-        SacState* s = sac_of(gc.m[i]);
-        s->n_updates += n_updates[i]; s->t_critic += n_updates[i]; s->t_actor += (int64_t)n_updates[i] * M;
-        s->last_B = B;
-    }
-    return 0;
+    return rgroup_end(gc, call, B, M);
 }

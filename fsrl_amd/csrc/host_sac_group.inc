@@ -15,7 +15,7 @@
 // actor in the first half of the forward launch, and its Polyak update in the actor's Adam pass, where SAC-Lag steps alpha.
 // ====================================================================================== grouped SAC-Lagrangian
 // ---- what the grouped SAC and CVPO updates share: the members, the group's stream and the events that order it against the
-//      members' streams.  Each group type embeds one as `core`.
+//      members' streams (each group type embeds one as `core`), and further down the frame of one grouped call.
 struct ReplayGroupCore {
     std::vector<fsrl_ctx*> m;                  // members (not owned; nullptr once destroyed)
     int device = 0;
@@ -68,6 +68,100 @@ static int rgroup_fanout(ReplayGroupCore& g, int i) {
     HIPCHK(hipStreamWaitEvent(g.m[i]->compute, g.done, 0));
     HIPCHK(hipStreamWaitEvent(g.m[i]->side, g.done, 0));     // a push must not overwrite rows the call still samples
     return 0;
+}
+
+// ---- the frame of one grouped call, the same for the fused, the layered (host_sac_group_layered.inc) and the CVPO
+//      (host_cvpo_group.inc) update: rgroup_begin validates, rgroup_enter joins the members and fills the step table, the update
+//      copies its tables and launches, rgroup_end fans out and books.  An update adds its own member checks, its member tables
+//      and whatever its step rows hold beyond the common part.
+struct ReplayGroupCall {
+    const int32_t* n = nullptr;                // [k]: the updates each member runs
+    int k = 0, n_max = 0;
+    char work[FSRL_MAX_GROUP] = {};            // n[i] > 0
+};
+// All validation, before anything is enqueued or any member's state changes.  cvpo: the kind the group was made for (fsrl_sac_init
+// / fsrl_cvpo_init re-create a member's state without telling its group).  member_ok(i, c, s): the update's own checks of a
+// member that is still of the group's kind.  call.n_max == 0 afterwards: nothing to do.
+// A CVPO context's cfg mirrors its ccfg in n_step and both learning rates (fsrl_cvpo_init and fsrl_set_lr keep the two equal), so
+// the frame reads cfg for every kind.
+template <class MemberOk>
+static int rgroup_begin(const ReplayGroupCore& g, bool cvpo, const int32_t* n_updates, ReplayGroupCall& call, MemberOk&& member_ok) {
+    call.n = n_updates; call.k = (int)g.m.size();
+    const SacState* s0 = sac_of(g.m[0]);
+    for (int i = 0; i < call.k; ++i) {
+        fsrl_ctx* c = g.m[i];
+        const SacState* s = sac_of(c);
+        CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
+        CHECK_ARG(s && s->cvpo == cvpo && s->ddpg == s0->ddpg && s->layered == s0->layered && s->cfg.n_step == s0->cfg.n_step,
+                  "member %d is no longer a context of the group's kind and shape", i);
+        const int rc = member_ok(i, c, s);
+        if (rc) return rc;
+        if (n_updates[i] > 0) CHECK_ARG(fsrl_store_len(c) > 0, "member %d: empty replay store", i);
+        call.n_max = std::max(call.n_max, (int)n_updates[i]);
+        call.work[i] = n_updates[i] > 0;
+    }
+    return 0;
+}
+// Every member with work joins (a join may regrow a member's working set and move its buffers); THEN build_tables() forms the
+// update's member tables; then the group's stream goes behind each member's.  Last the step table, what each member's own
+// updates would use: row(u, i, st, c, s) adds the update's own part to an active row, (u, i, st, nullptr, nullptr) to a row member
+// i sits out.
+template <class BuildTables, class Row>
+static int rgroup_enter(ReplayGroupCore& g, DevTable<SacGroupStep>& steps, const ReplayGroupCall& call, int B, BuildTables&& build_tables,
+                        Row&& row) {
+    const int k = call.k;
+    HIPCHK(hipSetDevice(g.device));
+    HIPCHK(hipStreamSynchronize(g.stream));            // the pinned tables of the previous call have been read
+    int rc = table_ensure(steps, (size_t)call.n_max * k, std::max<size_t>((size_t)call.n_max * k, 64));
+    if (rc) return rc;
+    for (int i = 0; i < k; ++i)
+        if (call.work[i]) { rc = rgroup_join(g.m[i], B); if (rc) return rc; }
+    rc = build_tables();
+    if (rc) return rc;
+    SacSampleArgs sa[FSRL_MAX_GROUP];                  // the member's sample; the counter is the step's
+    for (int i = 0; i < k; ++i) {
+        if (!call.work[i]) continue;
+        rc = rgroup_ready(g, i);
+        if (rc) return rc;
+        const fsrl_ctx* c = g.m[i];
+        const SacState* s = sac_of(g.m[i]);
+        sa[i] = s->cvpo ? cvpo_sample_args(c, s, B, fsrl_store_len(g.m[i])) : sac_sample_args(c, s, B, s->cfg.n_step, fsrl_store_len(g.m[i]), 0);
+    }
+    for (int u = 0; u < call.n_max; ++u)
+        for (int i = 0; i < k; ++i) {
+            SacGroupStep& st = steps.h[(size_t)u * k + i];
+            st = SacGroupStep{};
+            if (u >= call.n[i]) { row(u, i, st, nullptr, nullptr); continue; }
+            const fsrl_ctx* c = g.m[i];
+            const SacState* s = sac_of(g.m[i]);
+            const int64_t n = s->n_updates + u;
+            st.sa = sa[i]; st.sa.counter = (unsigned long long)n; st.row = (int)(n % SAC_RING); st.active = 1;
+            const AdamStep cs = adam_step(s->cfg.critic_lr, c->cfg.beta1, c->cfg.beta2, s->t_critic + u + 1);
+            st.c_step = cs.step_size; st.c_bc2 = cs.bc2_sqrt;
+            row(u, i, st, c, s);
+        }
+    return 0;
+}
+// After the launches: `done`, each member's streams wait for the call, and its bookkeeping is that of n_i own updates with
+// actor_steps Adam steps of the actor each.
+static int rgroup_end(ReplayGroupCore& g, const ReplayGroupCall& call, int B, int actor_steps) {
+    HIPCHK(hipEventRecord(g.done, g.stream));
+    for (int i = 0; i < call.k; ++i) {
+        if (!call.work[i]) continue;
+        const int rc = rgroup_fanout(g, i);
+        if (rc) return rc;
+        SacState* s = sac_of(g.m[i]);
+        s->n_updates += call.n[i]; s->t_critic += call.n[i]; s->t_actor += (int64_t)call.n[i] * actor_steps;
+        s->last_B = B;
+        s->pre_valid = false;                          // no rider blocks ran: the member's next own update draws its sample
+    }
+    return 0;
+}
+// the step row of a SAC-Lag or DDPG-Lag member: one Adam step of the actor per update
+static void sac_group_step_row(int u, SacGroupStep& st, const fsrl_ctx* c, const SacState* s) {
+    if (!s) return;
+    const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + u + 1);
+    st.a_step = as.step_size; st.a_bc2 = as.bc2_sqrt;
 }
 
 // a group of layered members (all fused or all layered): host_sac_group_layered.inc
@@ -165,7 +259,7 @@ static int group_wgrad_split(fsrl_ctx* c, const SacState* s, FbWgradArgs& wa, co
 }
 
 // the member's table entry: every argument of the nine launches as fsrl_sac_update forms it (library RNG, fold path)
-static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, int64_t stored, const double* lags, double rescaling,
+static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, const double* lags, double rescaling,
                             bool q_r4, bool a_r4, bool f_r4, bool small_wgrad, int* nsplit_q, int* nsplit_a) {
     const int ns = s->cfg.n_step, nt = s->n_tiles, rp = nt * 16;
     const float lam = (s->cfg.use_lagrangian && lags) ? (float)lags[0] : 0.0f;
@@ -174,11 +268,11 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
     t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
     t.PAT = s->ddpg ? s->PAT : nullptr;        // DDPG-Lag: the forward launch's first half runs it, the actor's Adam pass moves it
     // ---- actors (probe = 0: a probe build's phases are the solo path's); the forward launch carries the current actor's batch
-    //      and the sample + gather (sa.counter per step)
+    //      and the sample + gather (the sample's arguments: the step table's, rgroup_enter)
     const int det = s->ddpg ? 1 : 0;
     t.af = sac_actor_args(c, s, B, SAC_A_FWD, s->OBSN, s->eps_t, s->XN, s->LPN, resc, lam, det, 0);
     t.af.P2 = s->PA; t.af.obs2 = s->OBS; t.af.eps2 = s->eps_p; t.af.X2 = s->XP; t.af.lp2 = s->LP; t.af.tiles_half = f_r4 ? 4 * nt : nt;
-    t.af.sg_on = 1; t.af.sa = sac_sample_args(c, s, B, ns, stored, 0); t.af.ga = sac_gather_args(c, s, B, ns);
+    t.af.sg_on = 1; t.af.ga = sac_gather_args(c, s, B, ns);
     t.ab = sac_actor_args(c, s, B, SAC_A_BWD, s->OBS, s->eps_p, s->XP, s->LP, resc, lam, det, 0);
     // ---- Q-network tile launches
     const SacNstepArgs na = sac_nstep_args(c, s, B);
@@ -242,24 +336,19 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     fsrl_ctx* c0 = gc.m[0];
     SacState* s0 = sac_of(c0);
     if (s0 && s0->layered) return lay_sac_group_update(g, B, n_updates, lagrangians, rescaling);
-    int n_max = 0;
-    for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = gc.m[i];
-        const SacState* s = sac_of(c);
-        CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
-        CHECK_ARG(s && !s->cvpo && s->ddpg == s0->ddpg && !s->layered && s->cfg.n_step == s0->cfg.n_step, "member %d is no longer a context of the group's kind and shape", i);
+    ReplayGroupCall call;
+    int rc = rgroup_begin(gc, false, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState* s) {
         CHECK_ARG(s->wgrad_splitk == s0->wgrad_splitk, "members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)");
         // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
         // (fb_wgrad2_kernel); the tiled kernel fb_wgrad3_kernel needs re-laid observations the replay agents never hand over
         CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
                   "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
-        if (n_updates[i] > 0) CHECK_ARG(fsrl_store_len(c) > 0, "member %d: empty replay store", i);
-        n_max = std::max(n_max, (int)n_updates[i]);
-    }
+        return 0;
+    });
+    if (rc) return rc;
     CHECK_ARG(!s0->cfg.use_lagrangian || lagrangians, "lagrangians: [k][n_critics - 1] when use_lagrangian is on");
+    const int n_max = call.n_max;
     if (n_max == 0) return 0;
-    HIPCHK(hipSetDevice(gc.device));
-    HIPCHK(hipStreamSynchronize(gc.stream));           // the pinned tables of the previous call have been read
     const int H = c0->cfg.hidden, nt = (B + 15) / 16, rp = nt * 16, n_q = s0->n_q;     // 4 (SAC-Lag) or 2 (DDPG-Lag)
     // tile heights: the single-context rule applied to the group's whole launch (4-row tiles while it fits one round)
     const bool t16 = c0->probe_tile16;
@@ -268,38 +357,21 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     const bool f_r4 = a_r4 && (size_t)8 * nt * k <= (size_t)c0->n_cus;
     const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
     const size_t lag_stride = (size_t)std::max(1, c0->cfg.n_critics - 1);
-    int rc = table_ensure(g->steps, (size_t)n_max * k, std::max<size_t>((size_t)n_max * k, 64));
-    if (rc) return rc;
-    // ---- every member with work joins; its table entry; then the group's stream goes behind the member's
     int nsq = 1, nsa = 1, rq_total = 0, ra_total = 0;
-    for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = gc.m[i];
-        if (n_updates[i] == 0) continue;
-        rc = rgroup_join(c, B);
-        if (rc) return rc;
-        // the member's own side-stream prefetch writes the other set of batch buffers only: nothing to wait for
-        const double* lg = s0->cfg.use_lagrangian ? lagrangians + (size_t)i * lag_stride : nullptr;
-        SacGroupMember& t = g->tab.h[i];
-        rc = sac_group_member(c, sac_of(c), t, B, fsrl_store_len(c), lg, rescaling[i], q_r4, a_r4, f_r4, small_wgrad, &nsq, &nsa);
-        if (rc) return rc;                             // nsq, nsa, remap totals: one shape, one plan -- the same for every member
-        rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
-        rc = rgroup_ready(gc, i);
-        if (rc) return rc;
-    }
-    // ---- the step table: what each member's own fsrl_sac_update calls would use
-    for (int u = 0; u < n_max; ++u)
+    rc = rgroup_enter(gc, g->steps, call, B, [&]() {
         for (int i = 0; i < k; ++i) {
-            SacGroupStep& st = g->steps.h[(size_t)u * k + i];
-            st = SacGroupStep{};
-            if (u >= n_updates[i]) continue;
-            const fsrl_ctx* c = gc.m[i];
-            const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
-            const int64_t n = s->n_updates + u;
-            st.sa = g->tab.h[i].af.sa; st.sa.counter = (unsigned long long)n; st.row = (int)(n % SAC_RING); st.active = 1;
-            const AdamStep cs = adam_step(s->cfg.critic_lr, c->cfg.beta1, c->cfg.beta2, s->t_critic + u + 1);
-            const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + u + 1);
-            st.c_step = cs.step_size; st.c_bc2 = cs.bc2_sqrt; st.a_step = as.step_size; st.a_bc2 = as.bc2_sqrt;
+            if (!call.work[i]) continue;
+            // the member's own side-stream prefetch writes the other set of batch buffers only: nothing to wait for
+            fsrl_ctx* c = gc.m[i];
+            const double* lg = s0->cfg.use_lagrangian ? lagrangians + (size_t)i * lag_stride : nullptr;
+            SacGroupMember& t = g->tab.h[i];
+            const int rc = sac_group_member(c, sac_of(c), t, B, lg, rescaling[i], q_r4, a_r4, f_r4, small_wgrad, &nsq, &nsa);
+            if (rc) return rc;                         // nsq, nsa, remap totals: one shape, one plan -- the same for every member
+            rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
         }
+        return 0;
+    }, [](int u, int, SacGroupStep& st, const fsrl_ctx* c, const SacState* s) { sac_group_step_row(u, st, c, s); });
+    if (rc) return rc;
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
@@ -332,16 +404,5 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
         return 0;
     });
     if (rc) return rc;
-    HIPCHK(hipEventRecord(gc.done, gs));
-    // ---- each member's streams wait for the call; its bookkeeping is that of n_i own updates
-    for (int i = 0; i < k; ++i) {
-        if (n_updates[i] == 0) continue;
-        rc = rgroup_fanout(gc, i);
-        if (rc) return rc;
-        SacState* s = sac_of(gc.m[i]);
-        s->n_updates += n_updates[i]; s->t_critic += n_updates[i]; s->t_actor += n_updates[i];
-        s->last_B = B;
-        s->pre_valid = false;                                // no rider blocks ran: the member's next own update draws its sample
-    }
-    return 0;
+    return rgroup_end(gc, call, B, 1);
 }

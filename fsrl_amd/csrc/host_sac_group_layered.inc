@@ -205,51 +205,18 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
                                 const double* rescaling) {
     ReplayGroupCore& gc = g->core;
     const int k = (int)gc.m.size();
-    fsrl_ctx* c0 = gc.m[0];
-    SacState* s0 = sac_of(c0);
-    int n_max = 0;
-    char work[FSRL_MAX_GROUP] = {};
-    for (int i = 0; i < k; ++i) {
-        fsrl_ctx* c = gc.m[i];
-        const SacState* s = sac_of(c);
-        CHECK_ARG(n_updates[i] >= 0, "n_updates[%d] < 0", i);
-        CHECK_ARG(s && !s->cvpo && s->ddpg == s0->ddpg && s->layered && s->cfg.n_step == s0->cfg.n_step,
-                  "member %d is no longer a context of the group's kind and shape", i);
-        if (n_updates[i] > 0) CHECK_ARG(fsrl_store_len(c) > 0, "member %d: empty replay store", i);
-        n_max = std::max(n_max, (int)n_updates[i]);
-        work[i] = n_updates[i] > 0;
-    }
+    const SacState* s0 = sac_of(gc.m[0]);
+    ReplayGroupCall call;
+    int rc = rgroup_begin(gc, false, n_updates, call, [](int, const fsrl_ctx*, const SacState*) { return 0; });
+    if (rc) return rc;
     CHECK_ARG(!s0->cfg.use_lagrangian || lagrangians, "lagrangians: [k][n_critics - 1] when use_lagrangian is on");
+    const int n_max = call.n_max;
     if (n_max == 0) return 0;
-    HIPCHK(hipSetDevice(gc.device));
-    HIPCHK(hipStreamSynchronize(gc.stream));           // the pinned tables of the previous call have been read
     if (!g->lay) g->lay = new LaySacGroup();
     LaySacGroup& lg = *g->lay;
-    int rc = table_ensure(g->steps, (size_t)n_max * k, std::max<size_t>((size_t)n_max * k, 64));
+    rc = rgroup_enter(gc, g->steps, call, B, [&]() { return lay_sac_group_tables(g, lg, B, call.work, lagrangians, rescaling); },
+                      [](int u, int, SacGroupStep& st, const fsrl_ctx* c, const SacState* s) { sac_group_step_row(u, st, c, s); });
     if (rc) return rc;
-    // ---- every member with work joins (its working sets may regrow and move); THEN the tables; then the group's stream goes
-    //      behind the members'
-    for (int i = 0; i < k; ++i)
-        if (work[i]) { rc = rgroup_join(gc.m[i], B); if (rc) return rc; }
-    rc = lay_sac_group_tables(g, lg, B, work, lagrangians, rescaling);
-    if (rc) return rc;
-    for (int i = 0; i < k; ++i)
-        if (work[i]) { rc = rgroup_ready(gc, i); if (rc) return rc; }
-    // ---- the step table: what each member's own fsrl_sac_update calls would use
-    for (int u = 0; u < n_max; ++u)
-        for (int i = 0; i < k; ++i) {
-            SacGroupStep& st = g->steps.h[(size_t)u * k + i];
-            st = SacGroupStep{};
-            if (u >= n_updates[i]) continue;
-            const fsrl_ctx* c = gc.m[i];
-            const SacState* s = sac_of(const_cast<fsrl_ctx*>(c));
-            const int64_t n = s->n_updates + u;
-            st.sa = sac_sample_args(c, s, B, s->cfg.n_step, fsrl_store_len(const_cast<fsrl_ctx*>(c)), n);
-            st.row = (int)(n % SAC_RING); st.active = 1;
-            const AdamStep cs = adam_step(s->cfg.critic_lr, c->cfg.beta1, c->cfg.beta2, s->t_critic + u + 1);
-            const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + u + 1);
-            st.c_step = cs.step_size; st.c_bc2 = cs.bc2_sqrt; st.a_step = as.step_size; st.a_bc2 = as.bc2_sqrt;
-        }
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
     const ModelDesc mda = s0->mda, mdq = s0->mdq;
@@ -286,18 +253,7 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
         }
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(gc.done, gs));
-    // ---- each member's streams wait for the call; its bookkeeping is that of n_i own updates
-    for (int i = 0; i < k; ++i) {
-        if (!work[i]) continue;
-        rc = rgroup_fanout(gc, i);
-        if (rc) return rc;
-        SacState* s = sac_of(gc.m[i]);
-        s->n_updates += n_updates[i]; s->t_critic += n_updates[i]; s->t_actor += n_updates[i];
-        s->last_B = B;
-        s->pre_valid = false;
-    }
-    return 0;
+    return rgroup_end(gc, call, B, 1);
 }
 
 // ---------------------------------------------------------------- lock-step collection

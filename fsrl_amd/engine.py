@@ -709,9 +709,35 @@ class Engine:
                     fwdbwd_raw_ms=out[4])
 
 
-class _LockStepCollect:
+class _NativeGroup:
+    """`engines`, `lib` and the native handle `_g` of a group made by `<_symbols>_create` and freed by `<_symbols>_destroy`"""
+    _symbols = ""                       # the C ABI prefix of the group: fsrl_group, fsrl_sac_group, ...
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        assert self.engines, "a group needs at least one engine"
+        self.lib = self.engines[0].lib
+        k = len(self.engines)
+        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
+        self._g = C.c_void_p()
+        _lib.check(getattr(self.lib, self._symbols + "_create")(arr, k, C.byref(self._g)))
+
+    def close(self):
+        if getattr(self, "_g", None) is not None and self._g:
+            getattr(self.lib, self._symbols + "_destroy")(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _LockStepCollect(_NativeGroup):
     """collect_step of an object that owns `engines`, a native group handle `_g` and a `_collect_step_symbol` with
-    fsrl_group_collect_step's signature: the staging arrays and the call, shared by EngineGroup and EngineCollectGroup."""
+    fsrl_group_collect_step's signature: the staging arrays and the call, shared by EngineGroup and EngineCollectGroup, and the
+    three `<_symbols>_actor_*` calls of the group's resident collect kernel."""
     _collect_stage = None               # cached staging arrays + ctypes pointers of collect_step
 
     def collect_step(self, prevs, obs_acts, deterministic=False, bound_method=1, low=None, high=None):
@@ -773,6 +799,21 @@ class _LockStepCollect:
         k = int(a["k"].sum())
         return a["ptr"][:k], a["ei"][:k]
 
+    def actor_set_resident(self, on=True, idle_timeout_us=0.0):
+        """The group's resident collect kernel (include/fsrl_hip.h: fsrl_group_actor_set_resident,
+        fsrl_collect_group_actor_set_resident); on by default."""
+        _lib.check(getattr(self.lib, self._symbols + "_actor_set_resident")(self._g, int(bool(on)), float(idle_timeout_us)))
+
+    def actor_release(self):
+        """End the group's resident collect kernel now (a grouped collect is over)."""
+        if getattr(self, "_g", None) is not None and self._g:
+            getattr(self.lib, self._symbols + "_actor_release")(self._g)
+
+    def actor_resident_stats(self):
+        out = np.zeros(3, np.int64)
+        _lib.check(getattr(self.lib, self._symbols + "_actor_resident_stats")(self._g, _ptr(out, _i64p)))
+        return dict(launches=int(out[0]), requests=int(out[1]), live=bool(out[2]))
+
 
 class EngineGroup(_LockStepCollect):
     """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
@@ -784,41 +825,8 @@ class EngineGroup(_LockStepCollect):
     launches for all members instead of a resident kernel (actor_resident_stats counts those sequences, `live` stays False;
     actor_set_resident(False) selects the member-by-member calls; set_plan is accepted and has no effect)."""
 
+    _symbols = "fsrl_group"
     _collect_step_symbol = "fsrl_group_collect_step"
-
-    def __init__(self, engines):
-        self.engines = list(engines)
-        assert self.engines, "a group needs at least one engine"
-        self.lib = self.engines[0].lib
-        k = len(self.engines)
-        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
-        self._g = C.c_void_p()
-        _lib.check(self.lib.fsrl_group_create(arr, k, C.byref(self._g)))
-
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def actor_set_resident(self, on=True, idle_timeout_us=0.0):
-        """The group's resident collect kernel (include/fsrl_hip.h: fsrl_group_actor_set_resident); on by default."""
-        _lib.check(self.lib.fsrl_group_actor_set_resident(self._g, int(bool(on)), float(idle_timeout_us)))
-
-    def actor_release(self):
-        """End the group's resident collect kernel now (a grouped collect is over)."""
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_group_actor_release(self._g)
-
-    def actor_resident_stats(self):
-        out = np.zeros(3, np.int64)
-        _lib.check(self.lib.fsrl_group_actor_resident_stats(self._g, _ptr(out, _i64p)))
-        return dict(launches=int(out[0]), requests=int(out[1]), live=bool(out[2]))
 
     def set_plan(self, tall_tiles=-1):
         """32-row tiles per (member, network) in the forward / backward launch: -1 automatic, 0 none, n > 0 a count (A/B; same bits)."""
@@ -862,7 +870,7 @@ class EngineGroup(_LockStepCollect):
         return [s[:, :_lib.FOCOPS_NSTATS] for s in stats], stopped
 
 
-class EngineSacGroup:
+class EngineSacGroup(_NativeGroup):
     """k SAC-Lagrangian engines (sac_init, stochastic actor), or k DDPG-Lagrangian engines (sac_init(deterministic=True)),
     of one shape on one GPU, updated in lock step (fsrl_sac_group_*): every launch of an update carries all members that
     still have updates to run.  The group's kind is its first member's; the two kinds do not mix.  Members keep their
@@ -871,26 +879,7 @@ class EngineSacGroup:
     The members are all fused (two hidden layers of at most 256 units) or all layered contexts of one `hidden_sizes` and
     `force_layered`: a layered group runs the layered update's launch sequence with every member in each launch, and a member's
     grouped update is then bit-identical to its own sac_update at every group size."""
-
-    def __init__(self, engines):
-        self.engines = list(engines)
-        assert self.engines, "a group needs at least one engine"
-        self.lib = self.engines[0].lib
-        k = len(self.engines)
-        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
-        self._g = C.c_void_p()
-        _lib.check(self.lib.fsrl_sac_group_create(arr, k, C.byref(self._g)))
-
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_sac_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _symbols = "fsrl_sac_group"
 
     def update(self, batch_size, n_updates, lagrangians=None, rescalings=None):
         """n_updates[i] x Engine.sac_update(batch_size, ..., sync=False) on member i (library RNG), all in lock step.
@@ -904,31 +893,12 @@ class EngineSacGroup:
                                                   _ptr(lag, _f64p) if lag is not None and lag.size else None, _ptr(resc, _f64p)))
 
 
-class EngineCvpoGroup:
+class EngineCvpoGroup(_NativeGroup):
     """k CVPO engines (cvpo_init) of one launch structure on one GPU, updated in lock step (fsrl_cvpo_group_*): every launch of
     an update carries all members that still have updates to run.  Members keep their own streams, stores, parameters, duals,
     Philox keys and statistics rings, and stay ordinary engines between updates (push, collect_step with the resident actor,
     cvpo_pre_update / cvpo_post_update / cvpo_set_thres, own cvpo_update calls, sac_drain ...)."""
-
-    def __init__(self, engines):
-        self.engines = list(engines)
-        assert self.engines, "a group needs at least one engine"
-        self.lib = self.engines[0].lib
-        k = len(self.engines)
-        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
-        self._g = C.c_void_p()
-        _lib.check(self.lib.fsrl_cvpo_group_create(arr, k, C.byref(self._g)))
-
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_cvpo_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _symbols = "fsrl_cvpo_group"
 
     def update(self, batch_size, n_updates):
         """n_updates[i] x Engine.cvpo_update(batch_size, sync=False) on member i (library RNG), all in lock step.  Enqueues only:
@@ -947,38 +917,5 @@ class EngineCollectGroup(_LockStepCollect):
     SAC-Lag / DDPG-Lag members may all be layered contexts of one `hidden_sizes` (not CVPO members yet): the group then has no
     resident kernel -- a request is one launch sequence (L + 2 launches) for all members, actor_set_resident is accepted and has no
     effect, actor_release does nothing and actor_resident_stats counts the requests."""
+    _symbols = "fsrl_collect_group"
     _collect_step_symbol = "fsrl_collect_group_step"
-
-    def __init__(self, engines):
-        self.engines = list(engines)
-        assert self.engines, "a group needs at least one engine"
-        self.lib = self.engines[0].lib
-        k = len(self.engines)
-        arr = (C.c_void_p * k)(*[e._ctx for e in self.engines])
-        self._g = C.c_void_p()
-        _lib.check(self.lib.fsrl_collect_group_create(arr, k, C.byref(self._g)))
-
-    def close(self):
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_collect_group_destroy(self._g)
-            self._g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def actor_set_resident(self, on=True, idle_timeout_us=0.0):
-        """The group's resident collect kernel (include/fsrl_hip.h: fsrl_collect_group_actor_set_resident); on by default."""
-        _lib.check(self.lib.fsrl_collect_group_actor_set_resident(self._g, int(bool(on)), float(idle_timeout_us)))
-
-    def actor_release(self):
-        """End the group's resident collect kernel now (a grouped collect is over)."""
-        if getattr(self, "_g", None) is not None and self._g:
-            self.lib.fsrl_collect_group_actor_release(self._g)
-
-    def actor_resident_stats(self):
-        out = np.zeros(3, np.int64)
-        _lib.check(self.lib.fsrl_collect_group_actor_resident_stats(self._g, _ptr(out, _i64p)))
-        return dict(launches=int(out[0]), requests=int(out[1]), live=bool(out[2]))

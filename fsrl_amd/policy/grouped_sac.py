@@ -9,17 +9,19 @@ rows, same lr_scheduler steps.
     group.update(buffers, batch_size=256, n_updates=[n_0, n_1, ...])
     ... post_update_fn per agent (drains the rows into its logger) ...
 
-`ReplayPolicyGroup` holds the loop; `SACPolicyGroup` here and `DDPGPolicyGroup` (grouped_ddpg.py) name their policy class."""
+`ReplayPolicyGroup` holds the loop; `SACPolicyGroup` here and `DDPGPolicyGroup` (grouped_ddpg.py) name their policy class, and
+`CVPOPolicyGroup` (grouped_cvpo.py) its engine group and its engine call as well."""
 from typing import Sequence, Union
 
 from fsrl_amd.engine import EngineSacGroup
 from fsrl_amd.policy.sac_lag import SACLagrangian
 
-_RING_DRAIN = 2048          # SACLagrangian.learn / DDPGLagrangian.learn drain their statistics ring after this many pending updates
+_RING_DRAIN = 2048          # the policies' learn() drains their statistics ring after this many pending updates
 
 
 class ReplayPolicyGroup:
-    """k policies of `policy_cls` over an EngineSacGroup (fsrl_sac_group_*); subclasses set `policy_cls` and `algo_name`"""
+    """k policies of `policy_cls` over an EngineSacGroup (fsrl_sac_group_*); subclasses set `policy_cls` and `algo_name`, and
+    override `_make_group` / `_update_args` where their engine group is another"""
     policy_cls: type = None
     algo_name: str = ""
 
@@ -31,7 +33,20 @@ class ReplayPolicyGroup:
         # reference_rng=True draws the sample and the noise from the host's numpy / torch streams, one update at a time: a grouped
         # update has the device's Philox streams only
         assert not any(getattr(p, "_reference_rng", False) for p in self.policies), "reference_rng policies cannot be grouped"
-        self.group = engine_group if engine_group is not None else EngineSacGroup([p.engine for p in self.policies])
+        self.group = engine_group if engine_group is not None else self._make_group([p.engine for p in self.policies])
+
+    def _make_group(self, engines):
+        return EngineSacGroup(engines)
+
+    def _update_args(self):
+        """what `group.update(B, step, ...)` takes after the counts, the same for every chunk of one update"""
+        pols = self.policies
+        lags, resc = [], []
+        for p in pols:
+            lg, rs = p.lagrangians_and_rescaling() if p.use_lagrangian else ([], 1.0)
+            lags.append([float(x) for x in lg] or [0.0])
+            resc.append(float(rs))
+        return (lags if pols[0].use_lagrangian else None, resc)
 
     def close(self):
         self.group.close()
@@ -54,18 +69,13 @@ class ReplayPolicyGroup:
                     p.update(B, b)
                     p.updating = True
                     n[i] -= 1
-            use_lag = pols[0].use_lagrangian
-            lags, resc = [], []
-            for p in pols:
-                lg, rs = p.lagrangians_and_rescaling() if p.use_lagrangian else ([], 1.0)
-                lags.append([float(x) for x in lg] or [0.0])
-                resc.append(float(rs))
+            args = self._update_args()
             # an lr scheduler moves the rates between two updates: one update per grouped call then
             per_call = 1 if any(p.lr_scheduler is not None for p in pols) else _RING_DRAIN
             left = list(n)
             while any(left):
                 step = [min(x, per_call, _RING_DRAIN - p._pending) for x, p in zip(left, pols)]
-                self.group.update(B, step, lags if use_lag else None, resc)
+                self.group.update(B, step, *args)
                 for i, p in enumerate(pols):
                     if not step[i]:
                         continue
