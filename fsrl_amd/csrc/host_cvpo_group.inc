@@ -165,7 +165,12 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     th.q_r4 = (size_t)4 * nt * n_q * k <= (size_t)c0->n_cus && !t16;
     th.a_r4 = (size_t)4 * nt * k <= (size_t)c0->n_cus && !t16;
     th.f_r4 = th.a_r4 && (size_t)8 * nt * k <= (size_t)c0->n_cus;
-    th.k_r4 = (size_t)4 * ntk * n_q * k <= (size_t)c0->n_cus && !t16;
+    // the particle launch has K times the rows of any other launch, so under the whole-launch rule it was the first to leave
+    // four-row tiles as k grows and alone decided where a small-batch group stops being bit-identical to fsrl_cvpo_update (B 32, K 8:
+    // k = 2, while the B-row launches fit one round up to k = 16).  It keeps the height a member's own update gives it
+    // (sac_alloc_batch: k_rows4, four-row tiles up to 4 n_tiles_k n_q <= CUs, i.e. K * B <= 512 rows with single critics).  The
+    // benchmarked shapes (K * B = 4096 and up) run sixteen-row tiles under either rule.
+    th.k_r4 = (size_t)4 * ntk * n_q <= (size_t)c0->n_cus && !t16;
     const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
     const size_t n_steps = (size_t)n_max * k, n_iters = n_steps * M;
     HIPCHK(hipSetDevice(gc.device));

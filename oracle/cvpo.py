@@ -154,6 +154,35 @@ class CVPOOracle:
         """Independent(Normal(mu, sigma), 1).log_prob(a)"""
         return (-((a - mu)**2) / (2 * sigma**2) - sigma.log() - LOG_SQRT_2PI).sum(-1)
 
+    # ------------------------------------------------------------------ the dual steps (methods of their own: the sensitivity
+    # runs of tests/cvpo_dual_problems.py override them one at a time)
+    def estep_cost_q(self, obs_k, act_k):
+        """the cost value of the E-step's particles: the DoubleCritic's min (cvpo.py:341-351)"""
+        return self.q_predict(self.critics[1], obs_k, act_k)
+
+    def estep_duals(self, q, stats):
+        """cvpo.py:278-288, 353-365: estep_iter_num Adam steps on (eta, lambda), the clamp after the loop.  q = [q_r, q_c], each
+        [B,K]; q[0] is overwritten by every iteration (the aliasing of the module docstring)."""
+        cfg = self.cfg
+        K = q[0].shape[1]
+        for it in range(cfg.estep_iter_num):
+            self.estep_optim.zero_grad()
+            eta = self.estep_dual[0]
+            combined = q[0] - self.estep_dual[1] * q[1]
+            loss = eta * cfg.estep_kl + self.estep_dual[1] * cfg.qc_thres
+            loss = loss + eta * torch.mean(torch.logsumexp(combined / eta, dim=1) - np.log(K))
+            loss.backward()
+            self.estep_optim.step()
+            q[0] = combined.detach()                       # the in-place aliasing of cvpo.py:282-285
+            if it == 0:
+                stats["loss/estep_loss"] = loss.item()
+        self.estep_dual.data.clamp_(min=EPS10, max=cfg.estep_dual_max)
+
+    def mstep_multipliers(self):
+        """what the M-step's actor loss uses: the stored multipliers clipped to [0, mstep_dual_max] (cvpo.py:399-400)"""
+        return (float(np.clip(self.mstep_dual_mu.item(), 0.0, self.cfg.mstep_dual_max)),
+                float(np.clip(self.mstep_dual_std.item(), 0.0, self.cfg.mstep_dual_max)))
+
     # ------------------------------------------------------------------ update
     def update(self, store, index: ReplayIndex, indices, eps_target, eps_particles):
         """One CVPO.update: process_fn + learn.  store: dict of SLOT-indexed arrays."""
@@ -203,22 +232,13 @@ class CVPOOracle:
             mu_old, std_old = self.pi(self.actor_old, obs)
             particles = t(eps_particles) * std_old.expand(K, B, -1) + mu_old.expand(K, B, -1)      # [K,B,Da]
             obs_k = obs[None].expand(K, -1, -1).reshape(K * B, -1)
-            q = [self.q_predict(self.critics[i], obs_k, particles.reshape(K * B, -1)).reshape(K, B).T.clone()
-                 for i in range(2)]                                                               # [B,K] each
-        for it in range(cfg.estep_iter_num):
-            self.estep_optim.zero_grad()
-            eta = self.estep_dual[0]
-            combined = q[0] - self.estep_dual[1] * q[1]
-            loss = eta * cfg.estep_kl + self.estep_dual[1] * cfg.qc_thres
-            loss = loss + eta * torch.mean(torch.logsumexp(combined / eta, dim=1) - np.log(K))
-            loss.backward()
-            self.estep_optim.step()
-            q[0] = combined.detach()                       # the in-place aliasing of cvpo.py:282-285
-            if it == 0:
-                stats["loss/estep_loss"] = loss.item()
-        self.estep_dual.data.clamp_(min=EPS10, max=cfg.estep_dual_max)
+            act_k = particles.reshape(K * B, -1)
+            q = [v.reshape(K, B).T.clone() for v in (self.q_predict(self.critics[0], obs_k, act_k),
+                                                     self.estep_cost_q(obs_k, act_k))]           # [B,K] each
+        self.estep_duals(q, stats)
         d0, d1 = self.estep_dual[0].item(), self.estep_dual[1].item()
         stats["estep/dual0"], stats["estep/dual1"] = d0, d1
+        self.combined = (q[0] - d1 * q[1]).detach()          # [B,K]: what the weights are the softmax of, times eta
         w = torch.softmax((q[0].T - d1 * q[1].T) / d0, dim=0)                                    # [K,B]
         # ---- M-step (cvpo.py:378-417)
         for it in range(cfg.mstep_iter_num):
@@ -234,8 +254,7 @@ class CVPOOracle:
             self.mstep_optim.zero_grad()
             dual_loss.backward()
             self.mstep_optim.step()
-            dual_mu = float(np.clip(self.mstep_dual_mu.item(), 0.0, cfg.mstep_dual_max))
-            dual_std = float(np.clip(self.mstep_dual_std.item(), 0.0, cfg.mstep_dual_max))
+            dual_mu, dual_std = self.mstep_multipliers()
             loss_kl = dual_mu * (kl_mu - cfg.mstep_kl_mu) + dual_std * (kl_std - cfg.mstep_kl_std)
             loss_actor = loss_mle + loss_kl
             self.actor_optim.zero_grad()

@@ -5,6 +5,9 @@ only.  Records the replay store, parameters, the sampled indices and every N(0,1
 stats / parameters / duals after a few collect cycles (pre_update_fn .. updates .. post_update_fn).
 
     python tests/golden/gen_golden_cvpo.py
+    python tests/golden/gen_golden_cvpo.py depths      # hidden_sizes the fused kernels do not hold
+    python tests/golden/gen_golden_cvpo.py costly      # a cost threshold BELOW Qc: lambda grows, the duals meet their upper clamps;
+                                                       # each fixture's census (tests/cvpo_dual_problems.py::costly_census) is asserted
 """
 import json
 import os
@@ -36,7 +39,10 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, cycles, up
         max_action=1.0, cost_limit=10.0, max_episode_steps=100, tau=0.05, actor_lr=5e-4, critic_lr=1e-3,
         gamma=0.98, double_critic=False, sample_act_num=16, estep_iter_num=1, mstep_iter_num=1, estep_kl=0.02,
         estep_dual_max=20.0, estep_dual_lr=0.02, mstep_kl_mu=0.005, mstep_kl_std=0.0005, mstep_dual_max=0.5,
-        mstep_dual_lr=0.1):
+        mstep_dual_lr=0.1, census=None, critics_stride=1):
+    """census: a check of the recorded duals, run before the file is written (name, estep_dual, stats_keys, stats, cfg) -> a line.
+    critics_stride: theta_critics_final / theta_critics_old_final keep every critics_stride-th entry (the fixture then carries
+    `theta_final_stride`): what keeps a wide DoubleCritic case small."""
     seed_all(seed)
     actor = ActorProb(Net((obs_dim, ), hidden_sizes=hidden), (act_dim, ), max_action=max_action,
                       conditioned_sigma=True, unbounded=False)
@@ -154,8 +160,10 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, cycles, up
     out["mstep_dual"] = np.array(mduals, np.float32)
     out["theta_actor_final"] = flat([actor])
     out["theta_actor_old_cycles"] = np.stack(actor_old_log)
-    out["theta_critics_final"] = flat(critics)
-    out["theta_critics_old_final"] = flat(list(policy.critics_old))
+    out["theta_critics_final"] = flat(critics)[::critics_stride]
+    out["theta_critics_old_final"] = flat(list(policy.critics_old))[::critics_stride]
+    if critics_stride != 1:
+        out["theta_final_stride"] = np.array(critics_stride)
     cfg = dict(obs_dim=obs_dim, act_dim=act_dim, hidden=list(hidden), env_num=env_num, batch_size=batch_size,
                cycles=cycles, updates_per_cycle=updates_per_cycle, seed=seed, n_step=n_step, max_action=max_action,
                cost_limit=cost_limit, max_episode_steps=max_episode_steps, tau=tau, actor_lr=actor_lr,
@@ -165,6 +173,8 @@ def gen(name, obs_dim, act_dim, hidden, env_num, ep_lens, batch_size, cycles, up
                mstep_kl_std=mstep_kl_std, mstep_dual_max=mstep_dual_max, mstep_dual_lr=mstep_dual_lr,
                buffer_size=100000)
     out["cfg_json"] = np.array(json.dumps(cfg))
+    if census is not None:
+        print("    census " + census(name, out["estep_dual"], out["stats_keys"], out["stats"], cfg))
     np.savez_compressed(os.path.join(HERE, f"cvpo_{name}.npz"), **out)
     print(f"G11 cvpo_{name}.npz rows={len(used)} updates={n_updates} keys={keys}\n    last={merged[-1]}\n"
           f"    estep_dual={duals[-1]} mstep_dual={mduals[-1]}")
@@ -179,6 +189,23 @@ if __name__ == "__main__":
             mstep_kl_mu=2e-4, mstep_kl_std=2e-6, actor_lr=2e-3)
         gen("wide1_double", 8, 2, (272, ), 3, eps, batch_size=100, cycles=2, updates_per_cycle=3, seed=54, n_step=3, max_action=2.0,
             cost_limit=0.5, mstep_kl_mu=1e-3, double_critic=True, mstep_iter_num=2, estep_iter_num=2, sample_act_num=8)
+        sys.exit(0)
+    if sys.argv[1:] == ["costly"]:
+        # cost_limit -1: qc_thres = -0.434 lies below every Qc, so lambda grows by 0.2 .. 0.3 per update at estep_dual_lr 0.1 and the
+        # E-step's cost side (- lambda Qc, the overwrite of q[0] per iteration, the clamp after the loop) carries weight
+        sys.path[:0] = [os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))]      # tests/ and the oracle package
+        from cvpo_dual_problems import costly_census  # noqa: E402
+        kw = dict(cost_limit=-1.0, estep_dual_lr=0.1, census=costly_census)
+        tight = dict(mstep_kl_mu=2e-4, mstep_kl_std=2e-6, mstep_dual_max=0.15, actor_lr=2e-3)     # the M-step multipliers reach their cap
+        gen("costly_double", 8, 2, (64, 64), 3, eps, batch_size=100, cycles=1, updates_per_cycle=6, seed=60, double_critic=True,
+            sample_act_num=8, estep_iter_num=3, **kw)
+        gen("costly_k5", 6, 3, (64, 64), 3, eps, batch_size=64, cycles=1, updates_per_cycle=6, seed=61, sample_act_num=5,
+            estep_iter_num=2, estep_dual_max=0.45, **kw)                                           # K = 5: the per-state loop
+        gen("costly_deep3", 6, 3, (48, 64, 40), 3, eps, batch_size=64, cycles=2, updates_per_cycle=6, seed=62, estep_iter_num=2,
+            **tight, **kw)
+        # K B = 4096: four rounds of the E-step's lane path; the final critics are kept strided (four 128 x 128 Q-networks)
+        gen("costly_wide", 8, 2, (128, 128), 3, eps, batch_size=256, cycles=2, updates_per_cycle=4, seed=63, double_critic=True,
+            estep_iter_num=2, critics_stride=8, **tight, **kw)
         sys.exit(0)
     # small: cost threshold below Qc (lambda grows) and tight KL bounds (the M-step duals turn positive)
     gen("small", 6, 3, (64, 64), 3, eps, batch_size=64, cycles=2, updates_per_cycle=6, seed=50, cost_limit=0.3,

@@ -30,7 +30,23 @@ def cvpo_setup(name):
     return g, cfg, ocfg, store, ReplayIndex(g["env_rows"], sub, done)
 
 
-@pytest.mark.parametrize("name", ["small", "default", "double", "deep3", "wide1_double"])
+COSTLY = ["costly_double", "costly_k5", "costly_deep3", "costly_wide"]      # gen_golden_cvpo.py costly: lambda off its lower clamp
+
+
+def final_stride(g):
+    """theta_critics_final / theta_critics_old_final hold every final_stride-th entry (the wide DoubleCritic case)"""
+    return int(g.get("theta_final_stride", 1))
+
+
+@pytest.mark.parametrize("name", COSTLY)
+def test_costly_fixture_census(name):
+    """the committed fixture shows what its generator asserted when it wrote it: lambda >= 0.1 in at least half of the updates,
+    eta below 0.25 somewhere, and the fixture's own clamp claims (tests/cvpo_dual_problems.py::costly_census)"""
+    from cvpo_dual_problems import fixture_census
+    print(fixture_census(name))
+
+
+@pytest.mark.parametrize("name", ["small", "default", "double", "deep3", "wide1_double"] + COSTLY)
 def test_cvpo_updates(name):
     torch.set_num_threads(4)
     g, cfg, ocfg, store, index = cvpo_setup(name)
@@ -52,5 +68,5 @@ def test_cvpo_updates(name):
         o.post_update()
         np.testing.assert_allclose(o.actor_flat(old=True), g["theta_actor_old_cycles"][c], rtol=0, atol=3e-6)
     np.testing.assert_allclose(o.actor_flat(), g["theta_actor_final"], rtol=0, atol=3e-6)
-    np.testing.assert_allclose(o.critics_flat(), g["theta_critics_final"], rtol=0, atol=3e-6)
-    np.testing.assert_allclose(o.critics_flat(old=True), g["theta_critics_old_final"], rtol=0, atol=3e-6)
+    np.testing.assert_allclose(o.critics_flat()[::final_stride(g)], g["theta_critics_final"], rtol=0, atol=3e-6)
+    np.testing.assert_allclose(o.critics_flat(old=True)[::final_stride(g)], g["theta_critics_old_final"], rtol=0, atol=3e-6)
