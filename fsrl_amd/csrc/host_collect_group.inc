@@ -112,8 +112,6 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
                   "collect through fsrl_group_create / fsrl_group_collect_step", i);
         const SacState* s = sac_of(c);
         CHECK_ARG(s, "member %d is not initialised: fsrl_sac_init / fsrl_cvpo_init first", i);
-        CHECK_ARG(!(s->layered && s->cvpo), "member %d is a layered CVPO context: it has no fused actor network for the resident kernel, "
-                  "and layered CVPO members do not group yet", i);
         const SacState* s0 = sac_of(c0);
         CHECK_ARG(!s0 || s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a collect group is all fused (the "
                   "resident kernel) or all layered contexts", i, s->layered ? "layered" : "fused", s0->layered ? "layered" : "fused");

@@ -11,13 +11,21 @@
 // with the single path's split-K plan, and the tile height of a launch is the single-context rule applied to the whole group's
 // launch: a group of one is bit-identical to its solo run, a group that runs sixteen-row tiles in every launch is bit-identical to
 // solo runs created under FSRL_TILE16 (tests/test_gpu_cvpo_group.py).
+// A group is all fused or all layered contexts (hidden_sizes of any depth / width).  A layered group runs the launch sequence of the
+// member's own layered update, 6 L + 15 + mstep_iter_num (2 L + 6) launches per update for L hidden layers, and is bit-identical
+// to it at every k and batch size: host_cvpo_group_layered.inc.
 // ====================================================================================== grouped CVPO
+struct LayCvpoGroup;
+static void lay_cvpo_group_free(LayCvpoGroup* lg);
+static int lay_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32_t* n_updates);
+
 struct fsrl_cvpo_group {
     ReplayGroupCore core;                      // members, stream, events (host_sac_group.inc)
     DevTable<SacGroupMember> tab;              // [k]: what the SAC group's kernels read
     DevTable<CvpoGroupMember> ctab;            // [k]: CVPO's own launches
     DevTable<SacGroupStep> steps;              // [updates][k]
     DevTable<CvpoGroupIter> iters;             // [updates][mstep_iter_num][k]
+    LayCvpoGroup* lay = nullptr;               // job and head tables of a layered group, made by its first update
 };
 
 static void cvpo_group_detach(fsrl_ctx* c) {
@@ -31,6 +39,7 @@ extern "C" int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g) {
     for (fsrl_ctx* c : g->core.m) if (c) c->cvpo_group = nullptr;
     rgroup_destroy(g->core);
     table_free(g->tab); table_free(g->ctab); table_free(g->steps); table_free(g->iters);
+    lay_cvpo_group_free(g->lay);
     delete g;
     return 0;
 }
@@ -48,20 +57,24 @@ static int cvpo_group_check(fsrl_ctx* const* ctxs, int k, const fsrl_cvpo_group*
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
         CHECK_ARG(!s->ddpg, "member %d is a DDPG-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
         CHECK_ARG(s->cvpo, "member %d is a SAC-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
-        CHECK_ARG(!s->layered && !c->lay, "member %d is a layered context: grouped CVPO updates run the fused kernels (two hidden layers)", i);
+        const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
+        CHECK_ARG(s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a group is all fused (two hidden layers of at "
+                  "most 256 units) or all layered contexts", i, s->layered ? "layered" : "fused", s0->layered ? "layered" : "fused");
         CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
         CHECK_ARG(!c->sac_group, "member %d is already in a SAC group", i);
         CHECK_ARG(c->cvpo_group == own, "member %d is already in a CVPO group", i);
-        const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
         CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden &&
-                  c->h1 == c0->h1 && c->h2 == c0->h2,
-                  "member %d: members must have one network shape (obs_dim, act_dim, hidden layer widths)", i);
+                  (s->layered ? lay_same_shape(c->cfg, c0->cfg) : (c->h1 == c0->h1 && c->h2 == c0->h2)),
+                  "member %d: members must have one network shape (obs_dim, act_dim, hidden layer widths; layered: every hidden_sizes[l] "
+                  "and force_layered)", i);
         CHECK_ARG(s->ccfg.n_step == s0->ccfg.n_step, "member %d: members must share n_step", i);
         CHECK_ARG((s->ccfg.double_critic != 0) == (s0->ccfg.double_critic != 0), "member %d: members must share double_critic", i);
         CHECK_ARG(s->ccfg.sample_act_num == s0->ccfg.sample_act_num, "member %d: members must share sample_act_num", i);
         CHECK_ARG(s->ccfg.estep_iter_num == s0->ccfg.estep_iter_num, "member %d: members must share estep_iter_num", i);
         CHECK_ARG(s->ccfg.mstep_iter_num == s0->ccfg.mstep_iter_num, "member %d: members must share mstep_iter_num", i);
-        CHECK_ARG(s->wgrad_splitk == s0->wgrad_splitk, "member %d: members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)", i);
+        // a layered update has one weight-side plan
+        CHECK_ARG(s->layered || s->wgrad_splitk == s0->wgrad_splitk,
+                  "member %d: members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)", i);
     }
     return 0;
 }
@@ -137,6 +150,18 @@ static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGr
     return 0;
 }
 
+// the actor's M Adam steps of update u of member i (t_actor advances once per M iteration); zero where the member sits it out
+// (s == nullptr).  The fused and the layered update fill their CvpoGroupIter rows here.
+static void cvpo_group_iter_rows(fsrl_cvpo_group* g, int u, int i, int k, int M, const fsrl_ctx* c, const SacState* s) {
+    for (int it = 0; it < M; ++it) {
+        CvpoGroupIter& gi = g->iters.h[((size_t)u * M + it) * k + i];
+        gi = CvpoGroupIter{};
+        if (!s) continue;
+        const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + (int64_t)u * M + it + 1);
+        gi.a_step = as.step_size; gi.a_bc2 = as.bc2_sqrt;
+    }
+}
+
 extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32_t* n_updates) {
     CHECK_ARG(g && n_updates, "null argument");
     ReplayGroupCore& gc = g->core;
@@ -147,6 +172,7 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     if (rc) return rc;
     fsrl_ctx* c0 = gc.m[0];
     SacState* s0 = sac_of(c0);
+    if (s0->layered) return lay_cvpo_group_update(g, B, n_updates);
     ReplayGroupCall call;
     rc = rgroup_begin(gc, true, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState*) {
         // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
@@ -187,16 +213,7 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
             rq_total = t.fq.remap_total; ra_total = t.fa.remap_total;
         }
         return 0;
-    }, [&](int u, int i, SacGroupStep&, const fsrl_ctx* c, const SacState* s) {
-        // the actor's M Adam steps of the update (t_actor advances once per M iteration); zero where the member sits it out
-        for (int it = 0; it < M; ++it) {
-            CvpoGroupIter& gi = g->iters.h[((size_t)u * M + it) * k + i];
-            gi = CvpoGroupIter{};
-            if (!s) continue;
-            const AdamStep as = adam_step(s->cfg.actor_lr, c->cfg.beta1, c->cfg.beta2, s->t_actor + (int64_t)u * M + it + 1);
-            gi.a_step = as.step_size; gi.a_bc2 = as.bc2_sqrt;
-        }
-    });
+    }, [&](int u, int i, SacGroupStep&, const fsrl_ctx* c, const SacState* s) { cvpo_group_iter_rows(g, u, i, k, M, c, s); });
     if (rc) return rc;
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(SacGroupMember), hipMemcpyHostToDevice, gs));

@@ -10,7 +10,8 @@
 //            Bit-identical to the member's own fsrl_sac_update: see kernels_layered_sac_group.hpp.
 //   collect: no resident kernel -- lay_group_collect_post's staging (host_layered_group.inc) with the members' actor parameters
 //            SacState::PA and lay_raw_out_group_kernel as the last launch: L + 2 launches per vector step instead of k (L + 2).
-enum { LSG_LIN, LSG_SAMPLE, LSG_NSTEP, LSG_AHEAD, LSG_QHEAD, LSG_ADAM_Q, LSG_ADAM_A };
+enum { LSG_LIN, LSG_SAMPLE, LSG_NSTEP, LSG_AHEAD, LSG_QHEAD, LSG_ADAM_Q, LSG_ADAM_A,
+       LSG_CVPO_SAMPLE, LSG_CVPO_AHEAD, LSG_CVPO_ESTEP, LSG_CVPO_MDUAL, LSG_CVPO_ADAM_A };     // host_cvpo_group_layered.inc
 struct LaySacOp {
     int kind;
     int form = 0, nw = 4, gx = 1, gy = 1, n = 0, which = 0;     // LSG_LIN: the launch; heads: which of the three argument rows
@@ -41,28 +42,28 @@ static void lay_sac_group_launch(const LaySacOp& op, hipStream_t s, const LinGro
 #undef LSG_GO
 }
 
-// The tables and the launch list of one grouped call.  work[i] == 0: member i sits the whole call out (its working set may not
-// exist yet); its jobs stay empty and its step rows inactive.
-static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const char* work, const double* lagrangians,
-                                const double* rescaling) {
-    ReplayGroupCore& gc = g->core;
-    const int k = (int)gc.m.size();
-    fsrl_ctx* c0 = gc.m[0];
-    const SacState* s0 = sac_of(c0);
-    const int L = s0->ka.L, n_q = s0->n_q, Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim, Din = Do + Da;
-    const size_t lag_stride = (size_t)std::max(1, c0->cfg.n_critics - 1);
-    int rc = table_ensure(lg.ah, (size_t)3 * k, (size_t)3 * k);
-    if (!rc) rc = table_ensure(lg.qh, (size_t)3 * k, (size_t)3 * k);
-    if (!rc) rc = table_ensure(lg.ga, (size_t)k, (size_t)k);
-    if (!rc) rc = table_ensure(lg.na, (size_t)k, (size_t)k);
-    if (rc) return rc;
-    memset(lg.ah.h, 0, (size_t)3 * k * sizeof(LaySacActorArgs)); memset(lg.qh.h, 0, (size_t)3 * k * sizeof(LaySacQArgs));
-    memset(lg.ga.h, 0, (size_t)k * sizeof(SacGatherArgs)); memset(lg.na.h, 0, (size_t)k * sizeof(SacNstepArgs));
-    lg.hjobs.clear(); lg.prog.clear();
+// ---- the launch list of one grouped layered replay update while it is built: the Linear jobs of lay_fwd_k / lay_bwd_dz_k /
+//      lay_wgrad_k for every member in one launch each, and the other launches by kind.  The layered SAC / DDPG program below and
+//      the layered CVPO program (host_cvpo_group_layered.inc) are both written with it.  work[i] == 0: member i sits the whole call
+//      out (its working set may not exist yet); its jobs stay empty.
+struct LayReplayProg {
+    const ReplayGroupCore& gc;
+    const char* work;
+    std::vector<LinGroupJob>& hjobs;
+    std::vector<LaySacOp>& prog;
+    int k, L, n_q, Din, n_cus;
+    LayReplayProg(const ReplayGroupCore& gc_, const char* work_, std::vector<LinGroupJob>& hjobs_, std::vector<LaySacOp>& prog_)
+        : gc(gc_), work(work_), hjobs(hjobs_), prog(prog_) {
+        const fsrl_ctx* c0 = gc.m[0];
+        const SacState* s0 = sac_of(gc.m[0]);
+        k = (int)gc.m.size(); L = s0->ka.L; n_q = s0->n_q; Din = c0->cfg.obs_dim + c0->cfg.act_dim; n_cus = c0->n_cus;
+        hjobs.clear(); prog.clear();
+    }
     // one linear launch: `per` jobs per member, fill(i, y, job) forms job y of member i as the member's own launch would
-    auto lin = [&](int form, int per, auto&& fill) {
+    template <class Fill>
+    void lin(int form, int per, Fill&& fill) {
         LaySacOp op{LSG_LIN};
-        op.form = form; op.off = lg.hjobs.size(); op.n = k * per;
+        op.form = form; op.off = hjobs.size(); op.n = k * per;
         long wgs = 0;
         for (int i = 0; i < k; ++i)
             for (int y = 0; y < per; ++y) {
@@ -76,14 +77,15 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
                              lay_vec_ok(jb.N > 0 ? jb.B : nullptr, jb.ldb, form == LIN_F ? jb.K : jb.N);
                     wgs += (long)std::max(1, (jb.N + 63) / 64) * ((jb.M + 63) / 64);
                 }
-                lg.hjobs.push_back(gj);
+                hjobs.push_back(gj);
             }
-        op.nw = wgs <= 2 * c0->n_cus ? 4 : (wgs <= 4 * c0->n_cus ? 2 : 1);       // lay_launch's rule on the whole launch (any NW: the same bits)
-        lg.prog.push_back(op);
-    };
-    auto work_of = [&](int i, bool actor) -> const LayWork& { const SacState* s = sac_of(gc.m[i]); return actor ? s->ka : s->kq; };
-    // lay_fwd_k: P(i) the parameters, X(i) the input rows
-    auto fwd = [&](bool actor, auto&& P, auto&& X) {
+        op.nw = wgs <= 2 * n_cus ? 4 : (wgs <= 4 * n_cus ? 2 : 1);       // lay_launch's rule on the whole launch (any NW: the same bits)
+        prog.push_back(op);
+    }
+    const LayWork& work_of(int i, bool actor) const { const SacState* s = sac_of(gc.m[i]); return actor ? s->ka : s->kq; }
+    // lay_fwd_k over `rows` rows: P(i) the parameters, X(i) the input rows
+    template <class Par, class In>
+    void fwd(bool actor, int rows, Par&& P, In&& X) {
         const int nn = actor ? 1 : n_q;
         for (int l = 0; l <= L; ++l)
             lin(LIN_F, nn, [&](int i, int net, LinJob& jb) {
@@ -92,13 +94,14 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
                 jb.A = (l == 0) ? X(i) : w.act[net][l - 1]; jb.lda = ll.in;
                 jb.B = P(i) + ll.W; jb.ldb = ll.in;
                 jb.aux = P(i) + ll.b;
-                jb.M = B; jb.N = ll.out; jb.K = ll.in;
+                jb.M = rows; jb.N = ll.out; jb.K = ll.in;
                 if (l < L) { jb.C = w.act[net][l]; jb.ldc = ll.out; jb.relu = 1; }
                 else { jb.C = w.out + (size_t)net * w.mbp * FSRL_MAX_ACT; jb.ldc = FSRL_MAX_ACT; jb.relu = 0; }
             });
-    };
+    }
     // lay_bwd_dz_k; to_input: down to the network's input (the Q-networks' dQ / d[obs | act] into DXQ)
-    auto bwd = [&](bool actor, auto&& P, bool to_input) {
+    template <class Par>
+    void bwd(bool actor, int rows, Par&& P, bool to_input) {
         const int nn = actor ? 1 : n_q;
         for (int l = L - 1; l >= (to_input ? -1 : 0); --l)
             lin(LIN_X, nn, [&](int i, int net, LinJob& jb) {
@@ -109,11 +112,12 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
                 jb.B = P(i) + up.W; jb.ldb = up.in;
                 if (l >= 0) { jb.C = w.dz[net][l]; jb.ldc = up.in; jb.aux = w.act[net][l]; jb.ldaux = up.in; }
                 else { jb.C = sac_of(gc.m[i])->DXQ + (size_t)net * w.mbp * Din; jb.ldc = up.in; }
-                jb.M = B; jb.N = up.in; jb.K = up.out;
+                jb.M = rows; jb.N = up.in; jb.K = up.out;
             });
-    };
+    }
     // lay_wgrad_k: every Linear of every network of the family in one launch, into the member's GA / GQ
-    auto wgrad = [&](bool actor, auto&& X) {
+    template <class In>
+    void wgrad(bool actor, int rows, In&& X) {
         const int nn = actor ? 1 : n_q;
         lin(LIN_W, nn * (L + 1), [&](int i, int y, LinJob& jb) {
             const SacState* s = sac_of(gc.m[i]);
@@ -126,33 +130,63 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
             jb.B = (l == 0) ? X(i) : w.act[net][l - 1]; jb.ldb = ll.in;
             jb.C = G + ll.W; jb.ldc = ll.in;
             jb.bias_out = G + ll.b;
-            jb.M = ll.out; jb.N = ll.in; jb.K = B;
+            jb.M = ll.out; jb.N = ll.in; jb.K = rows;
         });
-    };
-    auto op = [&](int kind, int which = 0) { LaySacOp o{kind}; o.which = which; lg.prog.push_back(o); };
+    }
+    // any other launch; which: the argument row of a head (the M-iteration's first flag of a dual step); tiles: a head's row tiles
+    void op(int kind, int which = 0, int tiles = 0) { LaySacOp o{kind}; o.which = which; o.gx = std::max(1, tiles); prog.push_back(o); }
+    // the finished job list into the device table, on the group's stream
+    int upload(DevTable<LinGroupJob>& jobs) {
+        const size_t nj = hjobs.size();
+        const int rc = table_ensure(jobs, nj, nj);
+        if (rc) return rc;
+        memcpy(jobs.h, hjobs.data(), nj * sizeof(LinGroupJob));
+        HIPCHK(hipMemcpyAsync(jobs.d, jobs.h, nj * sizeof(LinGroupJob), hipMemcpyHostToDevice, gc.stream));
+        return 0;
+    }
+};
+
+// The tables and the launch list of one grouped call.  work[i] == 0: member i sits the whole call out (its working set may not
+// exist yet); its jobs stay empty and its step rows inactive.
+static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const char* work, const double* lagrangians,
+                                const double* rescaling) {
+    ReplayGroupCore& gc = g->core;
+    const int k = (int)gc.m.size();
+    fsrl_ctx* c0 = gc.m[0];
+    const SacState* s0 = sac_of(c0);
+    const int n_q = s0->n_q, Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim;
+    const size_t lag_stride = (size_t)std::max(1, c0->cfg.n_critics - 1);
+    int rc = table_ensure(lg.ah, (size_t)3 * k, (size_t)3 * k);
+    if (!rc) rc = table_ensure(lg.qh, (size_t)3 * k, (size_t)3 * k);
+    if (!rc) rc = table_ensure(lg.ga, (size_t)k, (size_t)k);
+    if (!rc) rc = table_ensure(lg.na, (size_t)k, (size_t)k);
+    if (rc) return rc;
+    memset(lg.ah.h, 0, (size_t)3 * k * sizeof(LaySacActorArgs)); memset(lg.qh.h, 0, (size_t)3 * k * sizeof(LaySacQArgs));
+    memset(lg.ga.h, 0, (size_t)k * sizeof(SacGatherArgs)); memset(lg.na.h, 0, (size_t)k * sizeof(SacNstepArgs));
+    LayReplayProg pg(gc, work, lg.hjobs, lg.prog);
     auto S = [&](int i) { return sac_of(gc.m[i]); };
     // ---- the update, launch by launch (fsrl_sac_update, layered branches)
-    op(LSG_SAMPLE);
-    fwd(true, [&](int i) { return S(i)->ddpg ? S(i)->PAT : S(i)->PA; }, [&](int i) { return S(i)->OBSN; });
-    op(LSG_AHEAD, 0);
-    fwd(true, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
-    op(LSG_AHEAD, 1);
-    fwd(false, [&](int i) { return S(i)->PQT; }, [&](int i) { return S(i)->XN; });
-    op(LSG_QHEAD, 0);
-    op(LSG_NSTEP);
-    fwd(false, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XQ; });
-    op(LSG_QHEAD, 1);
-    bwd(false, [&](int i) { return S(i)->PQ; }, false);
-    wgrad(false, [&](int i) { return S(i)->XQ; });
-    op(LSG_ADAM_Q);
-    fwd(false, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XP; });
-    op(LSG_QHEAD, 2);
-    bwd(false, [&](int i) { return S(i)->PQ; }, true);
-    fwd(true, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
-    op(LSG_AHEAD, 2);
-    bwd(true, [&](int i) { return S(i)->PA; }, false);
-    wgrad(true, [&](int i) { return S(i)->OBS; });
-    op(LSG_ADAM_A);
+    pg.op(LSG_SAMPLE);
+    pg.fwd(true, B, [&](int i) { return S(i)->ddpg ? S(i)->PAT : S(i)->PA; }, [&](int i) { return S(i)->OBSN; });
+    pg.op(LSG_AHEAD, 0);
+    pg.fwd(true, B, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
+    pg.op(LSG_AHEAD, 1);
+    pg.fwd(false, B, [&](int i) { return S(i)->PQT; }, [&](int i) { return S(i)->XN; });
+    pg.op(LSG_QHEAD, 0);
+    pg.op(LSG_NSTEP);
+    pg.fwd(false, B, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XQ; });
+    pg.op(LSG_QHEAD, 1);
+    pg.bwd(false, B, [&](int i) { return S(i)->PQ; }, false);
+    pg.wgrad(false, B, [&](int i) { return S(i)->XQ; });
+    pg.op(LSG_ADAM_Q);
+    pg.fwd(false, B, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XP; });
+    pg.op(LSG_QHEAD, 2);
+    pg.bwd(false, B, [&](int i) { return S(i)->PQ; }, true);
+    pg.fwd(true, B, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
+    pg.op(LSG_AHEAD, 2);
+    pg.bwd(true, B, [&](int i) { return S(i)->PA; }, false);
+    pg.wgrad(true, B, [&](int i) { return S(i)->OBS; });
+    pg.op(LSG_ADAM_A);
     // ---- per member: heads, sample, n-step targets, the Adam passes' member row
     for (int i = 0; i < k; ++i) {
         SacGroupMember& t = g->tab.h[i];
@@ -186,12 +220,9 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
         t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
         t.tau = s->cfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->cfg.tau);
     }
-    const size_t nj = lg.hjobs.size();
-    rc = table_ensure(lg.jobs, nj, nj);
+    rc = pg.upload(lg.jobs);
     if (rc) return rc;
-    memcpy(lg.jobs.h, lg.hjobs.data(), nj * sizeof(LinGroupJob));
     hipStream_t gs = gc.stream;
-    HIPCHK(hipMemcpyAsync(lg.jobs.d, lg.jobs.h, nj * sizeof(LinGroupJob), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(lg.ah.d, lg.ah.h, (size_t)3 * k * sizeof(LaySacActorArgs), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(lg.qh.d, lg.qh.h, (size_t)3 * k * sizeof(LaySacQArgs), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(lg.ga.d, lg.ga.h, (size_t)k * sizeof(SacGatherArgs), hipMemcpyHostToDevice, gs));

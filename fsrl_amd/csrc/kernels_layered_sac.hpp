@@ -162,10 +162,11 @@ struct LayCvpoActorArgs {
     int B, K, Do, Da, mode;
     float max_action;
 };
-__global__ __launch_bounds__(256) void lay_cvpo_actor_head_kernel(const LayCvpoActorArgs a) {
+// the workgroup's work on 16-row tile `tile`: shared by the kernel below and the grouped launch (kernels_layered_sac_group.hpp)
+__device__ __forceinline__ void lay_cvpo_actor_head_body(const LayCvpoActorArgs& a, const int tile) {
     __shared__ float stl[16 * 4];
     const int tid = threadIdx.x, i = tid >> 4, d = tid & 15, lane = tid & 63;
-    const int row0 = blockIdx.x * 16, r = row0 + i, Do = a.Do, Da = a.Da, Din = Do + Da;
+    const int row0 = tile * 16, r = row0 + i, Do = a.Do, Da = a.Da, Din = Do + Da;
     const int n_valid = max(0, min(16, a.B - row0));
     const bool valid = i < n_valid, on = valid && d < Da;
     if (a.mode == CVPO_A_PARTICLES) {               // observation columns of the K replicated rows
@@ -251,6 +252,7 @@ __global__ __launch_bounds__(256) void lay_cvpo_actor_head_kernel(const LayCvpoA
     if (tid < 4) {
         float t = 0.0f;
         for (int rr = 0; rr < 16; ++rr) t += stl[rr * 4 + tid];
-        a.statp[(size_t)blockIdx.x * FB_NSTAT + tid] = t;
+        a.statp[(size_t)tile * FB_NSTAT + tid] = t;
     }
 }
+__global__ __launch_bounds__(256) void lay_cvpo_actor_head_kernel(const LayCvpoActorArgs a) { lay_cvpo_actor_head_body(a, (int)blockIdx.x); }

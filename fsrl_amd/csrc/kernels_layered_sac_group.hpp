@@ -28,6 +28,14 @@ __global__ __launch_bounds__(256) void lay_sac_actor_head_group_kernel(const Lay
     lay_sac_actor_head_body(heads[blockIdx.y], (int)blockIdx.x);
 }
 
+// the CVPO actor head of a layered CVPO group (host_cvpo_group_layered.inc).  grid = (tiles, members).  The early return is
+// uniform per workgroup, so the __syncthreads() of the body's MBWD branch stays legal.
+__global__ __launch_bounds__(256) void lay_cvpo_actor_head_group_kernel(const LayCvpoActorArgs* __restrict__ heads,
+                                                                       const SacGroupStep* __restrict__ steps) {
+    if (steps[blockIdx.y].active == 0) return;
+    lay_cvpo_actor_head_body(heads[blockIdx.y], (int)blockIdx.x);
+}
+
 // grid = (tiles, n_q, members)
 __global__ __launch_bounds__(64) void lay_sac_q_head_group_kernel(const LaySacQArgs* __restrict__ heads, const SacGroupStep* __restrict__ steps) {
     if (!steps[blockIdx.z].active) return;

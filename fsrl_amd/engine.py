@@ -897,7 +897,11 @@ class EngineCvpoGroup(_NativeGroup):
     """k CVPO engines (cvpo_init) of one launch structure on one GPU, updated in lock step (fsrl_cvpo_group_*): every launch of
     an update carries all members that still have updates to run.  Members keep their own streams, stores, parameters, duals,
     Philox keys and statistics rings, and stay ordinary engines between updates (push, collect_step with the resident actor,
-    cvpo_pre_update / cvpo_post_update / cvpo_set_thres, own cvpo_update calls, sac_drain ...)."""
+    cvpo_pre_update / cvpo_post_update / cvpo_set_thres, own cvpo_update calls, sac_drain ...).
+    The members are all fused (two hidden layers of at most 256 units) or all layered contexts of one `hidden_sizes` and
+    `force_layered`: a layered group runs the layered update's launch sequence with every member in each launch -- without the
+    second actor forward of an M iteration, which recomputes the first: 6 L + 15 + mstep_iter_num (2 L + 6) launches per update
+    for L hidden layers -- and a member's grouped update is then bit-identical to its own cvpo_update at every group size."""
     _symbols = "fsrl_cvpo_group"
 
     def update(self, batch_size, n_updates):
@@ -914,7 +918,7 @@ class EngineCollectGroup(_LockStepCollect):
     for all members, per member bit-identical to its own collect_step.  Independent of the update groups: the members may also
     be in an EngineSacGroup / EngineCvpoGroup, and stay ordinary engines.  EngineGroup's collect interface, so
     GroupCollector(engine_collect_group, collectors) drives it.
-    SAC-Lag / DDPG-Lag members may all be layered contexts of one `hidden_sizes` (not CVPO members yet): the group then has no
+    The members (of any of the three kinds) may all be layered contexts of one `hidden_sizes`: the group then has no
     resident kernel -- a request is one launch sequence (L + 2 launches) for all members, actor_set_resident is accepted and has no
     effect, actor_release does nothing and actor_resident_stats counts the requests."""
     _symbols = "fsrl_collect_group"

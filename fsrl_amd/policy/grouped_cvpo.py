@@ -9,6 +9,9 @@ steps.
     group.update(buffers, batch_size=256, n_updates=[n_0, n_1, ...])
     ... post_update_fn per agent (drains the rows into its logger, actor_old <- actor) ...
 
+The policies' networks are all fused (two hidden layers of at most 256 units) or all layered of one `hidden_sizes`; layered seeds
+collect in lock step through `GroupCollector` over an `EngineCollectGroup` of their engines (L + 2 launches per vector step).
+
 The loop is grouped_sac.ReplayPolicyGroup's."""
 from fsrl_amd.engine import EngineCvpoGroup
 from fsrl_amd.policy.cvpo import CVPO

@@ -572,7 +572,7 @@ int fsrl_sac_actor_forward(fsrl_ctx* ctx, const float* obs, int32_t k, float* mu
  *      contexts, a member listed twice or already in a SAC group.  A member destroyed before its group makes the next update fail; fsrl_sac_group_destroy still works.
  *      LAYERED members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are layered and n_hidden,
  *      hidden_sizes[] and force_layered agree (a mix of fused and layered members, either order: "layered"; of widths or depths:
- *      "one network shape"; layered CVPO contexts are refused as CVPO contexts).  Each update is then the launch sequence of the
+ *      "one network shape"; layered CVPO contexts are refused as CVPO contexts: their groups are fsrl_cvpo_group_*).  Each update is then the launch sequence of the
  *      member's own layered fsrl_sac_update (9 L + 19 launches for L hidden layers, whatever k is) with every launch carrying all
  *      members that still have updates to run, and a member's grouped update is bit-identical to its own at every k and batch size. */
 typedef struct fsrl_sac_group fsrl_sac_group;
@@ -634,9 +634,16 @@ int fsrl_cvpo_last_particles(fsrl_ctx* ctx, float* eps_particles, int64_t n);
  *      next collect relaunches it).  Members must share what decides the launch structure: obs_dim, act_dim, the hidden layer
  *      widths, n_step, double_critic, sample_act_num, estep_iter_num, mstep_iter_num and fsrl_sac_set_plan bit 0; learning
  *      rates, tau, the KL bounds, dual learning rates and caps, qc_thres, seeds and store contents may differ.  Rejected with
- *      FSRL_EINVAL and the reason in fsrl_last_error: SAC-Lag, DDPG-Lag and layered contexts, another device, a mismatch of the
+ *      FSRL_EINVAL and the reason in fsrl_last_error: SAC-Lag and DDPG-Lag contexts, another device, a mismatch of the
  *      list above, a member listed twice or already in a SAC or CVPO group.  A member destroyed before its group makes the
- *      next update fail (FSRL_ESTATE); fsrl_cvpo_group_destroy still works.                                                 */
+ *      next update fail (FSRL_ESTATE); fsrl_cvpo_group_destroy still works.
+ *      LAYERED members (fsrl_config.n_hidden: any other hidden_sizes) form a group when ALL members are layered and n_hidden,
+ *      hidden_sizes[] and force_layered agree (a mix of fused and layered members, either order: "layered"; of widths or depths:
+ *      "one network shape"; fsrl_sac_set_plan bit 0 does not apply).  Each update is then the launch sequence of the member's own
+ *      layered fsrl_cvpo_update with every launch carrying all members that still have updates to run, without the second actor
+ *      forward of an M iteration (it recomputes the first): 6 L + 15 + mstep_iter_num (2 L + 6) launches for L hidden layers,
+ *      whatever k is, against 6 L + 15 + mstep_iter_num (3 L + 7) of the member's own update.  A member's grouped update is
+ *      bit-identical to its own at every k and batch size.                                                                   */
 typedef struct fsrl_cvpo_group fsrl_cvpo_group;
 int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_group** out);   /* 1 <= k <= 16, members not owned */
 int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g);
@@ -658,14 +665,14 @@ int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t
  *      read-only queries: own updates, fsrl_sac_put_params, fsrl_sac_group_update / fsrl_cvpo_group_update, own
  *      fsrl_collect_step / fsrl_actor_sample), by fsrl_collect_group_actor_release, and by its idle timeout; the next step
  *      launches it again.
- *      LAYERED SAC-Lag / DDPG-Lag members (all members layered, one n_hidden / hidden_sizes[] / force_layered) have no resident
+ *      LAYERED members of any of the three kinds (all members layered, one n_hidden / hidden_sizes[] / force_layered) have no resident
  *      kernel: a request is one launch sequence on the group's stream for all members -- the observation rows side by side in
  *      pinned memory, L + 1 linear launches with one job per member that has rows, one launch that leaves the raw head rows and
  *      completion words in pinned memory -- L + 2 launches per vector step instead of k (L + 2), any row count per member.  The
  *      releases listed above mark such a group instead of ending a kernel: its next request first waits for everything the
  *      members have enqueued on their compute streams; requests between two releases are ordered by the group's stream alone.
  *      create rejects with FSRL_EINVAL and the reason in fsrl_last_error: on-policy contexts (fsrl_group_create is theirs),
- *      layered CVPO contexts, a mix of fused and layered contexts, contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds,
+ *      a mix of fused and layered contexts, contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds,
  *      another device or network shape (obs_dim, act_dim, hidden; layered: hidden_sizes[], force_layered), a member listed twice or
  *      already in a collect group, k outside 1..16.
  *      A member destroyed before its group breaks it: later steps fail with FSRL_ESTATE, fsrl_collect_group_destroy still works. */

@@ -14,7 +14,7 @@ Modes: seq_ungrouped (each member's own FastCollector with its own resident acto
 launches per collect; the loop is lock-step collection + round(0.2 * n/st) updates per seed through SACPolicyGroup / CVPOPolicyGroup
 (DDPG-Lag: each seed's own updates, one seed after the other).
 
---hidden 256x256x256 (--algo sacl | ddpgl): layered members.  Their collect group has no resident kernel: a lock-step vector step is
+--hidden 256x256x256 (--algo sacl | ddpgl | cvpo): layered members.  Their collect group has no resident kernel: a lock-step vector step is
 one launch sequence (L + 2 launches) for all members against k (L + 2) member by member, and launches_per_collect counts requests.
 With --hidden the DDPG-Lag loop updates through DDPGPolicyGroup as the SAC-Lag loop does through SACPolicyGroup.
 
@@ -156,9 +156,9 @@ def main():
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
-                    help="--algo sacl | ddpgl: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
+                    help="--algo sacl | ddpgl | cvpo: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
     a = ap.parse_args()
-    assert a.hidden is None or a.algo in ("sacl", "ddpgl"), "--hidden: the replay agents' layered collect groups (--algo sacl | ddpgl)"
+    assert a.hidden is None or a.algo in ("sacl", "ddpgl", "cvpo"), "--hidden: the replay agents' layered collect groups (--algo sacl | ddpgl | cvpo)"
     if a.algo != "ppol":
         return _replay(a)
     from fsrl_amd.data import GroupCollector
