@@ -39,7 +39,9 @@ def main():
                     help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
     # options of the on-policy agents (the reference's constructor arguments of the same names)
-    ap.add_argument("--unbounded", action="store_true", help="actor mean without max_action * tanh")
+    ap.add_argument("--unbounded", action=argparse.BooleanOptionalAction, default=None,
+                    help="actor mean without max_action * tanh; --no-unbounded: with it (sacl, cvpo and the on-policy agents; "
+                         "absent: the agent's own default -- sacl unbounded, every other agent bounded)")
     ap.add_argument("--reward-normalization", action="store_true", help="critics learn returns / running std")
     ap.add_argument("--value-clip", action="store_true", help="PPO-Lag clipped value loss (needs --reward-normalization)")
     ap.add_argument("--recompute-advantage", action="store_true", help="PPO-Lag / FOCOPS: GAE from the current critics before every pass")
@@ -61,7 +63,9 @@ def main():
     kw = dict(cost_limit=a.cost_limit, device=a.device, seed=a.seed, hidden_sizes=(tuple(int(x) for x in a.hidden_sizes.split("x")) if a.hidden_sizes else (a.hidden, a.hidden)),
               training_num=a.envs)
     if a.algo in ("ppol", "cpo", "trpol", "focops"):
-        kw.update(unbounded=a.unbounded, reward_normalization=a.reward_normalization)
+        kw.update(unbounded=bool(a.unbounded), reward_normalization=a.reward_normalization)
+    if a.algo in ("sacl", "cvpo") and a.unbounded is not None:
+        kw.update(unbounded=a.unbounded)
     if a.algo == "ppol":
         kw.update(value_clip=a.value_clip)
     if a.algo in ("ppol", "focops"):

@@ -46,7 +46,7 @@ class SacConfig(C.Structure):
     _fields_ = [("actor_lr", C.c_float), ("critic_lr", C.c_float), ("alpha_lr", C.c_float), ("tau", C.c_float),
                 ("alpha", C.c_float), ("target_entropy", C.c_float), ("n_step", C.c_int32),
                 ("auto_alpha", C.c_int32), ("use_lagrangian", C.c_int32), ("deterministic", C.c_int32),
-                ("exploration_sigma", C.c_float)]
+                ("exploration_sigma", C.c_float), ("actor_mean", C.c_int32)]
 
 
 class FocopsConfig(C.Structure):
@@ -61,7 +61,19 @@ class CvpoConfig(C.Structure):
                 ("double_critic", C.c_int32), ("sample_act_num", C.c_int32), ("estep_iter_num", C.c_int32),
                 ("mstep_iter_num", C.c_int32), ("estep_kl", C.c_float), ("estep_dual_max", C.c_float),
                 ("estep_dual_lr", C.c_float), ("mstep_kl_mu", C.c_float), ("mstep_kl_std", C.c_float),
-                ("mstep_dual_max", C.c_float), ("mstep_dual_lr", C.c_float), ("qc_thres", C.c_double)]
+                ("mstep_dual_max", C.c_float), ("mstep_dual_lr", C.c_float), ("qc_thres", C.c_double),
+                ("actor_mean", C.c_int32)]
+
+
+# fsrl_sac_config / fsrl_cvpo_config .actor_mean: how the Gaussian actor's mean head becomes the mean
+ACTOR_MEAN_DEFAULT, ACTOR_MEAN_UNBOUNDED, ACTOR_MEAN_TANH = 0, 1, 2
+
+
+def actor_mean_code(unbounded):
+    """ActorProb's `unbounded` -> actor_mean: None keeps the kind's default (SAC-Lag unbounded, CVPO max_action * tanh)."""
+    if unbounded is None:
+        return ACTOR_MEAN_DEFAULT
+    return ACTOR_MEAN_UNBOUNDED if bool(unbounded) else ACTOR_MEAN_TANH
 
 
 CPO_NSTATS, TRPO_NSTATS, SAC_NSTATS, FOCOPS_NSTATS, CVPO_NSTATS = 17, 11, 10, 8, 17

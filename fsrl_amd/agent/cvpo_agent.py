@@ -26,13 +26,14 @@ class CVPOAgent(OffpolicyAgent):
         super().__init__()
         self.logger = logger if logger is not None else DummyLogger()
         self.cost_limit = cost_limit
-        assert np.isscalar(cost_limit) and conditioned_sigma and not unbounded, \
-            "the HIP CVPO path: one cost, state-conditioned sigma, bounded mean (the reference defaults)"
+        assert np.isscalar(cost_limit), "the HIP CVPO path: one cost"
+        assert conditioned_sigma, \
+            "conditioned_sigma=False is not supported on the HIP CVPO path: a state-independent sigma is another parameter layout"
         seed_all(seed)
         torch.set_num_threads(thread)
         assert hasattr(env.spec, "max_episode_steps"), \
             "Please use an env wrapper to provide 'max_episode_steps' for CVPO"
-        actor, critics = offpolicy_nets(env, hidden_sizes, "double" if double_critic else "single", unbounded=False,
+        actor, critics = offpolicy_nets(env, hidden_sizes, "double" if double_critic else "single", unbounded=unbounded,
                                         last_layer_scale=last_layer_scale)
         actor_optim, critic_optim = adam(actor, actor_lr), adam(critics, critic_lr)
         self.policy = CVPO(actor=actor, critics=critics, actor_optim=actor_optim, critic_optim=critic_optim,

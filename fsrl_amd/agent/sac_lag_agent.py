@@ -77,11 +77,12 @@ class SACLagAgent(OffpolicyAgent):
         super().__init__()
         self.logger = logger if logger is not None else DummyLogger()
         self.cost_limit = cost_limit
-        assert np.isscalar(cost_limit) and conditioned_sigma and unbounded, \
-            "the HIP SAC path: one cost, state-conditioned sigma, unbounded mean (the reference defaults)"
+        assert np.isscalar(cost_limit), "the HIP SAC path: one cost"
+        assert conditioned_sigma, \
+            "conditioned_sigma=False is not supported on the HIP SAC path: a state-independent sigma is another parameter layout"
         seed_all(seed)
         torch.set_num_threads(thread)
-        actor, critics = offpolicy_nets(env, hidden_sizes, "double", unbounded=True, last_layer_scale=last_layer_scale)
+        actor, critics = offpolicy_nets(env, hidden_sizes, "double", unbounded=unbounded, last_layer_scale=last_layer_scale)
         actor_optim, critic_optim = adam(actor, actor_lr), adam(critics, critic_lr)
         if auto_alpha:
             target_entropy = -float(np.prod(env.action_space.shape))

@@ -1236,7 +1236,7 @@ static void actor_draw(fsrl_ctx* c, int32_t deterministic, float* act_out) {
             if (u1 < 1e-300) u1 = 1e-300;
             u += c->act_sg[i] * (float)(std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2));
         }
-        act_out[i] = squash ? std::tanh(u) : u;     // DDPG-Lag / CVPO: mu is already max_action * tanh
+        act_out[i] = squash ? std::tanh(u) : u;     // only SAC squashes the draw; the mean's own transform (actor_mean) is sac_actor_finish's
     }
 }
 

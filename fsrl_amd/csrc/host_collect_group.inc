@@ -119,6 +119,8 @@ extern "C" int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collec
                   "member %d is a %s context, member 0 a %s one: a collect group has one kind of member", i, kinds[collect_group_kind(s)],
                   kinds[collect_group_kind(s0)]);
         CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
+        CHECK_ARG(!s0 || s->mean_tanh == s0->mean_tanh, "member %d: members must share actor_mean (the actor's mean is %s, member 0's %s)", i,
+                  s->mean_tanh ? "max_action * tanh(head)" : "unbounded", s0->mean_tanh ? "max_action * tanh(head)" : "unbounded");
         CHECK_ARG(c->cfg.obs_dim == c0->cfg.obs_dim && c->cfg.act_dim == c0->cfg.act_dim && c->cfg.hidden == c0->cfg.hidden &&
                   (!s->layered || lay_same_shape(c->cfg, c0->cfg)),
                   "member %d: members must have one network shape (obs_dim, act_dim, hidden; layered: every hidden_sizes[l] and force_layered)", i);

@@ -10,11 +10,14 @@ extern "C" int fsrl_cvpo_init(fsrl_ctx* c, const fsrl_cvpo_config* cfg) {
     CHECK_ARG(cfg->tau >= 0.0f && cfg->tau <= 1.0f, "tau should be in [0, 1]");
     CHECK_ARG(cfg->sample_act_num >= 1 && cfg->sample_act_num <= 64, "sample_act_num must be in [1, 64]");
     CHECK_ARG(cfg->estep_iter_num >= 1 && cfg->mstep_iter_num >= 1, "estep_iter_num and mstep_iter_num must be >= 1");
+    CHECK_ARG(cfg->actor_mean >= FSRL_ACTOR_MEAN_DEFAULT && cfg->actor_mean <= FSRL_ACTOR_MEAN_TANH,
+              "actor_mean must be 0 (default), 1 (unbounded) or 2 (max_action * tanh), got %d", cfg->actor_mean);
     ENTER_DEV(c);
     if (c->sac) sac_free(c);
     SacState* s = new SacState();
     c->sac = s;
     s->cvpo = true; s->ccfg = *cfg; s->nstats = FSRL_CVPO_NSTATS_K;
+    s->mean_tanh = cfg->actor_mean == FSRL_ACTOR_MEAN_UNBOUNDED ? 0 : 1;      // CVPO's default: max_action * tanh
     s->n_q = cfg->double_critic ? 4 : 2;
     s->cfg.actor_lr = cfg->actor_lr; s->cfg.critic_lr = cfg->critic_lr; s->cfg.tau = cfg->tau; s->cfg.n_step = cfg->n_step;
     s->cfg.auto_alpha = 0; s->cfg.alpha = 0.0f; s->cfg.use_lagrangian = 0;      // no entropy term, no PID multiplier
@@ -112,7 +115,7 @@ static CvpoActorArgs cvpo_actor_args(const fsrl_ctx* c, const SacState* s, int B
     }
     aa.obs = obs; aa.eps = eps; aa.X = X; aa.mu_old = s->MU_OLD; aa.std_old = s->STD_OLD; aa.W = s->Wk; aa.XK = s->XK;
     aa.sc = s->csc; aa.A1 = s->A1; aa.A2 = s->A2; aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi;
-    aa.B = B; aa.K = s->ccfg.sample_act_num; aa.mode = mode; aa.max_action = c->cfg.max_action;
+    aa.B = B; aa.K = s->ccfg.sample_act_num; aa.mode = mode; aa.max_action = c->cfg.max_action; aa.mean_tanh = s->mean_tanh;
     return aa;
 }
 static SacNstepArgs cvpo_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
@@ -196,7 +199,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
                 LayCvpoActorArgs h{};
                 h.out = s->ka.out; h.dout = s->ka.dout; h.obs = obs_; h.eps = eps_; h.X = X_; h.mu_old = s->MU_OLD; h.std_old = s->STD_OLD;
                 h.W = s->Wk; h.XK = s->XK; h.sc = s->csc; h.statp = s->stpi; h.B = B; h.K = K; h.Do = Do; h.Da = Da; h.mode = md_;
-                h.max_action = c->cfg.max_action;
+                h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
                 hipLaunchKernelGGL(lay_cvpo_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, st, h);
                 HIPCHK(hipGetLastError());
                 return 0;
@@ -361,8 +364,8 @@ static void sac_actor_finish(fsrl_ctx* c, const float* raw, int k, float* mu_out
                 if (sigma_out) sigma_out[(size_t)r * Da + d] = s->cfg.exploration_sigma;
                 continue;
             }
-            mu_out[(size_t)r * Da + d] = s->cvpo ? c->cfg.max_action * std::tanh(raw[(size_t)r * rc + d])
-                                                 : raw[(size_t)r * rc + d];
+            mu_out[(size_t)r * Da + d] = s->mean_tanh ? c->cfg.max_action * std::tanh(raw[(size_t)r * rc + d])
+                                                      : raw[(size_t)r * rc + d];
             if (sigma_out) {
                 const float l = std::min(std::max(raw[(size_t)r * rc + Da + d], -20.0f), 2.0f);
                 sigma_out[(size_t)r * Da + d] = std::exp(l);

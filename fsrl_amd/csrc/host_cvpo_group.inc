@@ -72,6 +72,8 @@ static int cvpo_group_check(fsrl_ctx* const* ctxs, int k, const fsrl_cvpo_group*
         CHECK_ARG(s->ccfg.sample_act_num == s0->ccfg.sample_act_num, "member %d: members must share sample_act_num", i);
         CHECK_ARG(s->ccfg.estep_iter_num == s0->ccfg.estep_iter_num, "member %d: members must share estep_iter_num", i);
         CHECK_ARG(s->ccfg.mstep_iter_num == s0->ccfg.mstep_iter_num, "member %d: members must share mstep_iter_num", i);
+        CHECK_ARG(s->mean_tanh == s0->mean_tanh, "member %d: members must share actor_mean (the actor's mean is %s, member 0's %s)", i,
+                  s->mean_tanh ? "max_action * tanh(head)" : "unbounded", s0->mean_tanh ? "max_action * tanh(head)" : "unbounded");
         // a layered update has one weight-side plan
         CHECK_ARG(s->layered || s->wgrad_splitk == s0->wgrad_splitk,
                   "member %d: members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)", i);

@@ -92,7 +92,7 @@ static int lay_cvpo_group_tables(fsrl_cvpo_group* g, LayCvpoGroup& lg, int B, co
             LayCvpoActorArgs& h = lg.ah.h[(size_t)w * k + i];
             h.out = s->ka.out; h.dout = s->ka.dout; h.mu_old = s->MU_OLD; h.std_old = s->STD_OLD;
             h.W = s->Wk; h.XK = s->XK; h.sc = s->csc; h.statp = s->stpi; h.B = B; h.K = K; h.Do = Do; h.Da = Da;
-            h.max_action = c->cfg.max_action;
+            h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
             if (w == LCG_TARGET) { h.obs = s->OBSN; h.eps = s->eps_t; h.X = s->XN; h.mode = CVPO_A_TARGET; }
             else if (w == LCG_PARTICLES) { h.obs = s->OBS; h.eps = s->eps_k; h.X = s->XK; h.mode = CVPO_A_PARTICLES; }
             else { h.obs = s->OBS; h.eps = nullptr; h.X = nullptr; h.mode = w == LCG_MFWD ? CVPO_A_MFWD : CVPO_A_MBWD; }

@@ -18,6 +18,7 @@ struct SacState {
     bool plan_separate = false;                // fsrl_sac_set_plan bit 1: sample and gather as launches of their own
     bool plan_nstep_sep = false;               // fsrl_sac_set_plan bit 2: the n-step targets as a launch of their own
     bool ddpg = false;
+    int mean_tanh = 0;          // the Gaussian actor's mean: 1 = max_action * tanh(head), 0 = the head (cfg.actor_mean / ccfg.actor_mean resolved)
     SacScalars* sc = nullptr;
     int64_t t_actor = 0, t_critic = 0;
     // per-batch buffers
@@ -193,12 +194,17 @@ extern "C" int fsrl_sac_init(fsrl_ctx* c, const fsrl_sac_config* cfg) {
     CHECK_ARG(c->cfg.obs_dim + c->cfg.act_dim <= FSRL_MAX_OBS, "obs_dim + act_dim too large");
     CHECK_ARG(cfg->n_step >= 1 && cfg->n_step <= 8, "n_step must be in [1, 8]");
     CHECK_ARG(cfg->tau >= 0.0f && cfg->tau <= 1.0f, "tau should be in [0, 1]");
+    CHECK_ARG(cfg->actor_mean >= FSRL_ACTOR_MEAN_DEFAULT && cfg->actor_mean <= FSRL_ACTOR_MEAN_TANH,
+              "actor_mean must be 0 (default), 1 (unbounded) or 2 (max_action * tanh), got %d", cfg->actor_mean);
+    CHECK_ARG(!(cfg->deterministic && cfg->actor_mean != FSRL_ACTOR_MEAN_DEFAULT),
+              "actor_mean %d: the deterministic (DDPG-Lagrangian) actor has no such option, pass 0", cfg->actor_mean);
     ENTER_DEV(c);
     if (c->sac) sac_free(c);
     SacState* s = new SacState();
     c->sac = s;
     s->cfg = *cfg;
     s->ddpg = cfg->deterministic != 0;
+    s->mean_tanh = cfg->actor_mean == FSRL_ACTOR_MEAN_TANH ? 1 : 0;       // SAC-Lag's default: the unbounded mean
     s->n_q = s->ddpg ? 2 : 4;
     if (s->ddpg) { s->cfg.auto_alpha = 0; s->cfg.alpha = 0.0f; }      // no entropy term anywhere
     sac_layout(c, s);
@@ -435,7 +441,7 @@ static SacGatherArgs sac_gather_args(const fsrl_ctx* c, const SacState* s, int B
 static SacActorArgs sac_actor_args(const fsrl_ctx* c, const SacState* s, int B, int mode, const float* obs, const float* eps, float* X,
                                    float* lp, float resc, float lam, int deterministic, int probe) {
     SacActorArgs aa{};
-    aa.deterministic = deterministic; aa.max_action = c->cfg.max_action;
+    aa.deterministic = deterministic; aa.max_action = c->cfg.max_action; aa.mean_tanh = s->mean_tanh;
     aa.obs = obs; aa.eps = eps; aa.X = X; aa.lp_out = lp; aa.DA = s->DA; aa.QP = s->QP; aa.sc = s->sc; aa.A1 = s->A1; aa.A2 = s->A2;
     aa.cr = -resc; aa.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f;
     aa.D1 = s->D1; aa.D2 = s->D2; aa.DO = s->DO; aa.statp = s->stpi; aa.B = B; aa.mode = mode; aa.rescale = resc;
@@ -749,7 +755,7 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
                 LaySacActorArgs h{};
                 h.out = s->ka.out; h.dout = s->ka.dout; h.eps = eps_; h.X = X_; h.lp = lp_; h.DXQ = s->DXQ; h.QP = s->QP; h.sc = s->sc;
                 h.statp = s->stpi; h.B = B; h.Bq = s->kq.mbp; h.Do = Do; h.Da = Da; h.mode = mode; h.deterministic = s->ddpg ? 1 : 0;
-                h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.cr = -resc;
+                h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh; h.cr = -resc;
                 h.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f; h.rescale = resc; h.alpha_fixed = s->cfg.alpha;
                 hipLaunchKernelGGL(lay_sac_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, st, h);
                 HIPCHK(hipGetLastError());

@@ -217,6 +217,8 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
                   (s->cfg.use_lagrangian != 0) == (s0->cfg.use_lagrangian != 0),
                   "member %d: members must share n_step, auto_alpha and use_lagrangian (learning rates, tau, seeds and data may differ)", i);
         CHECK_ARG(c->cfg.n_critics == c0->cfg.n_critics, "member %d: members must share n_critics (the lagrangians' row length)", i);
+        CHECK_ARG(s->mean_tanh == s0->mean_tanh, "member %d: members must share actor_mean (the actor's mean is %s, member 0's %s)", i,
+                  s->mean_tanh ? "max_action * tanh(head)" : "unbounded", s0->mean_tanh ? "max_action * tanh(head)" : "unbounded");
         for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member %d is listed twice", i);
     }
     HIPCHK(hipSetDevice(c0->device));

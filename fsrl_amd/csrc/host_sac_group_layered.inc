@@ -202,7 +202,7 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
             h.eps = v == 0 ? s->eps_t : s->eps_p; h.X = v == 0 ? s->XN : s->XP; h.lp = v == 0 ? s->LPN : s->LP;
             h.statp = s->stpi; h.B = B; h.Bq = s->kq.mbp; h.Do = Do; h.Da = Da; h.mode = v == 2 ? SAC_A_BWD : SAC_A_FWD;
             h.deterministic = s->ddpg ? 1 : 0;
-            h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.cr = -resc;
+            h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh; h.cr = -resc;
             h.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f; h.rescale = resc; h.alpha_fixed = s->cfg.alpha;
             LaySacQArgs& q = lg.qh.h[(size_t)v * k + i];
             q.out = s->kq.out; q.dout = s->kq.dout; q.tgt = s->Y; q.statp = v == 2 ? s->stdin_ : s->stq; q.B = B; q.mbp = s->kq.mbp;

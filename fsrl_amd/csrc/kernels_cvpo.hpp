@@ -1,7 +1,7 @@
 // kernels_cvpo.hpp -- CVPO update kernels (fsrl/policy/cvpo.py:206-430).  The replay gather, the
 // float64 n-step target, the Q-network launches, the weight-gradient / Adam / Polyak kernels are the
 // SAC path's (kernels_sac.hpp, kernels_fb.hpp); this file holds what is CVPO's own:
-//   * the Gaussian actor tile (mu = max_action * tanh(head), sigma = exp(clamp(head))) in four modes:
+//   * the Gaussian actor tile (mu = max_action * tanh(head), or the head itself: CvpoActorArgs::mean_tanh; sigma = exp(clamp(head))) in four modes:
 //     target action, the K particles of actor_old, the M-step statistics, the M-step backward;
 //   * the E-step: Adam on the two duals (eta, lambda) of the logsumexp loss and the softmax weights;
 //   * the M-step dual step (Adam on the two KL multipliers) and the logged statistics.
@@ -38,6 +38,7 @@ struct CvpoActorArgs {
     float* statp;            // [n_tiles][FB_NSTAT]
     int B, K, mode;
     float max_action;
+    int mean_tanh;           // 1 -> mu = max_action * tanh(head) (CVPO's default); 0 -> mu = head (ActorProb unbounded=True); uniform over the launch
     // a second batch in the same launch (tiles_half > 0): workgroups [tiles_half, 2 * tiles_half) run mode2 with the actor
     // P2 on obs2 / eps2 into X2.  Used for TARGET (current actor at s_{t+n}) + PARTICLES (actor_old at s_t): neither
     // depends on the critic step in between.
@@ -95,8 +96,8 @@ __device__ __forceinline__ void cvpo_actor_tile_body(TileSmem<H>& sm, const floa
         const bool valid = i < n_valid, on = valid && d < Da;
         float th = 0.0f, mu = 0.0f, sig = 1.0f, pass = 0.0f;
         if (on) {
-            th = tanhf(sm.out[i * FSRL_MAX_ACT + d]);
-            mu = a.max_action * th;
+            mu = sm.out[i * FSRL_MAX_ACT + d];
+            if (a.mean_tanh) { th = tanhf(mu); mu = a.max_action * th; }
             const float lraw = sm.out[i * FSRL_MAX_ACT + Da + d];
             pass = (lraw >= SAC_LOG_SIG_MIN && lraw <= SAC_LOG_SIG_MAX) ? 1.0f : 0.0f;
             sig = expf(fminf(fmaxf(lraw, SAC_LOG_SIG_MIN), SAC_LOG_SIG_MAX));
@@ -144,7 +145,7 @@ __device__ __forceinline__ void cvpo_actor_tile_body(TileSmem<H>& sm, const floa
                     // KL penalties: d kl_mu / d mu = (mu - mu_old) / var_old_c / B ; d kl_std / d sigma (0 where var is clamped)
                     g_mu += dual_mu * invB * (-dmu / var_oc);
                     if (var > 1e-6f) g_sg += dual_std * invB * (1.0f / sig - var_oc / (var * sig));
-                    sm.dout[i * FSRL_DOW + d] = g_mu * a.max_action * (1.0f - th * th);
+                    sm.dout[i * FSRL_DOW + d] = a.mean_tanh ? g_mu * a.max_action * (1.0f - th * th) : g_mu;
                     sm.dout[i * FSRL_DOW + Da + d] = g_sg * sig * pass;
                 }
             }

@@ -17,6 +17,7 @@ struct LaySacActorArgs {
     const SacScalars* sc;
     float* statp;                           // [tiles][FB_NSTAT]
     int B, Bq, Do, Da, mode, deterministic, auto_alpha;
+    int mean_tanh;                          // SacActorArgs::mean_tanh
     float max_action, cr, cc, rescale, alpha_fixed;
 };
 // the workgroup's work on 16-row tile `tile`: shared by the kernel below and the grouped launch (kernels_layered_sac_group.hpp)
@@ -42,9 +43,11 @@ __device__ __forceinline__ void lay_sac_actor_head_body(const LaySacActorArgs& a
         }
     } else {
         if (valid && d < Da) {
-            const float mu = o[d], lraw = o[Da + d];
+            float mu = o[d];
+            const float lraw = o[Da + d];
             pass = (lraw >= SAC_LOG_SIG_MIN && lraw <= SAC_LOG_SIG_MAX) ? 1.0f : 0.0f;
             sig = expf(fminf(fmaxf(lraw, SAC_LOG_SIG_MIN), SAC_LOG_SIG_MAX));
+            if (a.mean_tanh) mu = a.max_action * tanhf(mu);     // ActorProb(unbounded=False); log pi keeps its form: u - mu = sigma * eps
             ep = a.eps[(size_t)r * Da + d];
             const float u = mu + ep * sig;
             const float dv = u - mu;
@@ -80,6 +83,10 @@ __device__ __forceinline__ void lay_sac_actor_head_body(const LaySacActorArgs& a
     __syncthreads();
     if (a.mode == SAC_A_BWD && valid && d < Da) {
         float* dO = a.dout + (size_t)r * FSRL_DOW;
+        if (a.mean_tanh) {                               // the bounded mean: d mu / d head = max_action * (1 - tanh(head)^2), head read again
+            const float th = tanhf(a.out[(size_t)r * FSRL_MAX_ACT + d]);
+            g0 *= a.max_action * (1.0f - th * th);
+        }
         dO[d] = g0;
         if (!a.deterministic) dO[Da + d] = g1;
     }
@@ -161,6 +168,7 @@ struct LayCvpoActorArgs {
     float* statp;
     int B, K, Do, Da, mode;
     float max_action;
+    int mean_tanh;                          // CvpoActorArgs::mean_tanh
 };
 // the workgroup's work on 16-row tile `tile`: shared by the kernel below and the grouped launch (kernels_layered_sac_group.hpp)
 __device__ __forceinline__ void lay_cvpo_actor_head_body(const LayCvpoActorArgs& a, const int tile) {
@@ -180,8 +188,8 @@ __device__ __forceinline__ void lay_cvpo_actor_head_body(const LayCvpoActorArgs&
     const float* o = a.out + (size_t)(valid ? r : 0) * FSRL_MAX_ACT;
     float th = 0.0f, mu = 0.0f, sig = 1.0f, pass = 0.0f;
     if (on) {
-        th = tanhf(o[d]);
-        mu = a.max_action * th;
+        mu = o[d];
+        if (a.mean_tanh) { th = tanhf(mu); mu = a.max_action * th; }
         const float lraw = o[Da + d];
         pass = (lraw >= SAC_LOG_SIG_MIN && lraw <= SAC_LOG_SIG_MAX) ? 1.0f : 0.0f;
         sig = expf(fminf(fmaxf(lraw, SAC_LOG_SIG_MIN), SAC_LOG_SIG_MAX));
@@ -228,7 +236,7 @@ __device__ __forceinline__ void lay_cvpo_actor_head_body(const LayCvpoActorArgs&
             float g_sg = -invKB * (s_wdo2 / (var * sig) - s_w / sig);
             g_mu += dual_mu * invB * (-dmu / var_oc);
             if (var > 1e-6f) g_sg += dual_std * invB * (1.0f / sig - var_oc / (var * sig));
-            g0 = g_mu * a.max_action * (1.0f - th * th);
+            g0 = a.mean_tanh ? g_mu * a.max_action * (1.0f - th * th) : g_mu;
             g1 = g_sg * sig * pass;
         }
     }

@@ -103,6 +103,7 @@ struct SacActorArgs {
     float cr, cc;        // loss weights of min(Qr1,Qr2) and min(Qc1,Qc2): -rescale, rescale*lambda
     int deterministic;   // DDPG-Lag actor: a = max_action * tanh(out), single critics, no entropy (ddpg_lag.py:189-213)
     float max_action;
+    int mean_tanh;       // stochastic actor: 0 -> mu = head (ActorProb unbounded=True), 1 -> mu = max_action * tanh(head); uniform over the launch
     const SacScalars* sc;
     float* A1; float* A2; float* D1; float* D2; float* DO;   // side buffers (BWD)
     float* statp;        // [n_tiles][FB_NSTAT]  st[0] = sum log pi
@@ -247,7 +248,8 @@ __device__ __forceinline__ void sac_actor_tile_body(TileSmem<H>& sm, const float
             }
         } else {
         if (valid && d < Da) {
-            const float mu = sm.out[i * FSRL_MAX_ACT + d];
+            float mu = sm.out[i * FSRL_MAX_ACT + d];
+            if (a.mean_tanh) mu = a.max_action * tanhf(mu);     // ActorProb(unbounded=False); log pi keeps its form: u - mu = sigma * eps
             const float lraw = sm.out[i * FSRL_MAX_ACT + Da + d];
             pass = (lraw >= SAC_LOG_SIG_MIN && lraw <= SAC_LOG_SIG_MAX) ? 1.0f : 0.0f;
             sig = expf(fminf(fmaxf(lraw, SAC_LOG_SIG_MIN), SAC_LOG_SIG_MAX));
@@ -279,7 +281,12 @@ __device__ __forceinline__ void sac_actor_tile_body(TileSmem<H>& sm, const float
             const float c = a.rescale * alpha * invB;                 // weight of log pi in the loss
             const float sq = 2.0f * act * one_m / (one_m + SAC_F32_EPS);   // d(-log(1-a^2+eps))/du
             const float dLdu = c * sq + ga * one_m;                   // (+-(u-mu)/sigma^2 cancel)
-            sm.dout[i * FSRL_DOW + d] = dLdu;                         // d/dmu
+            float dhead = dLdu;                                       // d/dmu
+            if (a.mean_tanh) {                                        // d mu / d head = max_action * (1 - tanh(head)^2), head read again
+                const float th = tanhf(sm.out[i * FSRL_MAX_ACT + d]);
+                dhead = dLdu * (a.max_action * (1.0f - th * th));
+            }
+            sm.dout[i * FSRL_DOW + d] = dhead;                        // d/d(mean head)
             sm.dout[i * FSRL_DOW + Da + d] = (dLdu * ep * sig - c) * pass;   // d/d(raw log sigma)
         }
         }

@@ -543,12 +543,15 @@ class Engine:
     # ---------------------------------------------------------------- SAC-Lagrangian
     def sac_init(self, actor_lr=5e-4, critic_lr=1e-3, alpha_lr=3e-4, tau=0.05, alpha=0.005,
                  target_entropy=None, n_step=2, auto_alpha=True, use_lagrangian=True, deterministic=False,
-                 exploration_sigma=0.1):
-        """deterministic=True selects DDPG-Lagrangian (deterministic actor + target actor, single critics)."""
+                 exploration_sigma=0.1, unbounded=None):
+        """deterministic=True selects DDPG-Lagrangian (deterministic actor + target actor, single critics).
+        unbounded: ActorProb's option -- True: mu = head, False: mu = max_action * tanh(head), None: SAC-Lag's default (True)."""
         te = -float(self.cfg.act_dim) if target_entropy is None else float(target_entropy)
         cfg = _lib.SacConfig(actor_lr, critic_lr, alpha_lr, tau, alpha, te, int(n_step), int(auto_alpha),
-                             int(use_lagrangian), int(deterministic), float(exploration_sigma))
+                             int(use_lagrangian), int(deterministic), float(exploration_sigma),
+                             _lib.actor_mean_code(unbounded))
         _lib.check(self.lib.fsrl_sac_init(self._ctx, C.byref(cfg)))
+        self.actor_unbounded = None if deterministic else (True if unbounded is None else bool(unbounded))
         self.n_sac_actor = int(self.lib.fsrl_sac_param_count(self._ctx, 0))
         self.n_sac_critics = int(self.lib.fsrl_sac_param_count(self._ctx, 1))
 
@@ -620,12 +623,16 @@ class Engine:
     # ---------------------------------------------------------------- CVPO (on the SAC replay context)
     def cvpo_init(self, qc_thres, actor_lr=5e-4, critic_lr=1e-3, tau=0.05, n_step=2, double_critic=False,
                   sample_act_num=16, estep_iter_num=1, mstep_iter_num=1, estep_kl=0.02, estep_dual_max=20.0,
-                  estep_dual_lr=0.02, mstep_kl_mu=0.005, mstep_kl_std=0.0005, mstep_dual_max=0.5, mstep_dual_lr=0.1):
-        """fsrl_cvpo_init (cvpo.py:71-163).  Parameters then move through the sac_* accessors (which=3: actor_old)."""
+                  estep_dual_lr=0.02, mstep_kl_mu=0.005, mstep_kl_std=0.0005, mstep_dual_max=0.5, mstep_dual_lr=0.1,
+                  unbounded=None):
+        """fsrl_cvpo_init (cvpo.py:71-163).  Parameters then move through the sac_* accessors (which=3: actor_old).
+        unbounded: ActorProb's option -- True: mu = head, False: mu = max_action * tanh(head), None: CVPO's default (False)."""
         cfg = _lib.CvpoConfig(actor_lr, critic_lr, tau, int(n_step), int(double_critic), int(sample_act_num),
                               int(estep_iter_num), int(mstep_iter_num), estep_kl, estep_dual_max, estep_dual_lr,
-                              mstep_kl_mu, mstep_kl_std, mstep_dual_max, mstep_dual_lr, float(qc_thres))
+                              mstep_kl_mu, mstep_kl_std, mstep_dual_max, mstep_dual_lr, float(qc_thres),
+                              _lib.actor_mean_code(unbounded))
         _lib.check(self.lib.fsrl_cvpo_init(self._ctx, C.byref(cfg)))
+        self.actor_unbounded = False if unbounded is None else bool(unbounded)
         self.n_sac_actor = int(self.lib.fsrl_sac_param_count(self._ctx, 0))
         self.n_sac_critics = int(self.lib.fsrl_sac_param_count(self._ctx, 1))
         self._ring_cols = _lib.CVPO_NSTATS

@@ -39,8 +39,8 @@ class CVPO(BasePolicy):
                          action_bound_method, observation_space, action_space, lr_scheduler)
         assert self.critics_num == 2, "the HIP path supports one cost constraint (reward + cost critics)"
         assert 0.0 <= tau <= 1.0, "tau should be in [0, 1]"
-        assert getattr(actor, "_c_sigma", False) and not getattr(actor, "_unbounded", True), \
-            "the HIP CVPO path: state-conditioned sigma, bounded mean (the reference defaults, cvpo_agent.py:107-108)"
+        assert getattr(actor, "_c_sigma", False), \
+            "the HIP CVPO path needs ActorProb(conditioned_sigma=True): a state-independent sigma is another parameter layout"
         self.actor_old = deepcopy(self.actor)
         self.actor_old.eval()
         self.actor_optim, self.critics_optim = actor_optim, critic_optim
@@ -64,7 +64,7 @@ class CVPO(BasePolicy):
                               sample_act_num=sample_act_num, estep_iter_num=estep_iter_num, mstep_iter_num=mstep_iter_num,
                               estep_kl=estep_kl, estep_dual_max=estep_dual_max, estep_dual_lr=estep_dual_lr,
                               mstep_kl_mu=mstep_kl_mu, mstep_kl_std=mstep_kl_std, mstep_dual_max=mstep_dual_max,
-                              mstep_dual_lr=mstep_dual_lr)
+                              mstep_dual_lr=mstep_dual_lr, unbounded=bool(getattr(actor, "_unbounded", False)))
         self.engine.sac_set_params(SACLagrangian._flat([self.actor]), SACLagrangian._flat(list(self.critics)), 0.0)
         self.engine.cvpo_pre_update()
         # reference_rng: buffer.sample through numpy's and every Normal.sample through torch's global RNG, in the

@@ -51,15 +51,21 @@ class SACLagrangian(LagrangianPolicy):
         from fsrl_amd.utils.net import mlp_geometry
         obs_dim, hidden_sizes = mlp_geometry(actor.preprocess)
         act_dim = actor.mu.model[0].weight.shape[0]
+        assert getattr(actor, "_c_sigma", True), \
+            "the HIP SAC path needs ActorProb(conditioned_sigma=True): a state-independent sigma is another parameter layout"
+        # ActorProb's `unbounded` travels to the device (fsrl_sac_config.actor_mean): the update kernels and the
+        # collector's actor compute the mean this host mirror computes.  A bounded mean needs the actor's max_action.
+        unbounded = bool(getattr(actor, "_unbounded", True))
+        bound = {} if unbounded else {"max_action": float(actor._max)}
         dev = device if isinstance(device, int) else (int(str(device).split(":")[-1]) if ":" in str(device) else 0)
         self.engine = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=int(obs_dim), act_dim=int(act_dim),
                                           hidden_sizes=hidden_sizes, n_critics=2, env_num=int(env_num),
-                                          buffer_size=int(buffer_size), gamma=gamma, target_kl=None),
+                                          buffer_size=int(buffer_size), gamma=gamma, target_kl=None, **bound),
                              device=dev)
         self.engine.sac_init(actor_lr=actor_optim.param_groups[0]["lr"],
                              critic_lr=critic_optim.param_groups[0]["lr"], alpha_lr=alpha_lr, tau=tau,
                              alpha=alpha_fixed, target_entropy=self._target_entropy, n_step=n_step,
-                             auto_alpha=self._is_auto_alpha, use_lagrangian=use_lagrangian)
+                             auto_alpha=self._is_auto_alpha, use_lagrangian=use_lagrangian, unbounded=unbounded)
         self._push_params()
         self._dirty = self._rest_dirty = False
         # reference_rng=True: buffer.sample through numpy's and rsample through torch's global RNG,

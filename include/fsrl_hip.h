@@ -490,8 +490,9 @@ int fsrl_focops_set_nu(fsrl_ctx* ctx, double nu, double nu_loss);
  *      Create the context with algo = FSRL_ALGO_SAC_LAG (obs_dim, act_dim <= 8, hidden, env_num,
  *      buffer_size, gamma are read from fsrl_config), then fsrl_sac_init.
  *      Parameter vectors in torch parameters() order:
- *        actor   : W1[H,Do] b1 W2[H,H] b2 Wmu[Da,H] bmu Wsig[Da,H] bsig   (ActorProb, conditioned sigma,
- *                  unbounded mean; sac_lag_agent.py:126-134)
+ *        actor   : W1[H,Do] b1 W2[H,H] b2 Wmu[Da,H] bmu Wsig[Da,H] bsig   (ActorProb, conditioned sigma;
+ *                  sac_lag_agent.py:126-134.  The mean is the head itself by default, ActorProb(unbounded=True),
+ *                  or max_action * tanh(head): fsrl_sac_config.actor_mean)
  *        critics : for (reward, cost): pre1(W1[H,Do+Da] b1 W2 b2) pre2(..) last1(W[1,H] b) last2(W b)
  *                  (DoubleCritic, fsrl/utils/net/continuous.py:13-101)                          */
 typedef struct fsrl_sac_config {
@@ -510,7 +511,15 @@ typedef struct fsrl_sac_config {
      * exploration noise fsrl_actor_sample adds (GaussianNoise, ddpg_lag_agent.py:80,160).              */
     int32_t deterministic;
     float exploration_sigma;
+    /* How the Gaussian actor's mean head becomes the mean (ActorProb's `unbounded`, fsrl/utils/net/continuous.py):
+     *   0 = the kind's default (SAC-Lag: mu = head; CVPO: mu = max_action * tanh(head)),
+     *   1 = unbounded, mu = head,   2 = bounded, mu = max_action * tanh(head)   -- for either kind.
+     * The action is a = tanh(mu + sigma * eps) either way.  deterministic = 1 (tianshou's Actor has no such option) takes 0 only. */
+    int32_t actor_mean;
 } fsrl_sac_config;
+#define FSRL_ACTOR_MEAN_DEFAULT 0
+#define FSRL_ACTOR_MEAN_UNBOUNDED 1
+#define FSRL_ACTOR_MEAN_TANH 2
 #define FSRL_SAC_NSTATS 10  /* rescaling, lagrangian, actor_safety, alpha_loss, alpha_value, actor_rew,
                                actor_total (sac_lag.py:231-257) then q0, q1, q_total (:203-208) */
 int fsrl_sac_init(fsrl_ctx* ctx, const fsrl_sac_config* cfg);
@@ -587,7 +596,8 @@ int fsrl_sac_group_update(fsrl_sac_group* g, int32_t batch_size, const int32_t* 
 
 /* ---- CVPO (fsrl/policy/cvpo.py:71-430), on the replay context of SAC-Lagrangian: create the
  *      context with algo = FSRL_ALGO_SAC_LAG, then fsrl_cvpo_init INSTEAD of fsrl_sac_init.
- *      Networks (cvpo_agent.py:143-186): Gaussian actor, mu = max_action * tanh(head), sigma = exp(clamp(head,
+ *      Networks (cvpo_agent.py:143-186): Gaussian actor, mu = max_action * tanh(head) by default or mu = head
+ *      (fsrl_cvpo_config.actor_mean; the reference's MujocoBaseCfg sets unbounded=True), sigma = exp(clamp(head,
  *      -20, 2)), NOT squashed after sampling, with a hard-copied actor_old; per metric one SingleCritic
  *      (double_critic == 0; vector layout as DDPG-Lag's critics) or one DoubleCritic (layout as SAC's) with
  *      Polyak targets.  Parameters move through fsrl_sac_params_set / _get / _put (which = 3 is actor_old);
@@ -603,6 +613,7 @@ typedef struct fsrl_cvpo_config {
     float estep_kl, estep_dual_max, estep_dual_lr;                 /* 0.02, 20, 0.02                       */
     float mstep_kl_mu, mstep_kl_std, mstep_dual_max, mstep_dual_lr;/* 0.005, 0.0005, 0.5, 0.1              */
     double qc_thres;                       /* cost_limit * (1 - gamma^T) / (1 - gamma) / T   (cvpo.py:138-141) */
+    int32_t actor_mean;                    /* FSRL_ACTOR_MEAN_*: 0 = CVPO's default (tanh), 1 = unbounded, 2 = tanh */
 } fsrl_cvpo_config;
 #define FSRL_CVPO_NSTATS 17 /* estep_loss, dual0 (eta), dual1 (lambda)                      (cvpo.py:346-354)
                                kl_mu, kl_std, loss_kl, loss_mle, loss_total, dual_mu, dual_std, entropy (:405-415)

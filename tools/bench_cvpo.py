@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--updates", type=int, default=1000)
     ap.add_argument("--cpu-updates", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--unbounded", choices=("default", "true", "false"), default="default",
+                    help="the actor's mean: true = the head, false = max_action * tanh(head); default: the agent's own")
     a = ap.parse_args()
     Do, Da, H, E, B, K = a.obs, a.act, a.hidden, a.envs, a.batch, a.k
     T = a.rows // E
@@ -39,7 +41,7 @@ def main():
     ocfg = CVPOConfig(obs_dim=Do, act_dim=Da, hidden=(H, H), sample_act_num=K, max_episode_steps=300)
     eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden=H, n_critics=2, env_num=E,
                               buffer_size=a.rows, gamma=ocfg.gamma, target_kl=None))
-    eng.cvpo_init(ocfg.qc_thres, sample_act_num=K)
+    eng.cvpo_init(ocfg.qc_thres, sample_act_num=K, unbounded={"default": None, "true": True, "false": False}[a.unbounded])
     if os.environ.get("FSRL_SAC_SPLITK"):      # A/B: split-K weight gradients at every batch size (fsrl_sac_set_plan)
         eng.sac_set_plan(1)
     o = CVPOOracle(ocfg)
@@ -78,7 +80,7 @@ def main():
     assert np.isfinite(st).all() and len(st) == min(a.updates, 4096), st[-1]
     out = {"metric": "cvpo policy-updates/sec", "value": 1.0 / dev, "unit": "updates/s", "us_per_update": dev * 1e6,
            "config": {"workload": f"CVPO defaults: obs {Do} act {Da} {H}x{H}, SingleCritic pair, store {T * E} rows in HBM, "
-                                  f"batch {B}, K {K}, n_step 2", "updates": a.updates}, "dtype": "fp32",
+                                  f"batch {B}, K {K}, n_step 2", **({} if a.unbounded == "default" else {"unbounded": a.unbounded}), "updates": a.updates}, "dtype": "fp32",
            "last_stats": [float(x) for x in st[-1]]}
     # roofline of the whole update (13 launches), algorithmic FLOPs: forward F per row and network, gradient = 3 F
     Fq = 2 * ((Do + Da) * H + H * H + H); Fa = 2 * (Do * H + H * H + H * 2 * Da)

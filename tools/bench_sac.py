@@ -29,13 +29,15 @@ def main(argv=None, emit=True):
     ap.add_argument("--updates", type=int, default=1000)
     ap.add_argument("--cpu-updates", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--unbounded", choices=("default", "true", "false"), default="default",
+                    help="the actor's mean: true = the head, false = max_action * tanh(head); default: the agent's own")
     a = ap.parse_args(argv)
     Do, Da, H, E, B = 33, 8, a.hidden, a.envs, a.batch
     T = a.rows // E
     rng = np.random.default_rng(0)
     eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden=H, n_critics=2, env_num=E,
                               buffer_size=a.rows, gamma=0.99, target_kl=None))
-    eng.sac_init()
+    eng.sac_init(unbounded={"default": None, "true": True, "false": False}[a.unbounded])
     if os.environ.get("FSRL_SAC_SPLITK"):      # A/B: split-K weight gradients at every batch size (fsrl_sac_set_plan)
         eng.sac_set_plan(1)
     if os.environ.get("FSRL_SAC_PLAN"):        # A/B: plan bits (2 = sample / gather / n-step as launches of their own)
@@ -83,7 +85,7 @@ def main(argv=None, emit=True):
     out = {"metric": "sac_lag policy-updates/sec", "value": 1.0 / dev, "unit": "updates/s",
            "ms_per_update": dev * 1e3, "samples_per_s": B / dev,
            "config": {"workload": f"SAC-Lag SafetyAntRun shape obs {Do} act {Da} {H}x{H}, store {T * E} rows in HBM, "
-                                  f"batch {B}, n_step 2", "updates": a.updates, "blocks_us_per_update": [round(b * 1e6, 1) for b in blocks]},
+                                  f"batch {B}, n_step 2", **({} if a.unbounded == "default" else {"unbounded": a.unbounded}), "updates": a.updates, "blocks_us_per_update": [round(b * 1e6, 1) for b in blocks]},
            "store_fill_rows_per_s": T * E / fill_s, "dtype": "fp32",
            # r5 default: sample + gather inside the actors' forward launch; FSRL_SAC_PLAN bits 4 / 1 / 2 add launches back
            "launches_per_update": 9 + sum(1 for bit in (16, 2, 4) if int(os.environ.get("FSRL_SAC_PLAN", "0")) & bit)}
