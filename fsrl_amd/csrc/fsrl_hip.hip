@@ -243,8 +243,8 @@ static void collect_group_detach(fsrl_ctx* c);    // ... before its collect grou
 static void collect_group_actor_release(struct fsrl_collect_group* g);   // that group's resident actor: it holds this member's actor weights
 // grouped FOCOPS (host_focops_group.inc): the member checks of fsrl_group_create / _ppo_update, and the update itself
 static int focops_group_check(fsrl_ctx* const* ctxs, int k);
-static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
-                               float* const* stats_out, int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
+struct GroupUpdate;                                 // the frame of a grouped on-policy update (host_group.inc)
+static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repeat);
 #define ENTER_DEV(c) do { HIPCHK(hipSetDevice((c)->device)); pactor_release(c); } while (0)
 
 static int join_store(fsrl_ctx* c) {

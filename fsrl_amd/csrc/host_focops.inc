@@ -53,6 +53,8 @@ static void focops_blocks(const fsrl_ctx* c, int* nb_a, int* nb_c0, int* nb_c1) 
     *nb_c0 = (c->md.net[1].end - c->md.net[1].begin + 255) / 256;
     *nb_c1 = (c->md.net[2].end - c->md.net[2].begin + 255) / 256;
 }
+// 4-row tiles of the fused tile launch only while the three networks of its n_act members (focops_pass: 1) fit the chip in one round
+static bool focops_rows4(const fsrl_ctx* c, int tiles, int n_act) { return (size_t)tiles * 4 * 3 * n_act <= (size_t)c->n_cus; }
 // the FOCOPS working set for the current minibatch plan (c->mbp_max): allocated on first use, regrown with the minibatch
 // (focops_pass and, per member, the grouped update)
 static int focops_alloc(fsrl_ctx* c) {
@@ -173,7 +175,7 @@ static int focops_pass(fsrl_ctx* c, int32_t* stopped_out) {
         const int start = c->mb_start[(size_t)mb], size = c->mb_size[(size_t)mb];
         const int tiles = (size + 15) / 16, rows_pad = tiles * 16;
         FbArgs a = focops_tile_args(c, start, size);
-        const bool rows4 = !layered && 4 * tiles * 3 <= c->n_cus;
+        const bool rows4 = !layered && focops_rows4(c, tiles, 1);
         int rc = 0;
         if (layered) {
             LayState* ls = c->lay;

@@ -1,13 +1,14 @@
 // host_focops_group.inc -- grouped FOCOPS updates: fsrl_group_create / fsrl_group_ppo_update for a group of FOCOPS contexts
-// (part of fsrl_hip.hip, kernels: kernels_focops_group.hpp).  k x Engine.focops_update in lock step: begin -> per pass
-// ppo_pass_prepare of every member -> the minibatch steps, every launch carrying all members still active -> end.  Each
-// member keeps its own nu / nu_loss (fsrl_focops_set_nu), Adam counters, psq / sig_stash parity, store, statistics rows
-// and KL early stop (the `delta` check, always watched: a member that stops sits the later passes out).
+// (part of fsrl_hip.hip, kernels: kernels_focops_group.hpp).  k x Engine.focops_update in lock step inside the frame of a grouped
+// on-policy update (ogroup_*, host_group.inc: begin, per pass the batch preparation, counters and KL verdicts, end, the error
+// path); here: the FOCOPS checks, working sets, tables and launches, every launch carrying all members still active.  Each
+// member keeps its own nu / nu_loss (fsrl_focops_set_nu), Adam counters, psq / sig_stash parity, store, statistics rows and KL
+// early stop (the `delta` check, always watched: a member that stops sits the later passes out).
 // Bit-identity with focops_pass: the step table holds exactly the arguments focops_pass builds for the member's minibatch
 // (the same host helpers, host_focops.inc), each member keeps its own three- or four-launch plan, and the kernels run the
-// single-context bodies.  The tile height of a launch is the PPO group's rule (4-row tiles only while every active member
-// fits one round of workgroups), so a group of one is bit-identical to its solo run, and larger groups are wherever the tile
-// height does not change (tests/test_gpu_group_focops.py).
+// single-context bodies.  The tile height of a launch is focops_pass's rule over the whole launch (focops_rows4: 4-row tiles
+// only while every active member fits one round of workgroups), so a group of one is bit-identical to its solo run, and larger
+// groups are wherever the tile height does not change (tests/test_gpu_group_focops.py).
 // A group of LAYERED members (all of one shape) runs focops_pass's layered step instead: 2 L + 5 launches per minibatch step for
 // all members -- the PPO group's forward / backward / weight-side launches over its job tables (host_layered_group.inc), the
 // loss heads (lay_fb_head_group_kernel), prep with the finished gradient in G as the one partial, step.  No tile plan, no
@@ -35,48 +36,32 @@ static int focops_group_check(fsrl_ctx* const* ctxs, int k) {
     return 0;
 }
 
-static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat, const int64_t* const* perms, uint64_t seed,
-                               float* const* stats_out, int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
-    const int k = (int)g->m.size();
+static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repeat) {
+    fsrl_group* g = u.g; fsrl_ctx* c0 = g->m[0];
+    const int k = u.k; hipStream_t s = g->stream;
     int rc = focops_group_check(g->m.data(), k);
     if (rc) return rc;
-    group_actor_release(g);                     // the update goes behind the collect kernel, which ends
-    fsrl_ctx* c0 = g->m[0];
-    for (fsrl_ctx* m : g->m) m->theta_version += 1;
-    HIPCHK(hipSetDevice(c0->device));
-    hipStream_t s = g->stream;
     const int H = c0->cfg.hidden, nn = 3;
     const bool layered = c0->lay != nullptr;
-    auto abort_all = [&](int rc_) { for (fsrl_ctx* c : g->m) c->in_update = false; return rc_; };
-    // ---- begin: sample(0) + process_fn of every member (FOCOPS: no multipliers, rescaling 1, as Engine.focops_update)
+    // ---- begin (FOCOPS: no multipliers, rescaling 1, as Engine.focops_update).  The layered step's launches read the PPO group's
+    // tables too: per pass the step rows' active / mb_size / mb_start
     const double zero_lag[FSRL_MAX_CRITICS] = {};
-    std::vector<int64_t> n((size_t)k, 0);
-    for (int i = 0; i < k; ++i) {
-        rc = fsrl_ppo_begin(g->m[i], zero_lag, 1.0, batch_size, &n[i]);
-        if (rc) return abort_all(rc);
-        if (stopped_pass_out) stopped_pass_out[i] = -1;
-    }
-    std::vector<char> active((size_t)k, 1), fast((size_t)k, 0);
+    rc = ogroup_begin(u, zero_lag, 0, nullptr, batch_size, true, layered);
+    if (rc) return rc;
+    char fast[FSRL_MAX_GROUP] = {};
     for (int i = 0; i < k; ++i) {
         fsrl_ctx* c = g->m[i];
-        if (n[i] == 0) { active[(size_t)i] = 0; continue; }
+        if (!u.active[i]) continue;
         rc = focops_alloc(c);                   // the members' working sets before the first grouped pass
-        if (rc) return abort_all(rc);
-        fast[(size_t)i] = !layered && !c->foc->no_fast && c->mbp_max <= 512;
+        if (rc) return rc;
+        fast[i] = !layered && !c->foc->no_fast && c->mbp_max <= 512;
     }
-    size_t cap_nmb = 0;
-    for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
     rc = table_ensure(g->ftab, (size_t)k, (size_t)k);
-    if (rc) return abort_all(rc);
-    const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;          // grown as the PPO group's step table
-    rc = table_ensure(g->fsteps, n_steps, 2 * n_steps, g->stream);
-    if (rc) return abort_all(rc);
+    if (rc) return rc;
     if (layered) {
-        // the layered step's launches read the PPO group's tables: job tables of this update (the members' working sets are in
-        // place now), the member table for the observation operands, and per pass the step rows' active / mb_size / mb_start
-        rc = table_ensure(g->steps, n_steps, 2 * n_steps, g->stream);
-        if (!rc) rc = lay_group_tables(g->lay, g->m.data(), k, active.data(), s);
-        if (rc) return abort_all(rc);
+        // job tables of this update (the members' working sets are in place now) and the member table for the observation operands
+        rc = lay_group_tables(g->lay, g->m.data(), k, u.active, s);
+        if (rc) return rc;
         for (int i = 0; i < k; ++i) lay_group_agent(g->m[i], g->tab.h[i]);
         HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(GroupAgent), hipMemcpyHostToDevice, s));
     }
@@ -88,34 +73,24 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
     const int passes = wb.passes, NB = wb.NB;
     std::vector<char> rows4;
     for (int pass = 0; pass < repeat; ++pass) {
-        int n_act = 0;
-        for (int i = 0; i < k; ++i) n_act += active[(size_t)i] ? 1 : 0;
-        if (n_act == 0) break;
-        size_t max_nmb = 0;
-        for (int i = 0; i < k; ++i) if (active[(size_t)i]) max_nmb = std::max(max_nmb, g->m[i]->mb_start.size());
-        // the pinned tables of the previous pass must have left host memory before they are rewritten
-        if (g->steps_in_flight) { HIPCHK(hipEventSynchronize(g->steps_copied)); g->steps_in_flight = false; }
         // ---- per member: permutation + batch preparation of this pass; split-K buffers for its largest minibatch
-        for (int i = 0; i < k; ++i) {
-            if (!active[(size_t)i]) continue;
-            fsrl_ctx* c = g->m[i];
-            rc = ppo_pass_prepare(c, perms ? perms[i] + (size_t)pass * (size_t)n[i] : nullptr, seed ? seed + 1000003ull * i + pass : 0);
-            if (rc) return abort_all(rc);
-            if (!fast[(size_t)i] && !layered) {
-                int ns = 1;
-                for (int sz : c->mb_size) ns = std::max(ns, wgrad_plan((sz + 15) / 16 * 16, NB * nn, c->n_cus).nsplit);
-                rc = ensure_parts(c, c->n_dev, ns);
-                if (rc) return abort_all(rc);
-            }
-        }
-        // ---- tile height per minibatch step: the PPO group's rule over the members active in the pass (the layered step has
-        // no tile plan: 16-row tiles of the loss head, as the member's own pass)
+        rc = ogroup_pass_begin(u, pass, [&](int i, fsrl_ctx* c) {
+            if (fast[i] || layered) return 0;
+            int ns = 1;
+            for (int sz : c->mb_size) ns = std::max(ns, wgrad_plan((sz + 15) / 16 * 16, NB * nn, c->n_cus).nsplit);
+            return ensure_parts(c, c->n_dev, ns);
+        });
+        if (rc) return rc;
+        if (u.n_act == 0) break;
+        const size_t max_nmb = u.max_nmb;
+        // ---- tile height per minibatch step: focops_pass's rule over the members active in the pass (the layered step has no
+        // tile plan: 16-row tiles of the loss head, as the member's own pass)
         rows4.assign(max_nmb, 0);
         for (size_t mb = 0; mb < max_nmb && !layered; ++mb) {
             int tiles = 0;
             for (int i = 0; i < k; ++i)
-                if (active[(size_t)i] && mb < g->m[i]->mb_size.size()) tiles = std::max(tiles, (g->m[i]->mb_size[mb] + 15) / 16);
-            rows4[mb] = (size_t)tiles * 4 * nn * n_act <= (size_t)c0->n_cus;
+                if (u.active[i] && mb < g->m[i]->mb_size.size()) tiles = std::max(tiles, (g->m[i]->mb_size[mb] + 15) / 16);
+            rows4[mb] = focops_rows4(c0, tiles, u.n_act);
         }
         // ---- member table and step table of the pass: focops_pass's arguments, member by member
         memset(g->fsteps.h, 0, max_nmb * k * sizeof(FocGroupStep));
@@ -125,9 +100,9 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             FocGroupMember& t = g->ftab.h[i];
             memset(&t, 0, sizeof(t));
             t.P = c->P;
-            if (!active[(size_t)i]) continue;
+            if (!u.active[i]) continue;
             FocState* f = c->foc;
-            t.fast = fast[(size_t)i];
+            t.fast = fast[i];
             t.pass_prep = focops_step_args(c, f->pp);
             t.pass_prep.nparts = 0;
             const int nmb = (int)c->mb_start.size();
@@ -169,7 +144,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
         g->steps_in_flight = true;
         // ---- the pass: one pass-start prep for the three-launch members, then per minibatch step 3 or 4 launches for all
         bool any_fast = false;
-        for (int i = 0; i < k; ++i) any_fast = any_fast || (active[(size_t)i] && fast[(size_t)i]);
+        for (int i = 0; i < k; ++i) any_fast = any_fast || (u.active[i] && fast[i]);
         if (any_fast)
             hipLaunchKernelGGL((focops_prep_group_kernel<1>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->ftab.d, g->fsteps.d);
         for (size_t mb = 0; mb < max_nmb; ++mb) {
@@ -180,7 +155,7 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
             for (int i = 0; i < k; ++i) {
                 if (!hst[i].active) continue;
                 tiles = std::max(tiles, hst[i].n_tiles);
-                if (fast[(size_t)i]) f3 = true;
+                if (fast[i]) f3 = true;
                 else { f4 = true; remap = std::max(remap, hst[i].wa.remap_total); }
             }
             if (tiles == 0) continue;                            // no active member has a minibatch at this index
@@ -205,32 +180,14 @@ static int focops_group_update(fsrl_group* g, int32_t batch_size, int32_t repeat
                                            g->ftab.d, st);
                 return 0;
             });
-            if (rc) return abort_all(rc);
+            if (rc) return rc;
             if (f4) hipLaunchKernelGGL((focops_prep_group_kernel<0>), dim3(nb_all, k), dim3(256), 0, s, c0->md, g->ftab.d, st);
             hipLaunchKernelGGL(focops_step_group_kernel, dim3(nb_all + 1, k), dim3(256), 0, s, c0->md, st);
             HIPCHK(hipGetLastError());
         }
-        for (int i = 0; i < k; ++i) {
-            if (!active[(size_t)i]) continue;
-            fsrl_ctx* c = g->m[i];
-            c->n_steps += (int64_t)c->mb_start.size();
-            c->pass_index += 1;
-        }
-        // ---- pass-level KL early stop per member (focops_pass's verdict, always watched): one readback per pass for the group
-        for (int i = 0; i < k; ++i)
-            if (active[(size_t)i]) HIPCHK(hipMemcpyAsync(g->m[i]->h_ctrl, g->m[i]->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (int i = 0; i < k; ++i) {
-            if (active[(size_t)i] && g->m[i]->h_ctrl->stopped_after != INT_MAX) {
-                active[(size_t)i] = 0;
-                if (stopped_pass_out) stopped_pass_out[i] = pass;
-            }
-        }
-    }
-    // ---- end: statistics of every member
-    for (int i = 0; i < k; ++i) {
-        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, cap_steps, n_steps_out ? n_steps_out + i : nullptr);
-        if (rc) return abort_all(rc);
+        // ---- counters (the Adam steps are FocState's: focops_step_fill) and the KL early stop: focops_pass's verdict, always watched
+        rc = ogroup_pass_end(u, pass, false, true);
+        if (rc) return rc;
     }
     return 0;
 }

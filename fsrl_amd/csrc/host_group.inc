@@ -2,12 +2,13 @@
 // carries all of them as grid.y (part of fsrl_hip.hip; SURVEY 8e "optional within-GPU batching of k seeds").
 // The kernels inline the single-agent bodies; a member's update is bit-identical to fsrl_ppo_update on that member alone
 // only when the launch shapes agree (a group of ONE with at most 512 rows per minibatch): the group picks its tile height
-// from the number of active members and the largest member, and above 512 rows it keeps the in-kernel reduction where the
-// single path goes through the split-K kernels.  Otherwise: the golden tests' tolerances (tests/test_gpu_group.py).
+// from the number of active members and the largest member (ppo_tile_plan, host_ppo.inc: fsrl_ppo_pass's rule), and above 512
+// rows it keeps the in-kernel reduction where the single path goes through the split-K kernels.  Otherwise: the golden tests'
+// tolerances (tests/test_gpu_group.py).
 // A group of FOCOPS contexts runs the same entry points through host_focops_group.inc (one algorithm per group).
 // A group of LAYERED PPO-Lagrangian or FOCOPS contexts (any other `hidden_sizes`, all members of one shape) runs the layered
 // minibatch step with every member in each of its 2 L + 5 launches (host_layered_group.inc); there a member's update IS its own
-// fsrl_ppo_update / Engine.focops_update bit for bit, whatever the group.
+// fsrl_ppo_update / Engine.focops_update bit for bit, whatever the group.  All four run inside one frame (ogroup_*, below).
 // ====================================================================================== groups
 #define FSRL_MAX_GROUP 16
 
@@ -134,87 +135,114 @@ extern "C" int fsrl_group_set_plan(fsrl_group* g, int32_t tall_tiles) {
     return 0;
 }
 
-// k x BasePolicy.update (base_policy.py:332-355) in lock step.  lagrangians: [k][n_critics - 1]; rescaling: [k];
-// perms: NULL (library shuffles) or k pointers, member i's = [repeat][n_i]; stats_out: k pointers or NULL.
-// A FOCOPS group: k x Engine.focops_update (lagrangians / rescaling ignored, host_focops_group.inc).
-extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, const double* rescaling, int32_t batch_size,
-                                     int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
-                                     int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
-    CHECK_ARG(g, "null argument");
-    CHECK_ARG(repeat >= 0, "repeat must be >= 0");
-    if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
-    if (g->m[0]->cfg.algo == FSRL_ALGO_FOCOPS)
-        return focops_group_update(g, batch_size, repeat, perms, seed, stats_out, cap_steps, n_steps_out, stopped_pass_out);
-    CHECK_ARG(rescaling, "null argument");
+// ---- the frame of one grouped on-policy update, the same for the PPO-Lagrangian update below and the FOCOPS update
+//      (host_focops_group.inc), fused and layered: fsrl_group_ppo_update -> the update's own pre-checks, ogroup_begin, per pass
+//      ogroup_pass_begin / the update's tables, their copies and the steps_copied event behind them / its launches / ogroup_pass_end ->
+//      every member's fsrl_ppo_end.  One error path, in fsrl_group_ppo_update: once a member has been through fsrl_ppo_begin, a
+//      failure clears in_update on every member and does nothing else.
+struct GroupUpdate {
+    fsrl_group* g = nullptr; int k = 0;
+    const int64_t* const* perms = nullptr; uint64_t seed = 0;      // ppo_pass_prepare's, per member and pass
+    int32_t* stopped_pass_out = nullptr;
+    bool begun = false;                         // a member has been through fsrl_ppo_begin
+    int64_t n[FSRL_MAX_GROUP] = {};             // rows of each member's batch
+    char active[FSRL_MAX_GROUP] = {};           // still stepping: has rows and has not stopped on KL
+    int n_act = 0; size_t max_nmb = 0;          // of the current pass: the active members, the longest plan among them
+};
+// sample(0) + process_fn of every member, back to back on the shared stream; member i's multipliers are lagrangians + i * lag_stride
+// (NULL: none) and rescaling[i] (NULL: 1).  Then the step tables the update names (fsteps: the FOCOPS rows, steps: the GroupStep
+// rows): [minibatch steps of the longest plan][k] rows, grown to twice what this call needs, behind the stream's reads of the old tables.
+static int ogroup_begin(GroupUpdate& u, const double* lagrangians, size_t lag_stride, const double* rescaling, int32_t batch_size,
+                        bool fsteps, bool steps) {
+    fsrl_group* g = u.g;
     group_actor_release(g);                     // the update goes behind the collect kernel, which ends
-    const int k = (int)g->m.size();
-    fsrl_ctx* c0 = g->m[0];
     for (fsrl_ctx* m : g->m) m->theta_version += 1;
-    HIPCHK(hipSetDevice(c0->device));
-    hipStream_t s = g->stream;
-    const int C = c0->cfg.n_critics, H = c0->cfg.hidden, nn = c0->md.n_nets, Do = c0->cfg.obs_dim;
-    const bool layered = c0->lay != nullptr;
-    auto abort_all = [&](int rc) { for (fsrl_ctx* c : g->m) c->in_update = false; return rc; };
-    // ---- begin: sample(0) + process_fn of every member, back to back on the shared stream
-    std::vector<int64_t> n((size_t)k, 0);
-    for (int i = 0; i < k; ++i) {
-        int rc = fsrl_ppo_begin(g->m[i], lagrangians ? lagrangians + (size_t)i * (C - 1) : nullptr, rescaling[i], batch_size, &n[i]);
-        if (rc) return abort_all(rc);
-        if (stopped_pass_out) stopped_pass_out[i] = -1;
+    HIPCHK(hipSetDevice(g->m[0]->device));
+    u.begun = true;
+    size_t cap_nmb = 1;
+    for (int i = 0; i < u.k; ++i) {
+        int rc = fsrl_ppo_begin(g->m[i], lagrangians ? lagrangians + i * lag_stride : nullptr, rescaling ? rescaling[i] : 1.0, batch_size, &u.n[i]);
+        if (rc) return rc;
+        if (u.stopped_pass_out) u.stopped_pass_out[i] = -1;
+        u.active[i] = u.n[i] != 0;              // an empty member sits the update out: it keeps a stale plan from an earlier update
+        if (u.active[i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
     }
-    // ---- member table
+    const size_t rows = cap_nmb * u.k;
+    int rc = fsteps ? table_ensure(g->fsteps, rows, 2 * rows, g->stream) : 0;
+    if (!rc && steps) rc = table_ensure(g->steps, rows, 2 * rows, g->stream);
+    return rc;
+}
+// Start of a pass.  u.n_act == 0 afterwards: every member is empty or has stopped, the update is over.  Otherwise the pass has the steps
+// of the longest plan among the members still active (one that stopped on KL no longer counts), the previous pass's pinned tables have
+// left host memory, and every active member's permutation + batch preparation is enqueued, each followed by the update's prepared(i, c).
+template <class Prepared>
+static int ogroup_pass_begin(GroupUpdate& u, int pass, Prepared&& prepared) {
+    u.n_act = 0; u.max_nmb = 0;
+    for (int i = 0; i < u.k; ++i)
+        if (u.active[i]) { u.n_act += 1; u.max_nmb = std::max(u.max_nmb, u.g->m[i]->mb_start.size()); }
+    if (u.n_act == 0) return 0;
+    if (u.g->steps_in_flight) { HIPCHK(hipEventSynchronize(u.g->steps_copied)); u.g->steps_in_flight = false; }
+    for (int i = 0; i < u.k; ++i) {
+        if (!u.active[i]) continue;
+        int rc = ppo_pass_prepare(u.g->m[i], u.perms ? u.perms[i] + (size_t)pass * (size_t)u.n[i] : nullptr, u.seed ? u.seed + 1000003ull * i + pass : 0);
+        if (!rc) rc = prepared(i, u.g->m[i]);
+        if (rc) return rc;
+    }
+    return 0;
+}
+// After the launches of a pass: the active members' counters (ppo_adam_t: the context's Adam step count too; FOCOPS keeps its own in
+// FocState) and, if watch_kl, the pass-level KL early stop per member (the reference's `break`): one readback per pass for the group.
+static int ogroup_pass_end(GroupUpdate& u, int pass, bool ppo_adam_t, bool watch_kl) {
+    for (int i = 0; i < u.k; ++i) {
+        if (!u.active[i]) continue;
+        fsrl_ctx* c = u.g->m[i];
+        const int64_t nmb = (int64_t)c->mb_start.size();
+        c->n_steps += nmb; c->pass_index += 1;
+        if (ppo_adam_t) c->adam_t += nmb;
+        if (watch_kl) HIPCHK(hipMemcpyAsync(c->h_ctrl, c->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, u.g->stream));
+    }
+    if (!watch_kl) return 0;
+    HIPCHK(hipStreamSynchronize(u.g->stream));
+    for (int i = 0; i < u.k; ++i) {
+        if (!u.active[i] || u.g->m[i]->h_ctrl->stopped_after == INT_MAX) continue;
+        u.active[i] = 0;
+        if (u.stopped_pass_out) u.stopped_pass_out[i] = pass;
+    }
+    return 0;
+}
+
+// k x BasePolicy.update (base_policy.py:332-355) in lock step: the member table, the step table of a pass and the launches of a
+// minibatch step -- 3 (2 without a clip) for all fused members, 2 L + 5 for all layered ones (host_layered_group.inc)
+static int ppo_group_update(GroupUpdate& u, const double* lagrangians, const double* rescaling, int32_t batch_size, int32_t repeat) {
+    CHECK_ARG(rescaling, "null argument");
+    fsrl_group* g = u.g; fsrl_ctx* c0 = g->m[0];
+    const int k = u.k; hipStream_t s = g->stream;
+    const int C = c0->cfg.n_critics, H = c0->cfg.hidden, nn = c0->md.n_nets;
+    const bool layered = c0->lay != nullptr;
+    int rc = ogroup_begin(u, lagrangians, (size_t)(C - 1), rescaling, batch_size, false, true);
+    if (rc) return rc;
+    // ---- member table (wp.stats: per pass, the statistics table may be regrown)
     const int nparts = layered ? 0 : wg_grid(H, nn);
     for (int i = 0; i < k; ++i) {
         fsrl_ctx* c = g->m[i];
         GroupAgent& a = g->tab.h[i];
         if (layered) { lay_group_agent(c, a); continue; }
-        memset(&a, 0, sizeof(a));
-        a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G;
-        a.bp.obs_p = c->obs_p; a.bp.rd_p = c->rd_p; a.bp.A1 = c->A1; a.bp.A2 = c->A2; a.bp.D1 = c->D1; a.bp.D2 = c->D2;
-        a.bp.DO = c->DO; a.bp.statp = c->statp; a.bp.mbp_max = c->mbp_max; a.bp.ts = nullptr;
-        WgradPtrs& wp = a.wp;
-        wp.A1 = c->A1; wp.A2 = c->A2; wp.D1 = c->D1; wp.D2 = c->D2; wp.DO = c->DO; wp.X = c->obs_p; wp.grad = c->G;
-        wp.gsq_part = c->gsq_part; wp.ctrl = c->ctrl; wp.mbp_max = c->mbp_max; wp.P = c->P; wp.statp = c->statp;
-        wp.Pw = c->P; wp.M = c->M; wp.V = c->V;
-        a.gsq_part = c->gsq_part; a.ctrl = c->ctrl;
-        a.rescale = (float)c->rescaling;
-        for (int j = 0; j < FSRL_MAX_CRITICS; ++j) a.lam[j] = (float)c->lagr[j];
-        a.n_dev = c->n_dev; a.nparts = nparts;
+        group_agent_common(c, a);
+        a.bp = ppo_batch_ptrs(c); a.bp.ts = nullptr;
+        a.wp = ppo_wgrad_ptrs(c);
+        a.gsq_part = c->gsq_part; a.nparts = nparts;
     }
     PpoStepArgs base = ppo_base_args(c0);
-    std::vector<char> active((size_t)k, 1);
-    for (int i = 0; i < k; ++i) if (n[i] == 0) active[(size_t)i] = 0;
-    // minibatch steps of a pass = the longest plan among the members still ACTIVE in it (an empty member keeps a stale plan
-    // from an earlier update; a member that stopped on KL no longer counts): recomputed per pass
-    size_t cap_nmb = 0;
-    for (int i = 0; i < k; ++i) if (active[(size_t)i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
-    // grown to twice what this call needs, behind the stream's reads of the old tables
-    const size_t n_steps = std::max<size_t>(cap_nmb, 1) * k;
-    int rc = table_ensure(g->steps, n_steps, 2 * n_steps, g->stream);
-    if (rc) return abort_all(rc);
     if (layered) {                              // job tables of this update: the members' working sets are in place now
-        rc = lay_group_tables(g->lay, g->m.data(), k, active.data(), s);
-        if (rc) return abort_all(rc);
+        rc = lay_group_tables(g->lay, g->m.data(), k, u.active, s);
+        if (rc) return rc;
         base.fuse_adam = 0;                     // the layered step keeps the separate Adam launch (lay_ppo_steps)
     }
     for (int pass = 0; pass < repeat; ++pass) {
-        bool any = false;
-        for (int i = 0; i < k; ++i) any = any || active[(size_t)i];
-        if (!any) break;
-        size_t max_nmb = 0;
-        for (int i = 0; i < k; ++i) if (active[(size_t)i]) max_nmb = std::max(max_nmb, g->m[i]->mb_start.size());
-        // the pinned tables of the previous pass must have left host memory before they are rewritten
-        if (g->steps_in_flight) { HIPCHK(hipEventSynchronize(g->steps_copied)); g->steps_in_flight = false; }
-        // ---- per member: permutation + batch preparation of this pass; stats pointer (the table may have been regrown)
-        int max_mbsize = 0;
-        for (int i = 0; i < k; ++i) {
-            if (!active[(size_t)i]) continue;
-            fsrl_ctx* c = g->m[i];
-            rc = ppo_pass_prepare(c, perms ? perms[i] + (size_t)pass * (size_t)n[i] : nullptr, seed ? seed + 1000003ull * i + pass : 0);
-            if (rc) return abort_all(rc);
-            g->tab.h[i].wp.stats = c->d_stats;
-            for (int sz : c->mb_size) max_mbsize = std::max(max_mbsize, sz);
-        }
+        rc = ogroup_pass_begin(u, pass, [&](int i, fsrl_ctx* c) { g->tab.h[i].wp.stats = c->d_stats; return 0; });
+        if (rc) return rc;
+        if (u.n_act == 0) break;
+        const size_t max_nmb = u.max_nmb;
         HIPCHK(hipMemcpyAsync(g->tab.d, g->tab.h, (size_t)k * sizeof(GroupAgent), hipMemcpyHostToDevice, s));
         // ---- step table of the pass
         for (size_t mb = 0; mb < max_nmb; ++mb) {
@@ -223,7 +251,7 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
                 GroupStep& st = g->steps.h[mb * k + i];
                 memset(&st, 0, sizeof(st));
                 const size_t nmb = c->mb_start.size();
-                if (!active[(size_t)i] || mb >= nmb) continue;
+                if (!u.active[i] || mb >= nmb) continue;
                 st.active = 1;
                 st.mb_start = c->mb_start[mb]; st.mb_size = c->mb_size[mb]; st.mb_index = (int)mb;
                 st.step = (int)c->n_steps + (int)mb;
@@ -234,44 +262,28 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
             }
         }
         HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, max_nmb * k * sizeof(GroupStep), hipMemcpyHostToDevice, s));
-        HIPCHK(hipEventRecord(g->steps_copied, s));
+        HIPCHK(hipEventRecord(g->steps_copied, s));              // ogroup_pass_begin waits for it before the tables are rewritten
         g->steps_in_flight = true;
-        // ---- the minibatch steps: 3 (2 without a clip) launches for all members
-        int n_act = 0;
-        for (int i = 0; i < k; ++i) n_act += active[(size_t)i] ? 1 : 0;
-        (void)max_mbsize;
+        // ---- the minibatch steps
         for (size_t mb = 0; mb < max_nmb; ++mb) {
             const GroupStep* st = g->steps.d + mb * k;
             int mbs = 0;                                         // the largest minibatch any member has at this step
             for (int i = 0; i < k; ++i) mbs = std::max(mbs, g->steps.h[mb * k + i].active ? g->steps.h[mb * k + i].mb_size : 0);
             if (mbs == 0) continue;                              // no active member has a minibatch at this index: nothing to launch
-            if (layered) {                                       // 2 L + 5 launches for all members (host_layered_group.inc)
+            if (layered) {
                 rc = lay_group_step(g->lay, g->m.data(), k, s, g->tab.d, st, g->steps.h + mb * k, base);
-                if (rc) return abort_all(rc);
+                if (rc) return rc;
                 continue;
             }
             const int tiles = (mbs + 15) / 16;
-            // 4-row tiles only while the whole group still fits the chip in one round (a lone member: the single-agent rule)
-            const bool rows4 = (size_t)tiles * 4 * nn * n_act <= (size_t)c0->n_cus && !c0->probe_tile16;
-            const bool rows8 = !rows4 && (size_t)tiles * 2 * nn * n_act <= (size_t)c0->n_cus && !c0->probe_tile16;   // as in fsrl_ppo_pass
-            // tall tiles (r6 late): once the 16-row tiles need a second round of workgroups, every (member, network) runs 32-row tiles (a
-            // trailing odd 16-row group keeps a 16-row tile): 8 members x 3 networks x 256 rows = 192 workgroups instead of 384, half the
-            // L2 -> register weight ingest per row.  Same-box alternations (tools/bench_group.py --tall): k = 8 245 -> 283 updates/s aggregate,
-            // k = 6 207 -> 252, k = 12 260 -> 270, k = 16 309 -> 309; groups whose 16-row tiles fit one round LOSE with tall tiles (k = 4
-            // 245 -> 200, k = 5 266 -> 232) and keep them.  A mix sized to exactly one round (6 of 32 + 4 of 16 rows per pair at k = 8) was
-            // slower than either (228-240) and 7 + 2 differed by box (288 / 222): not used.  g->tall_tiles: -1 automatic, 0 none, n > 0
-            // exactly min(n, tiles / 2) leading tiles.
-            int n32 = 0;
-            if (!rows4 && !rows8 && H >= 128 && c0->md.Do <= TileSmem<256, 32>::XK && !c0->probe_tile16) {
-                if (g->tall_tiles < 0) n32 = tiles * nn * n_act > c0->n_cus ? tiles / 2 : 0;
-                else n32 = std::min(tiles / 2, g->tall_tiles);
-            }
-            const int per_net = tiles - n32;
+            // fsrl_ppo_pass's rule over the whole launch: a lone member gets its solo tiles
+            const PpoTilePlan tp = ppo_tile_plan(c0, tiles, nn, u.n_act, g->tall_tiles);
+            const int n32 = tp.n32, per_net = tiles - n32;
             const bool big = tiles * 16 > 256;                  // up to 256 rows: bursts of 4 k-steps, two workgroups per CU; above: the chunked 512-row form
             rc = dispatch_H(H, [&](auto hc) {
                 constexpr int HH = decltype(hc)::value;
-                if (rows4) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 4>), dim3(tiles * 4 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
-                else if (rows8) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 8>), dim3(tiles * 2 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
+                if (tp.rows4) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 4>), dim3(tiles * 4 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
+                else if (tp.rows8) hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 8>), dim3(tiles * 2 * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
                 else if (n32 > 0) {
                     if constexpr (HH >= 128)
                         hipLaunchKernelGGL((ppo_fwd_bwd_group_mix_kernel<HH>), dim3(per_net * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base,
@@ -279,8 +291,8 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
                 } else hipLaunchKernelGGL((ppo_fwd_bwd_group_kernel<HH, 16>), dim3(tiles * nn, k), dim3(4 * HH), 0, s, c0->md, g->tab.d, st, base);
 #define FSRL_WG(BIGV, FUSEV)                                                                                                      \
     do {                                                                                                                          \
-        if (rows4) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 4>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
-        else if (rows8) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 8>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
+        if (tp.rows4) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 4>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
+        else if (tp.rows8) hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 8>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base); \
         else hipLaunchKernelGGL((ppo_wgrad_group_kernel<HH, BIGV, FUSEV, 16>), dim3(nparts, k), dim3(1024), 0, s, c0->md, g->tab.d, st, base);      \
     } while (0)
                 if (base.fuse_adam) { if (big) FSRL_WG(true, true); else FSRL_WG(false, true); }
@@ -288,36 +300,31 @@ extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, c
 #undef FSRL_WG
                 return 0;
             });
-            if (rc) return abort_all(rc);
+            if (rc) return rc;
             if (!base.fuse_adam)
                 hipLaunchKernelGGL(adam_clip_group_kernel, dim3((c0->n_dev + 4 * ADAM_NT - 1) / (4 * ADAM_NT), k), dim3(ADAM_NT), 0, s,
                                    c0->md, g->tab.d, st, base);
             HIPCHK(hipGetLastError());
         }
-        for (int i = 0; i < k; ++i) {
-            if (!active[(size_t)i]) continue;
-            fsrl_ctx* c = g->m[i];
-            const int64_t nmb = (int64_t)c->mb_start.size();
-            c->n_steps += nmb; c->adam_t += nmb; c->pass_index += 1;
-        }
-        // ---- pass-level KL early stop, per member (the reference's `break`): one readback per pass for the group
-        if (c0->cfg.target_kl > 0.0f) {
-            for (int i = 0; i < k; ++i)
-                if (active[(size_t)i])
-                    HIPCHK(hipMemcpyAsync(g->m[i]->h_ctrl, g->m[i]->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            for (int i = 0; i < k; ++i) {
-                if (active[(size_t)i] && g->m[i]->h_ctrl->stopped_after != INT_MAX) {
-                    active[(size_t)i] = 0;
-                    if (stopped_pass_out) stopped_pass_out[i] = pass;
-                }
-            }
-        }
-    }
-    // ---- end: statistics of every member
-    for (int i = 0; i < k; ++i) {
-        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, cap_steps, n_steps_out ? n_steps_out + i : nullptr);
-        if (rc) return abort_all(rc);
+        rc = ogroup_pass_end(u, pass, true, c0->cfg.target_kl > 0.0f);
+        if (rc) return rc;
     }
     return 0;
+}
+
+// lagrangians: [k][n_critics - 1]; rescaling: [k]; perms: NULL (library shuffles) or k pointers, member i's = [repeat][n_i];
+// stats_out: k pointers or NULL.  A FOCOPS group: k x Engine.focops_update (lagrangians / rescaling ignored).
+extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, const double* rescaling, int32_t batch_size,
+                                     int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
+                                     int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
+    CHECK_ARG(g, "null argument");
+    CHECK_ARG(repeat >= 0, "repeat must be >= 0");
+    if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
+    GroupUpdate u{g, (int)g->m.size(), perms, seed, stopped_pass_out};
+    int rc = g->m[0]->cfg.algo == FSRL_ALGO_FOCOPS ? focops_group_update(u, batch_size, repeat)
+                                                   : ppo_group_update(u, lagrangians, rescaling, batch_size, repeat);
+    for (int i = 0; i < u.k && !rc; ++i)        // end: statistics of every member
+        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, cap_steps, n_steps_out ? n_steps_out + i : nullptr);
+    if (rc && u.begun) for (fsrl_ctx* c : g->m) c->in_update = false;
+    return rc;
 }

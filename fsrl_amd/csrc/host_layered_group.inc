@@ -158,14 +158,10 @@ static int lay_group_tables(LayGroup& lg, fsrl_ctx* const* m, int k, const char*
 // member i's row of the member table: what ppo_stats_group_kernel / adam_clip_group_kernel / the obs operands read
 static void lay_group_agent(fsrl_ctx* c, GroupAgent& a) {
     LayState* ls = c->lay;
-    memset(&a, 0, sizeof(a));
-    a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G;
+    group_agent_common(c, a);
     a.bp.obs_p = c->obs_p; a.bp.rd_p = c->rd_p; a.bp.statp = c->statp; a.bp.mbp_max = ls->mbp;
     a.wp.statp = c->statp; a.wp.ctrl = c->ctrl; a.wp.P = c->P; a.wp.grad = c->G; a.wp.mbp_max = ls->mbp;
-    a.gsq_part = ls->gsq; a.ctrl = c->ctrl;
-    a.rescale = (float)c->rescaling;
-    for (int j = 0; j < FSRL_MAX_CRITICS; ++j) a.lam[j] = (float)c->lagr[j];
-    a.n_dev = c->n_dev; a.nparts = ls->nparts;
+    a.gsq_part = ls->gsq; a.nparts = ls->nparts;
 }
 
 template <int FORM>

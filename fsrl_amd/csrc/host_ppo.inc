@@ -273,6 +273,56 @@ static PpoStepArgs ppo_base_args(fsrl_ctx* c) {
     return sa;
 }
 
+// a context's pointer blocks of the fused minibatch step: fsrl_ppo_pass and the group's member table (host_group.inc).  wp.X is the
+// first row; wp.stats is the caller's to set after ppo_pass_prepare, which may regrow the statistics table
+static PpoBatchPtrs ppo_batch_ptrs(const fsrl_ctx* c) {
+    PpoBatchPtrs bp{};
+    bp.obs_p = c->obs_p; bp.rd_p = c->rd_p; bp.A1 = c->A1; bp.A2 = c->A2; bp.D1 = c->D1; bp.D2 = c->D2;
+    bp.DO = c->DO; bp.statp = c->statp; bp.mbp_max = c->mbp_max;
+    bp.ts = c->probe_ts;                 // null outside probe builds
+    return bp;
+}
+static WgradPtrs ppo_wgrad_ptrs(const fsrl_ctx* c) {
+    WgradPtrs wp{};
+    wp.A1 = c->A1; wp.A2 = c->A2; wp.D1 = c->D1; wp.D2 = c->D2; wp.DO = c->DO; wp.X = c->obs_p; wp.grad = c->G;
+    wp.gsq_part = c->gsq_part; wp.ctrl = c->ctrl; wp.mbp_max = c->mbp_max; wp.P = c->P; wp.statp = c->statp;
+    wp.Pw = c->P; wp.M = c->M; wp.V = c->V;
+    return wp;
+}
+// a member's row of a group's member table, zeroed, with what fused (host_group.inc) and layered (host_layered_group.inc) members
+// have in common
+static void group_agent_common(const fsrl_ctx* c, GroupAgent& a) {
+    memset(&a, 0, sizeof(a));
+    a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G; a.ctrl = c->ctrl; a.n_dev = c->n_dev;
+    a.rescale = (float)c->rescaling;
+    for (int j = 0; j < FSRL_MAX_CRITICS; ++j) a.lam[j] = (float)c->lagr[j];
+}
+
+// Tile height of the fused step's forward / backward launch: `tiles` 16-row tiles per network, nn networks, n_act members in the launch
+// (fsrl_ppo_pass: 1, the group: the members active in the pass).
+//   rows4: 4-row tiles (4x4x1 MFMA) while the launch still fits the chip in one round: four times the CUs, a quarter of the MFMA time each
+//   rows8: 8-row tiles (two 4x4x1 passes on one fragment ingest) when the 4-row grid is more than one round but the 8-row grid is not:
+//          batch 512 ran 96 sixteen-row workgroups on a 256-CU chip
+//   n32:   tall tiles (r6 late): once the 16-row tiles need a second round of workgroups (a lone context: minibatches above ~1 360 rows
+//          with three networks) every (member, network) runs 32-row tiles (a trailing odd 16-row group keeps a 16-row tile): 8 members x
+//          3 networks x 256 rows = 192 workgroups instead of 384, half the L2 -> register weight ingest per row.  Same-box alternations
+//          (tools/bench_group.py --tall): k = 8 245 -> 283 updates/s aggregate, k = 6 207 -> 252, k = 12 260 -> 270, k = 16 309 -> 309;
+//          groups whose 16-row tiles fit one round LOSE with tall tiles (k = 4 245 -> 200, k = 5 266 -> 232) and keep them.  A mix sized
+//          to exactly one round (6 of 32 + 4 of 16 rows per pair at k = 8) was slower than either (228-240) and 7 + 2 differed by box
+//          (288 / 222): not used.  tall_tiles (fsrl_ppo_set_plan / fsrl_group_set_plan): -1 automatic, 0 none, n > 0 exactly
+//          min(n, tiles / 2) leading tiles.  Same bits either way.
+struct PpoTilePlan { bool rows4, rows8; int n32; };
+static PpoTilePlan ppo_tile_plan(const fsrl_ctx* c0, int tiles, int nn, int n_act, int tall_tiles) {
+    PpoTilePlan p{false, false, 0};
+    if (c0->probe_tile16) return p;
+    const size_t per16 = (size_t)tiles * nn * n_act, n_cus = (size_t)c0->n_cus;
+    p.rows4 = per16 * 4 <= n_cus;
+    p.rows8 = !p.rows4 && per16 * 2 <= n_cus;
+    if (!p.rows4 && !p.rows8 && c0->cfg.hidden >= 128 && c0->md.Do <= TileSmem<256, 32>::XK)
+        p.n32 = tall_tiles < 0 ? (per16 > n_cus ? tiles / 2 : 0) : std::min(tiles / 2, tall_tiles);
+    return p;
+}
+
 extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, int32_t* stopped_out) {
     CHECK_ARG(c, "null ctx");
     if (!c->in_update || !c->batch_ready) return fail(FSRL_ESTATE, "fsrl_ppo_pass before fsrl_ppo_begin");
@@ -295,15 +345,9 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
         if (c->cfg.target_kl > 0.0f) return pass_verdict(c, stopped_out);
         return 0;
     }
-    PpoBatchPtrs bp{};
-    bp.obs_p = c->obs_p; bp.rd_p = c->rd_p; bp.A1 = c->A1; bp.A2 = c->A2; bp.D1 = c->D1; bp.D2 = c->D2;
-    bp.DO = c->DO; bp.statp = c->statp; bp.mbp_max = c->mbp_max;
-    bp.ts = c->probe_ts;                 // null outside probe builds
-    WgradPtrs wp{};
-    wp.A1 = c->A1; wp.A2 = c->A2; wp.D1 = c->D1; wp.D2 = c->D2; wp.DO = c->DO; wp.X = c->obs_p; wp.grad = c->G;
-    wp.gsq_part = c->gsq_part; wp.ctrl = c->ctrl; wp.mbp_max = c->mbp_max;
-    wp.P = c->P; wp.statp = c->statp; wp.stats = c->d_stats;
-    wp.Pw = c->P; wp.M = c->M; wp.V = c->V;
+    const PpoBatchPtrs bp = ppo_batch_ptrs(c);
+    WgradPtrs wp = ppo_wgrad_ptrs(c);
+    wp.stats = c->d_stats;
     const int nparts = wg_grid(H, nn);   // tiles + aux parts of every network, + one extra block per network, + the logged-row block
 
     PpoStepArgs sa = ppo_base_args(c);
@@ -325,28 +369,15 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
             }
             HIPCHK(hipEventRecord(c->k_ev[c->k_ev_used], s));
         }
-        // 4-row tiles (4x4x1 MFMA) when they still fit the chip in one round: four times the CUs,
-        // a quarter of the MFMA time each; 16-row tiles otherwise
-        const bool rows4 = tiles * 4 * nn <= c->n_cus && !c->probe_tile16;
-        // 8-row tiles (two 4x4x1 passes on one fragment ingest) when the 4-row grid is more than one round but the 8-row grid is
-        // not: batch 512 ran 96 sixteen-row workgroups on a 256-CU chip
-        const bool rows8 = !rows4 && tiles * 2 * nn <= c->n_cus && !c->probe_tile16;
-        const int stat_tiles = rows4 ? tiles * 4 : rows8 ? tiles * 2 : tiles;
-        // tall tiles (r6 late, as the grouped launches): once the 16-row tiles need a second round of workgroups (minibatches above ~1 360
-        // rows with three networks) every network runs 32-row tiles (a trailing odd 16-row group keeps a 16-row tile); c->tall_tiles
-        // (fsrl_ppo_set_plan): -1 automatic, 0 none, n > 0 exactly min(n, tiles / 2) leading tiles.  Same bits either way.
-        int n32 = 0;
-        if (!rows4 && !rows8 && H >= 128 && c->md.Do <= TileSmem<256, 32>::XK && !c->probe_tile16) {
-            if (c->tall_tiles < 0) n32 = tiles * nn > c->n_cus ? tiles / 2 : 0;
-            else n32 = std::min(tiles / 2, c->tall_tiles);
-        }
+        const PpoTilePlan tp = ppo_tile_plan(c, tiles, nn, 1, c->tall_tiles);
+        const int n32 = tp.n32, stat_tiles = tp.rows4 ? tiles * 4 : tp.rows8 ? tiles * 2 : tiles;
         rc = dispatch_H(H, [&](auto hc) {
             constexpr int HH = decltype(hc)::value;
             // one network per XCD pair (see ppo_fwd_bwd_body): grid = 8 x ceil(tiles / 2), the blocks of XCD pairs beyond the networks exit
             sa.xcd_pair = (nn <= 4 && !c->no_xcd_pair) ? 1 : 0;
             auto fb_grid = [&](int nt) { return sa.xcd_pair ? dim3(8 * ((nt + 1) / 2)) : dim3(nt * nn); };
-            if (rows4) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 4>), fb_grid(tiles * 4), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
-            else if (rows8) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 8>), fb_grid(tiles * 2), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
+            if (tp.rows4) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 4>), fb_grid(tiles * 4), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
+            else if (tp.rows8) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 8>), fb_grid(tiles * 2), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
             else if (n32 > 0) {
                 if constexpr (HH >= 128)
                     hipLaunchKernelGGL((ppo_fwd_bwd_tall_kernel<HH>), dim3((tiles - n32) * nn), dim3(4 * HH), 0, s, c->P, c->md, bp, sa, n32, tiles - n32);
