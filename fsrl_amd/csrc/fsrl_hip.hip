@@ -13,7 +13,6 @@
 #include <cstring>
 #include <algorithm>
 #include <functional>
-#include <queue>
 #include <string>
 #include <vector>
 
@@ -26,6 +25,7 @@
 #include "kernels_layered.hpp"
 #include "kernels_focops_group.hpp"
 #include "resident_ring.hpp"
+#include "host_decisions.hpp"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1209,13 +1209,6 @@ extern "C" int fsrl_actor_forward(fsrl_ctx* c, const float* obs, int32_t k, floa
     int rc = actor_eval_launch(c, obs, k, sigma_out != nullptr);
     if (rc) return rc;
     return actor_eval_finish(c, mu_out, sigma_out);
-}
-
-static inline uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-static uint64_t xoshiro_next(uint64_t* s) {
-    const uint64_t result = rotl64(s[1] * 5, 7) * 9, t = s[1] << 17;
-    s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = rotl64(s[3], 45);
-    return result;
 }
 
 // Collector-time action sampling (fsrl/data/fast_collector.py:283-300: policy.forward -> dist.sample()):

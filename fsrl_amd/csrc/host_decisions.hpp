@@ -1,0 +1,160 @@
+// host_decisions.hpp -- what the update paths DECIDE on the host between their launches: CPO's dual solve, the two line searches'
+// acceptance rules and step schedules, the minibatch split, the permutation check / shuffle, the tile-split dispatch simulation.
+// Standard library only (no HIP), so tests/host/trust_host_sim.cpp drives it as a plain program (tests/test_trust_host.py).
+#pragma once
+#include <stdint.h>
+#include <algorithm>
+#include <cmath>
+#include <functional>
+#include <queue>
+#include <vector>
+
+// ---- CPO's dual problem (cpo.py:256-304), float32 like the reference.  q = g.H^-1 g, r = g.H^-1 b, s = b.H^-1 b, bb = b.b.
+static constexpr float CPO_EPS = 1e-8f;
+// case 4: no cost gradient and inside the limit -- the caller skips the second conjugate-gradient solve (H^-1 b := 0, r = s = 0)
+static inline bool cpo_cost_solve_skipped(float bb, float c_value) { return bb <= CPO_EPS && c_value < 0; }
+struct CpoDual { int ocase; float A, B, lam, nu; };
+static inline CpoDual cpo_dual_solve(float s_q, float s_r, float s_s, float c_value, float delta, float bb) {
+    const float EPS = CPO_EPS;
+    float A = 0.f, B = 0.f, lam, nu;
+    int ocase = 4;
+    if (!cpo_cost_solve_skipped(bb, c_value)) {
+        A = s_q - s_r * s_r / s_s;
+        B = 2.0f * delta - c_value * c_value / s_s;
+        if (c_value < 0 && B < 0) ocase = 3;
+        else if (c_value < 0 && B >= 0) ocase = 2;
+        else if (c_value >= 0 && B >= 0) ocase = 1;
+        else ocase = 0;
+    }
+    if (ocase == 3 || ocase == 4) {
+        lam = std::sqrt(s_q / (2.0f * delta));
+        nu = 0.0f;
+    } else if (ocase == 1 || ocase == 2) {
+        const float rc_ = s_r / c_value, inf = INFINITY;
+        float LA[2] = {0.0f, rc_}, LB[2] = {rc_, inf};
+        if (!(c_value < 0)) { std::swap(LA[0], LB[0]); std::swap(LA[1], LB[1]); }
+        auto proj = [](float x, const float* L) { return std::max(L[0], std::min(L[1], x)); };
+        const float lam_a = proj(std::sqrt(A / B), LA), lam_b = proj(std::sqrt(s_q / (2.0f * delta)), LB);
+        auto f_a = [&](float l) { return -0.5f * (A / (l + EPS) + B * l) - s_r * c_value / (s_s + EPS); };
+        auto f_b = [&](float l) { return -0.5f * (s_q / (l + EPS) + 2.0f * delta * l); };
+        lam = (f_a(lam_a) >= f_b(lam_b)) ? lam_a : lam_b;
+        nu = std::max(0.0f, lam * c_value - s_r) / (s_s + EPS);
+    } else {
+        nu = std::sqrt(2.0f * delta / (s_s + EPS));
+        lam = 0.0f;
+    }
+    return {ocase, A, B, lam, nu};
+}
+
+// ---- line searches.  `try_step(step)` moves theta to theta0 + step * dir, evaluates and says whether the step is accepted.
+// CPO (cpo.py:306-333): cases 0 and 1 (recovery) ignore the objective; the cost may rise by the room left under the limit.
+// TRPO-Lagrangian (trpo_lag.py:211-227): inside the trust region, strictly, and the loss must fall.
+static inline bool cpo_accepts(float new_kl, float new_obj, float new_cs, float delta, int ocase, float objective, float cost_sur,
+                               float c_value) {
+    return ((double)new_kl <= (double)delta) && (ocase > 1 ? new_obj > objective : true) &&
+           ((double)(new_cs - cost_sur) <= std::max(-(double)c_value, 0.0));
+}
+static inline bool trpo_accepts(float kl, float delta, float loss_new, float loss_actor) {
+    return (double)kl < (double)delta && loss_new < loss_actor;
+}
+// CPO's schedule, in float64 like the reference's: beta shrinks after EVERY refusal (a total failure logs coeff^max_backtracks);
+// a NaN multiplier tries nothing
+struct CpoSearch { double beta; int evals; };
+template <class Try>
+static CpoSearch cpo_line_search(float lam, double coeff, int max_backtracks, Try&& try_step) {
+    CpoSearch r{1.0, 0};
+    if (std::isnan(lam)) return r;
+    for (int bt = 0; bt < max_backtracks; ++bt) {
+        ++r.evals;
+        if (try_step(r.beta)) break;
+        r.beta *= coeff;
+    }
+    return r;
+}
+// TRPO-Lagrangian's: the step shrinks after a refusal except the last, where it is logged as 0 (the last tried theta stays)
+struct TrpoSearch { float step; int evals; };
+template <class Try>
+static TrpoSearch trpo_line_search(float step, float coeff, int max_backtracks, Try&& try_step) {
+    TrpoSearch r{step, 0};
+    for (int i = 0; i < max_backtracks; ++i) {
+        ++r.evals;
+        if (try_step(r.step)) break;
+        else if (i < max_backtracks - 1) r.step *= coeff;
+        else r.step = 0.0f;
+    }
+    return r;
+}
+
+// ---- minibatches: tianshou Batch.split(size, merge_last=True): the remainder is merged into the last chunk
+static inline void split_plan(int n, int B, std::vector<int>& st, std::vector<int>& sz) {
+    st.clear(); sz.clear();
+    const bool merge = (n % B) > 0;
+    for (int i = 0; i < n; i += B) {
+        if (merge && i + 2 * B >= n) { st.push_back(i); sz.push_back(n - i); break; }
+        st.push_back(i); sz.push_back(std::min(B, n - i));
+    }
+}
+
+// ---- xoshiro256**: the library's random streams (action noise, its own minibatch shuffles)
+static inline uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
+static inline uint64_t xoshiro_next(uint64_t* s) {
+    const uint64_t result = rotl64(s[1] * 5, 7) * 9, t = s[1] << 17;
+    s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = rotl64(s[3], 45);
+    return result;
+}
+// out[0 .. n) := the caller's permutation after checking it, or (perm == NULL) a Fisher-Yates shuffle from `rng`, which a
+// non-zero seed perturbs first.  A refusal names the entry: perm[index] == value.
+enum { PERM_OK = 0, PERM_RANGE, PERM_TWICE };
+struct PermFill { int code, index; long long value; };
+static inline PermFill perm_fill(int* out, int n, const int64_t* perm, uint64_t* rng, uint64_t seed) {
+    if (perm) {
+        std::vector<uint8_t> seen((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            if (!(perm[i] >= 0 && perm[i] < n)) return {PERM_RANGE, i, (long long)perm[i]};
+            if (seen[(size_t)perm[i]]) return {PERM_TWICE, i, (long long)perm[i]};
+            seen[(size_t)perm[i]] = 1;
+            out[i] = (int)perm[i];
+        }
+        return {PERM_OK, 0, 0};
+    }
+    if (seed) { rng[0] ^= seed; rng[1] += seed * 0x9E3779B97F4A7C15ull; }
+    for (int i = 0; i < n; ++i) out[i] = i;
+    for (int i = n - 1; i > 0; --i) std::swap(out[i], out[(int)(xoshiro_next(rng) % (uint64_t)(i + 1))]);
+    return {PERM_OK, 0, 0};
+}
+
+// ---- Tile heights of one full-batch launch over N rows of ny networks on n_cus CUs (one workgroup per CU): n32 32-row tiles
+// first, n16 16-row tiles for the remaining rows.  A 32-row tile moves half the weight-fragment bytes per row but a partly filled
+// LAST round of them idles most of the chip for a whole tile time, so the split is chosen by simulating the dispatch (blocks in
+// launch order onto the earliest free CU) with rho = duration of a 16-row tile / a 32-row tile.  Ties go to the larger n32.
+struct TileSplit { int n32, n16; };
+static inline TileSplit mixed_split(int64_t N, int ny, int n_cus, double rho) {
+    const int max32 = (int)((N + 31) / 32);
+    double best = 1e300; int best32 = 0, best16 = (int)((N + 15) / 16);
+    std::vector<double> cu((size_t)std::max(n_cus, 1));
+    for (int n32 = 0; n32 <= max32; ++n32) {
+        const int64_t rem = N - 32 * (int64_t)n32;
+        const int n16 = rem > 0 ? (int)((rem + 15) / 16) : 0;
+        if (n16 > 0 && n32 == max32) continue;
+        std::fill(cu.begin(), cu.end(), 0.0);
+        std::priority_queue<double, std::vector<double>, std::greater<double>> pq(cu.begin(), cu.end());
+        double span = 0.0;
+        for (int b = 0; b < ny * n32; ++b) { const double e = pq.top() + 1.0; pq.pop(); pq.push(e); span = std::max(span, e); }
+        for (int b = 0; b < ny * n16; ++b) { const double e = pq.top() + rho; pq.pop(); pq.push(e); span = std::max(span, e); }
+        if (span < best - 1e-9 || (std::fabs(span - best) <= 1e-9 && n32 > best32)) { best = span; best32 = n32; best16 = n16; }
+    }
+    return {best32, best16};
+}
+// the persistent launches' tile mix: 32-row tiles while a whole round of workgroup pairs is left, then 16-row tiles so that the
+// CUs run dry together (the dispatch is dynamic: no simulation needed, only the size of the fine-grained tail)
+static inline void co_plan(int64_t N, int n_wgs, int* n32_out, int* n16_out) {
+    const int64_t tail_rows = std::min<int64_t>(N, 16 * (int64_t)(n_wgs / 2));      // half a round of 16-row tiles
+    const int n32 = (int)((N - tail_rows) / 32);
+    const int64_t rem = N - 32 * (int64_t)n32;
+    *n32_out = n32; *n16_out = (int)((rem + 15) / 16);
+}
+static inline void forced_split(int64_t N, int want32, int* n32_out, int* n16_out) {
+    const int n32 = (int)std::min<int64_t>(want32, N / 32);             // whole 32-row tiles only
+    const int64_t rem = N - 32 * (int64_t)n32;
+    *n32_out = n32; *n16_out = (int)((rem + 15) / 16);
+}

@@ -2,14 +2,20 @@
 // Included once by fsrl_hip.hip: same translation unit, so the static helpers and fsrl_ctx above are visible.
 // ------------------------------------------------------------------------------ PPO-Lagrangian
 static int launch_gae(fsrl_ctx* c);
-static void split_plan(int n, int B, std::vector<int>& st, std::vector<int>& sz) {
-    // tianshou Batch.split(size, merge_last=True): the remainder is merged into the last chunk
-    st.clear(); sz.clear();
-    const bool merge = (n % B) > 0;
-    for (int i = 0; i < n; i += B) {
-        if (merge && i + 2 * B >= n) { st.push_back(i); sz.push_back(n - i); break; }
-        st.push_back(i); sz.push_back(std::min(B, n - i));
-    }
+// This pass's / repeat's permutation to the device: np.random.permutation on the caller's side, checked, or the library's own
+// shuffle (perm_fill).  Built in pageable memory first: the GPU keeps working on the previous pass meanwhile.  Only the previous
+// H2D copy out of the pinned buffer has to be over (an event, not a stream drain).
+static int perm_upload(fsrl_ctx* c, int n, const int64_t* perm, uint64_t seed) {
+    c->perm_tmp.resize((size_t)n);
+    const PermFill pf = perm_fill(c->perm_tmp.data(), n, perm, c->shuffle_rng, seed);
+    CHECK_ARG(pf.code != PERM_RANGE, "perm[%d]=%lld out of range", pf.index, pf.value);
+    CHECK_ARG(pf.code != PERM_TWICE, "perm is not a permutation: %lld appears twice", pf.value);
+    if (c->perm_in_flight) { HIPCHK(hipEventSynchronize(c->perm_copied)); c->perm_in_flight = false; }
+    memcpy(c->h_perm, c->perm_tmp.data(), (size_t)n * 4);
+    HIPCHK(hipMemcpyAsync(c->d_perm, c->h_perm, (size_t)n * 4, hipMemcpyHostToDevice, c->compute));
+    HIPCHK(hipEventRecord(c->perm_copied, c->compute));
+    c->perm_in_flight = true;
+    return 0;
 }
 
 static int ensure_ppo_buffers(fsrl_ctx* c, int B) {
@@ -201,34 +207,11 @@ static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed) {
         int rc0 = ppo_recompute_advantages(c);
         if (rc0) return rc0;
     }
-    // ---- permutation of this pass (np.random.permutation on the caller side, or our own), built in
-    //      pageable memory first: the GPU keeps working on the previous pass meanwhile.  Only the previous
-    //      H2D copy out of the pinned buffer has to be over (an event, not a stream drain).
-    c->perm_tmp.resize((size_t)n);
-    if (perm) {
-        std::vector<uint8_t> seen((size_t)n, 0);
-        for (int i = 0; i < n; ++i) {
-            CHECK_ARG(perm[i] >= 0 && perm[i] < n, "perm[%d]=%lld out of range", i, (long long)perm[i]);
-            CHECK_ARG(!seen[(size_t)perm[i]], "perm is not a permutation: %lld appears twice", (long long)perm[i]);
-            seen[(size_t)perm[i]] = 1;
-            c->perm_tmp[(size_t)i] = (int)perm[i];
-        }
-    } else {
-        if (seed) { c->shuffle_rng[0] ^= seed; c->shuffle_rng[1] += seed * 0x9E3779B97F4A7C15ull; }
-        for (int i = 0; i < n; ++i) c->perm_tmp[(size_t)i] = i;
-        for (int i = n - 1; i > 0; --i) {
-            const int j = (int)(xoshiro_next(c->shuffle_rng) % (uint64_t)(i + 1));
-            std::swap(c->perm_tmp[(size_t)i], c->perm_tmp[(size_t)j]);
-        }
-    }
-    if (c->perm_in_flight) { HIPCHK(hipEventSynchronize(c->perm_copied)); c->perm_in_flight = false; }
-    memcpy(c->h_perm, c->perm_tmp.data(), (size_t)n * 4);
-    const int nmb = (int)c->mb_start.size();
-    int rc = ensure_stats(c, c->n_steps + nmb);
+    int rc = perm_upload(c, n, perm, seed);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_perm, c->h_perm, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(c->perm_copied, s));
-    c->perm_in_flight = true;
+    const int nmb = (int)c->mb_start.size();
+    rc = ensure_stats(c, c->n_steps + nmb);
+    if (rc) return rc;
     {
         PrepArgs pa{};
         pa.obs = c->b.obs; pa.act = c->b.act; pa.advs = c->advs; pa.rets = c->rets; pa.logp_old = c->logp_old;

@@ -57,11 +57,11 @@ struct TrState {
     int na = 0;               // flat actor parameter count (API order)
     std::vector<int32_t> ls_iters;   // line-search evaluations of every repeat of the last learn call
 };
+static int actor_tensors(const fsrl_ctx* c) { return c->lay ? 1 + 2 * (c->lay->L + 1) : 7; }     // sigma_param + (W, b) of every Linear
 static TrState* tr_of(fsrl_ctx* c) {
     if (!c->tr) {
         c->tr = new TrState();
-        const int nt = c->lay ? 1 + 2 * (c->lay->L + 1) : 7;       // the actor's tensors: sigma_param + (W, b) of every Linear
-        for (int i = 0; i < nt; ++i) c->tr->na += c->tmap[i].n();
+        c->tr->na = (int)fsrl_actor_param_count(c);
     }
     return c->tr;
 }
@@ -73,25 +73,15 @@ static void tr_set_critic_steps(fsrl_ctx* c, int64_t t) { if (c->tr) { c->tr->cr
 static void tr_free(fsrl_ctx* c) {
     TrState* t = c->tr;
     if (!t) return;
-    for (float* p : {t->A1, t->A2, t->D1, t->D2, t->DO, t->RA1, t->RA2, t->RD1, t->RD2, t->RDO, t->statp,
-                     t->mu_old, t->Vdev, t->Out, t->rd, t->cg_r, t->cg_x, t->cg_g, t->obs_pad})
-        if (p) (void)hipFree(p);
-    if (t->vec) (void)hipFree(t->vec);
-    if (t->h_part) (void)hipHostFree(t->h_part);
-    if (t->h_rb) (void)hipHostFree(t->h_rb);
-    if (t->h_rb_done) (void)hipHostFree(t->h_rb_done);
-    if (t->cg_sc) (void)hipFree(t->cg_sc);
-    if (t->co_counter) (void)hipFree(t->co_counter);
     if (t->cstream) { (void)hipStreamSynchronize(t->cstream); (void)hipStreamDestroy(t->cstream); }
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
-    for (float* p : {t->cA1, t->cA2, t->cD1, t->cD2, t->cDO, t->cstatp, t->c_parts.p})
+    for (void* p : std::initializer_list<void*>{t->A1, t->A2, t->D1, t->D2, t->DO, t->RA1, t->RA2, t->RD1, t->RD2, t->RDO, t->statp,
+                     t->mu_old, t->Vdev, t->Out, t->rd, t->cg_r, t->cg_x, t->cg_g, t->obs_pad, t->vec, t->cg_sc, t->co_counter,
+                     t->cA1, t->cA2, t->cD1, t->cD2, t->cDO, t->cstatp, t->c_parts.p, t->c_d_scal, t->c_d_ssq, t->cg_part,
+                     t->d_scal, t->d_ssq})
         if (p) (void)hipFree(p);
-    if (t->c_d_scal) (void)hipFree(t->c_d_scal);
-    if (t->c_d_ssq) (void)hipFree(t->c_d_ssq);
-    if (t->h_crit) (void)hipHostFree(t->h_crit);
-    if (t->cg_part) (void)hipFree(t->cg_part);
-    if (t->d_scal) (void)hipFree(t->d_scal);
-    if (t->d_ssq) (void)hipFree(t->d_ssq);
+    for (void* p : std::initializer_list<void*>{t->h_part, t->h_rb, t->h_rb_done, t->h_crit})
+        if (p) (void)hipHostFree(p);
     delete t;
     c->tr = nullptr;
 }
@@ -99,8 +89,7 @@ static void tr_free(fsrl_ctx* c) {
 extern "C" int64_t fsrl_actor_param_count(const fsrl_ctx* c) {
     if (!c) return 0;
     int64_t n = 0;
-    const int nt = c->lay ? 1 + 2 * (c->lay->L + 1) : 7;      // sigma_param + (W, b) of every Linear of the actor
-    for (int i = 0; i < nt; ++i) n += c->tmap[i].n();
+    for (int i = 0; i < actor_tensors(c); ++i) n += c->tmap[i].n();
     return n;
 }
 
@@ -193,20 +182,15 @@ static int tr_alloc(fsrl_ctx* c, TrState* t, int64_t n) {
 // flat ACTOR vector (API order) <-> device-layout vector
 static int actor_to_dev(fsrl_ctx* c, const float* host, float* dev) {
     std::vector<float> tmp((size_t)c->md.net[0].end, 0.0f);
-    const int nt = c->lay ? 1 + 2 * (c->lay->L + 1) : 7;
-    for (int i = 0; i < nt; ++i) c->tmap[i].to_dev(tmp.data(), host);
-    if (c->lay) {               // no W2 mirror behind a layered parameter vector
-        HIPCHK(hipStreamSynchronize(c->compute));
-        HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
-        return 0;
-    }
+    for (int i = 0; i < actor_tensors(c); ++i) c->tmap[i].to_dev(tmp.data(), host);
+    HIPCHK(hipStreamSynchronize(c->compute));
+    HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
+    if (c->lay) return 0;       // no W2 mirror behind a layered parameter vector
     const int H = c->md.H;
     const NetOff& no = c->md.net[0];
     std::vector<float> mir((size_t)H * H);      // dev is P or a tangent vector: both carry the W2 mirror
     for (int n = 0; n < H; ++n)
         for (int k = 0; k < H; ++k) mir[(size_t)w2f_index(H, n, k)] = tmp[(size_t)no.W2 + (size_t)n * H + k];
-    HIPCHK(hipStreamSynchronize(c->compute));
-    HIPCHK(hipMemcpy(dev, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dev + no.W2f, mir.data(), mir.size() * 4, hipMemcpyHostToDevice));
     return 0;
 }
@@ -214,8 +198,7 @@ static int actor_from_dev(fsrl_ctx* c, const float* dev, float* host) {
     std::vector<float> tmp((size_t)c->md.net[0].end);
     HIPCHK(hipStreamSynchronize(c->compute));
     HIPCHK(hipMemcpy(tmp.data(), dev, tmp.size() * 4, hipMemcpyDeviceToHost));
-    const int nt = c->lay ? 1 + 2 * (c->lay->L + 1) : 7;
-    for (int i = 0; i < nt; ++i) c->tmap[i].to_api(host, tmp.data());
+    for (int i = 0; i < actor_tensors(c); ++i) c->tmap[i].to_api(host, tmp.data());
     return 0;
 }
 
@@ -301,49 +284,38 @@ static int rb_wait(fsrl_ctx* c, TrState* t, int n) {
     }
     return 0;
 }
-static int tr_stats(fsrl_ctx* c, TrState* t, int ny, double* out) {
-    if (t->opt_poll && t->h_rb && ny * FB_NSTAT <= CG_NB) {
-        const unsigned seq = rb_next(t);
-        hipLaunchKernelGGL(fb_reduce_stats_kernel, dim3(ny * FB_NSTAT), dim3(256), 0, c->compute, t->statp, t->n_tiles,
-                           ny, t->d_scal, t->h_rb, t->h_rb_done, seq);
-        HIPCHK(hipGetLastError());
-        int rc = rb_wait(c, t, ny * FB_NSTAT);
-        if (rc) return rc;
-        memcpy(out, t->h_rb, (size_t)ny * FB_NSTAT * sizeof(double));
-        return 0;
-    }
-    hipLaunchKernelGGL(fb_reduce_stats_kernel, dim3(ny * FB_NSTAT), dim3(256), 0, c->compute, t->statp, t->n_tiles,
-                       ny, t->d_scal);
+// One reducing launch of `blocks` blocks and its n doubles on the host.  `launch(hout, done, seq)` enqueues the kernel: with
+// polled completion words (the default) it writes its sums to h_rb as well and *got = h_rb; otherwise (null words) `dev` is copied
+// into `host` behind it, the stream is synchronised and *got = host.
+template <class Launch>
+static int tr_read_back(fsrl_ctx* c, TrState* t, int blocks, const double* dev, double* host, size_t n, const double** got, Launch&& launch) {
+    const bool poll = t->opt_poll && t->h_rb && blocks <= CG_NB;
+    launch(poll ? t->h_rb : nullptr, poll ? t->h_rb_done : nullptr, poll ? rb_next(t) : 0u);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, t->d_scal, (size_t)ny * FB_NSTAT * sizeof(double), hipMemcpyDeviceToHost, c->compute));
+    *got = poll ? t->h_rb : host;
+    if (poll) return rb_wait(c, t, blocks);
+    HIPCHK(hipMemcpyAsync(host, dev, n * sizeof(double), hipMemcpyDeviceToHost, c->compute));
     HIPCHK(hipStreamSynchronize(c->compute));
     return 0;
 }
+static int tr_stats(fsrl_ctx* c, TrState* t, int ny, double* out) {
+    const double* got = nullptr;
+    int rc = tr_read_back(c, t, ny * FB_NSTAT, t->d_scal, out, (size_t)ny * FB_NSTAT, &got, [&](double* hout, unsigned* done, unsigned seq) {
+        hipLaunchKernelGGL(fb_reduce_stats_kernel, dim3(ny * FB_NSTAT), dim3(256), 0, c->compute, t->statp, t->n_tiles, ny, t->d_scal,
+                           hout, done, seq);
+    });
+    if (rc) return rc;
+    if (got != out) memcpy(out, got, (size_t)ny * FB_NSTAT * sizeof(double));
+    return 0;
+}
 
-// Tile heights of one full-batch launch over N rows of ny networks on n_cus CUs (one 1024-thread workgroup per CU): n32
-// 32-row tiles first, n16 16-row tiles for the remaining rows.  A 32-row tile moves half the weight-fragment bytes per row
-// but a partly filled LAST round of them idles most of the chip for a whole tile time, so the split is chosen by simulating
-// the dispatch (blocks in launch order onto the earliest free CU) with rho = duration of a 16-row tile / a 32-row tile.
+// the simulated tile split (mixed_split, host_decisions.hpp) of a launch shape, computed once per (N, ny, kind)
 static void mixed_plan(TrState* t, int64_t N, int ny, int n_cus, int kind, double rho, int* n32_out, int* n16_out) {
     for (const TrState::Plan& p : t->plans)
         if (p.N == N && p.ny == ny && p.kind == kind) { *n32_out = p.n32; *n16_out = p.n16; return; }
-    const int max32 = (int)((N + 31) / 32);
-    double best = 1e300; int best32 = 0, best16 = (int)((N + 15) / 16);
-    std::vector<double> cu((size_t)std::max(n_cus, 1));
-    for (int n32 = 0; n32 <= max32; ++n32) {
-        const int64_t rem = N - 32 * (int64_t)n32;
-        const int n16 = rem > 0 ? (int)((rem + 15) / 16) : 0;
-        if (n16 > 0 && n32 == max32) continue;
-        std::fill(cu.begin(), cu.end(), 0.0);
-        // CUs take blocks in order; with two block durations the earliest-free CU is found by a running index per phase
-        std::priority_queue<double, std::vector<double>, std::greater<double>> pq(cu.begin(), cu.end());
-        double span = 0.0;
-        for (int b = 0; b < ny * n32; ++b) { const double e = pq.top() + 1.0; pq.pop(); pq.push(e); span = std::max(span, e); }
-        for (int b = 0; b < ny * n16; ++b) { const double e = pq.top() + rho; pq.pop(); pq.push(e); span = std::max(span, e); }
-        if (span < best - 1e-9 || (std::fabs(span - best) <= 1e-9 && n32 > best32)) { best = span; best32 = n32; best16 = n16; }
-    }
-    t->plans.push_back({N, ny, kind, best32, best16});
-    *n32_out = best32; *n16_out = best16;
+    const TileSplit sp = mixed_split(N, ny, n_cus, rho);
+    t->plans.push_back({N, ny, kind, sp.n32, sp.n16});
+    *n32_out = sp.n32; *n16_out = sp.n16;
 }
 // scheduling argument of a co-resident launch over `total` tiles on `grid` workgroups; advances the stream-ordered counter base
 static CoSched co_sched(TrState* t, int total, int grid, int n_cus, int delay) {
@@ -354,18 +326,11 @@ static CoSched co_sched(TrState* t, int total, int grid, int n_cus, int delay) {
     t->co_base += (unsigned)(total + grid);                           // every workgroup draws once more than it processes
     return cs;
 }
-// the persistent launches' tile mix: 32-row tiles while a whole round of workgroup pairs is left, then 16-row tiles so that the
-// CUs run dry together (the dispatch is dynamic: no simulation needed, only the size of the fine-grained tail)
-static void co_plan(int64_t N, int n_wgs, int* n32_out, int* n16_out) {
-    const int64_t tail_rows = std::min<int64_t>(N, 16 * (int64_t)(n_wgs / 2));      // half a round of 16-row tiles
-    const int n32 = (int)((N - tail_rows) / 32);
-    const int64_t rem = N - 32 * (int64_t)n32;
-    *n32_out = n32; *n16_out = (int)((rem + 15) / 16);
-}
-static void forced_split(int64_t N, int want32, int* n32_out, int* n16_out) {
-    const int n32 = (int)std::min<int64_t>(want32, N / 32);             // whole 32-row tiles only
-    const int64_t rem = N - 32 * (int64_t)n32;
-    *n32_out = n32; *n16_out = (int)((rem + 15) / 16);
+// tile split of a co-resident launch (two workgroups per CU): simulated, the persistent kernels' own, or forced (A/B)
+static void co_split(fsrl_ctx* c, TrState* t, int ny, int kind, double rho, int forced32, int* n32, int* n16) {
+    if (t->co_static) mixed_plan(t, t->vN, ny, 2 * c->n_cus, kind, rho, n32, n16);
+    else co_plan(t->vN, 2 * c->n_cus, n32, n16);
+    if (forced32 >= 0) forced_split(t->vN, forced32, n32, n16);
 }
 static constexpr double RHO_TILE = 0.62;   // fb_tile: 16-row / 32-row tile duration (profiles/r03_*)
 static constexpr double RHO_HVP = 0.62;    // HVP tiles
@@ -400,11 +365,7 @@ static int tr_tile(fsrl_ctx* c, TrState* t, int mode, int net0, int ny, float cr
         mixed_plan(t, t->vN, ny, c->n_cus, 0, RHO_TILE, &n32, &n16);
     // r5: the same tiles as TWO co-resident 512-thread workgroups per CU (kernels_fbco.hpp); tile_rows plan 32 keeps r4's kernel
     const bool co = c->cfg.hidden == 256 && c->cfg.obs_dim <= 64 && c->cfg.act_dim <= 4 && t->opt_tile_rows == 0;
-    if (co) {
-        if (t->co_static) mixed_plan(t, t->vN, ny, 2 * c->n_cus, 3, RHO_TILE_CO, &n32, &n16);
-        else co_plan(t->vN, 2 * c->n_cus, &n32, &n16);
-        if (t->split_tile >= 0) forced_split(t->vN, t->split_tile, &n32, &n16);
-    }
+    if (co) co_split(c, t, ny, 3, RHO_TILE_CO, t->split_tile, &n32, &n16);
     return dispatch_H(c->cfg.hidden, [&](auto hc) {
         constexpr int H = decltype(hc)::value;
         if constexpr (H == 256) {
@@ -432,62 +393,62 @@ static int tr_tile(fsrl_ctx* c, TrState* t, int mode, int net0, int ny, float cr
     });
 }
 
+// out := the sum of the nparts split-K partials in c->wg_parts over the parameters of networks net0 .. net0 + ny - 1
+static int tr_sum_parts(fsrl_ctx* c, TrState* t, int net0, int ny, float* out, int nparts) {
+    const int begin = c->md.net[net0].begin, end = c->md.net[net0 + ny - 1].end;
+    hipLaunchKernelGGL(fb_sum_parts_kernel, dim3((end - begin + 255) / 256), dim3(256), 0, c->compute, out, c->wg_parts,
+                       begin, end, nparts, c->n_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the observation operands of a weight-side launch over the current view (obs_pad brought up to date first)
+static int tr_wgrad_obs(fsrl_ctx* c, TrState* t, FbWgradArgs& wa) {
+    int rc = tr_ensure_pad(c, t);
+    if (rc) return rc;
+    wa.obs = t->vobs; wa.rows = t->rows16; wa.N = (int)t->vN;
+    wa.obs_pad = t->pad_valid ? t->obs_pad : nullptr; wa.obs_ko = t->pad_ko;
+    return 0;
+}
+
+// weight gradients from the side buffers: summed into `out`, or (parts_out) left as partials for the caller's next kernel to add up
 static int tr_wgrad_plain(fsrl_ctx* c, TrState* t, int net0, int ny, float* out, int* parts_out = nullptr) {
+    int nsplit = 1;
     if (c->lay) {               // one launch writes the finished gradient: handed on as a single "partial"
         int rc = lay_wgrad(c, t->vobs, (int)t->vN, net0, ny, c->lay->gvec, nullptr, false, true);
         if (rc) return rc;
         c->wg_parts = c->lay->gvec;
-        if (parts_out) { *parts_out = c->lay->gparts; return 0; }
-        const int begin = c->md.net[net0].begin, end = c->md.net[net0 + ny - 1].end;
-        hipLaunchKernelGGL(fb_sum_parts_kernel, dim3((end - begin + 255) / 256), dim3(256), 0, c->compute, out, c->wg_parts,
-                           begin, end, c->lay->gparts, c->n_dev);
-        HIPCHK(hipGetLastError());
-        return 0;
+        nsplit = c->lay->gparts;
+    } else {
+        FbWgradArgs wa{};
+        wgrad_fill_nets(wa, ny, net0, (size_t)c->cfg.hidden, (size_t)t->rows_pad, t->A1, t->A2, t->D1, t->D2, t->DO);
+        int rc = tr_wgrad_obs(c, t, wa);
+        if (rc) return rc;
+        rc = wgrad_launch<false>(c, c->md, wa, ny, c->n_dev, &nsplit);
+        if (rc) return rc;
     }
-    FbWgradArgs wa{};
-    wgrad_fill_nets(wa, ny, net0, (size_t)c->cfg.hidden, (size_t)t->rows_pad, t->A1, t->A2, t->D1, t->D2, t->DO);
-    wa.obs = t->vobs; wa.rows = t->rows16; wa.N = (int)t->vN;
-    int nsplit = 1;
-    int rc = tr_ensure_pad(c, t);
-    if (rc) return rc;
-    wa.obs_pad = t->pad_valid ? t->obs_pad : nullptr; wa.obs_ko = t->pad_ko;
-    rc = wgrad_launch<false>(c, c->md, wa, ny, c->n_dev, &nsplit);
-    if (rc) return rc;
     if (parts_out) { *parts_out = nsplit; return 0; }
-    const int begin = c->md.net[net0].begin, end = c->md.net[net0 + ny - 1].end;
-    hipLaunchKernelGGL(fb_sum_parts_kernel, dim3((end - begin + 255) / 256), dim3(256), 0, c->compute, out, c->wg_parts,
-                       begin, end, nsplit, c->n_dev);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return tr_sum_parts(c, t, net0, ny, out, nsplit);
 }
 
+// the 8 batch means of the actor's last tile launch
+static int tr_means(fsrl_ctx* c, TrState* t, double* means8) {
+    int rc = tr_stats(c, t, 1, means8);
+    if (rc) return rc;
+    for (int k = 0; k < FB_NSTAT; ++k) means8[k] /= (double)t->vN;
+    return 0;
+}
 // gradient of a scalar actor objective into a device vector (actor layout) and the 8 batch means
 static int tr_actor_grad_dev(fsrl_ctx* c, TrState* t, int mode, float cr, float cc, float* g_dev, double* means8) {
     int rc = tr_tile(c, t, mode, 0, 1, cr, cc);
     if (rc) return rc;
     rc = tr_wgrad_plain(c, t, 0, 1, g_dev);
     if (rc) return rc;
-    if (means8) {
-        rc = tr_stats(c, t, 1, means8);
-        if (rc) return rc;
-        for (int k = 0; k < FB_NSTAT; ++k) means8[k] /= (double)t->vN;
-    }
-    return 0;
-}
-// the same, returned as the flat ACTOR gradient in API order (fsrl_tr_grad)
-static int tr_actor_grad(fsrl_ctx* c, TrState* t, int mode, float cr, float cc, float* g_out, double* means8) {
-    int rc = tr_actor_grad_dev(c, t, mode, cr, cc, t->Out, means8);
-    if (rc) return rc;
-    return actor_from_dev(c, t->Out, g_out);
+    return means8 ? tr_means(c, t, means8) : 0;
 }
 
 static int tr_eval_means(fsrl_ctx* c, TrState* t, double* means8) {
     int rc = tr_tile(c, t, FB_MODE_EVAL, 0, 1, 0.f, 0.f);
-    if (rc) return rc;
-    rc = tr_stats(c, t, 1, means8);
-    if (rc) return rc;
-    for (int k = 0; k < FB_NSTAT; ++k) means8[k] /= (double)t->vN;
-    return 0;
+    return rc ? rc : tr_means(c, t, means8);
 }
 
 // H v for the tangent already in t->Vdev (main part + W2 mirror); result in t->Out (device).
@@ -503,10 +464,7 @@ static int tr_hvp_dev(fsrl_ctx* c, TrState* t, bool use_cache = false, int* part
         t->hvp_valid = true; t->hvp_version = c->theta_version; t->hvp_rd_version = t->rd_version;
         c->wg_parts = c->lay->gvec;
         if (parts_out) { *parts_out = c->lay->gparts; return 0; }
-        hipLaunchKernelGGL(fb_sum_parts_kernel, dim3((c->md.net[0].end - c->md.net[0].begin + 255) / 256), dim3(256), 0,
-                           c->compute, t->Out, c->wg_parts, c->md.net[0].begin, c->md.net[0].end, c->lay->gparts, c->n_dev);
-        HIPCHK(hipGetLastError());
-        return 0;
+        return tr_sum_parts(c, t, 0, 1, t->Out, c->lay->gparts);
     }
     HvpArgs ha{};
     ha.obs = t->vobs; ha.rd = t->vrd; ha.V = t->Vdev; ha.A1 = t->A1; ha.RA1 = t->RA1; ha.A2 = t->A2; ha.RA2 = t->RA2;
@@ -526,11 +484,7 @@ static int tr_hvp_dev(fsrl_ctx* c, TrState* t, bool use_cache = false, int* part
     // r6: the FIRST product of a solve (nothing cached yet) in the same form on the automatic plan: 262-357 -> 150-190 us per launch
     const bool co_first = !cached && mixed && use_cache && t->opt_hvp == 0 && t->co_static;
     const bool co = (cached || co_first) && c->cfg.hidden == 256 && t->opt_hvp != 3;
-    if (co) {
-        if (t->co_static) mixed_plan(t, t->vN, 1, 2 * c->n_cus, 2, RHO_HVP_CO, &n32, &n16);
-        else co_plan(t->vN, 2 * c->n_cus, &n32, &n16);
-        if (t->split_hvp >= 0) forced_split(t->vN, t->split_hvp, &n32, &n16);
-    }
+    if (co) co_split(c, t, 1, 2, RHO_HVP_CO, t->split_hvp, &n32, &n16);
     rc = dispatch_H(c->cfg.hidden, [&](auto hc) {
         constexpr int H = decltype(hc)::value;
         if constexpr (H == 256) {
@@ -568,11 +522,9 @@ static int tr_hvp_dev(fsrl_ctx* c, TrState* t, bool use_cache = false, int* part
     wn.w1_y = t->RD1;                                                             // R{dW1} = R{dz1}^T x
     wn.w3_xa = t->A2; wn.w3_ya = t->RDO; wn.w3_xb = t->RA2; wn.w3_yb = t->DO;     // R{dW3} = R{dout}^T h2 + dout^T R{h2}
     wn.b1_src = t->RD1; wn.b2_src = t->RD2; wn.do_src = t->RDO; wn.net = 0;
-    wa.obs = t->vobs; wa.rows = t->rows16; wa.N = (int)t->vN;
     int nsplit = 1;
-    rc = tr_ensure_pad(c, t);
+    rc = tr_wgrad_obs(c, t, wa);
     if (rc) return rc;
-    wa.obs_pad = t->pad_valid ? t->obs_pad : nullptr; wa.obs_ko = t->pad_ko;
     if (gn) {                    // dz2 = dout = 0: the second operand pairs vanish -- the one-pair weight-side launch, half the matrix work
         wn.w2_yb = wn.w2_xb = wn.w3_xb = wn.w3_yb = nullptr;
         rc = wgrad_launch<false>(c, c->md, wa, 1, c->n_dev, &nsplit);
@@ -580,10 +532,7 @@ static int tr_hvp_dev(fsrl_ctx* c, TrState* t, bool use_cache = false, int* part
     rc = wgrad_launch<true>(c, c->md, wa, 1, c->n_dev, &nsplit);
     if (rc) return rc;
     if (parts_out) { *parts_out = nsplit; return 0; }       // the caller's next kernel adds the partials up itself (tr_cg_dev)
-    hipLaunchKernelGGL(fb_sum_parts_kernel, dim3((c->md.net[0].end - c->md.net[0].begin + 255) / 256), dim3(256), 0,
-                       c->compute, t->Out, c->wg_parts, c->md.net[0].begin, c->md.net[0].end, nsplit, c->n_dev);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return tr_sum_parts(c, t, 0, 1, t->Out, nsplit);
 }
 static int tr_hvp(fsrl_ctx* c, TrState* t, const float* v, float* out, bool use_cache = false) {
     int rc = actor_to_dev(c, v, t->Vdev);
@@ -603,34 +552,32 @@ extern "C" int32_t fsrl_tr_linesearch_evals(fsrl_ctx* c, int32_t* out, int32_t c
     return n;
 }
 
-extern "C" int fsrl_tr_grad(fsrl_ctx* c, int32_t which, float* out, int64_t n) {
-    CHECK_ARG(c && out, "null argument");
+// what fsrl_tr_grad / _hvp / _hvp_cached check before they touch the device
+static int tr_product_enter(fsrl_ctx* c, bool args, const char* name, int64_t n) {
+    CHECK_ARG(c && args, "null argument");
     TrState* t = tr_of(c);
-    if (!t->ready) return fail(FSRL_ESTATE, "fsrl_tr_grad before fsrl_tr_begin");
+    if (!t->ready) return fail(FSRL_ESTATE, "%s before fsrl_tr_begin", name);
     CHECK_ARG(n == t->na, "expected %d actor parameters", t->na);
     ENTER_DEV(c);
-    if (which == 0) return tr_actor_grad(c, t, FB_MODE_SUR, 1.0f, 0.0f, out, nullptr);
-    if (which == 1) return tr_actor_grad(c, t, FB_MODE_SUR, 0.0f, -1.0f, out, nullptr);
-    if (which == 2) return tr_actor_grad(c, t, FB_MODE_KL, 0.0f, 0.0f, out, nullptr);
-    return fail(FSRL_EINVAL, "which must be 0, 1 or 2");
+    return 0;
+}
+extern "C" int fsrl_tr_grad(fsrl_ctx* c, int32_t which, float* out, int64_t n) {
+    int rc = tr_product_enter(c, out != nullptr, "fsrl_tr_grad", n);
+    if (rc) return rc;
+    TrState* t = c->tr;
+    CHECK_ARG(which >= 0 && which <= 2, "which must be 0, 1 or 2");      // reward surrogate | cost surrogate (negated) | KL
+    rc = tr_actor_grad_dev(c, t, which == 2 ? FB_MODE_KL : FB_MODE_SUR, which == 0 ? 1.0f : 0.0f, which == 1 ? -1.0f : 0.0f, t->Out, nullptr);
+    return rc ? rc : actor_from_dev(c, t->Out, out);
 }
 extern "C" int fsrl_tr_hvp(fsrl_ctx* c, const float* v, float* out, int64_t n) {
-    CHECK_ARG(c && v && out, "null argument");
-    TrState* t = tr_of(c);
-    if (!t->ready) return fail(FSRL_ESTATE, "fsrl_tr_hvp before fsrl_tr_begin");
-    CHECK_ARG(n == t->na, "expected %d actor parameters", t->na);
-    ENTER_DEV(c);
-    return tr_hvp(c, t, v, out);
+    int rc = tr_product_enter(c, v && out, "fsrl_tr_hvp", n);
+    return rc ? rc : tr_hvp(c, c->tr, v, out);
 }
 // the same product for a caller that promises theta, the batch and mean_old / std_old are those of its previous fsrl_tr_hvp /
 // fsrl_tr_hvp_cached call: the theta-only activations are read back (what conjugate gradients do inside the learn calls)
 extern "C" int fsrl_tr_hvp_cached(fsrl_ctx* c, const float* v, float* out, int64_t n) {
-    CHECK_ARG(c && v && out, "null argument");
-    TrState* t = tr_of(c);
-    if (!t->ready) return fail(FSRL_ESTATE, "fsrl_tr_hvp_cached before fsrl_tr_begin");
-    CHECK_ARG(n == t->na, "expected %d actor parameters", t->na);
-    ENTER_DEV(c);
-    return tr_hvp(c, t, v, out, true);
+    int rc = tr_product_enter(c, v && out, "fsrl_tr_hvp_cached", n);
+    return rc ? rc : tr_hvp(c, c->tr, v, out, true);
 }
 /* kernel plan of the full-batch path (A/B runs and the bit-identity tests; 0 = automatic everywhere) */
 extern "C" int fsrl_tr_set_plan(fsrl_ctx* c, int32_t tile_rows, int32_t hvp, int32_t wgrad) {
@@ -716,25 +663,16 @@ static int tr_mvp_dev(fsrl_ctx* c, TrState* t, const float* v_dev, float damping
 
 // up to four dot products of device vectors: float64 accumulation, rounded to fp32 once (as the host's vdot did).  One
 // synchronisation.  `sigma_out`: the actor's sigma_param comes back with the same copy (entropy of the logged row).
-static int tr_dots(fsrl_ctx* c, TrState* t, int n_pairs, const float* const* a, const float* const* b, float* out) {
+static int tr_dots(fsrl_ctx* c, TrState* t, std::initializer_list<std::pair<const float*, const float*>> pairs, float* out) {
     TrDotArgs da{};
-    da.n_pairs = n_pairs;
-    for (int k = 0; k < n_pairs; ++k) { da.a[k] = a[k]; da.b[k] = b[k]; }
+    const int n_pairs = da.n_pairs = (int)pairs.size();
+    for (int k = 0; k < n_pairs; ++k) { da.a[k] = pairs.begin()[k].first; da.b[k] = pairs.begin()[k].second; }
     double* part = t->cg_part;                       // free between CG solves
-    const double* hp = t->h_part;
-    if (t->opt_poll && t->h_rb) {
-        const unsigned seq = rb_next(t);
-        hipLaunchKernelGGL(tr_dots_kernel, dim3(CG_NB), dim3(256), 0, c->compute, da, part, c->md.net[0].end, t->h_rb, t->h_rb_done, seq);
-        HIPCHK(hipGetLastError());
-        int rc = rb_wait(c, t, CG_NB);
-        if (rc) return rc;
-        hp = t->h_rb;
-    } else {
-        hipLaunchKernelGGL(tr_dots_kernel, dim3(CG_NB), dim3(256), 0, c->compute, da, part, c->md.net[0].end);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(t->h_part, part, (size_t)n_pairs * CG_NB * sizeof(double), hipMemcpyDeviceToHost, c->compute));
-        HIPCHK(hipStreamSynchronize(c->compute));
-    }
+    const double* hp = nullptr;
+    int rc = tr_read_back(c, t, CG_NB, part, t->h_part, (size_t)n_pairs * CG_NB, &hp, [&](double* hout, unsigned* done, unsigned seq) {
+        hipLaunchKernelGGL(tr_dots_kernel, dim3(CG_NB), dim3(256), 0, c->compute, da, part, c->md.net[0].end, hout, done, seq);
+    });
+    if (rc) return rc;
     for (int k = 0; k < n_pairs; ++k) {
         double s = 0.0;
         for (int bl = 0; bl < CG_NB; ++bl) s += hp[k * CG_NB + bl];
@@ -833,7 +771,6 @@ static int tr_critic_enqueue(fsrl_ctx* c, TrState* t, int iters, float l2) {
                            (const float*)nullptr, 0, 0.0f, (float*)nullptr, (float*)nullptr, 0.0f, 0.0f, 1);   // 1: float64 sum of the partials
         HIPCHK(hipGetLastError());
     }
-    t->crit_pending = iters > 0;
     return 0;
 }
 // wait for the critic chain and turn its sums into the logged losses vf_out[C] (zeros when no step ran)
@@ -865,36 +802,12 @@ static int tr_prepare_repeat(fsrl_ctx* c, TrState* t, int32_t batch_size, const 
     const int n = (int)c->N;
     split_plan(n, std::max(1, std::min<int>(batch_size, std::max(n, 1))), st, sz);
     if (st.size() <= 1) { tr_set_view(t, c->b.obs, t->rd, n); return 0; }
-    c->perm_tmp.resize((size_t)n);
-    if (perm) {
-        std::vector<uint8_t> seen((size_t)n, 0);
-        for (int i = 0; i < n; ++i) {
-            CHECK_ARG(perm[i] >= 0 && perm[i] < n, "perm[%d]=%lld out of range", i, (long long)perm[i]);
-            CHECK_ARG(!seen[(size_t)perm[i]], "perm is not a permutation: %lld appears twice", (long long)perm[i]);
-            seen[(size_t)perm[i]] = 1;
-            c->perm_tmp[(size_t)i] = (int)perm[i];
-        }
-    } else {
-        if (seed) { c->shuffle_rng[0] ^= seed; c->shuffle_rng[1] += seed * 0x9E3779B97F4A7C15ull; }
-        for (int i = 0; i < n; ++i) c->perm_tmp[(size_t)i] = i;
-        for (int i = n - 1; i > 0; --i) {
-            const int j = (int)(xoshiro_next(c->shuffle_rng) % (uint64_t)(i + 1));
-            std::swap(c->perm_tmp[(size_t)i], c->perm_tmp[(size_t)j]);
-        }
-    }
-    if (c->perm_in_flight) { HIPCHK(hipEventSynchronize(c->perm_copied)); c->perm_in_flight = false; }
-    memcpy(c->h_perm, c->perm_tmp.data(), (size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(c->d_perm, c->h_perm, (size_t)n * 4, hipMemcpyHostToDevice, c->compute));
-    HIPCHK(hipEventRecord(c->perm_copied, c->compute));
-    c->perm_in_flight = true;
+    int rc = perm_upload(c, n, perm, seed);
+    if (rc) return rc;
     hipLaunchKernelGGL(fb_gather_rows_kernel, dim3(1024), dim3(256), 0, c->compute, c->obs_p, c->rd_p, c->b.obs, t->rd, c->d_perm,
                        n, c->cfg.obs_dim);
     HIPCHK(hipGetLastError());
     return 0;
-}
-static void tr_chunk_view(fsrl_ctx* c, TrState* t, const std::vector<int>& st, const std::vector<int>& sz, size_t k) {
-    if (st.size() <= 1) return;
-    tr_set_view(t, c->obs_p + (size_t)st[k] * c->cfg.obs_dim, c->rd_p + (size_t)st[k] * FSRL_RD, sz[k]);
 }
 
 // Joins the critic lane on EVERY exit of a step: an early `return rc` between tr_critic_enqueue and tr_critic_collect would leave
@@ -902,21 +815,31 @@ static void tr_chunk_view(fsrl_ctx* c, TrState* t, const std::vector<int>& st, c
 // error -- fsrl_params_get / fsrl_state_restore on the compute stream would race with them.
 struct CriticJoin {
     TrState* t;
-    explicit CriticJoin(TrState* t_) : t(t_) {}
-    ~CriticJoin() {
-        if (t->crit_pending && t->cstream) { (void)hipStreamSynchronize(t->cstream); t->crit_pending = false; }
-    }
+    ~CriticJoin() { if (t->crit_pending && t->cstream) { (void)hipStreamSynchronize(t->cstream); t->crit_pending = false; } }
 };
+
+// Puts the view back on the whole batch on EVERY exit of a learn call: one that fails after its first minibatch (a bad permutation
+// of a later repeat, a HIP error) would otherwise leave fsrl_tr_eval / _grad / _hvp working on one chunk of the permuted copy.
+struct WholeBatchView { fsrl_ctx* c; TrState* t; ~WholeBatchView() { tr_set_view(t, c->b.obs, t->rd, c->N); } };
+
+// one try of a line search: theta := theta0 + step * dir, then the batch means at the new theta
+static int tr_try_step(fsrl_ctx* c, TrState* t, const float* th0, const float* dir, float step, double* means8) {
+    t->hvp_valid = false;
+    c->theta_version += 1;
+    hipLaunchKernelGGL(tr_step_kernel, dim3(CG_NB), dim3(256), 0, c->compute, c->P, th0, dir, step, c->md.net[0].end, c->md);
+    HIPCHK(hipGetLastError());
+    return tr_eval_means(c, t, means8);
+}
 
 // one minibatch of CPO.learn on the current view: optim_critic_iters critic steps, then policy_loss (cpo.py:360-364)
 static int cpo_step(fsrl_ctx* c, TrState* t, double ave_cost_return, float* st, int* evals_out) {
     const fsrl_tr_config& k = t->cfg;
-    const float EPS = 1e-8f, delta = k.target_kl;
+    const float delta = k.target_kl;
     const int nd = c->md.net[0].end;
     const size_t vs = (size_t)c->n_dev;
     float *vg = t->vec, *vb = t->vec + vs, *vHg = t->vec + 2 * vs, *vHb = t->vec + 3 * vs, *vag = t->vec + 4 * vs,
           *vab = t->vec + 5 * vs, *vdir = t->vec + 6 * vs, *vth0 = t->vec + 7 * vs;
-    CriticJoin join(t);                                                    // whatever happens below, the lane is joined on the way out
+    CriticJoin join{t};                                                    // whatever happens below, the lane is joined on the way out
     int rc = tr_critic_enqueue(c, t, k.optim_critic_iters, k.l2_reg);      // on their own stream, beside everything below
     if (rc) return rc;
     // ---- objective, cost surrogate, KL and their gradients (cpo.py:238-254); g, b and everything derived from them
@@ -938,91 +861,55 @@ static int cpo_step(fsrl_ctx* c, TrState* t, double ave_cost_return, float* st, 
     rc = tr_mvp_dev(c, t, vHg, k.damping, vag);
     if (rc) return rc;
     const float c_value = cost_sur - (float)k.cost_limit;
-    float s_q, s_r = 0.f, s_s = 0.f, A = 0.f, B = 0.f;
-    int ocase;
-    float d2[2];
-    { const float* a_[2] = {vb, vag}; const float* b_[2] = {vb, vHg};
-      rc = tr_dots(c, t, 2, a_, b_, d2);
-      if (rc) return rc; }
-    s_q = d2[1];
-    if (d2[0] <= EPS && c_value < 0) {
+    float s_r = 0.f, s_s = 0.f, d2[2];
+    rc = tr_dots(c, t, {{vb, vb}, {vag, vHg}}, d2);
+    if (rc) return rc;
+    const float bb = d2[0], s_q = d2[1];
+    if (cpo_cost_solve_skipped(bb, c_value)) {
         HIPCHK(hipMemsetAsync(vHb, 0, (size_t)nd * 4, c->compute));
-        ocase = 4;
     } else {
         rc = tr_cg_dev(c, t, vb, k.damping, k.cg_iters, 1e-8f, vHb);
         if (rc) return rc;
         rc = tr_mvp_dev(c, t, vHb, k.damping, vab);
         if (rc) return rc;
-        { const float* a_[2] = {vag, vab}; const float* b_[2] = {vHb, vHb};
-          rc = tr_dots(c, t, 2, a_, b_, d2);
-          if (rc) return rc; }
+        rc = tr_dots(c, t, {{vag, vHb}, {vab, vHb}}, d2);
+        if (rc) return rc;
         s_r = d2[0]; s_s = d2[1];
-        A = s_q - s_r * s_r / s_s;
-        B = 2.0f * delta - c_value * c_value / s_s;
-        if (c_value < 0 && B < 0) ocase = 3;
-        else if (c_value < 0 && B >= 0) ocase = 2;
-        else if (c_value >= 0 && B >= 0) ocase = 1;
-        else ocase = 0;
     }
-    float lam, nu;
-    if (ocase == 3 || ocase == 4) {
-        lam = std::sqrt(s_q / (2.0f * delta));
-        nu = 0.0f;
-    } else if (ocase == 1 || ocase == 2) {
-        const float rc_ = s_r / c_value, inf = INFINITY;
-        float LA[2] = {0.0f, rc_}, LB[2] = {rc_, inf};
-        if (!(c_value < 0)) { std::swap(LA[0], LB[0]); std::swap(LA[1], LB[1]); }
-        auto proj = [](float x, const float* L) { return std::max(L[0], std::min(L[1], x)); };
-        const float lam_a = proj(std::sqrt(A / B), LA), lam_b = proj(std::sqrt(s_q / (2.0f * delta)), LB);
-        auto f_a = [&](float l) { return -0.5f * (A / (l + EPS) + B * l) - s_r * c_value / (s_s + EPS); };
-        auto f_b = [&](float l) { return -0.5f * (s_q / (l + EPS) + 2.0f * delta * l); };
-        lam = (f_a(lam_a) >= f_b(lam_b)) ? lam_a : lam_b;
-        nu = std::max(0.0f, lam * c_value - s_r) / (s_s + EPS);
-    } else {
-        nu = std::sqrt(2.0f * delta / (s_s + EPS));
-        lam = 0.0f;
-    }
+    const CpoDual d = cpo_dual_solve(s_q, s_r, s_s, c_value, delta, bb);
     // ---- line search (cpo.py:306-333); on failure the LAST tried theta stays in place
-    hipLaunchKernelGGL(tr_dir_kernel, dim3(CG_NB), dim3(256), 0, c->compute, vdir, vHg, vHb, 1.0f / (lam + EPS), nu,
-                       ocase > 0 ? 1 : 0, t->cg_part, nd);
+    hipLaunchKernelGGL(tr_dir_kernel, dim3(CG_NB), dim3(256), 0, c->compute, vdir, vHg, vHb, 1.0f / (d.lam + CPO_EPS), d.nu,
+                       d.ocase > 0 ? 1 : 0, t->cg_part, nd);
     hipLaunchKernelGGL(tr_unit_kernel, dim3(CG_NB), dim3(256), 0, c->compute, vdir, t->cg_part, nd);
     HIPCHK(hipGetLastError());
-    double beta = 1.0;
-    int evals = 0;
-    if (!std::isnan(lam)) {
-        for (int bt = 0; bt < k.max_backtracks; ++bt) {
-            ++evals;
-            t->hvp_valid = false;
-            c->theta_version += 1;
-            hipLaunchKernelGGL(tr_step_kernel, dim3(CG_NB), dim3(256), 0, c->compute, c->P, vth0, vdir, (float)beta, nd, c->md);
-            HIPCHK(hipGetLastError());
-            double e8[FB_NSTAT];
-            rc = tr_eval_means(c, t, e8);
-            if (rc) return rc;
-            const float new_kl = (float)e8[2], new_obj = (float)e8[0];
-            const float new_cs = ((float)ave_cost_return + (float)e8[1]) - (float)e8[5];
-            const bool ok = ((double)new_kl <= (double)delta) && (ocase > 1 ? new_obj > objective : true) &&
-                            ((double)(new_cs - cost_sur) <= std::max(-(double)c_value, 0.0));
-            if (ok) break;
-            beta *= (double)k.backtrack_coeff;
-        }
-    }
+    const CpoSearch ls = cpo_line_search(d.lam, (double)k.backtrack_coeff, k.max_backtracks, [&](double beta) {
+        double e8[FB_NSTAT];
+        rc = tr_try_step(c, t, vth0, vdir, (float)beta, e8);
+        if (rc) return true;                                               // an error ends the search; it is returned below
+        const float new_cs = ((float)ave_cost_return + (float)e8[1]) - (float)e8[5];
+        return cpo_accepts((float)e8[2], (float)e8[0], new_cs, delta, d.ocase, objective, cost_sur, c_value);
+    });
+    if (rc) return rc;
     rc = tr_critic_collect(c, t, k.l2_reg, st + 14);
     if (rc) return rc;
     st[16] = st[14] + st[15];
-    st[0] = kl; st[1] = ent; st[2] = objective; st[3] = cost_sur; st[4] = A; st[5] = B; st[6] = c_value;
-    st[7] = s_q; st[8] = s_r; st[9] = s_s; st[10] = lam; st[11] = nu; st[12] = (float)ocase; st[13] = (float)beta;
-    *evals_out = evals;
+    st[0] = kl; st[1] = ent; st[2] = objective; st[3] = cost_sur; st[4] = d.A; st[5] = d.B; st[6] = c_value;
+    st[7] = s_q; st[8] = s_r; st[9] = s_s; st[10] = d.lam; st[11] = d.nu; st[12] = (float)d.ocase; st[13] = (float)ls.beta;
+    *evals_out = ls.evals;
     return 0;
 }
 
-extern "C" int fsrl_cpo_learn_mb(fsrl_ctx* c, double ave_cost_return, int32_t repeat, int32_t batch_size, const int64_t* perms,
-                                 uint64_t seed, float* stats_out, int64_t cap_rows, int64_t* n_rows_out) {
+// The frame of both learn calls: `repeat` passes over the batch, each split into minibatches (tr_prepare_repeat), `step` on every
+// minibatch's view writing one row of `nstats` floats.  `step(t, row, &evals)`; `name` is the entry point's in the state error.
+template <class Step>
+static int tr_learn(fsrl_ctx* c, const char* name, int32_t repeat, int32_t batch_size, const int64_t* perms, uint64_t seed,
+                    float* stats_out, int nstats, int64_t cap_rows, int64_t* n_rows_out, Step&& step) {
     CHECK_ARG(c && stats_out, "null argument");
     CHECK_ARG(batch_size >= 1 && repeat >= 0, "batch_size must be >= 1, repeat >= 0");
     TrState* t = tr_of(c);
-    if (!t->ready) return fail(FSRL_ESTATE, "fsrl_cpo_learn before fsrl_tr_begin");
+    if (!t->ready) return fail(FSRL_ESTATE, "%s before fsrl_tr_begin", name);
     ENTER_DEV(c);
+    WholeBatchView whole{c, t};                      // on every way out
     t->ls_iters.clear();
     std::vector<int> mst, msz;
     int64_t row = 0;
@@ -1031,16 +918,21 @@ extern "C" int fsrl_cpo_learn_mb(fsrl_ctx* c, double ave_cost_return, int32_t re
         if (rc) return rc;
         for (size_t mb = 0; mb < mst.size(); ++mb, ++row) {
             CHECK_ARG(row < cap_rows, "stats_out holds %lld rows, the update has more", (long long)cap_rows);
-            tr_chunk_view(c, t, mst, msz, mb);
+            if (mst.size() > 1) tr_set_view(t, c->obs_p + (size_t)mst[mb] * c->cfg.obs_dim, c->rd_p + (size_t)mst[mb] * FSRL_RD, msz[mb]);
             int evals = 0;
-            rc = cpo_step(c, t, ave_cost_return, stats_out + (size_t)row * FSRL_CPO_NSTATS, &evals);
+            rc = step(t, stats_out + (size_t)row * (size_t)nstats, &evals);
             if (rc) return rc;
             t->ls_iters.push_back(evals);
         }
     }
-    tr_set_view(t, c->b.obs, t->rd, c->N);
     if (n_rows_out) *n_rows_out = row;
     return 0;
+}
+
+extern "C" int fsrl_cpo_learn_mb(fsrl_ctx* c, double ave_cost_return, int32_t repeat, int32_t batch_size, const int64_t* perms,
+                                 uint64_t seed, float* stats_out, int64_t cap_rows, int64_t* n_rows_out) {
+    return tr_learn(c, "fsrl_cpo_learn", repeat, batch_size, perms, seed, stats_out, FSRL_CPO_NSTATS, cap_rows, n_rows_out,
+                    [&](TrState* t, float* st, int* evals) { return cpo_step(c, t, ave_cost_return, st, evals); });
 }
 extern "C" int fsrl_cpo_learn(fsrl_ctx* c, double ave_cost_return, int32_t repeat, float* stats_out) {
     return fsrl_cpo_learn_mb(c, ave_cost_return, repeat, INT_MAX, nullptr, 0, stats_out, repeat, nullptr);
@@ -1055,7 +947,7 @@ static int trpo_step(fsrl_ctx* c, TrState* t, float lam0, float resc, float* st,
     const float delta = k.target_kl;
     // the critics' steps (trpo_lag.py:234-239) read the returns and the critics only: enqueued now on their own stream, they run
     // beside the actor's step instead of behind it
-    CriticJoin join(t);
+    CriticJoin join{t};
     int rc = tr_critic_enqueue(c, t, k.optim_critic_iters, 0.0f);
     if (rc) return rc;
     rc = tr_refresh_old(c, t);         // old_dist = pi_theta (detached), trpo_lag.py:189-190
@@ -1078,63 +970,34 @@ static int trpo_step(fsrl_ctx* c, TrState* t, float lam0, float resc, float* st,
     rc = tr_mvp_dev(c, t, vdir, k.damping, vHd);
     if (rc) return rc;
     float dHd;
-    { const float* a_[1] = {vdir}; const float* b_[1] = {vHd};
-      rc = tr_dots(c, t, 1, a_, b_, &dHd);
-      if (rc) return rc; }
-    float step = std::sqrt(2.0f * delta / dHd);
+    rc = tr_dots(c, t, {{vdir, vHd}}, &dHd);
+    if (rc) return rc;
     float kl = 0.0f;
-    int evals = 0;
-    for (int i = 0; i < k.max_backtracks; ++i) {
-        ++evals;
-        t->hvp_valid = false;
-        c->theta_version += 1;
-        hipLaunchKernelGGL(tr_step_kernel, dim3(CG_NB), dim3(256), 0, c->compute, c->P, vth0, vdir, step, nd, c->md);
-        HIPCHK(hipGetLastError());
+    const TrpoSearch ls = trpo_line_search(std::sqrt(2.0f * delta / dHd), k.backtrack_coeff, k.max_backtracks, [&](float step) {
         double e8[FB_NSTAT];
-        rc = tr_eval_means(c, t, e8);
-        if (rc) return rc;
+        rc = tr_try_step(c, t, vth0, vdir, step, e8);
+        if (rc) return true;                                               // an error ends the search; it is returned below
         kl = (float)e8[2];
         const float loss_new = resc * (-(float)e8[0] + (c->cfg.use_lagrangian ? (float)e8[1] * lam0 : 0.0f));
-        if ((double)kl < (double)delta && loss_new < loss_actor) break;
-        else if (i < k.max_backtracks - 1) step *= k.backtrack_coeff;
-        else step = 0.0f;   // total failure: the last tried parameters stay (trpo_lag.py:225-227)
-    }
+        return trpo_accepts(kl, delta, loss_new, loss_actor);
+    });
+    if (rc) return rc;
     float vf[FSRL_MAX_CRITICS] = {0, 0, 0, 0};
     rc = tr_critic_collect(c, t, 0.0f, vf);
     if (rc) return rc;
     st[0] = resc; st[1] = lam0; st[2] = loss_safety; st[3] = loss_rew; st[4] = loss_actor;
-    st[5] = vf[0]; st[6] = vf[1]; st[7] = vf[0] + vf[1]; st[8] = kl; st[9] = step; st[10] = ent;
-    *evals_out = evals;
+    st[5] = vf[0]; st[6] = vf[1]; st[7] = vf[0] + vf[1]; st[8] = kl; st[9] = ls.step; st[10] = ent;
+    *evals_out = ls.evals;
     return 0;
 }
 
 extern "C" int fsrl_trpo_learn_mb(fsrl_ctx* c, const double* lagrangians, double rescaling, int32_t repeat, int32_t batch_size,
                                   const int64_t* perms, uint64_t seed, float* stats_out, int64_t cap_rows, int64_t* n_rows_out) {
-    CHECK_ARG(c && stats_out, "null argument");
-    CHECK_ARG(batch_size >= 1 && repeat >= 0, "batch_size must be >= 1, repeat >= 0");
-    TrState* t = tr_of(c);
-    if (!t->ready) return fail(FSRL_ESTATE, "fsrl_trpo_learn before fsrl_tr_begin");
-    ENTER_DEV(c);
-    const float lam0 = (c->cfg.use_lagrangian && lagrangians) ? (float)lagrangians[0] : 0.0f;
-    const float resc = (float)rescaling;
-    t->ls_iters.clear();
-    std::vector<int> mst, msz;
-    int64_t row = 0;
-    for (int rep = 0; rep < repeat; ++rep) {
-        int rc = tr_prepare_repeat(c, t, batch_size, perms ? perms + (size_t)rep * (size_t)c->N : nullptr, seed ? seed + rep : 0, mst, msz);
-        if (rc) return rc;
-        for (size_t mb = 0; mb < mst.size(); ++mb, ++row) {
-            CHECK_ARG(row < cap_rows, "stats_out holds %lld rows, the update has more", (long long)cap_rows);
-            tr_chunk_view(c, t, mst, msz, mb);
-            int evals = 0;
-            rc = trpo_step(c, t, lam0, resc, stats_out + (size_t)row * FSRL_TRPO_NSTATS, &evals);
-            if (rc) return rc;
-            t->ls_iters.push_back(evals);
-        }
-    }
-    tr_set_view(t, c->b.obs, t->rd, c->N);
-    if (n_rows_out) *n_rows_out = row;
-    return 0;
+    return tr_learn(c, "fsrl_trpo_learn", repeat, batch_size, perms, seed, stats_out, FSRL_TRPO_NSTATS, cap_rows, n_rows_out,
+                    [&](TrState* t, float* st, int* evals) {
+        const float lam0 = (c->cfg.use_lagrangian && lagrangians) ? (float)lagrangians[0] : 0.0f;
+        return trpo_step(c, t, lam0, (float)rescaling, st, evals);
+    });
 }
 extern "C" int fsrl_trpo_learn(fsrl_ctx* c, const double* lagrangians, double rescaling, int32_t repeat,
                                float* stats_out) {

@@ -302,3 +302,51 @@ def test_policy_update_with_a_batch_size_below_the_buffer(which):
     assert pol.gradient_steps - g0 == 6 * per
     kl_rows = [kw for _, kw in rows if "loss/kl" in kw or "kl" in kw]
     assert len(kl_rows) == 6 and all(np.isfinite(list(kw.values())).all() for kw in kl_rows)
+
+
+@pytest.mark.parametrize("which", ["cpo", "trpo"])
+def test_a_failed_learn_call_leaves_the_whole_batch_in_view(which):
+    """A learn call that fails after its first minibatch must not leave the context looking at one chunk of the permuted copy.
+    Two engines prepared alike (N = 560, batch 150): the first runs two repeats whose SECOND permutation repeats an entry -- the
+    call raises and names it, after the three minibatches of the first repeat; the twin runs that first repeat alone.  Afterwards
+    both must be in the same state, bit for bit: tr_eval() over the batch (560 rows, not the 260 of the last chunk), the
+    parameters, and the rows of one further full-batch learn call."""
+    g = load_npz(f"{which}_minibatch.npz")
+    cfg = json.loads(str(g["cfg_json"]))
+    lag = g["lagrangian"] if which == "trpo" else None
+
+    def prepared():
+        if which == "cpo":
+            eng = _engine(cfg)
+        else:
+            eng = _engine(cfg, use_lagrangian=cfg["use_lagrangian"])
+        _start(eng, g); _push(eng, g)
+        if which == "cpo":
+            eng.tr_begin(target_kl=cfg["target_kl"], backtrack_coeff=cfg["backtrack_coeff"], damping=cfg["damping_coeff"],
+                         l2_reg=cfg["l2_reg"], critic_lr=cfg["lr"], max_backtracks=cfg["max_backtracks"],
+                         optim_critic_iters=cfg["optim_critic_iters"], norm_adv=cfg["advantage_normalization"],
+                         cost_limit=cfg["cost_limit"])
+        else:
+            eng.tr_begin(target_kl=cfg["target_kl"], backtrack_coeff=cfg["backtrack_coeff"], damping=0.1, l2_reg=0.0,
+                         critic_lr=cfg["lr"], max_backtracks=cfg["max_backtracks"],
+                         optim_critic_iters=cfg["optim_critic_iters"], norm_adv=cfg["advantage_normalization"])
+        return eng
+
+    def learn(eng, repeat, **kw):
+        if which == "cpo":
+            return eng.cpo_learn(cfg["cost_stat"], repeat, **kw)
+        return eng.trpo_learn(lag, 1.0 / (lag.sum() + 1.0), repeat, **kw)
+
+    perms = np.asarray(g["perms"], np.int64)
+    assert perms.shape == (2, 560) and cfg["batch_size"] == 150
+    bad = perms.copy()
+    bad[1, 401] = bad[1, 17]
+    first, twin = prepared(), prepared()
+    with pytest.raises(AssertionError, match=f"{int(bad[1, 17])} appears twice"):
+        learn(first, 2, batch_size=150, perms=bad)
+    assert learn(twin, 1, batch_size=150, perms=perms[:1]).shape[0] == 3
+    assert np.array_equal(first.tr_eval(), twin.tr_eval())
+    assert np.array_equal(first.get_params(), twin.get_params())
+    assert np.array_equal(learn(first, 1), learn(twin, 1), equal_nan=True)
+    assert np.array_equal(first.get_params(), twin.get_params())
+    first.close(); twin.close()
