@@ -38,6 +38,14 @@ tools/bench_group_collect.py --hidden ...): at 8 seeds of (256, 256, 256) 1.9x t
 collecting seed by seed; grouped updates lose to threads at 2 seeds or fewer, shared collection loses at one seed.
 Layered CVPO seeds do not group yet: --grouped --algo cvpo refuses them.
     python examples/train_multi_seed.py --algo sacl --seeds 8 --epoch 2 --grouped --hidden-sizes 64x48x32
+--grouped --algo cpo / trpol: ONE thread collects -- the seeds collect in lock step through an EngineCollectGroup over their
+on-policy engines (one actor request per vector step, the resident kernel of the PPO-Lag group; layered seeds: L + 2 launches) --
+each seed's pre_update_fn sees its cost, then ONE fsrl_amd.policy.TrustPolicyGroup.update runs every seed's own update
+(fsrl_tr_begin + fsrl_cpo_learn / fsrl_trpo_learn) on a worker thread per seed, beside each other; no launch is shared on the
+update side.  Per seed bit-identical to collecting and updating the seeds one after the other (tools/bench_group_trust.py,
+tools/bench_group_collect.py --algo cpo).  Fused and layered --hidden-sizes.
+    python examples/train_multi_seed.py --algo cpo --seeds 8 --epoch 2 --grouped
+    python examples/train_multi_seed.py --algo trpol --seeds 4 --epoch 2 --grouped --hidden-sizes 64x48x32
 """
 import argparse
 import os
@@ -53,7 +61,52 @@ from fsrl_amd.utils import BaseLogger  # noqa: E402
 
 AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops": FOCOPSAgent, "sacl": SACLagAgent,
           "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}
-GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo")      # what --grouped takes
+GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo", "cpo", "trpol")      # what --grouped takes
+
+
+def run_grouped_trust(a):
+    """k CPO (TRPO-Lag) seeds: lock-step collection from one host thread (a collect group over the seeds' on-policy engines), each
+    seed's pre_update_fn, then ONE TrustPolicyGroup.update -- the seeds' own updates on a worker thread each -- and reset_buffer."""
+    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
+    from fsrl_amd.engine import EngineCollectGroup
+    from fsrl_amd.policy import TrustPolicyGroup
+    agents, cols, bufs = [], [], []
+    for seed in range(a.seeds):
+        env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
+        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
+                               training_num=a.envs)
+        agent.policy.train()
+        buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
+        agents.append(agent); bufs.append(buf)
+        cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
+    cgroup = EngineCollectGroup([ag.policy.engine for ag in agents])
+    group = TrustPolicyGroup([ag.policy for ag in agents], collect_group=cgroup)
+    gcol = GroupCollector(cgroup, cols)
+    t0, steps, updates = time.time(), 0, 0
+    for ep in range(a.epoch):
+        budget = 6000
+        while budget > 0:
+            for ag, st in zip(agents, gcol.collect(n_episode=a.envs)):
+                ag.policy.pre_update_fn(stats_train=st)
+                ag.logger.store(**{"train/reward": st["rew"], "train/cost": st["cost"]})
+                steps += st["n/st"]
+            budget -= st["n/st"]
+            group.update(bufs, batch_size=99999, repeat=4)
+            updates += len(agents)
+            for col in cols:
+                col.reset_buffer(keep_statistics=True)
+        for seed, ag in enumerate(agents):
+            print(f"epoch {ep + 1} seed {seed}: reward {ag.logger.get_mean('train/reward'):.2f} "
+                  f"cost {ag.logger.get_mean('train/cost'):.2f}")
+            ag.logger.write(steps, display=False)
+    dt = time.time() - t0
+    print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
+          f"aggregate in {dt:.1f} s")
+    group.close()
+    cgroup.close()
+    for ag in agents:
+        ag.policy.engine.close()
 
 
 def run_grouped_replay(a):
@@ -109,9 +162,11 @@ def run_grouped_replay(a):
 def run_grouped(a):
     """k PPO-Lag (FOCOPS) seeds, one host thread: collect every seed's episodes in lock step, step each PID multiplier (each
     seed's cost goes to its nu step), ONE grouped update."""
-    assert a.algo in GROUPED_ALGOS, "--grouped: PPO-Lagrangian, FOCOPS, SAC-Lagrangian, DDPG-Lagrangian or CVPO"
+    assert a.algo in GROUPED_ALGOS, "--grouped: PPO-Lagrangian, FOCOPS, SAC-Lagrangian, DDPG-Lagrangian, CVPO, CPO or TRPO-Lagrangian"
     if a.algo in ("sacl", "ddpgl", "cvpo"):
         return run_grouped_replay(a)
+    if a.algo in ("cpo", "trpol"):
+        return run_grouped_trust(a)
     from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
     from fsrl_amd.policy import PolicyGroup
     agents, cols, bufs = [], [], []
@@ -164,10 +219,11 @@ def parse_args(argv=None):
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread")
+    ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread; "
+                                                           "CPO / TRPO-Lag: lock-step collection, the seeds' own updates beside each other")
     ap.add_argument("--hidden-sizes", default="128x128", type=lambda t: tuple(int(w) for w in t.lower().split("x")),
                     help="hidden layers of every network, e.g. 64x48x32 (anything but two layers of at most 256 units runs the "
-                         "layered kernels; --grouped takes such PPO-Lag, SAC-Lag and DDPG-Lag seeds too, not FOCOPS or CVPO seeds)")
+                         "layered kernels; --grouped takes such PPO-Lag, SAC-Lag, DDPG-Lag, CPO and TRPO-Lag seeds too, not FOCOPS or CVPO seeds)")
     a = ap.parse_args(argv)
     if isinstance(a.hidden_sizes, str):
         a.hidden_sizes = tuple(int(w) for w in a.hidden_sizes.lower().split("x"))

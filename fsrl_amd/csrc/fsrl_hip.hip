@@ -188,7 +188,7 @@ struct fsrl_ctx {
     bool probe_tile16 = false;
     struct fsrl_sac_group* sac_group = nullptr;      // the grouped SAC-Lagrangian update this context is a member of (host_sac_group.inc)
     struct fsrl_cvpo_group* cvpo_group = nullptr;    // the grouped CVPO update this context is a member of (host_cvpo_group.inc)
-    struct fsrl_collect_group* cgroup = nullptr;     // the replay agents' collect group this context is a member of (host_collect_group.inc)
+    struct fsrl_collect_group* cgroup = nullptr;     // the collect group this context is a member of (host_collect_group.inc: replay or on-policy members)
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)

@@ -1,7 +1,7 @@
 // host_actor_ring.inc -- the pinned ring of a resident actor kernel that serves SEVERAL contexts from one launch and one doorbell
 // (part of fsrl_hip.hip, before host_group.inc).  Two owners embed a GaRing: fsrl_group (host_group_collect.inc: on-policy members,
 // actor_group_resident_kernel<H, false>) and fsrl_collect_group (host_collect_group.inc: replay members,
-// actor_group_resident_kernel<H, true>).  The owner supplies the stream the kernel runs on and the launch itself; the protocol --
+// actor_group_resident_kernel<H, true>; on-policy members that keep their own streams, <H, false>).  The owner supplies the stream the kernel runs on and the launch itself; the protocol --
 // request / wait / release, generation and sequence numbers, the bounded wait -- is resident_ring.hpp's, the one a context's own
 // kernel runs, with 1 in the command word and a per-member row count k_m next to the doorbell.  Here: the layout, the request's rows
 // and the lock-step collect step both owners' entry points run (ga_collect_step).

@@ -297,13 +297,9 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
 static int lay_collect_group_step(fsrl_collect_group* g, const GaStepArgs& a) {
     const int n = (int)g->m.size(), Do = g->m[0]->cfg.obs_dim, Da = g->m[0]->cfg.act_dim, cols = g->raw_cols;
     auto post = [&]() -> int {
-        if (g->reorder) {
-            for (int i = 0; i < n; ++i) {
-                HIPCHK(hipEventRecord(g->ready[(size_t)i], g->m[i]->compute));
-                HIPCHK(hipStreamWaitEvent(g->stream, g->ready[(size_t)i], 0));
-            }
-            g->reorder = false;
-        }
+        std::lock_guard<std::mutex> lock(g->mu);                    // `reorder` is the release hook's, on any thread
+        const int ro = collect_group_reorder(g);
+        if (ro) return ro;
         fsrl_ctx* c0 = g->m[0];
         const SacState* s0 = sac_of(c0);
         return lay_group_collect_stage(

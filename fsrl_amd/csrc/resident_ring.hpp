@@ -1,6 +1,6 @@
 // resident_ring.hpp -- the host half of the protocol of a resident actor kernel (actor_resident_kernel and
 // actor_group_resident_kernel, kernels_mlp.hpp), once, for every owner: a context's own kernel (fsrl_hip.hip), an on-policy group's
-// (host_group_collect.inc) and a replay collect group's (host_collect_group.inc).  No HIP in here: the owner supplies the three
+// (host_group_collect.inc) and a collect group's (host_collect_group.inc).  No HIP in here: the owner supplies the three
 // protocol words in its pinned memory and two hooks -- launch a generation, and ask the kernel's stream -- so the same code runs
 // against a kernel made of host threads (tests/host/resident_ring_sim.cpp).
 //   request: [wait until every workgroup of the last generation has stored its end] -> launch generation g if none is live -> ring
@@ -12,6 +12,7 @@
 #pragma once
 #include <stdint.h>
 #include <chrono>
+#include <mutex>
 
 #define RR_MAX_MEMBERS 16
 #define RR_EXIT 0xFFFFFFFFu                     // the command word that ends the kernel
@@ -54,6 +55,17 @@ static inline void rr_release(ResidentRing& r) {
     if (!r.live) return;
     rr_command(r, RR_EXIT);
     r.live = false;
+}
+
+// Release from any number of host threads at once (a collect group's hook, host_collect_group.inc: its members' entry points run on
+// threads of their own and every one of them releases the SAME ring).  Under the owner's mutex one thread tests `live`, rings EXIT and
+// clears `live`, so a live generation hears exactly one EXIT and `seq` never repeats; `also()` runs under the same lock (the owner's
+// own mark).  A host lock only: nothing waits for the kernel.  The owner takes the same mutex around its requests and waits.
+template <class F>
+static inline void rr_release_guarded(ResidentRing& r, std::mutex& mu, F&& also) {
+    std::lock_guard<std::mutex> lock(mu);
+    rr_release(r);
+    also();
 }
 
 // how many workgroups of generation gen have ended

@@ -79,6 +79,7 @@ class Engine:
     def __init__(self, cfg: EngineConfig, device: int = 0):
         self.lib = _lib.load()
         self.cfg = cfg
+        self.device = int(device)
         self._ctx = C.c_void_p()
         ccfg = cfg.to_c()
         _lib.check(self.lib.fsrl_ctx_create(int(device), C.byref(ccfg), C.byref(self._ctx)))
@@ -927,6 +928,10 @@ class EngineCollectGroup(_LockStepCollect):
     GroupCollector(engine_collect_group, collectors) drives it.
     The members (of any of the three kinds) may all be layered contexts of one `hidden_sizes`: the group then has no
     resident kernel -- a request is one launch sequence (L + 2 launches) for all members, actor_set_resident is accepted and has no
-    effect, actor_release does nothing and actor_resident_stats counts the requests."""
+    effect, actor_release does nothing and actor_resident_stats counts the requests.
+    A fourth kind of member is the on-policy engine that keeps its own streams: CPO and TRPO-Lag engines (which may share a group:
+    only the actor matters here), PPO-Lag or FOCOPS engines outside an EngineGroup -- fused or layered, never mixed with replay
+    engines.  Their updates stay their own (tr_begin / cpo_learn / trpo_learn) and may run on one host thread per member at once
+    (fsrl_amd.policy.TrustPolicyGroup); a member's call that runs during a collect_step of its group is a caller error."""
     _symbols = "fsrl_collect_group"
     _collect_step_symbol = "fsrl_collect_group_step"

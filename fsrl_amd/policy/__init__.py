@@ -15,4 +15,5 @@ install(__name__, globals(), {
     "SACPolicyGroup": "grouped_sac",
     "DDPGPolicyGroup": "grouped_ddpg",
     "CVPOPolicyGroup": "grouped_cvpo",
+    "TrustPolicyGroup": "grouped_trust",
 })

@@ -77,20 +77,33 @@ class TRPOLagrangian(LagrangianPolicy):
         self._pending = DeviceBatch(self.engine, n, 0)
         return self._pending
 
-    def learn(self, batch, batch_size: int = 99999, repeat: int = 4, **kwargs: Any):
-        """trpo_lag.py:173-251 on the device = `fsrl_trpo_learn[_mb]`; `batch` is what process_fn returned."""
+    # learn() in three parts, so that fsrl_amd.policy.TrustPolicyGroup can run the device part of k policies on k threads while
+    # everything that touches a host random stream or the logger stays on the calling thread, in member order
+    def _learn_prepare(self, batch, batch_size: int, repeat: int) -> dict:
+        """host, before the device: takes the pending batch, reads the multiplier, draws learn's permutations from numpy's stream"""
         assert isinstance(batch, DeviceBatch) and batch is getattr(self, "_pending", None), \
             "learn() takes the DeviceBatch the last process_fn() returned (the processed batch lives in HBM)"
         self._pending = None
-        eng, n = self.engine, batch.n
+        n = batch.n
         lags, rescaling = self.lagrangians_and_rescaling() if self.use_lagrangian else ([], 1.0)
         # Batch.split(batch_size, merge_last=True) inside learn (trpo_lag.py:177-178) draws one np.random.permutation per
         # repeat from numpy's global stream -- also when one minibatch covers the batch (then the order only moves sums and
         # the device keeps store order)
         perms = [np.random.permutation(n) for _ in range(repeat)] if n > 0 else None
         sizes = _split_sizes(n, batch_size)
-        stats = (eng.trpo_learn(lags, rescaling, repeat, batch_size=batch_size, perms=perms if len(sizes) > 1 else None)
-                 if n > 0 else np.zeros((0, 11), np.float32))
+        return dict(n=n, repeat=repeat, batch_size=batch_size, sizes=sizes, perms=perms if len(sizes) > 1 else None,
+                    lags=lags, rescaling=rescaling)
+
+    def _learn_device(self, plan: dict):
+        """library calls only (ctypes releases the GIL inside them): -> (stats rows, line-search evaluations per row)"""
+        if plan["n"] <= 0:
+            return np.zeros((0, 11), np.float32), np.zeros(0, np.int32)
+        stats = self.engine.trpo_learn(plan["lags"], plan["rescaling"], plan["repeat"], batch_size=plan["batch_size"],
+                                       perms=plan["perms"])
+        return stats, self.engine.tr_linesearch_evals(cap=len(stats) + 1)
+
+    def _learn_finish(self, plan: dict, stats, evals):
+        """host, after the device: the logged rows, the reference's wasted torch draws, the stale mark"""
         for row in stats:
             d = dict(zip(TRPO_KEYS, (float(v) for v in row)))
             kl, step, ent = d.pop("loss/kl"), d.pop("loss/step_size"), d.pop("loss/entropy")
@@ -98,12 +111,17 @@ class TRPOLagrangian(LagrangianPolicy):
             self.logger.store(**d)
             self.logger.store(kl=kl, step_size=step, entropy=ent, tab="loss")
         self.logger.store(gradient_steps=self.gradient_steps, tab="update")
-        if n > 0:   # process_fn: one forward over the batch; per minibatch: 2 forward(s) + one per line-search evaluation
-            self._burn(n, 1)
-            for rows, ev in zip(sizes * repeat, eng.tr_linesearch_evals(cap=len(stats) + 1)):
+        if plan["n"] > 0:   # process_fn: one forward over the batch; per minibatch: 2 forward(s) + one per line-search evaluation
+            self._burn(plan["n"], 1)
+            for rows, ev in zip(plan["sizes"] * plan["repeat"], evals):
                 self._burn(rows, 2 + int(ev))
         self._mark_stale()                                       # host mirror refreshed on demand
         return {"gradient_steps": len(stats)}
+
+    def learn(self, batch, batch_size: int = 99999, repeat: int = 4, **kwargs: Any):
+        """trpo_lag.py:173-251 on the device = `fsrl_trpo_learn[_mb]`; `batch` is what process_fn returned."""
+        plan = self._learn_prepare(batch, batch_size, repeat)
+        return self._learn_finish(plan, *self._learn_device(plan))
 
     def update(self, sample_size: int, buffer, batch_size: int = 99999, repeat: int = 4, **kwargs: Any):
         """base_policy.py:332-355: sample(0) -> process_fn -> learn -> lr scheduler"""

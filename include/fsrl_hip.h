@@ -664,8 +664,8 @@ int fsrl_cvpo_group_destroy(fsrl_cvpo_group* g);
  * next work.                                                                                                                */
 int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t* n_updates);
 
-/* ---- Lock-step collection for replay-agent seeds: k SAC-Lag, k DDPG-Lag or k CVPO contexts (FSRL_ALGO_SAC_LAG after
- *      fsrl_sac_init / fsrl_cvpo_init) on one device collect with ONE call and ONE request per vector step to one resident actor
+/* ---- Lock-step collection for seeds that keep their own streams: k SAC-Lag, k DDPG-Lag or k CVPO contexts (FSRL_ALGO_SAC_LAG
+ *      after fsrl_sac_init / fsrl_cvpo_init), or k on-policy contexts (see ON-POLICY members below), on one device collect with ONE call and ONE request per vector step to one resident actor
  *      kernel (a workgroup per member and 16-row tile, running the member's actor network; raw head rows come back through a
  *      pinned ring).  Per member every result is bit-identical to fsrl_collect_step on that member: its own store and side
  *      stream, its own noise stream, its own bounds.  The object is independent of the update groups: a member may also be in an
@@ -682,10 +682,22 @@ int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t batch_size, const int32_t
  *      completion words in pinned memory -- L + 2 launches per vector step instead of k (L + 2), any row count per member.  The
  *      releases listed above mark such a group instead of ending a kernel: its next request first waits for everything the
  *      members have enqueued on their compute streams; requests between two releases are ordered by the group's stream alone.
- *      create rejects with FSRL_EINVAL and the reason in fsrl_last_error: on-policy contexts (fsrl_group_create is theirs),
- *      a mix of fused and layered contexts, contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds,
- *      another device or network shape (obs_dim, act_dim, hidden; layered: hidden_sizes[], force_layered), a member listed twice or
- *      already in a collect group, k outside 1..16.
+ *      ON-POLICY members.  The fourth kind of member is an on-policy context: CPO, TRPO-Lag, or a PPO-Lag / FOCOPS context that is
+ *      not in an fsrl_group (one that is shares that group's stream and collects through fsrl_group_collect_step).  Only the actor
+ *      matters to this object and every on-policy actor is the same Gaussian actor, so CPO and TRPO-Lag members may share a group;
+ *      on-policy and replay members do not mix.  Fused members are served by the resident kernel of fsrl_group_collect_step (the
+ *      on-policy head: means and the member's sigma_param row) with member 0's max_action, layered members by that call's L + 2
+ *      launches, both with the ordering described above; nothing on the update side is grouped -- the members run their own
+ *      fsrl_tr_begin / fsrl_cpo_learn / fsrl_trpo_learn (fsrl_ppo_update ...), each on its own streams.
+ *      THREADS.  Members' entry points may run on several host threads at once (one thread per member's update): the release they
+ *      all perform on this group's kernel is serialised inside the library, and it still waits for nothing on the device.  A member's
+ *      entry point that runs CONCURRENTLY WITH A STEP of its collect group remains a caller error: the step would answer with
+ *      parameters in the middle of a change.  Finish the step first, or the members' calls first.
+ *      create rejects with FSRL_EINVAL and the reason, naming the member, in fsrl_last_error: a mix of on-policy and replay
+ *      contexts, a mix of fused and layered contexts, another device, another network shape (obs_dim, act_dim, hidden; layered:
+ *      hidden_sizes[], force_layered; on-policy: n_critics, which places the actor's parameters), a member listed twice or already
+ *      in a collect group, k outside 1..16; replay members: contexts without fsrl_sac_init / fsrl_cvpo_init, mixed kinds, another
+ *      actor_mean; on-policy members: a member of an fsrl_group, another max_action, another `unbounded`.
  *      A member destroyed before its group breaks it: later steps fail with FSRL_ESTATE, fsrl_collect_group_destroy still works. */
 typedef struct fsrl_collect_group fsrl_collect_group;
 int fsrl_collect_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_collect_group** out);

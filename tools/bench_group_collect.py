@@ -18,7 +18,11 @@ launches per collect; the loop is lock-step collection + round(0.2 * n/st) updat
 one launch sequence (L + 2 launches) for all members against k (L + 2) member by member, and launches_per_collect counts requests.
 With --hidden the DDPG-Lag loop updates through DDPGPolicyGroup as the SAC-Lag loop does through SACPolicyGroup.
 
-    python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3] [--hidden 256x256x256]
+--algo cpo | trpol: trust-region seeds in the same collect group (on-policy members: the PPO-Lag group's actor kernel, launched from a
+group whose members keep their own streams), fused or --hidden.  The same modes and figures; the loop is lock-step collection + ONE
+TrustPolicyGroup.update(repeat=4) per collect (the seeds' own full-batch updates on a thread each) + reset_buffer.
+
+    python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3] [--hidden 256x256x256] [--out profiles/x.json]
 """
 import argparse
 import json
@@ -33,8 +37,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def _agents(k, envs, first_seed, device, algo="ppol", hidden=None):
-    from fsrl_amd.agent import CVPOAgent, DDPGLagAgent, PPOLagAgent, SACLagAgent
-    Agent = {"ppol": PPOLagAgent, "sacl": SACLagAgent, "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}[algo]
+    from fsrl_amd.agent import CPOAgent, CVPOAgent, DDPGLagAgent, PPOLagAgent, SACLagAgent, TRPOLagAgent
+    Agent = {"ppol": PPOLagAgent, "sacl": SACLagAgent, "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent, "cpo": CPOAgent,
+             "trpol": TRPOLagAgent}[algo]
     from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
     from fsrl_amd.env import SyntheticSafetyVectorEnv
     from fsrl_amd.utils import BaseLogger
@@ -73,11 +78,21 @@ def _call_us(fn, n):
     return (time.perf_counter() - t) / n * 1e6
 
 
+def _emit(a, res):
+    line = json.dumps(res)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def _replay(a):
-    """--algo sacl / ddpgl / cvpo: the collect group of the replay agents"""
+    """--algo sacl / ddpgl / cvpo: the collect group of the replay agents; --algo cpo / trpol: the same object over on-policy members"""
     from fsrl_amd.data import GroupCollector
     from fsrl_amd.engine import EngineCollectGroup
-    from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
+    from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup, TrustPolicyGroup
+    trust = a.algo in ("cpo", "trpol")
     n_ep = a.envs
     res = {"algo": a.algo, "envs": a.envs, "hidden": "x".join(str(w) for w in a.hidden) if a.hidden else 256, "rounds": a.rounds, "k": {}}
     for k in [int(x) for x in a.ks.split(",")]:
@@ -114,8 +129,9 @@ def _replay(a):
         cg.actor_release()
         out["group_call_over_member_call"] = round(out["us_group_call"] / out["us_member_call"], 3)
         # collect + update, the training loop's shape (examples/train_multi_seed.py --grouped): update_per_step 0.2
-        group_cls = {"sacl": SACPolicyGroup, "cvpo": CVPOPolicyGroup, "ddpgl": DDPGPolicyGroup if a.hidden else None}[a.algo]
-        group = group_cls([ag.policy for ag in grp_agents]) if group_cls else None
+        group_cls = {"sacl": SACPolicyGroup, "cvpo": CVPOPolicyGroup, "ddpgl": DDPGPolicyGroup if a.hidden else None,
+                     "cpo": TrustPolicyGroup, "trpol": TrustPolicyGroup}[a.algo]
+        group = group_cls([ag.policy for ag in grp_agents], **({"collect_group": cg} if trust else {})) if group_cls else None
         steps, updates = 0, 0
         t0 = time.perf_counter()
         for _ in range(2):
@@ -124,8 +140,12 @@ def _replay(a):
             for ag, st in zip(grp_agents, sts):
                 ag.policy.pre_update_fn(stats_train=st)
                 steps += st["n/st"]
-                n.append(round(0.2 * st["n/st"]))
-            if group is not None:
+                n.append(1 if trust else round(0.2 * st["n/st"]))
+            if trust:
+                group.update(grp_bufs, batch_size=99999, repeat=4)
+                for c in grp_cols:
+                    c.reset_buffer(keep_statistics=True)
+            elif group is not None:
                 group.update(grp_bufs, batch_size=256, n_updates=n)
             else:
                 for ag, buf, n_i in zip(grp_agents, grp_bufs, n):
@@ -144,21 +164,22 @@ def _replay(a):
         for ag in solo_agents + grp_agents:
             ag.policy.engine.close()
         print(f"k={k}: {json.dumps(out)}", file=sys.stderr, flush=True)
-    print(json.dumps(res))
+    _emit(a, res)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=("ppol", "sacl", "ddpgl", "cvpo"), default="ppol")
+    ap.add_argument("--algo", choices=("ppol", "sacl", "ddpgl", "cvpo", "cpo", "trpol"), default="ppol")
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
-                    help="--algo sacl | ddpgl | cvpo: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
+                    help="--algo sacl | ddpgl | cvpo | cpo | trpol: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file (profiles/...)")
     a = ap.parse_args()
-    assert a.hidden is None or a.algo in ("sacl", "ddpgl", "cvpo"), "--hidden: the replay agents' layered collect groups (--algo sacl | ddpgl | cvpo)"
+    assert a.hidden is None or a.algo != "ppol", "--hidden: the layered collect groups (--algo sacl | ddpgl | cvpo | cpo | trpol)"
     if a.algo != "ppol":
         return _replay(a)
     from fsrl_amd.data import GroupCollector
@@ -221,7 +242,7 @@ def main():
         for ag in solo_agents + grp_agents:
             ag.policy.engine.close()
         print(f"k={k}: {json.dumps(out)}", file=sys.stderr, flush=True)
-    print(json.dumps(res))
+    _emit(a, res)
 
 
 if __name__ == "__main__":
