@@ -46,6 +46,11 @@ update side.  Per seed bit-identical to collecting and updating the seeds one af
 tools/bench_group_collect.py --algo cpo).  Fused and layered --hidden-sizes.
     python examples/train_multi_seed.py --algo cpo --seeds 8 --epoch 2 --grouped
     python examples/train_multi_seed.py --algo trpol --seeds 4 --epoch 2 --grouped --hidden-sizes 64x48x32
+--workers W [--busy-us U] (every mode): each seed's envs live in W worker processes (fsrl_amd.env.ShmemVectorEnv), an env step costing U
+microseconds of host time.  --grouped then runs a whole collect of all seeds as ONE library call (GroupCollector's native loop ->
+fsrl_group_collect_episodes / fsrl_collect_episodes_group): every seed's step command is posted to its workers before the first is
+waited for, so k seeds pay one env-step time per vector step, not k (tools/bench_group_collect.py --workers).
+    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped --workers 2 --busy-us 100
 """
 import argparse
 import os
@@ -56,11 +61,19 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fsrl_amd.agent import CPOAgent, CVPOAgent, DDPGLagAgent, FOCOPSAgent, PPOLagAgent, SACLagAgent, TRPOLagAgent  # noqa: E402
-from fsrl_amd.env import SyntheticSafetyVectorEnv  # noqa: E402
+from fsrl_amd.env import ShmemVectorEnv, SyntheticSafetyVectorEnv  # noqa: E402
 from fsrl_amd.utils import BaseLogger  # noqa: E402
 
 AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops": FOCOPSAgent, "sacl": SACLagAgent,
           "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent}
+def make_env(a, seed):
+    """a seed's vector env: in-process, or --workers W worker processes (ShmemVectorEnv; --busy-us: host time of one env step).
+    Over worker-process envs a grouped collect is ONE library call and the seeds' workers step at the same time."""
+    if a.workers:
+        return ShmemVectorEnv(env_num=a.envs, workers=a.workers, obs_dim=8, act_dim=2, episode_len=300, seed=seed, busy_us=a.busy_us)
+    return SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+
+
 GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo", "cpo", "trpol")      # what --grouped takes
 
 
@@ -72,7 +85,7 @@ def run_grouped_trust(a):
     from fsrl_amd.policy import TrustPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+        env = make_env(a, seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
         agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
@@ -107,6 +120,8 @@ def run_grouped_trust(a):
     cgroup.close()
     for ag in agents:
         ag.policy.engine.close()
+    for col in cols:
+        col.env.close()
 
 
 def run_grouped_replay(a):
@@ -119,7 +134,7 @@ def run_grouped_replay(a):
     from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+        env = make_env(a, seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
         agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
@@ -157,6 +172,8 @@ def run_grouped_replay(a):
     group.close()
     for ag in agents:
         ag.policy.engine.close()
+    for col in cols:
+        col.env.close()
 
 
 def run_grouped(a):
@@ -171,7 +188,7 @@ def run_grouped(a):
     from fsrl_amd.policy import PolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+        env = make_env(a, seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
         agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
@@ -205,6 +222,8 @@ def run_grouped(a):
     group.close()
     for ag in agents:
         ag.policy.engine.close()
+    for col in cols:
+        col.env.close()
 
 
 def is_layered(hidden_sizes):
@@ -224,7 +243,12 @@ def parse_args(argv=None):
     ap.add_argument("--hidden-sizes", default="128x128", type=lambda t: tuple(int(w) for w in t.lower().split("x")),
                     help="hidden layers of every network, e.g. 64x48x32 (anything but two layers of at most 256 units runs the "
                          "layered kernels; --grouped takes such PPO-Lag, SAC-Lag, DDPG-Lag, CPO and TRPO-Lag seeds too, not FOCOPS or CVPO seeds)")
+    ap.add_argument("--workers", type=int, default=0, help="worker processes per seed's env (one ShmemVectorEnv per seed); 0: in-process envs. "
+                                                           "--grouped then collects with one library call per collect for all seeds")
+    ap.add_argument("--busy-us", type=float, default=0.0, help="--workers: host time of one env step in microseconds (a simulator's stand-in)")
     a = ap.parse_args(argv)
+    if a.workers < 0 or a.workers > a.envs:
+        ap.error("--workers: 0 (in-process envs) .. --envs")
     if isinstance(a.hidden_sizes, str):
         a.hidden_sizes = tuple(int(w) for w in a.hidden_sizes.lower().split("x"))
     if a.grouped and a.algo in ("focops", "cvpo") and is_layered(a.hidden_sizes):
@@ -239,8 +263,9 @@ def main():
         return run_grouped(a)
 
     def run(seed):
+        env = None
         try:
-            env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+            env = make_env(a, seed)
             logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
             agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                    training_num=a.envs)
@@ -254,6 +279,9 @@ def main():
             out[seed] = {k: round(float(v), 3) for k, v in stat.items() if k in ("train/reward", "train/cost", "update/env_step")}
         except Exception as e:      # a failing seed must not hang the others
             errs.append((seed, repr(e)))
+        finally:
+            if env is not None:
+                env.close()
 
     t0 = time.time()
     threads = [threading.Thread(target=run, args=(s, )) for s in range(a.seeds)]

@@ -140,6 +140,10 @@ SIGNATURES = {
     "fsrl_collect_group_actor_set_resident": (C.c_int, [_ctx, C.c_int32, C.c_double]),
     "fsrl_collect_group_actor_resident_stats": (C.c_int, [_ctx, _i64]),
     "fsrl_collect_group_actor_release": (C.c_int, [_ctx]),
+    "fsrl_group_collect_episodes": (C.c_int, [_ctx, _P(_P(ShmEnv)), _i32, _i32, _f, _i32, C.c_int32, C.c_int32, _f, _f, _i64, _d, _i32,
+                                              _i32, _d, _i32, _i32, _d, _i32]),
+    "fsrl_collect_episodes_group": (C.c_int, [_ctx, _P(_P(ShmEnv)), _i32, _i32, _f, _i32, C.c_int32, C.c_int32, _f, _f, _i64, _d, _i32,
+                                              _i32, _d, _i32, _i32, _d, _i32]),
     "fsrl_gae_return": (C.c_int, [_ctx, _f, _f, _d, _u8, C.c_int64, C.c_double, C.c_double, _d]),
     "fsrl_nstep_return": (C.c_int, [_ctx, _d, _u8, C.c_int64, _f, _i64, C.c_int64, C.c_int64, C.c_double, C.c_int32, _d]),
     "fsrl_launch_floors": (C.c_int, [_ctx, C.c_int32, C.c_int32, _d]),

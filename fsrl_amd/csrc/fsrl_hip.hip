@@ -1509,6 +1509,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_collect_group.inc"
 #include "host_sac_group_layered.inc"
 #include "host_cvpo_group_layered.inc"
+#include "host_group_episodes.inc"
 
 #include "host_comm.inc"
 

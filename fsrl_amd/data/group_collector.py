@@ -9,7 +9,12 @@ PPO-Lagrangian seeds, by one sequence of L + 2 launches carrying every member's 
 FastCollector._collect_fused's interpreted loop -- episode counts, resets of finished envs, surplus envs dropped, fill levels, the
 collector's counters, `reset_env` at the end -- and the library calls a member sees are the ones its own collect would make, so the
 stored rows, the actions and the member's noise stream are the same bit for bit.  A member that has its episodes stops contributing
-rows while the others go on."""
+rows while the others go on.
+
+When every member's env is a worker-process env (`native_desc`: ShmemVectorEnv) the whole collect is ONE library call
+(`collect_episodes` -> fsrl_group_collect_episodes / fsrl_collect_episodes_group): the same loop in C, with the step and reset
+commands of all members posted to their workers before the first is waited for -- the interpreted loop below steps member 0's env,
+waits, steps member 1's ... and so pays k env-step times per vector step.  `native_loop=False` keeps the interpreted loop."""
 import time
 from typing import Any, Dict, List, Sequence, Union
 
@@ -17,11 +22,12 @@ import numpy as np
 
 
 class GroupCollector:
-    def __init__(self, policy_group, collectors: Sequence):
+    def __init__(self, policy_group, collectors: Sequence, native_loop: bool = True):
         # policy_group: a PolicyGroup (its EngineGroup is used), an EngineCollectGroup (replay agents) or anything with
         # EngineGroup's collect_step / actor_release
         self.group = getattr(policy_group, "group", policy_group)
         self.collectors = list(collectors)
+        self.native_loop = bool(native_loop)
         engines = getattr(self.group, "engines", None)
         assert self.collectors, "a group collector needs at least one collector"
         for i, col in enumerate(self.collectors):
@@ -67,6 +73,8 @@ class GroupCollector:
         det, bound = dets[0], bounds[0]
         low = None if lows[0] is None else np.stack(lows)
         high = None if lows[0] is None else np.stack(highs)
+        if self.native_loop and hasattr(self.group, "collect_episodes") and all(hasattr(c.env, "native_desc") for c in cols):
+            return self._collect_native(mem, ns, t0, det, bound, low, high)
         out = self.group.collect_step([None] * n, [m["obs"] for m in mem], det, bound, low, high)
         for m, o in zip(mem, out):
             m["act"], m["env_act"] = o[0], o[1]
@@ -131,4 +139,39 @@ class GroupCollector:
             stats.append({"n/ep": m["episodes"], "n/st": m["steps"], "rew": float(rews.mean()), "len": float(lens.mean()),
                           "total_cost": m["cost"], "cost": m["cost"] / m["episodes"], "truncated": m["trunc"] / done_count,
                           "terminated": m["term"] / done_count})
+        return stats
+
+    def _collect_native(self, mem, ns, t0, det, bound, low, high):
+        """worker-process envs: the whole collect of every member in one library call; afterwards, per member, what
+        FastCollector._collect_native does.  A failed call may have left a command half-handled on the failing member's env only
+        (the library waits for the others'): that env refuses every later command, the others stay usable."""
+        cols = self.collectors
+        descs = [col.env.native_desc() for col in cols]
+        try:
+            res = self.group.collect_episodes(descs, [m["ready"] for m in mem], [m["obs"] for m in mem], ns, det, bound, low, high)
+        except BaseException as e:
+            bad = getattr(e, "failed_member", -1)
+            for col in cols:
+                col.env.sync_native()
+            # an argument error (AssertionError): nothing was posted to any env.  A failed step call names no member: env commands are
+            # waited for before a step call, so none is in flight then
+            if 0 <= bad < len(cols) and not isinstance(e, AssertionError):
+                cols[bad].env.mark_broken("a native group collect failed while env commands were in flight")
+            if bad >= 0 and e.args:
+                e.args = (f"GroupCollector, member {bad}: {e.args[0]}", ) + tuple(e.args[1:])
+            raise
+        dt = max(time.time() - t0, 1e-9)
+        stats = []
+        for col, r in zip(cols, res):
+            col.env.sync_native()
+            col.buffer.sync_sizes()
+            col.collect_step += r["steps"]
+            col.collect_episode += len(r["ep_rews"])
+            col.collect_time += dt
+            col.reset_env()
+            done_count = r["terminated"] + r["truncated"]
+            stats.append({"n/ep": len(r["ep_rews"]), "n/st": r["steps"], "rew": float(r["ep_rews"].mean()),
+                          "len": float(r["ep_lens"].mean()), "total_cost": r["total_cost"],
+                          "cost": r["total_cost"] / len(r["ep_rews"]), "truncated": r["truncated"] / done_count,
+                          "terminated": r["terminated"] / done_count})
         return stats

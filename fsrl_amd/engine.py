@@ -801,6 +801,52 @@ class _LockStepCollect(_NativeGroup):
             o += k; oa_ += ka
         return out
 
+    def collect_episodes(self, env_descs, readys, obs, n_episodes, deterministic=False, bound_method=1, low=None, high=None):
+        """GroupCollector.collect(n_episode) over worker-process envs in ONE C call (fsrl_group_collect_episodes for an EngineGroup,
+        fsrl_collect_episodes_group for an EngineCollectGroup): Engine.collect_episodes of every member, the members' envs stepped
+        together, one collect_step per vector step.  env_descs / readys / obs / n_episodes: one entry per member; low / high: None,
+        one array for every member or a per-member list.
+        -> per member dict(steps, total_cost, terminated, truncated, ep_rews, ep_lens, t_env, t_act) (t_*: the group's).
+        An error carries `failed_member`: the member an argument error names, or the one whose env failed (-1: none)."""
+        engs = self.engines
+        k = len(engs)
+        assert len(env_descs) == k and len(readys) == k and len(obs) == k and len(n_episodes) == k, "one entry per member"
+        Do, Da = engs[0].cfg.obs_dim, engs[0].cfg.act_dim
+        descs = (C.POINTER(_lib.ShmEnv) * k)(*[C.pointer(d) for d in env_descs])
+        n = np.array([len(r) for r in readys], np.int32)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(r, np.int32).reshape(-1) for r in readys]), np.int32)
+        ob = np.ascontiguousarray(np.concatenate([np.asarray(o, np.float32).reshape(len(r), -1) for o, r in zip(obs, readys)]), np.float32)
+        assert ob.shape[1] == Do, "obs: [n_i][obs_dim] per member"
+        ne = np.array([int(x) for x in n_episodes], np.int32)
+        lo = hi = None
+        if low is not None:
+            lo = np.empty((k, Da), np.float32); hi = np.empty((k, Da), np.float32)
+            lo[:] = np.asarray(low, np.float32).reshape(-1, Da); hi[:] = np.asarray(high, np.float32).reshape(-1, Da)
+        steps, cost = np.zeros(k, np.int64), np.zeros(k, np.float64)
+        nt, ntr, nep = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        cap = int(np.maximum(ne, 0).sum())
+        ep_rew, ep_len = np.zeros(max(cap, 1), np.float64), np.zeros(max(cap, 1), np.int32)
+        tm = np.zeros(2, np.float64)
+        failed = C.c_int32(-1)
+        rc = getattr(self.lib, self._collect_episodes_symbol)(
+            self._g, descs, _ptr(n, _i32p), _ptr(ids, _i32p), _ptr(ob, _f32p), _ptr(ne, _i32p), int(deterministic), int(bound_method),
+            _ptr(lo, _f32p) if lo is not None else None, _ptr(hi, _f32p) if hi is not None else None, _ptr(steps, _i64p),
+            _ptr(cost, _f64p), _ptr(nt, _i32p), _ptr(ntr, _i32p), _ptr(ep_rew, _f64p), _ptr(ep_len, _i32p), _ptr(nep, _i32p),
+            _ptr(tm, _f64p), C.byref(failed))
+        try:
+            _lib.check(rc)
+        except BaseException as e:
+            e.failed_member = int(failed.value)
+            raise
+        out, off = [], 0
+        for i in range(k):
+            j = int(nep[i])
+            out.append(dict(steps=int(steps[i]), total_cost=float(cost[i]), terminated=int(nt[i]), truncated=int(ntr[i]),
+                            ep_rews=ep_rew[off:off + j].copy(), ep_lens=ep_len[off:off + j].copy(), t_env=float(tm[0]),
+                            t_act=float(tm[1])))
+            off += int(ne[i])
+        return out
+
     def collect_step_outputs(self):
         """(ptr, ep_idx) of the rows the last collect_step stored, concatenated over members (views of the staging arrays)."""
         a = self._collect_stage["a"]
@@ -835,6 +881,7 @@ class EngineGroup(_LockStepCollect):
 
     _symbols = "fsrl_group"
     _collect_step_symbol = "fsrl_group_collect_step"
+    _collect_episodes_symbol = "fsrl_group_collect_episodes"
 
     def set_plan(self, tall_tiles=-1):
         """32-row tiles per (member, network) in the forward / backward launch: -1 automatic, 0 none, n > 0 a count (A/B; same bits)."""
@@ -935,3 +982,4 @@ class EngineCollectGroup(_LockStepCollect):
     (fsrl_amd.policy.TrustPolicyGroup); a member's call that runs during a collect_step of its group is a caller error."""
     _symbols = "fsrl_collect_group"
     _collect_step_symbol = "fsrl_collect_group_step"
+    _collect_episodes_symbol = "fsrl_collect_episodes_group"

@@ -720,6 +720,32 @@ int fsrl_collect_group_actor_resident_stats(fsrl_collect_group* g, int64_t* out3
 /* the collect is over: end the kernel now instead of at its idle timeout (a group of layered members: nothing to end)         */
 int fsrl_collect_group_actor_release(fsrl_collect_group* g);
 
+/* ---- a whole lock-step collect of a group over worker-process envs in ONE call: fsrl_collect_episodes of every member (the
+ *      reference's FastCollector.collect(n_episode), fsrl/data/fast_collector.py:283-368), the members' envs stepped TOGETHER --
+ *      every member's step (or reset) command is posted to its workers before the first one is waited for -- and one
+ *      fsrl_group_collect_step / fsrl_collect_group_step per vector step for all members.  Per member the same calls in the same
+ *      order as its own collect: same rows in the same slots, same noise stream.  A member that has its episodes contributes no
+ *      rows from then on while the others go on.
+ *      envs[k]: member m's env (no env twice); n[k]: its rows; ready / obs: the members' env ids / observations back to back, n[m]
+ *      rows each; n_episode[k] >= 1; act_low / act_high: NULL or [k][act_dim].  Outputs per member [k]: env steps, summed cost,
+ *      terminated / truncated counts, finished episodes; ep_rew_out / ep_len_out: n_episode[m] entries per member at prefix-sum
+ *      offsets, in the order the loop met them.  t_env_act_out2 (may be NULL): seconds spent waiting for the env workers /
+ *      in the step calls.  *failed_member_out: -1, or the member an argument error names (FSRL_EINVAL; nothing was posted or
+ *      launched), or the member whose env failed (a dead worker, a worker that raised): the commands posted to the other
+ *      members' envs have been waited for, the group's resident actor has ended and the group's and the members' streams are
+ *      drained; only that member's env may be left with a half-handled command.  On success the resident actor ends with the call.
+ *      Single-phase only (no counterpart of fsrl_collect_episodes_split).                                                    */
+int fsrl_group_collect_episodes(fsrl_group* g, fsrl_shm_env* const* envs, const int32_t* n, const int32_t* ready, const float* obs,
+                                const int32_t* n_episode, int32_t deterministic, int32_t bound_method, const float* act_low,
+                                const float* act_high, int64_t* steps_out, double* total_cost_out, int32_t* term_out,
+                                int32_t* trunc_out, double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out,
+                                double* t_env_act_out2, int32_t* failed_member_out);
+int fsrl_collect_episodes_group(fsrl_collect_group* g, fsrl_shm_env* const* envs, const int32_t* n, const int32_t* ready,
+                                const float* obs, const int32_t* n_episode, int32_t deterministic, int32_t bound_method,
+                                const float* act_low, const float* act_high, int64_t* steps_out, double* total_cost_out,
+                                int32_t* term_out, int32_t* trunc_out, double* ep_rew_out, int32_t* ep_len_out,
+                                int32_t* episodes_out, double* t_env_act_out2, int32_t* failed_member_out);
+
 /* ---- timing of the last update, measured with hipEvents on the compute stream --------- */
 /* out[0] = process_fn ms, out[1] = learn ms (all passes), out[2] = fused fwd/bwd kernel
  * total ms over the update (sum of per-launch event pairs when profiling is enabled),

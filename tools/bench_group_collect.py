@@ -22,7 +22,17 @@ With --hidden the DDPG-Lag loop updates through DDPGPolicyGroup as the SAC-Lag l
 group whose members keep their own streams), fused or --hidden.  The same modes and figures; the loop is lock-step collection + ONE
 TrustPolicyGroup.update(repeat=4) per collect (the seeds' own full-batch updates on a thread each) + reset_buffer.
 
+--workers W [--busy-us U] [--native 0|1] (every --algo): the members' envs are worker-process envs (one ShmemVectorEnv of W workers per
+member, an env step costing U microseconds of host time) and the legs are
+  interpreted     GroupCollector(native_loop=False): one library call per vector step, the members' envs stepped one after the other;
+  native          GroupCollector(native_loop=True): the whole collect in one library call (fsrl_group_collect_episodes /
+                  fsrl_collect_episodes_group), the members' workers stepping at the same time;
+  seq_native      k ungrouped seeds, each one's own FastCollector (fsrl_collect_episodes) in turn.
+--native 0 / 1 runs the interpreted / the native leg only.  k x W is capped at 14: the two sets of envs (grouped, ungrouped) never step
+at the same time, and a 16-CPU box keeps two CPUs for the collector.
+
     python tools/bench_group_collect.py [--algo ppol] [--ks 1,2,4,8] [--rounds 3] [--hidden 256x256x256] [--out profiles/x.json]
+    python tools/bench_group_collect.py --algo ppol --workers 2 --busy-us 100 --ks 1,2,4 --out profiles/group_episodes_collect.json
 """
 import argparse
 import json
@@ -36,16 +46,19 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _agents(k, envs, first_seed, device, algo="ppol", hidden=None):
+def _agents(k, envs, first_seed, device, algo="ppol", hidden=None, workers=0, busy_us=0.0):
     from fsrl_amd.agent import CPOAgent, CVPOAgent, DDPGLagAgent, PPOLagAgent, SACLagAgent, TRPOLagAgent
     Agent = {"ppol": PPOLagAgent, "sacl": SACLagAgent, "ddpgl": DDPGLagAgent, "cvpo": CVPOAgent, "cpo": CPOAgent,
              "trpol": TRPOLagAgent}[algo]
     from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
-    from fsrl_amd.env import SyntheticSafetyVectorEnv
+    from fsrl_amd.env import ShmemVectorEnv, SyntheticSafetyVectorEnv
     from fsrl_amd.utils import BaseLogger
     agents, cols, bufs = [], [], []
     for s in range(first_seed, first_seed + k):
-        env = SyntheticSafetyVectorEnv(env_num=envs, obs_dim=8, act_dim=2, episode_len=300, seed=s)
+        if workers:
+            env = ShmemVectorEnv(env_num=envs, workers=workers, obs_dim=8, act_dim=2, episode_len=300, seed=s, busy_us=busy_us)
+        else:
+            env = SyntheticSafetyVectorEnv(env_num=envs, obs_dim=8, act_dim=2, episode_len=300, seed=s)
         ag = Agent(env, BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_bgc{s}_"), name=f"s{s}"), cost_limit=10.0, device=device,
                    seed=s, hidden_sizes=hidden or (256, 256), training_num=envs)
         ag.policy.train()
@@ -85,6 +98,53 @@ def _emit(a, res):
         with open(a.out, "w") as f:
             f.write(line + "\n")
     print(line)
+
+
+def _workers(a):
+    """--workers: the members' envs are worker processes; interpreted / native lock-step collection and the seeds' own native collects"""
+    from fsrl_amd.data import GroupCollector
+    from fsrl_amd.engine import EngineCollectGroup
+    from fsrl_amd.policy import PolicyGroup
+    n_ep = a.envs
+    res = {"algo": a.algo, "envs": a.envs, "workers": a.workers, "busy_us": a.busy_us,
+           "hidden": "x".join(str(w) for w in a.hidden) if a.hidden else 256, "rounds": a.rounds, "k": {}}
+    legs = ["interpreted", "native", "seq_native"] if a.native is None else [["interpreted", "native"][a.native]]
+    for k in [int(x) for x in a.ks.split(",")]:
+        assert k * a.workers <= 14, f"k x workers = {k * a.workers}: at most 14 worker processes step at a time on a 16-CPU box"
+        solo_agents, solo_cols = [], []
+        if "seq_native" in legs:
+            solo_agents, solo_cols, _ = _agents(k, a.envs, 0, a.device, a.algo, a.hidden, a.workers, a.busy_us)
+        grp_agents, grp_cols, _ = _agents(k, a.envs, 0, a.device, a.algo, a.hidden, a.workers, a.busy_us)
+        if a.algo == "ppol":
+            group = PolicyGroup([ag.policy for ag in grp_agents])
+        else:
+            group = EngineCollectGroup([ag.policy.engine for ag in grp_agents])
+        gcs = {"interpreted": GroupCollector(group, grp_cols, native_loop=False), "native": GroupCollector(group, grp_cols, native_loop=True)}
+        run = {m: (lambda m=m: _seq(solo_cols, n_ep) if m == "seq_native" else _lock(gcs[m], grp_cols, n_ep)) for m in legs}
+        t = {m: [] for m in legs}
+        for m in legs:                                            # warm-up: code loading, first launches, the workers' first steps
+            run[m]()
+        for _ in range(a.rounds):
+            for m in legs:
+                t0 = time.perf_counter()
+                st = run[m]()
+                t[m].append(st / (time.perf_counter() - t0))
+        out = {m: round(float(np.median(v))) for m, v in t.items()}
+        out["all"] = {m: [round(x) for x in v] for m, v in t.items()}
+        out["spread"] = {m: round(max(v) - min(v)) for m, v in t.items()}
+        if "native" in out and "interpreted" in out:
+            out["native_over_interpreted"] = round(out["native"] / out["interpreted"], 3)
+        if "native" in out and "seq_native" in out:
+            out["native_over_seq_native"] = round(out["native"] / out["seq_native"], 3)
+        out["rows_per_member_per_collect"] = n_ep * 300
+        res["k"][str(k)] = out
+        group.close()
+        for ag in solo_agents + grp_agents:
+            ag.policy.engine.close()
+        for c in solo_cols + grp_cols:
+            c.env.close()
+        print(f"k={k}: {json.dumps(out)}", file=sys.stderr, flush=True)
+    _emit(a, res)
 
 
 def _replay(a):
@@ -178,8 +238,14 @@ def main():
     ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
                     help="--algo sacl | ddpgl | cvpo | cpo | trpol: hidden layers instead of 256x256, e.g. 256x256x256 or 64x48x32 (layered members)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file (profiles/...)")
+    ap.add_argument("--workers", type=int, default=0, help="worker processes per member's env (ShmemVectorEnv); 0: in-process envs")
+    ap.add_argument("--busy-us", type=float, default=0.0, help="--workers: host time of one env step, microseconds")
+    ap.add_argument("--native", type=int, choices=(0, 1), default=None,
+                    help="--workers: only the interpreted (0) or the native (1) lock-step leg; default: both and the seeds' own collects")
     a = ap.parse_args()
     assert a.hidden is None or a.algo != "ppol", "--hidden: the layered collect groups (--algo sacl | ddpgl | cvpo | cpo | trpol)"
+    if a.workers:
+        return _workers(a)
     if a.algo != "ppol":
         return _replay(a)
     from fsrl_amd.data import GroupCollector
