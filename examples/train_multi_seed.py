@@ -51,6 +51,12 @@ microseconds of host time.  --grouped then runs a whole collect of all seeds as 
 fsrl_group_collect_episodes / fsrl_collect_episodes_group): every seed's step command is posted to its workers before the first is
 waited for, so k seeds pay one env-step time per vector step, not k (tools/bench_group_collect.py --workers).
     python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped --workers 2 --busy-us 100
+--sweep NAME=v1,v2,... (repeatable; --grouped --algo ppol only; one value per seed): the members of the group are a SWEEP, member i
+running with value i of every swept PPOLagAgent keyword (eps_clip, dual_clip, vf_coef, max_grad_norm, target_kl, lr, gae_lambda,
+gamma, cost_limit; `none` switches dual_clip / target_kl off) and of batch_size / repeat_per_collect -- still one grouped update
+per collect (PolicyGroup.update with a batch size and a pass count per member -> fsrl_group_ppo_update_each).  The members must agree
+on whether max_grad_norm is on.  FOCOPS groups are not sweeps.
+    python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped --sweep eps_clip=0.1,0.2,0.2,0.3 --sweep batch_size=128,256,256,512
 """
 import argparse
 import os
@@ -72,6 +78,36 @@ def make_env(a, seed):
     if a.workers:
         return ShmemVectorEnv(env_num=a.envs, workers=a.workers, obs_dim=8, act_dim=2, episode_len=300, seed=seed, busy_us=a.busy_us)
     return SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+
+
+# --sweep: PPOLagAgent keywords (float; `none` where the agent takes None) and the two update arguments (int)
+SWEEP_AGENT_KEYS = ("eps_clip", "dual_clip", "vf_coef", "max_grad_norm", "target_kl", "lr", "gae_lambda", "gamma", "cost_limit")
+SWEEP_UPDATE_KEYS = ("batch_size", "repeat_per_collect")
+SWEEP_NONE_OK = ("dual_clip", "target_kl", "max_grad_norm")
+
+
+def parse_sweep(specs, k):
+    """--sweep NAME=v1,...,vk (repeatable) -> {name: [k values]}; ValueError with the message for ap.error"""
+    out = {}
+    for spec in specs or []:
+        name, eq, vals = spec.partition("=")
+        if not eq or name not in SWEEP_AGENT_KEYS + SWEEP_UPDATE_KEYS:
+            raise ValueError(f"--sweep {spec}: NAME=v1,v2,... with NAME one of {', '.join(SWEEP_AGENT_KEYS + SWEEP_UPDATE_KEYS)}")
+        if name in out:
+            raise ValueError(f"--sweep {name}: given twice")
+        vals = vals.split(",")
+        if len(vals) != k:
+            raise ValueError(f"--sweep {name}: {len(vals)} values for {k} seeds (one value per member)")
+        try:
+            if name in SWEEP_UPDATE_KEYS:
+                out[name] = [int(v) for v in vals]
+            else:
+                out[name] = [None if (v.lower() == "none" and name in SWEEP_NONE_OK) else float(v) for v in vals]
+        except ValueError:
+            raise ValueError(f"--sweep {spec}: not a number") from None
+        if name in SWEEP_UPDATE_KEYS and min(out[name]) < (1 if name == "batch_size" else 0):
+            raise ValueError(f"--sweep {name}: batch_size >= 1, repeat_per_collect >= 0")
+    return out
 
 
 GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo", "cpo", "trpol")      # what --grouped takes
@@ -190,13 +226,15 @@ def run_grouped(a):
     for seed in range(a.seeds):
         env = make_env(a, seed)
         logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
-                               training_num=a.envs)
+        kw = dict(cost_limit=10.0)
+        kw.update({name: vals[seed] for name, vals in a.sweep.items() if name in SWEEP_AGENT_KEYS})       # a sweep: member i's own values
+        agent = AGENTS[a.algo](env, logger, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes, training_num=a.envs, **kw)
         agent.policy.train()
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
     group = PolicyGroup([ag.policy for ag in agents])
+    batch_size, repeat = a.sweep.get("batch_size", 256), a.sweep.get("repeat_per_collect", 4)       # ints, or one int per member
     mult = (lambda p: f"nu {float(p._nu):.3f}") if a.algo == "focops" else (lambda p: f"lambda {p.lag_optims[0].get_lag():.3f}")
     gcol = GroupCollector(group, cols)
     t0, steps, updates = time.time(), 0, 0
@@ -208,7 +246,7 @@ def run_grouped(a):
                 ag.logger.store(**{"train/reward": st["rew"], "train/cost": st["cost"]})
                 steps += st["n/st"]
             budget -= st["n/st"]
-            group.update(bufs, batch_size=256, repeat=4)
+            group.update(bufs, batch_size=batch_size, repeat=repeat)
             updates += len(agents)
             for col in cols:
                 col.reset_buffer(keep_statistics=True)
@@ -246,7 +284,19 @@ def parse_args(argv=None):
     ap.add_argument("--workers", type=int, default=0, help="worker processes per seed's env (one ShmemVectorEnv per seed); 0: in-process envs. "
                                                            "--grouped then collects with one library call per collect for all seeds")
     ap.add_argument("--busy-us", type=float, default=0.0, help="--workers: host time of one env step in microseconds (a simulator's stand-in)")
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
+                    help="--grouped --algo ppol: member i runs with value i (one per seed) of a PPOLagAgent keyword ("
+                         + ", ".join(SWEEP_AGENT_KEYS) + ") or of " + " / ".join(SWEEP_UPDATE_KEYS) + "; repeatable")
     a = ap.parse_args(argv)
+    if a.sweep and not (a.grouped and a.algo == "ppol"):
+        ap.error("--sweep: PPO-Lagrangian groups only (--grouped --algo ppol); FOCOPS groups keep one set of hyper-parameters")
+    try:
+        a.sweep = parse_sweep(a.sweep, a.seeds)
+    except ValueError as e:
+        ap.error(str(e))
+    clip = a.sweep.get("max_grad_norm")
+    if clip and len({bool(v) for v in clip}) > 1:
+        ap.error("--sweep max_grad_norm: the members must agree on whether the clip is on (all values > 0, or all none / 0)")
     if a.workers < 0 or a.workers > a.envs:
         ap.error("--workers: 0 (in-process envs) .. --envs")
     if isinstance(a.hidden_sizes, str):

@@ -122,6 +122,7 @@ SIGNATURES = {
     "fsrl_group_set_plan": (C.c_int, [_ctx, C.c_int32]),
     "fsrl_group_ppo_update": (C.c_int, [_ctx, _d, _d, C.c_int32, C.c_int32, _P(_i64), C.c_uint64, _P(_f), C.c_int64, _i64,
                                         _i32]),
+    "fsrl_group_ppo_update_each": (C.c_int, [_ctx, _d, _d, _i32, _i32, _P(_i64), C.c_uint64, _P(_f), _i64, _i64, _i32]),
     "fsrl_group_collect_step": (C.c_int, [_ctx, _i32, _i32, _f, _f, _d, _d, _u8, _u8, _f, _i64, _d, _i32, _i64, _i32, _f, C.c_int32,
                                           C.c_int32, _f, _f, _f, _f]),
     "fsrl_group_actor_set_resident": (C.c_int, [_ctx, C.c_int32, C.c_double]),

@@ -244,7 +244,7 @@ static void collect_group_actor_release(struct fsrl_collect_group* g);   // that
 // grouped FOCOPS (host_focops_group.inc): the member checks of fsrl_group_create / _ppo_update, and the update itself
 static int focops_group_check(fsrl_ctx* const* ctxs, int k);
 struct GroupUpdate;                                 // the frame of a grouped on-policy update (host_group.inc)
-static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repeat);
+static int focops_group_update(GroupUpdate& u);
 #define ENTER_DEV(c) do { HIPCHK(hipSetDevice((c)->device)); pactor_release(c); } while (0)
 
 static int join_store(fsrl_ctx* c) {

@@ -36,7 +36,7 @@ static int focops_group_check(fsrl_ctx* const* ctxs, int k) {
     return 0;
 }
 
-static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repeat) {
+static int focops_group_update(GroupUpdate& u) {
     fsrl_group* g = u.g; fsrl_ctx* c0 = g->m[0];
     const int k = u.k; hipStream_t s = g->stream;
     int rc = focops_group_check(g->m.data(), k);
@@ -46,7 +46,7 @@ static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repea
     // ---- begin (FOCOPS: no multipliers, rescaling 1, as Engine.focops_update).  The layered step's launches read the PPO group's
     // tables too: per pass the step rows' active / mb_size / mb_start
     const double zero_lag[FSRL_MAX_CRITICS] = {};
-    rc = ogroup_begin(u, zero_lag, 0, nullptr, batch_size, true, layered);
+    rc = ogroup_begin(u, zero_lag, 0, nullptr, true, layered);
     if (rc) return rc;
     char fast[FSRL_MAX_GROUP] = {};
     for (int i = 0; i < k; ++i) {
@@ -72,7 +72,7 @@ static int focops_group_update(GroupUpdate& u, int32_t batch_size, int32_t repea
     const WgradBlocks wb = layered ? WgradBlocks{} : wgrad_blocks(c0->md.Do, H, false);
     const int passes = wb.passes, NB = wb.NB;
     std::vector<char> rows4;
-    for (int pass = 0; pass < repeat; ++pass) {
+    for (int pass = 0; pass < u.max_repeat; ++pass) {
         // ---- per member: permutation + batch preparation of this pass; split-K buffers for its largest minibatch
         rc = ogroup_pass_begin(u, pass, [&](int i, fsrl_ctx* c) {
             if (fast[i] || layered) return 0;

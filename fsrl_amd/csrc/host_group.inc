@@ -46,15 +46,29 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
         CHECK_ARG(c->device == c0->device, "members live on one device");
         CHECK_ARG(!c->in_update && !c->group, "member %d is inside an update or already grouped", i);
         const fsrl_config &a = c->cfg, &b = c0->cfg;
+        const bool ppo = c->cfg.algo == FSRL_ALGO_PPO_LAG;
+        CHECK_ARG(!ppo || a.n_critics == b.n_critics, "member %d: members must share n_critics (one set of networks per launch)", i);
         CHECK_ARG(a.obs_dim == b.obs_dim && a.act_dim == b.act_dim && a.n_critics == b.n_critics && (c->lay != nullptr) == (c0->lay != nullptr) &&
                   (c->lay ? lay_same_shape(a, b) : a.hidden == b.hidden),
-                  "members must have one network shape");
-        CHECK_ARG(a.eps_clip == b.eps_clip && a.dual_clip == b.dual_clip && a.vf_coef == b.vf_coef &&
-                  a.max_grad_norm == b.max_grad_norm && a.target_kl == b.target_kl && a.norm_adv == b.norm_adv &&
-                  a.use_lagrangian == b.use_lagrangian && a.beta1 == b.beta1 && a.beta2 == b.beta2 &&
-                  a.adam_eps == b.adam_eps && a.max_action == b.max_action && a.unbounded == b.unbounded &&
-                  a.rew_norm == b.rew_norm && a.value_clip == b.value_clip,
-                  "members must share the PPO hyper-parameters (learning rates, seeds and data may differ)");
+                  "member %d: members must have one network shape", i);
+        if (ppo) {
+            // A PPO-Lagrangian group may be a SWEEP: every member's own eps_clip, dual_clip, vf_coef, max_grad_norm value, target_kl,
+            // norm_adv, use_lagrangian, beta1 / beta2 / adam_eps, rew_norm and value_clip reach the kernels through its row of the
+            // member table (GroupAgent::hp) and its own host preparation.  What stays shared is what the launches themselves depend on.
+            CHECK_ARG(a.max_action == b.max_action, "member %d: members must share max_action (the shared collect kernel scales every member's actions by it)", i);
+            CHECK_ARG(a.unbounded == b.unbounded, "member %d: members must share unbounded (the shared collect kernel has one action head)", i);
+            CHECK_ARG((a.max_grad_norm > 0.0f) == (b.max_grad_norm > 0.0f),
+                      "member %d: members must agree on whether max_grad_norm is on (the step has 2 launches without the clip, 3 with it)", i);
+        } else {
+            // A FOCOPS group keeps the equality of every field: its kernels take their scalars from the FOCOPS step rows, and
+            // focops_group_check (below) asks for one l2_reg / delta / eta / tem_lambda / max_grad_norm per group.
+            CHECK_ARG(a.eps_clip == b.eps_clip && a.dual_clip == b.dual_clip && a.vf_coef == b.vf_coef &&
+                      a.max_grad_norm == b.max_grad_norm && a.target_kl == b.target_kl && a.norm_adv == b.norm_adv &&
+                      a.use_lagrangian == b.use_lagrangian && a.beta1 == b.beta1 && a.beta2 == b.beta2 &&
+                      a.adam_eps == b.adam_eps && a.max_action == b.max_action && a.unbounded == b.unbounded &&
+                      a.rew_norm == b.rew_norm && a.value_clip == b.value_clip,
+                      "members must share the PPO hyper-parameters (learning rates, seeds and data may differ)");
+        }
         for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member listed twice");
     }
     if (c0->cfg.algo == FSRL_ALGO_FOCOPS) {
@@ -136,14 +150,19 @@ extern "C" int fsrl_group_set_plan(fsrl_group* g, int32_t tall_tiles) {
 }
 
 // ---- the frame of one grouped on-policy update, the same for the PPO-Lagrangian update below and the FOCOPS update
-//      (host_focops_group.inc), fused and layered: fsrl_group_ppo_update -> the update's own pre-checks, ogroup_begin, per pass
+//      (host_focops_group.inc), fused and layered: fsrl_group_ppo_update_each (fsrl_group_ppo_update: the same call with its scalars
+//      repeated) -> the update's own pre-checks, ogroup_begin, per pass
 //      ogroup_pass_begin / the update's tables, their copies and the steps_copied event behind them / its launches / ogroup_pass_end ->
-//      every member's fsrl_ppo_end.  One error path, in fsrl_group_ppo_update: once a member has been through fsrl_ppo_begin, a
+//      every member's fsrl_ppo_end.  One error path, in fsrl_group_ppo_update_each: once a member has been through fsrl_ppo_begin, a
 //      failure clears in_update on every member and does nothing else.
+//      Member i has its own minibatch size (batch_sizes[i], its fsrl_ppo_begin's) and its own number of passes (repeats[i]): it
+//      leaves the update after its last pass the way a member that stopped on KL does, without a stopped pass.
 struct GroupUpdate {
     fsrl_group* g = nullptr; int k = 0;
+    const int32_t* batch_sizes = nullptr; const int32_t* repeats = nullptr;     // [k]
     const int64_t* const* perms = nullptr; uint64_t seed = 0;      // ppo_pass_prepare's, per member and pass
     int32_t* stopped_pass_out = nullptr;
+    int max_repeat = 0;                         // passes of the update: the most any member asks for
     bool begun = false;                         // a member has been through fsrl_ppo_begin
     int64_t n[FSRL_MAX_GROUP] = {};             // rows of each member's batch
     char active[FSRL_MAX_GROUP] = {};           // still stepping: has rows and has not stopped on KL
@@ -152,8 +171,7 @@ struct GroupUpdate {
 // sample(0) + process_fn of every member, back to back on the shared stream; member i's multipliers are lagrangians + i * lag_stride
 // (NULL: none) and rescaling[i] (NULL: 1).  Then the step tables the update names (fsteps: the FOCOPS rows, steps: the GroupStep
 // rows): [minibatch steps of the longest plan][k] rows, grown to twice what this call needs, behind the stream's reads of the old tables.
-static int ogroup_begin(GroupUpdate& u, const double* lagrangians, size_t lag_stride, const double* rescaling, int32_t batch_size,
-                        bool fsteps, bool steps) {
+static int ogroup_begin(GroupUpdate& u, const double* lagrangians, size_t lag_stride, const double* rescaling, bool fsteps, bool steps) {
     fsrl_group* g = u.g;
     group_actor_release(g);                     // the update goes behind the collect kernel, which ends
     for (fsrl_ctx* m : g->m) m->theta_version += 1;
@@ -161,10 +179,11 @@ static int ogroup_begin(GroupUpdate& u, const double* lagrangians, size_t lag_st
     u.begun = true;
     size_t cap_nmb = 1;
     for (int i = 0; i < u.k; ++i) {
-        int rc = fsrl_ppo_begin(g->m[i], lagrangians ? lagrangians + i * lag_stride : nullptr, rescaling ? rescaling[i] : 1.0, batch_size, &u.n[i]);
+        int rc = fsrl_ppo_begin(g->m[i], lagrangians ? lagrangians + i * lag_stride : nullptr, rescaling ? rescaling[i] : 1.0, u.batch_sizes[i], &u.n[i]);
         if (rc) return rc;
         if (u.stopped_pass_out) u.stopped_pass_out[i] = -1;
-        u.active[i] = u.n[i] != 0;              // an empty member sits the update out: it keeps a stale plan from an earlier update
+        // an empty member sits the update out (it keeps a stale plan from an earlier update), and so does one that asks for no pass
+        u.active[i] = u.n[i] != 0 && u.repeats[i] > 0;
         if (u.active[i]) cap_nmb = std::max(cap_nmb, g->m[i]->mb_start.size());
     }
     const size_t rows = cap_nmb * u.k;
@@ -173,13 +192,15 @@ static int ogroup_begin(GroupUpdate& u, const double* lagrangians, size_t lag_st
     return rc;
 }
 // Start of a pass.  u.n_act == 0 afterwards: every member is empty or has stopped, the update is over.  Otherwise the pass has the steps
-// of the longest plan among the members still active (one that stopped on KL no longer counts), the previous pass's pinned tables have
+// of the longest plan among the members still active (one that stopped on KL or has run its own passes no longer counts), the previous pass's pinned tables have
 // left host memory, and every active member's permutation + batch preparation is enqueued, each followed by the update's prepared(i, c).
 template <class Prepared>
 static int ogroup_pass_begin(GroupUpdate& u, int pass, Prepared&& prepared) {
     u.n_act = 0; u.max_nmb = 0;
-    for (int i = 0; i < u.k; ++i)
+    for (int i = 0; i < u.k; ++i) {
+        if (pass >= u.repeats[i]) u.active[i] = 0;               // the member's own pass count
         if (u.active[i]) { u.n_act += 1; u.max_nmb = std::max(u.max_nmb, u.g->m[i]->mb_start.size()); }
+    }
     if (u.n_act == 0) return 0;
     if (u.g->steps_in_flight) { HIPCHK(hipEventSynchronize(u.g->steps_copied)); u.g->steps_in_flight = false; }
     for (int i = 0; i < u.k; ++i) {
@@ -213,13 +234,13 @@ static int ogroup_pass_end(GroupUpdate& u, int pass, bool ppo_adam_t, bool watch
 
 // k x BasePolicy.update (base_policy.py:332-355) in lock step: the member table, the step table of a pass and the launches of a
 // minibatch step -- 3 (2 without a clip) for all fused members, 2 L + 5 for all layered ones (host_layered_group.inc)
-static int ppo_group_update(GroupUpdate& u, const double* lagrangians, const double* rescaling, int32_t batch_size, int32_t repeat) {
+static int ppo_group_update(GroupUpdate& u, const double* lagrangians, const double* rescaling) {
     CHECK_ARG(rescaling, "null argument");
     fsrl_group* g = u.g; fsrl_ctx* c0 = g->m[0];
     const int k = u.k; hipStream_t s = g->stream;
     const int C = c0->cfg.n_critics, H = c0->cfg.hidden, nn = c0->md.n_nets;
     const bool layered = c0->lay != nullptr;
-    int rc = ogroup_begin(u, lagrangians, (size_t)(C - 1), rescaling, batch_size, false, true);
+    int rc = ogroup_begin(u, lagrangians, (size_t)(C - 1), rescaling, false, true);
     if (rc) return rc;
     // ---- member table (wp.stats: per pass, the statistics table may be regrown)
     const int nparts = layered ? 0 : wg_grid(H, nn);
@@ -232,13 +253,16 @@ static int ppo_group_update(GroupUpdate& u, const double* lagrangians, const dou
         a.wp = ppo_wgrad_ptrs(c);
         a.gsq_part = c->gsq_part; a.nparts = nparts;
     }
-    PpoStepArgs base = ppo_base_args(c0);
+    // group-wide arguments only; a member's hyper-parameters are in its table row (group_agent_common: GroupAgent::hp)
+    PpoStepArgs base = group_base_args(c0);
+    bool watch_kl = false;                      // the pass-level KL readback: on when ANY member has a target
+    for (int i = 0; i < k; ++i) watch_kl = watch_kl || g->m[i]->cfg.target_kl > 0.0f;
     if (layered) {                              // job tables of this update: the members' working sets are in place now
         rc = lay_group_tables(g->lay, g->m.data(), k, u.active, s);
         if (rc) return rc;
         base.fuse_adam = 0;                     // the layered step keeps the separate Adam launch (lay_ppo_steps)
     }
-    for (int pass = 0; pass < repeat; ++pass) {
+    for (int pass = 0; pass < u.max_repeat; ++pass) {
         rc = ogroup_pass_begin(u, pass, [&](int i, fsrl_ctx* c) { g->tab.h[i].wp.stats = c->d_stats; return 0; });
         if (rc) return rc;
         if (u.n_act == 0) break;
@@ -306,25 +330,42 @@ static int ppo_group_update(GroupUpdate& u, const double* lagrangians, const dou
                                    c0->md, g->tab.d, st, base);
             HIPCHK(hipGetLastError());
         }
-        rc = ogroup_pass_end(u, pass, true, c0->cfg.target_kl > 0.0f);
+        rc = ogroup_pass_end(u, pass, true, watch_kl);
         if (rc) return rc;
     }
     return 0;
 }
 
-// lagrangians: [k][n_critics - 1]; rescaling: [k]; perms: NULL (library shuffles) or k pointers, member i's = [repeat][n_i];
-// stats_out: k pointers or NULL.  A FOCOPS group: k x Engine.focops_update (lagrangians / rescaling ignored).
+// lagrangians: [k][n_critics - 1]; rescaling: [k]; batch_sizes, repeats: [k], member i's minibatch size and number of passes (0: the
+// member sits the update out); perms: NULL (library shuffles) or k pointers, member i's = [repeats[i]][n_i]; stats_out: k pointers
+// or NULL, member i's holds cap_steps[i] rows.  A FOCOPS group: k x Engine.focops_update (lagrangians / rescaling ignored).
+extern "C" int fsrl_group_ppo_update_each(fsrl_group* g, const double* lagrangians, const double* rescaling, const int32_t* batch_sizes,
+                                          const int32_t* repeats, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
+                                          const int64_t* cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
+    CHECK_ARG(g && batch_sizes && repeats, "null argument");
+    CHECK_ARG(!stats_out || cap_steps, "null argument");
+    if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
+    GroupUpdate u;
+    u.g = g; u.k = (int)g->m.size(); u.batch_sizes = batch_sizes; u.repeats = repeats;
+    u.perms = perms; u.seed = seed; u.stopped_pass_out = stopped_pass_out;
+    for (int i = 0; i < u.k; ++i) {
+        CHECK_ARG(repeats[i] >= 0, "member %d: repeat must be >= 0", i);
+        u.max_repeat = std::max(u.max_repeat, (int)repeats[i]);
+    }
+    int rc = g->m[0]->cfg.algo == FSRL_ALGO_FOCOPS ? focops_group_update(u) : ppo_group_update(u, lagrangians, rescaling);
+    for (int i = 0; i < u.k && !rc; ++i)        // end: statistics of every member
+        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, stats_out ? cap_steps[i] : 0, n_steps_out ? n_steps_out + i : nullptr);
+    if (rc && u.begun) for (fsrl_ctx* c : g->m) c->in_update = false;
+    return rc;
+}
+
+// the same with one batch_size, one repeat and one row capacity for every member
 extern "C" int fsrl_group_ppo_update(fsrl_group* g, const double* lagrangians, const double* rescaling, int32_t batch_size,
                                      int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
                                      int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out) {
     CHECK_ARG(g, "null argument");
     CHECK_ARG(repeat >= 0, "repeat must be >= 0");
-    if (g->broken) return fail(FSRL_ESTATE, "a member of this group has been destroyed");
-    GroupUpdate u{g, (int)g->m.size(), perms, seed, stopped_pass_out};
-    int rc = g->m[0]->cfg.algo == FSRL_ALGO_FOCOPS ? focops_group_update(u, batch_size, repeat)
-                                                   : ppo_group_update(u, lagrangians, rescaling, batch_size, repeat);
-    for (int i = 0; i < u.k && !rc; ++i)        // end: statistics of every member
-        rc = fsrl_ppo_end(g->m[i], stats_out ? stats_out[i] : nullptr, cap_steps, n_steps_out ? n_steps_out + i : nullptr);
-    if (rc && u.begun) for (fsrl_ctx* c : g->m) c->in_update = false;
-    return rc;
+    int32_t bs[FSRL_MAX_GROUP], rp[FSRL_MAX_GROUP]; int64_t cap[FSRL_MAX_GROUP];
+    for (int i = 0; i < FSRL_MAX_GROUP; ++i) { bs[i] = batch_size; rp[i] = repeat; cap[i] = cap_steps; }
+    return fsrl_group_ppo_update_each(g, lagrangians, rescaling, bs, rp, perms, seed, stats_out, cap, n_steps_out, stopped_pass_out);
 }

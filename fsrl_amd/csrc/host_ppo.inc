@@ -236,7 +236,7 @@ static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed) {
 }
 
 // the step scalars that do not change inside an update (everything but the minibatch geometry and Adam's bias terms)
-static PpoStepArgs ppo_base_args(fsrl_ctx* c) {
+static PpoStepArgs ppo_base_args(const fsrl_ctx* c) {
     PpoStepArgs sa{};
     sa.rescale = (float)c->rescaling;
     for (int i = 0; i < FSRL_MAX_CRITICS; ++i) sa.lam[i] = (float)c->lagr[i];
@@ -273,12 +273,28 @@ static WgradPtrs ppo_wgrad_ptrs(const fsrl_ctx* c) {
     return wp;
 }
 // a member's row of a group's member table, zeroed, with what fused (host_group.inc) and layered (host_layered_group.inc) members
-// have in common
+// have in common.  hp: the member's OWN hyper-parameters, taken from its ppo_base_args so that every derived value (kl_thresh,
+// one_minus_b*) is the one its solo step would use; group_step_args lays them over the group-wide arguments.
 static void group_agent_common(const fsrl_ctx* c, GroupAgent& a) {
     memset(&a, 0, sizeof(a));
     a.P = c->P; a.Pw = c->P; a.M = c->M; a.V = c->V; a.G = c->G; a.ctrl = c->ctrl; a.n_dev = c->n_dev;
     a.rescale = (float)c->rescaling;
     for (int j = 0; j < FSRL_MAX_CRITICS; ++j) a.lam[j] = (float)c->lagr[j];
+    const PpoStepArgs sa = ppo_base_args(c);
+    GroupHyper& h = a.hp;
+    h.eps_clip = sa.eps_clip; h.dual_clip = sa.dual_clip; h.vf_coef = sa.vf_coef; h.max_grad_norm = sa.max_grad_norm;
+    h.target_kl = sa.target_kl; h.kl_thresh = sa.kl_thresh;
+    h.norm_adv = sa.norm_adv; h.use_lagrangian = sa.use_lagrangian; h.value_clip = sa.value_clip;
+    h.beta1 = sa.beta1; h.beta2 = sa.beta2; h.adam_eps = sa.adam_eps;
+    h.one_minus_b1 = sa.one_minus_b1; h.one_minus_b2 = sa.one_minus_b2;
+}
+// what of the step arguments is the same for every member of a group (its first member's; fsrl_group_create checks what the
+// members must agree on): everything else comes from the member and step tables (group_step_args)
+static PpoStepArgs group_base_args(const fsrl_ctx* c0) {
+    const PpoStepArgs m0 = ppo_base_args(c0);
+    PpoStepArgs sa{};
+    sa.max_action = m0.max_action; sa.fuse_adam = m0.fuse_adam; sa.xcd_pair = m0.xcd_pair; sa.dbg_phase = m0.dbg_phase;
+    return sa;
 }
 
 // Tile height of the fused step's forward / backward launch: `tiles` 16-row tiles per network, nn networks, n_act members in the launch

@@ -1519,6 +1519,15 @@ __global__ __launch_bounds__(1024) void ppo_wgrad_kernel(const ModelDesc md, con
 // whose fixed costs (launch floor, cold first touch of the freshly written parameters) dominate; k agents share each of
 // them.  The arithmetic per member is the single-agent body, inlined; grouped and one-by-one updates are bit-identical when
 // the tile shapes agree (a group of one, minibatches <= 512 rows) and within the golden tolerances otherwise.
+// A member's own hyper-parameters (a sweep: members of one PPO-Lagrangian group may differ in all of them).  Copied on the host from
+// the member's ppo_base_args, so kl_thresh and one_minus_b* are formed exactly as a solo context forms them.
+struct GroupHyper {
+    double kl_thresh;
+    float eps_clip, dual_clip, vf_coef, max_grad_norm, target_kl;
+    int norm_adv, use_lagrangian, value_clip;
+    float beta1, beta2, adam_eps, one_minus_b1, one_minus_b2;
+    int pad;
+};
 struct GroupAgent {          // per member; device memory, rewritten at the start of every grouped update
     const float* P;
     float *Pw, *M, *V, *G;
@@ -1527,6 +1536,7 @@ struct GroupAgent {          // per member; device memory, rewritten at the star
     const float* gsq_part; CtrlBlock* ctrl;
     float rescale; float lam[FSRL_MAX_CRITICS];
     int n_dev, nparts;
+    GroupHyper hp;
 };
 struct GroupStep {           // per (minibatch index of the pass, member); device memory, rewritten every pass
     int mb_start, mb_size, step, mb_index;
@@ -1541,6 +1551,13 @@ __device__ __forceinline__ PpoStepArgs group_step_args(const PpoStepArgs& base, 
     sa.rescale = a.rescale;
 #pragma unroll
     for (int i = 0; i < FSRL_MAX_CRITICS; ++i) sa.lam[i] = a.lam[i];
+    // the member's own hyper-parameters: uniform over the workgroup (the table row is indexed by a block index), so scalar loads
+    const GroupHyper& h = a.hp;
+    sa.eps_clip = h.eps_clip; sa.dual_clip = h.dual_clip; sa.vf_coef = h.vf_coef; sa.max_grad_norm = h.max_grad_norm;
+    sa.target_kl = h.target_kl; sa.kl_thresh = h.kl_thresh;
+    sa.norm_adv = h.norm_adv; sa.use_lagrangian = h.use_lagrangian; sa.value_clip = h.value_clip;
+    sa.beta1 = h.beta1; sa.beta2 = h.beta2; sa.adam_eps = h.adam_eps;
+    sa.one_minus_b1 = h.one_minus_b1; sa.one_minus_b2 = h.one_minus_b2;
     return sa;
 }
 

@@ -873,6 +873,10 @@ class EngineGroup(_LockStepCollect):
     """k PPO-Lagrangian engines, or k FOCOPS engines (focops_init), of one network shape on one GPU, updated in lock step
     (fsrl_group_*): every launch of the minibatch step carries all members.  Members keep their own store, parameters and
     random streams; use the engines as usual for everything else (push, collect_step, get_params ...).
+    A PPO-Lagrangian group may be a sweep: its members agree on the network shape, n_critics, max_action, unbounded and on whether
+    max_grad_norm is on, and may differ in every other hyper-parameter (eps_clip, dual_clip, vf_coef, the max_grad_norm value,
+    target_kl, norm_adv, use_lagrangian, rew_norm, value_clip, lr, beta1, beta2, adam_eps); ppo_update_each adds a minibatch size and a
+    number of passes per member.  A FOCOPS group keeps one set of hyper-parameters (learning rates may differ).
     The members may all be layered contexts of one `hidden_sizes` and `force_layered`: the group then runs the layered step,
     2 L + 5 launches for all members, bit-identical per member to Engine.ppo_update / Engine.focops_update at every group size
     (a layered FOCOPS group has no tile-height plan to differ in); collect_step is one sequence of L + 2
@@ -909,6 +913,34 @@ class EngineGroup(_LockStepCollect):
         _lib.check(self.lib.fsrl_group_ppo_update(self._g, _ptr(lag, _f64p) if lag.size else None, _ptr(resc, _f64p),
                                                   int(batch_size), int(repeat), pp, int(seed), sp, cap, _ptr(nst, _i64p),
                                                   _ptr(stop, _i32p)))
+        for e, n in zip(self.engines, sizes):
+            e._n = n
+        return [s[:int(n)] for s, n in zip(stats, nst)], [int(x) for x in stop]
+
+    def ppo_update_each(self, lagrangians, rescalings, batch_sizes, repeats, perms=None, seed=0):
+        """ppo_update with member i's own minibatch size batch_sizes[i] and number of passes repeats[i] (a sweep; 0 passes: the
+        member sits the update out).  perms: None or per member a list / array [repeats[i]][N_i].  Returns what ppo_update returns."""
+        k = len(self.engines)
+        lag = np.ascontiguousarray(lagrangians, np.float64).reshape(k, -1)
+        resc = np.ascontiguousarray(rescalings, np.float64).reshape(k)
+        bs = np.ascontiguousarray(batch_sizes, np.int32).reshape(k)
+        rp = np.ascontiguousarray(repeats, np.int32).reshape(k)
+        sizes = [len(e) for e in self.engines]
+        caps = np.array([max(1, -(-n // max(int(b), 1))) * max(int(r), 1) for n, b, r in zip(sizes, bs, rp)], np.int64)
+        stats = [np.empty((int(c), _lib.PPO_NSTATS), np.float32) for c in caps]
+        sp = (_f32p * k)(*[_ptr(s, _f32p) for s in stats])
+        pp, keep = None, []
+        if perms is not None:
+            for i in range(k):
+                a = np.ascontiguousarray([np.asarray(p, np.int64) for p in perms[i]], np.int64).reshape(len(perms[i]), sizes[i])
+                assert a.shape == (int(rp[i]), sizes[i]), "perms[i] must be [repeats[i]][N_i]"
+                keep.append(a)
+            pp = (_i64p * k)(*[_ptr(a, _i64p) for a in keep])
+        nst = np.zeros(k, np.int64)
+        stop = np.zeros(k, np.int32)
+        _lib.check(self.lib.fsrl_group_ppo_update_each(self._g, _ptr(lag, _f64p) if lag.size else None, _ptr(resc, _f64p),
+                                                       _ptr(bs, _i32p), _ptr(rp, _i32p), pp, int(seed), sp, _ptr(caps, _i64p),
+                                                       _ptr(nst, _i64p), _ptr(stop, _i32p)))
         for e, n in zip(self.engines, sizes):
             e._n = n
         return [s[:int(n)] for s, n in zip(stats, nst)], [int(x) for x in stop]

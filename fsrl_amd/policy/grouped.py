@@ -14,6 +14,11 @@ member's grouped update is its own update bit for bit.
     pre_update_fn) ...
     group.update(buffers, batch_size=256, repeat=4)
 
+A PPOLagrangian group may be a sweep: the members' own eps_clip, dual_clip, vf_coef, max_grad_norm value, target_kl, advantage /
+reward normalisation, value clip and optimiser settings are used, each member as in its own update (they must agree on the network
+shape, the number of critics, max_action, `unbounded` and on whether max_grad_norm is on), and `batch_size` / `repeat` may be one
+int per member.  A FOCOPS group keeps one set of hyper-parameters.
+
 Random streams: the library shuffles (member i seeded from `seed`), so k grouped seeds are k independent runs but not the
 reference's numpy permutation stream (PPOLagrangian.learn / FOCOPS.learn draw np.random.permutation per pass); pass `perms`
 for that."""
@@ -44,8 +49,17 @@ class PolicyGroup:
     def close(self):
         self.group.close()
 
-    def update(self, buffers, batch_size: int = 256, repeat: int = 4, perms: Optional[List] = None):
+    def update(self, buffers, batch_size: Union[int, Sequence[int]] = 256, repeat: Union[int, Sequence[int]] = 4,
+               perms: Optional[List] = None):
+        """batch_size / repeat: an int for every member, or one int per member (a sweep over batch_size / repeat_per_collect of a
+        PPOLagrangian group: EngineGroup.ppo_update_each; perms[i] then holds repeat[i] permutations)."""
         pols = self.policies
+        each = not (isinstance(batch_size, (int, np.integer)) and isinstance(repeat, (int, np.integer)))
+        if each:
+            assert not self.focops, "a FOCOPS group takes one batch_size and one repeat (sweeps are PPOLagrangian groups)"
+            per = lambda v: [int(v)] * len(pols) if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+            batch_size, repeat = per(batch_size), per(repeat)
+            assert len(batch_size) == len(pols) and len(repeat) == len(pols), "one batch_size and one repeat per member"
         for p, b in zip(pols, buffers):
             assert getattr(b, "engine", None) is p.engine, "buffer i must be the HipVectorReplayBuffer of policy i"
             p.updating = True
@@ -60,7 +74,8 @@ class PolicyGroup:
                 lr = [p.lagrangians_and_rescaling() if p.use_lagrangian else ([0.0] * (p.critics_num - 1), 1.0) for p in pols]
                 lags = np.array([x[0] if len(x[0]) else [0.0] for x in lr], np.float64)
                 resc = [x[1] for x in lr]
-                stats, stopped = self.group.ppo_update(lags, resc, batch_size, repeat, perms=perms, seed=seed)
+                update = self.group.ppo_update_each if each else self.group.ppo_update
+                stats, stopped = update(lags, resc, batch_size, repeat, perms=perms, seed=seed)
         except BaseException:
             # a failed group update may have stepped some parameters already: the host mirrors are stale, nobody is updating
             for p in pols:

@@ -295,7 +295,12 @@ int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
  *      alone within the golden tests' tolerances, and bit-identical only when the launch shapes agree (a group of one,
  *      minibatches of at most 512 rows): the group picks its tile height from the number of active members and keeps the
  *      in-kernel weight-gradient reduction above 512 rows.  Members keep their own store, parameters,
- *      Adam state and random streams; shape and PPO hyper-parameters must agree, batch sizes N_i may differ.
+ *      Adam state and random streams; batch lengths N_i may differ.  A PPO-Lagrangian group may be a SWEEP: members must agree
+ *      on the network shape, n_critics, max_action, unbounded and on whether max_grad_norm is on (> 0: the step has 3 launches,
+ *      2 without the clip) -- the refusal names the member and the field -- and may differ in eps_clip, dual_clip, vf_coef, the
+ *      value of max_grad_norm, target_kl (the pass-level KL stop is watched when any member has a target; a member without
+ *      one never stops), norm_adv, use_lagrangian, rew_norm, value_clip, recompute_adv, lr, beta1, beta2 and adam_eps; minibatch
+ *      size and passes per member: fsrl_group_ppo_update_each.  A FOCOPS group is not a sweep: its members share all of these.
  *      While grouped, a member's own update calls still work (they run on the group's stream).
  *      A group has one algorithm.  FOCOPS members must have run fsrl_focops_init and share l2_reg, delta,
  *      eta, tem_lambda, max_grad_norm and fsrl_focops_set_plan (learning rates may differ); checked again at every update.
@@ -322,6 +327,15 @@ int fsrl_group_set_plan(fsrl_group* group, int32_t tall_tiles);
 int fsrl_group_ppo_update(fsrl_group* group, const double* lagrangians, const double* rescaling, int32_t batch_size,
                           int32_t repeat, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
                           int64_t cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
+/* The same update with member i's own minibatch size batch_sizes[i] and number of passes repeats[i] (a sweep over batch_size /
+ * repeat_per_collect); fsrl_group_ppo_update is this call with its scalars repeated.  Member i is active for passes
+ * 0 .. repeats[i] - 1 and then leaves the update as a KL-stopped member does, but with stopped_pass_out[i] = -1; repeats[i] == 0:
+ * it sits the update out (its batch is sampled and processed as by its own update with repeat 0; no rows, parameters and Adam
+ * counters untouched).  perms: NULL or k pointers to [repeats[i]][N_i]; cap_steps [k]: rows that stats_out[i] holds.  The update
+ * runs max(repeats) passes.  A FOCOPS group takes per-member batch sizes and pass counts the same way.                         */
+int fsrl_group_ppo_update_each(fsrl_group* group, const double* lagrangians, const double* rescaling, const int32_t* batch_sizes,
+                               const int32_t* repeats, const int64_t* const* perms, uint64_t seed, float* const* stats_out,
+                               const int64_t* cap_steps, int64_t* n_steps_out, int32_t* stopped_pass_out);
 /* Lock-step collection: fsrl_collect_step on every member, member order, in ONE call with ONE actor request for all of them --
  * same stored rows and slots, same actions, same library-RNG consumption per member, bit for bit.  Row arrays are concatenated
  * over members: k[m] transitions to store (env_ids / obs / act / rew / cost / terminated / truncated / obs_next and the
