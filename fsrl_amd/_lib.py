@@ -158,6 +158,7 @@ SIGNATURES = {
     "fsrl_tr_grad": (C.c_int, [_ctx, C.c_int32, _f, C.c_int64]),
     "fsrl_tr_hvp": (C.c_int, [_ctx, _f, _f, C.c_int64]),
     "fsrl_tr_hvp_cached": (C.c_int, [_ctx, _f, _f, C.c_int64]),
+    "fsrl_tr_cg": (C.c_int, [_ctx, _f, C.c_int64, C.c_float, C.c_int32, C.c_float, _f, _i32, _f]),
     "fsrl_tr_eval": (C.c_int, [_ctx, _d]),
     "fsrl_tr_set_plan": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32]),
     "fsrl_tr_set_tile_split": (C.c_int, [_ctx, C.c_int32, C.c_int32]),

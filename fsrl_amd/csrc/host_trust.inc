@@ -649,6 +649,37 @@ static int tr_cg_dev(fsrl_ctx* c, TrState* t, const float* g_dev, float damping,
     return 0;
 }
 
+// the solver alone, for the parity tests: x = (H + damping)^-1 rhs at the current theta over the batch of the last fsrl_tr_begin,
+// exactly as the learn calls run it (tr_cg_dev on device vectors), then the scalars of the chain.  rhs goes up through t->Vdev:
+// actor_to_dev writes the W2 mirror behind the main vector, and only P-sized buffers have room for it -- a t->vec slot does not.
+extern "C" int fsrl_tr_cg(fsrl_ctx* c, const float* rhs, int64_t n, float damping, int32_t nsteps, float tol, float* x_out,
+                          int32_t* iters_out, float* rs_out) {
+    int rc = tr_product_enter(c, rhs && x_out && iters_out && rs_out, "fsrl_tr_cg", n);
+    if (rc) return rc;
+    CHECK_ARG(nsteps >= 0 && nsteps <= 64, "nsteps must be 0 .. 64");
+    TrState* t = c->tr;
+    const int nd = c->md.net[0].end;
+    float *vrhs = t->vec, *vx = t->vec + 2 * (size_t)c->n_dev;            // the g and H^-1 g slots: free between learn calls
+    rc = actor_to_dev(c, rhs, t->Vdev);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(vrhs, t->Vdev, (size_t)nd * 4, hipMemcpyDeviceToDevice, c->compute));
+    rc = tr_cg_dev(c, t, vrhs, damping, nsteps, tol, vx);
+    if (rc) return rc;
+    rc = actor_from_dev(c, vx, x_out);                                    // synchronises the compute stream
+    if (rc) return rc;
+    CgScal sc{};
+    HIPCHK(hipMemcpy(&sc, t->cg_sc, sizeof(CgScal), hipMemcpyDeviceToHost));
+    *iters_out = sc.iters;
+    if (nsteps > 0) *rs_out = sc.rs[sc.iters & 1];                        // cg_p_kernel: rs[(it + 1) & 1] = r.r leaving iteration `it`
+    else {                                                                // no iteration ran: r.r of cg_init_kernel, still in partials
+        double part[CG_NB], s = 0.0;
+        HIPCHK(hipMemcpy(part, t->cg_part + CG_NB, sizeof(part), hipMemcpyDeviceToHost));
+        for (int b = 0; b < CG_NB; ++b) s += part[b];
+        *rs_out = (float)s;
+    }
+    return 0;
+}
+
 // out = H v + damping v for a device vector v (cpo.py:177-182 with the damping of its callers)
 static int tr_mvp_dev(fsrl_ctx* c, TrState* t, const float* v_dev, float damping, float* out_dev) {
     const int nd = c->md.net[0].end;

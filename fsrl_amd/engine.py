@@ -492,6 +492,16 @@ class Engine:
         _lib.check(self.lib.fsrl_tr_hvp_cached(self._ctx, _ptr(v, _f32p), _ptr(out, _f32p), v.size))
         return out
 
+    def tr_cg(self, rhs, damping: float, nsteps: int, tol: float):
+        """The learn calls' conjugate-gradient solve on its own: (x, iterations run, last r.r) for (H + damping) x = rhs at the
+        current theta, at most `nsteps` iterations, stopping once r.r < tol."""
+        rhs = np.ascontiguousarray(rhs, np.float32)
+        x = np.empty_like(rhs)
+        iters, rs = C.c_int32(), C.c_float()
+        _lib.check(self.lib.fsrl_tr_cg(self._ctx, _ptr(rhs, _f32p), rhs.size, float(damping), int(nsteps), float(tol),
+                                       _ptr(x, _f32p), C.byref(iters), C.byref(rs)))
+        return x, int(iters.value), float(rs.value)
+
     def tr_set_plan(self, tile_rows: int = 0, hvp: int = 0, wgrad: int = 0):
         """Kernel plan of the full-batch path (A/B timing, bit-identity tests); 0 / 0 = automatic.  tile_rows + 64: critic steps on the
         compute stream; + 128: read-backs by copy + stream synchronisation instead of polled completion words."""

@@ -438,6 +438,12 @@ int fsrl_tr_hvp(fsrl_ctx* ctx, const float* v, float* out, int64_t n);
  * the kernel the conjugate-gradient solves inside fsrl_cpo_learn / fsrl_trpo_learn run for their 2nd .. 11th product
  * (cpo.py:184-204).  Bit-identical to fsrl_tr_hvp.                                                                     */
 int fsrl_tr_hvp_cached(fsrl_ctx* ctx, const float* v, float* out, int64_t n);
+/* the conjugate-gradient solve of the learn calls on its own (cpo.py:184-204 / trpo_lag.py:261-283): x_out = (H + damping)^-1 rhs
+ * after at most nsteps (0 .. 64; 0: x = 0) iterations at the current theta, stopping after the first iteration that leaves
+ * r.r < tol (the remaining ones are no-ops on the device).  rhs, x_out: flat ACTOR vectors like fsrl_tr_grad's out.
+ * *iters_out = iterations that ran, *rs_out = the last r.r the device computed.                                       */
+int fsrl_tr_cg(fsrl_ctx* ctx, const float* rhs, int64_t n, float damping, int32_t nsteps, float tol, float* x_out,
+               int32_t* iters_out, float* rs_out);
 /* stats8: mean(ratio*A_r), mean(ratio*A_c), mean KL, mean(logp_old - logp), mean A_r, mean A_c, 0, 0 */
 int fsrl_tr_eval(fsrl_ctx* ctx, double* stats8);
 /* Kernel plan of the full-batch path, for A/B timing and the bit-identity tests (no reference counterpart: the reference

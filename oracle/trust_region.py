@@ -61,6 +61,7 @@ class CPOConfig:
     lr: float = 1e-3           # Adam over the CRITIC parameters only (cpo_agent.py:147-148)
     unbounded: bool = False              # ActorProb(unbounded=True)
     reward_normalization: bool = False   # base_policy.py:430-444 (shared compute_gae_returns)
+    cg_iters: int = 10                   # cpo.py:184 nsteps
 
 
 @dataclass
@@ -81,6 +82,7 @@ class TRPOConfig:
     damping: float = 0.1       # trpo_lag.py:115
     unbounded: bool = False
     reward_normalization: bool = False
+    cg_iters: int = 10         # trpo_lag.py:261 nsteps
 
 
 class _TrustRegionBase(PPOLagOracle):
@@ -191,7 +193,7 @@ class CPOOracle(_TrustRegionBase):
         g = self.flat_grad(objective, retain_graph=True)
         b = self.flat_grad(-cost_sur, retain_graph=True)
         kl_grad = self.flat_grad(kl, create_graph=True)
-        H_inv_g = self.conjugate_gradients(g, kl_grad, c.damping_coeff)
+        H_inv_g = self.conjugate_gradients(g, kl_grad, c.damping_coeff, c.cg_iters)
         approx_g = self.hvp(H_inv_g, kl_grad, c.damping_coeff)
         c_value = cost_sur - c.cost_limit
         if torch.dot(b, b) <= EPS and c_value < 0:
@@ -199,7 +201,7 @@ class CPOOracle(_TrustRegionBase):
             s_q = torch.dot(approx_g, H_inv_g)
             case = 4
         else:
-            H_inv_b = self.conjugate_gradients(b, kl_grad, c.damping_coeff)
+            H_inv_b = self.conjugate_gradients(b, kl_grad, c.damping_coeff, c.cg_iters)
             approx_b = self.hvp(H_inv_b, kl_grad, c.damping_coeff)
             s_q, s_r, s_s = torch.dot(approx_g, H_inv_g), torch.dot(approx_g, H_inv_b), torch.dot(approx_b, H_inv_b)
             A = s_q - s_r**2 / s_s
@@ -306,7 +308,7 @@ class TRPOLagOracle(_TrustRegionBase):
         x = torch.zeros_like(g)
         r, p = g.clone(), g.clone()
         rdotr = r.dot(r)
-        for _ in range(10):
+        for _ in range(c.cg_iters):
             z = hv(p)
             alpha = rdotr / p.dot(z)
             x += alpha * p
