@@ -96,6 +96,10 @@ SIGNATURES = {
     "fsrl_optim_reset": (C.c_int, [_ctx]),
     "fsrl_state_snapshot": (C.c_int, [_ctx]),
     "fsrl_state_restore": (C.c_int, [_ctx]),
+    "fsrl_train_state_size": (C.c_int64, [_ctx, C.c_int32]),
+    "fsrl_train_state_export": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_int64, _i64]),
+    "fsrl_train_state_import": (C.c_int, [_ctx, C.c_void_p, C.c_int64]),
+    "fsrl_train_state_copy": (C.c_int, [_ctx, _ctx, C.c_int32]),
     "fsrl_ret_rms_get": (C.c_int, [_ctx, _d, C.c_int32]),
     "fsrl_ret_rms_set": (C.c_int, [_ctx, _d, C.c_int32]),
     "fsrl_set_lr": (C.c_int, [_ctx, C.c_int32, C.c_float]),

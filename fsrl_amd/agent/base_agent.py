@@ -45,7 +45,11 @@ class OnpolicyAgent(BaseAgent):
               step_per_epoch: int = 10000, repeat_per_collect: int = 4, buffer_size: Optional[int] = None,
               testing_num: int = 2, batch_size: int = 512, reward_threshold: float = 450,
               save_interval: int = 4, resume: bool = False, save_ckpt: bool = True,
-              verbose: bool = True, show_progress: bool = True, device_actor: bool = False):
+              verbose: bool = True, show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True):
+        """resume=True continues the run whose training state `<log_dir>/checkpoint/train_state.pt` holds (saved with every periodic
+        checkpoint while save_ckpt is on): epoch numbering, env steps, the best result, optimiser state and random streams carry
+        over; without such a file the run starts fresh and says so.  Env state is never saved: a resumed run resets its envs.
+        ckpt_store: whether the transition store goes into train_state.pt."""
         assert self.policy is not None, "The policy is not initialized"
         self.policy.train()
         eng = self.policy.engine
@@ -76,6 +80,8 @@ class OnpolicyAgent(BaseAgent):
                                   logger=self.logger, resume_from_log=resume,
                                   save_model_interval=save_interval, verbose=verbose,
                                   show_progress=show_progress)
+        if save_ckpt:                            # registered late: the state is the trainer's and the policy's
+            self.logger.setup_train_state_fn(lambda: trainer.train_state(with_store=ckpt_store))
         ep, stat, info = 0, {}, {}
         for ep, stat, info in trainer:
             self.logger.store(tab="train", cost_limit=self.cost_limit)

@@ -24,7 +24,12 @@ class OffpolicyAgent(BaseAgent):
               step_per_epoch: int = 3000, update_per_step: float = 0.1, buffer_size: Optional[int] = None,
               testing_num: int = 2, batch_size: int = 256, reward_threshold: float = 450,
               save_interval: int = 4, resume: bool = False, save_ckpt: bool = True, verbose: bool = True,
-              show_progress: bool = True, device_actor: bool = False):
+              show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True):
+        """resume=True continues the run whose training state `<log_dir>/checkpoint/train_state.pt` holds (saved with every periodic
+        checkpoint while save_ckpt is on): epoch numbering, env steps, the best result, the replay store, optimiser state and
+        random streams carry over; without such a file the run starts fresh and says so.  Env state is never saved: a resumed
+        run resets its envs.  ckpt_store: whether the replay store goes into train_state.pt (about 320 MB for a million rows of
+        33 observations and 8 actions); without it a resumed run starts from an empty store."""
         assert self.policy is not None, "The policy is not initialized"
         self.policy.train()
         eng = self.policy.engine
@@ -54,6 +59,8 @@ class OffpolicyAgent(BaseAgent):
                                    logger=self.logger, resume_from_log=resume,
                                    save_model_interval=save_interval, verbose=verbose,
                                    show_progress=show_progress)
+        if save_ckpt:                            # registered late: the state is the trainer's and the policy's
+            self.logger.setup_train_state_fn(lambda: trainer.train_state(with_store=ckpt_store))
         ep, stat, info = 0, {}, {}
         for ep, stat, info in trainer:
             self.logger.store(tab="train", cost_limit=self.cost_limit)

@@ -1582,3 +1582,5 @@ extern "C" float fsrl_get_lr(const fsrl_ctx* c, int32_t group) {
     if (c->cfg.algo == FSRL_ALGO_FOCOPS) return !c->foc ? -1.0f : group == 0 ? c->foc->cfg.actor_lr : group == 1 ? c->foc->cfg.critic_lr : -1.0f;
     return group == 0 ? c->cfg.lr : -1.0f;
 }
+
+#include "host_train_state.inc"

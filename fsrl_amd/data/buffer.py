@@ -45,6 +45,12 @@ class HipVectorReplayBuffer:
         """Fill levels from the engine (rows stored through fsrl_collect_step bypass this proxy)."""
         self._sizes[:] = self.engine.store_sizes()
 
+    def resync(self) -> None:
+        """Geometry and fill levels from the engine: a training state with the store was loaded into it (Engine.load_train_state)"""
+        self._sub, self.buffer_num = self.engine.store_geometry()
+        self.maxsize = self._sub * self.buffer_num
+        self.sync_sizes()
+
     def reset(self, keep_statistics: bool = False) -> None:
         self._sizes[:] = 0
         self.engine.reset_store(keep_statistics)

@@ -125,6 +125,32 @@ class Engine:
     def state_restore(self):
         _lib.check(self.lib.fsrl_state_restore(self._ctx))
 
+    def train_state_array(self, with_store: bool = True) -> np.ndarray:
+        """train_state() as the uint8 array the library wrote into: no second copy of a store of hundreds of megabytes"""
+        n = int(self.lib.fsrl_train_state_size(self._ctx, int(bool(with_store))))
+        if n < 0:
+            _lib.check(n)
+        buf = np.empty(n, np.uint8)
+        written = C.c_int64()
+        _lib.check(self.lib.fsrl_train_state_export(self._ctx, int(bool(with_store)), buf.ctypes.data, n, C.byref(written)))
+        return buf[:written.value]
+
+    def train_state(self, with_store: bool = True) -> bytes:
+        """The context's full training state as bytes (fsrl_train_state_export): parameters, optimiser state, random streams,
+        running statistics and, with_store, the transition store.  A pure function of the state; env state is not in it."""
+        return self.train_state_array(with_store).tobytes()
+
+    def load_train_state(self, blob) -> None:
+        """fsrl_train_state_import: everything about `blob` (bytes or a uint8 array) is checked before the first write, so a
+        refused blob (AssertionError naming the reason) leaves the context as it was."""
+        a = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        keep = a if a.size else np.zeros(8, np.uint8)         # an empty blob is refused by the validator, like any other
+        _lib.check(self.lib.fsrl_train_state_import(self._ctx, keep.ctypes.data, a.size))
+
+    def copy_train_state_from(self, other: "Engine", with_store: bool = True) -> None:
+        """fsrl_train_state_copy: `other`'s training state into this context, device to device (same device, same shapes)."""
+        _lib.check(self.lib.fsrl_train_state_copy(self._ctx, other._ctx, int(bool(with_store))))
+
     def optim_reset(self):
         _lib.check(self.lib.fsrl_optim_reset(self._ctx))
 

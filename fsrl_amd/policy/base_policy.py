@@ -134,6 +134,8 @@ class BasePolicy(ABC, nn.Module):
         """The device parameters moved on (an update ran): the host mirror is refreshed when it is next needed -- acting on
         the host, state_dict() -- not after every update (collecting with the device actor never needs it)."""
         self._stale = True
+        if hasattr(self, "_dirty"):              # the replay policies' two flags: actor mirror / critics and targets
+            self._dirty = self._rest_dirty = True
 
     def _pull_params(self) -> None:
         self._stale = False
@@ -156,6 +158,55 @@ class BasePolicy(ABC, nn.Module):
             self._push_params()
             self._stale = False
         return out
+
+    # ------------------------------------------------------------------ training state (resume)
+    _train_state_attrs = ()      # host-side scalars of a concrete policy that decide how a run continues (FOCOPS: nu)
+
+    def train_state_dict(self, with_store: bool = True) -> dict:
+        """Everything a run needs to continue exactly where it stands, beyond what `state_dict()` holds: the engine's training
+        state (`Engine.train_state`: parameters in device layout, optimiser state, random streams, running statistics and, with
+        `with_store`, the transition store) as a uint8 tensor; `get_extra_state()` where the policy defines it (PID multipliers);
+        `gradient_steps`; the lr scheduler's state; the torch / numpy / `random` generator states (acting on the host draws from
+        them).  Env state is not part of it: a resumed run resets its envs."""
+        import random
+        drain = getattr(self, "_drain", None)
+        if drain is not None:
+            drain()                              # statistics rows still on the device are logged, not lost
+        state = getattr(self.engine, "train_state_array", None)         # the array the library filled, not a copy of it
+        blob = state(with_store) if state is not None else np.frombuffer(self.engine.train_state(with_store), np.uint8).copy()
+        d = {"engine": torch.from_numpy(blob),
+             "gradient_steps": int(self.gradient_steps),
+             "rng": {"torch": torch.get_rng_state(), "numpy": np.random.get_state(), "python": random.getstate()}}
+        if type(self).get_extra_state is not nn.Module.get_extra_state:
+            d["extra_state"] = self.get_extra_state()
+        if self.lr_scheduler is not None:
+            d["lr_scheduler"] = self.lr_scheduler.state_dict()
+        if self._train_state_attrs:
+            d["host"] = {k: getattr(self, k) for k in self._train_state_attrs}
+        return d
+
+    def load_train_state_dict(self, d: dict) -> None:
+        """Inverse of `train_state_dict` on a policy of the same configuration: afterwards the host mirror is stale (the device
+        has the loaded parameters) and every optimiser group runs at the loaded schedule's rate."""
+        import random
+        self.engine.load_train_state(d["engine"].numpy())
+        self.gradient_steps = int(d["gradient_steps"])
+        if isinstance(getattr(self, "_pending", None), int):
+            self._pending = 0                    # the import dropped the statistics rows that were not drained
+        if d.get("extra_state") is not None:
+            self.set_extra_state(d["extra_state"])
+        for k, v in d.get("host", {}).items():
+            setattr(self, k, v)
+        torch.set_rng_state(d["rng"]["torch"]); np.random.set_state(d["rng"]["numpy"]); random.setstate(d["rng"]["python"])
+        self._mark_stale()
+        if self.lr_scheduler is not None and "lr_scheduler" in d:
+            self.lr_scheduler.load_state_dict(d["lr_scheduler"])
+            opt = getattr(self.lr_scheduler, "optimizer", None)       # torch restores the schedule, not the optimiser's rates
+            if opt is not None:
+                for group, lr in zip(opt.param_groups, self.lr_scheduler.get_last_lr()):
+                    group["lr"] = lr
+            for gid, opt in self._lr_groups():
+                self.engine.set_lr(gid, float(opt.param_groups[0]["lr"]))
 
     # ------------------------------------------------------------------ learning-rate schedule
     def _lr_groups(self):

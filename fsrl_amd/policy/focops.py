@@ -41,6 +41,8 @@ class FOCOPS(BasePolicy):
         self.engine.focops_init(actor_lr=actor_optim.param_groups[0]["lr"], critic_lr=critic_optim.param_groups[0]["lr"],
                                 l2_reg=l2_reg, delta=delta, eta=eta, tem_lambda=tem_lambda, max_grad_norm=max_grad_norm)
 
+    _train_state_attrs = ("_nu", "_ave_cost_return")      # the multiplier lives on the host (nu_step)
+
     def pre_update_fn(self, stats_train: Dict, **kwarg) -> Any:
         self._ave_cost_return = stats_train["cost"]
 

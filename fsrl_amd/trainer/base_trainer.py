@@ -60,13 +60,15 @@ class BaseTrainer(ABC):
         self.stop_fn, self.cost_limit = stop_fn, cost_limit
         self.verbose, self.show_progress, self.resume_from_log = verbose, show_progress, resume_from_log
         # run state
-        self.start_epoch = 0
+        self.start_epoch, self._start_step = 0, 0     # a resume moves both
         self.epoch, self.stop_fn_flag = self.start_epoch, False
         self.env_step, self.cum_cost, self.cum_episode = 0, 0, 0
         self._best, self._clock = _Best(cost_limit), _Clock()
         self._acc: Dict[str, float] = {}     # this rank's sums of the current epoch (parallel.EPOCH_KEYS)
         self.job_stats: Dict[str, float] = {}   # last epoch's job-level figures (all ranks; == this rank's alone)
         self.rank, self.world = parallel.rank_world()
+        if resume_from_log:
+            self._resume()
 
     # attributes the reference exposes under these names
     best_perf_rew = property(lambda self: self._best.reward)
@@ -74,9 +76,43 @@ class BaseTrainer(ABC):
     update_time = property(lambda self: self._clock.in_update)
     start_time = property(lambda self: self._clock.t0)
 
+    # ------------------------------------------------------------------ training state (resume)
+    def state_dict(self) -> Dict[str, Any]:
+        """The run's counters and its best result: what a resumed run continues from (the policy's state travels separately)."""
+        return {"epoch": int(self.epoch), "env_step": int(self.env_step), "cum_cost": self.cum_cost, "cum_episode": int(self.cum_episode),
+                "best_reward": float(self._best.reward), "best_cost": float(self._best.cost)}
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        self.start_epoch = self.epoch = int(state["epoch"])
+        self._start_step = self.env_step = int(state["env_step"])
+        self.cum_cost, self.cum_episode = state["cum_cost"], int(state["cum_episode"])
+        self._best.reward, self._best.cost = float(state["best_reward"]), float(state["best_cost"])
+
+    def train_state(self, with_store: bool = True) -> Dict[str, Any]:
+        """what the logger saves as train_state.pt (BaseLogger.setup_train_state_fn)"""
+        return {"trainer": self.state_dict(), "policy": self.policy.train_state_dict(with_store=with_store)}
+
+    def _resume(self) -> None:
+        """resume_from_log: continue from the logger's saved training state if it has one.  Env state is not saved anywhere:
+        the envs of a resumed run start from a reset."""
+        state = self.logger.load_train_state()
+        if state is None:
+            self.logger.print("resume: no saved training state in the log directory, starting a fresh run", "yellow")
+            return
+        self.load_state_dict(state["trainer"])
+        self.policy.load_train_state_dict(state["policy"])
+        buf = getattr(self.train_collector, "buffer", None)
+        if hasattr(buf, "resync"):
+            buf.resync()                         # the proxy's mirror of the store's geometry and fill levels
+        self.on_resumed(state)
+        self.logger.print(f"resume: continuing after epoch {self.epoch} at env step {self.env_step}", "green")
+
+    def on_resumed(self, state: Dict[str, Any]) -> None:
+        """hook: the saved state has just been loaded, nothing has been collected yet"""
+
     # ------------------------------------------------------------------ iteration protocol
     def reset(self) -> None:
-        self.env_step, self.epoch, self.stop_fn_flag = 0, self.start_epoch, False
+        self.env_step, self.epoch, self.stop_fn_flag = self._start_step, self.start_epoch, False
         self._clock.restart()
         self.train_collector.reset_stat()
         if self.test_collector is not None:
@@ -143,6 +179,8 @@ class BaseTrainer(ABC):
             self.logger.save_checkpoint()
         if self.perf_is_better(test=True):
             self.logger.save_checkpoint(suffix="best")
+        if self.epoch % self.save_model_interval == 0:
+            self.logger.save_train_state()       # behind the best-so-far update it carries; not saved for `best`
         stop_here = self.stop_fn is not None and self.stop_fn(self._best.reward, self._best.cost)
         # ---- the one exchange step of the multi-GPU layout: the epoch vector, all-reduced over the ranks.
         # The loss means come from this rank's logger (per-step rows of the epoch), weighted by its optimiser steps.

@@ -39,7 +39,9 @@ class BaseLogger:
         self.name = time.strftime("%Y-%m-%d_exp") if name is None else name
         self.log_dir = None if log_dir is None else os.path.join(log_dir, self.name)
         self.checkpoint_fn: Optional[Callable] = None
+        self.train_state_fn: Optional[Callable] = None
         self._table = None                     # progress.txt, opened lazily with its header row
+        self._resumed = False                  # load_train_state found a state: progress.txt is continued, not restarted
         self._want_table = bool(log_txt and self.log_dir)
         if self.log_dir:
             os.makedirs(self.log_dir, exist_ok=True)
@@ -87,8 +89,11 @@ class BaseLogger:
         if self._want_table:
             keys = list(self.logger_keys)
             if self._table is None:
-                self._table = open(os.path.join(self.log_dir, "progress.txt"), "w")
-                self._table.write("\t".join(["Steps"] + keys) + "\n")
+                path = os.path.join(self.log_dir, "progress.txt")
+                append = self._resumed and os.path.exists(path) and os.path.getsize(path) > 0
+                self._table = open(path, "a" if append else "w")
+                if not append:                 # a resumed run continues the table under the header it has
+                    self._table.write("\t".join(["Steps"] + keys) + "\n")
             self._table.write("\t".join(str(v) for v in [step] + self.get_mean_list(keys)) + "\n")
             self._table.flush()
         if display:
@@ -120,6 +125,41 @@ class BaseLogger:
         tag = "" if suffix is None else "_" + (str(suffix) if not isinstance(suffix, int) else "%d" % suffix)
         torch.save(self.checkpoint_fn(), os.path.join(folder, "model" + tag + ".pt"))
 
+    # ------------------------------------------------------------------ training state (resume)
+    def setup_train_state_fn(self, train_state_fn: Optional[Callable] = None) -> None:
+        """`train_state_fn()` -> what `save_train_state` pickles: the trainer's and the policy's training state"""
+        self.train_state_fn = train_state_fn
+
+    @property
+    def train_state_path(self) -> Optional[str]:
+        return None if not self.log_dir else os.path.join(self.log_dir, "checkpoint", "train_state.pt")
+
+    def save_train_state(self) -> None:
+        """<log_dir>/checkpoint/train_state.pt, written under a temporary name and moved into place: a run killed while it
+        writes (or a writer that raises) leaves the previous file whole."""
+        if not (self.train_state_fn and self.log_dir):
+            return
+        import torch
+        path = self.train_state_path
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        tmp = path + ".tmp"
+        try:
+            torch.save(self.train_state_fn(), tmp)
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+    def load_train_state(self):
+        """-> what the last `save_train_state` of this log_dir wrote, or None; progress.txt is then appended to."""
+        path = self.train_state_path
+        if path is None or not os.path.exists(path):
+            return None
+        import torch
+        state = torch.load(path, map_location="cpu", weights_only=False)
+        self._resumed = True
+        return state
+
     def save_config(self, config: dict, verbose=True) -> None:
         if self.log_dir:
             import yaml
@@ -139,6 +179,7 @@ class DummyLogger(BaseLogger):
 
     def __init__(self, *args, **kwarg) -> None:
         self.name, self.log_dir, self.checkpoint_fn = "dummy", None, None
+        self.train_state_fn, self._resumed = None, False
         self._table, self._want_table = None, False
         self.reset_data()
 
@@ -156,6 +197,15 @@ class DummyLogger(BaseLogger):
 
     def save_checkpoint(self, *args, **kwarg) -> None:
         pass
+
+    def setup_train_state_fn(self, *args, **kwarg) -> None:
+        pass
+
+    def save_train_state(self, *args, **kwarg) -> None:
+        pass
+
+    def load_train_state(self, *args, **kwarg) -> None:
+        return None
 
     def get_mean(self, key: str) -> float:
         return 0.0

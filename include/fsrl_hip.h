@@ -128,6 +128,32 @@ int fsrl_optim_reset(fsrl_ctx* ctx);                /* zero Adam moments and ste
  * equivalent); bench.py restores the same start state before every timed update with it.                                */
 int fsrl_state_snapshot(fsrl_ctx* ctx);
 int fsrl_state_restore(fsrl_ctx* ctx);
+/* The FULL training state of a context as bytes, for a run that is to continue in another process exactly as it would have
+ * here: parameters (with their device-layout mirrors), every Adam moment and step counter, the optimiser groups' current
+ * rates (fsrl_set_lr), the collector's noise stream and the minibatch shuffle stream, the return statistics; FOCOPS: nu and
+ * its step counters; CPO / TRPO-Lag: the critics' step counter; replay contexts: actor / critics / targets, the
+ * temperature and the CVPO duals with their Adam state, the update counter and the sampler's Philox key.  with_store != 0
+ * adds the transition store: its geometry, every sub-buffer's bookkeeping (the episode in progress included) and the live
+ * rows of the six columns.  Hyper-parameters are NOT state: they come from the importing context's own configuration.
+ *   blob = header (magic, version, flags, the FINGERPRINT of everything the layout depends on: algorithm and mode, fused
+ *          or layered, obs_dim, act_dim, hidden widths, n_critics, env_num, allocated store rows, rew_norm, Q-networks)
+ *          | tagged sections (tag, length, payload zero-padded to 8 bytes) | 64-bit checksum.
+ * A pure function of the state: export(import(b)) == b byte for byte.  DESIGN.md has the inventory.
+ * size: the bytes an export would write now (< 0: an error code).  export: flushes the staging window first; writes
+ * *written <= cap bytes.  import: checks magic, version, checksum, the fingerprint field by field (the error names the
+ * first field that differs, with both values), the section list (unknown / duplicate / missing tag, wrong length, a
+ * length past the end) and the store's bookkeeping BEFORE it writes anything: a refused import (FSRL_EINVAL) leaves the
+ * context exactly as it was.  A blob without the store leaves the context's store untouched.  copy: the same state
+ * device-to-device between two contexts of equal fingerprint on one device.
+ * import and copy (into dst) invalidate what is derived from the state: the current batch, the HBM snapshot of
+ * fsrl_state_snapshot, cached Hessian operands, a prefetched sample, the device copies of the sub-buffer books; rows of
+ * the SAC statistics ring that were not drained yet are dropped.  export, import and copy end a resident actor kernel that holds the
+ * context's weights (its own, its group's, its collect group's); none may be called inside an update (FSRL_ESTATE).
+ * Members of a group may export and import between grouped calls.  Env state is not part of any of this.             */
+int64_t fsrl_train_state_size(fsrl_ctx* ctx, int32_t with_store);
+int fsrl_train_state_export(fsrl_ctx* ctx, int32_t with_store, void* out, int64_t cap, int64_t* written);
+int fsrl_train_state_import(fsrl_ctx* ctx, const void* blob, int64_t n);
+int fsrl_train_state_copy(fsrl_ctx* dst, fsrl_ctx* src, int32_t with_store);
 /* lr_scheduler.step() at the end of BasePolicy.update (fsrl/policy/base_policy.py:352-354): the caller's torch
  * scheduler owns the schedule, this call moves the new rate of one optimiser into the engine; it applies from the next
  * optimiser step.  group: on-policy contexts 0 (the one Adam; for CPO / TRPO-Lag the critics' Adam); FOCOPS 0 actor,
