@@ -206,6 +206,19 @@ SIGNATURES = {
     "fsrl_metrics_allreduce": (C.c_int, [_ctx, _d, C.c_int32]),
     "fsrl_comm_info": (C.c_int, [_ctx, _i32, _i32]),
     "fsrl_comm_destroy": (C.c_int, [_ctx]),
+    "fsrl_traj_create": (C.c_int, [_ctx, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f, _f, _P(_ctx)]),
+    "fsrl_traj_destroy": (C.c_int, [_ctx]),
+    "fsrl_traj_attach": (C.c_int, [_ctx, _ctx, _i32]),
+    "fsrl_traj_detach": (C.c_int, [_ctx, _ctx]),
+    "fsrl_traj_abandon": (C.c_int, [_ctx, _ctx]),
+    "fsrl_traj_set_window": (C.c_int, [_ctx, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "fsrl_traj_flush": (C.c_int, [_ctx]),
+    "fsrl_traj_episodes": (C.c_int, [_ctx, C.c_int64, _i32, _i32, _d, _d, _i32, _i64]),
+    "fsrl_traj_keep": (C.c_int, [_ctx, _i32, C.c_int64]),
+    "fsrl_traj_replace": (C.c_int, [_ctx, C.c_int32]),
+    "fsrl_traj_export": (C.c_int, [_ctx, _f, _f, _f, _d, _d, _u8, _u8, C.c_int64, _i64]),
+    "fsrl_traj_clear": (C.c_int, [_ctx]),
+    "fsrl_traj_counters": (C.c_int, [_ctx, _i64, C.c_int32]),
     "fsrl_set_profiling": (C.c_int, [_ctx, C.c_int]),
     "fsrl_last_timing": (C.c_int, [_ctx, _d, C.c_int32]),
 }

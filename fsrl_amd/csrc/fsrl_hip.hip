@@ -207,6 +207,7 @@ struct fsrl_ctx {
                                     // steps, line-search steps): TrState::rd_version == theta_version <=> mean_old / std_old of the
                                     // trust-region batch were computed at the CURRENT theta (the Gauss-Newton form of the KL product)
     void* sac = nullptr;            // SacState, owned
+    struct fsrl_tap* tap = nullptr; // the trajectory archive's tap on this context's store ingest (host_traj.inc), owned by the archive
 };
 static bool ctx_is_replay(const fsrl_ctx* c);
 static void sac_free(fsrl_ctx* c);
@@ -225,6 +226,11 @@ static int lay_ppo_steps(fsrl_ctx* c);
 struct InferArgs;
 static int lay_infer(fsrl_ctx* c, const InferArgs& ia, int jobs_y, hipStream_t s);
 static void comm_free(fsrl_ctx* c);
+// the trajectory tap (host_traj.inc): every row fsrl_store_push stages, every window flush_stage sends
+static inline bool tap_closed(const fsrl_ctx* c, int e);
+static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, bool done);
+static int tap_flush(fsrl_ctx* c, int w, const uint8_t* recs_d, int stage_rec, int k);
+static void tap_ctx_gone(fsrl_ctx* c);           // a context destroyed before the archive it feeds
 static int focops_pass(fsrl_ctx* c, int32_t* stopped_out);
 static int pass_verdict(fsrl_ctx* c, int32_t* stopped_out);
 
@@ -495,6 +501,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (c->sac_group) sac_group_detach(c);
     if (c->cvpo_group) cvpo_group_detach(c);
     if (c->cgroup) collect_group_detach(c);
+    if (c->tap) tap_ctx_gone(c);            // ... before the trajectory archive it feeds: finished episodes are archived, the tap goes
     comm_free(c);
     tr_free(c);
     sac_free(c);
@@ -780,6 +787,9 @@ static int flush_stage(fsrl_ctx* c) {
     const int blocks = std::min(1024, (k * per + 255) / 256);
     hipLaunchKernelGGL(store_scatter_kernel, dim3(blocks), dim3(256), 0, c->side, c->st, s.d, (int)rec, k, Do, Da);
     HIPCHK(hipGetLastError());
+    // the tap's copy and launches go behind the window's own, before the event that frees the window's pinned memory (the tap's
+    // too); an archive without room fails the call AFTER the window's bookkeeping is complete
+    const int tap_rc = c->tap ? tap_flush(c, c->cur_stage, s.d, (int)rec, k) : 0;
     HIPCHK(hipEventRecord(s.done, c->side));
     s.in_flight = true;
     s.count = 0;
@@ -790,7 +800,7 @@ static int flush_stage(fsrl_ctx* c) {
         HIPCHK(hipEventSynchronize(nx.done));
         nx.in_flight = false;
     }
-    return 0;
+    return tap_rc;
 }
 
 extern "C" int fsrl_store_push(fsrl_ctx* c, const int32_t* env_ids, int32_t k, const float* obs,
@@ -810,7 +820,9 @@ extern "C" int fsrl_store_push(fsrl_ctx* c, const int32_t* env_ids, int32_t k, c
         // flush when the window is full -- or when this sub-buffer would wrap onto a slot that is
         // already in the window: the scatter kernel writes a window's rows in parallel, so one slot
         // must not appear twice in it (windows themselves are ordered on the side stream)
-        if (c->stage[c->cur_stage].count == fsrl_ctx::STAGE_CAP || c->env[e].staged == c->sub_size) {
+        // (tapped contexts: or when two episodes of this env ended inside the window -- both of its slots of the open-episode
+        // area hold rows of it, host_traj.inc)
+        if (c->stage[c->cur_stage].count == fsrl_ctx::STAGE_CAP || c->env[e].staged == c->sub_size || (c->tap && tap_closed(c, e))) {
             int rc = flush_stage(c);
             if (rc) return rc;
         }
@@ -831,6 +843,7 @@ extern "C" int fsrl_store_push(fsrl_ctx* c, const int32_t* env_ids, int32_t k, c
             memcpy(r + 24 + (size_t)Do * 8, act + (size_t)j * Da, (size_t)Da * 4);
         }
         c->h_flags[(size_t)gptr] = fl;
+        if (c->tap) tap_row(c, e, i, act + (size_t)j * Da, rew[j], cost ? cost[j] : 0.0, fl != 0);
         // ReplayBuffer.add bookkeeping (ptr, ep_rew, ep_len, ep_idx)
         eb.last_index = ptr;
         eb.size = std::min(eb.size + 1, c->sub_size);
@@ -1583,4 +1596,5 @@ extern "C" float fsrl_get_lr(const fsrl_ctx* c, int32_t group) {
     return group == 0 ? c->cfg.lr : -1.0f;
 }
 
+#include "host_traj.inc"
 #include "host_train_state.inc"

@@ -6,4 +6,6 @@ install(__name__, globals(), {
     "HipVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
     "GroupCollector": "group_collector",
+    "BasicCollector": "basic_collector",
+    "TrajectoryBuffer": "traj_buf",
 })

@@ -55,9 +55,14 @@ class FastCollector:
         self.preprocess_fn = preprocess_fn
         self.exploration_noise = exploration_noise
         self._action_space = env.action_space
+        self.traj_buffer = None              # set by TrajectoryBuffer.attach(collector); attach(policy) sets policy.traj_buffer
         if buffer is not None:
             assert buffer.buffer_num >= self.env_num
         self.reset(False)
+
+    def _traj_buffer(self):
+        """the TrajectoryBuffer that records this collector's rows: attached to the collector, or to its policy"""
+        return self.traj_buffer if self.traj_buffer is not None else getattr(self.policy, "traj_buffer", None)
 
     # ------------------------------------------------------------------ resets
     def reset(self, reset_buffer: bool = True, gym_reset_kwargs: Optional[Dict[str, Any]] = None) -> None:
@@ -76,6 +81,9 @@ class FastCollector:
     def reset_env(self, gym_reset_kwargs: Optional[Dict[str, Any]] = None) -> None:
         obs, info = self.env.reset(**(gym_reset_kwargs or {}))
         self._obs = np.asarray(obs)
+        tb = self._traj_buffer()
+        if tb is not None and self.buffer is not None:          # episodes cut short by this reset are no trajectories
+            tb.abandon(self)
 
     # ------------------------------------------------------------------ collect
     def collect(self, n_episode: int = 1, random: bool = False, render: bool = False,
@@ -83,7 +91,11 @@ class FastCollector:
         """fsrl/data/fast_collector.py:252-368.  With the actor on the device the resident actor kernel (fsrl_actor_set_resident) lives
         for the length of this call: the native loops end it themselves, the interpreted ones through fsrl_actor_release here."""
         try:
-            return self._collect(n_episode, random, render, no_grad, gym_reset_kwargs)
+            result = self._collect(n_episode, random, render, no_grad, gym_reset_kwargs)
+            tb = self._traj_buffer()
+            if tb is not None and self.buffer is not None:      # TrajectoryBuffer.attach: its keep / filter decisions, once per collect
+                tb.sync()
+            return result
         finally:
             if self.device_actor:
                 self.policy.engine.actor_release()

@@ -42,7 +42,10 @@ class GroupCollector:
         """FastCollector.collect(n_episode) of every member (n_episode: one count or one per member) -> one stats dict per member.
         The group's resident actor kernel lives for the length of this call."""
         try:
-            return self._collect(n_episode)
+            stats = self._collect(n_episode)
+            for buf in {id(b): b for b in (c._traj_buffer() for c in self.collectors) if b is not None}.values():
+                buf.sync()          # TrajectoryBuffer.attach(collector): its keep / filter decisions, once per collect
+            return stats
         finally:
             self.group.actor_release()
 

@@ -753,6 +753,101 @@ class Engine:
                     fwdbwd_raw_ms=out[4])
 
 
+TRAJ_COLUMNS = ("observations", "next_observations", "actions", "rewards", "costs", "terminals", "timeouts")
+TRAJ_COUNTERS = ("committed", "rejected_window", "dropped_long", "compactions", "rows", "refused_full", "episodes", "launches",
+                 "h2d_bytes", "abandoned")
+
+
+class TrajArchive:
+    """One fsrl_traj (include/fsrl_hip.h): finished episodes of the engines that feed it, in HBM, in the DSRL column layout.
+    Plumbing like Engine: every method forwards to one entry point.  fsrl_amd.data.TrajectoryBuffer puts the reference's
+    semantics on top."""
+
+    def __init__(self, engine: "Engine", max_rows: int, max_episodes: int, max_episode_len: int, bound_method: int = 1,
+                 low=None, high=None):
+        self.lib = engine.lib
+        self.obs_dim, self.act_dim = engine.cfg.obs_dim, engine.cfg.act_dim
+        self.max_rows, self.max_episodes, self.max_episode_len = int(max_rows), int(max_episodes), int(max_episode_len)
+        lo = None if low is None else np.ascontiguousarray(np.broadcast_to(np.asarray(low, np.float32), (self.act_dim,)))
+        hi = None if low is None else np.ascontiguousarray(np.broadcast_to(np.asarray(high, np.float32), (self.act_dim,)))
+        self._t = C.c_void_p()
+        _lib.check(self.lib.fsrl_traj_create(engine._ctx, self.max_rows, self.max_episodes, self.max_episode_len, int(bound_method),
+                                             _ptr(lo, _f32p), _ptr(hi, _f32p), C.byref(self._t)))
+
+    def close(self):
+        if getattr(self, "_t", None) is not None and self._t:
+            self.lib.fsrl_traj_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def attach(self, engine: "Engine") -> int:
+        """-> the source number the episodes of `engine` carry"""
+        src = C.c_int32()
+        _lib.check(self.lib.fsrl_traj_attach(self._t, engine._ctx, C.byref(src)))
+        return int(src.value)
+
+    def detach(self, engine: "Engine") -> None:
+        _lib.check(self.lib.fsrl_traj_detach(self._t, engine._ctx))
+
+    def abandon(self, engine: "Engine") -> None:
+        """the open episodes of `engine` are discarded: its envs were reset in mid-episode"""
+        _lib.check(self.lib.fsrl_traj_abandon(self._t, engine._ctx))
+
+    def set_window(self, rmin, rmax, cmin, cmax):
+        _lib.check(self.lib.fsrl_traj_set_window(self._t, float(rmin), float(rmax), float(cmin), float(cmax)))
+
+    def flush(self):
+        _lib.check(self.lib.fsrl_traj_flush(self._t))
+
+    def episodes(self):
+        """-> (ids, rows, reward returns, cost returns, sources) of the alive episodes in table order, as of the last flush"""
+        n = C.c_int64()
+        _lib.check(self.lib.fsrl_traj_episodes(self._t, 0, None, None, None, None, None, C.byref(n)))
+        k = max(int(n.value), 1)
+        ids, rows, src = np.empty(k, np.int32), np.empty(k, np.int32), np.empty(k, np.int32)
+        rew, cost = np.empty(k, np.float64), np.empty(k, np.float64)
+        _lib.check(self.lib.fsrl_traj_episodes(self._t, k, _ptr(ids, _i32p), _ptr(rows, _i32p), _ptr(rew, _f64p), _ptr(cost, _f64p),
+                                               _ptr(src, _i32p), C.byref(n)))
+        k = int(n.value)
+        return ids[:k], rows[:k], rew[:k], cost[:k], src[:k]
+
+    def keep(self, ids):
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        _lib.check(self.lib.fsrl_traj_keep(self._t, _ptr(ids, _i32p) if ids.size else None, ids.size))
+
+    def replace(self, victim_id: int):
+        _lib.check(self.lib.fsrl_traj_replace(self._t, int(victim_id)))
+
+    def export(self):
+        """-> dict of the seven DSRL columns (numpy), alive episodes in table order"""
+        n = C.c_int64()
+        _lib.check(self.lib.fsrl_traj_export(self._t, None, None, None, None, None, None, None, 0, C.byref(n)))
+        k = int(n.value)
+        out = dict(observations=np.empty((k, self.obs_dim), np.float32), next_observations=np.empty((k, self.obs_dim), np.float32),
+                   actions=np.empty((k, self.act_dim), np.float32), rewards=np.empty(k, np.float64), costs=np.empty(k, np.float64),
+                   terminals=np.empty(k, np.uint8), timeouts=np.empty(k, np.uint8))
+        if k:
+            _lib.check(self.lib.fsrl_traj_export(
+                self._t, _ptr(out["observations"], _f32p), _ptr(out["next_observations"], _f32p), _ptr(out["actions"], _f32p),
+                _ptr(out["rewards"], _f64p), _ptr(out["costs"], _f64p), _ptr(out["terminals"], _u8p), _ptr(out["timeouts"], _u8p),
+                k, C.byref(n)))
+        out["terminals"] = out["terminals"].astype(bool); out["timeouts"] = out["timeouts"].astype(bool)
+        return out
+
+    def clear(self):
+        _lib.check(self.lib.fsrl_traj_clear(self._t))
+
+    def counters(self) -> dict:
+        out = np.zeros(len(TRAJ_COUNTERS), np.int64)
+        _lib.check(self.lib.fsrl_traj_counters(self._t, _ptr(out, _i64p), out.size))
+        return dict(zip(TRAJ_COUNTERS, (int(v) for v in out)))
+
+
 class _NativeGroup:
     """`engines`, `lib` and the native handle `_g` of a group made by `<_symbols>_create` and freed by `<_symbols>_destroy`"""
     _symbols = ""                       # the C ABI prefix of the group: fsrl_group, fsrl_sac_group, ...

@@ -820,6 +820,65 @@ int fsrl_metrics_allreduce(fsrl_ctx* ctx, double* v, int32_t n);
 int fsrl_comm_info(const fsrl_ctx* ctx, int32_t* rank_out, int32_t* world_out);
 int fsrl_comm_destroy(fsrl_ctx* ctx);
 
+/* ---- the trajectory archive (fsrl/data/traj_buf.py TrajectoryBuffer, fed as basic_collector.py:238-248 feeds it): every finished
+ *      episode of the contexts that feed it, kept in HBM in the DSRL column layout -- observations / next_observations [rows][obs_dim]
+ *      and actions [rows][act_dim] float32, rewards / costs float64, terminals / timeouts uint8 -- until fsrl_traj_export.
+ *      A context that feeds an archive has a TAP on its store ingest: every row that goes through fsrl_store_push (so every collect
+ *      call, solo, grouped or over worker-process envs) also reaches the archive, whatever the store's geometry does meanwhile
+ *      (fsrl_store_reset, fsrl_store_configure, a sub-buffer that wraps).  The rows of an env are gathered in an open-episode area;
+ *      when the episode ends its float64 reward and cost returns (sums in push order, as `current_rew += rew.item()`) are held
+ *      against the window (traj_buf.py:71-73) and the episode is appended to the archive -- or dropped.  An episode that is still
+ *      open is never exported.  The `actions` column holds the action the ENV received: BasePolicy.map_action (bound_method 0 none /
+ *      1 clip / 2 tanh, then act_low / act_high, NULL = no scaling) of the pushed action, the very function -- and so bit for bit the
+ *      values -- fsrl_collect_step hands out as env_act.  The store keeps the raw policy action, as before.
+ *      Episodes longer than max_episode_len are dropped (and counted); the episode after one is intact.  The archive never
+ *      overwrites: when an episode does not fit max_rows it compacts (dead rows come from fsrl_traj_keep / _replace), and when it
+ *      still does not fit the push (or flush) that ends the episode returns FSRL_ENOMEM, the message naming max_rows; the episode
+ *      is dropped and counted.  Episode ids are the commit serial numbers, from 0, over all sources.
+ *      A context without a tap runs the code it ran before taps existed.  The archive is no part of fsrl_train_state_export.
+ *      Not thread safe: the calls of one archive and the pushes of the contexts that feed it come from one thread.
+ *
+ *      fsrl_traj_create   ctx gives the device and (obs_dim, act_dim); it is NOT attached.  Memory: two sets of columns of max_rows
+ *                         rows (a compaction copies from one to the other, so no run overlaps its destination).
+ *      fsrl_traj_attach   a context has at most one tap; several contexts of one (obs_dim, act_dim) on the archive's device may feed
+ *                         one archive (the seeds of a group).  Another shape or device: FSRL_EINVAL naming the field.  *source_out
+ *                         (may be NULL): the number the episodes of this context carry (0, 1, ... in attach order).  Allocates the
+ *                         context's open-episode area: 2 x env_num x max_episode_len rows.
+ *      fsrl_traj_detach   finished episodes are archived first; open ones are discarded.  A context destroyed while attached detaches
+ *                         itself; an archive destroyed first leaves its contexts untapped.
+ *      fsrl_traj_abandon  the open episodes of this context are discarded (and counted): its envs were reset in mid-episode, as a
+ *                         collector does at the end of a collect with the envs that were not needed for the episode count.
+ *      fsrl_traj_flush    the synchronisation point: every row pushed so far is in the archive or in an open episode, and the device
+ *                         work is complete.  _episodes and _counters report the state as of the last flush (_keep, _replace, _export
+ *                         and _clear flush themselves).
+ *      fsrl_traj_episodes the alive episodes in table order (commit order until _keep / _replace change it): id, rows, reward return,
+ *                         cost return, source; every output may be NULL, *n_out is always set.
+ *      fsrl_traj_keep     only these ids stay alive, in the order given = the new table order; the archive is compacted.
+ *      fsrl_traj_replace  the newest episode takes victim_id's place in table order (traj_buf.py:89-93); the victim is dead.
+ *      fsrl_traj_export   the alive episodes in table order, rows contiguous and chronological inside an episode: plain device-to-host
+ *                         copies of the compacted columns.  Every column may be NULL (all NULL: only *rows_out).
+ *      fsrl_traj_clear    drops every archived episode; open episodes go on.
+ *      fsrl_traj_counters out[0..n): episodes committed, rejected by the window, dropped as longer than max_episode_len, compactions,
+ *                         rows alive, episodes refused for lack of room, episodes alive, tap launches, tap host-to-device bytes, open
+ *                         episodes abandoned.  */
+typedef struct fsrl_traj fsrl_traj;
+int fsrl_traj_create(fsrl_ctx* ctx, int64_t max_rows, int32_t max_episodes, int32_t max_episode_len, int32_t bound_method,
+                     const float* act_low, const float* act_high, fsrl_traj** out);
+int fsrl_traj_destroy(fsrl_traj* t);
+int fsrl_traj_attach(fsrl_traj* t, fsrl_ctx* ctx, int32_t* source_out);
+int fsrl_traj_detach(fsrl_traj* t, fsrl_ctx* ctx);
+int fsrl_traj_abandon(fsrl_traj* t, fsrl_ctx* ctx);
+int fsrl_traj_set_window(fsrl_traj* t, double rmin, double rmax, double cmin, double cmax);
+int fsrl_traj_flush(fsrl_traj* t);
+int fsrl_traj_episodes(fsrl_traj* t, int64_t cap, int32_t* ids_out, int32_t* rows_out, double* rew_out, double* cost_out,
+                       int32_t* source_out, int64_t* n_out);
+int fsrl_traj_keep(fsrl_traj* t, const int32_t* episode_ids, int64_t n);
+int fsrl_traj_replace(fsrl_traj* t, int32_t victim_id);
+int fsrl_traj_export(fsrl_traj* t, float* obs, float* next_obs, float* act, double* rew, double* cost, uint8_t* terminals,
+                     uint8_t* timeouts, int64_t rows_cap, int64_t* rows_out);
+int fsrl_traj_clear(fsrl_traj* t);
+int fsrl_traj_counters(fsrl_traj* t, int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
