@@ -182,7 +182,8 @@ struct fsrl_ctx {
     int pa_cap = 0;
     void* h_pa = nullptr;           // pinned: [bell 8 B | pad | done[4] at 16 | state[4] at 32 | pad to 64 B | obs cap x Do | mu cap x Da | sigma_param]
     // timing-probe switches: always 0 / false in the shipped library; a -DFSRL_PROBES build reads them ONCE, at
-    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_TILE16 / FSRL_WGRAD_SKIP / FSRL_NO_SPIN (tools/phase_probe.sh)
+    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_WGRAD_SKIP / FSRL_NO_SPIN / ... (tools/phase_probe.sh).  Two switches are read by
+    // every build, the shipped library included: FSRL_TILE16 (probe_tile16) and FSRL_NO_W2B_EARLY (no_w2b_early)
     int probe_phase = 0, probe_wgrad_skip = 0;
     unsigned long long* probe_ts = nullptr;   // probe builds: [1024][16] phase stamps of the last fused-kernel launch
     bool probe_tile16 = false;
@@ -191,6 +192,7 @@ struct fsrl_ctx {
     struct fsrl_collect_group* cgroup = nullptr;     // the collect group this context is a member of (host_collect_group.inc: replay or on-policy members)
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
+    bool no_w2b_early = false;      // every build: FSRL_NO_W2B_EARLY launches the fused forward/backward kernel with its backward W2 fragment in one burst (A/B, bit-compare)
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
     bool no_spin = false;           // wait for the collector's actor with hipStreamSynchronize instead of the completion words
     std::vector<float> act_mu, act_sg;                   // mean / std of the last actor evaluation (host)
@@ -601,10 +603,13 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->h1 = h1_; c->h2 = h2_;
     c->device = device_id;
     c->n_cus = n_cus_probe > 0 ? n_cus_probe : 256;
-    // the one switch the shipped library reads: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
+    // the two switches the shipped library reads.  FSRL_TILE16: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
     // run sixteen-row tiles from a few members on; a single context created under FSRL_TILE16 is their exact twin
     // (tests/test_gpu_cvpo_group.py).  Results stay valid, a small batch only gets slower.
     c->probe_tile16 = getenv("FSRL_TILE16") != nullptr;
+    // FSRL_NO_W2B_EARLY: the single-agent PPO step launches ppo_fwd_bwd_kernel<H, 4 | 8> without the early issue of the backward W2
+    // fragment (kernels_mlp.hpp: W2bEarly) -- the same arithmetic, the twin of tests/test_gpu_ppo_w2b_early.py and of same-build A/B runs
+    c->no_w2b_early = getenv("FSRL_NO_W2B_EARLY") != nullptr;
 #ifdef FSRL_PROBES
     { const char* e = getenv("FSRL_DBG_PHASE"); c->probe_phase = e ? atoi(e) : 0; }
     { const char* e = getenv("FSRL_WGRAD_SKIP"); c->probe_wgrad_skip = e ? atoi(e) : 0; }

@@ -375,7 +375,12 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
             // one network per XCD pair (see ppo_fwd_bwd_body): grid = 8 x ceil(tiles / 2), the blocks of XCD pairs beyond the networks exit
             sa.xcd_pair = (nn <= 4 && !c->no_xcd_pair) ? 1 : 0;
             auto fb_grid = [&](int nt) { return sa.xcd_pair ? dim3(8 * ((nt + 1) / 2)) : dim3(nt * nn); };
-            if (tp.rows4) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 4>), fb_grid(tiles * 4), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
+            // 4- and 8-row tiles: part of the backward W2 fragment trickles in under the forward pass (W2bEarly, kernels_mlp.hpp);
+            // FSRL_NO_W2B_EARLY launches the one-burst instantiation (A/B; same bits)
+            const bool early = !c->no_w2b_early;
+            if (tp.rows4 && early) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 4, true>), fb_grid(tiles * 4), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
+            else if (tp.rows4) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 4>), fb_grid(tiles * 4), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
+            else if (tp.rows8 && early) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 8, true>), fb_grid(tiles * 2), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
             else if (tp.rows8) hipLaunchKernelGGL((ppo_fwd_bwd_kernel<HH, 8>), fb_grid(tiles * 2), dim3(4 * HH), 0, s, c->P, c->md, bp, sa);
             else if (n32 > 0) {
                 if constexpr (HH >= 128)

@@ -18,6 +18,7 @@
 //     workgroup with 16-way split-K over the waves (again: all loads of a wave in one burst),
 //     so no per-tile partial gradients ever reach HBM.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 // rows a tile of R rows needs room for: 4-, 8- and 16-row tiles share the 16-row layout, a 32-row tile (two 16-row MFMA
@@ -175,6 +176,49 @@ struct TileStage {
     }
 };
 
+// Hooks of tile_forward's 4- and 8-row layer-2 path: a caller can issue loads of its own from inside the forward pass, where the CU's
+// vector-memory path is idle.  mfma_iter(kc) runs behind the MFMAs of k-chunk kc, phase(0) behind the MFMA loop, phase(1) behind the h2
+// hand-off (in front of its barrier), phase(2) behind that barrier, in front of the head.  FwdNoHook: nothing (every caller but the
+// single-agent PPO step).
+struct FwdNoHook {
+    __device__ __forceinline__ void mfma_iter(int) const {}
+    __device__ __forceinline__ void phase(int) const {}
+};
+
+// The early part of the backward W2 fragment of ppo_fwd_bwd_body (rows jc < JE of wb[H/16][4]), trickled in under the forward pass at
+// a rate the CU's memory queue never fills at: one jc row (4 dwords per lane = 1 KB per wave) behind every LOOP_EVERY-th MFMA
+// iteration, then up to PHASE_ROWS rows at each of the three phase points, until the fragment's H / 16 rows are out (H = 256: 8 rows
+// in the loop, then 3 + 3 + 2: JE = 16, nothing is left for the late burst; H = 128: 4, then 3 + 1; H = 64: 2, then 2).
+// DESIGN_HISTORY 3 (i-b) / (i-c) issued the whole 256 KB at the L1's full rate and only moved the stall; the measured schedules and
+// their figures are in DESIGN.md 3.1.  Addresses, values and the order in which the dz1 loop consumes wb are those of the one-burst form.  The loads keep their place: no VMEM instruction crosses the scheduling
+// barriers around a row, nor does an MFMA, and VMEM returns in order, so the waits in front of the forward fragment's uses stay
+// counted (the early rows are issued BEHIND the forward burst).
+#define FSRL_SCHED_W2B 0x106     // sched_barrier mask: VALU, SALU and LDS reads may cross (address arithmetic, the next k-chunk's operand); MFMA and VMEM may not
+template <int H>
+struct W2bEarly {
+    static constexpr int KC = H / 16;
+    static constexpr int LOOP_EVERY = 2, PHASE_ROWS = 3;
+    static constexpr int JL = KC / LOOP_EVERY;                                        // rows issued inside the MFMA loop
+    static constexpr int JE = (JL + 3 * PHASE_ROWS < KC) ? JL + 3 * PHASE_ROWS : KC;  // rows issued early at all
+    float (&wb)[KC][4];
+    const float* __restrict__ W2c;        // P + W2 + the lane's column
+    const int q;
+    __device__ __forceinline__ void row(const int jc) const {
+        __builtin_amdgcn_sched_barrier(FSRL_SCHED_W2B);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) wb[jc][s] = W2c[(size_t)(16 * jc + 4 * q + s) * H];
+        __builtin_amdgcn_sched_barrier(FSRL_SCHED_W2B);
+    }
+    __device__ __forceinline__ void mfma_iter(const int kc) const {
+        if (kc % LOOP_EVERY == LOOP_EVERY - 1) row(kc / LOOP_EVERY);
+    }
+    __device__ __forceinline__ void phase(const int p) const {
+#pragma unroll
+        for (int u = 0; u < PHASE_ROWS; ++u)
+            if (JL + p * PHASE_ROWS + u < JE) row(JL + p * PHASE_ROWS + u);
+    }
+};
+
 // ---------------------------------------------------------------- forward of one 16-row tile
 // Pre: sm.xT filled + __syncthreads() done; wf holds this wave's W2 slice (may still be in
 // flight).  Post: sm.h1, sm.h2, sm.out valid (synced).
@@ -187,10 +231,11 @@ struct TileStage {
 // WIDE_HEAD (the replay agents' actors: 2 * act_dim outputs, 16 at act_dim 8): the head Linear of a tile of up to 16 rows on MFMA, split-K
 // over the waves, partial 16 x 16 tiles through sm.d2 (free until the backward pass) -- the wave-per-(row, output) loop below takes
 // R * out / WAVES dependent LDS -> FMA -> wave_sum trips (16 at out = 16: 5 us of the actors' forward launch, phase probes r6).
-template <int H, int R = 16, bool WIDE_HEAD = false>
+template <int H, int R = 16, bool WIDE_HEAD = false, class HOOK = FwdNoHook>
 __device__ __forceinline__ void tile_forward(TileSmem<H, tile_rows(R)>& sm, const float* __restrict__ P,
                                              const NetOff no, const int Do, const int tid,
-                                             const FwdW2Frag<H>& wf, unsigned long long* ts = nullptr) {
+                                             const FwdW2Frag<H>& wf, unsigned long long* ts = nullptr, const HOOK hook = HOOK()) {
+    static_assert(R < 16 || std::is_same<HOOK, FwdNoHook>::value, "only the 4- and 8-row layer-2 path calls the hook");
     constexpr int LD = TileSmem<H>::LD;
     constexpr int WAVES = TileGeom<H>::WAVES;
     constexpr int ROWS = tile_rows(R);
@@ -280,8 +325,10 @@ __device__ __forceinline__ void tile_forward(TileSmem<H, tile_rows(R)>& sm, cons
 #pragma unroll
                 for (int s = 0; s < 4; ++s) acc8 = mfma_4x4x1(a8[s], wf.b[kc][s], acc8);
             }
+            hook.mfma_iter(kc);
         }
         FSRL_TS(ts, 4);
+        hook.phase(0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {            // add the four k-classes: (q0 + q1) + (q2 + q3)
             acc[r] += __shfl_xor(acc[r], 16, 64);
@@ -297,6 +344,7 @@ __device__ __forceinline__ void tile_forward(TileSmem<H, tile_rows(R)>& sm, cons
                 if constexpr (R == 8) sm.h2[(4 + r) * LD + j] = fmaxf(acc8[r] + bias, 0.0f);
             }
         }
+        hook.phase(1);
     } else {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};     // acc2: rows 16..31 of a 32-row tile
         const float* arow = &sm.h1[li * LD + 4 * q];
@@ -321,6 +369,7 @@ __device__ __forceinline__ void tile_forward(TileSmem<H, tile_rows(R)>& sm, cons
     }
     __syncthreads();
     FSRL_TS(ts, 5);
+    if constexpr (R < 16) hook.phase(2);
 
     if constexpr (WIDE_HEAD && R <= 16) {        // a 4- or 8-row tile runs the same 16-row MFMAs: the rows beyond R are never read back
         if (no.out > 4) {
@@ -713,7 +762,9 @@ struct PpoBatchPtrs {
 
 // R = 32 (r6, grouped launches): two 16-row MFMA passes per weight fragment; a row's arithmetic does not depend on its tile's height and
 // the per-tile statistics keep their 16-row slots (stat_tile, stat_tile + 1), so 32- and 16-row tiles mix bit-identically.
-template <int H, int R>
+// W2B_EARLY (4- and 8-row tiles of the single-agent launch): the first W2bEarly<H>::JE rows of the backward W2 fragment are issued from
+// inside the forward pass (W2bEarly above), the rest where the whole burst is issued otherwise.  Same loads, same dz1 MFMA sequence.
+template <int H, int R, bool W2B_EARLY = false>
 __device__ __forceinline__ void ppo_fwd_bwd_body(TileSmem<H, tile_rows(R)>& sm, const float* __restrict__ P, const ModelDesc& md,
                                                  const PpoBatchPtrs& bp, const PpoStepArgs& sa, int tile = -1, int net = -1,
                                                  int stat_tile = -1) {
@@ -782,7 +833,12 @@ __device__ __forceinline__ void ppo_fwd_bwd_body(TileSmem<H, tile_rows(R)>& sm, 
     __syncthreads();
     FSRL_TS(bp.ts, 2);
     if (FSRL_PROBE(sa, 1)) { if (wf.b[0][0] == 123.f && sm.xT[tid] == 1.f) bp.statp[0] = 1.f; return; }
-    tile_forward<H, R>(sm, P, no, Do, tid, wf, bp.ts);
+    static_assert(!W2B_EARLY || R < 16, "the early backward fragment rides on the 4- and 8-row forward pass");
+    constexpr int JE = W2B_EARLY ? W2bEarly<H>::JE : 0;      // rows of wb issued from inside the forward pass
+    float wb[H / 16][4];
+    const float* __restrict__ W2c = P + no.W2 + wave * 16 + li;
+    if constexpr (W2B_EARLY) tile_forward<H, R, false, W2bEarly<H>>(sm, P, no, Do, tid, wf, bp.ts, W2bEarly<H>{wb, W2c, q});
+    else tile_forward<H, R>(sm, P, no, Do, tid, wf, bp.ts);
     FSRL_TS(bp.ts, 6);
     if (FSRL_PROBE(sa, 4)) { if (sm.out[tid & 15] == 123.f) bp.statp[0] = 1.f; return; }
     const size_t nb = (size_t)net * bp.mbp_max;
@@ -799,17 +855,17 @@ __device__ __forceinline__ void ppo_fwd_bwd_body(TileSmem<H, tile_rows(R)>& sm, 
     }
 
 
-    // W2 slice for the backward GEMM dz1 = dz2 @ W2 (column block of this wave): issued now (L2-warm after the forward
-    // burst), consumed after the loss head.  The 256 KB ingest is NOT hidden by issuing it earlier: a wave stalls at a VMEM
-    // instruction while the CU's memory queue is full, so the burst costs its ~1.4 us wherever it sits (in-kernel stamps,
+    // W2 slice for the backward GEMM dz1 = dz2 @ W2 (column block of this wave): the rows the forward pass has not issued already
+    // (W2B_EARLY: W2bEarly above; otherwise all of them) are issued now (L2-warm after the forward burst), consumed after the loss
+    // head.  With W2B_EARLY the loop below is EMPTY at every width the library builds (64, 128, 256: JE == H / 16): the whole fragment is on its way already.
+    // The 256 KB ingest is NOT hidden by issuing it earlier AT THE L1's FULL RATE: a wave stalls at a VMEM
+    // instruction while the CU's memory queue is full, so the burst costs its wait (~2.7 us) wherever it sits (in-kernel stamps,
     // tools/tstamp_probe.py: right after the forward MFMA loop 25 600 cycles per workgroup, interleaved chunk by chunk
     // into that loop 24 700, here 23 900); nor by a fragment-ordered mirror (16 dwordx4 instead of 64 dword loads per
     // lane: same time in this kernel, +1.0 us in the Adam kernel that has to keep the mirror).  DESIGN.md section 3.
-    float wb[H / 16][4];
     {
-        const float* __restrict__ W2c = P + no.W2 + wave * 16 + li;
 #pragma unroll
-        for (int jc = 0; jc < H / 16; ++jc) {
+        for (int jc = JE; jc < H / 16; ++jc) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) wb[jc][s] = W2c[(size_t)(16 * jc + 4 * q + s) * H];
         }
@@ -1012,13 +1068,13 @@ __device__ __forceinline__ void ppo_fwd_bwd_body(TileSmem<H, tile_rows(R)>& sm, 
     FSRL_TS(bp.ts, 13);
 }
 
-template <int H, int R>
+template <int H, int R, bool W2B_EARLY = false>
 __global__ __launch_bounds__(4 * H) void ppo_fwd_bwd_kernel(const float* __restrict__ P,
                                                            const ModelDesc md,
                                                            const PpoBatchPtrs bp,
                                                            const PpoStepArgs sa) {
     __shared__ TileSmem<H> sm;
-    ppo_fwd_bwd_body<H, R>(sm, P, md, bp, sa);
+    ppo_fwd_bwd_body<H, R, W2B_EARLY>(sm, P, md, bp, sa);
 }
 
 // r6 (late): tall tiles.  Once a launch's 16-row tiles exceed the CU count (a group of 8 members x 3 networks x 16 tiles = 384 workgroups on
