@@ -1,15 +1,19 @@
-// group_episodes.hpp -- the bookkeeping of a lock-step collect of k members over worker-process envs: FastCollector.collect(n_episode)
-// of every member (fast_collector.py:283-368; one member: fsrl_collect_episodes, host_collect.inc) with the members' envs stepped
-// TOGETHER and ONE step call per vector step for all of them -- GroupCollector's interpreted loop (fsrl_amd/data/group_collector.py),
-// keyed by member.  Standard library only (no HIP, no fsrl_ctx): the owner supplies a view of every member's env block and two
-// callbacks, so tests/host/group_episodes_sim.cpp drives it as a plain program (tests/test_group_episodes_host.py).
-//   run_env(cmd, ids, &failed) -- post command `cmd` (GE_CMD_STEP: the actions are in the blocks already; GE_CMD_RESET) for the envs
-//            ids[m] of every member m with a non-empty list, ALL members before the first wait, and return once all of them have
-//            answered: 0, or an error with the member whose env failed in `failed`;
-//   step(s) -- fsrl_group_collect_step / fsrl_collect_group_step: store every member's s.k[m] finished rows, evaluate its actor on
-//            its s.k_act[m] rows of s.obs_act; row arrays concatenated over members: 0 or an error.
-// Per member and vector step the calls are the ones its own collect makes, in its order: same rows in the same slots, same noise
-// stream.  A member that has its episodes contributes k = 0, k_act = 0 from then on while the others go on.
+// group_episodes.hpp -- the episode loop of the native collects over worker-process envs: FastCollector.collect(n_episode)
+// (fast_collector.py:283-368) written ONCE, with three owners:
+//   ge_collect, one member   -- fsrl_collect_episodes (host_collect.inc);
+//   ge_collect, k members    -- fsrl_group_collect_episodes / fsrl_collect_episodes_group (host_group_episodes.inc): that loop keyed by
+//                               member, the members' envs stepped TOGETHER and ONE step call per vector step for all of them
+//                               (GroupCollector's interpreted loop, fsrl_amd/data/group_collector.py);
+//   ge_collect_split         -- fsrl_collect_episodes_split: one env, its two lanes out of phase, a global episode budget
+//                               (FastCollector._collect_split).
+// Both loops are made of the same three pieces per ready list and step: ge_read_rows (the step's results), ge_next_rows (reset
+// observations in place, surplus envs dropped), ge_record (the finished episodes).  Standard library only (no HIP, no fsrl_ctx): the
+// owner supplies a view of every env block and callbacks, so tests/host/group_episodes_sim.cpp drives both loops as a plain program
+// (tests/test_group_episodes_host.py).
+//   step(s)  -- fsrl_collect_step / fsrl_group_collect_step / fsrl_collect_group_step: store every member's s.k[m] finished rows,
+//               evaluate its actor on its s.k_act[m] rows of s.obs_act; row arrays concatenated over members: 0 or an error.
+// Per member (per lane) and vector step the calls are the ones the interpreted loop makes, in its order: same rows in the same
+// slots, same noise stream.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -17,18 +21,20 @@
 
 #define GE_CMD_STEP 1u
 #define GE_CMD_RESET 2u
-// argument errors (ge_collect's return; the member in *failed_member).  Callbacks return their own NEGATIVE codes, passed through.
+// the loops' own errors (positive; the member in *failed_member).  Callbacks return their own NEGATIVE codes, passed through.
 enum { GE_OK = 0, GE_BAD_ROWS = 1,              // n[m] outside 1 .. env_num
        GE_BAD_EPISODES = 2,                     // n_episode[m] < 1
        GE_BAD_ID = 3,                           // an env id outside 0 .. env_num - 1
-       GE_DUP_ID = 4 };                         // an env id listed twice
+       GE_DUP_ID = 4,                           // an env id listed twice
+       GE_BAD_LANE = 5,                         // split loop: an env's lane is neither 0 nor 1
+       GE_STALLED = 6 };                        // split loop: no lane is busy but episodes are missing (NOT an argument error)
 
 // a member's env block: what the workers write (obs, rew, cost, term, trunc: [env_num] rows) and what the collector writes (act)
 struct GeEnvView {
     const float* obs; float* act; const double* rew; const double* cost; const uint8_t* term; const uint8_t* trunc;
     int env_num;
 };
-// one lock-step step, fsrl_group_collect_step's row arguments
+// one step call, fsrl_group_collect_step's row arguments (one member: fsrl_collect_step's)
 struct GeStep {
     const int32_t* k; const int32_t* env_ids; const float* obs; const float* act; const double* rew; const double* cost;
     const uint8_t* terminated; const uint8_t* truncated; const float* obs_next; int64_t* ptr_out; double* ep_rew_out;
@@ -38,175 +44,282 @@ struct GeStep {
 struct GeOut {
     int64_t* steps; double* total_cost; int32_t* term; int32_t* trunc; double* ep_rew; int32_t* ep_len; int32_t* episodes;
 };
+// the arrays behind a GeStep, `cap` rows each (a ready list never grows).  The rows a step call acts on and the actions it answers
+// with (obs_act, act_out, env_act_out) are exactly the rows the NEXT step call stores (obs, act) and the actions the envs take in
+// between (env_act) -- for all members at once, at the same offsets: advance() swaps them instead of copying
+struct GeRows {
+    std::vector<int32_t> ids, elen;
+    std::vector<float> obs, act, env_act, obs_next, obs_act, act_out, env_act_out;
+    std::vector<double> rew, cost, erew;
+    std::vector<uint8_t> term, trunc;
+    std::vector<int64_t> ptr, eidx;
+    GeRows(size_t cap, size_t Do, size_t Da)
+        : ids(cap), elen(cap), obs(cap * Do), act(cap * Da), env_act(cap * Da), obs_next(cap * Do), obs_act(cap * Do), act_out(cap * Da),
+          env_act_out(cap * Da), rew(cap), cost(cap), erew(cap), term(cap), trunc(cap), ptr(cap), eidx(cap) {}
+    GeStep step(const int32_t* k, const int32_t* k_act) {
+        return GeStep{k, ids.data(), obs.data(), act.data(), rew.data(), cost.data(), term.data(), trunc.data(), obs_next.data(), ptr.data(),
+                      erew.data(), elen.data(), eidx.data(), k_act, obs_act.data(), act_out.data(), env_act_out.data()};
+    }
+    void advance() { obs.swap(obs_act); act.swap(act_out); env_act.swap(env_act_out); }
+};
+// a ready list on its way through the loop (a member of the lock-step loop, a lane of the split loop): the envs being stepped; after
+// the step, `local` = the rows whose episode ended (ascending) and nready = the envs to act on next.  Its rows are in a GeRows.
+struct GeList {
+    std::vector<int32_t> ready, nready, local;
+};
 
-// ready / obs: the members' rows back to back, n[m] rows each.  *failed_member: the member of an argument error or of a failed env
-// command, -1 otherwise (a failed step call has no member).  After an env error NO further step call is made.
+// the argument refusals of one ready list
+static int ge_check_list(const GeEnvView& v, const int32_t* ready, int n, int n_episode) {
+    if (n < 1 || n > v.env_num) return GE_BAD_ROWS;
+    if (n_episode < 1) return GE_BAD_EPISODES;
+    std::vector<uint8_t> seen((size_t)v.env_num, 0);
+    for (int i = 0; i < n; ++i) {
+        const int32_t e = ready[i];
+        if (e < 0 || e >= v.env_num) return GE_BAD_ID;
+        if (seen[(size_t)e]) return GE_DUP_ID;
+        seen[(size_t)e] = 1;
+    }
+    return GE_OK;
+}
+// env.step's actions: the mapped actions of q's rows (R's rows o ..) into its envs' slots
+static void ge_put_actions(const GeEnvView& v, const GeList& q, size_t Da, const GeRows& R, size_t o) {
+    for (size_t i = 0; i < q.ready.size(); ++i) memcpy(v.act + (size_t)q.ready[i] * Da, R.env_act.data() + (o + i) * Da, Da * 4);
+}
+// (1) the results of q.ready's step out of the env block into R's rows o .. (whose obs / act are the ones the step was taken on),
+//     the finished rows in q.local, member m's counters
+static void ge_read_rows(const GeEnvView& v, GeList& q, size_t Do, GeRows& R, size_t o, const GeOut& out, int m) {
+    const size_t kk = q.ready.size();
+    q.local.clear();
+    for (size_t i = 0; i < kk; ++i) {
+        const size_t e = (size_t)q.ready[i], r = o + i;
+        R.ids[r] = q.ready[i];
+        R.rew[r] = v.rew[e]; R.cost[r] = v.cost[e]; R.term[r] = v.term[e]; R.trunc[r] = v.trunc[e];
+        memcpy(R.obs_next.data() + r * Do, v.obs + e * Do, Do * 4);
+        out.total_cost[m] += R.cost[r];
+        if (R.term[r] || R.trunc[r]) q.local.push_back((int32_t)i);
+        out.term[m] += R.term[r] ? 1 : 0; out.trunc[m] += R.trunc[r] ? 1 : 0;
+    }
+    out.steps[m] += (int64_t)kk;
+}
+// (2) the rows to act on, q.nready and R.obs_act's rows oa ..: the step's next observations (R's rows o ..) with the reset ones (in
+//     the block by now) in their place, and the first `surplus` finished envs of the step gone (fast_collector.py:341-362).  active:
+//     the envs the episodes still `wanted` (n_episode - episodes so far) are shared among -- the member's own rows, or both lanes'
+//     in the split loop
+static void ge_next_rows(const GeEnvView& v, GeList& q, size_t Do, GeRows& R, size_t o, size_t oa, int active, int wanted) {
+    const size_t kk = q.ready.size(), n_done = q.local.size();
+    if (!n_done) {
+        q.nready = q.ready;
+        memcpy(R.obs_act.data() + oa * Do, R.obs_next.data() + o * Do, kk * Do * 4);
+        return;
+    }
+    const int surplus = active - (wanted - (int)n_done);
+    q.nready.clear();
+    for (size_t i = 0, d = 0; i < kk; ++i) {
+        const bool done = d < n_done && (size_t)q.local[d] == i;
+        if (done && (int)d++ < surplus) continue;                     // one of the first `surplus` finished envs: it leaves
+        const float* row = done ? v.obs + (size_t)q.ready[i] * Do : R.obs_next.data() + (o + i) * Do;
+        memcpy(R.obs_act.data() + (oa + q.nready.size()) * Do, row, Do * 4);
+        q.nready.push_back(q.ready[i]);
+    }
+}
+// (3) the finished episodes of the step, from the step call's outputs, into member m's slice (at ep_off) of out.ep_rew / out.ep_len
+static void ge_record(const GeList& q, const GeRows& R, size_t o, const GeOut& out, int m, size_t ep_off, int n_episode, int& episodes) {
+    for (int32_t i : q.local) {
+        if (episodes < n_episode) {
+            out.ep_rew[ep_off + (size_t)episodes] = R.erew[o + (size_t)i];
+            out.ep_len[ep_off + (size_t)episodes] = R.elen[o + (size_t)i];
+        }
+        episodes += 1;
+    }
+    out.episodes[m] = episodes < n_episode ? episodes : n_episode;
+}
+
+// ---- the lock-step loop.  ready / obs: the members' rows back to back, n[m] rows each.
+//   run_env(cmd, ids, &failed) -- post command `cmd` (GE_CMD_STEP: the actions are in the blocks already; GE_CMD_RESET) for the envs
+//            ids[m] of every member m with a non-empty list, ALL members before the first wait, and return once all of them have
+//            answered: 0, or an error with the member whose env failed in `failed`.
+// *failed_member: the member of an argument error or of a failed env command, -1 otherwise (a failed step call has no member).
+// After an env error NO further step call is made.  A member that has its episodes contributes k = 0, k_act = 0 from then on
+// while the others go on.
 template <class RunEnv, class Step>
 static int ge_collect(int members, const GeEnvView* envs, int Do_, int Da_, const int32_t* n, const int32_t* ready_in,
                       const float* obs_in, const int32_t* n_episode, const GeOut& out, RunEnv&& run_env, Step&& step,
                       int* failed_member) {
     const size_t Do = (size_t)Do_, Da = (size_t)Da_;
-    struct Member {
-        std::vector<int32_t> ready, nready, local;
-        std::vector<float> obs, act, env_act, nxt;
+    struct Member : GeList {
         size_t ep_off = 0;                      // its slice of out.ep_rew / out.ep_len
-        int n_episode = 0, episodes = 0, k_next = 0;
+        int n_episode = 0, episodes = 0;
         bool live = true, last = false;
     };
-    *failed_member = -1;
     std::vector<Member> mem((size_t)members);
     size_t cap = 0, ep_off = 0;
     for (int m = 0; m < members; ++m) {
         *failed_member = m;
-        if (n[m] < 1 || n[m] > envs[m].env_num) return GE_BAD_ROWS;
-        if (n_episode[m] < 1) return GE_BAD_EPISODES;
-        std::vector<uint8_t> seen((size_t)envs[m].env_num, 0);
-        for (int i = 0; i < n[m]; ++i) {
-            const int32_t e = ready_in[cap + (size_t)i];
-            if (e < 0 || e >= envs[m].env_num) return GE_BAD_ID;
-            if (seen[(size_t)e]) return GE_DUP_ID;
-            seen[(size_t)e] = 1;
-        }
+        const int bad = ge_check_list(envs[m], ready_in + cap, n[m], n_episode[m]);
+        if (bad) return bad;
         Member& q = mem[(size_t)m];
         q.ready.assign(ready_in + cap, ready_in + cap + (size_t)n[m]);
-        q.obs.assign(obs_in + cap * Do, obs_in + (cap + (size_t)n[m]) * Do);
-        q.act.resize((size_t)n[m] * Da); q.env_act.resize((size_t)n[m] * Da);
         q.n_episode = n_episode[m]; q.ep_off = ep_off;
         out.steps[m] = 0; out.total_cost[m] = 0.0; out.term[m] = 0; out.trunc[m] = 0; out.episodes[m] = 0;
         cap += (size_t)n[m]; ep_off += (size_t)n_episode[m];
     }
     *failed_member = -1;
-    // the step call's rows, concatenated over members (a member never has more rows than it started with)
-    std::vector<int32_t> k((size_t)members), k_act((size_t)members), ids(cap), elen(cap);
-    std::vector<float> obs(cap * Do), act(cap * Da), obs_next(cap * Do), obs_act(cap * Do), act_out(cap * Da), env_act_out(cap * Da);
-    std::vector<double> rew(cap), cost(cap), erew(cap);
-    std::vector<uint8_t> term(cap), trunc(cap);
-    std::vector<int64_t> ptr(cap), eidx(cap);
+    // the step call's rows, concatenated over members
+    std::vector<int32_t> k((size_t)members, 0), k_act((size_t)members);
+    GeRows R(cap, Do, Da);
     std::vector<std::vector<int32_t>> cmd_ids((size_t)members);
-    const GeStep s{k.data(), ids.data(), obs.data(), act.data(), rew.data(), cost.data(), term.data(), trunc.data(), obs_next.data(),
-                   ptr.data(), erew.data(), elen.data(), eidx.data(), k_act.data(), obs_act.data(), act_out.data(), env_act_out.data()};
-    // a member's new actions: its k_act rows of the step's outputs
-    auto take_actions = [&]() {
-        size_t oa = 0;
-        for (int m = 0; m < members; ++m) {
-            Member& q = mem[(size_t)m];
-            const size_t ka = (size_t)k_act[(size_t)m];
-            q.act.assign(act_out.begin() + oa * Da, act_out.begin() + (oa + ka) * Da);
-            q.env_act.assign(env_act_out.begin() + oa * Da, env_act_out.begin() + (oa + ka) * Da);
-            oa += ka;
-        }
-    };
     // the first actions: nothing to store yet
-    for (int m = 0; m < members; ++m) { k[(size_t)m] = 0; k_act[(size_t)m] = n[m]; }
-    memcpy(obs_act.data(), obs_in, cap * Do * 4);
-    int rc = step(s);
+    for (int m = 0; m < members; ++m) k_act[(size_t)m] = n[m];
+    memcpy(R.obs_act.data(), obs_in, cap * Do * 4);
+    int rc = step(R.step(k.data(), k_act.data()));
     if (rc) return rc;
-    take_actions();
+    R.advance();
     for (;;) {
+        // every live member's rows: k_act[m] of them, at the offsets of the last step call's answers
         bool any_live = false;
+        size_t o = 0;
         for (int m = 0; m < members; ++m) {
             Member& q = mem[(size_t)m];
             cmd_ids[(size_t)m].clear();
+            k[(size_t)m] = 0;
             if (!q.live) continue;
             any_live = true;
-            for (size_t i = 0; i < q.ready.size(); ++i)
-                memcpy(envs[m].act + (size_t)q.ready[i] * Da, q.env_act.data() + i * Da, Da * 4);
+            k[(size_t)m] = (int32_t)q.ready.size();
+            ge_put_actions(envs[m], q, Da, R, o);
             cmd_ids[(size_t)m] = q.ready;
+            o += q.ready.size();
         }
         if (!any_live) break;
         // ---- env.step(env_act, ready) of every live member at once
         rc = run_env(GE_CMD_STEP, cmd_ids, failed_member);
         if (rc) return rc;
         // ---- results of the step; the envs whose episode ended
-        size_t o = 0;
+        o = 0;
         bool any_done = false;
         for (int m = 0; m < members; ++m) {
             Member& q = mem[(size_t)m];
             cmd_ids[(size_t)m].clear();
-            k[(size_t)m] = 0;
             if (!q.live) continue;
-            const GeEnvView& v = envs[m];
-            const size_t kk = q.ready.size();
-            k[(size_t)m] = (int32_t)kk;
-            q.local.clear();
-            memcpy(obs.data() + o * Do, q.obs.data(), kk * Do * 4);
-            memcpy(act.data() + o * Da, q.act.data(), kk * Da * 4);
-            for (size_t i = 0; i < kk; ++i) {
-                const size_t e = (size_t)q.ready[i], r = o + i;
-                ids[r] = q.ready[i];
-                rew[r] = v.rew[e]; cost[r] = v.cost[e]; term[r] = v.term[e]; trunc[r] = v.trunc[e];
-                memcpy(obs_next.data() + r * Do, v.obs + e * Do, Do * 4);
-                out.total_cost[m] += cost[r];
-                if (term[r] || trunc[r]) { q.local.push_back((int32_t)i); cmd_ids[(size_t)m].push_back(q.ready[i]); }
-                out.term[m] += term[r] ? 1 : 0; out.trunc[m] += trunc[r] ? 1 : 0;
-            }
-            out.steps[m] += (int64_t)kk;
+            ge_read_rows(envs[m], q, Do, R, o, out, m);
+            for (int32_t i : q.local) cmd_ids[(size_t)m].push_back(q.ready[(size_t)i]);
             any_done = any_done || !q.local.empty();
-            o += kk;
+            o += q.ready.size();
         }
         // ---- env.reset(finished envs) of every member that has some, at once
         if (any_done) {
             rc = run_env(GE_CMD_RESET, cmd_ids, failed_member);
             if (rc) return rc;
         }
-        // ---- per member: the observations to act on -- reset ones in place, surplus envs dropped (fast_collector.py:341-362: the
-        //      first `surplus` finished envs of the step leave); none once the member has its episodes
+        // ---- per member: the observations to act on; none once the member has its episodes
         o = 0;
         size_t oa = 0;
         for (int m = 0; m < members; ++m) {
             Member& q = mem[(size_t)m];
             k_act[(size_t)m] = 0;
             if (!q.live) continue;
-            const GeEnvView& v = envs[m];
-            const size_t kk = q.ready.size();
-            q.nxt.assign(obs_next.begin() + o * Do, obs_next.begin() + (o + kk) * Do);
-            q.nready = q.ready;
-            q.last = false;
-            if (!q.local.empty()) {
-                const int n_done = (int)q.local.size();
-                for (int32_t i : q.local) memcpy(q.nxt.data() + (size_t)i * Do, v.obs + (size_t)q.ready[(size_t)i] * Do, Do * 4);
-                const int surplus = (int)kk - (q.n_episode - q.episodes - n_done);
-                if (surplus > 0) {
-                    std::vector<uint8_t> drop(kk, 0);
-                    for (int j = 0; j < surplus && j < n_done; ++j) drop[(size_t)q.local[(size_t)j]] = 1;
-                    size_t w = 0;
-                    for (size_t i = 0; i < kk; ++i) {
-                        if (drop[i]) continue;
-                        q.nready[w] = q.ready[i];
-                        if (w != i) memmove(q.nxt.data() + w * Do, q.nxt.data() + i * Do, Do * 4);
-                        ++w;
-                    }
-                    q.nready.resize(w); q.nxt.resize(w * Do);
-                }
-                q.last = q.episodes + n_done >= q.n_episode;
+            q.last = q.episodes + (int)q.local.size() >= q.n_episode;
+            if (!q.last) {
+                ge_next_rows(envs[m], q, Do, R, o, oa, (int)q.ready.size(), q.n_episode - q.episodes);
+                k_act[(size_t)m] = (int32_t)q.nready.size();
             }
-            q.k_next = q.last ? 0 : (int)q.nready.size();
-            k_act[(size_t)m] = q.k_next;
-            memcpy(obs_act.data() + oa * Do, q.nxt.data(), (size_t)q.k_next * Do * 4);
-            o += kk; oa += (size_t)q.k_next;
+            o += q.ready.size(); oa += (size_t)k_act[(size_t)m];
         }
         // ---- buffer.add(rows) + policy(obs) + noise + map_action of every member: ONE call
-        rc = step(s);
+        rc = step(R.step(k.data(), k_act.data()));
         if (rc) return rc;
-        take_actions();
         o = 0;
         for (int m = 0; m < members; ++m) {
             Member& q = mem[(size_t)m];
             if (!q.live) continue;
-            const size_t kk = q.ready.size();
-            for (int32_t i : q.local) {
-                if (q.episodes < q.n_episode) {
-                    out.ep_rew[q.ep_off + (size_t)q.episodes] = erew[o + (size_t)i];
-                    out.ep_len[q.ep_off + (size_t)q.episodes] = elen[o + (size_t)i];
-                }
-                q.episodes += 1;
-            }
-            out.episodes[m] = q.episodes < q.n_episode ? q.episodes : q.n_episode;
-            o += kk;
-            if (q.last) { q.live = false; continue; }
+            ge_record(q, R, o, out, m, q.ep_off, q.n_episode, q.episodes);
+            o += q.ready.size();
             q.ready.swap(q.nready);
-            q.obs.swap(q.nxt);
+            q.live = !q.last;
         }
+        R.advance();
+    }
+    return GE_OK;
+}
+
+// ---- the split-phase loop: ONE env whose envs sit on two lanes (lane_of_env[e]: 0 / 1), the lanes out of phase -- while one lane's
+// workers step, the other lane's rows are stored, its actor evaluated and its next step posted.  The episode budget is global:
+// envs of either lane leave once the envs still running on BOTH cover the episodes still wanted.  out: one member.
+//   post(lane, ids, n, cmd) -- post `cmd` for the n envs `ids` (all of that lane) and return at once: 0 or an error (nothing posted);
+//   wait(lane)              -- return once the lane's posted command is answered: 0 or an error (the lane is idle either way);
+//   step(s)                 -- as above, one member; s.obs_act is null when no row is left to act on.
+// busy[l]: on EVERY return, whether lane l still has a command in flight (on success: none).  After a callback error no further post
+// or step call is made.  The noise stream is consumed lane by lane (not as by the lock-step loop).
+template <class Post, class Wait, class Step>
+static int ge_collect_split(const GeEnvView& env, const int32_t* lane_of_env, int Do_, int Da_, int n, const int32_t* ready_in,
+                            const float* obs_in, int n_episode, const GeOut& out, Post&& post, Wait&& wait, Step&& step, bool (&busy)[2]) {
+    const size_t Do = (size_t)Do_, Da = (size_t)Da_;
+    busy[0] = busy[1] = false;
+    int rc = ge_check_list(env, ready_in, n, n_episode);
+    if (rc) return rc;
+    GeList g[2];
+    for (int i = 0; i < n; ++i) {
+        const int32_t l = lane_of_env[ready_in[i]];
+        if (l < 0 || l > 1) return GE_BAD_LANE;
+        g[l].nready.push_back(ready_in[i]);
+    }
+    GeRows R[2] = {GeRows(g[0].nready.size(), Do, Da), GeRows(g[1].nready.size(), Do, Da)};      // a lane's rows wait while the other's are stored
+    for (size_t i = 0, w[2] = {0, 0}; i < (size_t)n; ++i) {
+        const int32_t l = lane_of_env[ready_in[i]];
+        memcpy(R[l].obs_act.data() + w[l]++ * Do, obs_in + i * Do, Do * 4);
+    }
+    out.steps[0] = 0; out.total_cost[0] = 0.0; out.term[0] = 0; out.trunc[0] = 0; out.episodes[0] = 0;
+    int episodes = 0;
+    // store lane l's k finished rows, act on its nready rows (in R[l].obs_act), and post their step
+    auto step_and_post = [&](int l, int32_t k) {
+        GeList& q = g[l];
+        const int32_t k_act = (int32_t)q.nready.size();
+        GeStep s = R[l].step(&k, &k_act);
+        if (!k_act) s.obs_act = nullptr;
+        int r = step(s);
+        if (r) return r;
+        ge_record(q, R[l], 0, out, 0, 0, n_episode, episodes);
+        q.ready.swap(q.nready);
+        R[l].advance();
+        if (q.ready.empty()) return 0;
+        ge_put_actions(env, q, Da, R[l], 0);
+        r = post(l, q.ready.data(), (int)q.ready.size(), GE_CMD_STEP);
+        busy[l] = r == 0;
+        return r;
+    };
+    // the first actions of each lane: nothing to store yet
+    for (int l = 0; l < 2; ++l) {
+        if (g[l].nready.empty()) continue;
+        rc = step_and_post(l, 0);
+        if (rc) return rc;
+    }
+    while (episodes < n_episode) {
+        if (!busy[0] && !busy[1]) return GE_STALLED;
+        for (int l = 0; l < 2; ++l) {
+            GeList& q = g[l];
+            if (!busy[l]) continue;
+            busy[l] = false;                    // waited for (or failed) either way
+            rc = wait(l);
+            if (rc) return rc;
+            ge_read_rows(env, q, Do, R[l], 0, out, 0);
+            // ---- an episode ended in this lane's step: reset those envs (this lane is idle now)
+            if (!q.local.empty()) {
+                q.nready.clear();
+                for (int32_t i : q.local) q.nready.push_back(q.ready[(size_t)i]);
+                rc = post(l, q.nready.data(), (int)q.nready.size(), GE_CMD_RESET);
+                if (!rc) rc = wait(l);
+                if (rc) return rc;
+            }
+            ge_next_rows(env, q, Do, R[l], 0, 0, (int)(g[0].ready.size() + g[1].ready.size()), n_episode - episodes);
+            rc = step_and_post(l, (int32_t)q.ready.size());
+            if (rc) return rc;
+        }
+    }
+    // the interpreted loop leaves its while at the same point: a lane may still be stepping envs nobody needs any more
+    for (int l = 0; l < 2; ++l) {
+        if (!busy[l]) continue;
+        busy[l] = false;
+        rc = wait(l);
+        if (rc) return rc;
     }
     return GE_OK;
 }

@@ -10,8 +10,11 @@
 // until they are done, stores the transitions and evaluates the actor on the new observations -- and returns at the
 // first vector step in which an episode ends (or after max_steps), with that step's results NOT yet stored: the reset
 // of the finished envs and the dropping of surplus envs (fast_collector.py:341-362) stay where they were.
+// The whole collect, episode boundaries included, is fsrl_collect_episodes[_split] below: the episode loop itself is written once,
+// in group_episodes.hpp (shared with the grouped calls of host_group_episodes.inc); this file holds the env handshake and the glue.
 #define FSRL_ENV_API static
 #include "../env/csrc/fsrl_env.c"
+#include "group_episodes.hpp"
 static double mono_seconds() {
     struct timespec t;
     clock_gettime(CLOCK_MONOTONIC, &t);
@@ -68,12 +71,13 @@ static void shm_touched(const fsrl_shm_env* env, const int32_t* ids, int n, std:
         if (!seen[(size_t)w]) { seen[(size_t)w] = 1; touched[env->lane_of_worker[w]].push_back(w); }
     }
 }
-// post a command for the envs `ids` (all of lane l) to lane l only: the OTHER lane's participation flags are not touched -- its
-// workers may be reading them right now (split-phase collect)
+// post a command for those of the envs `ids` that sit on lane l (ws: their workers) to lane l only: the OTHER lane's participation
+// flags are not touched -- its workers may be reading them right now (split-phase collect)
 static void shm_post_lane(fsrl_shm_env* env, int l, const int32_t* ids, int n, const std::vector<int32_t>& ws, uint32_t cmd) {
     for (int e = 0; e < env->env_num; ++e)
         if (env->lane_of_worker[env->owner[e]] == l) env->active[e] = 0;
-    for (int i = 0; i < n; ++i) env->active[ids[i]] = 1;
+    for (int i = 0; i < n; ++i)
+        if (env->lane_of_worker[env->owner[ids[i]]] == l) env->active[ids[i]] = 1;
     uint32_t g = (env->gen[l] + 1u) & 0x7FFFFFFFu;
     if (g == 0u) g = 1u;
     env->gen[l] = g;
@@ -82,20 +86,53 @@ static void shm_post_lane(fsrl_shm_env* env, int l, const int32_t* ids, int n, c
     fsrl_env_post(env->hs + (l * 3 + 0) * 16, env->hs + (l * 3 + 1) * 16, (uint32_t)ws.size(), g);
 }
 
-// ---- one command (step / reset) for a set of envs: actions are already in the block; stamps, post to the lanes, wait
-static int shm_run_cmd(fsrl_shm_env* env, const int32_t* ids, int n, uint32_t cmd) {
-    std::vector<int32_t> touched[2];
-    shm_touched(env, ids, n, touched);
-    std::vector<int32_t> lane_ids[2];
-    for (int i = 0; i < n; ++i) lane_ids[env->lane_of_worker[env->owner[ids[i]]]].push_back(ids[i]);
-    for (int l = 0; l < env->n_lanes; ++l)
-        if (!touched[l].empty()) shm_post_lane(env, l, lane_ids[l].data(), (int)lane_ids[l].size(), touched[l], cmd);
-    for (int l = 0; l < env->n_lanes; ++l) {
-        if (touched[l].empty()) continue;
-        int rc = shm_wait_lane(env, l, touched[l]);
-        if (rc) return rc;
+// ---- one command (step / reset) for the envs ids[m] of every member m (a single env: envs = &env): the actions are in the blocks
+// already; stamps and posts on all lanes of all members first, then waits for all of them, so the workers of all members step at
+// once.  The first failure is reported (code, text, member in *failed); the other commands are still waited for.
+static int shm_run_cmd(fsrl_shm_env* const* envs, const std::vector<std::vector<int32_t>>& ids, uint32_t cmd, int* failed) {
+    struct Posted { std::vector<int32_t> touched[2]; };
+    const size_t members = ids.size();
+    std::vector<Posted> posted(members);
+    for (size_t m = 0; m < members; ++m) {
+        if (ids[m].empty()) continue;
+        shm_touched(envs[m], ids[m].data(), (int)ids[m].size(), posted[m].touched);
+        for (int l = 0; l < envs[m]->n_lanes; ++l)
+            if (!posted[m].touched[l].empty()) shm_post_lane(envs[m], l, ids[m].data(), (int)ids[m].size(), posted[m].touched[l], cmd);
     }
+    int rc = 0;
+    std::string first;
+    for (size_t m = 0; m < members; ++m) {
+        if (ids[m].empty()) continue;
+        for (int l = 0; l < envs[m]->n_lanes; ++l) {
+            if (posted[m].touched[l].empty()) continue;
+            const int r = shm_wait_lane(envs[m], l, posted[m].touched[l]);
+            if (r && !rc) { rc = r; *failed = (int)m; first = g_err; }
+        }
+    }
+    if (rc) g_err = first;
+    return rc;
+}
+
+// ---- what every native collect checks of an env against its context.  who: "" or "member i: "
+static int shm_check_env(const fsrl_ctx* c, const fsrl_shm_env* env, int min_lanes, const char* who) {
+    CHECK_ARG(c && env, "%snull context / env", who);
+    CHECK_ARG(env->obs_dim == c->cfg.obs_dim && env->act_dim == c->cfg.act_dim,
+              "%senv shape (obs %d, act %d) != context shape (obs %d, act %d)", who, env->obs_dim, env->act_dim, c->cfg.obs_dim,
+              c->cfg.act_dim);
+    CHECK_ARG(env->n_lanes >= min_lanes && env->n_lanes <= 2, "%s%s", who,
+              min_lanes == 2 ? "the split-phase collect needs an env with two lanes" : "n_lanes must be 1 or 2");
     return 0;
+}
+// group_episodes.hpp's argument errors, as text
+static const char* const ge_what[] = {"", "the row count must be 1 .. env_num", "n_episode must be >= 1", "env id out of range",
+                                      "an env id is listed twice", "an env's lane is neither 0 nor 1"};
+// f() with its seconds added to t: fsrl_collect_timing's two figures
+template <class F>
+static int timed(double& t, F&& f) {
+    const double t0 = mono_seconds();
+    const int r = f();
+    t += mono_seconds() - t0;
+    return r;
 }
 
 extern "C" int fsrl_collect_run(fsrl_ctx* c, fsrl_shm_env* env, const int32_t* ready, int32_t n, float* obs, float* act,
@@ -103,26 +140,25 @@ extern "C" int fsrl_collect_run(fsrl_ctx* c, fsrl_shm_env* env, const int32_t* r
                                 const float* act_high, int32_t max_steps, int32_t* steps_out, double* cost_sum_out,
                                 double* rew_out, double* cost_out, uint8_t* term_out, uint8_t* trunc_out,
                                 float* obs_next_out) {
-    CHECK_ARG(c && env && ready && obs && act && env_act && steps_out && cost_sum_out, "null argument");
+    int rc = shm_check_env(c, env, 1, "");
+    if (rc) return rc;
+    CHECK_ARG(ready && obs && act && env_act && steps_out && cost_sum_out, "null argument");
     CHECK_ARG(rew_out && cost_out && term_out && trunc_out && obs_next_out, "null output");
     CHECK_ARG(n >= 1 && n <= env->env_num && max_steps >= 1, "bad row / step count");
-    CHECK_ARG(env->obs_dim == c->cfg.obs_dim && env->act_dim == c->cfg.act_dim, "env shape != context shape");
-    CHECK_ARG(env->n_lanes >= 1 && env->n_lanes <= 2, "n_lanes must be 1 or 2");
     const int Do = env->obs_dim, Da = env->act_dim;
     for (int i = 0; i < n; ++i) CHECK_ARG(ready[i] >= 0 && ready[i] < env->env_num, "env id out of range");
     std::vector<int64_t> ptr((size_t)n), eidx((size_t)n);
     std::vector<double> erew((size_t)n);
     std::vector<int32_t> elen((size_t)n);
-    int steps = 0;
+    const std::vector<std::vector<int32_t>> ids{std::vector<int32_t>(ready, ready + n)};
+    int steps = 0, failed = -1;
     double cost_sum = 0.0;
     *steps_out = 0; *cost_sum_out = 0.0;
     for (;;) {
         // ---- env.step(env_act, ready): actions in place, the lanes' participation stamps, one post per lane
         for (int i = 0; i < n; ++i) memcpy(env->act + (size_t)ready[i] * Da, env_act + (size_t)i * Da, (size_t)Da * 4);
-        {
-            int rc = shm_run_cmd(env, ready, n, 1u);                       // _CMD_STEP
-            if (rc) return rc;
-        }
+        rc = shm_run_cmd(&env, ids, GE_CMD_STEP, &failed);
+        if (rc) return rc;
         // ---- results of the step
         bool any_done = false;
         for (int i = 0; i < n; ++i) {
@@ -137,283 +173,106 @@ extern "C" int fsrl_collect_run(fsrl_ctx* c, fsrl_shm_env* env, const int32_t* r
         *steps_out = steps; *cost_sum_out = cost_sum;
         if (any_done || steps >= max_steps) return 0;       // this step's rows are the caller's to store (after its resets)
         // ---- buffer.add(rows) + policy(obs_next) + noise + map_action, as one collect step
-        int rc = fsrl_collect_step(c, ready, n, obs, act, rew_out, cost_out, term_out, trunc_out, obs_next_out, ptr.data(),
-                                   erew.data(), elen.data(), eidx.data(), obs_next_out, n, deterministic, bound_method,
-                                   act_low, act_high, act, env_act);
+        rc = fsrl_collect_step(c, ready, n, obs, act, rew_out, cost_out, term_out, trunc_out, obs_next_out, ptr.data(),
+                               erew.data(), elen.data(), eidx.data(), obs_next_out, n, deterministic, bound_method,
+                               act_low, act_high, act, env_act);
         if (rc) return rc;
         memcpy(obs, obs_next_out, (size_t)n * Do * 4);
     }
 }
 
-// FastCollector.collect(n_episode=...) over the worker-process env as ONE call (fsrl/data/fast_collector.py:283-368): the
-// vector steps, the store, the actor, AND what fsrl_collect_run left to the interpreter -- the reset of the envs whose episode
-// ended (a reset command to their workers), the episode accounting, and the dropping of surplus envs once the envs still
-// running cover the episodes still wanted (fast_collector.py:341-362: the first `surplus` finished envs of the step leave).
-// Same calls in the same order as the interpreted loop around fsrl_collect_step: the same rows in the same slots and the same
-// noise stream.  ep_rew_out / ep_len_out: one entry per finished episode in the order the loop met them ([n_episode] each).
+// FastCollector.collect(n_episode=...) over the worker-process env as ONE call (fsrl/data/fast_collector.py:283-368): the vector
+// steps, the store, the actor, AND what fsrl_collect_run leaves to the interpreter -- the reset of the envs whose episode ended (a
+// reset command to their workers), the episode accounting, and the dropping of surplus envs.  The loop itself is
+// group_episodes.hpp's; here are its callbacks, the checks and the way out:
+//   fsrl_collect_episodes       = ge_collect with ONE member: the env callback is shm_run_cmd, the step callback fsrl_collect_step.
+//       The same calls in the same order as the interpreted loop around fsrl_collect_step: same rows in the same slots, same noise
+//       stream.  ep_rew_out / ep_len_out: one entry per finished episode in the order the loop met them ([n_episode] each).
+//   fsrl_collect_episodes_split = ge_collect_split over the env's TWO LANES (the native form of FastCollector._collect_split): while
+//       lane A's workers step, the collector stores lane B's finished transitions, evaluates the actor on lane B's next observations
+//       and posts lane B's next step -- an env whose step costs more than the actor call hides that call behind the other lane's
+//       step.  post = shm_touched + shm_post_lane, wait = shm_wait_lane.  The calls are the interpreted split loop's, in its order
+//       (NOT the single-phase loop's: the noise stream is consumed lane by lane).  Rows of one env stay chronological, so sample(0)
+//       and the GAE scan see what they expect.
+// The way out of both.  Success: the resident actor ends here, not at its idle timeout.  Failure: the first error text is kept; every
+// lane still reported busy gets a bounded 2 s wait, so a caller that catches the error cannot post onto a lane whose completion
+// counter the workers are still decrementing (the Python side marks the env broken as well); the actor ends and the streams are
+// drained: no actor evaluation may still be writing the pinned head outputs when the error goes up.
+static int collect_leave(fsrl_ctx* c, fsrl_shm_env* env, int rc, const bool (&busy)[2]) {
+    const std::string keep = g_err;
+    for (int l = 0; rc && l < 2; ++l)
+        if (busy[l]) fsrl_env_wait_done(env->hs + (l * 3 + 1) * 16, 0u, 2000);
+    pactor_release(c);
+    if (rc) { (void)hipStreamSynchronize(c->compute); (void)hipStreamSynchronize(c->side); g_err = keep; }
+    return rc;
+}
+
+static int collect_episodes(fsrl_ctx* c, fsrl_shm_env* env, bool split, const int32_t* ready_in, int32_t n, const float* obs_in,
+                            int32_t n_episode, int32_t deterministic, int32_t bound_method, const float* act_low, const float* act_high,
+                            int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                            double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out) {
+    int rc = shm_check_env(c, env, split ? 2 : 1, "");
+    if (rc) return rc;
+    CHECK_ARG(ready_in && obs_in && steps_out && total_cost_out && term_count_out && trunc_count_out, "null argument");
+    CHECK_ARG(ep_rew_out && ep_len_out && episodes_out, "null output");
+    const GeEnvView view{env->obs, env->act, env->rew, env->cost, env->term, env->trunc, env->env_num};
+    const GeOut out{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out};
+    c->t_collect_env = c->t_collect_act = 0.0;
+    auto step = [&](const GeStep& s) {
+        return timed(c->t_collect_act, [&] {
+            return fsrl_collect_step(c, s.env_ids, s.k[0], s.obs, s.act, s.rew, s.cost, s.terminated, s.truncated, s.obs_next, s.ptr_out,
+                                     s.ep_rew_out, s.ep_len_out, s.ep_idx_out, s.obs_act, s.k_act[0], deterministic, bound_method, act_low,
+                                     act_high, s.act_out, s.env_act_out);
+        });
+    };
+    bool busy[2] = {false, false};              // the lock-step loop's env commands are synchronous: none is ever left in flight
+    if (!split) {
+        int failed = -1;
+        rc = ge_collect(1, &view, env->obs_dim, env->act_dim, &n, ready_in, obs_in, &n_episode, out,
+                        [&](uint32_t cmd, const std::vector<std::vector<int32_t>>& ids, int* bad) {
+                            return timed(c->t_collect_env, [&] { return shm_run_cmd(&env, ids, cmd, bad); });
+                        },
+                        step, &failed);
+    } else {
+        std::vector<int32_t> lane((size_t)env->env_num), touched[2];
+        for (int e = 0; e < env->env_num; ++e) lane[(size_t)e] = env->lane_of_worker[env->owner[e]];
+        rc = ge_collect_split(view, lane.data(), env->obs_dim, env->act_dim, n, ready_in, obs_in, n_episode, out,
+                              [&](int l, const int32_t* ids, int k, uint32_t cmd) {
+                                  return timed(c->t_collect_env, [&] {
+                                      std::vector<int32_t> tl[2];       // the other lane's list is in use: it is stepping
+                                      shm_touched(env, ids, k, tl);
+                                      touched[l].swap(tl[l]);
+                                      shm_post_lane(env, l, ids, k, touched[l], cmd);
+                                      return 0;
+                                  });
+                              },
+                              [&](int l) { return timed(c->t_collect_env, [&] { return shm_wait_lane(env, l, touched[l]); }); }, step, busy);
+    }
+    if (rc == GE_STALLED) rc = fail(FSRL_ESTATE, "split-phase collect: no env left but episodes are missing");
+    else if (rc > 0) return fail(FSRL_EINVAL, "%s", ge_what[rc]);           // an argument error: nothing was posted, nothing launched
+    return collect_leave(c, env, rc, busy);
+}
+
 extern "C" int fsrl_collect_episodes(fsrl_ctx* c, fsrl_shm_env* env, const int32_t* ready_in, int32_t n, const float* obs_in,
                                      int32_t n_episode, int32_t deterministic, int32_t bound_method, const float* act_low,
                                      const float* act_high, int64_t* steps_out, double* total_cost_out, int32_t* term_count_out,
                                      int32_t* trunc_count_out, double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out) {
-    CHECK_ARG(c && env && ready_in && obs_in && steps_out && total_cost_out && term_count_out && trunc_count_out, "null argument");
-    CHECK_ARG(ep_rew_out && ep_len_out && episodes_out, "null output");
-    CHECK_ARG(n >= 1 && n <= env->env_num && n_episode >= 1, "bad row / episode count");
-    CHECK_ARG(env->obs_dim == c->cfg.obs_dim && env->act_dim == c->cfg.act_dim, "env shape != context shape");
-    CHECK_ARG(env->n_lanes >= 1 && env->n_lanes <= 2, "n_lanes must be 1 or 2");
-    const size_t Do = (size_t)env->obs_dim, Da = (size_t)env->act_dim;
-    for (int i = 0; i < n; ++i) CHECK_ARG(ready_in[i] >= 0 && ready_in[i] < env->env_num, "env id out of range");
-    std::vector<int32_t> ready(ready_in, ready_in + n), nready;
-    std::vector<float> obs(obs_in, obs_in + (size_t)n * Do), act((size_t)n * Da), env_act((size_t)n * Da), nxt, obs_next((size_t)n * Do);
-    std::vector<float> act_new((size_t)n * Da), env_act_new((size_t)n * Da);
-    std::vector<double> rew((size_t)n), cost((size_t)n), erew((size_t)n);
-    std::vector<uint8_t> term((size_t)n), trunc((size_t)n);
-    std::vector<int64_t> ptr((size_t)n), eidx((size_t)n);
-    std::vector<int32_t> elen((size_t)n), local, reset_ids;
-    int64_t steps = 0;
-    double total_cost = 0.0;
-    int episodes = 0, term_count = 0, trunc_count = 0;
-    c->t_collect_env = c->t_collect_act = 0.0;
-    // env commands are synchronous here (post + wait inside shm_run_cmd), so a failure never leaves one half-handled; what CAN
-    // be left behind is a device actor evaluation still writing the pinned head outputs: drained before the error goes up
-    auto bail = [&](int code) { pactor_release(c); (void)hipStreamSynchronize(c->compute); (void)hipStreamSynchronize(c->side); return code; };
-    // the first actions: nothing to store yet
-    int rc = fsrl_collect_step(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, obs.data(), n, deterministic, bound_method, act_low, act_high, act.data(), env_act.data());
-    if (rc) return bail(rc);
-    for (;;) {
-        const int k = (int)ready.size();
-        for (int i = 0; i < k; ++i) memcpy(env->act + (size_t)ready[(size_t)i] * Da, env_act.data() + (size_t)i * Da, Da * 4);
-        const double t_e0 = mono_seconds();
-        rc = shm_run_cmd(env, ready.data(), k, 1u);                    // _CMD_STEP
-        if (rc) return bail(rc);
-        const double t_e1 = mono_seconds();
-        c->t_collect_env += t_e1 - t_e0;
-        local.clear();
-        for (int i = 0; i < k; ++i) {
-            const int e = ready[(size_t)i];
-            rew[(size_t)i] = env->rew[e]; cost[(size_t)i] = env->cost[e];
-            term[(size_t)i] = env->term[e]; trunc[(size_t)i] = env->trunc[e];
-            memcpy(obs_next.data() + (size_t)i * Do, env->obs + (size_t)e * Do, Do * 4);
-            total_cost += cost[(size_t)i];
-            if (term[(size_t)i] || trunc[(size_t)i]) local.push_back(i);
-            term_count += term[(size_t)i] ? 1 : 0; trunc_count += trunc[(size_t)i] ? 1 : 0;
-        }
-        steps += k;
-        if (local.empty()) {
-            rc = fsrl_collect_step(c, ready.data(), k, obs.data(), act.data(), rew.data(), cost.data(), term.data(), trunc.data(),
-                                   obs_next.data(), ptr.data(), erew.data(), elen.data(), eidx.data(), obs_next.data(), k, deterministic,
-                                   bound_method, act_low, act_high, act.data(), env_act.data());
-            if (rc) return bail(rc);
-            c->t_collect_act += mono_seconds() - t_e1;
-            obs.swap(obs_next);
-            obs_next.resize((size_t)k * Do);
-            continue;
-        }
-        // ---- an episode ended in this step: reset those envs, drop surplus ones, store the step, act on what is left
-        const int n_done = (int)local.size();
-        nxt.assign(obs_next.begin(), obs_next.begin() + (size_t)k * Do);
-        reset_ids.clear();
-        for (int i : local) reset_ids.push_back(ready[(size_t)i]);
-        rc = shm_run_cmd(env, reset_ids.data(), n_done, 2u);           // _CMD_RESET
-        if (rc) return bail(rc);
-        for (int i : local) memcpy(nxt.data() + (size_t)i * Do, env->obs + (size_t)ready[(size_t)i] * Do, Do * 4);
-        const int surplus = k - (n_episode - episodes - n_done);
-        nready.clear();
-        std::vector<float> nxt_kept;
-        nxt_kept.reserve((size_t)k * Do);
-        {
-            std::vector<uint8_t> drop((size_t)k, 0);
-            for (int j = 0; j < surplus && j < n_done; ++j) drop[(size_t)local[(size_t)j]] = 1;
-            for (int i = 0; i < k; ++i) {
-                if (drop[(size_t)i]) continue;
-                nready.push_back(ready[(size_t)i]);
-                nxt_kept.insert(nxt_kept.end(), nxt.begin() + (size_t)i * Do, nxt.begin() + (size_t)(i + 1) * Do);
-            }
-        }
-        const bool last = episodes + n_done >= n_episode;
-        const int k_next = last ? 0 : (int)nready.size();
-        rc = fsrl_collect_step(c, ready.data(), k, obs.data(), act.data(), rew.data(), cost.data(), term.data(), trunc.data(),
-                               obs_next.data(), ptr.data(), erew.data(), elen.data(), eidx.data(), last ? nullptr : nxt_kept.data(), k_next,
-                               deterministic, bound_method, act_low, act_high, act_new.data(), env_act_new.data());
-        if (rc) return bail(rc);
-        for (int i : local) {
-            if (episodes < n_episode) { ep_rew_out[episodes] = erew[(size_t)i]; ep_len_out[episodes] = elen[(size_t)i]; }
-            episodes += 1;
-        }
-        if (last) break;
-        ready.swap(nready);
-        obs.assign(nxt_kept.begin(), nxt_kept.end());
-        act.assign(act_new.begin(), act_new.begin() + (size_t)k_next * Da);
-        env_act.assign(env_act_new.begin(), env_act_new.begin() + (size_t)k_next * Da);
-        obs_next.resize((size_t)k_next * Do);
-    }
-    *steps_out = steps; *total_cost_out = total_cost; *term_count_out = term_count; *trunc_count_out = trunc_count;
-    *episodes_out = episodes;
-    pactor_release(c);                        // the collect is over: the resident actor ends here, not at its idle timeout
-    return 0;
+    return collect_episodes(c, env, false, ready_in, n, obs_in, n_episode, deterministic, bound_method, act_low, act_high, steps_out,
+                            total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out);
 }
 
-// The same collect over the env's TWO LANES, split-phase (the native form of FastCollector._collect_split): while lane A's
-// workers step, the collector stores lane B's finished transitions, evaluates the actor on lane B's next observations and posts
-// lane B's next step -- an env whose step costs more than the actor call hides that call behind the other lane's step.  Episode
-// accounting is global (envs of either lane leave once the envs still running cover the episodes still wanted), so exactly
-// n_episode episodes are collected (fast_collector.py:341-362).  The library calls are the interpreted split loop's, in its
-// order: the same rows in the same slots and the same noise stream as that loop (NOT as the single-phase loop: the noise
-// stream is consumed lane by lane).  Rows of one env stay chronological, so sample(0) and the GAE scan see what they expect.
 extern "C" int fsrl_collect_episodes_split(fsrl_ctx* c, fsrl_shm_env* env, const int32_t* ready_in, int32_t n, const float* obs_in,
                                            int32_t n_episode, int32_t deterministic, int32_t bound_method, const float* act_low,
                                            const float* act_high, int64_t* steps_out, double* total_cost_out,
                                            int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
                                            int32_t* ep_len_out, int32_t* episodes_out) {
-    CHECK_ARG(c && env && ready_in && obs_in && steps_out && total_cost_out && term_count_out && trunc_count_out, "null argument");
-    CHECK_ARG(ep_rew_out && ep_len_out && episodes_out, "null output");
-    CHECK_ARG(n >= 1 && n <= env->env_num && n_episode >= 1, "bad row / episode count");
-    CHECK_ARG(env->obs_dim == c->cfg.obs_dim && env->act_dim == c->cfg.act_dim, "env shape != context shape");
-    CHECK_ARG(env->n_lanes == 2, "the split-phase collect needs an env with two lanes");
-    const size_t Do = (size_t)env->obs_dim, Da = (size_t)env->act_dim;
-    for (int i = 0; i < n; ++i) CHECK_ARG(ready_in[i] >= 0 && ready_in[i] < env->env_num, "env id out of range");
-    struct Grp {
-        std::vector<int32_t> ready, touched;
-        std::vector<float> obs, act, env_act;
-        bool busy = false;
-    } g[2];
-    for (int i = 0; i < n; ++i) {
-        Grp& q = g[env->lane_of_worker[env->owner[ready_in[i]]]];
-        q.ready.push_back(ready_in[i]);
-        q.obs.insert(q.obs.end(), obs_in + (size_t)i * Do, obs_in + (size_t)(i + 1) * Do);
-    }
-    auto post_step = [&](int l) {
-        Grp& q = g[l];
-        const int k = (int)q.ready.size();
-        for (int i = 0; i < k; ++i) memcpy(env->act + (size_t)q.ready[(size_t)i] * Da, q.env_act.data() + (size_t)i * Da, Da * 4);
-        std::vector<int32_t> tl[2];
-        shm_touched(env, q.ready.data(), k, tl);
-        q.touched = tl[l];
-        shm_post_lane(env, l, q.ready.data(), k, q.touched, 1u);
-        q.busy = true;
-    };
-    int rc = 0;
-    // an error leaves with NO command in flight: the other lane's step (if any) is waited for first -- bounded, 2 s, the
-    // error text of the first failure is kept -- so a caller that catches the error cannot post onto a lane whose completion
-    // counter the workers are still decrementing (the Python side marks the env broken as well)
-    auto bail = [&](int code) {
-        const std::string keep = g_err;
-        pactor_release(c);                                        // the resident actor ends here, not at its idle timeout
-        for (int l = 0; l < 2; ++l)
-            if (g[l].busy) { fsrl_env_wait_done(env->hs + (l * 3 + 1) * 16, 0u, 2000); g[l].busy = false; }
-        (void)hipStreamSynchronize(c->compute); (void)hipStreamSynchronize(c->side);       // as fsrl_collect_episodes' bail
-        g_err = keep;
-        return code;
-    };
-    c->t_collect_env = c->t_collect_act = 0.0;
-    for (int l = 0; l < 2; ++l) {
-        Grp& q = g[l];
-        const int k = (int)q.ready.size();
-        if (!k) continue;
-        q.act.resize((size_t)k * Da); q.env_act.resize((size_t)k * Da);
-        rc = fsrl_collect_step(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, q.obs.data(), k, deterministic, bound_method, act_low, act_high, q.act.data(), q.env_act.data());
-        if (rc) return bail(rc);
-        post_step(l);
-    }
-    int64_t steps = 0;
-    double total_cost = 0.0;
-    int episodes = 0, term_count = 0, trunc_count = 0;
-    std::vector<double> rew, cost, erew;
-    std::vector<uint8_t> term, trunc;
-    std::vector<int64_t> ptr, eidx;
-    std::vector<int32_t> elen, local, nready, reset_ids;
-    std::vector<float> obs_next, nxt, nxt_kept, act_new, env_act_new;
-    while (episodes < n_episode) {
-        if (!g[0].busy && !g[1].busy) return bail(fail(FSRL_ESTATE, "split-phase collect: no env left but episodes are missing"));
-        for (int l = 0; l < 2; ++l) {
-            Grp& q = g[l];
-            if (!q.busy) continue;
-            const int k = (int)q.ready.size();
-            const double t_e0 = mono_seconds();
-            q.busy = false;                                       // waited for (or failed) either way
-            rc = shm_wait_lane(env, l, q.touched);
-            if (rc) return bail(rc);
-            const double t_e1 = mono_seconds();
-            c->t_collect_env += t_e1 - t_e0;
-            q.busy = false;
-            rew.resize((size_t)k); cost.resize((size_t)k); erew.resize((size_t)k); term.resize((size_t)k); trunc.resize((size_t)k);
-            ptr.resize((size_t)k); eidx.resize((size_t)k); elen.resize((size_t)k); obs_next.resize((size_t)k * Do);
-            act_new.resize((size_t)k * Da); env_act_new.resize((size_t)k * Da);
-            local.clear();
-            for (int i = 0; i < k; ++i) {
-                const int e = q.ready[(size_t)i];
-                rew[(size_t)i] = env->rew[e]; cost[(size_t)i] = env->cost[e];
-                term[(size_t)i] = env->term[e]; trunc[(size_t)i] = env->trunc[e];
-                memcpy(obs_next.data() + (size_t)i * Do, env->obs + (size_t)e * Do, Do * 4);
-                total_cost += cost[(size_t)i];
-                if (term[(size_t)i] || trunc[(size_t)i]) local.push_back(i);
-                term_count += term[(size_t)i] ? 1 : 0; trunc_count += trunc[(size_t)i] ? 1 : 0;
-            }
-            steps += k;
-            if (local.empty()) {
-                rc = fsrl_collect_step(c, q.ready.data(), k, q.obs.data(), q.act.data(), rew.data(), cost.data(), term.data(),
-                                       trunc.data(), obs_next.data(), ptr.data(), erew.data(), elen.data(), eidx.data(), obs_next.data(), k,
-                                       deterministic, bound_method, act_low, act_high, q.act.data(), q.env_act.data());
-                if (rc) return bail(rc);
-                q.obs.assign(obs_next.begin(), obs_next.end());
-                post_step(l);
-                c->t_collect_act += mono_seconds() - t_e1;
-                continue;
-            }
-            // ---- an episode ended in this lane's step: reset those envs (this lane is idle now), drop surplus ones
-            const int n_done = (int)local.size();
-            nxt.assign(obs_next.begin(), obs_next.end());
-            reset_ids.clear();
-            for (int i : local) reset_ids.push_back(q.ready[(size_t)i]);
-            {
-                std::vector<int32_t> tl[2];
-                shm_touched(env, reset_ids.data(), n_done, tl);
-                shm_post_lane(env, l, reset_ids.data(), n_done, tl[l], 2u);                 // _CMD_RESET
-                rc = shm_wait_lane(env, l, tl[l]);
-                if (rc) return bail(rc);
-            }
-            for (int i : local) memcpy(nxt.data() + (size_t)i * Do, env->obs + (size_t)q.ready[(size_t)i] * Do, Do * 4);
-            const int active = (int)(g[0].ready.size() + g[1].ready.size());
-            const int surplus = active - (n_episode - episodes - n_done);
-            nready.clear(); nxt_kept.clear();
-            {
-                std::vector<uint8_t> drop((size_t)k, 0);
-                for (int j = 0; j < surplus && j < n_done; ++j) drop[(size_t)local[(size_t)j]] = 1;
-                for (int i = 0; i < k; ++i) {
-                    if (drop[(size_t)i]) continue;
-                    nready.push_back(q.ready[(size_t)i]);
-                    nxt_kept.insert(nxt_kept.end(), nxt.begin() + (size_t)i * Do, nxt.begin() + (size_t)(i + 1) * Do);
-                }
-            }
-            const int k_next = (int)nready.size();
-            rc = fsrl_collect_step(c, q.ready.data(), k, q.obs.data(), q.act.data(), rew.data(), cost.data(), term.data(), trunc.data(),
-                                   obs_next.data(), ptr.data(), erew.data(), elen.data(), eidx.data(), k_next ? nxt_kept.data() : nullptr,
-                                   k_next, deterministic, bound_method, act_low, act_high, act_new.data(), env_act_new.data());
-            if (rc) return bail(rc);
-            for (int i : local) {
-                if (episodes < n_episode) { ep_rew_out[episodes] = erew[(size_t)i]; ep_len_out[episodes] = elen[(size_t)i]; }
-                episodes += 1;
-            }
-            q.ready = nready;
-            q.obs.assign(nxt_kept.begin(), nxt_kept.end());
-            q.act.assign(act_new.begin(), act_new.begin() + (size_t)k_next * Da);
-            q.env_act.assign(env_act_new.begin(), env_act_new.begin() + (size_t)k_next * Da);
-            if (k_next) post_step(l);
-            c->t_collect_act += mono_seconds() - t_e1;
-        }
-    }
-    // the interpreted loop leaves its while at the same point: a lane may still be stepping envs nobody needs any more
-    for (int l = 0; l < 2; ++l)
-        if (g[l].busy) { g[l].busy = false; rc = shm_wait_lane(env, l, g[l].touched); if (rc) return bail(rc); }
-    *steps_out = steps; *total_cost_out = total_cost; *term_count_out = term_count; *trunc_count_out = trunc_count;
-    *episodes_out = std::min(episodes, n_episode);
-    pactor_release(c);
-    return 0;
+    return collect_episodes(c, env, true, ready_in, n, obs_in, n_episode, deterministic, bound_method, act_low, act_high, steps_out,
+                            total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out);
 }
 
-// seconds the last fsrl_collect_episodes / _split spent waiting for the env workers (out[0]) and in its store + actor calls
-// (out[1]): FastCollector(split_phase="auto") picks the split loop when the env outweighs the actor call it could hide
+// seconds the last fsrl_collect_episodes / _split spent inside env commands -- step AND reset, post and wait (out[0]) -- and inside
+// its step calls, the first one and those of steps that end an episode included (out[1]): what the grouped calls report in
+// t_env_act_out2.  FastCollector(split_phase="auto") picks the split loop when the env outweighs the actor call it could hide
 extern "C" int fsrl_collect_timing(fsrl_ctx* c, double* out2) {
     CHECK_ARG(c && out2, "null argument");
     out2[0] = c->t_collect_env; out2[1] = c->t_collect_act;

@@ -1,49 +1,15 @@
 // host_group_episodes.inc -- GroupCollector.collect(n_episode) over worker-process envs as ONE library call (part of fsrl_hip.hip,
 // after host_collect_group.inc): every member's FastCollector.collect (fsrl_collect_episodes, host_collect.inc) with the members'
 // envs stepped TOGETHER and one actor request per vector step for all of them.  The loop and all its bookkeeping are
-// group_episodes.hpp's (no HIP there: tests/host/group_episodes_sim.cpp drives it); here are its two callbacks and the checks:
-//   * the env callback posts the command of every member on both lanes (shm_post_lane) and only then waits (shm_wait_lane), so the
-//     workers of all members step at once -- the interpreted loop steps member 0's env, waits, steps member 1's ...;
+// group_episodes.hpp's ge_collect -- fsrl_collect_episodes' own loop, keyed by member (no HIP there: tests/host/group_episodes_sim.cpp
+// drives it); here are its two callbacks and the checks:
+//   * the env callback is host_collect.inc's shm_run_cmd: the command of every member posted on both lanes, and only then the waits,
+//     so the workers of all members step at once -- the interpreted loop steps member 0's env, waits, steps member 1's ...;
 //   * the step callback is fsrl_group_collect_step / fsrl_collect_group_step as it is: the group's resident actor kernel for fused
 //     members, the L + 2 launches for layered ones.  Nothing on the device is new.
 // A failure (a dead worker, an env that raised, a failed step) waits for every command already posted, ends the group's resident
 // actor and drains the group's and the members' streams; only the failing member's env may be left with a half-handled command.
 #include "group_episodes.hpp"
-
-// post `cmd` for the envs ids[m] of every member, all lanes of all members first; then wait for all of them.  The first failure is
-// reported (code, text, member); the commands of the other members are still waited for.
-static int shm_group_run_cmd(fsrl_shm_env* const* envs, const std::vector<std::vector<int32_t>>& ids, uint32_t cmd, int* failed) {
-    struct Posted { std::vector<int32_t> touched[2]; };
-    const size_t members = ids.size();
-    std::vector<Posted> posted(members);
-    std::vector<int32_t> lane_ids[2];
-    for (size_t m = 0; m < members; ++m) {
-        if (ids[m].empty()) continue;
-        fsrl_shm_env* env = envs[m];
-        const int n = (int)ids[m].size();
-        shm_touched(env, ids[m].data(), n, posted[m].touched);
-        lane_ids[0].clear(); lane_ids[1].clear();
-        for (int32_t e : ids[m]) lane_ids[env->lane_of_worker[env->owner[e]]].push_back(e);
-        for (int l = 0; l < env->n_lanes; ++l)
-            if (!posted[m].touched[l].empty())
-                shm_post_lane(env, l, lane_ids[l].data(), (int)lane_ids[l].size(), posted[m].touched[l], cmd);
-    }
-    int rc = 0;
-    std::string first;
-    for (size_t m = 0; m < members; ++m) {
-        if (ids[m].empty()) continue;
-        for (int l = 0; l < envs[m]->n_lanes; ++l) {
-            if (posted[m].touched[l].empty()) continue;
-            const int r = shm_wait_lane(envs[m], l, posted[m].touched[l]);
-            if (r && !rc) {
-                rc = r; *failed = (int)m;
-                first = "member " + std::to_string(m) + ": " + g_err;
-            }
-        }
-    }
-    if (rc) g_err = first;
-    return rc;
-}
 
 // the checks and the loop; step(GeStep) is the owner's lock-step step, leave(failed) ends its resident actor (and, after a failure,
 // drains its streams)
@@ -59,11 +25,8 @@ static int group_collect_episodes(fsrl_ctx* const* mem, int members, fsrl_shm_en
     for (int i = 0; i < members; ++i) {
         const fsrl_shm_env* env = envs[i];
         *failed_member_out = i;
-        CHECK_ARG(env, "member %d: null env", i);
-        CHECK_ARG(env->obs_dim == mem[i]->cfg.obs_dim && env->act_dim == mem[i]->cfg.act_dim,
-                  "member %d: env shape (obs %d, act %d) != context shape (obs %d, act %d)", i, env->obs_dim, env->act_dim,
-                  mem[i]->cfg.obs_dim, mem[i]->cfg.act_dim);
-        CHECK_ARG(env->n_lanes >= 1 && env->n_lanes <= 2, "member %d: n_lanes must be 1 or 2", i);
+        const int bad = shm_check_env(mem[i], env, 1, ("member " + std::to_string(i) + ": ").c_str());
+        if (bad) return bad;
         for (int j = 0; j < i; ++j)
             CHECK_ARG(envs[j] != env && envs[j]->hs != env->hs, "member %d: its env is member %d's (an env listed twice)", i, j);
         views[(size_t)i] = GeEnvView{env->obs, env->act, env->rew, env->cost, env->term, env->trunc, env->env_num};
@@ -75,25 +38,14 @@ static int group_collect_episodes(fsrl_ctx* const* mem, int members, fsrl_shm_en
     const int rc = ge_collect(
         members, views.data(), Do, Da, n, ready, obs, n_episode, out,
         [&](uint32_t cmd, const std::vector<std::vector<int32_t>>& ids, int* bad) {
-            const double t0 = mono_seconds();
-            const int r = shm_group_run_cmd(envs, ids, cmd, bad);
-            t_env += mono_seconds() - t0;
+            const int r = timed(t_env, [&] { return shm_run_cmd(envs, ids, cmd, bad); });
+            if (r) g_err = "member " + std::to_string(*bad) + ": " + g_err;
             return r;
         },
-        [&](const GeStep& s) {
-            const double t0 = mono_seconds();
-            const int r = step(s);
-            t_act += mono_seconds() - t0;
-            return r;
-        },
-        &failed);
+        [&](const GeStep& s) { return timed(t_act, [&] { return step(s); }); }, &failed);
     *failed_member_out = failed;
     if (t_env_act_out2) { t_env_act_out2[0] = t_env; t_env_act_out2[1] = t_act; }
-    if (rc > 0) {                               // group_episodes.hpp's argument errors: nothing was posted, nothing launched
-        static const char* const what[] = {"", "n[i] must be 1 .. env_num", "n_episode[i] must be >= 1", "env id out of range",
-                                           "an env id is listed twice"};
-        return fail(FSRL_EINVAL, "member %d: %s", failed, what[rc]);
-    }
+    if (rc > 0) return fail(FSRL_EINVAL, "member %d: %s", failed, ge_what[rc]);       // an argument error: nothing posted, nothing launched
     // the collect is over, or failed: the group's resident actor ends here, not at its idle timeout; after a failure no actor
     // evaluation may still be writing the pinned outputs and no store flush may be in flight when the error goes up
     const std::string keep = g_err;

@@ -265,7 +265,9 @@ int fsrl_collect_episodes_split(fsrl_ctx* ctx, fsrl_shm_env* env, const int32_t*
                                 int32_t deterministic, int32_t bound_method, const float* act_low, const float* act_high,
                                 int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
                                 double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out);
-/* out2[0] = seconds the last fsrl_collect_episodes[_split] waited for the env workers, out2[1] = seconds in its store + actor calls */
+/* Of the last fsrl_collect_episodes[_split]: out2[0] = seconds inside env commands (step AND the once-per-episode reset; post and
+ * wait), out2[1] = seconds inside its fsrl_collect_step calls (the first one and those of steps that end an episode included; the
+ * gather of the rows belongs to neither).  The same two figures as t_env_act_out2 of the grouped calls.                          */
 int fsrl_collect_timing(fsrl_ctx* ctx, double* out2);
 /* The collector's actor as a RESIDENT workgroup (contexts with the fused two-layer networks, up to 64 rows per call):
  * instead of one kernel launch per vector step (fast_collector.py:283-300: `self.policy(self.data, last_state)` per step) one

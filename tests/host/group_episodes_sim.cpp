@@ -2,7 +2,9 @@
 // fsrl_collect_episodes_group) as a plain program: fake envs, a fake step call that records what every member is asked to store and
 // to act on, and for comparison a single-member collect loop written out here on its own (the rule of FastCollector's fused loop,
 // fast_collector.py:283-368: reset the finished envs, drop the first `surplus` of them, stop at n_episode) that does not go through
-// the header.  A member's record under the group must equal its record alone.  Exits 0 and prints "ok ..." per case.
+// the header.  A member's record under the group must equal its record alone ("k1" is fsrl_collect_episodes' own loop: ge_collect
+// with one member).  The split loop (ge_collect_split, fsrl_collect_episodes_split) runs against a two-lane loop written out here
+// the way FastCollector._collect_split has it: every request, post and wait, in order.  Exits 0 and prints "ok ..." per case.
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -280,6 +282,228 @@ static int run_refusals() {
     return 0;
 }
 
+// ---- the split loop (ge_collect_split).  One env whose envs sit on two lanes; a posted command takes effect only when its lane is
+// waited for, so results read before the wait, or actions put into the slots of a lane that is stepping, show.  Posts and waits go
+// into the agent's log between its requests: ONE record of everything the loop does, in order.
+struct LaneEnv {
+    FakeEnv env;
+    FakeAgent agent;
+    std::vector<int32_t> lane;                  // of every env
+    struct Pending { bool on = false; uint32_t cmd = 0; std::vector<int32_t> ids; } pend[2];
+    int posts = 0, waits = 0, step_waits[2] = {0, 0};
+    bool misuse = false;                        // a post onto a busy lane or for another lane's env, a wait on an idle lane
+    LaneEnv(const std::vector<int32_t>& lane_, int ep_len, int stagger)
+        : env(0, (int)lane_.size(), ep_len, stagger), agent(0, (int)lane_.size()), lane(lane_) {}
+    void post(int l, const int32_t* ids, int n, uint32_t cmd) {
+        posts += 1;
+        agent.log.push_back(-2000.0 - l); agent.log.push_back(cmd); agent.log.push_back(n);
+        if (pend[l].on) misuse = true;
+        for (int i = 0; i < n; ++i) { agent.log.push_back(ids[i]); if (lane[(size_t)ids[i]] != l) misuse = true; }
+        pend[l].on = true; pend[l].cmd = cmd; pend[l].ids.assign(ids, ids + n);
+    }
+    void wait(int l) {
+        waits += 1;
+        agent.log.push_back(-3000.0 - l);
+        if (!pend[l].on) { misuse = true; return; }
+        if (pend[l].cmd == GE_CMD_STEP) step_waits[l] += 1;
+        for (int32_t e : pend[l].ids) { if (pend[l].cmd == GE_CMD_STEP) env.step(e); else env.reset(e); }
+        pend[l].on = false;
+    }
+    void reset_all() { for (int e = 0; e < env.env_num; ++e) env.reset(e); }        // FastCollector.reset_env between two collects
+};
+
+// the two-lane loop written out the way FastCollector._collect_split has it (groups with ready / obs / act / busy, masks, a global
+// episode count), not through the header
+static Result split_alone(LaneEnv& w, int n_start, int n_episode) {
+    struct Group { std::vector<int32_t> ready; std::vector<float> obs, act; bool busy = false; } groups[2];
+    Result r;
+    int episode_count = 0;
+    auto step_async = [&](int l, const std::vector<float>& env_act, const std::vector<int32_t>& ids) {
+        for (size_t i = 0; i < ids.size(); ++i)
+            for (int d = 0; d < Da; ++d) w.env.act[(size_t)ids[i] * Da + d] = env_act[i * Da + d];
+        w.post(l, ids.data(), (int)ids.size(), GE_CMD_STEP);
+    };
+    for (int l = 0; l < 2; ++l) {
+        Group& g = groups[l];
+        for (int e = 0; e < n_start; ++e)
+            if (w.lane[(size_t)e] == l) {
+                g.ready.push_back(e);
+                g.obs.insert(g.obs.end(), w.env.obs.begin() + (size_t)e * Do, w.env.obs.begin() + (size_t)(e + 1) * Do);
+            }
+        if (g.ready.empty()) continue;
+        const int k = (int)g.ready.size();
+        std::vector<float> env_act((size_t)k * Da);
+        g.act.resize((size_t)k * Da);
+        w.agent.request(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k, g.obs.data(),
+                        g.act.data(), env_act.data());
+        step_async(l, env_act, g.ready);
+        g.busy = true;
+    }
+    while (episode_count < n_episode) {
+        if (!groups[0].busy && !groups[1].busy) { printf("split_alone: no env left but episodes are missing\n"); exit(2); }
+        for (int l = 0; l < 2; ++l) {
+            Group& g = groups[l];
+            if (!g.busy) continue;
+            const std::vector<int32_t> rdy = g.ready;
+            const int k = (int)rdy.size();
+            w.wait(l);
+            g.busy = false;
+            std::vector<double> rew((size_t)k), cost((size_t)k), ep_rew((size_t)k);
+            std::vector<uint8_t> term((size_t)k), trunc((size_t)k);
+            std::vector<int32_t> ep_len((size_t)k);
+            std::vector<float> obs_next((size_t)k * Do);
+            std::vector<int> local;
+            for (int i = 0; i < k; ++i) {
+                const size_t e = (size_t)rdy[(size_t)i];
+                rew[(size_t)i] = w.env.rew[e]; cost[(size_t)i] = w.env.cost[e]; term[(size_t)i] = w.env.term[e]; trunc[(size_t)i] = w.env.trunc[e];
+                for (int d = 0; d < Do; ++d) obs_next[(size_t)i * Do + d] = w.env.obs[e * Do + d];
+                r.total_cost += cost[(size_t)i];
+                if (term[(size_t)i] || trunc[(size_t)i]) local.push_back(i);
+            }
+            r.steps += k;
+            std::vector<float> nxt = obs_next;
+            std::vector<int32_t> nready = rdy;
+            if (!local.empty()) {
+                const int n_done = (int)local.size();
+                for (int i : local) { r.term += term[(size_t)i]; r.trunc += trunc[(size_t)i]; }
+                std::vector<int32_t> reset_ids;
+                for (int i : local) reset_ids.push_back(rdy[(size_t)i]);
+                w.post(l, reset_ids.data(), n_done, GE_CMD_RESET);                    // env.reset(rdy[local]): this lane is idle
+                w.wait(l);
+                for (int i : local)
+                    for (int d = 0; d < Do; ++d) nxt[(size_t)i * Do + d] = w.env.obs[(size_t)rdy[(size_t)i] * Do + d];
+                const int active = (int)(groups[0].ready.size() + groups[1].ready.size());
+                const int surplus = active - (n_episode - episode_count - n_done);
+                if (surplus > 0) {
+                    std::vector<bool> mask((size_t)k, true);
+                    for (int j = 0; j < std::min(surplus, n_done); ++j) mask[(size_t)local[(size_t)j]] = false;
+                    std::vector<float> nx2;
+                    std::vector<int32_t> nr2;
+                    for (int i = 0; i < k; ++i)
+                        if (mask[(size_t)i]) {
+                            nr2.push_back(rdy[(size_t)i]);
+                            nx2.insert(nx2.end(), nxt.begin() + (size_t)i * Do, nxt.begin() + (size_t)(i + 1) * Do);
+                        }
+                    nxt = nx2; nready = nr2;
+                }
+            }
+            const int k_act = (int)nready.size();
+            std::vector<float> act_new((size_t)k_act * Da), env_act_new((size_t)k_act * Da);
+            w.agent.request(k, rdy.data(), g.obs.data(), g.act.data(), rew.data(), cost.data(), term.data(), trunc.data(), obs_next.data(),
+                            ep_rew.data(), ep_len.data(), k_act, k_act ? nxt.data() : nullptr, act_new.data(), env_act_new.data());
+            for (int i : local) { r.ep_rew.push_back(ep_rew[(size_t)i]); r.ep_len.push_back(ep_len[(size_t)i]); }
+            episode_count += (int)local.size();
+            g.ready = nready; g.obs = nxt; g.act = act_new;
+            if (k_act) { step_async(l, env_act_new, nready); g.busy = true; }
+        }
+    }
+    for (int l = 0; l < 2; ++l)
+        if (groups[l].busy) { w.wait(l); groups[l].busy = false; }
+    r.episodes = episode_count;
+    return r;
+}
+
+struct Collect { int n_start, n_episode; };     // n_start < 0: min(env_num, n_episode), as FastCollector starts
+
+// the collects back to back on one env and agent, through the header and through split_alone.  fail_lane >= 0: the wait of that
+// lane's fail_step-th step fails (first collect).  want_trailing >= 0: waits after the last step call of the first collect
+static int run_split(const char* name, const std::vector<int32_t>& lane, int ep_len, int stagger, const std::vector<Collect>& collects,
+                     int fail_lane = -1, int fail_step = 0, int want_trailing = -1) {
+    LaneEnv w(lane, ep_len, stagger), ref(lane, ep_len, stagger);
+    long long total_steps = 0;
+    for (const Collect& c : collects) {
+        const int n = c.n_start < 0 ? std::min((int)lane.size(), c.n_episode) : c.n_start;
+        std::vector<int32_t> ready;
+        for (int i = 0; i < n; ++i) ready.push_back(i);
+        const std::vector<float> obs(w.env.obs.begin(), w.env.obs.begin() + (size_t)n * Do);
+        int64_t steps = -1; double total_cost = -1.0; int32_t term = -1, trunc = -1, episodes = -1;
+        std::vector<double> ep_rew((size_t)c.n_episode, -1.0);
+        std::vector<int32_t> ep_len_((size_t)c.n_episode, -1);
+        const GeOut out{&steps, &total_cost, &term, &trunc, ep_rew.data(), ep_len_.data(), &episodes};
+        bool busy[2] = {true, true}, null_obs_act_with_rows = false, obs_act_without_rows = false;
+        int step_calls = 0, calls_at_failure = -1, waits_at_last_step = 0;
+        const int rc = ge_collect_split(
+            w.env.view(), lane.data(), Do, Da, n, ready.data(), obs.data(), c.n_episode, out,
+            [&](int l, const int32_t* ids, int k, uint32_t cmd) { w.post(l, ids, k, cmd); return 0; },
+            [&](int l) {
+                if (l == fail_lane && w.pend[l].on && w.pend[l].cmd == GE_CMD_STEP && w.step_waits[l] + 1 == fail_step) {
+                    calls_at_failure = step_calls + w.posts;
+                    return -1;
+                }
+                w.wait(l);
+                return 0;
+            },
+            [&](const GeStep& s) {
+                step_calls += 1; waits_at_last_step = w.waits;
+                if (s.k_act[0] && !s.obs_act) { null_obs_act_with_rows = true; return -2; }
+                if (!s.k_act[0] && s.obs_act) obs_act_without_rows = true;
+                w.agent.request(s.k[0], s.env_ids, s.obs, s.act, s.rew, s.cost, s.terminated, s.truncated, s.obs_next, s.ep_rew_out,
+                                s.ep_len_out, s.k_act[0], s.obs_act, s.act_out, s.env_act_out);
+                return 0;
+            },
+            busy);
+        REQUIRE(!w.misuse, "a post onto a busy lane or for another lane's env, or a wait on an idle lane");
+        REQUIRE(!null_obs_act_with_rows && !obs_act_without_rows, "obs_act must be null exactly when no row is left to act on");
+        if (fail_lane >= 0) {
+            REQUIRE(rc == -1, "rc %d, expected the wait's -1", rc);
+            REQUIRE(busy[1 - fail_lane] && !busy[fail_lane], "busy %d %d: the other lane is posted, the failed one is not", busy[0], busy[1]);
+            REQUIRE(w.pend[1 - fail_lane].on, "the other lane was not posted when the wait failed");
+            REQUIRE(step_calls + w.posts == calls_at_failure, "a post or step call after the failed wait");
+            printf("ok  %s: lane %d's wait failed at its step %d, lane %d reported busy, no further post or step call\n", name, fail_lane,
+                   fail_step, 1 - fail_lane);
+            return 0;
+        }
+        REQUIRE(rc == 0 && !busy[0] && !busy[1], "rc %d, busy %d %d", rc, busy[0], busy[1]);
+        REQUIRE(!w.pend[0].on && !w.pend[1].on, "a command is still in flight after the loop");
+        if (want_trailing >= 0)
+            REQUIRE(w.waits - waits_at_last_step == want_trailing, "%d waits after the last step call, expected %d", w.waits - waits_at_last_step,
+                    want_trailing);
+        const Result r = split_alone(ref, n, c.n_episode);
+        REQUIRE(r.episodes >= c.n_episode, "the written-out loop: %d episodes, wanted %d", r.episodes, c.n_episode);
+        REQUIRE(w.agent.log == ref.agent.log, "n_episode %d: requests, posts and waits differ from the written-out loop's (%zu vs %zu numbers)",
+                c.n_episode, w.agent.log.size(), ref.agent.log.size());
+        REQUIRE(steps == r.steps && total_cost == r.total_cost && term == r.term && trunc == r.trunc && episodes == c.n_episode,
+                "n_episode %d: counts differ (steps %lld / %lld, episodes %d)", c.n_episode, (long long)steps, r.steps, episodes);
+        for (int j = 0; j < c.n_episode; ++j)
+            REQUIRE(ep_rew[(size_t)j] == r.ep_rew[(size_t)j] && ep_len_[(size_t)j] == r.ep_len[(size_t)j], "n_episode %d: episode %d differs",
+                    c.n_episode, j);
+        total_steps += r.steps;
+        w.reset_all(); ref.reset_all();
+    }
+    printf("ok  %s: %zu collects, %lld env steps, %d posts, %d waits, every request, post and wait equals the written-out loop's\n", name,
+           collects.size(), total_steps, w.posts, w.waits);
+    return 0;
+}
+
+static int run_split_refusals() {
+    const char* name = "split refusals";
+    FakeEnv a(0, 4, 3, 0);
+    std::vector<float> obs((size_t)5 * Do, 0.f);
+    int64_t steps; double cost, ep_rew[4]; int32_t term, trunc, eps, ep_len[4];
+    const GeOut out{&steps, &cost, &term, &trunc, ep_rew, ep_len, &eps};
+    int calls = 0;
+    auto post_cb = [&](int, const int32_t*, int, uint32_t) { calls += 1; return 0; };
+    auto wait_cb = [&](int) { calls += 1; return 0; };
+    auto step_cb = [&](const GeStep&) { calls += 1; return 0; };
+    struct { int32_t n; int32_t ready[5]; int32_t lane[4]; int32_t ne; int want; } cases[] = {
+        {5, {0, 1, 2, 3, 0}, {0, 0, 1, 1}, 4, GE_BAD_ROWS},
+        {0, {0, 1, 2, 3, 0}, {0, 0, 1, 1}, 4, GE_BAD_ROWS},
+        {4, {0, 1, 2, 3, 0}, {0, 0, 1, 1}, 0, GE_BAD_EPISODES},
+        {4, {0, 1, 4, 3, 0}, {0, 0, 1, 1}, 4, GE_BAD_ID},
+        {4, {0, 1, -1, 3, 0}, {0, 0, 1, 1}, 4, GE_BAD_ID},
+        {4, {0, 1, 1, 3, 0}, {0, 0, 1, 1}, 4, GE_DUP_ID},
+        {4, {0, 1, 2, 3, 0}, {0, 0, 2, 1}, 4, GE_BAD_LANE},
+    };
+    for (auto& c : cases) {
+        bool busy[2] = {true, true};
+        const int rc = ge_collect_split(a.view(), c.lane, Do, Da, c.n, c.ready, obs.data(), c.ne, out, post_cb, wait_cb, step_cb, busy);
+        REQUIRE(rc == c.want && !busy[0] && !busy[1], "rc %d (busy %d %d), expected %d", rc, busy[0], busy[1], c.want);
+    }
+    REQUIRE(calls == 0, "a refused call reached a callback");
+    printf("ok  split refusals: row counts, episode counts, env ids out of range and listed twice, a lane that is neither 0 nor 1\n");
+    return 0;
+}
+
 int main() {
     int bad = 0;
     bad += run_case("k3", {{17, 5, 0, 20}, {3, 7, 0, 6}, {4, 4, 0, 2}});
@@ -288,6 +512,17 @@ int main() {
     bad += run_case("one member's episodes all end in the same step", {{6, 4, 0, 6}, {5, 3, 1, 11}});
     bad += run_case("env failure", {{17, 5, 0, 20}, {3, 7, 0, 6}, {4, 4, 0, 2}}, 1, 3);
     bad += run_refusals();
+    const std::vector<int32_t> even{0, 0, 0, 1, 1, 1}, uneven{0, 0, 0, 0, 0, 1}, mixed{0, 1, 1, 0, 1, 1};
+    bad += run_split("split basic", even, 19, 0, {{-1, 6}, {-1, 10}, {-1, 3}, {-1, 1}, {-1, 7}, {-1, 12}});
+    bad += run_split("split uneven lanes", uneven, 19, 0, {{-1, 6}, {-1, 10}, {-1, 7}});
+    bad += run_split("split one lane empty", even, 19, 0, {{3, 5}, {3, 3}});
+    bad += run_split("split staggered", even, 19, 1, {{-1, 6}, {-1, 10}, {-1, 7}, {-1, 12}});
+    // both lanes finish 3 episodes in the same round with 4 wanted: lane 1 finds 1 left for its 3 and drops them all
+    bad += run_split("split both lanes in one round", even, 19, 0, {{6, 4}, {6, 5}});
+    // lane 0 = the envs of length 19, which give the 2 episodes; lane 1 (20, 21) has just been posted again: one trailing wait
+    bad += run_split("split fewer episodes than envs", mixed, 19, 1, {{6, 2}}, -1, 0, 1);
+    bad += run_split("split failing wait", even, 19, 0, {{-1, 6}}, 1, 3);
+    bad += run_split_refusals();
     if (bad) { printf("%d case(s) FAILED\n", bad); return 1; }
     printf("ok  all\n");
     return 0;
