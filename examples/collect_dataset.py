@@ -104,6 +104,7 @@ def main():
     path = tb.save(out, "dataset.hdf5")
     back = np.load(path)
     print(f"saved {path}: " + ", ".join(f"{k} {back[k].shape}" for k in back.files))
+    print(f"train a replay agent from it: python examples/train_agent.py --algo sacl --prefill {path}")
     tb.close()
     for eng in engines:
         eng.close()

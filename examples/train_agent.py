@@ -5,6 +5,7 @@ installed pass real vector envs exposing reset(ids) / step(act, ids) -> (obs, re
 
     python examples/train_agent.py --algo ppol --epoch 3
     python examples/train_agent.py --algo sacl --epoch 2 --device-actor
+    python examples/train_agent.py --algo sacl --epoch 2 --prefill /tmp/dataset/dataset.npz     (examples/collect_dataset.py --out /tmp/dataset)
 """
 import argparse
 import os
@@ -45,7 +46,12 @@ def main():
     ap.add_argument("--reward-normalization", action="store_true", help="critics learn returns / running std")
     ap.add_argument("--value-clip", action="store_true", help="PPO-Lag clipped value loss (needs --reward-normalization)")
     ap.add_argument("--recompute-advantage", action="store_true", help="PPO-Lag / FOCOPS: GAE from the current critics before every pass")
+    ap.add_argument("--prefill", default=None, metavar="PATH",
+                    help="sacl / ddpgl / cvpo: start from a replay store filled with the episodes of this dataset (the .npz that "
+                         "examples/collect_dataset.py or TrajectoryBuffer.save writes) instead of an empty one")
     a = ap.parse_args()
+    if a.prefill is not None and a.algo not in ("sacl", "ddpgl", "cvpo"):
+        ap.error(f"--prefill fills a replay store: --algo must be sacl, ddpgl or cvpo, not {a.algo}")
     if a.task == "point-circle":
         # the reference's own construction (train_ppol_agent.py:120-123): one factory per env, in process or in worker processes
         from fsrl_amd.env import DummyVectorEnv, PointCircleEnv, ShmemVectorEnv
@@ -73,7 +79,8 @@ def main():
     agent = AGENTS[a.algo](env, logger, **kw)
     if a.algo in ("sacl", "ddpgl", "cvpo"):
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, update_per_step=0.2,
-                          batch_size=a.batch_size, testing_num=2, device_actor=a.device_actor, verbose=True, save_ckpt=False)
+                          batch_size=a.batch_size, testing_num=2, device_actor=a.device_actor, verbose=True, save_ckpt=False,
+                          prefill=a.prefill)
     else:
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, repeat_per_collect=4,
                           batch_size=a.batch_size if a.algo in ("ppol", "focops") else a.tr_batch_size, testing_num=2, device_actor=a.device_actor,

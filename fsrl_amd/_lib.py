@@ -219,6 +219,8 @@ SIGNATURES = {
     "fsrl_traj_export": (C.c_int, [_ctx, _f, _f, _f, _d, _d, _u8, _u8, C.c_int64, _i64]),
     "fsrl_traj_clear": (C.c_int, [_ctx]),
     "fsrl_traj_counters": (C.c_int, [_ctx, _i64, C.c_int32]),
+    "fsrl_traj_import": (C.c_int, [_ctx, C.c_int64, _f, _f, _f, _d, _d, _u8, _u8, C.c_int32, _i64, _i64]),
+    "fsrl_store_fill": (C.c_int, [_ctx, _ctx, _i32, C.c_int64, C.c_int32, C.c_int32, _f, _f, _i64]),
     "fsrl_set_profiling": (C.c_int, [_ctx, C.c_int]),
     "fsrl_last_timing": (C.c_int, [_ctx, _d, C.c_int32]),
 }

@@ -24,12 +24,16 @@ class OffpolicyAgent(BaseAgent):
               step_per_epoch: int = 3000, update_per_step: float = 0.1, buffer_size: Optional[int] = None,
               testing_num: int = 2, batch_size: int = 256, reward_threshold: float = 450,
               save_interval: int = 4, resume: bool = False, save_ckpt: bool = True, verbose: bool = True,
-              show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True):
+              show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True, prefill=None):
         """resume=True continues the run whose training state `<log_dir>/checkpoint/train_state.pt` holds (saved with every periodic
         checkpoint while save_ckpt is on): epoch numbering, env steps, the best result, the replay store, optimiser state and
         random streams carry over; without such a file the run starts fresh and says so.  Env state is never saved: a resumed
         run resets its envs.  ckpt_store: whether the replay store goes into train_state.pt (about 320 MB for a million rows of
-        33 observations and 8 actions); without it a resumed run starts from an empty store."""
+        33 observations and 8 actions); without it a resumed run starts from an empty store.
+        prefill: a TrajectoryBuffer, or the path of a dataset one saved -- its episodes are poured into the replay store
+        (HipVectorReplayBuffer.fill_from, actions mapped back with this policy's inverse action map) after the store has been cut
+        to this call's geometry and before the first collect; no env step is counted for them.  Skipped, with a printed line, when
+        resume=True restored a store."""
         assert self.policy is not None, "The policy is not initialized"
         self.policy.train()
         eng = self.policy.engine
@@ -61,12 +65,40 @@ class OffpolicyAgent(BaseAgent):
                                    show_progress=show_progress)
         if save_ckpt:                            # registered late: the state is the trainer's and the policy's
             self.logger.setup_train_state_fn(lambda: trainer.train_state(with_store=ckpt_store))
+        if prefill is not None:
+            self._prefill(prefill, buffer, resumed=resume and len(buffer) > 0)
         ep, stat, info = 0, {}, {}
         for ep, stat, info in trainer:
             self.logger.store(tab="train", cost_limit=self.cost_limit)
             if verbose:
                 print(f"Epoch: {ep}", info)
         return ep, stat, info
+
+    def _prefill(self, prefill, buffer, resumed: bool) -> int:
+        """learn(prefill=...): a TrajectoryBuffer or a dataset path -> rows poured into `buffer`"""
+        if resumed:
+            print(f"prefill: skipped, the resumed run restored a replay store of {len(buffer)} rows")
+            return 0
+        from fsrl_amd.data.traj_buf import TrajectoryBuffer, _read_dataset
+        tb, own = prefill, False
+        if not isinstance(prefill, TrajectoryBuffer):
+            # a file: an archive of its own on this engine's device, sized for the file, attached to nothing (it records nothing)
+            # and gone after the fill; every episode of the file is kept (no window, no filter)
+            data = _read_dataset(prefill)
+            ends = np.flatnonzero(np.asarray(data["terminals"]).astype(bool) | np.asarray(data["timeouts"]).astype(bool)) + 1
+            longest = int(np.diff(np.concatenate([[0], ends])).max()) if len(ends) else 1
+            tb = TrajectoryBuffer(max_trajectory=max(len(ends), 1), use_grid_filter=False, max_rows=max(len(data["rewards"]), longest, 1),
+                                  max_episode_len=longest)
+            tb._create(self.policy.engine, self.policy)
+            own = True
+            tb.load(data)
+        try:
+            rows = buffer.fill_from(tb, policy=self.policy)
+        finally:
+            if own:
+                tb.close()
+        print(f"prefill: {rows} rows poured into the replay store ({len(buffer)} rows held)")
+        return rows
 
 
 class SACLagAgent(OffpolicyAgent):

@@ -230,7 +230,7 @@ static int lay_infer(fsrl_ctx* c, const InferArgs& ia, int jobs_y, hipStream_t s
 static void comm_free(fsrl_ctx* c);
 // the trajectory tap (host_traj.inc): every row fsrl_store_push stages, every window flush_stage sends
 static inline bool tap_closed(const fsrl_ctx* c, int e);
-static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, bool done);
+static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, uint8_t fl);
 static int tap_flush(fsrl_ctx* c, int w, const uint8_t* recs_d, int stage_rec, int k);
 static void tap_ctx_gone(fsrl_ctx* c);           // a context destroyed before the archive it feeds
 static int focops_pass(fsrl_ctx* c, int32_t* stopped_out);
@@ -848,7 +848,7 @@ extern "C" int fsrl_store_push(fsrl_ctx* c, const int32_t* env_ids, int32_t k, c
             memcpy(r + 24 + (size_t)Do * 8, act + (size_t)j * Da, (size_t)Da * 4);
         }
         c->h_flags[(size_t)gptr] = fl;
-        if (c->tap) tap_row(c, e, i, act + (size_t)j * Da, rew[j], cost ? cost[j] : 0.0, fl != 0);
+        if (c->tap) tap_row(c, e, i, act + (size_t)j * Da, rew[j], cost ? cost[j] : 0.0, fl);
         // ReplayBuffer.add bookkeeping (ptr, ep_rew, ep_len, ep_idx)
         eb.last_index = ptr;
         eb.size = std::min(eb.size + 1, c->sub_size);

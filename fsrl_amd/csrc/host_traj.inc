@@ -6,14 +6,21 @@
 //     one H2D copy      the tap's records of the window (+ the job table of the episodes that ended in it)
 //     traj_stage_kernel the window's rows -> the open-episode area
 //     traj_move_kernel  the episodes that ended in the window -> the tail of the archive     (only when one ended)
-// so a row is in HBM once and never comes back until fsrl_traj_export.  The bookkeeping -- episode table, room, the job tables, the
+// so a row is in HBM once and comes back to the host only in fsrl_traj_export.  The bookkeeping -- episode table, room, the job tables, the
 // two halves of the archive -- is traj_plan.hpp (HIP-free, driven by tests/host/traj_plan_sim.cpp).
 //
 // Ordering.  Everything a context feeds is ordered by that context's side stream.  Several contexts may feed one archive: their
 // commits go to disjoint rows the host assigned, so their side streams need no order among each other.  A compaction reads what all
 // of them wrote: it waits for every feeding context's side stream, runs on the archive's own stream and is waited for.  The calls
 // of one archive, and the pushes of the contexts that feed it, come from one thread.
+//
+// Datasets in.  fsrl_traj_import commits host columns in the export layout as tapped episodes are committed: the accepted rows go to
+// the tail of the current half in one copy per column and run of neighbouring accepted episodes, on the archive's own stream, and
+// are waited for.  fsrl_store_fill pours archived episodes into a context's store: one H2D copy of a job table (store_fill_plan.hpp)
+// and ONE launch of store_fill_kernel on that context's side stream.  The kernel reads the current half; a compaction (which makes
+// the other half current, so that the one after it would write what the kernel reads) waits for the last fill first.
 #include "traj_plan.hpp"
+#include "store_fill_plan.hpp"
 #include "kernels_traj.hpp"
 
 static_assert(sizeof(TrajJob) == sizeof(trajp::Job), "TrajJob mirrors trajp::Job");
@@ -30,7 +37,19 @@ struct fsrl_traj {
     std::vector<fsrl_tap*> taps;
     int32_t next_source = 0;
     int64_t launches = 0, h2d_bytes = 0;
+    // fsrl_store_fill: [job table | low[Da] | scale[Da]] in one pinned buffer and its device copy; fill_done is recorded behind the
+    // last fill's launch on the side stream it ran on
+    DevTable<uint8_t> fill;
+    hipEvent_t fill_done = nullptr;
+    bool fill_pending = false;
+    int64_t fill_launches = 0, fill_copies = 0;
 };
+static int traj_fill_wait(fsrl_traj* t) {
+    if (!t->fill_pending) return 0;
+    HIPCHK(hipEventSynchronize(t->fill_done));
+    t->fill_pending = false;
+    return 0;
+}
 
 struct fsrl_tap {
     fsrl_traj* t = nullptr;
@@ -60,7 +79,7 @@ static void traj_cols_free(TrajCols& c) {
 static inline bool tap_closed(const fsrl_ctx* c, int e) { return c->tap->env[(size_t)e].ends >= 2; }
 
 // one staged row: record i of the current window, env e
-static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, bool done) {
+static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, uint8_t fl) {
     fsrl_tap* tp = c->tap;
     fsrl_traj* t = tp->t;
     trajp::OpenEpisode& oe = tp->env[(size_t)e];
@@ -71,14 +90,16 @@ static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, dou
     map_env_action(t->Da, 1, t->bound_method, t->bounds ? t->low.data() : nullptr, t->bounds ? t->high.data() : nullptr, act,
                    reinterpret_cast<float*>(r + 4));
     oe.rows += 1; oe.rew += rew; oe.cost += cost;       // current_rew += ... .item() (traj_buf.py:66-69): float64, push order
-    if (!done) return;
+    if (!fl) return;
     if (oe.rows > tp->L) t->book.n.dropped_long += 1;
     else if (!t->book.in_window(oe.rew, oe.cost)) t->book.n.rejected_window += 1;
-    else tp->pending.push_back(trajp::Pending{slot, oe.rows, oe.rew, oe.cost});
+    else tp->pending.push_back(trajp::Pending{slot, oe.rows, oe.rew, oe.cost, fl});
     oe.next();              // its rows are in this window, in this slot: the env's next episode takes the other one
 }
 
 static int traj_compact(fsrl_traj* t) {
+    int frc = traj_fill_wait(t);
+    if (frc) return frc;
     for (fsrl_tap* tp : t->taps) HIPCHK(hipStreamSynchronize(tp->c->side));
     std::vector<trajp::Job> jobs;
     const int from = t->book.cur;
@@ -151,6 +172,9 @@ extern "C" int fsrl_traj_destroy(fsrl_traj* t) {
     if (!t) return 0;
     (void)hipSetDevice(t->device);
     while (!t->taps.empty()) tap_free(t->taps.back(), false);
+    (void)traj_fill_wait(t);
+    if (t->fill_done) (void)hipEventDestroy(t->fill_done);
+    table_free(t->fill);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
     traj_cols_free(t->half[0]); traj_cols_free(t->half[1]);
     table_free(t->jobs);
@@ -175,6 +199,7 @@ extern "C" int fsrl_traj_create(fsrl_ctx* c, int64_t max_rows, int32_t max_episo
     t->book.max_rows = max_rows; t->book.max_episodes = max_episodes; t->book.max_len = max_episode_len;
     int rc = 0;
     { hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking); if (e != hipSuccess) rc = fail(FSRL_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
+    if (!rc && hipEventCreateWithFlags(&t->fill_done, hipEventDisableTiming) != hipSuccess) rc = fail(FSRL_EHIP, "hipEventCreate failed");
     if (!rc) rc = traj_cols_alloc(t->half[0], (size_t)max_rows, t->Do, t->Da);
     if (!rc) rc = traj_cols_alloc(t->half[1], (size_t)max_rows, t->Do, t->Da);
     if (rc) { const std::string keep = g_err; fsrl_traj_destroy(t); g_err = keep; return rc; }
@@ -317,8 +342,143 @@ extern "C" int fsrl_traj_clear(fsrl_traj* t) {
 extern "C" int fsrl_traj_counters(fsrl_traj* t, int64_t* out, int32_t n) {
     CHECK_ARG(t && out && n >= 0, "bad argument");
     const trajp::Counters& k = t->book.n;
-    const int64_t v[10] = {k.committed, k.rejected_window, k.dropped_long, k.compactions, k.rows, k.refused_full,
-                           (int64_t)t->book.table.size(), t->launches, t->h2d_bytes, k.abandoned};
-    for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+    const int64_t v[13] = {k.committed, k.rejected_window, k.dropped_long, k.compactions, k.rows, k.refused_full,
+                           (int64_t)t->book.table.size(), t->launches, t->h2d_bytes, k.abandoned, k.import_open, t->fill_launches,
+                           t->fill_copies};
+    for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ datasets in
+// the accepted runs so far: one copy per column, host rows -> the tail of the current half, on the archive's stream
+static int import_send(fsrl_traj* t, std::vector<trajp::ImportRun>& runs, const float* obs, const float* next_obs, const float* act,
+                       const double* rew, const double* cost, const uint8_t* terminals, const uint8_t* timeouts) {
+    const TrajCols& a = t->half[t->book.cur];
+    const size_t Do = (size_t)t->Do, Da = (size_t)t->Da;
+    for (const trajp::ImportRun& r : runs) {
+        const size_t s = (size_t)r.src, d = (size_t)r.dst, n = (size_t)r.rows;
+        HIPCHK(hipMemcpyAsync(a.obs + d * Do, obs + s * Do, n * Do * 4, hipMemcpyHostToDevice, t->stream));
+        HIPCHK(hipMemcpyAsync(a.obs_next + d * Do, next_obs + s * Do, n * Do * 4, hipMemcpyHostToDevice, t->stream));
+        HIPCHK(hipMemcpyAsync(a.act + d * Da, act + s * Da, n * Da * 4, hipMemcpyHostToDevice, t->stream));
+        HIPCHK(hipMemcpyAsync(a.rew + d, rew + s, n * 8, hipMemcpyHostToDevice, t->stream));
+        if (cost) HIPCHK(hipMemcpyAsync(a.cost + d, cost + s, n * 8, hipMemcpyHostToDevice, t->stream));
+        else HIPCHK(hipMemsetAsync(a.cost + d, 0, n * 8, t->stream));
+        if (terminals) HIPCHK(hipMemcpyAsync(a.terminals + d, terminals + s, n, hipMemcpyHostToDevice, t->stream));
+        else HIPCHK(hipMemsetAsync(a.terminals + d, 0, n, t->stream));
+        if (timeouts) HIPCHK(hipMemcpyAsync(a.timeouts + d, timeouts + s, n, hipMemcpyHostToDevice, t->stream));
+        else HIPCHK(hipMemsetAsync(a.timeouts + d, 0, n, t->stream));
+    }
+    runs.clear();
+    HIPCHK(hipStreamSynchronize(t->stream));
+    return 0;
+}
+
+extern "C" int fsrl_traj_import(fsrl_traj* t, int64_t rows, const float* obs, const float* next_obs, const float* act,
+                                const double* rew, const double* cost, const uint8_t* terminals, const uint8_t* timeouts,
+                                int32_t source, int64_t* episodes_out, int64_t* rows_out) {
+    CHECK_ARG(t && rows >= 0, "bad argument");
+    CHECK_ARG(rows == 0 || (obs && next_obs && act && rew), "null column (observations, next_observations, actions and rewards are required)");
+    CHECK_ARG(terminals || timeouts || rows == 0, "terminals and timeouts are both null: no episode ever ends");
+    HIPCHK(hipSetDevice(t->device));
+    if (episodes_out) *episodes_out = 0;
+    if (rows_out) *rows_out = 0;
+    std::vector<trajp::ImportEpisode> eps;
+    trajp::import_scan(t->book, rows, rew, cost, terminals, timeouts, eps);
+    // the flag columns hold 0 / 1 in the archive whatever non-zero value the caller's have
+    std::vector<uint8_t> term01, time01;
+    if (terminals) { term01.resize((size_t)rows); for (int64_t i = 0; i < rows; ++i) term01[(size_t)i] = terminals[i] ? 1 : 0; }
+    if (timeouts) { time01.resize((size_t)rows); for (int64_t i = 0; i < rows; ++i) time01[(size_t)i] = timeouts[i] ? 1 : 0; }
+    const uint8_t* tm = terminals ? term01.data() : nullptr;
+    const uint8_t* to = timeouts ? time01.data() : nullptr;
+    std::vector<trajp::ImportRun> runs;
+    int64_t n_eps = 0, n_rows = 0;
+    int rc = 0, refused = 0;
+    std::string why;
+    for (const trajp::ImportEpisode& e : eps) {
+        int r = trajp::import_commit(t->book, e, source, runs);
+        if (r == 1) {       // rows accepted so far must be in the archive before a compaction copies them
+            rc = import_send(t, runs, obs, next_obs, act, rew, cost, tm, to);
+            if (!rc) rc = traj_compact(t);
+            if (rc) return rc;
+            r = trajp::import_commit(t->book, e, source, runs);
+        }
+        if (r == 0) { n_eps += 1; n_rows += e.rows; }
+        else if (r == -1 || r == 1) { if (!refused++) why = t->book.err; }
+    }
+    rc = import_send(t, runs, obs, next_obs, act, rew, cost, tm, to);
+    if (rc) return rc;
+    if (episodes_out) *episodes_out = n_eps;
+    if (rows_out) *rows_out = n_rows;
+    if (refused) return fail(FSRL_ENOMEM, "%s", why.c_str());
+    return 0;
+}
+
+extern "C" int fsrl_store_fill(fsrl_ctx* c, fsrl_traj* t, const int32_t* episode_ids, int64_t n, int32_t first_env,
+                               int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out) {
+    CHECK_ARG(c && t, "null argument");
+    CHECK_ARG(c->cfg.obs_dim == t->Do, "obs_dim: the context has %d, the trajectory archive %d", c->cfg.obs_dim, t->Do);
+    CHECK_ARG(c->cfg.act_dim == t->Da, "act_dim: the context has %d, the trajectory archive %d", c->cfg.act_dim, t->Da);
+    CHECK_ARG(c->device == t->device, "device: the context is on %d, the trajectory archive on %d", c->device, t->device);
+    CHECK_ARG(bound_method >= 0 && bound_method <= 2, "bound_method %d: 0 none, 1 clip, 2 tanh", bound_method);
+    CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
+    if (c->in_update || c->verdict_pending)
+        return fail(FSRL_ESTATE, "update: fsrl_store_fill inside an update (between fsrl_ppo_begin and fsrl_ppo_end)");
+    if (rows_out) *rows_out = 0;
+    ENTER_DEV(c);
+    // the archive's rows are final: every feeding context's window is flushed and its side stream has finished (this context's
+    // own window among them when it feeds `t`; an archive without room reports it here, before anything is written)
+    int rc = fsrl_traj_flush(t);
+    if (rc) return rc;
+    fillp::Plan p;
+    std::vector<fillp::SubBook> books((size_t)c->active_envs);
+    for (int e = 0; e < c->active_envs; ++e) {
+        const EnvBook& b = c->env[(size_t)e];
+        fillp::SubBook& s = books[(size_t)e];
+        s.index = b.index; s.size = b.size; s.last_index = b.last_index; s.ep_rew = b.ep_rew; s.ep_len = b.ep_len; s.ep_idx = b.ep_idx;
+    }
+    if (!fillp::plan(t->book.table, episode_ids, n, first_env, c->sub_size, c->active_envs, books, p))
+        return fail(p.code == fillp::REFUSE_STATE ? FSRL_ESTATE : FSRL_EINVAL, "%s", p.err.c_str());
+    if (rows_out) *rows_out = p.rows;
+    if (p.rows == 0) return 0;      // the loop of no pushes
+    // what the kernel relies on, once more, against the allocations themselves
+    for (const trajp::Job& j : p.jobs)
+        if (j.rows < 1 || j.src < 0 || j.src + j.rows > t->book.max_rows || j.dst < 0 || j.dst + j.rows > c->maxsize ||
+            c->maxsize > c->alloc_rows)
+            return fail(FSRL_ESTATE, "fsrl_store_fill: a job leaves its buffers (src %lld, dst %lld, rows %d)", (long long)j.src,
+                        (long long)j.dst, j.rows);
+    rc = flush_stage(c);            // rows already in the staging window land first
+    if (rc) return rc;
+    rc = traj_fill_wait(t);         // the last fill may still read the table
+    if (rc) return rc;
+    const size_t nj = p.jobs.size(), Da = (size_t)t->Da;
+    const size_t map_off = nj * sizeof(TrajJob), bytes = map_off + (act_low ? 2 * Da * 4 : 0);
+    rc = table_ensure(t->fill, bytes, bytes + bytes / 2 + 4096);
+    if (rc) return rc;
+    memcpy(t->fill.h, p.jobs.data(), map_off);
+    if (act_low) {
+        float* m = reinterpret_cast<float*>(t->fill.h + map_off);
+        const float eps = 1.1920928955078125e-07f;      // np.finfo(np.float32).eps
+        for (size_t d = 0; d < Da; ++d) {
+            float scale = act_high[d] - act_low[d];
+            if (scale < eps) scale += eps;              // scale[scale < eps] += eps (base_policy.py:279)
+            m[d] = act_low[d]; m[Da + d] = scale;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(t->fill.d, t->fill.h, bytes, hipMemcpyHostToDevice, c->side));
+    hipLaunchKernelGGL(store_fill_kernel, dim3((unsigned)std::min<size_t>(nj, 4096)), dim3(256), 0, c->side, t->half[t->book.cur],
+                       c->st, reinterpret_cast<const TrajJob*>(t->fill.d), (int)nj, t->Do, t->Da, (int)bound_method,
+                       act_low ? reinterpret_cast<const float*>(t->fill.d + map_off) : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t->fill_done, c->side));
+    t->fill_pending = true;
+    t->fill_launches += 1; t->fill_copies += 1;
+    // the host's side of the pushes: the flag mirror, the books, and a store that has changed
+    fillp::apply_flags(p, c->h_flags.data());
+    for (int e = 0; e < c->active_envs; ++e) {
+        EnvBook& b = c->env[(size_t)e];
+        const fillp::SubBook& s = p.books[(size_t)e];
+        b.index = s.index; b.size = s.size; b.last_index = s.last_index; b.ep_rew = s.ep_rew; b.ep_len = s.ep_len; b.ep_idx = s.ep_idx;
+    }
+    c->store_version += 1;
     return 0;
 }

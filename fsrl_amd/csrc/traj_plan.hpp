@@ -8,6 +8,7 @@
 // whatever the table order is (fsrl_traj_keep / _replace permute it).
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -25,9 +26,13 @@ struct Episode {
     int64_t first = 0;          // first row in the current half
     int32_t rows = 0, id = 0, source = 0;
     double rew = 0.0, cost = 0.0;
+    uint8_t end = 1;            // flags of its last row: terminal | timeout << 1 (every other row of an episode has none)
 };
 
-struct Counters { int64_t committed = 0, rejected_window = 0, dropped_long = 0, compactions = 0, rows = 0, refused_full = 0, abandoned = 0; };
+struct Counters {
+    int64_t committed = 0, rejected_window = 0, dropped_long = 0, compactions = 0, rows = 0, refused_full = 0, abandoned = 0;
+    int64_t import_open = 0;    // fsrl_traj_import: trailing runs without an end flag (open episodes are never archived)
+};
 
 static inline void add_run(std::vector<Job>& jobs, int64_t src, int64_t dst, int64_t rows) {
     for (int64_t o = 0; o < rows; o += JOB_ROWS)
@@ -65,9 +70,9 @@ struct Book {
         return -1;
     }
     // Append an episode at the tail (room() said 0).  Returns its first row.
-    int64_t commit(int32_t rows, int32_t source, double rew, double cost) {
+    int64_t commit(int32_t rows, int32_t source, double rew, double cost, uint8_t end = 1) {
         Episode e;
-        e.first = tail; e.rows = rows; e.id = next_id++; e.source = source; e.rew = rew; e.cost = cost;
+        e.first = tail; e.rows = rows; e.id = next_id++; e.source = source; e.rew = rew; e.cost = cost; e.end = end;
         table.push_back(e);
         // appended behind a packed archive, at the end of the table: still packed
         packed = packed && tail == alive_rows;
@@ -156,7 +161,7 @@ struct OpenEpisode {
     void next() { rew = cost = 0.0; rows = 0; ends += 1; parity ^= 1; }
 };
 // an episode that ended inside the current staging window and goes to the archive when the window is flushed
-struct Pending { int32_t slot, rows; double rew, cost; };
+struct Pending { int32_t slot, rows; double rew, cost; uint8_t end = 1; };
 
 static inline bool batch_wants_compaction(const Book& b, const std::vector<Pending>& batch) {
     int64_t need = 0;
@@ -170,9 +175,47 @@ static inline int commit_batch(Book& b, const std::vector<Pending>& batch, int L
         const bool fits = b.room(p.rows) == 0;
         if (ids_out) ids_out->push_back(fits ? b.next_id : -1);
         if (!fits) { b.n.refused_full += 1; refused += 1; continue; }
-        add_run(jobs, (int64_t)p.slot * L, b.commit(p.rows, source, p.rew, p.cost), p.rows);
+        add_run(jobs, (int64_t)p.slot * L, b.commit(p.rows, source, p.rew, p.cost, p.end), p.rows);
     }
     return refused;
+}
+
+// ---- fsrl_traj_import: host columns in the export layout -> episodes, committed as tapped ones are.
+// An episode ends at every row whose terminal or timeout flag is set; its float64 returns are the sums of its rows in row order.
+// A trailing run without an end flag is an open episode: dropped and counted.
+struct ImportEpisode { int64_t first; int32_t rows; double rew, cost; uint8_t end; };
+static inline void import_scan(Book& b, int64_t rows, const double* rew, const double* cost, const uint8_t* terminals,
+                               const uint8_t* timeouts, std::vector<ImportEpisode>& out) {
+    out.clear();
+    int64_t first = 0;
+    double r = 0.0, c = 0.0;
+    for (int64_t i = 0; i < rows; ++i) {
+        r += rew[i]; c += cost ? cost[i] : 0.0;
+        const uint8_t fl = (uint8_t)((terminals && terminals[i] ? 1 : 0) | (timeouts && timeouts[i] ? 2 : 0));
+        if (!fl) continue;
+        // an episode of 2^31 rows or more is longer than any max_len
+        out.push_back(ImportEpisode{first, (int32_t)std::min<int64_t>(i + 1 - first, INT32_MAX), r, c, fl});
+        first = i + 1; r = c = 0.0;
+    }
+    if (first < rows) b.n.import_open += 1;
+}
+// host rows [src, src + rows) -> rows [dst, dst + rows) of the current half: one copy per column
+struct ImportRun { int64_t src, dst, rows; };
+// One scanned episode against the limits, the window and the room.  0: committed (its rows are appended to `runs`, merged with the
+// run before it where both ends are adjacent); 1: a compaction can make room -- send `runs`, compact, call again; -1: no room (b.err
+// names the limit; dropped and counted); -2: too long or outside the window (dropped and counted).
+static inline int import_commit(Book& b, const ImportEpisode& e, int32_t source, std::vector<ImportRun>& runs) {
+    if (e.rows > b.max_len) { b.n.dropped_long += 1; return -2; }
+    if (!b.in_window(e.rew, e.cost)) { b.n.rejected_window += 1; return -2; }
+    const int room = b.room(e.rows);
+    if (room > 0) return 1;
+    if (room < 0) { b.n.refused_full += 1; return -1; }
+    const int64_t dst = b.commit(e.rows, source, e.rew, e.cost, e.end);
+    if (!runs.empty() && runs.back().src + runs.back().rows == e.first && runs.back().dst + runs.back().rows == dst)
+        runs.back().rows += e.rows;
+    else
+        runs.push_back(ImportRun{e.first, dst, e.rows});
+    return 0;
 }
 
 }  // namespace trajp

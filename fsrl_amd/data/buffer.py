@@ -41,6 +41,25 @@ class HipVectorReplayBuffer:
         for e in buffer_ids:
             self._sizes[e] = min(self._sizes[e] + 1, self._sub)
 
+    def fill_from(self, traj_buffer, episodes=None, policy=None, first_env: int = 0) -> int:
+        """Pour stored episodes of a TrajectoryBuffer into this store without leaving the device (fsrl_store_fill: one job table,
+        one launch).  `episodes`: indices into the buffer's stored order (None: all); episode j goes to sub-buffer
+        (first_env + j) % buffer_num, exactly as if its rows had been add()-ed one by one, wrap-around included.  The archive holds
+        the action the env received and the store the raw policy action: `policy` gives the inverse mapping (its
+        action_bound_method, action_scaling and action_space.low / high; None: actions are taken as they are).  Under tanh a
+        saturated action (+-1) is clamped to +-(1 - 2**-24) before the inverse, where the reference's map_action_inverse returns
+        +-inf.  The rows are not recorded again by a TrajectoryBuffer that taps this engine.  -> the number of rows poured."""
+        from fsrl_amd.data.traj_buf import policy_action_map
+        traj_buffer.sync()
+        archive = traj_buffer._archive
+        if archive is None:
+            raise RuntimeError("fill_from: the TrajectoryBuffer has no archive yet (attach an engine and load or collect episodes)")
+        ids = list(traj_buffer._ids) if episodes is None else [traj_buffer._ids[int(i)] for i in episodes]
+        code, low, high = policy_action_map(policy)
+        rows = self.engine.store_fill(archive, ids, first_env, code, low, high)
+        self.sync_sizes()
+        return rows
+
     def sync_sizes(self) -> None:
         """Fill levels from the engine (rows stored through fsrl_collect_step bypass this proxy)."""
         self._sizes[:] = self.engine.store_sizes()

@@ -6,9 +6,10 @@ Behaviour of fsrl/data/traj_buf.py, restated: an episode is stored when its rewa
 
 What differs is where the rows are.  The reference's collector hands the buffer one transition at a time on the host.  Here the
 buffer is a TAP on the engine's store ingest (fsrl_traj_*, include/fsrl_hip.h): every row any collector pushes -- solo, grouped,
-over worker-process envs, inside the native collect loops -- also reaches an archive in HBM, and comes back only in get_all() /
-save().  Python is not in that loop, so the keep / filter / replace decisions are made when the buffer is next looked at (len(),
-metrics, get_all(), ...): the episodes committed since the last look are run through the reference's decision sequence in commit
+over worker-process envs, inside the native collect loops -- also reaches an archive in HBM, and comes back to the host only in
+get_all() / save().  load() reads a saved dataset back into the archive, and HipVectorReplayBuffer.fill_from pours archived episodes
+into a replay store on the device.  Python is not in the push loop, so the keep / filter / replace decisions are made when the
+buffer is next looked at (len(), metrics, get_all(), ...): the episodes committed since the last look are run through the reference's decision sequence in commit
 order, which gives the reference's result because that sequence depends on nothing but the order of the accepted episodes and the
 random streams (`random` for the grid filter, `np.random` for the replacement).  The archive therefore has to hold what gathers
 between two looks: `max_rows` / `max_episode_len`; FastCollector-driven training looks after every collect when the buffer was
@@ -19,7 +20,7 @@ pushed policy action under this buffer's `action_bound_method` and `action_space
 bit the env_act the collect calls hand out.  Collectors that map actions in numpy (the host-actor path) record the library's mapping
 of the stored action, not numpy's.
 
-The archive is not part of Engine.train_state(): a resumed run starts with an empty buffer (save() before stopping)."""
+The archive is not part of Engine.train_state(): a resumed run starts with an empty buffer (save() before stopping, load() after)."""
 import numbers
 import os
 import random
@@ -60,6 +61,70 @@ def filter_points(points, target_size: int) -> list:
         if len(grid[cell]) == 0:
             non_empty.remove(cell)
     return kept[:target_size]
+
+
+BOUND_CODES = {None: 0, "": 0, "clip": 1, "tanh": 2}
+TANH_CLAMP = np.float32(1.0 - 2.0 ** -24)
+
+
+def inverse_action(act, bound_method=0, low=None, high=None) -> np.ndarray:
+    """BasePolicy.map_action_inverse in float32 numpy, as fsrl_store_fill applies it on the device: the recorded env action back to
+    the raw policy action a replay store holds.  low / high None: no rescale.  bound_method 0 none, 1 clip, 2 tanh (or the names).
+    One departure from the reference, the library's: under tanh the value is clamped to +-(1 - 2**-24) before the inverse, where
+    the reference returns +-inf at +-1."""
+    code = BOUND_CODES.get(bound_method, bound_method)
+    a = np.asarray(act, np.float32)
+    if low is not None:
+        low = np.asarray(low, np.float32)
+        scale = np.asarray(high, np.float32) - low
+        eps = np.finfo(np.float32).eps.item()
+        scale = np.where(scale < eps, scale + np.float32(eps), scale).astype(np.float32)
+        a = (a - low) * np.float32(2.0) / scale - np.float32(1.0)
+    if code == 2:
+        a = np.clip(a, -TANH_CLAMP, TANH_CLAMP)
+        a = (np.log(np.float32(1.0) + a) - np.log(np.float32(1.0) - a)) / np.float32(2.0)
+    return a.astype(np.float32)
+
+
+def policy_action_map(policy):
+    """(bound code, low, high) of a policy's map_action: what fill_from and the archive's `actions` column are mapped with"""
+    if policy is None:
+        return 0, None, None
+    space = getattr(policy, "action_space", None)
+    if space is None:
+        return 0, None, None
+    scale = bool(getattr(policy, "action_scaling", False)) and hasattr(space, "low")
+    return (BOUND_CODES[getattr(policy, "action_bound_method", "")], space.low if scale else None, space.high if scale else None)
+
+
+def _read_dataset(x) -> dict:
+    """the seven DSRL columns from a dict, an .npz, or an HDF5 file (h5py permitting)"""
+    if isinstance(x, dict):
+        data = x
+    else:
+        path = os.fspath(x)
+        stem, ext = os.path.splitext(path)
+        if ext.lower() != ".npz":
+            try:
+                import h5py
+            except ImportError:
+                h5py = None
+            if h5py is not None and hasattr(h5py, "File"):
+                with h5py.File(path, "r") as f:
+                    data = {k: np.asarray(f[k]) for k in COLUMNS}
+            elif os.path.exists(stem + ".npz"):
+                path, data = stem + ".npz", None
+            else:
+                raise ImportError(f"{path}: reading HDF5 needs h5py, and there is no {stem}.npz beside it")
+        else:
+            data = None
+        if data is None:
+            with np.load(path) as f:
+                data = {k: f[k] for k in COLUMNS}
+    missing = [k for k in COLUMNS if k not in data]
+    if missing:
+        raise KeyError(f"dataset without the column(s) {missing}")
+    return data
 
 
 def _engine_of(x):
@@ -266,6 +331,46 @@ class TrajectoryBuffer:
                 for k, v in data.items():
                     f.create_dataset(k, data=v, compression="gzip")
         return npz
+
+    def load(self, path_or_dict, source: Optional[int] = None) -> int:
+        """Read a dataset back into the archive: a `.npz` written by save(), the dict get_all() returns, or an HDF5 file with the
+        reference's keys where h5py imports (h5py is not among this project's test dependencies: the HDF5 branch is untested; a
+        `.hdf5` path without h5py falls back to the `.npz` of the same stem, which save() always writes).  -> the number of
+        episodes the archive accepted.
+
+        An episode ends at every row where terminals | timeouts is set; a trailing run without an end flag is an open episode and
+        is dropped.  Every episode is committed as a collected one is -- float64 returns summed in row order, this buffer's reward /
+        cost window, max_episode_len -- and then passes through the same decisions in file order (capacity, grid filter, random
+        replacement): loading is the reference's store() applied episode by episode.  `source`: the number the loaded episodes
+        carry in `sources` (default -1: no attached engine).  The archive lives on an engine's device, so one must be attached
+        first.  The file goes in pieces of whole episodes with a look between them, so that a dataset larger than what the archive
+        holds between two looks still loads when the decisions thin it."""
+        if self._archive is None:
+            raise RuntimeError("TrajectoryBuffer.load: attach an engine first (attach(engine_or_policy), or pass one to the "
+                               "constructor): the archive lives on its device")
+        data = _read_dataset(path_or_dict)
+        src = -1 if source is None else int(source)
+        self.sync()
+        ends = np.flatnonzero(np.asarray(data["terminals"]).astype(bool) | np.asarray(data["timeouts"]).astype(bool)) + 1
+        n = len(data["rewards"])
+        accepted, at = 0, 0
+        budget = max(1, int(getattr(self._archive, "max_rows", 1 << 16)) // 4)
+        while at < n:
+            # as many whole episodes as fit the budget, at least one; the open tail goes with the last piece
+            k = int(np.searchsorted(ends, at + budget, side="right"))       # episode ends inside the budget
+            if k == 0 or ends[k - 1] <= at:
+                k = int(np.searchsorted(ends, at, side="right")) + 1        # none: the next episode alone
+            stop = n if k >= len(ends) else int(ends[k - 1])
+            piece = {c: np.asarray(data[c])[at:stop] for c in COLUMNS}
+            try:
+                accepted += self._archive.import_rows(piece, src)[0]
+            except MemoryError:
+                accepted += getattr(self._archive, "last_import", (0, 0))[0]
+                self.sync()
+                raise
+            self.sync()
+            at = stop
+        return accepted
 
     def clear(self) -> None:
         if self._archive is not None:

@@ -221,6 +221,23 @@ class Engine:
         out["terminated"] = out["terminated"].astype(bool); out["truncated"] = out["truncated"].astype(bool)
         return out
 
+    def store_fill(self, archive: "TrajArchive", episode_ids=None, first_env: int = 0, bound_method: int = 0, low=None, high=None) -> int:
+        """fsrl_store_fill: pour alive episodes of `archive` (episode_ids = None: all, in table order) into this engine's store, episode
+        j into sub-buffer (first_env + j) % buffer_num, as if every row went through push() with map_action_inverse(actions) under
+        (bound_method, low, high) -- one host-to-device copy of a job table and one launch.  Under tanh the action is clamped to
+        +-(1 - 2**-24) before the inverse (the reference returns +-inf at +-1).  -> the rows the push loop would have pushed."""
+        ids = None if episode_ids is None else np.ascontiguousarray(episode_ids, np.int32).reshape(-1)
+        n = 0 if ids is None else ids.size
+        if ids is not None and n == 0:
+            ids = np.zeros(1, np.int32)         # an empty list is a list: a non-null pointer with n = 0 (NULL means every episode)
+        Da = self.cfg.act_dim
+        lo = None if low is None else np.ascontiguousarray(np.broadcast_to(np.asarray(low, np.float32), (Da,)))
+        hi = None if low is None else np.ascontiguousarray(np.broadcast_to(np.asarray(high, np.float32), (Da,)))
+        rows = C.c_int64()
+        _lib.check(self.lib.fsrl_store_fill(self._ctx, archive._t, _ptr(ids, _i32p), n, int(first_env),
+                                            int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p), C.byref(rows)))
+        return int(rows.value)
+
     def store_configure(self, total_size: int, buffer_num: int):
         """VectorReplayBuffer(total_size, buffer_num): re-cut the allocated store (empties it)."""
         _lib.check(self.lib.fsrl_store_configure(self._ctx, int(total_size), int(buffer_num)))
@@ -755,7 +772,7 @@ class Engine:
 
 TRAJ_COLUMNS = ("observations", "next_observations", "actions", "rewards", "costs", "terminals", "timeouts")
 TRAJ_COUNTERS = ("committed", "rejected_window", "dropped_long", "compactions", "rows", "refused_full", "episodes", "launches",
-                 "h2d_bytes", "abandoned")
+                 "h2d_bytes", "abandoned", "import_open", "fill_launches", "fill_copies")
 
 
 class TrajArchive:
@@ -838,6 +855,32 @@ class TrajArchive:
                 k, C.byref(n)))
         out["terminals"] = out["terminals"].astype(bool); out["timeouts"] = out["timeouts"].astype(bool)
         return out
+
+    def import_rows(self, data, source: int = 0):
+        """fsrl_traj_import: host columns in the export layout (a dict with the TRAJ_COLUMNS keys) -> (episodes accepted, rows
+        accepted).  Episodes end where terminals | timeouts is set; a trailing open run is dropped; every episode is committed as
+        a tapped one is (window, max_episode_len, room).  MemoryError when one found no room: the others are in."""
+        obs = np.ascontiguousarray(data["observations"], np.float32)
+        k = obs.shape[0]
+        obs = obs.reshape(k, -1)
+        nxt = np.ascontiguousarray(data["next_observations"], np.float32).reshape(k, -1)
+        act = np.ascontiguousarray(data["actions"], np.float32).reshape(k, -1)
+        assert k == 0 or (obs.shape[1] == self.obs_dim and nxt.shape[1] == self.obs_dim), \
+            f"obs_dim: the dataset has {obs.shape[1]}, the trajectory archive {self.obs_dim}"
+        assert k == 0 or act.shape[1] == self.act_dim, f"act_dim: the dataset has {act.shape[1]}, the trajectory archive {self.act_dim}"
+        rew = np.ascontiguousarray(data["rewards"], np.float64).reshape(-1)
+        cost = np.ascontiguousarray(data["costs"], np.float64).reshape(-1)
+        term = np.ascontiguousarray(np.asarray(data["terminals"]) != 0, np.uint8).reshape(-1)
+        tout = np.ascontiguousarray(np.asarray(data["timeouts"]) != 0, np.uint8).reshape(-1)
+        assert rew.size == k and cost.size == k and term.size == k and tout.size == k and len(nxt) == k and len(act) == k, \
+            "the dataset's columns differ in length"
+        ne, nr = C.c_int64(), C.c_int64()
+        self.last_import = (0, 0)
+        rc = self.lib.fsrl_traj_import(self._t, k, _ptr(obs, _f32p), _ptr(nxt, _f32p), _ptr(act, _f32p), _ptr(rew, _f64p),
+                                       _ptr(cost, _f64p), _ptr(term, _u8p), _ptr(tout, _u8p), int(source), C.byref(ne), C.byref(nr))
+        self.last_import = (int(ne.value), int(nr.value))      # also when the call reports an episode without room
+        _lib.check(rc)
+        return self.last_import
 
     def clear(self):
         _lib.check(self.lib.fsrl_traj_clear(self._t))

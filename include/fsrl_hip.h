@@ -824,7 +824,8 @@ int fsrl_comm_destroy(fsrl_ctx* ctx);
 
 /* ---- the trajectory archive (fsrl/data/traj_buf.py TrajectoryBuffer, fed as basic_collector.py:238-248 feeds it): every finished
  *      episode of the contexts that feed it, kept in HBM in the DSRL column layout -- observations / next_observations [rows][obs_dim]
- *      and actions [rows][act_dim] float32, rewards / costs float64, terminals / timeouts uint8 -- until fsrl_traj_export.
+ *      and actions [rows][act_dim] float32, rewards / costs float64, terminals / timeouts uint8 -- until fsrl_traj_export
+ *      hands them to the host or fsrl_store_fill to a replay store; fsrl_traj_import reads exported columns back.
  *      A context that feeds an archive has a TAP on its store ingest: every row that goes through fsrl_store_push (so every collect
  *      call, solo, grouped or over worker-process envs) also reaches the archive, whatever the store's geometry does meanwhile
  *      (fsrl_store_reset, fsrl_store_configure, a sub-buffer that wraps).  The rows of an env are gathered in an open-episode area;
@@ -862,7 +863,42 @@ int fsrl_comm_destroy(fsrl_ctx* ctx);
  *      fsrl_traj_clear    drops every archived episode; open episodes go on.
  *      fsrl_traj_counters out[0..n): episodes committed, rejected by the window, dropped as longer than max_episode_len, compactions,
  *                         rows alive, episodes refused for lack of room, episodes alive, tap launches, tap host-to-device bytes, open
- *                         episodes abandoned.  */
+ *                         episodes abandoned, open trailing runs dropped by fsrl_traj_import, fsrl_store_fill launches,
+ *                         fsrl_store_fill host-to-device copies.
+ *
+ *      Datasets in: the two calls that make the archive readable as well as writable.
+ *      fsrl_traj_import   `rows` rows of host columns in the export layout (what fsrl_traj_export writes; cost, terminals or timeouts
+ *                         may be NULL = all zero, not both flag columns).  An episode ends at every row where terminals | timeouts is
+ *                         set; a trailing run without an end flag is an open episode, dropped and counted.  An imported episode is
+ *                         committed exactly as a tapped one: float64 reward and cost returns summed on the host in row order, held
+ *                         against the window and max_episode_len, id = the next commit serial number, `source` the caller's number;
+ *                         the archive compacts when it lacks room, and when it still lacks room the call returns FSRL_ENOMEM, the
+ *                         message naming max_rows -- that episode is dropped and counted, the ones accepted before (and after) it
+ *                         stay.  Only accepted rows cross the bus: neighbouring accepted episodes go in one copy per column, on the
+ *                         archive's own stream, and the call waits for them.  *episodes_out / *rows_out (may be NULL): accepted.
+ *      fsrl_store_fill    pours alive episodes of the archive into ctx's store, in the order given (episode_ids == NULL: all of them,
+ *                         in table order; n is then ignored).  Defined by a model: with e_j = (first_env + j) % buffer_num for the
+ *                         j-th episode, the result is what this loop leaves -- for every j in order, for every row of episode j in
+ *                         order, fsrl_store_push(ctx, &e_j, 1, obs, inv(act), rew, cost, terminal, timeout, next_obs, ...) -- in the
+ *                         six store columns, the host flag mirror, every field of the sub-buffers' bookkeeping (index, size,
+ *                         last_index, ep_rew, ep_len, ep_idx) and a bumped store version (device books, a prefetched sample and the
+ *                         side -> compute stream join refresh as after a push).  Two intended differences: the rows are not tapped
+ *                         (filling from an archive ctx itself feeds adds nothing to it), and the whole fill is ONE host-to-device
+ *                         copy of a job table plus ONE launch on ctx's side stream.  A sub-buffer may wrap during a fill: where the
+ *                         loop would write a slot more than once only the last write is planned, the launch writes every slot at most
+ *                         once.  Rows in ctx's staging window land first; the archive is flushed first (fsrl_traj_flush).
+ *                         inv is BasePolicy.map_action_inverse (base_policy.py:258-283) under the parameters of THIS call: with
+ *                         act_low / act_high (NULL = no scaling) scale = high - low, + float32 eps where below eps, then
+ *                         a = (a - low) * 2 / scale - 1 in float32, every operation rounded on its own, in that order; with
+ *                         bound_method 2 (tanh) then a = (log(1 + a) - log(1 - a)) / 2.  One deliberate departure from the reference:
+ *                         a is clamped to +-(1 - 2^-24) before the tanh inverse -- at +-1 the reference returns +-inf, which no update
+ *                         survives, and a recorded, saturated tanh action is exactly +-1.  (The two logarithms are taken in float64 and
+ *                         the result rounded once.)  0 none and 1 clip add nothing after the rescale.
+ *                         Refused before the first write, the message naming the field: obs_dim / act_dim / device of ctx and the
+ *                         archive differ, first_env outside [0, buffer_num), bound_method outside {0, 1, 2}, an episode id that is
+ *                         unknown, dead or listed twice (episode_ids[i]) -- FSRL_EINVAL; ctx inside an update, or a target sub-buffer
+ *                         with an episode in progress (ep_len != 0: fills go between collects) -- FSRL_ESTATE.
+ *                         *rows_out (may be NULL): the rows the loop would have pushed.  */
 typedef struct fsrl_traj fsrl_traj;
 int fsrl_traj_create(fsrl_ctx* ctx, int64_t max_rows, int32_t max_episodes, int32_t max_episode_len, int32_t bound_method,
                      const float* act_low, const float* act_high, fsrl_traj** out);
@@ -880,6 +916,11 @@ int fsrl_traj_export(fsrl_traj* t, float* obs, float* next_obs, float* act, doub
                      uint8_t* timeouts, int64_t rows_cap, int64_t* rows_out);
 int fsrl_traj_clear(fsrl_traj* t);
 int fsrl_traj_counters(fsrl_traj* t, int64_t* out, int32_t n);
+int fsrl_traj_import(fsrl_traj* t, int64_t rows, const float* obs, const float* next_obs, const float* act,
+                     const double* rew, const double* cost, const uint8_t* terminals, const uint8_t* timeouts,
+                     int32_t source, int64_t* episodes_out, int64_t* rows_out);
+int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int64_t n, int32_t first_env,
+                    int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out);
 
 #ifdef __cplusplus
 }

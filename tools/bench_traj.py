@@ -4,6 +4,7 @@
     python tools/bench_traj.py [--repeats 3] [--collects 12] [--out profiles/traj_tap.json]
     python tools/bench_traj.py --untapped-only [--tree DIR]      # the untapped leg alone; DIR: another checkout's package (A/B
                                                                   # against a parent commit, whose library has no fsrl_traj_*)
+    python tools/bench_traj.py --fill [--out profiles/traj_fill.json]   # the fill leg alone
 
 collect: the native collect of bench.py's end-to-end leg -- 20 envs in 4 worker processes, 300-step episodes, actor on the device,
 one library call per collect(n_episode = 20) -- of ONE agent over ONE set of env workers, alternated collect by collect between
@@ -13,7 +14,13 @@ and host-to-device bytes per collect, the launch floor fsrl_launch_floors measur
 overhead that launches x floor explains (the extra bytes are a few KB per flush: 4 + 4 act_dim per row).
 
 export: `rows` rows (100 k and 1 M) pushed through a tapped engine; fsrl_traj_export of all of them against fsrl_store_read of the
-same rows in chunks of 65 536 slots."""
+same rows in chunks of 65 536 slots.
+
+fill: a 1 M-row archive (4000 episodes of 250 rows, obs 33 / act 8) poured into a 1 M-row replay store of 20 sub-buffers by ONE
+fsrl_store_fill, against the same rows exported to the host and pushed through Engine.push 20 rows per call (actions inverted in
+numpy), against fsrl_train_state_import of a store of that size; alternated, medians of three, wall clock around call + sync.  The
+fill's bytes/s count what the kernel reads plus what it writes (about 314 + 313 bytes per row), over that wall clock -- job planning,
+the table's copy and the launch included."""
 import argparse
 import json
 import os
@@ -124,6 +131,73 @@ def bench_export(rows, envs=64, ep_len=125):
     return out
 
 
+def bench_fill(rows=1_000_000, envs=20, ep_len=250, Do=33, Da=8):
+    from fsrl_amd import _lib
+    from fsrl_amd.data.traj_buf import inverse_action
+    from fsrl_amd.engine import Engine, EngineConfig, TrajArchive
+    n_eps = rows // ep_len // envs * envs
+    n = n_eps * ep_len
+
+    def engine():
+        eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=Do, act_dim=Da, hidden_sizes=(64, 64), n_critics=2, env_num=envs,
+                                  buffer_size=n, target_kl=None))
+        eng.sac_init()
+        return eng
+
+    a, b = engine(), engine()
+    rng = np.random.default_rng(0)
+    low, high = np.full(Da, -2.0, np.float32), np.full(Da, 3.0, np.float32)
+    term = np.zeros(n, bool); term[ep_len - 1::ep_len] = True
+    data = dict(observations=rng.standard_normal((n, Do), np.float32), next_observations=rng.standard_normal((n, Do), np.float32),
+                actions=rng.uniform(-2.0, 3.0, (n, Da)).astype(np.float32), rewards=rng.standard_normal(n), costs=np.zeros(n),
+                terminals=term, timeouts=np.zeros(n, bool))
+    arch = TrajArchive(a, n, n_eps + 1, ep_len, 1, low, high)
+    t0 = time.perf_counter()
+    assert arch.import_rows(data) == (n_eps, n)
+    t_import = time.perf_counter() - t0
+    del data
+    # lock-step order of the push loop: vector step t of the 20 episodes of block k, one per sub-buffer
+    step = (np.arange(envs) * ep_len)[None, :] + np.arange(ep_len)[:, None]                       # [ep_len, envs]
+    ids = np.arange(envs)
+    t_fill, t_push, t_state = [], [], []
+    blob = None
+    for _ in range(3):
+        a.reset_store(); a.sync()
+        t0 = time.perf_counter()
+        assert a.store_fill(arch, None, 0, 1, low, high) == n
+        a.sync()
+        t_fill.append(time.perf_counter() - t0)
+        b.reset_store(); b.sync()
+        t0 = time.perf_counter()
+        d = arch.export()
+        act = inverse_action(d["actions"], 1, low, high)
+        for k in range(n_eps // envs):
+            base = k * envs * ep_len
+            for t in range(ep_len):
+                r = step[t] + base
+                b.push(ids, d["observations"][r], act[r], d["rewards"][r], d["costs"][r], d["terminals"][r], d["timeouts"][r],
+                       d["next_observations"][r])
+        b.sync()
+        t_push.append(time.perf_counter() - t0)
+        del d, act
+        if blob is None:
+            blob = a.train_state_array(with_store=True)
+        t0 = time.perf_counter()
+        b.load_train_state(blob)
+        b.sync()
+        t_state.append(time.perf_counter() - t0)
+    moved = n * (2 * (2 * Do * 4 + Da * 4 + 16) + 3)
+    fill = float(np.median(t_fill))
+    out = {"rows": n, "episodes": n_eps, "obs_dim": Do, "act_dim": Da, "sub_buffers": envs, "import_ms": 1e3 * t_import,
+           "store_fill_ms": [1e3 * x for x in t_fill], "export_and_push_20_rows_per_call_ms": [1e3 * x for x in t_push],
+           "train_state_import_ms": [1e3 * x for x in t_state], "train_state_bytes": int(blob.size),
+           "store_fill_median_ms": 1e3 * fill, "export_and_push_median_ms": 1e3 * float(np.median(t_push)),
+           "train_state_import_median_ms": 1e3 * float(np.median(t_state)), "fill_bytes_read_plus_written": int(moved),
+           "fill_bytes_per_s": moved / fill, "fill_launches": arch.counters()["fill_launches"], "fill_copies": arch.counters()["fill_copies"]}
+    arch.close(); a.close(); b.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
@@ -131,9 +205,17 @@ def main():
     ap.add_argument("--untapped-only", action="store_true")
     ap.add_argument("--tree", default=ROOT, help="checkout whose fsrl_amd package (and library) is measured")
     ap.add_argument("--no-export", action="store_true")
+    ap.add_argument("--fill", action="store_true", help="the fsrl_store_fill leg alone (profiles/traj_fill.json)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
+    if a.fill:
+        res = {"fill": bench_fill()}
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = {"tree": os.path.relpath(os.path.abspath(a.tree), ROOT), "collect": bench_collect(a)}
     if not a.untapped_only and not a.no_export:
         res["export"] = [bench_export(100_000), bench_export(1_000_000)]
