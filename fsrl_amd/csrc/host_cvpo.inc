@@ -21,25 +21,14 @@ extern "C" int fsrl_cvpo_init(fsrl_ctx* c, const fsrl_cvpo_config* cfg) {
     s->n_q = cfg->double_critic ? 4 : 2;
     s->cfg.actor_lr = cfg->actor_lr; s->cfg.critic_lr = cfg->critic_lr; s->cfg.tau = cfg->tau; s->cfg.n_step = cfg->n_step;
     s->cfg.auto_alpha = 0; s->cfg.alpha = 0.0f; s->cfg.use_lagrangian = 0;      // no entropy term, no PID multiplier
-    sac_layout(c, s);
-    const size_t HH = (size_t)c->cfg.hidden * c->cfg.hidden;
-    const size_t ab = ((size_t)s->na_dev + HH) * 4, qb = ((size_t)s->nq_dev + 4 * HH) * 4;
-    for (float** p : {&s->PA, &s->MA, &s->VA, &s->PAT}) { HIPCHK(hipMalloc(p, ab)); HIPCHK(hipMemsetAsync(*p, 0, ab, c->compute)); }
-    for (float** p : {&s->PQ, &s->PQT, &s->MQ, &s->VQ}) { HIPCHK(hipMalloc(p, qb)); HIPCHK(hipMemsetAsync(*p, 0, qb, c->compute)); }
-    if (s->layered) {           // parameter-layout gradient vectors of the layered weight-side launches
-        HIPCHK(hipMalloc(&s->GA, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(s->GA, 0, (size_t)s->na_dev * 4, c->compute));
-        HIPCHK(hipMalloc(&s->GQ, (size_t)s->nq_dev * 4)); HIPCHK(hipMemsetAsync(s->GQ, 0, (size_t)s->nq_dev * 4, c->compute));
-    }
-    HIPCHK(hipMalloc(&s->sc, sizeof(SacScalars)));
+    const int rc = sac_alloc_state(c, s);
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(s->sc, 0, sizeof(SacScalars), c->compute));
     HIPCHK(hipMalloc(&s->csc, sizeof(CvpoScalars)));
     HIPCHK(hipMemsetAsync(s->csc, 0, sizeof(CvpoScalars), c->compute));
     HIPCHK(hipStreamSynchronize(c->compute));
     const float eta0 = 1.0f;                                                     // estep_dual = [1, 0]  (cvpo.py:150-152)
     HIPCHK(hipMemcpy(&s->csc->eta, &eta0, 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&s->d_stats, (size_t)SAC_RING * s->nstats * 4));
-    HIPCHK(hipMalloc(&s->d_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
-    HIPCHK(hipHostMalloc(&s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
     return 0;
 }
 
@@ -59,8 +48,7 @@ extern "C" int fsrl_cvpo_post_update(fsrl_ctx* c) {
     SacState* s = cvpo_of(c);
     if (!s) return fail(FSRL_ESTATE, "fsrl_cvpo_init first");
     ENTER_DEV(c);
-    HIPCHK(hipMemcpyAsync(s->PAT, s->PA, ((size_t)s->na_dev + (size_t)c->cfg.hidden * c->cfg.hidden) * 4,
-                          hipMemcpyDeviceToDevice, c->compute));
+    HIPCHK(hipMemcpyAsync(s->PAT, s->PA, sac_actor_bytes(c, s), hipMemcpyDeviceToDevice, c->compute));
     return 0;
 }
 
@@ -118,6 +106,15 @@ static CvpoActorArgs cvpo_actor_args(const fsrl_ctx* c, const SacState* s, int B
     aa.B = B; aa.K = s->ccfg.sample_act_num; aa.mode = mode; aa.max_action = c->cfg.max_action; aa.mean_tanh = s->mean_tanh;
     return aa;
 }
+// the head of a layered actor pass (lay_cvpo_actor_head_kernel behind lay_fwd_k); the M-step's modes take no noise and write no X
+static LayCvpoActorArgs lay_cvpo_actor_head_args(const fsrl_ctx* c, const SacState* s, int B, int mode, const float* obs,
+                                                 const float* eps, float* X) {
+    LayCvpoActorArgs h{};
+    h.out = s->ka.out; h.dout = s->ka.dout; h.obs = obs; h.eps = eps; h.X = X; h.mu_old = s->MU_OLD; h.std_old = s->STD_OLD;
+    h.W = s->Wk; h.XK = s->XK; h.sc = s->csc; h.statp = s->stpi; h.B = B; h.K = s->ccfg.sample_act_num; h.Do = c->cfg.obs_dim;
+    h.Da = c->cfg.act_dim; h.mode = mode; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
+    return h;
+}
 static SacNstepArgs cvpo_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
     SacNstepArgs na = sac_nstep_args(c, s, B);       // n_step: fsrl_cvpo_init copies it into s->cfg
     na.auto_alpha = 0; na.alpha_fixed = 0.0f; na.single = s->n_q == 2 ? 1 : 0;    // LPN stays zero: no entropy term
@@ -146,6 +143,27 @@ static CvpoFinalArgs cvpo_final_args(const fsrl_ctx* c, const SacState* s, int B
     return fa;
 }
 
+// the layered actor pass of a CVPO context, layer by layer: the forward and the actor head of the mode; with_particles: then, as the
+// fused launch's second batch, actor_old on (OBS, eps_k) and the PARTICLES head; CVPO_A_MBWD: also the activation side of the
+// backward pass
+static int lay_cvpo_actor_pass(fsrl_ctx* c, SacState* s, int B, int mode, const float* PAx, const float* obs, const float* eps,
+                               float* X, bool with_particles) {
+    auto one = [&](int md_, const float* Pn, const float* obs_, const float* eps_, float* X_) -> int {
+        int rc = lay_fwd_k(c, s->ka, Pn, obs_, B);
+        if (rc) return rc;
+        const LayCvpoActorArgs h = lay_cvpo_actor_head_args(c, s, B, md_, obs_, eps_, X_);
+        hipLaunchKernelGGL(lay_cvpo_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, c->compute, h);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    int rc = one(mode, PAx, obs, eps, X);
+    if (rc) return rc;
+    if (with_particles) { rc = one(CVPO_A_PARTICLES, s->PAT, s->OBS, s->eps_k, s->XK); if (rc) return rc; }
+    return mode == CVPO_A_MBWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
+}
+
+// The frame of the update is host_sac.inc's (replay_join .. replay_finish); CVPO's own: its sample launch, the TARGET + PARTICLES
+// actor launch, and behind the critic half the E-step and the M-step loop.
 extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, const float* eps_target,
                                 const float* eps_particles, uint64_t seed, float* stats_out) {
     CHECK_ARG(c, "null ctx");
@@ -156,23 +174,17 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     CHECK_ARG(stored > 0, "empty replay store");
     CHECK_ARG((indices != nullptr) == (eps_target != nullptr) && (indices != nullptr) == (eps_particles != nullptr),
               "indices, eps_target and eps_particles are given together (caller RNG) or all NULL (library RNG)");
-    ENTER_DEV(c);
-    int rc = join_store(c);
-    if (rc) return rc;
-    rc = sac_alloc_batch(c, s, B);
+    int rc = replay_join(c, s, B);
     if (rc) return rc;
     hipStream_t st = c->compute;
     const fsrl_cvpo_config& cc = s->ccfg;
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, K = cc.sample_act_num;
-    const size_t nk = (size_t)K * B * Da;
-    if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
+    replay_seed_key(s, seed);          // SAC's hash (host_sac.inc): if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
     bool fused_sg = false;
     const SacGatherArgs ga = sac_gather_args(c, s, B, cc.n_step);
     if (indices) {
-        rc = sac_stage_indices(c, s, B, indices, eps_target);
+        rc = sac_stage_indices(c, s, B, indices, eps_target, eps_particles, (size_t)K * B * Da, s->h_epsk, s->eps_k);
         if (rc) return rc;
-        memcpy(s->h_epsk, eps_particles, nk * 4);
-        HIPCHK(hipMemcpyAsync(s->eps_k, s->h_epsk, nk * 4, hipMemcpyHostToDevice, st));
     } else {
         rc = sac_upload_book(c, s);
         if (rc) return rc;
@@ -192,23 +204,7 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     }
     // with_particles: the launch's second batch is CVPO_A_PARTICLES (actor_old on OBS / eps_k -> MU_OLD, STD_OLD, XK)
     auto actor_launch = [&](int mode, const float* PAx, const float* obs, const float* eps, float* X, bool with_particles = false) {
-        if (s->layered) {       // layer by layer: forward, the CVPO actor head of the mode; MBWD also the activation side of the backward pass
-            auto one = [&](int md_, const float* Pn, const float* obs_, const float* eps_, float* X_) -> int {
-                int rc2 = lay_fwd_k(c, s->ka, Pn, obs_, B);
-                if (rc2) return rc2;
-                LayCvpoActorArgs h{};
-                h.out = s->ka.out; h.dout = s->ka.dout; h.obs = obs_; h.eps = eps_; h.X = X_; h.mu_old = s->MU_OLD; h.std_old = s->STD_OLD;
-                h.W = s->Wk; h.XK = s->XK; h.sc = s->csc; h.statp = s->stpi; h.B = B; h.K = K; h.Do = Do; h.Da = Da; h.mode = md_;
-                h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
-                hipLaunchKernelGGL(lay_cvpo_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, st, h);
-                HIPCHK(hipGetLastError());
-                return 0;
-            };
-            int rc2 = one(mode, PAx, obs, eps, X);
-            if (rc2) return rc2;
-            if (with_particles) { rc2 = one(CVPO_A_PARTICLES, s->PAT, s->OBS, s->eps_k, s->XK); if (rc2) return rc2; }
-            return mode == CVPO_A_MBWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
-        }
+        if (s->layered) return lay_cvpo_actor_pass(c, s, B, mode, PAx, obs, eps, X, with_particles);
         const bool r4 = s->a_rows4 && (!with_particles || 8 * s->n_tiles <= c->n_cus);
         const int tiles = r4 ? 4 * s->n_tiles : s->n_tiles;
         const int grid = with_particles ? 2 * tiles : tiles;
@@ -225,25 +221,10 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
     //      and, in the same launch, the K particles of actor_old at s_t for the E-step (they do not depend on the critic step)
     rc = actor_launch(CVPO_A_TARGET, s->PA, s->OBSN, s->eps_t, s->XN, true);
     if (rc) return rc;
-    rc = sac_q_launch(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B);
-    if (rc) return rc;
-    const SacNstepArgs na = cvpo_nstep_args(c, s, B);
-    // r6: the critics' tile launch computes its float64 targets itself (as SAC's does since r4) and leaves them in Y for the logged
-    // row; layered contexts and fsrl_sac_set_plan bit 2 keep the stand-alone launch
-    const bool ns_fold = !s->layered && !s->plan_nstep_sep;
-    if (!ns_fold) {
-        hipLaunchKernelGGL(sac_nstep_kernel, dim3((B + 255) / 256), dim3(256), 0, st, na);
-        HIPCHK(hipGetLastError());
-    }
-    // ---- critic step                                                                (cvpo.py:248-276)
-    rc = sac_q_launch(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, -1, -1, ns_fold ? &na : nullptr);
-    if (rc) return rc;
+    // ---- critics_old.predict, the float64 return, the critic step                     (cvpo.py:206-222, 248-276)
     int nsplit = 1;
-    rc = sac_wgrad(c, s, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &nsplit);
+    rc = replay_critic_half(c, s, B, cvpo_nstep_args(c, s, B), cc.critic_lr, cc.tau, &nsplit);
     if (rc) return rc;
-    s->t_critic += 1;
-    // sync_weight (cvpo.py:202-204) rides on the same pass: the critics do not change again within the update
-    adam_launch(c, s->mdq, s->PQ, s->MQ, s->VQ, c->wg_parts, s->nq_dev, cc.critic_lr, s->t_critic, nsplit, s->nq_dev, s->PQT, cc.tau);
     // ---- E-step: K particles of actor_old through the UPDATED critics                (cvpo.py:319-371)
     rc = sac_q_launch(c, s, s->PQ, s->XK, FB_MODE_Q_FWD, 0.f, 0.f, s->stqk, K * B, s->QK, s->n_tiles_k, s->k_rows4 ? 1 : 0);
     if (rc) return rc;
@@ -267,18 +248,12 @@ extern "C" int fsrl_cvpo_update(fsrl_ctx* c, int32_t B, const int64_t* indices, 
             adam_launch(c, s->mda, s->PA, s->MA, s->VA, c->wg_parts, s->na_dev, cc.actor_lr, s->t_actor, nsplit, s->na_dev);
     }
     // ---- the last actor Adam carries the logged-row block                             (cvpo.py:422-430)
-    float* stats_row = s->d_stats + (size_t)(s->n_updates % SAC_RING) * s->nstats;
+    float* stats_row = replay_stats_row(s);
     const CvpoFinalArgs fa = cvpo_final_args(c, s, B, s->q_rows4 ? 4 * s->n_tiles : s->n_tiles, stats_row);
     adam_final_launch<CvpoFinalArgs, cvpo_finalize_row>(c, s->mda, s->PA, s->MA, s->VA, c->wg_parts, s->na_dev, cc.actor_lr,
                                                         s->t_actor, nsplit, s->na_dev, nullptr, 0.0f, fa);
     HIPCHK(hipGetLastError());
-    s->n_updates += 1;
-    if (stats_out) {
-        HIPCHK(hipMemcpyAsync(stats_out, stats_row, (size_t)s->nstats * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        s->n_drained = s->n_updates;
-    }
-    return 0;
+    return replay_finish(c, s, stats_row, stats_out, (size_t)s->nstats);
 }
 
 // Rows of logged statistics of the updates issued with stats_out == NULL since the last drain

@@ -109,46 +109,21 @@ extern "C" int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_grou
 struct CvpoGroupTiles { bool q_r4, a_r4, f_r4, k_r4; };
 static int cvpo_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, CvpoGroupMember& v, int B, const CvpoGroupTiles& th,
                              bool small_wgrad, int* nsplit_q, int* nsplit_a) {
-    const int nt = s->n_tiles, rp = nt * 16, K = s->ccfg.sample_act_num;
-    t = SacGroupMember{};
+    const int nt = s->n_tiles, K = s->ccfg.sample_act_num;
+    const int rc = group_member_base(c, s, t, B, cvpo_nstep_args(c, s, B), s->ccfg.tau, small_wgrad, nsplit_q, nsplit_a);
+    if (rc) return rc;
     v = CvpoGroupMember{};
-    t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
-    v.PA = s->PA; v.MA = s->MA; v.VA = s->VA;
+    v.PA = s->PA; v.MA = s->MA; v.VA = s->VA; v.GA = t.GA;
+    member_adam_consts(v, c);
     v.ga = sac_gather_args(c, s, B, s->ccfg.n_step);
     v.at = cvpo_actor_args(c, s, B, CVPO_A_TARGET, s->OBSN, s->eps_t, s->XN, true, th.f_r4 ? 4 * nt : nt);
     v.am = cvpo_actor_args(c, s, B, CVPO_A_MFWD, s->OBS, nullptr, nullptr, false, 0);
     v.ab = cvpo_actor_args(c, s, B, CVPO_A_MBWD, s->OBS, nullptr, nullptr, false, 0);
-    const SacNstepArgs na = cvpo_nstep_args(c, s, B);
-    t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, nt, nullptr);
-    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, nt, &na);
     t.qd = sac_q_args(c, s, s->PQ, s->XK, FB_MODE_Q_FWD, 0.f, 0.f, s->stqk, K * B, s->QK, s->n_tiles_k, nullptr);   // the K * B particles
     v.es = cvpo_estep_args(c, s, B);
     v.md = cvpo_mdual_args(c, s, B, th.a_r4 ? 4 * nt : nt, 0);
     v.fin = cvpo_final_args(c, s, B, th.q_r4 ? 4 * nt : nt, nullptr);
     v.stats = s->d_stats; v.nstats = s->nstats;
-    // ---- weight gradients: sac_wgrad's plan for this member alone
-    if (small_wgrad) {
-        int rc = ensure_parts(c, s->nq_dev, 1);
-        if (rc) return rc;
-        t.GQ = c->wg_parts;
-        rc = ensure_parts(c, s->na_dev, 1);
-        if (rc) return rc;
-        t.GA = c->wg_parts;
-        if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
-        t.wq = group_wgrad_small(s, rp, s->XQ, const_cast<float*>(t.GQ));
-        t.wa = group_wgrad_small(s, rp, s->OBS, const_cast<float*>(t.GA));
-        *nsplit_q = *nsplit_a = 1;
-    } else {
-        int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
-        if (rc) return rc;
-        rc = group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
-        if (rc) return rc;
-    }
-    v.GA = t.GA;
-    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-    t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
-    t.tau = s->ccfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->ccfg.tau);
-    v.one_minus_b1 = t.one_minus_b1; v.beta2 = t.beta2; v.one_minus_b2 = t.one_minus_b2; v.adam_eps = t.adam_eps;
     return 0;
 }
 
@@ -176,12 +151,7 @@ extern "C" int fsrl_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32
     SacState* s0 = sac_of(c0);
     if (s0->layered) return lay_cvpo_group_update(g, B, n_updates);
     ReplayGroupCall call;
-    rc = rgroup_begin(gc, true, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState*) {
-        // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
-        CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
-                  "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
-        return 0;
-    });
+    rc = rgroup_begin(gc, true, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState*) { return rgroup_no_stream_wgrad(i, c, B); });
     if (rc) return rc;
     const int n_max = call.n_max;
     if (n_max == 0) return 0;

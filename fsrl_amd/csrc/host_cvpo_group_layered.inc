@@ -41,7 +41,7 @@ static int lay_cvpo_group_tables(fsrl_cvpo_group* g, LayCvpoGroup& lg, int B, co
     const int k = (int)gc.m.size();
     fsrl_ctx* c0 = gc.m[0];
     const SacState* s0 = sac_of(c0);
-    const int n_q = s0->n_q, Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim, K = s0->ccfg.sample_act_num;
+    const int K = s0->ccfg.sample_act_num;
     const int tiles = (B + 15) / 16, tiles_k = (K * B + 15) / 16;
     int rc = table_ensure(lg.ah, (size_t)LCG_NHEADS * k, (size_t)LCG_NHEADS * k);
     if (!rc) rc = table_ensure(lg.qh, (size_t)LCG_NQHEADS * k, (size_t)LCG_NQHEADS * k);
@@ -88,23 +88,16 @@ static int lay_cvpo_group_tables(fsrl_cvpo_group* g, LayCvpoGroup& lg, int B, co
         if (!work[i]) continue;
         fsrl_ctx* c = gc.m[i];
         const SacState* s = sac_of(c);
-        for (int w = 0; w < LCG_NHEADS; ++w) {       // fsrl_cvpo_update's actor_launch, layered branch
-            LayCvpoActorArgs& h = lg.ah.h[(size_t)w * k + i];
-            h.out = s->ka.out; h.dout = s->ka.dout; h.mu_old = s->MU_OLD; h.std_old = s->STD_OLD;
-            h.W = s->Wk; h.XK = s->XK; h.sc = s->csc; h.statp = s->stpi; h.B = B; h.K = K; h.Do = Do; h.Da = Da;
-            h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
-            if (w == LCG_TARGET) { h.obs = s->OBSN; h.eps = s->eps_t; h.X = s->XN; h.mode = CVPO_A_TARGET; }
-            else if (w == LCG_PARTICLES) { h.obs = s->OBS; h.eps = s->eps_k; h.X = s->XK; h.mode = CVPO_A_PARTICLES; }
-            else { h.obs = s->OBS; h.eps = nullptr; h.X = nullptr; h.mode = w == LCG_MFWD ? CVPO_A_MFWD : CVPO_A_MBWD; }
-        }
-        for (int w = 0; w < LCG_NQHEADS; ++w) {      // sac_q_launch, layered branch
-            LaySacQArgs& q = lg.qh.h[(size_t)w * k + i];
-            q.out = s->kq.out; q.dout = s->kq.dout; q.tgt = s->Y; q.mbp = s->kq.mbp; q.n_q = n_q; q.pair_shift = n_q == 2 ? 0 : 1;
-            q.mode = w == LCG_Q_TRAIN ? FB_MODE_Q_TRAIN : FB_MODE_Q_FWD;
-            if (w == LCG_Q_TARGET) { q.qout = s->QT; q.statp = s->stq; q.B = B; }
-            else if (w == LCG_Q_TRAIN) { q.qout = s->QP; q.statp = s->stq; q.B = B; }
-            else { q.qout = s->QK; q.statp = s->stqk; q.B = K * B; }
-        }
+        // the heads of fsrl_cvpo_update's actor passes (lay_cvpo_actor_pass) and Q-network passes (sac_q_launch), as it forms them
+        auto ah = [&](int w) -> LayCvpoActorArgs& { return lg.ah.h[(size_t)w * k + i]; };
+        ah(LCG_TARGET) = lay_cvpo_actor_head_args(c, s, B, CVPO_A_TARGET, s->OBSN, s->eps_t, s->XN);
+        ah(LCG_PARTICLES) = lay_cvpo_actor_head_args(c, s, B, CVPO_A_PARTICLES, s->OBS, s->eps_k, s->XK);
+        ah(LCG_MFWD) = lay_cvpo_actor_head_args(c, s, B, CVPO_A_MFWD, s->OBS, nullptr, nullptr);
+        ah(LCG_MBWD) = lay_cvpo_actor_head_args(c, s, B, CVPO_A_MBWD, s->OBS, nullptr, nullptr);
+        auto qh = [&](int w) -> LaySacQArgs& { return lg.qh.h[(size_t)w * k + i]; };
+        qh(LCG_Q_TARGET) = lay_sac_q_head_args(c, s, FB_MODE_Q_FWD, s->stq, B, nullptr, s->PQT);
+        qh(LCG_Q_TRAIN) = lay_sac_q_head_args(c, s, FB_MODE_Q_TRAIN, s->stq, B, nullptr, s->PQ);
+        qh(LCG_Q_PARTICLES) = lay_sac_q_head_args(c, s, FB_MODE_Q_FWD, s->stqk, K * B, s->QK, s->PQ);
         lg.na.h[i] = cvpo_nstep_args(c, s, B);
         t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
         t.GQ = s->GQ;                           // the weight-side launches leave the finished gradients there: one partial
@@ -114,10 +107,8 @@ static int lay_cvpo_group_tables(fsrl_cvpo_group* g, LayCvpoGroup& lg, int B, co
         v.md = cvpo_mdual_args(c, s, B, s->n_tiles, 0);
         v.fin = cvpo_final_args(c, s, B, s->n_tiles, nullptr);
         v.stats = s->d_stats; v.nstats = s->nstats;
-        const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-        t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
-        t.tau = s->ccfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->ccfg.tau);
-        v.one_minus_b1 = t.one_minus_b1; v.beta2 = t.beta2; v.one_minus_b2 = t.one_minus_b2; v.adam_eps = t.adam_eps;
+        member_adam_consts(t, c, s->ccfg.tau);
+        member_adam_consts(v, c);
     }
     rc = pg.upload(lg.jobs);
     if (rc) return rc;
@@ -153,33 +144,20 @@ static int lay_cvpo_group_update(fsrl_cvpo_group* g, int32_t B, const int32_t* n
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, n_steps * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
     HIPCHK(hipMemcpyAsync(g->iters.d, g->iters.h, n_iters * sizeof(CvpoGroupIter), hipMemcpyHostToDevice, gs));
-    const ModelDesc mda = s0->mda, mdq = s0->mdq;
-    const int na_dev = s0->na_dev, nq_dev = s0->nq_dev, n_q = s0->n_q;
+    const ModelDesc mda = s0->mda;
+    const int na_dev = s0->na_dev;
     const int sg_blocks = (B + SG_ROWS - 1) / SG_ROWS + (B * K + 255) / 256;
     const SacGroupMember* tab = g->tab.d;
     const CvpoGroupMember* ctab = g->ctab.d;
     // one launch of the program; it: the M iteration (0 in front of the M-step)
     auto launch = [&](const LaySacOp& op, const SacGroupStep* st, int u, int it) {
+        if (lay_replay_group_launch(op, gs, s0, B, k, lg.jobs.d, lg.qh.d, lg.na.d, tab, st)) return;
         switch (op.kind) {
-        case LSG_LIN:
-            if (op.form == LIN_F) lay_sac_group_launch<LIN_F>(op, gs, lg.jobs.d, st);
-            else if (op.form == LIN_X) lay_sac_group_launch<LIN_X>(op, gs, lg.jobs.d, st);
-            else lay_sac_group_launch<LIN_W>(op, gs, lg.jobs.d, st);
-            break;
         case LSG_CVPO_SAMPLE:
             hipLaunchKernelGGL(cvpo_sample_gather_group_kernel, dim3(sg_blocks, k), dim3(256), 0, gs, ctab, st);
             break;
-        case LSG_NSTEP:
-            hipLaunchKernelGGL(sac_nstep_group_kernel, dim3((B + 255) / 256, k), dim3(256), 0, gs, lg.na.d, st);
-            break;
         case LSG_CVPO_AHEAD:
             hipLaunchKernelGGL(lay_cvpo_actor_head_group_kernel, dim3(op.gx, k), dim3(256), 0, gs, lg.ah.d + (size_t)op.which * k, st);
-            break;
-        case LSG_QHEAD:
-            hipLaunchKernelGGL(lay_sac_q_head_group_kernel, dim3(op.gx, n_q, k), dim3(64), 0, gs, lg.qh.d + (size_t)op.which * k, st);
-            break;
-        case LSG_ADAM_Q:
-            hipLaunchKernelGGL(sac_adam_group_kernel, dim3((nq_dev + 255) / 256, k), dim3(256), 0, gs, mdq, tab, st, nq_dev, 1, nq_dev);
             break;
         case LSG_CVPO_ESTEP:
             hipLaunchKernelGGL(cvpo_estep_group_kernel, dim3(k), dim3(1024), 0, gs, ctab, st);

@@ -186,6 +186,29 @@ static void sac_layout(fsrl_ctx* c, SacState* s) {
     }
 }
 
+// bytes of the actor's / the Q-networks' parameter store with its W2 mirrors (used in P only; none in a layered context: hidden = 0)
+static size_t sac_actor_bytes(const fsrl_ctx* c, const SacState* s) { return ((size_t)s->na_dev + (size_t)c->cfg.hidden * c->cfg.hidden) * 4; }
+static size_t sac_critic_bytes(const fsrl_ctx* c, const SacState* s) { return ((size_t)s->nq_dev + 4 * (size_t)c->cfg.hidden * c->cfg.hidden) * 4; }
+
+// what fsrl_sac_init and fsrl_cvpo_init allocate alike once the kind (ddpg, n_q, nstats) is set: the layout, the parameter, target
+// and Adam stores (zeroed on the compute stream: the caller waits for it), a layered context's gradient vectors, the scalars, the
+// statistics ring and the sampler's books
+static int sac_alloc_state(fsrl_ctx* c, SacState* s) {
+    sac_layout(c, s);
+    const size_t ab = sac_actor_bytes(c, s), qb = sac_critic_bytes(c, s);
+    for (float** p : {&s->PA, &s->MA, &s->VA, &s->PAT}) { HIPCHK(hipMalloc(p, ab)); HIPCHK(hipMemsetAsync(*p, 0, ab, c->compute)); }
+    for (float** p : {&s->PQ, &s->PQT, &s->MQ, &s->VQ}) { HIPCHK(hipMalloc(p, qb)); HIPCHK(hipMemsetAsync(*p, 0, qb, c->compute)); }
+    if (s->layered) {           // parameter-layout gradient vectors of the layered weight-side launches
+        HIPCHK(hipMalloc(&s->GA, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(s->GA, 0, (size_t)s->na_dev * 4, c->compute));
+        HIPCHK(hipMalloc(&s->GQ, (size_t)s->nq_dev * 4)); HIPCHK(hipMemsetAsync(s->GQ, 0, (size_t)s->nq_dev * 4, c->compute));
+    }
+    HIPCHK(hipMalloc(&s->sc, sizeof(SacScalars)));
+    HIPCHK(hipMalloc(&s->d_stats, (size_t)SAC_RING * s->nstats * 4));
+    HIPCHK(hipMalloc(&s->d_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
+    HIPCHK(hipHostMalloc(&s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
+    return 0;
+}
+
 extern "C" int fsrl_sac_init(fsrl_ctx* c, const fsrl_sac_config* cfg) {
     CHECK_ARG(c && cfg, "null argument");
     CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG, "context was not created with FSRL_ALGO_SAC_LAG");
@@ -207,22 +230,11 @@ extern "C" int fsrl_sac_init(fsrl_ctx* c, const fsrl_sac_config* cfg) {
     s->mean_tanh = cfg->actor_mean == FSRL_ACTOR_MEAN_TANH ? 1 : 0;       // SAC-Lag's default: the unbounded mean
     s->n_q = s->ddpg ? 2 : 4;
     if (s->ddpg) { s->cfg.auto_alpha = 0; s->cfg.alpha = 0.0f; }      // no entropy term anywhere
-    sac_layout(c, s);
-    const size_t HH = (size_t)c->cfg.hidden * c->cfg.hidden;
-    const size_t ab = ((size_t)s->na_dev + HH) * 4, qb = ((size_t)s->nq_dev + 4 * HH) * 4;   // + W2 mirrors (used in P only)
-    for (float** p : {&s->PA, &s->MA, &s->VA, &s->PAT}) { HIPCHK(hipMalloc(p, ab)); HIPCHK(hipMemsetAsync(*p, 0, ab, c->compute)); }
-    for (float** p : {&s->PQ, &s->PQT, &s->MQ, &s->VQ}) { HIPCHK(hipMalloc(p, qb)); HIPCHK(hipMemsetAsync(*p, 0, qb, c->compute)); }
-    if (s->layered) {
-        HIPCHK(hipMalloc(&s->GA, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(s->GA, 0, (size_t)s->na_dev * 4, c->compute));
-        HIPCHK(hipMalloc(&s->GQ, (size_t)s->nq_dev * 4)); HIPCHK(hipMemsetAsync(s->GQ, 0, (size_t)s->nq_dev * 4, c->compute));
-    }
+    const int rc = sac_alloc_state(c, s);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->compute));
-    HIPCHK(hipMalloc(&s->sc, sizeof(SacScalars)));
     SacScalars init{cfg->auto_alpha ? 1.0f : cfg->alpha, 0.0f, 0.0f, 0.0f, 0, 0};
     HIPCHK(hipMemcpy(s->sc, &init, sizeof(init), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&s->d_stats, (size_t)SAC_RING * s->nstats * 4));
-    HIPCHK(hipMalloc(&s->d_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
-    HIPCHK(hipHostMalloc(&s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
     return 0;
 }
 
@@ -284,10 +296,8 @@ extern "C" int fsrl_sac_params_set(fsrl_ctx* c, const float* actor, int64_t na, 
     if (rc) return rc;
     rc = sac_copy(c, s->tmap_q, s->mdq, s->nq_dev, s->PQ, critics, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(s->PQT, s->PQ, ((size_t)s->nq_dev + 4 * (size_t)c->cfg.hidden * c->cfg.hidden) * 4,
-                     hipMemcpyDeviceToDevice));   // critics_old = deepcopy (with the W2 mirrors)
-    HIPCHK(hipMemcpy(s->PAT, s->PA, ((size_t)s->na_dev + (size_t)c->cfg.hidden * c->cfg.hidden) * 4,
-                     hipMemcpyDeviceToDevice));   // actor_old = deepcopy (DDPG-Lag)
+    HIPCHK(hipMemcpy(s->PQT, s->PQ, sac_critic_bytes(c, s), hipMemcpyDeviceToDevice));    // critics_old = deepcopy (with the W2 mirrors)
+    HIPCHK(hipMemcpy(s->PAT, s->PA, sac_actor_bytes(c, s), hipMemcpyDeviceToDevice));     // actor_old = deepcopy (DDPG-Lag)
     for (float* p : {s->MA, s->VA}) HIPCHK(hipMemsetAsync(p, 0, (size_t)s->na_dev * 4, c->compute));
     for (float* p : {s->MQ, s->VQ}) HIPCHK(hipMemsetAsync(p, 0, (size_t)s->nq_dev * 4, c->compute));
     HIPCHK(hipStreamSynchronize(c->compute));
@@ -338,7 +348,6 @@ static int sac_alloc_batch(fsrl_ctx* c, SacState* s, int B) {
     s->n_tiles = (B + 15) / 16;
     s->q_rows4 = !s->layered && 4 * s->n_tiles * s->n_q <= c->n_cus && !c->probe_tile16;
     s->a_rows4 = !s->layered && 4 * s->n_tiles <= c->n_cus && !c->probe_tile16;
-    if (s->layered) s->plan_nstep_sep = true;      // the layered Q head reads its n-step targets from the stand-alone launch
     if (s->cvpo) {
         s->n_tiles_k = (B * s->ccfg.sample_act_num + 15) / 16;
         s->k_rows4 = !s->layered && 4 * s->n_tiles_k * s->n_q <= c->n_cus && !c->probe_tile16;
@@ -449,6 +458,16 @@ static SacActorArgs sac_actor_args(const fsrl_ctx* c, const SacState* s, int B, 
     aa.probe = probe;
     return aa;
 }
+// the head of a layered actor pass (lay_sac_actor_head_kernel behind lay_fwd_k): sac_actor_args' selections
+static LaySacActorArgs lay_sac_actor_head_args(const fsrl_ctx* c, const SacState* s, int B, int mode, const float* eps, float* X,
+                                               float* lp, float resc, float lam) {
+    LaySacActorArgs h{};
+    h.out = s->ka.out; h.dout = s->ka.dout; h.eps = eps; h.X = X; h.lp = lp; h.DXQ = s->DXQ; h.QP = s->QP; h.sc = s->sc;
+    h.statp = s->stpi; h.B = B; h.Bq = s->kq.mbp; h.Do = c->cfg.obs_dim; h.Da = c->cfg.act_dim; h.mode = mode;
+    h.deterministic = s->ddpg ? 1 : 0; h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh;
+    h.cr = -resc; h.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f; h.rescale = resc; h.alpha_fixed = s->cfg.alpha;
+    return h;
+}
 static SacNstepArgs sac_nstep_args(const fsrl_ctx* c, const SacState* s, int B) {
     SacNstepArgs na{};
     na.QT = s->QT; na.lpn = s->LPN; na.chain = s->d_chain; na.endbits = s->d_end; na.rew = c->st.rew; na.cost = c->st.cost;
@@ -489,9 +508,11 @@ static int sac_upload_book(fsrl_ctx* c, SacState* s) {
     return 0;
 }
 
-// caller-provided sample (parity mode): the index chains on the host, staged through pinned memory with the target noise; the
-// caller stages its second noise block behind this
-static int sac_stage_indices(fsrl_ctx* c, SacState* s, int B, const int64_t* indices, const float* eps_target) {
+// caller-provided sample (parity mode): the index chains on the host, staged through pinned memory with the target noise; behind
+// them the update's second noise block, n2 floats through its pinned buffer h2 to d2 (SAC: the policy's, behind the target's in
+// h_eps, to eps_p; CVPO: the particles', through h_epsk to eps_k)
+static int sac_stage_indices(fsrl_ctx* c, SacState* s, int B, const int64_t* indices, const float* eps_target, const float* eps2,
+                             size_t n2, float* h2, float* d2) {
     hipStream_t st = c->compute;
     const int Da = c->cfg.act_dim, ns = s->cfg.n_step;
     HIPCHK(hipStreamSynchronize(st));      // pinned staging of the previous update has landed
@@ -511,20 +532,35 @@ static int sac_stage_indices(fsrl_ctx* c, SacState* s, int B, const int64_t* ind
     HIPCHK(hipMemcpyAsync(s->d_chain, s->h_chain, (size_t)B * ns * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(s->d_end, s->h_end, (size_t)B * ns, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(s->eps_t, s->h_eps, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
+    memcpy(h2, eps2, n2 * 4);
+    HIPCHK(hipMemcpyAsync(d2, h2, n2 * 4, hipMemcpyHostToDevice, st));
     return 0;
 }
 
+// where a Q-network launch leaves its values: the target networks' forward in QT, every other launch in QP, unless the caller names
+// the place (the K * B particle rows of CVPO's E-step: QK)
+static float* sac_q_out(const SacState* s, const float* params, int mode, float* qout_override) {
+    return qout_override ? qout_override : ((mode == FB_MODE_Q_FWD && params == s->PQT) ? s->QT : s->QP);
+}
 // the arguments of a Q-network tile launch of n_tiles 16-row groups (sac_q_launch; the grouped updates)
 static FbArgs sac_q_args(const fsrl_ctx* c, const SacState* s, const float* params, const float* X, int mode, float cr, float cc,
                          float* statp, int B, float* qout_override, int n_tiles, const SacNstepArgs* ns) {
     FbArgs a{};
     a.obs = X; a.rd = nullptr; a.A1 = s->A1; a.A2 = s->A2; a.D1 = s->D1; a.D2 = s->D2; a.DO = s->DO; a.statp = statp;
     a.N = B; a.rows_pad = n_tiles * 16; a.mode = mode; a.net0 = 0; a.cr = cr; a.cc = cc; a.max_action = 1.0f;
-    a.tgt = s->Y; a.qout = (mode == FB_MODE_Q_FWD && params == s->PQT) ? s->QT : s->QP; a.qin = s->QP; a.da_out = s->DA;
-    if (qout_override) a.qout = qout_override;
+    a.tgt = s->Y; a.qout = sac_q_out(s, params, mode, qout_override); a.qin = s->QP; a.da_out = s->DA;
     a.act_cols = c->cfg.act_dim; a.pair_shift = s->n_q == 2 ? 0 : 1;
     if (ns) { a.ns_on = 1; a.ns = *ns; }          // Q_TRAIN: the tile launch computes its n-step targets itself
     return a;
+}
+// the head of a layered Q-network pass (lay_sac_q_head_kernel behind lay_fwd_k over the B rows of `params`' networks)
+static LaySacQArgs lay_sac_q_head_args(const fsrl_ctx* c, const SacState* s, int mode, float* statp, int B, float* qout_override,
+                                       const float* params) {
+    LaySacQArgs qa{};
+    qa.out = s->kq.out; qa.dout = s->kq.dout; qa.tgt = s->Y; qa.statp = statp; qa.B = B; qa.mbp = s->kq.mbp; qa.n_q = s->n_q;
+    qa.mode = mode; qa.pair_shift = s->n_q == 2 ? 0 : 1;
+    qa.qout = sac_q_out(s, params, mode, qout_override);
+    return qa;
 }
 
 // qout_override / n_tiles / rows4: the K*B particle launch of CVPO's E-step (forward only) reuses the Q-net kernel
@@ -536,10 +572,7 @@ static int sac_q_launch(fsrl_ctx* c, SacState* s, const float* params, const flo
         // side of the backward pass (Q_DIN: down to the input, dQ / d[obs | act] per network in s->DXQ)
         int rc = lay_fwd_k(c, s->kq, params, X, B);
         if (rc) return rc;
-        LaySacQArgs qa{};
-        qa.out = s->kq.out; qa.dout = s->kq.dout; qa.tgt = s->Y; qa.statp = statp; qa.B = B; qa.mbp = s->kq.mbp; qa.n_q = s->n_q;
-        qa.mode = mode; qa.pair_shift = s->n_q == 2 ? 0 : 1;
-        qa.qout = qout_override ? qout_override : ((mode == FB_MODE_Q_FWD && params == s->PQT) ? s->QT : s->QP);
+        const LaySacQArgs qa = lay_sac_q_head_args(c, s, mode, statp, B, qout_override, params);
         hipLaunchKernelGGL(lay_sac_q_head_kernel, dim3((B + 15) / 16, s->n_q), dim3(64), 0, c->compute, qa);
         HIPCHK(hipGetLastError());
         if (mode == FB_MODE_Q_FWD) return 0;
@@ -572,6 +605,14 @@ static FbWgradArgs sac_wgrad_args(const fsrl_ctx* c, const SacState* s, int ny, 
     wa.obs = X; wa.rows = (int)rp; wa.N = B;
     return wa;
 }
+// ... and of batches of up to 512 padded rows (rp), where ppo_wgrad_body writes the final gradient into G (no `stats`: the extra
+// block only reduces db3)
+static WgradPtrs sac_wgrad_small_args(const SacState* s, int rp, const float* X, float* G) {
+    WgradPtrs w{};
+    w.A1 = s->A1; w.A2 = s->A2; w.D1 = s->D1; w.D2 = s->D2; w.DO = s->DO; w.X = X; w.grad = G;
+    w.gsq_part = s->gsq_scratch; w.mbp_max = rp;
+    return w;
+}
 
 // weight gradients of `ny` networks of `md` as split-K partials in c->wg_parts (stride = n_dev)
 static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, const float* X, int n_dev, int B, int* nsplit,
@@ -596,9 +637,7 @@ static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, cons
         int rc = ensure_parts(c, n_dev, 1);
         if (rc) return rc;
         if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
-        WgradPtrs wp{};
-        wp.A1 = s->A1; wp.A2 = s->A2; wp.D1 = s->D1; wp.D2 = s->D2; wp.DO = s->DO; wp.X = X; wp.grad = c->wg_parts;
-        wp.gsq_part = s->gsq_scratch; wp.mbp_max = (int)rp;       // no `stats`: the extra block only reduces db3
+        const WgradPtrs wp = sac_wgrad_small_args(s, (int)rp, X, c->wg_parts);
         *nsplit = 1;
         const PpoStepArgs none{};
         ModelDesc mdy = md;
@@ -656,6 +695,91 @@ static void adam_final_launch(fsrl_ctx* c, const ModelDesc& md, float* P, float*
                        c->cfg.adam_eps, nparts, stride, md, tgt, tau, (float)(1.0 - (double)tau), fa);
 }
 
+// the layered actor pass of a SAC-Lag / DDPG-Lag context, layer by layer: the forward and the actor head of the mode; `both`: then,
+// as the fused launch's second batch, the current actor on (OBS, eps_p) -> XP, LP; SAC_A_BWD: also the activation side of the
+// backward pass
+static int lay_sac_actor_pass(fsrl_ctx* c, SacState* s, int B, int mode, const float* PAx, const float* obs, const float* eps, float* X,
+                              float* lp, float resc, float lam, bool both) {
+    auto one = [&](const float* Pn, const float* obs_, const float* eps_, float* X_, float* lp_) -> int {
+        int rc = lay_fwd_k(c, s->ka, Pn, obs_, B);
+        if (rc) return rc;
+        const LaySacActorArgs h = lay_sac_actor_head_args(c, s, B, mode, eps_, X_, lp_, resc, lam);
+        hipLaunchKernelGGL(lay_sac_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, c->compute, h);
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    int rc = one(PAx, obs, eps, X, lp);
+    if (rc) return rc;
+    if (both) { rc = one(s->PA, s->OBS, s->eps_p, s->XP, s->LP); if (rc) return rc; }
+    return mode == SAC_A_BWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
+}
+
+// ---- the frame of one solo replay update, the same for fsrl_sac_update and fsrl_cvpo_update (host_cvpo.inc), beside the grouped
+//      frame of host_sac_group.inc: replay_join, the key (replay_seed_key), the caller's sample (sac_stage_indices) or the books
+//      (sac_upload_book), the update's own first actor launch, replay_critic_half, the update's own actor side up to its last Adam
+//      pass (which writes replay_stats_row), replay_finish.
+// the context before an update: its resident actor ends, its pushes land, its batch buffers hold B rows (rgroup_join: a member's)
+static int replay_join(fsrl_ctx* c, SacState* s, int B) {
+    ENTER_DEV(c);
+    const int rc = join_store(c);
+    return rc ? rc : sac_alloc_batch(c, s, B);
+}
+// the Philox key of the library-RNG mode is a hash of the last non-zero seed; a zero seed keeps the key
+static void replay_seed_key(SacState* s, uint64_t seed) { if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
+// the critic half: target Q-networks on (s_{t+n}, a') -> the float64 n-step return -> the critics' forward + backward -> their weight
+// gradients -> one Adam of all Q-networks.  na: the update's n-step arguments (sac_nstep_args / cvpo_nstep_args)
+static int replay_critic_half(fsrl_ctx* c, SacState* s, int B, const SacNstepArgs& na, float lr, float tau, int* nsplit) {
+    int rc = sac_q_launch(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B);
+    if (rc) return rc;
+    // the critics' tile launch computes its float64 targets itself and leaves them in Y for the logged row; the layered Q head reads
+    // them from the stand-alone launch, which fsrl_sac_set_plan bit 2 keeps for fused contexts too
+    const bool ns_fold = !s->layered && !s->plan_nstep_sep;
+    if (!ns_fold) {
+        hipLaunchKernelGGL(sac_nstep_kernel, dim3((B + 255) / 256), dim3(256), 0, c->compute, na);
+        HIPCHK(hipGetLastError());
+    }
+    rc = sac_q_launch(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, -1, -1, ns_fold ? &na : nullptr);
+    if (rc) return rc;
+    rc = sac_wgrad(c, s, s->mdq, s->n_q, s->XQ, s->nq_dev, B, nsplit);
+    if (rc) return rc;
+    s->t_critic += 1;
+    // sync_weight (sac_lag.py:132-134, cvpo.py:202-204) is folded into this pass: the critics do not change again within the update
+    adam_launch(c, s->mdq, s->PQ, s->MQ, s->VQ, c->wg_parts, s->nq_dev, lr, s->t_critic, *nsplit, s->nq_dev, s->PQT, tau);
+    return 0;
+}
+// the ring row the update's last Adam pass writes
+static float* replay_stats_row(const SacState* s) { return s->d_stats + (size_t)(s->n_updates % SAC_RING) * s->nstats; }
+// the update is issued: count it, and with stats_out read its row back (n_floats of it) synchronously and mark it drained
+static int replay_finish(fsrl_ctx* c, SacState* s, const float* stats_row, float* stats_out, size_t n_floats) {
+    s->n_updates += 1;
+    if (stats_out) {
+        HIPCHK(hipMemcpyAsync(stats_out, stats_row, n_floats * 4, hipMemcpyDeviceToHost, c->compute));
+        HIPCHK(hipStreamSynchronize(c->compute));
+        s->n_drained = s->n_updates;
+    }
+    return 0;
+}
+
+// the two sets of batch buffers change places (SacState::alt): a prefetched sample becomes this update's
+static void sac_swap_sets(SacState* s) {
+    std::swap(s->d_idx, s->alt.d_idx); std::swap(s->d_chain, s->alt.d_chain); std::swap(s->d_end, s->alt.d_end);
+    std::swap(s->XQ, s->alt.XQ); std::swap(s->OBS, s->alt.OBS); std::swap(s->OBSN, s->alt.OBSN); std::swap(s->XN, s->alt.XN);
+    std::swap(s->XP, s->alt.XP); std::swap(s->eps_t, s->alt.eps_t); std::swap(s->eps_p, s->alt.eps_p);
+}
+// the sample + gather arguments of update n_updates + 1 into the other set, which the builders address through the usual members
+static void sac_next_sample_args(const fsrl_ctx* c, SacState* s, int B, int64_t stored, SacSampleArgs& sa, SacGatherArgs& ga) {
+    sac_swap_sets(s);
+    sa = sac_sample_args(c, s, B, s->cfg.n_step, stored, s->n_updates + 1);
+    ga = sac_gather_args(c, s, B, s->cfg.n_step);
+    sac_swap_sets(s);                                         // this update's set is back
+}
+// that sample sits in the other set, drawn on the side stream or by rider blocks; update n_updates + 1 takes it if batch size, store
+// version, key and count are still these
+static void sac_mark_prefetched(const fsrl_ctx* c, SacState* s, int B, bool side) {
+    s->pre_valid = true; s->pre_side = side; s->pre_B = B; s->pre_store_version = c->store_version; s->pre_key = s->key;
+    s->pre_counter = s->n_updates + 1;
+}
+
 extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, const float* eps_target,
                                const float* eps_pi, uint64_t seed, const double* lagrangians, double rescaling,
                                float* stats_out) {
@@ -666,36 +790,21 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     if (s->cvpo) return fail(FSRL_ESTATE, "this context runs CVPO: call fsrl_cvpo_update");
     const int64_t stored = fsrl_store_len(c);
     CHECK_ARG(stored > 0, "empty replay store");
-    ENTER_DEV(c);
-    int rc = join_store(c);
-    if (rc) return rc;
-    rc = sac_alloc_batch(c, s, B);
+    CHECK_ARG((indices != nullptr) == (eps_target != nullptr) && (indices != nullptr) == (eps_pi != nullptr),
+              "indices, eps_target and eps_pi are given together (caller RNG) or all NULL (library RNG)");
+    int rc = replay_join(c, s, B);
     if (rc) return rc;
     hipStream_t st = c->compute;
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, ns = s->cfg.n_step;
-    CHECK_ARG((indices != nullptr) == (eps_target != nullptr) && (indices != nullptr) == (eps_pi != nullptr),
-              "indices, eps_target and eps_pi are given together (caller RNG) or all NULL (library RNG)");
-    if (seed) s->key = seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull;
+    replay_seed_key(s, seed);
     bool fused_gather = false;
     bool want_rider = false;                           // r6: the NEXT update's sample + gather inside this update's actor weight-gradient launch
-    auto sample_args = [&](SacSampleArgs& sa, SacGatherArgs& ga, int64_t counter) {      // of the batch set `s` addresses when called (swap_sets)
-        sa = sac_sample_args(c, s, B, ns, stored, counter);
-        ga = sac_gather_args(c, s, B, ns);
-    };
-    auto swap_sets = [&]() {
-        std::swap(s->d_idx, s->alt.d_idx); std::swap(s->d_chain, s->alt.d_chain); std::swap(s->d_end, s->alt.d_end);
-        std::swap(s->XQ, s->alt.XQ); std::swap(s->OBS, s->alt.OBS); std::swap(s->OBSN, s->alt.OBSN); std::swap(s->XN, s->alt.XN);
-        std::swap(s->XP, s->alt.XP); std::swap(s->eps_t, s->alt.eps_t); std::swap(s->eps_p, s->alt.eps_p);
-    };
-    bool fold = false;                                 // r5: sample + gather inside the actors' forward launch
+    bool fold = false;                                // r5: sample + gather inside the actors' forward launch
     SacSampleArgs fold_sa{}; SacGatherArgs fold_ga{};
     if (indices) {
         // ---- caller-provided sample (parity mode): the policy's noise goes behind the target's in the pinned block
-        rc = sac_stage_indices(c, s, B, indices, eps_target);
+        rc = sac_stage_indices(c, s, B, indices, eps_target, eps_pi, (size_t)B * Da, s->h_eps + (size_t)B * Da, s->eps_p);
         if (rc) return rc;
-        float* he_p = s->h_eps + (size_t)B * Da;
-        memcpy(he_p, eps_pi, (size_t)B * Da * 4);
-        HIPCHK(hipMemcpyAsync(s->eps_p, he_p, (size_t)B * Da * 4, hipMemcpyHostToDevice, st));
     } else {
         // ---- library RNG: everything on the device, nothing to wait for
         rc = sac_upload_book(c, s);
@@ -707,11 +816,11 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
         const bool hit = fused_gather && s->pre_valid && s->pre_B == B && s->pre_store_version == c->store_version &&
                          s->pre_key == s->key && s->pre_counter == s->n_updates && (s->pre_side ? can_prefetch : want_rider);
         if (hit) {                                            // this update's sample is already in the other buffer set
-            swap_sets();
+            sac_swap_sets(s);
             if (s->pre_side) HIPCHK(hipStreamWaitEvent(st, s->pre_done, 0));      // (the riders ran on this stream)
         } else {
-            SacSampleArgs sa{}; SacGatherArgs ga{};
-            sample_args(sa, ga, s->n_updates);
+            const SacSampleArgs sa = sac_sample_args(c, s, B, ns, stored, s->n_updates);
+            const SacGatherArgs ga = sac_gather_args(c, s, B, ns);
             // r5: the fused kernels' forward launch of both actors draws and gathers its own rows (9 launches per update)
             fold = fused_gather && !can_prefetch && !s->plan_nofold && !s->layered && !s->cvpo;
             if (fold) { fold_sa = sa; fold_ga = ga; }
@@ -723,17 +832,14 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
         if (can_prefetch) {
             // the next update's sample into the set this update does NOT use (its last readers: the previous update, whose end
             // upd_done marks), on the side stream -- behind every store flush issued so far, concurrent with this update's kernels
-            swap_sets();                                      // address the other set through the usual members ...
             SacSampleArgs sa{}; SacGatherArgs ga{};
-            sample_args(sa, ga, s->n_updates + 1);
-            swap_sets();                                      // ... and put this update's set back
+            sac_next_sample_args(c, s, B, stored, sa, ga);
             HIPCHK(hipStreamWaitEvent(c->side, s->upd_done, 0));
             HIPCHK(hipStreamWaitEvent(c->side, s->book_done, 0));     // the sub-buffer bookkeeping this sample reads has landed
             hipLaunchKernelGGL(sac_sample_gather_kernel, dim3((B + SG_ROWS - 1) / SG_ROWS), dim3(256), 0, c->side, sa, ga);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(s->pre_done, c->side));
-            s->pre_valid = true; s->pre_side = true; s->pre_B = B; s->pre_store_version = c->store_version; s->pre_key = s->key;
-            s->pre_counter = s->n_updates + 1;
+            sac_mark_prefetched(c, s, B, true);
         }
     }
     s->last_B = B;
@@ -745,27 +851,10 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
         hipLaunchKernelGGL(sac_gather_kernel, dim3(std::min(1024, (B * (Do + Da) + 255) / 256)), dim3(256), 0, st, ga);
         HIPCHK(hipGetLastError());
     }
-    // ---- target: a', log pi' at s_{t+n}; target Q-nets; float64 n-step return
+    // ---- target: a', log pi' at s_{t+n} (the target Q-nets and the float64 n-step return: replay_critic_half)
     // `both`: the forward launch also evaluates the current actor on (OBS, eps_p) -> XP, LP as its second batch
     auto actor_launch = [&](const float* obs, const float* eps, float* X, float* lp, int mode, const float* PAx, bool both = false) {
-        if (s->layered) {       // layer by layer: forward, the actor head of the mode; BWD also the activation side of the backward pass
-            auto one = [&](const float* Pn, const float* obs_, const float* eps_, float* X_, float* lp_) -> int {
-                int rc2 = lay_fwd_k(c, s->ka, Pn, obs_, B);
-                if (rc2) return rc2;
-                LaySacActorArgs h{};
-                h.out = s->ka.out; h.dout = s->ka.dout; h.eps = eps_; h.X = X_; h.lp = lp_; h.DXQ = s->DXQ; h.QP = s->QP; h.sc = s->sc;
-                h.statp = s->stpi; h.B = B; h.Bq = s->kq.mbp; h.Do = Do; h.Da = Da; h.mode = mode; h.deterministic = s->ddpg ? 1 : 0;
-                h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh; h.cr = -resc;
-                h.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f; h.rescale = resc; h.alpha_fixed = s->cfg.alpha;
-                hipLaunchKernelGGL(lay_sac_actor_head_kernel, dim3((B + 15) / 16), dim3(256), 0, st, h);
-                HIPCHK(hipGetLastError());
-                return 0;
-            };
-            int rc2 = one(PAx, obs, eps, X, lp);
-            if (rc2) return rc2;
-            if (both) { rc2 = one(s->PA, s->OBS, s->eps_p, s->XP, s->LP); if (rc2) return rc2; }
-            return mode == SAC_A_BWD ? lay_bwd_dz_k(c, s->ka, PAx, B) : 0;
-        }
+        if (s->layered) return lay_sac_actor_pass(c, s, B, mode, PAx, obs, eps, X, lp, resc, lam, both);
         // probe: c->probe_phase is 0 outside probe builds
         SacActorArgs aa = sac_actor_args(c, s, B, mode, obs, eps, X, lp, resc, lam, s->ddpg ? 1 : 0, c->probe_phase);
         // 4-row tiles while the launch fits the chip in one round; the two-batch forward is twice as many workgroups
@@ -786,23 +875,10 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     // second does not depend on the critic step in between
     rc = actor_launch(s->OBSN, s->eps_t, s->XN, s->LPN, SAC_A_FWD, s->ddpg ? s->PAT : s->PA, true);
     if (rc) return rc;
-    rc = sac_q_launch(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B);
-    if (rc) return rc;
-    const SacNstepArgs na = sac_nstep_args(c, s, B);
-    if (s->plan_nstep_sep) {     // the stand-alone float64 n-step launch; by default the critics' tile launch computes its targets itself
-        hipLaunchKernelGGL(sac_nstep_kernel, dim3((B + 255) / 256), dim3(256), 0, st, na);
-        HIPCHK(hipGetLastError());
-    }
     // ---- critic step (all four Q-nets, one Adam)
-    rc = sac_q_launch(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, -1, -1, s->plan_nstep_sep ? nullptr : &na);
-    if (rc) return rc;
     int nsplit = 1;
-    rc = sac_wgrad(c, s, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &nsplit);
+    rc = replay_critic_half(c, s, B, sac_nstep_args(c, s, B), s->cfg.critic_lr, s->cfg.tau, &nsplit);
     if (rc) return rc;
-    s->t_critic += 1;
-    // sync_weight (sac_lag.py:132-134) is folded into this pass: the critics do not change again within the update
-    adam_launch(c, s->mdq, s->PQ, s->MQ, s->VQ, c->wg_parts, s->nq_dev, s->cfg.critic_lr, s->t_critic, nsplit, s->nq_dev,
-                s->PQT, s->cfg.tau);
     // ---- actor step: a ~ pi(s), Q(s, a) with the UPDATED critics, dL/da, actor backward
     rc = sac_q_launch(c, s, s->PQ, s->XP, FB_MODE_Q_DIN, 0.f, 0.f, s->stdin_, B);   // Q values + unit-seed dQ/da
     if (rc) return rc;
@@ -811,21 +887,14 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     {
         SgRider rd{};
         bool rode = false;
-        if (want_rider) {                                     // the other set of batch arrays, the next update's Philox counter
-            swap_sets();
-            sample_args(rd.sa, rd.ga, s->n_updates + 1);
-            swap_sets();
-        }
+        if (want_rider) sac_next_sample_args(c, s, B, stored, rd.sa, rd.ga);      // the other set, the next update's Philox counter
         rc = sac_wgrad(c, s, s->mda, 1, s->OBS, s->na_dev, B, &nsplit, want_rider ? &rd : nullptr, &rode);
         if (rc) return rc;
-        if (rode) {
-            s->pre_valid = true; s->pre_side = false; s->pre_B = B; s->pre_store_version = c->store_version; s->pre_key = s->key;
-            s->pre_counter = s->n_updates + 1;
-        }
+        if (rode) sac_mark_prefetched(c, s, B, false);
     }
     s->t_actor += 1;
     // ---- actor Adam; its extra block does the alpha step + logged stats (reads only what earlier launches wrote)
-    float* stats_row = s->d_stats + (size_t)(s->n_updates % SAC_RING) * s->nstats;
+    float* stats_row = replay_stats_row(s);
     const SacFinalArgs fa = sac_final_args(c, s, B, resc, lam, s->q_rows4 ? 4 * s->n_tiles : s->n_tiles,
                                            s->a_rows4 ? 4 * s->n_tiles : s->n_tiles, stats_row);
     // DDPG-Lag: actor_old <- tau * actor + (1 - tau) * actor_old in the same pass (ddpg_lag.py:120-123)
@@ -833,11 +902,5 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
                                                       s->t_actor, nsplit, s->na_dev, s->ddpg ? s->PAT : nullptr, s->cfg.tau, fa);
     HIPCHK(hipGetLastError());
     if (s->upd_done && s->plan_prefetch) HIPCHK(hipEventRecord(s->upd_done, st));      // side-stream prefetch only: the batch buffers of this update are free from here on
-    s->n_updates += 1;
-    if (stats_out) {                           // synchronous: this update's row (and mark it drained)
-        HIPCHK(hipMemcpyAsync(stats_out, stats_row, FSRL_SAC_NSTATS_K * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        s->n_drained = s->n_updates;
-    }
-    return 0;
+    return replay_finish(c, s, stats_row, stats_out, FSRL_SAC_NSTATS_K);
 }

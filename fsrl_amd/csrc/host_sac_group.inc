@@ -49,13 +49,8 @@ static void rgroup_detach(ReplayGroupCore& g, fsrl_ctx* c) {
 }
 // member c before a grouped call: its resident actor ends, its pushes land, its batch buffers and sub-buffer books are current
 static int rgroup_join(fsrl_ctx* c, int B) {
-    SacState* s = sac_of(c);
-    ENTER_DEV(c);
-    int rc = join_store(c);
-    if (rc) return rc;
-    rc = sac_alloc_batch(c, s, B);
-    if (rc) return rc;
-    return sac_upload_book(c, s);
+    const int rc = replay_join(c, sac_of(c), B);
+    return rc ? rc : sac_upload_book(c, sac_of(c));
 }
 // the group's stream goes behind member i's stream; recorded once the member's table entry is built
 static int rgroup_ready(ReplayGroupCore& g, int i) {
@@ -164,6 +159,19 @@ static void sac_group_step_row(int u, SacGroupStep& st, const fsrl_ctx* c, const
     st.a_step = as.step_size; st.a_bc2 = as.bc2_sqrt;
 }
 
+// Adam's constants of member c in its row of a member table (SacGroupMember and CvpoGroupMember name them alike), as adam_launch
+// passes them ...
+template <class Row>
+static void member_adam_consts(Row& r, const fsrl_ctx* c) {
+    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
+    r.one_minus_b1 = (float)(1.0 - b1); r.beta2 = c->cfg.beta2; r.one_minus_b2 = (float)(1.0 - b2); r.adam_eps = c->cfg.adam_eps;
+}
+// ... and the Polyak pass that rides on the critics' Adam (DDPG-Lag: on the actor's too)
+static void member_adam_consts(SacGroupMember& t, const fsrl_ctx* c, float tau) {
+    member_adam_consts(t, c);
+    t.tau = tau; t.one_minus_tau = (float)(1.0 - (double)tau);
+}
+
 // a group of layered members (all fused or all layered): host_sac_group_layered.inc
 struct LaySacGroup;
 static void lay_sac_group_free(LaySacGroup* lg);
@@ -236,14 +244,8 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
     return 0;
 }
 
-// a member's weight-gradient arguments (the grouped CVPO update, host_cvpo_group.inc, forms its members' here too).
-// Batches of up to 512 padded rows: ppo_wgrad_body writes the final gradient into G.
-static WgradPtrs group_wgrad_small(const SacState* s, int rp, const float* X, float* G) {
-    WgradPtrs w{};
-    w.A1 = s->A1; w.A2 = s->A2; w.D1 = s->D1; w.D2 = s->D2; w.DO = s->DO; w.X = X; w.grad = G;
-    w.gsq_part = s->gsq_scratch; w.mbp_max = rp;
-    return w;
-}
+// a member's weight-gradient arguments (the grouped CVPO update, host_cvpo_group.inc, forms its members' here too).  Batches of up
+// to 512 padded rows: sac_wgrad_small_args (host_sac.inc).
 // larger batches: sac_wgrad's split-K plan of `ny` networks for this member alone, its partials in the member's own buffer *G
 static int group_wgrad_split(fsrl_ctx* c, const SacState* s, FbWgradArgs& wa, const ModelDesc& md, int ny, const float* X, int stride,
                              int B, const float** G, int* nsplit) {
@@ -259,15 +261,50 @@ static int group_wgrad_split(fsrl_ctx* c, const SacState* s, FbWgradArgs& wa, co
     *G = c->wg_parts; *nsplit = pl.nsplit;
     return 0;
 }
+// a fused member's check (rgroup_begin): fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give
+// this member another kernel alone (fb_wgrad2_kernel); the tiled kernel fb_wgrad3_kernel needs re-laid observations the replay
+// agents never hand over
+static int rgroup_no_stream_wgrad(int i, const fsrl_ctx* c, int B) {
+    CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
+              "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
+    return 0;
+}
+// what a SAC-Lag / DDPG-Lag and a CVPO member fill alike in the table the SAC group's kernels read: the parameter and Adam stores
+// with Adam's constants and the Polyak tau, the critic half's two tile launches (na: the member's n-step arguments), and both
+// weight-gradient launches, the critics' over XQ and the actor's over OBS, by sac_wgrad's plan for this member alone
+static int group_member_base(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, const SacNstepArgs& na, float tau, bool small_wgrad,
+                             int* nsplit_q, int* nsplit_a) {
+    t = SacGroupMember{};
+    t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
+    member_adam_consts(t, c, tau);
+    t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, s->n_tiles, nullptr);
+    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, s->n_tiles, &na);
+    if (!small_wgrad) {
+        const int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
+        return rc ? rc : group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
+    }
+    const int rp = s->n_tiles * 16;
+    int rc = ensure_parts(c, s->nq_dev, 1);
+    if (rc) return rc;
+    t.GQ = c->wg_parts;
+    rc = ensure_parts(c, s->na_dev, 1);
+    if (rc) return rc;
+    t.GA = c->wg_parts;
+    if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
+    t.wq = sac_wgrad_small_args(s, rp, s->XQ, const_cast<float*>(t.GQ));
+    t.wa = sac_wgrad_small_args(s, rp, s->OBS, const_cast<float*>(t.GA));
+    *nsplit_q = *nsplit_a = 1;
+    return 0;
+}
 
 // the member's table entry: every argument of the nine launches as fsrl_sac_update forms it (library RNG, fold path)
 static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, const double* lags, double rescaling,
                             bool q_r4, bool a_r4, bool f_r4, bool small_wgrad, int* nsplit_q, int* nsplit_a) {
-    const int ns = s->cfg.n_step, nt = s->n_tiles, rp = nt * 16;
+    const int ns = s->cfg.n_step, nt = s->n_tiles;
     const float lam = (s->cfg.use_lagrangian && lags) ? (float)lags[0] : 0.0f;
     const float resc = (float)rescaling;
-    t = SacGroupMember{};
-    t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
+    const int rc = group_member_base(c, s, t, B, sac_nstep_args(c, s, B), s->cfg.tau, small_wgrad, nsplit_q, nsplit_a);
+    if (rc) return rc;
     t.PAT = s->ddpg ? s->PAT : nullptr;        // DDPG-Lag: the forward launch's first half runs it, the actor's Adam pass moves it
     // ---- actors (probe = 0: a probe build's phases are the solo path's); the forward launch carries the current actor's batch
     //      and the sample + gather (the sample's arguments: the step table's, rgroup_enter)
@@ -276,35 +313,11 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
     t.af.P2 = s->PA; t.af.obs2 = s->OBS; t.af.eps2 = s->eps_p; t.af.X2 = s->XP; t.af.lp2 = s->LP; t.af.tiles_half = f_r4 ? 4 * nt : nt;
     t.af.sg_on = 1; t.af.ga = sac_gather_args(c, s, B, ns);
     t.ab = sac_actor_args(c, s, B, SAC_A_BWD, s->OBS, s->eps_p, s->XP, s->LP, resc, lam, det, 0);
-    // ---- Q-network tile launches
-    const SacNstepArgs na = sac_nstep_args(c, s, B);
-    t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, nt, nullptr);
-    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, nt, &na);
+    // ---- Q(s, a ~ pi) with the updated critics + dQ/da
     t.qd = sac_q_args(c, s, s->PQ, s->XP, FB_MODE_Q_DIN, 0.f, 0.f, s->stdin_, B, nullptr, nt, nullptr);
-    // ---- weight gradients: sac_wgrad's plan for this member alone
-    if (small_wgrad) {
-        int rc = ensure_parts(c, s->nq_dev, 1);
-        if (rc) return rc;
-        t.GQ = c->wg_parts;
-        rc = ensure_parts(c, s->na_dev, 1);
-        if (rc) return rc;
-        t.GA = c->wg_parts;
-        if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
-        t.wq = group_wgrad_small(s, rp, s->XQ, const_cast<float*>(t.GQ));
-        t.wa = group_wgrad_small(s, rp, s->OBS, const_cast<float*>(t.GA));
-        *nsplit_q = *nsplit_a = 1;
-    } else {
-        int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
-        if (rc) return rc;
-        rc = group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
-        if (rc) return rc;
-    }
-    // ---- the logged row (fin.stats per step) and Adam's constants
+    // ---- the logged row (fin.stats per step)
     t.fin = sac_final_args(c, s, B, resc, lam, q_r4 ? 4 * nt : nt, a_r4 ? 4 * nt : nt, nullptr);
     t.stats = s->d_stats; t.nstats = s->nstats;
-    const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-    t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
-    t.tau = s->cfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->cfg.tau);
     return 0;
 }
 
@@ -341,11 +354,7 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     ReplayGroupCall call;
     int rc = rgroup_begin(gc, false, n_updates, call, [&](int i, const fsrl_ctx* c, const SacState* s) {
         CHECK_ARG(s->wgrad_splitk == s0->wgrad_splitk, "members must agree on fsrl_sac_set_plan bit 0 (split-K weight gradients)");
-        // fsrl_tr_set_plan's one-pass streaming weight gradients (256 wide, >= 4096 rows) would give this member another kernel alone
-        // (fb_wgrad2_kernel); the tiled kernel fb_wgrad3_kernel needs re-laid observations the replay agents never hand over
-        CHECK_ARG(!(c->wgrad_stream && c->cfg.hidden == 256 && (B + 15) / 16 * 16 >= 4096),
-                  "member %d: the streaming weight-gradient plan (fsrl_tr_set_plan wgrad = 3) is not grouped", i);
-        return 0;
+        return rgroup_no_stream_wgrad(i, c, B);
     });
     if (rc) return rc;
     CHECK_ARG(!s0->cfg.use_lagrangian || lagrangians, "lagrangians: [k][n_critics - 1] when use_lagrangian is on");

@@ -41,6 +41,28 @@ static void lay_sac_group_launch(const LaySacOp& op, hipStream_t s, const LinGro
     else { if (op.nw == 4) LSG_GO(false, 4); else if (op.nw == 2) LSG_GO(false, 2); else LSG_GO(false, 1); }
 #undef LSG_GO
 }
+// the launches the layered SAC / DDPG program and the layered CVPO program (host_cvpo_group_layered.inc) have in common: the linear
+// jobs, the n-step targets, a Q head (op.gx row tiles) and the critics' Adam + Polyak.  false: the kind is the caller's own
+static bool lay_replay_group_launch(const LaySacOp& op, hipStream_t gs, const SacState* s0, int B, int k, const LinGroupJob* jobs,
+                                    const LaySacQArgs* qh, const SacNstepArgs* na, const SacGroupMember* tab, const SacGroupStep* st) {
+    switch (op.kind) {
+    case LSG_LIN:
+        if (op.form == LIN_F) lay_sac_group_launch<LIN_F>(op, gs, jobs, st);
+        else if (op.form == LIN_X) lay_sac_group_launch<LIN_X>(op, gs, jobs, st);
+        else lay_sac_group_launch<LIN_W>(op, gs, jobs, st);
+        return true;
+    case LSG_NSTEP:
+        hipLaunchKernelGGL(sac_nstep_group_kernel, dim3((B + 255) / 256, k), dim3(256), 0, gs, na, st);
+        return true;
+    case LSG_QHEAD:
+        hipLaunchKernelGGL(lay_sac_q_head_group_kernel, dim3(op.gx, s0->n_q, k), dim3(64), 0, gs, qh + (size_t)op.which * k, st);
+        return true;
+    case LSG_ADAM_Q:
+        hipLaunchKernelGGL(sac_adam_group_kernel, dim3((s0->nq_dev + 255) / 256, k), dim3(256), 0, gs, s0->mdq, tab, st, s0->nq_dev, 1, s0->nq_dev);
+        return true;
+    }
+    return false;
+}
 
 // ---- the launch list of one grouped layered replay update while it is built: the Linear jobs of lay_fwd_k / lay_bwd_dz_k /
 //      lay_wgrad_k for every member in one launch each, and the other launches by kind.  The layered SAC / DDPG program below and
@@ -153,8 +175,6 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
     ReplayGroupCore& gc = g->core;
     const int k = (int)gc.m.size();
     fsrl_ctx* c0 = gc.m[0];
-    const SacState* s0 = sac_of(c0);
-    const int n_q = s0->n_q, Do = c0->cfg.obs_dim, Da = c0->cfg.act_dim;
     const size_t lag_stride = (size_t)std::max(1, c0->cfg.n_critics - 1);
     int rc = table_ensure(lg.ah, (size_t)3 * k, (size_t)3 * k);
     if (!rc) rc = table_ensure(lg.qh, (size_t)3 * k, (size_t)3 * k);
@@ -164,26 +184,27 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
     memset(lg.ah.h, 0, (size_t)3 * k * sizeof(LaySacActorArgs)); memset(lg.qh.h, 0, (size_t)3 * k * sizeof(LaySacQArgs));
     memset(lg.ga.h, 0, (size_t)k * sizeof(SacGatherArgs)); memset(lg.na.h, 0, (size_t)k * sizeof(SacNstepArgs));
     LayReplayProg pg(gc, work, lg.hjobs, lg.prog);
+    const int tiles = (B + 15) / 16;                   // row tiles of a head launch
     auto S = [&](int i) { return sac_of(gc.m[i]); };
     // ---- the update, launch by launch (fsrl_sac_update, layered branches)
     pg.op(LSG_SAMPLE);
     pg.fwd(true, B, [&](int i) { return S(i)->ddpg ? S(i)->PAT : S(i)->PA; }, [&](int i) { return S(i)->OBSN; });
-    pg.op(LSG_AHEAD, 0);
+    pg.op(LSG_AHEAD, 0, tiles);
     pg.fwd(true, B, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
-    pg.op(LSG_AHEAD, 1);
+    pg.op(LSG_AHEAD, 1, tiles);
     pg.fwd(false, B, [&](int i) { return S(i)->PQT; }, [&](int i) { return S(i)->XN; });
-    pg.op(LSG_QHEAD, 0);
+    pg.op(LSG_QHEAD, 0, tiles);
     pg.op(LSG_NSTEP);
     pg.fwd(false, B, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XQ; });
-    pg.op(LSG_QHEAD, 1);
+    pg.op(LSG_QHEAD, 1, tiles);
     pg.bwd(false, B, [&](int i) { return S(i)->PQ; }, false);
     pg.wgrad(false, B, [&](int i) { return S(i)->XQ; });
     pg.op(LSG_ADAM_Q);
     pg.fwd(false, B, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XP; });
-    pg.op(LSG_QHEAD, 2);
+    pg.op(LSG_QHEAD, 2, tiles);
     pg.bwd(false, B, [&](int i) { return S(i)->PQ; }, true);
     pg.fwd(true, B, [&](int i) { return S(i)->PA; }, [&](int i) { return S(i)->OBS; });
-    pg.op(LSG_AHEAD, 2);
+    pg.op(LSG_AHEAD, 2, tiles);
     pg.bwd(true, B, [&](int i) { return S(i)->PA; }, false);
     pg.wgrad(true, B, [&](int i) { return S(i)->OBS; });
     pg.op(LSG_ADAM_A);
@@ -196,19 +217,13 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
         const SacState* s = sac_of(c);
         const float lam = s->cfg.use_lagrangian ? (float)lagrangians[(size_t)i * lag_stride] : 0.0f;
         const float resc = (float)rescaling[i];
-        for (int v = 0; v < 3; ++v) {
-            LaySacActorArgs& h = lg.ah.h[(size_t)v * k + i];
-            h.out = s->ka.out; h.dout = s->ka.dout; h.DXQ = s->DXQ; h.QP = s->QP; h.sc = s->sc;
-            h.eps = v == 0 ? s->eps_t : s->eps_p; h.X = v == 0 ? s->XN : s->XP; h.lp = v == 0 ? s->LPN : s->LP;
-            h.statp = s->stpi; h.B = B; h.Bq = s->kq.mbp; h.Do = Do; h.Da = Da; h.mode = v == 2 ? SAC_A_BWD : SAC_A_FWD;
-            h.deterministic = s->ddpg ? 1 : 0;
-            h.auto_alpha = s->cfg.auto_alpha; h.max_action = c->cfg.max_action; h.mean_tanh = s->mean_tanh; h.cr = -resc;
-            h.cc = s->cfg.use_lagrangian ? resc * lam : 0.0f; h.rescale = resc; h.alpha_fixed = s->cfg.alpha;
-            LaySacQArgs& q = lg.qh.h[(size_t)v * k + i];
-            q.out = s->kq.out; q.dout = s->kq.dout; q.tgt = s->Y; q.statp = v == 2 ? s->stdin_ : s->stq; q.B = B; q.mbp = s->kq.mbp;
-            q.n_q = n_q; q.mode = v == 0 ? FB_MODE_Q_FWD : (v == 1 ? FB_MODE_Q_TRAIN : FB_MODE_Q_DIN); q.pair_shift = n_q == 2 ? 0 : 1;
-            q.qout = v == 0 ? s->QT : s->QP;
-        }
+        // the heads of fsrl_sac_update's three actor passes and three Q-network passes, in its order
+        lg.ah.h[(size_t)0 * k + i] = lay_sac_actor_head_args(c, s, B, SAC_A_FWD, s->eps_t, s->XN, s->LPN, resc, lam);
+        lg.ah.h[(size_t)1 * k + i] = lay_sac_actor_head_args(c, s, B, SAC_A_FWD, s->eps_p, s->XP, s->LP, resc, lam);
+        lg.ah.h[(size_t)2 * k + i] = lay_sac_actor_head_args(c, s, B, SAC_A_BWD, s->eps_p, s->XP, s->LP, resc, lam);
+        lg.qh.h[(size_t)0 * k + i] = lay_sac_q_head_args(c, s, FB_MODE_Q_FWD, s->stq, B, nullptr, s->PQT);
+        lg.qh.h[(size_t)1 * k + i] = lay_sac_q_head_args(c, s, FB_MODE_Q_TRAIN, s->stq, B, nullptr, s->PQ);
+        lg.qh.h[(size_t)2 * k + i] = lay_sac_q_head_args(c, s, FB_MODE_Q_DIN, s->stdin_, B, nullptr, s->PQ);
         lg.ga.h[i] = sac_gather_args(c, s, B, s->cfg.n_step);
         lg.na.h[i] = sac_nstep_args(c, s, B);
         t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
@@ -216,9 +231,7 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
         t.GA = s->GA; t.GQ = s->GQ;             // the weight-side launches leave the finished gradients there: one partial
         t.fin = sac_final_args(c, s, B, resc, lam, s->n_tiles, s->n_tiles, nullptr);
         t.stats = s->d_stats; t.nstats = s->nstats;
-        const double b1 = c->cfg.beta1, b2 = c->cfg.beta2;
-        t.one_minus_b1 = (float)(1.0 - b1); t.beta2 = c->cfg.beta2; t.one_minus_b2 = (float)(1.0 - b2); t.adam_eps = c->cfg.adam_eps;
-        t.tau = s->cfg.tau; t.one_minus_tau = (float)(1.0 - (double)s->cfg.tau);
+        member_adam_consts(t, c, s->cfg.tau);
     }
     rc = pg.upload(lg.jobs);
     if (rc) return rc;
@@ -250,32 +263,19 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
     if (rc) return rc;
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
-    const ModelDesc mda = s0->mda, mdq = s0->mdq;
-    const int na_dev = s0->na_dev, nq_dev = s0->nq_dev, n_q = s0->n_q, tiles = (B + 15) / 16;
+    const ModelDesc mda = s0->mda;
+    const int na_dev = s0->na_dev;
     const SacGroupMember* tab = g->tab.d;
     for (int u = 0; u < n_max; ++u) {
         const SacGroupStep* st = g->steps.d + (size_t)u * k;
         for (const LaySacOp& op : lg.prog) {
+            if (lay_replay_group_launch(op, gs, s0, B, k, lg.jobs.d, lg.qh.d, lg.na.d, tab, st)) continue;
             switch (op.kind) {
-            case LSG_LIN:
-                if (op.form == LIN_F) lay_sac_group_launch<LIN_F>(op, gs, lg.jobs.d, st);
-                else if (op.form == LIN_X) lay_sac_group_launch<LIN_X>(op, gs, lg.jobs.d, st);
-                else lay_sac_group_launch<LIN_W>(op, gs, lg.jobs.d, st);
-                break;
             case LSG_SAMPLE:
                 hipLaunchKernelGGL(sac_sample_gather_group_kernel, dim3((B + SG_ROWS - 1) / SG_ROWS, k), dim3(256), 0, gs, lg.ga.d, st);
                 break;
-            case LSG_NSTEP:
-                hipLaunchKernelGGL(sac_nstep_group_kernel, dim3((B + 255) / 256, k), dim3(256), 0, gs, lg.na.d, st);
-                break;
             case LSG_AHEAD:
-                hipLaunchKernelGGL(lay_sac_actor_head_group_kernel, dim3(tiles, k), dim3(256), 0, gs, lg.ah.d + (size_t)op.which * k, st);
-                break;
-            case LSG_QHEAD:
-                hipLaunchKernelGGL(lay_sac_q_head_group_kernel, dim3(tiles, n_q, k), dim3(64), 0, gs, lg.qh.d + (size_t)op.which * k, st);
-                break;
-            case LSG_ADAM_Q:
-                hipLaunchKernelGGL(sac_adam_group_kernel, dim3((nq_dev + 255) / 256, k), dim3(256), 0, gs, mdq, tab, st, nq_dev, 1, nq_dev);
+                hipLaunchKernelGGL(lay_sac_actor_head_group_kernel, dim3(op.gx, k), dim3(256), 0, gs, lg.ah.d + (size_t)op.which * k, st);
                 break;
             case LSG_ADAM_A:
                 hipLaunchKernelGGL(sac_adam_final_group_kernel, dim3((na_dev + 255) / 256 + 1, k), dim3(256), 0, gs, mda, tab, st, na_dev, 1, na_dev);
