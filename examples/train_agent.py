@@ -49,7 +49,11 @@ def main():
     ap.add_argument("--prefill", default=None, metavar="PATH",
                     help="sacl / ddpgl / cvpo: start from a replay store filled with the episodes of this dataset (the .npz that "
                          "examples/collect_dataset.py or TrajectoryBuffer.save writes) instead of an empty one")
+    ap.add_argument("--per-alpha", type=float, default=None, help="sacl / ddpgl: prioritised replay with this priority exponent")
+    ap.add_argument("--per-beta", type=float, default=0.4, help="... and this importance-weight exponent (with --per-alpha)")
     a = ap.parse_args()
+    if a.per_alpha is not None and a.algo not in ("sacl", "ddpgl"):
+        ap.error(f"--per-alpha: prioritised replay is built for sacl and ddpgl, not {a.algo}")
     if a.prefill is not None and a.algo not in ("sacl", "ddpgl", "cvpo"):
         ap.error(f"--prefill fills a replay store: --algo must be sacl, ddpgl or cvpo, not {a.algo}")
     if a.task == "point-circle":
@@ -80,7 +84,8 @@ def main():
     if a.algo in ("sacl", "ddpgl", "cvpo"):
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, update_per_step=0.2,
                           batch_size=a.batch_size, testing_num=2, device_actor=a.device_actor, verbose=True, save_ckpt=False,
-                          prefill=a.prefill)
+                          prefill=a.prefill,
+                          **({} if a.per_alpha is None else {"prioritized_replay": dict(alpha=a.per_alpha, beta=a.per_beta)}))
     else:
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, repeat_per_collect=4,
                           batch_size=a.batch_size if a.algo in ("ppol", "focops") else a.tr_batch_size, testing_num=2, device_actor=a.device_actor,

@@ -193,6 +193,13 @@ SIGNATURES = {
     "fsrl_store_sizes": (C.c_int, [_ctx, _i64, C.c_int32]),
     "fsrl_sac_stats_drain": (C.c_int64, [_ctx, _f, C.c_int64]),
     "fsrl_sac_last_sample": (C.c_int, [_ctx, _i64, _f, _f, C.c_int32]),
+    "fsrl_sac_last_chain": (C.c_int, [_ctx, _i64, _u8, C.c_int32]),
+    "fsrl_per_enable": (C.c_int, [_ctx, C.c_double, C.c_double, C.c_int32]),
+    "fsrl_per_set_beta": (C.c_int, [_ctx, C.c_double]),
+    "fsrl_per_update_weight": (C.c_int, [_ctx, _i64, _d, C.c_int64]),
+    "fsrl_per_state": (C.c_int, [_ctx, _d, C.c_int64, _d, _d, _d]),
+    "fsrl_per_last_weights": (C.c_int, [_ctx, _f, C.c_int32]),
+    "fsrl_per_last_td": (C.c_int, [_ctx, _f, C.c_int32]),
     "fsrl_sac_actor_forward": (C.c_int, [_ctx, _f, C.c_int32, _f, _f]),
     "fsrl_cvpo_init": (C.c_int, [_ctx, _P(CvpoConfig)]),
     "fsrl_cvpo_pre_update": (C.c_int, [_ctx]),

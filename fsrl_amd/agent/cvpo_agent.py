@@ -14,6 +14,10 @@ from fsrl_amd.utils.logger import DummyLogger
 class CVPOAgent(OffpolicyAgent):
     name = "CVPOAgent"
 
+    def _check_prioritized(self, prioritized_replay: dict) -> None:
+        raise NotImplementedError("prioritized_replay is built for SACLagAgent and DDPGLagAgent: CVPO's update hands no TD error "
+                                  "back to the buffer (the library refuses fsrl_per_enable on a CVPO context)")
+
     def __init__(self, env, logger=None, cost_limit: float = 10, device: str = "cuda:0", thread: int = 4, seed: int = 10,
                  estep_iter_num: int = 1, estep_kl: float = 0.02, estep_dual_max: float = 20, estep_dual_lr: float = 0.02,
                  sample_act_num: int = 16, mstep_iter_num: int = 1, mstep_kl_mu: float = 0.005,

@@ -7,7 +7,7 @@ import torch
 
 from fsrl_amd.agent._nets import adam, offpolicy_nets
 from fsrl_amd.agent.base_agent import BaseAgent
-from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+from fsrl_amd.data import FastCollector, HipPrioritizedVectorReplayBuffer, HipVectorReplayBuffer
 from fsrl_amd.policy.sac_lag import SACLagrangian
 from fsrl_amd.trainer.offpolicy import OffpolicyTrainer
 from fsrl_amd.utils.exp_util import seed_all
@@ -24,7 +24,8 @@ class OffpolicyAgent(BaseAgent):
               step_per_epoch: int = 3000, update_per_step: float = 0.1, buffer_size: Optional[int] = None,
               testing_num: int = 2, batch_size: int = 256, reward_threshold: float = 450,
               save_interval: int = 4, resume: bool = False, save_ckpt: bool = True, verbose: bool = True,
-              show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True, prefill=None):
+              show_progress: bool = True, device_actor: bool = False, ckpt_store: bool = True, prefill=None,
+              prioritized_replay: Optional[dict] = None):
         """resume=True continues the run whose training state `<log_dir>/checkpoint/train_state.pt` holds (saved with every periodic
         checkpoint while save_ckpt is on): epoch numbering, env steps, the best result, the replay store, optimiser state and
         random streams carry over; without such a file the run starts fresh and says so.  Env state is never saved: a resumed
@@ -33,7 +34,11 @@ class OffpolicyAgent(BaseAgent):
         prefill: a TrajectoryBuffer, or the path of a dataset one saved -- its episodes are poured into the replay store
         (HipVectorReplayBuffer.fill_from, actions mapped back with this policy's inverse action map) after the store has been cut
         to this call's geometry and before the first collect; no env step is counted for them.  Skipped, with a printed line, when
-        resume=True restored a store."""
+        resume=True restored a store.
+        prioritized_replay: None, or dict(alpha=..., beta=..., weight_norm=True) -- the replay buffer is then what tianshou's
+        PrioritizedVectorReplayBuffer(buffer_size, len(train_envs), alpha, beta, weight_norm) is to the reference: updates draw
+        their batch by priority, weight the critics' loss and hand |TD| back as the new priorities, all on the device.  SAC-Lag
+        and DDPG-Lag with the library's sampler (not reference_rng, whose indices come from the host's uniform draw)."""
         assert self.policy is not None, "The policy is not initialized"
         self.policy.train()
         eng = self.policy.engine
@@ -43,7 +48,11 @@ class OffpolicyAgent(BaseAgent):
         # VectorReplayBuffer(buffer_size, len(train_envs)) of the reference (base_agent.py:279): the store is re-cut to
         # that geometry.  None = the size the agent was built with (its `buffer_size`, default 100 000 like the
         # reference's learn()); an explicit size must fit that allocation (AssertionError otherwise).
-        buffer = HipVectorReplayBuffer(eng, buffer_size, len(train_envs))
+        if prioritized_replay is not None:
+            self._check_prioritized(prioritized_replay)
+            buffer = HipPrioritizedVectorReplayBuffer(eng, buffer_size, len(train_envs), **prioritized_replay)
+        else:
+            buffer = HipVectorReplayBuffer(eng, buffer_size, len(train_envs))
         # device_actor=True: actor + noise on the MI355X (library RNG); over a worker-process env the collector then also
         # overlaps the actor with the env workers when that pays (split_phase="auto")
         train_collector = FastCollector(self.policy, train_envs, buffer, exploration_noise=True, device_actor=device_actor,
@@ -73,6 +82,14 @@ class OffpolicyAgent(BaseAgent):
             if verbose:
                 print(f"Epoch: {ep}", info)
         return ep, stat, info
+
+    def _check_prioritized(self, prioritized_replay: dict) -> None:
+        unknown = set(prioritized_replay) - {"alpha", "beta", "weight_norm"}
+        if unknown or not {"alpha", "beta"} <= set(prioritized_replay):
+            raise ValueError(f"prioritized_replay takes alpha, beta and optionally weight_norm, got {sorted(prioritized_replay)}")
+        if getattr(self.policy, "_reference_rng", False):
+            raise ValueError("prioritized_replay needs the library's sampler: with reference_rng=True the batch indices are drawn "
+                             "uniformly on the host")
 
     def _prefill(self, prefill, buffer, resumed: bool) -> int:
         """learn(prefill=...): a TrajectoryBuffer or a dataset path -> rows poured into `buffer`"""

@@ -210,6 +210,7 @@ struct fsrl_ctx {
                                     // trust-region batch were computed at the CURRENT theta (the Gauss-Newton form of the KL product)
     void* sac = nullptr;            // SacState, owned
     struct fsrl_tap* tap = nullptr; // the trajectory archive's tap on this context's store ingest (host_traj.inc), owned by the archive
+    struct PerState* per = nullptr; // prioritised replay: the sum tree over this context's store (host_per.inc), owned
 };
 static bool ctx_is_replay(const fsrl_ctx* c);
 static void sac_free(fsrl_ctx* c);
@@ -233,6 +234,10 @@ static inline bool tap_closed(const fsrl_ctx* c, int e);
 static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, uint8_t fl);
 static int tap_flush(fsrl_ctx* c, int w, const uint8_t* recs_d, int stage_rec, int k);
 static void tap_ctx_gone(fsrl_ctx* c);           // a context destroyed before the archive it feeds
+// prioritised replay (host_per.inc): the sum tree follows every row that reaches the store and every reset of it
+static int per_ingest(fsrl_ctx* c, const uint8_t* recs_d, int rec, int k);
+static int per_store_reset(fsrl_ctx* c);
+static void per_free(fsrl_ctx* c);
 static int focops_pass(fsrl_ctx* c, int32_t* stopped_out);
 static int pass_verdict(fsrl_ctx* c, int32_t* stopped_out);
 
@@ -507,6 +512,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     comm_free(c);
     tr_free(c);
     sac_free(c);
+    per_free(c);
     foc_free(c);
     lay_free(c);
     if (c->h_actor) (void)hipHostFree(c->h_actor);
@@ -792,6 +798,10 @@ static int flush_stage(fsrl_ctx* c) {
     const int blocks = std::min(1024, (k * per + 255) / 256);
     hipLaunchKernelGGL(store_scatter_kernel, dim3(blocks), dim3(256), 0, c->side, c->st, s.d, (int)rec, k, Do, Da);
     HIPCHK(hipGetLastError());
+    if (c->per) {           // PrioritizedReplayBuffer.add: the window's slots get max_prio ** alpha, behind the last update's priorities
+        const int prc = per_ingest(c, s.d, (int)rec, k);
+        if (prc) return prc;
+    }
     // the tap's copy and launches go behind the window's own, before the event that frees the window's pinned memory (the tap's
     // too); an archive without room fails the call AFTER the window's bookkeeping is complete
     const int tap_rc = c->tap ? tap_flush(c, c->cur_stage, s.d, (int)rec, k) : 0;
@@ -886,7 +896,7 @@ extern "C" int fsrl_store_reset(fsrl_ctx* c, int keep_statistics) {
     }
     c->batch_ready = false;
     c->store_version += 1;
-    return 0;
+    return c->per ? per_store_reset(c) : 0;
 }
 
 // VectorReplayBuffer(total_size, buffer_num) as the agents' learn() builds it (fsrl/agent/base_agent.py:279): re-cut the
@@ -909,7 +919,7 @@ extern "C" int fsrl_store_configure(fsrl_ctx* c, int64_t total_size, int32_t buf
     c->maxsize = sub * buffer_num;
     c->active_envs = buffer_num;
     std::fill(c->h_flags.begin(), c->h_flags.end(), (uint8_t)0);
-    return 0;
+    return c->per ? per_store_reset(c) : 0;      // the tree of the new geometry
 }
 extern "C" int fsrl_store_geometry(const fsrl_ctx* c, int64_t* sub_size_out, int32_t* buffer_num_out) {
     CHECK_ARG(c && sub_size_out && buffer_num_out, "null argument");

@@ -10,6 +10,7 @@ extern "C" int fsrl_cvpo_init(fsrl_ctx* c, const fsrl_cvpo_config* cfg) {
     CHECK_ARG(cfg->tau >= 0.0f && cfg->tau <= 1.0f, "tau should be in [0, 1]");
     CHECK_ARG(cfg->sample_act_num >= 1 && cfg->sample_act_num <= 64, "sample_act_num must be in [1, 64]");
     CHECK_ARG(cfg->estep_iter_num >= 1 && cfg->mstep_iter_num >= 1, "estep_iter_num and mstep_iter_num must be >= 1");
+    CHECK_ARG(!c->per, "this context has prioritised replay on (fsrl_per_enable), which is not built for CVPO");
     CHECK_ARG(cfg->actor_mean >= FSRL_ACTOR_MEAN_DEFAULT && cfg->actor_mean <= FSRL_ACTOR_MEAN_TANH,
               "actor_mean must be 0 (default), 1 (unbounded) or 2 (max_action * tanh), got %d", cfg->actor_mean);
     ENTER_DEV(c);

@@ -55,6 +55,8 @@ static int cvpo_group_check(fsrl_ctx* const* ctxs, int k, const fsrl_cvpo_group*
         for (int j = 0; j < i; ++j) CHECK_ARG(ctxs[j] != c, "member %d is listed twice", i);
         const SacState* s = reinterpret_cast<const SacState*>(c->sac);
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
+        CHECK_ARG(!c->per, "member %d has prioritised replay on (fsrl_per_enable): it covers solo SAC-Lagrangian and DDPG-Lagrangian "
+                  "contexts only", i);
         CHECK_ARG(!s->ddpg, "member %d is a DDPG-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
         CHECK_ARG(s->cvpo, "member %d is a SAC-Lagrangian context: grouped CVPO updates take CVPO contexts (fsrl_cvpo_init)", i);
         const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);

@@ -72,6 +72,8 @@ struct SacState {
 static constexpr int SAC_RING = 4096;
 
 static SacState* sac_of(fsrl_ctx* c) { return reinterpret_cast<SacState*>(c->sac); }
+static SacSampleArgs sac_sample_args(const fsrl_ctx* c, const SacState* s, int B, int n_step, int64_t stored, int64_t counter);
+#include "host_per.inc"
 
 // layered layout: dense tensors (no padded units, no W2 mirror), device order = the networks one after the other; the API orders
 // are the fused layout's (actor: preprocess, mu head, sigma head; critics per DoubleCritic: pre1 pre2 last1 last2)
@@ -551,6 +553,7 @@ static FbArgs sac_q_args(const fsrl_ctx* c, const SacState* s, const float* para
     a.tgt = s->Y; a.qout = sac_q_out(s, params, mode, qout_override); a.qin = s->QP; a.da_out = s->DA;
     a.act_cols = c->cfg.act_dim; a.pair_shift = s->n_q == 2 ? 0 : 1;
     if (ns) { a.ns_on = 1; a.ns = *ns; }          // Q_TRAIN: the tile launch computes its n-step targets itself
+    if (c->per && mode == FB_MODE_Q_TRAIN) a.wgt = c->per->w;      // prioritised replay: the rows' importance weights
     return a;
 }
 // the head of a layered Q-network pass (lay_sac_q_head_kernel behind lay_fwd_k over the B rows of `params`' networks)
@@ -560,6 +563,7 @@ static LaySacQArgs lay_sac_q_head_args(const fsrl_ctx* c, const SacState* s, int
     qa.out = s->kq.out; qa.dout = s->kq.dout; qa.tgt = s->Y; qa.statp = statp; qa.B = B; qa.mbp = s->kq.mbp; qa.n_q = s->n_q;
     qa.mode = mode; qa.pair_shift = s->n_q == 2 ? 0 : 1;
     qa.qout = sac_q_out(s, params, mode, qout_override);
+    if (c->per && mode == FB_MODE_Q_TRAIN) qa.wgt = c->per->w;
     return qa;
 }
 
@@ -733,13 +737,18 @@ static int replay_critic_half(fsrl_ctx* c, SacState* s, int B, const SacNstepArg
     if (rc) return rc;
     // the critics' tile launch computes its float64 targets itself and leaves them in Y for the logged row; the layered Q head reads
     // them from the stand-alone launch, which fsrl_sac_set_plan bit 2 keeps for fused contexts too
-    const bool ns_fold = !s->layered && !s->plan_nstep_sep;
+    // (a prioritised update keeps the stand-alone launch as well: per_update_kernel reads the targets from Y)
+    const bool ns_fold = !s->layered && !s->plan_nstep_sep && !c->per;
     if (!ns_fold) {
         hipLaunchKernelGGL(sac_nstep_kernel, dim3((B + 255) / 256), dim3(256), 0, c->compute, na);
         HIPCHK(hipGetLastError());
     }
     rc = sac_q_launch(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, -1, -1, ns_fold ? &na : nullptr);
     if (rc) return rc;
+    if (c->per) {           // the sampled rows' new priorities from the Q values and targets that launch just used
+        rc = per_update_launch(c, s, B);
+        if (rc) return rc;
+    }
     rc = sac_wgrad(c, s, s->mdq, s->n_q, s->XQ, s->nq_dev, B, nsplit);
     if (rc) return rc;
     s->t_critic += 1;
@@ -799,12 +808,25 @@ extern "C" int fsrl_sac_update(fsrl_ctx* c, int32_t B, const int64_t* indices, c
     replay_seed_key(s, seed);
     bool fused_gather = false;
     bool want_rider = false;                           // r6: the NEXT update's sample + gather inside this update's actor weight-gradient launch
+                                                       // (never with prioritised replay: the next sample depends on this update's priorities)
     bool fold = false;                                // r5: sample + gather inside the actors' forward launch
     SacSampleArgs fold_sa{}; SacGatherArgs fold_ga{};
     if (indices) {
         // ---- caller-provided sample (parity mode): the policy's noise goes behind the target's in the pinned block
         rc = sac_stage_indices(c, s, B, indices, eps_target, eps_pi, (size_t)B * Da, s->h_eps + (size_t)B * Da, s->eps_p);
         if (rc) return rc;
+        if (c->per) rc = per_sample_launch(c, s, B, false, stored);      // the importance weights of the caller's rows
+        if (rc) return rc;
+    } else if (c->per) {
+        // ---- prioritised replay: the descent of the sum tree, then the plain gather below.  The rider blocks and the side-stream
+        // prefetch (want_rider, can_prefetch) draw the NEXT update's sample while this one runs, but the next prioritised sample
+        // depends on the priorities this update writes; the fold into the actors' forward launch (fold) draws tile by tile, and
+        // weight_norm needs the maximum over the whole batch before the first weight is used.  All three stay off.
+        rc = sac_upload_book(c, s);
+        if (rc) return rc;
+        rc = per_sample_launch(c, s, B, true, stored);
+        if (rc) return rc;
+        s->pre_valid = false;
     } else {
         // ---- library RNG: everything on the device, nothing to wait for
         rc = sac_upload_book(c, s);

@@ -210,6 +210,8 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
         CHECK_ARG(c, "null member");
         const SacState* s = reinterpret_cast<const SacState*>(c->sac);
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped SAC updates take SAC-Lagrangian contexts (fsrl_sac_init)", i);
+        CHECK_ARG(!c->per, "member %d has prioritised replay on (fsrl_per_enable): it covers solo contexts only, a grouped update "
+                  "draws every member's sample inside shared launches", i);
         CHECK_ARG(!s->cvpo, "member %d runs CVPO: grouped SAC updates take SAC-Lagrangian contexts only", i);
         const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
         CHECK_ARG(s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a group is all fused (two hidden layers of at "

@@ -137,6 +137,31 @@ static int64_t ts_live_rows(const TsHostBuf& hb) {
     return n;
 }
 
+// prioritised replay (section T_PER, only while it is on): the options and the two scalars, and with the store the leaves -- the
+// tree above them is rebuilt on import.  A context without it writes no such section: its blob is what it always was.
+static int64_t ts_per_bytes(const fsrl_ctx* c, bool with_store) { return tstate::per_bytes(with_store ? c->per->slots : 0); }
+static int ts_per_export(fsrl_ctx* c, uint8_t* p, bool with_store) {
+    const PerState* ps = c->per;
+    double sc[3];
+    HIPCHK(hipMemcpy(sc, ps->sc, sizeof(sc), hipMemcpyDeviceToHost));
+    const tstate::PerHead h{ps->alpha, ps->beta, (int64_t)ps->weight_norm, sc[0], sc[1], with_store ? (int64_t)ps->slots : 0};
+    memcpy(p, &h, (size_t)tstate::PER_HEAD_BYTES);
+    if (with_store && ps->slots > 0)
+        HIPCHK(hipMemcpy(p + tstate::PER_HEAD_BYTES, ps->tree + ps->bound, (size_t)ps->slots * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+// ... into the context, whose store (geometry included) is already the blob's
+static int ts_per_import(fsrl_ctx* c, const uint8_t* p) {
+    tstate::PerHead h;
+    memcpy(&h, p, (size_t)tstate::PER_HEAD_BYTES);
+    PerState* ps = c->per;
+    ps->alpha = h.alpha; ps->beta = h.beta; ps->weight_norm = (int)h.weight_norm;
+    if (h.slots == 0) return 0;                 // a blob without the store: the tree stays this context's own, like its rows
+    std::vector<double> leaves((size_t)h.slots);
+    memcpy(leaves.data(), p + tstate::PER_HEAD_BYTES, (size_t)h.slots * 8);
+    return per_load(c, leaves.data(), h.max_prio, h.min_prio);
+}
+
 static int ts_idle(const fsrl_ctx* c, const char* what) {
     if (c->in_update || c->verdict_pending) return fail(FSRL_ESTATE, "%s inside an update (between fsrl_ppo_begin and fsrl_ppo_end)", what);
     return 0;
@@ -169,6 +194,7 @@ extern "C" int64_t fsrl_train_state_size(fsrl_ctx* c, int32_t with_store) {
     const int64_t live = ts_live_rows(hb);
     std::vector<int64_t> lens;
     for (const TsSection& s : tab) lens.push_back(s.kind == TS_STORE_COL ? live * s.bytes : s.bytes);
+    if (c->per) lens.push_back(ts_per_bytes(c, with_store != 0));
     return tstate::blob_bytes(lens.data(), (int)lens.size());
 }
 
@@ -194,7 +220,7 @@ extern "C" int fsrl_train_state_export(fsrl_ctx* c, int32_t with_store, void* ou
     const std::vector<TsRun> runs = ts_ranges(hb);
     const int64_t live = ts_live_rows(hb);
     tstate::Writer w(out, cap);
-    w.header(fp, with_store ? tstate::FLAG_STORE : 0u, (uint32_t)tab.size());
+    w.header(fp, with_store ? tstate::FLAG_STORE : 0u, (uint32_t)tab.size() + (c->per ? 1u : 0u));
     for (const TsSection& s : tab) {
         const int64_t len = s.kind == TS_STORE_COL ? live * s.bytes : s.bytes;
         uint8_t* p = w.section(s.tag, len);
@@ -206,6 +232,12 @@ extern "C" int fsrl_train_state_export(fsrl_ctx* c, int32_t with_store, void* ou
                 HIPCHK(hipMemcpy(p, (const char*)s.ptr + r.row0 * s.bytes, (size_t)(r.rows * s.bytes), hipMemcpyDeviceToHost));
                 p += r.rows * s.bytes;
             }
+    }
+    if (c->per) {
+        uint8_t* p = w.section(tstate::T_PER, ts_per_bytes(c, with_store != 0));
+        if (!p) return fail(FSRL_EINVAL, "the training state does not fit %lld bytes", (long long)cap);
+        rc = ts_per_export(c, p, with_store != 0);
+        if (rc) return rc;
     }
     const int64_t n = w.finish();
     if (n != need) return fail(FSRL_ESTATE, "the training state took %lld bytes, not the %lld announced", (long long)n, (long long)need);
@@ -226,7 +258,8 @@ extern "C" int fsrl_train_state_import(fsrl_ctx* c, const void* blob, int64_t n)
     ts_table(c, hb, true, tab);
     std::vector<tstate::SectionSpec> specs;
     for (const TsSection& s : tab) specs.push_back({s.tag, s.kind == TS_STORE_COL ? -1 : s.bytes, ts_is_store(s.kind)});
-    std::vector<tstate::Found> found(tab.size());
+    specs.push_back({tstate::T_PER, -1, false, c->per == nullptr});      // behind the table's: found[tab.size()]
+    std::vector<tstate::Found> found(specs.size());
     const uint8_t* b = (const uint8_t*)blob;
     uint32_t flags = 0;
     std::string err;
@@ -247,6 +280,12 @@ extern "C" int fsrl_train_state_import(fsrl_ctx* c, const void* blob, int64_t n)
     if (with_store) {
         const tstate::StoreDims d{c->cfg.env_num, c->alloc_rows, c->cfg.obs_dim, c->cfg.act_dim};
         if (tstate::validate_store(geom, book, col_len, d, err)) return fail(FSRL_EINVAL, "%s", err.c_str());
+    }
+    const tstate::Found per_found = found[tab.size()];
+    if (per_found.off >= 0) {                            // (present exactly when this context has prioritised replay on: validate)
+        int64_t want_slots = 0;
+        if (with_store) { int64_t g[2]; memcpy(g, geom, 16); want_slots = g[0] * g[1]; }
+        if (tstate::validate_per(b + per_found.off, per_found.len, want_slots, err)) return fail(FSRL_EINVAL, "%s", err.c_str());
     }
     // ---- writes
     ENTER_DEV(c);                                        // a resident actor holds the old weights in registers: it ends here
@@ -275,6 +314,7 @@ extern "C" int fsrl_train_state_import(fsrl_ctx* c, const void* blob, int64_t n)
         const uint8_t* p = flag_col;
         for (const TsRun& r : runs) { memcpy(c->h_flags.data() + r.row0, p, (size_t)r.rows); p += r.rows; }
     }
+    if (per_found.off >= 0) { rc = ts_per_import(c, b + per_found.off); if (rc) return rc; }
     ts_invalidate(c);
     return 0;
 }
@@ -294,6 +334,8 @@ extern "C" int fsrl_train_state_copy(fsrl_ctx* dst, fsrl_ctx* src, int32_t with_
     const int d = tstate::fingerprint_diff(fs, fd);
     CHECK_ARG(d < 0, "training state: %s differs: the source has %lld, the destination %lld", tstate::FIELD_NAMES[d], (long long)fs.v[d],
               (long long)fd.v[d]);
+    CHECK_ARG((dst->per != nullptr) == (src->per != nullptr), "training state: prioritised replay is %s in the source and %s in the "
+              "destination (fsrl_per_enable on both, or on neither)", src->per ? "on" : "off", dst->per ? "on" : "off");
     ENTER_DEV(src);
     rc = join_store(src);
     if (rc) return rc;
@@ -320,6 +362,15 @@ extern "C" int fsrl_train_state_copy(fsrl_ctx* dst, fsrl_ctx* src, int32_t with_
     HIPCHK(hipStreamSynchronize(dst->compute));          // the source may change again as soon as this call returns
     ts_scatter(dst, hs, with_store != 0);
     if (with_store) dst->h_flags = src->h_flags;
+    if (src->per) {                                      // the options always; with the store its tree and scalars, node for node
+        PerState *ps = src->per, *pd = dst->per;
+        pd->alpha = ps->alpha; pd->beta = ps->beta; pd->weight_norm = ps->weight_norm;
+        if (with_store) {
+            pd->slots = ps->slots; pd->bound = ps->bound;
+            HIPCHK(hipMemcpy(pd->tree, ps->tree, (size_t)2 * ps->bound * 8, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(pd->sc, ps->sc, 3 * 8, hipMemcpyDeviceToDevice));
+        }
+    }
     ts_invalidate(dst);
     return 0;
 }

@@ -469,6 +469,10 @@ extern "C" int fsrl_store_fill(fsrl_ctx* c, fsrl_traj* t, const int32_t* episode
                        c->st, reinterpret_cast<const TrajJob*>(t->fill.d), (int)nj, t->Do, t->Da, (int)bound_method,
                        act_low ? reinterpret_cast<const float*>(t->fill.d + map_off) : nullptr);
     HIPCHK(hipGetLastError());
+    if (c->per) {                   // the poured rows' leaves (the pushes of the model: max_prio ** alpha each), read from the same job table
+        rc = per_fill(c, reinterpret_cast<const TrajJob*>(t->fill.d), (int)nj);
+        if (rc) return rc;
+    }
     HIPCHK(hipEventRecord(t->fill_done, c->side));
     t->fill_pending = true;
     t->fill_launches += 1; t->fill_copies += 1;

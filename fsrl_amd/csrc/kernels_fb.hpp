@@ -90,6 +90,7 @@ struct FbArgs {
     int pair_shift;       // Q_TRAIN target of net n is tgt[n >> pair_shift]: 1 = double critics (SAC), 0 = single (DDPG)
     int ns_on;            // Q_TRAIN: the regression targets are computed HERE (sac_nstep_target) instead of read from tgt: one
     SacNstepArgs ns;      //   launch less per update; the same float64 operations, so the same bits
+    const float* wgt;     // Q_TRAIN: [N] importance weights of prioritised replay (loss = mean(td^2 * w)); NULL: none, today's arithmetic
 };
 
 // ---- the actor's loss head of the trust-region modes (SUR, KL, EVAL): ONE definition with floating-point contraction off, called
@@ -392,8 +393,10 @@ __device__ __forceinline__ void fb_tile_body(TileSmem<H, tile_rows(R)>& sm, cons
             if (valid && d == 0) {
                 if (a.mode == FB_MODE_Q_TRAIN) {
                     const float td = qv - (a.ns_on ? sm.st[i] : a.tgt[(size_t)(net >> a.pair_shift) * a.N + r]);
-                    sm.dout[i * FSRL_DOW] = 2.0f * td * invN;
-                    st[0] = td * td;
+                    float seed = 2.0f * td * invN, sq = td * td;
+                    if (a.wgt) { const float w = a.wgt[r]; seed *= w; sq *= w; }
+                    sm.dout[i * FSRL_DOW] = seed;
+                    st[0] = sq;
                     a.qout[(size_t)net * a.N + r] = qv;
                 } else if (a.mode == FB_MODE_Q_FWD) {
                     a.qout[(size_t)net * a.N + r] = qv;

@@ -113,6 +113,7 @@ struct LaySacQArgs {
     const float* out; float* dout;          // [n_q][mbp][16] / [n_q][mbp][FSRL_DOW]
     const float* tgt; float* qout; float* statp;
     int B, mbp, n_q, mode, pair_shift;
+    const float* wgt;                       // Q_TRAIN: [B] importance weights of prioritised replay, or NULL
 };
 __device__ __forceinline__ void lay_sac_q_head_body(const LaySacQArgs& a, const int tile, const int net) {
     const int tid = threadIdx.x;
@@ -124,8 +125,10 @@ __device__ __forceinline__ void lay_sac_q_head_body(const LaySacQArgs& a, const 
         if (a.mode == FB_MODE_Q_TRAIN) {
             const float td = qv - a.tgt[(size_t)(net >> a.pair_shift) * a.B + r];
             for (int e = 0; e < FSRL_DOW; ++e) dO[e] = 0.0f;
-            dO[0] = 2.0f * td * (1.0f / (float)a.B);
-            st0 = td * td;
+            float seed = 2.0f * td * (1.0f / (float)a.B), sq = td * td;
+            if (a.wgt) { const float w = a.wgt[r]; seed *= w; sq *= w; }
+            dO[0] = seed;
+            st0 = sq;
             a.qout[(size_t)net * a.B + r] = qv;
         } else if (a.mode == FB_MODE_Q_FWD) {
             a.qout[(size_t)net * a.B + r] = qv;

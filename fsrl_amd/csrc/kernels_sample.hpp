@@ -54,17 +54,11 @@ __device__ __forceinline__ void sac_sample_noise(const SacSampleArgs& a, const i
     a.eps_t[(size_t)b * a.Da + d0] = t0; a.eps_p[(size_t)b * a.Da + d0] = p0;
     if (d0 + 1 < a.Da) { a.eps_t[(size_t)b * a.Da + d0 + 1] = t1; a.eps_p[(size_t)b * a.Da + d0 + 1] = p1; }
 }
-// index and n-step chain of sampled row b -> (index, terminal index); the chain's LAST end bit is left to the caller as (flag byte,
-// at-the-write-head) so that the load behind it need not have landed when the caller moves on (sac_sample_end_last)
-__device__ __forceinline__ void sac_sample_index(const SacSampleArgs& a, const SacBook* __restrict__ book, const int b,
-                                                 const uint32_t k0, const uint32_t k1, int& idx, int& term,
-                                                 unsigned char& f_last, bool& head_last) {
-    uint32_t c[4] = {(uint32_t)b, 0u, (uint32_t)a.counter, (uint32_t)(a.counter >> 32)};
-    philox4x32_10(c, k0, k1);
-    unsigned long long k = ((unsigned long long)c[0] * a.stored) >> 32;    // uniform over the stored rows
-    int e = 0;
-    while (e < a.env_num - 1 && k >= (unsigned long long)book[e].size) { k -= book[e].size; ++e; }
-    int cur = e * a.sub_size + (int)k;
+// n-step chain of sampled row b from its index `cur` -> (index, terminal index); the chain's LAST end bit is left to the caller as
+// (flag byte, at-the-write-head) so that the load behind it need not have landed when the caller moves on (sac_sample_end_last).
+// Shared by the uniform draw below and the prioritised one (per_sample_kernel, kernels_per.hpp).
+__device__ __forceinline__ void sac_sample_chain(const SacSampleArgs& a, const SacBook* __restrict__ book, const int b, int cur,
+                                                 int& idx, int& term, unsigned char& f_last, bool& head_last) {
     a.idx[b] = cur;
     idx = cur;
     unsigned char f = a.flags[cur];
@@ -83,6 +77,17 @@ __device__ __forceinline__ void sac_sample_index(const SacSampleArgs& a, const S
     }
     term = cur;                                        // the chain's last element
     f_last = f; head_last = head;
+}
+// uniform index of sampled row b and its chain (sac_sample_chain)
+__device__ __forceinline__ void sac_sample_index(const SacSampleArgs& a, const SacBook* __restrict__ book, const int b,
+                                                 const uint32_t k0, const uint32_t k1, int& idx, int& term,
+                                                 unsigned char& f_last, bool& head_last) {
+    uint32_t c[4] = {(uint32_t)b, 0u, (uint32_t)a.counter, (uint32_t)(a.counter >> 32)};
+    philox4x32_10(c, k0, k1);
+    unsigned long long k = ((unsigned long long)c[0] * a.stored) >> 32;    // uniform over the stored rows
+    int e = 0;
+    while (e < a.env_num - 1 && k >= (unsigned long long)book[e].size) { k -= book[e].size; ++e; }
+    sac_sample_chain(a, book, b, e * a.sub_size + (int)k, idx, term, f_last, head_last);
 }
 __device__ __forceinline__ void sac_sample_end_last(const SacSampleArgs& a, const int b, const unsigned char f_last, const bool head_last) {
     a.endbits[(size_t)(a.n_step - 1) * a.B + b] = (f_last != 0 || head_last) ? 1 : 0;

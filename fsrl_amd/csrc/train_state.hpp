@@ -59,6 +59,7 @@ static constexpr uint32_t T_SACS = fourcc('S', 'A', 'C', 'S'), T_CVPS = fourcc('
 static constexpr uint32_t T_GEOM = fourcc('G', 'E', 'O', 'M'), T_BOOK = fourcc('B', 'O', 'O', 'K');
 static constexpr uint32_t T_SOBS = fourcc('S', 'O', 'B', 'S'), T_SNXT = fourcc('S', 'N', 'X', 'T'), T_SACT = fourcc('S', 'A', 'C', 'T');
 static constexpr uint32_t T_SREW = fourcc('S', 'R', 'E', 'W'), T_SCST = fourcc('S', 'C', 'S', 'T'), T_SFLG = fourcc('S', 'F', 'L', 'G');
+static constexpr uint32_t T_PER = fourcc('P', 'E', 'R', ' ');       // prioritised replay (PerHead, then the leaves): only when it is on
 
 static inline std::string tag_name(uint32_t t) {
     char s[5];
@@ -68,8 +69,9 @@ static inline std::string tag_name(uint32_t t) {
 }
 
 // what a context expects of one section.  bytes < 0: the length is the blob's to state (the store's columns: their rows follow
-// from the sub-buffer books, validate_store checks them); store: the section exists exactly in blobs with FLAG_STORE
-struct SectionSpec { uint32_t tag; int64_t bytes; bool store; };
+// from the sub-buffer books, validate_store checks them); store: the section exists exactly in blobs with FLAG_STORE; absent: the
+// section belongs to an option this context has OFF (prioritised replay), so a blob that carries it is refused by name
+struct SectionSpec { uint32_t tag; int64_t bytes; bool store; bool absent = false; };
 struct Found { int64_t off = -1, len = 0; };          // a section's payload inside the blob
 
 static constexpr int64_t HEADER_BYTES = 24 + 8 * (int64_t)F_N;
@@ -194,6 +196,9 @@ static inline int validate(const uint8_t* b, int64_t n, const Fingerprint& want,
         int k = -1;
         for (int i = 0; i < nspecs; ++i) if (specs[i].tag == tag) { k = i; break; }
         if (k < 0) return refuse(err, "training state: unknown section %s", tag_name(tag).c_str());
+        if (specs[k].absent)
+            return refuse(err, "training state: section %s: the blob carries %s state and this context has it off", tag_name(tag).c_str(),
+                          tag == T_PER ? "prioritised-replay" : "optional");
         if (specs[k].store && !with_store) return refuse(err, "training state: store section %s in a blob without the store", tag_name(tag).c_str());
         if (found[k].off >= 0) return refuse(err, "training state: duplicate section %s", tag_name(tag).c_str());
         if (specs[k].bytes >= 0 && len != specs[k].bytes)
@@ -207,7 +212,9 @@ static inline int validate(const uint8_t* b, int64_t n, const Fingerprint& want,
     }
     if (seen != nsec) return refuse(err, "training state: the header counts %u sections, %u are there", nsec, seen);
     for (int i = 0; i < nspecs; ++i)
-        if (found[i].off < 0 && (!specs[i].store || with_store)) return refuse(err, "training state: missing section %s", tag_name(specs[i].tag).c_str());
+        if (found[i].off < 0 && !specs[i].absent && (!specs[i].store || with_store))
+            return refuse(err, "training state: missing section %s%s", tag_name(specs[i].tag).c_str(),
+                          specs[i].tag == T_PER ? ": this context has prioritised replay on and the blob was taken from one without it" : "");
     if (flags_out) *flags_out = flags;
     return 0;
 }
@@ -279,6 +286,37 @@ static inline int validate_store(const uint8_t* geom, const uint8_t* book, const
         if (col_len[k] != rows * column_width(d, k))
             return refuse(err, "training state: store column %s has %lld bytes, %lld live rows need %lld", names[k], (long long)col_len[k],
                           (long long)rows, (long long)(rows * column_width(d, k)));
+    return 0;
+}
+
+// ---- prioritised replay (section T_PER, present exactly when the exporting context has it on).  PerHead, then `slots` float64
+//      leaves in slot order; slots = sub_size * buffer_num in a blob with the store, 0 in one without (the leaves describe the
+//      store's rows: without them only the options travel).  The tree above the leaves is rebuilt on import.
+struct PerHead { double alpha, beta; int64_t weight_norm; double max_prio, min_prio; int64_t slots; };
+static constexpr int64_t PER_HEAD_BYTES = 48;
+static_assert(sizeof(PerHead) == PER_HEAD_BYTES, "PerHead is six 8-byte fields");
+static inline int64_t per_bytes(int64_t slots) { return PER_HEAD_BYTES + 8 * slots; }
+// want_slots: sub_size * buffer_num of the geometry the blob brings (validate_store has accepted it), 0 for a blob without the store
+static inline int validate_per(const uint8_t* payload, int64_t len, int64_t want_slots, std::string& err) {
+    if (len < PER_HEAD_BYTES) return refuse(err, "training state: section PER_ of %lld bytes is shorter than its head", (long long)len);
+    PerHead h;
+    memcpy(&h, payload, (size_t)PER_HEAD_BYTES);
+    if (!(std::isfinite(h.alpha) && h.alpha >= 0.0 && std::isfinite(h.beta) && h.beta >= 0.0))
+        return refuse(err, "training state: prioritised replay: alpha and beta must be finite and >= 0");
+    if (h.weight_norm != 0 && h.weight_norm != 1) return refuse(err, "training state: prioritised replay: weight_norm is %lld", (long long)h.weight_norm);
+    if (!(std::isfinite(h.max_prio) && std::isfinite(h.min_prio) && h.min_prio > 0.0 && h.min_prio <= h.max_prio))
+        return refuse(err, "training state: prioritised replay: max_prio and min_prio must be finite with 0 < min_prio <= max_prio");
+    if (h.slots != want_slots)
+        return refuse(err, "training state: prioritised replay: leaves for %lld slots, the blob's store has %lld", (long long)h.slots,
+                      (long long)want_slots);
+    if (h.slots < 0 || h.slots > (INT64_MAX - PER_HEAD_BYTES) / 8 || len != per_bytes(h.slots))
+        return refuse(err, "training state: section PER_ has %lld bytes, %lld slots need %lld", (long long)len, (long long)h.slots,
+                      (long long)(h.slots < 0 || h.slots > (INT64_MAX - PER_HEAD_BYTES) / 8 ? -1 : per_bytes(h.slots)));
+    for (int64_t i = 0; i < h.slots; ++i) {
+        double v;
+        memcpy(&v, payload + PER_HEAD_BYTES + 8 * i, 8);
+        if (!(std::isfinite(v) && v >= 0.0)) return refuse(err, "training state: prioritised replay: leaf %lld is not finite and >= 0", (long long)i);
+    }
     return 0;
 }
 

@@ -4,6 +4,7 @@ from fsrl_amd._lazy import install
 install(__name__, globals(), {
     "Batch": "batch",
     "HipVectorReplayBuffer": "buffer",
+    "HipPrioritizedVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
     "GroupCollector": "group_collector",
     "BasicCollector": "basic_collector",

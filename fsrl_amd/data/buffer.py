@@ -90,3 +90,29 @@ class HipVectorReplayBuffer:
         counts = np.bincount(pick, minlength=self.buffer_num)
         return np.concatenate([np.random.choice(int(lengths[e]), int(counts[e])) + e * self._sub
                                for e in range(self.buffer_num)]).astype(np.int64)
+
+
+class HipPrioritizedVectorReplayBuffer(HipVectorReplayBuffer):
+    """tianshou's `PrioritizedVectorReplayBuffer(total_size, buffer_num, alpha, beta, weight_norm)` over the HIP-resident store:
+    the sum tree lives on the device next to the rows (`fsrl_per_enable`).  A SAC-Lag / DDPG-Lag update on the engine then draws
+    its batch from the tree, weights the critics' loss and writes the new priorities back without leaving the device; the methods
+    below are the host's view of the same tree."""
+
+    def __init__(self, engine, total_size=None, buffer_num=None, alpha=0.6, beta=0.4, weight_norm=True):
+        super().__init__(engine, total_size, buffer_num)
+        self._alpha, self._beta, self._weight_norm = float(alpha), float(beta), bool(weight_norm)
+        engine.per_enable(self._alpha, self._beta, self._weight_norm)
+
+    def set_beta(self, beta: float) -> None:
+        self._beta = float(beta)
+        self.engine.per_set_beta(self._beta)
+
+    def update_weight(self, index, new_weight) -> None:
+        """priority of the rows `index` = |new_weight| + float32 eps; of repeated indices the last one counts"""
+        w = new_weight.detach().cpu().numpy() if hasattr(new_weight, "detach") else np.asarray(new_weight)
+        self.engine.per_update_weight(np.asarray(index, np.int64), w.astype(np.float64))
+
+    def get_weight(self, index):
+        """importance weights of the rows `index`: (priority ** alpha / min_prio) ** (-beta), not normalised"""
+        leaves, _, min_prio, _ = self.engine.per_state()
+        return (leaves[np.asarray(index, np.int64)] / min_prio)**(-self._beta)

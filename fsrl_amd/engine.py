@@ -666,6 +666,46 @@ class Engine:
                                                  int(batch_size)))
         return idx, et, ep
 
+    def sac_last_chain(self, batch_size, n_step):
+        """n-step chains [n_step][B] and end bits of the last sac_update's sample"""
+        ch = np.empty((int(n_step), int(batch_size)), np.int64); end = np.empty(ch.shape, np.uint8)
+        _lib.check(self.lib.fsrl_sac_last_chain(self._ctx, _ptr(ch, _i64p), _ptr(end, _u8p), int(batch_size)))
+        return ch, end
+
+    # ---------------------------------------------------------------- prioritised replay (solo SAC-Lag / DDPG-Lag contexts)
+    def per_enable(self, alpha, beta, weight_norm=True):
+        """tianshou PrioritizedReplayBuffer's sum tree over this context's store, on the device (include/fsrl_hip.h)"""
+        _lib.check(self.lib.fsrl_per_enable(self._ctx, float(alpha), float(beta), int(bool(weight_norm))))
+        self.per_on = True
+
+    def per_set_beta(self, beta):
+        _lib.check(self.lib.fsrl_per_set_beta(self._ctx, float(beta)))
+
+    def per_update_weight(self, indices, weights):
+        idx = np.ascontiguousarray(indices, np.int64).reshape(-1)
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        assert idx.size == w.size
+        _lib.check(self.lib.fsrl_per_update_weight(self._ctx, _ptr(idx, _i64p), _ptr(w, _f64p), idx.size))
+
+    def per_state(self, leaves=True):
+        """(leaves float64 [buffer_num * sub_size] or None, max_prio, min_prio, total)"""
+        sub, num = self.store_geometry()
+        out = np.empty(sub * num, np.float64) if leaves else None
+        mx, mn, tot = C.c_double(), C.c_double(), C.c_double()
+        _lib.check(self.lib.fsrl_per_state(self._ctx, _ptr(out, _f64p), 0 if out is None else out.size, C.byref(mx), C.byref(mn),
+                                           C.byref(tot)))
+        return out, mx.value, mn.value, tot.value
+
+    def per_last_weights(self, batch_size):
+        out = np.empty(int(batch_size), np.float32)
+        _lib.check(self.lib.fsrl_per_last_weights(self._ctx, _ptr(out, _f32p), int(batch_size)))
+        return out
+
+    def per_last_td(self, batch_size):
+        out = np.empty(int(batch_size), np.float32)
+        _lib.check(self.lib.fsrl_per_last_td(self._ctx, _ptr(out, _f32p), int(batch_size)))
+        return out
+
     def sac_actor_forward(self, obs):
         obs = np.ascontiguousarray(obs, np.float32).reshape(-1, self.cfg.obs_dim)
         k = obs.shape[0]

@@ -615,6 +615,44 @@ int64_t fsrl_sac_stats_drain(fsrl_ctx* ctx, float* out, int64_t max_rows);
 /* The sample the last fsrl_sac_update used, either mode (tests: library-RNG updates can be replayed
  * through the caller-RNG arguments).                                                              */
 int fsrl_sac_last_sample(fsrl_ctx* ctx, int64_t* indices, float* eps_target, float* eps_pi, int32_t batch_size);
+/* ... and its n-step chains [n_step][batch_size] with their end bits (done | unfinished tail), as the update used them. */
+int fsrl_sac_last_chain(fsrl_ctx* ctx, int64_t* chain_out, uint8_t* end_out, int32_t batch_size);
+
+/* ---- Prioritised experience replay for solo SAC-Lagrangian / DDPG-Lagrangian contexts (fused or layered): tianshou 0.5
+ *      PrioritizedReplayBuffer / SegmentTree, which the reference reaches through critics_loss's batch.weight (sac_lag.py:189-201,
+ *      ddpg_lag.py:170-179), learn's `batch.weight = td` (sac_lag.py:263, ddpg_lag.py:218) and post_process_fn's
+ *      buffer.update_weight (base_policy.py:326-330).  One float64 sum tree over the whole store lives in HBM: 2 * bound nodes, bound
+ *      = the next power of two at or above buffer_num * sub_size, the leaf of global slot env * sub_size + local = priority ** alpha,
+ *      every internal node exactly left + right.  max_prio and min_prio (raw priorities) start at 1.
+ *        a row reaching the store (fsrl_store_push, fsrl_store_fill)   leaf = max_prio ** alpha, max_prio as of the last update
+ *                                                                      issued before the push
+ *        fsrl_store_reset / fsrl_store_configure                       empty tree, both scalars back at 1
+ *        fsrl_sac_update, library RNG     row b: u = word 0 of Philox block (b, 0, update count) * 2^-32 in float64, scalar = u * root;
+ *                                         i = 1; while i < bound: i *= 2; l = tree[i]; if l < scalar: scalar -= l, i += 1; slot =
+ *                                         i - bound.  n-step chain, end bits and noise as the uniform sampler forms them.
+ *        fsrl_sac_update, caller RNG      the caller's indices; weights and priorities as below
+ *        importance weight of a row       (leaf / min_prio) ** (-beta), with weight_norm divided by the batch's maximum, as float32;
+ *                                         the critics' loss per Q-network is mean(td^2 * w), and the logged loss/q* are the weighted ones
+ *        behind the critic step           td_avg = float32 mean over the update's Q-networks of Q_j - target (the values the step used);
+ *                                         p = |td_avg| + float32 eps in float64; leaf[idx] = p ** alpha (duplicate indices: the highest
+ *                                         batch position wins); max_prio = max(max_prio, max p), min_prio = min(min_prio, min p)
+ *      A prioritised update draws its sample in a launch of its own, gathers in a second and computes the n-step targets in a third
+ *      (the folds into other launches are off, and so is the sample drawn one update ahead: the next sample depends on this
+ *      update's priorities).  Refused, with the reason in fsrl_last_error: CVPO contexts, a context that is a member of a SAC / CVPO group
+ *      (and fsrl_sac_group_create / fsrl_cvpo_group_create refuse a member with prioritised replay on).
+ *      fsrl_per_enable         switches it on (again: from scratch); rows already stored get max_prio ** alpha = 1.
+ *      fsrl_per_set_beta       the exponent of the NEXT sample's weights (PrioritizedReplayBuffer.set_beta).
+ *      fsrl_per_update_weight  PrioritizedReplayBuffer.update_weight(indices, weights) from the host, n entries; waits.
+ *      fsrl_per_state          leaves_out[n] (n = buffer_num * sub_size; NULL: none) and the scalars; total = the root.  Waits for
+ *                              everything issued so far on both streams.
+ *      fsrl_per_last_weights   the float32 weights of the last fsrl_sac_update's batch; fsrl_per_last_td its td_avg per row.   */
+int fsrl_per_enable(fsrl_ctx* ctx, double alpha, double beta, int32_t weight_norm);
+int fsrl_per_set_beta(fsrl_ctx* ctx, double beta);
+int fsrl_per_update_weight(fsrl_ctx* ctx, const int64_t* indices, const double* weights, int64_t n);
+int fsrl_per_state(fsrl_ctx* ctx, double* leaves_out, int64_t n, double* max_prio, double* min_prio, double* total);
+int fsrl_per_last_weights(fsrl_ctx* ctx, float* w_out, int32_t batch_size);
+int fsrl_per_last_td(fsrl_ctx* ctx, float* td_out, int32_t batch_size);
+
 /* the actor for the collector: mu and sigma = exp(clamp(log sigma)) of the tanh-Gaussian policy   */
 int fsrl_sac_actor_forward(fsrl_ctx* ctx, const float* obs, int32_t k, float* mu_out, float* sigma_out);
 

@@ -2,7 +2,9 @@
 """Secondary benchmark: BASELINE.json configs[3] -- SAC-Lagrangian on the SafetyAntRun shape
 (obs 33, act 8, 256x256 actor + 2 double critics), 1 M-row replay store resident in HBM, batch 1024,
 n_step 2, auto alpha.  One JSON line; the CPU figure is the oracle (torch fp32, 4 threads) on the
-same store.  `--rows` shrinks the store for a quick run."""
+same store.  `--rows` shrinks the store for a quick run.  `--per` switches prioritised replay on (alpha 0.6, beta 0.4, weight_norm)
+after the fill: the same shape with the batch drawn from the sum tree, the critics' loss weighted and the priorities written back;
+profiles/per_sac.json holds it beside the uniform update of the same build and of the parent commit."""
 import argparse
 import json
 import os
@@ -31,6 +33,7 @@ def main(argv=None, emit=True):
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--unbounded", choices=("default", "true", "false"), default="default",
                     help="the actor's mean: true = the head, false = max_action * tanh(head); default: the agent's own")
+    ap.add_argument("--per", action="store_true", help="prioritised replay on (fsrl_per_enable after the fill)")
     a = ap.parse_args(argv)
     Do, Da, H, E, B = 33, 8, a.hidden, a.envs, a.batch
     T = a.rows // E
@@ -68,6 +71,8 @@ def main(argv=None, emit=True):
         eng.push(ids, obs[t], act[t], rew[t], cost[t], term[t], trunc[t], obs[t + 1])
     eng.sync()
     fill_s = time.perf_counter() - t0
+    if a.per:
+        eng.per_enable(0.6, 0.4, True)
     lag, resc = [0.3], 1.0 / 1.3
     for _ in range(200):                                   # 200 updates of warm-up: the GPU's clocks have ramped after the
         eng.sac_update(B, lag, resc, seed=0, sync=False)   # host-bound store fill (a 20-update warm-up left some runs at 260 us)
@@ -88,7 +93,12 @@ def main(argv=None, emit=True):
                                   f"batch {B}, n_step 2", **({} if a.unbounded == "default" else {"unbounded": a.unbounded}), "updates": a.updates, "blocks_us_per_update": [round(b * 1e6, 1) for b in blocks]},
            "store_fill_rows_per_s": T * E / fill_s, "dtype": "fp32",
            # r5 default: sample + gather inside the actors' forward launch; FSRL_SAC_PLAN bits 4 / 1 / 2 add launches back
-           "launches_per_update": 9 + sum(1 for bit in (16, 2, 4) if int(os.environ.get("FSRL_SAC_PLAN", "0")) & bit)}
+           # prioritised replay: the sample, the gather and the n-step targets as launches of their own, and the priority update
+           "launches_per_update": 13 if a.per else 9 + sum(1 for bit in (16, 2, 4) if int(os.environ.get("FSRL_SAC_PLAN", "0")) & bit)}
+    if a.per:
+        out["metric"] = "sac_lag prioritised-replay policy-updates/sec"
+        _, mx, mn, total = eng.per_state(leaves=False)
+        out["per"] = {"alpha": 0.6, "beta": 0.4, "weight_norm": True, "max_prio": mx, "min_prio": mn, "total": total}
     # roofline of the whole update (12 launches): algorithmic FLOPs per sample (~4.9 MFLOP at 256x256)
     Fq = 2 * ((Do + Da) * H + H * H + H); Fa = 2 * (Do * H + H * H + H * 2 * Da)
     per_sample = (2 * Fa            # actor forwards at s_{t+n} and s_t
