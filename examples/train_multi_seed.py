@@ -28,6 +28,11 @@ tools/bench_group_cvpo.py).
 --grouped --algo ddpgl: the same loop with DDPG-Lag seeds (ONE grouped update through fsrl_amd.policy.DDPGPolicyGroup ->
 fsrl_sac_group_update over deterministic-actor contexts; tools/bench_group_sac.py --algo ddpgl).
     python examples/train_multi_seed.py --algo ddpgl --seeds 4 --epoch 2 --grouped
+--per-alpha A [--per-beta B] [--per-no-weight-norm] (--algo sacl / ddpgl, every mode): prioritised replay -- every seed's buffer is a
+HipPrioritizedVectorReplayBuffer, its sum tree on the device.  --grouped: the seeds' prioritised updates share every launch, the
+solo prioritised update's sequence once per update for all seeds (13 launches for fused seeds; tools/bench_group_sac.py --per A,B).
+CVPO hands no TD error back to a buffer: --algo cvpo refuses the flags.
+    python examples/train_multi_seed.py --algo sacl --seeds 8 --epoch 2 --grouped --per-alpha 0.6 --per-beta 0.4
 --hidden-sizes 64x48x32 (every mode): the networks' hidden layers.  Anything but two layers of at most 256 units makes layered
 contexts; --grouped --algo ppol takes them as well: a layered minibatch step is 2 L + 5 launches whatever the number of seeds
 and the actor request of a vector step L + 2 (tools/bench_group_layered.py).
@@ -164,8 +169,9 @@ def run_grouped_replay(a):
     """k SAC-Lag (CVPO, DDPG-Lag) seeds, one host thread: the seeds collect in lock step (one collect-group call per vector step) and
     run their pre_update_fn (SAC-Lag / DDPG-Lag: the PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped
     update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed), then each
-    seed's post_update_fn."""
-    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
+    seed's post_update_fn.  --per-alpha: every seed's buffer is prioritised (made before the group: its members agree on that)."""
+    from fsrl_amd.data import FastCollector, GroupCollector, HipPrioritizedVectorReplayBuffer, HipVectorReplayBuffer
+    per = prioritized_replay(a)
     from fsrl_amd.engine import EngineCollectGroup
     from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
@@ -175,7 +181,10 @@ def run_grouped_replay(a):
         agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
                                training_num=a.envs)
         agent.policy.train()
-        buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
+        if per is None:
+            buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
+        else:
+            buf = HipPrioritizedVectorReplayBuffer(agent.policy.engine, None, a.envs, **per)
         agents.append(agent); bufs.append(buf)
         cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
     group = {"sacl": SACPolicyGroup, "ddpgl": DDPGPolicyGroup, "cvpo": CVPOPolicyGroup}[a.algo]([ag.policy for ag in agents])
@@ -264,6 +273,13 @@ def run_grouped(a):
         col.env.close()
 
 
+def prioritized_replay(a):
+    """--per-alpha / --per-beta / --per-no-weight-norm -> the agents' `prioritized_replay` dict, or None"""
+    if a.per_alpha is None:
+        return None
+    return dict(alpha=a.per_alpha, beta=a.per_beta, weight_norm=not a.per_no_weight_norm)
+
+
 def is_layered(hidden_sizes):
     """the engine's rule: anything but two hidden layers of at most 256 units makes a layered context"""
     return len(hidden_sizes) != 2 or max(hidden_sizes) > 256
@@ -287,7 +303,19 @@ def parse_args(argv=None):
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
                     help="--grouped --algo ppol: member i runs with value i (one per seed) of a PPOLagAgent keyword ("
                          + ", ".join(SWEEP_AGENT_KEYS) + ") or of " + " / ".join(SWEEP_UPDATE_KEYS) + "; repeatable")
+    ap.add_argument("--per-alpha", type=float, default=None, help="sacl / ddpgl: prioritised replay with this priority exponent")
+    ap.add_argument("--per-beta", type=float, default=None, help="... and this importance-weight exponent (with --per-alpha; default 0.4)")
+    ap.add_argument("--per-no-weight-norm", action="store_true", help="... without dividing the weights by the batch maximum (with --per-alpha)")
     a = ap.parse_args(argv)
+    if a.per_alpha is None and (a.per_beta is not None or a.per_no_weight_norm):
+        ap.error("--per-beta / --per-no-weight-norm: options of prioritised replay, which --per-alpha switches on")
+    if a.per_alpha is not None:
+        if a.algo not in ("sacl", "ddpgl"):
+            ap.error(f"--per-alpha: prioritised replay is built for sacl and ddpgl, not {a.algo}"
+                     + (": CVPO's update has no per-row TD error to hand back to the buffer" if a.algo == "cvpo" else ""))
+        a.per_beta = 0.4 if a.per_beta is None else a.per_beta
+        if a.per_alpha < 0 or a.per_beta < 0:
+            ap.error("--per-alpha / --per-beta: >= 0")
     if a.sweep and not (a.grouped and a.algo == "ppol"):
         ap.error("--sweep: PPO-Lagrangian groups only (--grouped --algo ppol); FOCOPS groups keep one set of hyper-parameters")
     try:
@@ -322,6 +350,8 @@ def main():
             kw = dict(epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, device_actor=True, verbose=False,
                       save_ckpt=False, show_progress=False)
             if a.algo in ("sacl", "ddpgl", "cvpo"):
+                if prioritized_replay(a) is not None:
+                    kw["prioritized_replay"] = prioritized_replay(a)
                 ep, stat, info = agent.learn(env, None, update_per_step=0.2, batch_size=256, **kw)
             else:
                 ep, stat, info = agent.learn(env, None, repeat_per_collect=4,

@@ -1530,6 +1530,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_cvpo.inc"
 
 #include "kernels_sac_group.hpp"
+#include "kernels_per_group.hpp"
 #include "host_sac_group.inc"
 #include "kernels_layered_sac_group.hpp"
 #include "kernels_cvpo_group.hpp"

@@ -1,10 +1,11 @@
-// host_per.inc -- prioritised experience replay for solo SAC-Lag / DDPG-Lag contexts: fsrl_per_* (part of fsrl_hip.hip, included by
-// host_sac.inc behind SacState).  The sum tree lives in HBM next to the store (kernels_per.hpp); nothing of a sample, a weight or a
+// host_per.inc -- prioritised experience replay for SAC-Lag / DDPG-Lag contexts: fsrl_per_* (part of fsrl_hip.hip, included by
+// host_sac.inc behind SacState; a group of prioritised members: host_sac_group.inc).  The sum tree lives in HBM next to the store (kernels_per.hpp); nothing of a sample, a weight or a
 // TD error crosses the bus inside an update.
 //   who writes the tree          on which stream
 //   rows reaching the store      side    (flush_stage, fsrl_store_fill: per_ingest / per_fill behind the row copies)
 //   fsrl_store_reset / configure side    (per_store_reset)
 //   an update's new priorities   compute (per_update_launch behind the critics' Q_TRAIN launch), fsrl_per_update_weight
+//   a grouped call's priorities  the group's stream, which the member's compute and side streams wait for (rgroup_end)
 // The side stream's writers wait for upd_done first -- the last update's priorities are in and max_prio is the value after it --
 // and the compute stream picks the side stream's work up through join_store, as it does the rows themselves.
 #include "kernels_per.hpp"
@@ -102,8 +103,8 @@ extern "C" int fsrl_per_enable(fsrl_ctx* c, double alpha, double beta, int32_t w
     if (!s) return fail(FSRL_ESTATE, "prioritised replay: fsrl_sac_init first (SAC-Lagrangian and DDPG-Lagrangian contexts)");
     CHECK_ARG(!s->cvpo, "prioritised replay is not built for CVPO contexts: its update has no per-row TD error to hand back");
     CHECK_ARG(!c->sac_group && !c->cvpo_group,
-              "prioritised replay covers solo contexts: this one is already in a group of grouped updates (they draw every member's "
-              "sample inside shared launches)");
+              "this context is already in a group of grouped updates, whose members all have prioritised replay on or all off: "
+              "fsrl_per_enable before the group is made");
     CHECK_ARG(std::isfinite(alpha) && alpha >= 0.0 && std::isfinite(beta) && beta >= 0.0, "alpha and beta must be finite and >= 0");
     CHECK_ARG(!c->in_update, "fsrl_per_enable inside an update");
     ENTER_DEV(c);
@@ -148,23 +149,32 @@ static int per_alloc_batch(fsrl_ctx* c, int B) {
     p->cap_B = B;
     return 0;
 }
+// the weights' side of a sample of B rows, and the priorities' side of the update behind it (the solo launches below; a
+// prioritised group's member table, host_sac_group.inc)
+static PerBatch per_batch_args(const PerState* p, int B) {
+    PerBatch pb{};
+    pb.w = p->w; pb.wd = p->wd; pb.B = B; pb.weight_norm = p->weight_norm; pb.beta = p->beta;
+    return pb;
+}
+static PerUpd per_upd_args(const PerState* p, const SacState* s, int B) {
+    PerUpd u{};
+    u.idx = s->d_idx; u.q = s->QP; u.y = s->Y; u.ext = nullptr; u.td_out = p->td; u.B = B; u.n_q = s->n_q; u.pair_shift = s->n_q == 2 ? 0 : 1;
+    return u;
+}
 // the update's sample (draw: library RNG; otherwise the caller's indices are already in s->d_idx) and its importance weights
 static int per_sample_launch(fsrl_ctx* c, SacState* s, int B, bool draw, int64_t stored) {
     PerState* p = c->per;
     int rc = per_alloc_batch(c, B);
     if (rc) return rc;
     const SacSampleArgs sa = sac_sample_args(c, s, B, s->cfg.n_step, stored, s->n_updates);
-    PerBatch pb{};
-    pb.w = p->w; pb.wd = p->wd; pb.B = B; pb.weight_norm = p->weight_norm; pb.beta = p->beta;
-    hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(PER_THREADS), 0, c->compute, sa, per_dev(p), pb, draw ? 1 : 0);
+    hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(PER_THREADS), 0, c->compute, sa, per_dev(p), per_batch_args(p, B), draw ? 1 : 0);
     HIPCHK(hipGetLastError());
     return 0;
 }
 // behind the critics' Q_TRAIN launch: the sampled rows' new priorities from the TD errors that launch used
 static int per_update_launch(fsrl_ctx* c, SacState* s, int B) {
     PerState* p = c->per;
-    PerUpd u{};
-    u.idx = s->d_idx; u.q = s->QP; u.y = s->Y; u.ext = nullptr; u.td_out = p->td; u.B = B; u.n_q = s->n_q; u.pair_shift = s->n_q == 2 ? 0 : 1;
+    const PerUpd u = per_upd_args(p, s, B);
     hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0, c->compute, per_dev(p), u);
     HIPCHK(hipGetLastError());
     return per_mark_update(c);

@@ -13,6 +13,13 @@
 // A DDPG-Lag group is the same nine launches with the DDPG context's arguments: n_q = 2 single critics (the Q grids, the small
 // weight-gradient grid, the split-K plan and the tile-height rule all take the group's n_q), the deterministic actor, the target
 // actor in the first half of the forward launch, and its Polyak update in the actor's Adam pass, where SAC-Lag steps alpha.
+// A group of PRIORITISED members (fsrl_per_enable on every one of them before the group is made; alpha, beta and weight_norm are
+// the member's own) runs fsrl_sac_update's prioritised sequence, thirteen launches whatever k is: per_sample_group (one workgroup
+// per member: the descent of its sum tree, its weights) -> gather -> the actors' forward with the fold off -> target Q -> the n-step
+// targets as a launch of their own -> Q_TRAIN with the member's weights -> per_update_group (one workgroup per member: its new
+// priorities) -> the rest as above.  Ordering: the group's stream is behind each member's compute stream, which has joined its
+// side stream and any per_ingest / per_fill on it; after the call both of the member's streams wait for `done`, and upd_done is
+// recorded behind that wait, so the side stream's next tree write follows the call's priorities (kernels_per_group.hpp).
 // ====================================================================================== grouped SAC-Lagrangian
 // ---- what the grouped SAC and CVPO updates share: the members, the group's stream and the events that order it against the
 //      members' streams (each group type embeds one as `core`), and further down the frame of one grouped call.
@@ -49,7 +56,8 @@ static void rgroup_detach(ReplayGroupCore& g, fsrl_ctx* c) {
 }
 // member c before a grouped call: its resident actor ends, its pushes land, its batch buffers and sub-buffer books are current
 static int rgroup_join(fsrl_ctx* c, int B) {
-    const int rc = replay_join(c, sac_of(c), B);
+    int rc = replay_join(c, sac_of(c), B);
+    if (!rc && c->per) rc = per_alloc_batch(c, B);         // a prioritised member: its weights and TD averages
     return rc ? rc : sac_upload_book(c, sac_of(c));
 }
 // the group's stream goes behind member i's stream; recorded once the member's table entry is built
@@ -143,7 +151,9 @@ static int rgroup_end(ReplayGroupCore& g, const ReplayGroupCall& call, int B, in
     HIPCHK(hipEventRecord(g.done, g.stream));
     for (int i = 0; i < call.k; ++i) {
         if (!call.work[i]) continue;
-        const int rc = rgroup_fanout(g, i);
+        int rc = rgroup_fanout(g, i);
+        // a prioritised member: the call's priorities are the last update's for the side stream's next tree write (per_side_enter)
+        if (!rc && g.m[i]->per) rc = per_mark_update(g.m[i]);
         if (rc) return rc;
         SacState* s = sac_of(g.m[i]);
         s->n_updates += call.n[i]; s->t_critic += call.n[i]; s->t_actor += (int64_t)call.n[i] * actor_steps;
@@ -182,7 +192,28 @@ struct fsrl_sac_group {
     DevTable<SacGroupMember> tab;              // [k]
     DevTable<SacGroupStep> steps;              // [updates][k]
     LaySacGroup* lay = nullptr;                // job and head tables of a layered group, made by its first update
+    DevTable<PerGroupMember> per;              // [k], a group of prioritised members: their tree arguments, rebuilt per call
+    DevTable<SacNstepArgs> per_na;             // [k], ... fused: the stand-alone n-step launch's (a layered group has its own)
 };
+// the members of a group agree on prioritised replay, and stay so: fsrl_sac_group_create checks it, fsrl_per_enable refuses a
+// context in a group, and nothing else switches it on or off
+static bool sac_group_per(const fsrl_sac_group* g) { return g->core.m[0] && g->core.m[0]->per; }
+// The tree arguments of every member with work, as its own per_sample_launch / per_update_launch would pass them: alpha, beta and
+// weight_norm are the member's as of this call, the buffers the ones its join left (rgroup_enter's build_tables step).
+static int per_group_table(fsrl_sac_group* g, const ReplayGroupCall& call, int B) {
+    const size_t k = (size_t)call.k;
+    const int rc = table_ensure(g->per, k, k);
+    if (rc) return rc;
+    memset(g->per.h, 0, k * sizeof(PerGroupMember));
+    for (int i = 0; i < call.k; ++i) {
+        if (!call.work[i]) continue;
+        fsrl_ctx* c = g->core.m[i];
+        PerGroupMember& m = g->per.h[i];
+        m.p = per_dev(c->per); m.pb = per_batch_args(c->per, B); m.u = per_upd_args(c->per, sac_of(c), B);
+    }
+    HIPCHK(hipMemcpyAsync(g->per.d, g->per.h, k * sizeof(PerGroupMember), hipMemcpyHostToDevice, g->core.stream));
+    return 0;
+}
 
 static void sac_group_detach(fsrl_ctx* c) {
     if (!c->sac_group) return;
@@ -194,7 +225,7 @@ extern "C" int fsrl_sac_group_destroy(fsrl_sac_group* g) {
     if (!g) return 0;
     for (fsrl_ctx* c : g->core.m) if (c) c->sac_group = nullptr;
     rgroup_destroy(g->core);
-    table_free(g->tab); table_free(g->steps);
+    table_free(g->tab); table_free(g->steps); table_free(g->per); table_free(g->per_na);
     lay_sac_group_free(g->lay);
     delete g;
     return 0;
@@ -210,8 +241,10 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
         CHECK_ARG(c, "null member");
         const SacState* s = reinterpret_cast<const SacState*>(c->sac);
         CHECK_ARG(c->cfg.algo == FSRL_ALGO_SAC_LAG && s, "member %d: grouped SAC updates take SAC-Lagrangian contexts (fsrl_sac_init)", i);
-        CHECK_ARG(!c->per, "member %d has prioritised replay on (fsrl_per_enable): it covers solo contexts only, a grouped update "
-                  "draws every member's sample inside shared launches", i);
+        if ((c->per != nullptr) != (c0->per != nullptr))
+            return fail(FSRL_EINVAL, "member %d has prioritised replay on and member %d does not: a group's members all have it on "
+                        "(fsrl_per_enable before the group is made; alpha, beta and weight_norm may differ) or all off", c->per ? i : 0,
+                        c->per ? 0 : i);
         CHECK_ARG(!s->cvpo, "member %d runs CVPO: grouped SAC updates take SAC-Lagrangian contexts only", i);
         const SacState* s0 = reinterpret_cast<const SacState*>(c0->sac);
         CHECK_ARG(s->layered == s0->layered, "member %d is a %s context and member 0 a %s one: a group is all fused (two hidden layers of at "
@@ -280,7 +313,8 @@ static int group_member_base(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B,
     t.PA = s->PA; t.MA = s->MA; t.VA = s->VA; t.PQ = s->PQ; t.PQT = s->PQT; t.MQ = s->MQ; t.VQ = s->VQ;
     member_adam_consts(t, c, tau);
     t.qf = sac_q_args(c, s, s->PQT, s->XN, FB_MODE_Q_FWD, 0.f, 0.f, s->stq, B, nullptr, s->n_tiles, nullptr);
-    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, s->n_tiles, &na);
+    // (a prioritised member's training launch reads its targets from Y: the stand-alone n-step launch runs, per_update reads them too)
+    t.qt = sac_q_args(c, s, s->PQ, s->XQ, FB_MODE_Q_TRAIN, 0.f, 0.f, s->stq, B, nullptr, s->n_tiles, c->per ? nullptr : &na);
     if (!small_wgrad) {
         const int rc = group_wgrad_split(c, s, t.fq, s->mdq, s->n_q, s->XQ, s->nq_dev, B, &t.GQ, nsplit_q);
         return rc ? rc : group_wgrad_split(c, s, t.fa, s->mda, 1, s->OBS, s->na_dev, B, &t.GA, nsplit_a);
@@ -313,7 +347,9 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
     const int det = s->ddpg ? 1 : 0;
     t.af = sac_actor_args(c, s, B, SAC_A_FWD, s->OBSN, s->eps_t, s->XN, s->LPN, resc, lam, det, 0);
     t.af.P2 = s->PA; t.af.obs2 = s->OBS; t.af.eps2 = s->eps_p; t.af.X2 = s->XP; t.af.lp2 = s->LP; t.af.tiles_half = f_r4 ? 4 * nt : nt;
-    t.af.sg_on = 1; t.af.ga = sac_gather_args(c, s, B, ns);
+    // a prioritised member's sample is per_sample_group's and its gather a launch of its own (weight_norm needs the whole batch's
+    // maximum before the first weight is used): the fold stays off, as in fsrl_sac_update
+    t.af.sg_on = c->per ? 0 : 1; t.af.ga = sac_gather_args(c, s, B, ns);
     t.ab = sac_actor_args(c, s, B, SAC_A_BWD, s->OBS, s->eps_p, s->XP, s->LP, resc, lam, det, 0);
     // ---- Q(s, a ~ pi) with the updated critics + dQ/da
     t.qd = sac_q_args(c, s, s->PQ, s->XP, FB_MODE_Q_DIN, 0.f, 0.f, s->stdin_, B, nullptr, nt, nullptr);
@@ -326,18 +362,22 @@ static int sac_group_member(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B, 
 // ---- the critic half of one grouped update, the same four launches for SAC and CVPO members: target Q-networks on (s_{t+n}, a'),
 //      the critics' forward + backward with their n-step targets, their weight gradients, their Adam with the Polyak targets.
 //      mdq_w: the ModelDesc of the small weight-gradient launch (its n_nets = the networks the launch covers)
-struct ReplayGroupCritic { int k, n_q, qt, rp, gq, nq_dev, nsq; bool q_r4, small_wgrad; };
+//      per != NULL (a group of prioritised members): the n-step targets as a launch of their own (na) before the training launch,
+//      and behind it the sampled rows' new priorities
+struct ReplayGroupCritic {
+    int k, n_q, qt, rp, gq, nq_dev, nsq; bool q_r4, small_wgrad;
+    const PerGroupMember* per = nullptr; const SacNstepArgs* na = nullptr; int B = 0;
+};
 template <int HH>
 static void rgroup_critic_half(hipStream_t gs, const ReplayGroupCritic& p, const ModelDesc& mdq, const ModelDesc& mdq_w,
                                const SacGroupMember* tab, const SacGroupStep* st) {
     const int k = p.k, n_q = p.n_q, qt = p.qt;
-    if (p.q_r4) {
-        hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-        hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-    } else {
-        hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-        hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
-    }
+    if (p.q_r4) hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+    else hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 0>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+    if (p.per) hipLaunchKernelGGL(sac_nstep_group_kernel, dim3((p.B + 255) / 256, k), dim3(256), 0, gs, p.na, st);
+    if (p.q_r4) hipLaunchKernelGGL((sac_q_group_kernel<HH, 4, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+    else hipLaunchKernelGGL((sac_q_group_kernel<HH, 16, 1>), dim3(qt, n_q, k), dim3(4 * HH), 0, gs, mdq, tab, st);
+    if (p.per) hipLaunchKernelGGL(per_update_group_kernel, dim3(k), dim3(PER_THREADS), 0, gs, p.per, st);
     if (p.small_wgrad) hipLaunchKernelGGL((sac_wgrad_group_kernel<HH, 0>), dim3(wg_grid(HH, n_q), k), dim3(1024), 0, gs, mdq_w, tab, st, p.rp);
     else hipLaunchKernelGGL((sac_wgrad_split_group_kernel<HH, 0>), dim3(p.gq, k), dim3(1024), 0, gs, mdq, tab, st);
     hipLaunchKernelGGL(sac_adam_group_kernel, dim3((p.nq_dev + 255) / 256, k), dim3(256), 0, gs, mdq, tab, st, p.nq_dev, p.nsq, p.nq_dev);
@@ -371,7 +411,17 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
     const bool small_wgrad = rp <= 512 && !s0->wgrad_splitk;
     const size_t lag_stride = (size_t)std::max(1, c0->cfg.n_critics - 1);
     int nsq = 1, nsa = 1, rq_total = 0, ra_total = 0;
+    const bool per_on = sac_group_per(g);
     rc = rgroup_enter(gc, g->steps, call, B, [&]() {
+        if (per_on) {
+            int rc = per_group_table(g, call, B);
+            if (!rc) rc = table_ensure(g->per_na, (size_t)k, (size_t)k);
+            if (rc) return rc;
+            memset(g->per_na.h, 0, (size_t)k * sizeof(SacNstepArgs));
+            for (int i = 0; i < k; ++i)
+                if (call.work[i]) g->per_na.h[i] = sac_nstep_args(gc.m[i], sac_of(gc.m[i]), B);
+            HIPCHK(hipMemcpyAsync(g->per_na.d, g->per_na.h, (size_t)k * sizeof(SacNstepArgs), hipMemcpyHostToDevice, gc.stream));
+        }
         for (int i = 0; i < k; ++i) {
             if (!call.work[i]) continue;
             // the member's own side-stream prefetch writes the other set of batch buffers only: nothing to wait for
@@ -395,10 +445,17 @@ extern "C" int fsrl_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t
         constexpr int HH = decltype(hc)::value;
         const int ft = f_r4 ? 4 * nt : nt, qt = q_r4 ? 4 * nt : nt, at = a_r4 ? 4 * nt : nt;
         const int ga = round_up(ra_total, 8);
-        const ReplayGroupCritic cr{k, n_q, qt, rp, round_up(rq_total, 8), s0->nq_dev, nsq, q_r4, small_wgrad};
+        ReplayGroupCritic cr{k, n_q, qt, rp, round_up(rq_total, 8), s0->nq_dev, nsq, q_r4, small_wgrad};
+        if (per_on) { cr.per = g->per.d; cr.na = g->per_na.d; cr.B = B; }
+        const int gather_blocks = std::min(1024, (B * (c0->cfg.obs_dim + c0->cfg.act_dim) + 255) / 256);
         for (int u = 0; u < n_max; ++u) {
             const SacGroupStep* st = g->steps.d + (size_t)u * k;
-            // 1. both actors' forward, the sample drawn and gathered inside
+            // a group of prioritised members: the descent of each member's sum tree with its weights, then the plain gather
+            if (per_on) {
+                hipLaunchKernelGGL(per_sample_group_kernel, dim3(k), dim3(PER_THREADS), 0, gs, g->per.d, st);
+                hipLaunchKernelGGL(sac_gather_group_kernel, dim3(gather_blocks, k), dim3(256), 0, gs, &tab->af.ga, sizeof(SacGroupMember), st);
+            }
+            // 1. both actors' forward, the sample drawn and gathered inside (prioritised: drawn and gathered above)
             if (f_r4) hipLaunchKernelGGL((sac_actor_group_kernel<HH, 4, SAC_A_FWD>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, tab, st);
             else hipLaunchKernelGGL((sac_actor_group_kernel<HH, 16, SAC_A_FWD>), dim3(2 * ft, k), dim3(4 * HH), 0, gs, mda, tab, st);
             // 2. - 5. the critic half

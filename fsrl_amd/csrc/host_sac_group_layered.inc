@@ -8,10 +8,13 @@
 //            and the heads' arguments sit in device tables, built once per grouped call after every member has joined (a join may
 //            regrow a member's working set and move its buffers); the list of launches (`prog`) is built with them.
 //            Bit-identical to the member's own fsrl_sac_update: see kernels_layered_sac_group.hpp.
+//            A group of prioritised members (host_sac_group.inc): per_sample_group + gather in place of sample + gather, and
+//            per_update_group behind the training Q head, whose rows carry the members' weights: 9 L + 21 launches.
 //   collect: no resident kernel -- lay_group_collect_post's staging (host_layered_group.inc) with the members' actor parameters
 //            SacState::PA and lay_raw_out_group_kernel as the last launch: L + 2 launches per vector step instead of k (L + 2).
 enum { LSG_LIN, LSG_SAMPLE, LSG_NSTEP, LSG_AHEAD, LSG_QHEAD, LSG_ADAM_Q, LSG_ADAM_A,
-       LSG_CVPO_SAMPLE, LSG_CVPO_AHEAD, LSG_CVPO_ESTEP, LSG_CVPO_MDUAL, LSG_CVPO_ADAM_A };     // host_cvpo_group_layered.inc
+       LSG_CVPO_SAMPLE, LSG_CVPO_AHEAD, LSG_CVPO_ESTEP, LSG_CVPO_MDUAL, LSG_CVPO_ADAM_A,      // host_cvpo_group_layered.inc
+       LSG_PER_UPDATE };                       // a group of prioritised members: the new priorities behind the training Q head
 struct LaySacOp {
     int kind;
     int form = 0, nw = 4, gx = 1, gy = 1, n = 0, which = 0;     // LSG_LIN: the launch; heads: which of the three argument rows
@@ -197,6 +200,7 @@ static int lay_sac_group_tables(fsrl_sac_group* g, LaySacGroup& lg, int B, const
     pg.op(LSG_NSTEP);
     pg.fwd(false, B, [&](int i) { return S(i)->PQ; }, [&](int i) { return S(i)->XQ; });
     pg.op(LSG_QHEAD, 1, tiles);
+    if (sac_group_per(g)) pg.op(LSG_PER_UPDATE);       // reads the Q values and targets that head just used
     pg.bwd(false, B, [&](int i) { return S(i)->PQ; }, false);
     pg.wgrad(false, B, [&](int i) { return S(i)->XQ; });
     pg.op(LSG_ADAM_Q);
@@ -258,13 +262,18 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
     if (n_max == 0) return 0;
     if (!g->lay) g->lay = new LaySacGroup();
     LaySacGroup& lg = *g->lay;
-    rc = rgroup_enter(gc, g->steps, call, B, [&]() { return lay_sac_group_tables(g, lg, B, call.work, lagrangians, rescaling); },
+    const bool per_on = sac_group_per(g);
+    rc = rgroup_enter(gc, g->steps, call, B, [&]() {
+        const int rc = per_on ? per_group_table(g, call, B) : 0;
+        return rc ? rc : lay_sac_group_tables(g, lg, B, call.work, lagrangians, rescaling);
+    },
                       [](int u, int, SacGroupStep& st, const fsrl_ctx* c, const SacState* s) { sac_group_step_row(u, st, c, s); });
     if (rc) return rc;
     hipStream_t gs = gc.stream;
     HIPCHK(hipMemcpyAsync(g->steps.d, g->steps.h, (size_t)n_max * k * sizeof(SacGroupStep), hipMemcpyHostToDevice, gs));
     const ModelDesc mda = s0->mda;
     const int na_dev = s0->na_dev;
+    const int gather_blocks = std::min(1024, (B * (gc.m[0]->cfg.obs_dim + gc.m[0]->cfg.act_dim) + 255) / 256);
     const SacGroupMember* tab = g->tab.d;
     for (int u = 0; u < n_max; ++u) {
         const SacGroupStep* st = g->steps.d + (size_t)u * k;
@@ -272,7 +281,13 @@ static int lay_sac_group_update(fsrl_sac_group* g, int32_t B, const int32_t* n_u
             if (lay_replay_group_launch(op, gs, s0, B, k, lg.jobs.d, lg.qh.d, lg.na.d, tab, st)) continue;
             switch (op.kind) {
             case LSG_SAMPLE:
-                hipLaunchKernelGGL(sac_sample_gather_group_kernel, dim3((B + SG_ROWS - 1) / SG_ROWS, k), dim3(256), 0, gs, lg.ga.d, st);
+                if (per_on) {       // the descent of each member's sum tree with its weights, then the plain gather
+                    hipLaunchKernelGGL(per_sample_group_kernel, dim3(k), dim3(PER_THREADS), 0, gs, g->per.d, st);
+                    hipLaunchKernelGGL(sac_gather_group_kernel, dim3(gather_blocks, k), dim3(256), 0, gs, lg.ga.d, sizeof(SacGatherArgs), st);
+                } else hipLaunchKernelGGL(sac_sample_gather_group_kernel, dim3((B + SG_ROWS - 1) / SG_ROWS, k), dim3(256), 0, gs, lg.ga.d, st);
+                break;
+            case LSG_PER_UPDATE:
+                hipLaunchKernelGGL(per_update_group_kernel, dim3(k), dim3(PER_THREADS), 0, gs, g->per.d, st);
                 break;
             case LSG_AHEAD:
                 hipLaunchKernelGGL(lay_sac_actor_head_group_kernel, dim3(op.gx, k), dim3(256), 0, gs, lg.ah.d + (size_t)op.which * k, st);

@@ -106,10 +106,11 @@ struct PerBatch {
     int B, weight_norm;
     double beta;
 };
-__global__ __launch_bounds__(PER_THREADS) void per_sample_kernel(const SacSampleArgs a, const PerDev p, const PerBatch pb, const int draw) {
-    constexpr int BOOK_LDS = 512;
-    __shared__ SacBook book_s[BOOK_LDS];
-    __shared__ double red[PER_THREADS];
+#define PER_BOOK_LDS 512
+// the body of per_sample_kernel and of per_sample_group_kernel (kernels_per_group.hpp); book_s[PER_BOOK_LDS], red[PER_THREADS]: LDS
+__device__ __forceinline__ void per_sample_body(const SacSampleArgs& a, const PerDev& p, const PerBatch& pb, const int draw,
+                                                SacBook* book_s, double* red) {
+    constexpr int BOOK_LDS = PER_BOOK_LDS;
     const int tid = threadIdx.x, nt = blockDim.x;
     if (draw) {
         const bool in_lds = a.env_num <= BOOK_LDS;
@@ -151,6 +152,11 @@ __global__ __launch_bounds__(PER_THREADS) void per_sample_kernel(const SacSample
     if (pb.weight_norm) mx = per_block_extreme<true>(mx, red);
     for (int b = tid; b < pb.B; b += nt) pb.w[b] = (float)(pb.weight_norm ? pb.wd[b] / mx : pb.wd[b]);
 }
+__global__ __launch_bounds__(PER_THREADS) void per_sample_kernel(const SacSampleArgs a, const PerDev p, const PerBatch pb, const int draw) {
+    __shared__ SacBook book_s[PER_BOOK_LDS];
+    __shared__ double red[PER_THREADS];
+    per_sample_body(a, p, pb, draw, book_s, red);
+}
 
 // ---- PrioritizedReplayBuffer.update_weight, ONE workgroup.  ext == NULL: behind the critics' Q_TRAIN launch, td_avg of row b =
 //      the float32 mean over the n_q networks of Q_j - y (critics_loss's td_average: summed in network order, then divided), kept in
@@ -164,8 +170,8 @@ struct PerUpd {
     float* td_out;       // [B] (ext == NULL)
     int B, n_q, pair_shift;
 };
-__global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const PerDev p, const PerUpd u) {
-    __shared__ double red[PER_THREADS];
+// the body of per_update_kernel and of per_update_group_kernel (kernels_per_group.hpp); red[PER_THREADS]: LDS
+__device__ __forceinline__ void per_update_body(const PerDev& p, const PerUpd& u, double* red) {
     const int tid = threadIdx.x, nt = blockDim.x;
     auto slot_of = [&](int b) {
         const int s = u.idx[b];
@@ -202,4 +208,8 @@ __global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const PerDev p,
     if (tid == 0 && u.B > 0) { p.sc[0] = fmax(p.sc[0], mx); p.sc[1] = fmin(p.sc[1], mn); }
     __syncthreads();
     per_repair(p, u.B, slot_of);
+}
+__global__ __launch_bounds__(PER_THREADS) void per_update_kernel(const PerDev p, const PerUpd u) {
+    __shared__ double red[PER_THREADS];
+    per_update_body(p, u, red);
 }

@@ -12,7 +12,8 @@
 #define FSRL_SAC_NSTATS_K 10
 
 // (SacGatherArgs, the sampler's structs and device functions: kernels_sample.hpp)
-__global__ void sac_gather_kernel(const SacGatherArgs a) {
+// grid-strided over blockIdx.x: the body of sac_gather_kernel and of sac_gather_group_kernel (kernels_per_group.hpp)
+__device__ __forceinline__ void sac_gather_body(const SacGatherArgs a) {
     const int Din = a.Do + a.Da;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.B * Din; e += gridDim.x * blockDim.x) {
         const int r = e / Din, f = e - r * Din;
@@ -26,6 +27,7 @@ __global__ void sac_gather_kernel(const SacGatherArgs a) {
         }
     }
 }
+__global__ void sac_gather_kernel(const SacGatherArgs a) { sac_gather_body(a); }
 
 __global__ __launch_bounds__(256) void sac_sample_kernel(const SacSampleArgs a) {
     // SAC / DDPG: one thread per sampled row.  CVPO (eps_k != NULL): B * K threads, thread (b, kp) also draws particle

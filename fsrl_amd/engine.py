@@ -672,7 +672,7 @@ class Engine:
         _lib.check(self.lib.fsrl_sac_last_chain(self._ctx, _ptr(ch, _i64p), _ptr(end, _u8p), int(batch_size)))
         return ch, end
 
-    # ---------------------------------------------------------------- prioritised replay (solo SAC-Lag / DDPG-Lag contexts)
+    # ---------------------------------------------------------------- prioritised replay (SAC-Lag / DDPG-Lag contexts, solo or grouped)
     def per_enable(self, alpha, beta, weight_norm=True):
         """tianshou PrioritizedReplayBuffer's sum tree over this context's store, on the device (include/fsrl_hip.h)"""
         _lib.check(self.lib.fsrl_per_enable(self._ctx, float(alpha), float(beta), int(bool(weight_norm))))
@@ -1179,7 +1179,11 @@ class EngineSacGroup(_NativeGroup):
     collect_step with the resident actor, sac_get_params, sac_drain ...).
     The members are all fused (two hidden layers of at most 256 units) or all layered contexts of one `hidden_sizes` and
     `force_layered`: a layered group runs the layered update's launch sequence with every member in each launch, and a member's
-    grouped update is then bit-identical to its own sac_update at every group size."""
+    grouped update is then bit-identical to its own sac_update at every group size.
+    Prioritised replay (per_enable) is on for every member or for none, switched on BEFORE the group is made; alpha, beta and
+    weight_norm may differ.  A grouped update of prioritised members draws each member's batch from its own sum tree and writes its
+    new priorities back inside the shared launches; per_state / per_last_weights / per_last_td / sac_last_sample then answer for
+    the member's last update of the call."""
     _symbols = "fsrl_sac_group"
 
     def update(self, batch_size, n_updates, lagrangians=None, rescalings=None):

@@ -2,7 +2,9 @@
 step on one MI355X -- `fsrl_sac_group_update`, every launch of an update carrying all members.  Per member,
 `SACPolicyGroup.update(buffers, batch_size, n_updates)` is what OffpolicyTrainer.policy_update_fn does between pre_update_fn and
 post_update_fn: n_i calls of `policy.update(batch_size, buffer)` -- same lambda and rescaling, same Philox stream, same statistics
-rows, same lr_scheduler steps.
+rows, same lr_scheduler steps.  The policies' buffers may be `HipPrioritizedVectorReplayBuffer`s (all of them, made before the
+group; alpha, beta and weight_norm may differ): the grouped update then draws every member's batch from its sum tree, weights its
+critics' loss and writes its new priorities back inside the shared launches, as n_i prioritised `policy.update` calls would.
 
     group = SACPolicyGroup([agent.policy for agent in agents])
     ... every agent collects into ITS buffer (its own resident device actor), steps ITS PID multiplier (pre_update_fn) ...
@@ -33,6 +35,9 @@ class ReplayPolicyGroup:
         # reference_rng=True draws the sample and the noise from the host's numpy / torch streams, one update at a time: a grouped
         # update has the device's Philox streams only
         assert not any(getattr(p, "_reference_rng", False) for p in self.policies), "reference_rng policies cannot be grouped"
+        # prioritised replay (the policies' HipPrioritizedVectorReplayBuffers, made before the group): on every member or on none
+        per = [bool(getattr(p.engine, "per_on", False)) for p in self.policies]
+        assert all(per) or not any(per), "grouped updates: every policy's buffer is a HipPrioritizedVectorReplayBuffer, or none is"
         self.group = engine_group if engine_group is not None else self._make_group([p.engine for p in self.policies])
 
     def _make_group(self, engines):

@@ -618,7 +618,7 @@ int fsrl_sac_last_sample(fsrl_ctx* ctx, int64_t* indices, float* eps_target, flo
 /* ... and its n-step chains [n_step][batch_size] with their end bits (done | unfinished tail), as the update used them. */
 int fsrl_sac_last_chain(fsrl_ctx* ctx, int64_t* chain_out, uint8_t* end_out, int32_t batch_size);
 
-/* ---- Prioritised experience replay for solo SAC-Lagrangian / DDPG-Lagrangian contexts (fused or layered): tianshou 0.5
+/* ---- Prioritised experience replay for SAC-Lagrangian / DDPG-Lagrangian contexts (fused or layered), solo or grouped: tianshou 0.5
  *      PrioritizedReplayBuffer / SegmentTree, which the reference reaches through critics_loss's batch.weight (sac_lag.py:189-201,
  *      ddpg_lag.py:170-179), learn's `batch.weight = td` (sac_lag.py:263, ddpg_lag.py:218) and post_process_fn's
  *      buffer.update_weight (base_policy.py:326-330).  One float64 sum tree over the whole store lives in HBM: 2 * bound nodes, bound
@@ -638,8 +638,13 @@ int fsrl_sac_last_chain(fsrl_ctx* ctx, int64_t* chain_out, uint8_t* end_out, int
  *                                         batch position wins); max_prio = max(max_prio, max p), min_prio = min(min_prio, min p)
  *      A prioritised update draws its sample in a launch of its own, gathers in a second and computes the n-step targets in a third
  *      (the folds into other launches are off, and so is the sample drawn one update ahead: the next sample depends on this
- *      update's priorities).  Refused, with the reason in fsrl_last_error: CVPO contexts, a context that is a member of a SAC / CVPO group
- *      (and fsrl_sac_group_create / fsrl_cvpo_group_create refuse a member with prioritised replay on).
+ *      update's priorities).  Refused, with the reason in fsrl_last_error: CVPO contexts and fsrl_cvpo_group_create over a member that
+ *      has it on; fsrl_per_enable on a context that is already in a SAC / CVPO group.
+ *      Groups: fsrl_sac_group_create takes members that ALL have prioritised replay on (alpha, beta and weight_norm may differ) or all
+ *      off, and names the two members that disagree otherwise.  fsrl_sac_group_update over prioritised members runs the same sequence
+ *      with every member in each launch (one workgroup per member draws its sample and one writes its priorities; 13 launches per
+ *      update for fused members whatever the group size) and leaves each member -- tree, last sample, chain, weights, TD averages --
+ *      as its own fsrl_sac_update calls would.
  *      fsrl_per_enable         switches it on (again: from scratch); rows already stored get max_prio ** alpha = 1.
  *      fsrl_per_set_beta       the exponent of the NEXT sample's weights (PrioritizedReplayBuffer.set_beta).
  *      fsrl_per_update_weight  PrioritizedReplayBuffer.update_weight(indices, weights) from the host, n entries; waits.

@@ -11,7 +11,13 @@ engines (the default shape is also the reference's ddpgl_cfg.py).
 whose grouped update is the layered launch sequence with every member in each launch, bit-identical per member to its own update).
 
     python tools/bench_group_sac.py --hidden 256x256x256 --shapes default --repeats 3
-    python tools/bench_group_sac.py --algo ddpgl --hidden 64x48x32 --shapes default --repeats 3"""
+    python tools/bench_group_sac.py --algo ddpgl --hidden 64x48x32 --shapes default --repeats 3
+
+--per ALPHA,BETA: every context has prioritised replay on (fsrl_per_enable after the fill, weight_norm on): the grouped mode then runs
+the grouped prioritised update (the solo prioritised sequence once per update for all members, 13 launches for fused members), the
+threaded mode k solo prioritised contexts, the solo mode one.  --rows shrinks the stores (and with them the sum trees' depth).
+
+    python tools/bench_group_sac.py --per 0.6,0.4 --shapes configs3 --repeats 3"""
 import argparse
 import json
 import os
@@ -29,7 +35,7 @@ SHAPES = {
 }
 
 
-def _engine(sh, seed, algo="sacl", hidden=None):
+def _engine(sh, seed, algo="sacl", hidden=None, prio=None):
     import torch
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
@@ -52,6 +58,8 @@ def _engine(sh, seed, algo="sacl", hidden=None):
         a = rng.uniform(-1, 1, (n, E, sh["act"])).astype(np.float32)
         for t in range(n):
             eng.push(ids, o[t], a[t], np.full(E, 0.5), np.zeros(E), np.zeros(E, bool), np.full(E, (t0 + t + 1) % 1000 == 0), o[t])
+    if prio:
+        eng.per_enable(prio[0], prio[1], True)
     eng.sac_update(sh["B"], [0.3], 1 / 1.3, seed=seed + 1, sync=False)       # key + warm-up
     eng.sac_drain()
     return eng
@@ -62,11 +70,11 @@ def _sync(engs):
         e.sac_get_params(0)
 
 
-def run(shape, k, mode, updates, algo="sacl", hidden=None):
+def run(shape, k, mode, updates, algo="sacl", hidden=None, per=None, rows=None):
     from fsrl_amd.engine import EngineSacGroup
-    sh = SHAPES[shape]
+    sh = dict(SHAPES[shape], **({"rows": rows} if rows else {}))
     B = sh["B"]
-    engs = [_engine(sh, 10 + i, algo, hidden) for i in range(1 if mode == "solo" else k)]
+    engs = [_engine(sh, 10 + i, algo, hidden, per) for i in range(1 if mode == "solo" else k)]
     per_call = 50
     if mode == "grouped":
         g = EngineSacGroup(engs)
@@ -107,7 +115,7 @@ def run(shape, k, mode, updates, algo="sacl", hidden=None):
         total = updates * len(engs)
     for e in engs:
         e.close()
-    return dict(algo=algo, shape=shape, k=k, mode=mode, batch=B, hidden="x".join(str(w) for w in hidden) if hidden else sh["H"], updates=total, seconds=round(dt, 4),
+    return dict(algo=algo, shape=shape, k=k, mode=mode, batch=B, **({"per": list(per), "rows": sh["rows"]} if per else {}), hidden="x".join(str(w) for w in hidden) if hidden else sh["H"], updates=total, seconds=round(dt, 4),
                 updates_per_s=round(total / dt, 1), us_per_member_update=round(dt / total * 1e6, 2))
 
 
@@ -121,7 +129,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=1, help="alternate the modes this many times on the same box")
     ap.add_argument("--hidden", default=None, type=lambda t: tuple(int(w) for w in t.lower().split("x")),
                     help="hidden layers instead of the shape's, e.g. 256x256x256 or 64x48x32 (layered members)")
+    ap.add_argument("--per", default=None, metavar="ALPHA,BETA", type=lambda t: tuple(float(x) for x in t.split(",")),
+                    help="prioritised replay on every context with these exponents (weight_norm on)")
+    ap.add_argument("--rows", type=int, default=None, help="rows of every store instead of the shape's")
     a = ap.parse_args()
+    if a.per is not None and len(a.per) != 2:
+        ap.error("--per ALPHA,BETA")
     ks = [int(x) for x in a.ks.split(",")]
     for shape in a.shapes.split(","):
         for k in ks:
@@ -129,7 +142,7 @@ def main():
                 for mode in a.modes.split(","):
                     if mode == "solo" and k != ks[0]:
                         continue                            # one context alone: measured once per shape
-                    print(json.dumps(run(shape, k, mode, a.updates, a.algo, a.hidden)), flush=True)
+                    print(json.dumps(run(shape, k, mode, a.updates, a.algo, a.hidden, a.per, a.rows)), flush=True)
 
 
 if __name__ == "__main__":
