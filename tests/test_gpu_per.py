@@ -30,13 +30,17 @@ NOISE_BOUND = 8.0 * 2.0**-24            # tests/test_gpu_sampler.py: |device - f
 
 
 class Rig:
-    """a replay context of `kind` on store `name`, the mirror of its rows, the oracle with the same parameters"""
+    """a replay context of `kind` on store `name`, the mirror of its rows, the oracle with the same parameters; `name` is a key of
+    test_per_model.STORES, or a geometry with a rollout of its own (.name, .E, .sub, .rollout(): tests/per_big_problems.py)"""
 
     def __init__(self, name, kind="sac", hidden=(64, 64), n_step=2, per=(ALPHA, BETA, True), fill=True, enable_first=True):
         from fsrl_amd import _lib
         from fsrl_amd.engine import Engine, EngineConfig
-        self.name, self.kind, self.n_step = name, kind, n_step
-        self.E, self.sub, _ = STORES[name]
+        self.kind, self.n_step = kind, n_step
+        if isinstance(name, str):
+            self.name, (self.E, self.sub, _), steps = name, STORES[name], lambda: rollout(name)
+        else:
+            self.name, self.E, self.sub, steps = name.name, name.E, name.sub, name.rollout
         self.oracle, a, c = make_oracle(kind, hidden, n_step)
         ocfg = self.oracle.cfg
         self.eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, obs_dim=OBS_DIM, act_dim=ACT_DIM, hidden_sizes=tuple(hidden), n_critics=2,
@@ -54,7 +58,7 @@ class Rig:
             if per and enable_first:
                 self.eng.per_enable(*per)
             if fill:
-                for step in rollout(name):
+                for step in steps():
                     self.push(step)
             if per and not enable_first:
                 self.eng.per_enable(*per)
