@@ -6,6 +6,8 @@ installed pass real vector envs exposing reset(ids) / step(act, ids) -> (obs, re
     python examples/train_agent.py --algo ppol --epoch 3
     python examples/train_agent.py --algo sacl --epoch 2 --device-actor
     python examples/train_agent.py --algo sacl --epoch 2 --prefill /tmp/dataset/dataset.npz     (examples/collect_dataset.py --out /tmp/dataset)
+    python examples/train_agent.py --algo ppol --epoch 3 --task device-point-circle    (envs on the GPU: whole collects in one looping kernel)
+    python examples/train_agent.py --algo cpo --epoch 3 --task device-linear
 """
 import argparse
 import os
@@ -36,8 +38,10 @@ def main():
     ap.add_argument("--batch-size", type=int, default=256, help="minibatch size of PPO-Lag / FOCOPS and the off-policy agents")
     ap.add_argument("--tr-batch-size", type=int, default=99999,
                     help="CPO / TRPO-Lag: Batch.split size inside learn (the reference's default 99999 = the whole buffer)")
-    ap.add_argument("--task", choices=["synthetic", "point-circle"], default="synthetic",
-                    help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories")
+    ap.add_argument("--task", choices=["synthetic", "point-circle", "device-point-circle", "device-linear"], default="synthetic",
+                    help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories; "
+                         "device-point-circle / device-linear: the same two envs as device functions (ppol, cpo, trpol, focops; at most 64 envs), "
+                         "collected by DeviceCollector")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
     # options of the on-policy agents (the reference's constructor arguments of the same names)
     ap.add_argument("--unbounded", action=argparse.BooleanOptionalAction, default=None,
@@ -56,7 +60,12 @@ def main():
         ap.error(f"--per-alpha: prioritised replay is built for sacl and ddpgl, not {a.algo}")
     if a.prefill is not None and a.algo not in ("sacl", "ddpgl", "cvpo"):
         ap.error(f"--prefill fills a replay store: --algo must be sacl, ddpgl or cvpo, not {a.algo}")
-    if a.task == "point-circle":
+    device_task = a.task.startswith("device-")
+    if device_task and a.algo not in ("ppol", "cpo", "trpol", "focops"):
+        ap.error(f"--task {a.task}: device collects serve the on-policy agents (ppol, cpo, trpol, focops), not {a.algo}")
+    if device_task and (a.envs > 64 or a.workers > 0):
+        ap.error("a device env holds at most 64 envs and needs no worker processes")
+    if a.task in ("point-circle", "device-point-circle"):
         # the reference's own construction (train_ppol_agent.py:120-123): one factory per env, in process or in worker processes
         from fsrl_amd.env import DummyVectorEnv, PointCircleEnv, ShmemVectorEnv
         fns = [lambda: PointCircleEnv(max_episode_steps=100) for _ in range(a.envs)]
@@ -67,7 +76,7 @@ def main():
         env = ShmemVectorEnv(env_num=a.envs, workers=a.workers, obs_dim=8, act_dim=2, episode_len=300, seed=a.seed)
     else:
         env = SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=a.seed)
-    if a.task != "point-circle":
+    if a.task not in ("point-circle", "device-point-circle"):
         test_env = SyntheticSafetyVectorEnv(env_num=2, obs_dim=8, act_dim=2, episode_len=300, seed=a.seed + 1)
     logger = BaseLogger(tempfile.mkdtemp(prefix="fsrl_amd_"), name=a.algo)
     kw = dict(cost_limit=a.cost_limit, device=a.device, seed=a.seed, hidden_sizes=(tuple(int(x) for x in a.hidden_sizes.split("x")) if a.hidden_sizes else (a.hidden, a.hidden)),
@@ -81,6 +90,11 @@ def main():
     if a.algo in ("ppol", "focops"):
         kw.update(recompute_advantage=a.recompute_advantage)
     agent = AGENTS[a.algo](env, logger, **kw)
+    if device_task:
+        # the host env above gave the agent its spaces; the training envs themselves live on the agent's GPU (evaluation keeps the host envs)
+        from fsrl_amd.env import DeviceLinear, DevicePointCircle
+        env = (DevicePointCircle(agent.policy, a.envs, max_episode_steps=100, seed=a.seed) if a.task == "device-point-circle"
+               else DeviceLinear(agent.policy, like=env, seed=a.seed))
     if a.algo in ("sacl", "ddpgl", "cvpo"):
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, update_per_step=0.2,
                           batch_size=a.batch_size, testing_num=2, device_actor=a.device_actor, verbose=True, save_ckpt=False,

@@ -65,6 +65,14 @@ class CvpoConfig(C.Structure):
                 ("actor_mean", C.c_int32)]
 
 
+class DevEnvConfig(C.Structure):
+    """struct fsrl_devenv_config (include/fsrl_hip.h)"""
+    _fields_ = [("kind", C.c_int32), ("env_num", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32),
+                ("max_episode_steps", C.c_int32), ("seed", C.c_uint64), ("p", C.c_float * 8), ("A", C.c_void_p), ("B", C.c_void_p)]
+
+
+DEVENV_POINT_CIRCLE, DEVENV_LINEAR = 0, 1
+
 # fsrl_sac_config / fsrl_cvpo_config .actor_mean: how the Gaussian actor's mean head becomes the mean
 ACTOR_MEAN_DEFAULT, ACTOR_MEAN_UNBOUNDED, ACTOR_MEAN_TANH = 0, 1, 2
 
@@ -228,6 +236,15 @@ SIGNATURES = {
     "fsrl_traj_counters": (C.c_int, [_ctx, _i64, C.c_int32]),
     "fsrl_traj_import": (C.c_int, [_ctx, C.c_int64, _f, _f, _f, _d, _d, _u8, _u8, C.c_int32, _i64, _i64]),
     "fsrl_store_fill": (C.c_int, [_ctx, _ctx, _i32, C.c_int64, C.c_int32, C.c_int32, _f, _f, _i64]),
+    "fsrl_devenv_create": (C.c_int, [_ctx, _P(DevEnvConfig), _P(_ctx)]),
+    "fsrl_devenv_destroy": (C.c_int, [_ctx]),
+    "fsrl_devenv_seed": (C.c_int, [_ctx, C.c_uint64]),
+    "fsrl_devenv_reset": (C.c_int, [_ctx, _i32, C.c_int32, _f]),
+    "fsrl_devenv_step": (C.c_int, [_ctx, _i32, C.c_int32, _f, _f, _d, _d, _u8, _u8]),
+    "fsrl_devenv_get_state": (C.c_int, [_ctx, _f, _i32, _i64]),
+    "fsrl_devenv_set_state": (C.c_int, [_ctx, _f, _i32, _i64]),
+    "fsrl_collect_device": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,
+                                      _i32, _i32]),
     "fsrl_set_profiling": (C.c_int, [_ctx, C.c_int]),
     "fsrl_last_timing": (C.c_int, [_ctx, _d, C.c_int32]),
 }

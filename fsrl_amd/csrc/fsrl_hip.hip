@@ -1418,6 +1418,7 @@ extern "C" int fsrl_nstep_return(fsrl_ctx* c, const double* metric, const uint8_
 }
 
 #include "host_collect.inc"
+#include "host_devcollect.inc"
 
 #include "host_ppo.inc"
 

@@ -1,0 +1,361 @@
+// host_devcollect.inc -- device environments and whole collects on the GPU (part of fsrl_hip.hip; include/fsrl_hip.h "Device environments").
+//
+// fsrl_devenv_reset / _step make a device env an ordinary vector env: one small launch on the env's OWN stream (so that a resident
+// actor on the compute stream keeps running: a launch behind it would wait for its idle timeout) over pinned host memory, and a wait.
+// fsrl_collect_device runs collect_device_kernel on the context's compute stream -- behind every update, in front of the next -- once
+// per max_steps_per_launch vector steps, reads the launch's DcState and log back and replays the log through the bookkeeping of
+// fsrl_store_push (devcollect_plan.hpp dc_replay_row: EnvBook, h_flags, store_version), so that the store, the episode statistics
+// and everything derived from them are as if the rows had been pushed one vector step at a time.
+#include "kernels_devcollect.hpp"
+
+struct fsrl_devenv {
+    fsrl_ctx* c = nullptr;
+    fsrl_devenv_config cfg{};
+    uint64_t key = 0;
+    hipStream_t es = nullptr;           // reset / step launches
+    DevEnvArrays ea{};
+    float *dA = nullptr, *dB = nullptr;
+    char* h_io = nullptr;               // pinned: ids | act | obs | rew | cost | flags, for env_num rows
+    DcState* d_state = nullptr; DcState* h_state = nullptr;     // device / pinned
+    DcLogRow* d_log = nullptr; DcLogRow* h_log = nullptr; int log_steps = 0;
+    DevCollectArgs* d_args = nullptr; DevCollectArgs* h_args = nullptr;     // the collect kernel's arguments: device / pinned
+};
+static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
+static DevEnvParams devenv_params(const fsrl_devenv* v) {
+    DevEnvParams P{};
+    P.kind = v->cfg.kind; P.env_num = v->cfg.env_num; P.Do = v->cfg.obs_dim; P.Da = v->cfg.act_dim; P.max_steps = v->cfg.max_episode_steps;
+    memcpy(P.p, v->cfg.p, sizeof(P.p));
+    P.A = v->dA; P.B = v->dB;
+    return P;
+}
+struct DevEnvIoLayout { int32_t* ids; float* act; float* obs; double* rew; double* cost; uint32_t* flags; };
+static DevEnvIoLayout devenv_io(const fsrl_devenv* v) {
+    const size_t n = (size_t)v->cfg.env_num, Do = (size_t)v->cfg.obs_dim, Da = (size_t)v->cfg.act_dim;
+    char* b = v->h_io;
+    DevEnvIoLayout l;
+    l.rew = (double*)b; l.cost = l.rew + n;
+    l.ids = (int32_t*)(l.cost + n); l.flags = (uint32_t*)(l.ids + n);
+    l.act = (float*)(l.flags + n); l.obs = l.act + n * Da;
+    (void)Do;
+    return l;
+}
+static size_t devenv_io_bytes(int n, int Do, int Da) { return (size_t)n * (8 + 8 + 4 + 4 + 4 * (size_t)(Do + Da)); }
+
+static void devenv_free(fsrl_devenv* v) {
+    if (!v) return;
+    if (v->es) { (void)hipStreamSynchronize(v->es); (void)hipStreamDestroy(v->es); }
+    if (v->ea.state) (void)hipFree(v->ea.state);
+    if (v->ea.obs) (void)hipFree(v->ea.obs);
+    if (v->ea.nxt) (void)hipFree(v->ea.nxt);
+    if (v->ea.t) (void)hipFree(v->ea.t);
+    if (v->ea.ordinal) (void)hipFree(v->ea.ordinal);
+    if (v->dA) (void)hipFree(v->dA);
+    if (v->dB) (void)hipFree(v->dB);
+    if (v->h_io) (void)hipHostFree(v->h_io);
+    if (v->d_state) (void)hipFree(v->d_state);
+    if (v->h_state) (void)hipHostFree(v->h_state);
+    if (v->d_log) (void)hipFree(v->d_log);
+    if (v->h_log) (void)hipHostFree(v->h_log);
+    if (v->d_args) (void)hipFree(v->d_args);
+    if (v->h_args) (void)hipHostFree(v->h_args);
+    delete v;
+}
+
+extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fsrl_devenv** out) {
+    CHECK_ARG(c && cfg && out, "null argument");
+    CHECK_ARG(cfg->kind == FSRL_DEVENV_POINT_CIRCLE || cfg->kind == FSRL_DEVENV_LINEAR, "kind %d: no such device env", cfg->kind);
+    CHECK_ARG(cfg->env_num >= 1 && cfg->env_num <= DC_MAX_ENVS, "env_num %d: a device env holds 1 .. %d envs", cfg->env_num, DC_MAX_ENVS);
+    CHECK_ARG(cfg->obs_dim == c->cfg.obs_dim && cfg->act_dim == c->cfg.act_dim,
+              "env shape (obs_dim %d, act_dim %d) != context shape (obs_dim %d, act_dim %d)", cfg->obs_dim, cfg->act_dim, c->cfg.obs_dim,
+              c->cfg.act_dim);
+    CHECK_ARG(cfg->act_dim >= 1 && cfg->act_dim <= FSRL_MAX_ACT, "act_dim %d above %d", cfg->act_dim, FSRL_MAX_ACT);
+    CHECK_ARG(cfg->max_episode_steps >= 1, "max_episode_steps must be >= 1");
+    if (cfg->kind == FSRL_DEVENV_POINT_CIRCLE) {
+        CHECK_ARG(cfg->obs_dim == 6 && cfg->act_dim == 2, "the point-circle env has obs_dim 6 and act_dim 2");
+    } else {
+        CHECK_ARG(cfg->obs_dim >= 2 && cfg->obs_dim <= DEVENV_STATE, "the linear env takes 2 <= obs_dim <= %d", DEVENV_STATE);
+        CHECK_ARG(cfg->A && cfg->B, "the linear env needs A[obs_dim][obs_dim] and B[act_dim][obs_dim]");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    fsrl_devenv* v = new fsrl_devenv();
+    v->c = c; v->cfg = *cfg; v->cfg.A = nullptr; v->cfg.B = nullptr;
+    v->key = devenv_key(cfg->seed);
+    const size_t n = (size_t)cfg->env_num, Do = (size_t)cfg->obs_dim, Da = (size_t)cfg->act_dim;
+    auto bail = [&](hipError_t e, const char* what) {
+        devenv_free(v);
+        return fail(FSRL_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+#define DEVENV_TRY(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return bail(_e, #expr); } while (0)
+    DEVENV_TRY(hipStreamCreateWithFlags(&v->es, hipStreamNonBlocking));
+    DEVENV_TRY(hipMalloc(&v->ea.state, n * DEVENV_STATE * 4));
+    DEVENV_TRY(hipMalloc(&v->ea.obs, n * Do * 4));
+    DEVENV_TRY(hipMalloc(&v->ea.nxt, n * Do * 4));
+    DEVENV_TRY(hipMalloc(&v->ea.t, n * 4));
+    DEVENV_TRY(hipMalloc(&v->ea.ordinal, n * 8));
+    DEVENV_TRY(hipMemset(v->ea.state, 0, n * DEVENV_STATE * 4));
+    DEVENV_TRY(hipMemset(v->ea.obs, 0, n * Do * 4));
+    DEVENV_TRY(hipMemset(v->ea.nxt, 0, n * Do * 4));
+    DEVENV_TRY(hipMemset(v->ea.t, 0, n * 4));
+    DEVENV_TRY(hipMemset(v->ea.ordinal, 0, n * 8));
+    if (cfg->kind == FSRL_DEVENV_LINEAR) {
+        DEVENV_TRY(hipMalloc(&v->dA, Do * Do * 4));
+        DEVENV_TRY(hipMalloc(&v->dB, Da * Do * 4));
+        DEVENV_TRY(hipMemcpy(v->dA, cfg->A, Do * Do * 4, hipMemcpyHostToDevice));
+        DEVENV_TRY(hipMemcpy(v->dB, cfg->B, Da * Do * 4, hipMemcpyHostToDevice));
+    }
+    DEVENV_TRY(hipHostMalloc(&v->h_io, devenv_io_bytes((int)n, (int)Do, (int)Da)));
+    DEVENV_TRY(hipMalloc(&v->d_state, sizeof(DcState)));
+    DEVENV_TRY(hipHostMalloc(&v->h_state, sizeof(DcState)));
+    DEVENV_TRY(hipMalloc(&v->d_args, sizeof(DevCollectArgs)));
+    DEVENV_TRY(hipHostMalloc(&v->h_args, sizeof(DevCollectArgs)));
+#undef DEVENV_TRY
+    *out = v;
+    return 0;
+}
+
+extern "C" int fsrl_devenv_destroy(fsrl_devenv* v) {
+    if (!v) return 0;
+    if (v->c) {
+        (void)hipSetDevice(v->c->device);
+        (void)hipStreamSynchronize(v->c->compute);      // a collect kernel reads the env's arrays
+    }
+    devenv_free(v);
+    return 0;
+}
+
+extern "C" int fsrl_devenv_seed(fsrl_devenv* v, uint64_t seed) {
+    CHECK_ARG(v, "null env");
+    HIPCHK(hipSetDevice(v->c->device));
+    HIPCHK(hipStreamSynchronize(v->es));
+    v->cfg.seed = seed;
+    v->key = devenv_key(seed);
+    HIPCHK(hipMemset(v->ea.ordinal, 0, (size_t)v->cfg.env_num * 8));
+    return 0;
+}
+
+// ids (or NULL) of a reset / step call, checked and copied into the pinned block
+static int devenv_take_ids(fsrl_devenv* v, const int32_t* ids, int32_t n, const DevEnvIoLayout& l) {
+    CHECK_ARG(n >= 0 && n <= v->cfg.env_num, "%d rows but the device env has %d envs", n, v->cfg.env_num);
+    if (!ids) return 0;
+    uint64_t seen = 0;
+    for (int i = 0; i < n; ++i) {
+        CHECK_ARG(ids[i] >= 0 && ids[i] < v->cfg.env_num, "env id %d out of range", ids[i]);
+        CHECK_ARG(!(seen >> ids[i] & 1ull), "env id %d is listed twice", ids[i]);
+        seen |= 1ull << ids[i];
+        l.ids[i] = ids[i];
+    }
+    return 0;
+}
+
+static int devenv_reset_launch(fsrl_devenv* v, const DevEnvIo& io, hipStream_t s) {
+    const DevEnvParams P = devenv_params(v);
+    const uint32_t k0 = (uint32_t)v->key, k1 = (uint32_t)(v->key >> 32);
+    devenv_dispatch(v->cfg.kind, [&](auto env) {
+        using Env = decltype(env);
+        hipLaunchKernelGGL(devenv_reset_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, s, P, v->ea, io, k0, k1);
+    });
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int fsrl_devenv_reset(fsrl_devenv* v, const int32_t* ids, int32_t n, float* obs_out) {
+    CHECK_ARG(v, "null env");
+    HIPCHK(hipSetDevice(v->c->device));       // keeps a resident actor alive
+    const DevEnvIoLayout l = devenv_io(v);
+    if (!ids && n <= 0) n = v->cfg.env_num;
+    int rc = devenv_take_ids(v, ids, n, l);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    DevEnvIo io{};
+    io.ids = ids ? l.ids : nullptr; io.obs = l.obs; io.n = n;
+    rc = devenv_reset_launch(v, io, v->es);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(v->es));
+    if (obs_out) memcpy(obs_out, l.obs, (size_t)n * v->cfg.obs_dim * 4);
+    return 0;
+}
+
+extern "C" int fsrl_devenv_step(fsrl_devenv* v, const int32_t* ids, int32_t n, const float* env_act, float* obs_next_out,
+                                double* rew_out, double* cost_out, uint8_t* term_out, uint8_t* trunc_out) {
+    CHECK_ARG(v && env_act && obs_next_out && rew_out && cost_out && term_out && trunc_out, "null argument");
+    HIPCHK(hipSetDevice(v->c->device));       // keeps a resident actor alive
+    const DevEnvIoLayout l = devenv_io(v);
+    if (!ids && n <= 0) n = v->cfg.env_num;
+    int rc = devenv_take_ids(v, ids, n, l);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    const int Do = v->cfg.obs_dim, Da = v->cfg.act_dim;
+    memcpy(l.act, env_act, (size_t)n * Da * 4);
+    DevEnvIo io{};
+    io.ids = ids ? l.ids : nullptr; io.act = l.act; io.obs = l.obs; io.rew = l.rew; io.cost = l.cost; io.flags = l.flags; io.n = n;
+    const DevEnvParams P = devenv_params(v);
+    const uint32_t k0 = (uint32_t)v->key, k1 = (uint32_t)(v->key >> 32);
+    devenv_dispatch(v->cfg.kind, [&](auto env) {
+        using Env = decltype(env);
+        hipLaunchKernelGGL(devenv_step_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea, io, k0, k1);
+    });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(v->es));
+    memcpy(obs_next_out, l.obs, (size_t)n * Do * 4);
+    for (int i = 0; i < n; ++i) {
+        rew_out[i] = l.rew[i]; cost_out[i] = l.cost[i];
+        term_out[i] = (uint8_t)(l.flags[i] & 1u); trunc_out[i] = (uint8_t)((l.flags[i] >> 1) & 1u);
+    }
+    return 0;
+}
+
+extern "C" int fsrl_devenv_get_state(fsrl_devenv* v, float* state_out, int32_t* t_out, int64_t* ordinal_out) {
+    CHECK_ARG(v, "null env");
+    HIPCHK(hipSetDevice(v->c->device));
+    HIPCHK(hipStreamSynchronize(v->es));
+    HIPCHK(hipStreamSynchronize(v->c->compute));
+    const int n = v->cfg.env_num, sd = devenv_state_dim(v->cfg.kind, v->cfg.obs_dim);
+    if (state_out)
+        HIPCHK(hipMemcpy2D(state_out, (size_t)sd * 4, v->ea.state, (size_t)DEVENV_STATE * 4, (size_t)sd * 4, (size_t)n, hipMemcpyDeviceToHost));
+    if (t_out) HIPCHK(hipMemcpy(t_out, v->ea.t, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (ordinal_out) HIPCHK(hipMemcpy(ordinal_out, v->ea.ordinal, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const int32_t* t, const int64_t* ordinal) {
+    CHECK_ARG(v, "null env");
+    HIPCHK(hipSetDevice(v->c->device));
+    HIPCHK(hipStreamSynchronize(v->es));
+    HIPCHK(hipStreamSynchronize(v->c->compute));
+    const int n = v->cfg.env_num, sd = devenv_state_dim(v->cfg.kind, v->cfg.obs_dim);
+    if (t) for (int e = 0; e < n; ++e) CHECK_ARG(t[e] >= 0, "t[%d] is negative", e);
+    if (ordinal) for (int e = 0; e < n; ++e) CHECK_ARG(ordinal[e] >= 0, "ordinal[%d] is negative", e);
+    if (state)
+        HIPCHK(hipMemcpy2D(v->ea.state, (size_t)DEVENV_STATE * 4, state, (size_t)sd * 4, (size_t)sd * 4, (size_t)n, hipMemcpyHostToDevice));
+    if (t) HIPCHK(hipMemcpy(v->ea.t, t, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (ordinal) HIPCHK(hipMemcpy(v->ea.ordinal, ordinal, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (state) {
+        const DevEnvParams P = devenv_params(v);
+        devenv_dispatch(v->cfg.kind, [&](auto env) {
+            using Env = decltype(env);
+            hipLaunchKernelGGL(devenv_observe_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea);
+        });
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(v->es));
+    }
+    return 0;
+}
+
+// ---- the collect.  Everything that can refuse the call is checked before anything is touched.
+static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
+                            const float* act_high, int32_t max_steps) {
+    CHECK_ARG(c && v, "null context / env");
+    CHECK_ARG(v->c == c, "the device env was created on another context");
+    CHECK_ARG(!ctx_is_replay(c), "device collects serve on-policy contexts; replay contexts (SAC-Lag, DDPG-Lag, CVPO) are not supported yet");
+    CHECK_ARG(!c->lay, "device collects are not supported on layered contexts yet");
+    CHECK_ARG(!c->group && !c->cgroup, "device collects are not supported on grouped contexts yet");
+    CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
+    if (c->in_update) return fail(FSRL_ESTATE, "fsrl_collect_device inside an update");
+    CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
+    CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
+    CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
+              v->cfg.obs_dim, v->cfg.act_dim);
+    CHECK_ARG(n_episode >= 1, "n_episode must be >= 1");
+    CHECK_ARG(bound_method >= 0 && bound_method <= 2, "bound_method: 0 none, 1 clip, 2 tanh");
+    CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
+    CHECK_ARG(max_steps <= DC_MAX_STEPS, "max_steps_per_launch %d above %d", max_steps, DC_MAX_STEPS);
+    CHECK_ARG(c->sub_size >= 1 && c->maxsize <= INT_MAX, "the store's geometry does not fit a device collect");
+    return 0;
+}
+
+extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                   const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                   double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                   int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    int rc = devcollect_check(c, v, n_episode, bound_method, act_low, act_high, max_steps_per_launch);
+    if (rc) return rc;
+    CHECK_ARG(steps_out && total_cost_out && term_count_out && trunc_count_out && ep_rew_out && ep_len_out && episodes_out, "null output");
+    const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
+    const int n = v->cfg.env_num, Da = v->cfg.act_dim;
+    ENTER_DEV(c);                                   // a live resident actor ends first
+    HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
+    rc = join_store(c);                             // rows in the staging window land first; the side stream is in front of the kernel
+    if (rc) return rc;
+    if (v->log_steps < max_steps) {
+        if (v->d_log) HIPCHK(hipFree(v->d_log));
+        if (v->h_log) HIPCHK(hipHostFree(v->h_log));
+        v->d_log = nullptr; v->h_log = nullptr; v->log_steps = 0;
+        HIPCHK(hipMalloc(&v->d_log, (size_t)max_steps * n * sizeof(DcLogRow)));
+        HIPCHK(hipHostMalloc(&v->h_log, (size_t)max_steps * n * sizeof(DcLogRow)));
+        v->log_steps = max_steps;
+    }
+    DcState& hs = *v->h_state;
+    memset(&hs, 0, sizeof(hs));
+    hs.n_live = dc_first_live(n, n_episode); hs.n_episode = n_episode;
+    for (int e = 0; e < DC_MAX_ENVS; ++e) hs.live[e] = e < n ? e : 0;
+    for (int e = 0; e < n; ++e) hs.index[e] = (int32_t)c->env[(size_t)e].index;
+    hipStream_t s = c->compute;
+    HIPCHK(hipMemcpyAsync(v->d_state, &hs, sizeof(DcState), hipMemcpyHostToDevice, s));
+    // the arguments travel through device memory: ~350 bytes of kernel arguments held in scalar registers next to tile_forward's own
+    // pushed the 256-wide kernel over its 128-VGPR cap (scalar spills live in vector registers)
+    DevCollectArgs& a = *v->h_args;
+    a = DevCollectArgs{};
+    a.ep = devenv_params(v); a.ea = v->ea; a.k0 = (uint32_t)v->key; a.k1 = (uint32_t)(v->key >> 32);
+    a.st = c->st; a.sub_size = c->sub_size; a.state = v->d_state; a.log = v->d_log; a.max_steps = max_steps;
+    a.deterministic = deterministic ? 1 : 0; a.bound_method = bound_method; a.scaled = act_low ? 1 : 0;
+    for (int d = 0; d < Da && act_low; ++d) { a.low[d] = act_low[d]; a.high[d] = act_high[d]; }
+    a.max_action = c->cfg.max_action;
+    a.magic_per = div_magic(2 * v->cfg.obs_dim + Da); a.magic_da = div_magic(Da);
+    HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));
+    int64_t rows = 0;
+    double total_cost = 0.0;
+    int32_t terms = 0, truncs = 0, episodes = 0, launches = 0;
+    // every launch that is not the last takes max_steps vector steps, each of which stores at least one row: at most
+    // ceil(n_episode x max_episode_steps / max_steps) + 1 launches finish any collect
+    const int64_t launch_cap = ((int64_t)n_episode * v->cfg.max_episode_steps + max_steps - 1) / max_steps + 1;
+    for (;;) {
+        if (launches >= launch_cap) return fail(FSRL_ESTATE, "device collect: %d launches did not finish %d episodes", launches, n_episode);
+        rc = dispatch_H(c->cfg.hidden, [&](auto hc) {
+            constexpr int H = decltype(hc)::value;
+            devenv_dispatch(v->cfg.kind, [&](auto env) {
+                using Env = decltype(env);
+                hipLaunchKernelGGL((collect_device_kernel<H, Env>), dim3(1), dim3(4 * H), 0, s, c->P, c->md, (const DevCollectArgs*)v->d_args);
+            });
+            HIPCHK(hipGetLastError());
+            return 0;
+        });
+        if (rc) return rc;
+        ++launches;
+        HIPCHK(hipMemcpyAsync(&hs, v->d_state, sizeof(DcState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hs.log_rows < 0 || hs.log_rows > max_steps * n || hs.steps < 0 || hs.steps > max_steps)
+            return fail(FSRL_ESTATE, "device collect: the kernel reported %d rows in %d steps", hs.log_rows, hs.steps);
+        if (hs.log_rows > 0) {
+            HIPCHK(hipMemcpyAsync(v->h_log, v->d_log, (size_t)hs.log_rows * sizeof(DcLogRow), hipMemcpyDeviceToHost, s));     // the log: ONE copy
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        // ---- replay: the bookkeeping of fsrl_store_push, row by row in the kernel's order
+        for (int i = 0; i < hs.log_rows; ++i) {
+            const DcLogRow& r = v->h_log[i];
+            if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device collect: log row %d names env %d", i, r.env);
+            double er = 0.0; int32_t el = 0;
+            const bool done = dc_replay_row(c->env[(size_t)r.env], c->sub_size, c->h_flags.data(), r, &er, &el);
+            total_cost += r.cost;
+            terms += (int32_t)(r.flags & 1u); truncs += (int32_t)((r.flags >> 1) & 1u);
+            if (done) {
+                if (episodes < n_episode) { ep_rew_out[episodes] = er; ep_len_out[episodes] = el; }
+                ++episodes;
+            }
+        }
+        rows += hs.log_rows;
+        c->store_version += (uint64_t)hs.steps;          // one bump per pushed vector step
+        if (hs.finished) break;
+        if (hs.steps == 0) return fail(FSRL_ESTATE, "device collect: a launch made no step");
+    }
+    if (episodes != hs.episodes) return fail(FSRL_ESTATE, "device collect: the log holds %d episodes, the kernel counted %d", episodes, hs.episodes);
+    // FastCollector.reset_env at the end of every collect: ALL envs
+    DevEnvIo io{};
+    io.n = n;
+    rc = devenv_reset_launch(v, io, s);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    *steps_out = rows; *total_cost_out = total_cost; *term_count_out = terms; *trunc_count_out = truncs;
+    *episodes_out = std::min(episodes, n_episode);
+    if (launches_out) *launches_out = launches;
+    return 0;
+}

@@ -1,0 +1,163 @@
+// kernels_devcollect.hpp -- FastCollector.collect(n_episode) as ONE workgroup that loops on the device (fsrl_collect_device).
+//
+// collect_device_kernel<H, Env>: 4 * H threads, staged like actor_resident_kernel<H, false> -- the W2 fragment in registers and the small
+// parameters in LDS, loaded once per launch, the same tile_forward and the same head, so a deterministic collect computes the actions
+// of the existing collectors bit for bit.  Per vector step, over the live envs in position order:
+//   1. per tile of 16 rows (at most 4): the rows' observations (device memory) -> sm.xT, tile_forward, then
+//      a = mu (+ exp(sigma_param) * eps, eps from the action stream of device_env.hpp) and map_action -- into LDS
+//   2. a thread per live env: Env::step, the time limit, rew / cost / flags into the store slot, one log row for the host
+//   3. all threads: obs, obs_next, act of the rows into their store slots
+//   4. a thread per live env: reset where the episode ended (the ordinal advances, dropped or not), else obs := obs_next
+//   5. thread 0: the surplus rule and the end of the collect (devcollect_plan.hpp)
+// The loop has a fixed upper trip count (max_steps <= DC_MAX_STEPS), waits on nothing but its own workgroup's barriers and touches
+// device memory only.  What must survive a launch -- live set, episode count, write indices -- is in DcState; env state is in the
+// env's own arrays.
+// Registers.  At H = 256 the workgroup has 1024 threads, i.e. 128 VGPRs per lane, 64 of them the W2 fragment: nothing else may stay
+// live across tile_forward.  Hence (a) the arguments come through a pointer (held by value they filled the scalar file, and scalar
+// spills live in vector registers), (b) every vector step and the epilogue take a fresh, opaque copy of the thread id, so that no
+// per-lane address arithmetic of the phases is hoisted out of the loop, (c) the live count is read into a scalar register, and (d) the
+// two divisions by run-time constants are multiply-highs with host-made magics (a hoisted reciprocal is a long-lived VGPR).  No
+// instantiation spills (tests/test_code_object.py).
+#pragma once
+#include "kernels_mlp.hpp"
+#include "device_env.hpp"
+
+struct DevCollectArgs {
+    DevEnvParams ep;
+    DevEnvArrays ea;
+    uint32_t k0, k1;
+    StorePtrs st;
+    int64_t sub_size;
+    DcState* state;
+    DcLogRow* log;          // [max_steps][env_num]
+    int max_steps;
+    int deterministic, bound_method, scaled;
+    float low[FSRL_MAX_ACT], high[FSRL_MAX_ACT];
+    float max_action;
+    unsigned magic_per, magic_da;   // div_magic(2 * Do + Da), div_magic(Da): no integer division in the loop
+};
+
+struct DevCollectSmem {
+    int32_t live[DC_MAX_ENVS], index[DC_MAX_ENVS], slot[DC_MAX_ENVS];
+    uint8_t done[DC_MAX_ENVS];
+    int32_t n_live, episodes, finished;
+    float act[DC_MAX_ENVS * FSRL_MAX_ACT];      // the policy's actions (what the store holds)
+    float eact[DC_MAX_ENVS * FSRL_MAX_ACT];     // mapped into the env's range
+};
+
+template <int H, class Env>
+__global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __restrict__ P, const ModelDesc md, const DevCollectArgs* __restrict__ ap) {
+    const DevCollectArgs& a = *ap;
+    __shared__ TileSmem<H> sm;
+    __shared__ DevCollectSmem sh;
+    constexpr int NT = TileGeom<H>::NT;
+    constexpr int NX = TileStage<H>::NX;
+    const int tid = threadIdx.x;
+    const NetOff no = md.net[0];
+    const int Do = md.Do, Da = md.Da;
+    const unsigned magic = div_magic(Do);
+    TileStage<H> stg;
+    stg.issue(P, no, Do, Da, P, nullptr, 0, tid);             // the small parameters; no rows (n_valid = 0 masks the x loads)
+    FwdW2Frag<H> wf;
+    wf.load(P + no.W2f, tid >> 6, tid & 63);
+    stg.commit(sm, no, Do, tid);
+    if (tid < DC_MAX_ENVS) { sh.live[tid] = a.state->live[tid]; sh.index[tid] = a.state->index[tid]; }
+    if (tid == 0) { sh.n_live = a.state->n_live; sh.episodes = a.state->episodes; sh.finished = a.state->finished; }
+    const int n_episode = a.state->n_episode;
+    const int per = 2 * Do + Da;
+    int step = 0, log_rows = 0;
+    for (; step < a.max_steps; ++step) {
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane(sh.finished)) break;
+        const int n_live = __builtin_amdgcn_readfirstlane(sh.n_live);      // workgroup-uniform: scalar registers
+        int lt = threadIdx.x;
+        asm volatile("" : "+v"(lt));           // this step's thread id, opaque: see Registers above
+        // ---- 1. actor, noise, map_action
+        for (int row0 = 0; row0 < n_live; row0 += 16) {
+            const int n_valid = min(16, n_live - row0);
+#pragma unroll
+            for (int u = 0; u < NX; ++u) {
+                const int e = lt + u * NT;
+                if (e < 16 * Do) {
+                    const int i = div_by_magic((unsigned)e, magic), k = e - i * Do;
+                    sm.xT[k * 16 + i] = (i < n_valid) ? a.ea.obs[(size_t)sh.live[row0 + i] * Do + k] : 0.0f;
+                }
+            }
+            __syncthreads();
+            tile_forward<H>(sm, P, no, Do, lt, wf);
+            if (lt < n_valid * Da) {
+#pragma clang fp contract(off)
+                const int i = div_by_magic((unsigned)lt, a.magic_da), d = lt - i * Da, p = row0 + i, e = sh.live[p];
+                const float x = sm.out[i * FSRL_MAX_ACT + d];
+                float act = md.unbounded ? x : a.max_action * tanhf(x);
+                if (!a.deterministic) {
+                    const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+                    const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
+                    act = act + expf(sm.sig[d]) * eps;
+                }
+                sh.act[p * FSRL_MAX_ACT + d] = act;
+                sh.eact[p * FSRL_MAX_ACT + d] = devenv_map_action(act, a.bound_method, a.scaled != 0, a.low[d], a.high[d]);
+            }
+            __syncthreads();
+        }
+        // ---- 2. env step, scalars of the row, log
+        if (lt < n_live) {
+            const int e = sh.live[lt];
+            const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+            const int32_t t = a.ea.t[e];
+            double rew, cost;
+            bool term;
+            Env::step(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, &sh.eact[lt * FSRL_MAX_ACT], g, (uint32_t)t,
+                      a.ea.nxt + (size_t)e * Do, rew, cost, term);
+            a.ea.t[e] = t + 1;
+            const uint32_t fl = dc_flags(term, dc_truncated(t + 1, a.ep.max_steps));
+            const int64_t slot = dc_slot(e, a.sub_size, sh.index[e]);
+            sh.index[e] = dc_next_index(sh.index[e], a.sub_size);
+            sh.slot[lt] = (int32_t)slot;
+            sh.done[lt] = fl != 0u;
+            a.st.rew[slot] = rew; a.st.cost[slot] = cost; a.st.flags[slot] = (uint8_t)fl;
+            DcLogRow lr;
+            lr.env = e; lr.flags = fl; lr.rew = rew; lr.cost = cost;
+            a.log[log_rows + lt] = lr;
+        }
+        __syncthreads();
+        // ---- 3. the rows' vectors into the store
+        for (int x = lt; x < n_live * per; x += NT) {
+            const int p = div_by_magic((unsigned)x, a.magic_per), f = x - p * per, e = sh.live[p];
+            const size_t slot = (size_t)sh.slot[p];
+            if (f < Do) a.st.obs[slot * Do + f] = a.ea.obs[(size_t)e * Do + f];
+            else if (f < 2 * Do) a.st.obs_next[slot * Do + (f - Do)] = a.ea.nxt[(size_t)e * Do + (f - Do)];
+            else a.st.act[slot * Da + (f - 2 * Do)] = sh.act[p * FSRL_MAX_ACT + (f - 2 * Do)];
+        }
+        __syncthreads();
+        // ---- 4. the next observation: a reset where the episode ended
+        if (lt < n_live) {
+            const int e = sh.live[lt];
+            if (sh.done[lt]) {
+                const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)a.ea.ordinal[e]};
+                Env::reset(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, g, a.ea.obs + (size_t)e * Do);
+                a.ea.t[e] = 0;
+                a.ea.ordinal[e] += 1;
+            } else {
+                for (int j = 0; j < Do; ++j) a.ea.obs[(size_t)e * Do + j] = a.ea.nxt[(size_t)e * Do + j];
+            }
+        }
+        log_rows += n_live;
+        __syncthreads();
+        // ---- 5. who goes on
+        if (lt == 0) {
+            int32_t ep = sh.episodes;
+            sh.n_live = dc_episode_end(sh.live, n_live, sh.done, n_episode, &ep);
+            sh.episodes = ep;
+            sh.finished = dc_complete(ep, n_episode) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    int te = threadIdx.x;
+    asm volatile("" : "+v"(te));
+    if (te < DC_MAX_ENVS) { a.state->live[te] = sh.live[te]; a.state->index[te] = sh.index[te]; }
+    if (te == 0) {
+        a.state->n_live = sh.n_live; a.state->episodes = sh.episodes; a.state->finished = sh.finished;
+        a.state->steps = step; a.state->log_rows = log_rows;
+    }
+}

@@ -6,6 +6,7 @@ install(__name__, globals(), {
     "HipVectorReplayBuffer": "buffer",
     "HipPrioritizedVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
+    "DeviceCollector": "device_collector",
     "GroupCollector": "group_collector",
     "BasicCollector": "basic_collector",
     "TrajectoryBuffer": "traj_buf",

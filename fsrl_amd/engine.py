@@ -368,6 +368,83 @@ class Engine:
         return dict(steps=int(steps.value), total_cost=float(cost.value), terminated=int(nt.value), truncated=int(ntr.value),
                     ep_rews=ep_rew[:k], ep_lens=ep_len[:k], t_env=float(tm[0]), t_act=float(tm[1]))
 
+    # ---------------------------------------------------------------- device environments (include/fsrl_hip.h "Device environments")
+    def devenv_create(self, kind, env_num, max_episode_steps, seed=0, params=(), A=None, B=None):
+        """fsrl_devenv_create -> handle.  obs_dim / act_dim are the engine's; A [obs_dim, obs_dim] and B [act_dim, obs_dim] for the
+        linear kind.  The envs are not reset."""
+        cfg = _lib.DevEnvConfig()
+        cfg.kind, cfg.env_num, cfg.obs_dim, cfg.act_dim = int(kind), int(env_num), self.cfg.obs_dim, self.cfg.act_dim
+        cfg.max_episode_steps, cfg.seed = int(max_episode_steps), int(seed) & 0xFFFFFFFFFFFFFFFF
+        for i, v in enumerate(params):
+            cfg.p[i] = float(v)
+        a = b = None
+        if A is not None:
+            a = np.ascontiguousarray(A, np.float32); b = np.ascontiguousarray(B, np.float32)
+            assert a.shape == (self.cfg.obs_dim, self.cfg.obs_dim) and b.shape == (self.cfg.act_dim, self.cfg.obs_dim), \
+                "A is [obs_dim, obs_dim], B is [act_dim, obs_dim]"
+            cfg.A, cfg.B = a.ctypes.data, b.ctypes.data
+        h = C.c_void_p()
+        _lib.check(self.lib.fsrl_devenv_create(self._ctx, C.byref(cfg), C.byref(h)))      # copies A and B
+        return h
+
+    def devenv_destroy(self, h):
+        if h:
+            self.lib.fsrl_devenv_destroy(h)
+
+    def devenv_seed(self, h, seed):
+        _lib.check(self.lib.fsrl_devenv_seed(h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def devenv_reset(self, h, env_num, ids=None):
+        """-> obs of the reset envs (ids = None: all)"""
+        idv = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+        n = int(env_num) if idv is None else idv.size
+        obs = np.empty((n, self.cfg.obs_dim), np.float32)
+        if n:
+            _lib.check(self.lib.fsrl_devenv_reset(h, _ptr(idv, _i32p), n, _ptr(obs, _f32p)))
+        return obs
+
+    def devenv_step(self, h, env_num, act, ids=None):
+        """-> (obs_next, rew, cost, terminated, truncated) of the listed envs (ids = None: all)"""
+        idv = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+        n = int(env_num) if idv is None else idv.size
+        a = np.ascontiguousarray(act, np.float32).reshape(n, self.cfg.act_dim)
+        obs = np.empty((n, self.cfg.obs_dim), np.float32)
+        rew, cost = np.empty(n, np.float64), np.empty(n, np.float64)
+        term, trunc = np.empty(n, np.uint8), np.empty(n, np.uint8)
+        if n:
+            _lib.check(self.lib.fsrl_devenv_step(h, _ptr(idv, _i32p), n, _ptr(a, _f32p), _ptr(obs, _f32p), _ptr(rew, _f64p),
+                                                 _ptr(cost, _f64p), _ptr(term, _u8p), _ptr(trunc, _u8p)))
+        return obs, rew, cost, term.astype(bool), trunc.astype(bool)
+
+    def devenv_get_state(self, h, env_num, state_dim):
+        """-> (state [env_num, state_dim], steps of the running episode [env_num], reset ordinals [env_num])"""
+        st = np.empty((int(env_num), int(state_dim)), np.float32)
+        t, od = np.empty(int(env_num), np.int32), np.empty(int(env_num), np.int64)
+        _lib.check(self.lib.fsrl_devenv_get_state(h, _ptr(st, _f32p), _ptr(t, _i32p), _ptr(od, _i64p)))
+        return st, t, od
+
+    def devenv_set_state(self, h, state=None, t=None, ordinal=None):
+        st = None if state is None else np.ascontiguousarray(state, np.float32)
+        tt = None if t is None else np.ascontiguousarray(t, np.int32)
+        od = None if ordinal is None else np.ascontiguousarray(ordinal, np.int64)
+        _lib.check(self.lib.fsrl_devenv_set_state(h, _ptr(st, _f32p), _ptr(tt, _i32p), _ptr(od, _i64p)))
+
+    def collect_device(self, h, n_episode, deterministic=False, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """FastCollector.collect(n_episode) as a whole on the device (fsrl_collect_device).
+        -> dict(steps, total_cost, terminated, truncated, ep_rews, ep_lens, launches)"""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        steps, cost = C.c_int64(), C.c_double()
+        nt, ntr, nep, nl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        ep_rew, ep_len = np.zeros(max(int(n_episode), 1), np.float64), np.zeros(max(int(n_episode), 1), np.int32)
+        _lib.check(self.lib.fsrl_collect_device(
+            self._ctx, h, int(n_episode), int(bool(deterministic)), int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p),
+            int(max_steps_per_launch), C.byref(steps), C.byref(cost), C.byref(nt), C.byref(ntr), _ptr(ep_rew, _f64p),
+            _ptr(ep_len, _i32p), C.byref(nep), C.byref(nl)))
+        k = nep.value
+        return dict(steps=int(steps.value), total_cost=float(cost.value), terminated=int(nt.value), truncated=int(ntr.value),
+                    ep_rews=ep_rew[:k], ep_lens=ep_len[:k], launches=int(nl.value))
+
     def actor_set_resident(self, on=True, idle_timeout_us=0.0):
         """The collector's actor as a resident workgroup (include/fsrl_hip.h: fsrl_actor_set_resident); on by default."""
         _lib.check(self.lib.fsrl_actor_set_resident(self._ctx, int(bool(on)), float(idle_timeout_us)))

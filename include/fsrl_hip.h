@@ -965,6 +965,62 @@ int fsrl_traj_import(fsrl_traj* t, int64_t rows, const float* obs, const float* 
 int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int64_t n, int32_t first_env,
                     int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out);
 
+/* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy contexts.
+ *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc; INTEGRATION.md "Device environments")
+ *
+ *      A device env holds env_num envs of one kind in device memory: per env a state row, the current observation, the step count of
+ *      the running episode and the env's reset ordinal.  Kinds:
+ *        FSRL_DEVENV_POINT_CIRCLE  fsrl_amd/env/toy.py in float32: obs 6, act 2, state (pos, vel) = 4 floats; p = (radius, x_lim, dt);
+ *                                  a reset draws pos ~ U(-0.5, 0.5)^2, vel = 0
+ *        FSRL_DEVENV_LINEAR        SyntheticSafetyVectorEnv: s' = s @ A + act @ B + 0.05 N(0, 1), A[obs_dim][obs_dim] and
+ *                                  B[act_dim][obs_dim] copied at creation; p = (cost_threshold); 2 <= obs_dim <= 64; state = obs;
+ *                                  a reset draws s ~ N(0, 1)
+ *      truncated = steps of the episode >= max_episode_steps, decided by the stepping kernel, not by the env.
+ *      Random numbers: Philox4x32-10, key = seed * 0x9E3779B97F4A7C15 + 0x243F6A8885A308D3, counter = (env id, reset ordinal, step in
+ *      the episode, stream << 28 | dimension / 4); streams 0 reset draws, 1 action noise, 2 step noise.  The reset ordinal of an env
+ *      counts its resets since creation or the last fsrl_devenv_seed (which zeroes it and leaves the env states alone).
+ *
+ *      fsrl_devenv_create    ctx gives the device, obs_dim / act_dim must be the context's; env_num <= 64.  The envs are NOT reset.
+ *      fsrl_devenv_reset / _step   the env as an ordinary vector env for the existing collectors: one small launch on the env's own
+ *                            stream (a live resident actor keeps running) and a wait.  ids == NULL: envs 0 .. n - 1.  Outputs are per
+ *                            listed env; after a step the env's observation is obs_next (a finished env is reset by the caller).
+ *      fsrl_devenv_get_state / _set_state   tests: state [env_num][state floats] (4 / obs_dim), steps [env_num], ordinals [env_num];
+ *                            every pointer may be NULL.  set_state recomputes the observations.
+ *      fsrl_collect_device   FastCollector.collect(n_episode) as a whole on the device: actor, action noise, map_action, env step,
+ *                            store write and episode bookkeeping in one workgroup that loops for up to max_steps_per_launch vector
+ *                            steps per launch (<= 0: the default, 64; at most 4096); the host launches again until n_episode episodes
+ *                            are complete, replays the launch's log of rows through the store's bookkeeping (as if fsrl_store_push had
+ *                            been called once per vector step), and at the end resets ALL envs, as FastCollector.reset_env does.
+ *                            A collect starts from envs 0 .. min(env_num, n_episode) - 1 in their current state.  Rows in the staging
+ *                            window are flushed first, a live resident actor is ended first.  Outputs as fsrl_collect_episodes;
+ *                            *launches_out (may be NULL): launches of the collect kernel.
+ *                            Refused before anything changes, the message naming the reason: replay contexts (SAC-Lag, DDPG-Lag,
+ *                            CVPO), layered contexts, grouped contexts, a context with a trajectory tap -- FSRL_EINVAL; a context
+ *                            inside an update -- FSRL_ESTATE; env_num above 64 or above the store's sub-buffers, obs_dim / act_dim
+ *                            that differ from the context's, a devenv of another context -- FSRL_EINVAL.  */
+#define FSRL_DEVENV_POINT_CIRCLE 0
+#define FSRL_DEVENV_LINEAR 1
+typedef struct fsrl_devenv_config {
+    int32_t kind, env_num, obs_dim, act_dim, max_episode_steps;
+    uint64_t seed;
+    float p[8];
+    const float* A;
+    const float* B;
+} fsrl_devenv_config;
+typedef struct fsrl_devenv fsrl_devenv;
+int fsrl_devenv_create(fsrl_ctx* ctx, const fsrl_devenv_config* cfg, fsrl_devenv** out);
+int fsrl_devenv_destroy(fsrl_devenv* env);
+int fsrl_devenv_seed(fsrl_devenv* env, uint64_t seed);
+int fsrl_devenv_reset(fsrl_devenv* env, const int32_t* ids, int32_t n, float* obs_out);
+int fsrl_devenv_step(fsrl_devenv* env, const int32_t* ids, int32_t n, const float* env_act, float* obs_next_out, double* rew_out,
+                     double* cost_out, uint8_t* term_out, uint8_t* trunc_out);
+int fsrl_devenv_get_state(fsrl_devenv* env, float* state_out, int32_t* t_out, int64_t* ordinal_out);
+int fsrl_devenv_set_state(fsrl_devenv* env, const float* state, const int32_t* t, const int64_t* ordinal);
+int fsrl_collect_device(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                        const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                        double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                        int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+
 #ifdef __cplusplus
 }
 #endif
