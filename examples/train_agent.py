@@ -8,6 +8,7 @@ installed pass real vector envs exposing reset(ids) / step(act, ids) -> (obs, re
     python examples/train_agent.py --algo sacl --epoch 2 --prefill /tmp/dataset/dataset.npz     (examples/collect_dataset.py --out /tmp/dataset)
     python examples/train_agent.py --algo ppol --epoch 3 --task device-point-circle    (envs on the GPU: whole collects in one looping kernel)
     python examples/train_agent.py --algo cpo --epoch 3 --task device-linear
+    python examples/train_agent.py --algo sacl --epoch 2 --task device-point-circle    (ddpgl and cvpo likewise: nothing per step on the host)
 """
 import argparse
 import os
@@ -40,8 +41,8 @@ def main():
                     help="CPO / TRPO-Lag: Batch.split size inside learn (the reference's default 99999 = the whole buffer)")
     ap.add_argument("--task", choices=["synthetic", "point-circle", "device-point-circle", "device-linear"], default="synthetic",
                     help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories; "
-                         "device-point-circle / device-linear: the same two envs as device functions (ppol, cpo, trpol, focops; at most 64 envs), "
-                         "collected by DeviceCollector")
+                         "device-point-circle / device-linear: the same two envs as device functions (every agent; at most 64 envs; two "
+                         "hidden layers of at most 256 units -- the library refuses layered --hidden-sizes with its reason), collected by DeviceCollector")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
     # options of the on-policy agents (the reference's constructor arguments of the same names)
     ap.add_argument("--unbounded", action=argparse.BooleanOptionalAction, default=None,
@@ -61,8 +62,6 @@ def main():
     if a.prefill is not None and a.algo not in ("sacl", "ddpgl", "cvpo"):
         ap.error(f"--prefill fills a replay store: --algo must be sacl, ddpgl or cvpo, not {a.algo}")
     device_task = a.task.startswith("device-")
-    if device_task and a.algo not in ("ppol", "cpo", "trpol", "focops"):
-        ap.error(f"--task {a.task}: device collects serve the on-policy agents (ppol, cpo, trpol, focops), not {a.algo}")
     if device_task and (a.envs > 64 or a.workers > 0):
         ap.error("a device env holds at most 64 envs and needs no worker processes")
     if a.task in ("point-circle", "device-point-circle"):

@@ -55,8 +55,15 @@ class OffpolicyAgent(BaseAgent):
             buffer = HipVectorReplayBuffer(eng, buffer_size, len(train_envs))
         # device_actor=True: actor + noise on the MI355X (library RNG); over a worker-process env the collector then also
         # overlaps the actor with the env workers when that pays (split_phase="auto")
-        train_collector = FastCollector(self.policy, train_envs, buffer, exploration_noise=True, device_actor=device_actor,
-                                        split_phase="auto" if device_actor else False)
+        from fsrl_amd.env.device import DeviceVectorEnv
+        if isinstance(train_envs, DeviceVectorEnv):
+            # the envs live on the GPU: a collect is a handful of launches of one looping kernel (fsrl_collect_device), and with a
+            # prioritised buffer the rows' leaves are written behind each of them
+            from fsrl_amd.data.device_collector import DeviceCollector
+            train_collector = DeviceCollector(self.policy, train_envs, buffer, exploration_noise=True)
+        else:
+            train_collector = FastCollector(self.policy, train_envs, buffer, exploration_noise=True, device_actor=device_actor,
+                                            split_phase="auto" if device_actor else False)
         test_collector = FastCollector(self.policy, test_envs) if test_envs is not None else None
 
         def stop_fn(reward, cost):

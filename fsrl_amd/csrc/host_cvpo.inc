@@ -360,3 +360,21 @@ extern "C" int fsrl_sac_actor_forward(fsrl_ctx* c, const float* obs, int32_t k, 
 }
 
 static bool sac_squashes(fsrl_ctx* c) { SacState* s = sac_of(c); return s && !s->ddpg && !s->cvpo; }
+
+// fsrl_collect_device on a replay context (host_devcollect.inc): the head arithmetic of sac_actor_finish + actor_draw as
+// collect_device_kernel's arguments.  false: no fused actor (layered / not initialised)
+static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head) {
+    SacState* s = sac_of(c);
+    if (!s || s->layered) return false;
+    *head = s->ddpg ? DC_HEAD_DDPG : DC_HEAD_GAUSS;
+    a->mean_tanh = s->mean_tanh; a->squash = sac_squashes(c) ? 1 : 0; a->exploration_sigma = s->cfg.exploration_sigma;
+    return true;
+}
+// ... and what a push does to a sample drawn ahead: the store_version bump drops it at the next update; one still in flight on the
+// side stream reads rows the kernel is about to overwrite, so the kernel goes behind it
+static int sac_devcollect_enter(fsrl_ctx* c) {
+    SacState* s = sac_of(c);
+    if (s->pre_valid && s->pre_side) HIPCHK(hipStreamWaitEvent(c->compute, s->pre_done, 0));
+    s->pre_valid = false;
+    return 0;
+}

@@ -6,7 +6,13 @@
 // per max_steps_per_launch vector steps, reads the launch's DcState and log back and replays the log through the bookkeeping of
 // fsrl_store_push (devcollect_plan.hpp dc_replay_row: EnvBook, h_flags, store_version), so that the store, the episode statistics
 // and everything derived from them are as if the rows had been pushed one vector step at a time.
+// Replay contexts (SAC-Lag, DDPG-Lag, CVPO): the same kernel with their fused actor's parameters and its head arithmetic on the device
+// (DC_HEAD_GAUSS / DC_HEAD_DDPG); with prioritised replay on, a small launch behind every collect launch gives the rows' slots their
+// leaves (host_per.inc per_devcollect).
 #include "kernels_devcollect.hpp"
+static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head);      // defined with the SAC / CVPO code
+static int sac_devcollect_enter(fsrl_ctx* c);
+static int per_devcollect(fsrl_ctx* c, const int32_t* slots_d, const int32_t* n_rows_d, int cap);       // host_per.inc
 
 struct fsrl_devenv {
     fsrl_ctx* c = nullptr;
@@ -18,6 +24,7 @@ struct fsrl_devenv {
     char* h_io = nullptr;               // pinned: ids | act | obs | rew | cost | flags, for env_num rows
     DcState* d_state = nullptr; DcState* h_state = nullptr;     // device / pinned
     DcLogRow* d_log = nullptr; DcLogRow* h_log = nullptr; int log_steps = 0;
+    int32_t* d_slot = nullptr;          // [log_steps][env_num]: the log rows' store slots (prioritised replay's leaves)
     DevCollectArgs* d_args = nullptr; DevCollectArgs* h_args = nullptr;     // the collect kernel's arguments: device / pinned
 };
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
@@ -56,6 +63,7 @@ static void devenv_free(fsrl_devenv* v) {
     if (v->h_state) (void)hipHostFree(v->h_state);
     if (v->d_log) (void)hipFree(v->d_log);
     if (v->h_log) (void)hipHostFree(v->h_log);
+    if (v->d_slot) (void)hipFree(v->d_slot);
     if (v->d_args) (void)hipFree(v->d_args);
     if (v->h_args) (void)hipHostFree(v->h_args);
     delete v;
@@ -246,9 +254,14 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
                             const float* act_high, int32_t max_steps) {
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
-    CHECK_ARG(!ctx_is_replay(c), "device collects serve on-policy contexts; replay contexts (SAC-Lag, DDPG-Lag, CVPO) are not supported yet");
     CHECK_ARG(!c->lay, "device collects are not supported on layered contexts yet");
-    CHECK_ARG(!c->group && !c->cgroup, "device collects are not supported on grouped contexts yet");
+    CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
+    if (ctx_is_replay(c)) {
+        const float* P; const ModelDesc* md;
+        CHECK_ARG(sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md),
+                  "device collects on replay contexts (SAC-Lag, DDPG-Lag, CVPO) need fsrl_sac_init / fsrl_cvpo_init first");
+        CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
+    }
     CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
     if (c->in_update) return fail(FSRL_ESTATE, "fsrl_collect_device inside an update");
     CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
@@ -279,8 +292,10 @@ extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episod
     if (v->log_steps < max_steps) {
         if (v->d_log) HIPCHK(hipFree(v->d_log));
         if (v->h_log) HIPCHK(hipHostFree(v->h_log));
-        v->d_log = nullptr; v->h_log = nullptr; v->log_steps = 0;
+        if (v->d_slot) HIPCHK(hipFree(v->d_slot));
+        v->d_log = nullptr; v->h_log = nullptr; v->d_slot = nullptr; v->log_steps = 0;
         HIPCHK(hipMalloc(&v->d_log, (size_t)max_steps * n * sizeof(DcLogRow)));
+        HIPCHK(hipMalloc(&v->d_slot, (size_t)max_steps * n * sizeof(int32_t)));
         HIPCHK(hipHostMalloc(&v->h_log, (size_t)max_steps * n * sizeof(DcLogRow)));
         v->log_steps = max_steps;
     }
@@ -301,6 +316,16 @@ extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episod
     for (int d = 0; d < Da && act_low; ++d) { a.low[d] = act_low[d]; a.high[d] = act_high[d]; }
     a.max_action = c->cfg.max_action;
     a.magic_per = div_magic(2 * v->cfg.obs_dim + Da); a.magic_da = div_magic(Da);
+    // whose actor: the context's own networks, or a replay context's fused actor with its head arithmetic
+    int head = DC_HEAD_ONPOLICY;
+    const float* P = c->P; const ModelDesc* md = &c->md;
+    if (ctx_is_replay(c)) {
+        if (!sac_actor_resident_args(c, &P, &md) || !sac_devcollect_head(c, &a, &head)) return fail(FSRL_ESTATE, "no fused actor network");
+        rc = sac_devcollect_enter(c);
+        if (rc) return rc;
+        a.slots = c->per ? v->d_slot : nullptr;
+    }
+    const ModelDesc mdv = *md;
     HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));
     int64_t rows = 0;
     double total_cost = 0.0;
@@ -314,12 +339,19 @@ extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episod
             constexpr int H = decltype(hc)::value;
             devenv_dispatch(v->cfg.kind, [&](auto env) {
                 using Env = decltype(env);
-                hipLaunchKernelGGL((collect_device_kernel<H, Env>), dim3(1), dim3(4 * H), 0, s, c->P, c->md, (const DevCollectArgs*)v->d_args);
+                const DevCollectArgs* da = v->d_args;
+                if (head == DC_HEAD_GAUSS) hipLaunchKernelGGL((collect_device_kernel<H, Env, DC_HEAD_GAUSS>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
+                else if (head == DC_HEAD_DDPG) hipLaunchKernelGGL((collect_device_kernel<H, Env, DC_HEAD_DDPG>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
+                else hipLaunchKernelGGL((collect_device_kernel<H, Env>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
             });
             HIPCHK(hipGetLastError());
             return 0;
         });
         if (rc) return rc;
+        if (a.slots) {      // PrioritizedReplayBuffer.add for the launch's rows: their number is DcState::log_rows, on the device
+            rc = per_devcollect(c, v->d_slot, &v->d_state->log_rows, max_steps * n);
+            if (rc) return rc;
+        }
         ++launches;
         HIPCHK(hipMemcpyAsync(&hs, v->d_state, sizeof(DcState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));

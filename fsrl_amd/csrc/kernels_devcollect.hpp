@@ -18,6 +18,15 @@
 // per-lane address arithmetic of the phases is hoisted out of the loop, (c) the live count is read into a scalar register, and (d) the
 // two divisions by run-time constants are multiply-highs with host-made magics (a hoisted reciprocal is a long-lived VGPR).  No
 // instantiation spills (tests/test_code_object.py).
+//
+// HEAD: whose actor this is.  DC_HEAD_ONPOLICY is the kernel above.  The replay agents' fused actors (P / md are what
+// sac_actor_resident_args returns, staged as actor_resident_kernel<H, true> stages them) leave the RAW head row in sm.out, and phase 1
+// does in float32, every operation rounded on its own, what sac_actor_finish + actor_draw do on the host:
+//   DC_HEAD_GAUSS (SAC-Lag, CVPO; 2 * Da raw columns, Da <= 8):  m = mean_tanh ? max_action * tanhf(raw[d]) : raw[d],
+//       sigma = expf(clamp(raw[Da + d], -20, 2)), u = m (+ sigma * eps), a = squash ? tanhf(u) : u      (squash: SAC-Lag only)
+//   DC_HEAD_DDPG (DDPG-Lag; Da raw columns, Da <= 16):            m = max_action * tanhf(raw[d]), a = m (+ exploration_sigma * eps)
+// eps is the same draw of the action stream as above.  These instantiations also write every row's slot next to the log (a.slots,
+// when the context has prioritised replay on) for per_slots_kernel behind the launch.  Phases 2 - 5 are the same code.
 #pragma once
 #include "kernels_mlp.hpp"
 #include "device_env.hpp"
@@ -35,7 +44,14 @@ struct DevCollectArgs {
     float low[FSRL_MAX_ACT], high[FSRL_MAX_ACT];
     float max_action;
     unsigned magic_per, magic_da;   // div_magic(2 * Do + Da), div_magic(Da): no integer division in the loop
+    // the replay heads only
+    int mean_tanh, squash;
+    float exploration_sigma;
+    int32_t* slots;         // [max_steps][env_num] or NULL: the store slot of every log row (prioritised replay)
 };
+#define DC_HEAD_ONPOLICY 0
+#define DC_HEAD_GAUSS 1
+#define DC_HEAD_DDPG 2
 
 struct DevCollectSmem {
     int32_t live[DC_MAX_ENVS], index[DC_MAX_ENVS], slot[DC_MAX_ENVS];
@@ -45,7 +61,7 @@ struct DevCollectSmem {
     float eact[DC_MAX_ENVS * FSRL_MAX_ACT];     // mapped into the env's range
 };
 
-template <int H, class Env>
+template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
 __global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __restrict__ P, const ModelDesc md, const DevCollectArgs* __restrict__ ap) {
     const DevCollectArgs& a = *ap;
     __shared__ TileSmem<H> sm;
@@ -89,11 +105,29 @@ __global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __re
 #pragma clang fp contract(off)
                 const int i = div_by_magic((unsigned)lt, a.magic_da), d = lt - i * Da, p = row0 + i, e = sh.live[p];
                 const float x = sm.out[i * FSRL_MAX_ACT + d];
-                float act = md.unbounded ? x : a.max_action * tanhf(x);
-                if (!a.deterministic) {
-                    const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
-                    const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
-                    act = act + expf(sm.sig[d]) * eps;
+                float act;
+                if constexpr (HEAD == DC_HEAD_ONPOLICY) {
+                    act = md.unbounded ? x : a.max_action * tanhf(x);
+                    if (!a.deterministic) {
+                        const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+                        const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
+                        act = act + expf(sm.sig[d]) * eps;
+                    }
+                } else {                             // the replay agents: the raw head row -> (m, sigma) -> the draw
+                    float sg;
+                    if constexpr (HEAD == DC_HEAD_GAUSS) {
+                        act = a.mean_tanh ? a.max_action * tanhf(x) : x;
+                        sg = expf(fminf(fmaxf(sm.out[i * FSRL_MAX_ACT + Da + d], -20.0f), 2.0f));
+                    } else {
+                        act = a.max_action * tanhf(x);
+                        sg = a.exploration_sigma;
+                    }
+                    if (!a.deterministic) {
+                        const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+                        const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
+                        act = act + sg * eps;
+                    }
+                    if (HEAD == DC_HEAD_GAUSS && a.squash) act = tanhf(act);
                 }
                 sh.act[p * FSRL_MAX_ACT + d] = act;
                 sh.eact[p * FSRL_MAX_ACT + d] = devenv_map_action(act, a.bound_method, a.scaled != 0, a.low[d], a.high[d]);
@@ -119,6 +153,7 @@ __global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __re
             DcLogRow lr;
             lr.env = e; lr.flags = fl; lr.rew = rew; lr.cost = cost;
             a.log[log_rows + lt] = lr;
+            if constexpr (HEAD != DC_HEAD_ONPOLICY) { if (a.slots) a.slots[log_rows + lt] = (int32_t)slot; }
         }
         __syncthreads();
         // ---- 3. the rows' vectors into the store

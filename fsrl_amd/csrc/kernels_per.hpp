@@ -67,6 +67,24 @@ __global__ __launch_bounds__(PER_THREADS) void per_ingest_kernel(const PerDev p,
     per_repair(p, k, slot_of);
 }
 
+// ... behind collect_device_kernel (replay heads): the launch wrote *n_rows rows (DcState::log_rows, at most cap) into the store
+// itself and left their slots in `slots`; the same leaves and the same repair as per_ingest_kernel's
+__global__ __launch_bounds__(PER_THREADS) void per_slots_kernel(const PerDev p, const int32_t* __restrict__ slots,
+                                                                const int32_t* __restrict__ n_rows, const int cap) {
+    const double v = pow(p.sc[0], p.alpha);
+    const int k = min(max(*n_rows, 0), cap);
+    auto slot_of = [&](int i) {
+        const int s = slots[i];
+        return (s >= 0 && s < p.slots) ? s : -1;
+    };
+    for (int i = threadIdx.x; i < k; i += blockDim.x) {
+        const int s = slot_of(i);
+        if (s >= 0) p.tree[p.bound + s] = v;
+    }
+    __syncthreads();
+    per_repair(p, k, slot_of);
+}
+
 // ... behind store_fill_kernel: the leaves of every job's destination run (per_rebuild_kernel follows)
 __global__ __launch_bounds__(256) void per_fill_kernel(const PerDev p, const TrajJob* __restrict__ jobs, const int n_jobs) {
     const double v = pow(p.sc[0], p.alpha);

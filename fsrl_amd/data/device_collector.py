@@ -2,7 +2,9 @@
 map_action, env step, store write and episode bookkeeping run in one workgroup that loops on the device; the host sees a handful of
 launches and one small read-back per collect instead of one doorbell round trip per vector step.  Same result dict, same counters,
 same store contents and episode-exact behaviour (surplus envs dropped, every env reset at the end of a collect) as `FastCollector`;
-the action noise comes from the env's Philox stream, not from the library's xoshiro stream."""
+the action noise comes from the env's Philox stream, not from the library's xoshiro stream.  On-policy and replay
+policies alike (SAC-Lag, DDPG-Lag, CVPO: the actor's head arithmetic runs on the device too; a prioritised buffer's leaves follow
+the rows); layered and grouped engines are refused by the library, with the reason."""
 import time
 from typing import Any, Dict
 
@@ -10,7 +12,10 @@ import numpy as np
 
 
 class DeviceCollector:
-    def __init__(self, policy, env, buffer, max_steps_per_launch: int = 0):
+    def __init__(self, policy, env, buffer, max_steps_per_launch: int = 0, exploration_noise: bool = False):
+        """exploration_noise is taken for call compatibility with FastCollector: the device draws the action as the policy's
+        training-mode forward does (the replay agents' Gaussian / exploration noise included) unless the policy is in
+        deterministic evaluation, whatever this argument says."""
         from fsrl_amd.env.device import DeviceVectorEnv
         if not isinstance(env, DeviceVectorEnv):
             raise TypeError("DeviceCollector collects from a DeviceVectorEnv")

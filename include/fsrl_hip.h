@@ -965,7 +965,7 @@ int fsrl_traj_import(fsrl_traj* t, int64_t rows, const float* obs, const float* 
 int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int64_t n, int32_t first_env,
                     int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out);
 
-/* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy contexts.
+/* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy and replay contexts.
  *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc; INTEGRATION.md "Device environments")
  *
  *      A device env holds env_num envs of one kind in device memory: per env a state row, the current observation, the step count of
@@ -994,10 +994,19 @@ int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int
  *                            A collect starts from envs 0 .. min(env_num, n_episode) - 1 in their current state.  Rows in the staging
  *                            window are flushed first, a live resident actor is ended first.  Outputs as fsrl_collect_episodes;
  *                            *launches_out (may be NULL): launches of the collect kernel.
- *                            Refused before anything changes, the message naming the reason: replay contexts (SAC-Lag, DDPG-Lag,
- *                            CVPO), layered contexts, grouped contexts, a context with a trajectory tap -- FSRL_EINVAL; a context
- *                            inside an update -- FSRL_ESTATE; env_num above 64 or above the store's sub-buffers, obs_dim / act_dim
- *                            that differ from the context's, a devenv of another context -- FSRL_EINVAL.  */
+ *                            Replay contexts (after fsrl_sac_init / fsrl_cvpo_init): the fused actor's raw head row becomes the action
+ *                            on the device, in float32 with every operation rounded on its own, as fsrl_collect_step forms it on the
+ *                            host -- SAC-Lag a = tanh(m + sigma eps), CVPO a = m + sigma eps, with m = the head or max_action tanh(head)
+ *                            (actor_mean) and sigma = exp(clamp(log sigma head, -20, 2)); DDPG-Lag a = max_action tanh(head) +
+ *                            exploration_sigma eps; deterministic: eps = 0.  eps is the env's action stream, not the context's
+ *                            xoshiro stream, and the device's tanhf / expf are not the host's: rows agree with fsrl_collect_step to
+ *                            float32 rounding, not bit for bit.  With prioritised replay on, every written slot gets the leaf
+ *                            fsrl_store_push would give it (max_prio ** alpha, ancestors repaired) by a launch behind the collect's.
+ *                            Refused before anything changes, the message naming the reason: layered contexts, grouped contexts
+ *                            (update groups, collect groups, replay groups), a context with a trajectory tap, a replay context
+ *                            before fsrl_sac_init / fsrl_cvpo_init -- FSRL_EINVAL; a context inside an update -- FSRL_ESTATE; env_num
+ *                            above 64 or above the store's sub-buffers, obs_dim / act_dim that differ from the context's, a devenv
+ *                            of another context -- FSRL_EINVAL.  */
 #define FSRL_DEVENV_POINT_CIRCLE 0
 #define FSRL_DEVENV_LINEAR 1
 typedef struct fsrl_devenv_config {

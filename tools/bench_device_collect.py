@@ -9,7 +9,12 @@ for 20 and 64 envs at hidden (256, 256) and (64, 64).  Every round times `--call
 alternate inside a round; the result is the median over the rounds and their spread (max - min).  For (a) also the time per vector
 step and per launch, at the default steps per launch and with the whole collect in one launch.
 
+--algo sacl | ddpgl | cvpo runs the same three paths on a replay context of that agent (default: the on-policy leg, output unchanged)
+and adds the loop a user runs: a collect of env_num episodes, then round(update_per_step * n/st) updates of --batch-size rows (library
+sampler, enqueued, statistics drained once per collect), device collect against FastCollector over the in-process env; env-steps/s.
+
     python tools/bench_device_collect.py --rounds 3 --out profiles/device_collect.json
+    python tools/bench_device_collect.py --algo sacl --rounds 3 --out profiles/device_collect_replay.json
 """
 import argparse
 import json
@@ -20,6 +25,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fsrl_amd import _lib  # noqa: E402
 from fsrl_amd.data import DeviceCollector, FastCollector, HipVectorReplayBuffer  # noqa: E402
 from fsrl_amd.engine import Engine, EngineConfig  # noqa: E402
 from fsrl_amd.env import Box, DeviceLinear, SyntheticSafetyVectorEnv  # noqa: E402
@@ -38,9 +44,21 @@ class Pol:
         self.action_space = Box(-1.0, 1.0, (eng.cfg.act_dim, ))
 
 
-def setup(path, hidden, n):
-    eng = Engine(EngineConfig(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN), device=0)
-    eng.set_params((0.1 * np.random.default_rng(0).standard_normal(eng.n_params)).astype(np.float32))
+def setup(path, hidden, n, algo="onpolicy"):
+    kw = dict(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN)
+    if algo == "onpolicy":
+        eng = Engine(EngineConfig(**kw), device=0)
+        eng.set_params((0.1 * np.random.default_rng(0).standard_normal(eng.n_params)).astype(np.float32))
+    else:
+        eng = Engine(EngineConfig(algo=_lib.ALGO_SAC_LAG, **kw), device=0)
+        if algo == "cvpo":
+            eng.cvpo_init(qc_thres=5.0)
+        else:
+            eng.sac_init(deterministic=algo == "ddpgl")
+        rng = np.random.default_rng(0)
+        eng.sac_put_params(0, (0.1 * rng.standard_normal(eng.n_sac_actor)).astype(np.float32))
+        eng.sac_put_params(1, (0.1 * rng.standard_normal(eng.n_sac_critics)).astype(np.float32))
+        eng.sac_put_params(2, eng.sac_get_params(1)[0])
     host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1)
     pol, buf = Pol(eng), HipVectorReplayBuffer(eng, n * 2 * EPISODE_LEN, n)
     if path == "in_process":
@@ -60,8 +78,32 @@ def timed(col, n, calls):
     return rows, time.perf_counter() - t0
 
 
+def timed_loop(eng, col, n, calls, algo, update_per_step, batch):
+    """`calls` x (collect of n episodes, then round(update_per_step * n/st) updates); the store keeps its rows between the collects"""
+    def one():
+        st = col.collect(n_episode=n)["n/st"]
+        k = int(round(update_per_step * st))
+        for _ in range(k):
+            if algo == "cvpo":
+                eng.cvpo_update(batch, sync=False)
+            else:
+                eng.sac_update(batch, [0.5], 1.0, sync=False)
+        eng.sac_drain()
+        return st, k
+    col.reset_buffer()
+    one()
+    rows, t0 = 0, time.perf_counter()
+    for _ in range(calls):
+        st, k = one()
+        rows += st
+    return rows, time.perf_counter() - t0, k
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--algo", choices=["onpolicy", "sacl", "ddpgl", "cvpo"], default="onpolicy")
+    ap.add_argument("--update-per-step", type=float, default=0.1, help="replay legs: updates per collected env step in the loop figure")
+    ap.add_argument("--batch-size", type=int, default=256, help="replay legs: rows per update in the loop figure")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--calls", type=int, default=4)
     ap.add_argument("--envs", default="20,64")
@@ -71,9 +113,11 @@ def main():
     paths = ("device", "in_process", "stepped")
     result = dict(metric="env-steps/s of a collect loop, training mode, linear env obs 8 / act 2, episode length 300", rounds=a.rounds,
                   calls=a.calls, configs=[])
+    if a.algo != "onpolicy":
+        result.update(algo=a.algo, update_per_step=a.update_per_step, batch_size=a.batch_size)
     for hidden in (int(h) for h in a.hidden.split(",")):
         for n in (int(e) for e in a.envs.split(",")):
-            objs = {p: setup(p, hidden, n) for p in paths}
+            objs = {p: setup(p, hidden, n, a.algo) for p in paths}
             rates = {p: [] for p in paths}
             for _ in range(a.rounds):
                 for p in paths:
@@ -96,6 +140,17 @@ def main():
                                              us_per_launch=float(np.median(per_launch)),
                                              us_per_vector_step_spread=float(np.max(per_step) - np.min(per_step)))
             col.max_steps_per_launch = 0
+            if a.algo != "onpolicy":
+                # the loop a user runs: collect + updates, the two collectors alternating inside a round
+                loop, per_collect = {p: [] for p in ("device", "in_process")}, 0
+                for _ in range(a.rounds):
+                    for p in loop:
+                        rows, dt, per_collect = timed_loop(objs[p][0], objs[p][2], n, a.calls, a.algo, a.update_per_step, a.batch_size)
+                        loop[p].append(rows / dt)
+                cfg["loop"] = dict(updates_per_collect=per_collect)
+                for p in loop:
+                    cfg["loop"][p] = dict(median=float(np.median(loop[p])), spread=float(np.max(loop[p]) - np.min(loop[p])),
+                                          rounds=[float(r) for r in loop[p]])
             result["configs"].append(cfg)
             print(json.dumps(cfg), flush=True)
             for eng, env, col in objs.values():
@@ -108,6 +163,10 @@ def main():
             json.dump(result, f, indent=1)
     print(json.dumps(dict(device_collect=[(c["hidden"][0], c["env_num"], round(c["device"]["median"]), round(c["in_process"]["median"]),
                                            round(c["stepped"]["median"])) for c in result["configs"]])))
+    if a.algo != "onpolicy":
+        print(json.dumps(dict(algo=a.algo, collect_plus_updates=[(c["hidden"][0], c["env_num"], c["loop"]["updates_per_collect"],
+                                                                  round(c["loop"]["device"]["median"]), round(c["loop"]["in_process"]["median"]))
+                                                                 for c in result["configs"]])))
 
 
 if __name__ == "__main__":
