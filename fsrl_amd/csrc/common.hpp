@@ -81,6 +81,11 @@ struct PpoStepArgs {
     int fuse_adam;     // max_grad_norm off (the agent default): the weight-gradient kernel applies Adam itself, 2 launches per step
     int xcd_pair;      // fused forward/backward launch: 1 = one network per XCD pair (single-agent step, <= 4 networks), 0 = tile-major blocks
     int dbg_phase;     // probe builds only (-DFSRL_PROBES, env FSRL_DBG_PHASE): early-exit timing experiments, results invalid
+    // clipped step in two launches (ppo_wgrad_kernel<H, false, true, true>): the tag this step's squared-norm slots carry (never 0,
+    // rising from step to step, so no slot is ever reset) and how long a block may wait for a slot, in wall_clock64 ticks of 10 ns
+    // (0: every block gives up before its first poll)
+    unsigned clip_epoch;
+    int clip_limit;
 };
 // Early-exit timing probes of the step kernels (tools/phase_probe.sh).  They exist only in a build with -DFSRL_PROBES
 // (fsrl_amd/csrc/build.sh --probes -> libfsrl_hip_probe.so); in the shipped library the conditions fold to false and
@@ -109,8 +114,9 @@ __device__ __forceinline__ void ppo_adam_math(const float g, float& m, float& v,
 // Device-resident control block (one per context).
 struct CtrlBlock {
     int stopped_after;   // passes with index > stopped_after are skipped (INT_MAX = none)
-    int pad;
-    double kl_sum;       // sum of per-minibatch approx-KL of the current pass (python float sum)
+    int poisoned;        // sticky: a block of a fused clip + Adam launch gave up waiting for the other blocks' squared norms and
+                         // applied nothing; the update is replayed from its snapshot with three launches per step (host_ppo.inc)
+    double kl_sum;      // sum of per-minibatch approx-KL of the current pass (python float sum)
     float last_grad_norm;
     float pad2;
 };

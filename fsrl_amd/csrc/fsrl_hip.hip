@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include <atomic>
 #include "kernels_misc.hpp"
 #include "kernels_mlp.hpp"
 #include "kernels_fb.hpp"
@@ -182,8 +183,8 @@ struct fsrl_ctx {
     int pa_cap = 0;
     void* h_pa = nullptr;           // pinned: [bell 8 B | pad | done[4] at 16 | state[4] at 32 | pad to 64 B | obs cap x Do | mu cap x Da | sigma_param]
     // timing-probe switches: always 0 / false in the shipped library; a -DFSRL_PROBES build reads them ONCE, at
-    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_WGRAD_SKIP / FSRL_NO_SPIN / ... (tools/phase_probe.sh).  Two switches are read by
-    // every build, the shipped library included: FSRL_TILE16 (probe_tile16) and FSRL_NO_W2B_EARLY (no_w2b_early)
+    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_WGRAD_SKIP / FSRL_NO_SPIN / ... (tools/phase_probe.sh).  Three switches are read by
+    // every build, the shipped library included: FSRL_TILE16 (probe_tile16), FSRL_NO_W2B_EARLY (no_w2b_early) and FSRL_NO_CLIP_FUSE (no_clip_fuse)
     int probe_phase = 0, probe_wgrad_skip = 0;
     unsigned long long* probe_ts = nullptr;   // probe builds: [1024][16] phase stamps of the last fused-kernel launch
     bool probe_tile16 = false;
@@ -193,6 +194,19 @@ struct fsrl_ctx {
     int tall_tiles = -1;               // fsrl_ppo_set_plan: 32-row tiles of the minibatch step's forward / backward launch (-1 automatic)
     bool no_fuse_adam = false;      // probe builds: FSRL_NO_FUSE_ADAM keeps the separate Adam launch without a clip (A/B, bit-compare)
     bool no_w2b_early = false;      // every build: FSRL_NO_W2B_EARLY launches the fused forward/backward kernel with its backward W2 fragment in one burst (A/B, bit-compare)
+    // the clipped PPO-Lagrangian step in two launches (host_ppo.inc: clip + Adam inside the weight-gradient launch, bounded wait, replay)
+    bool counted_live = false;      // this context is in g_live_ctx[device]
+    int clip_fuse_mode = -1;        // fsrl_ppo_set_clip_fuse: -1 automatic, 0 off, 1 on
+    int clip_fuse_limit = CLIP_FUSE_DEFAULT_TICKS;   // a block's longest wait for a squared-norm slot, wall_clock64 ticks (10 ns)
+    bool no_clip_fuse = false;      // every build: FSRL_NO_CLIP_FUSE keeps the three-launch clipped step (A/B, bit-compare)
+    bool clip_fuse_dead = false;    // a wait ran out once: this context keeps the three-launch step for good
+    bool clip_fuse_active = false;  // this update runs the two-launch step (decided in fsrl_ppo_begin)
+    int64_t clip_fuse_fallbacks = 0, clip_fuse_steps = 0;   // updates replayed | two-launch steps enqueued
+    unsigned clip_epoch = 0;        // tag of the last two-launch step's slots
+    unsigned long long* clip_slots = nullptr;     // [1024 x CLIP_SLOT_STRIDE] slot words, zeroed once
+    float* clip_snap = nullptr;     // P (with mirrors) | M | V as fsrl_ppo_begin found them
+    int64_t clip_snap_adam_t = 0;
+    std::vector<std::vector<int>> clip_perms;     // every pass's permutation as uploaded
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
     bool no_spin = false;           // wait for the collector's actor with hipStreamSynchronize instead of the completion words
     std::vector<float> act_mu, act_sg;                   // mean / std of the last actor evaluation (host)
@@ -499,6 +513,9 @@ static void fill_mirrors(const ModelDesc& md, std::vector<float>& v) {
     }
 }
 
+// contexts alive per device in this process (fsrl_ctx_create / _destroy): the automatic rule of the two-launch clipped step asks
+static std::atomic<int> g_live_ctx[64];
+static int live_contexts_on(int device) { return (device >= 0 && device < 64) ? g_live_ctx[device].load() : 2; }
 extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
@@ -524,6 +541,8 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (c->mu_old) (void)hipFree(c->mu_old);
     if (c->sigma_old) (void)hipFree(c->sigma_old);
     if (c->snap) (void)hipFree(c->snap);
+    if (c->clip_snap) (void)hipFree(c->clip_snap);
+    if (c->clip_slots) (void)hipFree(c->clip_slots);
     void* dptrs[] = {c->P, c->M, c->V, c->G, c->ctrl, c->st.obs, c->st.obs_next, c->st.act, c->st.rew,
                      c->st.cost, c->st.flags, c->b.obs, c->b.obs_next, c->b.act, c->b.rew, c->b.cost,
                      c->b.flags, c->d_indices, c->d_end, c->d_seg, c->values, c->vnext, c->advs,
@@ -543,6 +562,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     for (hipEvent_t e : c->k_ev) (void)hipEventDestroy(e);
     if (c->compute) (void)hipStreamDestroy(c->compute);
     if (c->side) (void)hipStreamDestroy(c->side);
+    if (c->counted_live && c->device >= 0 && c->device < 64) g_live_ctx[c->device].fetch_sub(1);
     delete c;
     return 0;
 }
@@ -608,6 +628,7 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->cfg.hidden = Hpad_;                 // from here on `hidden` is the kernels' width; h1 / h2 are the caller's layers
     c->h1 = h1_; c->h2 = h2_;
     c->device = device_id;
+    if (device_id >= 0 && device_id < 64) { g_live_ctx[device_id].fetch_add(1); c->counted_live = true; }
     c->n_cus = n_cus_probe > 0 ? n_cus_probe : 256;
     // the two switches the shipped library reads.  FSRL_TILE16: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
     // run sixteen-row tiles from a few members on; a single context created under FSRL_TILE16 is their exact twin
@@ -616,6 +637,8 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     // FSRL_NO_W2B_EARLY: the single-agent PPO step launches ppo_fwd_bwd_kernel<H, 4 | 8> without the early issue of the backward W2
     // fragment (kernels_mlp.hpp: W2bEarly) -- the same arithmetic, the twin of tests/test_gpu_ppo_w2b_early.py and of same-build A/B runs
     c->no_w2b_early = getenv("FSRL_NO_W2B_EARLY") != nullptr;
+    // FSRL_NO_CLIP_FUSE: the clipped PPO-Lagrangian step keeps its own clip + Adam launch (same bits; A/B runs)
+    c->no_clip_fuse = getenv("FSRL_NO_CLIP_FUSE") != nullptr;
 #ifdef FSRL_PROBES
     { const char* e = getenv("FSRL_DBG_PHASE"); c->probe_phase = e ? atoi(e) : 0; }
     { const char* e = getenv("FSRL_WGRAD_SKIP"); c->probe_wgrad_skip = e ? atoi(e) : 0; }

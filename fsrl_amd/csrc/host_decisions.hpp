@@ -158,3 +158,47 @@ static inline void forced_split(int64_t N, int want32, int* n32_out, int* n16_ou
     const int64_t rem = N - 32 * (int64_t)n32;
     *n32_out = n32; *n16_out = (int)((rem + 15) / 16);
 }
+
+// ---- The clipped PPO-Lagrangian step in two launches: the weight-gradient launch exchanges its blocks' squared-norm partials inside
+// the launch and applies clip + Adam itself (kernels_mlp.hpp: clip_exchange).  Its blocks wait for each other, so (a) all of them must
+// fit the chip at once, (b) the wait is bounded, and (c) an update in which a wait ran out is replayed from a snapshot with three
+// launches per step -- which reproduces the update only where nothing but P, M, V and the step counters carries over from it.
+// The bound: an exchange takes 1.7 us on an idle chip (profiles/clip_exchange_ubench.txt) and the blocks of one weight-gradient launch
+// finish within about 6 us of each other, so 50 us = 5 000 ticks of the 100 MHz wall clock is some 30 exchanges -- far above
+// anything a launch that has the chip to itself needs, far below anything a person would call a hang.
+static constexpr int CLIP_FUSE_DEFAULT_TICKS = 5000;
+static constexpr int CLIP_FUSE_MAX_OBS = 64;       // the dW1 role holds back one gradient element per 16 observation columns, 4 at most
+struct ClipFuseFacts {
+    int mode;                 // fsrl_ppo_set_clip_fuse: -1 automatic, 0 off, 1 on
+    bool env_off;             // FSRL_NO_CLIP_FUSE
+    bool dead;                // a wait ran out earlier in this context's life
+    bool ppo_lag, layered, grouped;
+    bool recompute_adv, rew_norm;
+    float max_grad_norm;
+    int nparts, n_cus;        // blocks of the weight-gradient launch | CUs
+    int obs_dim;
+    int live_contexts;        // contexts alive on this device in this process, this one included
+};
+// may THIS UPDATE take the two-launch step?  mode 1 forces nothing the kernel or the replay cannot do.  The automatic rule has one
+// condition more: the context is alone on its device in this process.  Contexts that update side by side (one host thread each:
+// bench.py's multi_seed leg) take CUs from each other's weight-gradient launches, the waits run out, and every context pays one
+// replayed update before it settles on three launches (measured: each of three contexts fell back in its first concurrent update,
+// the six-update leg 181 -> 149 updates/s aggregate); other PROCESSES on the GPU cannot be seen from here, the bounded wait covers them.
+static inline bool clip_fuse_update_ok(const ClipFuseFacts& f) {
+    if (f.mode == 0 || f.env_off || f.dead) return false;
+    if (f.mode < 0 && f.live_contexts > 1) return false;
+    if (!f.ppo_lag || f.layered || f.grouped) return false;                 // solo fused PPO-Lagrangian contexts only
+    if (!(f.max_grad_norm > 0.0f)) return false;                            // no clip: the fuse_adam form needs no exchange
+    if (f.recompute_adv || f.rew_norm) return false;                        // a replay would not reproduce the update
+    if (f.nparts > f.n_cus || f.nparts > 1024) return false;                // every block resident at once, one poller thread per block
+    return f.obs_dim <= CLIP_FUSE_MAX_OBS;
+}
+// may this STEP?  padded rows of the minibatch: above 512 the weight gradients take the split-K route and its own Adam launch
+static inline bool clip_fuse_step_ok(bool update_ok, int rows_pad) { return update_ok && rows_pad <= 512; }
+// after a read of the control block: replay?  (only an update that ran two-launch steps can have been poisoned)
+static inline bool clip_fuse_must_replay(bool active, int poisoned) { return active && poisoned != 0; }
+// what a replay starts from
+struct ClipFuseReplay { long long adam_t, n_steps; int pass_index, passes; };
+static inline ClipFuseReplay clip_fuse_replay_plan(long long snap_adam_t, int passes_enqueued) {
+    return {snap_adam_t, 0, 0, passes_enqueued};
+}

@@ -2,6 +2,8 @@
 // Included once by fsrl_hip.hip: same translation unit, so the static helpers and fsrl_ctx above are visible.
 // ------------------------------------------------------------------------------ PPO-Lagrangian
 static int launch_gae(fsrl_ctx* c);
+static int perm_send(fsrl_ctx* c, int n);
+static int clip_fuse_begin(fsrl_ctx* c);
 // This pass's / repeat's permutation to the device: np.random.permutation on the caller's side, checked, or the library's own
 // shuffle (perm_fill).  Built in pageable memory first: the GPU keeps working on the previous pass meanwhile.  Only the previous
 // H2D copy out of the pinned buffer has to be over (an event, not a stream drain).
@@ -10,6 +12,10 @@ static int perm_upload(fsrl_ctx* c, int n, const int64_t* perm, uint64_t seed) {
     const PermFill pf = perm_fill(c->perm_tmp.data(), n, perm, c->shuffle_rng, seed);
     CHECK_ARG(pf.code != PERM_RANGE, "perm[%d]=%lld out of range", pf.index, pf.value);
     CHECK_ARG(pf.code != PERM_TWICE, "perm is not a permutation: %lld appears twice", pf.value);
+    return perm_send(c, n);
+}
+// c->perm_tmp[0 .. n) to the device (perm_upload, and the replay of a kept pass: clip_fuse_check)
+static int perm_send(fsrl_ctx* c, int n) {
     if (c->perm_in_flight) { HIPCHK(hipEventSynchronize(c->perm_copied)); c->perm_in_flight = false; }
     memcpy(c->h_perm, c->perm_tmp.data(), (size_t)n * 4);
     HIPCHK(hipMemcpyAsync(c->d_perm, c->h_perm, (size_t)n * 4, hipMemcpyHostToDevice, c->compute));
@@ -76,7 +82,11 @@ extern "C" int fsrl_ppo_begin(fsrl_ctx* c, const double* lagrangians, double res
     *c->h_ctrl = init;
     hipStream_t s = c->compute;
     HIPCHK(hipMemcpyAsync(c->ctrl, c->h_ctrl, sizeof(CtrlBlock), hipMemcpyHostToDevice, s));
+    c->clip_fuse_active = false;
+    c->clip_perms.clear();
     if (n == 0) { c->batch_ready = true; return 0; }
+    rc = clip_fuse_begin(c);
+    if (rc) return rc;
     // episode segments for the GAE scan
     int nseg = 0;
     c->h_seg[nseg++] = 0;
@@ -198,7 +208,8 @@ static int ensure_stats(fsrl_ctx* c, int64_t steps) {
 
 // first half of a pass, shared by fsrl_ppo_pass and the grouped update: this pass's permutation to the device and the
 // per-pass batch preparation (per-minibatch advantage statistics + rows in pass order)
-static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed) {
+// kept: a permutation as an earlier call uploaded it (the replay of a pass), instead of perm / seed
+static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed, const std::vector<int>* kept = nullptr) {
     const int n = (int)c->N;
     hipStream_t s = c->compute;
     const int C = c->cfg.n_critics;
@@ -207,8 +218,11 @@ static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed) {
         int rc0 = ppo_recompute_advantages(c);
         if (rc0) return rc0;
     }
-    int rc = perm_upload(c, n, perm, seed);
+    int rc;
+    if (kept) { c->perm_tmp = *kept; rc = perm_send(c, n); }
+    else rc = perm_upload(c, n, perm, seed);
     if (rc) return rc;
+    if (c->clip_fuse_active && !kept) c->clip_perms.push_back(c->perm_tmp);      // what a replay of this pass uploads again
     const int nmb = (int)c->mb_start.size();
     rc = ensure_stats(c, c->n_steps + nmb);
     if (rc) return rc;
@@ -322,6 +336,7 @@ static PpoTilePlan ppo_tile_plan(const fsrl_ctx* c0, int tiles, int nn, int n_ac
     return p;
 }
 
+static int ppo_pass_enqueue(fsrl_ctx* c, const int64_t* perm, uint64_t seed, const std::vector<int>* kept);
 extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, int32_t* stopped_out) {
     CHECK_ARG(c, "null ctx");
     if (!c->in_update || !c->batch_ready) return fail(FSRL_ESTATE, "fsrl_ppo_pass before fsrl_ppo_begin");
@@ -330,23 +345,38 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
     if (stopped_out) *stopped_out = 0;
     const int n = (int)c->N;
     if (n == 0) return 0;
-    hipStream_t s = c->compute;
-    const int H = c->cfg.hidden, nn = c->md.n_nets;
-    int rc = ppo_pass_prepare(c, perm, seed);
-    if (rc) return rc;
-    const int nmb = (int)c->mb_start.size();
-    if (c->cfg.algo == FSRL_ALGO_FOCOPS) return focops_pass(c, stopped_out);
+    int rc;
+    if (c->cfg.algo == FSRL_ALGO_FOCOPS || c->lay) {
+        rc = ppo_pass_prepare(c, perm, seed);
+        if (rc) return rc;
+        if (c->cfg.algo == FSRL_ALGO_FOCOPS) return focops_pass(c, stopped_out);
+    }
     if (c->lay) {               // hidden_sizes of another depth / width: one launch per Linear (host_layered.inc)
         rc = lay_ppo_steps(c);
         if (rc) return rc;
-        c->n_steps += nmb;
+        c->n_steps += (int)c->mb_start.size();
         c->pass_index += 1;
         if (c->cfg.target_kl > 0.0f) return pass_verdict(c, stopped_out);
         return 0;
     }
+    rc = ppo_pass_enqueue(c, perm, seed, nullptr);
+    if (rc) return rc;
+    // ---- pass-level KL early stop: one small readback per pass (the reference's `break`)
+    if (c->cfg.target_kl > 0.0f) return pass_verdict(c, stopped_out);
+    return 0;
+}
+// one pass of the fused PPO-Lagrangian step, enqueued: preparation, then every minibatch step (fsrl_ppo_pass, and the replay of a
+// kept pass: clip_fuse_check)
+static int ppo_pass_enqueue(fsrl_ctx* c, const int64_t* perm, uint64_t seed, const std::vector<int>* kept) {
+    hipStream_t s = c->compute;
+    const int H = c->cfg.hidden, nn = c->md.n_nets;
+    int rc = ppo_pass_prepare(c, perm, seed, kept);
+    if (rc) return rc;
+    const int nmb = (int)c->mb_start.size();
     const PpoBatchPtrs bp = ppo_batch_ptrs(c);
     WgradPtrs wp = ppo_wgrad_ptrs(c);
     wp.stats = c->d_stats;
+    wp.clip_slots = c->clip_slots;
     const int nparts = wg_grid(H, nn);   // tiles + aux parts of every network, + one extra block per network, + the logged-row block
 
     PpoStepArgs sa = ppo_base_args(c);
@@ -398,6 +428,14 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
             c->k_ev_used += 3;
         }
         const bool big = tiles * 16 > 512;
+        // clip + Adam inside the weight-gradient launch (two launches for this step): its slots carry a tag of their own
+        const bool clip_step = clip_fuse_step_ok(c->clip_fuse_active, tiles * 16);
+        if (clip_step) {
+            c->clip_epoch += 1;
+            if (c->clip_epoch == 0) c->clip_epoch = 1;      // 0 is the tag of a slot never written
+            sa.clip_epoch = c->clip_epoch; sa.clip_limit = c->clip_fuse_limit;
+            c->clip_fuse_steps += 1;
+        }
         if (big) {
             // More than 512 rows (batch sizes above 256, or the merged last minibatch of batch 512): the one-workgroup-per-
             // output-tile kernel would walk the rows in chunks (66 us at 1 024 rows: 64 % of such a step).  The full-batch
@@ -422,19 +460,98 @@ extern "C" int fsrl_ppo_pass(fsrl_ctx* c, const int64_t* perm, uint64_t seed, in
             constexpr int HH = decltype(hc)::value;
             // (more than 512 rows took the split-K route above: the chunked BIG form of this kernel runs in the grouped launches only)
             if (sa.fuse_adam) hipLaunchKernelGGL((ppo_wgrad_kernel<HH, false, true>), dim3(nparts), dim3(1024), 0, s, c->md, wp, tiles * 16, sa, stat_tiles);
+            else if (clip_step) hipLaunchKernelGGL((ppo_wgrad_kernel<HH, false, true, true>), dim3(nparts), dim3(1024), 0, s, c->md, wp, tiles * 16, sa, stat_tiles);
             else hipLaunchKernelGGL((ppo_wgrad_kernel<HH, false, false>), dim3(nparts), dim3(1024), 0, s, c->md, wp, tiles * 16, sa, stat_tiles);
             return 0;
         });
         if (rc) return rc;
-        if (!sa.fuse_adam)
+        if (!sa.fuse_adam && !clip_step)
             hipLaunchKernelGGL(adam_clip_kernel, dim3((c->n_dev + 4 * ADAM_NT - 1) / (4 * ADAM_NT)), dim3(ADAM_NT), 0, s, c->P, c->M, c->V, c->G,
                                c->gsq_part, nparts, c->n_dev, sa, c->ctrl, c->md);
         HIPCHK(hipGetLastError());
     }
     c->n_steps += nmb;
     c->pass_index += 1;
-    // ---- pass-level KL early stop: one small readback per pass (the reference's `break`)
-    if (c->cfg.target_kl > 0.0f) return pass_verdict(c, stopped_out);
+    return 0;
+}
+
+// ---- the two-launch clipped step's host side.  fsrl_ppo_begin decides (host_decisions.hpp: clip_fuse_update_ok) and snapshots P, M, V:
+// three device-to-device copies on the compute stream, next to process_fn, which writes none of them.  Every read of the control block (pass_verdict,
+// fsrl_ppo_pass_result, fsrl_ppo_end) looks at `poisoned`: a block of some weight-gradient launch gave up waiting for the others.
+static int clip_fuse_begin(fsrl_ctx* c) {
+    ClipFuseFacts f{};
+    f.mode = c->clip_fuse_mode; f.env_off = c->no_clip_fuse; f.dead = c->clip_fuse_dead;
+    f.ppo_lag = c->cfg.algo == FSRL_ALGO_PPO_LAG; f.layered = c->lay != nullptr; f.grouped = c->group != nullptr;
+    f.recompute_adv = c->cfg.recompute_adv != 0; f.rew_norm = c->cfg.rew_norm != 0;
+    f.max_grad_norm = c->cfg.max_grad_norm;
+    f.nparts = c->lay ? 0 : wg_grid(c->cfg.hidden, c->md.n_nets); f.n_cus = c->n_cus; f.obs_dim = c->cfg.obs_dim;
+    f.live_contexts = live_contexts_on(c->device);
+    if (!clip_fuse_update_ok(f)) return 0;
+    hipStream_t s = c->compute;
+    if (!c->clip_slots) {
+        HIPCHK(hipMalloc(&c->clip_slots, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(c->clip_slots, 0, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long), s));
+    }
+    if (!c->clip_snap) HIPCHK(hipMalloc(&c->clip_snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4));
+    HIPCHK(hipMemcpyAsync(c->clip_snap, c->P, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc, c->M, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc + c->n_dev, c->V, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    c->clip_snap_adam_t = c->adam_t;
+    c->clip_fuse_active = true;
+    return 0;
+}
+// The compute stream is drained and h_ctrl holds the control block.  A poisoned update: back to the snapshot, the three-launch step
+// for good, every pass enqueued so far again with the permutation it ran with; then h_ctrl holds the replay's control block.
+static int clip_fuse_check(fsrl_ctx* c) {
+    if (!clip_fuse_must_replay(c->clip_fuse_active, c->h_ctrl->poisoned)) return 0;
+    hipStream_t s = c->compute;
+    const ClipFuseReplay rp = clip_fuse_replay_plan(c->clip_snap_adam_t, c->pass_index);
+    c->clip_fuse_active = false; c->clip_fuse_dead = true;
+    c->clip_fuse_fallbacks += 1;
+    HIPCHK(hipMemcpyAsync(c->P, c->clip_snap, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->M, c->clip_snap + c->n_alloc, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->V, c->clip_snap + c->n_alloc + c->n_dev, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    c->adam_t = rp.adam_t; c->n_steps = rp.n_steps; c->pass_index = rp.pass_index;
+    c->k_ev_used = 0;
+    CtrlBlock init{INT_MAX, 0, 0.0, 0.0f, 0.0f};
+    *c->h_ctrl = init;
+    HIPCHK(hipMemcpyAsync(c->ctrl, c->h_ctrl, sizeof(CtrlBlock), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));                      // h_ctrl is read back below: the upload out of it has to be over
+    for (int k = 0; k < rp.passes; ++k) {
+        int rc = ppo_pass_enqueue(c, nullptr, 0, &c->clip_perms[(size_t)k]);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_ctrl, c->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    c->clip_perms.clear();
+    return 0;
+}
+// mode: -1 automatic, 0 off, 1 on (where the kernel and the replay allow it: clip_fuse_update_ok); limit_ticks: a block's longest wait
+// for another block's squared norm in 10 ns ticks, 0 = every block gives up at once (the fallback, on demand), < 0 = the default
+extern "C" int fsrl_ppo_set_clip_fuse(fsrl_ctx* c, int32_t mode, int32_t limit_ticks) {
+    CHECK_ARG(c, "null ctx");
+    CHECK_ARG(mode >= -1 && mode <= 1, "mode: -1 (automatic), 0 (off) or 1 (on)");
+    CHECK_ARG(limit_ticks <= 100000000, "limit_ticks: at most 10^8 (one second)");
+    CHECK_ARG(!c->in_update, "fsrl_ppo_set_clip_fuse inside an update");
+    c->clip_fuse_mode = mode;
+    c->clip_fuse_limit = limit_ticks < 0 ? CLIP_FUSE_DEFAULT_TICKS : limit_ticks;
+    return 0;
+}
+// out[0] = 1 if the next update may take the two-launch step (mode, switch, no fallback so far; the shape rule is applied per update),
+// out[1] = updates replayed after a wait ran out, out[2] = two-launch steps enqueued, out[3] = 1 if the LAST update took the step.
+// grad_norm_out (optional, between updates): the gradient norm the last clipped step saw, read from the control block
+extern "C" int fsrl_ppo_clip_fuse_stats(fsrl_ctx* c, int64_t* out, float* grad_norm_out) {
+    CHECK_ARG(c && out, "null argument");
+    if (grad_norm_out) {
+        CHECK_ARG(!c->in_update, "the gradient norm is read between updates");
+        ENTER_DEV(c);
+        CtrlBlock cb;
+        HIPCHK(hipStreamSynchronize(c->compute));
+        HIPCHK(hipMemcpy(&cb, c->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost));
+        *grad_norm_out = cb.last_grad_norm;
+    }
+    out[0] = (c->clip_fuse_mode != 0 && !c->no_clip_fuse && !c->clip_fuse_dead) ? 1 : 0;
+    out[1] = c->clip_fuse_fallbacks; out[2] = c->clip_fuse_steps; out[3] = c->clip_fuse_active ? 1 : 0;
     return 0;
 }
 
@@ -445,6 +562,8 @@ static int pass_verdict(fsrl_ctx* c, int32_t* stopped_out) {
     HIPCHK(hipMemcpyAsync(c->h_ctrl, c->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, c->compute));
     if (!stopped_out) { c->verdict_pending = true; return 0; }
     HIPCHK(hipStreamSynchronize(c->compute));
+    int rc = clip_fuse_check(c);
+    if (rc) return rc;
     if (c->h_ctrl->stopped_after != INT_MAX) *stopped_out = 1;
     return 0;
 }
@@ -453,7 +572,11 @@ extern "C" int fsrl_ppo_pass_result(fsrl_ctx* c, int32_t* stopped_out) {
     CHECK_ARG(c && stopped_out, "null argument");
     if (!c->in_update) return fail(FSRL_ESTATE, "fsrl_ppo_pass_result outside an update");
     ENTER_DEV(c);
-    if (c->verdict_pending) { HIPCHK(hipStreamSynchronize(c->compute)); c->verdict_pending = false; }
+    if (c->verdict_pending) {
+        HIPCHK(hipStreamSynchronize(c->compute)); c->verdict_pending = false;
+        int rc = clip_fuse_check(c);
+        if (rc) return rc;
+    }
     const bool watched = c->cfg.target_kl > 0.0f || c->cfg.algo == FSRL_ALGO_FOCOPS;
     *stopped_out = (watched && c->pass_index > 0 && c->h_ctrl->stopped_after != INT_MAX) ? 1 : 0;
     return 0;
@@ -465,6 +588,9 @@ extern "C" int fsrl_ppo_end(fsrl_ctx* c, float* stats_out, int64_t cap_steps, in
     ENTER_DEV(c);
     hipStream_t s = c->compute;
     HIPCHK(hipEventRecord(c->ev_c, s));
+    // two-launch steps: the control block once more, with the statistics (was a wait cut short since the last look?)
+    const bool look = c->clip_fuse_active;
+    if (look) HIPCHK(hipMemcpyAsync(c->h_ctrl, c->ctrl, sizeof(CtrlBlock), hipMemcpyDeviceToHost, s));
     if (stats_out && c->n_steps > 0) {
         CHECK_ARG(cap_steps >= c->n_steps, "stats_out holds %lld steps, need %lld", (long long)cap_steps,
                   (long long)c->n_steps);
@@ -472,6 +598,18 @@ extern "C" int fsrl_ppo_end(fsrl_ctx* c, float* stats_out, int64_t cap_steps, in
                               hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
+    if (look) {
+        c->verdict_pending = false;
+        const int64_t before = c->clip_fuse_fallbacks;
+        int rc = clip_fuse_check(c);
+        if (rc) { c->in_update = false; return rc; }
+        if (c->clip_fuse_fallbacks != before) {           // replayed: the statistics of the replay, and its time
+            HIPCHK(hipEventRecord(c->ev_c, s));
+            if (stats_out && c->n_steps > 0)
+                HIPCHK(hipMemcpyAsync(stats_out, c->d_stats, (size_t)c->n_steps * FSRL_PPO_NSTATS * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
     if (n_steps_out) *n_steps_out = c->n_steps;
     c->in_update = false;
     if (c->N > 0) {

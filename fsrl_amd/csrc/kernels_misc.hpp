@@ -292,6 +292,31 @@ __global__ __launch_bounds__(256) void w2f_sync_kernel(float* __restrict__ P, co
 #ifndef ADAM_NT
 #define ADAM_NT 256
 #endif
+// clip_grad_norm_'s coefficient from the per-block squared-norm partials, the ONE definition of its summation order (adam_clip_body
+// and the weight-gradient kernel that clips and steps itself both call it, so the two cannot drift): threads [0, ADAM_NT) of the
+// block sum the partials at stride ADAM_NT in float64, each of their waves is reduced by wave_sum_d, and thread 0 adds the wave sums
+// in ascending order.  Every thread of the block calls it (two barriers inside); `parts` is global memory or LDS; `sh`: ADAM_NT / 64
+// doubles and `out`: 2 floats of LDS.  out[0] = the coefficient, out[1] = the norm.
+__device__ __forceinline__ void clip_coef_from_parts(const float* __restrict__ parts, const int nparts, const float max_norm,
+                                                     double* sh, float* out) {
+    const int tid = threadIdx.x;
+    if (tid < ADAM_NT) {
+        double s = 0.0;
+        for (int k = tid; k < nparts; k += ADAM_NT) s += (double)parts[k];
+        s = wave_sum_d(s);
+        if ((tid & 63) == 0) sh[tid >> 6] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < ADAM_NT / 64; ++w) tot += sh[w];
+        const float norm = sqrtf((float)tot);
+        out[0] = fminf(max_norm / (norm + 1e-6f), 1.0f);
+        out[1] = norm;
+    }
+    __syncthreads();
+}
+
 // clip_grad_norm_(max_norm) then torch.optim.Adam single-tensor update, same operation order
 // as torch (lerp_ / mul_+addcmul_ / sqrt / div / add_(eps) / addcdiv_), ppo_lag.py:235-241.
 __device__ __forceinline__ void adam_clip_body(float* __restrict__ P, float* __restrict__ M,
@@ -301,7 +326,7 @@ __device__ __forceinline__ void adam_clip_body(float* __restrict__ P, float* __r
                                                int n, const PpoStepArgs& sa,
                                                CtrlBlock* ctrl, const ModelDesc& md) {
     __shared__ double sh[ADAM_NT / 64];
-    __shared__ float coef_s;
+    __shared__ float coef_s[2];
     const int tid = threadIdx.x;
     if (FSRL_PROBE(sa, 30)) return;                     // launch floor of this kernel (timing experiments only)
     const int i4 = (blockIdx.x * ADAM_NT + tid) * 4;   // float4 per thread
@@ -313,20 +338,9 @@ __device__ __forceinline__ void adam_clip_body(float* __restrict__ P, float* __r
     }
     float coef = 1.0f;
     if (sa.max_grad_norm > 0.0f) {
-        double s = 0.0;
-        for (int k = tid; k < nparts; k += ADAM_NT) s += (double)gsq_part[k];
-        s = wave_sum_d(s);
-        if ((tid & 63) == 0) sh[tid >> 6] = s;
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0;
-            for (int w = 0; w < ADAM_NT / 64; ++w) tot += sh[w];
-            const float norm = sqrtf((float)tot);
-            coef_s = fminf(sa.max_grad_norm / (norm + 1e-6f), 1.0f);
-            if (blockIdx.x == 0) ctrl->last_grad_norm = norm;
-        }
-        __syncthreads();
-        coef = coef_s;
+        clip_coef_from_parts(gsq_part, nparts, sa.max_grad_norm, sh, coef_s);
+        coef = coef_s[0];
+        if (blockIdx.x == 0 && tid == 0) ctrl->last_grad_norm = coef_s[1];
     }
     if (i4 < n) {
 #pragma unroll

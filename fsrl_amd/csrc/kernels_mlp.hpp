@@ -1120,7 +1120,82 @@ struct WgradPtrs {
     float* Pw; float* M; float* V;   // fused-Adam instantiation (FUSE): parameters and Adam moments, updated in place
     float* gsq_net;    // optional [n_nets]: the extra block's share of the squared norm (db3, dsigma) PER NETWORK -- FOCOPS clips the
                        // actor alone (focops.py:205-213); with `stats` null the extra block skips the PPO row
+    unsigned long long* clip_slots;   // CLIP instantiation: one {squared-norm partial, step tag} word per block, CLIP_SLOT_STRIDE apart
 };
+
+// ---- the clipped step in TWO launches (CLIP instantiation of the weight-gradient kernel).  Of everything clip_grad_norm_ + Adam need,
+// only the per-block squared-norm partials cross workgroups: gridDim.x floats.  Every block publishes its partial as ONE 8-byte word
+// {float bits, step tag} with one relaxed agent-scope atomic store (write-through, nothing to flush), polls the words of all blocks
+// with relaxed agent-scope atomic loads (they bypass the L1; nothing to invalidate), forms the coefficient with adam_clip_body's own
+// summation (clip_coef_from_parts) and steps the gradient elements it still holds in registers.  No counter, no read-modify-write,
+// no fence: one hop (tools/ubench/slot_exchange.hip, profiles/clip_exchange_ubench.txt).
+// The wait needs every block of the launch resident at once (the host launches it only where gridDim.x <= CUs), which nothing
+// guarantees on a shared GPU, so it is BOUNDED: a block whose slot does not arrive within sa.clip_limit ticks sets the sticky
+// CtrlBlock::poisoned, applies nothing and leaves; blocks that see the word set leave too.  The host then restores the update's
+// snapshot and replays it with three launches per step (host_ppo.inc: clip_fuse_check).
+#define CLIP_SLOT_STRIDE 16    // in 8-byte words: every slot on its own 128-byte line (1.70 us per exchange; packed 2.72)
+#define CLIP_NP 5              // gradient elements a thread may hold back: 4 dW1 column groups (obs_dim <= 64) + db1
+struct ClipPend {
+    int i[CLIP_NP];            // parameter index, -1: none
+    float g[CLIP_NP], m[CLIP_NP], v[CLIP_NP], p[CLIP_NP];
+    int mi;                    // slot 0 only: its place in the forward-fragment mirror of W2, or -1
+};
+// slot s := element gi (or none): its P, M, V loads are issued here, early, and land under the role's GEMM
+template <int S>
+__device__ __forceinline__ void clip_pend_load(ClipPend& cp, const WgradPtrs& wp, const int gi) {
+    cp.i[S] = gi; cp.g[S] = 0.0f; cp.m[S] = 0.0f; cp.v[S] = 0.0f; cp.p[S] = 0.0f;
+    if (gi >= 0) { cp.m[S] = wp.M[gi]; cp.v[S] = wp.V[gi]; cp.p[S] = wp.Pw[gi]; }
+}
+// `part`: this block's squared-norm partial (thread 0's value counts).  vals: gridDim.x floats of LDS nobody reads any more.
+// first_block: the block that reports the norm.  Returns false when the block gave up (nothing may be applied).
+__device__ __forceinline__ bool clip_exchange(const WgradPtrs& wp, const PpoStepArgs& sa, const float part, float* vals,
+                                              const bool reports, float& coef) {
+    __shared__ double sh[ADAM_NT / 64];
+    __shared__ float out[2];
+    __shared__ int bail;
+    const int tid = threadIdx.x, nparts = (int)gridDim.x;
+    if (tid == 0) {
+        bail = sa.clip_limit <= 0 ? 1 : 0;
+        __hip_atomic_store(wp.clip_slots + (size_t)blockIdx.x * CLIP_SLOT_STRIDE,
+                           ((unsigned long long)sa.clip_epoch << 32) | (unsigned long long)__float_as_uint(part), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();                                    // `vals` is free from here on (the roles' last reads are behind a barrier)
+    if (tid < nparts && sa.clip_limit > 0) {
+        const unsigned long long* slot = wp.clip_slots + (size_t)tid * CLIP_SLOT_STRIDE;
+        const long long t0 = wall_clock64();
+        unsigned long long w;
+        while (true) {
+            w = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((unsigned)(w >> 32) == sa.clip_epoch) break;
+            if (wall_clock64() - t0 > (long long)sa.clip_limit ||
+                __hip_atomic_load(&wp.ctrl->poisoned, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { bail = 1; break; }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        vals[tid] = __uint_as_float((unsigned)w);
+    }
+    __syncthreads();
+    if (bail) {                                         // block-uniform: written before the barrier, read after it
+        if (tid == 0) __hip_atomic_store(&wp.ctrl->poisoned, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return false;
+    }
+    clip_coef_from_parts(vals, nparts, sa.max_grad_norm, sh, out);
+    coef = out[0];
+    if (reports && tid == 0) wp.ctrl->last_grad_norm = out[1];
+    return true;
+}
+// the Adam step of every element the thread held back, with the clipped gradient: adam_clip_body's g * coef
+__device__ __forceinline__ void clip_pend_apply(const ClipPend& cp, const WgradPtrs& wp, const PpoStepArgs& sa, const float coef) {
+#pragma unroll
+    for (int s = 0; s < CLIP_NP; ++s) {
+        if (cp.i[s] >= 0) {
+            float m = cp.m[s], v = cp.v[s], p = cp.p[s];
+            ppo_adam_math(cp.g[s] * coef, m, v, p, sa);
+            wp.M[cp.i[s]] = m; wp.V[cp.i[s]] = v; wp.Pw[cp.i[s]] = p;
+            if (s == 0 && cp.mi >= 0) wp.Pw[cp.mi] = p;
+        }
+    }
+}
 
 // torch.optim.Adam single-tensor update of ONE element with an unclipped gradient -- the same operations in the same
 // order as adam_clip_kernel with coef == 1 (g * 1.0f == g), so the two launch sequences are bit-identical.  Used by the
@@ -1205,9 +1280,10 @@ __device__ __forceinline__ void ppo_stats_finalize(const ModelDesc& md, const Wg
 //   e == n_nets: the step's logged row (FUSE: the block of network 0 writes it first -- it reads the sigma_param its own Adam step
 //                is about to change -- and this block only leaves a zero behind)
 // `red`: at least 32 x 33 floats of LDS.
-template <bool BIG, bool FUSE>
+// CLIP: the block's Adam steps wait for the clip coefficient: they go to `cp`, the block's squared-norm partial to `part` (thread 0).
+template <bool BIG, bool FUSE, bool CLIP = false>
 __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const WgradPtrs& wp, const int mbp, const PpoStepArgs& sa,
-                                                      const int n_stat_tiles, float* red, const int e) {
+                                                      const int n_stat_tiles, float* red, const int e, ClipPend& cp, float& part) {
     const int CH = BIG ? (mbp + 511) / 512 : 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (FSRL_PROBE(sa, 21)) return;
@@ -1222,6 +1298,7 @@ __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const
     }
     if (e == md.n_nets) {                     // nothing of the gradient is produced here
         if (tid == 0) wp.gsq_part[blockIdx.x] = 0.0f;
+        part = 0.0f;
         return;
     }
     // db3[o] / dsigma[d] = column sums of DO over the minibatch rows:
@@ -1232,6 +1309,10 @@ __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const
         const NetOff no = md.net[net];
         const float* __restrict__ DOn = wp.DO + (size_t)net * wp.mbp_max * FSRL_DOW;
         const int col = tid & 31, php = tid >> 5;
+        if constexpr (CLIP) {
+            clip_pend_load<0>(cp, wp, tid < no.out ? no.b3 + tid : -1);
+            clip_pend_load<1>(cp, wp, (no.sigma >= 0 && tid >= 16 && tid < 16 + md.Da) ? no.sigma + tid - 16 : -1);
+        }
         float t = 0.0f;
         for (int ch = 0; ch < CH; ++ch) {
             float v[16];
@@ -1254,11 +1335,13 @@ __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const
             for (int p2 = 0; p2 < 32; ++p2) tot += red[p2 * 33 + tid];
             if (tid < no.out) {
                 wp.grad[no.b3 + tid] = tot; sqs = fmaf(tot, tot, sqs);
-                if constexpr (FUSE) ppo_adam_elem(wp, sa, no.b3 + tid, tot);
+                if constexpr (CLIP) cp.g[0] = tot;
+                else if constexpr (FUSE) ppo_adam_elem(wp, sa, no.b3 + tid, tot);
             }
             if (no.sigma >= 0 && tid >= 16 && tid < 16 + md.Da) {
                 wp.grad[no.sigma + tid - 16] = tot; sqs = fmaf(tot, tot, sqs);
-                if constexpr (FUSE) ppo_adam_elem(wp, sa, no.sigma + tid - 16, tot);   // wave 0 logged the entropy first
+                if constexpr (CLIP) cp.g[1] = tot;
+                else if constexpr (FUSE) ppo_adam_elem(wp, sa, no.sigma + tid - 16, tot);   // wave 0 logged the entropy first
             }
         }
     }
@@ -1266,6 +1349,7 @@ __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const
         sqs = wave_sum(sqs);                  // lanes >= 32 hold 0
         if (lane == 0) {
             wp.gsq_part[blockIdx.x] = sqs;
+            part = sqs;
             if (wp.gsq_net) wp.gsq_net[e] = sqs;          // this network's share on its own (FOCOPS clips the actor alone)
         }
     }
@@ -1278,17 +1362,30 @@ __device__ __forceinline__ void ppo_wgrad_extra_block(const ModelDesc& md, const
 //      where a dW2 tile moves 64 KB -- the role timing of a probe build: launch floor 4.4 us, tiles alone 5.4, aux blocks alone 7.2, with
 //      D1 / X only 6.2).  Per element the loads, MFMA order and the two-round LDS reduction are unchanged: same bits.
 //      (v1 did this with VALU + LDS broadcasts on 12 blocks and took 16 us.)
-template <int H, bool BIG, bool FUSE, int U, bool PA, bool PB>
+template <int H, bool BIG, bool FUSE, int U, bool PA, bool PB, bool CLIP = false>
 __device__ __forceinline__ void ppo_wgrad_aux(const ModelDesc& md, const WgradPtrs& wp, const int mbp, const PpoStepArgs& sa,
                                               const NetOff& no, const float* __restrict__ A2, const float* __restrict__ D1,
                                               const float* __restrict__ D2, const float* __restrict__ DOb, const int j0,
-                                              float* red, float& sq) {
+                                              float* red, float& sq, ClipPend& cp) {
     const int CH = BIG ? (mbp + 64 * U - 1) / (64 * U) : 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
     const int Do = md.Do, out = no.out;
     const int KS = mbp >> 2;
     const float* __restrict__ X = wp.X;
+    if constexpr (CLIP) {                     // the elements this thread will produce below, in the slots it will fill
+        const int e = tid & 511, jl = e >> 4, kk = e & 15;
+        if constexpr (PA) {                   // slot k0 / 16: dW1 (the host takes this route for obs_dim <= 16 * 4 only); slot 4: db1
+            clip_pend_load<0>(cp, wp, (tid < 512 && kk < Do) ? no.W1 + (j0 + jl) * Do + kk : -1);
+            clip_pend_load<1>(cp, wp, (tid < 512 && 16 + kk < Do) ? no.W1 + (j0 + jl) * Do + 16 + kk : -1);
+            clip_pend_load<2>(cp, wp, (tid < 512 && 32 + kk < Do) ? no.W1 + (j0 + jl) * Do + 32 + kk : -1);
+            clip_pend_load<3>(cp, wp, (tid < 512 && 48 + kk < Do) ? no.W1 + (j0 + jl) * Do + 48 + kk : -1);
+            clip_pend_load<4>(cp, wp, tid < 32 ? no.b1 + j0 + tid : -1);
+        }
+        if constexpr (PB)                     // slot 0: dW3 (threads 512 ..) or db2 (threads 32 .. 63)
+            clip_pend_load<0>(cp, wp, (tid >= 512 && kk < out) ? no.W3 + kk * H + j0 + jl
+                                                               : (tid >= 32 && tid < 64) ? no.b2 + j0 + tid - 32 : -1);
+    }
     for (int k0 = 0; k0 < (PA ? Do : 1); k0 += 16) {
         const bool first = (k0 == 0);
         f32x4 ax0 = {0, 0, 0, 0}, ax1 = {0, 0, 0, 0}, ad0 = {0, 0, 0, 0}, ad1 = {0, 0, 0, 0};
@@ -1406,14 +1503,18 @@ __device__ __forceinline__ void ppo_wgrad_aux(const ModelDesc& md, const WgradPt
                         const int gi = no.W1 + (j0 + jl) * Do + k0 + kk;
                         wp.grad[gi] = v;
                         sq = fmaf(v, v, sq);
-                        if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, v);
+                        if constexpr (CLIP) {
+                            const int it = k0 >> 4;
+                            if (it == 0) cp.g[0] = v; else if (it == 1) cp.g[1] = v; else if (it == 2) cp.g[2] = v; else cp.g[3] = v;
+                        } else if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, v);
                     }
                 }
             } else if (PB && first && kk < out) {
                 const int gi = no.W3 + kk * H + j0 + jl;
                 wp.grad[gi] = v;
                 sq = fmaf(v, v, sq);
-                if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, v);
+                if constexpr (CLIP) cp.g[0] = v;
+                else if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, v);
             }
             if (first && ((PA && tid < 32) || (PB && tid >= 32 && tid < 64))) {
                 float bsum = 0.0f;
@@ -1422,7 +1523,8 @@ __device__ __forceinline__ void ppo_wgrad_aux(const ModelDesc& md, const WgradPt
                 const int gi = (tid < 32) ? no.b1 + j0 + tid : no.b2 + j0 + tid - 32;
                 wp.grad[gi] = bsum;
                 sq = fmaf(bsum, bsum, sq);
-                if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, bsum);
+                if constexpr (CLIP) { if (tid < 32) cp.g[4] = bsum; else cp.g[0] = bsum; }
+                else if constexpr (FUSE) ppo_adam_elem(wp, sa, gi, bsum);
             }
         }
     }
@@ -1434,7 +1536,9 @@ __device__ __forceinline__ void ppo_wgrad_aux(const ModelDesc& md, const WgradPt
 // that the clipped path keeps its register budget (one kernel with a runtime switch spilled 42 VGPRs).
 // U: k-steps per wave and load burst in the tile role (a chunk = 64 U rows).  8 for the single-agent launches; the grouped launches
 // take 4 -- a 256-row minibatch needs no more -- to fit 64 VGPRs, so that TWO workgroups share a CU (r6).
-template <int H, bool BIG, bool FUSE, int U = WG_MAXU>
+// CLIP (with FUSE; single-agent launches of at most one workgroup per CU): the gradient-norm clip and Adam in this launch too, see
+// clip_exchange above.  Gradient loads, MFMA order and reductions are those of the other forms: same bits.
+template <int H, bool BIG, bool FUSE, int U = WG_MAXU, bool CLIP = false>
 __device__ __forceinline__ void ppo_wgrad_body(const ModelDesc& md, const WgradPtrs& wp, const int mbp,
                                                const PpoStepArgs& sa, const int n_stat_tiles) {
     const int CH = BIG ? (mbp + 64 * U - 1) / (64 * U) : 1;      // row chunks
@@ -1446,9 +1550,22 @@ __device__ __forceinline__ void ppo_wgrad_body(const ModelDesc& md, const WgradP
     __shared__ float red[1024 * 9];      // 8 split-K partial slots of a 32x32 tile / aux reduce scratch
     __shared__ float wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    static_assert(!CLIP || (FUSE && !BIG), "the clip exchange belongs to the fused-Adam form of the one-burst kernel");
     if (FSRL_PROBE(sa, 20)) return;
+    ClipPend cp;
+    if constexpr (CLIP) {
+#pragma unroll
+        for (int s = 0; s < CLIP_NP; ++s) cp.i[s] = -1;
+        cp.mi = -1;
+    }
     if ((int)blockIdx.x >= md.n_nets * PB) {  // the extra blocks: one per network + the logged row
-        ppo_wgrad_extra_block<BIG, FUSE>(md, wp, mbp, sa, n_stat_tiles, red, (int)blockIdx.x - md.n_nets * PB);
+        const int e = (int)blockIdx.x - md.n_nets * PB;
+        float part = 0.0f;
+        ppo_wgrad_extra_block<BIG, FUSE, CLIP>(md, wp, mbp, sa, n_stat_tiles, red, e, cp, part);
+        if constexpr (CLIP) {                 // the logged-row block publishes its zero as well: every slot is summed
+            float coef = 1.0f;
+            if (clip_exchange(wp, sa, part, red, e == 0, coef) && e < md.n_nets) clip_pend_apply(cp, wp, sa, coef);
+        }
         return;
     }
     const int net = blockIdx.x / PB, rb = blockIdx.x % PB;
@@ -1472,6 +1589,11 @@ __device__ __forceinline__ void ppo_wgrad_body(const ModelDesc& md, const WgradP
         const float* __restrict__ pb = A1 + tk * 32 + 2 * c;
         const int KS = mbp >> 2;
         f32x4 acc00 = {0, 0, 0, 0}, acc01 = {0, 0, 0, 0}, acc10 = {0, 0, 0, 0}, acc11 = {0, 0, 0, 0};
+        if constexpr (CLIP) {                 // this thread's output element (as below): P, M, V on their way before the burst
+            const int gi = no.W2 + (tj * 32 + (tid >> 5)) * H + tk * 32 + (tid & 31);
+            clip_pend_load<0>(cp, wp, gi);
+            cp.mi = no.W2f + w2f_index(H, tj * 32 + (tid >> 5), tk * 32 + (tid & 31));
+        }
         for (int ch = 0; ch < CH; ++ch) {
             int s0 = 16 * U * ch;
             // BIG: the chunk base is made opaque to the optimiser.  Left visible, it hoists the 64-bit address of every load of the
@@ -1534,24 +1656,29 @@ __device__ __forceinline__ void ppo_wgrad_body(const ModelDesc& md, const WgradP
             const int gi = no.W2 + (tj * 32 + jl) * H + tk * 32 + kl;
             wp.grad[gi] = v;
             sq = v * v;
-            if constexpr (FUSE)
+            if constexpr (CLIP) cp.g[0] = v;
+            else if constexpr (FUSE)
                 ppo_adam_elem(wp, sa, gi, v, no.W2f + w2f_index(H, tj * 32 + jl, tk * 32 + kl));
         }
     } else if (rb < NT2 + NA) {
-        ppo_wgrad_aux<H, BIG, FUSE, U, true, false>(md, wp, mbp, sa, no, A2, D1, D2, DOb, (rb - NT2) * 32, red, sq);
+        ppo_wgrad_aux<H, BIG, FUSE, U, true, false, CLIP>(md, wp, mbp, sa, no, A2, D1, D2, DOb, (rb - NT2) * 32, red, sq, cp);
     } else {
-        ppo_wgrad_aux<H, BIG, FUSE, U, false, true>(md, wp, mbp, sa, no, A2, D1, D2, DOb, (rb - NT2 - NA) * 32, red, sq);
+        ppo_wgrad_aux<H, BIG, FUSE, U, false, true, CLIP>(md, wp, mbp, sa, no, A2, D1, D2, DOb, (rb - NT2 - NA) * 32, red, sq, cp);
     }
     // ---- block sum of squares (fixed order => deterministic)
     sq = wave_sum(sq);
     __syncthreads();
     if (lane == 0) wsum[wave] = sq;
     __syncthreads();
+    float t = 0.0f;
     if (tid == 0) {
-        float t = 0.0f;
 #pragma unroll
         for (int w = 0; w < 16; ++w) t += wsum[w];
         wp.gsq_part[blockIdx.x] = t;
+    }
+    if constexpr (CLIP) {
+        float coef = 1.0f;
+        if (clip_exchange(wp, sa, t, red, false, coef)) clip_pend_apply(cp, wp, sa, coef);
     }
 }
 
@@ -1562,11 +1689,11 @@ __global__ __launch_bounds__(64) void ppo_stats_kernel(const ModelDesc md, const
     ppo_stats_finalize(md, wp, sa, n_stat_tiles, (int)threadIdx.x);
 }
 
-template <int H, bool BIG, bool FUSE>
+template <int H, bool BIG, bool FUSE, bool CLIP = false>
 __global__ __launch_bounds__(1024) void ppo_wgrad_kernel(const ModelDesc md, const WgradPtrs wp,
                                                         const int mbp, const PpoStepArgs sa,
                                                         const int n_stat_tiles) {
-    ppo_wgrad_body<H, BIG, FUSE>(md, wp, mbp, sa, n_stat_tiles);
+    ppo_wgrad_body<H, BIG, FUSE, WG_MAXU, CLIP>(md, wp, mbp, sa, n_stat_tiles);
 }
 
 // ---------------------------------------------------------------- grouped launches (several agents, one stream)

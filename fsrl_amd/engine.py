@@ -519,6 +519,19 @@ class Engine:
         """32-row tiles in the forward / backward launch of a minibatch step: -1 automatic, 0 none, n > 0 a count (A/B; same bits)"""
         _lib.check(self.lib.fsrl_ppo_set_plan(self._ctx, int(tall_tiles)))
 
+    def ppo_set_clip_fuse(self, mode: int = -1, limit_ticks: int = -1):
+        """The clipped step in two launches (clip + Adam inside the weight-gradient launch; same bits): mode -1 automatic, 0 off, 1 on;
+        limit_ticks: a workgroup's longest wait in 10 ns ticks (< 0 default, 0 every workgroup gives up: the update is replayed)."""
+        _lib.check(self.lib.fsrl_ppo_set_clip_fuse(self._ctx, int(mode), int(limit_ticks)))
+
+    def ppo_clip_fuse_stats(self):
+        """-> dict(available, fallbacks, steps, last_update_fused, grad_norm); between updates"""
+        out = (C.c_int64 * 4)()
+        gn = C.c_float()
+        _lib.check(self.lib.fsrl_ppo_clip_fuse_stats(self._ctx, out, C.byref(gn)))
+        return dict(available=bool(out[0]), fallbacks=int(out[1]), steps=int(out[2]), last_update_fused=bool(out[3]),
+                    grad_norm=np.float32(gn.value))
+
     def ppo_update(self, lagrangians, rescaling, batch_size, repeat, perms=None, seed=0):
         """-> (stats [steps, 11] float32, stopped_pass or -1)."""
         n = self.ppo_begin(lagrangians, rescaling, batch_size)

@@ -316,6 +316,18 @@ int fsrl_ppo_update(fsrl_ctx* ctx, const double* lagrangians, double rescaling,
  * ~1 360 rows with three networks), 0 none, n > 0 min(n, tiles / 2).  Needs hidden >= 128 and obs_dim <= 64.                        */
 int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
 
+/* The clipped PPO-Lagrangian step (max_grad_norm > 0) in TWO launches: the weight-gradient launch exchanges its workgroups' squared-norm
+ * partials inside the launch and applies clip + Adam itself (same bits as the three-launch step).  Taken by a solo fused context whose
+ * weight-gradient grid fits the chip, for minibatches of at most 512 rows, without recompute_adv and reward normalisation.  The
+ * workgroups wait for each other at most `limit_ticks` ticks of 10 ns (< 0: the default, 5 000 = 50 us; 0: every workgroup gives up at
+ * once).  An update in which a wait ran out (a shared GPU) is restored from its snapshot and replayed with three launches per step
+ * inside the call that notices it; the context then keeps the three-launch step.  mode: -1 automatic (default), 0 off, 1 on.
+ * Environment: FSRL_NO_CLIP_FUSE (read at fsrl_ctx_create) keeps the three-launch step.
+ * fsrl_ppo_clip_fuse_stats: out[4] = {two-launch step still available (0 / 1), updates replayed, two-launch steps enqueued,
+ * last update took it (0 / 1)}; grad_norm_out (may be NULL; between updates only): the gradient norm the last clipped step saw.   */
+int fsrl_ppo_set_clip_fuse(fsrl_ctx* ctx, int32_t mode, int32_t limit_ticks);
+int fsrl_ppo_clip_fuse_stats(fsrl_ctx* ctx, int64_t* out, float* grad_norm_out);
+
 /* ---- grouped updates: k independent PPO-Lagrangian agents, or k FOCOPS agents, of ONE network shape on one GPU, stepped in lock step
  *      (multi-seed runs; SURVEY 8e "within-GPU batching of k seeds").  The reference runs seeds as separate jobs; one
  *      agent's update is a chain of small dependent launches that leaves most of an MI355X idle, so k agents share every
