@@ -62,6 +62,13 @@ gamma, cost_limit; `none` switches dual_clip / target_kl off) and of batch_size 
 per collect (PolicyGroup.update with a batch size and a pass count per member -> fsrl_group_ppo_update_each).  The members must agree
 on whether max_grad_norm is on.  FOCOPS groups are not sweeps.
     python examples/train_multi_seed.py --algo ppol --seeds 4 --epoch 2 --grouped --sweep eps_clip=0.1,0.2,0.2,0.3 --sweep batch_size=128,256,256,512
+--task device-linear | device-point-circle (--grouped, every algo it takes): the seeds' envs live on the GPU (fsrl_amd.env.DeviceLinear:
+the default task's dynamics; DevicePointCircle), each seed has a DeviceVectorEnv on its engine and a DeviceCollector, and a collect
+of all seeds is ONE fsrl_amd.data.GroupDeviceCollector.collect -> fsrl_collect_device_group: every launch carries all seeds'
+collects, a workgroup per seed, per seed bit-identical to its own device collect (tools/bench_device_collect.py --ks; DESIGN.md
+3.4.1).  The updates go through the same groups as above.  Layered --hidden-sizes are refused by the library at the first collect.
+    python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --task device-linear
+    python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped --task device-point-circle
 """
 import argparse
 import os
@@ -72,7 +79,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fsrl_amd.agent import CPOAgent, CVPOAgent, DDPGLagAgent, FOCOPSAgent, PPOLagAgent, SACLagAgent, TRPOLagAgent  # noqa: E402
-from fsrl_amd.env import ShmemVectorEnv, SyntheticSafetyVectorEnv  # noqa: E402
+from fsrl_amd.env import DeviceLinear, DevicePointCircle, PointCircleEnv, ShmemVectorEnv, SyntheticSafetyVectorEnv  # noqa: E402
 from fsrl_amd.utils import BaseLogger  # noqa: E402
 
 AGENTS = {"ppol": PPOLagAgent, "cpo": CPOAgent, "trpol": TRPOLagAgent, "focops": FOCOPSAgent, "sacl": SACLagAgent,
@@ -83,6 +90,36 @@ def make_env(a, seed):
     if a.workers:
         return ShmemVectorEnv(env_num=a.envs, workers=a.workers, obs_dim=8, act_dim=2, episode_len=300, seed=seed, busy_us=a.busy_us)
     return SyntheticSafetyVectorEnv(env_num=a.envs, obs_dim=8, act_dim=2, episode_len=300, seed=seed)
+
+
+def make_seed(a, seed, **agent_kw):
+    """a seed's agent and the vector env it collects from.  --task device-*: the agent is built over a host env of the task's shapes,
+    the envs it collects from live on its engine's GPU"""
+    host = PointCircleEnv() if a.task == "device-point-circle" else make_env(a, seed)
+    logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
+    agent = AGENTS[a.algo](host, logger, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes, training_num=a.envs, **agent_kw)
+    agent.policy.train()
+    if a.task == "device-point-circle":
+        return agent, DevicePointCircle(agent.policy, a.envs, max_episode_steps=300, seed=seed)
+    if a.task == "device-linear":
+        return agent, DeviceLinear(agent.policy, like=host, seed=seed)
+    return agent, host
+
+
+def make_collector(a, agent, env, buf):
+    from fsrl_amd.data import DeviceCollector, FastCollector
+    if a.task.startswith("device-"):
+        return DeviceCollector(agent.policy, env, buf)
+    return FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True)
+
+
+def make_group_collector(a, group_of, cols):
+    """device envs: every seed's whole collect in one looping launch; else lock step through `group_of()`'s shared actor request"""
+    from fsrl_amd.data import GroupCollector, GroupDeviceCollector
+    if a.task.startswith("device-"):
+        return None, GroupDeviceCollector(cols)
+    g = group_of()
+    return g, GroupCollector(g, cols)
 
 
 # --sweep: PPOLagAgent keywords (float; `none` where the agent takes None) and the two update arguments (int)
@@ -121,22 +158,17 @@ GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo", "cpo", "trpol")     
 def run_grouped_trust(a):
     """k CPO (TRPO-Lag) seeds: lock-step collection from one host thread (a collect group over the seeds' on-policy engines), each
     seed's pre_update_fn, then ONE TrustPolicyGroup.update -- the seeds' own updates on a worker thread each -- and reset_buffer."""
-    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
+    from fsrl_amd.data import HipVectorReplayBuffer
     from fsrl_amd.engine import EngineCollectGroup
     from fsrl_amd.policy import TrustPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = make_env(a, seed)
-        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
-                               training_num=a.envs)
-        agent.policy.train()
+        agent, env = make_seed(a, seed, cost_limit=10.0)
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
-        cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
-    cgroup = EngineCollectGroup([ag.policy.engine for ag in agents])
+        cols.append(make_collector(a, agent, env, buf))
+    cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
     group = TrustPolicyGroup([ag.policy for ag in agents], collect_group=cgroup)
-    gcol = GroupCollector(cgroup, cols)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -158,11 +190,12 @@ def run_grouped_trust(a):
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
     group.close()
-    cgroup.close()
+    if cgroup is not None:
+        cgroup.close()
+    for col in cols:
+        col.env.close()              # a device env goes before the engine it lives on
     for ag in agents:
         ag.policy.engine.close()
-    for col in cols:
-        col.env.close()
 
 
 def run_grouped_replay(a):
@@ -170,26 +203,21 @@ def run_grouped_replay(a):
     run their pre_update_fn (SAC-Lag / DDPG-Lag: the PID multiplier's step; CVPO: the M-step multipliers' reset), then ONE grouped
     update runs each seed's round(update_per_step * n/st) updates (what OffpolicyTrainer.policy_update_fn runs per seed), then each
     seed's post_update_fn.  --per-alpha: every seed's buffer is prioritised (made before the group: its members agree on that)."""
-    from fsrl_amd.data import FastCollector, GroupCollector, HipPrioritizedVectorReplayBuffer, HipVectorReplayBuffer
+    from fsrl_amd.data import HipPrioritizedVectorReplayBuffer, HipVectorReplayBuffer
     per = prioritized_replay(a)
     from fsrl_amd.engine import EngineCollectGroup
     from fsrl_amd.policy import CVPOPolicyGroup, DDPGPolicyGroup, SACPolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = make_env(a, seed)
-        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
-        agent = AGENTS[a.algo](env, logger, cost_limit=10.0, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes,
-                               training_num=a.envs)
-        agent.policy.train()
+        agent, env = make_seed(a, seed, cost_limit=10.0)
         if per is None:
             buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         else:
             buf = HipPrioritizedVectorReplayBuffer(agent.policy.engine, None, a.envs, **per)
         agents.append(agent); bufs.append(buf)
-        cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
+        cols.append(make_collector(a, agent, env, buf))
     group = {"sacl": SACPolicyGroup, "ddpgl": DDPGPolicyGroup, "cvpo": CVPOPolicyGroup}[a.algo]([ag.policy for ag in agents])
-    cgroup = EngineCollectGroup([ag.policy.engine for ag in agents])
-    gcol = GroupCollector(cgroup, cols)
+    cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
     update_per_step, t0, steps, updates = 0.2, time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -213,12 +241,13 @@ def run_grouped_replay(a):
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
-    cgroup.close()
+    if cgroup is not None:
+        cgroup.close()
     group.close()
+    for col in cols:
+        col.env.close()              # a device env goes before the engine it lives on
     for ag in agents:
         ag.policy.engine.close()
-    for col in cols:
-        col.env.close()
 
 
 def run_grouped(a):
@@ -229,23 +258,20 @@ def run_grouped(a):
         return run_grouped_replay(a)
     if a.algo in ("cpo", "trpol"):
         return run_grouped_trust(a)
-    from fsrl_amd.data import FastCollector, GroupCollector, HipVectorReplayBuffer
+    from fsrl_amd.data import HipVectorReplayBuffer
     from fsrl_amd.policy import PolicyGroup
     agents, cols, bufs = [], [], []
     for seed in range(a.seeds):
-        env = make_env(a, seed)
-        logger = BaseLogger(tempfile.mkdtemp(prefix=f"fsrl_amd_s{seed}_"), name=f"{a.algo}-s{seed}")
         kw = dict(cost_limit=10.0)
         kw.update({name: vals[seed] for name, vals in a.sweep.items() if name in SWEEP_AGENT_KEYS})       # a sweep: member i's own values
-        agent = AGENTS[a.algo](env, logger, device=a.device, seed=seed, hidden_sizes=a.hidden_sizes, training_num=a.envs, **kw)
-        agent.policy.train()
+        agent, env = make_seed(a, seed, **kw)
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
-        cols.append(FastCollector(agent.policy, env, buf, exploration_noise=True, device_actor=True))
+        cols.append(make_collector(a, agent, env, buf))
     group = PolicyGroup([ag.policy for ag in agents])
     batch_size, repeat = a.sweep.get("batch_size", 256), a.sweep.get("repeat_per_collect", 4)       # ints, or one int per member
     mult = (lambda p: f"nu {float(p._nu):.3f}") if a.algo == "focops" else (lambda p: f"lambda {p.lag_optims[0].get_lag():.3f}")
-    gcol = GroupCollector(group, cols)
+    _, gcol = make_group_collector(a, lambda: group, cols)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -267,10 +293,10 @@ def run_grouped(a):
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
     group.close()
+    for col in cols:
+        col.env.close()              # a device env goes before the engine it lives on
     for ag in agents:
         ag.policy.engine.close()
-    for col in cols:
-        col.env.close()
 
 
 def prioritized_replay(a):
@@ -292,6 +318,9 @@ def parse_args(argv=None):
     ap.add_argument("--epoch", type=int, default=2)
     ap.add_argument("--envs", type=int, default=20)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--task", choices=["linear", "device-linear", "device-point-circle"], default="linear",
+                    help="linear: the in-process synthetic env (or --workers); device-*: the seeds' envs live on the GPU and --grouped runs "
+                         "every seed's whole collect in one looping launch (GroupDeviceCollector)")
     ap.add_argument("--grouped", action="store_true", help="PPO-Lag / FOCOPS / SAC-Lag / DDPG-Lag / CVPO: lock-step collection and grouped updates from one thread; "
                                                            "CPO / TRPO-Lag: lock-step collection, the seeds' own updates beside each other")
     ap.add_argument("--hidden-sizes", default="128x128", type=lambda t: tuple(int(w) for w in t.lower().split("x")),
@@ -325,6 +354,12 @@ def parse_args(argv=None):
     clip = a.sweep.get("max_grad_norm")
     if clip and len({bool(v) for v in clip}) > 1:
         ap.error("--sweep max_grad_norm: the members must agree on whether the clip is on (all values > 0, or all none / 0)")
+    if a.task != "linear" and not a.grouped:
+        ap.error("--task device-*: the grouped device collect of this example (--grouped); one seed's device env: the agents' learn()")
+    if a.task != "linear" and a.workers:
+        ap.error("--task device-*: the envs live on the GPU, there are no worker processes (--workers 0)")
+    if a.task != "linear" and a.envs > 64:
+        ap.error("--task device-*: a device env holds at most 64 envs per seed")
     if a.workers < 0 or a.workers > a.envs:
         ap.error("--workers: 0 (in-process envs) .. --envs")
     if isinstance(a.hidden_sizes, str):

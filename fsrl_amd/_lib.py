@@ -119,6 +119,7 @@ SIGNATURES = {
     "fsrl_store_read": (C.c_int, [_ctx, _i64, C.c_int64, _f, _f, _d, _d, _u8, _u8, _f]),
     "fsrl_store_configure": (C.c_int, [_ctx, C.c_int64, C.c_int32]),
     "fsrl_store_geometry": (C.c_int, [_ctx, _i64, _i32]),
+    "fsrl_store_version": (C.c_int, [_ctx, _P(C.c_uint64)]),
     "fsrl_store_sample0": (C.c_int, [_ctx, _i64, C.c_int64, _i64]),
     "fsrl_actor_forward": (C.c_int, [_ctx, _f, C.c_int32, _f, _f]),
     "fsrl_ppo_begin": (C.c_int, [_ctx, _d, C.c_double, C.c_int32, _i64]),
@@ -247,6 +248,8 @@ SIGNATURES = {
     "fsrl_devenv_set_state": (C.c_int, [_ctx, _f, _i32, _i64]),
     "fsrl_collect_device": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,
                                       _i32, _i32]),
+    "fsrl_collect_device_group": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
+                                            _i32, _d, _i32, _i32, _i32]),
     "fsrl_set_profiling": (C.c_int, [_ctx, C.c_int]),
     "fsrl_last_timing": (C.c_int, [_ctx, _d, C.c_int32]),
 }

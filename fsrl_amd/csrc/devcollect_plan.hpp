@@ -61,6 +61,40 @@ DC_HD bool dc_complete(int32_t episodes, int32_t n_episode) { return episodes >=
 DC_HD int64_t dc_slot(int32_t e, int64_t sub_size, int32_t index) { return (int64_t)e * sub_size + index; }
 DC_HD int32_t dc_next_index(int32_t index, int64_t sub_size) { return (int64_t)index + 1 >= sub_size ? 0 : index + 1; }     // index < sub_size: (index + 1) % sub_size without the division
 
+// ---- how many launches a collect may take.  Every launch that is not the last takes max_steps vector steps, each of which stores at
+// least one row: at most ceil(n_episode x max_episode_steps / max_steps) + 1 launches finish any collect.
+DC_HD int64_t dc_launch_cap(int32_t n_episode, int32_t max_episode_steps, int32_t max_steps) {
+    return ((int64_t)n_episode * max_episode_steps + max_steps - 1) / max_steps + 1;
+}
+
+// ---- k collects in one launch (fsrl_collect_device_group).  The members' episode arrays are concatenated in member order:
+// off[i] = n_episode[0] + .. + n_episode[i - 1], off[k] = the total.
+DC_HD void dc_group_offsets(const int32_t* n_episode, int32_t k, int64_t* off) {
+    off[0] = 0;
+    for (int32_t i = 0; i < k; ++i) off[i + 1] = off[i] + n_episode[i];
+}
+// the launch goes on until EVERY member is finished, so its cap is the largest of the members' caps
+DC_HD int64_t dc_group_launch_cap(const int32_t* n_episode, const int32_t* max_episode_steps, int32_t k, int32_t max_steps) {
+    int64_t cap = 0;
+    for (int32_t i = 0; i < k; ++i) {
+        const int64_t c = dc_launch_cap(n_episode[i], max_episode_steps[i], max_steps);
+        cap = c > cap ? c : cap;
+    }
+    return cap;
+}
+// "a launch made no step" holds against the members that were UNFINISHED going in only: a finished member's workgroup breaks at the
+// loop's first test and reports 0 steps every time.  Returns the first member that was unfinished and made no step, or -1.
+DC_HD int32_t dc_group_stalled(const uint8_t* was_finished, const int32_t* steps, int32_t k) {
+    for (int32_t i = 0; i < k; ++i)
+        if (!was_finished[i] && steps[i] == 0) return i;
+    return -1;
+}
+DC_HD bool dc_group_complete(const uint8_t* finished, int32_t k) {
+    for (int32_t i = 0; i < k; ++i)
+        if (!finished[i]) return false;
+    return true;
+}
+
 // ---- host replay.  BOOK has the fields of the store's per-env bookkeeping (index, size, last_index, ep_rew, ep_len, ep_idx); one log
 // row moves them exactly as fsrl_store_push moves them for one pushed row.  Returns true when the row ends an episode; then
 // *ep_rew / *ep_len hold the episode's return and length (what the push reports in ep_rew_out / ep_len_out).

@@ -950,6 +950,12 @@ extern "C" int fsrl_store_geometry(const fsrl_ctx* c, int64_t* sub_size_out, int
     return 0;
 }
 
+extern "C" int fsrl_store_version(const fsrl_ctx* c, uint64_t* version_out) {
+    CHECK_ARG(c && version_out, "null argument");
+    *version_out = c->store_version;
+    return 0;
+}
+
 extern "C" int64_t fsrl_store_len(const fsrl_ctx* c) {
     int64_t n = 0;
     if (c) for (const EnvBook& e : c->env) n += e.size;
@@ -1563,6 +1569,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_sac_group_layered.inc"
 #include "host_cvpo_group_layered.inc"
 #include "host_group_episodes.inc"
+#include "host_devcollect_group.inc"
 
 #include "host_comm.inc"
 

@@ -9,6 +9,8 @@
 // Replay contexts (SAC-Lag, DDPG-Lag, CVPO): the same kernel with their fused actor's parameters and its head arithmetic on the device
 // (DC_HEAD_GAUSS / DC_HEAD_DDPG); with prioritised replay on, a small launch behind every collect launch gives the rows' slots their
 // leaves (host_per.inc per_devcollect).
+// Grouped seeds: fsrl_collect_device_group (host_devcollect_group.inc) runs k members' collects as the k workgroups of one launch,
+// with this file's checks, entry and replay per member (devcollect_check, devcollect_begin, devcollect_replay).
 #include "kernels_devcollect.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head);      // defined with the SAC / CVPO code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -26,6 +28,10 @@ struct fsrl_devenv {
     DcLogRow* d_log = nullptr; DcLogRow* h_log = nullptr; int log_steps = 0;
     int32_t* d_slot = nullptr;          // [log_steps][env_num]: the log rows' store slots (prioritised replay's leaves)
     DevCollectArgs* d_args = nullptr; DevCollectArgs* h_args = nullptr;     // the collect kernel's arguments: device / pinned
+    // fsrl_collect_device_group (host_devcollect_group.inc), made by the env's first grouped collect and kept
+    hipEvent_t g_ready = nullptr;       // this member's compute stream as the grouped collect found it
+    hipEvent_t g_done = nullptr;        // member 0's env: behind the grouped launch
+    DevCollectGroupTable* d_tab = nullptr; DevCollectGroupTable* h_tab = nullptr;      // member 0's env: the member table, device / pinned
 };
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
 static DevEnvParams devenv_params(const fsrl_devenv* v) {
@@ -66,6 +72,10 @@ static void devenv_free(fsrl_devenv* v) {
     if (v->d_slot) (void)hipFree(v->d_slot);
     if (v->d_args) (void)hipFree(v->d_args);
     if (v->h_args) (void)hipHostFree(v->h_args);
+    if (v->g_ready) (void)hipEventDestroy(v->g_ready);
+    if (v->g_done) (void)hipEventDestroy(v->g_done);
+    if (v->d_tab) (void)hipFree(v->d_tab);
+    if (v->h_tab) (void)hipHostFree(v->h_tab);
     delete v;
 }
 
@@ -249,13 +259,15 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
     return 0;
 }
 
-// ---- the collect.  Everything that can refuse the call is checked before anything is touched.
+// ---- the collect.  Everything that can refuse the call is checked before anything is touched.  solo: fsrl_collect_device, which
+// refuses grouped contexts; fsrl_collect_device_group (host_devcollect_group.inc) runs the same checks on every member without that clause.
 static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
-                            const float* act_high, int32_t max_steps) {
+                            const float* act_high, int32_t max_steps, bool solo = true) {
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
     CHECK_ARG(!c->lay, "device collects are not supported on layered contexts yet");
-    CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
+    if (solo)
+        CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
         const float* P; const ModelDesc* md;
         CHECK_ARG(sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md),
@@ -263,7 +275,7 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
         CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
     }
     CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
-    if (c->in_update) return fail(FSRL_ESTATE, "fsrl_collect_device inside an update");
+    if (c->in_update) return fail(FSRL_ESTATE, "%s inside an update", solo ? "fsrl_collect_device" : "fsrl_collect_device_group");
     CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
     CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
@@ -276,18 +288,16 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     return 0;
 }
 
-extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                                   const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
-                                   double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
-                                   int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
-    int rc = devcollect_check(c, v, n_episode, bound_method, act_low, act_high, max_steps_per_launch);
-    if (rc) return rc;
-    CHECK_ARG(steps_out && total_cost_out && term_count_out && trunc_count_out && ep_rew_out && ep_len_out && episodes_out, "null output");
-    const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
+// What a collect does on entry, for one context: its resident actor ends (and through the release hooks its group's), the env's own
+// stream is waited for, the staging window lands, the log holds max_steps vector steps, and the initial DcState and the kernel's
+// arguments go up on the context's compute stream.  *P / *md / *head: whose actor the kernel runs.
+struct DcActor { const float* P; const ModelDesc* md; int head; };
+static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                            const float* act_low, const float* act_high, int max_steps, DcActor* actor) {
     const int n = v->cfg.env_num, Da = v->cfg.act_dim;
     ENTER_DEV(c);                                   // a live resident actor ends first
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
-    rc = join_store(c);                             // rows in the staging window land first; the side stream is in front of the kernel
+    int rc = join_store(c);                         // rows in the staging window land first; the side stream is in front of the kernel
     if (rc) return rc;
     if (v->log_steps < max_steps) {
         if (v->d_log) HIPCHK(hipFree(v->d_log));
@@ -317,22 +327,64 @@ extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episod
     a.max_action = c->cfg.max_action;
     a.magic_per = div_magic(2 * v->cfg.obs_dim + Da); a.magic_da = div_magic(Da);
     // whose actor: the context's own networks, or a replay context's fused actor with its head arithmetic
-    int head = DC_HEAD_ONPOLICY;
-    const float* P = c->P; const ModelDesc* md = &c->md;
+    actor->head = DC_HEAD_ONPOLICY; actor->P = c->P; actor->md = &c->md;
     if (ctx_is_replay(c)) {
-        if (!sac_actor_resident_args(c, &P, &md) || !sac_devcollect_head(c, &a, &head)) return fail(FSRL_ESTATE, "no fused actor network");
+        if (!sac_actor_resident_args(c, &actor->P, &actor->md) || !sac_devcollect_head(c, &a, &actor->head))
+            return fail(FSRL_ESTATE, "no fused actor network");
         rc = sac_devcollect_enter(c);
         if (rc) return rc;
         a.slots = c->per ? v->d_slot : nullptr;
     }
-    const ModelDesc mdv = *md;
     HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));
-    int64_t rows = 0;
-    double total_cost = 0.0;
-    int32_t terms = 0, truncs = 0, episodes = 0, launches = 0;
-    // every launch that is not the last takes max_steps vector steps, each of which stores at least one row: at most
-    // ceil(n_episode x max_episode_steps / max_steps) + 1 launches finish any collect
-    const int64_t launch_cap = ((int64_t)n_episode * v->cfg.max_episode_steps + max_steps - 1) / max_steps + 1;
+    return 0;
+}
+
+// One launch's log (in v->h_log, hs = what the kernel reported) through the bookkeeping of fsrl_store_push, row by row in the
+// kernel's order; the collect's running totals
+struct DcTotals { int64_t rows = 0; double total_cost = 0.0; int32_t terms = 0, truncs = 0, episodes = 0; };
+static bool devcollect_state_sane(const DcState& hs, int max_steps, int n) {
+    return hs.log_rows >= 0 && hs.log_rows <= max_steps * n && hs.steps >= 0 && hs.steps <= max_steps;
+}
+static int devcollect_replay(fsrl_ctx* c, fsrl_devenv* v, const DcState& hs, int32_t n_episode, DcTotals& t, double* ep_rew_out,
+                             int32_t* ep_len_out) {
+    const int n = v->cfg.env_num;
+    for (int i = 0; i < hs.log_rows; ++i) {
+        const DcLogRow& r = v->h_log[i];
+        if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device collect: log row %d names env %d", i, r.env);
+        double er = 0.0; int32_t el = 0;
+        const bool done = dc_replay_row(c->env[(size_t)r.env], c->sub_size, c->h_flags.data(), r, &er, &el);
+        t.total_cost += r.cost;
+        t.terms += (int32_t)(r.flags & 1u); t.truncs += (int32_t)((r.flags >> 1) & 1u);
+        if (done) {
+            if (t.episodes < n_episode) { ep_rew_out[t.episodes] = er; ep_len_out[t.episodes] = el; }
+            ++t.episodes;
+        }
+    }
+    t.rows += hs.log_rows;
+    c->store_version += (uint64_t)hs.steps;          // one bump per pushed vector step
+    return 0;
+}
+
+extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                   const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                   double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                   int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    int rc = devcollect_check(c, v, n_episode, bound_method, act_low, act_high, max_steps_per_launch);
+    if (rc) return rc;
+    CHECK_ARG(steps_out && total_cost_out && term_count_out && trunc_count_out && ep_rew_out && ep_len_out && episodes_out, "null output");
+    const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
+    const int n = v->cfg.env_num;
+    DcActor actor{};
+    rc = devcollect_begin(c, v, n_episode, deterministic, bound_method, act_low, act_high, max_steps, &actor);
+    if (rc) return rc;
+    DcState& hs = *v->h_state;
+    const bool per = v->h_args->slots != nullptr;
+    hipStream_t s = c->compute;
+    const float* P = actor.P; const int head = actor.head;
+    const ModelDesc mdv = *actor.md;
+    DcTotals t;
+    int32_t launches = 0;
+    const int64_t launch_cap = dc_launch_cap(n_episode, v->cfg.max_episode_steps, max_steps);
     for (;;) {
         if (launches >= launch_cap) return fail(FSRL_ESTATE, "device collect: %d launches did not finish %d episodes", launches, n_episode);
         rc = dispatch_H(c->cfg.hidden, [&](auto hc) {
@@ -348,46 +400,34 @@ extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episod
             return 0;
         });
         if (rc) return rc;
-        if (a.slots) {      // PrioritizedReplayBuffer.add for the launch's rows: their number is DcState::log_rows, on the device
+        if (per) {          // PrioritizedReplayBuffer.add for the launch's rows: their number is DcState::log_rows, on the device
             rc = per_devcollect(c, v->d_slot, &v->d_state->log_rows, max_steps * n);
             if (rc) return rc;
         }
         ++launches;
         HIPCHK(hipMemcpyAsync(&hs, v->d_state, sizeof(DcState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (hs.log_rows < 0 || hs.log_rows > max_steps * n || hs.steps < 0 || hs.steps > max_steps)
+        if (!devcollect_state_sane(hs, max_steps, n))
             return fail(FSRL_ESTATE, "device collect: the kernel reported %d rows in %d steps", hs.log_rows, hs.steps);
         if (hs.log_rows > 0) {
             HIPCHK(hipMemcpyAsync(v->h_log, v->d_log, (size_t)hs.log_rows * sizeof(DcLogRow), hipMemcpyDeviceToHost, s));     // the log: ONE copy
             HIPCHK(hipStreamSynchronize(s));
         }
-        // ---- replay: the bookkeeping of fsrl_store_push, row by row in the kernel's order
-        for (int i = 0; i < hs.log_rows; ++i) {
-            const DcLogRow& r = v->h_log[i];
-            if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device collect: log row %d names env %d", i, r.env);
-            double er = 0.0; int32_t el = 0;
-            const bool done = dc_replay_row(c->env[(size_t)r.env], c->sub_size, c->h_flags.data(), r, &er, &el);
-            total_cost += r.cost;
-            terms += (int32_t)(r.flags & 1u); truncs += (int32_t)((r.flags >> 1) & 1u);
-            if (done) {
-                if (episodes < n_episode) { ep_rew_out[episodes] = er; ep_len_out[episodes] = el; }
-                ++episodes;
-            }
-        }
-        rows += hs.log_rows;
-        c->store_version += (uint64_t)hs.steps;          // one bump per pushed vector step
+        rc = devcollect_replay(c, v, hs, n_episode, t, ep_rew_out, ep_len_out);
+        if (rc) return rc;
         if (hs.finished) break;
         if (hs.steps == 0) return fail(FSRL_ESTATE, "device collect: a launch made no step");
     }
-    if (episodes != hs.episodes) return fail(FSRL_ESTATE, "device collect: the log holds %d episodes, the kernel counted %d", episodes, hs.episodes);
+    if (t.episodes != hs.episodes)
+        return fail(FSRL_ESTATE, "device collect: the log holds %d episodes, the kernel counted %d", t.episodes, hs.episodes);
     // FastCollector.reset_env at the end of every collect: ALL envs
     DevEnvIo io{};
     io.n = n;
     rc = devenv_reset_launch(v, io, s);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
-    *steps_out = rows; *total_cost_out = total_cost; *term_count_out = terms; *trunc_count_out = truncs;
-    *episodes_out = std::min(episodes, n_episode);
+    *steps_out = t.rows; *total_cost_out = t.total_cost; *term_count_out = t.terms; *trunc_count_out = t.truncs;
+    *episodes_out = std::min(t.episodes, n_episode);
     if (launches_out) *launches_out = launches;
     return 0;
 }

@@ -61,11 +61,12 @@ struct DevCollectSmem {
     float eact[DC_MAX_ENVS * FSRL_MAX_ACT];     // mapped into the env's range
 };
 
-template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
-__global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __restrict__ P, const ModelDesc md, const DevCollectArgs* __restrict__ ap) {
+// The collect of ONE workgroup: the whole loop above over (P, md, ap).  collect_device_kernel runs it on its own arguments,
+// collect_device_group_kernel on its member's row of the table; nothing in it knows which.
+template <int H, class Env, int HEAD>
+__device__ __forceinline__ void collect_device_body(const float* __restrict__ P, const ModelDesc& md, const DevCollectArgs* __restrict__ ap,
+                                                    TileSmem<H>& sm, DevCollectSmem& sh) {
     const DevCollectArgs& a = *ap;
-    __shared__ TileSmem<H> sm;
-    __shared__ DevCollectSmem sh;
     constexpr int NT = TileGeom<H>::NT;
     constexpr int NX = TileStage<H>::NX;
     const int tid = threadIdx.x;
@@ -195,4 +196,44 @@ __global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __re
         a.state->n_live = sh.n_live; a.state->episodes = sh.episodes; a.state->finished = sh.finished;
         a.state->steps = step; a.state->log_rows = log_rows;
     }
+}
+
+template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
+__global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __restrict__ P, const ModelDesc md, const DevCollectArgs* __restrict__ ap) {
+    __shared__ TileSmem<H> sm;
+    __shared__ DevCollectSmem sh;
+    collect_device_body<H, Env, HEAD>(P, md, ap, sm, sh);
+}
+
+// ---- k collects in one launch (fsrl_collect_device_group): grid k, workgroup b runs member b's collect, the loop above unchanged.
+// The members share nothing -- each has its own store, env arrays, DcState and log -- and the workgroups do not communicate: no
+// flags, no waits on another block's data; a member that is finished breaks at the loop's first test and reports 0 steps, 0 rows.
+// Per-member inputs come from a table in device memory (by value they would fill the scalar file: Registers above); md is member 0's,
+// the host checks that the members agree on what it describes.  blockIdx.x and the two pointers are workgroup-uniform: scalar registers.
+#ifndef FSRL_MAX_GROUP
+#define FSRL_MAX_GROUP 16
+#endif
+struct DevCollectGroupTable {
+    const float* P[FSRL_MAX_GROUP];
+    const DevCollectArgs* a[FSRL_MAX_GROUP];
+};
+// A pointer read from memory is a flat pointer to the compiler, and a flat load never becomes a scalar load.  AS = 1 says that it is
+// global; AS = 4 that what it points to is constant for the length of the kernel (the arguments: nothing writes them while a launch
+// runs), which is what the solo kernel's `const __restrict__` kernel argument says: the fields are read with scalar loads, whenever
+// they are needed, and none of them has to stay in a vector register across tile_forward.
+template <int AS, class T>
+__device__ __forceinline__ const T* dc_uniform_ptr(const T* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    typedef const T __attribute__((address_space(AS))) * SpacePtr;
+    return (const T*)(SpacePtr)(((unsigned long long)hi << 32) | lo);
+}
+template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
+__global__ __launch_bounds__(4 * H) void collect_device_group_kernel(const ModelDesc md, const DevCollectGroupTable* __restrict__ tab) {
+    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const float* P = dc_uniform_ptr<1>(tab->P[b]);
+    const DevCollectArgs* ap = dc_uniform_ptr<4>(tab->a[b]);
+    __shared__ TileSmem<H> sm;
+    __shared__ DevCollectSmem sh;
+    collect_device_body<H, Env, HEAD>(P, md, ap, sm, sh);
 }

@@ -7,6 +7,7 @@ install(__name__, globals(), {
     "HipPrioritizedVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
     "DeviceCollector": "device_collector",
+    "GroupDeviceCollector": "device_collector",
     "GroupCollector": "group_collector",
     "BasicCollector": "basic_collector",
     "TrajectoryBuffer": "traj_buf",

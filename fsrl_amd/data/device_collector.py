@@ -4,11 +4,34 @@ launches and one small read-back per collect instead of one doorbell round trip 
 same store contents and episode-exact behaviour (surplus envs dropped, every env reset at the end of a collect) as `FastCollector`;
 the action noise comes from the env's Philox stream, not from the library's xoshiro stream.  On-policy and replay
 policies alike (SAC-Lag, DDPG-Lag, CVPO: the actor's head arithmetic runs on the device too; a prioritised buffer's leaves follow
-the rows); layered and grouped engines are refused by the library, with the reason."""
+the rows); layered engines are refused by the library, with the reason, and so is a `DeviceCollector` of its own on a grouped engine.
+
+Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
+through `GroupDeviceCollector(collectors)`: ONE launch per `max_steps_per_launch` vector steps carries every member's collect, a
+workgroup per member (fsrl_collect_device_group), and each member's rows, env states, statistics and counters are what its own
+`DeviceCollector.collect` would have produced, bit for bit.  `GroupCollector` over `DeviceCollector`s delegates to it."""
 import time
-from typing import Any, Dict
+from typing import Any, Dict, List, Sequence, Union
 
 import numpy as np
+
+
+def _collect_args(pol):
+    """deterministic, bound method and bounds as FastCollector._collect_fused derives them"""
+    det = bool(pol._deterministic_eval and not pol.training)
+    space = pol.action_space
+    bound = {"": 0, "clip": 1, "tanh": 2}[pol.action_bound_method] if space is not None else 0
+    low = np.asarray(space.low, np.float32) if (space is not None and pol.action_scaling) else None
+    high = np.asarray(space.high, np.float32) if low is not None else None
+    return det, bound, low, high
+
+
+def _collect_stats(r):
+    n_ep = len(r["ep_rews"])
+    done_count = r["terminated"] + r["truncated"]
+    return {"n/ep": n_ep, "n/st": r["steps"], "rew": float(r["ep_rews"].mean()), "len": float(r["ep_lens"].mean()),
+            "total_cost": r["total_cost"], "cost": r["total_cost"] / n_ep, "truncated": r["truncated"] / done_count,
+            "terminated": r["terminated"] / done_count}
 
 
 class DeviceCollector:
@@ -57,20 +80,55 @@ class DeviceCollector:
         t0 = time.time()
         if hasattr(pol, "_drain"):
             pol._drain()
-        # deterministic, bound method and bounds as FastCollector._collect_fused derives them
-        det = bool(pol._deterministic_eval and not pol.training)
-        space = pol.action_space
-        bound = {"": 0, "clip": 1, "tanh": 2}[pol.action_bound_method] if space is not None else 0
-        low = np.asarray(space.low, np.float32) if (space is not None and pol.action_scaling) else None
-        high = np.asarray(space.high, np.float32) if low is not None else None
+        det, bound, low, high = _collect_args(pol)
         r = eng.collect_device(self.env._h, n_episode, det, bound, low, high, self.max_steps_per_launch)
         self.last_launches = r["launches"]
         self.buffer.sync_sizes()
-        n_ep = len(r["ep_rews"])
         self.collect_step += r["steps"]
-        self.collect_episode += n_ep
+        self.collect_episode += len(r["ep_rews"])
         self.collect_time += max(time.time() - t0, 1e-9)
-        done_count = r["terminated"] + r["truncated"]
-        return {"n/ep": n_ep, "n/st": r["steps"], "rew": float(r["ep_rews"].mean()), "len": float(r["ep_lens"].mean()),
-                "total_cost": r["total_cost"], "cost": r["total_cost"] / n_ep, "truncated": r["truncated"] / done_count,
-                "terminated": r["terminated"] / done_count}
+        return _collect_stats(r)
+
+
+class GroupDeviceCollector:
+    """`DeviceCollector.collect` of every member in one looping launch (fsrl_collect_device_group).  collectors: one `DeviceCollector`
+    per seed; the seeds' engines may be members of any kind of group, or of none."""
+
+    def __init__(self, collectors: Sequence[DeviceCollector], max_steps_per_launch: int = 0):
+        self.collectors = list(collectors)
+        assert self.collectors, "a group collector needs at least one collector"
+        assert all(isinstance(c, DeviceCollector) for c in self.collectors), "GroupDeviceCollector: every collector is a DeviceCollector"
+        self.max_steps_per_launch = int(max_steps_per_launch)
+        self.last_launches = 0
+
+    def collect(self, n_episode: Union[int, Sequence[int]] = 1, **_ignored) -> List[Dict[str, Any]]:
+        """n_episode: one count or one per member -> one stats dict per member, with the keys of DeviceCollector.collect"""
+        from fsrl_amd.engine import collect_device_group
+        cols = self.collectors
+        n = len(cols)
+        ns = [int(n_episode)] * n if np.isscalar(n_episode) else [int(x) for x in n_episode]
+        assert len(ns) == n and all(x > 0 for x in ns), "n_episode: a positive count, or one per member"
+        t0 = time.time()
+        args = []
+        for col in cols:
+            if hasattr(col.policy, "_drain"):
+                col.policy._drain()
+            args.append(_collect_args(col.policy))
+        # one library call carries every member: they must agree on what the call takes once
+        assert len({a[0] for a in args}) == 1 and len({a[1] for a in args}) == 1, "members must agree on deterministic / action_bound_method"
+        assert len({a[2] is None for a in args}) == 1, "members must agree on action_scaling"
+        det, bound = args[0][0], args[0][1]
+        lows = None if args[0][2] is None else np.stack([a[2] for a in args])
+        highs = None if args[0][2] is None else np.stack([a[3] for a in args])
+        res = collect_device_group([col.policy.engine for col in cols], [col.env._h for col in cols], ns, det, bound, lows, highs,
+                                   self.max_steps_per_launch)
+        dt = max(time.time() - t0, 1e-9)
+        stats = []
+        for col, r in zip(cols, res):
+            col.last_launches = self.last_launches = r["launches"]
+            col.buffer.sync_sizes()
+            col.collect_step += r["steps"]
+            col.collect_episode += len(r["ep_rews"])
+            col.collect_time += dt
+            stats.append(_collect_stats(r))
+        return stats

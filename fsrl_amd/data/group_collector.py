@@ -30,6 +30,12 @@ class GroupCollector:
         self.native_loop = bool(native_loop)
         engines = getattr(self.group, "engines", None)
         assert self.collectors, "a group collector needs at least one collector"
+        # device envs: every member's whole collect in one looping launch (GroupDeviceCollector), no lock step on the host
+        from fsrl_amd.data.device_collector import DeviceCollector, GroupDeviceCollector
+        n_dev = sum(isinstance(col, DeviceCollector) for col in self.collectors)
+        assert n_dev in (0, len(self.collectors)), \
+            "GroupCollector: a mix of DeviceCollectors and other collectors; a group collects on the device with every member or with none"
+        self.device = GroupDeviceCollector(self.collectors, max(c.max_steps_per_launch for c in self.collectors)) if n_dev else None
         for i, col in enumerate(self.collectors):
             assert col.device_actor, "GroupCollector: collectors with device_actor=True"
             assert col.buffer is not None, "GroupCollector: every collector has its member's buffer"
@@ -41,6 +47,8 @@ class GroupCollector:
     def collect(self, n_episode: Union[int, Sequence[int]] = 1) -> List[Dict[str, Any]]:
         """FastCollector.collect(n_episode) of every member (n_episode: one count or one per member) -> one stats dict per member.
         The group's resident actor kernel lives for the length of this call."""
+        if self.device is not None:
+            return self.device.collect(n_episode)
         try:
             stats = self._collect(n_episode)
             for buf in {id(b): b for b in (c._traj_buffer() for c in self.collectors) if b is not None}.values():

@@ -248,6 +248,12 @@ class Engine:
         _lib.check(self.lib.fsrl_store_geometry(self._ctx, C.byref(sub), C.byref(num)))
         return int(sub.value), int(num.value)
 
+    def store_version(self):
+        """the store's version: bumped by every push (per vector step) and every reset (fsrl_store_version)"""
+        v = C.c_uint64()
+        _lib.check(self.lib.fsrl_store_version(self._ctx, C.byref(v)))
+        return int(v.value)
+
     def sample0(self):
         n = C.c_int64()
         cap = len(self)
@@ -1019,6 +1025,39 @@ class TrajArchive:
         out = np.zeros(len(TRAJ_COUNTERS), np.int64)
         _lib.check(self.lib.fsrl_traj_counters(self._t, _ptr(out, _i64p), out.size))
         return dict(zip(TRAJ_COUNTERS, (int(v) for v in out)))
+
+
+def collect_device_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
+                         max_steps_per_launch=0):
+    """Engine.collect_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_collect_device_group):
+    member i's collect is Engine.collect_device on it, bit for bit.  The engines may be ungrouped or members of any kind of group.
+    env_handles: each engine's devenv handle; n_episodes: one count or one per member; lows / highs: None or one row per member.
+    -> one dict per member with the keys of Engine.collect_device (`launches` is the call's)."""
+    engines = list(engines)
+    k = len(engines)
+    assert len(env_handles) == k, "one device env per engine"
+    n_ep = np.ascontiguousarray(np.broadcast_to(np.asarray(n_episodes, np.int32), (k,)) if k else np.zeros(0, np.int32))
+    lib = engines[0].lib if k else _lib.load()
+    ctxs = (C.c_void_p * max(k, 1))(*[e._ctx for e in engines])
+    envs = (C.c_void_p * max(k, 1))(*[h if isinstance(h, C.c_void_p) else C.c_void_p(h) for h in env_handles])
+    lo = hi = None
+    if lows is not None and k:
+        Da = engines[0].cfg.act_dim
+        lo = np.ascontiguousarray(np.asarray(lows, np.float32).reshape(k, Da))
+        hi = np.ascontiguousarray(np.asarray(highs, np.float32).reshape(k, Da))
+    off = np.concatenate([[0], np.cumsum(np.maximum(n_ep, 0), dtype=np.int64)])
+    tot = max(int(off[-1]), 1)
+    steps, cost = np.zeros(max(k, 1), np.int64), np.zeros(max(k, 1), np.float64)
+    nt, ntr, nep = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
+    ep_rew, ep_len = np.zeros(tot, np.float64), np.zeros(tot, np.int32)
+    nl = C.c_int32()
+    _lib.check(lib.fsrl_collect_device_group(
+        ctxs, envs, k, _ptr(n_ep, _i32p), int(bool(deterministic)), int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p),
+        int(max_steps_per_launch), _ptr(steps, _i64p), _ptr(cost, _f64p), _ptr(nt, _i32p), _ptr(ntr, _i32p), _ptr(ep_rew, _f64p),
+        _ptr(ep_len, _i32p), _ptr(nep, _i32p), C.byref(nl)))
+    return [dict(steps=int(steps[i]), total_cost=float(cost[i]), terminated=int(nt[i]), truncated=int(ntr[i]),
+                 ep_rews=ep_rew[off[i]:off[i] + nep[i]].copy(), ep_lens=ep_len[off[i]:off[i] + nep[i]].copy(), launches=int(nl.value))
+            for i in range(k)]
 
 
 class _NativeGroup:

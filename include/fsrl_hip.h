@@ -188,6 +188,10 @@ int fsrl_store_read(fsrl_ctx* ctx, const int64_t* indices, int64_t n, float* obs
  * allocation of fsrl_ctx_create (cfg.buffer_size rows, cfg.env_num sub-buffers), else FSRL_EINVAL; empties the store. */
 int fsrl_store_configure(fsrl_ctx* ctx, int64_t total_size, int32_t buffer_num);
 int fsrl_store_geometry(const fsrl_ctx* ctx, int64_t* sub_size_out, int32_t* buffer_num_out);
+/* The store's version: 1 at creation, bumped by every push (one per call, i.e. per vector step) and every reset; device copies of
+ * the bookkeeping and samples drawn ahead are valid for one version.  For tests that hold two ways of filling a store against
+ * each other. */
+int fsrl_store_version(const fsrl_ctx* ctx, uint64_t* version_out);
 /* buffer.sample_indices(0): env-major, chronological inside each sub-buffer.             */
 int fsrl_store_sample0(fsrl_ctx* ctx, int64_t* indices_out, int64_t cap, int64_t* n_out);
 
@@ -1041,6 +1045,30 @@ int fsrl_collect_device(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int3
                         const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
                         double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
                         int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_collect_device_group   k seeds' collects in ONE looping launch: workgroup i of every launch runs member i's collect, the
+ *                            loop of fsrl_collect_device on member i's store, envs and Philox counters, so that a member's rows, env
+ *                            states, statistics and store_version are those of fsrl_collect_device on it, bit for bit.  1 <= k <= 16.
+ *                            A free function over contexts: a member may be ungrouped or belong to an fsrl_group, an
+ *                            fsrl_collect_group, an fsrl_sac_group or an fsrl_cvpo_group (its group's resident kernel is ended
+ *                            first); fsrl_collect_device on such a context stays refused.  n_episode [k]; act_low / act_high
+ *                            [k][act_dim] or both NULL; deterministic, bound_method and max_steps_per_launch are the call's.
+ *                            Outputs per member: steps / total_cost / term_count / trunc_count / episodes [k]; ep_rew / ep_len
+ *                            concatenated in member order, member i at offset n_episode[0] + .. + n_episode[i - 1] (sum of n_episode
+ *                            entries); *launches_out (may be NULL): launches of the collect kernel, until EVERY member is finished
+ *                            (a finished member's workgroup idles through the later ones).  The launches go on member 0's compute
+ *                            stream, behind every member's compute stream; every launch is waited for.  Prioritised members get
+ *                            their leaves by their own small launch behind each collect launch.  At the end ALL envs of ALL members
+ *                            are reset.
+ *                            Refused before anything changes, the message naming the member and the reason: k outside 1..16; a
+ *                            context or env listed twice; members on several devices; whatever fsrl_collect_device refuses of a
+ *                            member, the grouped clause apart; members that differ in obs_dim, act_dim, hidden or n_critics, in the
+ *                            env kind or max_episode_steps, in the head kind (on-policy | SAC-Lag, CVPO | DDPG-Lag), in `unbounded`
+ *                            (on-policy) or actor_mean (replay).  env_num, n_episode, env seeds, bounds, max_action, and prioritised
+ *                            replay on or off may differ.  */
+int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                              int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                              int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                              double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 
 #ifdef __cplusplus
 }

@@ -15,11 +15,24 @@ sampler, enqueued, statistics drained once per collect), device collect against 
 
     python tools/bench_device_collect.py --rounds 3 --out profiles/device_collect.json
     python tools/bench_device_collect.py --algo sacl --rounds 3 --out profiles/device_collect_replay.json
+
+--ks 1,2,4,8 measures grouped seeds instead (on-policy contexts, k seeds on one GPU), aggregate env-steps/s over the k seeds:
+
+  (a) grouped    GroupDeviceCollector: fsrl_collect_device_group, the k collects as the k workgroups of one looping launch
+  (b) solo_seq   k solo device collects one after the other, on ungrouped twins
+  (c) lock_step  GroupCollector over in-process envs with the EngineGroup's resident actor: one request per vector step for all seeds
+
+--ab-tree DIR (with --ks) also holds the SOLO device collect of this tree against another checkout's (DIR: a built tree, e.g. the
+parent commit), the two tools run as processes of their own, alternating; both sets of numbers go to --out.
+
+    python tools/bench_device_collect.py --ks 1,2,4,8 --ab-tree ../parent --rounds 3 --out profiles/device_collect_group.json
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -27,7 +40,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fsrl_amd import _lib  # noqa: E402
 from fsrl_amd.data import DeviceCollector, FastCollector, HipVectorReplayBuffer  # noqa: E402
-from fsrl_amd.engine import Engine, EngineConfig  # noqa: E402
+from fsrl_amd.engine import Engine, EngineConfig, EngineGroup  # noqa: E402
 from fsrl_amd.env import Box, DeviceLinear, SyntheticSafetyVectorEnv  # noqa: E402
 
 EPISODE_LEN = 300
@@ -99,6 +112,108 @@ def timed_loop(eng, col, n, calls, algo, update_per_step, batch):
     return rows, time.perf_counter() - t0, k
 
 
+def setup_group(path, hidden, n, k):
+    """k on-policy seeds for one of the grouped paths -> (engines, envs, EngineGroup or None, an object with .collect(n) -> stats per seed)"""
+    from fsrl_amd.data import GroupCollector, GroupDeviceCollector
+    engs, envs, cols = [], [], []
+    for i in range(k):
+        eng = Engine(EngineConfig(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN), device=0)
+        eng.set_params((0.1 * np.random.default_rng(i).standard_normal(eng.n_params)).astype(np.float32))
+        host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1 + i)
+        pol, buf = Pol(eng), HipVectorReplayBuffer(eng, n * 2 * EPISODE_LEN, n)
+        if path == "lock_step":
+            cols.append(FastCollector(pol, host, buf, device_actor=True))
+        else:
+            envs.append(DeviceLinear(eng, like=host, seed=1 + i))
+            cols.append(DeviceCollector(pol, envs[-1], buf))
+        engs.append(eng)
+    group = EngineGroup(engs) if path != "solo_seq" else None
+
+    class Seq:
+        collectors = cols
+
+        def collect(self, n_episode):
+            return [c.collect(n_episode=n_episode) for c in cols]
+    col = Seq() if path == "solo_seq" else GroupDeviceCollector(cols) if path == "grouped" else GroupCollector(group, cols)
+    return engs, envs, group, col
+
+
+def timed_group(col, n, calls):
+    def reset():
+        for c in col.collectors:
+            c.reset_buffer()
+    reset()
+    col.collect(n)
+    reset()
+    rows, t0 = 0, time.perf_counter()
+    for _ in range(calls):
+        rows += sum(st["n/st"] for st in col.collect(n))
+        reset()
+    return rows, time.perf_counter() - t0
+
+
+def summary(rates):
+    return dict(median=float(np.median(rates)), spread=float(np.max(rates) - np.min(rates)), rounds=[float(r) for r in rates])
+
+
+def solo_ab(a):
+    """the solo device collect of this tree against the tree at a.ab_tree: each tool in a process of its own, one round per process,
+    alternating; per (hidden, env_num) the rates of both"""
+    tools = {"tree": os.path.abspath(__file__), "other": os.path.join(os.path.abspath(a.ab_tree), "tools", "bench_device_collect.py")}
+    rates = {}
+    for _ in range(a.rounds):
+        for who, tool in tools.items():
+            with tempfile.TemporaryDirectory() as tmp:
+                out = os.path.join(tmp, "r.json")
+                env = {k: v for k, v in os.environ.items() if k != "FSRL_HIP_LIB"}
+                subprocess.run([sys.executable, tool, "--rounds", "1", "--calls", str(a.calls), "--envs", a.envs, "--hidden", a.hidden, "--out", out],
+                               check=True, stdout=subprocess.DEVNULL, env=env, cwd=os.path.dirname(os.path.dirname(tool)), timeout=600)
+                with open(out) as f:
+                    for c in json.load(f)["configs"]:
+                        rates.setdefault((c["hidden"][0], c["env_num"]), {}).setdefault(who, []).append(c["device"]["median"])
+    res = []
+    for (hidden, n), r in sorted(rates.items(), reverse=True):
+        res.append(dict(hidden=[hidden, hidden], env_num=n, tree=summary(r["tree"]), other=summary(r["other"])))
+        print(json.dumps(res[-1]), flush=True)
+    return res
+
+
+def main_groups(a):
+    paths = ("grouped", "solo_seq", "lock_step")
+    result = dict(metric="aggregate env-steps/s of k seeds' collects on one GPU, training mode, linear env obs 8 / act 2, episode length 300, "
+                         "on-policy contexts", rounds=a.rounds, calls=a.calls, configs=[])
+    for hidden in (int(h) for h in a.hidden.split(",")):
+        for n in (int(e) for e in a.envs.split(",")):
+            for k in (int(x) for x in a.ks.split(",")):
+                objs = {p: setup_group(p, hidden, n, k) for p in paths}
+                rates = {p: [] for p in paths}
+                for _ in range(a.rounds):
+                    for p in paths:
+                        rows, dt = timed_group(objs[p][3], n, a.calls)
+                        rates[p].append(rows / dt)
+                cfg = dict(hidden=[hidden, hidden], env_num=n, k=k, launches_per_collect=objs["grouped"][3].last_launches)
+                for p in paths:
+                    cfg[p] = summary(rates[p])
+                result["configs"].append(cfg)
+                print(json.dumps(cfg), flush=True)
+                for engs, envs, group, col in objs.values():
+                    for env in envs:
+                        env.close()
+                    if group is not None:
+                        group.close()
+                    for eng in engs:
+                        eng.close()
+    if a.ab_tree:
+        result["solo_tree_vs_other"] = dict(what="solo fsrl_collect_device, env-steps/s: this tree against the tree it was measured next to (the "
+                                                 "parent commit), processes alternating, one round per process", configs=solo_ab(a))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    print(json.dumps(dict(device_collect_group=[(c["hidden"][0], c["env_num"], c["k"], round(c["grouped"]["median"]), round(c["solo_seq"]["median"]),
+                                                 round(c["lock_step"]["median"])) for c in result["configs"]])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", choices=["onpolicy", "sacl", "ddpgl", "cvpo"], default="onpolicy")
@@ -109,7 +224,11 @@ def main():
     ap.add_argument("--envs", default="20,64")
     ap.add_argument("--hidden", default="256,64")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ks", default=None, help="group sizes, e.g. 1,2,4,8: measure grouped seeds (on-policy) instead")
+    ap.add_argument("--ab-tree", default=None, help="with --ks: another built checkout whose solo device collect this tree's is held against")
     a = ap.parse_args()
+    if a.ks:
+        return main_groups(a)
     paths = ("device", "in_process", "stepped")
     result = dict(metric="env-steps/s of a collect loop, training mode, linear env obs 8 / act 2, episode length 300", rounds=a.rounds,
                   calls=a.calls, configs=[])
