@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 import devenv_model as dm
+import devenv_replay_model as rm
+from devcollect_rows import action_draws, check_action, check_collect_rows, check_continuous, check_discontinuous
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -37,19 +39,21 @@ class Pol:
             self.action_space.low[:], self.action_space.high[:] = low_high
 
 
-def make(kind, n, H=64, rows_per_env=200, seed=3, algo=None, sub_buffers=None, **cfg):
-    """-> (engine with fixed random parameters, device env of `kind`: 'pc' | 'lin8' | 'lin33')"""
+def make(kind, n, H=64, rows_per_env=200, seed=3, algo=None, sub_buffers=None, oracle_params=False, **cfg):
+    """-> (engine with fixed random parameters, device env of `kind`: 'pc' or a linear shape of devenv_replay_model.SHAPES).
+    oracle_params: set the fixed parameters on a context made with hidden_sizes too (two unrelated widths that the device pads),
+    through the oracle's layout, which is what set_params takes"""
     from fsrl_amd.engine import Engine, EngineConfig
     from fsrl_amd.env import DeviceLinear, DevicePointCircle, SyntheticSafetyVectorEnv
     from fsrl_amd.env.synthetic import stable_coupling
-    Do, Da = {"pc": (6, 2), "lin8": (8, 2), "lin33": (33, 8)}[kind]
+    Do, Da = rm.SHAPES[kind]
     kw = dict(obs_dim=Do, act_dim=Da, hidden=H, env_num=sub_buffers or n, buffer_size=(sub_buffers or n) * rows_per_env)
     if algo is not None:
         kw["algo"] = algo
     kw.update(cfg)
     eng = Engine(EngineConfig(**kw), device=0)
-    if algo is None and "hidden_sizes" not in cfg:
-        eng.set_params((0.3 * np.random.default_rng(7).standard_normal(eng.n_params)).astype(F32))
+    if algo is None and ("hidden_sizes" not in cfg or oracle_params):
+        eng.set_params(rm.onpolicy_params(eng.n_params))
     if kind == "pc":
         env = DevicePointCircle(eng, n, max_episode_steps=7, seed=seed, **PC)
     else:
@@ -70,21 +74,6 @@ def same_rows(a, b):
 
 def same_state(ea, eb):
     return all(np.array_equal(x, y) for x, y in zip(ea.get_state(), eb.get_state()))
-
-
-def check_discontinuous(dev_cost, dev_term, r32, what):
-    share, near = dm.band_share(r32)
-    print(f"{what}: rows within the band {share:.4f}")
-    assert share <= dm.BAND_CAP, what
-    assert np.array_equal(np.asarray(dev_cost)[~near], r32["cost"][~near]), what
-    assert np.array_equal(np.asarray(dev_term, bool)[~near], r32["terminated"][~near]), what
-
-
-def check_continuous(dev, r64, r32, scale, what):
-    d_dev, d_r32, bound = dm.yardstick(dev, r64, r32, scale)
-    print(f"{what}: device {d_dev:.3e} from float64, float32 restatement {d_r32:.3e}, bound {bound:.3e}")
-    assert d_dev <= bound, (what, d_dev, d_r32)
-    return d_dev, d_r32
 
 
 # ------------------------------------------------------------------------------------------------ 1. the env alone
@@ -147,11 +136,15 @@ def test_env_alone_one_step_from_injected_states(name):
     ("lin8", 1, (2, 1), "clip", None),
 ])
 def test_deterministic_collect_is_the_existing_path_bit_for_bit(kind, n, episodes, bound, low_high):
+    deterministic_collect_twins(kind, n, episodes, bound, low_high)
+
+
+def deterministic_collect_twins(kind, n, episodes, bound, low_high, **make_kw):
     """twin contexts, twin envs: FastCollector(device_actor=True) over DeviceVectorEnv.step (_collect_fused) against DeviceCollector"""
     from fsrl_amd.data import DeviceCollector, FastCollector, HipVectorReplayBuffer
     out = []
     for device in (False, True):
-        eng, env = make(kind, n, rows_per_env=6)               # 6-row sub-buffers: a full episode (7 steps) wraps its sub-buffer
+        eng, env = make(kind, n, rows_per_env=6, **make_kw)    # 6-row sub-buffers: a full episode (7 steps) wraps its sub-buffer
         pol = Pol(eng, bound, low_high)
         buf = HipVectorReplayBuffer(eng, n * 6, n)
         col = DeviceCollector(pol, env, buf) if device else FastCollector(pol, env, buf, device_actor=True)
@@ -197,21 +190,6 @@ def test_deterministic_collect_under_tanh_is_the_existing_path_to_tolerance():
 
 
 # ------------------------------------------------------------------------------------------------ 3. stochastic collects, row by row
-def rows_with_counters(eng, env, ord0, rows_idx, rows):
-    """(env, ordinal, t) of every stored row: rows of an env are chronological, the first one continues at (ord0 - 1, 0)"""
-    sub, _ = eng.store_geometry()
-    e = (rows_idx // sub).astype(np.int64)
-    ordinal, t = np.zeros(len(e), np.int64), np.zeros(len(e), np.int64)
-    first = np.zeros(len(e), bool)
-    cur = {}
-    for i, ei in enumerate(e):
-        o, tt = cur.get(int(ei), (int(ord0[ei]) - 1, 0))
-        ordinal[i], t[i], first[i] = o, tt, tt == 0
-        done = rows["terminated"][i] or rows["truncated"][i]
-        cur[int(ei)] = (o + 1, 0) if done else (o, tt + 1)
-    return e, ordinal, t, first
-
-
 @pytest.mark.parametrize("kind,n,n_ep", [("pc", 17, 25), ("lin33", 5, 12), ("lin8", 64, 70), ("lin8", 1, 3)])
 def test_stochastic_collect_row_by_row_against_the_model(kind, n, n_ep):
     eng, env = make(kind, n, seed=11)
@@ -219,61 +197,13 @@ def test_stochastic_collect_row_by_row_against_the_model(kind, n, n_ep):
     _, t0, ord0 = env.get_state()
     assert np.all(t0 == 0) and np.all(ord0 == 1)
     res = eng.collect_device(env._h, n_ep, deterministic=False, bound_method=1)
-    idx, rows = store_rows(eng)
-    key = dm.key_of(11)
-    Do, Da = eng.cfg.obs_dim, eng.cfg.act_dim
-    e, ordinal, t, first = rows_with_counters(eng, env, ord0, idx, rows)
-    done = rows["terminated"] | rows["truncated"]
-    # ---- episode count, time limit, statistics
-    assert done.sum() == n_ep == len(res["ep_rews"]) and res["steps"] == len(idx)
-    assert np.array_equal(rows["truncated"], t == 6) and np.all(t <= 6)
-    ep_rew, ep_len, acc = [], [], {}
-    for i in range(len(idx)):                                   # float64 sums over the stored rows, in order
-        r_, l_ = acc.get(int(e[i]), (0.0, 0))
-        r_, l_ = r_ + rows["rew"][i], l_ + 1
-        if done[i]:
-            ep_rew.append(r_); ep_len.append(l_); r_, l_ = 0.0, 0
-        acc[int(e[i])] = (r_, l_)
-    assert sorted(ep_rew) == sorted(res["ep_rews"].tolist()) and sorted(ep_len) == sorted(res["ep_lens"].tolist())
-    assert res["total_cost"] == rows["cost"].sum() and res["terminated"] == rows["terminated"].sum() and res["truncated"] == rows["truncated"].sum()
-    # ---- the action noise: (act - mu) / sigma is the model's normal of (env, ordinal, t, dim)
-    mu, sigma = eng.actor_forward(rows["obs"])
-    mu, sigma = mu.astype(F64), sigma.astype(F64)
-    d = np.arange(Da)[None, :]
-    eps64 = dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_ACT, d, F64)
-    eps32 = dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_ACT, d, F32)
-    act32 = (mu.astype(F32) + sigma.astype(F32) * eps32).astype(F32)
-    scale = np.maximum(dm.normal_scale(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_ACT, d), (np.abs(mu) + np.abs(sigma * eps64)) / sigma)
-    check_continuous((rows["act"].astype(F64) - mu) / sigma, eps64, (act32.astype(F64) - mu) / sigma, scale, f"{kind} action noise")
-    # ---- the transition: obs_next, rew, cost, terminated from (obs, mapped act, model noise)
-    env_act = dm.map_action(rows["act"], 1)
-    if kind == "pc":
-        r64 = dm.point_step(rows["obs"][:, :4], env_act, PC["radius"], PC["x_lim"], PC["dt"], F64)
-        r32 = dm.point_step(rows["obs"][:, :4], env_act, PC["radius"], PC["x_lim"], PC["dt"], F32)
-    else:
-        dd = np.arange(Do)[None, :]
-        nz = [dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_STEP, dd, dt_) for dt_ in (F64, F32)]
-        r64 = dm.linear_step(rows["obs"], env_act, env.A, env.B, nz[0], env.cost_threshold, F64)
-        r32 = dm.linear_step(rows["obs"], env_act, env.A, env.B, nz[1], env.cost_threshold, F32)
-    check_continuous(rows["obs_next"], r64["obs_next"], r32["obs_next"], r32["obs_scale"], f"{kind} obs_next")
-    check_continuous(rows["rew"], r64["rew"], r32["rew"], r32["rew_scale"], f"{kind} rew")
-    check_discontinuous(rows["cost"], rows["terminated"], r32, kind)
-    if kind == "pc":
-        assert rows["cost"].sum() > 0 and rows["terminated"].sum() > 0
-    # ---- chaining: inside an episode obs_next[t] is obs[t + 1], bit for bit; an episode starts at the model's reset draw
-    same_env_next = (e[1:] == e[:-1]) & ~done[:-1]
-    assert np.array_equal(rows["obs_next"][:-1][same_env_next], rows["obs"][1:][same_env_next]) and same_env_next.sum() > 0
-    if kind == "pc":
-        st0, ob0 = dm.point_reset(key, e[first], ordinal[first], PC["radius"], PC["x_lim"], F32)
-        assert np.array_equal(rows["obs"][first], ob0)
-    else:
-        dd = np.arange(Do)[None, :]
-        ef, of = e[first][:, None], ordinal[first][:, None]
-        check_continuous(rows["obs"][first], dm.normal(key, ef, of, 0, dm.STREAM_RESET, dd, F64), dm.normal(key, ef, of, 0, dm.STREAM_RESET, dd, F32),
-                         dm.normal_scale(key, ef, of, 0, dm.STREAM_RESET, dd), f"{kind} first obs")
-    # every env was reset at the end of the collect
-    _, t1, ord1 = env.get_state()
-    assert np.all(t1 == 0) and np.all(ord1 >= 2)
+
+    def action(rows, e, ordinal, t, key):
+        # the action noise: (act - mu) / sigma is the model's normal of (env, ordinal, t, dim)
+        mu, sigma = eng.actor_forward(rows["obs"])
+        eps64, eps32, nscale = action_draws(rows, e, ordinal, t, key, eng.cfg.act_dim)
+        return check_action("onpolicy", rows["act"], mu, sigma, eps64, eps32, False, nscale, f"{kind} action noise")
+    check_collect_rows(eng, env, ord0, res, n_ep, kind, 11, kind, action)
     env.close(); eng.close()
 
 

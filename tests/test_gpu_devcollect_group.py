@@ -54,12 +54,16 @@ def group_collect(engs, envs, n_eps, **kw):
 def test_onpolicy_members_of_an_update_group_equal_their_twins():
     """env_num 1 / 17 / 64, n_episode 3 / 25 / 70, 8 vector steps per launch: the members finish in different launches and the
     finished workgroups are launched again idle; then new parameters on everyone and a second collect"""
+    onpolicy_members_equal_their_twins(64)
+
+
+def onpolicy_members_equal_their_twins(H):
     from fsrl_amd.engine import EngineGroup
     ns, n_eps = (1, 17, 64), (3, 25, 70)
     lows = np.array([[-2.0, -0.5], [-1.0, -1.5], [-0.25, -3.0]], F32)
     highs = np.array([[0.5, 1.0], [2.0, 0.75], [1.5, 0.5]], F32)
-    mem = [on.make("lin8", n, rows_per_env=6, seed=3 + i) for i, n in enumerate(ns)]
-    twin = [on.make("lin8", n, rows_per_env=6, seed=3 + i) for i, n in enumerate(ns)]
+    mem = [on.make("lin8", n, H=H, rows_per_env=6, seed=3 + i) for i, n in enumerate(ns)]
+    twin = [on.make("lin8", n, H=H, rows_per_env=6, seed=3 + i) for i, n in enumerate(ns)]
     group = EngineGroup([e for e, _ in mem])
     for _, v in mem + twin:
         v.reset()
@@ -93,11 +97,15 @@ def test_onpolicy_members_of_an_update_group_equal_their_twins():
 def test_replay_members_equal_their_twins(agent, kind):
     """SAC-Lag members of an EngineSacGroup with prioritised replay on (leaves, max_prio, min_prio and the root too), DDPG-Lag
     members of an EngineCollectGroup, CVPO members of an EngineCvpoGroup; k = 2, unequal env_num and n_episode, 9-row sub-buffers"""
+    replay_members_equal_their_twins(agent, kind, 64)
+
+
+def replay_members_equal_their_twins(agent, kind, H):
     from fsrl_amd.engine import EngineCollectGroup, EngineCvpoGroup, EngineSacGroup
     ns, n_eps = (5, 17), (12, 20)
     per = (0.6, 0.4) if agent == "sacl" else None
-    mem = [rp.make(agent, kind, n, rows_per_env=9, seed=5 + i, per=per) for i, n in enumerate(ns)]
-    twin = [rp.make(agent, kind, n, rows_per_env=9, seed=5 + i, per=per) for i, n in enumerate(ns)]
+    mem = [rp.make(agent, kind, n, H=H, rows_per_env=9, seed=5 + i, per=per) for i, n in enumerate(ns)]
+    twin = [rp.make(agent, kind, n, H=H, rows_per_env=9, seed=5 + i, per=per) for i, n in enumerate(ns)]
     Group = {"sacl": EngineSacGroup, "ddpgl": EngineCollectGroup, "cvpo": EngineCvpoGroup}[agent]
     group = Group([e for e, _ in mem])
     for _, v in mem + twin:

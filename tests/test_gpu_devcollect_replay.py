@@ -13,8 +13,8 @@ compared bit for bit, against the same rows pushed one vector step at a time int
 import numpy as np
 import pytest
 
-import devenv_model as dm
 import devenv_replay_model as rm
+from devcollect_rows import action_draws, check_action, check_collect_rows
 
 pytestmark = pytest.mark.gpu
 F32, F64 = np.float32, np.float64
@@ -23,8 +23,10 @@ LAG, RESC = [0.5], 1 / 1.5
 ROW_KEYS = ("obs", "act", "rew", "cost", "terminated", "truncated", "obs_next")
 
 
-def make(agent, kind, n, H=64, rows_per_env=200, seed=3, sub_buffers=None, init=True, per=None, **cfg):
-    """-> (replay engine of `agent` with fixed random actor and critic parameters, device env of `kind`)"""
+def make(agent, kind, n, H=64, rows_per_env=200, seed=3, sub_buffers=None, init=True, per=None, unbounded=None,
+         exploration_sigma=rm.EXPLORATION_SIGMA, **cfg):
+    """-> (replay engine of `agent` with fixed random actor and critic parameters, device env of `kind`).  unbounded: the actor-mean
+    option of SAC-Lag and CVPO (None: the agent's default); max_action goes to the EngineConfig with the rest of cfg"""
     from fsrl_amd import _lib
     from fsrl_amd.engine import Engine, EngineConfig
     from fsrl_amd.env import DeviceLinear, DevicePointCircle
@@ -34,11 +36,11 @@ def make(agent, kind, n, H=64, rows_per_env=200, seed=3, sub_buffers=None, init=
     eng = Engine(EngineConfig(**kw), device=0)
     if init:
         if agent == "sacl":
-            eng.sac_init()
+            eng.sac_init(unbounded=unbounded)
         elif agent == "ddpgl":
-            eng.sac_init(deterministic=True, exploration_sigma=rm.EXPLORATION_SIGMA)
+            eng.sac_init(deterministic=True, exploration_sigma=exploration_sigma)
         else:
-            eng.cvpo_init(qc_thres=5.0)
+            eng.cvpo_init(qc_thres=5.0, unbounded=unbounded)
         if "hidden_sizes" not in cfg:
             eng.sac_put_params(0, rm.actor_params(eng.n_sac_actor))           # the actor of the CPU test's closed loop
             eng.sac_put_params(1, (0.15 * np.random.default_rng(8).standard_normal(eng.n_sac_critics)).astype(F32))
@@ -60,36 +62,6 @@ def store_rows(eng):
 
 def same_rows(a, b):
     return all(np.array_equal(a[k], b[k]) for k in ROW_KEYS)
-
-
-def check_discontinuous(dev_cost, dev_term, r32, what):
-    share, near = dm.band_share(r32)
-    print(f"{what}: rows within the band {share:.4f}")
-    assert share <= dm.BAND_CAP, what
-    assert np.array_equal(np.asarray(dev_cost)[~near], r32["cost"][~near]), what
-    assert np.array_equal(np.asarray(dev_term, bool)[~near], r32["terminated"][~near]), what
-
-
-def check_continuous(dev, r64, r32, scale, what):
-    d_dev, d_r32, bound = dm.yardstick(dev, r64, r32, scale)
-    print(f"{what}: device {d_dev:.3e} from float64, float32 restatement {d_r32:.3e}, bound {bound:.3e}")
-    assert d_dev <= bound, (what, d_dev, d_r32)
-    return d_dev, d_r32
-
-
-def rows_with_counters(eng, ord0, rows_idx, rows):
-    """(env, ordinal, t) of every stored row: rows of an env are chronological, the first one continues at (ord0 - 1, 0)"""
-    sub, _ = eng.store_geometry()
-    e = (rows_idx // sub).astype(np.int64)
-    ordinal, t = np.zeros(len(e), np.int64), np.zeros(len(e), np.int64)
-    first = np.zeros(len(e), bool)
-    cur = {}
-    for i, ei in enumerate(e):
-        o, tt = cur.get(int(ei), (int(ord0[ei]) - 1, 0))
-        ordinal[i], t[i], first[i] = o, tt, tt == 0
-        done = rows["terminated"][i] or rows["truncated"][i]
-        cur[int(ei)] = (o + 1, 0) if done else (o, tt + 1)
-    return e, ordinal, t, first
 
 
 def push_collects(eng, rows, queues, n, n_eps):
@@ -128,66 +100,23 @@ def test_collect_row_by_row_against_the_model(agent, kind, n, n_ep, deterministi
     _, t0, ord0 = env.get_state()
     assert np.all(t0 == 0) and np.all(ord0 == 1)
     res = eng.collect_device(env._h, n_ep, deterministic=deterministic, bound_method=1)
-    idx, rows = store_rows(eng)
-    key = dm.key_of(rm.ENV_SEED)
-    Do, Da = eng.cfg.obs_dim, eng.cfg.act_dim
-    e, ordinal, t, first = rows_with_counters(eng, ord0, idx, rows)
-    done = rows["terminated"] | rows["truncated"]
     what = f"{agent} {kind} n={n} {'deterministic' if deterministic else 'training'}"
-    # ---- episode count, time limit, statistics
-    assert done.sum() == n_ep == len(res["ep_rews"]) and res["steps"] == len(idx)
-    assert np.array_equal(rows["truncated"], t == 6) and np.all(t <= 6)
-    ep_rew, ep_len, acc = [], [], {}
-    for i in range(len(idx)):                                   # float64 sums over the stored rows, in order
-        r_, l_ = acc.get(int(e[i]), (0.0, 0))
-        r_, l_ = r_ + rows["rew"][i], l_ + 1
-        if done[i]:
-            ep_rew.append(r_); ep_len.append(l_); r_, l_ = 0.0, 0
-        acc[int(e[i])] = (r_, l_)
-    assert sorted(ep_rew) == sorted(res["ep_rews"].tolist()) and sorted(ep_len) == sorted(res["ep_lens"].tolist())
-    assert res["total_cost"] == rows["cost"].sum() and res["terminated"] == rows["terminated"].sum() and res["truncated"] == rows["truncated"].sum()
-    # ---- the action: the agent's formula over (m, sigma) of the row's observation and the model's draw of (env, ordinal, t, dim)
+    rows, _ = check_collect_rows(eng, env, ord0, res, n_ep, kind, rm.ENV_SEED, what,
+                                 lambda rows, e, ordinal, t, key: replay_action_check(eng, agent, deterministic, what, rows, e, ordinal, t, key))
+    env.close(); eng.close()
+
+
+def replay_action_check(eng, agent, deterministic, what, rows, e, ordinal, t, key):
+    """the stored action against the agent's formula over (m, sigma) of the row's observation (Engine.sac_actor_forward) and the
+    model's draw of (env, ordinal, t, dim)"""
     mu, sigma = eng.sac_actor_forward(rows["obs"])
-    d = np.arange(Da)[None, :]
-    eps64 = dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_ACT, d, F64)
-    eps32 = dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_ACT, d, F32)
-    act64 = rm.action(agent, mu, sigma, eps64, deterministic, F64)
-    act32 = rm.action(agent, mu, sigma, eps32, deterministic, F32)
-    check_continuous(rows["act"], act64, act32, rm.action_scale(mu, sigma, eps64, deterministic), what + " act")
+    eps64, eps32, nscale = action_draws(rows, e, ordinal, t, key, eng.cfg.act_dim)
+    dist = check_action(agent, rows["act"], mu, sigma, eps64, eps32, deterministic, nscale, what + " act")
     if agent == "sacl":
         assert np.abs(rows["act"]).max() <= 1.0 and 0.05 < np.mean(np.abs(rows["act"]) < 0.99)      # squashed, and not all saturated
     if not deterministic:
         assert np.abs(rows["act"].astype(F64) - rm.action(agent, mu, sigma, 0 * eps64, True, F64)).max() > 1e-3      # the noise is in
-    # ---- the transition: obs_next, rew, cost, terminated from (obs, mapped act, model noise)
-    env_act = dm.map_action(rows["act"], 1)
-    if kind == "pc":
-        r64 = dm.point_step(rows["obs"][:, :4], env_act, PC["radius"], PC["x_lim"], PC["dt"], F64)
-        r32 = dm.point_step(rows["obs"][:, :4], env_act, PC["radius"], PC["x_lim"], PC["dt"], F32)
-    else:
-        dd = np.arange(Do)[None, :]
-        nz = [dm.normal(key, e[:, None], ordinal[:, None], t[:, None], dm.STREAM_STEP, dd, dt_) for dt_ in (F64, F32)]
-        r64 = dm.linear_step(rows["obs"], env_act, env.A, env.B, nz[0], env.cost_threshold, F64)
-        r32 = dm.linear_step(rows["obs"], env_act, env.A, env.B, nz[1], env.cost_threshold, F32)
-    check_continuous(rows["obs_next"], r64["obs_next"], r32["obs_next"], r32["obs_scale"], what + " obs_next")
-    check_continuous(rows["rew"], r64["rew"], r32["rew"], r32["rew_scale"], what + " rew")
-    check_discontinuous(rows["cost"], rows["terminated"], r32, what)
-    if kind == "pc":
-        assert rows["cost"].sum() > 0 and rows["terminated"].sum() > 0
-    # ---- chaining: inside an episode obs_next[t] is obs[t + 1], bit for bit; an episode starts at the model's reset draw
-    same_env_next = (e[1:] == e[:-1]) & ~done[:-1]
-    assert np.array_equal(rows["obs_next"][:-1][same_env_next], rows["obs"][1:][same_env_next]) and same_env_next.sum() > 0
-    if kind == "pc":
-        st0, ob0 = dm.point_reset(key, e[first], ordinal[first], PC["radius"], PC["x_lim"], F32)
-        assert np.array_equal(rows["obs"][first], ob0)
-    else:
-        dd = np.arange(Do)[None, :]
-        ef, of = e[first][:, None], ordinal[first][:, None]
-        check_continuous(rows["obs"][first], dm.normal(key, ef, of, 0, dm.STREAM_RESET, dd, F64), dm.normal(key, ef, of, 0, dm.STREAM_RESET, dd, F32),
-                         dm.normal_scale(key, ef, of, 0, dm.STREAM_RESET, dd), what + " first obs")
-    # every env was reset at the end of the collect
-    _, t1, ord1 = env.get_state()
-    assert np.all(t1 == 0) and np.all(ord1 >= 2)
-    env.close(); eng.close()
+    return dist
 
 
 # ------------------------------------------------------------------------------------------------ 2. the store is as pushes would leave it
