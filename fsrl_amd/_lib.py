@@ -94,6 +94,7 @@ _ctx = C.c_void_p
 SIGNATURES = {
     "fsrl_last_error": (C.c_char_p, []),
     "fsrl_config_default": (None, [_P(Config)]),
+    "fsrl_mem_live": (C.c_int, [_i64, _i64, _i64, _i64]),
     "fsrl_ctx_create": (C.c_int, [C.c_int, _P(Config), _P(_ctx)]),
     "fsrl_ctx_destroy": (C.c_int, [_ctx]),
     "fsrl_sync": (C.c_int, [_ctx]),

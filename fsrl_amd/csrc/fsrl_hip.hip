@@ -27,6 +27,7 @@
 #include "kernels_focops_group.hpp"
 #include "resident_ring.hpp"
 #include "host_decisions.hpp"
+#include "dev_mem.hpp"
 
 // ------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -93,6 +94,7 @@ static inline size_t stage_rec_bytes(int Do, int Da) { return ((size_t)24 + 4 * 
 struct fsrl_group;
 struct fsrl_ctx {
     fsrl_config cfg{};
+    Mem mem;                       // owns every device / pinned block of this context itself (dev_mem.hpp); the sub-states own theirs
     fsrl_group* group = nullptr;   // set while the context is a member of a grouped-update set (host_group.inc)
     struct CommState* comm = nullptr;   // RCCL communicator of the metric exchange (host_comm.inc), owned
     int device = 0;
@@ -137,7 +139,7 @@ struct fsrl_ctx {
     int batch_size = 0, mbp_max = 0, n_tiles_max = 0;
     float *A1 = nullptr, *A2 = nullptr, *D1 = nullptr, *D2 = nullptr, *DO = nullptr;
     float *obs_p = nullptr, *rd_p = nullptr;   // pass-ordered batch (+32 pad rows)
-    float *statp = nullptr, *gsq_part = nullptr;
+    float *statp = nullptr, *gsq_part = nullptr;   // statp is this context's (c->mem) also where lay_ensure_rows regrows it
     int *d_perm = nullptr, *h_perm = nullptr;            // [N] (pinned host)
     int *d_mbstart = nullptr, *d_mbsize = nullptr, *h_mbplan = nullptr;  // h_mbplan pinned [2*cap]
     size_t mb_cap = 0;
@@ -225,6 +227,7 @@ struct fsrl_ctx {
     void* sac = nullptr;            // SacState, owned
     struct fsrl_tap* tap = nullptr; // the trajectory archive's tap on this context's store ingest (host_traj.inc), owned by the archive
     struct PerState* per = nullptr; // prioritised replay: the sum tree over this context's store (host_per.inc), owned
+    std::vector<struct fsrl_devenv*> devenvs;     // device envs made on this context, not owned: one that outlives it loses its back pointer
 };
 static bool ctx_is_replay(const fsrl_ctx* c);
 static void sac_free(fsrl_ctx* c);
@@ -248,6 +251,7 @@ static inline bool tap_closed(const fsrl_ctx* c, int e);
 static void tap_row(fsrl_ctx* c, int e, int i, const float* act, double rew, double cost, uint8_t fl);
 static int tap_flush(fsrl_ctx* c, int w, const uint8_t* recs_d, int stage_rec, int k);
 static void tap_ctx_gone(fsrl_ctx* c);           // a context destroyed before the archive it feeds
+static void devenv_ctx_gone(fsrl_ctx* c);        // ... before a device env made on it (host_devcollect.inc)
 // prioritised replay (host_per.inc): the sum tree follows every row that reaches the store and every reset of it
 static int per_ingest(fsrl_ctx* c, const uint8_t* recs_d, int rec, int k);
 static int per_store_reset(fsrl_ctx* c);
@@ -285,11 +289,7 @@ static int join_store(fsrl_ctx* c) {
 }
 
 static int ensure_scratch(fsrl_ctx* c, size_t bytes) {
-    if (c->scratch_bytes >= bytes) return 0;
-    if (c->scratch) HIPCHK(hipFree(c->scratch));
-    c->scratch = nullptr; c->scratch_bytes = 0;
-    HIPCHK(hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
+    HIPCHK(c->mem.regrow(c->scratch_bytes, bytes, bytes, {Mem::D(&c->scratch, bytes)}));
     return 0;
 }
 
@@ -302,18 +302,19 @@ template <class T>
 static int table_ensure(DevTable<T>& t, size_t need, size_t grow_to, hipStream_t sync = nullptr) {
     if (need <= t.cap) return 0;
     if (sync) HIPCHK(hipStreamSynchronize(sync));
-    if (t.d) HIPCHK(hipFree(t.d));
-    if (t.h) HIPCHK(hipHostFree(t.h));
-    t.d = nullptr; t.h = nullptr; t.cap = 0;
-    HIPCHK(hipMalloc(&t.d, grow_to * sizeof(T)));
-    HIPCHK(hipHostMalloc(&t.h, grow_to * sizeof(T)));
+    const size_t old = t.cap * sizeof(T);
+    t.cap = 0;
+    if (t.d) { T* d = t.d; t.d = nullptr; HIPCHK(HipMem::dev_free(d, old)); }
+    if (t.h) { T* h = t.h; t.h = nullptr; HIPCHK(HipMem::host_free(h, old)); }
+    HIPCHK(HipMem::dev_alloc((void**)&t.d, grow_to * sizeof(T)));
+    HIPCHK(HipMem::host_alloc((void**)&t.h, grow_to * sizeof(T)));
     t.cap = grow_to;
     return 0;
 }
 template <class T>
 static void table_free(DevTable<T>& t) {
-    if (t.d) (void)hipFree(t.d);
-    if (t.h) (void)hipHostFree(t.h);
+    if (t.d) (void)HipMem::dev_free(t.d, t.cap * sizeof(T));
+    if (t.h) (void)HipMem::host_free(t.h, t.cap * sizeof(T));
     t = DevTable<T>{};
 }
 
@@ -355,11 +356,9 @@ static int ensure_parts(fsrl_ctx* c, int stride, int nsplit) {
     const size_t floats = (size_t)stride * nsplit;
     if (slot->floats < floats) {
         HIPCHK(hipStreamSynchronize(c->compute));
-        if (slot->p) HIPCHK(hipFree(slot->p));
-        slot->p = nullptr; slot->floats = 0; slot->stride = stride;
-        HIPCHK(hipMalloc(&slot->p, floats * 4));
+        slot->stride = stride;
+        HIPCHK(c->mem.regrow(slot->floats, floats, floats, {Mem::D(&slot->p, floats * 4)}));
         HIPCHK(hipMemsetAsync(slot->p, 0, floats * 4, c->compute));
-        slot->floats = floats;
     }
     c->wg_parts = slot->p;
     return 0;
@@ -516,6 +515,11 @@ static void fill_mirrors(const ModelDesc& md, std::vector<float>& v) {
 // contexts alive per device in this process (fsrl_ctx_create / _destroy): the automatic rule of the two-launch clipped step asks
 static std::atomic<int> g_live_ctx[64];
 static int live_contexts_on(int device) { return (device >= 0 && device < 64) ? g_live_ctx[device].load() : 2; }
+extern "C" int fsrl_mem_live(int64_t* dev_blocks, int64_t* dev_bytes, int64_t* pinned_blocks, int64_t* pinned_bytes) {
+    int64_t* out[4] = {dev_blocks, dev_bytes, pinned_blocks, pinned_bytes};
+    for (int i = 0; i < 4; ++i) if (out[i]) *out[i] = HipMem::live[i].load();
+    return 0;
+}
 extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
@@ -525,6 +529,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     if (c->sac_group) sac_group_detach(c);
     if (c->cvpo_group) cvpo_group_detach(c);
     if (c->cgroup) collect_group_detach(c);
+    devenv_ctx_gone(c);
     if (c->tap) tap_ctx_gone(c);            // ... before the trajectory archive it feeds: finished episodes are archived, the tap goes
     comm_free(c);
     tr_free(c);
@@ -532,32 +537,8 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     per_free(c);
     foc_free(c);
     lay_free(c);
-    if (c->h_actor) (void)hipHostFree(c->h_actor);
-    if (c->h_done) (void)hipHostFree(c->h_done);
-    if (c->h_pa) (void)hipHostFree(c->h_pa);
-    if (c->mbstat) (void)hipFree(c->mbstat);
-    if (c->d_rms) (void)hipFree(c->d_rms);
-    if (c->ret64) (void)hipFree(c->ret64);
-    if (c->mu_old) (void)hipFree(c->mu_old);
-    if (c->sigma_old) (void)hipFree(c->sigma_old);
-    if (c->snap) (void)hipFree(c->snap);
-    if (c->clip_snap) (void)hipFree(c->clip_snap);
-    if (c->clip_slots) (void)hipFree(c->clip_slots);
-    void* dptrs[] = {c->P, c->M, c->V, c->G, c->ctrl, c->st.obs, c->st.obs_next, c->st.act, c->st.rew,
-                     c->st.cost, c->st.flags, c->b.obs, c->b.obs_next, c->b.act, c->b.rew, c->b.cost,
-                     c->b.flags, c->d_indices, c->d_end, c->d_seg, c->values, c->vnext, c->advs,
-                     c->rets, c->logp_old, c->A1, c->A2, c->D1, c->D2, c->DO, c->obs_p, c->rd_p, c->statp,
-                     c->gsq_part, c->d_perm, c->d_mbstart, c->d_mbsize, c->d_stats,
-                     c->scratch};
-    for (void* p : dptrs) if (p) (void)hipFree(p);
-    for (auto& pp : c->parts) if (pp.p) (void)hipFree(pp.p);
-    void* hptrs[] = {c->h_ctrl, c->h_indices, c->h_end, c->h_seg, c->h_perm, c->h_mbplan};
-    for (void* p : hptrs) if (p) (void)hipHostFree(p);
-    for (auto& s : c->stage) {
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
+    c->mem.release_all();
+    for (auto& st : c->stage) if (st.done) (void)hipEventDestroy(st.done);
     for (hipEvent_t e : {c->store_ready, c->ev_a, c->ev_b, c->ev_c, c->perm_copied}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->k_ev) (void)hipEventDestroy(e);
     if (c->compute) (void)hipStreamDestroy(c->compute);
@@ -646,8 +627,8 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->no_xcd_pair = getenv("FSRL_NO_XCD_PAIR") != nullptr;
     c->no_fuse_adam = getenv("FSRL_NO_FUSE_ADAM") != nullptr;
     if (getenv("FSRL_TSTAMP")) {
-        (void)hipMalloc(&c->probe_ts, 1024 * 16 * sizeof(unsigned long long));
-        (void)hipMemset(c->probe_ts, 0, 1024 * 16 * sizeof(unsigned long long));
+        if (c->mem.dev(&c->probe_ts, 1024 * 16 * sizeof(unsigned long long)) == hipSuccess)
+            (void)hipMemset(c->probe_ts, 0, 1024 * 16 * sizeof(unsigned long long));
     }
 #endif
     if (layered) lay_build_layout(c, cfg->hidden_sizes, cfg->n_hidden);
@@ -656,17 +637,17 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     TRY(hipStreamCreateWithFlags(&c->compute, hipStreamNonBlocking));
     TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     const size_t pb = (size_t)c->n_dev * sizeof(float);
-    TRY(hipMalloc(&c->P, (size_t)c->n_alloc * sizeof(float))); TRY(hipMemsetAsync(c->P, 0, (size_t)c->n_alloc * sizeof(float), c->compute));
-    TRY(hipMalloc(&c->M, pb)); TRY(hipMalloc(&c->V, pb)); TRY(hipMalloc(&c->G, pb));
+    TRY(c->mem.dev(&c->P, (size_t)c->n_alloc * sizeof(float))); TRY(hipMemsetAsync(c->P, 0, (size_t)c->n_alloc * sizeof(float), c->compute));
+    TRY(c->mem.dev(&c->M, pb)); TRY(c->mem.dev(&c->V, pb)); TRY(c->mem.dev(&c->G, pb));
     TRY(hipMemsetAsync(c->M, 0, pb, c->compute)); TRY(hipMemsetAsync(c->V, 0, pb, c->compute)); TRY(hipMemsetAsync(c->G, 0, pb, c->compute));
-    TRY(hipMalloc(&c->ctrl, sizeof(CtrlBlock)));
+    TRY(c->mem.dev(&c->ctrl, sizeof(CtrlBlock)));
     if (cfg->rew_norm) {      // RunningMeanStd(): mean 0, var 1, count 0 per critic
-        TRY(hipMalloc(&c->d_rms, 3 * FSRL_MAX_CRITICS * sizeof(double)));
+        TRY(c->mem.dev(&c->d_rms, 3 * FSRL_MAX_CRITICS * sizeof(double)));
         double init[3 * FSRL_MAX_CRITICS];
         for (int i = 0; i < FSRL_MAX_CRITICS; ++i) { init[3 * i] = 0.0; init[3 * i + 1] = 1.0; init[3 * i + 2] = 0.0; }
         TRY(hipMemcpy(c->d_rms, init, sizeof(init), hipMemcpyHostToDevice));
     }
-    TRY(hipHostMalloc(&c->h_ctrl, sizeof(CtrlBlock)));
+    TRY(c->mem.pinned(&c->h_ctrl, sizeof(CtrlBlock)));
     // store: n sub-buffers of ceil(total/n) rows (tianshou VectorReplayBuffer)
     c->sub_size = (cfg->buffer_size + cfg->env_num - 1) / cfg->env_num;
     c->maxsize = c->sub_size * cfg->env_num;
@@ -676,26 +657,26 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->h_flags.assign((size_t)c->alloc_rows, 0);
     const size_t ms = (size_t)c->alloc_rows;
     const int Do = cfg->obs_dim, Da = cfg->act_dim;
-    TRY(hipMalloc(&c->st.obs, ms * Do * 4)); TRY(hipMalloc(&c->st.obs_next, ms * Do * 4));
-    TRY(hipMalloc(&c->st.act, ms * Da * 4)); TRY(hipMalloc(&c->st.rew, ms * 8));
-    TRY(hipMalloc(&c->st.cost, ms * 8)); TRY(hipMalloc(&c->st.flags, ms));
-    TRY(hipMalloc(&c->b.obs, ms * Do * 4)); TRY(hipMalloc(&c->b.obs_next, ms * Do * 4));
-    TRY(hipMalloc(&c->b.act, ms * Da * 4)); TRY(hipMalloc(&c->b.rew, ms * 8));
-    TRY(hipMalloc(&c->b.cost, ms * 8)); TRY(hipMalloc(&c->b.flags, ms));
-    TRY(hipMalloc(&c->d_indices, ms * 4)); TRY(hipMalloc(&c->d_end, ms)); TRY(hipMalloc(&c->d_seg, (ms + 2) * 4));
-    TRY(hipHostMalloc(&c->h_indices, ms * 4)); TRY(hipHostMalloc(&c->h_end, ms)); TRY(hipHostMalloc(&c->h_seg, (ms + 2) * 4));
+    TRY(c->mem.dev(&c->st.obs, ms * Do * 4)); TRY(c->mem.dev(&c->st.obs_next, ms * Do * 4));
+    TRY(c->mem.dev(&c->st.act, ms * Da * 4)); TRY(c->mem.dev(&c->st.rew, ms * 8));
+    TRY(c->mem.dev(&c->st.cost, ms * 8)); TRY(c->mem.dev(&c->st.flags, ms));
+    TRY(c->mem.dev(&c->b.obs, ms * Do * 4)); TRY(c->mem.dev(&c->b.obs_next, ms * Do * 4));
+    TRY(c->mem.dev(&c->b.act, ms * Da * 4)); TRY(c->mem.dev(&c->b.rew, ms * 8));
+    TRY(c->mem.dev(&c->b.cost, ms * 8)); TRY(c->mem.dev(&c->b.flags, ms));
+    TRY(c->mem.dev(&c->d_indices, ms * 4)); TRY(c->mem.dev(&c->d_end, ms)); TRY(c->mem.dev(&c->d_seg, (ms + 2) * 4));
+    TRY(c->mem.pinned(&c->h_indices, ms * 4)); TRY(c->mem.pinned(&c->h_end, ms)); TRY(c->mem.pinned(&c->h_seg, (ms + 2) * 4));
     const int C = cfg->n_critics;
-    TRY(hipMalloc(&c->values, ms * C * 4)); TRY(hipMalloc(&c->vnext, ms * C * 4));
-    TRY(hipMalloc(&c->advs, ms * C * 4)); TRY(hipMalloc(&c->rets, ms * C * 4));
-    TRY(hipMalloc(&c->logp_old, ms * 4));
-    TRY(hipMalloc(&c->d_perm, ms * 4)); TRY(hipHostMalloc(&c->h_perm, ms * 4));
-    TRY(hipMalloc(&c->obs_p, (ms + 32) * Do * 4)); TRY(hipMemsetAsync(c->obs_p, 0, (ms + 32) * Do * 4, c->compute));
-    TRY(hipMalloc(&c->rd_p, (ms + 32) * FSRL_RD * 4)); TRY(hipMemsetAsync(c->rd_p, 0, (ms + 32) * FSRL_RD * 4, c->compute));
+    TRY(c->mem.dev(&c->values, ms * C * 4)); TRY(c->mem.dev(&c->vnext, ms * C * 4));
+    TRY(c->mem.dev(&c->advs, ms * C * 4)); TRY(c->mem.dev(&c->rets, ms * C * 4));
+    TRY(c->mem.dev(&c->logp_old, ms * 4));
+    TRY(c->mem.dev(&c->d_perm, ms * 4)); TRY(c->mem.pinned(&c->h_perm, ms * 4));
+    TRY(c->mem.dev(&c->obs_p, (ms + 32) * Do * 4)); TRY(hipMemsetAsync(c->obs_p, 0, (ms + 32) * Do * 4, c->compute));
+    TRY(c->mem.dev(&c->rd_p, (ms + 32) * FSRL_RD * 4)); TRY(hipMemsetAsync(c->rd_p, 0, (ms + 32) * FSRL_RD * 4, c->compute));
     TRY(hipStreamSynchronize(c->compute));     // zero fills have landed before any other stream touches them
     for (auto& s : c->stage) {
         const size_t k = fsrl_ctx::STAGE_CAP;
-        TRY(hipHostMalloc(&s.h, k * stage_rec_bytes(Do, Da)));
-        TRY(hipMalloc(&s.d, k * stage_rec_bytes(Do, Da)));
+        TRY(c->mem.pinned(&s.h, k * stage_rec_bytes(Do, Da)));
+        TRY(c->mem.dev(&s.d, k * stage_rec_bytes(Do, Da)));
         TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
     TRY(hipEventCreateWithFlags(&c->store_ready, hipEventDisableTiming));
@@ -776,7 +757,7 @@ extern "C" int fsrl_state_snapshot(fsrl_ctx* c) {
     CHECK_ARG(!ctx_is_replay(c), "fsrl_state_snapshot covers on-policy contexts (PPO-Lag, FOCOPS, CPO, TRPO-Lag) only");
     ENTER_DEV(c);
     if (!c->snap) {
-        HIPCHK(hipMalloc(&c->snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4 + 3 * FSRL_MAX_CRITICS * sizeof(double)));
+        HIPCHK(c->mem.dev(&c->snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4 + 3 * FSRL_MAX_CRITICS * sizeof(double)));
     }
     hipStream_t st = c->compute;
     HIPCHK(hipMemcpyAsync(c->snap, c->P, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, st));
@@ -1155,9 +1136,9 @@ static int pactor_post(fsrl_ctx* c, const float* obs, int k) {
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim;
     ResidentRing& r = c->pa;
     if (!c->h_pa) {
-        c->pa_cap = 16 * PACTOR_BLOCKS;
-        const size_t bytes = 64 + ((size_t)c->pa_cap * (Do + 2 * Da) + FSRL_MAX_ACT) * 4;
-        HIPCHK(hipHostMalloc(&c->h_pa, bytes));
+        const int cap = 16 * PACTOR_BLOCKS;
+        const size_t bytes = 64 + ((size_t)cap * (Do + 2 * Da) + FSRL_MAX_ACT) * 4;
+        HIPCHK(c->mem.regrow(c->pa_cap, cap, cap, {Mem::H(&c->h_pa, bytes)}));
         memset(c->h_pa, 0, bytes);
         const PaLayout l = pa_layout(c);
         r.bell = l.bell; r.done = l.done; r.state = l.state;
@@ -1184,10 +1165,7 @@ static int actor_eval_launch(fsrl_ctx* c, const float* obs, int32_t k, bool want
     const size_t need = ob + mb + FSRL_MAX_ACT * 4;
     if (c->h_actor_bytes < need) {
         HIPCHK(hipStreamSynchronize(c->compute));
-        if (c->h_actor) HIPCHK(hipHostFree(c->h_actor));
-        c->h_actor = nullptr; c->h_actor_bytes = 0;
-        HIPCHK(hipHostMalloc(&c->h_actor, need * 2));
-        c->h_actor_bytes = need * 2;
+        HIPCHK(c->mem.regrow(c->h_actor_bytes, need, need * 2, {Mem::H(&c->h_actor, need * 2)}));
     }
     float* h_obs = (float*)c->h_actor;
     float* h_mu = (float*)((char*)c->h_actor + ob);
@@ -1197,10 +1175,8 @@ static int actor_eval_launch(fsrl_ctx* c, const float* obs, int32_t k, bool want
     // (a stream synchronisation costs several microseconds more than the kernel itself at these sizes)
     c->actor_blocks = (k + 15) / 16;
     if (c->actor_blocks > c->done_cap) {
-        if (c->h_done) HIPCHK(hipHostFree(c->h_done));
-        c->h_done = nullptr;
-        c->done_cap = std::max(2 * c->actor_blocks, 64);
-        HIPCHK(hipHostMalloc(&c->h_done, (size_t)c->done_cap * 4));
+        const int cap = std::max(2 * c->actor_blocks, 64);
+        HIPCHK(c->mem.regrow(c->done_cap, c->actor_blocks, cap, {Mem::H(&c->h_done, (size_t)cap * 4)}));
         memset(c->h_done, 0, (size_t)c->done_cap * 4);
     }
     c->actor_seq += 1;

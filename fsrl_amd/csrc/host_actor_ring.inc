@@ -17,6 +17,7 @@ static constexpr int GA_ROWS = GACTOR_MAX_WG * 16;
 struct GaRing : ResidentRing {                  // ResidentRing::owner is the GaRing itself (ga_bind)
     int Do = 0, cols = 0;                       // observation width / floats per output row of the ring
     void* h = nullptr;                          // pinned ring (GaLayout)
+    Mem mem;                                    // owns it, and a layered group's collect buffers (LayGroup::ch / cd: that struct is reset by assignment)
     hipStream_t stream = nullptr;               // the stream the kernel is launched on (the group's)
     void* group = nullptr;                      // the fsrl_group / fsrl_collect_group, for its launch hook
 };
@@ -44,7 +45,7 @@ static void ga_bind(GaRing& r, hipStream_t stream, int (*launch)(void*, Resident
 static int gactor_ensure(GaRing& r, fsrl_ctx* const* m, int n, int cols) {
     if (r.h) return 0;
     const size_t bytes = ga_bytes(m[0]->cfg.obs_dim, cols);
-    HIPCHK(hipHostMalloc(&r.h, bytes));
+    HIPCHK(r.mem.pinned(&r.h, bytes));
     memset(r.h, 0, bytes);
     r.n = n; r.Do = m[0]->cfg.obs_dim; r.cols = cols;
     int base = 0;

@@ -108,9 +108,9 @@ extern "C" int fsrl_collect_group_destroy(fsrl_collect_group* g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (fsrl_ctx* c : g->m) if (c) c->cgroup = nullptr;
     for (hipEvent_t e : g->ready) if (e) (void)hipEventDestroy(e);
-    lay_group_free(g->lay);
+    lay_group_free(g->lay, g->ga.mem);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->ga.h) (void)hipHostFree(g->ga.h);
+    g->ga.mem.release_all();
     delete g;
     return 0;
 }

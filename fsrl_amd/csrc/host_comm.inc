@@ -61,6 +61,7 @@ static int rccl_load() {
 
 struct CommState {
     void* comm = nullptr;
+    Mem mem;
     int rank = 0, world = 1;
     double* d_buf = nullptr; double* h_buf = nullptr;      // device / pinned staging of the vector
 };
@@ -69,8 +70,7 @@ static void comm_free(fsrl_ctx* c) {
     CommState* m = c->comm;
     if (!m) return;
     if (m->comm && g_rccl.comm_destroy) (void)g_rccl.comm_destroy(m->comm);
-    if (m->d_buf) (void)hipFree(m->d_buf);
-    if (m->h_buf) (void)hipHostFree(m->h_buf);
+    m->mem.release_all();
     delete m;
     c->comm = nullptr;
 }
@@ -107,8 +107,8 @@ extern "C" int fsrl_comm_init(fsrl_ctx* c, int32_t rank, int32_t world, const ui
         comm_free(c);
         return fail(FSRL_EHIP, "ncclCommInitRank failed: %s", g_rccl.err ? g_rccl.err(r) : "rccl error");
     }
-    if (hipMalloc(&m->d_buf, FSRL_COMM_MAX * sizeof(double)) != hipSuccess ||
-        hipHostMalloc(&m->h_buf, FSRL_COMM_MAX * sizeof(double)) != hipSuccess) {
+    if (m->mem.dev(&m->d_buf, FSRL_COMM_MAX * sizeof(double)) != hipSuccess ||
+        m->mem.pinned(&m->h_buf, FSRL_COMM_MAX * sizeof(double)) != hipSuccess) {
         comm_free(c);
         return fail(FSRL_EHIP, "staging buffers of the metric exchange: %s", hipGetErrorString(hipGetLastError()));
     }

@@ -25,7 +25,7 @@ extern "C" int fsrl_cvpo_init(fsrl_ctx* c, const fsrl_cvpo_config* cfg) {
     const int rc = sac_alloc_state(c, s);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(s->sc, 0, sizeof(SacScalars), c->compute));
-    HIPCHK(hipMalloc(&s->csc, sizeof(CvpoScalars)));
+    HIPCHK(s->mem.dev(&s->csc, sizeof(CvpoScalars)));
     HIPCHK(hipMemsetAsync(s->csc, 0, sizeof(CvpoScalars), c->compute));
     HIPCHK(hipStreamSynchronize(c->compute));
     const float eta0 = 1.0f;                                                     // estep_dual = [1, 0]  (cvpo.py:150-152)
@@ -305,7 +305,7 @@ static int sac_actor_launch(fsrl_ctx* c, const float* h_obs, float* h_raw, int k
     SacState* s = sac_of(c);
     if (!s) return fail(FSRL_ESTATE, "fsrl_sac_init / fsrl_cvpo_init first");
     if (s->layered) {           // forward layer by layer, then the raw head outputs to the pinned staging + the completion words
-        int rc = lay_work_ensure(c, s->ka, k);
+        int rc = lay_work_ensure(c, s->mem, s->ka, k);
         if (rc) return rc;
         rc = lay_fwd_k(c, s->ka, s->PA, h_obs, k);
         if (rc) return rc;

@@ -92,12 +92,8 @@ extern "C" int fsrl_cvpo_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_cvpo_grou
     HIPCHK(hipSetDevice(c0->device));
     fsrl_cvpo_group* g = new fsrl_cvpo_group();
     hipError_t e = rgroup_create(g->core, c0->device, k);
-    if (e == hipSuccess) e = hipMalloc(&g->tab.d, (size_t)k * sizeof(SacGroupMember));
-    if (e == hipSuccess) e = hipHostMalloc(&g->tab.h, (size_t)k * sizeof(SacGroupMember));
-    if (e == hipSuccess) e = hipMalloc(&g->ctab.d, (size_t)k * sizeof(CvpoGroupMember));
-    if (e == hipSuccess) e = hipHostMalloc(&g->ctab.h, (size_t)k * sizeof(CvpoGroupMember));
-    if (e != hipSuccess) {
-        fail(FSRL_EHIP, "CVPO group allocation failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) fail(FSRL_EHIP, "CVPO group allocation failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess || table_ensure(g->tab, (size_t)k, (size_t)k) || table_ensure(g->ctab, (size_t)k, (size_t)k)) {
         (void)fsrl_cvpo_group_destroy(g);
         return FSRL_EHIP;
     }

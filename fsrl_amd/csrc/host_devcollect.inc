@@ -19,6 +19,7 @@ static int per_devcollect(fsrl_ctx* c, const int32_t* slots_d, const int32_t* n_
 struct fsrl_devenv {
     fsrl_ctx* c = nullptr;
     fsrl_devenv_config cfg{};
+    Mem mem;
     uint64_t key = 0;
     hipStream_t es = nullptr;           // reset / step launches
     DevEnvArrays ea{};
@@ -57,25 +58,9 @@ static size_t devenv_io_bytes(int n, int Do, int Da) { return (size_t)n * (8 + 8
 static void devenv_free(fsrl_devenv* v) {
     if (!v) return;
     if (v->es) { (void)hipStreamSynchronize(v->es); (void)hipStreamDestroy(v->es); }
-    if (v->ea.state) (void)hipFree(v->ea.state);
-    if (v->ea.obs) (void)hipFree(v->ea.obs);
-    if (v->ea.nxt) (void)hipFree(v->ea.nxt);
-    if (v->ea.t) (void)hipFree(v->ea.t);
-    if (v->ea.ordinal) (void)hipFree(v->ea.ordinal);
-    if (v->dA) (void)hipFree(v->dA);
-    if (v->dB) (void)hipFree(v->dB);
-    if (v->h_io) (void)hipHostFree(v->h_io);
-    if (v->d_state) (void)hipFree(v->d_state);
-    if (v->h_state) (void)hipHostFree(v->h_state);
-    if (v->d_log) (void)hipFree(v->d_log);
-    if (v->h_log) (void)hipHostFree(v->h_log);
-    if (v->d_slot) (void)hipFree(v->d_slot);
-    if (v->d_args) (void)hipFree(v->d_args);
-    if (v->h_args) (void)hipHostFree(v->h_args);
+    v->mem.release_all();
     if (v->g_ready) (void)hipEventDestroy(v->g_ready);
     if (v->g_done) (void)hipEventDestroy(v->g_done);
-    if (v->d_tab) (void)hipFree(v->d_tab);
-    if (v->h_tab) (void)hipHostFree(v->h_tab);
     delete v;
 }
 
@@ -105,37 +90,40 @@ extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fs
     };
 #define DEVENV_TRY(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return bail(_e, #expr); } while (0)
     DEVENV_TRY(hipStreamCreateWithFlags(&v->es, hipStreamNonBlocking));
-    DEVENV_TRY(hipMalloc(&v->ea.state, n * DEVENV_STATE * 4));
-    DEVENV_TRY(hipMalloc(&v->ea.obs, n * Do * 4));
-    DEVENV_TRY(hipMalloc(&v->ea.nxt, n * Do * 4));
-    DEVENV_TRY(hipMalloc(&v->ea.t, n * 4));
-    DEVENV_TRY(hipMalloc(&v->ea.ordinal, n * 8));
+    DEVENV_TRY(v->mem.dev(&v->ea.state, n * DEVENV_STATE * 4));
+    DEVENV_TRY(v->mem.dev(&v->ea.obs, n * Do * 4));
+    DEVENV_TRY(v->mem.dev(&v->ea.nxt, n * Do * 4));
+    DEVENV_TRY(v->mem.dev(&v->ea.t, n * 4));
+    DEVENV_TRY(v->mem.dev(&v->ea.ordinal, n * 8));
     DEVENV_TRY(hipMemset(v->ea.state, 0, n * DEVENV_STATE * 4));
     DEVENV_TRY(hipMemset(v->ea.obs, 0, n * Do * 4));
     DEVENV_TRY(hipMemset(v->ea.nxt, 0, n * Do * 4));
     DEVENV_TRY(hipMemset(v->ea.t, 0, n * 4));
     DEVENV_TRY(hipMemset(v->ea.ordinal, 0, n * 8));
     if (cfg->kind == FSRL_DEVENV_LINEAR) {
-        DEVENV_TRY(hipMalloc(&v->dA, Do * Do * 4));
-        DEVENV_TRY(hipMalloc(&v->dB, Da * Do * 4));
+        DEVENV_TRY(v->mem.dev(&v->dA, Do * Do * 4));
+        DEVENV_TRY(v->mem.dev(&v->dB, Da * Do * 4));
         DEVENV_TRY(hipMemcpy(v->dA, cfg->A, Do * Do * 4, hipMemcpyHostToDevice));
         DEVENV_TRY(hipMemcpy(v->dB, cfg->B, Da * Do * 4, hipMemcpyHostToDevice));
     }
-    DEVENV_TRY(hipHostMalloc(&v->h_io, devenv_io_bytes((int)n, (int)Do, (int)Da)));
-    DEVENV_TRY(hipMalloc(&v->d_state, sizeof(DcState)));
-    DEVENV_TRY(hipHostMalloc(&v->h_state, sizeof(DcState)));
-    DEVENV_TRY(hipMalloc(&v->d_args, sizeof(DevCollectArgs)));
-    DEVENV_TRY(hipHostMalloc(&v->h_args, sizeof(DevCollectArgs)));
+    DEVENV_TRY(v->mem.pinned(&v->h_io, devenv_io_bytes((int)n, (int)Do, (int)Da)));
+    DEVENV_TRY(v->mem.dev(&v->d_state, sizeof(DcState)));
+    DEVENV_TRY(v->mem.pinned(&v->h_state, sizeof(DcState)));
+    DEVENV_TRY(v->mem.dev(&v->d_args, sizeof(DevCollectArgs)));
+    DEVENV_TRY(v->mem.pinned(&v->h_args, sizeof(DevCollectArgs)));
 #undef DEVENV_TRY
+    c->devenvs.push_back(v);
     *out = v;
     return 0;
 }
 
+static void devenv_ctx_gone(fsrl_ctx* c) { for (fsrl_devenv* v : c->devenvs) v->c = nullptr; }     // destroy is all such an env still takes
 extern "C" int fsrl_devenv_destroy(fsrl_devenv* v) {
     if (!v) return 0;
     if (v->c) {
         (void)hipSetDevice(v->c->device);
         (void)hipStreamSynchronize(v->c->compute);      // a collect kernel reads the env's arrays
+        v->c->devenvs.erase(std::remove(v->c->devenvs.begin(), v->c->devenvs.end(), v), v->c->devenvs.end());
     }
     devenv_free(v);
     return 0;
@@ -300,14 +288,9 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     int rc = join_store(c);                         // rows in the staging window land first; the side stream is in front of the kernel
     if (rc) return rc;
     if (v->log_steps < max_steps) {
-        if (v->d_log) HIPCHK(hipFree(v->d_log));
-        if (v->h_log) HIPCHK(hipHostFree(v->h_log));
-        if (v->d_slot) HIPCHK(hipFree(v->d_slot));
-        v->d_log = nullptr; v->h_log = nullptr; v->d_slot = nullptr; v->log_steps = 0;
-        HIPCHK(hipMalloc(&v->d_log, (size_t)max_steps * n * sizeof(DcLogRow)));
-        HIPCHK(hipMalloc(&v->d_slot, (size_t)max_steps * n * sizeof(int32_t)));
-        HIPCHK(hipHostMalloc(&v->h_log, (size_t)max_steps * n * sizeof(DcLogRow)));
-        v->log_steps = max_steps;
+        const size_t rows = (size_t)max_steps * n;
+        HIPCHK(v->mem.regrow(v->log_steps, max_steps, max_steps, {Mem::D(&v->d_log, rows * sizeof(DcLogRow)),
+                             Mem::D(&v->d_slot, rows * sizeof(int32_t)), Mem::H(&v->h_log, rows * sizeof(DcLogRow))}));
     }
     DcState& hs = *v->h_state;
     memset(&hs, 0, sizeof(hs));

@@ -18,8 +18,8 @@ static int devcollect_group_ensure(fsrl_devenv* v, bool first) {
     if (!v->g_ready) HIPCHK(hipEventCreateWithFlags(&v->g_ready, hipEventDisableTiming));
     if (!first) return 0;
     if (!v->g_done) HIPCHK(hipEventCreateWithFlags(&v->g_done, hipEventDisableTiming));
-    if (!v->d_tab) HIPCHK(hipMalloc(&v->d_tab, sizeof(DevCollectGroupTable)));
-    if (!v->h_tab) HIPCHK(hipHostMalloc(&v->h_tab, sizeof(DevCollectGroupTable)));
+    if (!v->d_tab) HIPCHK(v->mem.dev(&v->d_tab, sizeof(DevCollectGroupTable)));
+    if (!v->h_tab) HIPCHK(v->mem.pinned(&v->h_tab, sizeof(DevCollectGroupTable)));
     return 0;
 }
 

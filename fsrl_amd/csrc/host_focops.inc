@@ -3,6 +3,7 @@
 // ====================================================================================== FOCOPS
 struct FocState {
     fsrl_focops_config cfg{};
+    Mem mem;
     double nu = 0.0, nu_loss = 0.0;
     int64_t t_actor = 0, t_critic = 0;
     float *statp_pi = nullptr, *psq = nullptr, *gsq = nullptr, *sig_stash = nullptr;   // statp_pi: [tiles][3 networks][FB_NSTAT]
@@ -20,7 +21,7 @@ static void foc_steps(fsrl_ctx* c, int64_t* t_actor, int64_t* t_critic, bool set
 static void foc_free(fsrl_ctx* c) {
     FocState* f = c->foc;
     if (!f) return;
-    for (float* p : {f->statp_pi, f->psq, f->gsq, f->sig_stash, f->gsq_net}) if (p) (void)hipFree(p);
+    f->mem.release_all();
     delete f;
     c->foc = nullptr;
 }
@@ -64,13 +65,13 @@ static int focops_alloc(fsrl_ctx* c) {
     focops_blocks(c, &nb_a, &nb_c0, &nb_c1);
     if (f->cap_tiles < max_tiles || f->cap_psq < nb_c0 + nb_c1) {
         HIPCHK(hipStreamSynchronize(c->compute));
-        for (float** p : {&f->statp_pi, &f->psq, &f->gsq}) { if (*p) HIPCHK(hipFree(*p)); *p = nullptr; }
-        HIPCHK(hipMalloc(&f->statp_pi, (size_t)(4 * max_tiles + 4) * 3 * FB_NSTAT * 4));      // three networks per tile
-        if (!f->sig_stash) HIPCHK(hipMalloc(&f->sig_stash, 2 * FSRL_MAX_ACT * 4));
-        if (!f->gsq_net) HIPCHK(hipMalloc(&f->gsq_net, FSRL_MAX_NETS * 4));
-        HIPCHK(hipMalloc(&f->psq, (size_t)2 * (nb_c0 + nb_c1) * 4));
-        HIPCHK(hipMalloc(&f->gsq, (size_t)nb_a * 4));
-        f->cap_tiles = max_tiles; f->cap_psq = nb_c0 + nb_c1;
+        if (!f->sig_stash) HIPCHK(f->mem.dev(&f->sig_stash, 2 * FSRL_MAX_ACT * 4));
+        if (!f->gsq_net) HIPCHK(f->mem.dev(&f->gsq_net, FSRL_MAX_NETS * 4));
+        f->cap_tiles = f->cap_psq = 0;      // one set behind both capacities: either growing regrows it
+        HIPCHK(f->mem.regrow(f->cap_tiles, std::max(max_tiles, 1), std::max(max_tiles, 1),
+                             {Mem::D(&f->statp_pi, (size_t)(4 * max_tiles + 4) * 3 * FB_NSTAT * 4),      // three networks per tile
+                              Mem::D(&f->psq, (size_t)2 * (nb_c0 + nb_c1) * 4), Mem::D(&f->gsq, (size_t)nb_a * 4)}));
+        f->cap_psq = nb_c0 + nb_c1;
     }
     return 0;
 }

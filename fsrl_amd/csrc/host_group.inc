@@ -90,13 +90,11 @@ extern "C" int fsrl_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_group** out) {
         c->compute = g->stream;                 // everything a member enqueues from now on goes to the shared stream
         c->group = g;
     }
-    hipError_t e = hipMalloc(&g->tab.d, (size_t)k * sizeof(GroupAgent));
-    if (e == hipSuccess) e = hipHostMalloc(&g->tab.h, (size_t)k * sizeof(GroupAgent));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->steps_copied, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        fail(FSRL_EHIP, "group allocation failed: %s", hipGetErrorString(e));
+    int rc_tab = table_ensure(g->tab, (size_t)k, (size_t)k);
+    if (!rc_tab && hipEventCreateWithFlags(&g->steps_copied, hipEventDisableTiming) != hipSuccess) rc_tab = fail(FSRL_EHIP, "group allocation failed");
+    if (rc_tab) {
         (void)fsrl_group_destroy(g);            // gives the members their own streams back
-        return FSRL_EHIP;
+        return rc_tab;
     }
     *out = g;
     return 0;
@@ -110,7 +108,7 @@ static void group_detach(fsrl_ctx* c) {
     if (!g) return;
     group_actor_release(g);
     (void)hipStreamSynchronize(g->stream);
-    lay_group_free(g->lay);                     // job tables and collect buffers of a layered group: they name this member's memory
+    lay_group_free(g->lay, g->ga.mem);          // job tables and collect buffers of a layered group: they name this member's memory
     for (size_t i = 0; i < g->m.size(); ++i) {
         fsrl_ctx* m = g->m[i];
         if (!m) continue;
@@ -131,9 +129,9 @@ extern "C" int fsrl_group_destroy(fsrl_group* g) {
     if (g->stream) (void)hipStreamDestroy(g->stream);
     table_free(g->tab); table_free(g->steps);
     if (g->steps_copied) (void)hipEventDestroy(g->steps_copied);
-    if (g->ga.h) (void)hipHostFree(g->ga.h);
     table_free(g->ftab); table_free(g->fsteps);
-    lay_group_free(g->lay);
+    lay_group_free(g->lay, g->ga.mem);
+    g->ga.mem.release_all();
     delete g;
     return 0;
 }

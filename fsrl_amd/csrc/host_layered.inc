@@ -21,16 +21,16 @@ struct LayWork {
     float* out = nullptr;               // [nn][mbp][FSRL_MAX_ACT]
     float* dout = nullptr;              // [nn][mbp][FSRL_DOW]
 };
-static int lay_work_ensure(fsrl_ctx* c, LayWork& k, int rows) {
+// m: the owner of k's state (LayWork itself goes by value into launches and holds no owner)
+static int lay_work_ensure(fsrl_ctx* c, Mem& m, LayWork& k, int rows) {
     const int mbp = round_up(std::max(rows, 16), 16);
     if (mbp <= k.mbp) return 0;
     HIPCHK(hipStreamSynchronize(c->compute));
-    if (k.ws) { HIPCHK(hipFree(k.ws)); k.ws = nullptr; }
     const int nn = k.lm.n_nets, L = k.L;
     size_t per_net = 0;
     for (int l = 0; l < L; ++l) per_net += (size_t)mbp * round_up(k.w[l], 4);
     const size_t floats = (size_t)nn * (2 * per_net + (size_t)mbp * (FSRL_MAX_ACT + FSRL_DOW));
-    HIPCHK(hipMalloc(&k.ws, floats * 4));
+    HIPCHK(m.regrow(k.mbp, mbp, mbp, {Mem::D(&k.ws, floats * 4)}));
     HIPCHK(hipMemsetAsync(k.ws, 0, floats * 4, c->compute));
     float* p = k.ws;
     for (int net = 0; net < nn; ++net)
@@ -40,12 +40,11 @@ static int lay_work_ensure(fsrl_ctx* c, LayWork& k, int rows) {
         }
     k.out = p; p += (size_t)nn * mbp * FSRL_MAX_ACT;
     k.dout = p;
-    k.mbp = mbp;
     return 0;
 }
-static void lay_work_free(LayWork& k) { if (k.ws) (void)hipFree(k.ws); k.ws = nullptr; k.mbp = 0; }
 
 struct LayState : LayWork {
+    Mem mem;                            // owns ws, gsq, rws, gvec, inf (c->statp stays the context's)
     float* gsq = nullptr; int nparts = 0; dim3 wgrid{1, 1, 1};
     // trust-region extras (host_trust.inc): tangents of the actor's activations / their gradients (R-operator), and a
     // parameter-layout vector the weight-side launch writes a gradient / a Hessian-vector product into
@@ -63,13 +62,8 @@ struct LayState : LayWork {
 
 static void lay_free(fsrl_ctx* c) {
     if (!c->lay) return;
-    LayState* ls = c->lay;
-    if (ls->ws) (void)hipFree(ls->ws);
-    if (ls->gsq) (void)hipFree(ls->gsq);
-    if (ls->inf) (void)hipFree(ls->inf);
-    if (ls->rws) (void)hipFree(ls->rws);
-    if (ls->gvec) (void)hipFree(ls->gvec);
-    delete ls;
+    c->lay->mem.release_all();
+    delete c->lay;
     c->lay = nullptr;
 }
 
@@ -128,23 +122,23 @@ static void lay_build_layout(fsrl_ctx* c, const int* widths, int L) {
 static int lay_ensure_rows(fsrl_ctx* c, int rows, bool rop) {
     LayState* ls = c->lay;
     const int mbp = round_up(std::max(rows, 16), 16);
-    if (!ls->gsq) HIPCHK(hipMalloc(&ls->gsq, (size_t)ls->nparts * 4));
+    if (!ls->gsq) HIPCHK(ls->mem.dev(&ls->gsq, (size_t)ls->nparts * 4));
     const int nn = ls->lm.n_nets, L = ls->L;
-    if (mbp > ls->mbp) {
+    if (mbp > ls->mbp || mbp > c->mbp_max) {      // the second: statp (the context's own block) failed after the working set grew
         HIPCHK(hipStreamSynchronize(c->compute));
-        if (ls->rws) { HIPCHK(hipFree(ls->rws)); ls->rws = nullptr; ls->rop = false; }
-        if (c->statp) { HIPCHK(hipFree(c->statp)); c->statp = nullptr; }
-        int rc = lay_work_ensure(c, *ls, mbp);
+        ls->rop = false; c->mbp_max = 0;
+        HIPCHK(ls->mem.release(&ls->rws));
+        HIPCHK(c->mem.release(&c->statp));
+        int rc = lay_work_ensure(c, ls->mem, *ls, mbp);
         if (rc) return rc;
-        HIPCHK(hipMalloc(&c->statp, (size_t)(mbp / 16) * nn * 4 * 4));
-        c->mbp_max = mbp;
+        HIPCHK(c->mem.regrow(c->mbp_max, mbp, mbp, {Mem::D(&c->statp, (size_t)(mbp / 16) * nn * 4 * 4)}));
     }
     if (rop && !ls->rop) {
         HIPCHK(hipStreamSynchronize(c->compute));
         size_t per = 0;
         for (int l = 0; l < L; ++l) per += (size_t)ls->mbp * round_up(ls->w[l], 4);
         const size_t floats = 2 * per + (size_t)ls->mbp * (FSRL_MAX_ACT + FSRL_DOW);
-        HIPCHK(hipMalloc(&ls->rws, floats * 4));
+        HIPCHK(ls->mem.regrow(ls->rop, true, true, {Mem::D(&ls->rws, floats * 4)}));
         HIPCHK(hipMemsetAsync(ls->rws, 0, floats * 4, c->compute));
         float* p = ls->rws;
         for (int l = 0; l < L; ++l) {
@@ -153,10 +147,9 @@ static int lay_ensure_rows(fsrl_ctx* c, int rows, bool rop) {
         }
         ls->rout = p; p += (size_t)ls->mbp * FSRL_MAX_ACT;
         ls->rdout = p;
-        ls->rop = true;
     }
     if (rop && !ls->gvec) {
-        HIPCHK(hipMalloc(&ls->gvec, (size_t)LAY_KSPLIT_MAX * c->n_dev * 4));
+        HIPCHK(ls->mem.dev(&ls->gvec, (size_t)LAY_KSPLIT_MAX * c->n_dev * 4));
         HIPCHK(hipMemsetAsync(ls->gvec, 0, (size_t)LAY_KSPLIT_MAX * c->n_dev * 4, c->compute));
     }
     return 0;
@@ -206,9 +199,7 @@ static int lay_infer(fsrl_ctx* c, const InferArgs& ia, int jobs_y, hipStream_t s
     const size_t need = (size_t)jobs_y * N * (2 * hm + FSRL_MAX_ACT);
     if (need > ls->inf_floats) {
         HIPCHK(hipStreamSynchronize(s));
-        if (ls->inf) { HIPCHK(hipFree(ls->inf)); ls->inf = nullptr; ls->inf_floats = 0; }
-        HIPCHK(hipMalloc(&ls->inf, need * 4));
-        ls->inf_floats = need;
+        HIPCHK(ls->mem.regrow(ls->inf_floats, need, need, {Mem::D(&ls->inf, need * 4)}));
     }
     float* bufs[2] = {ls->inf, ls->inf + (size_t)jobs_y * N * hm};
     float* outb = ls->inf + 2 * (size_t)jobs_y * N * hm;

@@ -34,11 +34,10 @@ static LayGroupPinned lay_group_pinned(const LayGroup& lg, int Do, int cols) {
     return p;
 }
 
-static void lay_group_free(LayGroup& lg) {
+static void lay_group_free(LayGroup& lg, Mem& m) {       // m: the embedding group's ring owner (GaRing::mem)
     table_free(lg.jobs); table_free(lg.heads);
     if (lg.copied) (void)hipEventDestroy(lg.copied);
-    if (lg.ch) (void)hipHostFree(lg.ch);
-    if (lg.cd) (void)hipFree(lg.cd);
+    (void)m.release(&lg.ch); (void)m.release(&lg.cd);
     lg = LayGroup{};
 }
 
@@ -257,15 +256,12 @@ static int lay_group_collect_stage(LayGroup& lg, GaRing& ga, fsrl_ctx* c0, const
     for (int i = 0; i < k; ++i) maxk = std::max(maxk, (int)k_act[i]);
     if (maxk > lg.ccap || k != lg.ck) {
         HIPCHK(hipStreamSynchronize(s));
-        if (lg.ch) { HIPCHK(hipHostFree(lg.ch)); lg.ch = nullptr; }
-        if (lg.cd) { HIPCHK(hipFree(lg.cd)); lg.cd = nullptr; }
-        lg.ccap = 0;
         const int cap = round_up(std::max(2 * maxk, 64), 16);
         const size_t hbytes = (size_t)round_up(k * (cap / 16) * 4, 256) + ((size_t)k * cap * (Do + cols) + (size_t)k * FSRL_MAX_ACT) * 4;
-        HIPCHK(hipHostMalloc(&lg.ch, hbytes));
+        lg.ccap = 0;                // regrows for another member count too
+        HIPCHK(ga.mem.regrow(lg.ccap, cap, cap, {Mem::H(&lg.ch, hbytes), Mem::D(&lg.cd, (size_t)k * cap * (2 * hm + FSRL_MAX_ACT) * 4)}));
         memset(lg.ch, 0, hbytes);
-        HIPCHK(hipMalloc(&lg.cd, (size_t)k * cap * (2 * hm + FSRL_MAX_ACT) * 4));
-        lg.ccap = cap; lg.ck = k;
+        lg.ck = k;
     }
     const LayGroupPinned pin = lay_group_pinned(lg, Do, cols);
     const int cap = lg.ccap;

@@ -11,6 +11,7 @@
 #include "kernels_per.hpp"
 
 struct PerState {
+    Mem mem;
     double alpha = 0.6, beta = 0.4;
     int weight_norm = 1;
     int bound = 1, slots = 0;
@@ -30,8 +31,7 @@ static PerDev per_dev(const PerState* p) {
 static void per_free(fsrl_ctx* c) {
     PerState* p = c->per;
     if (!p) return;
-    for (void* q : {(void*)p->tree, (void*)p->sc, (void*)p->stamp, (void*)p->w, (void*)p->wd, (void*)p->td, (void*)p->u_idx, (void*)p->u_w})
-        if (q) (void)hipFree(q);
+    p->mem.release_all();
     if (p->upd_done) (void)hipEventDestroy(p->upd_done);
     delete p;
     c->per = nullptr;
@@ -126,9 +126,9 @@ extern "C" int fsrl_per_enable(fsrl_ctx* c, double alpha, double beta, int32_t w
     c->per = p;
     p->alpha = alpha; p->beta = beta; p->weight_norm = weight_norm ? 1 : 0;
     p->cap_nodes = 2 * (int64_t)per_pow2_at_least(std::max<int64_t>(c->alloc_rows, c->maxsize));
-    HIPCHK(hipMalloc(&p->tree, (size_t)p->cap_nodes * 8));
-    HIPCHK(hipMalloc(&p->sc, 3 * 8));
-    HIPCHK(hipMalloc(&p->stamp, (size_t)(p->cap_nodes / 2) * 4));
+    HIPCHK(p->mem.dev(&p->tree, (size_t)p->cap_nodes * 8));
+    HIPCHK(p->mem.dev(&p->sc, 3 * 8));
+    HIPCHK(p->mem.dev(&p->stamp, (size_t)(p->cap_nodes / 2) * 4));
     HIPCHK(hipMemset(p->stamp, 0xff, (size_t)(p->cap_nodes / 2) * 4));
     HIPCHK(hipEventCreateWithFlags(&p->upd_done, hipEventDisableTiming));
     // rows already stored: PrioritizedReplayBuffer.add's max_prio ** alpha with max_prio at its initial 1
@@ -151,11 +151,8 @@ static int per_alloc_batch(fsrl_ctx* c, int B) {
     PerState* p = c->per;
     if (B <= p->cap_B) return 0;
     HIPCHK(hipStreamSynchronize(c->compute));
-    for (void* q : {(void*)p->w, (void*)p->wd, (void*)p->td}) if (q) HIPCHK(hipFree(q));
-    p->w = nullptr; p->wd = nullptr; p->td = nullptr; p->cap_B = 0;
-    HIPCHK(hipMalloc(&p->w, (size_t)B * 4)); HIPCHK(hipMalloc(&p->wd, (size_t)B * 8)); HIPCHK(hipMalloc(&p->td, (size_t)B * 4));
+    HIPCHK(p->mem.regrow(p->cap_B, B, B, {Mem::D(&p->w, (size_t)B * 4), Mem::D(&p->wd, (size_t)B * 8), Mem::D(&p->td, (size_t)B * 4)}));
     HIPCHK(hipMemsetAsync(p->td, 0, (size_t)B * 4, c->compute));
-    p->cap_B = B;
     return 0;
 }
 // the weights' side of a sample of B rows, and the priorities' side of the update behind it (the solo launches below; a
@@ -205,11 +202,7 @@ extern "C" int fsrl_per_update_weight(fsrl_ctx* c, const int64_t* indices, const
     if (rc) return rc;
     if (n > p->cap_u) {
         HIPCHK(hipStreamSynchronize(c->compute));
-        if (p->u_idx) HIPCHK(hipFree(p->u_idx));
-        if (p->u_w) HIPCHK(hipFree(p->u_w));
-        p->u_idx = nullptr; p->u_w = nullptr; p->cap_u = 0;
-        HIPCHK(hipMalloc(&p->u_idx, (size_t)n * 4)); HIPCHK(hipMalloc(&p->u_w, (size_t)n * 8));
-        p->cap_u = n;
+        HIPCHK(p->mem.regrow(p->cap_u, n, n, {Mem::D(&p->u_idx, (size_t)n * 4), Mem::D(&p->u_w, (size_t)n * 8)}));
     }
     HIPCHK(hipMemcpyAsync(p->u_idx, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->compute));
     HIPCHK(hipMemcpyAsync(p->u_w, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->compute));

@@ -28,16 +28,13 @@ static int ensure_ppo_buffers(fsrl_ctx* c, int B) {
     const int mbp = round_up(2 * B, 32);      // 32: a grouped launch's 32-row tiles may cover one 16-row group past the last minibatch row
     if (mbp <= c->mbp_max) return 0;
     HIPCHK(hipStreamSynchronize(c->compute));
-    for (float** p : {&c->A1, &c->A2, &c->D1, &c->D2, &c->DO, &c->statp, &c->gsq_part})
-        if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
     const int H = c->cfg.hidden, nn = c->md.n_nets;
     const size_t act = (size_t)nn * mbp * H * 4;
-    HIPCHK(hipMalloc(&c->A1, act)); HIPCHK(hipMalloc(&c->A2, act));
-    HIPCHK(hipMalloc(&c->D1, act)); HIPCHK(hipMalloc(&c->D2, act));
-    HIPCHK(hipMalloc(&c->DO, (size_t)nn * mbp * FSRL_DOW * 4));
-    HIPCHK(hipMalloc(&c->statp, (size_t)(mbp / 4) * nn * 4 * 4));      // one slot per 4-row tile
-    HIPCHK(hipMalloc(&c->gsq_part, (size_t)std::max(wg_grid(H, nn), c->n_dev / 256 + 2) * 4));   // per-block squared norms (either wgrad path)
-    c->mbp_max = mbp;
+    HIPCHK(c->mem.regrow(c->mbp_max, mbp, mbp,
+                         {Mem::D(&c->A1, act), Mem::D(&c->A2, act), Mem::D(&c->D1, act), Mem::D(&c->D2, act),
+                          Mem::D(&c->DO, (size_t)nn * mbp * FSRL_DOW * 4),
+                          Mem::D(&c->statp, (size_t)(mbp / 4) * nn * 4 * 4),      // one slot per 4-row tile
+                          Mem::D(&c->gsq_part, (size_t)std::max(wg_grid(H, nn), c->n_dev / 256 + 2) * 4)}));   // per-block squared norms (either wgrad path)
     c->n_tiles_max = mbp / 16;
     return 0;
 }
@@ -110,8 +107,8 @@ extern "C" int fsrl_ppo_begin(fsrl_ctx* c, const double* lagrangians, double res
     ia.values = c->values; ia.vnext = c->vnext; ia.logp_old = c->logp_old; ia.mu_out = nullptr;
     if (c->cfg.algo == FSRL_ALGO_FOCOPS) {      // old distribution of the pass batches: means + sigma_param snapshot
         if (!c->mu_old) {
-            HIPCHK(hipMalloc(&c->mu_old, (size_t)c->alloc_rows * Da * 4));
-            HIPCHK(hipMalloc(&c->sigma_old, FSRL_MAX_ACT * 4));
+            HIPCHK(c->mem.dev(&c->mu_old, (size_t)c->alloc_rows * Da * 4));
+            HIPCHK(c->mem.dev(&c->sigma_old, FSRL_MAX_ACT * 4));
         }
         ia.mu_out = c->mu_old;
         HIPCHK(hipMemcpyAsync(c->sigma_old, c->P + c->md.net[0].sigma, (size_t)Da * 4, hipMemcpyDeviceToDevice, s));
@@ -133,14 +130,8 @@ extern "C" int fsrl_ppo_begin(fsrl_ctx* c, const double* lagrangians, double res
     const size_t nmb = c->mb_start.size();
     if (nmb > c->mb_cap) {
         HIPCHK(hipStreamSynchronize(s));
-        if (c->d_mbstart) HIPCHK(hipFree(c->d_mbstart));
-        if (c->d_mbsize) HIPCHK(hipFree(c->d_mbsize));
-        if (c->h_mbplan) HIPCHK(hipHostFree(c->h_mbplan));
-        c->d_mbstart = c->d_mbsize = nullptr; c->h_mbplan = nullptr;
         const size_t cap = nmb * 2;
-        HIPCHK(hipMalloc(&c->d_mbstart, cap * 4)); HIPCHK(hipMalloc(&c->d_mbsize, cap * 4));
-        HIPCHK(hipHostMalloc(&c->h_mbplan, cap * 2 * 4));
-        c->mb_cap = cap;
+        HIPCHK(c->mem.regrow(c->mb_cap, nmb, cap, {Mem::D(&c->d_mbstart, cap * 4), Mem::D(&c->d_mbsize, cap * 4), Mem::H(&c->h_mbplan, cap * 2 * 4)}));
     }
     memcpy(c->h_mbplan, c->mb_start.data(), nmb * 4);
     memcpy(c->h_mbplan + c->mb_cap, c->mb_size.data(), nmb * 4);
@@ -160,10 +151,7 @@ static int launch_gae(fsrl_ctx* c) {
     if (c->cfg.rew_norm) {
         if (c->ret64_cap < c->N) {
             HIPCHK(hipStreamSynchronize(c->compute));
-            if (c->ret64) HIPCHK(hipFree(c->ret64));
-            c->ret64 = nullptr;
-            HIPCHK(hipMalloc(&c->ret64, (size_t)c->cfg.n_critics * c->alloc_rows * 8));
-            c->ret64_cap = c->alloc_rows;
+            HIPCHK(c->mem.regrow(c->ret64_cap, c->N, c->alloc_rows, {Mem::D(&c->ret64, (size_t)c->cfg.n_critics * c->alloc_rows * 8)}));
         }
         ga.rms = c->d_rms; ga.ret64 = c->ret64;
     }
@@ -195,11 +183,11 @@ static int ensure_stats(fsrl_ctx* c, int64_t steps) {
     int64_t cap = std::max<int64_t>(steps, c->stats_cap * 2);
     cap = std::max<int64_t>(cap, 1024);
     float* nw = nullptr;
-    HIPCHK(hipMalloc(&nw, (size_t)cap * FSRL_PPO_NSTATS * 4));
+    HIPCHK(c->mem.dev(&nw, (size_t)cap * FSRL_PPO_NSTATS * 4));      // the rows so far are kept: the old block goes after the copy
     if (c->d_stats) {
         HIPCHK(hipStreamSynchronize(c->compute));
         HIPCHK(hipMemcpy(nw, c->d_stats, (size_t)c->stats_cap * FSRL_PPO_NSTATS * 4, hipMemcpyDeviceToDevice));
-        HIPCHK(hipFree(c->d_stats));
+        HIPCHK(c->mem.release(&c->d_stats));
     }
     c->d_stats = nw;
     c->stats_cap = cap;
@@ -236,10 +224,7 @@ static int ppo_pass_prepare(fsrl_ctx* c, const int64_t* perm, uint64_t seed, con
         pa.mean_old = (c->cfg.algo == FSRL_ALGO_FOCOPS) ? c->mu_old : nullptr; pa.sigma_old = c->sigma_old;
         if ((size_t)nmb > c->mbstat_cap) {
             HIPCHK(hipStreamSynchronize(s));
-            if (c->mbstat) HIPCHK(hipFree(c->mbstat));
-            c->mbstat = nullptr;
-            HIPCHK(hipMalloc(&c->mbstat, (size_t)nmb * 2 * FSRL_MAX_CRITICS * 2 * sizeof(float)));
-            c->mbstat_cap = (size_t)nmb * 2;
+            HIPCHK(c->mem.regrow(c->mbstat_cap, (size_t)nmb, (size_t)nmb * 2, {Mem::D(&c->mbstat, (size_t)nmb * 2 * FSRL_MAX_CRITICS * 2 * sizeof(float))}));
         }
         pa.mbstat = c->mbstat; pa.batch = c->mb_size[0]; pa.nmb = nmb;
         if (pa.norm_adv) hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(nmb), dim3(1024), 0, s, pa);
@@ -489,10 +474,10 @@ static int clip_fuse_begin(fsrl_ctx* c) {
     if (!clip_fuse_update_ok(f)) return 0;
     hipStream_t s = c->compute;
     if (!c->clip_slots) {
-        HIPCHK(hipMalloc(&c->clip_slots, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long)));
+        HIPCHK(c->mem.dev(&c->clip_slots, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(c->clip_slots, 0, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long), s));
     }
-    if (!c->clip_snap) HIPCHK(hipMalloc(&c->clip_snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4));
+    if (!c->clip_snap) HIPCHK(c->mem.dev(&c->clip_snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4));
     HIPCHK(hipMemcpyAsync(c->clip_snap, c->P, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc, c->M, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc + c->n_dev, c->V, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));

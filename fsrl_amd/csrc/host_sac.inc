@@ -7,6 +7,7 @@
 
 struct SacState {
     fsrl_sac_config cfg{};
+    Mem mem;                                   // every block of this state, the alternate batch set, the CVPO fields and ka / kq's working sets
     ModelDesc mda{}, mdq{};
     std::vector<TensorMap> tmap_a, tmap_q;     // API order -> device offsets
     int na_api = 0, nq_api = 0, na_dev = 0, nq_dev = 0;
@@ -198,16 +199,16 @@ static size_t sac_critic_bytes(const fsrl_ctx* c, const SacState* s) { return ((
 static int sac_alloc_state(fsrl_ctx* c, SacState* s) {
     sac_layout(c, s);
     const size_t ab = sac_actor_bytes(c, s), qb = sac_critic_bytes(c, s);
-    for (float** p : {&s->PA, &s->MA, &s->VA, &s->PAT}) { HIPCHK(hipMalloc(p, ab)); HIPCHK(hipMemsetAsync(*p, 0, ab, c->compute)); }
-    for (float** p : {&s->PQ, &s->PQT, &s->MQ, &s->VQ}) { HIPCHK(hipMalloc(p, qb)); HIPCHK(hipMemsetAsync(*p, 0, qb, c->compute)); }
+    for (float** p : {&s->PA, &s->MA, &s->VA, &s->PAT}) { HIPCHK(s->mem.dev(p, ab)); HIPCHK(hipMemsetAsync(*p, 0, ab, c->compute)); }
+    for (float** p : {&s->PQ, &s->PQT, &s->MQ, &s->VQ}) { HIPCHK(s->mem.dev(p, qb)); HIPCHK(hipMemsetAsync(*p, 0, qb, c->compute)); }
     if (s->layered) {           // parameter-layout gradient vectors of the layered weight-side launches
-        HIPCHK(hipMalloc(&s->GA, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(s->GA, 0, (size_t)s->na_dev * 4, c->compute));
-        HIPCHK(hipMalloc(&s->GQ, (size_t)s->nq_dev * 4)); HIPCHK(hipMemsetAsync(s->GQ, 0, (size_t)s->nq_dev * 4, c->compute));
+        HIPCHK(s->mem.dev(&s->GA, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(s->GA, 0, (size_t)s->na_dev * 4, c->compute));
+        HIPCHK(s->mem.dev(&s->GQ, (size_t)s->nq_dev * 4)); HIPCHK(hipMemsetAsync(s->GQ, 0, (size_t)s->nq_dev * 4, c->compute));
     }
-    HIPCHK(hipMalloc(&s->sc, sizeof(SacScalars)));
-    HIPCHK(hipMalloc(&s->d_stats, (size_t)SAC_RING * s->nstats * 4));
-    HIPCHK(hipMalloc(&s->d_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
-    HIPCHK(hipHostMalloc(&s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
+    HIPCHK(s->mem.dev(&s->sc, sizeof(SacScalars)));
+    HIPCHK(s->mem.dev(&s->d_stats, (size_t)SAC_RING * s->nstats * 4));
+    HIPCHK(s->mem.dev(&s->d_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
+    HIPCHK(s->mem.pinned(&s->h_book, (size_t)c->cfg.env_num * sizeof(SacBook)));
     return 0;
 }
 
@@ -243,24 +244,10 @@ extern "C" int fsrl_sac_init(fsrl_ctx* c, const fsrl_sac_config* cfg) {
 static void sac_free(fsrl_ctx* c) {
     SacState* s = sac_of(c);
     if (!s) return;
-    for (void* p : {(void*)s->PAT, (void*)s->PA, (void*)s->MA, (void*)s->VA, (void*)s->PQ, (void*)s->PQT, (void*)s->MQ,
-                    (void*)s->VQ, (void*)s->sc, (void*)s->d_idx, (void*)s->d_chain, (void*)s->d_end,
-                    (void*)s->XQ, (void*)s->OBS, (void*)s->OBSN, (void*)s->XN, (void*)s->XP, (void*)s->eps_t,
-                    (void*)s->eps_p, (void*)s->LPN, (void*)s->LP, (void*)s->QT, (void*)s->QP, (void*)s->Y,
-                    (void*)s->DA, (void*)s->A1, (void*)s->A2, (void*)s->D1, (void*)s->D2, (void*)s->DO,
-                    (void*)s->stq, (void*)s->stdin_, (void*)s->stpi, (void*)s->gsq_scratch, (void*)s->d_stats, (void*)s->d_book,
-                    (void*)s->csc, (void*)s->MU_OLD, (void*)s->STD_OLD, (void*)s->XK, (void*)s->QK, (void*)s->q0,
-                    (void*)s->q1, (void*)s->Wk, (void*)s->eps_k, (void*)s->stqk, (void*)s->alt.d_idx, (void*)s->alt.d_chain,
-                    (void*)s->alt.d_end, (void*)s->alt.XQ, (void*)s->alt.OBS, (void*)s->alt.OBSN, (void*)s->alt.XN, (void*)s->alt.XP,
-                    (void*)s->alt.eps_t, (void*)s->alt.eps_p})
-        if (p) (void)hipFree(p);
-    for (float* p : {s->GA, s->GQ, s->DXQ}) if (p) (void)hipFree(p);
-    lay_work_free(s->ka); lay_work_free(s->kq);
+    s->mem.release_all();
     if (s->pre_done) (void)hipEventDestroy(s->pre_done);
     if (s->upd_done) (void)hipEventDestroy(s->upd_done);
     if (s->book_done) (void)hipEventDestroy(s->book_done);
-    for (void* p : {(void*)s->h_idx, (void*)s->h_chain, (void*)s->h_end, (void*)s->h_eps, (void*)s->h_book, (void*)s->h_epsk})
-        if (p) (void)hipHostFree(p);
     delete s;
     c->sac = nullptr;
 }
@@ -362,57 +349,37 @@ static int sac_alloc_batch(fsrl_ctx* c, SacState* s, int B) {
                         HIPCHK(hipEventCreateWithFlags(&s->book_done, hipEventDisableTiming)); }
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim, Din = Do + Da, H = c->cfg.hidden, ns = s->cfg.n_step;
     const size_t Bp = (size_t)s->n_tiles * 16 + 64;
-    auto re = [&](auto** p, size_t bytes) -> int {
-        if (*p) HIPCHK(hipFree(*p));
-        *p = nullptr;
-        bytes = std::max<size_t>(bytes, 16);          // a layered context has no tile-kernel slabs (H = 0)
-        HIPCHK(hipMalloc(p, bytes));
-        HIPCHK(hipMemsetAsync(*p, 0, bytes, c->compute));
-        return 0;
-    };
-    auto reh = [&](auto** p, size_t bytes) -> int {
-        if (*p) HIPCHK(hipHostFree(*p));
-        *p = nullptr;
-        HIPCHK(hipHostMalloc(p, bytes));
-        return 0;
-    };
-    int rc = 0;
-    rc |= re(&s->d_idx, Bp * 4); rc |= re(&s->d_chain, Bp * ns * 4); rc |= re(&s->d_end, Bp * ns);
-    rc |= reh(&s->h_idx, Bp * 4); rc |= reh(&s->h_chain, Bp * ns * 4); rc |= reh(&s->h_end, Bp * ns);
-    rc |= reh(&s->h_eps, Bp * Da * 4 * 2);
-    rc |= re(&s->XQ, Bp * Din * 4); rc |= re(&s->XN, Bp * Din * 4); rc |= re(&s->XP, Bp * Din * 4);
-    rc |= re(&s->OBS, Bp * Do * 4); rc |= re(&s->OBSN, Bp * Do * 4);
-    rc |= re(&s->eps_t, Bp * Da * 4); rc |= re(&s->eps_p, Bp * Da * 4);
-    if (!s->cvpo) {
-        rc |= re(&s->alt.d_idx, Bp * 4); rc |= re(&s->alt.d_chain, Bp * ns * 4); rc |= re(&s->alt.d_end, Bp * ns);
-        rc |= re(&s->alt.XQ, Bp * Din * 4); rc |= re(&s->alt.XN, Bp * Din * 4); rc |= re(&s->alt.XP, Bp * Din * 4);
-        rc |= re(&s->alt.OBS, Bp * Do * 4); rc |= re(&s->alt.OBSN, Bp * Do * 4);
-        rc |= re(&s->alt.eps_t, Bp * Da * 4); rc |= re(&s->alt.eps_p, Bp * Da * 4);
-    }
-    rc |= re(&s->LPN, Bp * 4); rc |= re(&s->LP, Bp * 4); rc |= re(&s->QT, 4 * Bp * 4); rc |= re(&s->QP, 4 * Bp * 4);
-    rc |= re(&s->Y, 2 * Bp * 4); rc |= re(&s->DA, 4 * Bp * Da * 4);
-    rc |= re(&s->A1, 4 * Bp * H * 4); rc |= re(&s->A2, 4 * Bp * H * 4); rc |= re(&s->D1, 4 * Bp * H * 4);
-    rc |= re(&s->D2, 4 * Bp * H * 4); rc |= re(&s->DO, 4 * Bp * FSRL_DOW * 4);
-    // per-tile partial statistics: room for 4-row tiles (4 x the 16-row tile count)
-    rc |= re(&s->stq, (size_t)(4 * s->n_tiles + 4) * 4 * FB_NSTAT * 4); rc |= re(&s->stdin_, (size_t)(4 * s->n_tiles + 4) * 4 * FB_NSTAT * 4);
-    rc |= re(&s->stpi, (size_t)(8 * s->n_tiles + 8) * FB_NSTAT * 4);     // two batches in the merged forward launch
-    if (s->cvpo) {
-        const size_t K = (size_t)s->ccfg.sample_act_num, KB = K * Bp;
-        rc |= re(&s->MU_OLD, Bp * Da * 4); rc |= re(&s->STD_OLD, Bp * Da * 4);
-        rc |= re(&s->XK, KB * Din * 4); rc |= re(&s->QK, 4 * KB * 4); rc |= re(&s->q0, KB * 4); rc |= re(&s->q1, KB * 4);
-        rc |= re(&s->Wk, KB * 4); rc |= re(&s->eps_k, KB * Da * 4); rc |= reh(&s->h_epsk, KB * Da * 4);
-        rc |= re(&s->stqk, (size_t)(4 * ((KB + 15) / 16) + 4) * 4 * FB_NSTAT * 4);
-    }
-    if (rc) return FSRL_EHIP;
+    s->cap_B = 0;               // until the whole set stands: also over the layered working sets and DXQ
     if (s->layered) {
-        rc = lay_work_ensure(c, s->ka, (int)Bp);
+        int rc = lay_work_ensure(c, s->mem, s->ka, (int)Bp);
         if (rc) return rc;
-        rc = lay_work_ensure(c, s->kq, s->cvpo ? (int)(Bp * s->ccfg.sample_act_num) : (int)Bp);      // CVPO: the K x B particle rows of the E-step
+        rc = lay_work_ensure(c, s->mem, s->kq, s->cvpo ? (int)(Bp * s->ccfg.sample_act_num) : (int)Bp);      // CVPO: the K x B particle rows of the E-step
         if (rc) return rc;
-        if (s->DXQ) { HIPCHK(hipFree(s->DXQ)); s->DXQ = nullptr; }
-        HIPCHK(hipMalloc(&s->DXQ, (size_t)s->n_q * s->kq.mbp * Din * 4));
+        HIPCHK(s->mem.release(&s->DXQ));
+        HIPCHK(s->mem.dev(&s->DXQ, (size_t)s->n_q * s->kq.mbp * Din * 4));
     }
-    s->cap_B = B;
+    // device buffers are zero-filled below; at least 16 bytes: a layered context has no tile-kernel slabs (H = 0).  on = false: not in this mode
+    auto d = [](auto** p, size_t bytes, bool on = true) { return Mem::D(p, on ? std::max<size_t>(bytes, 16) : 0); };
+    const bool cv = s->cvpo;
+    const size_t K = cv ? (size_t)s->ccfg.sample_act_num : 0, KB = K * Bp;
+    const std::initializer_list<Mem::Req> set = {
+        d(&s->d_idx, Bp * 4), d(&s->d_chain, Bp * ns * 4), d(&s->d_end, Bp * ns),
+        Mem::H(&s->h_idx, Bp * 4), Mem::H(&s->h_chain, Bp * ns * 4), Mem::H(&s->h_end, Bp * ns), Mem::H(&s->h_eps, Bp * Da * 4 * 2),
+        d(&s->XQ, Bp * Din * 4), d(&s->XN, Bp * Din * 4), d(&s->XP, Bp * Din * 4), d(&s->OBS, Bp * Do * 4), d(&s->OBSN, Bp * Do * 4),
+        d(&s->eps_t, Bp * Da * 4), d(&s->eps_p, Bp * Da * 4),
+        d(&s->alt.d_idx, Bp * 4, !cv), d(&s->alt.d_chain, Bp * ns * 4, !cv), d(&s->alt.d_end, Bp * ns, !cv),
+        d(&s->alt.XQ, Bp * Din * 4, !cv), d(&s->alt.XN, Bp * Din * 4, !cv), d(&s->alt.XP, Bp * Din * 4, !cv),
+        d(&s->alt.OBS, Bp * Do * 4, !cv), d(&s->alt.OBSN, Bp * Do * 4, !cv), d(&s->alt.eps_t, Bp * Da * 4, !cv), d(&s->alt.eps_p, Bp * Da * 4, !cv),
+        d(&s->LPN, Bp * 4), d(&s->LP, Bp * 4), d(&s->QT, 4 * Bp * 4), d(&s->QP, 4 * Bp * 4), d(&s->Y, 2 * Bp * 4), d(&s->DA, 4 * Bp * Da * 4),
+        d(&s->A1, 4 * Bp * H * 4), d(&s->A2, 4 * Bp * H * 4), d(&s->D1, 4 * Bp * H * 4), d(&s->D2, 4 * Bp * H * 4), d(&s->DO, 4 * Bp * FSRL_DOW * 4),
+        // per-tile partial statistics: room for 4-row tiles (4 x the 16-row tile count); stpi: two batches in the merged forward launch
+        d(&s->stq, (size_t)(4 * s->n_tiles + 4) * 4 * FB_NSTAT * 4), d(&s->stdin_, (size_t)(4 * s->n_tiles + 4) * 4 * FB_NSTAT * 4),
+        d(&s->stpi, (size_t)(8 * s->n_tiles + 8) * FB_NSTAT * 4),
+        d(&s->MU_OLD, Bp * Da * 4, cv), d(&s->STD_OLD, Bp * Da * 4, cv), d(&s->XK, KB * Din * 4, cv), d(&s->QK, 4 * KB * 4, cv),
+        d(&s->q0, KB * 4, cv), d(&s->q1, KB * 4, cv), d(&s->Wk, KB * 4, cv), d(&s->eps_k, KB * Da * 4, cv), Mem::H(&s->h_epsk, KB * Da * 4),
+        d(&s->stqk, (size_t)(4 * ((KB + 15) / 16) + 4) * 4 * FB_NSTAT * 4, cv)};
+    HIPCHK(s->mem.regrow(s->cap_B, B, B, set));
+    for (const Mem::Req& r : set) if (!r.pin && r.bytes) HIPCHK(hipMemsetAsync(*r.field, 0, r.bytes, c->compute));
     return 0;
 }
 
@@ -640,7 +607,7 @@ static int sac_wgrad(fsrl_ctx* c, SacState* s, const ModelDesc& md, int ny, cons
         // nothing for the Adam kernel to add up.
         int rc = ensure_parts(c, n_dev, 1);
         if (rc) return rc;
-        if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
+        if (!s->gsq_scratch) HIPCHK(s->mem.dev(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
         const WgradPtrs wp = sac_wgrad_small_args(s, (int)rp, X, c->wg_parts);
         *nsplit = 1;
         const PpoStepArgs none{};

@@ -267,10 +267,8 @@ extern "C" int fsrl_sac_group_create(fsrl_ctx** ctxs, int32_t k, fsrl_sac_group*
     HIPCHK(hipSetDevice(c0->device));
     fsrl_sac_group* g = new fsrl_sac_group();
     hipError_t e = rgroup_create(g->core, c0->device, k);
-    if (e == hipSuccess) e = hipMalloc(&g->tab.d, (size_t)k * sizeof(SacGroupMember));
-    if (e == hipSuccess) e = hipHostMalloc(&g->tab.h, (size_t)k * sizeof(SacGroupMember));
-    if (e != hipSuccess) {
-        fail(FSRL_EHIP, "SAC group allocation failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) fail(FSRL_EHIP, "SAC group allocation failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess || table_ensure(g->tab, (size_t)k, (size_t)k)) {
         (void)fsrl_sac_group_destroy(g);
         return FSRL_EHIP;
     }
@@ -326,7 +324,7 @@ static int group_member_base(fsrl_ctx* c, SacState* s, SacGroupMember& t, int B,
     rc = ensure_parts(c, s->na_dev, 1);
     if (rc) return rc;
     t.GA = c->wg_parts;
-    if (!s->gsq_scratch) HIPCHK(hipMalloc(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
+    if (!s->gsq_scratch) HIPCHK(s->mem.dev(&s->gsq_scratch, (size_t)wg_grid(256, FSRL_MAX_NETS) * 4));
     t.wq = sac_wgrad_small_args(s, rp, s->XQ, const_cast<float*>(t.GQ));
     t.wa = sac_wgrad_small_args(s, rp, s->OBS, const_cast<float*>(t.GA));
     *nsplit_q = *nsplit_a = 1;

@@ -40,6 +40,7 @@ struct fsrl_traj {
     // fsrl_store_fill: [job table | low[Da] | scale[Da]] in one pinned buffer and its device copy; fill_done is recorded behind the
     // last fill's launch on the side stream it ran on
     DevTable<uint8_t> fill;
+    Mem mem;                            // the two halves' columns
     hipEvent_t fill_done = nullptr;
     bool fill_pending = false;
     int64_t fill_launches = 0, fill_copies = 0;
@@ -54,6 +55,7 @@ static int traj_fill_wait(fsrl_traj* t) {
 struct fsrl_tap {
     fsrl_traj* t = nullptr;
     fsrl_ctx* c = nullptr;
+    Mem mem;                            // the open-episode columns and the two windows
     int32_t source = 0;
     int L = 0;                          // rows per env of the open-episode area = max_episode_len
     std::vector<trajp::OpenEpisode> env;
@@ -64,16 +66,11 @@ struct fsrl_tap {
     size_t rec = 0, max_jobs = 0;
 };
 
-static int traj_cols_alloc(TrajCols& c, size_t rows, int Do, int Da) {
-    HIPCHK(hipMalloc(&c.obs, rows * Do * 4)); HIPCHK(hipMalloc(&c.obs_next, rows * Do * 4));
-    HIPCHK(hipMalloc(&c.act, rows * Da * 4)); HIPCHK(hipMalloc(&c.rew, rows * 8)); HIPCHK(hipMalloc(&c.cost, rows * 8));
-    HIPCHK(hipMalloc(&c.terminals, rows)); HIPCHK(hipMalloc(&c.timeouts, rows));
+static int traj_cols_alloc(Mem& m, TrajCols& c, size_t rows, int Do, int Da) {
+    HIPCHK(m.dev(&c.obs, rows * Do * 4)); HIPCHK(m.dev(&c.obs_next, rows * Do * 4));
+    HIPCHK(m.dev(&c.act, rows * Da * 4)); HIPCHK(m.dev(&c.rew, rows * 8)); HIPCHK(m.dev(&c.cost, rows * 8));
+    HIPCHK(m.dev(&c.terminals, rows)); HIPCHK(m.dev(&c.timeouts, rows));
     return 0;
-}
-static void traj_cols_free(TrajCols& c) {
-    void* p[] = {c.obs, c.obs_next, c.act, c.rew, c.cost, c.terminals, c.timeouts};
-    for (void* q : p) if (q) (void)hipFree(q);
-    c = TrajCols{};
 }
 
 static inline bool tap_closed(const fsrl_ctx* c, int e) { return c->tap->env[(size_t)e].ends >= 2; }
@@ -159,11 +156,7 @@ static void tap_free(fsrl_tap* tp, bool commit) {
     c->tap = nullptr;
     fsrl_traj* t = tp->t;
     t->taps.erase(std::remove(t->taps.begin(), t->taps.end(), tp), t->taps.end());
-    traj_cols_free(tp->open);
-    for (int i = 0; i < 2; ++i) {
-        if (tp->h[i]) (void)hipHostFree(tp->h[i]);
-        if (tp->d[i]) (void)hipFree(tp->d[i]);
-    }
+    tp->mem.release_all();
     delete tp;
 }
 static void tap_ctx_gone(fsrl_ctx* c) { if (c->tap) tap_free(c->tap, true); }
@@ -176,7 +169,7 @@ extern "C" int fsrl_traj_destroy(fsrl_traj* t) {
     if (t->fill_done) (void)hipEventDestroy(t->fill_done);
     table_free(t->fill);
     if (t->stream) { (void)hipStreamSynchronize(t->stream); (void)hipStreamDestroy(t->stream); }
-    traj_cols_free(t->half[0]); traj_cols_free(t->half[1]);
+    t->mem.release_all();
     table_free(t->jobs);
     delete t;
     return 0;
@@ -200,8 +193,8 @@ extern "C" int fsrl_traj_create(fsrl_ctx* c, int64_t max_rows, int32_t max_episo
     int rc = 0;
     { hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking); if (e != hipSuccess) rc = fail(FSRL_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
     if (!rc && hipEventCreateWithFlags(&t->fill_done, hipEventDisableTiming) != hipSuccess) rc = fail(FSRL_EHIP, "hipEventCreate failed");
-    if (!rc) rc = traj_cols_alloc(t->half[0], (size_t)max_rows, t->Do, t->Da);
-    if (!rc) rc = traj_cols_alloc(t->half[1], (size_t)max_rows, t->Do, t->Da);
+    if (!rc) rc = traj_cols_alloc(t->mem, t->half[0], (size_t)max_rows, t->Do, t->Da);
+    if (!rc) rc = traj_cols_alloc(t->mem, t->half[1], (size_t)max_rows, t->Do, t->Da);
     if (rc) { const std::string keep = g_err; fsrl_traj_destroy(t); g_err = keep; return rc; }
     *out = t;
     return 0;
@@ -222,9 +215,9 @@ extern "C" int fsrl_traj_attach(fsrl_traj* t, fsrl_ctx* c, int32_t* source_out) 
     tp->rec = 4 + 4 * (size_t)t->Da;
     tp->max_jobs = 2 * (size_t)c->cfg.env_num * (((size_t)tp->L + trajp::JOB_ROWS - 1) / trajp::JOB_ROWS);
     const size_t bytes = ((size_t)fsrl_ctx::STAGE_CAP * tp->rec + 7) / 8 * 8 + tp->max_jobs * sizeof(TrajJob);
-    rc = traj_cols_alloc(tp->open, 2 * (size_t)c->cfg.env_num * tp->L, t->Do, t->Da);
+    rc = traj_cols_alloc(tp->mem, tp->open, 2 * (size_t)c->cfg.env_num * tp->L, t->Do, t->Da);
     for (int i = 0; i < 2 && !rc; ++i) {
-        if (hipHostMalloc(&tp->h[i], bytes) != hipSuccess || hipMalloc(&tp->d[i], bytes) != hipSuccess)
+        if (tp->mem.pinned(&tp->h[i], bytes) != hipSuccess || tp->mem.dev(&tp->d[i], bytes) != hipSuccess)
             rc = fail(FSRL_EHIP, "trajectory tap: allocating %zu bytes failed", bytes);
     }
     t->taps.push_back(tp);

@@ -20,7 +20,8 @@ struct TrState {
     float *cA1 = nullptr, *cA2 = nullptr, *cD1 = nullptr, *cD2 = nullptr, *cDO = nullptr, *cstatp = nullptr;
     double *c_d_scal = nullptr, *c_d_ssq = nullptr;
     double* h_crit = nullptr;           // pinned: [C * FB_NSTAT] batch sums of the last step | [32 * C] squared-norm partials
-    fsrl_ctx::Parts c_parts;            // the lane's split-K partials (swapped into fsrl_ctx::parts while the lane is current)
+    fsrl_ctx::Parts c_parts;            // the lane's split-K partials (swapped into fsrl_ctx::parts while the lane is current): like every
+                                        // Parts block it is ensure_parts' and so the context's (c->mem), never this state's
     bool crit_pending = false; int crit_l2 = 0;
     bool opt_overlap = true;            // fsrl_tr_set_plan(tile_rows + 64): critic steps on the compute stream, one after the other (A/B)
     uint64_t rd_version = 0;            // fsrl_ctx::theta_version when mean_old / std_old of the batch (view) were computed
@@ -53,6 +54,7 @@ struct TrState {
     double* d_scal = nullptr;
     double* d_ssq = nullptr;        // [32 * n_critics] partial sums of squares (l2 term of the logged critic loss)
     size_t cap_rows = 0;
+    Mem mem;
     int64_t critic_t = 0;     // Adam step count of the critic optimiser
     int na = 0;               // flat actor parameter count (API order)
     std::vector<int32_t> ls_iters;   // line-search evaluations of every repeat of the last learn call
@@ -75,13 +77,7 @@ static void tr_free(fsrl_ctx* c) {
     if (!t) return;
     if (t->cstream) { (void)hipStreamSynchronize(t->cstream); (void)hipStreamDestroy(t->cstream); }
     if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
-    for (void* p : std::initializer_list<void*>{t->A1, t->A2, t->D1, t->D2, t->DO, t->RA1, t->RA2, t->RD1, t->RD2, t->RDO, t->statp,
-                     t->mu_old, t->Vdev, t->Out, t->rd, t->cg_r, t->cg_x, t->cg_g, t->obs_pad, t->vec, t->cg_sc, t->co_counter,
-                     t->cA1, t->cA2, t->cD1, t->cD2, t->cDO, t->cstatp, t->c_parts.p, t->c_d_scal, t->c_d_ssq, t->cg_part,
-                     t->d_scal, t->d_ssq})
-        if (p) (void)hipFree(p);
-    for (void* p : std::initializer_list<void*>{t->h_part, t->h_rb, t->h_rb_done, t->h_crit})
-        if (p) (void)hipHostFree(p);
+    t->mem.release_all();
     delete t;
     c->tr = nullptr;
 }
@@ -118,64 +114,52 @@ static int tr_alloc(fsrl_ctx* c, TrState* t, int64_t n) {
     t->crit_pending = false;
     if ((size_t)t->rows_pad <= t->cap_rows) return 0;
     HIPCHK(hipStreamSynchronize(c->compute));
-    for (float** p : {&t->A1, &t->A2, &t->D1, &t->D2, &t->DO, &t->RA1, &t->RA2, &t->RD1, &t->RD2, &t->RDO,
-                      &t->statp, &t->mu_old, &t->rd, &t->obs_pad})
-        if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+    t->cap_rows = 0;            // from here until the whole working set stands: also the layered one and the once-only block
     const size_t rows = (size_t)t->rows_pad + 64, H = c->cfg.hidden, nn = c->md.n_nets;
     if (c->lay) {               // layered context: the layer-by-layer working set (host_layered.inc) instead of the tile kernels' slabs
         int rc = lay_ensure_rows(c, t->rows_pad, true);
         if (rc) return rc;
-    } else {
-    HIPCHK(hipMalloc(&t->A1, nn * rows * H * 4)); HIPCHK(hipMalloc(&t->A2, nn * rows * H * 4));
-    HIPCHK(hipMalloc(&t->D1, nn * rows * H * 4)); HIPCHK(hipMalloc(&t->D2, nn * rows * H * 4));
-    HIPCHK(hipMalloc(&t->DO, nn * rows * FSRL_DOW * 4));
-    HIPCHK(hipMalloc(&t->RA1, rows * H * 4)); HIPCHK(hipMalloc(&t->RA2, rows * H * 4));
-    HIPCHK(hipMalloc(&t->RD1, rows * H * 4)); HIPCHK(hipMalloc(&t->RD2, rows * H * 4));
-    HIPCHK(hipMalloc(&t->RDO, rows * FSRL_DOW * 4));
-    if (H == 256) {
-        t->pad_ko = (c->cfg.obs_dim + 63) / 64;
-        HIPCHK(hipMalloc(&t->obs_pad, rows * 64 * (size_t)t->pad_ko * 4));
     }
-    }
-    if (!c->lay && nn > 1) {            // the critic lane's own slabs (nets 1 .. C), so that its launches never touch what the actor's read
-        for (float** p : {&t->cA1, &t->cA2, &t->cD1, &t->cD2, &t->cDO, &t->cstatp})
-            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-        HIPCHK(hipMalloc(&t->cA1, (nn - 1) * rows * H * 4)); HIPCHK(hipMalloc(&t->cA2, (nn - 1) * rows * H * 4));
-        HIPCHK(hipMalloc(&t->cD1, (nn - 1) * rows * H * 4)); HIPCHK(hipMalloc(&t->cD2, (nn - 1) * rows * H * 4));
-        HIPCHK(hipMalloc(&t->cDO, (nn - 1) * rows * FSRL_DOW * 4));
-        HIPCHK(hipMalloc(&t->cstatp, (size_t)(tiles + 4) * nn * FB_NSTAT * 4));
-    }
-    HIPCHK(hipMalloc(&t->statp, (size_t)(tiles + 4) * nn * FB_NSTAT * 4));
-    HIPCHK(hipMalloc(&t->mu_old, rows * c->cfg.act_dim * 4));
-    HIPCHK(hipMalloc(&t->rd, rows * FSRL_RD * 4));
-    if (!t->Vdev) {
-        HIPCHK(hipMalloc(&t->Vdev, (size_t)c->n_alloc * 4)); HIPCHK(hipMalloc(&t->Out, (size_t)c->n_dev * 4));
+    if (!t->ev_fork) {              // once; ev_fork comes last, so a failure in here is tried again
+        HIPCHK(t->mem.dev(&t->Vdev, (size_t)c->n_alloc * 4)); HIPCHK(t->mem.dev(&t->Out, (size_t)c->n_dev * 4));
         for (float** p : {&t->cg_r, &t->cg_x, &t->cg_g}) {
-            HIPCHK(hipMalloc(p, (size_t)c->n_dev * 4));
+            HIPCHK(t->mem.dev(p, (size_t)c->n_dev * 4));
             HIPCHK(hipMemsetAsync(*p, 0, (size_t)c->n_dev * 4, c->compute));
         }
-        HIPCHK(hipMalloc(&t->vec, (size_t)8 * c->n_dev * 4));
+        HIPCHK(t->mem.dev(&t->vec, (size_t)8 * c->n_dev * 4));
         HIPCHK(hipMemsetAsync(t->vec, 0, (size_t)8 * c->n_dev * 4, c->compute));
-        HIPCHK(hipHostMalloc(&t->h_part, (4 * CG_NB + FSRL_MAX_ACT) * sizeof(double)));
-        HIPCHK(hipHostMalloc(&t->h_rb, 4 * CG_NB * sizeof(double)));
-        HIPCHK(hipHostMalloc(&t->h_rb_done, CG_NB * sizeof(unsigned)));
+        HIPCHK(t->mem.pinned(&t->h_part, (4 * CG_NB + FSRL_MAX_ACT) * sizeof(double)));
+        HIPCHK(t->mem.pinned(&t->h_rb, 4 * CG_NB * sizeof(double)));
+        HIPCHK(t->mem.pinned(&t->h_rb_done, CG_NB * sizeof(unsigned)));
         memset(t->h_rb_done, 0, CG_NB * sizeof(unsigned));
-        HIPCHK(hipMalloc(&t->cg_sc, sizeof(CgScal)));
-        HIPCHK(hipMalloc(&t->cg_part, 4 * CG_NB * sizeof(double)));
-        HIPCHK(hipMalloc(&t->co_counter, 64));
+        HIPCHK(t->mem.dev(&t->cg_sc, sizeof(CgScal)));
+        HIPCHK(t->mem.dev(&t->cg_part, 4 * CG_NB * sizeof(double)));
+        HIPCHK(t->mem.dev(&t->co_counter, 64));
         HIPCHK(hipMemsetAsync(t->co_counter, 0, 64, c->compute));
         t->co_base = 0u;
         HIPCHK(hipMemsetAsync(t->Vdev, 0, (size_t)c->n_alloc * 4, c->compute)); HIPCHK(hipMemsetAsync(t->Out, 0, (size_t)c->n_dev * 4, c->compute));
         HIPCHK(hipStreamSynchronize(c->compute));
-        HIPCHK(hipMalloc(&t->d_scal, 64 * sizeof(double)));
-        HIPCHK(hipMalloc(&t->d_ssq, 32 * FSRL_MAX_CRITICS * sizeof(double)));
-        HIPCHK(hipMalloc(&t->c_d_scal, 64 * sizeof(double)));
-        HIPCHK(hipMalloc(&t->c_d_ssq, 32 * FSRL_MAX_CRITICS * sizeof(double)));
-        HIPCHK(hipHostMalloc(&t->h_crit, (FSRL_MAX_CRITICS * FB_NSTAT + 32 * FSRL_MAX_CRITICS) * sizeof(double)));
-        HIPCHK(hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking));
+        HIPCHK(t->mem.dev(&t->d_scal, 64 * sizeof(double)));
+        HIPCHK(t->mem.dev(&t->d_ssq, 32 * FSRL_MAX_CRITICS * sizeof(double)));
+        HIPCHK(t->mem.dev(&t->c_d_scal, 64 * sizeof(double)));
+        HIPCHK(t->mem.dev(&t->c_d_ssq, 32 * FSRL_MAX_CRITICS * sizeof(double)));
+        HIPCHK(t->mem.pinned(&t->h_crit, (FSRL_MAX_CRITICS * FB_NSTAT + 32 * FSRL_MAX_CRITICS) * sizeof(double)));
+        if (!t->cstream) HIPCHK(hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
     }
-    t->cap_rows = (size_t)t->rows_pad;
+    // the tile kernels' slabs (not layered); obs_pad at 256 wide; the critic lane's own slabs (nets 1 .. C), so that its launches
+    // never touch what the actor's read
+    const size_t slab = c->lay ? 0 : rows * H * 4, dow = c->lay ? 0 : rows * FSRL_DOW * 4, cn = nn > 1 ? nn - 1 : 0;
+    const size_t stat = (size_t)(tiles + 4) * nn * FB_NSTAT * 4;
+    if (!c->lay && H == 256) t->pad_ko = (c->cfg.obs_dim + 63) / 64;
+    HIPCHK(t->mem.regrow(t->cap_rows, (size_t)t->rows_pad, (size_t)t->rows_pad,
+                         {Mem::D(&t->A1, nn * slab), Mem::D(&t->A2, nn * slab), Mem::D(&t->D1, nn * slab), Mem::D(&t->D2, nn * slab),
+                          Mem::D(&t->DO, nn * dow), Mem::D(&t->RA1, slab), Mem::D(&t->RA2, slab), Mem::D(&t->RD1, slab),
+                          Mem::D(&t->RD2, slab), Mem::D(&t->RDO, dow),
+                          Mem::D(&t->obs_pad, !c->lay && H == 256 ? rows * 64 * (size_t)t->pad_ko * 4 : 0),
+                          Mem::D(&t->cA1, cn * slab), Mem::D(&t->cA2, cn * slab), Mem::D(&t->cD1, cn * slab), Mem::D(&t->cD2, cn * slab),
+                          Mem::D(&t->cDO, cn * dow), Mem::D(&t->cstatp, c->lay || !cn ? 0 : stat),
+                          Mem::D(&t->statp, stat), Mem::D(&t->mu_old, rows * c->cfg.act_dim * 4), Mem::D(&t->rd, rows * FSRL_RD * 4)}));
     return 0;
 }
 

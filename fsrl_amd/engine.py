@@ -18,6 +18,13 @@ def _ptr(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
 
+def mem_live():
+    """Device and pinned blocks / bytes the library holds in this process right now (fsrl_mem_live)."""
+    v = [C.c_int64(0) for _ in range(4)]
+    _lib.check(_lib.load().fsrl_mem_live(*[C.byref(x) for x in v]))
+    return dict(zip(("dev_blocks", "dev_bytes", "pinned_blocks", "pinned_bytes"), (x.value for x in v)))
+
+
 @dataclass
 class EngineConfig:
     """Mirror of struct fsrl_config; defaults = PPOLagAgent defaults (ppo_lag_agent.py:82-116)."""

@@ -107,6 +107,12 @@ typedef struct fsrl_config {
 const char* fsrl_last_error(void);
 void fsrl_config_default(fsrl_config* cfg); /* reference defaults for PPO-Lag            */
 
+/* ---- memory ------------------------------------------------------------------------- */
+/* Device and pinned blocks (and their bytes) this process holds through the library right now, over every context, state, env,
+ * archive and group.  Read-only, no context, any thread; NULL outputs are skipped.  After everything is destroyed the four
+ * figures are back where they were before it was created: the leak test's exact statement. */
+int fsrl_mem_live(int64_t* dev_blocks, int64_t* dev_bytes, int64_t* pinned_blocks, int64_t* pinned_bytes);
+
 /* ---- context ------------------------------------------------------------------------ */
 /* replaces: PPOLagAgent.__init__ building nets + optimiser + policy on `device`
  * (fsrl/agent/ppo_lag_agent.py:127-200). */
