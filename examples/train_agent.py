@@ -90,10 +90,15 @@ def main():
         kw.update(recompute_advantage=a.recompute_advantage)
     agent = AGENTS[a.algo](env, logger, **kw)
     if device_task:
-        # the host env above gave the agent its spaces; the training envs themselves live on the agent's GPU (evaluation keeps the host envs)
+        # the host envs above gave the agent its spaces; the training envs and the test envs live on the agent's GPU: learn() and
+        # evaluate() run whole evaluations there too, storing nothing (fsrl_evaluate_device; layered --hidden-sizes step the device
+        # test envs from the host instead)
         from fsrl_amd.env import DeviceLinear, DevicePointCircle
-        env = (DevicePointCircle(agent.policy, a.envs, max_episode_steps=100, seed=a.seed) if a.task == "device-point-circle"
-               else DeviceLinear(agent.policy, like=env, seed=a.seed))
+        if a.task == "device-point-circle":
+            env = DevicePointCircle(agent.policy, a.envs, max_episode_steps=100, seed=a.seed)
+            test_env = DevicePointCircle(agent.policy, 2, max_episode_steps=100, seed=a.seed + 1000)
+        else:
+            env, test_env = DeviceLinear(agent.policy, like=env, seed=a.seed), DeviceLinear(agent.policy, like=test_env, seed=a.seed + 1)
     if a.algo in ("sacl", "ddpgl", "cvpo"):
         out = agent.learn(env, test_env, epoch=a.epoch, episode_per_collect=a.envs, step_per_epoch=6000, update_per_step=0.2,
                           batch_size=a.batch_size, testing_num=2, device_actor=a.device_actor, verbose=True, save_ckpt=False,

@@ -69,6 +69,12 @@ collects, a workgroup per seed, per seed bit-identical to its own device collect
 3.4.1).  The updates go through the same groups as above.  Layered --hidden-sizes are refused by the library at the first collect.
     python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --task device-linear
     python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped --task device-point-circle
+--test-episodes N (--grouped; default 0: no evaluation): after every epoch each seed's policy is evaluated for N episodes on test envs
+of its own and one line per seed is printed.  Over device tasks every seed has a second DeviceVectorEnv and a store-less
+DeviceCollector, and the evaluation of ALL seeds is one GroupDeviceCollector.collect -> fsrl_evaluate_device_group: nothing is
+stored and no seed's store, sampler or random stream moves, so the training run is the one without the flag, bit for bit.  Over host
+envs the seeds are evaluated one after the other (FastCollector over a host test env).
+    python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --task device-linear --test-episodes 4
 """
 import argparse
 import os
@@ -122,6 +128,50 @@ def make_group_collector(a, group_of, cols):
     return g, GroupCollector(g, cols)
 
 
+class Evaluator:
+    """--test-episodes N: the seeds' test envs and collectors.  Device tasks: a second device env per seed on its engine, store-less
+    DeviceCollectors, ONE grouped launch sequence for every seed's evaluation; host tasks: a FastCollector per seed, in turn."""
+
+    def __init__(self, a, agents):
+        from fsrl_amd.data import DeviceCollector, FastCollector, GroupDeviceCollector
+        self.a, self.agents, self.envs, self.group = a, agents, [], None
+        test_num = min(a.envs, max(1, min(a.test_episodes, 2)))
+        for seed, ag in enumerate(agents):
+            if a.task == "device-point-circle":
+                self.envs.append(DevicePointCircle(ag.policy, test_num, max_episode_steps=300, seed=seed + 1000))
+            elif a.task == "device-linear":
+                like = SyntheticSafetyVectorEnv(env_num=test_num, obs_dim=8, act_dim=2, episode_len=300, seed=seed + 1000)
+                self.envs.append(DeviceLinear(ag.policy, like=like, seed=seed + 1000))
+            else:
+                self.envs.append(SyntheticSafetyVectorEnv(env_num=test_num, obs_dim=8, act_dim=2, episode_len=300, seed=seed + 1000))
+        if a.task.startswith("device-"):
+            self.cols = [DeviceCollector(ag.policy, env) for ag, env in zip(agents, self.envs)]
+            self.group = GroupDeviceCollector(self.cols)
+        else:
+            self.cols = [FastCollector(ag.policy, env) for ag, env in zip(agents, self.envs)]
+
+    def run(self, epoch):
+        for ag in self.agents:
+            ag.policy.eval()
+        for col in self.cols:
+            col.reset_env()
+        n = self.a.test_episodes
+        stats = self.group.collect(n_episode=n) if self.group is not None else [col.collect(n_episode=n) for col in self.cols]
+        for seed, (ag, st) in enumerate(zip(self.agents, stats)):
+            ag.policy.train()
+            ag.logger.store(**{"test/reward": st["rew"], "test/cost": st["cost"], "test/length": int(st["len"])})
+            print(f"epoch {epoch} seed {seed}: test reward {st['rew']:.2f} cost {st['cost']:.2f} length {st['len']:.1f} ({st['n/ep']} episodes)")
+
+    def close(self):
+        for env in self.envs:
+            if hasattr(env, "close"):
+                env.close()
+
+
+def make_evaluator(a, agents):
+    return Evaluator(a, agents) if a.test_episodes > 0 else None
+
+
 # --sweep: PPOLagAgent keywords (float; `none` where the agent takes None) and the two update arguments (int)
 SWEEP_AGENT_KEYS = ("eps_clip", "dual_clip", "vf_coef", "max_grad_norm", "target_kl", "lr", "gae_lambda", "gamma", "cost_limit")
 SWEEP_UPDATE_KEYS = ("batch_size", "repeat_per_collect")
@@ -169,6 +219,7 @@ def run_grouped_trust(a):
         cols.append(make_collector(a, agent, env, buf))
     cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
     group = TrustPolicyGroup([ag.policy for ag in agents], collect_group=cgroup)
+    evaluator = make_evaluator(a, agents)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -186,9 +237,13 @@ def run_grouped_trust(a):
             print(f"epoch {ep + 1} seed {seed}: reward {ag.logger.get_mean('train/reward'):.2f} "
                   f"cost {ag.logger.get_mean('train/cost'):.2f}")
             ag.logger.write(steps, display=False)
+        if evaluator is not None:
+            evaluator.run(ep + 1)
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
+    if evaluator is not None:
+        evaluator.close()                # device test envs go before their engines too
     group.close()
     if cgroup is not None:
         cgroup.close()
@@ -218,6 +273,7 @@ def run_grouped_replay(a):
         cols.append(make_collector(a, agent, env, buf))
     group = {"sacl": SACPolicyGroup, "ddpgl": DDPGPolicyGroup, "cvpo": CVPOPolicyGroup}[a.algo]([ag.policy for ag in agents])
     cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
+    evaluator = make_evaluator(a, agents)
     update_per_step, t0, steps, updates = 0.2, time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -238,9 +294,13 @@ def run_grouped_replay(a):
             print(f"epoch {ep + 1} seed {seed}: reward {ag.logger.get_mean('train/reward'):.2f} "
                   f"cost {ag.logger.get_mean('train/cost'):.2f}")
             ag.logger.write(steps, display=False)
+        if evaluator is not None:
+            evaluator.run(ep + 1)
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
+    if evaluator is not None:
+        evaluator.close()                # device test envs go before their engines too
     if cgroup is not None:
         cgroup.close()
     group.close()
@@ -272,6 +332,7 @@ def run_grouped(a):
     batch_size, repeat = a.sweep.get("batch_size", 256), a.sweep.get("repeat_per_collect", 4)       # ints, or one int per member
     mult = (lambda p: f"nu {float(p._nu):.3f}") if a.algo == "focops" else (lambda p: f"lambda {p.lag_optims[0].get_lag():.3f}")
     _, gcol = make_group_collector(a, lambda: group, cols)
+    evaluator = make_evaluator(a, agents)
     t0, steps, updates = time.time(), 0, 0
     for ep in range(a.epoch):
         budget = 6000
@@ -289,9 +350,13 @@ def run_grouped(a):
             print(f"epoch {ep + 1} seed {seed}: reward {ag.logger.get_mean('train/reward'):.2f} "
                   f"cost {ag.logger.get_mean('train/cost'):.2f} {mult(ag.policy)}")
             ag.logger.write(steps, display=False)
+        if evaluator is not None:
+            evaluator.run(ep + 1)
     dt = time.time() - t0
     print(f"{a.seeds} seeds x {a.epoch} epochs grouped on {a.device}: {steps / dt:.0f} env-steps/s, {updates / dt:.1f} updates/s "
           f"aggregate in {dt:.1f} s")
+    if evaluator is not None:
+        evaluator.close()                # device test envs go before their engines too
     group.close()
     for col in cols:
         col.env.close()              # a device env goes before the engine it lives on
@@ -329,6 +394,9 @@ def parse_args(argv=None):
     ap.add_argument("--workers", type=int, default=0, help="worker processes per seed's env (one ShmemVectorEnv per seed); 0: in-process envs. "
                                                            "--grouped then collects with one library call per collect for all seeds")
     ap.add_argument("--busy-us", type=float, default=0.0, help="--workers: host time of one env step in microseconds (a simulator's stand-in)")
+    ap.add_argument("--test-episodes", type=int, default=0,
+                    help="--grouped: evaluate every seed for this many episodes after each epoch (0: off); over device tasks all seeds' "
+                         "evaluations run in one grouped store-less launch sequence (fsrl_evaluate_device_group)")
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
                     help="--grouped --algo ppol: member i runs with value i (one per seed) of a PPOLagAgent keyword ("
                          + ", ".join(SWEEP_AGENT_KEYS) + ") or of " + " / ".join(SWEEP_UPDATE_KEYS) + "; repeatable")
@@ -354,6 +422,8 @@ def parse_args(argv=None):
     clip = a.sweep.get("max_grad_norm")
     if clip and len({bool(v) for v in clip}) > 1:
         ap.error("--sweep max_grad_norm: the members must agree on whether the clip is on (all values > 0, or all none / 0)")
+    if a.test_episodes < 0 or (a.test_episodes and not a.grouped):
+        ap.error("--test-episodes: >= 0, with --grouped (a seed of its own evaluates through the agents' learn(test_envs))")
     if a.task != "linear" and not a.grouped:
         ap.error("--task device-*: the grouped device collect of this example (--grouped); one seed's device env: the agents' learn()")
     if a.task != "linear" and a.workers:

@@ -5,6 +5,7 @@ from abc import ABC, abstractmethod
 from typing import Optional, Tuple
 
 from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
+from fsrl_amd.data.device_collector import evaluation_collector
 from fsrl_amd.trainer import OnpolicyTrainer
 from fsrl_amd.utils.logger import BaseLogger, DummyLogger
 
@@ -27,7 +28,8 @@ class BaseAgent(ABC):
         if state_dict is not None:
             self.policy.load_state_dict(state_dict)
         self.policy.train() if train_mode else self.policy.eval()
-        result = FastCollector(self.policy, test_envs).collect(n_episode=eval_episodes, render=render)
+        # device envs of this policy's engine: the whole evaluation on the GPU, nothing stored (fsrl_evaluate_device)
+        result = evaluation_collector(self.policy, test_envs, render=render).collect(n_episode=eval_episodes, render=render)
         return result["rew"], result["len"], result["cost"]
 
     @property
@@ -71,7 +73,7 @@ class OnpolicyAgent(BaseAgent):
         else:
             train_collector = FastCollector(self.policy, train_envs, buffer, exploration_noise=True, device_actor=device_actor,
                                             split_phase="auto" if device_actor else False)
-        test_collector = FastCollector(self.policy, test_envs) if test_envs is not None else None
+        test_collector = evaluation_collector(self.policy, test_envs)       # device test envs: store-less DeviceCollector
 
         def stop_fn(reward, cost):
             return reward > reward_threshold and cost < self.cost_limit

@@ -8,6 +8,7 @@ import torch
 from fsrl_amd.agent._nets import adam, offpolicy_nets
 from fsrl_amd.agent.base_agent import BaseAgent
 from fsrl_amd.data import FastCollector, HipPrioritizedVectorReplayBuffer, HipVectorReplayBuffer
+from fsrl_amd.data.device_collector import evaluation_collector
 from fsrl_amd.policy.sac_lag import SACLagrangian
 from fsrl_amd.trainer.offpolicy import OffpolicyTrainer
 from fsrl_amd.utils.exp_util import seed_all
@@ -64,7 +65,7 @@ class OffpolicyAgent(BaseAgent):
         else:
             train_collector = FastCollector(self.policy, train_envs, buffer, exploration_noise=True, device_actor=device_actor,
                                             split_phase="auto" if device_actor else False)
-        test_collector = FastCollector(self.policy, test_envs) if test_envs is not None else None
+        test_collector = evaluation_collector(self.policy, test_envs)       # device test envs: store-less DeviceCollector
 
         def stop_fn(reward, cost):
             return reward > reward_threshold and cost < self.cost_limit

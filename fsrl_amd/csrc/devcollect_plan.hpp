@@ -112,3 +112,19 @@ static inline bool dc_replay_row(BOOK& eb, int64_t sub_size, uint8_t* h_flags, c
     eb.ep_rew = 0.0; eb.ep_len = 0; eb.ep_idx = eb.index;
     return true;
 }
+
+// ---- the replay of an evaluation (fsrl_evaluate_device): nothing was stored, so no book moves.  The episode's return and length run
+// in accumulators that belong to the evaluated env, one per env, zeroed when an evaluation starts; one log row moves them as
+// dc_replay_row moves a book's ep_rew / ep_len, in the same order of additions, and reports an ended episode the same way.
+struct DcEvalAcc {
+    double ep_rew;
+    int32_t ep_len;
+};
+static inline bool dc_eval_row(DcEvalAcc& acc, const DcLogRow& r, double* ep_rew, int32_t* ep_len) {
+    acc.ep_rew += r.rew;
+    acc.ep_len += 1;
+    if (r.flags == 0) return false;
+    *ep_rew = acc.ep_rew; *ep_len = acc.ep_len;
+    acc.ep_rew = 0.0; acc.ep_len = 0;
+    return true;
+}

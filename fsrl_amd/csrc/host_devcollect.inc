@@ -11,6 +11,9 @@
 // leaves (host_per.inc per_devcollect).
 // Grouped seeds: fsrl_collect_device_group (host_devcollect_group.inc) runs k members' collects as the k workgroups of one launch,
 // with this file's checks, entry and replay per member (devcollect_check, devcollect_begin, devcollect_replay).
+// Evaluations: fsrl_evaluate_device / _group (host_devcollect_group.inc) run the store-less form of the kernel through the same
+// checks and entry with `store = false` -- whatever concerns the store is skipped, nothing of the context but its resident actor
+// is touched -- and replay the log through the env's own accumulators (deveval_replay).
 #include "kernels_devcollect.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head);      // defined with the SAC / CVPO code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -33,6 +36,7 @@ struct fsrl_devenv {
     hipEvent_t g_ready = nullptr;       // this member's compute stream as the grouped collect found it
     hipEvent_t g_done = nullptr;        // member 0's env: behind the grouped launch
     DevCollectGroupTable* d_tab = nullptr; DevCollectGroupTable* h_tab = nullptr;      // member 0's env: the member table, device / pinned
+    DcEvalAcc acc[DC_MAX_ENVS] = {};    // fsrl_evaluate_device: the running episode of every env, from the log alone
 };
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
 static DevEnvParams devenv_params(const fsrl_devenv* v) {
@@ -249,43 +253,48 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
 
 // ---- the collect.  Everything that can refuse the call is checked before anything is touched.  solo: fsrl_collect_device, which
 // refuses grouped contexts; fsrl_collect_device_group (host_devcollect_group.inc) runs the same checks on every member without that clause.
+// store = false (an evaluation, grouped or not): nothing is stored, so a tap, a group and the store's geometry are no reasons.
 static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
-                            const float* act_high, int32_t max_steps, bool solo = true) {
+                            const float* act_high, int32_t max_steps, bool solo = true, bool store = true) {
+    const char* const what = store ? "collects" : "evaluations";
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
-    CHECK_ARG(!c->lay, "device collects are not supported on layered contexts yet");
-    if (solo)
+    CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
+    if (solo && store)
         CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
         const float* P; const ModelDesc* md;
         CHECK_ARG(sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md),
-                  "device collects on replay contexts (SAC-Lag, DDPG-Lag, CVPO) need fsrl_sac_init / fsrl_cvpo_init first");
+                  "device %s on replay contexts (SAC-Lag, DDPG-Lag, CVPO) need fsrl_sac_init / fsrl_cvpo_init first", what);
         CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
     }
-    CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
-    if (c->in_update) return fail(FSRL_ESTATE, "%s inside an update", solo ? "fsrl_collect_device" : "fsrl_collect_device_group");
+    if (store) CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
+    if (c->in_update)
+        return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device", solo ? "" : "_group");
     CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
-    CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
+    if (store) CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
               v->cfg.obs_dim, v->cfg.act_dim);
     CHECK_ARG(n_episode >= 1, "n_episode must be >= 1");
     CHECK_ARG(bound_method >= 0 && bound_method <= 2, "bound_method: 0 none, 1 clip, 2 tanh");
     CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
     CHECK_ARG(max_steps <= DC_MAX_STEPS, "max_steps_per_launch %d above %d", max_steps, DC_MAX_STEPS);
-    CHECK_ARG(c->sub_size >= 1 && c->maxsize <= INT_MAX, "the store's geometry does not fit a device collect");
+    if (store) CHECK_ARG(c->sub_size >= 1 && c->maxsize <= INT_MAX, "the store's geometry does not fit a device collect");
     return 0;
 }
 
 // What a collect does on entry, for one context: its resident actor ends (and through the release hooks its group's), the env's own
 // stream is waited for, the staging window lands, the log holds max_steps vector steps, and the initial DcState and the kernel's
 // arguments go up on the context's compute stream.  *P / *md / *head: whose actor the kernel runs.
+// store = false: the staging window stays as it is, the write indices, the store's pointers and the slot array are not arguments,
+// a sample drawn ahead stays valid (no row is overwritten), and the env's episode accumulators start at zero.
 struct DcActor { const float* P; const ModelDesc* md; int head; };
 static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                            const float* act_low, const float* act_high, int max_steps, DcActor* actor) {
+                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store = true) {
     const int n = v->cfg.env_num, Da = v->cfg.act_dim;
     ENTER_DEV(c);                                   // a live resident actor ends first
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
-    int rc = join_store(c);                         // rows in the staging window land first; the side stream is in front of the kernel
+    int rc = store ? join_store(c) : 0;             // rows in the staging window land first; the side stream is in front of the kernel
     if (rc) return rc;
     if (v->log_steps < max_steps) {
         const size_t rows = (size_t)max_steps * n;
@@ -296,7 +305,8 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     memset(&hs, 0, sizeof(hs));
     hs.n_live = dc_first_live(n, n_episode); hs.n_episode = n_episode;
     for (int e = 0; e < DC_MAX_ENVS; ++e) hs.live[e] = e < n ? e : 0;
-    for (int e = 0; e < n; ++e) hs.index[e] = (int32_t)c->env[(size_t)e].index;
+    for (int e = 0; e < n && store; ++e) hs.index[e] = (int32_t)c->env[(size_t)e].index;
+    if (!store) for (int e = 0; e < DC_MAX_ENVS; ++e) v->acc[e] = DcEvalAcc{0.0, 0};
     hipStream_t s = c->compute;
     HIPCHK(hipMemcpyAsync(v->d_state, &hs, sizeof(DcState), hipMemcpyHostToDevice, s));
     // the arguments travel through device memory: ~350 bytes of kernel arguments held in scalar registers next to tile_forward's own
@@ -304,7 +314,8 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     DevCollectArgs& a = *v->h_args;
     a = DevCollectArgs{};
     a.ep = devenv_params(v); a.ea = v->ea; a.k0 = (uint32_t)v->key; a.k1 = (uint32_t)(v->key >> 32);
-    a.st = c->st; a.sub_size = c->sub_size; a.state = v->d_state; a.log = v->d_log; a.max_steps = max_steps;
+    if (store) { a.st = c->st; a.sub_size = c->sub_size; }
+    a.state = v->d_state; a.log = v->d_log; a.max_steps = max_steps;
     a.deterministic = deterministic ? 1 : 0; a.bound_method = bound_method; a.scaled = act_low ? 1 : 0;
     for (int d = 0; d < Da && act_low; ++d) { a.low[d] = act_low[d]; a.high[d] = act_high[d]; }
     a.max_action = c->cfg.max_action;
@@ -314,9 +325,9 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     if (ctx_is_replay(c)) {
         if (!sac_actor_resident_args(c, &actor->P, &actor->md) || !sac_devcollect_head(c, &a, &actor->head))
             return fail(FSRL_ESTATE, "no fused actor network");
-        rc = sac_devcollect_enter(c);
+        rc = store ? sac_devcollect_enter(c) : 0;
         if (rc) return rc;
-        a.slots = c->per ? v->d_slot : nullptr;
+        a.slots = store && c->per ? v->d_slot : nullptr;
     }
     HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));
     return 0;
@@ -345,6 +356,25 @@ static int devcollect_replay(fsrl_ctx* c, fsrl_devenv* v, const DcState& hs, int
     }
     t.rows += hs.log_rows;
     c->store_version += (uint64_t)hs.steps;          // one bump per pushed vector step
+    return 0;
+}
+
+// ... and an evaluation's log through the env's own accumulators: the same totals and episodes, in the same order, and no book
+static int deveval_replay(fsrl_devenv* v, const DcState& hs, int32_t n_episode, DcTotals& t, double* ep_rew_out, int32_t* ep_len_out) {
+    const int n = v->cfg.env_num;
+    for (int i = 0; i < hs.log_rows; ++i) {
+        const DcLogRow& r = v->h_log[i];
+        if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device evaluation: log row %d names env %d", i, r.env);
+        double er = 0.0; int32_t el = 0;
+        const bool done = dc_eval_row(v->acc[r.env], r, &er, &el);
+        t.total_cost += r.cost;
+        t.terms += (int32_t)(r.flags & 1u); t.truncs += (int32_t)((r.flags >> 1) & 1u);
+        if (done) {
+            if (t.episodes < n_episode) { ep_rew_out[t.episodes] = er; ep_len_out[t.episodes] = el; }
+            ++t.episodes;
+        }
+    }
+    t.rows += hs.log_rows;
     return 0;
 }
 

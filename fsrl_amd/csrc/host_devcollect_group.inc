@@ -14,6 +14,9 @@
 // Prioritised members: per_devcollect on the member's OWN compute stream behind an event recorded after the group launch, waited
 // for before the next launch overwrites the slots; it re-records upd_done as on the solo path.
 // The member table and the events are made by an env's first grouped collect and kept (fsrl_devenv).
+// Evaluations.  fsrl_evaluate_device_group is the same call with `store = false`: evaluate_device_group_kernel in the launch, no
+// tree launches, deveval_replay for the logs; fsrl_evaluate_device is its one-member case (the table-driven launch at k = 1), so
+// there is one store-less kernel family.  The members' stores, books, samplers and random streams are not touched.
 static int devcollect_group_ensure(fsrl_devenv* v, bool first) {
     if (!v->g_ready) HIPCHK(hipEventCreateWithFlags(&v->g_ready, hipEventDisableTiming));
     if (!first) return 0;
@@ -62,14 +65,16 @@ struct DcGroupOut {
 };
 // everything behind the checks; the caller waits for the launch stream when this fails half-way
 static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, const int32_t* n_episode, int32_t deterministic,
-                                int32_t bound_method, const float* act_low, const float* act_high, int max_steps, const DcGroupOut& o) {
+                                int32_t bound_method, const float* act_low, const float* act_high, int max_steps, const DcGroupOut& o,
+                                bool store) {
+    const char* const what = store ? "grouped device collect" : "device evaluation";
     fsrl_devenv* v0 = envs[0];
     const int Da = v0->cfg.act_dim;
     DcActor actor0{};
     for (int i = 0; i < k; ++i) {
         DcActor actor{};
         const int rc = devcollect_begin(ctxs[i], envs[i], n_episode[i], deterministic, bound_method, act_low ? act_low + (size_t)i * Da : nullptr,
-                                        act_high ? act_high + (size_t)i * Da : nullptr, max_steps, &actor);
+                                        act_high ? act_high + (size_t)i * Da : nullptr, max_steps, &actor, store);
         if (rc) return rc;
         if (i == 0) actor0 = actor;
         if (actor.head != actor0.head) return fail(FSRL_ESTATE, "member %d: its actor's head kind changed under the call", i);
@@ -98,13 +103,17 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
     const int64_t launch_cap = dc_group_launch_cap(n_episode, mes, k, max_steps);
     int32_t launches = 0;
     for (;;) {
-        if (launches >= launch_cap) return fail(FSRL_ESTATE, "grouped device collect: %d launches did not finish every member", launches);
+        if (launches >= launch_cap) return fail(FSRL_ESTATE, "%s: %d launches did not finish every member", what, launches);
         int rc = dispatch_H(ctxs[0]->cfg.hidden, [&](auto hc) {
             constexpr int H = decltype(hc)::value;
             devenv_dispatch(v0->cfg.kind, [&](auto env) {
                 using Env = decltype(env);
                 const DevCollectGroupTable* tab = v0->d_tab;
-                if (head == DC_HEAD_GAUSS) hipLaunchKernelGGL((collect_device_group_kernel<H, Env, DC_HEAD_GAUSS>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
+                if (!store) {
+                    if (head == DC_HEAD_GAUSS) hipLaunchKernelGGL((evaluate_device_group_kernel<H, Env, DC_HEAD_GAUSS>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
+                    else if (head == DC_HEAD_DDPG) hipLaunchKernelGGL((evaluate_device_group_kernel<H, Env, DC_HEAD_DDPG>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
+                    else hipLaunchKernelGGL((evaluate_device_group_kernel<H, Env>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
+                } else if (head == DC_HEAD_GAUSS) hipLaunchKernelGGL((collect_device_group_kernel<H, Env, DC_HEAD_GAUSS>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
                 else if (head == DC_HEAD_DDPG) hipLaunchKernelGGL((collect_device_group_kernel<H, Env, DC_HEAD_DDPG>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
                 else hipLaunchKernelGGL((collect_device_group_kernel<H, Env>), dim3(k), dim3(4 * H), 0, s, mdv, tab);
             });
@@ -132,9 +141,9 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         for (int i = 0; i < k; ++i) {
             const DcState& hs = *envs[i]->h_state;
             if (!devcollect_state_sane(hs, max_steps, envs[i]->cfg.env_num))
-                return fail(FSRL_ESTATE, "grouped device collect: member %d's workgroup reported %d rows in %d steps", i, hs.log_rows, hs.steps);
+                return fail(FSRL_ESTATE, "%s: member %d's workgroup reported %d rows in %d steps", what, i, hs.log_rows, hs.steps);
             if (finished[i] && (hs.steps != 0 || hs.log_rows != 0))
-                return fail(FSRL_ESTATE, "grouped device collect: member %d was finished and its workgroup reported %d rows in %d steps", i,
+                return fail(FSRL_ESTATE, "%s: member %d was finished and its workgroup reported %d rows in %d steps", what, i,
                             hs.log_rows, hs.steps);
             if (hs.log_rows > 0) {
                 HIPCHK(hipMemcpyAsync(envs[i]->h_log, envs[i]->d_log, (size_t)hs.log_rows * sizeof(DcLogRow), hipMemcpyDeviceToHost, s));
@@ -144,17 +153,18 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         if (any_rows) HIPCHK(hipStreamSynchronize(s));
         for (int i = 0; i < k; ++i) {
             const DcState& hs = *envs[i]->h_state;
-            rc = devcollect_replay(ctxs[i], envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i]);
+            rc = store ? devcollect_replay(ctxs[i], envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i])
+                       : deveval_replay(envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i]);
             if (rc) { g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
             was_finished[i] = finished[i]; steps[i] = hs.steps; finished[i] = hs.finished ? 1 : 0;
         }
         if (dc_group_complete(finished, k)) break;
         const int stalled = dc_group_stalled(was_finished, steps, k);
-        if (stalled >= 0) return fail(FSRL_ESTATE, "grouped device collect: a launch made no step for member %d", stalled);
+        if (stalled >= 0) return fail(FSRL_ESTATE, "%s: a launch made no step for member %d", what, stalled);
     }
     for (int i = 0; i < k; ++i)
         if (t[i].episodes != envs[i]->h_state->episodes)
-            return fail(FSRL_ESTATE, "grouped device collect: member %d's log holds %d episodes, the kernel counted %d", i, t[i].episodes,
+            return fail(FSRL_ESTATE, "%s: member %d's log holds %d episodes, the kernel counted %d", what, i, t[i].episodes,
                         envs[i]->h_state->episodes);
     // FastCollector.reset_env at the end of every collect: ALL envs of ALL members, then one wait
     for (int i = 0; i < k; ++i) {
@@ -172,13 +182,13 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
     return 0;
 }
 
-extern "C" int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
-                                         int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
-                                         int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
-                                         double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
-    CHECK_ARG(k >= 1 && k <= FSRL_MAX_GROUP, "k %d: a grouped device collect has 1..%d members", k, FSRL_MAX_GROUP);
+// the grouped call, storing or not.  named: the refusals of a member say which (the solo evaluation has one and does not)
+static int devcollect_group_call(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                 int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                 const DcGroupOut& o, bool store, bool named) {
+    CHECK_ARG(k >= 1 && k <= FSRL_MAX_GROUP, "k %d: a grouped device %s has 1..%d members", k, store ? "collect" : "evaluation", FSRL_MAX_GROUP);
     CHECK_ARG(ctxs && envs && n_episode, "null argument");
-    CHECK_ARG(steps_out && total_cost_out && term_count_out && trunc_count_out && ep_rew_out && ep_len_out && episodes_out, "null output");
+    CHECK_ARG(o.steps && o.total_cost && o.terms && o.truncs && o.ep_rew && o.ep_len && o.episodes, "null output");
     CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
     // ---- every refusal before anything is touched
     for (int i = 0; i < k; ++i) {
@@ -191,8 +201,8 @@ extern "C" int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, in
     const int Da0 = ctxs[0]->cfg.act_dim;
     for (int i = 0; i < k; ++i) {
         const int rc = devcollect_check(ctxs[i], envs[i], n_episode[i], bound_method, act_low ? act_low + (size_t)i * Da0 : nullptr,
-                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, false);
-        if (rc) { g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
+                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, !named, store);
+        if (rc) { if (named) g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
     }
     for (int i = 1; i < k; ++i) {
         const int rc = devcollect_group_agree(ctxs[i], envs[i], ctxs[0], envs[0], i);
@@ -203,12 +213,36 @@ extern "C" int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, in
     for (int i = 0; i < k; ++i) pactor_release(ctxs[i]);       // the table's first allocation would wait for a live resident actor's idle timeout
     int rc = devcollect_group_ensure(envs[0], true);
     if (rc) return rc;
-    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
-    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o);
+    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o, store);
     if (rc) {       // leave nothing of the call in flight: the kernel reads every member's env arrays from member 0's stream
         const std::string why = g_err;
         (void)hipStreamSynchronize(ctxs[0]->compute);
         g_err = why;
     }
     return rc;
+}
+
+extern "C" int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                         int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                         int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                         double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    return devcollect_group_call(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, true, true);
+}
+
+extern "C" int fsrl_evaluate_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                          int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                          int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                          double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    return devcollect_group_call(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, false, true);
+}
+
+extern "C" int fsrl_evaluate_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                    const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                    double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                    int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    CHECK_ARG(c && v, "null context / env");
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    return devcollect_group_call(&c, &v, 1, &n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, false, false);
 }

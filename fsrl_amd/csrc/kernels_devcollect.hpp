@@ -63,7 +63,9 @@ struct DevCollectSmem {
 
 // The collect of ONE workgroup: the whole loop above over (P, md, ap).  collect_device_kernel runs it on its own arguments,
 // collect_device_group_kernel on its member's row of the table; nothing in it knows which.
-template <int H, class Env, int HEAD>
+// STORE = false is the evaluation (fsrl_evaluate_device): the same loop with nothing stored -- no slot, no write index, no phase 3 and
+// its barrier; phases 1, 4 and 5 and the log are the code above, so an evaluated step is a collected step.
+template <int H, class Env, int HEAD, bool STORE = true>
 __device__ __forceinline__ void collect_device_body(const float* __restrict__ P, const ModelDesc& md, const DevCollectArgs* __restrict__ ap,
                                                     TileSmem<H>& sm, DevCollectSmem& sh) {
     const DevCollectArgs& a = *ap;
@@ -78,7 +80,10 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
     FwdW2Frag<H> wf;
     wf.load(P + no.W2f, tid >> 6, tid & 63);
     stg.commit(sm, no, Do, tid);
-    if (tid < DC_MAX_ENVS) { sh.live[tid] = a.state->live[tid]; sh.index[tid] = a.state->index[tid]; }
+    if (tid < DC_MAX_ENVS) {
+        sh.live[tid] = a.state->live[tid];
+        if constexpr (STORE) sh.index[tid] = a.state->index[tid];
+    }
     if (tid == 0) { sh.n_live = a.state->n_live; sh.episodes = a.state->episodes; sh.finished = a.state->finished; }
     const int n_episode = a.state->n_episode;
     const int per = 2 * Do + Da;
@@ -146,26 +151,31 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
                       a.ea.nxt + (size_t)e * Do, rew, cost, term);
             a.ea.t[e] = t + 1;
             const uint32_t fl = dc_flags(term, dc_truncated(t + 1, a.ep.max_steps));
-            const int64_t slot = dc_slot(e, a.sub_size, sh.index[e]);
-            sh.index[e] = dc_next_index(sh.index[e], a.sub_size);
-            sh.slot[lt] = (int32_t)slot;
+            [[maybe_unused]] int64_t slot = 0;
+            if constexpr (STORE) {
+                slot = dc_slot(e, a.sub_size, sh.index[e]);
+                sh.index[e] = dc_next_index(sh.index[e], a.sub_size);
+                sh.slot[lt] = (int32_t)slot;
+            }
             sh.done[lt] = fl != 0u;
-            a.st.rew[slot] = rew; a.st.cost[slot] = cost; a.st.flags[slot] = (uint8_t)fl;
+            if constexpr (STORE) { a.st.rew[slot] = rew; a.st.cost[slot] = cost; a.st.flags[slot] = (uint8_t)fl; }
             DcLogRow lr;
             lr.env = e; lr.flags = fl; lr.rew = rew; lr.cost = cost;
             a.log[log_rows + lt] = lr;
-            if constexpr (HEAD != DC_HEAD_ONPOLICY) { if (a.slots) a.slots[log_rows + lt] = (int32_t)slot; }
+            if constexpr (STORE && HEAD != DC_HEAD_ONPOLICY) { if (a.slots) a.slots[log_rows + lt] = (int32_t)slot; }
         }
         __syncthreads();
-        // ---- 3. the rows' vectors into the store
-        for (int x = lt; x < n_live * per; x += NT) {
-            const int p = div_by_magic((unsigned)x, a.magic_per), f = x - p * per, e = sh.live[p];
-            const size_t slot = (size_t)sh.slot[p];
-            if (f < Do) a.st.obs[slot * Do + f] = a.ea.obs[(size_t)e * Do + f];
-            else if (f < 2 * Do) a.st.obs_next[slot * Do + (f - Do)] = a.ea.nxt[(size_t)e * Do + (f - Do)];
-            else a.st.act[slot * Da + (f - 2 * Do)] = sh.act[p * FSRL_MAX_ACT + (f - 2 * Do)];
+        if constexpr (STORE) {
+            // ---- 3. the rows' vectors into the store
+            for (int x = lt; x < n_live * per; x += NT) {
+                const int p = div_by_magic((unsigned)x, a.magic_per), f = x - p * per, e = sh.live[p];
+                const size_t slot = (size_t)sh.slot[p];
+                if (f < Do) a.st.obs[slot * Do + f] = a.ea.obs[(size_t)e * Do + f];
+                else if (f < 2 * Do) a.st.obs_next[slot * Do + (f - Do)] = a.ea.nxt[(size_t)e * Do + (f - Do)];
+                else a.st.act[slot * Da + (f - 2 * Do)] = sh.act[p * FSRL_MAX_ACT + (f - 2 * Do)];
+            }
+            __syncthreads();
         }
-        __syncthreads();
         // ---- 4. the next observation: a reset where the episode ended
         if (lt < n_live) {
             const int e = sh.live[lt];
@@ -191,7 +201,10 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
     __syncthreads();
     int te = threadIdx.x;
     asm volatile("" : "+v"(te));
-    if (te < DC_MAX_ENVS) { a.state->live[te] = sh.live[te]; a.state->index[te] = sh.index[te]; }
+    if (te < DC_MAX_ENVS) {
+        a.state->live[te] = sh.live[te];
+        if constexpr (STORE) a.state->index[te] = sh.index[te];
+    }
     if (te == 0) {
         a.state->n_live = sh.n_live; a.state->episodes = sh.episodes; a.state->finished = sh.finished;
         a.state->steps = step; a.state->log_rows = log_rows;
@@ -236,4 +249,17 @@ __global__ __launch_bounds__(4 * H) void collect_device_group_kernel(const Model
     __shared__ TileSmem<H> sm;
     __shared__ DevCollectSmem sh;
     collect_device_body<H, Env, HEAD>(P, md, ap, sm, sh);
+}
+
+// ---- k evaluations in one launch (fsrl_evaluate_device_group; fsrl_evaluate_device is its one-member case): the table-driven launch
+// above over the store-less loop.  The members' stores, write indices and slot arrays are not arguments of this form: a.st, a.sub_size
+// and a.slots are never read.
+template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
+__global__ __launch_bounds__(4 * H) void evaluate_device_group_kernel(const ModelDesc md, const DevCollectGroupTable* __restrict__ tab) {
+    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const float* P = dc_uniform_ptr<1>(tab->P[b]);
+    const DevCollectArgs* ap = dc_uniform_ptr<4>(tab->a[b]);
+    __shared__ TileSmem<H> sm;
+    __shared__ DevCollectSmem sh;
+    collect_device_body<H, Env, HEAD, false>(P, md, ap, sm, sh);
 }

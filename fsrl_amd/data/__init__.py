@@ -7,7 +7,9 @@ install(__name__, globals(), {
     "HipPrioritizedVectorReplayBuffer": "buffer",
     "FastCollector": "fast_collector",
     "DeviceCollector": "device_collector",
+    "DeviceEvalCollector": "device_collector",
     "GroupDeviceCollector": "device_collector",
+    "evaluation_collector": "device_collector",
     "GroupCollector": "group_collector",
     "BasicCollector": "basic_collector",
     "TrajectoryBuffer": "traj_buf",

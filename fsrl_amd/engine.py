@@ -447,10 +447,21 @@ class Engine:
         -> dict(steps, total_cost, terminated, truncated, ep_rews, ep_lens, launches)"""
         lo = np.ascontiguousarray(low, np.float32) if low is not None else None
         hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_collect_device, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
+
+    def evaluate_device(self, h, n_episode, deterministic=True, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.collect_device that stores nothing (fsrl_evaluate_device): FastCollector(policy, test_envs) with no buffer.  The
+        same loop on the env `h`, the same result dict; the store, its books, the sampler and every random stream of the engine stay
+        as they are.  Works with a trajectory archive attached, on a member of a group and with more envs than sub-buffers."""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_evaluate_device, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
+
+    def _collect_device(self, fn, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch):
         steps, cost = C.c_int64(), C.c_double()
         nt, ntr, nep, nl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         ep_rew, ep_len = np.zeros(max(int(n_episode), 1), np.float64), np.zeros(max(int(n_episode), 1), np.int32)
-        _lib.check(self.lib.fsrl_collect_device(
+        _lib.check(fn(
             self._ctx, h, int(n_episode), int(bool(deterministic)), int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p),
             int(max_steps_per_launch), C.byref(steps), C.byref(cost), C.byref(nt), C.byref(ntr), _ptr(ep_rew, _f64p),
             _ptr(ep_len, _i32p), C.byref(nep), C.byref(nl)))
@@ -1034,8 +1045,16 @@ class TrajArchive:
         return dict(zip(TRAJ_COUNTERS, (int(v) for v in out)))
 
 
+def evaluate_device_group(engines, env_handles, n_episodes, deterministic=True, bound_method=1, lows=None, highs=None,
+                          max_steps_per_launch=0):
+    """Engine.evaluate_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_evaluate_device_group):
+    member i's result and env state are Engine.evaluate_device's on it, bit for bit; nothing of any member's store moves.
+    Arguments and result as collect_device_group."""
+    return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch, _store=False)
+
+
 def collect_device_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
-                         max_steps_per_launch=0):
+                         max_steps_per_launch=0, _store=True):
     """Engine.collect_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_collect_device_group):
     member i's collect is Engine.collect_device on it, bit for bit.  The engines may be ungrouped or members of any kind of group.
     env_handles: each engine's devenv handle; n_episodes: one count or one per member; lows / highs: None or one row per member.
@@ -1058,7 +1077,7 @@ def collect_device_group(engines, env_handles, n_episodes, deterministic=False, 
     nt, ntr, nep = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
     ep_rew, ep_len = np.zeros(tot, np.float64), np.zeros(tot, np.int32)
     nl = C.c_int32()
-    _lib.check(lib.fsrl_collect_device_group(
+    _lib.check((lib.fsrl_collect_device_group if _store else lib.fsrl_evaluate_device_group)(
         ctxs, envs, k, _ptr(n_ep, _i32p), int(bool(deterministic)), int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p),
         int(max_steps_per_launch), _ptr(steps, _i64p), _ptr(cost, _f64p), _ptr(nt, _i32p), _ptr(ntr, _i32p), _ptr(ep_rew, _f64p),
         _ptr(ep_len, _i32p), _ptr(nep, _i32p), C.byref(nl)))

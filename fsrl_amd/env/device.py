@@ -1,8 +1,11 @@
 """Environments that live on the GPU (include/fsrl_hip.h "Device environments"): the env's dynamics are device functions, its state
 never leaves HBM.  `DeviceVectorEnv` gives such an env the calling convention of `SyntheticSafetyVectorEnv` -- `len(env)`,
 `reset(ids=None) -> (obs, info)`, `step(act, ids) -> (obs, rew, terminated, truncated, {"cost": cost})` -- one small launch per call
-(`fsrl_devenv_reset` / `fsrl_devenv_step`), so every collector of this package and `evaluate()` work over it unchanged.  What it is
-for is `DeviceCollector` (fsrl_amd/data/device_collector.py): a whole `collect(n_episode)` in a handful of launches."""
+(`fsrl_devenv_reset` / `fsrl_devenv_step`), so every collector of this package works over it unchanged.  What it is for is
+`DeviceCollector` (fsrl_amd/data/device_collector.py): a whole `collect(n_episode)` in a handful of launches -- with a buffer the
+training collect (fsrl_collect_device), without one the evaluation that stores nothing (fsrl_evaluate_device), which is what the
+agents' `learn(train_envs, test_envs)` and `evaluate(test_envs)` run over device test envs of their own engine.  Layered engines
+and `render=True` evaluate through `FastCollector` over `step`, call by call."""
 from types import SimpleNamespace
 
 import numpy as np

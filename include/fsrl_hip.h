@@ -1075,6 +1075,31 @@ int fsrl_collect_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, co
                               int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
                               int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
                               double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_evaluate_device / fsrl_evaluate_device_group   the collect that stores nothing: FastCollector(policy, test_envs) with no
+ *                            buffer.  The same loop, actor, action noise (the evaluated env's own Philox stream), env functions and
+ *                            episode rule as fsrl_collect_device / _group, the same arguments and the same outputs -- on twin
+ *                            contexts and twin envs an evaluation and a collect return the same numbers and leave the same env state,
+ *                            bit for bit -- in the store-less form of the kernel: no slot, no write index, no row.  The solo call is
+ *                            the grouped call with k = 1 (one table-driven launch family).  It changes the evaluated env (its state
+ *                            arrays, as a collect does, the reset of ALL envs at the end included; its DcState, log and arguments)
+ *                            and ends a live resident actor; it changes NOTHING else: store rows and flags, the per-env books, the
+ *                            staging window, store_version, the prioritised-replay tree and max_prio, a replay context's
+ *                            pre-drawn sample, every random stream of the library, the return statistics, other envs.  Episode
+ *                            returns and lengths come from the log alone, through accumulators of the env.
+ *                            Accepted where a collect is refused: a context with a trajectory tap (nothing reaches the archive), an
+ *                            env with more envs than the store has sub-buffers (<= 64) and any store geometry, a context that is a
+ *                            member of any kind of group (the solo call too).  Refused as a collect refuses, before anything
+ *                            changes: layered contexts, an env of another context, shapes, bound_method, max_steps_per_launch above
+ *                            4096, n_episode < 1, null outputs, a call inside an update (FSRL_ESTATE), a replay context before
+ *                            fsrl_sac_init / fsrl_cvpo_init; in the grouped call also what members must agree on, the member named.  */
+int fsrl_evaluate_device(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                         const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                         double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                         int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+int fsrl_evaluate_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                               int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                               int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                               double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,18 @@ sampler, enqueued, statistics drained once per collect), device collect against 
 parent commit), the two tools run as processes of their own, alternating; both sets of numbers go to --out.
 
     python tools/bench_device_collect.py --ks 1,2,4,8 --ab-tree ../parent --rounds 3 --out profiles/device_collect_group.json
+
+--eval measures an EVALUATION of env_num episodes instead (the policy in eval mode, as BaseTrainer.test_step and evaluate() run it),
+over a real agent's policy (PPOLagAgent, then SACLagAgent; --algo sacl: the second only), in episodes/s and env-steps/s:
+
+  (a) evaluate   the store-less DeviceCollector(policy, env): fsrl_evaluate_device, nothing stored
+  (b) stepped    FastCollector(policy, env): the host torch actor over DeviceVectorEnv.step, what evaluation over a device env was
+  (c) collect    DeviceCollector(policy, env, buffer): the storing device collect, same mode
+
+and with --ks the grouped evaluation (GroupDeviceCollector over store-less collectors, fsrl_evaluate_device_group) against k solo
+evaluations one after the other, aggregate over the k seeds.
+
+    python tools/bench_device_collect.py --eval --rounds 3 --ks 1,2,4,8 --out profiles/device_eval.json
 """
 import argparse
 import json
@@ -214,6 +226,101 @@ def main_groups(a):
                                                  round(c["lock_step"]["median"])) for c in result["configs"]])))
 
 
+class EvalPol(Pol):
+    training = False
+
+
+def setup_eval(hidden, n, algo):
+    """a real agent (the host path needs its torch actor) and the three collectors of an evaluation, each over a device env of its own"""
+    import tempfile as tf
+    from fsrl_amd.agent import PPOLagAgent, SACLagAgent
+    from fsrl_amd.utils import BaseLogger
+    host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1)
+    Agent = SACLagAgent if algo == "sacl" else PPOLagAgent
+    agent = Agent(host, BaseLogger(tf.mkdtemp(prefix="fsrl_amd_bench_"), name="eval"), cost_limit=10, device="cuda:0", seed=1,
+                  hidden_sizes=(hidden, hidden), training_num=n, buffer_size=n * 2 * EPISODE_LEN)
+    pol = agent.policy
+    pol.eval()
+    envs = [DeviceLinear(pol, like=host, seed=1) for _ in range(3)]
+    buf = HipVectorReplayBuffer(pol.engine, n * 2 * EPISODE_LEN, n)
+    cols = dict(evaluate=DeviceCollector(pol, envs[0]), stepped=FastCollector(pol, envs[1]), collect=DeviceCollector(pol, envs[2], buf))
+    return agent, envs, cols
+
+
+def timed_eval(col, n, calls):
+    col.collect(n_episode=n)
+    rows, eps, t0 = 0, 0, time.perf_counter()
+    for _ in range(calls):
+        st = col.collect(n_episode=n)
+        rows += st["n/st"]; eps += st["n/ep"]
+        col.reset_buffer()
+    return rows, eps, time.perf_counter() - t0
+
+
+def main_eval(a):
+    assert a.algo in ("onpolicy", "sacl"), "--eval: PPOLagAgent and SACLagAgent (the default), or --algo sacl alone"
+    paths = ("evaluate", "stepped", "collect")
+    algos = ("onpolicy", "sacl") if a.algo == "onpolicy" else (a.algo, )
+    result = dict(metric="an evaluation of env_num episodes, policy in eval mode, linear env obs 8 / act 2, episode length 300: episodes/s and "
+                         "env-steps/s", rounds=a.rounds, calls=a.calls, configs=[], groups=[])
+    for algo, hidden, n in ((al, int(h), int(e)) for al in algos for h in a.hidden.split(",") for e in a.envs.split(",")):
+        agent, envs, cols = setup_eval(hidden, n, algo)
+        steps, eps = {p: [] for p in paths}, {p: [] for p in paths}
+        for _ in range(a.rounds):
+            for p in paths:
+                rows, ne, dt = timed_eval(cols[p], n, a.calls)
+                steps[p].append(rows / dt); eps[p].append(ne / dt)
+        cfg = dict(algo=algo, hidden=[hidden, hidden], env_num=n, launches_per_evaluation=cols["evaluate"].last_launches)
+        for p in paths:
+            cfg[p] = dict(env_steps_per_s=summary(steps[p]), episodes_per_s=summary(eps[p]))
+        result["configs"].append(cfg)
+        print(json.dumps(cfg), flush=True)
+        for env in envs:
+            env.close()
+        agent.policy.engine.close()
+    if a.ks and "onpolicy" in algos:
+        from fsrl_amd.data import GroupDeviceCollector
+        for hidden in (int(h) for h in a.hidden.split(",")):
+            for n in (int(e) for e in a.envs.split(",")):
+                for k in (int(x) for x in a.ks.split(",")):
+                    sets = {}
+                    for p in ("grouped", "solo_seq"):
+                        engs, envs, cols = [], [], []
+                        for i in range(k):
+                            eng = Engine(EngineConfig(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN), device=0)
+                            eng.set_params((0.1 * np.random.default_rng(i).standard_normal(eng.n_params)).astype(np.float32))
+                            host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1 + i)
+                            envs.append(DeviceLinear(eng, like=host, seed=1 + i))
+                            cols.append(DeviceCollector(EvalPol(eng), envs[-1]))
+                            engs.append(eng)
+
+                        class Seq:
+                            collectors = cols
+
+                            def collect(self, n_episode, _cols=cols):
+                                return [c.collect(n_episode=n_episode) for c in _cols]
+                        sets[p] = (engs, envs, GroupDeviceCollector(cols) if p == "grouped" else Seq())
+                    rates = {p: [] for p in sets}
+                    for _ in range(a.rounds):
+                        for p in sets:
+                            rows, dt = timed_group(sets[p][2], n, a.calls)
+                            rates[p].append(rows / dt)
+                    cfg = dict(hidden=[hidden, hidden], env_num=n, k=k, grouped=summary(rates["grouped"]), solo_seq=summary(rates["solo_seq"]))
+                    result["groups"].append(cfg)
+                    print(json.dumps(cfg), flush=True)
+                    for engs, envs, _ in sets.values():
+                        for env in envs:
+                            env.close()
+                        for eng in engs:
+                            eng.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    print(json.dumps(dict(device_eval=[(c["algo"], c["hidden"][0], c["env_num"]) + tuple(round(c[p]["env_steps_per_s"]["median"]) for p in paths)
+                                       for c in result["configs"]])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", choices=["onpolicy", "sacl", "ddpgl", "cvpo"], default="onpolicy")
@@ -226,7 +333,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ks", default=None, help="group sizes, e.g. 1,2,4,8: measure grouped seeds (on-policy) instead")
     ap.add_argument("--ab-tree", default=None, help="with --ks: another built checkout whose solo device collect this tree's is held against")
+    ap.add_argument("--eval", action="store_true", help="measure evaluations: the store-less device evaluation, the host-stepped path it "
+                                                        "replaces and a storing collect; with --ks also grouped against solo evaluations")
     a = ap.parse_args()
+    if a.eval:
+        return main_eval(a)
     if a.ks:
         return main_groups(a)
     paths = ("device", "in_process", "stepped")
