@@ -243,9 +243,10 @@ class PPOLagOracle:
         loss = loss_actor + cfg.vf_coef * loss_vf
         return loss, dist, stats
 
-    def learn(self, pb, lagrangians, rescaling, batch_size, repeat, perms=None, data=None):
+    def learn(self, pb, lagrangians, rescaling, batch_size, repeat, perms=None, data=None, grad_norms=None):
         """Minibatch SGD passes.  `perms[k]` = permutation of pass k (None: draw from the
-        numpy global RNG like Batch.split).  Returns (stats [steps, 11] f64, early_stop_pass)."""
+        numpy global RNG like Batch.split).  Returns (stats [steps, 11] f64, early_stop_pass).
+        `grad_norms`: a list that receives every step's pre-clip gradient norm (clip_grad_norm_'s return value)."""
         cfg = self.cfg
         n = len(pb["logp_old"])
         rows = []
@@ -263,7 +264,9 @@ class PPOLagOracle:
                 self.optim.zero_grad()
                 loss.backward()
                 if cfg.max_grad_norm:
-                    torch.nn.utils.clip_grad_norm_(self._leaves, max_norm=cfg.max_grad_norm)
+                    norm = torch.nn.utils.clip_grad_norm_(self._leaves, max_norm=cfg.max_grad_norm)
+                    if grad_norms is not None:
+                        grad_norms.append(float(norm))
                 self.optim.step()
                 self.gradient_steps += 1
                 st["loss/total"] = loss.item()
@@ -275,7 +278,7 @@ class PPOLagOracle:
                 break
         return np.array(rows, np.float64), stopped_at
 
-    def update(self, data: OnPolicyData, lagrangians, rescaling, batch_size, repeat, perms=None):
+    def update(self, data: OnPolicyData, lagrangians, rescaling, batch_size, repeat, perms=None, grad_norms=None):
         pb = self.process(data)
-        stats, stopped_at = self.learn(pb, lagrangians, rescaling, batch_size, repeat, perms, data=data)
+        stats, stopped_at = self.learn(pb, lagrangians, rescaling, batch_size, repeat, perms, data=data, grad_norms=grad_norms)
         return pb, stats, stopped_at
