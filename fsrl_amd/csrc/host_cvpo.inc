@@ -361,8 +361,8 @@ extern "C" int fsrl_sac_actor_forward(fsrl_ctx* c, const float* obs, int32_t k, 
 
 static bool sac_squashes(fsrl_ctx* c) { SacState* s = sac_of(c); return s && !s->ddpg && !s->cvpo; }
 
-// fsrl_collect_device on a replay context (host_devcollect.inc): the head arithmetic of sac_actor_finish + actor_draw as
-// collect_device_kernel's arguments.  false: no fused actor (layered / not initialised)
+// A device collect on a replay context (host_devcollect.inc devcollect_begin): the head arithmetic of sac_actor_finish + actor_draw
+// as the collect kernels' arguments.  false: no fused actor (layered / not initialised)
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head) {
     SacState* s = sac_of(c);
     if (!s || s->layered) return false;

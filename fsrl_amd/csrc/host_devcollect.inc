@@ -2,22 +2,21 @@
 //
 // fsrl_devenv_reset / _step make a device env an ordinary vector env: one small launch on the env's OWN stream (so that a resident
 // actor on the compute stream keeps running: a launch behind it would wait for its idle timeout) over pinned host memory, and a wait.
-// fsrl_collect_device runs collect_device_kernel on the context's compute stream -- behind every update, in front of the next -- once
-// per max_steps_per_launch vector steps, reads the launch's DcState and log back and replays the log through the bookkeeping of
+// A device collect runs collect_device_group_kernel on the context's compute stream -- behind every update, in front of the next --
+// once per max_steps_per_launch vector steps, reads the launch's DcState and log back and replays the log through the bookkeeping of
 // fsrl_store_push (devcollect_plan.hpp dc_replay_row: EnvBook, h_flags, store_version), so that the store, the episode statistics
 // and everything derived from them are as if the rows had been pushed one vector step at a time.
 // Replay contexts (SAC-Lag, DDPG-Lag, CVPO): the same kernel with their fused actor's parameters and its head arithmetic on the device
 // (DC_HEAD_GAUSS / DC_HEAD_DDPG); with prioritised replay on, a small launch behind every collect launch gives the rows' slots their
 // leaves (host_per.inc per_devcollect).
-// Grouped seeds: fsrl_collect_device_group (host_devcollect_group.inc) runs k members' collects as the k workgroups of one launch,
-// with this file's checks, entry and replay per member (devcollect_check, devcollect_begin, devcollect_replay).
-// Evaluations: fsrl_evaluate_device / _group (host_devcollect_group.inc) run the store-less form of the kernel through the same
-// checks and entry with `store = false` -- whatever concerns the store is skipped, nothing of the context but its resident actor
-// is touched -- and replay the log through the env's own accumulators (deveval_replay).
+// This file holds what ONE member of such a call needs: the checks, the entry and the log replay (devcollect_check, devcollect_begin,
+// devcollect_replay).  The launch loop and all four entry points -- fsrl_collect_device, fsrl_evaluate_device and their _group forms
+// -- are in host_devcollect_group.inc, behind the SAC code: the solo calls are the one-member launch.
+// Evaluations go through the same checks and entry with `store = false` -- whatever concerns the store is skipped, nothing of the
+// context but its resident actor is touched -- and replay the log through the env's own accumulators.
 #include "kernels_devcollect.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head);      // defined with the SAC / CVPO code
 static int sac_devcollect_enter(fsrl_ctx* c);
-static int per_devcollect(fsrl_ctx* c, const int32_t* slots_d, const int32_t* n_rows_d, int cap);       // host_per.inc
 
 struct fsrl_devenv {
     fsrl_ctx* c = nullptr;
@@ -32,9 +31,10 @@ struct fsrl_devenv {
     DcLogRow* d_log = nullptr; DcLogRow* h_log = nullptr; int log_steps = 0;
     int32_t* d_slot = nullptr;          // [log_steps][env_num]: the log rows' store slots (prioritised replay's leaves)
     DevCollectArgs* d_args = nullptr; DevCollectArgs* h_args = nullptr;     // the collect kernel's arguments: device / pinned
-    // fsrl_collect_device_group (host_devcollect_group.inc), made by the env's first grouped collect and kept
-    hipEvent_t g_ready = nullptr;       // this member's compute stream as the grouped collect found it
-    hipEvent_t g_done = nullptr;        // member 0's env: behind the grouped launch
+    // the launch loop's (host_devcollect_group.inc): made by the env's first collect or evaluation in that role and kept
+    // (devcollect_group_ensure, devcollect_group_run); the table goes with `mem`, the events in devenv_free
+    hipEvent_t g_ready = nullptr;       // a later member on a stream of its own: that stream as the call found it
+    hipEvent_t g_done = nullptr;        // member 0's env: behind the launch
     DevCollectGroupTable* d_tab = nullptr; DevCollectGroupTable* h_tab = nullptr;      // member 0's env: the member table, device / pinned
     DcEvalAcc acc[DC_MAX_ENVS] = {};    // fsrl_evaluate_device: the running episode of every env, from the log alone
 };
@@ -251,16 +251,16 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
     return 0;
 }
 
-// ---- the collect.  Everything that can refuse the call is checked before anything is touched.  solo: fsrl_collect_device, which
-// refuses grouped contexts; fsrl_collect_device_group (host_devcollect_group.inc) runs the same checks on every member without that clause.
+// ---- one member of a collect.  Everything that can refuse the call is checked before anything is touched.  named = false: the solo
+// calls; fsrl_collect_device refuses grouped contexts, and the _group calls run the same checks on every member without that clause.
 // store = false (an evaluation, grouped or not): nothing is stored, so a tap, a group and the store's geometry are no reasons.
 static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
-                            const float* act_high, int32_t max_steps, bool solo = true, bool store = true) {
+                            const float* act_high, int32_t max_steps, bool named, bool store) {
     const char* const what = store ? "collects" : "evaluations";
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
     CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
-    if (solo && store)
+    if (!named && store)
         CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
         const float* P; const ModelDesc* md;
@@ -270,7 +270,7 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     }
     if (store) CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
     if (c->in_update)
-        return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device", solo ? "" : "_group");
+        return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device", named ? "_group" : "");
     CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
     if (store) CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
@@ -290,7 +290,7 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
 // a sample drawn ahead stays valid (no row is overwritten), and the env's episode accumulators start at zero.
 struct DcActor { const float* P; const ModelDesc* md; int head; };
 static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store = true) {
+                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store) {
     const int n = v->cfg.env_num, Da = v->cfg.act_dim;
     ENTER_DEV(c);                                   // a live resident actor ends first
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
@@ -333,20 +333,22 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     return 0;
 }
 
-// One launch's log (in v->h_log, hs = what the kernel reported) through the bookkeeping of fsrl_store_push, row by row in the
-// kernel's order; the collect's running totals
+// One launch's log (in v->h_log, hs = what the kernel reported), row by row in the kernel's order, and the call's running totals.
+// A collect's rows go through the bookkeeping of fsrl_store_push on the context's book, with one store_version bump per pushed
+// vector step; an evaluation's through the env's own accumulators: the same totals and episodes, in the same order, and no book.
 struct DcTotals { int64_t rows = 0; double total_cost = 0.0; int32_t terms = 0, truncs = 0, episodes = 0; };
 static bool devcollect_state_sane(const DcState& hs, int max_steps, int n) {
     return hs.log_rows >= 0 && hs.log_rows <= max_steps * n && hs.steps >= 0 && hs.steps <= max_steps;
 }
 static int devcollect_replay(fsrl_ctx* c, fsrl_devenv* v, const DcState& hs, int32_t n_episode, DcTotals& t, double* ep_rew_out,
-                             int32_t* ep_len_out) {
+                             int32_t* ep_len_out, bool store) {
     const int n = v->cfg.env_num;
     for (int i = 0; i < hs.log_rows; ++i) {
         const DcLogRow& r = v->h_log[i];
-        if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device collect: log row %d names env %d", i, r.env);
+        if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device %s: log row %d names env %d", store ? "collect" : "evaluation", i, r.env);
         double er = 0.0; int32_t el = 0;
-        const bool done = dc_replay_row(c->env[(size_t)r.env], c->sub_size, c->h_flags.data(), r, &er, &el);
+        const bool done = store ? dc_replay_row(c->env[(size_t)r.env], c->sub_size, c->h_flags.data(), r, &er, &el)
+                                : dc_eval_row(v->acc[r.env], r, &er, &el);
         t.total_cost += r.cost;
         t.terms += (int32_t)(r.flags & 1u); t.truncs += (int32_t)((r.flags >> 1) & 1u);
         if (done) {
@@ -355,92 +357,6 @@ static int devcollect_replay(fsrl_ctx* c, fsrl_devenv* v, const DcState& hs, int
         }
     }
     t.rows += hs.log_rows;
-    c->store_version += (uint64_t)hs.steps;          // one bump per pushed vector step
-    return 0;
-}
-
-// ... and an evaluation's log through the env's own accumulators: the same totals and episodes, in the same order, and no book
-static int deveval_replay(fsrl_devenv* v, const DcState& hs, int32_t n_episode, DcTotals& t, double* ep_rew_out, int32_t* ep_len_out) {
-    const int n = v->cfg.env_num;
-    for (int i = 0; i < hs.log_rows; ++i) {
-        const DcLogRow& r = v->h_log[i];
-        if (r.env < 0 || r.env >= n) return fail(FSRL_ESTATE, "device evaluation: log row %d names env %d", i, r.env);
-        double er = 0.0; int32_t el = 0;
-        const bool done = dc_eval_row(v->acc[r.env], r, &er, &el);
-        t.total_cost += r.cost;
-        t.terms += (int32_t)(r.flags & 1u); t.truncs += (int32_t)((r.flags >> 1) & 1u);
-        if (done) {
-            if (t.episodes < n_episode) { ep_rew_out[t.episodes] = er; ep_len_out[t.episodes] = el; }
-            ++t.episodes;
-        }
-    }
-    t.rows += hs.log_rows;
-    return 0;
-}
-
-extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                                   const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
-                                   double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
-                                   int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
-    int rc = devcollect_check(c, v, n_episode, bound_method, act_low, act_high, max_steps_per_launch);
-    if (rc) return rc;
-    CHECK_ARG(steps_out && total_cost_out && term_count_out && trunc_count_out && ep_rew_out && ep_len_out && episodes_out, "null output");
-    const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
-    const int n = v->cfg.env_num;
-    DcActor actor{};
-    rc = devcollect_begin(c, v, n_episode, deterministic, bound_method, act_low, act_high, max_steps, &actor);
-    if (rc) return rc;
-    DcState& hs = *v->h_state;
-    const bool per = v->h_args->slots != nullptr;
-    hipStream_t s = c->compute;
-    const float* P = actor.P; const int head = actor.head;
-    const ModelDesc mdv = *actor.md;
-    DcTotals t;
-    int32_t launches = 0;
-    const int64_t launch_cap = dc_launch_cap(n_episode, v->cfg.max_episode_steps, max_steps);
-    for (;;) {
-        if (launches >= launch_cap) return fail(FSRL_ESTATE, "device collect: %d launches did not finish %d episodes", launches, n_episode);
-        rc = dispatch_H(c->cfg.hidden, [&](auto hc) {
-            constexpr int H = decltype(hc)::value;
-            devenv_dispatch(v->cfg.kind, [&](auto env) {
-                using Env = decltype(env);
-                const DevCollectArgs* da = v->d_args;
-                if (head == DC_HEAD_GAUSS) hipLaunchKernelGGL((collect_device_kernel<H, Env, DC_HEAD_GAUSS>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
-                else if (head == DC_HEAD_DDPG) hipLaunchKernelGGL((collect_device_kernel<H, Env, DC_HEAD_DDPG>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
-                else hipLaunchKernelGGL((collect_device_kernel<H, Env>), dim3(1), dim3(4 * H), 0, s, P, mdv, da);
-            });
-            HIPCHK(hipGetLastError());
-            return 0;
-        });
-        if (rc) return rc;
-        if (per) {          // PrioritizedReplayBuffer.add for the launch's rows: their number is DcState::log_rows, on the device
-            rc = per_devcollect(c, v->d_slot, &v->d_state->log_rows, max_steps * n);
-            if (rc) return rc;
-        }
-        ++launches;
-        HIPCHK(hipMemcpyAsync(&hs, v->d_state, sizeof(DcState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (!devcollect_state_sane(hs, max_steps, n))
-            return fail(FSRL_ESTATE, "device collect: the kernel reported %d rows in %d steps", hs.log_rows, hs.steps);
-        if (hs.log_rows > 0) {
-            HIPCHK(hipMemcpyAsync(v->h_log, v->d_log, (size_t)hs.log_rows * sizeof(DcLogRow), hipMemcpyDeviceToHost, s));     // the log: ONE copy
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        rc = devcollect_replay(c, v, hs, n_episode, t, ep_rew_out, ep_len_out);
-        if (rc) return rc;
-        if (hs.finished) break;
-        if (hs.steps == 0) return fail(FSRL_ESTATE, "device collect: a launch made no step");
-    }
-    if (t.episodes != hs.episodes)
-        return fail(FSRL_ESTATE, "device collect: the log holds %d episodes, the kernel counted %d", t.episodes, hs.episodes);
-    // FastCollector.reset_env at the end of every collect: ALL envs
-    DevEnvIo io{};
-    io.n = n;
-    rc = devenv_reset_launch(v, io, s);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    *steps_out = t.rows; *total_cost_out = t.total_cost; *term_count_out = t.terms; *trunc_count_out = t.truncs;
-    *episodes_out = std::min(t.episodes, n_episode);
-    if (launches_out) *launches_out = launches;
+    if (store) c->store_version += (uint64_t)hs.steps;
     return 0;
 }

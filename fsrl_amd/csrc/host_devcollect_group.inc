@@ -1,28 +1,29 @@
-// host_devcollect_group.inc -- k seeds' whole collects in one looping launch: fsrl_collect_device_group (part of fsrl_hip.hip, behind
-// every kind of group; include/fsrl_hip.h "Device environments").
+// host_devcollect_group.inc -- the launch loop of every device collect and evaluation, and their four entry points: fsrl_collect_device,
+// fsrl_collect_device_group, fsrl_evaluate_device, fsrl_evaluate_device_group (part of fsrl_hip.hip, behind every kind of group;
+// include/fsrl_hip.h "Device environments").
 //
 // A device collect is ONE workgroup (kernels_devcollect.hpp), and k seeds' collects share nothing: collect_device_group_kernel runs
-// them as the k workgroups of one launch, workgroup b the loop of collect_device_kernel on member b's store, env arrays, DcState and
-// log.  The host side is fsrl_collect_device's, per member: devcollect_check without its grouped clause, devcollect_begin,
-// devcollect_replay (host_devcollect.inc).  It is a free function over contexts because there are four kinds of group: a member may be
-// ungrouped or sit in an fsrl_group, an fsrl_collect_group, an fsrl_sac_group or an fsrl_cvpo_group, and is not owned here.
+// them as the k workgroups of one launch, workgroup b the loop on member b's store, env arrays, DcState and log.  There is one loop
+// on the host (devcollect_group_run) over what host_devcollect.inc does per member: devcollect_check, devcollect_begin,
+// devcollect_replay.  It is a free function over contexts because there are four kinds of group: a member may be ungrouped or sit
+// in an fsrl_group, an fsrl_collect_group, an fsrl_sac_group or an fsrl_cvpo_group, and is not owned here.
+// The solo calls are the one-member launch (`named = false`): fsrl_collect_device keeps its refusal of grouped contexts, and their
+// failures name no member and no group.
 //
 // Ordering.  The launches go on member 0's compute stream.  devcollect_begin leaves every member's uploads on ITS compute stream, behind
 // whatever that member has enqueued (updates, parameter uploads; grouped updates make the members' streams wait for the update
 // group's `done`); an event per member then puts member 0's stream behind all of them -- once per collect, not per launch.  Every
 // launch is waited for on the host before its logs are replayed, so whatever a member enqueues after the call is behind the collect.
-// Prioritised members: per_devcollect on the member's OWN compute stream behind an event recorded after the group launch, waited
-// for before the next launch overwrites the slots; it re-records upd_done as on the solo path.
-// The member table and the events are made by an env's first grouped collect and kept (fsrl_devenv).
-// Evaluations.  fsrl_evaluate_device_group is the same call with `store = false`: evaluate_device_group_kernel in the launch, no
-// tree launches, deveval_replay for the logs; fsrl_evaluate_device is its one-member case (the table-driven launch at k = 1), so
-// there is one store-less kernel family.  The members' stores, books, samplers and random streams are not touched.
-static int devcollect_group_ensure(fsrl_devenv* v, bool first) {
-    if (!v->g_ready) HIPCHK(hipEventCreateWithFlags(&v->g_ready, hipEventDisableTiming));
-    if (!first) return 0;
-    if (!v->g_done) HIPCHK(hipEventCreateWithFlags(&v->g_done, hipEventDisableTiming));
-    if (!v->d_tab) HIPCHK(v->mem.dev(&v->d_tab, sizeof(DevCollectGroupTable)));
-    if (!v->h_tab) HIPCHK(v->mem.pinned(&v->h_tab, sizeof(DevCollectGroupTable)));
+// Prioritised members: per_devcollect on the member's OWN compute stream, which re-records upd_done.  Where that is the launch stream
+// (always, for one member) it is directly behind the launch by stream order; elsewhere behind an event recorded after the launch,
+// and waited for before the next launch overwrites the slots.
+// The member table and the events are made by an env's first call in the role that needs them, and kept (fsrl_devenv).
+// Evaluations are the same call with `store = false`: evaluate_device_group_kernel in the launch, no tree launches, the logs replayed
+// through the envs' accumulators.  The members' stores, books, samplers and random streams are not touched.
+static int devcollect_group_ensure(fsrl_devenv* v0) {       // member 0's env: the table and the event behind the launch
+    if (!v0->g_done) HIPCHK(hipEventCreateWithFlags(&v0->g_done, hipEventDisableTiming));
+    if (!v0->d_tab) HIPCHK(v0->mem.dev(&v0->d_tab, sizeof(DevCollectGroupTable)));
+    if (!v0->h_tab) HIPCHK(v0->mem.pinned(&v0->h_tab, sizeof(DevCollectGroupTable)));
     return 0;
 }
 
@@ -66,8 +67,14 @@ struct DcGroupOut {
 // everything behind the checks; the caller waits for the launch stream when this fails half-way
 static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, const int32_t* n_episode, int32_t deterministic,
                                 int32_t bound_method, const float* act_low, const float* act_high, int max_steps, const DcGroupOut& o,
-                                bool store) {
-    const char* const what = store ? "grouped device collect" : "device evaluation";
+                                bool store, bool named) {
+    const char* const what = !store ? "device evaluation" : named ? "grouped device collect" : "device collect";
+    // how a failure names member i: `grouped` with its number in place of the %d, `solo` for the one member of an unnamed call
+    const auto who = [&](int i, const char* solo, const char* grouped) {
+        char b[64];
+        snprintf(b, sizeof(b), grouped, i);
+        return named ? std::string(b) : std::string(solo);
+    };
     fsrl_devenv* v0 = envs[0];
     const int Da = v0->cfg.act_dim;
     DcActor actor0{};
@@ -80,14 +87,11 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         if (actor.head != actor0.head) return fail(FSRL_ESTATE, "member %d: its actor's head kind changed under the call", i);
         v0->h_tab->P[i] = actor.P; v0->h_tab->a[i] = envs[i]->d_args;
     }
-    // the members' resident kernels are on their way out (ENTER_DEV above): the allocations below do not wait for an idle timeout
-    for (int i = 0; i < k; ++i) {
-        const int rc = devcollect_group_ensure(envs[i], false);
-        if (rc) return rc;
-    }
     hipStream_t s = ctxs[0]->compute;
     for (int i = 1; i < k; ++i) {
         if (ctxs[i]->compute == s) continue;           // members of one fsrl_group share a stream
+        // the members' resident kernels are on their way out (ENTER_DEV above): making the event does not wait for an idle timeout
+        if (!envs[i]->g_ready) HIPCHK(hipEventCreateWithFlags(&envs[i]->g_ready, hipEventDisableTiming));
         HIPCHK(hipEventRecord(envs[i]->g_ready, ctxs[i]->compute));
         HIPCHK(hipStreamWaitEvent(s, envs[i]->g_ready, 0));
     }
@@ -103,7 +107,9 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
     const int64_t launch_cap = dc_group_launch_cap(n_episode, mes, k, max_steps);
     int32_t launches = 0;
     for (;;) {
-        if (launches >= launch_cap) return fail(FSRL_ESTATE, "%s: %d launches did not finish every member", what, launches);
+        if (launches >= launch_cap)
+            return fail(FSRL_ESTATE, "%s: %d launches did not finish %s", what, launches,
+                        named ? "every member" : (std::to_string(n_episode[0]) + " episodes").c_str());
         int rc = dispatch_H(ctxs[0]->cfg.hidden, [&](auto hc) {
             constexpr int H = decltype(hc)::value;
             devenv_dispatch(v0->cfg.kind, [&](auto env) {
@@ -122,10 +128,10 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         });
         if (rc) return rc;
         // PrioritizedReplayBuffer.add for the rows of every prioritised member that went in unfinished: its own small launch, on its
-        // own compute stream, behind this launch
-        bool per_any = false;
-        for (int i = 0; i < k; ++i) per_any = per_any || (envs[i]->h_args->slots && !finished[i]);
-        if (per_any) HIPCHK(hipEventRecord(v0->g_done, s));
+        // own compute stream, behind this launch -- by stream order where that is the launch stream, else through g_done
+        bool per_other = false;
+        for (int i = 0; i < k; ++i) per_other = per_other || (envs[i]->h_args->slots && !finished[i] && ctxs[i]->compute != s);
+        if (per_other) HIPCHK(hipEventRecord(v0->g_done, s));
         for (int i = 0; i < k; ++i) {
             if (!envs[i]->h_args->slots || finished[i]) continue;
             if (ctxs[i]->compute != s) HIPCHK(hipStreamWaitEvent(ctxs[i]->compute, v0->g_done, 0));
@@ -141,7 +147,8 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         for (int i = 0; i < k; ++i) {
             const DcState& hs = *envs[i]->h_state;
             if (!devcollect_state_sane(hs, max_steps, envs[i]->cfg.env_num))
-                return fail(FSRL_ESTATE, "%s: member %d's workgroup reported %d rows in %d steps", what, i, hs.log_rows, hs.steps);
+                return fail(FSRL_ESTATE, "%s: %s reported %d rows in %d steps", what, who(i, "the kernel", "member %d's workgroup").c_str(),
+                            hs.log_rows, hs.steps);
             if (finished[i] && (hs.steps != 0 || hs.log_rows != 0))
                 return fail(FSRL_ESTATE, "%s: member %d was finished and its workgroup reported %d rows in %d steps", what, i,
                             hs.log_rows, hs.steps);
@@ -153,19 +160,18 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         if (any_rows) HIPCHK(hipStreamSynchronize(s));
         for (int i = 0; i < k; ++i) {
             const DcState& hs = *envs[i]->h_state;
-            rc = store ? devcollect_replay(ctxs[i], envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i])
-                       : deveval_replay(envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i]);
-            if (rc) { g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
+            rc = devcollect_replay(ctxs[i], envs[i], hs, n_episode[i], t[i], o.ep_rew + off[i], o.ep_len + off[i], store);
+            if (rc) { if (named) g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
             was_finished[i] = finished[i]; steps[i] = hs.steps; finished[i] = hs.finished ? 1 : 0;
         }
         if (dc_group_complete(finished, k)) break;
         const int stalled = dc_group_stalled(was_finished, steps, k);
-        if (stalled >= 0) return fail(FSRL_ESTATE, "%s: a launch made no step for member %d", what, stalled);
+        if (stalled >= 0) return fail(FSRL_ESTATE, "%s: a launch made no step%s", what, who(stalled, "", " for member %d").c_str());
     }
     for (int i = 0; i < k; ++i)
         if (t[i].episodes != envs[i]->h_state->episodes)
-            return fail(FSRL_ESTATE, "%s: member %d's log holds %d episodes, the kernel counted %d", what, i, t[i].episodes,
-                        envs[i]->h_state->episodes);
+            return fail(FSRL_ESTATE, "%s: %s holds %d episodes, the kernel counted %d", what, who(i, "the log", "member %d's log").c_str(),
+                        t[i].episodes, envs[i]->h_state->episodes);
     // FastCollector.reset_env at the end of every collect: ALL envs of ALL members, then one wait
     for (int i = 0; i < k; ++i) {
         DevEnvIo io{};
@@ -182,38 +188,44 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
     return 0;
 }
 
-// the grouped call, storing or not.  named: the refusals of a member say which (the solo evaluation has one and does not)
+// the call behind the four entry points, storing or not.  named: the _group calls, whose refusals and failures say which member.
+// named = false: a solo call -- one member, made of the caller's own non-null arguments -- whose refusals are devcollect_check's, in
+// its order, and then the outputs'
 static int devcollect_group_call(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
                                  int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
                                  const DcGroupOut& o, bool store, bool named) {
-    CHECK_ARG(k >= 1 && k <= FSRL_MAX_GROUP, "k %d: a grouped device %s has 1..%d members", k, store ? "collect" : "evaluation", FSRL_MAX_GROUP);
-    CHECK_ARG(ctxs && envs && n_episode, "null argument");
-    CHECK_ARG(o.steps && o.total_cost && o.terms && o.truncs && o.ep_rew && o.ep_len && o.episodes, "null output");
-    CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
     // ---- every refusal before anything is touched
-    for (int i = 0; i < k; ++i) {
-        CHECK_ARG(ctxs[i] && envs[i], "member %d: null context / env", i);
-        for (int j = 0; j < i; ++j) {
-            CHECK_ARG(ctxs[j] != ctxs[i], "member %d: its context is listed twice (member %d)", i, j);
-            CHECK_ARG(envs[j] != envs[i], "member %d: its device env is listed twice (member %d)", i, j);
+    const bool outputs = o.steps && o.total_cost && o.terms && o.truncs && o.ep_rew && o.ep_len && o.episodes;
+    if (named) {        // the lists' own
+        CHECK_ARG(k >= 1 && k <= FSRL_MAX_GROUP, "k %d: a grouped device %s has 1..%d members", k, store ? "collect" : "evaluation", FSRL_MAX_GROUP);
+        CHECK_ARG(ctxs && envs && n_episode, "null argument");
+        CHECK_ARG(outputs, "null output");
+        CHECK_ARG((act_low == nullptr) == (act_high == nullptr), "act_low and act_high are given together");
+        for (int i = 0; i < k; ++i) {
+            CHECK_ARG(ctxs[i] && envs[i], "member %d: null context / env", i);
+            for (int j = 0; j < i; ++j) {
+                CHECK_ARG(ctxs[j] != ctxs[i], "member %d: its context is listed twice (member %d)", i, j);
+                CHECK_ARG(envs[j] != envs[i], "member %d: its device env is listed twice (member %d)", i, j);
+            }
         }
     }
     const int Da0 = ctxs[0]->cfg.act_dim;
     for (int i = 0; i < k; ++i) {
         const int rc = devcollect_check(ctxs[i], envs[i], n_episode[i], bound_method, act_low ? act_low + (size_t)i * Da0 : nullptr,
-                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, !named, store);
+                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, named, store);
         if (rc) { if (named) g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
     }
     for (int i = 1; i < k; ++i) {
         const int rc = devcollect_group_agree(ctxs[i], envs[i], ctxs[0], envs[0], i);
         if (rc) return rc;
     }
+    CHECK_ARG(outputs, "null output");
     const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
     HIPCHK(hipSetDevice(ctxs[0]->device));
     for (int i = 0; i < k; ++i) pactor_release(ctxs[i]);       // the table's first allocation would wait for a live resident actor's idle timeout
-    int rc = devcollect_group_ensure(envs[0], true);
+    int rc = devcollect_group_ensure(envs[0]);
     if (rc) return rc;
-    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o, store);
+    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o, store, named);
     if (rc) {       // leave nothing of the call in flight: the kernel reads every member's env arrays from member 0's stream
         const std::string why = g_err;
         (void)hipStreamSynchronize(ctxs[0]->compute);
@@ -236,6 +248,16 @@ extern "C" int fsrl_evaluate_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, i
                                           double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
     const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
     return devcollect_group_call(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, false, true);
+}
+
+// ---- the solo calls: the one-member launch over the caller's own arguments
+extern "C" int fsrl_collect_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                   const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                   double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                   int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    CHECK_ARG(c && v, "null context / env");
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    return devcollect_group_call(&c, &v, 1, &n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, true, false);
 }
 
 extern "C" int fsrl_evaluate_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,

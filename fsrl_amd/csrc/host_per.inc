@@ -55,8 +55,8 @@ static int per_ingest(fsrl_ctx* c, const uint8_t* recs_d, int rec, int k) {
     HIPCHK(hipGetLastError());
     return 0;
 }
-// fsrl_collect_device: collect_device_kernel is enqueued on the COMPUTE stream and writes its rows' slots (slots_d) and their number
-// (n_rows_d) itself.  Ordering: the compute stream is behind the last update's priorities by stream order (max_prio is the value
+// A device collect: collect_device_group_kernel has written the member's rows' slots (slots_d) and their number (n_rows_d) itself, and
+// the member's COMPUTE stream is behind that launch (host_devcollect_group.inc).  Ordering: the compute stream is behind the last update's priorities by stream order (max_prio is the value
 // after it, as per_side_enter gives the side stream's writers) and behind the side stream's tree writers through the collect's
 // join_store; the side stream's NEXT writer waits for upd_done, which is recorded again behind this launch.
 static int per_devcollect(fsrl_ctx* c, const int32_t* slots_d, const int32_t* n_rows_d, int cap) {

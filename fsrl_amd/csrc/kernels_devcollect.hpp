@@ -1,6 +1,6 @@
 // kernels_devcollect.hpp -- FastCollector.collect(n_episode) as ONE workgroup that loops on the device (fsrl_collect_device).
 //
-// collect_device_kernel<H, Env>: 4 * H threads, staged like actor_resident_kernel<H, false> -- the W2 fragment in registers and the small
+// collect_device_body<H, Env, HEAD>, a workgroup of collect_device_group_kernel: 4 * H threads, staged like actor_resident_kernel<H, false> -- the W2 fragment in registers and the small
 // parameters in LDS, loaded once per launch, the same tile_forward and the same head, so a deterministic collect computes the actions
 // of the existing collectors bit for bit.  Per vector step, over the live envs in position order:
 //   1. per tile of 16 rows (at most 4): the rows' observations (device memory) -> sm.xT, tile_forward, then
@@ -61,8 +61,8 @@ struct DevCollectSmem {
     float eact[DC_MAX_ENVS * FSRL_MAX_ACT];     // mapped into the env's range
 };
 
-// The collect of ONE workgroup: the whole loop above over (P, md, ap).  collect_device_kernel runs it on its own arguments,
-// collect_device_group_kernel on its member's row of the table; nothing in it knows which.
+// The collect of ONE workgroup: the whole loop above over (P, md, ap), which the kernels below read from their member's row of the
+// table; nothing in it knows whose they are.
 // STORE = false is the evaluation (fsrl_evaluate_device): the same loop with nothing stored -- no slot, no write index, no phase 3 and
 // its barrier; phases 1, 4 and 5 and the log are the code above, so an evaluated step is a collected step.
 template <int H, class Env, int HEAD, bool STORE = true>
@@ -211,14 +211,8 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
     }
 }
 
-template <int H, class Env, int HEAD = DC_HEAD_ONPOLICY>
-__global__ __launch_bounds__(4 * H) void collect_device_kernel(const float* __restrict__ P, const ModelDesc md, const DevCollectArgs* __restrict__ ap) {
-    __shared__ TileSmem<H> sm;
-    __shared__ DevCollectSmem sh;
-    collect_device_body<H, Env, HEAD>(P, md, ap, sm, sh);
-}
-
-// ---- k collects in one launch (fsrl_collect_device_group): grid k, workgroup b runs member b's collect, the loop above unchanged.
+// ---- k collects in one launch (fsrl_collect_device_group; fsrl_collect_device is its one-member case): grid k, workgroup b runs
+// member b's collect, the loop above.
 // The members share nothing -- each has its own store, env arrays, DcState and log -- and the workgroups do not communicate: no
 // flags, no waits on another block's data; a member that is finished breaks at the loop's first test and reports 0 steps, 0 rows.
 // Per-member inputs come from a table in device memory (by value they would fill the scalar file: Registers above); md is member 0's,
@@ -232,8 +226,8 @@ struct DevCollectGroupTable {
 };
 // A pointer read from memory is a flat pointer to the compiler, and a flat load never becomes a scalar load.  AS = 1 says that it is
 // global; AS = 4 that what it points to is constant for the length of the kernel (the arguments: nothing writes them while a launch
-// runs), which is what the solo kernel's `const __restrict__` kernel argument says: the fields are read with scalar loads, whenever
-// they are needed, and none of them has to stay in a vector register across tile_forward.
+// runs), which is what `const __restrict__` says of a kernel argument: the fields are read with scalar loads, whenever they are
+// needed, and none of them has to stay in a vector register across tile_forward.
 template <int AS, class T>
 __device__ __forceinline__ const T* dc_uniform_ptr(const T* p) {
     const unsigned long long v = (unsigned long long)p;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(PER_THREADS) void per_ingest_kernel(const PerDev p,
     per_repair(p, k, slot_of);
 }
 
-// ... behind collect_device_kernel (replay heads): the launch wrote *n_rows rows (DcState::log_rows, at most cap) into the store
+// ... behind collect_device_group_kernel (replay heads): the launch wrote *n_rows rows (DcState::log_rows, at most cap) into the store
 // itself and left their slots in `slots`; the same leaves and the same repair as per_ingest_kernel's
 __global__ __launch_bounds__(PER_THREADS) void per_slots_kernel(const PerDev p, const int32_t* __restrict__ slots,
                                                                 const int32_t* __restrict__ n_rows, const int cap) {

@@ -988,7 +988,7 @@ int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int
                     int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out);
 
 /* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy and replay contexts.
- *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc; INTEGRATION.md "Device environments")
+ *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc, host_devcollect_group.inc; INTEGRATION.md "Device environments")
  *
  *      A device env holds env_num envs of one kind in device memory: per env a state row, the current observation, the step count of
  *      the running episode and the env's reset ordinal.  Kinds:
@@ -1015,7 +1015,9 @@ int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int
  *                            been called once per vector step), and at the end resets ALL envs, as FastCollector.reset_env does.
  *                            A collect starts from envs 0 .. min(env_num, n_episode) - 1 in their current state.  Rows in the staging
  *                            window are flushed first, a live resident actor is ended first.  Outputs as fsrl_collect_episodes;
- *                            *launches_out (may be NULL): launches of the collect kernel.
+ *                            *launches_out (may be NULL): launches of the collect kernel.  The call is fsrl_collect_device_group's
+ *                            launch with one member -- one kernel family, one host loop -- on an ungrouped context; its messages
+ *                            name no member.
  *                            Replay contexts (after fsrl_sac_init / fsrl_cvpo_init): the fused actor's raw head row becomes the action
  *                            on the device, in float32 with every operation rounded on its own, as fsrl_collect_step forms it on the
  *                            host -- SAC-Lag a = tanh(m + sigma eps), CVPO a = m + sigma eps, with m = the head or max_action tanh(head)

@@ -39,23 +39,26 @@ def test_entry_point_is_exported_and_declared():
 
 
 def test_group_kernel_instantiations_do_not_spill():
-    """collect_device_group_kernel<H, Env, HEAD> for H = 64 / 128 / 256 x both envs x the three heads, and the solo family next to
-    it after its body moved into a shared device function: zero spilled VGPRs, no scratch, inside the 128-VGPR cap of 4 H threads"""
+    """collect_device_group_kernel<H, Env, HEAD> for H = 64 / 128 / 256 x both envs x the three heads: zero spilled VGPRs, no scratch,
+    inside the 128-VGPR cap of 4 H threads.  It is the only storing family: the solo call is its one-member launch, and every kernel
+    named collect_device* or evaluate_device* is one of the 18 + 18 table-driven ones"""
     assert os.path.exists(LIB), "libfsrl_hip.so is not built"
     import sonotes
     notes = sonotes.kernel_notes(LIB)
-    pat = re.compile(r"^_Z\d+(collect_device_group_kernel|collect_device_kernel)ILi(\d+)E(\d+[A-Za-z]+)Li(\d)EE")
-    seen = {"collect_device_group_kernel": set(), "collect_device_kernel": set()}
+    pat = re.compile(r"^_Z\d+(collect_device\w*|evaluate_device\w*)ILi(\d+)E(\d+[A-Za-z]+)Li(\d)EE")
+    seen = {}
     for name, k in notes.items():
+        assert pat.match(name) or not re.match(r"^(_Z\d+)?(collect_device|evaluate_device)", name), name
         m = pat.match(name)
         if not m:
             continue
-        seen[m.group(1)].add((int(m.group(2)), m.group(3), int(m.group(4))))
+        seen.setdefault(m.group(1), set()).add((int(m.group(2)), m.group(3), int(m.group(4))))
         assert k["vgpr_spill_count"] == 0 and k["private_segment_fixed_size"] == 0, (name, k)
         assert k["vgpr_count"] <= 128, (name, k)
     want = {(H, env, head) for H in (64, 128, 256) for env in ENVS for head in (0, 1, 2)}
-    assert seen["collect_device_group_kernel"] == want, sorted(want - seen["collect_device_group_kernel"])
-    assert seen["collect_device_kernel"] == want, sorted(want - seen["collect_device_kernel"])
+    assert set(seen) == {"collect_device_group_kernel", "evaluate_device_group_kernel"}, sorted(seen)
+    assert seen["collect_device_group_kernel"] == want, sorted(want ^ seen["collect_device_group_kernel"])
+    assert seen["evaluate_device_group_kernel"] == want, sorted(want ^ seen["evaluate_device_group_kernel"])
 
 
 def test_example_takes_device_tasks_for_every_grouped_algo(capsys):

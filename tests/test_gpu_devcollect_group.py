@@ -275,3 +275,50 @@ def test_refusals_name_the_member_and_the_reason_and_change_nothing():
     res = group_collect([a[0], b[0], c[0]], [a[1], b[1], c[1]], [2, 3, 4], bound_method=1)       # ... and the call still works
     assert [len(r["ep_rews"]) for r in res] == [2, 3, 4]
     close(*[v for _, v in everyone]); close(*[e for e, _ in everyone])
+
+
+# ------------------------------------------------------------------------------------------------ 7. an env changes roles
+@pytest.mark.parametrize("agent", ["onpolicy", "sacl_per"])
+def test_envs_change_roles_between_solo_grouped_and_evaluating_calls(agent):
+    """An env's member table and events are made by whichever call first needs them, and an env may be the only member, member 0 or a
+    later member, collecting or evaluating: solo(A), solo(B), group([B, A]), solo(A), evaluate(B), group([A, B]) on two ungrouped
+    engines against twins that make the same calls one member at a time.  3 envs, episodes of 7 steps, 4 episodes, 4 vector steps per
+    launch: every call takes several launches and the surplus rule drops envs.  Then the one-member grouped call against the solo call"""
+    kw = dict(deterministic=False, bound_method=1, max_steps_per_launch=4)
+    per = agent == "sacl_per"
+
+    def pair():
+        if per:
+            return [rp.make("sacl", "lin8", 3, rows_per_env=9, seed=3 + i, per=(0.6, 0.4)) for i in range(2)]
+        return [on.make("lin8", 3, rows_per_env=9, seed=3 + i) for i in range(2)]
+    mem, twin = pair(), pair()
+    for _, v in mem + twin:
+        v.reset()
+    A, B = 0, 1
+    solo = lambda p, i: p[i][0].collect_device(p[i][1]._h, 4, **kw)
+    evaluate = lambda p, i: p[i][0].evaluate_device(p[i][1]._h, 4, **kw)
+
+    def same(i, got, want, what, launches=True):
+        assert_same_stats(got, want, what)
+        assert not launches or got["launches"] == want["launches"] > 1, (what, got["launches"], want["launches"])
+        assert_same_snapshot(snapshot(*mem[i]), snapshot(*twin[i]), what)
+        if per:
+            (lm, mxm, mnm, totm), (lt, mxt, mnt, tott) = mem[i][0].per_state(), twin[i][0].per_state()
+            assert np.array_equal(lm, lt) and (mxm, mnm, totm) == (mxt, mnt, tott), what + ": the sum tree"
+
+    steps = [("solo", [A]), ("solo", [B]), ("group", [B, A]), ("solo", [A]), ("evaluate", [B]), ("group", [A, B])]
+    for n, (call, who) in enumerate(steps):
+        what = f"{agent} call {n} {call}{who}"
+        if call == "group":
+            res = group_collect([mem[i][0] for i in who], [mem[i][1] for i in who], [4] * len(who), **kw)
+            assert res[0]["launches"] > 1
+        else:
+            res = [(solo if call == "solo" else evaluate)(mem, who[0])]
+        for i, r in zip(who, res):
+            want = (evaluate if call == "evaluate" else solo)(twin, i)
+            assert len(r["ep_rews"]) == 4
+            same(i, r, want, what, launches=call != "group")
+    assert all(e.store_sizes().max() == 9 for e, _ in mem)           # the sub-buffers wrapped
+    # k = 1 through the grouped entry point == the solo call
+    same(A, group_collect([mem[A][0]], [mem[A][1]], [4], **kw)[0], solo(twin, A), f"{agent} k = 1")
+    close(*[v for _, v in mem + twin]); close(*[e for e, _ in mem + twin])
