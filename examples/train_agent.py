@@ -41,8 +41,9 @@ def main():
                     help="CPO / TRPO-Lag: Batch.split size inside learn (the reference's default 99999 = the whole buffer)")
     ap.add_argument("--task", choices=["synthetic", "point-circle", "device-point-circle", "device-linear"], default="synthetic",
                     help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories; "
-                         "device-point-circle / device-linear: the same two envs as device functions (every agent; at most 64 envs; two "
-                         "hidden layers of at most 256 units -- the library refuses layered --hidden-sizes with its reason), collected by DeviceCollector")
+                         "device-point-circle / device-linear: the same two envs as device functions (every agent; at most 64 envs; any "
+                         "--hidden-sizes: two layers of at most 256 units collect through fsrl_collect_device, every other shape through "
+                         "fsrl_collect_device_layered), collected by DeviceCollector")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
     # options of the on-policy agents (the reference's constructor arguments of the same names)
     ap.add_argument("--unbounded", action=argparse.BooleanOptionalAction, default=None,

@@ -255,6 +255,10 @@ SIGNATURES = {
                                        _i32, _i32]),
     "fsrl_evaluate_device_group": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
                                              _i32, _d, _i32, _i32, _i32]),
+    "fsrl_collect_device_layered": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
+                                              _i32, _d, _i32, _i32, _i32]),
+    "fsrl_evaluate_device_layered": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
+                                               _i32, _d, _i32, _i32, _i32]),
     "fsrl_set_profiling": (C.c_int, [_ctx, C.c_int]),
     "fsrl_last_timing": (C.c_int, [_ctx, _d, C.c_int32]),
 }

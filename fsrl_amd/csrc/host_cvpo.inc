@@ -362,10 +362,10 @@ extern "C" int fsrl_sac_actor_forward(fsrl_ctx* c, const float* obs, int32_t k, 
 static bool sac_squashes(fsrl_ctx* c) { SacState* s = sac_of(c); return s && !s->ddpg && !s->cvpo; }
 
 // A device collect on a replay context (host_devcollect.inc devcollect_begin): the head arithmetic of sac_actor_finish + actor_draw
-// as the collect kernels' arguments.  false: no fused actor (layered / not initialised)
-static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head) {
+// as the collect kernels' arguments.  false: no actor of the asked kind (fused / layered), or not initialised
+static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered) {
     SacState* s = sac_of(c);
-    if (!s || s->layered) return false;
+    if (!s || s->layered != layered) return false;
     *head = s->ddpg ? DC_HEAD_DDPG : DC_HEAD_GAUSS;
     a->mean_tanh = s->mean_tanh; a->squash = sac_squashes(c) ? 1 : 0; a->exploration_sigma = s->cfg.exploration_sigma;
     return true;

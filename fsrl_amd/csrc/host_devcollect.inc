@@ -14,8 +14,11 @@
 // -- are in host_devcollect_group.inc, behind the SAC code: the solo calls are the one-member launch.
 // Evaluations go through the same checks and entry with `store = false` -- whatever concerns the store is skipped, nothing of the
 // context but its resident actor is touched -- and replay the log through the env's own accumulators.
-#include "kernels_devcollect.hpp"
-static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head);      // defined with the SAC / CVPO code
+// Layered contexts come in through fsrl_collect_device_layered / fsrl_evaluate_device_layered: the same checks, entry, loop and replay
+// with `layered = true`, lay_collect_kernel (kernels_devcollect_layered.hpp) in the launch and the env's activation workspace.
+#include "kernels_devcollect_layered.hpp"
+static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered);      // defined with the SAC / CVPO code
+static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax);    // ... and behind the layered code
 static int sac_devcollect_enter(fsrl_ctx* c);
 
 struct fsrl_devenv {
@@ -36,6 +39,10 @@ struct fsrl_devenv {
     hipEvent_t g_ready = nullptr;       // a later member on a stream of its own: that stream as the call found it
     hipEvent_t g_done = nullptr;        // member 0's env: behind the launch
     DevCollectGroupTable* d_tab = nullptr; DevCollectGroupTable* h_tab = nullptr;      // member 0's env: the member table, device / pinned
+    // layered collects: the activation workspace [2][DC_MAX_ENVS][ws_ld], made by the env's first layered collect (an env belongs to
+    // one context, so once), and member 0's env: the layered member table, device / pinned
+    float* d_ws = nullptr; int ws_ld = 0;
+    LayCollectTable* d_ltab = nullptr; LayCollectTable* h_ltab = nullptr;
     DcEvalAcc acc[DC_MAX_ENVS] = {};    // fsrl_evaluate_device: the running episode of every env, from the log alone
 };
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
@@ -255,22 +262,25 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
 // calls; fsrl_collect_device refuses grouped contexts, and the _group calls run the same checks on every member without that clause.
 // store = false (an evaluation, grouped or not): nothing is stored, so a tap, a group and the store's geometry are no reasons.
 static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
-                            const float* act_high, int32_t max_steps, bool named, bool store) {
+                            const float* act_high, int32_t max_steps, bool named, bool store, bool layered) {
     const char* const what = store ? "collects" : "evaluations";
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
-    CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
-    if (!named && store)
+    if (!layered) CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
+    else CHECK_ARG(c->lay, "a fused context (two hidden layers of at most 256 units): its device %s go through %s", what,
+                   store ? "fsrl_collect_device" : "fsrl_evaluate_device");
+    if (!named && store && !layered)
         CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
-        const float* P; const ModelDesc* md;
-        CHECK_ARG(sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md),
+        const float* P; const ModelDesc* md; const LayNet* net; int hmax;
+        CHECK_ARG(layered ? devcollect_lay_actor(const_cast<fsrl_ctx*>(c), &P, &net, &hmax) : sac_actor_resident_args(const_cast<fsrl_ctx*>(c), &P, &md),
                   "device %s on replay contexts (SAC-Lag, DDPG-Lag, CVPO) need fsrl_sac_init / fsrl_cvpo_init first", what);
         CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
     }
     if (store) CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
     if (c->in_update)
-        return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device", named ? "_group" : "");
+        return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device",
+                    layered ? "_layered" : named ? "_group" : "");
     CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
     if (store) CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
@@ -288,9 +298,10 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
 // arguments go up on the context's compute stream.  *P / *md / *head: whose actor the kernel runs.
 // store = false: the staging window stays as it is, the write indices, the store's pointers and the slot array are not arguments,
 // a sample drawn ahead stays valid (no row is overwritten), and the env's episode accumulators start at zero.
-struct DcActor { const float* P; const ModelDesc* md; int head; };
+// layered = true: the actor is (P, net) of devcollect_lay_actor, md stays null, and the env's activation workspace exists.
+struct DcActor { const float* P; const ModelDesc* md; int head; const LayNet* net; };
 static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store) {
+                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store, bool layered) {
     const int n = v->cfg.env_num, Da = v->cfg.act_dim;
     ENTER_DEV(c);                                   // a live resident actor ends first
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
@@ -321,10 +332,17 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     a.max_action = c->cfg.max_action;
     a.magic_per = div_magic(2 * v->cfg.obs_dim + Da); a.magic_da = div_magic(Da);
     // whose actor: the context's own networks, or a replay context's fused actor with its head arithmetic
-    actor->head = DC_HEAD_ONPOLICY; actor->P = c->P; actor->md = &c->md;
+    actor->head = DC_HEAD_ONPOLICY; actor->P = c->P; actor->md = &c->md; actor->net = nullptr;
+    if (layered) {
+        int hmax = 0;
+        actor->md = nullptr;
+        if (!devcollect_lay_actor(c, &actor->P, &actor->net, &hmax)) return fail(FSRL_ESTATE, "no layered actor network");
+        const int ld = round_up(std::max(hmax, v->cfg.obs_dim), 4);        // layer 0's input, the observations, is gathered into it too
+        HIPCHK(v->mem.regrow(v->ws_ld, ld, ld, {Mem::D(&v->d_ws, (size_t)2 * DC_MAX_ENVS * ld * sizeof(float))}));
+    }
     if (ctx_is_replay(c)) {
-        if (!sac_actor_resident_args(c, &actor->P, &actor->md) || !sac_devcollect_head(c, &a, &actor->head))
-            return fail(FSRL_ESTATE, "no fused actor network");
+        if ((!layered && !sac_actor_resident_args(c, &actor->P, &actor->md)) || !sac_devcollect_head(c, &a, &actor->head, layered))
+            return fail(FSRL_ESTATE, "no %s actor network", layered ? "layered" : "fused");
         rc = store ? sac_devcollect_enter(c) : 0;
         if (rc) return rc;
         a.slots = store && c->per ? v->d_slot : nullptr;

@@ -20,11 +20,28 @@
 // The member table and the events are made by an env's first call in the role that needs them, and kept (fsrl_devenv).
 // Evaluations are the same call with `store = false`: evaluate_device_group_kernel in the launch, no tree launches, the logs replayed
 // through the envs' accumulators.  The members' stores, books, samplers and random streams are not touched.
-static int devcollect_group_ensure(fsrl_devenv* v0) {       // member 0's env: the table and the event behind the launch
+static int devcollect_group_ensure(fsrl_devenv* v0, bool layered) {       // member 0's env: the table and the event behind the launch
     if (!v0->g_done) HIPCHK(hipEventCreateWithFlags(&v0->g_done, hipEventDisableTiming));
+    if (layered) {
+        if (!v0->d_ltab) HIPCHK(v0->mem.dev(&v0->d_ltab, sizeof(LayCollectTable)));
+        if (!v0->h_ltab) HIPCHK(v0->mem.pinned(&v0->h_ltab, sizeof(LayCollectTable)));
+        return 0;
+    }
     if (!v0->d_tab) HIPCHK(v0->mem.dev(&v0->d_tab, sizeof(DevCollectGroupTable)));
     if (!v0->h_tab) HIPCHK(v0->mem.pinned(&v0->h_tab, sizeof(DevCollectGroupTable)));
     return 0;
+}
+
+// the actor of a layered context as lay_collect_kernel takes it: the on-policy context's own first network, or a replay context's
+// actor (SacState::ka, PA).  false: not a layered context, or a replay context nothing was initialised on
+static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax) {
+    if (!c->lay) return false;
+    *hmax = c->lay->hmax;
+    if (!ctx_is_replay(c)) { *P = c->P; *net = &c->lay->lm.net[0]; return true; }
+    SacState* s = sac_of(c);
+    if (!s || !s->layered) return false;
+    *P = s->PA; *net = &s->ka.lm.net[0];
+    return true;
 }
 
 static int devcollect_head_kind(const fsrl_ctx* c) {
@@ -35,7 +52,7 @@ static int devcollect_head_kind(const fsrl_ctx* c) {
 
 // member i against member 0: everything the ONE instantiation and the shared ModelDesc stand for.  What travels in each member's own
 // DevCollectArgs may differ: env_num, n_episode, the env seed, the bounds, max_action, squash, exploration_sigma, prioritised replay.
-static int devcollect_group_agree(const fsrl_ctx* c, const fsrl_devenv* v, const fsrl_ctx* c0, const fsrl_devenv* v0, int i) {
+static int devcollect_group_agree(const fsrl_ctx* c, const fsrl_devenv* v, const fsrl_ctx* c0, const fsrl_devenv* v0, int i, bool layered) {
     static const char* const heads[] = {"an on-policy", "a Gaussian replay (SAC-Lag, CVPO)", "a DDPG-Lag"};
     CHECK_ARG(c->device == c0->device, "member %d: members live on one device", i);
     CHECK_ARG(devcollect_head_kind(c) == devcollect_head_kind(c0), "member %d is %s context and member 0 %s one: a grouped device collect "
@@ -45,6 +62,9 @@ static int devcollect_group_agree(const fsrl_ctx* c, const fsrl_devenv* v, const
               "member %d: members must have one network shape (obs_dim, act_dim, hidden, n_critics): (%d, %d, %d, %d), member 0's "
               "(%d, %d, %d, %d)", i, c->cfg.obs_dim, c->cfg.act_dim, c->cfg.hidden, c->cfg.n_critics, c0->cfg.obs_dim, c0->cfg.act_dim,
               c0->cfg.hidden, c0->cfg.n_critics);
+    if (layered)        // every member brings its own LayNet, but the groups ask one shape of layered members and so does this call
+        CHECK_ARG(lay_same_shape(c->cfg, c0->cfg), "member %d: members of a layered device collect must have one hidden_sizes and "
+                  "force_layered (it has %d hidden layers, member 0 %d)", i, c->cfg.n_hidden, c0->cfg.n_hidden);
     CHECK_ARG(v->cfg.kind == v0->cfg.kind, "member %d: its device env is of kind %d, member 0's of kind %d: one env kind per grouped collect "
               "(the kernel is instantiated once)", i, v->cfg.kind, v0->cfg.kind);
     CHECK_ARG(v->cfg.max_episode_steps == v0->cfg.max_episode_steps, "member %d: members must share max_episode_steps (%d, member 0's %d)", i,
@@ -67,7 +87,7 @@ struct DcGroupOut {
 // everything behind the checks; the caller waits for the launch stream when this fails half-way
 static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, const int32_t* n_episode, int32_t deterministic,
                                 int32_t bound_method, const float* act_low, const float* act_high, int max_steps, const DcGroupOut& o,
-                                bool store, bool named) {
+                                bool store, bool named, bool layered) {
     const char* const what = !store ? "device evaluation" : named ? "grouped device collect" : "device collect";
     // how a failure names member i: `grouped` with its number in place of the %d, `solo` for the one member of an unnamed call
     const auto who = [&](int i, const char* solo, const char* grouped) {
@@ -81,11 +101,17 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
     for (int i = 0; i < k; ++i) {
         DcActor actor{};
         const int rc = devcollect_begin(ctxs[i], envs[i], n_episode[i], deterministic, bound_method, act_low ? act_low + (size_t)i * Da : nullptr,
-                                        act_high ? act_high + (size_t)i * Da : nullptr, max_steps, &actor, store);
+                                        act_high ? act_high + (size_t)i * Da : nullptr, max_steps, &actor, store, layered);
         if (rc) return rc;
         if (i == 0) actor0 = actor;
         if (actor.head != actor0.head) return fail(FSRL_ESTATE, "member %d: its actor's head kind changed under the call", i);
-        v0->h_tab->P[i] = actor.P; v0->h_tab->a[i] = envs[i]->d_args;
+        if (layered) {
+            LayCollectMember& m = v0->h_ltab->m[i];
+            m.P = actor.P; m.a = envs[i]->d_args; m.ws = envs[i]->d_ws; m.ld = envs[i]->ws_ld;
+            m.unbounded = ctxs[i]->cfg.unbounded ? 1 : 0; m.net = *actor.net;
+        } else {
+            v0->h_tab->P[i] = actor.P; v0->h_tab->a[i] = envs[i]->d_args;
+        }
     }
     hipStream_t s = ctxs[0]->compute;
     for (int i = 1; i < k; ++i) {
@@ -95,8 +121,9 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         HIPCHK(hipEventRecord(envs[i]->g_ready, ctxs[i]->compute));
         HIPCHK(hipStreamWaitEvent(s, envs[i]->g_ready, 0));
     }
-    HIPCHK(hipMemcpyAsync(v0->d_tab, v0->h_tab, sizeof(DevCollectGroupTable), hipMemcpyHostToDevice, s));
-    const ModelDesc mdv = *actor0.md;
+    if (layered) HIPCHK(hipMemcpyAsync(v0->d_ltab, v0->h_ltab, sizeof(LayCollectTable), hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(v0->d_tab, v0->h_tab, sizeof(DevCollectGroupTable), hipMemcpyHostToDevice, s));
+    const ModelDesc mdv = layered ? ModelDesc{} : *actor0.md;
     const int head = actor0.head;
     DcTotals t[FSRL_MAX_GROUP];
     uint8_t finished[FSRL_MAX_GROUP] = {}, was_finished[FSRL_MAX_GROUP] = {};
@@ -110,7 +137,20 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
         if (launches >= launch_cap)
             return fail(FSRL_ESTATE, "%s: %d launches did not finish %s", what, launches,
                         named ? "every member" : (std::to_string(n_episode[0]) + " episodes").c_str());
-        int rc = dispatch_H(ctxs[0]->cfg.hidden, [&](auto hc) {
+        // layered members: the one looping kernel of kernels_devcollect_layered.hpp, whatever the widths
+        const auto lay_go = [&]() {
+            devenv_dispatch(v0->cfg.kind, [&](auto env) {
+                using Env = decltype(env);
+                const LayCollectTable* tab = v0->d_ltab;
+#define LAYC_GO(HEAD_, STORE_) hipLaunchKernelGGL((lay_collect_kernel<Env, HEAD_, STORE_>), dim3(k), dim3(LAYC_NT), 0, s, tab)
+                if (store) { if (head == DC_HEAD_GAUSS) LAYC_GO(DC_HEAD_GAUSS, true); else if (head == DC_HEAD_DDPG) LAYC_GO(DC_HEAD_DDPG, true); else LAYC_GO(DC_HEAD_ONPOLICY, true); }
+                else { if (head == DC_HEAD_GAUSS) LAYC_GO(DC_HEAD_GAUSS, false); else if (head == DC_HEAD_DDPG) LAYC_GO(DC_HEAD_DDPG, false); else LAYC_GO(DC_HEAD_ONPOLICY, false); }
+#undef LAYC_GO
+            });
+            HIPCHK(hipGetLastError());
+            return 0;
+        };
+        int rc = layered ? lay_go() : dispatch_H(ctxs[0]->cfg.hidden, [&](auto hc) {
             constexpr int H = decltype(hc)::value;
             devenv_dispatch(v0->cfg.kind, [&](auto env) {
                 using Env = decltype(env);
@@ -193,7 +233,7 @@ static int devcollect_group_run(fsrl_ctx** ctxs, fsrl_devenv** envs, int k, cons
 // its order, and then the outputs'
 static int devcollect_group_call(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
                                  int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
-                                 const DcGroupOut& o, bool store, bool named) {
+                                 const DcGroupOut& o, bool store, bool named, bool layered = false) {
     // ---- every refusal before anything is touched
     const bool outputs = o.steps && o.total_cost && o.terms && o.truncs && o.ep_rew && o.ep_len && o.episodes;
     if (named) {        // the lists' own
@@ -212,20 +252,20 @@ static int devcollect_group_call(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
     const int Da0 = ctxs[0]->cfg.act_dim;
     for (int i = 0; i < k; ++i) {
         const int rc = devcollect_check(ctxs[i], envs[i], n_episode[i], bound_method, act_low ? act_low + (size_t)i * Da0 : nullptr,
-                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, named, store);
+                                        act_high ? act_high + (size_t)i * Da0 : nullptr, max_steps_per_launch, named, store, layered);
         if (rc) { if (named) g_err = "member " + std::to_string(i) + ": " + g_err; return rc; }
     }
     for (int i = 1; i < k; ++i) {
-        const int rc = devcollect_group_agree(ctxs[i], envs[i], ctxs[0], envs[0], i);
+        const int rc = devcollect_group_agree(ctxs[i], envs[i], ctxs[0], envs[0], i, layered);
         if (rc) return rc;
     }
     CHECK_ARG(outputs, "null output");
     const int max_steps = max_steps_per_launch > 0 ? max_steps_per_launch : DC_DEFAULT_STEPS;
     HIPCHK(hipSetDevice(ctxs[0]->device));
     for (int i = 0; i < k; ++i) pactor_release(ctxs[i]);       // the table's first allocation would wait for a live resident actor's idle timeout
-    int rc = devcollect_group_ensure(envs[0]);
+    int rc = devcollect_group_ensure(envs[0], layered);
     if (rc) return rc;
-    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o, store, named);
+    rc = devcollect_group_run(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps, o, store, named, layered);
     if (rc) {       // leave nothing of the call in flight: the kernel reads every member's env arrays from member 0's stream
         const std::string why = g_err;
         (void)hipStreamSynchronize(ctxs[0]->compute);
@@ -267,4 +307,24 @@ extern "C" int fsrl_evaluate_device(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episo
     CHECK_ARG(c && v, "null context / env");
     const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
     return devcollect_group_call(&c, &v, 1, &n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, false, false);
+}
+
+// ---- layered contexts: the _group calls' arguments, the same loop, lay_collect_kernel in the launch.  k = 1 is the solo collect, and
+// its failures name no member; members may sit in any kind of group or in none.
+extern "C" int fsrl_collect_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                           int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                           int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                           double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    if (k == 1) CHECK_ARG(ctxs && envs && n_episode && ctxs[0] && envs[0], "null context / env");
+    return devcollect_group_call(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, true, k != 1, true);
+}
+
+extern "C" int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                            int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                            int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                            double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out) {
+    const DcGroupOut o{steps_out, total_cost_out, term_count_out, trunc_count_out, ep_rew_out, ep_len_out, episodes_out, launches_out};
+    if (k == 1) CHECK_ARG(ctxs && envs && n_episode && ctxs[0] && envs[0], "null context / env");
+    return devcollect_group_call(ctxs, envs, k, n_episode, deterministic, bound_method, act_low, act_high, max_steps_per_launch, o, false, k != 1, true);
 }

@@ -61,6 +61,131 @@ struct DevCollectSmem {
     float eact[DC_MAX_ENVS * FSRL_MAX_ACT];     // mapped into the env's range
 };
 
+// ---- the phases of one vector step as functions: collect_device_body below and the layered loop (kernels_devcollect_layered.hpp)
+// are the same calls around their own phase 1.  Every one takes this step's opaque thread id (Registers above).
+// what a launch starts from / leaves behind in DcState
+template <bool STORE>
+__device__ __forceinline__ void dc_state_load(const DevCollectArgs& a, DevCollectSmem& sh, const int tid) {
+    if (tid < DC_MAX_ENVS) {
+        sh.live[tid] = a.state->live[tid];
+        if constexpr (STORE) sh.index[tid] = a.state->index[tid];
+    }
+    if (tid == 0) { sh.n_live = a.state->n_live; sh.episodes = a.state->episodes; sh.finished = a.state->finished; }
+}
+template <bool STORE>
+__device__ __forceinline__ void dc_state_save(const DevCollectArgs& a, DevCollectSmem& sh, const int step, const int log_rows) {
+    int te = threadIdx.x;
+    asm volatile("" : "+v"(te));
+    if (te < DC_MAX_ENVS) {
+        a.state->live[te] = sh.live[te];
+        if constexpr (STORE) a.state->index[te] = sh.index[te];
+    }
+    if (te == 0) {
+        a.state->n_live = sh.n_live; a.state->episodes = sh.episodes; a.state->finished = sh.finished;
+        a.state->steps = step; a.state->log_rows = log_rows;
+    }
+}
+// phase 1's tail for component d of the row at live position p: the head arithmetic, the draw and map_action.  `raw` is the row's raw
+// head outputs (raw[d]; DC_HEAD_GAUSS: the log sigma head at raw[Da + d]), `sig` the actor's sigma_param (DC_HEAD_ONPOLICY); both are
+// read only where the mode needs them.
+template <int HEAD>
+__device__ __forceinline__ void dc_head(const DevCollectArgs& a, DevCollectSmem& sh, const float* raw, const float* sig, const int unbounded,
+                                        const int Da, const int p, const int d) {
+#pragma clang fp contract(off)
+    const int e = sh.live[p];
+    const float x = raw[d];
+    float act;
+    if constexpr (HEAD == DC_HEAD_ONPOLICY) {
+        act = unbounded ? x : a.max_action * tanhf(x);
+        if (!a.deterministic) {
+            const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+            const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
+            act = act + expf(sig[d]) * eps;
+        }
+    } else {                             // the replay agents: the raw head row -> (m, sigma) -> the draw
+        float sg;
+        if constexpr (HEAD == DC_HEAD_GAUSS) {
+            act = a.mean_tanh ? a.max_action * tanhf(x) : x;
+            sg = expf(fminf(fmaxf(raw[Da + d], -20.0f), 2.0f));
+        } else {
+            act = a.max_action * tanhf(x);
+            sg = a.exploration_sigma;
+        }
+        if (!a.deterministic) {
+            const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+            const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
+            act = act + sg * eps;
+        }
+        if (HEAD == DC_HEAD_GAUSS && a.squash) act = tanhf(act);
+    }
+    sh.act[p * FSRL_MAX_ACT + d] = act;
+    sh.eact[p * FSRL_MAX_ACT + d] = devenv_map_action(act, a.bound_method, a.scaled != 0, a.low[d], a.high[d]);
+}
+// phase 2: env step, scalars of the row, log
+template <class Env, int HEAD, bool STORE>
+__device__ __forceinline__ void dc_env_step(const DevCollectArgs& a, DevCollectSmem& sh, const int lt, const int n_live, const int log_rows,
+                                            const int Do) {
+    if (lt < n_live) {
+        const int e = sh.live[lt];
+        const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
+        const int32_t t = a.ea.t[e];
+        double rew, cost;
+        bool term;
+        Env::step(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, &sh.eact[lt * FSRL_MAX_ACT], g, (uint32_t)t,
+                  a.ea.nxt + (size_t)e * Do, rew, cost, term);
+        a.ea.t[e] = t + 1;
+        const uint32_t fl = dc_flags(term, dc_truncated(t + 1, a.ep.max_steps));
+        [[maybe_unused]] int64_t slot = 0;
+        if constexpr (STORE) {
+            slot = dc_slot(e, a.sub_size, sh.index[e]);
+            sh.index[e] = dc_next_index(sh.index[e], a.sub_size);
+            sh.slot[lt] = (int32_t)slot;
+        }
+        sh.done[lt] = fl != 0u;
+        if constexpr (STORE) { a.st.rew[slot] = rew; a.st.cost[slot] = cost; a.st.flags[slot] = (uint8_t)fl; }
+        DcLogRow lr;
+        lr.env = e; lr.flags = fl; lr.rew = rew; lr.cost = cost;
+        a.log[log_rows + lt] = lr;
+        if constexpr (STORE && HEAD != DC_HEAD_ONPOLICY) { if (a.slots) a.slots[log_rows + lt] = (int32_t)slot; }
+    }
+}
+// phase 3: the rows' vectors into the store, nt threads
+__device__ __forceinline__ void dc_store_rows(const DevCollectArgs& a, DevCollectSmem& sh, const int lt, const int nt, const int n_live,
+                                              const int Do, const int Da) {
+    const int per = 2 * Do + Da;
+    for (int x = lt; x < n_live * per; x += nt) {
+        const int p = div_by_magic((unsigned)x, a.magic_per), f = x - p * per, e = sh.live[p];
+        const size_t slot = (size_t)sh.slot[p];
+        if (f < Do) a.st.obs[slot * Do + f] = a.ea.obs[(size_t)e * Do + f];
+        else if (f < 2 * Do) a.st.obs_next[slot * Do + (f - Do)] = a.ea.nxt[(size_t)e * Do + (f - Do)];
+        else a.st.act[slot * Da + (f - 2 * Do)] = sh.act[p * FSRL_MAX_ACT + (f - 2 * Do)];
+    }
+}
+// phase 4: the next observation: a reset where the episode ended
+template <class Env>
+__device__ __forceinline__ void dc_next_obs(const DevCollectArgs& a, DevCollectSmem& sh, const int lt, const int n_live, const int Do) {
+    if (lt < n_live) {
+        const int e = sh.live[lt];
+        if (sh.done[lt]) {
+            const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)a.ea.ordinal[e]};
+            Env::reset(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, g, a.ea.obs + (size_t)e * Do);
+            a.ea.t[e] = 0;
+            a.ea.ordinal[e] += 1;
+        } else {
+            for (int j = 0; j < Do; ++j) a.ea.obs[(size_t)e * Do + j] = a.ea.nxt[(size_t)e * Do + j];
+        }
+    }
+}
+// phase 5: who goes on (thread 0)
+__device__ __forceinline__ void dc_who_goes_on(DevCollectSmem& sh, const int lt, const int n_live, const int n_episode) {
+    if (lt == 0) {
+        int32_t ep = sh.episodes;
+        sh.n_live = dc_episode_end(sh.live, n_live, sh.done, n_episode, &ep);
+        sh.episodes = ep;
+        sh.finished = dc_complete(ep, n_episode) ? 1 : 0;
+    }
+}
+
 // The collect of ONE workgroup: the whole loop above over (P, md, ap), which the kernels below read from their member's row of the
 // table; nothing in it knows whose they are.
 // STORE = false is the evaluation (fsrl_evaluate_device): the same loop with nothing stored -- no slot, no write index, no phase 3 and
@@ -80,13 +205,8 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
     FwdW2Frag<H> wf;
     wf.load(P + no.W2f, tid >> 6, tid & 63);
     stg.commit(sm, no, Do, tid);
-    if (tid < DC_MAX_ENVS) {
-        sh.live[tid] = a.state->live[tid];
-        if constexpr (STORE) sh.index[tid] = a.state->index[tid];
-    }
-    if (tid == 0) { sh.n_live = a.state->n_live; sh.episodes = a.state->episodes; sh.finished = a.state->finished; }
+    dc_state_load<STORE>(a, sh, tid);
     const int n_episode = a.state->n_episode;
-    const int per = 2 * Do + Da;
     int step = 0, log_rows = 0;
     for (; step < a.max_steps; ++step) {
         __syncthreads();
@@ -108,107 +228,28 @@ __device__ __forceinline__ void collect_device_body(const float* __restrict__ P,
             __syncthreads();
             tile_forward<H>(sm, P, no, Do, lt, wf);
             if (lt < n_valid * Da) {
-#pragma clang fp contract(off)
-                const int i = div_by_magic((unsigned)lt, a.magic_da), d = lt - i * Da, p = row0 + i, e = sh.live[p];
-                const float x = sm.out[i * FSRL_MAX_ACT + d];
-                float act;
-                if constexpr (HEAD == DC_HEAD_ONPOLICY) {
-                    act = md.unbounded ? x : a.max_action * tanhf(x);
-                    if (!a.deterministic) {
-                        const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
-                        const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
-                        act = act + expf(sm.sig[d]) * eps;
-                    }
-                } else {                             // the replay agents: the raw head row -> (m, sigma) -> the draw
-                    float sg;
-                    if constexpr (HEAD == DC_HEAD_GAUSS) {
-                        act = a.mean_tanh ? a.max_action * tanhf(x) : x;
-                        sg = expf(fminf(fmaxf(sm.out[i * FSRL_MAX_ACT + Da + d], -20.0f), 2.0f));
-                    } else {
-                        act = a.max_action * tanhf(x);
-                        sg = a.exploration_sigma;
-                    }
-                    if (!a.deterministic) {
-                        const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
-                        const float eps = devenv_normal(g, (uint32_t)a.ea.t[e], DEVENV_STREAM_ACT, d);
-                        act = act + sg * eps;
-                    }
-                    if (HEAD == DC_HEAD_GAUSS && a.squash) act = tanhf(act);
-                }
-                sh.act[p * FSRL_MAX_ACT + d] = act;
-                sh.eact[p * FSRL_MAX_ACT + d] = devenv_map_action(act, a.bound_method, a.scaled != 0, a.low[d], a.high[d]);
+                const int i = div_by_magic((unsigned)lt, a.magic_da), d = lt - i * Da;
+                dc_head<HEAD>(a, sh, &sm.out[i * FSRL_MAX_ACT], sm.sig, md.unbounded, Da, row0 + i, d);
             }
             __syncthreads();
         }
         // ---- 2. env step, scalars of the row, log
-        if (lt < n_live) {
-            const int e = sh.live[lt];
-            const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)(a.ea.ordinal[e] - 1)};
-            const int32_t t = a.ea.t[e];
-            double rew, cost;
-            bool term;
-            Env::step(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, &sh.eact[lt * FSRL_MAX_ACT], g, (uint32_t)t,
-                      a.ea.nxt + (size_t)e * Do, rew, cost, term);
-            a.ea.t[e] = t + 1;
-            const uint32_t fl = dc_flags(term, dc_truncated(t + 1, a.ep.max_steps));
-            [[maybe_unused]] int64_t slot = 0;
-            if constexpr (STORE) {
-                slot = dc_slot(e, a.sub_size, sh.index[e]);
-                sh.index[e] = dc_next_index(sh.index[e], a.sub_size);
-                sh.slot[lt] = (int32_t)slot;
-            }
-            sh.done[lt] = fl != 0u;
-            if constexpr (STORE) { a.st.rew[slot] = rew; a.st.cost[slot] = cost; a.st.flags[slot] = (uint8_t)fl; }
-            DcLogRow lr;
-            lr.env = e; lr.flags = fl; lr.rew = rew; lr.cost = cost;
-            a.log[log_rows + lt] = lr;
-            if constexpr (STORE && HEAD != DC_HEAD_ONPOLICY) { if (a.slots) a.slots[log_rows + lt] = (int32_t)slot; }
-        }
+        dc_env_step<Env, HEAD, STORE>(a, sh, lt, n_live, log_rows, Do);
         __syncthreads();
         if constexpr (STORE) {
             // ---- 3. the rows' vectors into the store
-            for (int x = lt; x < n_live * per; x += NT) {
-                const int p = div_by_magic((unsigned)x, a.magic_per), f = x - p * per, e = sh.live[p];
-                const size_t slot = (size_t)sh.slot[p];
-                if (f < Do) a.st.obs[slot * Do + f] = a.ea.obs[(size_t)e * Do + f];
-                else if (f < 2 * Do) a.st.obs_next[slot * Do + (f - Do)] = a.ea.nxt[(size_t)e * Do + (f - Do)];
-                else a.st.act[slot * Da + (f - 2 * Do)] = sh.act[p * FSRL_MAX_ACT + (f - 2 * Do)];
-            }
+            dc_store_rows(a, sh, lt, NT, n_live, Do, Da);
             __syncthreads();
         }
         // ---- 4. the next observation: a reset where the episode ended
-        if (lt < n_live) {
-            const int e = sh.live[lt];
-            if (sh.done[lt]) {
-                const DevRng g{a.k0, a.k1, (uint32_t)e, (uint32_t)a.ea.ordinal[e]};
-                Env::reset(a.ep, a.ea.state + (size_t)e * DEVENV_STATE, g, a.ea.obs + (size_t)e * Do);
-                a.ea.t[e] = 0;
-                a.ea.ordinal[e] += 1;
-            } else {
-                for (int j = 0; j < Do; ++j) a.ea.obs[(size_t)e * Do + j] = a.ea.nxt[(size_t)e * Do + j];
-            }
-        }
+        dc_next_obs<Env>(a, sh, lt, n_live, Do);
         log_rows += n_live;
         __syncthreads();
         // ---- 5. who goes on
-        if (lt == 0) {
-            int32_t ep = sh.episodes;
-            sh.n_live = dc_episode_end(sh.live, n_live, sh.done, n_episode, &ep);
-            sh.episodes = ep;
-            sh.finished = dc_complete(ep, n_episode) ? 1 : 0;
-        }
+        dc_who_goes_on(sh, lt, n_live, n_episode);
     }
     __syncthreads();
-    int te = threadIdx.x;
-    asm volatile("" : "+v"(te));
-    if (te < DC_MAX_ENVS) {
-        a.state->live[te] = sh.live[te];
-        if constexpr (STORE) a.state->index[te] = sh.index[te];
-    }
-    if (te == 0) {
-        a.state->n_live = sh.n_live; a.state->episodes = sh.episodes; a.state->finished = sh.finished;
-        a.state->steps = step; a.state->log_rows = log_rows;
-    }
+    dc_state_save<STORE>(a, sh, step, log_rows);
 }
 
 // ---- k collects in one launch (fsrl_collect_device_group; fsrl_collect_device is its one-member case): grid k, workgroup b runs

@@ -4,7 +4,9 @@ launches and one small read-back per collect instead of one doorbell round trip 
 same store contents and episode-exact behaviour (surplus envs dropped, every env reset at the end of a collect) as `FastCollector`;
 the action noise comes from the env's Philox stream, not from the library's xoshiro stream.  On-policy and replay
 policies alike (SAC-Lag, DDPG-Lag, CVPO: the actor's head arithmetic runs on the device too; a prioritised buffer's leaves follow
-the rows); layered engines are refused by the library, with the reason, and so is a `DeviceCollector` of its own on a grouped engine.
+the rows).  Layered engines (hidden_sizes of any depth and width) collect through the layered entry points of the library
+(fsrl_collect_device_layered / fsrl_evaluate_device_layered: one kernel for every shape, the weights streamed from L2); the collectors
+route on `_layered(engine)`.  A `DeviceCollector` of its own on a grouped fused engine is refused by the library, with the reason.
 
 Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
 through `GroupDeviceCollector(collectors)`: ONE launch per `max_steps_per_launch` vector steps carries every member's collect, a
@@ -43,7 +45,8 @@ def _collect_stats(r):
 
 
 def _layered(eng) -> bool:
-    """whether the engine's context is a layered one (include/fsrl_hip.h fsrl_config.n_hidden): no device collects there"""
+    """whether the engine's context is a layered one (include/fsrl_hip.h fsrl_config.n_hidden): its device collects and
+    evaluations are the library's _layered calls"""
     hs = eng.cfg.hidden_sizes
     if hs is None:
         return False
@@ -107,7 +110,8 @@ class DeviceCollector:
 
     # ------------------------------------------------------------------ collect
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
-        return self._collect(n_episode, self.policy.engine.collect_device)
+        eng = self.policy.engine
+        return self._collect(n_episode, eng.collect_device_layered if _layered(eng) else eng.collect_device)
 
     def _collect(self, n_episode, run) -> Dict[str, Any]:
         if n_episode is None:
@@ -137,7 +141,8 @@ class DeviceEvalCollector(DeviceCollector):
         super().__init__(policy, env, None, max_steps_per_launch, exploration_noise)
 
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
-        return self._collect(n_episode, self.policy.engine.evaluate_device)
+        eng = self.policy.engine
+        return self._collect(n_episode, eng.evaluate_device_layered if _layered(eng) else eng.evaluate_device)
 
 
 class GroupDeviceCollector:
@@ -153,12 +158,18 @@ class GroupDeviceCollector:
         assert n_eval in (0, len(self.collectors)), \
             "GroupDeviceCollector: a mix of store-less and storing collectors; a group evaluates or collects with every member"
         self.store = n_eval == 0
+        # one launch, one kernel family: the members' engines are all layered or all fused
+        self.layered = _layered(self.collectors[0].policy.engine)
+        for i, c in enumerate(self.collectors):
+            assert _layered(c.policy.engine) == self.layered, \
+                f"GroupDeviceCollector: member {i} is a {'layered' if not self.layered else 'fused'} engine and member 0 a " \
+                f"{'layered' if self.layered else 'fused'} one; a group is all layered or all fused"
         self.max_steps_per_launch = int(max_steps_per_launch)
         self.last_launches = 0
 
     def collect(self, n_episode: Union[int, Sequence[int]] = 1, **_ignored) -> List[Dict[str, Any]]:
         """n_episode: one count or one per member -> one stats dict per member, with the keys of DeviceCollector.collect"""
-        from fsrl_amd.engine import collect_device_group, evaluate_device_group
+        from fsrl_amd.engine import collect_device_group, collect_device_layered, evaluate_device_group, evaluate_device_layered
         cols = self.collectors
         n = len(cols)
         ns = [int(n_episode)] * n if np.isscalar(n_episode) else [int(x) for x in n_episode]
@@ -175,8 +186,9 @@ class GroupDeviceCollector:
         det, bound = args[0][0], args[0][1]
         lows = None if args[0][2] is None else np.stack([a[2] for a in args])
         highs = None if args[0][2] is None else np.stack([a[3] for a in args])
-        res = (collect_device_group if self.store else evaluate_device_group)([col.policy.engine for col in cols], [col.env._h for col in cols], ns, det, bound, lows, highs,
-                                                                              self.max_steps_per_launch)
+        run = ((collect_device_layered if self.store else evaluate_device_layered) if self.layered
+               else (collect_device_group if self.store else evaluate_device_group))
+        res = run([col.policy.engine for col in cols], [col.env._h for col in cols], ns, det, bound, lows, highs, self.max_steps_per_launch)
         dt = max(time.time() - t0, 1e-9)
         stats = []
         for col, r in zip(cols, res):

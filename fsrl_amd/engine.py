@@ -457,6 +457,17 @@ class Engine:
         hi = np.ascontiguousarray(high, np.float32) if low is not None else None
         return self._collect_device(self.lib.fsrl_evaluate_device, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
 
+    def collect_device_layered(self, h, n_episode, deterministic=False, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.collect_device for a LAYERED engine (hidden_sizes of any depth and width): fsrl_collect_device_layered with this one
+        member.  The same arguments and result dict; the engine may be a member of any kind of group."""
+        return collect_device_layered([self], [h], n_episode, deterministic, bound_method, None if low is None else [low],
+                                      None if low is None else [high], max_steps_per_launch)[0]
+
+    def evaluate_device_layered(self, h, n_episode, deterministic=True, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.evaluate_device for a LAYERED engine: fsrl_evaluate_device_layered with this one member; nothing is stored."""
+        return evaluate_device_layered([self], [h], n_episode, deterministic, bound_method, None if low is None else [low],
+                                       None if low is None else [high], max_steps_per_launch)[0]
+
     def _collect_device(self, fn, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch):
         steps, cost = C.c_int64(), C.c_double()
         nt, ntr, nep, nl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
@@ -1053,8 +1064,24 @@ def evaluate_device_group(engines, env_handles, n_episodes, deterministic=True, 
     return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch, _store=False)
 
 
+def collect_device_layered(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
+                           max_steps_per_launch=0):
+    """collect_device_group for LAYERED engines (fsrl_collect_device_layered): k members' whole collects in one looping launch of the
+    layered collect kernel, one workgroup per member; one member is the solo collect.  The members share hidden_sizes and may sit in
+    any kind of group or in none.  Arguments and result as collect_device_group."""
+    return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch,
+                                _fn="fsrl_collect_device_layered")
+
+
+def evaluate_device_layered(engines, env_handles, n_episodes, deterministic=True, bound_method=1, lows=None, highs=None,
+                            max_steps_per_launch=0):
+    """evaluate_device_group for LAYERED engines (fsrl_evaluate_device_layered): collect_device_layered that stores nothing."""
+    return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch,
+                                _fn="fsrl_evaluate_device_layered")
+
+
 def collect_device_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
-                         max_steps_per_launch=0, _store=True):
+                         max_steps_per_launch=0, _store=True, _fn=None):
     """Engine.collect_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_collect_device_group):
     member i's collect is Engine.collect_device on it, bit for bit.  The engines may be ungrouped or members of any kind of group.
     env_handles: each engine's devenv handle; n_episodes: one count or one per member; lows / highs: None or one row per member.
@@ -1077,7 +1104,7 @@ def collect_device_group(engines, env_handles, n_episodes, deterministic=False, 
     nt, ntr, nep = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
     ep_rew, ep_len = np.zeros(tot, np.float64), np.zeros(tot, np.int32)
     nl = C.c_int32()
-    _lib.check((lib.fsrl_collect_device_group if _store else lib.fsrl_evaluate_device_group)(
+    _lib.check(getattr(lib, _fn or ("fsrl_collect_device_group" if _store else "fsrl_evaluate_device_group"))(
         ctxs, envs, k, _ptr(n_ep, _i32p), int(bool(deterministic)), int(bound_method), _ptr(lo, _f32p), _ptr(hi, _f32p),
         int(max_steps_per_launch), _ptr(steps, _i64p), _ptr(cost, _f64p), _ptr(nt, _i32p), _ptr(ntr, _i32p), _ptr(ep_rew, _f64p),
         _ptr(ep_len, _i32p), _ptr(nep, _i32p), C.byref(nl)))

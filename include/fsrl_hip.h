@@ -1102,6 +1102,27 @@ int fsrl_evaluate_device_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, c
                                int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
                                int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
                                double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_collect_device_layered / fsrl_evaluate_device_layered   the two _group calls for LAYERED contexts (hidden_sizes of any
+ *                            depth and width, or force_layered): the same arguments, outputs, checks, launch loop, log replay,
+ *                            prioritised-replay launches and reset of all envs at the end, with one looping kernel for every shape
+ *                            in the launch -- a workgroup per member that streams the actor's weights from L2 every vector step and
+ *                            keeps its activations in a workspace of 2 x 64 x round_up(max(widest layer, obs_dim), 4) floats the env
+ *                            owns from its first layered collect on.  Every output element of a layer is accumulated by the MFMA
+ *                            sequence of the layered forward launches, so a deterministic on-policy collect stores the actions
+ *                            fsrl_collect_step computes on the same context, bit for bit; replay contexts agree to float32
+ *                            rounding, as in fsrl_collect_device.  k = 1 is the solo collect (its failures name no member);
+ *                            members may sit in any kind of group or in none.
+ *                            Refused before anything changes: a fused member (the message names fsrl_collect_device /
+ *                            fsrl_evaluate_device, which keep their refusal of layered contexts); members whose hidden_sizes[] or
+ *                            force_layered differ; everything fsrl_collect_device_group / fsrl_evaluate_device_group refuse.  */
+int fsrl_collect_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                              int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                              int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                              double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                               int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                               int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                               double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 
 #ifdef __cplusplus
 }

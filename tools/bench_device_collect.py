@@ -38,6 +38,14 @@ and with --ks the grouped evaluation (GroupDeviceCollector over store-less colle
 evaluations one after the other, aggregate over the k seeds.
 
     python tools/bench_device_collect.py --eval --rounds 3 --ks 1,2,4,8 --out profiles/device_eval.json
+
+A --hidden entry written with x (256x256x256, 64x48x32) is a LAYERED context's hidden_sizes; every mode above takes it, and the
+collectors route it to fsrl_collect_device_layered / fsrl_evaluate_device_layered (lock_step is then the layered EngineGroup's
+lock-step collection, (b) the layered actor's L + 2 launches per vector step).  --layered runs the four legs on such shapes (default
+256x256x256 and 64x48x32) in one process -- the three solo paths on-policy and for one replay agent (--algo, default sacl), the
+grouped seeds (--ks, default 1,2,4,8) and the evaluations -- and writes them into one file:
+
+    python tools/bench_device_collect.py --layered --rounds 3 --out profiles/device_collect_layered.json
 """
 import argparse
 import json
@@ -69,8 +77,25 @@ class Pol:
         self.action_space = Box(-1.0, 1.0, (eng.cfg.act_dim, ))
 
 
+def parse_hidden(text):
+    """'256,64' -> [256, 64] (fused: two layers of that width); entries written with x are a layered context's hidden_sizes"""
+    return [tuple(int(w) for w in h.split("x")) if "x" in h else int(h) for h in text.split(",")]
+
+
+def hidden_kw(hidden):
+    return dict(hidden_sizes=hidden) if isinstance(hidden, tuple) else dict(hidden=hidden)
+
+
+def hidden_list(hidden):
+    return list(hidden) if isinstance(hidden, tuple) else [hidden, hidden]
+
+
+def shape_name(c):
+    return "x".join(str(w) for w in c["hidden"])
+
+
 def setup(path, hidden, n, algo="onpolicy"):
-    kw = dict(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN)
+    kw = dict(obs_dim=8, act_dim=2, env_num=n, buffer_size=n * 2 * EPISODE_LEN, **hidden_kw(hidden))
     if algo == "onpolicy":
         eng = Engine(EngineConfig(**kw), device=0)
         eng.set_params((0.1 * np.random.default_rng(0).standard_normal(eng.n_params)).astype(np.float32))
@@ -129,7 +154,7 @@ def setup_group(path, hidden, n, k):
     from fsrl_amd.data import GroupCollector, GroupDeviceCollector
     engs, envs, cols = [], [], []
     for i in range(k):
-        eng = Engine(EngineConfig(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN), device=0)
+        eng = Engine(EngineConfig(obs_dim=8, act_dim=2, env_num=n, buffer_size=n * 2 * EPISODE_LEN, **hidden_kw(hidden)), device=0)
         eng.set_params((0.1 * np.random.default_rng(i).standard_normal(eng.n_params)).astype(np.float32))
         host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1 + i)
         pol, buf = Pol(eng), HipVectorReplayBuffer(eng, n * 2 * EPISODE_LEN, n)
@@ -182,10 +207,10 @@ def solo_ab(a):
                                check=True, stdout=subprocess.DEVNULL, env=env, cwd=os.path.dirname(os.path.dirname(tool)), timeout=600)
                 with open(out) as f:
                     for c in json.load(f)["configs"]:
-                        rates.setdefault((c["hidden"][0], c["env_num"]), {}).setdefault(who, []).append(c["device"]["median"])
+                        rates.setdefault((shape_name(c), c["env_num"]), {}).setdefault(who, []).append(c["device"]["median"])
     res = []
     for (hidden, n), r in sorted(rates.items(), reverse=True):
-        res.append(dict(hidden=[hidden, hidden], env_num=n, tree=summary(r["tree"]), other=summary(r["other"])))
+        res.append(dict(hidden=[int(w) for w in hidden.split("x")], env_num=n, tree=summary(r["tree"]), other=summary(r["other"])))
         print(json.dumps(res[-1]), flush=True)
     return res
 
@@ -194,7 +219,7 @@ def main_groups(a):
     paths = ("grouped", "solo_seq", "lock_step")
     result = dict(metric="aggregate env-steps/s of k seeds' collects on one GPU, training mode, linear env obs 8 / act 2, episode length 300, "
                          "on-policy contexts", rounds=a.rounds, calls=a.calls, configs=[])
-    for hidden in (int(h) for h in a.hidden.split(",")):
+    for hidden in parse_hidden(a.hidden):
         for n in (int(e) for e in a.envs.split(",")):
             for k in (int(x) for x in a.ks.split(",")):
                 objs = {p: setup_group(p, hidden, n, k) for p in paths}
@@ -203,7 +228,7 @@ def main_groups(a):
                     for p in paths:
                         rows, dt = timed_group(objs[p][3], n, a.calls)
                         rates[p].append(rows / dt)
-                cfg = dict(hidden=[hidden, hidden], env_num=n, k=k, launches_per_collect=objs["grouped"][3].last_launches)
+                cfg = dict(hidden=hidden_list(hidden), env_num=n, k=k, launches_per_collect=objs["grouped"][3].last_launches)
                 for p in paths:
                     cfg[p] = summary(rates[p])
                 result["configs"].append(cfg)
@@ -222,8 +247,9 @@ def main_groups(a):
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
-    print(json.dumps(dict(device_collect_group=[(c["hidden"][0], c["env_num"], c["k"], round(c["grouped"]["median"]), round(c["solo_seq"]["median"]),
+    print(json.dumps(dict(device_collect_group=[(shape_name(c), c["env_num"], c["k"], round(c["grouped"]["median"]), round(c["solo_seq"]["median"]),
                                                  round(c["lock_step"]["median"])) for c in result["configs"]])))
+    return result
 
 
 class EvalPol(Pol):
@@ -238,7 +264,7 @@ def setup_eval(hidden, n, algo):
     host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1)
     Agent = SACLagAgent if algo == "sacl" else PPOLagAgent
     agent = Agent(host, BaseLogger(tf.mkdtemp(prefix="fsrl_amd_bench_"), name="eval"), cost_limit=10, device="cuda:0", seed=1,
-                  hidden_sizes=(hidden, hidden), training_num=n, buffer_size=n * 2 * EPISODE_LEN)
+                  hidden_sizes=tuple(hidden_list(hidden)), training_num=n, buffer_size=n * 2 * EPISODE_LEN)
     pol = agent.policy
     pol.eval()
     envs = [DeviceLinear(pol, like=host, seed=1) for _ in range(3)]
@@ -263,14 +289,14 @@ def main_eval(a):
     algos = ("onpolicy", "sacl") if a.algo == "onpolicy" else (a.algo, )
     result = dict(metric="an evaluation of env_num episodes, policy in eval mode, linear env obs 8 / act 2, episode length 300: episodes/s and "
                          "env-steps/s", rounds=a.rounds, calls=a.calls, configs=[], groups=[])
-    for algo, hidden, n in ((al, int(h), int(e)) for al in algos for h in a.hidden.split(",") for e in a.envs.split(",")):
+    for algo, hidden, n in ((al, h, int(e)) for al in algos for h in parse_hidden(a.hidden) for e in a.envs.split(",")):
         agent, envs, cols = setup_eval(hidden, n, algo)
         steps, eps = {p: [] for p in paths}, {p: [] for p in paths}
         for _ in range(a.rounds):
             for p in paths:
                 rows, ne, dt = timed_eval(cols[p], n, a.calls)
                 steps[p].append(rows / dt); eps[p].append(ne / dt)
-        cfg = dict(algo=algo, hidden=[hidden, hidden], env_num=n, launches_per_evaluation=cols["evaluate"].last_launches)
+        cfg = dict(algo=algo, hidden=hidden_list(hidden), env_num=n, launches_per_evaluation=cols["evaluate"].last_launches)
         for p in paths:
             cfg[p] = dict(env_steps_per_s=summary(steps[p]), episodes_per_s=summary(eps[p]))
         result["configs"].append(cfg)
@@ -280,14 +306,14 @@ def main_eval(a):
         agent.policy.engine.close()
     if a.ks and "onpolicy" in algos:
         from fsrl_amd.data import GroupDeviceCollector
-        for hidden in (int(h) for h in a.hidden.split(",")):
+        for hidden in parse_hidden(a.hidden):
             for n in (int(e) for e in a.envs.split(",")):
                 for k in (int(x) for x in a.ks.split(",")):
                     sets = {}
                     for p in ("grouped", "solo_seq"):
                         engs, envs, cols = [], [], []
                         for i in range(k):
-                            eng = Engine(EngineConfig(obs_dim=8, act_dim=2, hidden=hidden, env_num=n, buffer_size=n * 2 * EPISODE_LEN), device=0)
+                            eng = Engine(EngineConfig(obs_dim=8, act_dim=2, env_num=n, buffer_size=n * 2 * EPISODE_LEN, **hidden_kw(hidden)), device=0)
                             eng.set_params((0.1 * np.random.default_rng(i).standard_normal(eng.n_params)).astype(np.float32))
                             host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1 + i)
                             envs.append(DeviceLinear(eng, like=host, seed=1 + i))
@@ -305,7 +331,7 @@ def main_eval(a):
                         for p in sets:
                             rows, dt = timed_group(sets[p][2], n, a.calls)
                             rates[p].append(rows / dt)
-                    cfg = dict(hidden=[hidden, hidden], env_num=n, k=k, grouped=summary(rates["grouped"]), solo_seq=summary(rates["solo_seq"]))
+                    cfg = dict(hidden=hidden_list(hidden), env_num=n, k=k, grouped=summary(rates["grouped"]), solo_seq=summary(rates["solo_seq"]))
                     result["groups"].append(cfg)
                     print(json.dumps(cfg), flush=True)
                     for engs, envs, _ in sets.values():
@@ -317,8 +343,9 @@ def main_eval(a):
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
-    print(json.dumps(dict(device_eval=[(c["algo"], c["hidden"][0], c["env_num"]) + tuple(round(c[p]["env_steps_per_s"]["median"]) for p in paths)
+    print(json.dumps(dict(device_eval=[(c["algo"], shape_name(c), c["env_num"]) + tuple(round(c[p]["env_steps_per_s"]["median"]) for p in paths)
                                        for c in result["configs"]])))
+    return result
 
 
 def main():
@@ -335,17 +362,48 @@ def main():
     ap.add_argument("--ab-tree", default=None, help="with --ks: another built checkout whose solo device collect this tree's is held against")
     ap.add_argument("--eval", action="store_true", help="measure evaluations: the store-less device evaluation, the host-stepped path it "
                                                         "replaces and a storing collect; with --ks also grouped against solo evaluations")
+    ap.add_argument("--layered", action="store_true", help="the four legs on layered shapes (--hidden entries written with x; default "
+                                                           "256x256x256,64x48x32) in one process, one --out file")
     a = ap.parse_args()
+    if a.layered:
+        return main_layered(a)
     if a.eval:
         return main_eval(a)
     if a.ks:
         return main_groups(a)
+    return main_solo(a)
+
+
+def main_layered(a):
+    if "x" not in a.hidden:
+        a.hidden = "256x256x256,64x48x32"
+    assert all(isinstance(h, tuple) for h in parse_hidden(a.hidden)), "--layered: every --hidden entry is written with x"
+    out, a.out = a.out, None
+    replay = a.algo if a.algo != "onpolicy" else "sacl"
+    result = dict(metric="layered device collects and evaluations (fsrl_collect_device_layered / fsrl_evaluate_device_layered) against the "
+                         "lock-step and stepped paths, linear env obs 8 / act 2, episode length 300; see the legs", rounds=a.rounds, calls=a.calls)
+    a.algo, ks = "onpolicy", a.ks or "1,2,4,8"
+    a.ks = None
+    result["collect"] = main_solo(a)
+    a.algo = replay
+    result["collect_replay"] = main_solo(a)
+    a.algo, a.ks = "onpolicy", ks
+    result["groups"] = main_groups(a)
+    result["eval"] = main_eval(a)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
+
+
+def main_solo(a):
     paths = ("device", "in_process", "stepped")
     result = dict(metric="env-steps/s of a collect loop, training mode, linear env obs 8 / act 2, episode length 300", rounds=a.rounds,
                   calls=a.calls, configs=[])
     if a.algo != "onpolicy":
         result.update(algo=a.algo, update_per_step=a.update_per_step, batch_size=a.batch_size)
-    for hidden in (int(h) for h in a.hidden.split(",")):
+    for hidden in parse_hidden(a.hidden):
         for n in (int(e) for e in a.envs.split(",")):
             objs = {p: setup(p, hidden, n, a.algo) for p in paths}
             rates = {p: [] for p in paths}
@@ -353,7 +411,7 @@ def main():
                 for p in paths:
                     rows, dt = timed(objs[p][2], n, a.calls)
                     rates[p].append(rows / dt)
-            cfg = dict(hidden=[hidden, hidden], env_num=n)
+            cfg = dict(hidden=hidden_list(hidden), env_num=n)
             for p in paths:
                 cfg[p] = dict(median=float(np.median(rates[p])), spread=float(np.max(rates[p]) - np.min(rates[p])), rounds=[float(r) for r in rates[p]])
             # (a) per vector step and per launch: the default steps per launch, and the whole collect in one launch
@@ -391,12 +449,13 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
-    print(json.dumps(dict(device_collect=[(c["hidden"][0], c["env_num"], round(c["device"]["median"]), round(c["in_process"]["median"]),
+    print(json.dumps(dict(device_collect=[(shape_name(c), c["env_num"], round(c["device"]["median"]), round(c["in_process"]["median"]),
                                            round(c["stepped"]["median"])) for c in result["configs"]])))
     if a.algo != "onpolicy":
-        print(json.dumps(dict(algo=a.algo, collect_plus_updates=[(c["hidden"][0], c["env_num"], c["loop"]["updates_per_collect"],
+        print(json.dumps(dict(algo=a.algo, collect_plus_updates=[(shape_name(c), c["env_num"], c["loop"]["updates_per_collect"],
                                                                   round(c["loop"]["device"]["median"]), round(c["loop"]["in_process"]["median"]))
                                                                  for c in result["configs"]])))
+    return result
 
 
 if __name__ == "__main__":
