@@ -132,6 +132,7 @@ SIGNATURES = {
     "fsrl_ppo_set_plan": (C.c_int, [_ctx, C.c_int32]),
     "fsrl_ppo_set_clip_fuse": (C.c_int, [_ctx, C.c_int32, C.c_int32]),
     "fsrl_ppo_clip_fuse_stats": (C.c_int, [_ctx, _i64, _f]),
+    "fsrl_ppo_process_stats": (C.c_int, [_ctx, _i64]),
     "fsrl_batch_get": (C.c_int, [_ctx, C.c_char_p, _f, C.c_int64]),
     "fsrl_group_create": (C.c_int, [_P(_ctx), C.c_int32, _P(_ctx)]),
     "fsrl_group_destroy": (C.c_int, [_ctx]),

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libfsrl_hip.so for gfx950 (cross-compiles without a GPU).  In-tree output so the
 # .so travels to the GPU box with the repo snapshot.
-#   build.sh            -> fsrl_amd/libfsrl_hip.so        (the product: no timing probes; three env switches, FSRL_TILE16, FSRL_NO_W2B_EARLY and FSRL_NO_CLIP_FUSE)
+#   build.sh            -> fsrl_amd/libfsrl_hip.so        (the product: no timing probes; four env switches, FSRL_TILE16, FSRL_NO_W2B_EARLY, FSRL_NO_CLIP_FUSE and FSRL_NO_VNEXT_REUSE)
 #   build.sh --probes   -> fsrl_amd/libfsrl_hip_probe.so  (-DFSRL_PROBES: early-exit phase probes for
 #                          tools/phase_probe.sh; select it with FSRL_HIP_LIB=...; its results are invalid)
 set -euo pipefail

@@ -128,8 +128,18 @@ struct fsrl_ctx {
 
     // batch (sample(0) order)
     BatchPtrs b{};
+    // fsrl_ppo_begin's one upload (host_decisions.hpp: upload_layout): a pinned and a device block of the same layout.  ctrl / h_ctrl lead
+    // them, d_indices / h_indices follow at a fixed offset (the sampler writes in place); d_end, d_seg, d_mbstart and d_mbsize are set per
+    // update.  h_end and h_seg are the host's own copies (pinned as before), copied into the block once n is known.
+    char *d_up = nullptr, *h_up = nullptr;
     int* d_indices = nullptr; uint8_t* d_end = nullptr; int* d_seg = nullptr;
     int* h_indices = nullptr; uint8_t* h_end = nullptr; int* h_seg = nullptr;  // pinned
+    // V(obs_next) from V(obs) (kernels_misc.hpp: batch_gather_flag_kernel, kernels_mlp.hpp: mlp_infer_kernel)
+    uint8_t* next_same = nullptr;      // [alloc_rows]
+    int* miss_list = nullptr;          // [alloc_rows]
+    int* miss_count = nullptr;         // in d_up
+    bool no_vnext_reuse = false;       // every build: FSRL_NO_VNEXT_REUSE evaluates every V(obs_next) row as before (A/B, bit-compare)
+    bool vnext_reuse_active = false;   // the current / last update's process_fn ran with the flags
     float *values = nullptr, *vnext = nullptr, *advs = nullptr, *rets = nullptr, *logp_old = nullptr;
     int64_t N = 0;
     int n_seg = 0;                 // episode segments of the current batch (GAE scan)
@@ -141,8 +151,7 @@ struct fsrl_ctx {
     float *obs_p = nullptr, *rd_p = nullptr;   // pass-ordered batch (+32 pad rows)
     float *statp = nullptr, *gsq_part = nullptr;   // statp is this context's (c->mem) also where lay_ensure_rows regrows it
     int *d_perm = nullptr, *h_perm = nullptr;            // [N] (pinned host)
-    int *d_mbstart = nullptr, *d_mbsize = nullptr, *h_mbplan = nullptr;  // h_mbplan pinned [2*cap]
-    size_t mb_cap = 0;
+    int *d_mbstart = nullptr, *d_mbsize = nullptr;       // in d_up
     std::vector<int> mb_start, mb_size;
     float* d_stats = nullptr; int64_t stats_cap = 0;     // [steps][11]
     int64_t n_steps = 0;
@@ -185,8 +194,9 @@ struct fsrl_ctx {
     int pa_cap = 0;
     void* h_pa = nullptr;           // pinned: [bell 8 B | pad | done[4] at 16 | state[4] at 32 | pad to 64 B | obs cap x Do | mu cap x Da | sigma_param]
     // timing-probe switches: always 0 / false in the shipped library; a -DFSRL_PROBES build reads them ONCE, at
-    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_WGRAD_SKIP / FSRL_NO_SPIN / ... (tools/phase_probe.sh).  Three switches are read by
-    // every build, the shipped library included: FSRL_TILE16 (probe_tile16), FSRL_NO_W2B_EARLY (no_w2b_early) and FSRL_NO_CLIP_FUSE (no_clip_fuse)
+    // fsrl_ctx_create, from FSRL_DBG_PHASE / FSRL_WGRAD_SKIP / FSRL_NO_SPIN / ... (tools/phase_probe.sh).  Four switches are read by
+    // every build, the shipped library included: FSRL_TILE16 (probe_tile16), FSRL_NO_W2B_EARLY (no_w2b_early), FSRL_NO_CLIP_FUSE (no_clip_fuse)
+    // and FSRL_NO_VNEXT_REUSE (no_vnext_reuse)
     int probe_phase = 0, probe_wgrad_skip = 0;
     unsigned long long* probe_ts = nullptr;   // probe builds: [1024][16] phase stamps of the last fused-kernel launch
     bool probe_tile16 = false;
@@ -206,7 +216,8 @@ struct fsrl_ctx {
     int64_t clip_fuse_fallbacks = 0, clip_fuse_steps = 0;   // updates replayed | two-launch steps enqueued
     unsigned clip_epoch = 0;        // tag of the last two-launch step's slots
     unsigned long long* clip_slots = nullptr;     // [1024 x CLIP_SLOT_STRIDE] slot words, zeroed once
-    float* clip_snap = nullptr;     // P (with mirrors) | M | V as fsrl_ppo_begin found them
+    char* clip_snap = nullptr;      // the pmv block (P with mirrors | M | V) as fsrl_ppo_begin found it
+    char* pmv = nullptr; size_t pmv_bytes = 0;      // the one allocation behind P, M and V
     int64_t clip_snap_adam_t = 0;
     std::vector<std::vector<int>> clip_perms;     // every pass's permutation as uploaded
     bool no_xcd_pair = false;       // probe builds: FSRL_NO_XCD_PAIR keeps the tile-major block order of the fused forward/backward launch (A/B)
@@ -611,7 +622,7 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->device = device_id;
     if (device_id >= 0 && device_id < 64) { g_live_ctx[device_id].fetch_add(1); c->counted_live = true; }
     c->n_cus = n_cus_probe > 0 ? n_cus_probe : 256;
-    // the two switches the shipped library reads.  FSRL_TILE16: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
+    // the switches the shipped library reads.  FSRL_TILE16: sixteen-row tiles in every tile launch of this context.  The grouped replay updates
     // run sixteen-row tiles from a few members on; a single context created under FSRL_TILE16 is their exact twin
     // (tests/test_gpu_cvpo_group.py).  Results stay valid, a small batch only gets slower.
     c->probe_tile16 = getenv("FSRL_TILE16") != nullptr;
@@ -620,6 +631,9 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     c->no_w2b_early = getenv("FSRL_NO_W2B_EARLY") != nullptr;
     // FSRL_NO_CLIP_FUSE: the clipped PPO-Lagrangian step keeps its own clip + Adam launch (same bits; A/B runs)
     c->no_clip_fuse = getenv("FSRL_NO_CLIP_FUSE") != nullptr;
+    // FSRL_NO_VNEXT_REUSE: process_fn evaluates V(obs_next) of every row instead of taking it from the V(obs) pass where the rows coincide
+    // (same bits; the twin of tests/test_gpu_ppo_vnext_reuse.py and of A/B runs)
+    c->no_vnext_reuse = getenv("FSRL_NO_VNEXT_REUSE") != nullptr;
 #ifdef FSRL_PROBES
     { const char* e = getenv("FSRL_DBG_PHASE"); c->probe_phase = e ? atoi(e) : 0; }
     { const char* e = getenv("FSRL_WGRAD_SKIP"); c->probe_wgrad_skip = e ? atoi(e) : 0; }
@@ -637,17 +651,23 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     TRY(hipStreamCreateWithFlags(&c->compute, hipStreamNonBlocking));
     TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     const size_t pb = (size_t)c->n_dev * sizeof(float);
-    TRY(c->mem.dev(&c->P, (size_t)c->n_alloc * sizeof(float))); TRY(hipMemsetAsync(c->P, 0, (size_t)c->n_alloc * sizeof(float), c->compute));
-    TRY(c->mem.dev(&c->M, pb)); TRY(c->mem.dev(&c->V, pb)); TRY(c->mem.dev(&c->G, pb));
-    TRY(hipMemsetAsync(c->M, 0, pb, c->compute)); TRY(hipMemsetAsync(c->V, 0, pb, c->compute)); TRY(hipMemsetAsync(c->G, 0, pb, c->compute));
-    TRY(c->mem.dev(&c->ctrl, sizeof(CtrlBlock)));
+    // P (with mirrors) | M | V in ONE allocation, each on 256 bytes: the snapshot of the two-launch clipped step is one copy (clip_fuse_begin).
+    // Everything else keeps addressing them through c->P, c->M, c->V.
+    {
+        auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t pbytes = al((size_t)c->n_alloc * sizeof(float));
+        c->pmv_bytes = pbytes + 2 * al(pb);
+        TRY(c->mem.dev(&c->pmv, c->pmv_bytes)); TRY(hipMemsetAsync(c->pmv, 0, c->pmv_bytes, c->compute));
+        c->P = reinterpret_cast<float*>(c->pmv); c->M = reinterpret_cast<float*>(c->pmv + pbytes);
+        c->V = reinterpret_cast<float*>(c->pmv + pbytes + al(pb));
+    }
+    TRY(c->mem.dev(&c->G, pb)); TRY(hipMemsetAsync(c->G, 0, pb, c->compute));
     if (cfg->rew_norm) {      // RunningMeanStd(): mean 0, var 1, count 0 per critic
         TRY(c->mem.dev(&c->d_rms, 3 * FSRL_MAX_CRITICS * sizeof(double)));
         double init[3 * FSRL_MAX_CRITICS];
         for (int i = 0; i < FSRL_MAX_CRITICS; ++i) { init[3 * i] = 0.0; init[3 * i + 1] = 1.0; init[3 * i + 2] = 0.0; }
         TRY(hipMemcpy(c->d_rms, init, sizeof(init), hipMemcpyHostToDevice));
     }
-    TRY(c->mem.pinned(&c->h_ctrl, sizeof(CtrlBlock)));
     // store: n sub-buffers of ceil(total/n) rows (tianshou VectorReplayBuffer)
     c->sub_size = (cfg->buffer_size + cfg->env_num - 1) / cfg->env_num;
     c->maxsize = c->sub_size * cfg->env_num;
@@ -663,8 +683,18 @@ extern "C" int fsrl_ctx_create(int device_id, const fsrl_config* cfg, fsrl_ctx**
     TRY(c->mem.dev(&c->b.obs, ms * Do * 4)); TRY(c->mem.dev(&c->b.obs_next, ms * Do * 4));
     TRY(c->mem.dev(&c->b.act, ms * Da * 4)); TRY(c->mem.dev(&c->b.rew, ms * 8));
     TRY(c->mem.dev(&c->b.cost, ms * 8)); TRY(c->mem.dev(&c->b.flags, ms));
-    TRY(c->mem.dev(&c->d_indices, ms * 4)); TRY(c->mem.dev(&c->d_end, ms)); TRY(c->mem.dev(&c->d_seg, (ms + 2) * 4));
-    TRY(c->mem.pinned(&c->h_indices, ms * 4)); TRY(c->mem.pinned(&c->h_end, ms)); TRY(c->mem.pinned(&c->h_seg, (ms + 2) * 4));
+    static_assert(sizeof(CtrlBlock) <= 64, "the control block leads the upload block: 64 bytes");
+    TRY(c->mem.dev(&c->d_up, upload_capacity(ms))); TRY(c->mem.pinned(&c->h_up, upload_capacity(ms)));
+    TRY(hipMemsetAsync(c->d_up, 0, upload_capacity(ms), c->compute));
+    memset(c->h_up, 0, upload_capacity(ms));
+    {
+        const UploadLayout u = upload_layout(ms, ms, ms);
+        c->ctrl = (CtrlBlock*)(c->d_up + u.ctrl); c->h_ctrl = (CtrlBlock*)(c->h_up + u.ctrl);
+        c->miss_count = (int*)(c->d_up + u.miss_count);
+        c->d_indices = (int*)(c->d_up + u.indices); c->h_indices = (int*)(c->h_up + u.indices);
+    }
+    TRY(c->mem.pinned(&c->h_end, ms)); TRY(c->mem.pinned(&c->h_seg, (ms + 2) * 4));
+    TRY(c->mem.dev(&c->next_same, ms)); TRY(c->mem.dev(&c->miss_list, ms * 4));
     const int C = cfg->n_critics;
     TRY(c->mem.dev(&c->values, ms * C * 4)); TRY(c->mem.dev(&c->vnext, ms * C * 4));
     TRY(c->mem.dev(&c->advs, ms * C * 4)); TRY(c->mem.dev(&c->rets, ms * C * 4));
@@ -1038,8 +1068,7 @@ static int launch_infer(fsrl_ctx* c, const InferArgs& ia, int jobs_y, hipStream_
     if (c->lay) return lay_infer(c, ia, jobs_y, s);
     return dispatch_H(c->cfg.hidden, [&](auto hc) {
         constexpr int H = decltype(hc)::value;
-        // persistent over tiles: about one workgroup per CU in total (their LDS footprint allows no more)
-        const int gx = std::min(tiles, std::max(1, c->n_cus / jobs_y));
+        const int gx = infer_grid_x(tiles, c->n_cus, jobs_y);
         hipLaunchKernelGGL(mlp_infer_kernel<H>, dim3(gx, jobs_y), dim3(4 * H), 0, s, c->P, c->md, ia);
         HIPCHK(hipGetLastError());
         return 0;

@@ -202,3 +202,67 @@ struct ClipFuseReplay { long long adam_t, n_steps; int pass_index, passes; };
 static inline ClipFuseReplay clip_fuse_replay_plan(long long snap_adam_t, int passes_enqueued) {
     return {snap_adam_t, 0, 0, passes_enqueued};
 }
+
+// ---- process_fn: V(obs_next) from V(obs).  In an on-policy store obs_next[t] is obs[t + 1] unless the episode ended or the ring wrapped,
+// so the value job of row r + 1 also gives vnext[r] where the two rows' words are bitwise equal (next_same[r], written next to the gather);
+// the "next" jobs of mlp_infer_kernel walk only the compacted list of the other rows ("misses").  The split of the launch's workgroups over
+// its jobs is decided IN the kernel from the device-side miss count (no host synchronisation); the host calls the same function for its
+// counters and the tests.  gx x jobs_y: the launch grid (jobs_y = 2 C + 1 with the actor job, 2 C without), C next jobs, jobs_y - C full
+// jobs of n_tiles 16-row tiles, miss_tiles tiles of listed rows per next job.
+//   bn workgroups per next job, bf per full job, C * bn + (jobs_y - C) * bf <= gx * jobs_y; the workgroups left over exit at once.
+//   The workgroups are shared out in proportion to the tiles: bn = ceil(T * m / (F * n + C * m)), at most gx and at most m.  A store whose
+//   rows never coincide (m = n) gives bn = bf = gx, the equal split of a launch without reuse.
+#if defined(__HIPCC__)
+#define FSRL_HD __host__ __device__
+#else
+#define FSRL_HD
+#endif
+// persistent over tiles: about one workgroup per CU in total (their LDS footprint allows no more), gx per job
+static inline int infer_grid_x(int tiles, int n_cus, int jobs_y) { return std::min(tiles, std::max(1, n_cus / jobs_y)); }
+struct InferSplit { int bn, bf, equal; };
+FSRL_HD static inline InferSplit infer_split(int gx, int jobs_y, int C, int n_tiles, int miss_tiles) {
+    const int F = jobs_y - C, T = gx * jobs_y;
+    InferSplit s{0, 0, 0};
+    if (miss_tiles > 0) {
+        const long long den = (long long)F * n_tiles + (long long)C * miss_tiles;
+        long long bn = ((long long)T * miss_tiles + den - 1) / den;
+        if (bn > gx) bn = gx;
+        if (bn > miss_tiles) bn = miss_tiles;
+        if (bn < 1) bn = 1;
+        s.bn = (int)bn;
+    }
+    if (s.bn == gx) { s.bf = gx; s.equal = 1; return s; }
+    s.bf = (T - C * s.bn) / F;
+    if (s.bf > n_tiles) s.bf = n_tiles;
+    return s;
+}
+// the host's count of the rows whose obs_next is the next batch row's obs, word for word (tests; the device flags the same rows)
+static inline int next_same_count(const uint32_t* obs, const uint32_t* obs_next, int n, int Do) {
+    int same = 0;
+    for (int r = 0; r + 1 < n; ++r) {
+        bool eq = true;
+        for (int k = 0; k < Do && eq; ++k) eq = obs_next[(size_t)r * Do + k] == obs[(size_t)(r + 1) * Do + k];
+        same += eq ? 1 : 0;
+    }
+    return same;
+}
+
+// ---- fsrl_ppo_begin's one upload: everything the device needs from the host for an update in one pinned block, one device block of
+// the same layout and one copy.  Byte offsets; every array starts on 64 bytes.  The control block leads (its device address never
+// moves), the miss counter of the V(obs_next) reuse follows it (uploaded as 0), then the sample(0) indices -- written in place by the
+// sampler, before n is known to anybody else, which is why they come first -- the end flags, the GAE segment starts and the minibatch plan.
+struct UploadLayout { size_t ctrl, miss_count, indices, end, seg, mb_start, mb_size, total; };
+static constexpr size_t UPLOAD_HEAD = 128;            // control block (<= 64 bytes) | miss counter
+static inline size_t upload_align(size_t x) { return (x + 63) / 64 * 64; }
+static inline UploadLayout upload_layout(size_t n, size_t n_seg, size_t n_mb) {
+    UploadLayout u{};
+    u.ctrl = 0; u.miss_count = 64; u.indices = UPLOAD_HEAD;
+    u.end = u.indices + upload_align(n * 4);
+    u.seg = u.end + upload_align(n);
+    u.mb_start = u.seg + upload_align((n_seg + 1) * 4);
+    u.mb_size = u.mb_start + upload_align(n_mb * 4);
+    u.total = u.mb_size + upload_align(n_mb * 4);
+    return u;
+}
+// capacity of the two blocks for a store of `rows` rows: at most `rows` segments and `rows` minibatches
+static inline size_t upload_capacity(size_t rows) { return upload_layout(rows, rows, rows).total; }

@@ -77,34 +77,64 @@ extern "C" int fsrl_ppo_begin(fsrl_ctx* c, const double* lagrangians, double res
     c->t_fwdbwd_ms = 0; c->n_fwdbwd = 0; c->k_ev_used = 0;
     CtrlBlock init{INT_MAX, 0, 0.0, 0.0f, 0.0f};
     *c->h_ctrl = init;
+    *reinterpret_cast<int*>(c->h_up + upload_layout(0, 0, 0).miss_count) = 0;
     hipStream_t s = c->compute;
-    HIPCHK(hipMemcpyAsync(c->ctrl, c->h_ctrl, sizeof(CtrlBlock), hipMemcpyHostToDevice, s));
     c->clip_fuse_active = false;
+    c->vnext_reuse_active = false;
     c->clip_perms.clear();
-    if (n == 0) { c->batch_ready = true; return 0; }
-    rc = clip_fuse_begin(c);
-    if (rc) return rc;
+    if (n == 0) {               // the head alone: control block + miss counter
+        HIPCHK(hipMemcpyAsync(c->d_up, c->h_up, UPLOAD_HEAD, hipMemcpyHostToDevice, s));
+        c->batch_ready = true;
+        return 0;
+    }
     // episode segments for the GAE scan
     int nseg = 0;
     c->h_seg[nseg++] = 0;
     for (int64_t i = 0; i + 1 < n; ++i) if (c->h_end[i]) c->h_seg[nseg++] = (int)i + 1;
     c->h_seg[nseg] = (int)n;
+    // ---- minibatch plan of every pass (same for all passes)
+    split_plan((int)n, batch_size, c->mb_start, c->mb_size);
+    // working set of one minibatch: never more rows than the batch has (CPO / TRPO-Lag begin with batch_size = 2^20 = "the
+    // whole batch": sized by that, the four activation arrays alone were 25 GB)
+    const int bs_rows = (int)std::min<int64_t>(batch_size, std::max<int64_t>(n, 1));
+    rc = c->lay ? lay_ensure_mb(c, bs_rows) : ensure_ppo_buffers(c, bs_rows);
+    if (rc) return rc;
+    // ---- the one upload: control block, miss counter, indices (in place since sample0), end flags, segments, minibatch plan
+    const size_t nmb = c->mb_start.size();
+    const UploadLayout u = upload_layout((size_t)n, (size_t)nseg, nmb);
+    memcpy(c->h_up + u.end, c->h_end, (size_t)n);
+    memcpy(c->h_up + u.seg, c->h_seg, (size_t)(nseg + 1) * 4);
+    memcpy(c->h_up + u.mb_start, c->mb_start.data(), nmb * 4);
+    memcpy(c->h_up + u.mb_size, c->mb_size.data(), nmb * 4);
+    c->d_end = reinterpret_cast<uint8_t*>(c->d_up + u.end); c->d_seg = reinterpret_cast<int*>(c->d_up + u.seg);
+    c->d_mbstart = reinterpret_cast<int*>(c->d_up + u.mb_start); c->d_mbsize = reinterpret_cast<int*>(c->d_up + u.mb_size);
+    rc = clip_fuse_begin(c);
+    if (rc) return rc;
     HIPCHK(hipEventRecord(c->ev_a, s));
-    HIPCHK(hipMemcpyAsync(c->d_indices, c->h_indices, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_end, c->h_end, (size_t)n, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_seg, c->h_seg, (size_t)(nseg + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->d_up, c->h_up, u.total, hipMemcpyHostToDevice, s));
     const int Do = c->cfg.obs_dim, Da = c->cfg.act_dim;
+    // V(obs_next) from V(obs) where the rows coincide: the fused PPO-Lagrangian contexts (layered contexts and the other algorithms run
+    // process_fn as before)
+    const bool reuse = !c->no_vnext_reuse && !c->lay && c->cfg.algo == FSRL_ALGO_PPO_LAG && c->cfg.n_critics >= 1;
     {
         const size_t work = (size_t)n * (2 * Do + Da + 1);
         const int blocks = (int)std::min<size_t>(2048, (work + 255) / 256);
-        hipLaunchKernelGGL(batch_gather_kernel, dim3(blocks), dim3(256), 0, s, c->st, c->b, c->d_indices,
-                           c->d_end, (int)n, Do, Da);
+        if (reuse) {
+            const int fblocks = (int)((n + 255) / 256);
+            hipLaunchKernelGGL(batch_gather_flag_kernel, dim3(blocks + fblocks), dim3(256), 0, s, c->st, c->b, c->d_indices,
+                               c->d_end, (int)n, Do, Da, blocks, NextSamePtrs{c->next_same, c->miss_list, c->miss_count});
+        } else {
+            hipLaunchKernelGGL(batch_gather_kernel, dim3(blocks), dim3(256), 0, s, c->st, c->b, c->d_indices,
+                               c->d_end, (int)n, Do, Da);
+        }
         HIPCHK(hipGetLastError());
     }
+    c->vnext_reuse_active = reuse;
     // ---- process_fn: V_i(obs), V_i(obs_next)*~terminated, logp_old, then float64 GAE per critic
     InferArgs ia{};
     ia.obs = c->b.obs; ia.obs_next = c->b.obs_next; ia.act = c->b.act; ia.flags = c->b.flags;
     ia.values = c->values; ia.vnext = c->vnext; ia.logp_old = c->logp_old; ia.mu_out = nullptr;
+    if (reuse) { ia.next_same = c->next_same; ia.miss_list = c->miss_list; ia.miss_count = c->miss_count; }
     if (c->cfg.algo == FSRL_ALGO_FOCOPS) {      // old distribution of the pass batches: means + sigma_param snapshot
         if (!c->mu_old) {
             HIPCHK(c->mem.dev(&c->mu_old, (size_t)c->alloc_rows * Da * 4));
@@ -120,23 +150,6 @@ extern "C" int fsrl_ppo_begin(fsrl_ctx* c, const double* lagrangians, double res
     rc = launch_gae(c);
     if (rc) return rc;
     HIPCHK(hipEventRecord(c->ev_b, s));
-    // ---- minibatch plan of every pass (same for all passes)
-    split_plan((int)n, batch_size, c->mb_start, c->mb_size);
-    // working set of one minibatch: never more rows than the batch has (CPO / TRPO-Lag begin with batch_size = 2^20 = "the
-    // whole batch": sized by that, the four activation arrays alone were 25 GB)
-    const int bs_rows = (int)std::min<int64_t>(batch_size, std::max<int64_t>(n, 1));
-    rc = c->lay ? lay_ensure_mb(c, bs_rows) : ensure_ppo_buffers(c, bs_rows);
-    if (rc) return rc;
-    const size_t nmb = c->mb_start.size();
-    if (nmb > c->mb_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        const size_t cap = nmb * 2;
-        HIPCHK(c->mem.regrow(c->mb_cap, nmb, cap, {Mem::D(&c->d_mbstart, cap * 4), Mem::D(&c->d_mbsize, cap * 4), Mem::H(&c->h_mbplan, cap * 2 * 4)}));
-    }
-    memcpy(c->h_mbplan, c->mb_start.data(), nmb * 4);
-    memcpy(c->h_mbplan + c->mb_cap, c->mb_size.data(), nmb * 4);
-    HIPCHK(hipMemcpyAsync(c->d_mbstart, c->h_mbplan, nmb * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->d_mbsize, c->h_mbplan + c->mb_cap, nmb * 4, hipMemcpyHostToDevice, s));
     c->batch_ready = true;
     return 0;
 }
@@ -173,6 +186,8 @@ static int ppo_recompute_advantages(fsrl_ctx* c) {
     ia.obs = c->b.obs; ia.obs_next = c->b.obs_next; ia.act = nullptr; ia.flags = c->b.flags;
     ia.values = c->values; ia.vnext = c->vnext; ia.logp_old = nullptr; ia.mu_out = nullptr;
     ia.N = (int)c->N; ia.C = C; ia.max_action = c->cfg.max_action;
+    // the batch has not changed since fsrl_ppo_begin: its flags and its list of misses still hold
+    if (c->vnext_reuse_active) { ia.next_same = c->next_same; ia.miss_list = c->miss_list; ia.miss_count = c->miss_count; }
     int rc = launch_infer(c, ia, 2 * C, c->compute);          // jobs 0 .. 2C-1: the critics (job 2C would be the actor)
     if (rc) return rc;
     return launch_gae(c);
@@ -461,7 +476,7 @@ static int ppo_pass_enqueue(fsrl_ctx* c, const int64_t* perm, uint64_t seed, con
 }
 
 // ---- the two-launch clipped step's host side.  fsrl_ppo_begin decides (host_decisions.hpp: clip_fuse_update_ok) and snapshots P, M, V:
-// three device-to-device copies on the compute stream, next to process_fn, which writes none of them.  Every read of the control block (pass_verdict,
+// one device-to-device copy of their shared allocation on the compute stream, next to process_fn, which writes none of them.  Every read of the control block (pass_verdict,
 // fsrl_ppo_pass_result, fsrl_ppo_end) looks at `poisoned`: a block of some weight-gradient launch gave up waiting for the others.
 static int clip_fuse_begin(fsrl_ctx* c) {
     ClipFuseFacts f{};
@@ -477,10 +492,8 @@ static int clip_fuse_begin(fsrl_ctx* c) {
         HIPCHK(c->mem.dev(&c->clip_slots, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(c->clip_slots, 0, (size_t)1024 * CLIP_SLOT_STRIDE * sizeof(unsigned long long), s));
     }
-    if (!c->clip_snap) HIPCHK(c->mem.dev(&c->clip_snap, ((size_t)c->n_alloc + 2 * (size_t)c->n_dev) * 4));
-    HIPCHK(hipMemcpyAsync(c->clip_snap, c->P, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc, c->M, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->clip_snap + c->n_alloc + c->n_dev, c->V, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    if (!c->clip_snap) HIPCHK(c->mem.dev(&c->clip_snap, c->pmv_bytes));
+    HIPCHK(hipMemcpyAsync(c->clip_snap, c->pmv, c->pmv_bytes, hipMemcpyDeviceToDevice, s));      // P, M and V share one allocation
     c->clip_snap_adam_t = c->adam_t;
     c->clip_fuse_active = true;
     return 0;
@@ -493,9 +506,7 @@ static int clip_fuse_check(fsrl_ctx* c) {
     const ClipFuseReplay rp = clip_fuse_replay_plan(c->clip_snap_adam_t, c->pass_index);
     c->clip_fuse_active = false; c->clip_fuse_dead = true;
     c->clip_fuse_fallbacks += 1;
-    HIPCHK(hipMemcpyAsync(c->P, c->clip_snap, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->M, c->clip_snap + c->n_alloc, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(c->V, c->clip_snap + c->n_alloc + c->n_dev, (size_t)c->n_dev * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->pmv, c->clip_snap, c->pmv_bytes, hipMemcpyDeviceToDevice, s));
     c->adam_t = rp.adam_t; c->n_steps = rp.n_steps; c->pass_index = rp.pass_index;
     c->k_ev_used = 0;
     CtrlBlock init{INT_MAX, 0, 0.0, 0.0f, 0.0f};
@@ -537,6 +548,24 @@ extern "C" int fsrl_ppo_clip_fuse_stats(fsrl_ctx* c, int64_t* out, float* grad_n
     }
     out[0] = (c->clip_fuse_mode != 0 && !c->no_clip_fuse && !c->clip_fuse_dead) ? 1 : 0;
     out[1] = c->clip_fuse_fallbacks; out[2] = c->clip_fuse_steps; out[3] = c->clip_fuse_active ? 1 : 0;
+    return 0;
+}
+
+// process_fn of the last fsrl_ppo_begin (between launches or updates; waits for the compute stream): out[0] = batch rows whose V(obs_next) the
+// V(obs) pass gave, out[1] = rows the next jobs evaluated (per critic; out[0] + out[1] = N), out[2] = 1 if the launch ran the equal split,
+// out[3] = 1 if the reuse was on (0: FSRL_NO_VNEXT_REUSE, a layered context or another algorithm -- then out[1] = N and out[2] = 1)
+extern "C" int fsrl_ppo_process_stats(fsrl_ctx* c, int64_t* out) {
+    CHECK_ARG(c && out, "null argument");
+    if (!c->batch_ready) return fail(FSRL_ESTATE, "no batch: call fsrl_ppo_begin first");
+    ENTER_DEV(c);
+    out[0] = 0; out[1] = c->N; out[2] = 1; out[3] = c->vnext_reuse_active ? 1 : 0;
+    if (!c->vnext_reuse_active || c->N == 0) return 0;
+    int m = 0;
+    HIPCHK(hipStreamSynchronize(c->compute));
+    HIPCHK(hipMemcpy(&m, c->miss_count, sizeof(int), hipMemcpyDeviceToHost));
+    const int tiles = (int)((c->N + 15) / 16), jobs_y = 2 * c->cfg.n_critics + 1;
+    const InferSplit sp = infer_split(infer_grid_x(tiles, c->n_cus, jobs_y), jobs_y, c->cfg.n_critics, tiles, (m + 15) / 16);
+    out[0] = c->N - m; out[1] = m; out[2] = sp.equal;
     return 0;
 }
 

@@ -43,11 +43,12 @@ struct BatchPtrs {
     float* obs; float* obs_next; float* act; double* rew; double* cost; uint8_t* flags;
 };
 
-__global__ void batch_gather_kernel(StorePtrs st, BatchPtrs b, const int* __restrict__ indices,
-                                    const uint8_t* __restrict__ end_flag, int n, int Do, int Da) {
+// block `bx` of `nb` gathering blocks
+__device__ __forceinline__ void batch_gather_body(const StorePtrs& st, const BatchPtrs& b, const int* __restrict__ indices,
+                                                  const uint8_t* __restrict__ end_flag, int n, int Do, int Da, int bx, int nb) {
     const int per = 2 * Do + Da + 1;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)n * per;
-         e += (size_t)gridDim.x * blockDim.x) {
+    for (size_t e = (size_t)bx * blockDim.x + threadIdx.x; e < (size_t)n * per;
+         e += (size_t)nb * blockDim.x) {
         const int row = (int)(e / per), f = (int)(e - (size_t)row * per);
         const size_t src = (size_t)indices[row];
         if (f < Do) b.obs[(size_t)row * Do + f] = st.obs[src * Do + f];
@@ -57,6 +58,51 @@ __global__ void batch_gather_kernel(StorePtrs st, BatchPtrs b, const int* __rest
             b.rew[row] = st.rew[src];
             b.cost[row] = st.cost[src];
             b.flags[row] = (uint8_t)((st.flags[src] & 3) | (end_flag[row] ? 4 : 0));
+        }
+    }
+}
+__global__ void batch_gather_kernel(StorePtrs st, BatchPtrs b, const int* __restrict__ indices,
+                                    const uint8_t* __restrict__ end_flag, int n, int Do, int Da) {
+    batch_gather_body(st, b, indices, end_flag, n, Do, Da, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The gather of fsrl_ppo_begin with a sibling in the same launch: blocks [0, gather_blocks) gather, the others flag the rows whose
+// V(obs_next) the value pass of the NEXT batch row gives (mlp_infer_kernel):  next_same[r] = 1 iff r + 1 < n and the Do words of
+// st.obs_next[indices[r]] and st.obs[indices[r + 1]] are equal as uint32 (-0.0 != +0.0, NaNs by payload); the last row is always 0.
+// The other rows ("misses") are appended to miss_list, one atomic per wave; *miss_count is 0 when the launch starts (it travels with
+// the update's upload) and the number of misses when it ends.  Order within the list: whatever the atomics give.
+// One thread per row, every word read (no early exit: the loads of a row stay independent of each other).
+struct NextSamePtrs { uint8_t* next_same; int* miss_list; int* miss_count; };
+__global__ __launch_bounds__(256) void batch_gather_flag_kernel(StorePtrs st, BatchPtrs b, const int* __restrict__ indices,
+                                                                const uint8_t* __restrict__ end_flag, int n, int Do, int Da,
+                                                                int gather_blocks, NextSamePtrs ns) {
+    if ((int)blockIdx.x < gather_blocks) {
+        batch_gather_body(st, b, indices, end_flag, n, Do, Da, (int)blockIdx.x, gather_blocks);
+        return;
+    }
+    const int fb = (int)blockIdx.x - gather_blocks, nfb = (int)gridDim.x - gather_blocks, lane = threadIdx.x & 63;
+    const uint32_t* __restrict__ so = reinterpret_cast<const uint32_t*>(st.obs);
+    const uint32_t* __restrict__ sn = reinterpret_cast<const uint32_t*>(st.obs_next);
+    for (int r0 = fb * 256; r0 < n; r0 += nfb * 256) {       // r0 is uniform for the block: whole waves reach the ballot
+        const int r = r0 + (int)threadIdx.x;
+        bool miss = false;
+        if (r < n) {
+            miss = true;
+            if (r + 1 < n) {
+                const uint32_t* __restrict__ x = sn + (size_t)indices[r] * Do;
+                const uint32_t* __restrict__ y = so + (size_t)indices[r + 1] * Do;
+                uint32_t d = 0;
+                for (int k = 0; k < Do; ++k) d |= x[k] ^ y[k];
+                miss = d != 0;
+            }
+            ns.next_same[r] = miss ? 0 : 1;
+        }
+        const unsigned long long m = __ballot(miss);
+        if (m) {
+            int base = 0;
+            if (lane == __ffsll((long long)m) - 1) base = atomicAdd(ns.miss_count, __popcll(m));
+            base = __shfl(base, __ffsll((long long)m) - 1, 64);
+            if (miss) ns.miss_list[base + __popcll(m & ((1ull << lane) - 1ull))] = r;
         }
     }
 }

@@ -20,6 +20,7 @@
 #pragma once
 #include <type_traits>
 #include "common.hpp"
+#include "host_decisions.hpp"      // infer_split: mlp_infer_kernel and the host share the rule
 
 // rows a tile of R rows needs room for: 4-, 8- and 16-row tiles share the 16-row layout, a 32-row tile (two 16-row MFMA
 // passes per weight fragment: half the L2 -> register weight traffic per row) has its own
@@ -428,6 +429,12 @@ struct InferArgs {
     float* sigma_param_out; // optional [Da]: the actor's sigma_param (collector: one launch, no extra copy)
     unsigned* done;         // optional [gridDim.x] in pinned host memory: block b stores `seq` here after its outputs are
     unsigned seq;           //   visible system-wide -- the collector spins on these instead of a stream synchronisation
+    // V(obs_next) from V(obs) (fsrl_ppo_begin / recompute_advantage; null for every other caller, which runs the equal split over all rows):
+    // next_same[r] = 1: obs_next[r] is obs[r + 1] word for word, so value job c also stores vnext[c][r] when it has V_c(obs[r + 1]); the next
+    // jobs evaluate only the *miss_count rows of miss_list.  The workgroups are shared out by infer_split (host_decisions.hpp).
+    const uint8_t* next_same;   // [N]
+    const int* miss_list;       // [*miss_count] batch rows, any order
+    const int* miss_count;
 };
 
 #define LOG_SQRT_2PI 0.9189385332046727f
@@ -443,35 +450,56 @@ __global__ __launch_bounds__(4 * H) void mlp_infer_kernel(const float* __restric
     constexpr int NT = TileGeom<H>::NT;
     constexpr int NX = TileStage<H>::NX;
     const int tid = threadIdx.x;
-    const int job = blockIdx.y;
     const int C = a.C;
+    int job = blockIdx.y, bx = blockIdx.x, gx = gridDim.x;
+    int n_rows = a.N;                             // rows of this job: the batch, or the listed rows of a next job under reuse
+    const int* __restrict__ list = nullptr;       // a next job under reuse: its rows
+    if (a.next_same) {                            // kernel-uniform; the split is the same in every workgroup (one device count)
+        const int m = *a.miss_count;
+        const InferSplit sp = infer_split((int)gridDim.x, (int)gridDim.y, C, (a.N + 15) >> 4, (m + 15) >> 4);
+        const int lb = (int)(blockIdx.y * gridDim.x + blockIdx.x), nb = C * sp.bn;
+        if (lb < nb) { job = C + lb / sp.bn; bx = lb % sp.bn; gx = sp.bn; list = a.miss_list; n_rows = m; }
+        else {
+            const int f = (lb - nb) / sp.bf;      // full jobs: V_0 .. V_{C-1}(obs), then the actor if the launch has it
+            if (f >= (int)gridDim.y - C) return;
+            bx = (lb - nb) % sp.bf; gx = sp.bf; job = f < C ? f : 2 * C;
+        }
+    }
     const bool is_actor = (job == 2 * C);
     const int net = is_actor ? 0 : 1 + (C > 0 ? job % C : 0);
     const bool use_next = (!is_actor) && job >= C;
     const NetOff no = md.net[net];
     const int Do = md.Do;
-    const int n_tiles = (a.N + 15) >> 4;
+    const int n_tiles = (n_rows + 15) >> 4;
     const unsigned magic = div_magic(Do);      // e / Do as a multiply-high (exact for e < 2^16)
     const float* __restrict__ X = use_next ? a.obs_next : a.obs;
-    int tile = blockIdx.x;
+    int tile = bx;
     int row0 = tile * 16;
-    int n_valid = min(16, a.N - row0);
+    int n_valid = min(16, n_rows - row0);
+    // element e of the tile whose first row is r0 (nv rows): contiguous rows, or the listed rows gathered
+    auto xload = [&](const int e, const int r0, const int nv) -> float {
+        if (e >= nv * Do) return 0.0f;
+        if (!list) return X[(size_t)r0 * Do + e];
+        const int i = div_by_magic((unsigned)e, magic), k = e - i * Do;
+        return X[(size_t)list[r0 + i] * Do + k];
+    };
     TileStage<H> stg;
-    stg.issue(P, no, Do, md.Da, X + (size_t)row0 * Do, nullptr, n_valid, tid);
+    stg.issue(P, no, Do, md.Da, list ? X : X + (size_t)row0 * Do, nullptr, list ? 0 : n_valid, tid);
+    if (list) {
+#pragma unroll
+        for (int u = 0; u < NX; ++u) stg.xv[u] = xload(tid + u * NT, row0, n_valid);
+    }
     FwdW2Frag<H> wf;
     wf.load(P + no.W2f, tid >> 6, tid & 63);
     stg.commit(sm, no, Do, tid);
     while (true) {
         // prefetch the next tile's observations (registers), consumed after this tile's epilogue
-        const int ntile = tile + gridDim.x;
-        const int nrow0 = ntile * 16, nn_valid = min(16, a.N - nrow0);
+        const int ntile = tile + gx;
+        const int nrow0 = ntile * 16, nn_valid = min(16, n_rows - nrow0);
         float xn[NX];
         if (ntile < n_tiles) {
 #pragma unroll
-            for (int u = 0; u < NX; ++u) {
-                const int e = tid + u * NT;
-                xn[u] = (e < nn_valid * Do) ? X[(size_t)nrow0 * Do + e] : 0.0f;      // rows are contiguous
-            }
+            for (int u = 0; u < NX; ++u) xn[u] = xload(tid + u * NT, nrow0, nn_valid);
         }
         __syncthreads();
         tile_forward<H>(sm, P, no, Do, tid, wf);
@@ -482,7 +510,7 @@ __global__ __launch_bounds__(4 * H) void mlp_infer_kernel(const float* __restric
                 a.raw_out[(size_t)(row0 + i) * a.raw_cols + o] = sm.out[i * FSRL_MAX_ACT + o];
             }
         } else if (tid < n_valid) {
-            const int r = row0 + tid;
+            const int r = list ? list[row0 + tid] : row0 + tid;
             if (!is_actor) {
                 float v = sm.out[tid * FSRL_MAX_ACT];
                 const int c = (C > 0) ? job % C : 0;
@@ -491,6 +519,8 @@ __global__ __launch_bounds__(4 * H) void mlp_infer_kernel(const float* __restric
                     a.vnext[(size_t)c * a.N + r] = v;
                 } else {
                     a.values[(size_t)c * a.N + r] = v;
+                    // the same network on the same words: V_c(obs_next[r - 1]) bit for bit
+                    if (a.next_same && r > 0 && a.next_same[r - 1]) a.vnext[(size_t)c * a.N + r - 1] = (a.flags[r - 1] & 1) ? 0.0f : v;
                 }
             } else {
                 float logp = 0.0f;

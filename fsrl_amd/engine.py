@@ -567,6 +567,13 @@ class Engine:
         return dict(available=bool(out[0]), fallbacks=int(out[1]), steps=int(out[2]), last_update_fused=bool(out[3]),
                     grad_norm=np.float32(gn.value))
 
+    def ppo_process_stats(self):
+        """process_fn of the last ppo_begin -> dict(rows_reused, rows_evaluated, equal_split, reuse): V(obs_next) rows taken from the
+        V(obs) pass | evaluated by the next jobs (per critic), whether the launch ran the equal split, whether the reuse was on"""
+        out = (C.c_int64 * 4)()
+        _lib.check(self.lib.fsrl_ppo_process_stats(self._ctx, out))
+        return dict(rows_reused=int(out[0]), rows_evaluated=int(out[1]), equal_split=bool(out[2]), reuse=bool(out[3]))
+
     def ppo_update(self, lagrangians, rescaling, batch_size, repeat, perms=None, seed=0):
         """-> (stats [steps, 11] float32, stopped_pass or -1)."""
         n = self.ppo_begin(lagrangians, rescaling, batch_size)

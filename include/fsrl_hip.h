@@ -338,6 +338,13 @@ int fsrl_ppo_set_plan(fsrl_ctx* ctx, int32_t tall_tiles);
 int fsrl_ppo_set_clip_fuse(fsrl_ctx* ctx, int32_t mode, int32_t limit_ticks);
 int fsrl_ppo_clip_fuse_stats(fsrl_ctx* ctx, int64_t* out, float* grad_norm_out);
 
+/* process_fn of a fused PPO-Lagrangian context takes V(obs_next[r]) from the V(obs) pass wherever obs_next[r] and obs[r + 1] of the batch
+ * are equal word for word (every row of an on-policy store but the ends of episodes and the ring's seam) and evaluates only the other
+ * rows -- the same bits as evaluating every row.  Environment: FSRL_NO_VNEXT_REUSE (read at fsrl_ctx_create) evaluates every row.
+ * fsrl_ppo_process_stats (after fsrl_ppo_begin; waits for the device): out[4] = {rows taken from the V(obs) pass, rows evaluated
+ * (per critic; they add up to the batch), the launch ran the equal split of its workgroups (0 / 1), the reuse was on (0 / 1)}.   */
+int fsrl_ppo_process_stats(fsrl_ctx* ctx, int64_t* out);
+
 /* ---- grouped updates: k independent PPO-Lagrangian agents, or k FOCOPS agents, of ONE network shape on one GPU, stepped in lock step
  *      (multi-seed runs; SURVEY 8e "within-GPU batching of k seeds").  The reference runs seeds as separate jobs; one
  *      agent's update is a chain of small dependent launches that leaves most of an MI355X idle, so k agents share every
