@@ -8,6 +8,7 @@ installed pass real vector envs exposing reset(ids) / step(act, ids) -> (obs, re
     python examples/train_agent.py --algo sacl --epoch 2 --prefill /tmp/dataset/dataset.npz     (examples/collect_dataset.py --out /tmp/dataset)
     python examples/train_agent.py --algo ppol --epoch 3 --task device-point-circle    (envs on the GPU: whole collects in one looping kernel)
     python examples/train_agent.py --algo cpo --epoch 3 --task device-linear
+    python examples/train_agent.py --algo ppol --epoch 3 --task device-linear --envs 1024    (65 .. 4096 envs: one launch per vector step)
     python examples/train_agent.py --algo sacl --epoch 2 --task device-point-circle    (ddpgl and cvpo likewise: nothing per step on the host)
 """
 import argparse
@@ -41,7 +42,7 @@ def main():
                     help="CPO / TRPO-Lag: Batch.split size inside learn (the reference's default 99999 = the whole buffer)")
     ap.add_argument("--task", choices=["synthetic", "point-circle", "device-point-circle", "device-linear"], default="synthetic",
                     help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories; "
-                         "device-point-circle / device-linear: the same two envs as device functions (every agent; at most 64 envs; any "
+                         "device-point-circle / device-linear: the same two envs as device functions (every agent; up to 64 envs in one looping kernel, 65 .. 4096, e.g. --envs 1024, one launch per vector step: fsrl_collect_device_wide; any "
                          "--hidden-sizes: two layers of at most 256 units collect through fsrl_collect_device, every other shape through "
                          "fsrl_collect_device_layered), collected by DeviceCollector")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
@@ -63,8 +64,11 @@ def main():
     if a.prefill is not None and a.algo not in ("sacl", "ddpgl", "cvpo"):
         ap.error(f"--prefill fills a replay store: --algo must be sacl, ddpgl or cvpo, not {a.algo}")
     device_task = a.task.startswith("device-")
-    if device_task and (a.envs > 64 or a.workers > 0):
-        ap.error("a device env holds at most 64 envs and needs no worker processes")
+    if device_task and (a.envs > 4096 or a.workers > 0):
+        ap.error("a device env holds at most 4096 envs and needs no worker processes")
+    if device_task and a.envs > 64 and (a.per_alpha is not None or (a.hidden_sizes and (a.hidden_sizes.count("x") != 1 or max(map(int, a.hidden_sizes.split("x"))) > 256))):
+        ap.error("more than 64 device envs collect through fsrl_collect_device_wide: fused contexts (two hidden layers of at most 256 units) "
+                 "without prioritised replay")
     if a.task in ("point-circle", "device-point-circle"):
         # the reference's own construction (train_ppol_agent.py:120-123): one factory per env, in process or in worker processes
         from fsrl_amd.env import DummyVectorEnv, PointCircleEnv, ShmemVectorEnv

@@ -72,6 +72,7 @@ class DevEnvConfig(C.Structure):
 
 
 DEVENV_POINT_CIRCLE, DEVENV_LINEAR = 0, 1
+DC_MAX_ENVS, DCW_MAX_ENVS = 64, 4096       # envs of a device env / of a wide one (include/fsrl_hip.h)
 
 # fsrl_sac_config / fsrl_cvpo_config .actor_mean: how the Gaussian actor's mean head becomes the mean
 ACTOR_MEAN_DEFAULT, ACTOR_MEAN_UNBOUNDED, ACTOR_MEAN_TANH = 0, 1, 2
@@ -242,6 +243,7 @@ SIGNATURES = {
     "fsrl_traj_import": (C.c_int, [_ctx, C.c_int64, _f, _f, _f, _d, _d, _u8, _u8, C.c_int32, _i64, _i64]),
     "fsrl_store_fill": (C.c_int, [_ctx, _ctx, _i32, C.c_int64, C.c_int32, C.c_int32, _f, _f, _i64]),
     "fsrl_devenv_create": (C.c_int, [_ctx, _P(DevEnvConfig), _P(_ctx)]),
+    "fsrl_devenv_create_wide": (C.c_int, [_ctx, _P(DevEnvConfig), _P(_ctx)]),
     "fsrl_devenv_destroy": (C.c_int, [_ctx]),
     "fsrl_devenv_seed": (C.c_int, [_ctx, C.c_uint64]),
     "fsrl_devenv_reset": (C.c_int, [_ctx, _i32, C.c_int32, _f]),
@@ -250,6 +252,9 @@ SIGNATURES = {
     "fsrl_devenv_set_state": (C.c_int, [_ctx, _f, _i32, _i64]),
     "fsrl_collect_device": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,
                                       _i32, _i32]),
+    "fsrl_collect_device_wide": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,
+                                      _i32, _i32]),
+    "fsrl_collect_device_wide_timing": (C.c_int, [_ctx, _d]),
     "fsrl_collect_device_group": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
                                             _i32, _d, _i32, _i32, _i32]),
     "fsrl_evaluate_device": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,

@@ -57,6 +57,40 @@ DC_HD int32_t dc_episode_end(int32_t* live, int32_t n_live, const uint8_t* done,
 }
 DC_HD bool dc_complete(int32_t episodes, int32_t n_episode) { return episodes >= n_episode; }
 
+// ---- the wide collect (fsrl_collect_device_wide, kernels_devcollect_wide.hpp): one launch per vector step, one workgroup per
+// 16-row tile.  dc_episode_end as a rule per POSITION, for threads that each know only their own position: with
+// rank = the number of finished positions in front of p, position p leaves iff it finished and rank < surplus, and a survivor moves
+// up by the number of leavers in front of it, min(rank, surplus).  tests/host/devcollect_wide_sim.cpp holds it to dc_episode_end.
+#ifndef DCW_MAX_ENVS
+#define DCW_MAX_ENVS 4096       // envs of one wide device env: one round of 256 tiles (include/fsrl_hip.h has it too)
+#endif
+#define DCW_MAX_LOG_ROWS (1 << 20)     // log rows of one batch of launches
+DC_HD int32_t dc_wide_surplus(int32_t n_live, int32_t n_done, int32_t n_episode, int32_t episodes_after) {
+    const int32_t s = n_live - (n_episode - episodes_after);
+    return n_done == 0 || s <= 0 ? 0 : s;
+}
+DC_HD bool dc_wide_leaves(bool done, int32_t rank, int32_t surplus) { return done && rank < surplus; }
+DC_HD int32_t dc_wide_new_pos(int32_t p, int32_t rank, int32_t surplus) { return p - (rank < surplus ? rank : surplus); }
+DC_HD int32_t dc_wide_n_live(int32_t n_live, int32_t n_done, int32_t surplus) { return n_live - (n_done < surplus ? n_done : surplus); }
+// vector steps of one batch when the caller names none: clamp(2^20 / env_num, 1, 64); a named count is cut to the log's cap
+DC_HD int32_t dc_wide_batch_steps(int32_t env_num, int32_t asked) {
+    const int32_t cap = DCW_MAX_LOG_ROWS / env_num;
+    const int32_t s = asked > 0 ? asked : DC_DEFAULT_STEPS;
+    return s < cap ? s : (cap < 1 ? 1 : cap);
+}
+// What persists between the launches of a wide collect.  Everything a launch writes that another workgroup of the SAME launch reads is
+// held twice, by the parity of the launch ordinal t: launch t reads side t & 1 and writes side (t + 1) & 1.  s[] describes the
+// collect as the step before left it: `pending` says that this step's flags in done[] have not been through the surplus rule yet (the
+// next launch does that first, in every workgroup); lpar names the half of live[] that holds the live list.
+struct DcwScalars { int32_t n_live, episodes, finished, log_rows, steps, lpar, pending, pad; };
+struct DcwState {
+    DcwScalars s[2];
+    int32_t n_episode, pad[15];
+    int32_t live[2][DCW_MAX_ENVS];              // env ids in position order
+    uint32_t done[2][DCW_MAX_ENVS / 4];         // a byte per position: the step's episode ends
+    int32_t index[DCW_MAX_ENVS];                // write index of every env's sub-buffer, by env id (its own thread's alone)
+};
+
 // slot of env e's next row and the index behind it (tianshou ReplayBuffer.add: ptr = index, index = (index + 1) % maxsize)
 DC_HD int64_t dc_slot(int32_t e, int64_t sub_size, int32_t index) { return (int64_t)e * sub_size + index; }
 DC_HD int32_t dc_next_index(int32_t index, int64_t sub_size) { return (int64_t)index + 1 >= sub_size ? 0 : index + 1; }     // index < sub_size: (index + 1) % sub_size without the division

@@ -164,7 +164,8 @@ static inline bool devenv_dispatch(const int kind, F&& f) {
 static inline int devenv_state_dim(const int kind, const int Do) { return kind == FSRL_DEVENV_POINT_CIRCLE ? DevEnvPointCircle::STATE : Do; }
 
 // ---------------------------------------------------------------- the env as a vector env: reset / step / observe of listed envs
-// One workgroup of DC_MAX_ENVS threads, a thread per listed env.  ids / act and the outputs are pinned host memory.
+// Workgroups of DC_MAX_ENVS threads, a thread per listed env: one workgroup up to DC_MAX_ENVS rows, ceil(n / DC_MAX_ENVS) for a wide
+// env (fsrl_devenv_create_wide).  ids / act and the outputs are pinned host memory.
 struct DevEnvIo {
     const int32_t* ids;     // [n] or NULL = envs 0 .. n - 1
     const float* act;       // [n][Da]
@@ -176,7 +177,7 @@ struct DevEnvIo {
 template <class Env>
 __global__ __launch_bounds__(DC_MAX_ENVS) void devenv_reset_kernel(const DevEnvParams P, const DevEnvArrays ea, const DevEnvIo io,
                                                                     const uint32_t k0, const uint32_t k1) {
-    const int p = threadIdx.x;
+    const int p = blockIdx.x * DC_MAX_ENVS + threadIdx.x;
     if (p >= io.n) return;
     const int e = io.ids ? io.ids[p] : p;
     const DevRng g{k0, k1, (uint32_t)e, (uint32_t)ea.ordinal[e]};
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(DC_MAX_ENVS) void devenv_reset_kernel(const DevEnvP
 template <class Env>
 __global__ __launch_bounds__(DC_MAX_ENVS) void devenv_step_kernel(const DevEnvParams P, const DevEnvArrays ea, const DevEnvIo io,
                                                                    const uint32_t k0, const uint32_t k1) {
-    const int p = threadIdx.x;
+    const int p = blockIdx.x * DC_MAX_ENVS + threadIdx.x;
     if (p >= io.n) return;
     const int e = io.ids ? io.ids[p] : p;
     const DevRng g{k0, k1, (uint32_t)e, (uint32_t)(ea.ordinal[e] - 1)};
@@ -208,6 +209,6 @@ __global__ __launch_bounds__(DC_MAX_ENVS) void devenv_step_kernel(const DevEnvPa
 // fsrl_devenv_set_state: the observations of injected states
 template <class Env>
 __global__ __launch_bounds__(DC_MAX_ENVS) void devenv_observe_kernel(const DevEnvParams P, const DevEnvArrays ea) {
-    const int e = threadIdx.x;
+    const int e = blockIdx.x * DC_MAX_ENVS + threadIdx.x;
     if (e < P.env_num) Env::observe(P, ea.state + (size_t)e * DEVENV_STATE, ea.obs + (size_t)e * P.Do);
 }

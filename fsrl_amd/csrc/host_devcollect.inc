@@ -17,6 +17,7 @@
 // Layered contexts come in through fsrl_collect_device_layered / fsrl_evaluate_device_layered: the same checks, entry, loop and replay
 // with `layered = true`, lay_collect_kernel (kernels_devcollect_layered.hpp) in the launch and the env's activation workspace.
 #include "kernels_devcollect_layered.hpp"
+#include "kernels_devcollect_wide.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered);      // defined with the SAC / CVPO code
 static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax);    // ... and behind the layered code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -44,7 +45,14 @@ struct fsrl_devenv {
     float* d_ws = nullptr; int ws_ld = 0;
     LayCollectTable* d_ltab = nullptr; LayCollectTable* h_ltab = nullptr;
     DcEvalAcc acc[DC_MAX_ENVS] = {};    // fsrl_evaluate_device: the running episode of every env, from the log alone
+    // a wide env (fsrl_devenv_create_wide, host_devcollect_wide.inc): up to DCW_MAX_ENVS envs, collected by fsrl_collect_device_wide alone
+    bool wide = false;
+    DcwState* d_wstate = nullptr; DcwState* h_wstate = nullptr;                 // device / pinned
+    WideCollectArgs* d_wargs = nullptr; WideCollectArgs* h_wargs = nullptr;     // device / pinned
+    uint32_t wide_t = 0;                // launch ordinal of the next wide launch: its parity picks the state's side
+    double wide_seconds[2] = {0.0, 0.0};        // the last wide collect: in all, in the host replay (fsrl_collect_device_wide_timing)
 };
+static dim3 devenv_grid(int n) { return dim3((unsigned)((n + DC_MAX_ENVS - 1) / DC_MAX_ENVS)); }
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
 static DevEnvParams devenv_params(const fsrl_devenv* v) {
     DevEnvParams P{};
@@ -75,10 +83,12 @@ static void devenv_free(fsrl_devenv* v) {
     delete v;
 }
 
-extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fsrl_devenv** out) {
+static int devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fsrl_devenv** out, bool wide) {
     CHECK_ARG(c && cfg && out, "null argument");
     CHECK_ARG(cfg->kind == FSRL_DEVENV_POINT_CIRCLE || cfg->kind == FSRL_DEVENV_LINEAR, "kind %d: no such device env", cfg->kind);
-    CHECK_ARG(cfg->env_num >= 1 && cfg->env_num <= DC_MAX_ENVS, "env_num %d: a device env holds 1 .. %d envs", cfg->env_num, DC_MAX_ENVS);
+    if (!wide) CHECK_ARG(cfg->env_num >= 1 && cfg->env_num <= DC_MAX_ENVS, "env_num %d: a device env holds 1 .. %d envs (fsrl_devenv_create_wide: up to %d)",
+                         cfg->env_num, DC_MAX_ENVS, DCW_MAX_ENVS);
+    else CHECK_ARG(cfg->env_num >= 1 && cfg->env_num <= DCW_MAX_ENVS, "env_num %d: a wide device env holds 1 .. %d envs", cfg->env_num, DCW_MAX_ENVS);
     CHECK_ARG(cfg->obs_dim == c->cfg.obs_dim && cfg->act_dim == c->cfg.act_dim,
               "env shape (obs_dim %d, act_dim %d) != context shape (obs_dim %d, act_dim %d)", cfg->obs_dim, cfg->act_dim, c->cfg.obs_dim,
               c->cfg.act_dim);
@@ -92,7 +102,7 @@ extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fs
     }
     HIPCHK(hipSetDevice(c->device));
     fsrl_devenv* v = new fsrl_devenv();
-    v->c = c; v->cfg = *cfg; v->cfg.A = nullptr; v->cfg.B = nullptr;
+    v->c = c; v->cfg = *cfg; v->cfg.A = nullptr; v->cfg.B = nullptr; v->wide = wide;
     v->key = devenv_key(cfg->seed);
     const size_t n = (size_t)cfg->env_num, Do = (size_t)cfg->obs_dim, Da = (size_t)cfg->act_dim;
     auto bail = [&](hipError_t e, const char* what) {
@@ -122,11 +132,19 @@ extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fs
     DEVENV_TRY(v->mem.pinned(&v->h_state, sizeof(DcState)));
     DEVENV_TRY(v->mem.dev(&v->d_args, sizeof(DevCollectArgs)));
     DEVENV_TRY(v->mem.pinned(&v->h_args, sizeof(DevCollectArgs)));
+    if (wide) {
+        DEVENV_TRY(v->mem.dev(&v->d_wstate, sizeof(DcwState)));
+        DEVENV_TRY(v->mem.pinned(&v->h_wstate, sizeof(DcwState)));
+        DEVENV_TRY(v->mem.dev(&v->d_wargs, sizeof(WideCollectArgs)));
+        DEVENV_TRY(v->mem.pinned(&v->h_wargs, sizeof(WideCollectArgs)));
+    }
 #undef DEVENV_TRY
     c->devenvs.push_back(v);
     *out = v;
     return 0;
 }
+extern "C" int fsrl_devenv_create(fsrl_ctx* c, const fsrl_devenv_config* cfg, fsrl_devenv** out) { return devenv_create(c, cfg, out, false); }
+extern "C" int fsrl_devenv_create_wide(fsrl_ctx* c, const fsrl_devenv_config* cfg, fsrl_devenv** out) { return devenv_create(c, cfg, out, true); }
 
 static void devenv_ctx_gone(fsrl_ctx* c) { for (fsrl_devenv* v : c->devenvs) v->c = nullptr; }     // destroy is all such an env still takes
 extern "C" int fsrl_devenv_destroy(fsrl_devenv* v) {
@@ -154,11 +172,11 @@ extern "C" int fsrl_devenv_seed(fsrl_devenv* v, uint64_t seed) {
 static int devenv_take_ids(fsrl_devenv* v, const int32_t* ids, int32_t n, const DevEnvIoLayout& l) {
     CHECK_ARG(n >= 0 && n <= v->cfg.env_num, "%d rows but the device env has %d envs", n, v->cfg.env_num);
     if (!ids) return 0;
-    uint64_t seen = 0;
+    uint64_t seen[DCW_MAX_ENVS / 64] = {};
     for (int i = 0; i < n; ++i) {
         CHECK_ARG(ids[i] >= 0 && ids[i] < v->cfg.env_num, "env id %d out of range", ids[i]);
-        CHECK_ARG(!(seen >> ids[i] & 1ull), "env id %d is listed twice", ids[i]);
-        seen |= 1ull << ids[i];
+        CHECK_ARG(!(seen[ids[i] >> 6] >> (ids[i] & 63) & 1ull), "env id %d is listed twice", ids[i]);
+        seen[ids[i] >> 6] |= 1ull << (ids[i] & 63);
         l.ids[i] = ids[i];
     }
     return 0;
@@ -169,7 +187,7 @@ static int devenv_reset_launch(fsrl_devenv* v, const DevEnvIo& io, hipStream_t s
     const uint32_t k0 = (uint32_t)v->key, k1 = (uint32_t)(v->key >> 32);
     devenv_dispatch(v->cfg.kind, [&](auto env) {
         using Env = decltype(env);
-        hipLaunchKernelGGL(devenv_reset_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, s, P, v->ea, io, k0, k1);
+        hipLaunchKernelGGL(devenv_reset_kernel<Env>, devenv_grid(io.n), dim3(DC_MAX_ENVS), 0, s, P, v->ea, io, k0, k1);
     });
     HIPCHK(hipGetLastError());
     return 0;
@@ -209,7 +227,7 @@ extern "C" int fsrl_devenv_step(fsrl_devenv* v, const int32_t* ids, int32_t n, c
     const uint32_t k0 = (uint32_t)v->key, k1 = (uint32_t)(v->key >> 32);
     devenv_dispatch(v->cfg.kind, [&](auto env) {
         using Env = decltype(env);
-        hipLaunchKernelGGL(devenv_step_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea, io, k0, k1);
+        hipLaunchKernelGGL(devenv_step_kernel<Env>, devenv_grid(io.n), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea, io, k0, k1);
     });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(v->es));
@@ -250,7 +268,7 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
         const DevEnvParams P = devenv_params(v);
         devenv_dispatch(v->cfg.kind, [&](auto env) {
             using Env = decltype(env);
-            hipLaunchKernelGGL(devenv_observe_kernel<Env>, dim3(1), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea);
+            hipLaunchKernelGGL(devenv_observe_kernel<Env>, devenv_grid(v->cfg.env_num), dim3(DC_MAX_ENVS), 0, v->es, P, v->ea);
         });
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(v->es));
@@ -262,10 +280,13 @@ extern "C" int fsrl_devenv_set_state(fsrl_devenv* v, const float* state, const i
 // calls; fsrl_collect_device refuses grouped contexts, and the _group calls run the same checks on every member without that clause.
 // store = false (an evaluation, grouped or not): nothing is stored, so a tap, a group and the store's geometry are no reasons.
 static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_episode, int32_t bound_method, const float* act_low,
-                            const float* act_high, int32_t max_steps, bool named, bool store, bool layered) {
+                            const float* act_high, int32_t max_steps, bool named, bool store, bool layered, bool wide = false) {
     const char* const what = store ? "collects" : "evaluations";
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
+    if (!wide) CHECK_ARG(!v->wide, "a wide device env (fsrl_devenv_create_wide): its collects go through fsrl_collect_device_wide; evaluations, "
+                         "grouped and layered collects over wide envs are not supported yet");
+    else CHECK_ARG(v->wide, "fsrl_collect_device_wide takes a wide device env (fsrl_devenv_create_wide); this one collects through fsrl_collect_device");
     if (!layered) CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
     else CHECK_ARG(c->lay, "a fused context (two hidden layers of at most 256 units): its device %s go through %s", what,
                    store ? "fsrl_collect_device" : "fsrl_evaluate_device");
@@ -278,10 +299,11 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
         CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
     }
     if (store) CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
+    if (wide) CHECK_ARG(!c->per, "wide device collects are not supported on a context with prioritised replay on yet");
     if (c->in_update)
         return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device",
-                    layered ? "_layered" : named ? "_group" : "");
-    CHECK_ARG(v->cfg.env_num <= DC_MAX_ENVS, "env_num %d above %d", v->cfg.env_num, DC_MAX_ENVS);
+                    wide ? "_wide" : layered ? "_layered" : named ? "_group" : "");
+    CHECK_ARG(v->cfg.env_num <= (wide ? DCW_MAX_ENVS : DC_MAX_ENVS), "env_num %d above %d", v->cfg.env_num, wide ? DCW_MAX_ENVS : DC_MAX_ENVS);
     if (store) CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
               v->cfg.obs_dim, v->cfg.act_dim);
@@ -301,7 +323,8 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
 // layered = true: the actor is (P, net) of devcollect_lay_actor, md stays null, and the env's activation workspace exists.
 struct DcActor { const float* P; const ModelDesc* md; int head; const LayNet* net; };
 static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int32_t deterministic, int32_t bound_method,
-                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store, bool layered) {
+                            const float* act_low, const float* act_high, int max_steps, DcActor* actor, bool store, bool layered,
+                            bool wide = false) {
     const int n = v->cfg.env_num, Da = v->cfg.act_dim;
     ENTER_DEV(c);                                   // a live resident actor ends first
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
@@ -312,14 +335,22 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
         HIPCHK(v->mem.regrow(v->log_steps, max_steps, max_steps, {Mem::D(&v->d_log, rows * sizeof(DcLogRow)),
                              Mem::D(&v->d_slot, rows * sizeof(int32_t)), Mem::H(&v->h_log, rows * sizeof(DcLogRow))}));
     }
-    DcState& hs = *v->h_state;
-    memset(&hs, 0, sizeof(hs));
-    hs.n_live = dc_first_live(n, n_episode); hs.n_episode = n_episode;
-    for (int e = 0; e < DC_MAX_ENVS; ++e) hs.live[e] = e < n ? e : 0;
-    for (int e = 0; e < n && store; ++e) hs.index[e] = (int32_t)c->env[(size_t)e].index;
-    if (!store) for (int e = 0; e < DC_MAX_ENVS; ++e) v->acc[e] = DcEvalAcc{0.0, 0};
     hipStream_t s = c->compute;
-    HIPCHK(hipMemcpyAsync(v->d_state, &hs, sizeof(DcState), hipMemcpyHostToDevice, s));
+    if (wide) {         // the wide collect's state: settled, on the side the next launch reads
+        DcwState& ws = *v->h_wstate;
+        memset(&ws, 0, sizeof(ws));
+        ws.s[v->wide_t & 1].n_live = dc_first_live(n, n_episode); ws.n_episode = n_episode;
+        for (int e = 0; e < n; ++e) { ws.live[0][e] = e; ws.index[e] = (int32_t)c->env[(size_t)e].index; }
+        HIPCHK(hipMemcpyAsync(v->d_wstate, &ws, sizeof(DcwState), hipMemcpyHostToDevice, s));
+    } else {
+        DcState& hs = *v->h_state;
+        memset(&hs, 0, sizeof(hs));
+        hs.n_live = dc_first_live(n, n_episode); hs.n_episode = n_episode;
+        for (int e = 0; e < DC_MAX_ENVS; ++e) hs.live[e] = e < n ? e : 0;
+        for (int e = 0; e < n && store; ++e) hs.index[e] = (int32_t)c->env[(size_t)e].index;
+        if (!store) for (int e = 0; e < DC_MAX_ENVS; ++e) v->acc[e] = DcEvalAcc{0.0, 0};
+        HIPCHK(hipMemcpyAsync(v->d_state, &hs, sizeof(DcState), hipMemcpyHostToDevice, s));
+    }
     // the arguments travel through device memory: ~350 bytes of kernel arguments held in scalar registers next to tile_forward's own
     // pushed the 256-wide kernel over its 128-VGPR cap (scalar spills live in vector registers)
     DevCollectArgs& a = *v->h_args;
@@ -346,6 +377,12 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
         rc = store ? sac_devcollect_enter(c) : 0;
         if (rc) return rc;
         a.slots = store && c->per ? v->d_slot : nullptr;
+    }
+    if (wide) {
+        WideCollectArgs& w = *v->h_wargs;
+        w.a = a; w.ws = v->d_wstate; w.log_cap = max_steps * n;
+        HIPCHK(hipMemcpyAsync(v->d_wargs, v->h_wargs, sizeof(WideCollectArgs), hipMemcpyHostToDevice, s));
+        return 0;
     }
     HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));
     return 0;

@@ -7,6 +7,9 @@ policies alike (SAC-Lag, DDPG-Lag, CVPO: the actor's head arithmetic runs on the
 the rows).  Layered engines (hidden_sizes of any depth and width) collect through the layered entry points of the library
 (fsrl_collect_device_layered / fsrl_evaluate_device_layered: one kernel for every shape, the weights streamed from L2); the collectors
 route on `_layered(engine)`.  A `DeviceCollector` of its own on a grouped fused engine is refused by the library, with the reason.
+A WIDE env (more than 64 envs, up to 4096, or `wide=True`) collects through fsrl_collect_device_wide: one launch per vector step, a
+workgroup per 16-row tile, `max_steps_per_launch` step launches per batch; without a buffer, on layered engines and in a
+`GroupDeviceCollector` a wide env is refused by name.
 
 Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
 through `GroupDeviceCollector(collectors)`: ONE launch per `max_steps_per_launch` vector steps carries every member's collect, a
@@ -61,7 +64,8 @@ def evaluation_collector(policy, test_envs, render: bool = False):
         return None
     from fsrl_amd.env.device import DeviceVectorEnv
     eng = getattr(policy, "engine", None)
-    if isinstance(test_envs, DeviceVectorEnv) and eng is not None and test_envs.engine is eng and not _layered(eng) and not render:
+    if (isinstance(test_envs, DeviceVectorEnv) and eng is not None and test_envs.engine is eng and not _layered(eng) and not render
+            and not test_envs.wide):
         return DeviceCollector(policy, test_envs)
     from fsrl_amd.data.fast_collector import FastCollector
     return FastCollector(policy, test_envs)
@@ -111,6 +115,8 @@ class DeviceCollector:
     # ------------------------------------------------------------------ collect
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
         eng = self.policy.engine
+        if self.env.wide:       # layered engines: the library refuses, by name
+            return self._collect(n_episode, eng.collect_device_wide)
         return self._collect(n_episode, eng.collect_device_layered if _layered(eng) else eng.collect_device)
 
     def _collect(self, n_episode, run) -> Dict[str, Any]:
@@ -138,6 +144,10 @@ class DeviceEvalCollector(DeviceCollector):
 
     def __init__(self, policy, env, buffer=None, max_steps_per_launch: int = 0, exploration_noise: bool = False):
         assert buffer is None, "a DeviceEvalCollector stores nothing: DeviceCollector(policy, env, buffer) collects into a buffer"
+        if getattr(env, "wide", False):
+            raise ValueError("evaluations over wide device envs are not supported yet: a wide env (more than 64 envs, or wide=True) "
+                             "collects into a buffer through Engine.collect_device_wide (fsrl_collect_device_wide); evaluate it with "
+                             "FastCollector(policy, env)")
         super().__init__(policy, env, None, max_steps_per_launch, exploration_noise)
 
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:

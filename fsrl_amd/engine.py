@@ -382,9 +382,9 @@ class Engine:
                     ep_rews=ep_rew[:k], ep_lens=ep_len[:k], t_env=float(tm[0]), t_act=float(tm[1]))
 
     # ---------------------------------------------------------------- device environments (include/fsrl_hip.h "Device environments")
-    def devenv_create(self, kind, env_num, max_episode_steps, seed=0, params=(), A=None, B=None):
+    def devenv_create(self, kind, env_num, max_episode_steps, seed=0, params=(), A=None, B=None, wide=False):
         """fsrl_devenv_create -> handle.  obs_dim / act_dim are the engine's; A [obs_dim, obs_dim] and B [act_dim, obs_dim] for the
-        linear kind.  The envs are not reset."""
+        linear kind.  The envs are not reset.  wide: fsrl_devenv_create_wide -- up to 4096 envs, collected by collect_device_wide."""
         cfg = _lib.DevEnvConfig()
         cfg.kind, cfg.env_num, cfg.obs_dim, cfg.act_dim = int(kind), int(env_num), self.cfg.obs_dim, self.cfg.act_dim
         cfg.max_episode_steps, cfg.seed = int(max_episode_steps), int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -397,7 +397,8 @@ class Engine:
                 "A is [obs_dim, obs_dim], B is [act_dim, obs_dim]"
             cfg.A, cfg.B = a.ctypes.data, b.ctypes.data
         h = C.c_void_p()
-        _lib.check(self.lib.fsrl_devenv_create(self._ctx, C.byref(cfg), C.byref(h)))      # copies A and B
+        create = self.lib.fsrl_devenv_create_wide if wide else self.lib.fsrl_devenv_create
+        _lib.check(create(self._ctx, C.byref(cfg), C.byref(h)))      # copies A and B
         return h
 
     def devenv_destroy(self, h):
@@ -448,6 +449,20 @@ class Engine:
         lo = np.ascontiguousarray(low, np.float32) if low is not None else None
         hi = np.ascontiguousarray(high, np.float32) if low is not None else None
         return self._collect_device(self.lib.fsrl_collect_device, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
+
+    def collect_device_wide(self, h, n_episode, deterministic=False, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.collect_device over a WIDE env (devenv_create(..., wide=True), up to 4096 envs): fsrl_collect_device_wide, one launch
+        per vector step and a workgroup per 16-row tile.  max_steps_per_launch: step launches per batch (0: min(64, 2^20 / env_num)).
+        The same result dict; `launches` counts kernel launches."""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_collect_device_wide, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
+
+    def collect_device_wide_timing(self, h):
+        """-> (seconds of the env's last wide collect, seconds of it in the host's log replay)"""
+        out = np.zeros(2, np.float64)
+        _lib.check(self.lib.fsrl_collect_device_wide_timing(h, _ptr(out, _f64p)))
+        return float(out[0]), float(out[1])
 
     def evaluate_device(self, h, n_episode, deterministic=True, bound_method=1, low=None, high=None, max_steps_per_launch=0):
         """Engine.collect_device that stores nothing (fsrl_evaluate_device): FastCollector(policy, test_envs) with no buffer.  The

@@ -5,7 +5,9 @@ never leaves HBM.  `DeviceVectorEnv` gives such an env the calling convention of
 `DeviceCollector` (fsrl_amd/data/device_collector.py): a whole `collect(n_episode)` in a handful of launches -- with a buffer the
 training collect (fsrl_collect_device), without one the evaluation that stores nothing (fsrl_evaluate_device), which is what the
 agents' `learn(train_envs, test_envs)` and `evaluate(test_envs)` run over device test envs of their own engine.  Layered engines
-and `render=True` evaluate through `FastCollector` over `step`, call by call."""
+and `render=True` evaluate through `FastCollector` over `step`, call by call.  More than 64 envs (up to 4096), or `wide=True`, make
+a WIDE env (fsrl_devenv_create_wide): the same calling convention, and `DeviceCollector` collects it with one launch per vector step
+(fsrl_collect_device_wide); evaluations over wide envs go through `FastCollector`."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -25,9 +27,10 @@ def _engine_of(engine_or_policy):
 
 class DeviceVectorEnv:
     """`kind`: "point-circle" (params radius, x_lim, dt) or "linear" (params cost_threshold; A [obs, obs], B [act, obs]).  The env is
-    bound to the engine it was created on: its shapes are the engine's, and only that engine's DeviceCollector can drive it."""
+    bound to the engine it was created on: its shapes are the engine's, and only that engine's DeviceCollector can drive it.
+    wide: None -> env_num > 64; True makes a wide env at any count."""
 
-    def __init__(self, engine_or_policy, kind, env_num, max_episode_steps, seed=0, params=(), A=None, B=None, spec_id="DeviceEnv-v0"):
+    def __init__(self, engine_or_policy, kind, env_num, max_episode_steps, seed=0, params=(), A=None, B=None, spec_id="DeviceEnv-v0", wide=None):
         self.engine = _engine_of(engine_or_policy)
         self.kind = KINDS[kind] if isinstance(kind, str) else int(kind)
         self.env_num = int(env_num)
@@ -36,7 +39,8 @@ class DeviceVectorEnv:
         self.observation_space = Box(-np.inf, np.inf, (self.obs_dim, ))
         self.action_space = Box(-1.0, 1.0, (self.act_dim, ))
         self.spec = SimpleNamespace(id=spec_id, max_episode_steps=int(max_episode_steps))
-        self._h = self.engine.devenv_create(self.kind, self.env_num, max_episode_steps, seed, params, A, B)
+        self.wide = self.env_num > _lib.DC_MAX_ENVS if wide is None else bool(wide)
+        self._h = self.engine.devenv_create(self.kind, self.env_num, max_episode_steps, seed, params, A, B, **({"wide": True} if self.wide else {}))
 
     def __len__(self):
         return self.env_num
@@ -74,8 +78,9 @@ class DeviceVectorEnv:
 class DevicePointCircle(DeviceVectorEnv):
     """`PointCircleEnv` (fsrl_amd/env/toy.py) in float32 on the device: obs 6, act 2"""
 
-    def __init__(self, engine_or_policy, env_num, max_episode_steps=100, radius=1.5, x_lim=1.0, dt=0.1, seed=0):
-        super().__init__(engine_or_policy, "point-circle", env_num, max_episode_steps, seed, (radius, x_lim, dt), spec_id="DevicePointCircle-v0")
+    def __init__(self, engine_or_policy, env_num, max_episode_steps=100, radius=1.5, x_lim=1.0, dt=0.1, seed=0, wide=None):
+        super().__init__(engine_or_policy, "point-circle", env_num, max_episode_steps, seed, (radius, x_lim, dt), spec_id="DevicePointCircle-v0",
+                         wide=wide)
         self.radius, self.x_lim, self.dt = float(radius), float(x_lim), float(dt)
 
 
@@ -83,7 +88,7 @@ class DeviceLinear(DeviceVectorEnv):
     """`SyntheticSafetyVectorEnv`'s dynamics on the device.  `like`: a host env to take A, B, the episode length and the cost
     threshold from (its env_num too, unless one is given)."""
 
-    def __init__(self, engine_or_policy, env_num=None, episode_len=300, cost_threshold=1.0, A=None, B=None, seed=0, like=None):
+    def __init__(self, engine_or_policy, env_num=None, episode_len=300, cost_threshold=1.0, A=None, B=None, seed=0, like=None, wide=None):
         if like is not None:
             A, B = like.A, like.B
             episode_len, cost_threshold = like.episode_len, like.cost_threshold
@@ -92,4 +97,5 @@ class DeviceLinear(DeviceVectorEnv):
             raise ValueError("DeviceLinear needs A and B, or like=SyntheticSafetyVectorEnv(...)")
         self.A, self.B = np.asarray(A, np.float32), np.asarray(B, np.float32)
         self.cost_threshold = float(cost_threshold)
-        super().__init__(engine_or_policy, "linear", env_num, episode_len, seed, (cost_threshold, ), self.A, self.B, spec_id="DeviceLinear-v0")
+        super().__init__(engine_or_policy, "linear", env_num, episode_len, seed, (cost_threshold, ), self.A, self.B, spec_id="DeviceLinear-v0",
+                         wide=wide)

@@ -1009,7 +1009,7 @@ int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int
  *      the episode, stream << 28 | dimension / 4); streams 0 reset draws, 1 action noise, 2 step noise.  The reset ordinal of an env
  *      counts its resets since creation or the last fsrl_devenv_seed (which zeroes it and leaves the env states alone).
  *
- *      fsrl_devenv_create    ctx gives the device, obs_dim / act_dim must be the context's; env_num <= 64.  The envs are NOT reset.
+ *      fsrl_devenv_create    ctx gives the device, obs_dim / act_dim must be the context's; env_num <= 64 (more: fsrl_devenv_create_wide).  The envs are NOT reset.
  *      fsrl_devenv_reset / _step   the env as an ordinary vector env for the existing collectors: one small launch on the env's own
  *                            stream (a live resident actor keeps running) and a wait.  ids == NULL: envs 0 .. n - 1.  Outputs are per
  *                            listed env; after a step the env's observation is obs_next (a finished env is reset by the caller).
@@ -1130,6 +1130,31 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
                                int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
                                int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
                                double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_devenv_create_wide / fsrl_collect_device_wide   device collects over 1 .. DCW_MAX_ENVS envs (kernels_devcollect_wide.hpp,
+ *                            host_devcollect_wide.inc).  fsrl_devenv_create_wide is fsrl_devenv_create without the 64-env limit: the
+ *                            same fsrl_devenv, marked wide; reset / step / seed / get_state / set_state reach every env.
+ *                            fsrl_collect_device_wide takes the arguments of fsrl_collect_device and leaves what it leaves -- store
+ *                            rows, books, flags, store_version, statistics, env states and the reset of ALL envs at the end; on twin
+ *                            contexts the two calls agree bit for bit -- with another split of the work: ONE LAUNCH PER VECTOR STEP,
+ *                            a workgroup per 16-row tile of the live list, the surplus rule of a step applied at the start of the
+ *                            next launch by every workgroup.  max_steps_per_launch is the number of step launches of a BATCH (<= 0:
+ *                            min(64, 2^20 / env_num); a batch's log holds at most 2^20 rows, a larger count is cut to that): a batch
+ *                            and its one-workgroup settle launch are enqueued without waiting, then the state and the log are read
+ *                            back once and replayed.  *launches_out: kernel launches, settle launches included.  On-policy, SAC-Lag /
+ *                            CVPO and DDPG-Lag contexts.
+ *                            Refused before anything changes, by name: an env of fsrl_devenv_create; layered contexts; contexts in
+ *                            any kind of group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device refuses.
+ *                            fsrl_collect_device, fsrl_evaluate_device and their _group / _layered forms refuse a wide env and name
+ *                            this call: evaluations, grouped and layered collects over wide envs are not supported yet.  */
+#define DCW_MAX_ENVS 4096
+int fsrl_devenv_create_wide(fsrl_ctx* ctx, const fsrl_devenv_config* cfg, fsrl_devenv** out);
+int fsrl_collect_device_wide(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                             const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                             double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                             int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_collect_device_wide_timing   the env's last wide collect on the host's clock: out[0] seconds from the first launch to the
+ *                            end of the call, out[1] of them in the replay of the log (tools/bench_device_collect.py --wide).  */
+int fsrl_collect_device_wide_timing(fsrl_devenv* env, double* out);
 
 #ifdef __cplusplus
 }

@@ -113,8 +113,8 @@ def setup(path, hidden, n, algo="onpolicy"):
     pol, buf = Pol(eng), HipVectorReplayBuffer(eng, n * 2 * EPISODE_LEN, n)
     if path == "in_process":
         return eng, None, FastCollector(pol, host, buf, device_actor=True)
-    env = DeviceLinear(eng, like=host, seed=1)
-    return eng, env, (DeviceCollector(pol, env, buf) if path == "device" else FastCollector(pol, env, buf, device_actor=True))
+    env = DeviceLinear(eng, like=host, seed=1, wide=True if path == "wide" else None)
+    return eng, env, (DeviceCollector(pol, env, buf) if path in ("device", "wide") else FastCollector(pol, env, buf, device_actor=True))
 
 
 def timed(col, n, calls):
@@ -364,7 +364,12 @@ def main():
                                                         "replaces and a storing collect; with --ks also grouped against solo evaluations")
     ap.add_argument("--layered", action="store_true", help="the four legs on layered shapes (--hidden entries written with x; default "
                                                            "256x256x256,64x48x32) in one process, one --out file")
+    ap.add_argument("--wide", action="store_true", help="the wide device collect (fsrl_collect_device_wide, one launch per vector step) at "
+                                                        "--envs (default 20,64,256,1024,4096) beside the in-process lock-step path and, up "
+                                                        "to 64 envs, the looping device collect; the host replay's share of the wall time")
     a = ap.parse_args()
+    if a.wide:
+        return main_wide(a)
     if a.layered:
         return main_layered(a)
     if a.eval:
@@ -393,6 +398,43 @@ def main_layered(a):
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
+
+
+def main_wide(a):
+    if a.envs == "20,64":
+        a.envs = "20,64,256,1024,4096"
+    result = dict(metric="env-steps/s of a collect loop, training mode, linear env obs 8 / act 2, episode length 300: the wide device "
+                         "collect beside the in-process lock-step path and (up to 64 envs) the looping device collect", algo=a.algo,
+                  rounds=a.rounds, calls=a.calls, configs=[])
+    for hidden in parse_hidden(a.hidden):
+        for n in (int(e) for e in a.envs.split(",")):
+            paths = ("wide", "in_process") + (("device", ) if n <= 64 else ())
+            objs = {p: setup(p, hidden, n, a.algo) for p in paths}
+            rates, per_step, share = {p: [] for p in paths}, [], []
+            for _ in range(a.rounds):           # the legs alternate inside a round
+                for p in paths:
+                    rows, dt = timed(objs[p][2], n, a.calls)
+                    rates[p].append(rows / dt)
+                    if p == "wide":
+                        per_step.append(dt / a.calls / EPISODE_LEN * 1e6)
+                        total, replay = objs[p][0].collect_device_wide_timing(objs[p][1]._h)
+                        share.append(replay / total)
+            cfg = dict(hidden=hidden_list(hidden), env_num=n, launches_per_collect=objs["wide"][2].last_launches,
+                       us_per_vector_step=float(np.median(per_step)), us_per_vector_step_spread=float(np.max(per_step) - np.min(per_step)),
+                       host_replay_share=float(np.median(share)))
+            for p in paths:
+                cfg[p] = dict(median=float(np.median(rates[p])), spread=float(np.max(rates[p]) - np.min(rates[p])), rounds=[float(r) for r in rates[p]])
+            result["configs"].append(cfg)
+            print(json.dumps(cfg), flush=True)
+            for eng, env, col in objs.values():
+                if env is not None:
+                    env.close()
+                eng.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
     return result
 
