@@ -44,7 +44,8 @@ def main():
                     help="synthetic: the vectorised stand-in dynamics; point-circle: per-instance gym-style envs built from factories; "
                          "device-point-circle / device-linear: the same two envs as device functions (every agent; up to 64 envs in one looping kernel, 65 .. 4096, e.g. --envs 1024, one launch per vector step: fsrl_collect_device_wide; any "
                          "--hidden-sizes: two layers of at most 256 units collect through fsrl_collect_device, every other shape through "
-                         "fsrl_collect_device_layered), collected by DeviceCollector")
+                         "fsrl_collect_device_layered -- above 64 envs, e.g. --envs 256 --hidden-sizes 256x256x256, through "
+                         "fsrl_collect_device_wide_layered), collected by DeviceCollector")
     ap.add_argument("--workers", type=int, default=0, help="> 0: the training envs step in that many worker processes (ShmemVectorEnv)")
     # options of the on-policy agents (the reference's constructor arguments of the same names)
     ap.add_argument("--unbounded", action=argparse.BooleanOptionalAction, default=None,
@@ -66,9 +67,8 @@ def main():
     device_task = a.task.startswith("device-")
     if device_task and (a.envs > 4096 or a.workers > 0):
         ap.error("a device env holds at most 4096 envs and needs no worker processes")
-    if device_task and a.envs > 64 and (a.per_alpha is not None or (a.hidden_sizes and (a.hidden_sizes.count("x") != 1 or max(map(int, a.hidden_sizes.split("x"))) > 256))):
-        ap.error("more than 64 device envs collect through fsrl_collect_device_wide: fused contexts (two hidden layers of at most 256 units) "
-                 "without prioritised replay")
+    if device_task and a.envs > 64 and a.per_alpha is not None:
+        ap.error("more than 64 device envs collect through fsrl_collect_device_wide / fsrl_collect_device_wide_layered: without prioritised replay")
     if a.task in ("point-circle", "device-point-circle"):
         # the reference's own construction (train_ppol_agent.py:120-123): one factory per env, in process or in worker processes
         from fsrl_amd.env import DummyVectorEnv, PointCircleEnv, ShmemVectorEnv

@@ -73,6 +73,7 @@ class DevEnvConfig(C.Structure):
 
 DEVENV_POINT_CIRCLE, DEVENV_LINEAR = 0, 1
 DC_MAX_ENVS, DCW_MAX_ENVS = 64, 4096       # envs of a device env / of a wide one (include/fsrl_hip.h)
+DCWL_LDS_WIDTH = 1024       # widest layer of a wide layered collect whose activations stay in LDS (csrc/devcollect_plan.hpp)
 
 # fsrl_sac_config / fsrl_cvpo_config .actor_mean: how the Gaussian actor's mean head becomes the mean
 ACTOR_MEAN_DEFAULT, ACTOR_MEAN_UNBOUNDED, ACTOR_MEAN_TANH = 0, 1, 2
@@ -254,6 +255,8 @@ SIGNATURES = {
                                       _i32, _i32]),
     "fsrl_collect_device_wide": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d, _i32,
                                       _i32, _i32]),
+    "fsrl_collect_device_wide_layered": (C.c_int, [_ctx, _ctx, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32, _i32, _d,
+                                                   _i32, _i32, _i32]),
     "fsrl_collect_device_wide_timing": (C.c_int, [_ctx, _d]),
     "fsrl_collect_device_group": (C.c_int, [_P(_ctx), _P(_ctx), C.c_int32, _i32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _i64, _d, _i32,
                                             _i32, _d, _i32, _i32, _i32]),

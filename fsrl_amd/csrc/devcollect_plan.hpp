@@ -78,6 +78,15 @@ DC_HD int32_t dc_wide_batch_steps(int32_t env_num, int32_t asked) {
     const int32_t s = asked > 0 ? asked : DC_DEFAULT_STEPS;
     return s < cap ? s : (cap < 1 ? 1 : cap);
 }
+// ---- wide collects for layered contexts (fsrl_collect_device_wide_layered, kernels_devcollect_wide_layered.hpp): a tile's
+// activations are two halves of 16 rows of ld = round_up(max(widest hidden layer, obs_dim), 4) floats.  Up to DCWL_LDS_WIDTH they
+// live in dynamic LDS at the row stride dc_wl_stride(ld) -- the first multiple of 4 at or above ld whose quarter is odd, so that the
+// sixteen rows of a 16-byte read fall into sixteen different four-bank groups; 128 x 1028 bytes at the limit, next to 10 KB of static
+// arrays in a CU's 160 KB -- and beyond it in a per-tile slice of a device-memory workspace, at stride ld.
+#define DCWL_LDS_WIDTH 1024
+DC_HD bool dc_wl_in_lds(int32_t ld) { return ld <= DCWL_LDS_WIDTH; }
+DC_HD int32_t dc_wl_stride(int32_t ld) { return !dc_wl_in_lds(ld) || ((ld >> 2) & 1) ? ld : ld + 4; }
+DC_HD int64_t dc_wl_lds_bytes(int32_t ld) { return dc_wl_in_lds(ld) ? (int64_t)2 * 16 * dc_wl_stride(ld) * 4 : 0; }
 // What persists between the launches of a wide collect.  Everything a launch writes that another workgroup of the SAME launch reads is
 // held twice, by the parity of the launch ordinal t: launch t reads side t & 1 and writes side (t + 1) & 1.  s[] describes the
 // collect as the step before left it: `pending` says that this step's flags in done[] have not been through the surplus rule yet (the

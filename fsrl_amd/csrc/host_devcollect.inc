@@ -18,6 +18,7 @@
 // with `layered = true`, lay_collect_kernel (kernels_devcollect_layered.hpp) in the launch and the env's activation workspace.
 #include "kernels_devcollect_layered.hpp"
 #include "kernels_devcollect_wide.hpp"
+#include "kernels_devcollect_wide_layered.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered);      // defined with the SAC / CVPO code
 static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax);    // ... and behind the layered code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -51,6 +52,10 @@ struct fsrl_devenv {
     WideCollectArgs* d_wargs = nullptr; WideCollectArgs* h_wargs = nullptr;     // device / pinned
     uint32_t wide_t = 0;                // launch ordinal of the next wide launch: its parity picks the state's side
     double wide_seconds[2] = {0.0, 0.0};        // the last wide collect: in all, in the host replay (fsrl_collect_device_wide_timing)
+    // a wide env of a layered context (fsrl_collect_device_wide_layered): the actor's row, device / pinned, made by the first such
+    // collect; d_ws is then [tiles][2][16][ws_ld], made only for shapes beyond DCWL_LDS_WIDTH (the looping layered collect never
+    // sees a wide env)
+    WideLayActor* d_wlact = nullptr; WideLayActor* h_wlact = nullptr;
 };
 static dim3 devenv_grid(int n) { return dim3((unsigned)((n + DC_MAX_ENVS - 1) / DC_MAX_ENVS)); }
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
@@ -284,13 +289,15 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     const char* const what = store ? "collects" : "evaluations";
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
-    if (!wide) CHECK_ARG(!v->wide, "a wide device env (fsrl_devenv_create_wide): its collects go through fsrl_collect_device_wide; evaluations, "
-                         "grouped and layered collects over wide envs are not supported yet");
-    else CHECK_ARG(v->wide, "fsrl_collect_device_wide takes a wide device env (fsrl_devenv_create_wide); this one collects through fsrl_collect_device");
-    if (!layered) CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
+    if (!wide) CHECK_ARG(!v->wide, "a wide device env (fsrl_devenv_create_wide): its collects go through fsrl_collect_device_wide (layered contexts: "
+                         "fsrl_collect_device_wide_layered); evaluations and grouped collects over wide envs are not supported yet");
+    else CHECK_ARG(v->wide, "fsrl_collect_device_wide%s takes a wide device env (fsrl_devenv_create_wide); this one collects through fsrl_collect_device%s",
+                   layered ? "_layered" : "", layered ? "_layered" : "");
+    if (!layered && wide) CHECK_ARG(!c->lay, "a layered context: its wide device collects go through fsrl_collect_device_wide_layered");
+    else if (!layered) CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
     else CHECK_ARG(c->lay, "a fused context (two hidden layers of at most 256 units): its device %s go through %s", what,
-                   store ? "fsrl_collect_device" : "fsrl_evaluate_device");
-    if (!named && store && !layered)
+                   wide ? "fsrl_collect_device_wide" : store ? "fsrl_collect_device" : "fsrl_evaluate_device");
+    if (!named && store && (!layered || wide))
         CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
         const float* P; const ModelDesc* md; const LayNet* net; int hmax;
@@ -302,7 +309,7 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     if (wide) CHECK_ARG(!c->per, "wide device collects are not supported on a context with prioritised replay on yet");
     if (c->in_update)
         return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device",
-                    wide ? "_wide" : layered ? "_layered" : named ? "_group" : "");
+                    wide ? (layered ? "_wide_layered" : "_wide") : layered ? "_layered" : named ? "_group" : "");
     CHECK_ARG(v->cfg.env_num <= (wide ? DCW_MAX_ENVS : DC_MAX_ENVS), "env_num %d above %d", v->cfg.env_num, wide ? DCW_MAX_ENVS : DC_MAX_ENVS);
     if (store) CHECK_ARG(v->cfg.env_num <= c->active_envs, "env_num %d but the store has %d sub-buffers", v->cfg.env_num, c->active_envs);
     CHECK_ARG(v->cfg.obs_dim == c->cfg.obs_dim && v->cfg.act_dim == c->cfg.act_dim, "env shape (obs_dim %d, act_dim %d) != context shape",
@@ -369,7 +376,16 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
         actor->md = nullptr;
         if (!devcollect_lay_actor(c, &actor->P, &actor->net, &hmax)) return fail(FSRL_ESTATE, "no layered actor network");
         const int ld = round_up(std::max(hmax, v->cfg.obs_dim), 4);        // layer 0's input, the observations, is gathered into it too
-        HIPCHK(v->mem.regrow(v->ws_ld, ld, ld, {Mem::D(&v->d_ws, (size_t)2 * DC_MAX_ENVS * ld * sizeof(float))}));
+        if (!wide) {
+            HIPCHK(v->mem.regrow(v->ws_ld, ld, ld, {Mem::D(&v->d_ws, (size_t)2 * DC_MAX_ENVS * ld * sizeof(float))}));
+        } else {        // a tile's activations: LDS, or its slice of [tiles][2][16][ld]; the actor's row goes up with the arguments
+            if (!dc_wl_in_lds(ld)) HIPCHK(v->mem.regrow(v->ws_ld, ld, ld, {Mem::D(&v->d_ws, (size_t)((n + 15) / 16) * 32 * ld * sizeof(float))}));
+            if (!v->d_wlact) HIPCHK(v->mem.dev(&v->d_wlact, sizeof(WideLayActor)));
+            if (!v->h_wlact) HIPCHK(v->mem.pinned(&v->h_wlact, sizeof(WideLayActor)));
+            WideLayActor& la = *v->h_wlact;
+            la.P = actor->P; la.ws = dc_wl_in_lds(ld) ? nullptr : v->d_ws; la.ld = ld; la.ldp = dc_wl_stride(ld);
+            la.unbounded = c->cfg.unbounded ? 1 : 0; la.net = *actor->net;
+        }
     }
     if (ctx_is_replay(c)) {
         if ((!layered && !sac_actor_resident_args(c, &actor->P, &actor->md)) || !sac_devcollect_head(c, &a, &actor->head, layered))
@@ -382,6 +398,7 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
         WideCollectArgs& w = *v->h_wargs;
         w.a = a; w.ws = v->d_wstate; w.log_cap = max_steps * n;
         HIPCHK(hipMemcpyAsync(v->d_wargs, v->h_wargs, sizeof(WideCollectArgs), hipMemcpyHostToDevice, s));
+        if (layered) HIPCHK(hipMemcpyAsync(v->d_wlact, v->h_wlact, sizeof(WideLayActor), hipMemcpyHostToDevice, s));
         return 0;
     }
     HIPCHK(hipMemcpyAsync(v->d_args, v->h_args, sizeof(DevCollectArgs), hipMemcpyHostToDevice, s));

@@ -8,7 +8,8 @@ the rows).  Layered engines (hidden_sizes of any depth and width) collect throug
 (fsrl_collect_device_layered / fsrl_evaluate_device_layered: one kernel for every shape, the weights streamed from L2); the collectors
 route on `_layered(engine)`.  A `DeviceCollector` of its own on a grouped fused engine is refused by the library, with the reason.
 A WIDE env (more than 64 envs, up to 4096, or `wide=True`) collects through fsrl_collect_device_wide: one launch per vector step, a
-workgroup per 16-row tile, `max_steps_per_launch` step launches per batch; without a buffer, on layered engines and in a
+workgroup per 16-row tile, `max_steps_per_launch` step launches per batch; on a layered engine through
+fsrl_collect_device_wide_layered, the same scheme with the layer-by-layer tile actor.  Without a buffer and in a
 `GroupDeviceCollector` a wide env is refused by name.
 
 Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
@@ -115,8 +116,8 @@ class DeviceCollector:
     # ------------------------------------------------------------------ collect
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
         eng = self.policy.engine
-        if self.env.wide:       # layered engines: the library refuses, by name
-            return self._collect(n_episode, eng.collect_device_wide)
+        if self.env.wide:
+            return self._collect(n_episode, eng.collect_device_wide_layered if _layered(eng) else eng.collect_device_wide)
         return self._collect(n_episode, eng.collect_device_layered if _layered(eng) else eng.collect_device)
 
     def _collect(self, n_episode, run) -> Dict[str, Any]:

@@ -458,6 +458,14 @@ class Engine:
         hi = np.ascontiguousarray(high, np.float32) if low is not None else None
         return self._collect_device(self.lib.fsrl_collect_device_wide, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
 
+    def collect_device_wide_layered(self, h, n_episode, deterministic=False, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.collect_device_wide for a LAYERED engine (hidden_sizes of any depth and width): fsrl_collect_device_wide_layered,
+        the same launch scheme around an actor that runs layer by layer on a tile's 16 rows.  The same arguments and result dict."""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_collect_device_wide_layered, h, n_episode, deterministic, bound_method, lo, hi,
+                                    max_steps_per_launch)
+
     def collect_device_wide_timing(self, h):
         """-> (seconds of the env's last wide collect, seconds of it in the host's log replay)"""
         out = np.zeros(2, np.float64)

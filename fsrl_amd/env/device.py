@@ -7,7 +7,8 @@ training collect (fsrl_collect_device), without one the evaluation that stores n
 agents' `learn(train_envs, test_envs)` and `evaluate(test_envs)` run over device test envs of their own engine.  Layered engines
 and `render=True` evaluate through `FastCollector` over `step`, call by call.  More than 64 envs (up to 4096), or `wide=True`, make
 a WIDE env (fsrl_devenv_create_wide): the same calling convention, and `DeviceCollector` collects it with one launch per vector step
-(fsrl_collect_device_wide); evaluations over wide envs go through `FastCollector`."""
+(fsrl_collect_device_wide; on a layered engine fsrl_collect_device_wide_layered); evaluations over wide envs go through
+`FastCollector`."""
 from types import SimpleNamespace
 
 import numpy as np

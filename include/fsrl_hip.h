@@ -1145,14 +1145,30 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
  *                            Refused before anything changes, by name: an env of fsrl_devenv_create; layered contexts; contexts in
  *                            any kind of group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device refuses.
  *                            fsrl_collect_device, fsrl_evaluate_device and their _group / _layered forms refuse a wide env and name
- *                            this call: evaluations, grouped and layered collects over wide envs are not supported yet.  */
+ *                            this call: evaluations and grouped collects over wide envs are not supported yet.
+ *      fsrl_collect_device_wide_layered   fsrl_collect_device_wide for LAYERED contexts (hidden_sizes of any depth and width, or
+ *                            force_layered; kernels_devcollect_wide_layered.hpp): the same arguments, outputs, batches, settle launches,
+ *                            log replay and timing, with one kernel for every shape in the launch -- a workgroup of 512 threads runs
+ *                            the actor on its tile's 16 rows layer by layer, the weights streamed from L2 one 64-k chunk ahead of the
+ *                            MFMAs, the activations in dynamic LDS sized to the shape (up to 1024-wide layers) or, beyond that, in
+ *                            a workspace of ceil(env_num / 16) x 2 x 16 x width floats the env owns from its first such collect on.
+ *                            Every output element is accumulated by the MFMA sequence of the layered forward launches: on twin
+ *                            contexts it agrees with fsrl_collect_device_layered bit for bit.
+ *                            Refused before anything changes, by name: a fused context (fsrl_collect_device_wide takes it, and
+ *                            keeps its refusal of layered contexts, now naming this call); an env of fsrl_devenv_create
+ *                            (fsrl_collect_device_layered takes it, and keeps its refusal of wide envs); contexts in any kind of
+ *                            group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device_wide refuses.  */
 #define DCW_MAX_ENVS 4096
 int fsrl_devenv_create_wide(fsrl_ctx* ctx, const fsrl_devenv_config* cfg, fsrl_devenv** out);
 int fsrl_collect_device_wide(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
                              const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
                              double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
                              int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
-/*      fsrl_collect_device_wide_timing   the env's last wide collect on the host's clock: out[0] seconds from the first launch to the
+int fsrl_collect_device_wide_layered(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                     const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                     double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                     int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_collect_device_wide_timing  the env's last wide collect on the host's clock: out[0] seconds from the first launch to the
  *                            end of the call, out[1] of them in the replay of the log (tools/bench_device_collect.py --wide).  */
 int fsrl_collect_device_wide_timing(fsrl_devenv* env, double* out);
 

@@ -366,8 +366,11 @@ def main():
                                                            "256x256x256,64x48x32) in one process, one --out file")
     ap.add_argument("--wide", action="store_true", help="the wide device collect (fsrl_collect_device_wide, one launch per vector step) at "
                                                         "--envs (default 20,64,256,1024,4096) beside the in-process lock-step path and, up "
-                                                        "to 64 envs, the looping device collect; the host replay's share of the wall time")
+                                                        "to 64 envs, the looping device collect; the host replay's share of the wall time; "
+                                                        "with --layered: on layered shapes, on-policy and SAC-Lag, in one file")
     a = ap.parse_args()
+    if a.wide and a.layered:
+        return main_wide_layered(a)
     if a.wide:
         return main_wide(a)
     if a.layered:
@@ -395,6 +398,26 @@ def main_layered(a):
     a.algo, a.ks = "onpolicy", ks
     result["groups"] = main_groups(a)
     result["eval"] = main_eval(a)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
+
+
+def main_wide_layered(a):
+    """--wide --layered: the legs of --wide on layered shapes (default 256x256x256,64x48x32), on-policy and --algo's replay agent
+    (default SAC-Lag), in one process and one --out file.  The `wide` leg is fsrl_collect_device_wide_layered, the `device` leg (up
+    to 64 envs) the looping layered collect, `in_process` the lock-step path."""
+    if "x" not in a.hidden:
+        a.hidden = "256x256x256,64x48x32"
+    assert all(isinstance(h, tuple) for h in parse_hidden(a.hidden)), "--wide --layered: every --hidden entry is written with x"
+    out, a.out = a.out, None
+    replay = a.algo if a.algo != "onpolicy" else "sacl"
+    result = dict(metric="wide layered device collects (fsrl_collect_device_wide_layered) beside the in-process lock-step path and, up to "
+                         "64 envs, the looping layered collect; linear env obs 8 / act 2, episode length 300", rounds=a.rounds, calls=a.calls)
+    for a.algo in ("onpolicy", replay):
+        result[a.algo] = main_wide(a)
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
