@@ -78,6 +78,31 @@ DC_HD int32_t dc_wide_batch_steps(int32_t env_num, int32_t asked) {
     const int32_t s = asked > 0 ? asked : DC_DEFAULT_STEPS;
     return s < cap ? s : (cap < 1 ? 1 : cap);
 }
+// ---- k wide collects in one launch per vector step (fsrl_collect_device_wide_group).  The grid is the members' tiles laid end to end:
+// prefix[m] = tiles in front of member m, and every entry from k on holds the grid, so that a search over all DCWG_MAX_MEMBERS
+// entries needs no k.  A workgroup's member is the number of entries 1 .. DCWG_MAX_MEMBERS - 1 at or below its block number: fifteen
+// comparisons, the same for every block.  Every member has at least one tile (env_num, n_episode >= 1).
+#define DCWG_MAX_MEMBERS 16     // FSRL_MAX_GROUP
+DC_HD int32_t dc_wide_tiles(int32_t env_num, int32_t n_episode) { return (dc_first_live(env_num, n_episode) + 15) / 16; }
+DC_HD int32_t dc_wgroup_prefix(const int32_t* env_num, const int32_t* n_episode, int32_t k, int32_t* prefix) {      // prefix[DCWG_MAX_MEMBERS + 1] -> the grid
+    int32_t at = 0;
+    for (int32_t i = 0; i <= DCWG_MAX_MEMBERS; ++i) {
+        prefix[i] = at;
+        if (i < k) at += dc_wide_tiles(env_num[i], n_episode[i]);
+    }
+    return at;
+}
+DC_HD int32_t dc_wgroup_member(const int32_t* prefix, int32_t b) {
+    int32_t m = 0;
+    for (int32_t i = 1; i < DCWG_MAX_MEMBERS; ++i) m += b >= prefix[i] ? 1 : 0;
+    return m;
+}
+// a batch's step launches: dc_wide_batch_steps of the LARGEST member, so that every member's log holds the batch
+DC_HD int32_t dc_wgroup_batch_steps(const int32_t* env_num, int32_t k, int32_t asked) {
+    int32_t widest = 1;
+    for (int32_t i = 0; i < k; ++i) widest = env_num[i] > widest ? env_num[i] : widest;
+    return dc_wide_batch_steps(widest, asked);
+}
 // ---- wide collects for layered contexts (fsrl_collect_device_wide_layered, kernels_devcollect_wide_layered.hpp): a tile's
 // activations are two halves of 16 rows of ld = round_up(max(widest hidden layer, obs_dim), 4) floats.  Up to DCWL_LDS_WIDTH they
 // live in dynamic LDS at the row stride dc_wl_stride(ld) -- the first multiple of 4 at or above ld whose quarter is odd, so that the

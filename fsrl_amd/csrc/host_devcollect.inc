@@ -56,6 +56,10 @@ struct fsrl_devenv {
     // collect; d_ws is then [tiles][2][16][ws_ld], made only for shapes beyond DCWL_LDS_WIDTH (the looping layered collect never
     // sees a wide env)
     WideLayActor* d_wlact = nullptr; WideLayActor* h_wlact = nullptr;
+    // member 0's env of a grouped wide collect (fsrl_collect_device_wide_group): the member table and the block the settle launch
+    // gathers the members' settled scalars in, device / pinned, made by the first such collect
+    WideGroupTable* d_wgtab = nullptr; WideGroupTable* h_wgtab = nullptr;
+    DcwScalars* d_wgs = nullptr; DcwScalars* h_wgs = nullptr;
 };
 static dim3 devenv_grid(int n) { return dim3((unsigned)((n + DC_MAX_ENVS - 1) / DC_MAX_ENVS)); }
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
@@ -290,7 +294,8 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
     if (!wide) CHECK_ARG(!v->wide, "a wide device env (fsrl_devenv_create_wide): its collects go through fsrl_collect_device_wide (layered contexts: "
-                         "fsrl_collect_device_wide_layered); evaluations and grouped collects over wide envs are not supported yet");
+                         "fsrl_collect_device_wide_layered; k members' in one launch per step: fsrl_collect_device_wide_group); evaluations over wide "
+                         "envs are not supported yet");
     else CHECK_ARG(v->wide, "fsrl_collect_device_wide%s takes a wide device env (fsrl_devenv_create_wide); this one collects through fsrl_collect_device%s",
                    layered ? "_layered" : "", layered ? "_layered" : "");
     if (!layered && wide) CHECK_ARG(!c->lay, "a layered context: its wide device collects go through fsrl_collect_device_wide_layered");

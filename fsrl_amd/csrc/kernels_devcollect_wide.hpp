@@ -28,6 +28,16 @@
 #pragma once
 #include "kernels_devcollect.hpp"
 
+// The grouped kernels are compiled without the packed-fp32 instructions (v_pk_add / mul / fma_f32), as wide_layered_step_kernel is.
+// Not for register fit: with them the 256-wide forms take 128 / 126 VGPRs and do not spill.  The one-lane forms round identically
+// (the bits are the solo kernels'), and the rate is the same with and without to the measurement's last stable digit (DESIGN.md
+// 3.4.1), so the attribute is free and keeps the new kernels independent of how the two-lane forms behave.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DCW_NO_PK __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DCW_NO_PK           // the host pass does not know the feature
+#endif
+
 struct WideCollectArgs {
     DevCollectArgs a;       // a.state and a.max_steps are not read
     DcwState* ws;
@@ -131,19 +141,22 @@ __device__ __forceinline__ void dcw_env_step(const DevCollectArgs& a, DevCollect
     }
 }
 
+// One workgroup's launch: a tile of ONE collect, whoever launched it.  wp: the collect's arguments, a uniform pointer into constant memory
+// (dc_uniform_ptr<4>); t: the collect's own launch ordinal; tile: the tile's number in that collect's live list, uniform.  `settled`
+// (uniform, or null): where the writer also leaves the state it hands on -- the grouped settle launch gathers the members' there.
+// wide_collect_step_kernel and wide_collect_group_step_kernel are this function behind two ways of finding (wp, P, t, tile).
 template <int H, class Env, int HEAD>
-__global__ __launch_bounds__(4 * H) void wide_collect_step_kernel(const ModelDesc md, const float* __restrict__ P, const WideCollectArgs* __restrict__ wap,
-                                                                  const int t, const int first, const int settle) {
+__device__ __forceinline__ void wide_collect_step_body(const ModelDesc& md, const float* __restrict__ P, const WideCollectArgs* wp, const int t, const int first,
+                                                       const int settle, const int tile, DcwScalars* settled) {
     __shared__ TileSmem<H> sm;
     __shared__ DevCollectSmem sh;
     __shared__ int32_t wtot[16];
     constexpr int NT = TileGeom<H>::NT;
     constexpr int NX = TileStage<H>::NX;
-    const WideCollectArgs* wp = dc_uniform_ptr<4>(wap);
     const DevCollectArgs& a = wp->a;
     DcwState* ws = wp->ws;
     const int side = t & 1, nside = side ^ 1;
-    const int tile0 = 16 * __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const int tile0 = 16 * tile;
     const bool writer = tile0 == 0;
     const int tid = threadIdx.x;
     const NetOff no = md.net[0];
@@ -164,6 +177,7 @@ __global__ __launch_bounds__(4 * H) void wide_collect_step_kernel(const ModelDes
         DcwScalars nx = s;
         if (go) { nx.log_rows = s.log_rows + s.n_live; nx.steps = s.steps + 1; nx.pending = 1; }
         ws->s[nside] = nx;
+        if (settled) *settled = nx;
     }
     if (!go || tile0 >= s.n_live) return;
     const int n_valid = min(16, s.n_live - tile0);
@@ -195,4 +209,50 @@ __global__ __launch_bounds__(4 * H) void wide_collect_step_kernel(const ModelDes
     dc_store_rows(a, sh, lt, NT, n_valid, Do, Da);
     __syncthreads();
     dc_next_obs<Env>(a, sh, lt, n_valid, Do);
+}
+
+template <int H, class Env, int HEAD>
+__global__ __launch_bounds__(4 * H) void wide_collect_step_kernel(const ModelDesc md, const float* __restrict__ P, const WideCollectArgs* __restrict__ wap,
+                                                                  const int t, const int first, const int settle) {
+    wide_collect_step_body<H, Env, HEAD>(md, P, dc_uniform_ptr<4>(wap), t, first, settle, __builtin_amdgcn_readfirstlane((int)blockIdx.x), nullptr);
+}
+
+// ---- k wide collects in one launch per vector step (fsrl_collect_device_wide_group, host_devcollect_wide_group.inc).
+// The grid is the members' tiles laid end to end -- sum over members of ceil(first_live_m / 16) workgroups, fixed for the collect --
+// not a k x max-tiles rectangle: members may differ in env_num by two orders of magnitude (17 envs beside 4096 would launch 512
+// workgroups for 258 tiles).  A workgroup finds (member, tile) from the prefix of tile counts with scalar loads and fifteen scalar
+// comparisons (dc_wgroup_member, devcollect_plan.hpp), reads its member's row with scalar loads and runs wide_collect_step_body on
+// that member's pointers: its own WideCollectArgs (store, env arrays, log, DcwState, log_cap), parameters and launch ordinal
+// t_m = par0[m] + j (only the parity of an ordinal is ever read) -- every env counts its own launches (fsrl_devenv::wide_t), members arrive with different parities, and all of
+// them advance by one per launch of the call.  Phase 5' runs over the member's flags and live list in each of its workgroups, the
+// writer is the member's tile 0, a finished member's workgroups and tiles beyond its live count exit at the first test.  Nothing is
+// shared between members, so the launch has the solo launch's property between ALL its workgroups: no word one of them writes is
+// read by another, no atomics, fences or waits.
+// The settle launch (settle = 1) is k workgroups, workgroup m the tile 0 of member m; it also leaves the settled scalars of member
+// m in settled[m], so that the host reads every member's back with one copy.
+// md is member 0's: the host checks that the members agree on what it describes, as for collect_device_group_kernel.  The row is
+// read through constant address space, whenever a field is needed: nothing of it has to live in a vector register.
+struct WideGroupTable {
+    int32_t prefix[DCWG_MAX_MEMBERS + 1];       // tiles in front of member m; from k on: the grid
+    int32_t par0[DCWG_MAX_MEMBERS];             // the PARITY of the member's launch ordinal at the call's first launch
+    const WideCollectArgs* wa[DCWG_MAX_MEMBERS];
+    const float* P[DCWG_MAX_MEMBERS];           // fused members: the actor's parameters
+    const struct WideLayActor* la[DCWG_MAX_MEMBERS];   // layered members: the actor's row (kernels_devcollect_wide_layered.hpp)
+};
+static_assert(DCWG_MAX_MEMBERS == FSRL_MAX_GROUP, "the plan's member count is the group's");
+// (member, tile) of this workgroup, both in scalar registers
+__device__ __forceinline__ void dcwg_find(const WideGroupTable* tb, const int settle, int& m, int& tile) {
+    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    m = settle ? b : __builtin_amdgcn_readfirstlane(dc_wgroup_member(tb->prefix, b));
+    tile = settle ? 0 : b - tb->prefix[m];
+}
+template <int H, class Env, int HEAD>
+__global__ __launch_bounds__(4 * H) DCW_NO_PK void wide_collect_group_step_kernel(const ModelDesc md, const WideGroupTable* __restrict__ tab,
+                                                                                  DcwScalars* __restrict__ settled, const int j, const int first,
+                                                                                  const int settle) {
+    const WideGroupTable* tb = dc_uniform_ptr<4>(tab);
+    int m, tile;
+    dcwg_find(tb, settle, m, tile);
+    wide_collect_step_body<H, Env, HEAD>(md, dc_uniform_ptr<1>(tb->P[m]), dc_uniform_ptr<4>(tb->wa[m]), tb->par0[m] + j, first, settle, tile,
+                                         settle ? settled + m : nullptr);
 }

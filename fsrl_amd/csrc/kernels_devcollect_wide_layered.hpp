@@ -100,20 +100,19 @@ __device__ __forceinline__ const float* wl_wrow(const float* P, const LayLayer& 
 #else
 #define WL_NO_PK            // the host pass does not know the feature
 #endif
+// One workgroup's launch: a tile of ONE collect (wide_collect_step_body's arguments, the actor's row in the place of (md, P)); both
+// pointers are uniform and point into constant memory (read through dc_uniform_ptr<4> here).  wide_layered_step_kernel and wide_layered_group_step_kernel call it.
 template <class Env, int HEAD, bool DEVWS>
-__global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_layered_step_kernel(const WideCollectArgs* __restrict__ wap, const WideLayActor* __restrict__ lap,
-                                                                           const int t, const int first, const int settle) {
-    extern __shared__ __align__(16) float wl_lds[];             // !DEVWS: [2][16][ldp]
-    __shared__ DevCollectSmem sh;                               // the tile uses its first 16 rows
-    __shared__ float raw[16 * FSRL_MAX_ACT];                    // the head's raw rows
-    __shared__ int32_t wtot[16];
+__device__ __forceinline__ void wide_layered_step_body(const WideCollectArgs* __restrict__ wap, const WideLayActor* __restrict__ lap, const int t, const int first,
+                                                       const int settle, const int tile, DcwScalars* settled, float* wl_lds, DevCollectSmem& sh,
+                                                       float* raw, int32_t* wtot) {
     const WideCollectArgs* wp = dc_uniform_ptr<4>(wap);
     const WideLayActor& la = *dc_uniform_ptr<4>(lap);
     const DevCollectArgs& a = wp->a;
     DcwState* ws = wp->ws;
     const float* P = dc_uniform_ptr<1>(la.P);
     const int side = t & 1, nside = side ^ 1;
-    const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x), tile0 = 16 * tile;
+    const int tile0 = 16 * tile;
     const bool writer = tile0 == 0;
     const int Do = a.ep.Do, Da = a.ep.Da, ldp = la.ldp, nl = la.net.nl;
     f32x4 b0[4], b1[4];         // the weights of this unit and of the one behind it: b0 holds the current unit's while par == 0
@@ -135,6 +134,7 @@ __global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_layered_step_kernel(const
         DcwScalars nx = s;
         if (go) { nx.log_rows = s.log_rows + s.n_live; nx.steps = s.steps + 1; nx.pending = 1; }
         ws->s[nside] = nx;
+        if (settled) *settled = nx;
     }
     if (!go || tile0 >= s.n_live) return;
     const int n_valid = min(16, s.n_live - tile0);
@@ -217,4 +217,32 @@ __global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_layered_step_kernel(const
     dc_store_rows(a, sh, lt, WL_NT, n_valid, Do, Da);
     __syncthreads();
     dc_next_obs<Env>(a, sh, lt, n_valid, Do);
+}
+
+template <class Env, int HEAD, bool DEVWS>
+__global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_layered_step_kernel(const WideCollectArgs* __restrict__ wap, const WideLayActor* __restrict__ lap,
+                                                                           const int t, const int first, const int settle) {
+    extern __shared__ __align__(16) float wl_lds[];             // !DEVWS: [2][16][ldp]
+    __shared__ DevCollectSmem sh;                               // the tile uses its first 16 rows
+    __shared__ float raw[16 * FSRL_MAX_ACT];                    // the head's raw rows
+    __shared__ int32_t wtot[16];
+    wide_layered_step_body<Env, HEAD, DEVWS>(wap, lap, t, first, settle, __builtin_amdgcn_readfirstlane((int)blockIdx.x), nullptr, wl_lds, sh, raw, wtot);
+}
+
+// ---- k wide layered collects in one launch per vector step: the grid, the member table and the settle launch of
+// wide_collect_group_step_kernel (kernels_devcollect_wide.hpp) around wide_layered_step_body.  A member's row names its own
+// WideLayActor -- parameters, LayNet, and in the DEVWS form its own workspace, indexed by the tile's number in THAT member's list.
+// The members share hidden_sizes (the host checks it), so one dynamic LDS size and one form serve the whole launch.
+template <class Env, int HEAD, bool DEVWS>
+__global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_layered_group_step_kernel(const WideGroupTable* __restrict__ tab, DcwScalars* __restrict__ settled,
+                                                                                 const int j, const int first, const int settle) {
+    extern __shared__ __align__(16) float wl_lds[];             // !DEVWS: [2][16][ldp]
+    __shared__ DevCollectSmem sh;                               // the tile uses its first 16 rows
+    __shared__ float raw[16 * FSRL_MAX_ACT];                    // the head's raw rows
+    __shared__ int32_t wtot[16];
+    const WideGroupTable* tb = dc_uniform_ptr<4>(tab);
+    int m, tile;
+    dcwg_find(tb, settle, m, tile);
+    wide_layered_step_body<Env, HEAD, DEVWS>(tb->wa[m], tb->la[m], tb->par0[m] + j, first, settle, tile,
+                                             settle ? settled + m : nullptr, wl_lds, sh, raw, wtot);
 }

@@ -9,13 +9,16 @@ the rows).  Layered engines (hidden_sizes of any depth and width) collect throug
 route on `_layered(engine)`.  A `DeviceCollector` of its own on a grouped fused engine is refused by the library, with the reason.
 A WIDE env (more than 64 envs, up to 4096, or `wide=True`) collects through fsrl_collect_device_wide: one launch per vector step, a
 workgroup per 16-row tile, `max_steps_per_launch` step launches per batch; on a layered engine through
-fsrl_collect_device_wide_layered, the same scheme with the layer-by-layer tile actor.  Without a buffer and in a
-`GroupDeviceCollector` a wide env is refused by name.
+fsrl_collect_device_wide_layered, the same scheme with the layer-by-layer tile actor.  Without a buffer (an evaluation) a wide env
+is refused by name.
 
 Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
 through `GroupDeviceCollector(collectors)`: ONE launch per `max_steps_per_launch` vector steps carries every member's collect, a
 workgroup per member (fsrl_collect_device_group), and each member's rows, env states, statistics and counters are what its own
 `DeviceCollector.collect` would have produced, bit for bit.  `GroupCollector` over `DeviceCollector`s delegates to it.
+Members whose envs are all WIDE collect through fsrl_collect_device_wide_group: one launch per vector step carries the 16-row tiles
+of every member, fused or layered, and each member again gets its own solo wide collect bit for bit; a mix of wide and narrow envs
+is refused, the member named.
 
 Evaluation: `DeviceCollector(policy, test_envs)` with no buffer is the reference's `FastCollector(policy, test_envs)` (it makes a
 `DeviceEvalCollector`, whose collect() is the other library call; a storing collector's collect() only ever sees training envs) -- the
@@ -175,12 +178,19 @@ class GroupDeviceCollector:
             assert _layered(c.policy.engine) == self.layered, \
                 f"GroupDeviceCollector: member {i} is a {'layered' if not self.layered else 'fused'} engine and member 0 a " \
                 f"{'layered' if self.layered else 'fused'} one; a group is all layered or all fused"
+        # one launch scheme: the members' envs are all wide (a launch per vector step) or all narrow (the looping launch)
+        self.wide = bool(self.collectors[0].env.wide)
+        for i, c in enumerate(self.collectors):
+            assert bool(c.env.wide) == self.wide, \
+                f"GroupDeviceCollector: member {i}'s env is {'narrow (at most 64 envs)' if self.wide else 'wide'} and member 0's " \
+                f"{'wide' if self.wide else 'narrow'}; a group's envs are all wide (fsrl_collect_device_wide_group) or all narrow"
         self.max_steps_per_launch = int(max_steps_per_launch)
         self.last_launches = 0
 
     def collect(self, n_episode: Union[int, Sequence[int]] = 1, **_ignored) -> List[Dict[str, Any]]:
         """n_episode: one count or one per member -> one stats dict per member, with the keys of DeviceCollector.collect"""
-        from fsrl_amd.engine import collect_device_group, collect_device_layered, evaluate_device_group, evaluate_device_layered
+        from fsrl_amd.engine import (collect_device_group, collect_device_layered, collect_device_wide_group, evaluate_device_group,
+                                     evaluate_device_layered)
         cols = self.collectors
         n = len(cols)
         ns = [int(n_episode)] * n if np.isscalar(n_episode) else [int(x) for x in n_episode]
@@ -199,6 +209,9 @@ class GroupDeviceCollector:
         highs = None if args[0][2] is None else np.stack([a[3] for a in args])
         run = ((collect_device_layered if self.store else evaluate_device_layered) if self.layered
                else (collect_device_group if self.store else evaluate_device_group))
+        if self.wide:
+            assert self.store, "GroupDeviceCollector: evaluations over wide device envs are not supported yet (fsrl_collect_device_wide_group stores)"
+            run = collect_device_wide_group
         res = run([col.policy.engine for col in cols], [col.env._h for col in cols], ns, det, bound, lows, highs, self.max_steps_per_launch)
         dt = max(time.time() - t0, 1e-9)
         stats = []

@@ -1110,6 +1110,17 @@ def evaluate_device_layered(engines, env_handles, n_episodes, deterministic=True
                                 _fn="fsrl_evaluate_device_layered")
 
 
+def collect_device_wide_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
+                              max_steps_per_launch=0):
+    """Engine.collect_device_wide / collect_device_wide_layered for k engines with ONE launch per vector step for all of them
+    (fsrl_collect_device_wide_group): the members' 16-row tiles are the workgroups of one grid, and member i's collect is its own
+    solo wide collect, bit for bit.  Every env is a wide one (65 .. 4096 envs, or wide=True); the engines are all fused or all
+    layered, ungrouped or members of any kind of group.  max_steps_per_launch: step launches per batch.  Arguments and result as
+    collect_device_group."""
+    return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch,
+                                _fn="fsrl_collect_device_wide_group")
+
+
 def collect_device_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
                          max_steps_per_launch=0, _store=True, _fn=None):
     """Engine.collect_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_collect_device_group):

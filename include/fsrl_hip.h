@@ -1145,7 +1145,8 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
  *                            Refused before anything changes, by name: an env of fsrl_devenv_create; layered contexts; contexts in
  *                            any kind of group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device refuses.
  *                            fsrl_collect_device, fsrl_evaluate_device and their _group / _layered forms refuse a wide env and name
- *                            this call: evaluations and grouped collects over wide envs are not supported yet.
+ *                            this call: evaluations over wide envs are not supported yet; grouped collects over wide envs go
+ *                            through fsrl_collect_device_wide_group.
  *      fsrl_collect_device_wide_layered   fsrl_collect_device_wide for LAYERED contexts (hidden_sizes of any depth and width, or
  *                            force_layered; kernels_devcollect_wide_layered.hpp): the same arguments, outputs, batches, settle launches,
  *                            log replay and timing, with one kernel for every shape in the launch -- a workgroup of 512 threads runs
@@ -1157,7 +1158,23 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
  *                            Refused before anything changes, by name: a fused context (fsrl_collect_device_wide takes it, and
  *                            keeps its refusal of layered contexts, now naming this call); an env of fsrl_devenv_create
  *                            (fsrl_collect_device_layered takes it, and keeps its refusal of wide envs); contexts in any kind of
- *                            group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device_wide refuses.  */
+ *                            group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device_wide refuses.
+ *      fsrl_collect_device_wide_group   k members' wide collects, ONE launch per vector step for all of them
+ *                            (host_devcollect_wide_group.inc): the arguments and output layout of fsrl_collect_device_group, every
+ *                            env a wide one.  The grid of a step launch is the members' tiles laid end to end, the sum of
+ *                            ceil(min(env_num, n_episode) / 16) workgroups; a workgroup finds its member and tile in a table in
+ *                            device memory and runs the solo kernel's body on that member's store, env arrays, log and state, under
+ *                            the member's own launch ordinal.  A batch is S step launches, S = max_steps_per_launch cut by the
+ *                            LARGEST member's log (<= 0: min(64, 2^20 / its env_num)), and one settle launch of k workgroups; then
+ *                            one copy brings every member's settled scalars back, the logs follow, and each member is replayed as
+ *                            solo.  The call ends when every member has finished; all envs of all members are reset.  Each
+ *                            member's rows, env states, books, statistics and random streams are what fsrl_collect_device_wide /
+ *                            _wide_layered leave on a twin context, bit for bit.  *launches_out: the call's kernel launches.
+ *                            Members may sit in any kind of group or in none, and are all fused or all layered.
+ *                            Refused before anything changes, the member named: an env of fsrl_devenv_create; a fused member
+ *                            beside a layered one; a context or env listed twice; a trajectory tap; prioritised replay; a call
+ *                            inside an update; and what fsrl_collect_device_group asks members to agree on -- device, head kind,
+ *                            network shape (layered: hidden_sizes), env kind, max_episode_steps, unbounded / actor_mean.  */
 #define DCW_MAX_ENVS 4096
 int fsrl_devenv_create_wide(fsrl_ctx* ctx, const fsrl_devenv_config* cfg, fsrl_devenv** out);
 int fsrl_collect_device_wide(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
@@ -1168,6 +1185,10 @@ int fsrl_collect_device_wide_layered(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_
                                      const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
                                      double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
                                      int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+int fsrl_collect_device_wide_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                   int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                   int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                   double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 /*      fsrl_collect_device_wide_timing  the env's last wide collect on the host's clock: out[0] seconds from the first launch to the
  *                            end of the call, out[1] of them in the replay of the log (tools/bench_device_collect.py --wide).  */
 int fsrl_collect_device_wide_timing(fsrl_devenv* env, double* out);

@@ -149,9 +149,12 @@ def timed_loop(eng, col, n, calls, algo, update_per_step, batch):
     return rows, time.perf_counter() - t0, k
 
 
-def setup_group(path, hidden, n, k):
-    """k on-policy seeds for one of the grouped paths -> (engines, envs, EngineGroup or None, an object with .collect(n) -> stats per seed)"""
-    from fsrl_amd.data import GroupCollector, GroupDeviceCollector
+def setup_group(path, hidden, n, k, wide=False, algo="onpolicy"):
+    """k seeds for one of the grouped paths -> (engines, envs, EngineGroup or None, an object with .collect(n) -> stats per seed).
+    wide: the device envs are wide ones, so that `grouped` is fsrl_collect_device_wide_group and `solo_seq` k solo wide collects;
+    algo 'sacl' (wide only): SAC-Lag seeds, ungrouped engines, lock step through an EngineCollectGroup"""
+    if algo != "onpolicy":
+        return setup_group_replay(path, hidden, n, k, algo)
     engs, envs, cols = [], [], []
     for i in range(k):
         eng = Engine(EngineConfig(obs_dim=8, act_dim=2, env_num=n, buffer_size=n * 2 * EPISODE_LEN, **hidden_kw(hidden)), device=0)
@@ -161,18 +164,36 @@ def setup_group(path, hidden, n, k):
         if path == "lock_step":
             cols.append(FastCollector(pol, host, buf, device_actor=True))
         else:
-            envs.append(DeviceLinear(eng, like=host, seed=1 + i))
+            envs.append(DeviceLinear(eng, like=host, seed=1 + i, wide=True if wide else None))
             cols.append(DeviceCollector(pol, envs[-1], buf))
         engs.append(eng)
     group = EngineGroup(engs) if path != "solo_seq" else None
+    return engs, envs, group, group_collector(path, group, cols)
+
+
+def setup_group_replay(path, hidden, n, k, algo):
+    """setup_group for k SAC-Lag seeds over wide envs (setup()'s engines with parameters of their own)"""
+    from fsrl_amd.engine import EngineCollectGroup
+    engs, envs, cols = [], [], []
+    for i in range(k):
+        eng, env, col = setup("in_process" if path == "lock_step" else "wide", hidden, n, algo)
+        eng.sac_put_params(0, (0.1 * np.random.default_rng(10 + i).standard_normal(eng.n_sac_actor)).astype(np.float32))
+        engs.append(eng); cols.append(col)
+        if env is not None:
+            envs.append(env)
+    group = EngineCollectGroup(engs) if path == "lock_step" else None
+    return engs, envs, group, group_collector(path, group, cols)
+
+
+def group_collector(path, group, cols):
+    from fsrl_amd.data import GroupCollector, GroupDeviceCollector
 
     class Seq:
         collectors = cols
 
         def collect(self, n_episode):
             return [c.collect(n_episode=n_episode) for c in cols]
-    col = Seq() if path == "solo_seq" else GroupDeviceCollector(cols) if path == "grouped" else GroupCollector(group, cols)
-    return engs, envs, group, col
+    return Seq() if path == "solo_seq" else GroupDeviceCollector(cols) if path == "grouped" else GroupCollector(group, cols)
 
 
 def timed_group(col, n, calls):
@@ -203,11 +224,12 @@ def solo_ab(a):
             with tempfile.TemporaryDirectory() as tmp:
                 out = os.path.join(tmp, "r.json")
                 env = {k: v for k, v in os.environ.items() if k != "FSRL_HIP_LIB"}
-                subprocess.run([sys.executable, tool, "--rounds", "1", "--calls", str(a.calls), "--envs", a.envs, "--hidden", a.hidden, "--out", out],
+                subprocess.run([sys.executable, tool, "--rounds", "1", "--calls", str(a.calls), "--envs", a.envs, "--hidden", a.hidden, "--out", out]
+                               + (["--wide", "--algo", a.algo] if a.wide else []),
                                check=True, stdout=subprocess.DEVNULL, env=env, cwd=os.path.dirname(os.path.dirname(tool)), timeout=600)
                 with open(out) as f:
                     for c in json.load(f)["configs"]:
-                        rates.setdefault((shape_name(c), c["env_num"]), {}).setdefault(who, []).append(c["device"]["median"])
+                        rates.setdefault((shape_name(c), c["env_num"]), {}).setdefault(who, []).append(c["wide" if a.wide else "device"]["median"])
     res = []
     for (hidden, n), r in sorted(rates.items(), reverse=True):
         res.append(dict(hidden=[int(w) for w in hidden.split("x")], env_num=n, tree=summary(r["tree"]), other=summary(r["other"])))
@@ -215,14 +237,21 @@ def solo_ab(a):
     return res
 
 
-def main_groups(a):
+def main_groups(a, wide=False):
+    """wide: the legs over wide envs -- (a) `grouped` fsrl_collect_device_wide_group, (b) `solo_seq` k solo wide collects one after
+    the other, (c) `lock_step`; per config also us per vector step of (a) and (b) (a vector step: one step of every seed) and the
+    host replay's share of (a)'s wall time"""
     paths = ("grouped", "solo_seq", "lock_step")
     result = dict(metric="aggregate env-steps/s of k seeds' collects on one GPU, training mode, linear env obs 8 / act 2, episode length 300, "
-                         "on-policy contexts", rounds=a.rounds, calls=a.calls, configs=[])
+                         + ("wide device envs (fsrl_collect_device_wide_group against k solo wide collects and lock step; us_per_vector_step: one step of every seed; "
+                            "replay_share: the members' host replay seconds summed over the grouped call's seconds), " + a.algo if wide
+                            else "on-policy contexts"), rounds=a.rounds, calls=a.calls, configs=[])
     for hidden in parse_hidden(a.hidden):
-        for n in (int(e) for e in a.envs.split(",")):
-            for k in (int(x) for x in a.ks.split(",")):
-                objs = {p: setup_group(p, hidden, n, k) for p in paths}
+        for n, at in ((int(e.partition("@")[0]), e.partition("@")[2]) for e in a.envs.split(",")):       # 4096@8: 4096 envs at k = 8 alone
+            for k in (int(x) for x in a.ks.split(",") if x != "0"):         # --ks 0 with --ab-tree: the solo A/B alone
+                if at and k != int(at):
+                    continue
+                objs = {p: setup_group(p, hidden, n, k, wide, a.algo if wide else "onpolicy") for p in paths}
                 rates = {p: [] for p in paths}
                 for _ in range(a.rounds):
                     for p in paths:
@@ -231,6 +260,11 @@ def main_groups(a):
                 cfg = dict(hidden=hidden_list(hidden), env_num=n, k=k, launches_per_collect=objs["grouped"][3].last_launches)
                 for p in paths:
                     cfg[p] = summary(rates[p])
+                if wide:        # a vector step moves n * k envs; the last grouped collect's clock: the call's seconds, the members' replays
+                    engs, envs = objs["grouped"][0], objs["grouped"][1]
+                    clock = [e.collect_device_wide_timing(v._h) for e, v in zip(engs, envs)]
+                    cfg["us_per_vector_step"] = {p: 1e6 * n * k / cfg[p]["median"] for p in ("grouped", "solo_seq")}
+                    cfg["replay_share"] = float(sum(c[1] for c in clock) / clock[0][0])
                 result["configs"].append(cfg)
                 print(json.dumps(cfg), flush=True)
                 for engs, envs, group, col in objs.values():
@@ -249,6 +283,26 @@ def main_groups(a):
             json.dump(result, f, indent=1)
     print(json.dumps(dict(device_collect_group=[(shape_name(c), c["env_num"], c["k"], round(c["grouped"]["median"]), round(c["solo_seq"]["median"]),
                                                  round(c["lock_step"]["median"])) for c in result["configs"]])))
+    return result
+
+
+def main_wide_groups(a):
+    """--wide --ks: main_groups over wide envs once per --algo entry -> one file, `runs` = [(algo, configs)]; --ab-tree: the solo wide
+    collects of this tree against another built checkout's at --envs / --hidden (first algo), in `solo_tree_vs_other`"""
+    out, a.out, ab, a.ab_tree, algos = a.out, None, a.ab_tree, None, a.algo.split(",")
+    result = dict(rounds=a.rounds, calls=a.calls, runs=[])
+    for a.algo in algos:
+        r = main_groups(a, wide=True)
+        result.setdefault("metric", r["metric"].rsplit(", ", 1)[0] + "; algo per run")
+        result["runs"].append(dict(algo=a.algo, configs=r["configs"]))
+    if ab:
+        a.algo, a.ab_tree = algos[0], ab
+        result["solo_tree_vs_other"] = dict(what="solo fsrl_collect_device_wide / _wide_layered, env-steps/s: this tree against the tree it was measured "
+                                                 "next to (the parent commit), processes alternating, one round per process", configs=solo_ab(a))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
     return result
 
 
@@ -350,7 +404,8 @@ def main_eval(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", choices=["onpolicy", "sacl", "ddpgl", "cvpo"], default="onpolicy")
+    ap.add_argument("--algo", default="onpolicy", help="onpolicy | sacl | ddpgl | cvpo; --wide --ks takes a list, e.g. onpolicy,sacl: one run per "
+                                                      "algo in one --out file")
     ap.add_argument("--update-per-step", type=float, default=0.1, help="replay legs: updates per collected env step in the loop figure")
     ap.add_argument("--batch-size", type=int, default=256, help="replay legs: rows per update in the loop figure")
     ap.add_argument("--rounds", type=int, default=3)
@@ -369,6 +424,11 @@ def main():
                                                         "to 64 envs, the looping device collect; the host replay's share of the wall time; "
                                                         "with --layered: on layered shapes, on-policy and SAC-Lag, in one file")
     a = ap.parse_args()
+    if a.wide and a.ks:
+        if a.layered and "x" not in a.hidden:
+            a.hidden = "256x256x256"
+        return main_wide_groups(a)
+    assert a.algo in ("onpolicy", "sacl", "ddpgl", "cvpo"), "--algo: one of onpolicy, sacl, ddpgl, cvpo (a list with --wide --ks only)"
     if a.wide and a.layered:
         return main_wide_layered(a)
     if a.wide:
