@@ -125,6 +125,29 @@ struct DcwState {
     int32_t index[DCW_MAX_ENVS];                // write index of every env's sub-buffer, by env id (its own thread's alone)
 };
 
+// ---- wide evaluations (fsrl_evaluate_device_wide, kernels_deveval_wide.hpp): the EPISODE is the unit that leaves the GPU.  An env's
+// running return, cost and length are held by env id (its own thread's alone); an ending episode is parked at its POSITION on the
+// side of the next launch, and the next launch's settle -- which has every finished position's rank anyway -- moves it to row
+// episodes_before + rank of the episode log: step-major, position order inside a step, the order devcollect_replay meets the ending
+// rows in.  The row of old position p is written by the workgroup that ran p's tile in the step before, tile p / 16 of the fixed grid
+// (it exists in every launch of the collect, whatever the live count has shrunk to); the one-workgroup settle launch writes all.
+// tests/host/deveval_wide_sim.cpp holds the rule to a sequential walk of dc_episode_end.
+struct DcEpisodeRow {       // 24 bytes: a parked record and a row of the episode log
+    double rew, cost;
+    int32_t len;
+    uint32_t flags;         // of the episode's last step: bit 0 terminated, bit 1 truncated
+};
+DC_HD int32_t dc_wide_episode_row(bool done, int32_t episodes_before, int32_t rank, int32_t n_episode) {     // -1: no row
+    const int32_t r = episodes_before + rank;
+    return done && r < n_episode ? r : -1;
+}
+DC_HD bool dc_wide_row_owner(int32_t p, int32_t tile, bool all_rows) { return all_rows || (p >> 4) == tile; }
+struct DcwEval {
+    double rew[DCW_MAX_ENVS], cost[DCW_MAX_ENVS];       // the running episode of every env, by env id
+    int32_t len[DCW_MAX_ENVS];
+    DcEpisodeRow park[2][DCW_MAX_ENVS];                 // by the parity of the launch that settles them, by position
+};
+
 // slot of env e's next row and the index behind it (tianshou ReplayBuffer.add: ptr = index, index = (index + 1) % maxsize)
 DC_HD int64_t dc_slot(int32_t e, int64_t sub_size, int32_t index) { return (int64_t)e * sub_size + index; }
 DC_HD int32_t dc_next_index(int32_t index, int64_t sub_size) { return (int64_t)index + 1 >= sub_size ? 0 : index + 1; }     // index < sub_size: (index + 1) % sub_size without the division

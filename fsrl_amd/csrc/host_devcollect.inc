@@ -19,6 +19,7 @@
 #include "kernels_devcollect_layered.hpp"
 #include "kernels_devcollect_wide.hpp"
 #include "kernels_devcollect_wide_layered.hpp"
+#include "kernels_deveval_wide.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered);      // defined with the SAC / CVPO code
 static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax);    // ... and behind the layered code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -60,6 +61,11 @@ struct fsrl_devenv {
     // gathers the members' settled scalars in, device / pinned, made by the first such collect
     WideGroupTable* d_wgtab = nullptr; WideGroupTable* h_wgtab = nullptr;
     DcwScalars* d_wgs = nullptr; DcwScalars* h_wgs = nullptr;
+    // a wide env's evaluations (fsrl_evaluate_device_wide, host_deveval_wide.inc), made by the first one: the running episodes and the
+    // park, the kernels' arguments (device / pinned) and the episode log of eplog_rows rows (device / pinned)
+    DcwEval* d_weval = nullptr;
+    WideEvalArgs* d_weargs = nullptr; WideEvalArgs* h_weargs = nullptr;
+    DcEpisodeRow* d_eplog = nullptr; DcEpisodeRow* h_eplog = nullptr; int32_t eplog_rows = 0;
 };
 static dim3 devenv_grid(int n) { return dim3((unsigned)((n + DC_MAX_ENVS - 1) / DC_MAX_ENVS)); }
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }
@@ -294,14 +300,16 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
     CHECK_ARG(c && v, "null context / env");
     CHECK_ARG(v->c == c, "the device env was created on another context");
     if (!wide) CHECK_ARG(!v->wide, "a wide device env (fsrl_devenv_create_wide): its collects go through fsrl_collect_device_wide (layered contexts: "
-                         "fsrl_collect_device_wide_layered; k members' in one launch per step: fsrl_collect_device_wide_group); evaluations over wide "
-                         "envs are not supported yet");
-    else CHECK_ARG(v->wide, "fsrl_collect_device_wide%s takes a wide device env (fsrl_devenv_create_wide); this one collects through fsrl_collect_device%s",
-                   layered ? "_layered" : "", layered ? "_layered" : "");
-    if (!layered && wide) CHECK_ARG(!c->lay, "a layered context: its wide device collects go through fsrl_collect_device_wide_layered");
+                         "fsrl_collect_device_wide_layered; k members' in one launch per step: fsrl_collect_device_wide_group), its "
+                         "evaluations through fsrl_evaluate_device_wide (layered contexts: fsrl_evaluate_device_wide_layered)");
+    else CHECK_ARG(v->wide, "%s_wide%s takes a wide device env (fsrl_devenv_create_wide); this one %s through %s%s",
+                   store ? "fsrl_collect_device" : "fsrl_evaluate_device", layered ? "_layered" : "", store ? "collects" : "evaluates",
+                   store ? "fsrl_collect_device" : "fsrl_evaluate_device", layered ? "_layered" : "");
+    if (!layered && wide) CHECK_ARG(!c->lay, "a layered context: its wide device %s go through %s_wide_layered", what,
+                                    store ? "fsrl_collect_device" : "fsrl_evaluate_device");
     else if (!layered) CHECK_ARG(!c->lay, "device %s are not supported on layered contexts yet", what);
     else CHECK_ARG(c->lay, "a fused context (two hidden layers of at most 256 units): its device %s go through %s", what,
-                   wide ? "fsrl_collect_device_wide" : store ? "fsrl_collect_device" : "fsrl_evaluate_device");
+                   wide ? (store ? "fsrl_collect_device_wide" : "fsrl_evaluate_device_wide") : store ? "fsrl_collect_device" : "fsrl_evaluate_device");
     if (!named && store && (!layered || wide))
         CHECK_ARG(!c->group && !c->cgroup && !c->sac_group && !c->cvpo_group, "device collects are not supported on grouped contexts yet");
     if (ctx_is_replay(c)) {
@@ -311,7 +319,7 @@ static int devcollect_check(const fsrl_ctx* c, const fsrl_devenv* v, int32_t n_e
         CHECK_ARG(sac_raw_cols(c) <= FSRL_MAX_ACT, "the actor's %d head outputs do not fit a head row of %d", sac_raw_cols(c), FSRL_MAX_ACT);
     }
     if (store) CHECK_ARG(!c->tap, "device collects are not supported on a context with a trajectory tap attached yet");
-    if (wide) CHECK_ARG(!c->per, "wide device collects are not supported on a context with prioritised replay on yet");
+    if (wide && store) CHECK_ARG(!c->per, "wide device collects are not supported on a context with prioritised replay on yet");
     if (c->in_update)
         return fail(FSRL_ESTATE, "%s%s inside an update", store ? "fsrl_collect_device" : "fsrl_evaluate_device",
                     wide ? (layered ? "_wide_layered" : "_wide") : layered ? "_layered" : named ? "_group" : "");
@@ -342,7 +350,7 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
     HIPCHK(hipStreamSynchronize(v->es));            // the env's own launches are complete (they are, every call waits; cheap)
     int rc = store ? join_store(c) : 0;             // rows in the staging window land first; the side stream is in front of the kernel
     if (rc) return rc;
-    if (v->log_steps < max_steps) {
+    if ((store || !wide) && v->log_steps < max_steps) {         // a wide evaluation has no log of rows
         const size_t rows = (size_t)max_steps * n;
         HIPCHK(v->mem.regrow(v->log_steps, max_steps, max_steps, {Mem::D(&v->d_log, rows * sizeof(DcLogRow)),
                              Mem::D(&v->d_slot, rows * sizeof(int32_t)), Mem::H(&v->h_log, rows * sizeof(DcLogRow))}));
@@ -352,7 +360,7 @@ static int devcollect_begin(fsrl_ctx* c, fsrl_devenv* v, int32_t n_episode, int3
         DcwState& ws = *v->h_wstate;
         memset(&ws, 0, sizeof(ws));
         ws.s[v->wide_t & 1].n_live = dc_first_live(n, n_episode); ws.n_episode = n_episode;
-        for (int e = 0; e < n; ++e) { ws.live[0][e] = e; ws.index[e] = (int32_t)c->env[(size_t)e].index; }
+        for (int e = 0; e < n; ++e) { ws.live[0][e] = e; ws.index[e] = store ? (int32_t)c->env[(size_t)e].index : 0; }
         HIPCHK(hipMemcpyAsync(v->d_wstate, &ws, sizeof(DcwState), hipMemcpyHostToDevice, s));
     } else {
         DcState& hs = *v->h_state;

@@ -13,7 +13,8 @@
 // function.  A tile's activations are dynamic LDS sized to the shape, or (a layer beyond DCWL_LDS_WIDTH) the env's workspace.
 // k members' wide collects in one launch per step are fsrl_collect_device_wide_group (host_devcollect_wide_group.inc, behind this file):
 // the same batch loop, devcollect_wide_run, with the grouped kernels in the launch.
-// Not here: evaluations over wide envs, prioritised contexts -- refused by name.
+// Evaluations over wide envs have kernels and a batch loop of their own (host_deveval_wide.inc: no log, no replay).
+// Not here: prioritised contexts -- refused by name.
 #include <chrono>
 static int devcollect_wide_launch(fsrl_ctx* c, fsrl_devenv* v, const DcActor& actor, int grid, bool first, bool settle) {
     hipStream_t s = c->compute;

@@ -93,54 +93,22 @@ __device__ __forceinline__ const float* wl_wrow(const float* P, const LayLayer& 
     return P + ll.W + (size_t)min(16 * ct + li, ll.out - 1) * ll.in;
 }
 
-// Compiled without the packed-fp32 instructions (v_pk_add / mul / fma_f32): the arithmetic outside the MFMAs is a few dozen
-// operations a step, the one-lane forms round identically, and the kernel does not depend on how the two-lane forms behave.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define WL_NO_PK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define WL_NO_PK            // the host pass does not know the feature
-#endif
-// One workgroup's launch: a tile of ONE collect (wide_collect_step_body's arguments, the actor's row in the place of (md, P)); both
-// pointers are uniform and point into constant memory (read through dc_uniform_ptr<4> here).  wide_layered_step_kernel and wide_layered_group_step_kernel call it.
-template <class Env, int HEAD, bool DEVWS>
-__device__ __forceinline__ void wide_layered_step_body(const WideCollectArgs* __restrict__ wap, const WideLayActor* __restrict__ lap, const int t, const int first,
-                                                       const int settle, const int tile, DcwScalars* settled, float* wl_lds, DevCollectSmem& sh,
-                                                       float* raw, int32_t* wtot) {
-    const WideCollectArgs* wp = dc_uniform_ptr<4>(wap);
-    const WideLayActor& la = *dc_uniform_ptr<4>(lap);
-    const DevCollectArgs& a = wp->a;
-    DcwState* ws = wp->ws;
-    const float* P = dc_uniform_ptr<1>(la.P);
-    const int side = t & 1, nside = side ^ 1;
-    const int tile0 = 16 * tile;
-    const bool writer = tile0 == 0;
-    const int Do = a.ep.Do, Da = a.ep.Da, ldp = la.ldp, nl = la.net.nl;
-    f32x4 b0[4], b1[4];         // the weights of this unit and of the one behind it: b0 holds the current unit's while par == 0
+// Every wave's first 64 k of its first weight row of layer 0, issued before the settle (not in a settle launch: it runs no actor)
+__device__ __forceinline__ void wl_prefetch(f32x4 (&b0)[4], const WideLayActor& la, const float* P, const int settle) {
+    int t0 = threadIdx.x;
+    asm volatile("" : "+v"(t0));
+    const int wave = __builtin_amdgcn_readfirstlane(t0 >> 6), li = t0 & 15, q = (t0 & 63) >> 4;
+    const LayLayer l0 = la.net.l[0];
+    if (!settle && wave < ((l0.out + 15) >> 4)) wl_load_w(b0, wl_wrow(P, l0, wave, li), l0.in, 0, q);
+}
+// Phases 0 and 1 of a tile's step, the layered tile actor: the live rows' observations, then the layers; the head's raw rows are left in
+// `raw` behind the last layer's barrier.  b0: what wl_prefetch issued.  Every thread of the workgroup calls it (barriers).
+// wide_layered_step_body and the evaluation's body (kernels_deveval_wide.hpp) are this function between their own settle and phase 2.
+template <bool DEVWS>
+__device__ __forceinline__ void wl_tile_actor(const DevCollectArgs& a, const WideLayActor& la, const float* P, DevCollectSmem& sh, float* wl_lds, float* raw,
+                                              f32x4 (&b0)[4], f32x4 (&b1)[4], const int lt, const int tile, const int n_valid) {
+    const int Do = a.ep.Do, ldp = la.ldp, nl = la.net.nl;
     int par = 0;
-    {
-        int t0 = threadIdx.x;
-        asm volatile("" : "+v"(t0));
-        const int wave = __builtin_amdgcn_readfirstlane(t0 >> 6), li = t0 & 15, q = (t0 & 63) >> 4;
-        const LayLayer l0 = la.net.l[0];
-        if (!settle && wave < ((l0.out + 15) >> 4)) wl_load_w(b0, wl_wrow(P, l0, wave, li), l0.in, 0, q);
-    }
-    // ---- 5'. the state of this side, uniform; the step before is settled
-    DcwScalars s = *dc_uniform_ptr<4>(&ws->s[side]);
-    const int n_episode = *dc_uniform_ptr<4>(&ws->n_episode);
-    if (first) { s.log_rows = 0; s.steps = 0; }
-    s = dcw_settle<WL_NT>(ws, s, side, n_episode, tile0, sh.live, wtot, writer);
-    const bool go = !settle && !s.finished && s.log_rows + s.n_live <= wp->log_cap;
-    if (writer && threadIdx.x == 0) {
-        DcwScalars nx = s;
-        if (go) { nx.log_rows = s.log_rows + s.n_live; nx.steps = s.steps + 1; nx.pending = 1; }
-        ws->s[nside] = nx;
-        if (settled) *settled = nx;
-    }
-    if (!go || tile0 >= s.n_live) return;
-    const int n_valid = min(16, s.n_live - tile0);
-    __syncthreads();
-    int lt = threadIdx.x;
-    asm volatile("" : "+v"(lt));
     float* act;
     if constexpr (DEVWS) act = const_cast<float*>(dc_uniform_ptr<1>((const float*)la.ws)) + (size_t)tile * 32 * ldp;
     else act = wl_lds;
@@ -205,6 +173,50 @@ __device__ __forceinline__ void wide_layered_step_body(const WideCollectArgs* __
             __syncthreads();
         }
     }
+}
+
+// Compiled without the packed-fp32 instructions (v_pk_add / mul / fma_f32): the arithmetic outside the MFMAs is a few dozen
+// operations a step, the one-lane forms round identically, and the kernel does not depend on how the two-lane forms behave.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define WL_NO_PK __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WL_NO_PK            // the host pass does not know the feature
+#endif
+// One workgroup's launch: a tile of ONE collect (wide_collect_step_body's arguments, the actor's row in the place of (md, P)); both
+// pointers are uniform and point into constant memory (read through dc_uniform_ptr<4> here).  wide_layered_step_kernel and wide_layered_group_step_kernel call it.
+template <class Env, int HEAD, bool DEVWS>
+__device__ __forceinline__ void wide_layered_step_body(const WideCollectArgs* __restrict__ wap, const WideLayActor* __restrict__ lap, const int t, const int first,
+                                                       const int settle, const int tile, DcwScalars* settled, float* wl_lds, DevCollectSmem& sh,
+                                                       float* raw, int32_t* wtot) {
+    const WideCollectArgs* wp = dc_uniform_ptr<4>(wap);
+    const WideLayActor& la = *dc_uniform_ptr<4>(lap);
+    const DevCollectArgs& a = wp->a;
+    DcwState* ws = wp->ws;
+    const float* P = dc_uniform_ptr<1>(la.P);
+    const int side = t & 1, nside = side ^ 1;
+    const int tile0 = 16 * tile;
+    const bool writer = tile0 == 0;
+    const int Do = a.ep.Do, Da = a.ep.Da;
+    f32x4 b0[4], b1[4];         // the weights of this unit and of the one behind it: b0 holds the current unit's while par == 0
+    wl_prefetch(b0, la, P, settle);
+    // ---- 5'. the state of this side, uniform; the step before is settled
+    DcwScalars s = *dc_uniform_ptr<4>(&ws->s[side]);
+    const int n_episode = *dc_uniform_ptr<4>(&ws->n_episode);
+    if (first) { s.log_rows = 0; s.steps = 0; }
+    s = dcw_settle<WL_NT>(ws, s, side, n_episode, tile0, sh.live, wtot, writer);
+    const bool go = !settle && !s.finished && s.log_rows + s.n_live <= wp->log_cap;
+    if (writer && threadIdx.x == 0) {
+        DcwScalars nx = s;
+        if (go) { nx.log_rows = s.log_rows + s.n_live; nx.steps = s.steps + 1; nx.pending = 1; }
+        ws->s[nside] = nx;
+        if (settled) *settled = nx;
+    }
+    if (!go || tile0 >= s.n_live) return;
+    const int n_valid = min(16, s.n_live - tile0);
+    __syncthreads();
+    int lt = threadIdx.x;
+    asm volatile("" : "+v"(lt));
+    wl_tile_actor<DEVWS>(a, la, P, sh, wl_lds, raw, b0, b1, lt, tile, n_valid);
     if (lt < n_valid * Da) {
         const int i = div_by_magic((unsigned)lt, a.magic_da), d = lt - i * Da;
         dc_head<HEAD>(a, sh, &raw[i * FSRL_MAX_ACT], P + la.net.sigma, la.unbounded, Da, i, d);

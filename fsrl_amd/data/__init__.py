@@ -8,6 +8,7 @@ install(__name__, globals(), {
     "FastCollector": "fast_collector",
     "DeviceCollector": "device_collector",
     "DeviceEvalCollector": "device_collector",
+    "WideDeviceEvalCollector": "device_collector",
     "GroupDeviceCollector": "device_collector",
     "evaluation_collector": "device_collector",
     "GroupCollector": "group_collector",

@@ -10,7 +10,9 @@ route on `_layered(engine)`.  A `DeviceCollector` of its own on a grouped fused 
 A WIDE env (more than 64 envs, up to 4096, or `wide=True`) collects through fsrl_collect_device_wide: one launch per vector step, a
 workgroup per 16-row tile, `max_steps_per_launch` step launches per batch; on a layered engine through
 fsrl_collect_device_wide_layered, the same scheme with the layer-by-layer tile actor.  Without a buffer (an evaluation) a wide env
-is refused by name.
+goes through `WideDeviceEvalCollector` (fsrl_evaluate_device_wide / _wide_layered): the same launches with the episodes accumulated
+and ordered on the GPU, so the host reads 32 bytes per batch and n_episode episode rows at the end; `DeviceCollector(policy,
+wide_env)` itself refuses and names both.
 
 Grouped seeds (k seeds on one GPU, in an EngineGroup / EngineSacGroup / EngineCvpoGroup / EngineCollectGroup or in none) collect
 through `GroupDeviceCollector(collectors)`: ONE launch per `max_steps_per_launch` vector steps carries every member's collect, a
@@ -25,7 +27,8 @@ Evaluation: `DeviceCollector(policy, test_envs)` with no buffer is the reference
 same launches in their store-less form (fsrl_evaluate_device): the same statistics, and nothing of the engine's store, books, sampler or
 random streams moves, so a run with test envs trains to the bits of the run without.  It also works where a storing collector is
 refused: on a member of a group, with a trajectory archive attached, with more test envs than the store has sub-buffers.
-`evaluation_collector(policy, test_envs)` is what the agents' `learn()` and `evaluate()` build; a `GroupDeviceCollector` of store-less
+`evaluation_collector(policy, test_envs)` is what the agents' `learn()` and `evaluate()` build (over wide test envs of a fused engine
+a `WideDeviceEvalCollector`); a `GroupDeviceCollector` of store-less
 collectors evaluates every seed in one launch (fsrl_evaluate_device_group)."""
 import time
 from typing import Any, Dict, List, Sequence, Union
@@ -62,15 +65,15 @@ def _layered(eng) -> bool:
 
 def evaluation_collector(policy, test_envs, render: bool = False):
     """The collector an agent evaluates with (None without test envs): the store-less DeviceCollector when the envs live on the
-    GPU of this policy's engine -- a whole evaluation in a handful of launches -- and FastCollector(policy, test_envs), which steps
-    any vector env (a device env too: layered engines, rendering), otherwise."""
+    GPU of this policy's engine -- a whole evaluation in a handful of launches, over a wide env the WideDeviceEvalCollector's launch
+    per vector step -- and FastCollector(policy, test_envs), which steps any vector env (a device env too: layered engines,
+    rendering), otherwise."""
     if test_envs is None:
         return None
     from fsrl_amd.env.device import DeviceVectorEnv
     eng = getattr(policy, "engine", None)
-    if (isinstance(test_envs, DeviceVectorEnv) and eng is not None and test_envs.engine is eng and not _layered(eng) and not render
-            and not test_envs.wide):
-        return DeviceCollector(policy, test_envs)
+    if isinstance(test_envs, DeviceVectorEnv) and eng is not None and test_envs.engine is eng and not _layered(eng) and not render:
+        return WideDeviceEvalCollector(policy, test_envs) if test_envs.wide else DeviceCollector(policy, test_envs)
     from fsrl_amd.data.fast_collector import FastCollector
     return FastCollector(policy, test_envs)
 
@@ -148,15 +151,28 @@ class DeviceEvalCollector(DeviceCollector):
 
     def __init__(self, policy, env, buffer=None, max_steps_per_launch: int = 0, exploration_noise: bool = False):
         assert buffer is None, "a DeviceEvalCollector stores nothing: DeviceCollector(policy, env, buffer) collects into a buffer"
-        if getattr(env, "wide", False):
-            raise ValueError("evaluations over wide device envs are not supported yet: a wide env (more than 64 envs, or wide=True) "
-                             "collects into a buffer through Engine.collect_device_wide (fsrl_collect_device_wide); evaluate it with "
-                             "FastCollector(policy, env)")
+        if bool(getattr(env, "wide", False)) != isinstance(self, WideDeviceEvalCollector):
+            raise ValueError("a wide env (more than 64 envs, or wide=True) collects into a buffer through Engine.collect_device_wide "
+                             "(fsrl_collect_device_wide) and is evaluated by WideDeviceEvalCollector(policy, env) "
+                             "(Engine.evaluate_device_wide); a narrow one by DeviceCollector(policy, env)")
         super().__init__(policy, env, None, max_steps_per_launch, exploration_noise)
 
     def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
         eng = self.policy.engine
         return self._collect(n_episode, eng.evaluate_device_layered if _layered(eng) else eng.evaluate_device)
+
+
+class WideDeviceEvalCollector(DeviceEvalCollector):
+    """DeviceEvalCollector for a WIDE env (up to 4096 envs): collect() is fsrl_evaluate_device_wide, on a layered engine
+    fsrl_evaluate_device_wide_layered -- one launch per vector step, the episodes accumulated and ordered on the GPU.  The same
+    result dict, counters and resets; max_steps_per_launch is the number of step launches of a batch (0: 64)."""
+
+    def __init__(self, policy, env, max_steps_per_launch: int = 0):
+        super().__init__(policy, env, None, max_steps_per_launch)
+
+    def collect(self, n_episode: int = 1, **_ignored) -> Dict[str, Any]:
+        eng = self.policy.engine
+        return self._collect(n_episode, eng.evaluate_device_wide_layered if _layered(eng) else eng.evaluate_device_wide)
 
 
 class GroupDeviceCollector:

@@ -480,6 +480,21 @@ class Engine:
         hi = np.ascontiguousarray(high, np.float32) if low is not None else None
         return self._collect_device(self.lib.fsrl_evaluate_device, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
 
+    def evaluate_device_wide(self, h, n_episode, deterministic=True, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.evaluate_device over a WIDE env (fsrl_evaluate_device_wide): the launch scheme of collect_device_wide, the episodes
+        accumulated and ordered on the GPU -- the host reads 32 bytes per batch and n_episode episode rows at the end.  Nothing is
+        stored or moved; valid wherever evaluate_device is.  max_steps_per_launch: step launches per batch (0: 64).  The same dict."""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_evaluate_device_wide, h, n_episode, deterministic, bound_method, lo, hi, max_steps_per_launch)
+
+    def evaluate_device_wide_layered(self, h, n_episode, deterministic=True, bound_method=1, low=None, high=None, max_steps_per_launch=0):
+        """Engine.evaluate_device_wide for a LAYERED engine (fsrl_evaluate_device_wide_layered): the same arguments and result dict."""
+        lo = np.ascontiguousarray(low, np.float32) if low is not None else None
+        hi = np.ascontiguousarray(high, np.float32) if low is not None else None
+        return self._collect_device(self.lib.fsrl_evaluate_device_wide_layered, h, n_episode, deterministic, bound_method, lo, hi,
+                                    max_steps_per_launch)
+
     def collect_device_layered(self, h, n_episode, deterministic=False, bound_method=1, low=None, high=None, max_steps_per_launch=0):
         """Engine.collect_device for a LAYERED engine (hidden_sizes of any depth and width): fsrl_collect_device_layered with this one
         member.  The same arguments and result dict; the engine may be a member of any kind of group."""

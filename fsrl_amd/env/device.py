@@ -8,7 +8,8 @@ agents' `learn(train_envs, test_envs)` and `evaluate(test_envs)` run over device
 and `render=True` evaluate through `FastCollector` over `step`, call by call.  More than 64 envs (up to 4096), or `wide=True`, make
 a WIDE env (fsrl_devenv_create_wide): the same calling convention, and `DeviceCollector` collects it with one launch per vector step
 (fsrl_collect_device_wide; on a layered engine fsrl_collect_device_wide_layered); evaluations over wide envs go through
-`FastCollector`."""
+`WideDeviceEvalCollector` (fsrl_evaluate_device_wide / _wide_layered: the episodes are accumulated and ordered on the GPU), which is
+what `evaluation_collector` builds for wide test envs of a fused engine."""
 from types import SimpleNamespace
 
 import numpy as np

@@ -1145,8 +1145,8 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
  *                            Refused before anything changes, by name: an env of fsrl_devenv_create; layered contexts; contexts in
  *                            any kind of group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device refuses.
  *                            fsrl_collect_device, fsrl_evaluate_device and their _group / _layered forms refuse a wide env and name
- *                            this call: evaluations over wide envs are not supported yet; grouped collects over wide envs go
- *                            through fsrl_collect_device_wide_group.
+ *                            this call: evaluations over wide envs go through fsrl_evaluate_device_wide, grouped collects over wide
+ *                            envs through fsrl_collect_device_wide_group.
  *      fsrl_collect_device_wide_layered   fsrl_collect_device_wide for LAYERED contexts (hidden_sizes of any depth and width, or
  *                            force_layered; kernels_devcollect_wide_layered.hpp): the same arguments, outputs, batches, settle launches,
  *                            log replay and timing, with one kernel for every shape in the launch -- a workgroup of 512 threads runs
@@ -1192,6 +1192,28 @@ int fsrl_collect_device_wide_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t 
 /*      fsrl_collect_device_wide_timing  the env's last wide collect on the host's clock: out[0] seconds from the first launch to the
  *                            end of the call, out[1] of them in the replay of the log (tools/bench_device_collect.py --wide).  */
 int fsrl_collect_device_wide_timing(fsrl_devenv* env, double* out);
+/*      fsrl_evaluate_device_wide / fsrl_evaluate_device_wide_layered   fsrl_evaluate_device over a wide env (kernels_deveval_wide.hpp,
+ *                            host_deveval_wide.inc): the arguments and outputs of fsrl_collect_device_wide, nothing stored.  The launch
+ *                            scheme is the wide collect's -- one launch per vector step, a workgroup per 16-row tile, batches of
+ *                            max_steps_per_launch step launches (<= 0: 64; no log caps it) and a settle launch -- but the EPISODE is
+ *                            what leaves the GPU: every env's running return, cost and length are accumulated on the device, an
+ *                            ended episode is parked at its position and moved by the next launch's settle to row
+ *                            episodes_before + rank of an episode log, in the collector's order (step-major, position order inside a
+ *                            step).  The host reads 32 bytes of settled scalars per batch and n_episode rows of 24 bytes once at the
+ *                            end.  The statistics, episodes and env states are those fsrl_collect_device_wide leaves on a twin
+ *                            context (and, up to 64 envs, those of fsrl_evaluate_device), bit for bit; *total_cost_out is the sum
+ *                            of the episodes' costs, *steps_out the kernels' step count, checked against the episodes' lengths.
+ *                            As fsrl_evaluate_device, the call touches nothing of the context but its resident actor and is valid
+ *                            on a member of any group, with a trajectory tap, with more envs than sub-buffers and with prioritised
+ *                            replay on.  _layered: the same for layered contexts; each refuses the other's contexts by name.  */
+int fsrl_evaluate_device_wide(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                              const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                              double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                              int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+int fsrl_evaluate_device_wide_layered(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n_episode, int32_t deterministic, int32_t bound_method,
+                                      const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
+                                      double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
+                                      int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 
 #ifdef __cplusplus
 }

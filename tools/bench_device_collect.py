@@ -59,7 +59,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fsrl_amd import _lib  # noqa: E402
-from fsrl_amd.data import DeviceCollector, FastCollector, HipVectorReplayBuffer  # noqa: E402
+from fsrl_amd.data import DeviceCollector, FastCollector, HipVectorReplayBuffer, WideDeviceEvalCollector  # noqa: E402
 from fsrl_amd.engine import Engine, EngineConfig, EngineGroup  # noqa: E402
 from fsrl_amd.env import Box, DeviceLinear, SyntheticSafetyVectorEnv  # noqa: E402
 
@@ -310,8 +310,9 @@ class EvalPol(Pol):
     training = False
 
 
-def setup_eval(hidden, n, algo):
-    """a real agent (the host path needs its torch actor) and the three collectors of an evaluation, each over a device env of its own"""
+def setup_eval(hidden, n, algo, wide=False):
+    """a real agent (the host path needs its torch actor) and the three collectors of an evaluation, each over a device env of its own
+    wide: over wide envs -- the wide evaluation, FastCollector over the same kind of env, the storing wide collect"""
     import tempfile as tf
     from fsrl_amd.agent import PPOLagAgent, SACLagAgent
     from fsrl_amd.utils import BaseLogger
@@ -321,10 +322,57 @@ def setup_eval(hidden, n, algo):
                   hidden_sizes=tuple(hidden_list(hidden)), training_num=n, buffer_size=n * 2 * EPISODE_LEN)
     pol = agent.policy
     pol.eval()
-    envs = [DeviceLinear(pol, like=host, seed=1) for _ in range(3)]
+    envs = [DeviceLinear(pol, like=host, seed=1, wide=True if wide else None) for _ in range(3)]
     buf = HipVectorReplayBuffer(pol.engine, n * 2 * EPISODE_LEN, n)
-    cols = dict(evaluate=DeviceCollector(pol, envs[0]), stepped=FastCollector(pol, envs[1]), collect=DeviceCollector(pol, envs[2], buf))
+    cols = dict(evaluate=WideDeviceEvalCollector(pol, envs[0]) if wide else DeviceCollector(pol, envs[0]), stepped=FastCollector(pol, envs[1]),
+                collect=DeviceCollector(pol, envs[2], buf))
     return agent, envs, cols
+
+
+def main_wide_eval(a):
+    """--wide --eval: per (agent, shape, env_num) three legs alternated inside every round -- (a) `evaluate` the wide device evaluation
+    (fsrl_evaluate_device_wide / _wide_layered), (b) `stepped` FastCollector with the host actor over the same wide env, what (a)
+    replaces, (c) `collect` a storing wide collect -- and at 64 envs (a) beside `narrow`, the looping fsrl_evaluate_device.
+    --ab-tree: the storing wide collect of this tree against that built checkout, at 256 and 4096 envs, 256 x 256."""
+    if a.ab_tree:
+        a.envs, a.hidden, a.algo = "256,4096", "256", "onpolicy"
+        result = dict(metric="env-steps/s of the storing wide collect, this tree against --ab-tree, one process per round, alternating",
+                      rounds=a.rounds, calls=a.calls, configs=solo_ab(a))
+    else:
+        if a.envs == "20,64":
+            a.envs = "256,1024,4096"
+        if a.hidden == "256,64":
+            a.hidden = "256,64,256x256x256"
+        result = dict(metric="an evaluation of env_num episodes over a wide linear env obs 8 / act 2, episode length 300, real agents in eval "
+                             "mode: env-steps/s and episodes/s", rounds=a.rounds, calls=a.calls, configs=[], narrow=[])
+        for algo, hidden, n in ((al, h, int(e)) for al in ("onpolicy", "sacl") for h in parse_hidden(a.hidden) for e in ["64"] + a.envs.split(",")):
+            if isinstance(hidden, tuple) and algo != "onpolicy":
+                continue            # the layered shape: PPO-Lag
+            if n == 64 and hidden != 256:
+                continue            # the narrow row: 256 x 256
+            agent, envs, cols = setup_eval(hidden, n, algo, wide=True)
+            paths = ("evaluate", "stepped", "collect")
+            if n == 64:
+                envs.append(DeviceLinear(agent.policy, like=SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1), seed=1))
+                cols, paths = dict(evaluate=cols["evaluate"], narrow=DeviceCollector(agent.policy, envs[-1])), ("evaluate", "narrow")
+            steps, eps = {p: [] for p in paths}, {p: [] for p in paths}
+            for _ in range(a.rounds):
+                for p in paths:
+                    rows, ne, dt = timed_eval(cols[p], n, a.calls)
+                    steps[p].append(rows / dt); eps[p].append(ne / dt)
+            cfg = dict(algo=algo, hidden=hidden_list(hidden), env_num=n, launches_per_evaluation=cols["evaluate"].last_launches)
+            for p in paths:
+                cfg[p] = dict(env_steps_per_s=summary(steps[p]), episodes_per_s=summary(eps[p]))
+            result["narrow" if n == 64 else "configs"].append(cfg)
+            print(json.dumps(cfg), flush=True)
+            for env in envs:
+                env.close()
+            agent.policy.engine.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
 
 
 def timed_eval(col, n, calls):
@@ -429,6 +477,8 @@ def main():
             a.hidden = "256x256x256"
         return main_wide_groups(a)
     assert a.algo in ("onpolicy", "sacl", "ddpgl", "cvpo"), "--algo: one of onpolicy, sacl, ddpgl, cvpo (a list with --wide --ks only)"
+    if a.wide and a.eval:
+        return main_wide_eval(a)
     if a.wide and a.layered:
         return main_wide_layered(a)
     if a.wide:
