@@ -1578,6 +1578,7 @@ extern "C" int fsrl_launch_floors(fsrl_ctx* c, int32_t mb_rows, int32_t iters, d
 #include "host_devcollect_wide.inc"
 #include "host_devcollect_wide_group.inc"
 #include "host_deveval_wide.inc"
+#include "host_deveval_wide_group.inc"
 
 #include "host_comm.inc"
 

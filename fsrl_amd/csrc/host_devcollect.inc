@@ -20,6 +20,7 @@
 #include "kernels_devcollect_wide.hpp"
 #include "kernels_devcollect_wide_layered.hpp"
 #include "kernels_deveval_wide.hpp"
+#include "kernels_deveval_wide_group.hpp"
 static bool sac_devcollect_head(fsrl_ctx* c, DevCollectArgs* a, int* head, bool layered);      // defined with the SAC / CVPO code
 static bool devcollect_lay_actor(fsrl_ctx* c, const float** P, const LayNet** net, int* hmax);    // ... and behind the layered code
 static int sac_devcollect_enter(fsrl_ctx* c);
@@ -66,6 +67,9 @@ struct fsrl_devenv {
     DcwEval* d_weval = nullptr;
     WideEvalArgs* d_weargs = nullptr; WideEvalArgs* h_weargs = nullptr;
     DcEpisodeRow* d_eplog = nullptr; DcEpisodeRow* h_eplog = nullptr; int32_t eplog_rows = 0;
+    // member 0's env of a grouped wide evaluation (fsrl_evaluate_device_wide_group): the evaluations' member table, device / pinned,
+    // made by the first such call; the settle launch gathers the members' scalars in d_wgs / h_wgs as a grouped wide collect's does
+    WideEvalGroupTable* d_wegtab = nullptr; WideEvalGroupTable* h_wegtab = nullptr;
 };
 static dim3 devenv_grid(int n) { return dim3((unsigned)((n + DC_MAX_ENVS - 1) / DC_MAX_ENVS)); }
 static uint64_t devenv_key(uint64_t seed) { return seed * 0x9E3779B97F4A7C15ull + 0x243F6A8885A308D3ull; }

@@ -22,7 +22,9 @@
 // fences or waits.  The host reads 32 bytes of settled scalars per batch and n_episode rows once at the end (host_deveval_wide.inc).
 //
 // wide_eval_step_kernel<H, Env, HEAD>: fused contexts, TileStage / tile_forward / dc_head / dc_next_obs as wide_collect_step_kernel
-// uses them; wide_eval_layered_step_kernel<Env, HEAD, DEVWS>: layered contexts, around wl_prefetch / wl_tile_actor.  The actions, the
+// uses them; wide_eval_layered_step_kernel<Env, HEAD, DEVWS>: layered contexts, around wl_prefetch / wl_tile_actor.  Both are their
+// body functions (wide_eval_step_body / wide_eval_layered_step_body) behind the kernel's own arguments and blockIdx; the grouped
+// kernels (kernels_deveval_wide_group.hpp) call the same bodies with a member's row.  The actions, the
 // env steps and the draws (keyed by env id, ordinal, t) are the collect's, so an evaluation leaves the env where a collect leaves it.
 // Registers: the rules of kernels_devcollect.hpp; the settle copies a record as three 8-byte words, one in flight at a time, and holds
 // nothing across the actor.  No instantiation spills or uses scratch, and none takes more LDS than its collect counterpart
@@ -153,20 +155,25 @@ __device__ __forceinline__ void dcw_eval_hand_on(DcwState* __restrict__ ws, cons
     ws->s[nside] = nx;
 }
 
+// One workgroup's launch: a tile of ONE evaluation, whoever launched it (wide_collect_step_body's contract).  wp: the evaluation's
+// arguments, a uniform pointer into constant memory; t: the env's own launch ordinal; tile: the tile's number in THAT evaluation's
+// fixed grid, uniform -- the row owner of old position p is tile p / 16 of the member, not of the launch.  `settled` (uniform, or
+// null; given by a settle launch alone): where the writer also leaves the settled scalars -- the grouped settle launch gathers the
+// members' there.  wide_eval_step_kernel and wide_eval_group_step_kernel (kernels_deveval_wide_group.hpp) are this function behind
+// two ways of finding (wp, P, t, tile).
 template <int H, class Env, int HEAD>
-__global__ __launch_bounds__(4 * H) DCW_NO_PK void wide_eval_step_kernel(const ModelDesc md, const float* __restrict__ P, const WideEvalArgs* __restrict__ wap,
-                                                                         const int t, const int first, const int settle) {
+__device__ __forceinline__ void wide_eval_step_body(const ModelDesc& md, const float* __restrict__ P, const WideEvalArgs* wp, const int t, const int first,
+                                                    const int settle, const int tile, DcwScalars* settled) {
     __shared__ TileSmem<H> sm;
     __shared__ DevCollectSmem sh;
     __shared__ int32_t wtot[16];
     constexpr int NT = TileGeom<H>::NT;
     constexpr int NX = TileStage<H>::NX;
-    const WideEvalArgs* wp = dc_uniform_ptr<4>(wap);
     const DevCollectArgs& a = wp->a;
     DcwState* ws = wp->ws;
     DcwEval* ev = wp->ev;
     const int side = t & 1, nside = side ^ 1;
-    const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x), tile0 = 16 * tile;
+    const int tile0 = 16 * tile;
     const bool writer = tile0 == 0;
     const int tid = threadIdx.x;
     const NetOff no = md.net[0];
@@ -183,7 +190,10 @@ __global__ __launch_bounds__(4 * H) DCW_NO_PK void wide_eval_step_kernel(const M
     if (first) { s.log_rows = 0; s.steps = 0; }
     s = dcw_eval_settle<NT>(ws, s, side, n_episode, tile, sh.live, wtot, writer, settle != 0, ev->park[side], wp->ep_log);
     const bool go = !settle && !s.finished;
-    if (writer && tid == 0) dcw_eval_hand_on(ws, s, go, nside);
+    if (writer && tid == 0) {
+        dcw_eval_hand_on(ws, s, go, nside);
+        if (settled) *settled = s;          // a settle launch makes no step: what it hands on is s
+    }
     if (!go || tile0 >= s.n_live) return;
     const int n_valid = min(16, s.n_live - tile0);
     stg.commit(sm, no, Do, tid);
@@ -212,13 +222,18 @@ __global__ __launch_bounds__(4 * H) DCW_NO_PK void wide_eval_step_kernel(const M
     dc_next_obs<Env>(a, sh, lt, n_valid, Do);
 }
 
+template <int H, class Env, int HEAD>
+__global__ __launch_bounds__(4 * H) DCW_NO_PK void wide_eval_step_kernel(const ModelDesc md, const float* __restrict__ P, const WideEvalArgs* __restrict__ wap,
+                                                                         const int t, const int first, const int settle) {
+    wide_eval_step_body<H, Env, HEAD>(md, P, dc_uniform_ptr<4>(wap), t, first, settle, __builtin_amdgcn_readfirstlane((int)blockIdx.x), nullptr);
+}
+
+// The layered form of wide_eval_step_body (wide_layered_step_body's arguments): both pointers are uniform and point into constant
+// memory.  wide_eval_layered_step_kernel and wide_eval_layered_group_step_kernel call it.
 template <class Env, int HEAD, bool DEVWS>
-__global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_eval_layered_step_kernel(const WideEvalArgs* __restrict__ wap, const WideLayActor* __restrict__ lap,
-                                                                                const int t, const int first, const int settle) {
-    extern __shared__ __align__(16) float wl_lds[];             // !DEVWS: [2][16][ldp]
-    __shared__ DevCollectSmem sh;                               // the tile uses its first 16 rows
-    __shared__ float raw[16 * FSRL_MAX_ACT];                    // the head's raw rows
-    __shared__ int32_t wtot[16];
+__device__ __forceinline__ void wide_eval_layered_step_body(const WideEvalArgs* __restrict__ wap, const WideLayActor* __restrict__ lap, const int t,
+                                                            const int first, const int settle, const int tile, DcwScalars* settled, float* wl_lds,
+                                                            DevCollectSmem& sh, float* raw, int32_t* wtot) {
     const WideEvalArgs* wp = dc_uniform_ptr<4>(wap);
     const WideLayActor& la = *dc_uniform_ptr<4>(lap);
     const DevCollectArgs& a = wp->a;
@@ -226,7 +241,7 @@ __global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_eval_layered_step_kernel(
     DcwEval* ev = wp->ev;
     const float* P = dc_uniform_ptr<1>(la.P);
     const int side = t & 1, nside = side ^ 1;
-    const int tile = __builtin_amdgcn_readfirstlane((int)blockIdx.x), tile0 = 16 * tile;
+    const int tile0 = 16 * tile;
     const bool writer = tile0 == 0;
     const int Do = a.ep.Do, Da = a.ep.Da;
     f32x4 b0[4], b1[4];
@@ -237,7 +252,10 @@ __global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_eval_layered_step_kernel(
     if (first) { s.log_rows = 0; s.steps = 0; }
     s = dcw_eval_settle<WL_NT>(ws, s, side, n_episode, tile, sh.live, wtot, writer, settle != 0, ev->park[side], wp->ep_log);
     const bool go = !settle && !s.finished;
-    if (writer && threadIdx.x == 0) dcw_eval_hand_on(ws, s, go, nside);
+    if (writer && threadIdx.x == 0) {
+        dcw_eval_hand_on(ws, s, go, nside);
+        if (settled) *settled = s;
+    }
     if (!go || tile0 >= s.n_live) return;
     const int n_valid = min(16, s.n_live - tile0);
     __syncthreads();
@@ -253,4 +271,14 @@ __global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_eval_layered_step_kernel(
     // ---- 2. / 4.
     dcw_eval_env_step<Env>(a, sh, ws, ev, lt, n_valid, tile0, nside, Do);
     dc_next_obs<Env>(a, sh, lt, n_valid, Do);
+}
+
+template <class Env, int HEAD, bool DEVWS>
+__global__ __launch_bounds__(WL_NT) WL_NO_PK void wide_eval_layered_step_kernel(const WideEvalArgs* __restrict__ wap, const WideLayActor* __restrict__ lap,
+                                                                                const int t, const int first, const int settle) {
+    extern __shared__ __align__(16) float wl_lds[];             // !DEVWS: [2][16][ldp]
+    __shared__ DevCollectSmem sh;                               // the tile uses its first 16 rows
+    __shared__ float raw[16 * FSRL_MAX_ACT];                    // the head's raw rows
+    __shared__ int32_t wtot[16];
+    wide_eval_layered_step_body<Env, HEAD, DEVWS>(wap, lap, t, first, settle, __builtin_amdgcn_readfirstlane((int)blockIdx.x), nullptr, wl_lds, sh, raw, wtot);
 }

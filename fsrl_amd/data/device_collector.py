@@ -20,7 +20,8 @@ workgroup per member (fsrl_collect_device_group), and each member's rows, env st
 `DeviceCollector.collect` would have produced, bit for bit.  `GroupCollector` over `DeviceCollector`s delegates to it.
 Members whose envs are all WIDE collect through fsrl_collect_device_wide_group: one launch per vector step carries the 16-row tiles
 of every member, fused or layered, and each member again gets its own solo wide collect bit for bit; a mix of wide and narrow envs
-is refused, the member named.
+is refused, the member named.  Store-less collectors over wide envs (`WideDeviceEvalCollector`s) evaluate through
+fsrl_evaluate_device_wide_group: the same grid, each member's episodes accumulated and ordered on the GPU as in its solo evaluation.
 
 Evaluation: `DeviceCollector(policy, test_envs)` with no buffer is the reference's `FastCollector(policy, test_envs)` (it makes a
 `DeviceEvalCollector`, whose collect() is the other library call; a storing collector's collect() only ever sees training envs) -- the
@@ -178,7 +179,7 @@ class WideDeviceEvalCollector(DeviceEvalCollector):
 class GroupDeviceCollector:
     """`DeviceCollector.collect` of every member in one looping launch (fsrl_collect_device_group).  collectors: one `DeviceCollector`
     per seed; the seeds' engines may be members of any kind of group, or of none.  The collectors all store (training) or are all
-    store-less (evaluation, fsrl_evaluate_device_group)."""
+    store-less (evaluation, fsrl_evaluate_device_group; over wide envs fsrl_evaluate_device_wide_group)."""
 
     def __init__(self, collectors: Sequence[DeviceCollector], max_steps_per_launch: int = 0):
         self.collectors = list(collectors)
@@ -206,7 +207,7 @@ class GroupDeviceCollector:
     def collect(self, n_episode: Union[int, Sequence[int]] = 1, **_ignored) -> List[Dict[str, Any]]:
         """n_episode: one count or one per member -> one stats dict per member, with the keys of DeviceCollector.collect"""
         from fsrl_amd.engine import (collect_device_group, collect_device_layered, collect_device_wide_group, evaluate_device_group,
-                                     evaluate_device_layered)
+                                     evaluate_device_layered, evaluate_device_wide_group)
         cols = self.collectors
         n = len(cols)
         ns = [int(n_episode)] * n if np.isscalar(n_episode) else [int(x) for x in n_episode]
@@ -226,8 +227,7 @@ class GroupDeviceCollector:
         run = ((collect_device_layered if self.store else evaluate_device_layered) if self.layered
                else (collect_device_group if self.store else evaluate_device_group))
         if self.wide:
-            assert self.store, "GroupDeviceCollector: evaluations over wide device envs are not supported yet (fsrl_collect_device_wide_group stores)"
-            run = collect_device_wide_group
+            run = collect_device_wide_group if self.store else evaluate_device_wide_group
         res = run([col.policy.engine for col in cols], [col.env._h for col in cols], ns, det, bound, lows, highs, self.max_steps_per_launch)
         dt = max(time.time() - t0, 1e-9)
         stats = []

@@ -1136,6 +1136,17 @@ def collect_device_wide_group(engines, env_handles, n_episodes, deterministic=Fa
                                 _fn="fsrl_collect_device_wide_group")
 
 
+def evaluate_device_wide_group(engines, env_handles, n_episodes, deterministic=True, bound_method=1, lows=None, highs=None,
+                               max_steps_per_launch=0):
+    """Engine.evaluate_device_wide / evaluate_device_wide_layered for k engines with ONE launch per vector step for all of them
+    (fsrl_evaluate_device_wide_group): collect_device_wide_group that stores nothing -- the episodes are accumulated and ordered on
+    the GPU, the host reads k x 32 bytes per batch and each member's episode rows once.  Member i's result and env state are its own
+    solo wide evaluation's, bit for bit; `launches` is batches x (max_steps_per_launch + 1) whatever k is.  Valid on members of any
+    kind of group or of none, on tapped and prioritised engines.  Arguments and result as collect_device_group."""
+    return collect_device_group(engines, env_handles, n_episodes, deterministic, bound_method, lows, highs, max_steps_per_launch,
+                                _fn="fsrl_evaluate_device_wide_group")
+
+
 def collect_device_group(engines, env_handles, n_episodes, deterministic=False, bound_method=1, lows=None, highs=None,
                          max_steps_per_launch=0, _store=True, _fn=None):
     """Engine.collect_device for k engines in ONE looping launch per max_steps_per_launch vector steps (fsrl_collect_device_group):

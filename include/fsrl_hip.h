@@ -1145,8 +1145,8 @@ int fsrl_evaluate_device_layered(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k,
  *                            Refused before anything changes, by name: an env of fsrl_devenv_create; layered contexts; contexts in
  *                            any kind of group; a trajectory tap; prioritised replay; whatever else fsrl_collect_device refuses.
  *                            fsrl_collect_device, fsrl_evaluate_device and their _group / _layered forms refuse a wide env and name
- *                            this call: evaluations over wide envs go through fsrl_evaluate_device_wide, grouped collects over wide
- *                            envs through fsrl_collect_device_wide_group.
+ *                            this call: evaluations over wide envs go through fsrl_evaluate_device_wide (k members':
+ *                            fsrl_evaluate_device_wide_group), grouped collects over wide envs through fsrl_collect_device_wide_group.
  *      fsrl_collect_device_wide_layered   fsrl_collect_device_wide for LAYERED contexts (hidden_sizes of any depth and width, or
  *                            force_layered; kernels_devcollect_wide_layered.hpp): the same arguments, outputs, batches, settle launches,
  *                            log replay and timing, with one kernel for every shape in the launch -- a workgroup of 512 threads runs
@@ -1214,6 +1214,29 @@ int fsrl_evaluate_device_wide_layered(fsrl_ctx* ctx, fsrl_devenv* env, int32_t n
                                       const float* act_low, const float* act_high, int32_t max_steps_per_launch, int64_t* steps_out,
                                       double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out, double* ep_rew_out,
                                       int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
+/*      fsrl_evaluate_device_wide_group   k members' wide evaluations, ONE launch per vector step for all of them
+ *                            (kernels_deveval_wide_group.hpp, host_deveval_wide_group.inc): the arguments and output layout of
+ *                            fsrl_collect_device_wide_group, nothing stored.  The grid of a step launch is the members' tiles laid
+ *                            end to end, the sum of ceil(min(env_num, n_episode) / 16) workgroups; a workgroup finds its member and
+ *                            tile in a table in device memory (the evaluations' own) and runs the solo evaluation kernel's body on
+ *                            that member's env arrays, state, running episodes and episode log, under the member's own launch
+ *                            ordinal.  A batch is S = max_steps_per_launch step launches (<= 0: 64; no log caps it) and one settle
+ *                            launch of k workgroups; then ONE copy of k x 32 bytes brings every member's settled scalars back.  The
+ *                            call ends when every member has finished: each member's n_episode rows come back once, all envs of all
+ *                            members are reset.  *launches_out = batches x (S + 1), whatever k is.  Each member's episodes,
+ *                            statistics, env states, random streams and reset ordinals are what fsrl_evaluate_device_wide /
+ *                            _wide_layered leave on a twin context, bit for bit; one member is the solo call.
+ *                            As the solo evaluation, valid on members of any kind of group or of none, with a trajectory tap, with
+ *                            prioritised replay on and with more envs than sub-buffers: no store, book, sum tree or sampler moves.
+ *                            Refused before anything changes, the member named: k outside 1..16 (the groups' limit); null arguments; an
+ *                            env of fsrl_devenv_create; a fused member beside a layered one; a context or env listed twice; a call
+ *                            inside an update; whatever else fsrl_evaluate_device_wide refuses of a member; and what
+ *                            fsrl_collect_device_group asks members to agree on -- device, head kind, network shape (layered:
+ *                            hidden_sizes), env kind, max_episode_steps, unbounded / actor_mean.  */
+int fsrl_evaluate_device_wide_group(fsrl_ctx** ctxs, fsrl_devenv** envs, int32_t k, const int32_t* n_episode, int32_t deterministic,
+                                    int32_t bound_method, const float* act_low, const float* act_high, int32_t max_steps_per_launch,
+                                    int64_t* steps_out, double* total_cost_out, int32_t* term_count_out, int32_t* trunc_count_out,
+                                    double* ep_rew_out, int32_t* ep_len_out, int32_t* episodes_out, int32_t* launches_out);
 
 #ifdef __cplusplus
 }

@@ -310,22 +310,24 @@ class EvalPol(Pol):
     training = False
 
 
-def setup_eval(hidden, n, algo, wide=False):
+def setup_eval(hidden, n, algo, wide=False, seed=1):
     """a real agent (the host path needs its torch actor) and the three collectors of an evaluation, each over a device env of its own
     wide: over wide envs -- the wide evaluation, FastCollector over the same kind of env, the storing wide collect"""
     import tempfile as tf
     from fsrl_amd.agent import PPOLagAgent, SACLagAgent
     from fsrl_amd.utils import BaseLogger
-    host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=1)
+    host = SyntheticSafetyVectorEnv(env_num=n, obs_dim=8, act_dim=2, episode_len=EPISODE_LEN, seed=seed)
     Agent = SACLagAgent if algo == "sacl" else PPOLagAgent
-    agent = Agent(host, BaseLogger(tf.mkdtemp(prefix="fsrl_amd_bench_"), name="eval"), cost_limit=10, device="cuda:0", seed=1,
+    agent = Agent(host, BaseLogger(tf.mkdtemp(prefix="fsrl_amd_bench_"), name="eval"), cost_limit=10, device="cuda:0", seed=seed,
                   hidden_sizes=tuple(hidden_list(hidden)), training_num=n, buffer_size=n * 2 * EPISODE_LEN)
     pol = agent.policy
     pol.eval()
-    envs = [DeviceLinear(pol, like=host, seed=1, wide=True if wide else None) for _ in range(3)]
+    envs = [DeviceLinear(pol, like=host, seed=seed, wide=True if wide else None) for _ in range(4 if wide else 3)]
     buf = HipVectorReplayBuffer(pol.engine, n * 2 * EPISODE_LEN, n)
     cols = dict(evaluate=WideDeviceEvalCollector(pol, envs[0]) if wide else DeviceCollector(pol, envs[0]), stepped=FastCollector(pol, envs[1]),
                 collect=DeviceCollector(pol, envs[2], buf))
+    if wide:        # a second evaluation env: the solo leg beside the grouped one (--wide --eval --ks)
+        cols["solo"] = WideDeviceEvalCollector(pol, envs[3])
     return agent, envs, cols
 
 
@@ -373,6 +375,91 @@ def main_wide_eval(a):
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
     return result
+
+
+def main_wide_eval_groups(a):
+    """--wide --eval --ks: k seeds' evaluations of env_num episodes each over wide envs, real agents in eval mode, three legs alternated
+    inside every round -- (a) `grouped` fsrl_evaluate_device_wide_group through GroupDeviceCollector, (b) `solo_seq` k solo wide
+    evaluations one after the other, (c) `stepped` FastCollector with the host actor per seed.  --algo takes a list (one run per algo);
+    --envs entries like 4096@8 run at that k alone.  Wall time around whole calls.
+    --ab-tree: the solo wide evaluation and the solo storing wide collect of this tree against that built checkout (--envs, --hidden)."""
+    from fsrl_amd.data import GroupDeviceCollector
+    if a.ab_tree:
+        result = dict(metric="env-steps/s, this tree against --ab-tree, one process per round, alternating: `evaluate` the solo wide evaluation, "
+                             "`collect` the solo storing wide collect; wall time around whole calls", rounds=a.rounds, calls=a.calls,
+                      configs=eval_ab(a))
+    else:
+        paths = ("grouped", "solo_seq", "stepped")
+        result = dict(metric="aggregate env-steps/s of k seeds' evaluations (env_num episodes each) on one GPU, real agents in eval mode, wide linear "
+                             "env obs 8 / act 2, episode length 300; wall time around whole calls; ratio = grouped / solo_seq; us_per_vector_step: "
+                             "one step of every seed", rounds=a.rounds, calls=a.calls, configs=[])
+        for algo in a.algo.split(","):
+            for hidden in parse_hidden(a.hidden):
+                if isinstance(hidden, tuple) and algo != "onpolicy":
+                    continue            # the layered shape: PPO-Lag
+                for n, at in ((int(e.partition("@")[0]), e.partition("@")[2]) for e in a.envs.split(",")):
+                    for k in (int(x) for x in a.ks.split(",")):
+                        if at and k != int(at):
+                            continue
+                        seeds = [setup_eval(hidden, n, algo, wide=True, seed=1 + i) for i in range(k)]
+                        cols = {p: [c[p] for _, _, c in seeds] for p in ("evaluate", "solo", "stepped")}
+                        legs = dict(grouped=GroupDeviceCollector(cols["evaluate"]), solo_seq=Seq(cols["solo"]), stepped=Seq(cols["stepped"]))
+                        rates = {p: [] for p in paths}
+                        for _ in range(a.rounds):
+                            for p in paths:
+                                rows, dt = timed_group(legs[p], n, a.calls)
+                                rates[p].append(rows / dt)
+                        cfg = dict(algo=algo, hidden=hidden_list(hidden), env_num=n, k=k, launches_per_evaluation=legs["grouped"].last_launches)
+                        for p in paths:
+                            cfg[p] = summary(rates[p])
+                        cfg["ratio"] = cfg["grouped"]["median"] / cfg["solo_seq"]["median"]
+                        cfg["us_per_vector_step"] = {p: 1e6 * n * k / cfg[p]["median"] for p in ("grouped", "solo_seq")}
+                        result["configs"].append(cfg)
+                        print(json.dumps(cfg), flush=True)
+                        for agent, envs, _ in seeds:
+                            for env in envs:
+                                env.close()
+                            agent.policy.engine.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+    return result
+
+
+class Seq:
+    """k collectors one after the other, with GroupDeviceCollector's collect()"""
+
+    def __init__(self, cols):
+        self.collectors = cols
+
+    def collect(self, n_episode):
+        return [c.collect(n_episode=n_episode) for c in self.collectors]
+
+
+def eval_ab(a):
+    """`--wide --eval` of this tree and of the tree at a.ab_tree, each in a process of its own, one round per process, alternating
+    -> per (hidden, env_num) the rates of the wide evaluation and of the storing wide collect, both trees"""
+    tools = {"tree": os.path.abspath(__file__), "other": os.path.join(os.path.abspath(a.ab_tree), "tools", "bench_device_collect.py")}
+    rates = {}
+    for _ in range(a.rounds):
+        for who, tool in tools.items():
+            with tempfile.TemporaryDirectory() as tmp:
+                out = os.path.join(tmp, "r.json")
+                env = {k: v for k, v in os.environ.items() if k != "FSRL_HIP_LIB"}
+                subprocess.run([sys.executable, tool, "--wide", "--eval", "--rounds", "1", "--calls", str(a.calls), "--envs", a.envs, "--hidden", a.hidden,
+                                "--algo", "onpolicy", "--out", out], check=True, stdout=subprocess.DEVNULL, env=env,
+                               cwd=os.path.dirname(os.path.dirname(tool)), timeout=900)
+                with open(out) as f:
+                    for c in json.load(f)["configs"]:
+                        if c["algo"] == "onpolicy":
+                            for leg in ("evaluate", "collect"):
+                                rates.setdefault((shape_name(c), c["env_num"], leg), {}).setdefault(who, []).append(c[leg]["env_steps_per_s"]["median"])
+    res = []
+    for (hidden, n, leg), r in sorted(rates.items(), reverse=True):
+        res.append(dict(hidden=[int(w) for w in hidden.split("x")], env_num=n, leg=leg, tree=summary(r["tree"]), other=summary(r["other"])))
+        print(json.dumps(res[-1]), flush=True)
+    return res
 
 
 def timed_eval(col, n, calls):
@@ -472,6 +559,8 @@ def main():
                                                         "to 64 envs, the looping device collect; the host replay's share of the wall time; "
                                                         "with --layered: on layered shapes, on-policy and SAC-Lag, in one file")
     a = ap.parse_args()
+    if a.wide and a.eval and a.ks:
+        return main_wide_eval_groups(a)
     if a.wide and a.ks:
         if a.layered and "x" not in a.hidden:
             a.hidden = "256x256x256"
