@@ -6,6 +6,7 @@ installed pass real vector envs exposing reset(ids) / step(act, ids) -> (obs, re
     python examples/train_agent.py --algo ppol --epoch 3
     python examples/train_agent.py --algo sacl --epoch 2 --device-actor
     python examples/train_agent.py --algo sacl --epoch 2 --prefill /tmp/dataset/dataset.npz     (examples/collect_dataset.py --out /tmp/dataset)
+    python examples/train_agent.py --algo ppol --epoch 2 --pretrain-from /tmp/dataset/dataset.npz --pretrain-updates 500 --pretrain-loss nll
     python examples/train_agent.py --algo ppol --epoch 3 --task device-point-circle    (envs on the GPU: whole collects in one looping kernel)
     python examples/train_agent.py --algo cpo --epoch 3 --task device-linear
     python examples/train_agent.py --algo ppol --epoch 3 --task device-linear --envs 1024    (65 .. 4096 envs: one launch per vector step)
@@ -57,6 +58,11 @@ def main():
     ap.add_argument("--prefill", default=None, metavar="PATH",
                     help="sacl / ddpgl / cvpo: start from a replay store filled with the episodes of this dataset (the .npz that "
                          "examples/collect_dataset.py or TrajectoryBuffer.save writes) instead of an empty one")
+    ap.add_argument("--pretrain-from", default=None, metavar="FILE",
+                    help="every agent: before training, regress the actor onto the actions of this dataset on the device (behaviour "
+                         "cloning, agent.pretrain_from -> fsrl_bc_update); the store is empty again afterwards")
+    ap.add_argument("--pretrain-updates", type=int, default=1000, help="... for this many Adam steps of --batch-size rows")
+    ap.add_argument("--pretrain-loss", choices=["mse", "nll"], default="mse", help="... under this loss (nll: not ddpgl)")
     ap.add_argument("--per-alpha", type=float, default=None, help="sacl / ddpgl: prioritised replay with this priority exponent")
     ap.add_argument("--per-beta", type=float, default=0.4, help="... and this importance-weight exponent (with --per-alpha)")
     a = ap.parse_args()
@@ -94,6 +100,9 @@ def main():
     if a.algo in ("ppol", "focops"):
         kw.update(recompute_advantage=a.recompute_advantage)
     agent = AGENTS[a.algo](env, logger, **kw)
+    if a.pretrain_from is not None:
+        losses = agent.pretrain_from(a.pretrain_from, batch_size=a.batch_size, n_updates=a.pretrain_updates, loss=a.pretrain_loss, seed=a.seed)
+        print(f"pretrain: {len(losses)} updates, {a.pretrain_loss} {losses[0]:.4f} -> {losses[-1]:.4f}")
     if device_task:
         # the host envs above gave the agent its spaces; the training envs and the test envs live on the agent's GPU: learn() and
         # evaluate() run whole evaluations there too, storing nothing (fsrl_evaluate_device; layered --hidden-sizes step the device

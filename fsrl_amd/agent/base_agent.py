@@ -4,6 +4,8 @@ HIP-resident store proxy bound to the policy's engine."""
 from abc import ABC, abstractmethod
 from typing import Optional, Tuple
 
+import numpy as np
+
 from fsrl_amd.data import FastCollector, HipVectorReplayBuffer
 from fsrl_amd.data.device_collector import evaluation_collector
 from fsrl_amd.trainer import OnpolicyTrainer
@@ -35,6 +37,46 @@ class BaseAgent(ABC):
     @property
     def state_dict(self):
         return self.policy.state_dict()
+
+    def _prefill(self, prefill, buffer, resumed: bool) -> int:
+        """learn(prefill=...): a TrajectoryBuffer or a dataset path -> rows poured into `buffer`"""
+        if resumed:
+            print(f"prefill: skipped, the resumed run restored a replay store of {len(buffer)} rows")
+            return 0
+        from fsrl_amd.data.traj_buf import TrajectoryBuffer, _read_dataset
+        tb, own = prefill, False
+        if not isinstance(prefill, TrajectoryBuffer):
+            # a file: an archive of its own on this engine's device, sized for the file, attached to nothing (it records nothing)
+            # and gone after the fill; every episode of the file is kept (no window, no filter)
+            data = _read_dataset(prefill)
+            ends = np.flatnonzero(np.asarray(data["terminals"]).astype(bool) | np.asarray(data["timeouts"]).astype(bool)) + 1
+            longest = int(np.diff(np.concatenate([[0], ends])).max()) if len(ends) else 1
+            tb = TrajectoryBuffer(max_trajectory=max(len(ends), 1), use_grid_filter=False, max_rows=max(len(data["rewards"]), longest, 1),
+                                  max_episode_len=longest)
+            tb._create(self.policy.engine, self.policy)
+            own = True
+            tb.load(data)
+        try:
+            rows = buffer.fill_from(tb, policy=self.policy)
+        finally:
+            if own:
+                tb.close()
+        print(f"prefill: {rows} rows poured into the replay store ({len(buffer)} rows held)")
+        return rows
+
+    def pretrain_from(self, dataset, batch_size: int = 256, n_updates: int = 1000, loss: str = "mse", seed: int = 0) -> np.ndarray:
+        """Warm-start the actor by behaviour cloning (policy.pretrain -> fsrl_bc_update) on a dataset: a TrajectoryBuffer, or the
+        path of one saved (examples/collect_dataset.py).  Its episodes are poured into the agent's store, the actor is regressed
+        onto their actions for n_updates Adam steps of batch_size rows (loss "mse" | "nll"), and the store is emptied again, so
+        that learn() afterwards starts as it does today -- from the pre-trained actor.  Critics are not touched.  Every agent with
+        two hidden layers of at most 256 units; other shapes are refused by name ("layered").  -> the per-update losses."""
+        buffer = HipVectorReplayBuffer(self.policy.engine)
+        buffer.reset()
+        try:
+            self._prefill(dataset, buffer, resumed=False)
+            return self.policy.pretrain(buffer, batch_size=batch_size, n_updates=n_updates, loss=loss, seed=seed)
+        finally:
+            buffer.reset()
 
 
 class OnpolicyAgent(BaseAgent):

@@ -99,32 +99,6 @@ class OffpolicyAgent(BaseAgent):
             raise ValueError("prioritized_replay needs the library's sampler: with reference_rng=True the batch indices are drawn "
                              "uniformly on the host")
 
-    def _prefill(self, prefill, buffer, resumed: bool) -> int:
-        """learn(prefill=...): a TrajectoryBuffer or a dataset path -> rows poured into `buffer`"""
-        if resumed:
-            print(f"prefill: skipped, the resumed run restored a replay store of {len(buffer)} rows")
-            return 0
-        from fsrl_amd.data.traj_buf import TrajectoryBuffer, _read_dataset
-        tb, own = prefill, False
-        if not isinstance(prefill, TrajectoryBuffer):
-            # a file: an archive of its own on this engine's device, sized for the file, attached to nothing (it records nothing)
-            # and gone after the fill; every episode of the file is kept (no window, no filter)
-            data = _read_dataset(prefill)
-            ends = np.flatnonzero(np.asarray(data["terminals"]).astype(bool) | np.asarray(data["timeouts"]).astype(bool)) + 1
-            longest = int(np.diff(np.concatenate([[0], ends])).max()) if len(ends) else 1
-            tb = TrajectoryBuffer(max_trajectory=max(len(ends), 1), use_grid_filter=False, max_rows=max(len(data["rewards"]), longest, 1),
-                                  max_episode_len=longest)
-            tb._create(self.policy.engine, self.policy)
-            own = True
-            tb.load(data)
-        try:
-            rows = buffer.fill_from(tb, policy=self.policy)
-        finally:
-            if own:
-                tb.close()
-        print(f"prefill: {rows} rows poured into the replay store ({len(buffer)} rows held)")
-        return rows
-
 
 class SACLagAgent(OffpolicyAgent):
     name = "SACLagAgent"

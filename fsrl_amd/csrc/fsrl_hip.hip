@@ -239,6 +239,7 @@ struct fsrl_ctx {
     struct fsrl_tap* tap = nullptr; // the trajectory archive's tap on this context's store ingest (host_traj.inc), owned by the archive
     struct PerState* per = nullptr; // prioritised replay: the sum tree over this context's store (host_per.inc), owned
     std::vector<struct fsrl_devenv*> devenvs;     // device envs made on this context, not owned: one that outlives it loses its back pointer
+    struct BcState* bc = nullptr;   // behaviour cloning's working set (host_bc.inc), owned
 };
 static bool ctx_is_replay(const fsrl_ctx* c);
 static void sac_free(fsrl_ctx* c);
@@ -267,6 +268,7 @@ static void devenv_ctx_gone(fsrl_ctx* c);        // ... before a device env made
 static int per_ingest(fsrl_ctx* c, const uint8_t* recs_d, int rec, int k);
 static int per_store_reset(fsrl_ctx* c);
 static void per_free(fsrl_ctx* c);
+static void bc_free(fsrl_ctx* c);
 static int focops_pass(fsrl_ctx* c, int32_t* stopped_out);
 static int pass_verdict(fsrl_ctx* c, int32_t* stopped_out);
 
@@ -546,6 +548,7 @@ extern "C" int fsrl_ctx_destroy(fsrl_ctx* c) {
     tr_free(c);
     sac_free(c);
     per_free(c);
+    bc_free(c);
     foc_free(c);
     lay_free(c);
     c->mem.release_all();
@@ -757,8 +760,12 @@ extern "C" int fsrl_params_get(fsrl_ctx* c, float* flat, int64_t n) {
     CHECK_ARG(c && flat, "null argument");
     return copy_flat(c, c->P, flat, nullptr, n);
 }
+static int bc_grads_get(fsrl_ctx* c, float* flat, int64_t n, bool* served);      // host_bc.inc: replay contexts after fsrl_bc_update
 extern "C" int fsrl_grads_get(fsrl_ctx* c, float* flat, int64_t n) {
     CHECK_ARG(c && flat, "null argument");
+    bool served = false;
+    const int rc = bc_grads_get(c, flat, n, &served);
+    if (served) return rc;
     return copy_flat(c, c->G, flat, nullptr, n);
 }
 extern "C" int fsrl_optim_reset(fsrl_ctx* c) {
@@ -1654,3 +1661,5 @@ extern "C" float fsrl_get_lr(const fsrl_ctx* c, int32_t group) {
 
 #include "host_traj.inc"
 #include "host_train_state.inc"
+#include "kernels_bc.hpp"
+#include "host_bc.inc"

@@ -121,9 +121,27 @@ class Engine:
         return out
 
     def get_grads(self):
-        out = np.empty(self.n_params, np.float32)
+        """the last minibatch gradient; a replay context after bc_update: the actor gradient of the last BC step"""
+        out = np.empty(getattr(self, "n_sac_actor", self.n_params) if getattr(self, "_bc_ran", False) else self.n_params, np.float32)
         _lib.check(self.lib.fsrl_grads_get(self._ctx, _ptr(out, _f32p), out.size))
         return out
+
+    def bc_update(self, batch_size, n_updates, loss="mse", indices=None, seed=0) -> np.ndarray:
+        """fsrl_bc_update: n_updates behaviour-cloning steps of the actor alone onto the store's actions, batch_size stored rows each
+        (indices: [n_updates, batch_size] store slots; None: the library draws them from `seed`).  loss "mse" | "nll".  Fused contexts
+        of every agent; layered contexts, an empty store, an index outside the stored rows, nll on the DDPG-Lag actor and a member
+        of a live group are refused (AssertionError naming the reason).  -> the per-update losses."""
+        code = {"mse": 0, "nll": 1}.get(loss)
+        if code is None:
+            raise ValueError(f"loss must be 'mse' or 'nll', got {loss!r}")
+        idx = None if indices is None else np.ascontiguousarray(indices, np.int64).reshape(-1)
+        if idx is not None and idx.size != int(batch_size) * int(n_updates):
+            raise ValueError(f"indices must hold n_updates * batch_size = {int(batch_size) * int(n_updates)} slots, got {idx.size}")
+        out = np.empty(max(int(n_updates), 1), np.float32)
+        _lib.check(self.lib.fsrl_bc_update(self._ctx, int(batch_size), int(n_updates), code, _ptr(idx, _i64p), int(seed),
+                                           _ptr(out, _f32p)))
+        self._bc_ran = True
+        return out[:int(n_updates)]
 
     def state_snapshot(self):
         """Checkpoint parameters + Adam state in HBM (device-to-device, asynchronous)."""
@@ -146,6 +164,18 @@ class Engine:
         """The context's full training state as bytes (fsrl_train_state_export): parameters, optimiser state, random streams,
         running statistics and, with_store, the transition store.  A pure function of the state; env state is not in it."""
         return self.train_state_array(with_store).tobytes()
+
+    def train_state_sections(self, with_store: bool = False) -> dict:
+        """train_state() cut into its tagged sections: {tag: payload bytes as a uint8 array}, e.g. "P" / "M" / "V" (on-policy
+        parameters and Adam moments, float32, the API's flat order first), "PA" / "MA" / "VA" / "PAT" / "PQ" / "PQT" / "MQ" / "VQ"
+        (replay contexts), "HOST" (counters, streams, rates) and, with_store, the store's books and columns."""
+        blob = self.train_state_array(with_store)
+        pos, out = 24 + 8 * int(blob[16:20].view(np.uint32)[0]), {}
+        while pos < blob.size - 8:
+            n = int(blob[pos + 8:pos + 16].view(np.int64)[0])
+            out[blob[pos:pos + 4].tobytes().decode().strip()] = blob[pos + 16:pos + 16 + n]
+            pos += 16 + (n + 7) // 8 * 8
+        return out
 
     def load_train_state(self, blob) -> None:
         """fsrl_train_state_import: everything about `blob` (bytes or a uint8 array) is checked before the first write, so a

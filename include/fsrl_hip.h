@@ -994,6 +994,30 @@ int fsrl_traj_import(fsrl_traj* t, int64_t rows, const float* obs, const float* 
 int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int64_t n, int32_t first_env,
                     int32_t bound_method, const float* act_low, const float* act_high, int64_t* rows_out);
 
+/* ---- Behaviour cloning: the fused actor regressed onto the store's actions on the device.
+ *      (fsrl_amd/csrc/kernels_bc.hpp, host_bc.inc; DESIGN.md "Behaviour cloning"; INTEGRATION.md "Behaviour cloning")
+ *
+ *      n_updates optimiser steps on the ACTOR alone, each over batch_size stored rows (any batch_size >= 1): two launches per step --
+ *      bc_fwd_bwd_kernel (gather by index, actor forward, loss head, activation backward per 16-row tile) and bc_wgrad_kernel (weight
+ *      gradients per 16 x 16 output tile with the Adam step of the tile fused in).  No gradient-norm clip.
+ *        loss 0 (mse)  mean over rows of sum_d (m_d - a_d)^2, m the actor's mean as the context's collector forms it: max_action *
+ *                      tanh(head), or the head under `unbounded` / an unbounded actor_mean; the DDPG-Lag actor always takes the tanh
+ *        loss 1 (nll)  mean over rows of sum_d [ (a_d - m_d)^2 / (2 sigma_d^2) + log sigma_d ]; on-policy: sigma = exp(sigma_param);
+ *                      SAC-Lag / CVPO: sigma = exp(clamp(head[Da + d], -20, 2)), the clamp's gradient zero outside it
+ *      indices: [n_updates][batch_size] store slots, or NULL: the library draws them uniformly over the stored rows from `seed`.
+ *      loss_out: [n_updates] losses (the call then waits for them), or NULL (the call returns with the work enqueued).  Every call
+ *      first waits for the context's compute stream to drain.  fsrl_grads_get afterwards returns the last step's gradient (on-policy
+ *      mse: sigma_param's slots zero; replay contexts: the actor's gradient, n = the actor's parameter count).
+ *      The step uses the actor optimiser's moments, step count and learning rate: PPO-Lag the shared Adam (its one step count
+ *      advances; the critics' slots are not touched), FOCOPS and the replay agents the actor's Adam, CPO / TRPO-Lag -- whose actor has
+ *      no optimiser -- the actor's otherwise unused slots of the shared vectors.  The actor's W2 mirror follows W2; DDPG-Lag's and
+ *      CVPO's actor_old is set equal to the actor at the end of the call.  fsrl_train_state_export / _import carry all of it.
+ *      FSRL_EINVAL / FSRL_ESTATE before anything is touched, the reason in fsrl_last_error(): a layered context, an empty store, an
+ *      index outside the stored rows, nll on the deterministic (DDPG-Lagrangian) actor, a member of a live group.
+ *      Stream order: as an update's entry (the staging window is flushed, the store joined, a resident actor ended). */
+int fsrl_bc_update(fsrl_ctx* ctx, int32_t batch_size, int32_t n_updates, int32_t loss, const int64_t* indices, uint64_t seed,
+                   float* loss_out);
+
 /* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy and replay contexts.
  *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc, host_devcollect_group.inc; INTEGRATION.md "Device environments")
  *
