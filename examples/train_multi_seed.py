@@ -69,6 +69,10 @@ collects, a workgroup per seed, per seed bit-identical to its own device collect
 3.4.1).  The updates go through the same groups as above.  Layered --hidden-sizes are refused by the library at the first collect.
     python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --task device-linear
     python examples/train_multi_seed.py --algo sacl --seeds 4 --epoch 2 --grouped --task device-point-circle
+--pretrain-from FILE (--grouped, every algo it takes; --pretrain-updates N, --pretrain-loss mse|nll): before the groups are built every
+seed's actor is regressed onto the dataset's actions (examples/collect_dataset.py) -- the dataset poured ONCE into seed 0's store, all
+seeds' updates in the two launches per step of one (fsrl_amd.agent.pretrain_group_from -> fsrl_bc_update_group), the store empty again.
+    python examples/train_multi_seed.py --algo ppol --seeds 8 --epoch 2 --grouped --pretrain-from /tmp/dataset/dataset.npz
 --test-episodes N (--grouped; default 0: no evaluation): after every epoch each seed's policy is evaluated for N episodes on test envs
 of its own and one line per seed is printed.  Over device tasks every seed has a second DeviceVectorEnv and a store-less
 DeviceCollector, and the evaluation of ALL seeds is one GroupDeviceCollector.collect -> fsrl_evaluate_device_group: nothing is
@@ -205,6 +209,18 @@ def parse_sweep(specs, k):
 GROUPED_ALGOS = ("ppol", "focops", "sacl", "ddpgl", "cvpo", "cpo", "trpol")      # what --grouped takes
 
 
+def pretrain_seeds(a, agents):
+    """--pretrain-from: warm-start every seed's actor by behaviour cloning BEFORE the groups exist -- the dataset poured once into seed
+    0's store, all seeds regressed onto it in the two launches per step of one (fsrl_bc_update_group), seed i drawing its minibatches
+    from its own stream; the store is empty again afterwards"""
+    if a.pretrain_from is None:
+        return
+    from fsrl_amd.agent import pretrain_group_from
+    losses = pretrain_group_from(agents, a.pretrain_from, batch_size=256, n_updates=a.pretrain_updates, loss=a.pretrain_loss)
+    for seed, l in enumerate(losses):
+        print(f"pretrain seed {seed}: {len(l)} updates, {a.pretrain_loss} {l[0]:.4f} -> {l[-1]:.4f}")
+
+
 def run_grouped_trust(a):
     """k CPO (TRPO-Lag) seeds: lock-step collection from one host thread (a collect group over the seeds' on-policy engines), each
     seed's pre_update_fn, then ONE TrustPolicyGroup.update -- the seeds' own updates on a worker thread each -- and reset_buffer."""
@@ -217,6 +233,7 @@ def run_grouped_trust(a):
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(make_collector(a, agent, env, buf))
+    pretrain_seeds(a, agents)
     cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
     group = TrustPolicyGroup([ag.policy for ag in agents], collect_group=cgroup)
     evaluator = make_evaluator(a, agents)
@@ -271,6 +288,7 @@ def run_grouped_replay(a):
             buf = HipPrioritizedVectorReplayBuffer(agent.policy.engine, None, a.envs, **per)
         agents.append(agent); bufs.append(buf)
         cols.append(make_collector(a, agent, env, buf))
+    pretrain_seeds(a, agents)
     group = {"sacl": SACPolicyGroup, "ddpgl": DDPGPolicyGroup, "cvpo": CVPOPolicyGroup}[a.algo]([ag.policy for ag in agents])
     cgroup, gcol = make_group_collector(a, lambda: EngineCollectGroup([ag.policy.engine for ag in agents]), cols)
     evaluator = make_evaluator(a, agents)
@@ -328,6 +346,7 @@ def run_grouped(a):
         buf = HipVectorReplayBuffer(agent.policy.engine, None, a.envs)
         agents.append(agent); bufs.append(buf)
         cols.append(make_collector(a, agent, env, buf))
+    pretrain_seeds(a, agents)
     group = PolicyGroup([ag.policy for ag in agents])
     batch_size, repeat = a.sweep.get("batch_size", 256), a.sweep.get("repeat_per_collect", 4)       # ints, or one int per member
     mult = (lambda p: f"nu {float(p._nu):.3f}") if a.algo == "focops" else (lambda p: f"lambda {p.lag_optims[0].get_lag():.3f}")
@@ -403,7 +422,16 @@ def parse_args(argv=None):
     ap.add_argument("--per-alpha", type=float, default=None, help="sacl / ddpgl: prioritised replay with this priority exponent")
     ap.add_argument("--per-beta", type=float, default=None, help="... and this importance-weight exponent (with --per-alpha; default 0.4)")
     ap.add_argument("--per-no-weight-norm", action="store_true", help="... without dividing the weights by the batch maximum (with --per-alpha)")
+    ap.add_argument("--pretrain-from", default=None, metavar="FILE",
+                    help="--grouped: a dataset saved by examples/collect_dataset.py; every seed's actor is regressed onto its actions first "
+                         "(behaviour cloning for all seeds at once, fsrl_amd.agent.pretrain_group_from -> fsrl_bc_update_group)")
+    ap.add_argument("--pretrain-updates", type=int, default=1000, help="... for this many Adam steps of 256 rows")
+    ap.add_argument("--pretrain-loss", choices=["mse", "nll"], default="mse", help="... under this loss (nll: not ddpgl)")
     a = ap.parse_args(argv)
+    if a.pretrain_from is not None and not a.grouped:
+        ap.error("--pretrain-from: with --grouped (one seed: examples/train_agent.py --pretrain-from)")
+    if a.pretrain_from is not None and (a.pretrain_updates < 1 or (a.pretrain_loss == "nll" and a.algo == "ddpgl")):
+        ap.error("--pretrain-updates: >= 1; --pretrain-loss nll needs a Gaussian actor, the DDPG-Lagrangian actor is deterministic")
     if a.per_alpha is None and (a.per_beta is not None or a.per_no_weight_norm):
         ap.error("--per-beta / --per-no-weight-norm: options of prioritised replay, which --per-alpha switches on")
     if a.per_alpha is not None:
@@ -434,6 +462,8 @@ def parse_args(argv=None):
         ap.error("--workers: 0 (in-process envs) .. --envs")
     if isinstance(a.hidden_sizes, str):
         a.hidden_sizes = tuple(int(w) for w in a.hidden_sizes.lower().split("x"))
+    if a.pretrain_from is not None and is_layered(a.hidden_sizes):
+        ap.error("--pretrain-from: behaviour cloning runs on the fused kernels (two hidden layers of at most 256 units), not on layered seeds")
     if a.grouped and a.algo in ("focops", "cvpo") and is_layered(a.hidden_sizes):
         ap.error(f"--grouped --algo {a.algo}: layered seeds (--hidden-sizes other than two layers of at most 256 units) do not group yet")
     return a

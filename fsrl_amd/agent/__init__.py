@@ -3,6 +3,7 @@ from fsrl_amd._lazy import install
 
 install(__name__, globals(), {
     "BaseAgent": "base_agent",
+    "pretrain_group_from": "base_agent",
     "OnpolicyAgent": "base_agent",
     "OffpolicyAgent": "sac_lag_agent",
     "PPOLagAgent": "ppo_lag_agent",

@@ -79,6 +79,28 @@ class BaseAgent(ABC):
             buffer.reset()
 
 
+def pretrain_group_from(agents, dataset, batch_size=256, n_updates=1000, loss="mse", seeds=None, shared_store=True):
+    """BaseAgent.pretrain_from for k agents at once (fsrl_amd.policy.pretrain_group -> fsrl_bc_update_group): the dataset is poured
+    ONCE, into agents[0]'s store, every agent's actor is regressed onto its rows in the same two launches per step, and that store
+    is emptied again.  Agent i's indices are drawn from seeds[i] (default: i), so the seeds see different minibatches of the one
+    dataset; its actor is what its own pretrain_from leaves with that seed.  shared_store=False pours the dataset into every agent's
+    own store instead.  Call it before the agents' policies are put into a PolicyGroup.  -> one array of losses per agent."""
+    from fsrl_amd.policy import pretrain_group
+    agents = list(agents)
+    holders = agents[:1] if shared_store else agents
+    buffers = [HipVectorReplayBuffer(ag.policy.engine) for ag in holders]
+    for b in buffers:
+        b.reset()
+    try:
+        for ag, b in zip(holders, buffers):
+            ag._prefill(dataset, b, resumed=False)
+        return pretrain_group([ag.policy for ag in agents], buffers[0] if shared_store else None, batch_size=batch_size, n_updates=n_updates,
+                              loss=loss, seeds=list(range(len(agents))) if seeds is None else seeds, shared_store=shared_store)
+    finally:
+        for b in buffers:
+            b.reset()
+
+
 class OnpolicyAgent(BaseAgent):
     name = "OnpolicyAgent"
 

@@ -1662,4 +1662,6 @@ extern "C" float fsrl_get_lr(const fsrl_ctx* c, int32_t group) {
 #include "host_traj.inc"
 #include "host_train_state.inc"
 #include "kernels_bc.hpp"
+#include "kernels_bc_group.hpp"
 #include "host_bc.inc"
+#include "host_bc_group.inc"

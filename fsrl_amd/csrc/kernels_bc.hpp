@@ -40,13 +40,15 @@ struct BcArgs {
     float max_action;
 };
 
+// The tile's whole pass.  bc_fwd_bwd_kernel runs it on its arguments, bc_fwd_bwd_group_kernel (kernels_bc_group.hpp) on the member's:
+// ONE body, so a member's tile is the solo tile instruction for instruction.  `tile` is uniform (a scalar register).
 template <int H, int HEAD>
-__global__ __launch_bounds__(4 * H) void bc_fwd_bwd_kernel(const float* __restrict__ P, const ModelDesc md, const BcArgs a) {
+__device__ __forceinline__ void bc_fwd_bwd_body(const float* __restrict__ P, const ModelDesc& md, const BcArgs& a, const int tile) {
     __shared__ TileSmem<H> sm;
     constexpr int NT = TileGeom<H>::NT;
     constexpr int KC = H / 16, JE = BcEarly<H>::JE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, q = lane >> 4;
-    const int row0 = (int)blockIdx.x * 16;
+    const int row0 = tile * 16;
     const NetOff no = md.net[0];
     const int Do = md.Do, Da = md.Da;
     const int n_valid = min(16, a.B - row0);           // >= 1: the grid is ceil(B / 16)
@@ -131,10 +133,14 @@ __global__ __launch_bounds__(4 * H) void bc_fwd_bwd_kernel(const float* __restri
     if (tid == 0) {                                          // rows in ascending order (fixed => deterministic)
         float t = 0.0f;
         for (int i = 0; i < 16; ++i) t += sm.st[i * 4];
-        a.lossp[blockIdx.x] = t;
+        a.lossp[tile] = t;
     }
     tile_backward<H, 16>(sm, no, wb, a.A1 + (size_t)row0 * H, a.A2 + (size_t)row0 * H, a.D1 + (size_t)row0 * H,
                          a.D2 + (size_t)row0 * H, a.DO + (size_t)row0 * FSRL_DOW, tid, false);
+}
+template <int H, int HEAD>
+__global__ __launch_bounds__(4 * H) void bc_fwd_bwd_kernel(const float* __restrict__ P, const ModelDesc md, const BcArgs a) {
+    bc_fwd_bwd_body<H, HEAD>(P, md, a, (int)blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------ weight gradients + Adam
@@ -153,8 +159,9 @@ __host__ __device__ constexpr int bc_wg_n2(int H) { return (H / 16) * (H / 16); 
 __host__ __device__ inline int bc_wg_n1(int H, int Do) { return (H / 16) * ((Do + 15) / 16); }
 __host__ __device__ inline int bc_wg_grid(int H, int Do, int sigma_job) { return bc_wg_n2(H) + bc_wg_n1(H, Do) + H / 16 + (sigma_job ? 1 : 0) + 1; }
 
+// workgroup b of the nb = bc_wg_grid(...) of one update (the solo launch's grid; a member's share of the grouped launch's)
 template <int H>
-__global__ __launch_bounds__(256) void bc_wgrad_kernel(const ModelDesc md, const BcWgradArgs a) {
+__device__ __forceinline__ void bc_wgrad_body(const ModelDesc& md, const BcWgradArgs& a, int b, const int nb) {
     __shared__ float part[4][256];
     __shared__ float partb[4][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, q = lane >> 4;
@@ -162,8 +169,7 @@ __global__ __launch_bounds__(256) void bc_wgrad_kernel(const ModelDesc md, const
     const int Do = md.Do, Da = md.Da;
     constexpr int T = H / 16;
     const int n2 = bc_wg_n2(H), n1 = bc_wg_n1(H, Do);
-    int b = (int)blockIdx.x;
-    if (b == (int)gridDim.x - 1) {                           // the update's mean loss: tiles in ascending order
+    if (b == nb - 1) {                                       // the update's mean loss: tiles in ascending order
         if (tid == 0) {
             float t = 0.0f;
             for (int i = 0; i < a.tiles; ++i) t += a.lossp[i];
@@ -241,4 +247,8 @@ __global__ __launch_bounds__(256) void bc_wgrad_kernel(const ModelDesc md, const
         adam_element(a.P, a.M, a.V, i, a.P[i], g, 1.0f, 0.0f, a.one_minus_b1, a.beta2, a.one_minus_b2, a.step_size, a.bc2_sqrt, a.eps, md,
                      nullptr, 0.0f, 0.0f);
     }
+}
+template <int H>
+__global__ __launch_bounds__(256) void bc_wgrad_kernel(const ModelDesc md, const BcWgradArgs a) {
+    bc_wgrad_body<H>(md, a, (int)blockIdx.x, (int)gridDim.x);
 }

@@ -1210,6 +1210,41 @@ def collect_device_group(engines, env_handles, n_episodes, deterministic=False, 
             for i in range(k)]
 
 
+def bc_update_group(engines, batch_size, n_updates, loss="mse", indices=None, seeds=None, shared_store=False):
+    """Engine.bc_update for k engines in the TWO launches per step of one (fsrl_bc_update_group): member i's losses, gradient and
+    actor are Engine.bc_update's on it, bit for bit.  The engines are fused, share a network shape and head kind, and sit in no live
+    group (pre-train first, build the groups afterwards).  batch_size, n_updates, loss: one value or one per member; n_updates 0: the
+    member sits the call out.  indices: None (member i's are drawn from seeds[i]; seeds: one value or one per member, default 0) or
+    one [n_updates_i, batch_size_i] array per member (None for a member that sits out).  shared_store: every member gathers its rows
+    from engines[0]'s store.  -> one array of per-update losses per member."""
+    engines = list(engines)
+    k = len(engines)
+    each = lambda v, t: np.ascontiguousarray(np.broadcast_to(np.asarray(v, t), (k,)) if k else np.zeros(0, t))
+    B, n = each(batch_size, np.int32), each(n_updates, np.int32)
+    codes = [{"mse": 0, "nll": 1}.get(v) for v in ([loss] * k if isinstance(loss, str) else list(loss))]
+    if len(codes) != k or None in codes:
+        raise ValueError(f"loss must be 'mse' or 'nll', or one of them per member, got {loss!r}")
+    idx = None
+    if indices is not None:
+        assert len(indices) == k, "one index array per engine"
+        blocks = [np.zeros(0, np.int64) if n[i] <= 0 else np.asarray(indices[i], np.int64).reshape(-1) for i in range(k)]
+        for i in range(k):
+            if blocks[i].size != max(int(n[i]), 0) * int(B[i]):
+                raise ValueError(f"member {i}: indices must hold n_updates * batch_size = {int(n[i]) * int(B[i])} slots, got {blocks[i].size}")
+        idx = np.ascontiguousarray(np.concatenate(blocks)) if k else None
+    sd = each(0 if seeds is None else seeds, np.uint64)
+    off = np.concatenate([[0], np.cumsum(np.maximum(n, 0), dtype=np.int64)])
+    out = np.empty(max(int(off[-1]), 1), np.float32)
+    lib = engines[0].lib if k else _lib.load()
+    ctxs = (C.c_void_p * max(k, 1))(*[e._ctx for e in engines])
+    _lib.check(lib.fsrl_bc_update_group(ctxs, k, _ptr(B, _i32p), _ptr(n, _i32p), _ptr(np.asarray(codes, np.int32), _i32p), _ptr(idx, _i64p),
+                                        _ptr(sd, C.POINTER(C.c_uint64)), int(bool(shared_store)), _ptr(out, _f32p)))
+    for i, e in enumerate(engines):
+        if n[i] > 0:
+            e._bc_ran = True
+    return [out[off[i]:off[i + 1]].copy() for i in range(k)]
+
+
 class _NativeGroup:
     """`engines`, `lib` and the native handle `_g` of a group made by `<_symbols>_create` and freed by `<_symbols>_destroy`"""
     _symbols = ""                       # the C ABI prefix of the group: fsrl_group, fsrl_sac_group, ...

@@ -3,6 +3,7 @@ from fsrl_amd._lazy import install
 
 install(__name__, globals(), {
     "BasePolicy": "base_policy",
+    "pretrain_group": "base_policy",
     "LagrangianPolicy": "lagrangian_base",
     "PPOLagrangian": "ppo_lag",
     "TRPOLagrangian": "trpo_lag",

@@ -316,3 +316,24 @@ class BasePolicy(ABC, nn.Module):
     @abstractmethod
     def update(self, sample_size: int, buffer, **kwargs: Any):
         pass
+
+
+def pretrain_group(policies, buffer=None, batch_size=256, n_updates=1000, loss="mse", seeds=0, indices=None, shared_store=False):
+    """BasePolicy.pretrain for k policies in the two launches per step of one (fsrl_amd.engine.bc_update_group ->
+    fsrl_bc_update_group): policy i's actor is the one its own pretrain() leaves, bit for bit.  The policies are fused, share a network
+    shape and head kind and sit in no PolicyGroup yet.  batch_size, n_updates, loss, seeds: one value or one per policy (n_updates
+    0: the policy sits out).  buffer: None (every policy's own filled buffer), or the buffer of policies[0]'s engine with
+    shared_store=True: every policy is regressed onto the rows of that ONE store.  Every pre-trained policy's host mirror is synced
+    afterwards, as pretrain() does.  -> one array of per-update losses per policy."""
+    from fsrl_amd.engine import bc_update_group
+    policies = list(policies)
+    if buffer is not None:
+        assert shared_store and getattr(buffer, "engine", None) is policies[0].engine, \
+            "pretrain_group() takes the buffer of policies[0]'s engine, with shared_store=True"
+    losses = bc_update_group([p.engine for p in policies], batch_size, n_updates, loss=loss, indices=indices, seeds=seeds,
+                             shared_store=shared_store)
+    for p, l in zip(policies, losses):
+        if len(l):
+            p._mark_stale()
+            p._pull_params()
+    return losses

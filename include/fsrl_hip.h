@@ -1017,6 +1017,25 @@ int fsrl_store_fill(fsrl_ctx* ctx, fsrl_traj* t, const int32_t* episode_ids, int
  *      Stream order: as an update's entry (the staging window is flushed, the store joined, a resident actor ended). */
 int fsrl_bc_update(fsrl_ctx* ctx, int32_t batch_size, int32_t n_updates, int32_t loss, const int64_t* indices, uint64_t seed,
                    float* loss_out);
+/*      k contexts' updates in the two launches of one (kernels_bc_group.hpp, host_bc_group.inc): 1 <= k <= 16 fused contexts, none of
+ *      them in a live group -- pre-train first, build the groups afterwards.  batch_size[k], n_updates[k], loss[k] are per member
+ *      and may differ; n_updates[i] == 0: member i sits the call out and nothing of it is touched (step count, theta_version).  The
+ *      call runs max_i n_updates[i] steps, member i active in the first n_updates[i] of them: bc_fwd_bwd_group_kernel over the active
+ *      members' 16-row tiles laid end to end, bc_wgrad_group_kernel with the member as grid.y.  indices: the members'
+ *      [n_updates[i]][batch_size[i]] blocks concatenated in member order, or NULL: member i's are drawn from seeds[i] exactly as the
+ *      solo call draws them from `seed` (seeds may be NULL with indices).  loss_out: sum(n_updates) losses in member order, or NULL.
+ *      shared_store != 0: every member gathers its rows from MEMBER 0's store -- a dataset is poured once, not k times; index checks
+ *      and the draw run over member 0's stored rows, only that store is joined, the other members' stores are neither read nor moved.
+ *      Per member the result is fsrl_bc_update's on a context holding the same rows, BIT FOR BIT: losses, fsrl_grads_get, parameters,
+ *      W2 mirror, moments, step count, actor_old, theta_version (one kernel body for both, the same host Adam scalars); k = 1 is the
+ *      solo call.  Members must agree on obs_dim, act_dim, hidden / hidden1 / hidden2, the head kind (on-policy | SAC-Lag, CVPO |
+ *      DDPG-Lag) and unbounded / actor_mean, and live on one device; max_action, learning rates, betas / eps may differ.
+ *      Refused before anything is touched, naming the member: k outside 1..16, null arguments, a context listed twice, whatever
+ *      fsrl_bc_update refuses of a member (the empty store and the indices: member 0's under shared_store), members that disagree.
+ *      Stream order: the launches go on member 0's compute stream (also where member 0 sits out), behind everything every active
+ *      member's compute stream holds; every active member's stream is ordered behind the call's last launch. */
+int fsrl_bc_update_group(fsrl_ctx** ctxs, int32_t k, const int32_t* batch_size, const int32_t* n_updates, const int32_t* loss,
+                         const int64_t* indices, const uint64_t* seeds, int32_t shared_store, float* loss_out);
 
 /* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy and replay contexts.
  *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc, host_devcollect_group.inc; INTEGRATION.md "Device environments")
