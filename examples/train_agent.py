@@ -60,7 +60,8 @@ def main():
                          "examples/collect_dataset.py or TrajectoryBuffer.save writes) instead of an empty one")
     ap.add_argument("--pretrain-from", default=None, metavar="FILE",
                     help="every agent: before training, regress the actor onto the actions of this dataset on the device (behaviour "
-                         "cloning, agent.pretrain_from -> fsrl_bc_update); the store is empty again afterwards")
+                         "cloning, agent.pretrain_from -> fsrl_bc_update, with layered --hidden-sizes fsrl_bc_update_layered); the store is "
+                         "empty again afterwards")
     ap.add_argument("--pretrain-updates", type=int, default=1000, help="... for this many Adam steps of --batch-size rows")
     ap.add_argument("--pretrain-loss", choices=["mse", "nll"], default="mse", help="... under this loss (nll: not ddpgl)")
     ap.add_argument("--per-alpha", type=float, default=None, help="sacl / ddpgl: prioritised replay with this priority exponent")

@@ -244,6 +244,7 @@ SIGNATURES = {
     "fsrl_traj_import": (C.c_int, [_ctx, C.c_int64, _f, _f, _f, _d, _d, _u8, _u8, C.c_int32, _i64, _i64]),
     "fsrl_store_fill": (C.c_int, [_ctx, _ctx, _i32, C.c_int64, C.c_int32, C.c_int32, _f, _f, _i64]),
     "fsrl_bc_update": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _i64, C.c_uint64, _f]),
+    "fsrl_bc_update_layered": (C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_int32, _i64, C.c_uint64, _f]),
     "fsrl_bc_update_group": (C.c_int, [_P(_ctx), C.c_int32, _i32, _i32, _i32, _i64, _P(C.c_uint64), C.c_int32, _f]),
     "fsrl_devenv_create": (C.c_int, [_ctx, _P(DevEnvConfig), _P(_ctx)]),
     "fsrl_devenv_create_wide": (C.c_int, [_ctx, _P(DevEnvConfig), _P(_ctx)]),

@@ -65,11 +65,11 @@ class BaseAgent(ABC):
         return rows
 
     def pretrain_from(self, dataset, batch_size: int = 256, n_updates: int = 1000, loss: str = "mse", seed: int = 0) -> np.ndarray:
-        """Warm-start the actor by behaviour cloning (policy.pretrain -> fsrl_bc_update) on a dataset: a TrajectoryBuffer, or the
+        """Warm-start the actor by behaviour cloning (policy.pretrain -> fsrl_bc_update / fsrl_bc_update_layered) on a dataset: a TrajectoryBuffer, or the
         path of one saved (examples/collect_dataset.py).  Its episodes are poured into the agent's store, the actor is regressed
         onto their actions for n_updates Adam steps of batch_size rows (loss "mse" | "nll"), and the store is emptied again, so
-        that learn() afterwards starts as it does today -- from the pre-trained actor.  Critics are not touched.  Every agent with
-        two hidden layers of at most 256 units; other shapes are refused by name ("layered").  -> the per-update losses."""
+        that learn() afterwards starts as it does today -- from the pre-trained actor.  Critics are not touched.  Every agent, any
+        hidden_sizes: two launches per update whatever the depth.  -> the per-update losses."""
         buffer = HipVectorReplayBuffer(self.policy.engine)
         buffer.reset()
         try:

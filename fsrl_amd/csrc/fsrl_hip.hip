@@ -1665,3 +1665,5 @@ extern "C" float fsrl_get_lr(const fsrl_ctx* c, int32_t group) {
 #include "kernels_bc_group.hpp"
 #include "host_bc.inc"
 #include "host_bc_group.inc"
+#include "kernels_bc_layered.hpp"
+#include "host_bc_layered.inc"

@@ -13,7 +13,8 @@
 //
 // The call is four steps that fsrl_bc_update_group (host_bc_group.inc) takes per member as well: bc_check_ctx / bc_check_call (every
 // refusal, nothing touched), bc_prepare (the working set, the indices on their way to the device), bc_member (the kernels' arguments,
-// whose optimiser), and per update bc_advance (the step count and the host's Adam scalars).
+// whose optimiser), and per update bc_advance (the step count and the host's Adam scalars).  fsrl_bc_update_layered
+// (host_bc_layered.inc) shares the checks, bc_prepare's index half (bc_prepare_idx), bc_who, bc_advance and bc_actor_old.
 struct BcState {
     Mem mem;
     int cap_rows = 0; size_t cap_idx = 0; int cap_updates = 0;
@@ -46,14 +47,22 @@ static int bc_grads_get(fsrl_ctx* c, float* flat, int64_t n, bool* served) {
 }
 
 // what is refused of a context, whatever the call asks of it
-static int bc_check_ctx(fsrl_ctx* c) {
-    CHECK_ARG(!c->lay, "fsrl_bc_update: layered contexts are not supported (two hidden layers of at most 256 units only)");
+static int bc_check_state(fsrl_ctx* c) {
     CHECK_ARG(!c->in_update, "fsrl_bc_update inside an update");
     CHECK_ARG(!c->group && !c->sac_group && !c->cvpo_group && !c->cgroup,
               "fsrl_bc_update: the context is a member of a live group (destroy the group first)");
     if (ctx_is_replay(c) && !sac_of(c)) return fail(FSRL_ESTATE, "fsrl_bc_update before fsrl_sac_init / fsrl_cvpo_init");
     if (c->cfg.algo == FSRL_ALGO_FOCOPS && !c->foc) return fail(FSRL_ESTATE, "fsrl_bc_update before fsrl_focops_init");
     return 0;
+}
+// the fused calls (solo and grouped) and the layered one each refuse the other's contexts, then share the rest
+static int bc_check_ctx(fsrl_ctx* c) {
+    CHECK_ARG(!c->lay, "fsrl_bc_update: layered contexts are not supported (two hidden layers of at most 256 units only): use fsrl_bc_update_layered");
+    return bc_check_state(c);
+}
+static int bc_check_ctx_layered(fsrl_ctx* c) {
+    CHECK_ARG(c->lay, "fsrl_bc_update_layered: the context is fused (two hidden layers of at most 256 units): use fsrl_bc_update");
+    return bc_check_state(c);
 }
 // ... and of n_updates updates of batch_size rows on it, the rows taken from `store`'s store (the context's own; a grouped call
 // with shared_store: member 0's)
@@ -75,25 +84,12 @@ static int bc_check_call(fsrl_ctx* c, const fsrl_ctx* store, int32_t batch_size,
     return 0;
 }
 
-// The working set at the call's size and the call's [n_updates][B] indices on their way to the device, on stream `st` (the context's
-// compute stream; a grouped call: member 0's).  The caller has joined `store`'s store.
-static int bc_prepare(fsrl_ctx* c, const fsrl_ctx* store, int B, int n_updates, const int64_t* indices, uint64_t seed, hipStream_t st) {
-    if (!c->bc) c->bc = new BcState();
+// The call's [n_updates][B] indices on their way to the device on stream `st`, with the per-update loss slots and a replay context's
+// gradient vector: the half of bc_prepare that the fused and the layered call share.  The caller has drained the streams.
+static int bc_prepare_idx(fsrl_ctx* c, const fsrl_ctx* store, int B, int n_updates, const int64_t* indices, uint64_t seed, hipStream_t st) {
     BcState* k = c->bc;
     SacState* s = sac_of(c);
-    const int H = c->cfg.hidden, rows_pad = round_up(B, 16), tiles = rows_pad / 16;
     const size_t n_idx = (size_t)B * n_updates;
-    // an earlier call's copies have left the pinned buffers and its kernels the side buffers: every call waits here for the context's
-    // stream to drain before it enqueues its own work (with loss_out == NULL it returns without waiting for THAT work); a grouped
-    // call leaves every member's stream behind its last launch
-    HIPCHK(hipStreamSynchronize(c->compute));
-    if (st != c->compute) HIPCHK(hipStreamSynchronize(st));
-    if (k->cap_rows < rows_pad) {
-        const size_t rh = (size_t)rows_pad * H * 4;
-        HIPCHK(k->mem.regrow(k->cap_rows, rows_pad, rows_pad,
-                             {Mem::D(&k->A1, rh), Mem::D(&k->A2, rh), Mem::D(&k->D1, rh), Mem::D(&k->D2, rh),
-                              Mem::D(&k->DO, (size_t)rows_pad * FSRL_DOW * 4), Mem::D(&k->lossp, (size_t)tiles * 4)}));
-    }
     if (s && !k->G) { HIPCHK(k->mem.dev(&k->G, (size_t)s->na_dev * 4)); HIPCHK(hipMemsetAsync(k->G, 0, (size_t)s->na_dev * 4, st)); }
     if (k->cap_idx < n_idx) HIPCHK(k->mem.regrow(k->cap_idx, n_idx, n_idx, {Mem::D(&k->d_idx, n_idx * 4), Mem::H(&k->h_idx, n_idx * 4)}));
     if (k->cap_updates < n_updates)
@@ -109,6 +105,25 @@ static int bc_prepare(fsrl_ctx* c, const fsrl_ctx* store, int B, int n_updates, 
     HIPCHK(hipMemcpyAsync(k->d_idx, k->h_idx, n_idx * 4, hipMemcpyHostToDevice, st));
     return 0;
 }
+// The working set at the call's size and the call's [n_updates][B] indices on their way to the device, on stream `st` (the context's
+// compute stream; a grouped call: member 0's).  The caller has joined `store`'s store.
+static int bc_prepare(fsrl_ctx* c, const fsrl_ctx* store, int B, int n_updates, const int64_t* indices, uint64_t seed, hipStream_t st) {
+    if (!c->bc) c->bc = new BcState();
+    BcState* k = c->bc;
+    const int H = c->cfg.hidden, rows_pad = round_up(B, 16), tiles = rows_pad / 16;
+    // an earlier call's copies have left the pinned buffers and its kernels the side buffers: every call waits here for the context's
+    // stream to drain before it enqueues its own work (with loss_out == NULL it returns without waiting for THAT work); a grouped
+    // call leaves every member's stream behind its last launch
+    HIPCHK(hipStreamSynchronize(c->compute));
+    if (st != c->compute) HIPCHK(hipStreamSynchronize(st));
+    if (k->cap_rows < rows_pad) {
+        const size_t rh = (size_t)rows_pad * H * 4;
+        HIPCHK(k->mem.regrow(k->cap_rows, rows_pad, rows_pad,
+                             {Mem::D(&k->A1, rh), Mem::D(&k->A2, rh), Mem::D(&k->D1, rh), Mem::D(&k->D2, rh),
+                              Mem::D(&k->DO, (size_t)rows_pad * FSRL_DOW * 4), Mem::D(&k->lossp, (size_t)tiles * 4)}));
+    }
+    return bc_prepare_idx(c, store, B, n_updates, indices, seed, st);
+}
 
 // A prepared context as the kernels and the step loop take it: both kernels' arguments for update 0 (idx, loss_out: the call's first
 // block and slot), the actor's parameters, the head, and whose step count and rate the updates use.
@@ -118,22 +133,29 @@ struct BcMember {
     int head, tiles, grid_w;
     int64_t* t; float lr;
 };
+// whose optimiser a BC step is (the table above) and what the loss head makes of the actor's output; G: where the step's gradient goes
+struct BcWho { float *P, *M, *V, *G; int64_t* t; float lr; int head, mean_tanh; };
+static BcWho bc_who(fsrl_ctx* c, const ModelDesc* md) {
+    SacState* s = sac_of(c);
+    BcWho w{c->P, c->M, c->V, c->G, &c->adam_t, c->cfg.lr, DC_HEAD_ONPOLICY, md->unbounded ? 0 : 1};
+    if (s) {
+        w.P = s->PA; w.M = s->MA; w.V = s->VA; w.G = c->bc->G; w.t = &s->t_actor;
+        w.lr = s->cvpo ? s->ccfg.actor_lr : s->cfg.actor_lr;
+        w.head = s->ddpg ? DC_HEAD_DDPG : DC_HEAD_GAUSS; w.mean_tanh = s->ddpg ? 1 : s->mean_tanh;
+    } else if (c->foc) {
+        w.t = &c->foc->t_actor; w.lr = c->foc->cfg.actor_lr;
+    }
+    return w;
+}
 static BcMember bc_member(fsrl_ctx* c, const fsrl_ctx* store, int B, int loss) {
     BcState* k = c->bc;
     SacState* s = sac_of(c);
     BcMember m{};
     m.md = s ? &s->mda : &c->md;
-    float *P = c->P, *M = c->M, *V = c->V, *G = c->G;
-    m.lr = c->cfg.lr; m.t = &c->adam_t;
-    m.head = DC_HEAD_ONPOLICY;
-    int mean_tanh = m.md->unbounded ? 0 : 1;
-    if (s) {
-        P = s->PA; M = s->MA; V = s->VA; G = k->G; m.t = &s->t_actor;
-        m.lr = s->cvpo ? s->ccfg.actor_lr : s->cfg.actor_lr;
-        m.head = s->ddpg ? DC_HEAD_DDPG : DC_HEAD_GAUSS; mean_tanh = s->ddpg ? 1 : s->mean_tanh;
-    } else if (c->foc) {
-        m.t = &c->foc->t_actor; m.lr = c->foc->cfg.actor_lr;
-    }
+    const BcWho who = bc_who(c, m.md);
+    float *P = who.P, *M = who.M, *V = who.V, *G = who.G;
+    m.lr = who.lr; m.t = who.t; m.head = who.head;
+    const int mean_tanh = who.mean_tanh;
     m.P = P;
     const int rows_pad = round_up(B, 16);
     m.tiles = rows_pad / 16;

@@ -131,6 +131,14 @@ class Engine:
         (indices: [n_updates, batch_size] store slots; None: the library draws them from `seed`).  loss "mse" | "nll".  Fused contexts
         of every agent; layered contexts, an empty store, an index outside the stored rows, nll on the DDPG-Lag actor and a member
         of a live group are refused (AssertionError naming the reason).  -> the per-update losses."""
+        return self._bc_update(self.lib.fsrl_bc_update, batch_size, n_updates, loss, indices, seed)
+
+    def bc_update_layered(self, batch_size, n_updates, loss="mse", indices=None, seed=0) -> np.ndarray:
+        """Engine.bc_update for a LAYERED engine (hidden_sizes of any depth and width, or force_layered): fsrl_bc_update_layered, the
+        same arguments and result, two launches per update at any depth.  A fused engine is refused ("use fsrl_bc_update")."""
+        return self._bc_update(self.lib.fsrl_bc_update_layered, batch_size, n_updates, loss, indices, seed)
+
+    def _bc_update(self, fn, batch_size, n_updates, loss, indices, seed):
         code = {"mse": 0, "nll": 1}.get(loss)
         if code is None:
             raise ValueError(f"loss must be 'mse' or 'nll', got {loss!r}")
@@ -138,8 +146,7 @@ class Engine:
         if idx is not None and idx.size != int(batch_size) * int(n_updates):
             raise ValueError(f"indices must hold n_updates * batch_size = {int(batch_size) * int(n_updates)} slots, got {idx.size}")
         out = np.empty(max(int(n_updates), 1), np.float32)
-        _lib.check(self.lib.fsrl_bc_update(self._ctx, int(batch_size), int(n_updates), code, _ptr(idx, _i64p), int(seed),
-                                           _ptr(out, _f32p)))
+        _lib.check(fn(self._ctx, int(batch_size), int(n_updates), code, _ptr(idx, _i64p), int(seed), _ptr(out, _f32p)))
         self._bc_ran = True
         return out[:int(n_updates)]
 

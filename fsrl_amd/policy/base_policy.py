@@ -148,13 +148,16 @@ class BasePolicy(ABC, nn.Module):
                 off += n
 
     def pretrain(self, buffer, batch_size: int = 256, n_updates: int = 1000, loss: str = "mse", seed: int = 0) -> np.ndarray:
-        """Behaviour cloning on the device (Engine.bc_update): regress the actor onto the actions stored in `buffer`, the agent's
+        """Behaviour cloning on the device (Engine.bc_update; a layered engine -- any hidden_sizes -- Engine.bc_update_layered, routed
+        as the device collectors route): regress the actor onto the actions stored in `buffer`, the agent's
         HIP buffer (already filled or poured from a dataset), for n_updates Adam steps of batch_size rows.  The critics are not
         touched.  The host mirror of the actor is synced afterwards, so state_dict() and the host-actor collectors agree with the
         device.  The replay policies' critic and target mirrors (DDPG-Lag / CVPO: actor_old, which the device set equal to the actor)
         stay flagged and are pulled when they are next needed -- forward(model="actor_old"), state_dict().  -> the per-update losses."""
         assert getattr(buffer, "engine", self.engine) is self.engine, "pretrain() takes the buffer of this policy's engine"
-        losses = self.engine.bc_update(batch_size, n_updates, loss=loss, seed=seed)
+        from fsrl_amd.data.device_collector import _layered
+        step = self.engine.bc_update_layered if _layered(self.engine) else self.engine.bc_update
+        losses = step(batch_size, n_updates, loss=loss, seed=seed)
         self._mark_stale()
         self._pull_params()
         return losses

@@ -1036,6 +1036,16 @@ int fsrl_bc_update(fsrl_ctx* ctx, int32_t batch_size, int32_t n_updates, int32_t
  *      member's compute stream holds; every active member's stream is ordered behind the call's last launch. */
 int fsrl_bc_update_group(fsrl_ctx** ctxs, int32_t k, const int32_t* batch_size, const int32_t* n_updates, const int32_t* loss,
                          const int64_t* indices, const uint64_t* seeds, int32_t shared_store, float* loss_out);
+/*      fsrl_bc_update for LAYERED contexts of all seven agents (hidden_sizes of any depth and width, or force_layered;
+ *      kernels_bc_layered.hpp, host_bc_layered.inc): the same arguments, index draw, losses, loss_out, optimiser table, gradient
+ *      read-back, actor_old and return codes, still two launches per update at any depth -- bc_lay_fwd_bwd_kernel (a 16-row tile per
+ *      workgroup: the layers forward, the loss head, the layers backward, weights streamed from L2 one unit ahead) and
+ *      bc_lay_wgrad_kernel (every layer's weight-gradient tiles with their Adam step in one launch).  The working set is the actor's
+ *      own layered one, grown to round_up(batch_size, 16) rows.  Refused before anything is touched: a fused context ("use
+ *      fsrl_bc_update"), and everything fsrl_bc_update refuses.  Grouped layered behaviour cloning does not exist: fsrl_bc_update and
+ *      fsrl_bc_update_group keep refusing layered contexts. */
+int fsrl_bc_update_layered(fsrl_ctx* ctx, int32_t batch_size, int32_t n_updates, int32_t loss, const int64_t* indices, uint64_t seed,
+                           float* loss_out);
 
 /* ---- Device environments: envs written as device functions, and whole collects on the GPU for on-policy and replay contexts.
  *      (fsrl_amd/csrc/device_env.hpp, kernels_devcollect.hpp, host_devcollect.inc, host_devcollect_group.inc; INTEGRATION.md "Device environments")

@@ -8,6 +8,9 @@ within a round: `grouped` (one bc_update_group call, each member GROUP_UPDATES u
 bc_update calls one after the other) and `threads` (k threads, a solo call each).  --ab-tree PATH adds `solo_ab`: the solo update of
 this tree and of the built checkout of another commit at PATH (its package and library), a fresh process per window, the two alternating.
     python tools/bench_bc.py --ks 1,2,4,8 [--ab-tree /path/to/built/checkout] --out profiles/bc_update_group.json
+--hidden 64x48x32,256x256x256,1024x1024: these hidden_sizes instead (obs 33 / act 8, batch 256), each through the call its shape routes to
+(a layered shape: fsrl_bc_update_layered, windows of UPDATES updates) next to the same stock-torch loop over a network of that depth.
+    python tools/bench_bc.py --hidden 64x48x32,256x256x256,1024x1024 --out profiles/bc_update_layered.json
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.environ.get("FSRL_BENCH_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # --ab-tree's children
 from fsrl_amd.engine import Engine, EngineConfig
+from fsrl_amd.data.device_collector import _layered
 
 SHAPES = [((256, 256), 33, 8, 256), ((256, 256), 33, 8, 1024), ((64, 64), 6, 2, 256)]
 ROWS, UPDATES, HIP_UPDATES, ROUNDS = 4096, 2000, 10000, 7
@@ -35,13 +39,16 @@ def hip_window(hidden, Do, Da, B, rng):
     for _ in range(ROWS // 16):
         o = rng.standard_normal((16, Do)).astype(np.float32)
         eng.push(ids, o, np.tanh(rng.standard_normal((16, Da))).astype(np.float32), z, z, f, f, o)
+    if _layered(eng):
+        return eng, lambda n=UPDATES: eng.bc_update_layered(B, n, loss="mse", seed=1)
     return eng, lambda n=HIP_UPDATES: eng.bc_update(B, n, loss="mse", seed=1)      # returns the losses: synchronises
 
 
 def torch_window(hidden, Do, Da, B, rng):
     dev = torch.device("cuda:0")
-    net = torch.nn.Sequential(torch.nn.Linear(Do, hidden[0]), torch.nn.ReLU(), torch.nn.Linear(hidden[0], hidden[1]), torch.nn.ReLU(),
-                              torch.nn.Linear(hidden[1], Da), torch.nn.Tanh()).to(dev)
+    widths = [Do, *hidden]
+    body = [m for i, o in zip(widths, widths[1:]) for m in (torch.nn.Linear(i, o), torch.nn.ReLU())]
+    net = torch.nn.Sequential(*body, torch.nn.Linear(widths[-1], Da), torch.nn.Tanh()).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=5e-4)
     obs = torch.tensor(rng.standard_normal((ROWS, Do)), dtype=torch.float32, device=dev)
     act = torch.tanh(torch.tensor(rng.standard_normal((ROWS, Da)), dtype=torch.float32, device=dev))
@@ -125,6 +132,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ks", default=None, type=lambda t: [int(v) for v in t.split(",")], help="group sizes, e.g. 1,2,4,8: measure fsrl_bc_update_group")
     ap.add_argument("--ab-tree", default=None, help="with --ks: a built checkout of another commit, its solo update alternated with this tree's")
+    ap.add_argument("--hidden", default=None, type=lambda t: [tuple(int(w) for w in h.split("x")) for h in t.split(",")],
+                    help="hidden_sizes tuples, e.g. 64x48x32,256x256x256,1024x1024 (obs 33 / act 8, batch 256); layered ones run fsrl_bc_update_layered")
     ap.add_argument("--solo-window", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_bc.py needs a GPU"
@@ -140,16 +149,17 @@ def main():
                 json.dump(doc, f, indent=1)
         return
     results = []
-    for hidden, Do, Da, B in SHAPES:
+    for hidden, Do, Da, B in ([(h, 33, 8, 256) for h in a.hidden] if a.hidden else SHAPES):
         rng = np.random.default_rng(0)
         (eng, hip), (_, ref) = hip_window(hidden, Do, Da, B, rng), torch_window(hidden, Do, Da, B, rng)
         hip(); ref()
         us = {"hip": [], "torch": []}
+        n_hip = UPDATES if _layered(eng) else HIP_UPDATES
         for _ in range(ROUNDS):
-            for name, fn, n in (("hip", hip, HIP_UPDATES), ("torch", ref, UPDATES)):
+            for name, fn, n in (("hip", hip, n_hip), ("torch", ref, UPDATES)):
                 t0 = time.perf_counter(); fn(); us[name].append((time.perf_counter() - t0) * 1e6 / n)
         eng.close()
-        row = {"hidden": list(hidden), "obs_dim": Do, "act_dim": Da, "batch": B, "updates_per_window": {"hip": HIP_UPDATES, "torch": UPDATES}, "rounds": ROUNDS}
+        row = {"hidden": list(hidden), "obs_dim": Do, "act_dim": Da, "batch": B, "updates_per_window": {"hip": n_hip, "torch": UPDATES}, "rounds": ROUNDS}
         for name, v in us.items():
             spread(row, name, v)
         results.append(row)
